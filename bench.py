@@ -1,13 +1,17 @@
 #!/usr/bin/env python3
 """Benchmark of the MI355X path-tracing core on BASELINE.json's metric (Mrays/s at 1920x1080, 8 bounces).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   N > 1 without a torchrun environment: bench.py starts `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr
   127.0.0.1 --master-port P bench.py ...` as a CHILD (before anything touches the GPU) and exits with its code.
 
-Headline workload = the scene the north-star target is quoted on: the 1 M-triangle Sponza-class hall (BASELINE config 3). At N = 1 the
-Example-class scene (config 2) and the 10 M-triangle scan (config 5's scene) are timed after it and reported under "secondary" in the
-same JSON line (`--secondary none` skips them).
+Headline workload = the scene the north-star target is quoted on: the 1 M-triangle Sponza-class hall (BASELINE config 3). A plain run does
+only what the headline needs: it builds and uploads that scene, runs W untimed and K timed steps, writes the frame moments the timed steps
+accumulated as DIR/<name>.npy if --dump-outputs is given, and prints the result line.
+--full adds everything else, after the timed steps: at N = 1 the Example-class scene (config 2) and the 10 M-triangle scan (config 5's
+scene) are timed and reported under "secondary" in the same JSON line (`--secondary none` skips them), the headline workload is timed
+once more in the bit-exact flavour (value_exact), the output chain is timed, the oracle gives the CPU baseline, and the full record is
+written to bench_out/bench_detail.json.
 
 Step   = one wavefront pass per GPU: every rank takes its pixels of the 1920x1080 frame through all 9 depth passes (8 bounces) for
          --samples-per-pass (default 64) x N sample ids, i.e. 1920*1080*64 = 133 M paths (66 GB of queues, under a quarter of the 288 GB) per GPU and
@@ -19,8 +23,8 @@ N > 1  = the frame is cut into 32x32 tiles dealt to the ranks by a lattice - til
          rendering); each rank accumulates its own pixels and ONE RCCL collective at the end assembles the frame moments on rank 0: a gather of
          the ranks' own tiles behind the C ABI (lumc_frame_gather; --reduce cabi-reduce: the reduce of zero-padded full frames it replaced).
 Prints ONE JSON line on rank 0, as the LAST line of stdout, at most 4 KB (`headline`): the contract's fields, the dominant kernel's roofline, the three
-big kernels in brief, value_exact (the bit-exact flavour on the same scene), the CPU baseline, the secondaries' values. Everything else - prose, ceilings,
-L2 figures, per-ray counts, the secondaries' own blocks - goes to profiles/bench_detail.json (written by the same run) and to stderr.
+big kernels in brief and, with --full, value_exact (the bit-exact flavour on the same scene), the CPU baseline, the secondaries' values. Everything
+else - prose, ceilings, L2 figures, per-ray counts, the secondaries' own blocks - goes to stderr and, with --full, to bench_out/bench_detail.json.
 
 roofline: the block of the kernel that took most of the timed region, chosen over ALL kernels; the three big kernels are also
 reported by name (roofline_trace, roofline_shadow, roofline_shade). For a ray kernel
@@ -63,6 +67,8 @@ NODE_BYTES, TRI_BYTES = 112, 48  # one node visit fetches 7 x 16 B of a 128-B BV
 IO_TRACE_BYTES = 24 + 4 + 12  # origin+dir, tmax, hit
 IO_SHADOW_BYTES = 24 + 4 + 12  # origin+dir, tmax, RGB visibility
 PMC_FILE = os.path.join(ROOT, "profiles", "pmc_counters.json")
+DETAIL_FILE = "bench_out/bench_detail.json"  # --full's record, relative to ROOT (ignored by git: profiles/ holds the committed records)
+DUMP_LIMIT_BYTES = 64_000_000  # --dump-outputs writes at most this much; a larger frame is sampled
 
 from luminary_amd.distributed import assemble_frame, tile_lattice_step, tile_pixels  # noqa: E402  (numpy only at import time)
 
@@ -186,6 +192,29 @@ def cpu_baseline(view, budget_s):
                       "%.0f rays in %.1f s (its %.1f s BVH build excluded)" % (cores, npx, spp, rays, dt, t_build)}
 
 
+def dump_outputs(out_dir, fm, sm, pixels, width, height):
+    """--dump-outputs: what the timed steps handed their caller, the frame moments after the last step, as float32 in frame order:
+    first_moment [3, H, W] (per-channel radiance sums) and second_moment [H, W]. A frame above DUMP_LIMIT_BYTES is written as a fixed,
+    seeded sample of pixels instead: first_moment [3, n], second_moment [n] and the frame indices of those pixels (sample_pixels, float64)."""
+    n = width * height
+    fm = fm.view(3, -1).cpu().numpy()
+    sm = sm.cpu().numpy()
+    if pixels is not None:  # the paths' pixel order (--pixel-tile) back to frame order
+        order = np.asarray(pixels, dtype=np.int64)
+        f, s = np.zeros((3, n), np.float32), np.zeros(n, np.float32)
+        f[:, order], s[order] = fm, sm
+        fm, sm = f, s
+    header = 4096  # room for the .npy headers
+    if 16 * n + header <= DUMP_LIMIT_BYTES:
+        arrays = {"first_moment": fm.reshape(3, height, width), "second_moment": sm.reshape(height, width)}
+    else:
+        idx = np.sort(np.random.default_rng(0).choice(n, (DUMP_LIMIT_BYTES - header) // 24, replace=False))
+        arrays = {"first_moment": fm[:, idx], "second_moment": sm[idx], "sample_pixels": idx.astype(np.float64)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+
+
 def spawn_distributed(n):
     """`bench.py --gpus N` outside a torchrun environment: run the N-rank job as a child process and return its exit code. Nothing in
     this process has touched the GPU yet (no torch.cuda call, no HIP library loaded)."""
@@ -199,9 +228,9 @@ def spawn_distributed(n):
     return subprocess.call(cmd, env=env)
 
 
-def run_workload(core, name, args, rank, world, dist, steps, warmup, want_output_chain, exact_steps=0):
-    """Uploads workload `name`, times `steps` passes after `warmup` untimed ones (barrier + synchronize on both sides, max over ranks) and
-    returns (json dict, device scene view)."""
+def run_workload(core, name, args, rank, world, dist, steps, warmup, want_output_chain, exact_steps=0, dump_dir=None):
+    """Uploads workload `name`, times `steps` passes after `warmup` untimed ones (barrier + synchronize on both sides, max over ranks), writes
+    the frame moments of the last timed step to `dump_dir` (one process only) and returns (json dict, device scene view)."""
     import torch
     from luminary_amd.core import CNT_AMBIENT_DEFERRED, CNT_AMBIENT_FALLBACK, CNT_LIGHT_BVH, CNT_NODES, CNT_SHADOW, CNT_TRACE, CNT_TRIS, CNT_VERTICES
     t_build = time.time()
@@ -293,6 +322,8 @@ def run_workload(core, name, args, rank, world, dist, steps, warmup, want_output
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.time() - t0
+    if dump_dir is not None:  # before anything below renders into the same accumulators
+        dump_outputs(dump_dir, fm, sm, pixels, view.width, view.height)
 
     cnt = core.counters()
     times = core.kernel_times()
@@ -457,14 +488,18 @@ def main():
     ap.add_argument("--steps", type=int, default=8)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--workload", default="hall", choices=sorted(WORKLOADS))
-    ap.add_argument("--secondary", default="example,scan", help="workloads timed after the headline at N = 1 and reported under 'secondary' ('none' skips them)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what the headline does not need: secondaries, value_exact, output chain, CPU baseline, and write " + DETAIL_FILE)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the frame moments the timed steps accumulated to DIR/<name>.npy (float32, at most 64 MB; one process only)")
+    ap.add_argument("--secondary", default="example,scan", help="--full: workloads timed after the headline at N = 1 and reported under 'secondary' ('none' skips them)")
     ap.add_argument("--secondary-steps", type=int, default=4)
-    ap.add_argument("--exact-steps", type=int, default=4, help="N = 1: steps of the headline workload timed once more in the bit-exact flavour (value_exact; 0 or --secondary none skip it)")
+    ap.add_argument("--exact-steps", type=int, default=4, help="--full, N = 1: steps of the headline workload timed once more in the bit-exact flavour (value_exact; 0 or --secondary none skip it)")
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--bounces", type=int, default=8)
     ap.add_argument("--samples-per-pass", type=int, default=64, help="sample ids per wavefront pass = per step")
-    ap.add_argument("--cpu-budget", type=float, default=20.0, help="seconds of CPU baseline work (0 = skip)")
+    ap.add_argument("--cpu-budget", type=float, default=20.0, help="--full: seconds of CPU baseline work (0 = skip)")
     ap.add_argument("--flavour", default=None, choices=["fast", "exact"], help="arithmetic flavour of the device code (default: the library's, fast)")
     ap.add_argument("--reduce", default="cabi", choices=["cabi", "cabi-reduce", "torch"],
                     help="N > 1: who assembles the frame on rank 0 - the library behind the C ABI with one ncclGather of the ranks' own tiles (lumc_frame_gather, default) or "
@@ -479,6 +514,10 @@ def main():
     ap.add_argument("--sky", default="constant", choices=["constant", "procedural"],
                     help="constant = the benchmark settings (SURVEY §8d); procedural = sky mode DEFAULT: ray-marched atmosphere and sun sampling")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs is not None and (args.gpus > 1 or "WORLD_SIZE" in os.environ):
+        ap.error("--dump-outputs needs one process (--gpus 1, no torchrun)")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -525,12 +564,13 @@ def main():
             dist.destroy_process_group()
             raise SystemExit("bench.py: the library's communicator reports %d ranks, the job has %d" % (core.comm_count(), world))
     # value_exact belongs to the full report, like the secondaries: `--secondary none` (profiling passes, A/B tools) times the headline flavour alone
-    head, view = run_workload(core, args.workload, args, rank, world, dist, args.steps, args.warmup, True, exact_steps=args.exact_steps if args.secondary != "none" else 0)
+    head, view = run_workload(core, args.workload, args, rank, world, dist, args.steps, args.warmup, args.full,
+                              exact_steps=args.exact_steps if (args.full and args.secondary != "none") else 0, dump_dir=args.dump_outputs)
     exact = head.pop("value_exact", None)
     # reported at N=1 only; the oracle needs the sky tables for the procedural sky, which the bench does not generate on the CPU
-    cpu = cpu_baseline(view, args.cpu_budget) if (args.cpu_budget > 0 and dist is None and args.sky == "constant" and rank == 0) else None
+    cpu = cpu_baseline(view, args.cpu_budget) if (args.full and args.cpu_budget > 0 and dist is None and args.sky == "constant" and rank == 0) else None
     secondary = {}
-    if dist is None and args.secondary != "none":
+    if args.full and dist is None and args.secondary != "none":
         for name in [s for s in args.secondary.split(",") if s and s != args.workload]:
             sec, _ = run_workload(core, name, args, rank, world, None, args.secondary_steps, 1, False)
             sec.pop("value_exact", None)
@@ -555,14 +595,17 @@ def main():
               "ms_per_step": head["ms_per_step"], "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
               "config": head["config"], "roofline": head["roofline"], "roofline_trace": head["roofline_trace"], "roofline_shadow": head["roofline_shadow"],
               "roofline_shade": head["roofline_shade"], "value_exact": exact, "cpu_baseline": cpu, "secondary": secondary or None}
-    # Everything goes to the sidecar (and to stderr); stdout's LAST line is the headline alone, a few KB: the driver keeps the tail of stdout only.
-    detail_path = os.path.join(ROOT, "profiles", "bench_detail.json")
-    try:
-        with open(detail_path, "w") as f:
-            json.dump(detail, f, indent=1)
-            f.write("\n")
-    except OSError as e:
-        sys.stderr.write("bench.py: could not write %s (%s)\n" % (detail_path, e))
+    # Everything goes to stderr (and with --full to the sidecar); stdout's LAST line is the headline alone, a few KB: the driver keeps the tail of stdout only.
+    if args.full:
+        detail_path = os.path.join(ROOT, DETAIL_FILE)
+        try:
+            os.makedirs(os.path.dirname(detail_path), exist_ok=True)
+            with open(detail_path, "w") as f:
+                json.dump(detail, f, indent=1)
+                f.write("\n")
+            detail["detail"] = DETAIL_FILE
+        except OSError as e:
+            sys.stderr.write("bench.py: could not write %s (%s)\n" % (detail_path, e))
     sys.stderr.write("bench detail: " + json.dumps(detail) + "\n")
     sys.stderr.flush()
     line = json.dumps(headline(detail))
@@ -583,7 +626,7 @@ def _r(x, digits=5):
 
 def headline(d):
     """The one JSON line the driver parses: the contract's fields, the dominant kernel's roofline in full, the three big kernels in brief, the CPU
-    baseline, the secondaries' values. Prose, ceilings, L2 figures, per-ray counts and the secondaries' blocks live in profiles/bench_detail.json."""
+    baseline, the secondaries' values. Prose, ceilings, L2 figures, per-ray counts and the secondaries' blocks live in the record `detail` names (--full)."""
     c = d["config"]
     cfg_keys = ["workload", "width", "height", "max_ray_depth", "flavour", "lds_stack_bytes", "spp_per_step", "paths_per_gpu_per_step", "partition", "frame_reduce", "rccl_ranks",
                 "samples_per_s", "seconds_to_1024spp", "rays", "rays_answered_without_trace", "mrays_per_s_answered", "ambient_reuse", "value_note", "bvh", "source_hash",
@@ -612,7 +655,8 @@ def headline(d):
         h["cpu_baseline"] = {"value": b["value"], "unit": b["unit"], "cores": b["cores"], "kind": b["kind"], "cpu": b.get("cpu"), "sample": b.get("sample_short", b.get("sample", ""))[:160]}
     if d.get("secondary"):
         h["secondary"] = {n: {"value": s["value"], "ms_per_step": s["ms_per_step"], "steps": s["steps"], "samples_per_s": s["config"].get("samples_per_s")} for n, s in d["secondary"].items()}
-    h["detail"] = "profiles/bench_detail.json"
+    if d.get("detail"):
+        h["detail"] = d["detail"]
 
     def rnd(o):
         if isinstance(o, dict):

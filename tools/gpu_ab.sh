@@ -5,6 +5,6 @@ for flags in "$@"; do
   LUM_CXXFLAGS="$flags" python -m luminary_amd.build --force > /dev/null 2>&1 || { echo "[$flags] build failed"; continue; }
   for w in ${WORKLOADS:-hall scan}; do
     echo -n "[$flags] $w $BENCH_ARGS: "
-    LUM_CXXFLAGS="$flags" python bench.py --steps 3 --warmup 1 --cpu-budget 0 --secondary none --workload $w $BENCH_ARGS 2>/dev/null | python tools/ab_line.py
+    LUM_CXXFLAGS="$flags" python bench.py --full --steps 3 --warmup 1 --cpu-budget 0 --secondary none --workload $w $BENCH_ARGS 2>/dev/null | python tools/ab_line.py
   done
 done

@@ -9,7 +9,7 @@ for flags in "-DLUM_BVH4Q=0" "-DLUM_BVH4Q=1"; do
   LUM_CXXFLAGS="$flags" python -m luminary_amd.build --force > /dev/null 2>&1 || { echo "[$flags] build failed"; continue; }
   for w in hall scan example; do
     echo -n "[$flags] $w: "
-    LUM_CXXFLAGS="$flags" python bench.py --steps 3 --warmup 1 --cpu-budget 0 --secondary none --workload $w 2>/dev/null | python tools/ab_line.py
+    LUM_CXXFLAGS="$flags" python bench.py --full --steps 3 --warmup 1 --cpu-budget 0 --secondary none --workload $w 2>/dev/null | python tools/ab_line.py
   done
 done
 done

@@ -2,6 +2,6 @@
 for e in "$@"; do
   for w in ${WORKLOADS:-hall}; do
     echo -n "[$e] $w $BENCH_ARGS: "
-    env $e python bench.py --steps 3 --warmup 1 --cpu-budget 0 --secondary none --workload $w $BENCH_ARGS 2>/dev/null | python tools/ab_line.py
+    env $e python bench.py --full --steps 3 --warmup 1 --cpu-budget 0 --secondary none --workload $w $BENCH_ARGS 2>/dev/null | python tools/ab_line.py
   done
 done

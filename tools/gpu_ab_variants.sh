@@ -9,6 +9,6 @@ for v in "$@"; do
   [ -f $lib ] || { echo "[$v] no library" | tee -a $out; continue; }
   for w in ${WORKLOADS:-hall scan}; do
     echo -n "[$v] $w $BENCH_ARGS: " | tee -a $out
-    LUM_LIB=$lib timeout 600 python bench.py --steps 3 --warmup 1 --cpu-budget 0 --secondary none --workload $w $BENCH_ARGS 2>/dev/null | python tools/ab_line.py | tee -a $out
+    LUM_LIB=$lib timeout 600 python bench.py --full --steps 3 --warmup 1 --cpu-budget 0 --secondary none --workload $w $BENCH_ARGS 2>/dev/null | python tools/ab_line.py | tee -a $out
   done
 done

@@ -18,7 +18,9 @@
  * sun and sky light through the surface with caustics), clouds (three ray-marched layers over generated noise textures, procedural sky
  * mode, baked into the panorama in HDRI mode; their shadow in the aerial perspective), textures, adaptive sampling, the undersampling preview, the display chain with bloom,
  * and the debug shading modes. Rendering runs on the library's own "Device" thread once luminary_host_start_new_render was called,
- * like the reference's. The physical camera is stored and returned unchanged but does not influence the image yet.
+ * like the reference's. The physical camera (use_physical_camera) traces the camera rays through a lens of spherical interfaces, the
+ * reference's double-Gauss prescription unless luminary_ext_set_camera_lens gives another; its spectral rendering
+ * (physical.use_spectral_rendering) is out of scope and refused.
  *
  * Additive extension (the reference only returns tone-mapped ARGB8): the luminary_ext_* functions at the
  * end give access to float radiance, ray counters and batch rendering. Existing symbols are untouched.
@@ -378,8 +380,25 @@ LUMINARY_API LuminaryResult luminary_ext_get_mesh(LuminaryHost* host, uint32_t m
 /* Converts the current scene to the device format (device_structs.c conversions + light tree build). The view and everything it points
  * to stay valid until the next call or host destruction. Needs no GPU. */
 /* Whether replacing `old` by `input` restarts the integration (camera.c:80-147, settings.c:45-72) or only changes the outputs.
- * entity 0: LuminaryRendererSettings, 1: LuminaryCamera. luminary_host_set_camera / set_settings apply this rule. */
+ * entity 0: LuminaryRendererSettings, 1: LuminaryCamera, 2: LuminaryCameraLens (any change restarts; luminary_ext_set_camera_lens applies it
+ * while the camera is physical). luminary_host_set_camera / set_settings apply this rule. */
 LUMINARY_API LuminaryResult luminary_ext_change_restarts_integration(int entity, const void* input, const void* old, bool* restarts);
+/* The physical camera's lens (the camera "given through the API" that device_physical_camera.c:17-54 leaves as a TODO): interface i is a sphere
+ * of `radius` (signed: centre at vertex - radius) whose vertex lies at `vertex` on the optical axis, cut off at `cylindrical_radius`; medium i
+ * lies in front of interface i (num_interfaces + 1 media; cylindrical_radius FLT_MAX in air). Lengths in mm, the sensor side first. `abbe` is
+ * kept for spectral rendering, which is out of scope. Default: the reference's 12-interface double-Gauss lens scaled to 50.53 mm focal length.
+ * Rejected (LUMINARY_ERROR_INVALID_API_ARGUMENT): 0 or more than LUMINARY_CAMERA_LENS_MAX_INTERFACES interfaces, non-finite values, an index of
+ * refraction <= 0. A new lens restarts the integration while use_physical_camera is set. */
+#define LUMINARY_CAMERA_LENS_MAX_INTERFACES 24
+typedef struct LuminaryCameraLensInterface { float radius, vertex, cylindrical_radius; } LuminaryCameraLensInterface;
+typedef struct LuminaryCameraLensMedium { float design_ior, abbe, cylindrical_radius; } LuminaryCameraLensMedium;
+typedef struct LuminaryCameraLens {
+  uint32_t num_interfaces;
+  LuminaryCameraLensInterface interfaces[LUMINARY_CAMERA_LENS_MAX_INTERFACES];
+  LuminaryCameraLensMedium media[LUMINARY_CAMERA_LENS_MAX_INTERFACES + 1];
+} LuminaryCameraLens;
+LUMINARY_API LuminaryResult luminary_ext_set_camera_lens(LuminaryHost* host, const LuminaryCameraLens* lens);
+LUMINARY_API LuminaryResult luminary_ext_get_camera_lens(LuminaryHost* host, LuminaryCameraLens* lens);
 /* The path of a file named inside `base_file` (mesh files of a .lum, material libraries of an .obj, maps of an .mtl): path_extend +
  * path_apply of src/luminary/path.c */
 LUMINARY_API LuminaryResult luminary_ext_path_extend(const char* base_file, const char* name, char* out, size_t out_size);

@@ -68,6 +68,22 @@ class Camera(C.Structure):
                 ("thin_lens", _ThinLens), ("physical", _Physical)]
 
 
+LENS_MAX_INTERFACES = 24  # LUMINARY_CAMERA_LENS_MAX_INTERFACES
+
+
+class LensInterface(C.Structure):
+    _fields_ = [("radius", C.c_float), ("vertex", C.c_float), ("cylindrical_radius", C.c_float)]
+
+
+class LensMedium(C.Structure):
+    _fields_ = [("design_ior", C.c_float), ("abbe", C.c_float), ("cylindrical_radius", C.c_float)]
+
+
+class CameraLens(C.Structure):
+    """include/luminary_amd.h LuminaryCameraLens: the physical camera's interfaces (sensor side first) and the num_interfaces + 1 media around them."""
+    _fields_ = [("num_interfaces", C.c_uint32), ("interfaces", LensInterface * LENS_MAX_INTERFACES), ("media", LensMedium * (LENS_MAX_INTERFACES + 1))]
+
+
 class Sky(C.Structure):
     _fields_ = [("geometry_offset", Vec3)] + [(n, C.c_float) for n in ("azimuth", "altitude", "moon_azimuth", "moon_altitude", "moon_tex_offset",
                                                                        "sun_strength", "base_density")] + \
@@ -273,6 +289,16 @@ class Host:
 
     def set_camera(self, c):
         _call("luminary_host_set_camera", self._h, C.byref(c))
+
+    def get_camera_lens(self):
+        """luminary_ext_get_camera_lens: the physical camera's lens (default: the reference's double-Gauss prescription)"""
+        lens = CameraLens()
+        _call("luminary_ext_get_camera_lens", self._h, C.byref(lens))
+        return lens
+
+    def set_camera_lens(self, lens):
+        """luminary_ext_set_camera_lens: restarts the integration while the camera is physical"""
+        _call("luminary_ext_set_camera_lens", self._h, C.byref(lens))
 
     def get_sky(self):
         return self._get("sky", Sky)

@@ -57,6 +57,25 @@ class AdaptiveInfo(C.Structure):
                 ("tasks_per_execution", C.c_uint32), ("variance_total", C.c_float), ("build_pending", C.c_uint32)]
 
 
+LENS_MAX_INTERFACES = 24  # LUMC_LENS_MAX_INTERFACES
+
+
+class LensInterface(C.Structure):
+    _fields_ = [("radius", C.c_float), ("vertex", C.c_float), ("cylindrical_radius", C.c_float)]
+
+
+class LensMedium(C.Structure):
+    _fields_ = [("design_ior", C.c_float), ("abbe", C.c_float), ("cylindrical_radius", C.c_float)]
+
+
+class PhysicalCamera(C.Structure):
+    """include/lum_core.h LumPhysicalCamera: the converted physical camera (radii, mm) and its lens."""
+    _fields_ = [(n, C.c_float) for n in ("aperture_point", "aperture_radius", "exit_pupil_point", "exit_pupil_radius", "image_plane_distance",
+                                          "sensor_width")] + \
+               [("allow_reflections", C.c_uint32), ("num_interfaces", C.c_uint32), ("interfaces", LensInterface * LENS_MAX_INTERFACES),
+                ("media", LensMedium * (LENS_MAX_INTERFACES + 1))]
+
+
 class Core:
     def __init__(self, device=0):
         self._lib = _lib()
@@ -156,6 +175,28 @@ class Core:
         fn = self._lib.lumc_get_ambient_reuse
         fn.restype = C.c_int
         return bool(fn(self._ctx))
+
+    def set_physical_camera(self, camera):
+        """lumc_set_physical_camera: a PhysicalCamera, or None for the scene's thin lens"""
+        self._call("lumc_set_physical_camera", C.byref(camera) if camera is not None else C.c_void_p(0))
+
+    def camera_rays(self, pixels, first_sample, samples):
+        """lumc_camera_rays: every camera ray of the sample ids x pixels, sample-major: origins [N, 3], directions [N, 3], weights [N] (0: invalid)"""
+        px = np.ascontiguousarray(pixels, dtype=np.uint32)
+        n = px.size * samples
+        o = np.zeros((n, 3), dtype=np.float32)
+        d = np.zeros((n, 3), dtype=np.float32)
+        w = np.zeros(n, dtype=np.float32)
+        self._call("lumc_camera_rays", px.ctypes.data_as(C.c_void_p), C.c_uint32(px.size), C.c_uint32(first_sample), C.c_uint32(samples),
+                   o.ctypes.data_as(C.c_void_p), d.ctypes.data_as(C.c_void_p), w.ctypes.data_as(C.c_void_p))
+        return o, d, w
+
+    def pixel_query(self, x, y, sample_id=0):
+        """lumc_pixel_query: (instance id, triangle id, t, direction [3])"""
+        out = (C.c_uint32 * 6)()
+        self._call("lumc_pixel_query", C.c_uint32(x), C.c_uint32(y), C.c_uint32(sample_id), out)
+        a = np.array(list(out), dtype=np.uint32)
+        return int(a[0]), int(a[1]), float(a[2:3].view(np.float32)[0]), a[3:6].view(np.float32).copy()
 
     def set_flavour(self, name):
         self._call("lumc_set_flavour", C.c_int({"exact": 0, "fast": 1}[name]))

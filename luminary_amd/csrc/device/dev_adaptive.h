@@ -138,9 +138,11 @@ __global__ __launch_bounds__(256) void k_adaptive_uniform_tasks(const uint8_t* _
 // (block_task_end * executions).
 // (struct AdaptivePass: dev_scene.h)
 
-__global__ __launch_bounds__(256) void k_generate_adaptive(DeviceScene sc, AdaptiveView a, AdaptivePass pass, PathQueue q, float4* results, uint32_t* count) {
-  const uint32_t lane = threadIdx.x & 63u;
-  const unsigned long long below = (1ull << lane) - 1ull;
+template <int kCam>
+__global__ __launch_bounds__(256) void k_generate_adaptive(DeviceScene sc, AdaptiveView a, AdaptivePass pass, PathQueue q, float4* results, uint32_t* count,
+                                                          DeviceLens lens_arg) {
+  __shared__ DeviceLens lds_lens;
+  const DeviceLens& lens = stage_lens<kCam>(lens_arg, &lds_lens);
   const uint32_t pass_tasks = pass.task_end - pass.task_begin;
   const uint32_t rounds = (pass_tasks + gridDim.x * 256u - 1u) / (gridDim.x * 256u);
   for (uint32_t round = 0; round < rounds; round++) {
@@ -168,23 +170,7 @@ __global__ __launch_bounds__(256) void k_generate_adaptive(DeviceScene sc, Adapt
       valid = x < sc.width && y < sc.height && sample_id < kMaxGlobalSamples;
       results[slot] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     }
-    const unsigned long long ballot = __ballot(valid);
-    if (ballot) {
-      uint32_t base = 0;
-      if (lane == (uint32_t) __builtin_ctzll(ballot)) base = atomicAdd(count, (uint32_t) __popcll(ballot));
-      base = __shfl(base, __builtin_ctzll(ballot));
-      if (valid) {
-        const uint32_t i = base + (uint32_t) __popcll(ballot & below);
-        const Sampler smp{sc.bluenoise_2d, x, y, sample_id, 0};
-        V3 o, d;
-        camera_ray(sc, smp, o, d);
-        const U2 rec = record_pack(splat(1.0f));
-        q.origin_t[i] = make_float4(o.x, o.y, o.z, kFltMax);
-        q.dir_slot[i] = make_float4(d.x, d.y, d.z, bitsf(slot));
-        q.aux[i]      = make_uint4(rec.x, rec.y, initial_medium(sc, o), kStDeltaPath | kStCameraDirection | kStAllowEmission | kStAllowAmbient);
-        q.hit_id[i]   = make_uint4(0u, 0u, x | (y << 16), initial_volumes(sc, o, sample_id));
-      }
-    }
+    generate_path<kCam>(sc, lens, q, count, valid, x, y, sample_id, slot);
   }
 }
 

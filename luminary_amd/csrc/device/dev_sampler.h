@@ -9,6 +9,7 @@ LUM_NS_BEGIN
 
 // random.cuh:24-66 - every allocation skips one slot: START_next = START + count * sets + 1.
 enum RandomTarget : uint32_t {
+  kRndLensMethod = 0,  // LENS_METHOD: one dimension per step through the physical camera's lens, 0 ... 31 (dev_camera.h)
   kRndLens = 33, kRndLensBlade = 35,
   kRndBsdfReflection = 39, kRndBsdfDiffuse = 43, kRndBsdfRefraction = 47, kRndBsdfResampling = 51, kRndBsdfOpacity = 55,
   kRndRussianRoulette = 61, kRndCameraJitter = 63,

@@ -294,6 +294,20 @@ struct AdaptiveView {
 };
 struct AdaptivePass { uint32_t task_begin, task_end, block_begin, block_end, executions; };
 
+// Physical camera (dev_camera.h; cuda/camera_physical.cuh, device_structs.c:40-72): the lens prescription and the converted camera parameters. Not part
+// of DeviceScene - only the camera-ray kernels take it, as an argument of their own - so the argument block of every other kernel stays as it is.
+constexpr uint32_t kLensMaxInterfaces = 24;  // interfaces of one lens; the table (interfaces + media) stays under 600 bytes
+struct LensInterface { float radius, vertex, cylindrical_radius; };  // DeviceCameraInterface: a spherical surface on the axis
+struct LensMedium { float design_ior, abbe, cylindrical_radius; };    // DeviceCameraMedium: medium i lies before interface i (abbe: spectral only)
+struct DeviceLens {
+  float aperture_point, aperture_radius, exit_pupil_point, exit_pupil_radius, image_plane_distance, sensor_width;
+  uint32_t num_interfaces, pad;
+  LensInterface iface[kLensMaxInterfaces];
+  LensMedium medium[kLensMaxInterfaces + 1];
+};
+// which camera the camera-ray kernels are compiled for (k_generate<kCam>, k_generate_adaptive<kCam>)
+enum CameraKind : int { kCamThinLens = 0, kCamPhysical = 1, kCamPhysicalReflections = 2 };
+
 enum PathState : uint32_t {  // cuda/utils.cuh:114-121
   kStDeltaPath = 1, kStCameraDirection = 2, kStVolumeScattered = 4, kStAllowEmission = 8, kStAllowAmbient = 16, kStUseIgnoreHandle = 32
 };

@@ -19,6 +19,7 @@
 #include "dev_particle.h"
 #include "dev_water.h"
 #include "dev_cloud_march.h"
+#include "dev_camera.h"
 
 LUM_NS_BEGIN
 
@@ -95,23 +96,108 @@ LUM_DEV uint32_t initial_volumes(const DeviceScene& sc, V3 origin, uint32_t samp
   return w;
 }
 
-__global__ __launch_bounds__(kBlock) void k_generate(DeviceScene sc, PassParams pp, PathQueue q, float4* results, uint32_t* count) {
-  const uint32_t total = pp.num_pixels * pp.batch;
-  for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < total; i += gridDim.x * kBlock) {
-    const uint32_t b = i / pp.num_pixels, p = i - b * pp.num_pixels;
-    const uint32_t index = pp.pixels ? pp.pixels[p] : p;
-    const uint32_t y = index / sc.width, x = index - y * sc.width;
-    const Sampler smp{sc.bluenoise_2d, x, y, pp.first_sample + b, 0};
-    V3 o, d;
-    camera_ray(sc, smp, o, d);
-    const U2 rec = record_pack(splat(1.0f));
-    q.origin_t[i] = make_float4(o.x, o.y, o.z, kFltMax);
-    q.dir_slot[i] = make_float4(d.x, d.y, d.z, bitsf(i));
-    q.aux[i]      = make_uint4(rec.x, rec.y, initial_medium(sc, o), kStDeltaPath | kStCameraDirection | kStAllowEmission | kStAllowAmbient);
-    q.hit_id[i]   = make_uint4(0u, 0u, x | (y << 16), initial_volumes(sc, o, pp.first_sample + b));
-    results[i]    = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+// The camera ray of a sample by camera kind; returns its weight (the thin lens's is 1).
+template <int kCam>
+LUM_DEV float camera_sample(const DeviceScene& sc, const DeviceLens& lens, const Sampler& smp, V3& o, V3& d) {
+  if constexpr (kCam == kCamThinLens) { camera_ray(sc, smp, o, d); return 1.0f; }
+  else return camera_sample_physical<kCam == kCamPhysicalReflections>(sc, lens, smp, o, d);
+}
+
+// One camera path of k_generate<physical> / k_generate_adaptive: the lanes whose ray is valid append it to the queue, one atomic per wave
+// (kernels.cuh:109-135: a ray with weight 0 gets no task; its result slot, zeroed by the caller, then adds a zero sample). Every lane of the wave
+// calls this; `active`: the lane holds a task. The thin lens's validity does not depend on the ray, so it samples after the ballot.
+template <int kCam>
+LUM_DEV void generate_path(const DeviceScene& sc, const DeviceLens& lens, const PathQueue& q, uint32_t* count, bool active, uint32_t x, uint32_t y,
+                           uint32_t sample_id, uint32_t slot) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const unsigned long long below = (1ull << lane) - 1ull;
+  V3 o, d;
+  float w = 1.0f;
+  if (kCam != kCamThinLens && active) {
+    const Sampler smp{sc.bluenoise_2d, x, y, sample_id, 0};
+    w = camera_sample<kCam>(sc, lens, smp, o, d);
   }
-  if (blockIdx.x == 0 && threadIdx.x == 0) *count = total;
+  const bool valid = active && w > 0.0f;  // color_any (math.cuh:944-946)
+  const unsigned long long ballot = __ballot(valid);
+  if (ballot) {
+    uint32_t base = 0;
+    if (lane == (uint32_t) __builtin_ctzll(ballot)) base = atomicAdd(count, (uint32_t) __popcll(ballot));
+    base = __shfl(base, __builtin_ctzll(ballot));
+    if (valid) {
+      const uint32_t i = base + (uint32_t) __popcll(ballot & below);
+      if (kCam == kCamThinLens) {
+        const Sampler smp{sc.bluenoise_2d, x, y, sample_id, 0};
+        camera_ray(sc, smp, o, d);
+      }
+      const U2 rec = record_pack(splat(w));
+      q.origin_t[i] = make_float4(o.x, o.y, o.z, kFltMax);
+      q.dir_slot[i] = make_float4(d.x, d.y, d.z, bitsf(slot));
+      q.aux[i]      = make_uint4(rec.x, rec.y, initial_medium(sc, o), kStDeltaPath | kStCameraDirection | kStAllowEmission | kStAllowAmbient);
+      q.hit_id[i]   = make_uint4(0u, 0u, x | (y << 16), initial_volumes(sc, o, sample_id));
+    }
+  }
+}
+
+// Camera paths of one pass. The thin lens fills slot i of the queue with the ray of slot i; the physical camera appends only the rays that left the
+// lens (generate_path), so the pass's path count is counted on the device from zero (the caller clears it).
+template <int kCam>
+__global__ __launch_bounds__(kBlock) void k_generate(DeviceScene sc, PassParams pp, PathQueue q, float4* results, uint32_t* count, DeviceLens lens_arg) {
+  const uint32_t total = pp.num_pixels * pp.batch;
+  if constexpr (kCam == kCamThinLens) {
+    for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < total; i += gridDim.x * kBlock) {
+      const uint32_t b = i / pp.num_pixels, p = i - b * pp.num_pixels;
+      const uint32_t index = pp.pixels ? pp.pixels[p] : p;
+      const uint32_t y = index / sc.width, x = index - y * sc.width;
+      const Sampler smp{sc.bluenoise_2d, x, y, pp.first_sample + b, 0};
+      V3 o, d;
+      camera_ray(sc, smp, o, d);
+      const U2 rec = record_pack(splat(1.0f));
+      q.origin_t[i] = make_float4(o.x, o.y, o.z, kFltMax);
+      q.dir_slot[i] = make_float4(d.x, d.y, d.z, bitsf(i));
+      q.aux[i]      = make_uint4(rec.x, rec.y, initial_medium(sc, o), kStDeltaPath | kStCameraDirection | kStAllowEmission | kStAllowAmbient);
+      q.hit_id[i]   = make_uint4(0u, 0u, x | (y << 16), initial_volumes(sc, o, pp.first_sample + b));
+      results[i]    = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) *count = total;
+  }
+  else {
+    __shared__ DeviceLens lds_lens;
+    const DeviceLens& lens = stage_lens<kCam>(lens_arg, &lds_lens);
+    const uint32_t rounds = (total + gridDim.x * kBlock - 1u) / (gridDim.x * kBlock);  // whole waves go round together: the append is per wave
+    for (uint32_t round = 0; round < rounds; round++) {
+      const uint32_t i = (round * gridDim.x + blockIdx.x) * kBlock + threadIdx.x;
+      const bool active = i < total;
+      uint32_t x = 0, y = 0, b = 0;
+      if (active) {
+        b = i / pp.num_pixels;
+        const uint32_t p = i - b * pp.num_pixels;
+        const uint32_t index = pp.pixels ? pp.pixels[p] : p;
+        y = index / sc.width; x = index - y * sc.width;
+        results[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+      }
+      generate_path<kCam>(sc, lens, q, count, active, x, y, pp.first_sample + b, i);
+    }
+  }
+}
+
+// Every camera ray of (pixels x sample ids), valid or not, sample-major like k_generate: origin, direction and weight (0 = did not leave the lens).
+// The camera-ray function of k_generate, for the tests (lumc_camera_rays).
+template <int kCam>
+__global__ __launch_bounds__(kBlock) void k_camera_rays(DeviceScene sc, DeviceLens lens_arg, const uint32_t* pixels, uint32_t n, uint32_t first_sample, uint32_t samples,
+                                                        float* out_origin, float* out_dir, float* out_weight) {
+  __shared__ DeviceLens lds_lens;
+  const DeviceLens& lens = stage_lens<kCam>(lens_arg, &lds_lens);
+  const uint32_t total = n * samples;
+  for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < total; i += gridDim.x * kBlock) {
+    const uint32_t b = i / n, index = pixels[i - b * n];
+    const uint32_t y = index / sc.width, x = index - y * sc.width;
+    const Sampler smp{sc.bluenoise_2d, x, y, first_sample + b, 0};
+    V3 o, d;
+    const float w = camera_sample<kCam>(sc, lens, smp, o, d);
+    out_origin[3 * i] = o.x; out_origin[3 * i + 1] = o.y; out_origin[3 * i + 2] = o.z;
+    out_dir[3 * i] = d.x; out_dir[3 * i + 1] = d.y; out_dir[3 * i + 2] = d.z;
+    out_weight[i] = w;
+  }
 }
 
 // ---- closest-hit pass (replaces optix/optix_kernel_raytrace.cu:147-183) ----
@@ -2248,14 +2334,18 @@ __global__ __launch_bounds__(256) void k_sobol_table(uint2* __restrict__ table, 
 }
 
 #if !LUM_FAST  // flavour-neutral: compiled once, in the exact translation unit
-// ---- camera ray of one pixel (first sample id), for pixel queries ----
-__global__ void k_pixel_ray(DeviceScene sc, uint32_t x, uint32_t y, uint32_t sample_id, float* origin, float* dir) {
+// ---- camera ray of one pixel (first sample id), for pixel queries; valid[0] = 0: the ray did not leave the lens ----
+__global__ void k_pixel_ray(DeviceScene sc, DeviceLens lens, int cam, uint32_t x, uint32_t y, uint32_t sample_id, float* origin, float* dir, uint32_t* valid) {
   if (blockIdx.x != 0 || threadIdx.x != 0) return;
   const Sampler smp{sc.bluenoise_2d, x, y, sample_id, 0};
   V3 o, d;
-  camera_ray(sc, smp, o, d);
+  float w = 1.0f;
+  if (cam == kCamThinLens) camera_ray(sc, smp, o, d);
+  else if (cam == kCamPhysical) w = camera_sample<kCamPhysical>(sc, lens, smp, o, d);
+  else w = camera_sample<kCamPhysicalReflections>(sc, lens, smp, o, d);
   origin[0] = o.x; origin[1] = o.y; origin[2] = o.z;
   dir[0] = d.x; dir[1] = d.y; dir[2] = d.z;
+  valid[0] = w > 0.0f ? 1u : 0u;
 }
 
 // ---- BSDF energy LUTs (cuda/bsdf_lut.cuh:20-211): pixel (0,0), depth 0, sample id = iteration ----

@@ -19,9 +19,11 @@ struct WavefrontKernels {
   int (*init_sampler_seeds)();
   // the Sobol / Owen pairs of a pass's sample ids for `dims` dimensions, rows of `stride` entries (dev_sampler.h LUM_SOBOL_TABLE)
   void (*sobol_table)(hipStream_t s, uint2* table, uint32_t first_sample, uint32_t count, uint32_t stride, uint32_t dims);
-  void (*generate)(uint32_t grid, hipStream_t s, const DeviceScene& sc, const PassParams& pp, const PathQueue& q, float4* results, uint32_t* count);
+  // the camera paths of a pass; cam: CameraKind (dev_scene.h), `lens` is read by the physical camera only
+  void (*generate)(uint32_t grid, hipStream_t s, const DeviceScene& sc, const PassParams& pp, const PathQueue& q, float4* results, uint32_t* count, const DeviceLens& lens,
+                   int cam);
   void (*generate_adaptive)(uint32_t grid, hipStream_t s, const DeviceScene& sc, const AdaptiveView& a, const AdaptivePass& pass, const PathQueue& q, float4* results,
-                            uint32_t* count);
+                            uint32_t* count, const DeviceLens& lens, int cam);
   void (*trace)(uint32_t grid, size_t lds, hipStream_t s, const DeviceScene& sc, const PathQueue& q, const uint32_t* order, uint32_t* ctrl, uint64_t* counters,
                 uint32_t lds_nodes);
   void (*sky_inscattering)(uint32_t grid, hipStream_t s, const DeviceScene& sc, const PathQueue& in, float4* results, const uint32_t* ctrl, uint32_t depth_const);
@@ -64,6 +66,9 @@ struct WavefrontKernels {
   void (*clouds)(uint32_t grid, hipStream_t s, const DeviceScene& sc, const PathQueue& in, const CloudQueue& cq, float4* results, const uint32_t* ctrl, uint32_t depth_const);
   void (*trace_rays)(uint32_t grid, size_t lds, hipStream_t s, const DeviceScene& sc, uint32_t n, const float* origins, const float* dirs, const uint32_t* ignore, uint32_t* out,
                      uint32_t* cursor, uint64_t* counters, uint32_t lds_nodes);
+  // every camera ray of `samples` sample ids of n pixels (device buffers; origin / dir float3, weight float), the invalid ones included (k_camera_rays)
+  void (*camera_rays)(uint32_t grid, hipStream_t s, const DeviceScene& sc, const DeviceLens& lens, int cam, const uint32_t* pixels, uint32_t n, uint32_t first_sample,
+                      uint32_t samples, float* origin, float* dir, float* weight);
 };
 
 const WavefrontKernels* wavefront_kernels_exact();  // csrc/host/core.hip

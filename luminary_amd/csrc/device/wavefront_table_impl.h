@@ -36,12 +36,21 @@ static int init_sampler_seeds() {
 static void sobol_table(hipStream_t s, uint2* table, uint32_t first_sample, uint32_t count, uint32_t stride, uint32_t dims) {
   hipLaunchKernelGGL(k_sobol_table, dim3((dims * stride + 255u) / 256u), dim3(256), 0, s, table, first_sample, count, stride, dims);
 }
-static void generate(uint32_t grid, hipStream_t s, const DeviceScene& sc, const PassParams& pp, const PathQueue& q, float4* results, uint32_t* count) {
-  hipLaunchKernelGGL(k_generate, dim3(grid), dim3(kBlock), 0, s, sc, pp, q, results, count);
+static void generate(uint32_t grid, hipStream_t s, const DeviceScene& sc, const PassParams& pp, const PathQueue& q, float4* results, uint32_t* count, const DeviceLens& lens,
+                     int cam) {
+  auto* k = cam == kCamPhysical ? k_generate<kCamPhysical> : cam == kCamPhysicalReflections ? k_generate<kCamPhysicalReflections> : k_generate<kCamThinLens>;
+  hipLaunchKernelGGL(k, dim3(grid), dim3(kBlock), 0, s, sc, pp, q, results, count, lens);
 }
 static void generate_adaptive(uint32_t grid, hipStream_t s, const DeviceScene& sc, const AdaptiveView& a, const AdaptivePass& pass, const PathQueue& q, float4* results,
-                              uint32_t* count) {
-  hipLaunchKernelGGL(k_generate_adaptive, dim3(grid), dim3(kBlock), 0, s, sc, a, pass, q, results, count);
+                              uint32_t* count, const DeviceLens& lens, int cam) {
+  auto* k = cam == kCamPhysical ? k_generate_adaptive<kCamPhysical> : cam == kCamPhysicalReflections ? k_generate_adaptive<kCamPhysicalReflections>
+                                                                                                     : k_generate_adaptive<kCamThinLens>;
+  hipLaunchKernelGGL(k, dim3(grid), dim3(kBlock), 0, s, sc, a, pass, q, results, count, lens);
+}
+static void camera_rays(uint32_t grid, hipStream_t s, const DeviceScene& sc, const DeviceLens& lens, int cam, const uint32_t* pixels, uint32_t n, uint32_t first_sample,
+                        uint32_t samples, float* origin, float* dir, float* weight) {
+  auto* k = cam == kCamPhysical ? k_camera_rays<kCamPhysical> : cam == kCamPhysicalReflections ? k_camera_rays<kCamPhysicalReflections> : k_camera_rays<kCamThinLens>;
+  hipLaunchKernelGGL(k, dim3(grid), dim3(kBlock), 0, s, sc, lens, pixels, n, first_sample, samples, origin, dir, weight);
 }
 static void trace(uint32_t grid, size_t lds, hipStream_t s, const DeviceScene& sc, const PathQueue& q, const uint32_t* order, uint32_t* ctrl, uint64_t* counters,
                   uint32_t lds_nodes) {
@@ -144,7 +153,8 @@ static void trace_rays(uint32_t grid, size_t lds, hipStream_t s, const DeviceSce
 }
 
 static const WavefrontKernels kTable = {LUM_FLAVOUR_NAME, (uint32_t) kTraceBlock, set_ray_kernel_lds, init_sampler_seeds, sobol_table, generate,    generate_adaptive, trace,  sky_inscattering, shade,
-                                        shade_debug,      sky,              light_query,        shadow_rays, resolve, resolve_reuse, resolve_listed, resolve_ended, LUM_FAST && !LUM_SHADE_STAGED, volume_inscatter, volume_resolve, volume_events, volume_bounce, trace_particles, particle_shade, trace_ocean, ocean_shade, clouds_list, clouds_march, clouds, trace_rays};
+                                        shade_debug,      sky,              light_query,        shadow_rays, resolve, resolve_reuse, resolve_listed, resolve_ended, LUM_FAST && !LUM_SHADE_STAGED, volume_inscatter, volume_resolve, volume_events, volume_bounce, trace_particles, particle_shade, trace_ocean, ocean_shade, clouds_list, clouds_march, clouds, trace_rays,
+                                        camera_rays};
 
 }  // namespace table
 LUM_NS_END

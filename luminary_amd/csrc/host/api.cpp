@@ -7,6 +7,7 @@
 //     are due, while the frontend only polls luminary_host_try_await_output / luminary_host_acquire_output (mandarin_duck.c:140-244); or
 //   * synchronously inside the additive luminary_ext_render* calls (tests, batch tools), when no render was started.
 // (DESIGN.md "Threading".)
+#include <algorithm>
 #include <atomic>
 #include <cmath>
 #include <cfloat>
@@ -127,6 +128,20 @@ bool camera_change_restarts(const LuminaryCamera& in, const LuminaryCamera& old)
   else d = d || in.thin_lens.fov != old.thin_lens.fov || in.thin_lens.aperture_size != old.thin_lens.aperture_size;
   return d;
 }
+// Any change of the lens restarts the integration of a physical camera (the lens is part of camera_check_for_dirty's physical block there).
+bool lens_change_restarts(const LuminaryCameraLens& in, const LuminaryCameraLens& old) {
+  if (in.num_interfaces != old.num_interfaces) return true;
+  const uint32_t n = std::min<uint32_t>(in.num_interfaces, LUMINARY_CAMERA_LENS_MAX_INTERFACES);
+  for (uint32_t i = 0; i < n; i++) {
+    const auto &a = in.interfaces[i], &b = old.interfaces[i];
+    if (a.radius != b.radius || a.vertex != b.vertex || a.cylindrical_radius != b.cylindrical_radius) return true;
+  }
+  for (uint32_t i = 0; i <= n; i++) {
+    const auto &a = in.media[i], &b = old.media[i];
+    if (a.design_ior != b.design_ior || a.abbe != b.abbe || a.cylindrical_radius != b.cylindrical_radius) return true;
+  }
+  return false;
+}
 bool settings_change_restarts(const LuminaryRendererSettings& in, const LuminaryRendererSettings& old) {
   bool d = in.width != old.width || in.height != old.height || in.supersampling != old.supersampling || in.bridge_max_num_vertices != old.bridge_max_num_vertices ||
            in.undersampling != old.undersampling || in.shading_mode != old.shading_mode || in.enable_adaptive_sampling != old.enable_adaptive_sampling ||
@@ -160,6 +175,17 @@ LuminaryResult ensure_device_scene(LuminaryHost* h) {
   return LUMINARY_SUCCESS;
 }
 
+// The camera a context renders with besides its scene: the converted physical camera or the scene's thin lens (lumc_set_physical_camera). Only host
+// state of the context: set on every use, so no context of any device slot can miss a camera or lens change.
+LuminaryResult set_camera(LuminaryHost* h, LumContext* core) {
+  const lum::DeviceSceneBuffers& b = h->device_scene;
+  if (lumc_set_physical_camera(core, b.use_physical_camera ? &b.physical_camera : nullptr)) {
+    std::fprintf(stderr, "[luminary_amd] %s\n", lumc_last_error(core));
+    return LUMINARY_ERROR_API_EXCEPTION;
+  }
+  return LUMINARY_SUCCESS;
+}
+
 LuminaryResult ensure_core(LuminaryHost* h) {
   if (!h->core) {
     if (lumc_context_create(h->device_ordinal, &h->core)) {
@@ -182,7 +208,7 @@ LuminaryResult ensure_core(LuminaryHost* h) {
     h->core_width = v.width; h->core_height = v.height;
     if (!same_frame || h->partition_n > 1 || lumc_clear_accumulators(h->core)) h->num_pixels = 0;
   }
-  return LUMINARY_SUCCESS;
+  return set_camera(h, h->core);
 }
 
 // The enabled devices, main device first. Rendering is tiled over them when the whole frame is rendered uniformly; adaptive sampling, render
@@ -218,6 +244,7 @@ LuminaryResult ensure_partition_cores(LuminaryHost* h, std::vector<LumContext*>*
       slot->scene_valid = true;
       h->partition_n = 0;  // the accumulation restarts: the render loop deals the tiles again (which also clears every device's accumulators)
     }
+    if (const LuminaryResult rc = set_camera(h, slot->core)) return rc;
     cores->push_back(slot->core);
   }
   return LUMINARY_SUCCESS;
@@ -578,6 +605,7 @@ LuminaryResult luminary_host_get_pixel_info(LuminaryHost* host, uint16_t x, uint
   if (x >= v.width || y >= v.height) return LUMINARY_SUCCESS;
   uint32_t q[6];
   if (lumc_pixel_query(host->core, x, y, 0, q)) return LUMINARY_ERROR_CUDA;
+  if (q[0] == 0xFFFFFFFFu) return LUMINARY_SUCCESS;  // the physical camera's ray did not leave the lens: it has no task, like a pixel without a G-buffer entry
   float depth, dir[3];
   std::memcpy(&depth, &q[2], 4); std::memcpy(dir, &q[3], 12);
   result->depth = depth;
@@ -775,7 +803,8 @@ LumOutputParams output_params(const LuminaryHost* h, uint32_t dst_width, uint32_
   p.src_width = v.width; p.src_height = v.height; p.dst_width = dst_width; p.dst_height = dst_height;
   p.inv_sample_count = 1.0f / (float) h->accumulated_samples;
   p.exposure = std::exp(c.exposure);
-  p.tonemap = (uint32_t) c.tonemap; p.filter = (uint32_t) c.filter; p.dithering = c.dithering ? 1u : 0u; p.purkinje = c.purkinje ? 1u : 0u;
+  p.tonemap = (uint32_t) c.tonemap; p.filter = (uint32_t) c.filter; p.dithering = c.dithering ? 1u : 0u;
+  p.purkinje = (c.purkinje && !c.use_physical_camera) ? 1u : 0u;  // device_structs.c:48: no Purkinje shift behind the physical camera
   p.use_color_correction = c.use_color_correction ? 1u : 0u;
   // tonemap_apply leaves the pixel alone for debug shading modes and for the adaptive-sampling diagnostic images (tonemap.cuh:206-211)
   p.passthrough = (h->scene.settings.shading_mode != LUMINARY_SHADING_MODE_DEFAULT ||
@@ -1202,7 +1231,24 @@ LuminaryResult luminary_ext_change_restarts_integration(int entity, const void* 
   CHECK_NULL(input); CHECK_NULL(old); CHECK_NULL(restarts);
   if (entity == 0) *restarts = settings_change_restarts(*(const LuminaryRendererSettings*) input, *(const LuminaryRendererSettings*) old);
   else if (entity == 1) *restarts = camera_change_restarts(*(const LuminaryCamera*) input, *(const LuminaryCamera*) old);
+  else if (entity == 2) *restarts = lens_change_restarts(*(const LuminaryCameraLens*) input, *(const LuminaryCameraLens*) old);
   else return LUMINARY_ERROR_INVALID_API_ARGUMENT;
+  return LUMINARY_SUCCESS;
+}
+LuminaryResult luminary_ext_set_camera_lens(LuminaryHost* host, const LuminaryCameraLens* lens) {
+  CHECK_NULL(host); CHECK_NULL(lens);
+  const std::string e = lum::validate_camera_lens(*lens);
+  if (!e.empty()) { std::fprintf(stderr, "[luminary_amd] %s\n", e.c_str()); return LUMINARY_ERROR_INVALID_API_ARGUMENT; }
+  ApiLock lock(host);
+  const bool restarts = host->scene.camera.use_physical_camera && lens_change_restarts(*lens, host->scene.lens);
+  host->scene.lens = *lens;
+  if (restarts) invalidate(host, LUMC_DIRTY_CONSTANTS);
+  return LUMINARY_SUCCESS;
+}
+LuminaryResult luminary_ext_get_camera_lens(LuminaryHost* host, LuminaryCameraLens* lens) {
+  CHECK_NULL(host); CHECK_NULL(lens);
+  ApiLock lock(host);
+  *lens = host->scene.lens;
   return LUMINARY_SUCCESS;
 }
 void* luminary_ext_get_core_context(LuminaryHost* host) {

@@ -7,6 +7,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cfloat>
 #include <queue>
 #include <cstdio>
@@ -40,6 +41,8 @@ struct LumContext {
   int device = 0;
   std::string error;
   const WavefrontKernels* wf = wavefront_kernels_fast();  // flavour of the wavefront kernels (lumc_set_flavour; LUM_FLAVOUR=exact|fast overrides the default)
+  int camera = kCamThinLens;  // CameraKind of the camera-ray kernels (lumc_set_physical_camera)
+  DeviceLens lens{};          // the physical camera's lens, an argument of those kernels
   // device allocations of the scene by the part of it they belong to (lumc_scene_update frees and rebuilds a part at a time)
   enum AllocGroup { kGrpMesh = 0, kGrpInst, kGrpMat, kGrpLight, kGrpTex, kGrpConst, kGrpPart, kGrpOnce, kGrpCount };
   std::vector<void*> scene_allocs[kGrpCount];
@@ -2080,7 +2083,7 @@ int lumc_render(LumContext* ctx, uint32_t first_sample, uint32_t num_samples, ui
     HIP_TRY(ctx, hipMemsetAsync(ctx->d_ctrl, 0, sizeof(uint32_t) * kCtlStride * (max_depth + 2), stream));
     {
       Launch l(ctx, stream, LUMC_KERNEL_GENERATE);
-      ctx->wf->generate(grid_for(N), stream, sc, pp, ctx->queue[0], ctx->d_results, ctx->d_ctrl + kCtlPaths);
+      ctx->wf->generate(grid_for(N), stream, sc, pp, ctx->queue[0], ctx->d_results, ctx->d_ctrl + kCtlPaths, ctx->lens, ctx->camera);
     }
     if (wavefront_depths(ctx, stream, N, first_sample + done, batch)) return 1;
     {
@@ -2136,7 +2139,7 @@ int lumc_render_undersampled(LumContext* ctx, uint32_t stage, uint32_t iteration
   HIP_TRY(ctx, hipMemsetAsync(ctx->d_ctrl, 0, sizeof(uint32_t) * kCtlStride * (sc.max_ray_depth + 2), stream));
   {
     Launch l(ctx, stream, LUMC_KERNEL_GENERATE);
-    ctx->wf->generate(grid_for(n), stream, sc, pp, ctx->queue[0], ctx->d_results, ctx->d_ctrl + kCtlPaths);
+    ctx->wf->generate(grid_for(n), stream, sc, pp, ctx->queue[0], ctx->d_results, ctx->d_ctrl + kCtlPaths, ctx->lens, ctx->camera);
   }
   if (wavefront_depths(ctx, stream, n)) return 1;
   {
@@ -2238,7 +2241,7 @@ int adaptive_execute(LumContext* ctx, hipStream_t stream, uint32_t merged) {
     HIP_TRY(ctx, hipMemsetAsync(ctx->d_ctrl, 0, sizeof(uint32_t) * kCtlStride * (sc.max_ray_depth + 2), stream));
     {
       Launch l(ctx, stream, LUMC_KERNEL_GENERATE);
-      ctx->wf->generate_adaptive(grid_for(N), stream, sc, view, pass, ctx->queue[0], ctx->d_results, ctx->d_ctrl + kCtlPaths);
+      ctx->wf->generate_adaptive(grid_for(N), stream, sc, view, pass, ctx->queue[0], ctx->d_results, ctx->d_ctrl + kCtlPaths, ctx->lens, ctx->camera);
     }
     if (wavefront_depths(ctx, stream, N)) return 1;
     {
@@ -2696,12 +2699,72 @@ int lumc_pixel_query(LumContext* ctx, uint32_t x, uint32_t y, uint32_t sample_id
   if (x >= ctx->scene.width || y >= ctx->scene.height) { ctx->error = "lumc_pixel_query: pixel outside the frame"; return 1; }
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   float* d = nullptr;
-  HIP_TRY(ctx, hipMalloc((void**) &d, sizeof(float) * 9));
-  hipLaunchKernelGGL(k_pixel_ray, dim3(1), dim3(64), 0, 0, ctx->scene, x, y, sample_id, d, d + 3);
-  int rc = lumc_trace_closest(ctx, 1, d, d + 3, nullptr, (uint32_t*) (d + 6), nullptr);
-  if (!rc && (hipDeviceSynchronize() != hipSuccess || hipMemcpy(out, d + 6, 12, hipMemcpyDeviceToHost) != hipSuccess ||
+  HIP_TRY(ctx, hipMalloc((void**) &d, sizeof(float) * 10));
+  hipLaunchKernelGGL(k_pixel_ray, dim3(1), dim3(64), 0, 0, ctx->scene, ctx->lens, ctx->camera, x, y, sample_id, d, d + 3, (uint32_t*) (d + 9));
+  uint32_t valid = 0;
+  int rc = (hipMemcpy(&valid, d + 9, 4, hipMemcpyDeviceToHost) != hipSuccess) ? 1 : 0;
+  if (rc) ctx->error = "lumc_pixel_query: device error";
+  else if (valid) rc = lumc_trace_closest(ctx, 1, d, d + 3, nullptr, (uint32_t*) (d + 6), nullptr);
+  if (!rc && (hipDeviceSynchronize() != hipSuccess || (valid && hipMemcpy(out, d + 6, 12, hipMemcpyDeviceToHost) != hipSuccess) ||
               hipMemcpy(out + 3, d + 3, 12, hipMemcpyDeviceToHost) != hipSuccess)) { ctx->error = "lumc_pixel_query: device error"; rc = 1; }
+  if (!rc && !valid) { out[0] = 0xFFFFFFFFu; out[1] = 0u; std::memcpy(&out[2], &kFltMax, 4); }  // the ray did not leave the lens: nothing is hit
   (void) hipFree(d);
+  return rc;
+}
+
+int lumc_set_physical_camera(LumContext* ctx, const LumPhysicalCamera* c) {
+  if (!ctx) return 1;
+  if (!c) { ctx->camera = kCamThinLens; return 0; }
+  if (c->num_interfaces == 0 || c->num_interfaces > LUMC_LENS_MAX_INTERFACES) { ctx->error = "lumc_set_physical_camera: 1 ... 24 interfaces"; return 1; }
+  const uint32_t n = c->num_interfaces;
+  bool finite = std::isfinite(c->aperture_point) && std::isfinite(c->aperture_radius) && std::isfinite(c->exit_pupil_point) && std::isfinite(c->exit_pupil_radius) &&
+                std::isfinite(c->image_plane_distance) && std::isfinite(c->sensor_width);
+  bool ior_ok = true;
+  for (uint32_t i = 0; i < n; i++) {
+    const LumLensInterface& f = c->interfaces[i];
+    finite = finite && std::isfinite(f.radius) && std::isfinite(f.vertex) && std::isfinite(f.cylindrical_radius);
+  }
+  for (uint32_t i = 0; i <= n; i++) {
+    const LumLensMedium& m = c->media[i];
+    finite = finite && std::isfinite(m.design_ior) && std::isfinite(m.abbe) && std::isfinite(m.cylindrical_radius);
+    ior_ok = ior_ok && m.design_ior > 0.0f;
+  }
+  if (!finite) { ctx->error = "lumc_set_physical_camera: non-finite parameter"; return 1; }
+  if (!(c->exit_pupil_radius > 0.0f) || !(c->aperture_radius > 0.0f)) { ctx->error = "lumc_set_physical_camera: exit pupil and aperture must be larger than 0"; return 1; }
+  if (!ior_ok) { ctx->error = "lumc_set_physical_camera: index of refraction <= 0"; return 1; }
+  static_assert(sizeof(LumLensInterface) == sizeof(LensInterface) && sizeof(LumLensMedium) == sizeof(LensMedium), "lens tables: one layout");
+  DeviceLens l{};
+  l.aperture_point = c->aperture_point; l.aperture_radius = c->aperture_radius; l.exit_pupil_point = c->exit_pupil_point; l.exit_pupil_radius = c->exit_pupil_radius;
+  l.image_plane_distance = c->image_plane_distance; l.sensor_width = c->sensor_width; l.num_interfaces = n;
+  std::memcpy(l.iface, c->interfaces, sizeof(LensInterface) * n);
+  std::memcpy(l.medium, c->media, sizeof(LensMedium) * (n + 1));
+  ctx->lens = l;
+  ctx->camera = c->allow_reflections ? kCamPhysicalReflections : kCamPhysical;
+  return 0;
+}
+
+int lumc_camera_rays(LumContext* ctx, const uint32_t* pixels, uint32_t n, uint32_t first_sample, uint32_t samples, float* out_origin, float* out_dir, float* out_weight) {
+  if (!ctx || !ctx->has_scene || !pixels || !out_origin || !out_dir || !out_weight) { if (ctx) ctx->error = "lumc_camera_rays: no scene or null argument"; return 1; }
+  const uint64_t total = (uint64_t) n * samples;
+  if (total == 0) return 0;
+  if (total > 0x7FFFFFFFull) { ctx->error = "lumc_camera_rays: too many rays"; return 1; }
+  for (uint32_t p = 0; p < n; p++)
+    if (pixels[p] >= ctx->scene.width * ctx->scene.height) { ctx->error = "lumc_camera_rays: pixel outside the frame"; return 1; }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  uint32_t* d_px = nullptr;
+  float* d = nullptr;
+  HIP_TRY(ctx, hipMalloc((void**) &d_px, sizeof(uint32_t) * (size_t) n));
+  if (hipMalloc((void**) &d, sizeof(float) * 7 * (size_t) total) != hipSuccess) { (void) hipFree(d_px); ctx->error = "lumc_camera_rays: out of device memory"; return 1; }
+  int rc = 0;
+  if (hipMemcpy(d_px, pixels, sizeof(uint32_t) * (size_t) n, hipMemcpyHostToDevice) != hipSuccess) rc = 1;
+  if (!rc) {
+    ctx->wf->camera_rays(grid_for((uint32_t) total), 0, ctx->scene, ctx->lens, ctx->camera, d_px, n, first_sample, samples, d, d + 3 * total, d + 6 * total);
+    if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess || hipMemcpy(out_origin, d, sizeof(float) * 3 * total, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(out_dir, d + 3 * total, sizeof(float) * 3 * total, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(out_weight, d + 6 * total, sizeof(float) * total, hipMemcpyDeviceToHost) != hipSuccess) rc = 1;
+  }
+  if (rc) ctx->error = "lumc_camera_rays: device error";
+  (void) hipFree(d_px); (void) hipFree(d);
   return rc;
 }
 

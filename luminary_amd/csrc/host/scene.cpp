@@ -52,6 +52,59 @@ void default_camera(LuminaryCamera* c) {  // camera.c:7-66
   c->physical.sensor_width = 20.0f;
 }
 
+// The reference's lens (device_physical_camera.c:17-54, "a placeholder until the camera is given through the API"): a double-Gauss prescription of
+// 12 spherical interfaces and 13 media (design index of refraction, Abbe number, cylindrical radius; the cylindrical radii are the reference's own
+// rough estimates), radii and vertices scaled by 50.53 / 100 in float.
+void default_camera_lens(LuminaryCameraLens* l) {
+  std::memset(l, 0, sizeof(*l));
+  static const float iface[12][3] = {{-94.29f, 0.0f, 14.0f},    {181.58f, 7.17f, 14.0f},  {-72.86f, 9.3f, 12.0f},   {76.74f, 21.7f, 12.0f},
+                                     {-43.02f, 23.83f, 12.0f},  {27.44f, 45.14f, 17.0f},  {-321.70f, 49.53f, 17.0f}, {50.96f, 70.01f, 17.0f},
+                                     {120.34f, 70.97f, 20.0f},  {68.99f, 78.97f, 20.0f},  {251.93f, 79.18f, 23.2f},  {94.00f, 88.18f, 23.2f}};
+  const float air = 1.0003f, open = FLT_MAX;  // IOR_AIR (device_utils.h:71); air has no rim
+  static const float glass[13][3] = {{0.0f, 0.0f, 0.0f},      {1.6435f, 53.5f, 14.0f}, {0.0f, 0.0f, 0.0f},      {1.6935f, 53.5f, 12.0f}, {1.5174f, 52.5f, 12.0f},
+                                     {0.0f, 0.0f, 0.0f},      {1.7174f, 29.5f, 17.0f}, {1.6385f, 55.5f, 17.0f}, {0.0f, 0.0f, 0.0f},      {1.7173f, 47.9f, 20.0f},
+                                     {0.0f, 0.0f, 0.0f},      {1.6935f, 53.5f, 23.2f}, {0.0f, 0.0f, 0.0f}};  // zero rows: air
+  const float scale = 50.53f / 100.0f;
+  l->num_interfaces = 12;
+  for (int i = 0; i < 12; i++) l->interfaces[i] = LuminaryCameraLensInterface{iface[i][0] * scale, iface[i][1] * scale, iface[i][2]};
+  for (int i = 0; i < 13; i++)
+    l->media[i] = glass[i][0] == 0.0f ? LuminaryCameraLensMedium{air, 0.0f, open} : LuminaryCameraLensMedium{glass[i][0], glass[i][1], glass[i][2]};
+}
+
+std::string validate_camera_lens(const LuminaryCameraLens& l) {
+  if (l.num_interfaces == 0 || l.num_interfaces > LUMINARY_CAMERA_LENS_MAX_INTERFACES) return "camera lens: 1 ... 24 interfaces";
+  for (uint32_t i = 0; i < l.num_interfaces; i++) {
+    const LuminaryCameraLensInterface& f = l.interfaces[i];
+    if (!std::isfinite(f.radius) || !std::isfinite(f.vertex) || !std::isfinite(f.cylindrical_radius)) return "camera lens: non-finite interface";
+  }
+  for (uint32_t i = 0; i <= l.num_interfaces; i++) {
+    const LuminaryCameraLensMedium& m = l.media[i];
+    if (!std::isfinite(m.design_ior) || !std::isfinite(m.abbe) || !std::isfinite(m.cylindrical_radius)) return "camera lens: non-finite medium";
+    if (!(m.design_ior > 0.0f)) return "camera lens: index of refraction <= 0";
+  }
+  return "";
+}
+
+std::string physical_camera_convert(const LuminaryCamera& c, const LuminaryCameraLens& l, LumPhysicalCamera* out) {
+  if (c.physical.use_spectral_rendering) return "physical camera: spectral rendering (physical.use_spectral_rendering) is outside the supported scope";
+  const std::string e = validate_camera_lens(l);
+  if (!e.empty()) return e;
+  const auto& p = c.physical;
+  for (float v : {p.aperture_point, p.aperture_diameter, p.exit_pupil_point, p.exit_pupil_diameter, p.image_plane_distance, p.sensor_width})
+    if (!std::isfinite(v)) return "physical camera: non-finite parameter";
+  if (!(p.aperture_diameter > 0.0f) || !(p.exit_pupil_diameter > 0.0f)) return "physical camera: aperture and exit pupil diameters must be larger than 0";
+  std::memset(out, 0, sizeof(*out));
+  out->aperture_point = p.aperture_point; out->aperture_radius = p.aperture_diameter * 0.5f;
+  out->exit_pupil_point = p.exit_pupil_point; out->exit_pupil_radius = p.exit_pupil_diameter * 0.5f;
+  out->image_plane_distance = p.image_plane_distance; out->sensor_width = p.sensor_width;
+  out->allow_reflections = p.allow_reflections ? 1u : 0u;
+  out->num_interfaces = l.num_interfaces;
+  static_assert(sizeof(LumLensInterface) == sizeof(LuminaryCameraLensInterface) && sizeof(LumLensMedium) == sizeof(LuminaryCameraLensMedium), "one layout");
+  std::memcpy(out->interfaces, l.interfaces, sizeof(LumLensInterface) * l.num_interfaces);
+  std::memcpy(out->media, l.media, sizeof(LumLensMedium) * (l.num_interfaces + 1));
+  return "";
+}
+
 // jendersie_eon_phase_parameters, cuda/math.cuh:1189-1232: the four parameters depend on the droplet diameter only, so they are
 // evaluated once here (the reference evaluates them per ray on the device) and travel with the scene.
 void jendersie_eon_parameters(float d, float out[4]) {
@@ -198,7 +251,7 @@ void default_particles(LuminaryParticles* p) {  // particles.c:6-24
 }
 
 HostScene::HostScene() {
-  default_settings(&settings); default_camera(&camera); default_ocean(&ocean); default_sky(&sky); default_cloud(&cloud);
+  default_settings(&settings); default_camera(&camera); default_camera_lens(&lens); default_ocean(&ocean); default_sky(&sky); default_cloud(&cloud);
   default_fog(&fog); default_particles(&particles);
 }
 
@@ -937,7 +990,11 @@ std::string update_device_scene(const HostScene& scene, const std::vector<uint32
   if (st.supersampling > 3) return "supersampling exceeds its 2-bit field";
   const uint32_t width = st.width << st.supersampling, height = st.height << st.supersampling;  // device_structs.c:20-21
   if (width == 0 || height == 0 || width >= 16384 || height >= 16384) return "internal resolution must be in [1, 16383] (14-bit pixel ids)";
-  if (scene.camera.use_physical_camera) return "physical camera is outside the supported scope (thin lens only)";
+  if (scene.camera.use_physical_camera) {
+    const std::string e = physical_camera_convert(scene.camera, scene.lens, &out->physical_camera);
+    if (!e.empty()) return e;
+  }
+  out->use_physical_camera = scene.camera.use_physical_camera;
   if (scene.materials.size() > 0xFFFF) return "too many materials";
 
   DeviceSceneBuffers& b = *out;

@@ -35,6 +35,7 @@ struct HostTexture { uint32_t width = 0, height = 0; float gamma = 1.0f; std::ve
 struct HostScene {
   LuminaryRendererSettings settings;
   LuminaryCamera camera;
+  LuminaryCameraLens lens;  // the physical camera's lens (luminary_ext_set_camera_lens)
   LuminaryOcean ocean;
   LuminarySky sky;
   LuminaryCloud cloud;
@@ -51,6 +52,11 @@ struct HostScene {
 // Defaults (settings.c:6-28, camera.c:7-66, sky.c:6-41, material.c:5-29 and the out-of-scope entities' own files).
 void default_settings(LuminaryRendererSettings* s);
 void default_camera(LuminaryCamera* c);
+void default_camera_lens(LuminaryCameraLens* l);  // device_physical_camera.c:17-54
+// An empty string or why the lens cannot be used (count, non-finite values, an index of refraction <= 0).
+std::string validate_camera_lens(const LuminaryCameraLens& l);
+// device_struct_camera_convert (device_structs.c:40-72) for the physical camera: diameters to radii, the lens table. An empty string or an error.
+std::string physical_camera_convert(const LuminaryCamera& c, const LuminaryCameraLens& l, LumPhysicalCamera* out);
 void default_sky(LuminarySky* s);
 void default_material(LuminaryMaterial* m);
 void default_ocean(LuminaryOcean* o);
@@ -87,6 +93,9 @@ struct DeviceSceneBuffers {
   uint32_t num_textures = 0, moon_albedo_tex = 0xFFFFFFFFu, moon_normal_tex = 0xFFFFFFFFu;
   bool moon_in_pool = false;
   uint32_t rebuilt = 0;  // LUMC_DIRTY_* parts the last update_device_scene rebuilt (what the core has to take over)
+  // the camera the contexts render with besides the view (lumc_set_physical_camera): valid when use_physical_camera
+  bool use_physical_camera = false;
+  LumPhysicalCamera physical_camera{};
 };
 
 // Fills `out` from the scene. `bluenoise` must hold 65536 texels. Returns an empty string or an error message.

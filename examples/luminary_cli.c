@@ -5,7 +5,7 @@
  * the same calls a frontend makes against the reference library, linked against libluminary_amd.so instead.
  *
  *   gcc -std=c11 -I include examples/luminary_cli.c -L luminary_amd/lib -lluminary_amd -Wl,-rpath,$PWD/luminary_amd/lib -o luminary_cli
- *   ./luminary_cli scene.lum 64 out.png [width height]
+ *   ./luminary_cli scene.lum 64 out.png [width height] [--denoise]
  */
 #include <stdio.h>
 #include <stdlib.h>
@@ -23,8 +23,15 @@
   } while (0)
 
 int main(int argc, char** argv) {
+  int denoise = 0; /* --denoise (anywhere): the output passes through the denoiser (luminary_ext_set_denoiser) */
+  for (int i = 1; i < argc; i++) {
+    if (strcmp(argv[i], "--denoise") != 0) continue;
+    denoise = 1;
+    for (int k = i; k + 1 < argc; k++) argv[k] = argv[k + 1];
+    argc--; i--;
+  }
   if (argc < 4) {
-    fprintf(stderr, "usage: %s <scene.lum|scene.obj> <samples> <out.png> [width height]\n", argv[0]);
+    fprintf(stderr, "usage: %s <scene.lum|scene.obj> <samples> <out.png> [width height] [--denoise]\n", argv[0]);
     return 1;
   }
   const char* scene = argv[1];
@@ -52,6 +59,13 @@ int main(int argc, char** argv) {
   }
   settings.undersampling = 0; /* no preview stages in a batch render */
   CHECK(luminary_host_set_settings(host, &settings));
+
+  if (denoise) {
+    LuminaryDenoiserSettings dn;
+    CHECK(luminary_ext_get_denoiser(host, &dn));
+    dn.enabled = true;
+    CHECK(luminary_ext_set_denoiser(host, &dn));
+  }
 
   LuminaryOutputRequestProperties request;
   memset(&request, 0, sizeof(request));

@@ -423,6 +423,24 @@ LUMINARY_API LuminaryResult luminary_ext_is_rendering(LuminaryHost* host, bool* 
 LUMINARY_API LuminaryResult luminary_ext_get_accumulators(LuminaryHost* host, float* first_moment, float* second_moment, uint32_t* num_pixels);
 /* Radiance = first moment / sample_count for the full frame (rgb interleaved, width*height*3 floats). */
 LUMINARY_API LuminaryResult luminary_ext_get_radiance(LuminaryHost* host, float* rgb, uint32_t* sample_count, uint32_t width, uint32_t height);
+/* Denoiser (include/lum_core.h lumc_denoise): a variance-guided edge-avoiding a-trous filter on albedo-demodulated radiance, guided by first-hit albedo, normal and
+ * depth. When enabled it runs between the result image and bloom, on beauty images of the whole frame in the default shading mode (where bloom runs); not on the
+ * undersampling preview, the debug shading modes or the adaptive-sampling diagnostic images. The guides are rendered once per accumulation (guide_samples sample
+ * ids, one closest-hit pass each, on the device that holds the frame). Off by default; setting it does not restart the integration.
+ * The reference's `GENERAL DENOISER` key of .lum v4 files stays unread, as in the reference. */
+typedef struct LuminaryDenoiserSettings {
+  bool enabled;           /* false */
+  uint32_t guide_samples; /* 4: 1 ... 1024 */
+  uint32_t iterations;    /* 5: a-trous iterations, at most 6 */
+  float sigma_luminance;  /* 4 */
+  float sigma_normal;     /* 128 */
+  float sigma_depth;      /* 1 */
+} LuminaryDenoiserSettings;
+LUMINARY_API LuminaryResult luminary_ext_set_denoiser(LuminaryHost* host, const LuminaryDenoiserSettings* settings);
+LUMINARY_API LuminaryResult luminary_ext_get_denoiser(LuminaryHost* host, LuminaryDenoiserSettings* settings);
+/* The denoised mean radiance of the full frame (rgb interleaved, width*height*3 floats), whether or not the denoiser is enabled for the outputs;
+ * luminary_ext_get_radiance keeps returning the undenoised mean. */
+LUMINARY_API LuminaryResult luminary_ext_get_denoised(LuminaryHost* host, float* rgb, uint32_t width, uint32_t height);
 /* out[0] closest-hit rays, [1] shadow rays, [2] light-BVH queries, [3] shaded vertices, [4] BVH nodes visited, [5] triangles tested. */
 LUMINARY_API LuminaryResult luminary_ext_get_ray_counters(LuminaryHost* host, uint64_t out[8]);
 /* The lumc context of this host (include/lum_core.h), for callers that drive passes themselves. */

@@ -84,6 +84,12 @@ class CameraLens(C.Structure):
     _fields_ = [("num_interfaces", C.c_uint32), ("interfaces", LensInterface * LENS_MAX_INTERFACES), ("media", LensMedium * (LENS_MAX_INTERFACES + 1))]
 
 
+class DenoiserSettings(C.Structure):
+    """include/luminary_amd.h LuminaryDenoiserSettings (defaults: off, 4 guide samples, 5 iterations, sigmas 4 / 128 / 1)."""
+    _fields_ = [("enabled", C.c_bool), ("guide_samples", C.c_uint32), ("iterations", C.c_uint32), ("sigma_luminance", C.c_float), ("sigma_normal", C.c_float),
+                ("sigma_depth", C.c_float)]
+
+
 class Sky(C.Structure):
     _fields_ = [("geometry_offset", Vec3)] + [(n, C.c_float) for n in ("azimuth", "altitude", "moon_azimuth", "moon_altitude", "moon_tex_offset",
                                                                        "sun_strength", "base_density")] + \
@@ -537,6 +543,26 @@ class Host:
         sm = np.zeros(n.value, dtype=np.float32)
         _call("luminary_ext_get_accumulators", self._h, fm.ctypes.data_as(C.c_void_p), sm.ctypes.data_as(C.c_void_p), C.byref(n))
         return fm.reshape(3, -1), sm
+
+    def get_denoiser(self):
+        """luminary_ext_get_denoiser"""
+        d = DenoiserSettings()
+        _call("luminary_ext_get_denoiser", self._h, C.byref(d))
+        return d
+
+    def set_denoiser(self, settings=None, **fields):
+        """luminary_ext_set_denoiser: the given settings, or the current ones with `fields` changed (set_denoiser(enabled=True)). Does not restart the integration."""
+        d = settings if settings is not None else self.get_denoiser()
+        for k, v in fields.items():
+            setattr(d, k, v)
+        _call("luminary_ext_set_denoiser", self._h, C.byref(d))
+
+    def denoised(self, width, height):
+        """luminary_ext_get_denoised: the denoised mean radiance [H, W, 3] of the accumulated frame."""
+        import numpy as np
+        out = np.zeros((height, width, 3), dtype=np.float32)
+        _call("luminary_ext_get_denoised", self._h, out.ctypes.data_as(C.c_void_p), C.c_uint32(width), C.c_uint32(height))
+        return out
 
     def ray_counters(self):
         out = (C.c_uint64 * 8)()

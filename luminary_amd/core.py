@@ -76,6 +76,20 @@ class PhysicalCamera(C.Structure):
                 ("media", LensMedium * (LENS_MAX_INTERFACES + 1))]
 
 
+class DenoiseParams(C.Structure):
+    """include/lum_core.h LumDenoiseParams"""
+    _fields_ = [("iterations", C.c_uint32), ("sigma_luminance", C.c_float), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("uniform_samples", C.c_uint32)]
+
+
+def default_denoise_params(uniform_samples=0, **fields):
+    p = DenoiseParams()
+    _lib().lumc_denoise_default_params(C.byref(p))
+    p.uniform_samples = uniform_samples
+    for k, v in fields.items():
+        setattr(p, k, v)
+    return p
+
+
 class Core:
     def __init__(self, device=0):
         self._lib = _lib()
@@ -392,6 +406,34 @@ class Core:
         """Bloom of a planar result image [3, H >> stage, W >> stage] (host array); returns the processed copy."""
         img = np.ascontiguousarray(image, dtype=np.float32).copy()
         self._call("lumc_post_bloom_host", img.ctypes.data_as(C.c_void_p), C.c_uint32(full_width), C.c_uint32(full_height), C.c_uint32(stage), C.c_float(blend))
+        return img
+
+    # ---- denoiser (lumc_render_guides, lumc_denoise) ----
+    def render_guides(self, num_samples=4, stream=0):
+        """First-hit guides of the whole frame from sample ids [0, num_samples); returns (albedo [3, H, W], normal [3, H, W], depth [H, W], -1 = nothing hit)."""
+        self._call("lumc_render_guides", C.c_uint32(num_samples), C.c_void_p(stream))
+        return self.guides()
+
+    def guides(self):
+        a, n, d = (np.zeros((3, self.height, self.width), np.float32), np.zeros((3, self.height, self.width), np.float32), np.zeros((self.height, self.width), np.float32))
+        self._call("lumc_download_guides", a.ctypes.data_as(C.c_void_p), n.ctypes.data_as(C.c_void_p), d.ctypes.data_as(C.c_void_p))
+        return a, n, d
+
+    def set_denoise_form(self, lds):
+        """a-trous iterations with taps 1 and 2 apart: tile and halo staged in LDS (True, default) or every tap loaded directly; same bits"""
+        self._call("lumc_set_denoise_form", C.c_int(1 if lds else 0))
+
+    def denoise(self, image=None, params=None, **fields):
+        """lumc_denoise on a planar image [3, H, W] (host array; returns the filtered copy) or, with image None, in place on the context's result image
+        (returns it). `params`: DenoiseParams, or the defaults with `fields` changed."""
+        p = params if params is not None else default_denoise_params(**fields)
+        if image is None:
+            self._call("lumc_denoise", C.byref(p), C.c_void_p(0), C.c_void_p(0))
+            out = np.zeros((3, self.height, self.width), dtype=np.float32)
+            self._call("lumc_download_result_image", out.ctypes.data_as(C.c_void_p))
+            return out
+        img = np.ascontiguousarray(image, dtype=np.float32).copy()
+        self._call("lumc_denoise_host", C.byref(p), img.ctypes.data_as(C.c_void_p))
         return img
 
     def render_undersampled(self, stage, iteration, stream=0):

@@ -293,6 +293,11 @@ struct AdaptiveView {
   uint32_t stage_id;
 };
 struct AdaptivePass { uint32_t task_begin, task_end, block_begin, block_end, executions; };
+// One launch of the denoiser's kernels (dev_denoise.h): the frame, the a-trous iteration's tap distance, the sample count outside adaptive mode, the edge weights.
+struct DenoiseArgs {
+  uint32_t width, height, step, uniform_samples;
+  float sigma_luminance, sigma_normal, sigma_depth;
+};
 
 // Physical camera (dev_camera.h; cuda/camera_physical.cuh, device_structs.c:40-72): the lens prescription and the converted camera parameters. Not part
 // of DeviceScene - only the camera-ray kernels take it, as an argument of their own - so the argument block of every other kernel stays as it is.

@@ -69,6 +69,14 @@ struct WavefrontKernels {
   // every camera ray of `samples` sample ids of n pixels (device buffers; origin / dir float3, weight float), the invalid ones included (k_camera_rays)
   void (*camera_rays)(uint32_t grid, hipStream_t s, const DeviceScene& sc, const DeviceLens& lens, int cam, const uint32_t* pixels, uint32_t n, uint32_t first_sample,
                       uint32_t samples, float* origin, float* dir, float* weight);
+  // denoiser (dev_denoise.h): first-hit guides of the paths of one sample id after a closest-hit pass (`planes`: 9 sum planes of n pixels), their means, and the
+  // filter's three stages; `lds`: the a-trous iteration stages its tile and halo in LDS (steps 1 and 2 only)
+  void (*guide)(uint32_t grid, hipStream_t s, const DeviceScene& sc, const PathQueue& in, const uint32_t* ctrl, float* planes, uint32_t n);
+  void (*guide_normalise)(uint32_t grid, hipStream_t s, float* planes, uint32_t n, uint32_t samples);
+  void (*denoise_prepare)(uint32_t grid, hipStream_t s, const AdaptiveView& a, const DenoiseArgs& p, const float* fm, const float* sm, const float* image, const float* guides,
+                          float4* rec_a, uint4* rec_b);
+  void (*denoise_atrous)(hipStream_t s, const DenoiseArgs& p, const float4* a_in, const uint4* rec_b, float4* a_out, bool lds);
+  void (*denoise_finish)(uint32_t grid, hipStream_t s, const DenoiseArgs& p, const float4* rec_a, const float* guides, float* image);
 };
 
 const WavefrontKernels* wavefront_kernels_exact();  // csrc/host/core.hip

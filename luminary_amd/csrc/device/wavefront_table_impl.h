@@ -4,6 +4,7 @@
 #include <vector>
 
 #include "dev_adaptive.h"
+#include "dev_denoise.h"
 #include "wavefront_table.h"
 
 LUM_NS_BEGIN
@@ -151,10 +152,28 @@ static void trace_rays(uint32_t grid, size_t lds, hipStream_t s, const DeviceSce
                        uint32_t* cursor, uint64_t* counters, uint32_t lds_nodes) {
   hipLaunchKernelGGL(k_trace_rays, dim3(grid), dim3(kTraceBlock), lds, s, sc, n, origins, dirs, ignore, out, cursor, counters, lds_nodes);
 }
+static void guide(uint32_t grid, hipStream_t s, const DeviceScene& sc, const PathQueue& in, const uint32_t* ctrl, float* planes, uint32_t n) {
+  hipLaunchKernelGGL(k_guide, dim3(grid), dim3(kBlock), 0, s, sc, in, ctrl, planes, n);
+}
+static void guide_normalise(uint32_t grid, hipStream_t s, float* planes, uint32_t n, uint32_t samples) {
+  hipLaunchKernelGGL(k_guide_normalise, dim3(grid), dim3(256), 0, s, planes, n, samples);
+}
+static void denoise_prepare(uint32_t grid, hipStream_t s, const AdaptiveView& a, const DenoiseArgs& p, const float* fm, const float* sm, const float* image, const float* guides,
+                            float4* rec_a, uint4* rec_b) {
+  hipLaunchKernelGGL(k_denoise_prepare, dim3(grid), dim3(256), 0, s, a, p, fm, sm, image, guides, rec_a, rec_b);
+}
+static void denoise_atrous(hipStream_t s, const DenoiseArgs& p, const float4* a_in, const uint4* rec_b, float4* a_out, bool lds) {
+  const dim3 grid((p.width + kDenoiseTileX - 1u) / kDenoiseTileX, (p.height + kDenoiseTileY - 1u) / kDenoiseTileY);
+  if (lds && p.step <= kDenoiseMaxLdsStep) hipLaunchKernelGGL(k_denoise_atrous<true>, grid, dim3(256), 0, s, p, a_in, rec_b, a_out);
+  else hipLaunchKernelGGL(k_denoise_atrous<false>, grid, dim3(256), 0, s, p, a_in, rec_b, a_out);
+}
+static void denoise_finish(uint32_t grid, hipStream_t s, const DenoiseArgs& p, const float4* rec_a, const float* guides, float* image) {
+  hipLaunchKernelGGL(k_denoise_finish, dim3(grid), dim3(256), 0, s, p, rec_a, guides, image);
+}
 
 static const WavefrontKernels kTable = {LUM_FLAVOUR_NAME, (uint32_t) kTraceBlock, set_ray_kernel_lds, init_sampler_seeds, sobol_table, generate,    generate_adaptive, trace,  sky_inscattering, shade,
                                         shade_debug,      sky,              light_query,        shadow_rays, resolve, resolve_reuse, resolve_listed, resolve_ended, LUM_FAST && !LUM_SHADE_STAGED, volume_inscatter, volume_resolve, volume_events, volume_bounce, trace_particles, particle_shade, trace_ocean, ocean_shade, clouds_list, clouds_march, clouds, trace_rays,
-                                        camera_rays};
+                                        camera_rays,      guide,            guide_normalise,    denoise_prepare, denoise_atrous, denoise_finish};
 
 }  // namespace table
 LUM_NS_END

@@ -58,6 +58,8 @@ struct LuminaryHost {
   uint32_t num_pixels = 0;
   uint32_t accumulated_samples = 0;  // uniform rendering: samples per pixel; adaptive rendering: executions (the reference's sample count)
   bool adaptive_active = false;      // the accumulation is driven by lumc_adaptive_* (luminary_ext_render with adaptive sampling enabled)
+  LuminaryDenoiserSettings denoiser = {false, 4u, 5u, 4.0f, 128.0f, 1.0f};  // luminary_ext_set_denoiser
+  bool guides_valid = false;         // the main context holds the denoiser's guides of the current accumulation
   bool hdri_origin_pending = true;   // the next scene build re-bakes the sky panorama from the camera's position (SCENE_DIRTY_FLAG_HDRI)
   lum::OutputStore outputs;
   double render_seconds = 0.0;
@@ -102,6 +104,7 @@ void invalidate(LuminaryHost* h, uint32_t dirty = LUMC_DIRTY_ALL) {
   // normalised by the stale per-block sample counts.
   if (h->adaptive_active) h->num_pixels = 0;
   h->device_scene_valid = false; h->core_scene_valid = false; h->accumulated_samples = 0; h->adaptive_active = false;
+  h->guides_valid = false;
   for (auto& slot : h->devices) { slot.scene_valid = false; slot.dirty |= dirty; }
   { std::lock_guard<std::mutex> l(h->worker_mutex); h->async_failed = false; }  // the edit may have repaired what failed
   h->worker_cv.notify_all();
@@ -409,6 +412,7 @@ LuminaryResult luminary_host_start_new_render(LuminaryHost* host) {
   {
     ApiLock lock(host);
     host->accumulated_samples = 0;
+    host->guides_valid = false;
     host->render_seconds = 0.0;
     host->adaptive_active = false;
     if (host->core && host->num_pixels) lumc_clear_accumulators(host->core);
@@ -836,10 +840,24 @@ std::vector<PreviewState> preview_schedule(LuminaryHost* h) {
 // sample count of one. Returns the parameters to hand to lumc_generate_output*.
 // device_post_apply (device/device_post.c:204-226), run between the result image and the display chain: bloom, for beauty images of
 // the whole frame in the default shading mode
+// The denoiser on the main context's result image (lumc_denoise). Its guides are rendered once per accumulation: whatever restarts the integration
+// drops them (invalidate and the other places that zero accumulated_samples).
+int denoise_result(LuminaryHost* h) {
+  if (!h->guides_valid || !lumc_has_guides(h->core)) {
+    if (lumc_render_guides(h->core, h->denoiser.guide_samples, nullptr)) return 1;
+    h->guides_valid = true;
+  }
+  LumDenoiseParams dp;
+  dp.iterations = h->denoiser.iterations; dp.sigma_luminance = h->denoiser.sigma_luminance; dp.sigma_normal = h->denoiser.sigma_normal;
+  dp.sigma_depth = h->denoiser.sigma_depth; dp.uniform_samples = h->adaptive_active ? 0u : h->accumulated_samples;
+  return lumc_denoise(h->core, &dp, nullptr, nullptr);
+}
+
 int post_process(LuminaryHost* h, PreviewState preview) {
   const LuminaryRendererSettings& st = h->scene.settings;
   if (st.shading_mode != LUMINARY_SHADING_MODE_DEFAULT || st.adaptive_sampling_output_mode != LUMINARY_ADAPTIVE_SAMPLING_OUTPUT_MODE_BEAUTY) return 0;
   if (!(st.region_width >= 1.0f && st.region_height >= 1.0f)) return 0;
+  if (h->denoiser.enabled && preview.stage == 0 && denoise_result(h)) return 1;  // result image -> denoise -> bloom; never the coarse preview images
   const float blend = h->scene.camera.bloom_blend;
   if (!(blend > 0.0f)) return 0;  // device_post_update, device_post.c:186-202
   const LumDeviceSceneView& v = h->device_scene.view;
@@ -967,6 +985,7 @@ LuminaryResult render_samples_locked(LuminaryHost* host, const uint32_t* pixels,
     if (!all) host->pixels.assign(pixels, pixels + num_pixels);
     host->num_pixels = all ? v.width * v.height : num_pixels;
     host->accumulated_samples = 0;
+    host->guides_valid = false;
     if (handoff) {
       for (uint32_t k = 0; k < want_n; k++)
         if (lumc_accumulators_from_frame(cores[k], host->core)) { std::fprintf(stderr, "[luminary_amd] %s\n", lumc_last_error(cores[k])); return LUMINARY_ERROR_CUDA; }
@@ -1041,6 +1060,7 @@ LuminaryResult render_locked(LuminaryHost* host, uint32_t num_samples, uint32_t 
         host->pixels_all = true;
         host->num_pixels = host->device_scene.view.width * host->device_scene.view.height;
         host->accumulated_samples = 0;
+    host->guides_valid = false;
         host->render_seconds = 0.0;
         bool ran = false;
         const LuminaryResult rp = render_first_sample_as_preview(host, &ran);
@@ -1088,6 +1108,7 @@ LuminaryResult render_locked(LuminaryHost* host, uint32_t num_samples, uint32_t 
     host->pixels_all = true;
     host->num_pixels = v.width * v.height;
     host->accumulated_samples = 0;
+    host->guides_valid = false;
     host->render_seconds = 0.0;
     host->handoff_preview = false;
     host->adaptive_active = true;
@@ -1193,6 +1214,39 @@ LuminaryResult luminary_ext_get_radiance(LuminaryHost* host, float* rgb, uint32_
   for (size_t p = 0; p < host->num_pixels; p++)
     for (int c = 0; c < 3; c++) rgb[3 * p + c] = fm[(size_t) c * host->num_pixels + p] * norm;
   if (sample_count) *sample_count = host->accumulated_samples;
+  return LUMINARY_SUCCESS;
+}
+LuminaryResult luminary_ext_set_denoiser(LuminaryHost* host, const LuminaryDenoiserSettings* settings) {
+  CHECK_NULL(host); CHECK_NULL(settings);
+  if (settings->guide_samples == 0 || settings->guide_samples > 1024 || settings->iterations > 6 || !(settings->sigma_luminance > 0.0f) || !(settings->sigma_normal >= 0.0f) ||
+      !(settings->sigma_depth > 0.0f))
+    return LUMINARY_ERROR_INVALID_API_ARGUMENT;
+  ApiLock lock(host);
+  if (settings->guide_samples != host->denoiser.guide_samples) host->guides_valid = false;
+  host->denoiser = *settings;  // changes how the accumulated frame is shown, like an output-only camera edit: the integration goes on
+  return LUMINARY_SUCCESS;
+}
+LuminaryResult luminary_ext_get_denoiser(LuminaryHost* host, LuminaryDenoiserSettings* settings) {
+  CHECK_NULL(host); CHECK_NULL(settings);
+  ApiLock lock(host);
+  *settings = host->denoiser;
+  return LUMINARY_SUCCESS;
+}
+LuminaryResult luminary_ext_get_denoised(LuminaryHost* host, float* rgb, uint32_t width, uint32_t height) {
+  CHECK_NULL(host); CHECK_NULL(rgb);
+  ApiLock lock(host);
+  if (!host->core || !host->pixels_all || host->num_pixels == 0 || host->accumulated_samples == 0) return LUMINARY_ERROR_API_EXCEPTION;
+  const LumDeviceSceneView& v = host->device_scene.view;
+  if (width != v.width || height != v.height) return LUMINARY_ERROR_INVALID_API_ARGUMENT;
+  if (host->partition_n > 1) { const LuminaryResult ra = assemble_partition(host); if (ra) return ra; }
+  if (lumc_generate_result(host->core, 0, 0, host->adaptive_active ? 0u : host->accumulated_samples, 1.0f, nullptr, nullptr, nullptr) || denoise_result(host)) {
+    std::fprintf(stderr, "[luminary_amd] %s\n", lumc_last_error(host->core));
+    return LUMINARY_ERROR_CUDA;
+  }
+  std::vector<float> planes(3 * (size_t) host->num_pixels);
+  if (lumc_download_result_image(host->core, planes.data())) return LUMINARY_ERROR_CUDA;
+  for (size_t p = 0; p < host->num_pixels; p++)
+    for (int c = 0; c < 3; c++) rgb[3 * p + c] = planes[(size_t) c * host->num_pixels + p];
   return LUMINARY_SUCCESS;
 }
 LuminaryResult luminary_ext_get_ray_counters(LuminaryHost* host, uint64_t out[8]) {

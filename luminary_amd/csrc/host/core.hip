@@ -136,6 +136,13 @@ struct LumContext {
   std::vector<uint32_t> sky_hdri_key;  // what the bake was made from (sky parameters, origin, dim, samples): an unchanged key reuses it
   float* d_frame_result = nullptr;  // mean radiance planes of lumc_generate_result [3 * W * H]
   uint32_t frame_result_pixels = 0;
+  // denoiser (dev_denoise.h): the guide planes (9 while they are summed, then albedo[3] normal[3] depth), the filter's records (A twice: ping-pong, B once)
+  float* d_guides = nullptr;
+  uint32_t guide_pixels = 0;
+  bool guides_valid = false;
+  void* d_denoise_rec[3] = {nullptr, nullptr, nullptr};
+  uint32_t denoise_pixels = 0;
+  int denoise_lds = 1;              // a-trous steps 1 and 2 stage their tile in LDS (lumc_set_denoise_form; LUM_DENOISE_LDS=0|1)
   // ray ordering (N1): keys + permutation, double-buffered for hipcub's radix sort; sized for the visibility items (4 per path)
   bool sync_debug = false;
   int sort_mode = 0;              // 0 queue order, 1 closest-hit rays of depth >= 1 traced through a sorted permutation, 2 visibility rays too, 3 the path queue physically reordered (lumc_set_ray_sorting, LUM_SORT)
@@ -645,6 +652,7 @@ int lumc_context_create(int device_ordinal, LumContext** out) {
   if (const char* e = getenv("LUM_SHADE_GRID")) ctx->shade_grid_rounds = (uint32_t) atoi(e);
   if (const char* e = getenv("LUM_SOBOL_TABLE_RT")) ctx->sobol_table = atoi(e) != 0 ? 1 : 0;
   if (const char* e = getenv("LUM_FUSED_ENDED")) ctx->fused_ended = ctx->fused_ended_default = (LUM_SHADE_DYNAMIC && atoi(e) != 0) ? 1 : 0;
+  if (const char* e = getenv("LUM_DENOISE_LDS")) ctx->denoise_lds = atoi(e) != 0 ? 1 : 0;
   if (const char* f = getenv("LUM_FLAVOUR")) ctx->wf = (std::strcmp(f, "exact") == 0) ? wavefront_kernels_exact() : wavefront_kernels_fast();
   *out = ctx;
   int count = 0;
@@ -680,6 +688,8 @@ void lumc_context_destroy(LumContext* ctx) {
   if (ctx->d_argb8) (void) hipFree(ctx->d_argb8);
   if (ctx->d_counters) (void) hipFree(ctx->d_counters);
   if (ctx->d_frame_result) (void) hipFree(ctx->d_frame_result);
+  if (ctx->d_guides) (void) hipFree(ctx->d_guides);
+  for (void* r : ctx->d_denoise_rec) if (r) (void) hipFree(r);
   if (ctx->d_gather_send) (void) hipFree(ctx->d_gather_send);
   if (ctx->d_gather_recv) (void) hipFree(ctx->d_gather_recv);
   if (ctx->d_gather_pixels) (void) hipFree(ctx->d_gather_pixels);
@@ -1109,6 +1119,7 @@ static int build_particle_tree(LumContext* ctx, const LumDeviceSceneView* v, Dev
 // The scene on the device, part by part (lumc_scene_update). Every part frees what it allocated before; parts that are not dirty keep their device
 // arrays and the fields of ctx->scene that point at them.
 static int scene_update(LumContext* ctx, const LumDeviceSceneView* v, unsigned dirty) {
+  ctx->guides_valid = false;  // the denoiser's guides were rendered from the scene as it was
   DeviceScene& sc = ctx->scene;
   if (!v->bluenoise_2d) { ctx->error = "scene has no blue-noise mask"; return 1; }
   if (v->max_ray_depth > 63) { ctx->error = "max_ray_depth exceeds 63 (6-bit field, device_structs.h:9)"; return 1; }
@@ -2485,6 +2496,13 @@ int lumc_generate_result_undersampled_host(LumContext* ctx, uint32_t stage, uint
   return 0;
 }
 
+int lumc_download_result_image(LumContext* ctx, float* result) {
+  if (!ctx || !result || !ctx->d_frame_result || !ctx->has_scene || ctx->frame_result_pixels != ctx->scene.width * ctx->scene.height) { if (ctx) ctx->error = "lumc_download_result_image: no result image"; return 1; }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipDeviceSynchronize());
+  HIP_TRY(ctx, hipMemcpy(result, ctx->d_frame_result, sizeof(float) * 3 * (size_t) ctx->frame_result_pixels, hipMemcpyDeviceToHost));
+  return 0;
+}
 const float* lumc_result_image(LumContext* ctx) { return ctx ? ctx->d_frame_result : nullptr; }
 
 // _device_post_bloom_apply, device/device_post.c:56-139
@@ -2538,6 +2556,136 @@ int lumc_post_bloom_host(LumContext* ctx, float* image, uint32_t full_width, uin
       hipDeviceSynchronize() == hipSuccess && hipMemcpy(image, d, bytes, hipMemcpyDeviceToHost) == hipSuccess)
     rc = 0;
   else if (ctx->error.empty()) ctx->error = "lumc_post_bloom_host: transfer failed";
+  (void) hipFree(d);
+  return rc;
+}
+
+// ---- denoiser (dev_denoise.h) ----
+int lumc_render_guides(LumContext* ctx, uint32_t num_samples, void* stream_) {
+  if (!ctx || !ctx->has_scene) { if (ctx) ctx->error = "lumc_render_guides: no scene"; return 1; }
+  if (num_samples == 0) num_samples = 4;
+  if (num_samples > 1024u) { ctx->error = "lumc_render_guides: at most 1024 guide samples"; return 1; }
+  hipStream_t stream = (hipStream_t) stream_;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  DeviceScene sc = ctx->scene;
+  sc.sobol_table = nullptr;
+  const uint32_t n = sc.width * sc.height;
+  if (n == 0 || sc.width > 0xFFFFu || sc.height > 0xFFFFu) { ctx->error = "lumc_render_guides: frame size"; return 1; }
+  ctx->guides_valid = false;
+  if (ctx->guide_pixels != n) {
+    if (ctx->d_guides) (void) hipFree(ctx->d_guides);
+    ctx->d_guides = nullptr; ctx->guide_pixels = 0;
+    HIP_TRY(ctx, hipMalloc((void**) &ctx->d_guides, sizeof(float) * kGuideSumPlanes * (size_t) n));
+    ctx->guide_pixels = n;
+  }
+  if (ensure_work(ctx, n)) return 1;
+  HIP_TRY(ctx, hipMemsetAsync(ctx->d_guides, 0, sizeof(float) * kGuideSumPlanes * (size_t) n, stream));
+  const WavefrontKernels& wf = *ctx->wf;
+  const size_t lds_dyn = (size_t) ctx->lds_nodes * kNodeBytes + LUM_LDS_STACK_BYTES;
+  // one sample id of every pixel per pass: the closest-hit pass of the debug shading modes (wavefront_depths), then k_guide adds into the planes
+  for (uint32_t s = 0; s < num_samples; s++) {
+    PassParams pp{nullptr, n, 1u, s};
+    HIP_TRY(ctx, hipMemsetAsync(ctx->d_ctrl, 0, sizeof(uint32_t) * kCtlStride * (sc.max_ray_depth + 2), stream));
+    {
+      Launch l(ctx, stream, LUMC_KERNEL_GENERATE);
+      wf.generate(grid_for(n), stream, sc, pp, ctx->queue[0], ctx->d_results, ctx->d_ctrl + kCtlPaths, ctx->lens, ctx->camera);
+    }
+    {
+      Launch l(ctx, stream, LUMC_KERNEL_TRACE);
+      wf.trace(grid_persistent(ctx, n), lds_dyn, stream, sc, ctx->queue[0], nullptr, ctx->d_ctrl, ctx->d_counters, ctx->lds_nodes);
+    }
+    if (sc.particles_active) trace_particles(ctx, stream, ctx->queue[0], ctx->d_ctrl, n);
+    if (sc.ocean_active) {
+      Launch l(ctx, stream, LUMC_KERNEL_TRACE);
+      wf.trace_ocean(grid_for(n), stream, sc, ctx->queue[0], (const uint32_t*) ctx->d_ctrl);
+    }
+    Launch l(ctx, stream, LUMC_KERNEL_OUTPUT);
+    wf.guide(grid_for(n), stream, sc, ctx->queue[0], (const uint32_t*) ctx->d_ctrl, ctx->d_guides, n);
+  }
+  {
+    Launch l(ctx, stream, LUMC_KERNEL_OUTPUT);
+    wf.guide_normalise(grid_for(n), stream, ctx->d_guides, n, num_samples);
+  }
+  HIP_TRY(ctx, hipGetLastError());
+  ctx->guides_valid = true;
+  return 0;
+}
+
+int lumc_download_guides(LumContext* ctx, float* albedo, float* normal, float* depth) {
+  if (!ctx || !ctx->guides_valid) { if (ctx) ctx->error = "lumc_download_guides: no guides (lumc_render_guides)"; return 1; }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipDeviceSynchronize());
+  const size_t n = ctx->guide_pixels;
+  if (albedo) HIP_TRY(ctx, hipMemcpy(albedo, ctx->d_guides, sizeof(float) * 3 * n, hipMemcpyDeviceToHost));
+  if (normal) HIP_TRY(ctx, hipMemcpy(normal, ctx->d_guides + 3 * n, sizeof(float) * 3 * n, hipMemcpyDeviceToHost));
+  if (depth) HIP_TRY(ctx, hipMemcpy(depth, ctx->d_guides + 6 * n, sizeof(float) * n, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int lumc_has_guides(const LumContext* ctx) { return (ctx && ctx->guides_valid) ? 1 : 0; }
+
+void lumc_denoise_default_params(LumDenoiseParams* p) {
+  if (!p) return;
+  p->iterations = 5; p->sigma_luminance = 4.0f; p->sigma_normal = 128.0f; p->sigma_depth = 1.0f; p->uniform_samples = 0;
+}
+
+int lumc_set_denoise_form(LumContext* ctx, int lds) {
+  if (!ctx) return 1;
+  ctx->denoise_lds = lds != 0 ? 1 : 0;
+  return 0;
+}
+
+int lumc_denoise(LumContext* ctx, const LumDenoiseParams* params, float* d_image, void* stream_) {
+  if (!ctx || !params || !ctx->has_scene) { if (ctx) ctx->error = "lumc_denoise: no scene or null argument"; return 1; }
+  const uint32_t n = ctx->scene.width * ctx->scene.height;
+  if (!ctx->guides_valid || ctx->guide_pixels != n) { ctx->error = "lumc_denoise: no guides for this frame (lumc_render_guides)"; return 1; }
+  const bool framed = ctx->use_frame && ctx->d_frame && ctx->frame_capacity == n;
+  if (!framed && (!ctx->d_first_moment || ctx->d_pixels || ctx->num_pixels != n)) { ctx->error = "lumc_denoise: needs the full-frame accumulators"; return 1; }
+  if (!d_image) d_image = (ctx->frame_result_pixels == n) ? ctx->d_frame_result : nullptr;
+  if (!d_image) { ctx->error = "lumc_denoise: no image"; return 1; }
+  if (!ctx->adaptive.active && params->uniform_samples == 0) { ctx->error = "lumc_denoise: no samples"; return 1; }
+  if (!(params->sigma_luminance > 0.0f) || !(params->sigma_normal >= 0.0f) || !(params->sigma_depth > 0.0f)) { ctx->error = "lumc_denoise: sigmas must be positive"; return 1; }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t stream = (hipStream_t) stream_;
+  if (ctx->denoise_pixels != n) {
+    for (void*& r : ctx->d_denoise_rec) { if (r) (void) hipFree(r); r = nullptr; }
+    ctx->denoise_pixels = 0;
+    for (void*& r : ctx->d_denoise_rec) HIP_TRY(ctx, hipMalloc(&r, 16 * (size_t) n));
+    ctx->denoise_pixels = n;
+  }
+  const float* src_fm = framed ? ctx->d_frame : ctx->d_first_moment;
+  const float* src_sm = framed ? ctx->d_frame + 3 * (size_t) n : ctx->d_second_moment;
+  AdaptiveView view;
+  std::memset(&view, 0, sizeof(view));
+  if (ctx->adaptive.active) view = adaptive_view(ctx);
+  DenoiseArgs args{ctx->scene.width, ctx->scene.height, 1u, params->uniform_samples, params->sigma_luminance, params->sigma_normal, params->sigma_depth};
+  const uint32_t iterations = std::min(params->iterations, 6u);
+  float4* rec_a[2] = {(float4*) ctx->d_denoise_rec[0], (float4*) ctx->d_denoise_rec[1]};
+  uint4* rec_b = (uint4*) ctx->d_denoise_rec[2];
+  const WavefrontKernels& wf = *ctx->wf;
+  Launch l(ctx, stream, LUMC_KERNEL_OUTPUT);
+  wf.denoise_prepare(grid_for(n), stream, view, args, src_fm, src_sm, d_image, ctx->d_guides, rec_a[0], rec_b);
+  uint32_t cur = 0;
+  for (uint32_t i = 0; i < iterations; i++, cur ^= 1u) {
+    args.step = 1u << i;
+    wf.denoise_atrous(stream, args, rec_a[cur], rec_b, rec_a[cur ^ 1u], ctx->denoise_lds != 0);
+  }
+  wf.denoise_finish(grid_for(n), stream, args, rec_a[cur], ctx->d_guides, d_image);
+  HIP_TRY(ctx, hipGetLastError());
+  return 0;
+}
+
+int lumc_denoise_host(LumContext* ctx, const LumDenoiseParams* params, float* image) {
+  if (!ctx || !image || !ctx->has_scene) { if (ctx) ctx->error = "lumc_denoise_host: null argument"; return 1; }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const size_t bytes = sizeof(float) * 3 * (size_t) ctx->scene.width * ctx->scene.height;
+  float* d = nullptr;
+  HIP_TRY(ctx, hipMalloc((void**) &d, bytes));
+  int rc = 1;
+  if (hipMemcpy(d, image, bytes, hipMemcpyHostToDevice) == hipSuccess && lumc_denoise(ctx, params, d, nullptr) == 0 && hipDeviceSynchronize() == hipSuccess &&
+      hipMemcpy(image, d, bytes, hipMemcpyDeviceToHost) == hipSuccess)
+    rc = 0;
+  else if (ctx->error.empty()) ctx->error = "lumc_denoise_host: transfer failed";
   (void) hipFree(d);
   return rc;
 }
@@ -2714,6 +2862,7 @@ int lumc_pixel_query(LumContext* ctx, uint32_t x, uint32_t y, uint32_t sample_id
 
 int lumc_set_physical_camera(LumContext* ctx, const LumPhysicalCamera* c) {
   if (!ctx) return 1;
+  ctx->guides_valid = false;
   if (!c) { ctx->camera = kCamThinLens; return 0; }
   if (c->num_interfaces == 0 || c->num_interfaces > LUMC_LENS_MAX_INTERFACES) { ctx->error = "lumc_set_physical_camera: 1 ... 24 interfaces"; return 1; }
   const uint32_t n = c->num_interfaces;

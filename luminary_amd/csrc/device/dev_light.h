@@ -526,19 +526,6 @@ LUM_DEV float light_direction_probability_terms(const MatParams& p, V3 Vl, const
 // ---- light sampling (light.cuh:84-159) ----
 struct LightSample { uint32_t light_id; V3 ray; Col color; float dist, root_sum; };
 
-// Measurement switch LUM_DUP (bit mask; profiles/r06_ab_experiments.txt "what the parts of k_shade cost"): the named part of a vertex's work is done TWICE - the second time
-// on inputs the compiler cannot see through, its results handed to an empty asm statement - so that the part's cost shows as the kernel's extra time while every result,
-// every path and every other kernel stay what they are. (Leaving a part OUT - the LUM_ABLATE switches - also removes whatever only it kept alive, and changes the paths.)
-//   1 the light tree's root pass   2 the candidate loop   4 the surface context   8 the bounce sample   16 the BSDF-driven light direction   32 the local frame
-#ifndef LUM_DUP
-#define LUM_DUP 0
-#endif
-LUM_DEV void dup_sink(float x) { asm volatile("" :: "v"(x)); }
-LUM_DEV void dup_sink(uint32_t x) { asm volatile("" :: "v"(x)); }
-LUM_DEV void dup_sink(V3 a) { asm volatile("" :: "v"(a.x), "v"(a.y), "v"(a.z)); }
-LUM_DEV void dup_sink(Col a) { asm volatile("" :: "v"(a.r), "v"(a.g), "v"(a.b)); }
-LUM_DEV GeoContext dup_launder(GeoContext g) { asm volatile("" : "+v"(g.position.x), "+v"(g.position.y), "+v"(g.position.z), "+v"(g.normal.x), "+v"(g.V.x)); return g; }
-
 template <class Smp>
 LUM_DEV LightSample light_candidates(const DeviceScene& sc, const GeoContext& g, const Smp& smp, ShadeClock& clock, const StagedLights& staged, const TreeWork& work,
                                      const Energy& energy);
@@ -546,20 +533,8 @@ template <class Smp>
 LUM_DEV LightSample sample_light(const DeviceScene& sc, const GeoContext& g, const Smp& smp, ShadeClock& clock, const StagedLights& staged) {
   LUM_STAT(14, 15);
   const TreeWork work = tree_prepass(sc, g, smp);
-  if (LUM_DUP & 1) {
-    const TreeWork again = tree_prepass(sc, dup_launder(g), smp);
-#pragma unroll
-    for (uint32_t l = 0; l < kLightTreeOutputs; l++) dup_sink(again.cont[l]);
-    dup_sink(again.root_sum);
-  }
   const Energy energy = energy_terms(sc, g.params, world_ndotv(g));
   LUM_LAP(clock, 1);
-  if (LUM_DUP & 2) {
-    TreeWork w2 = work;
-    asm volatile("" : "+v"(w2.cont[0]), "+v"(w2.root_sum));
-    const LightSample again = light_candidates(sc, dup_launder(g), smp, clock, staged, w2, energy);
-    dup_sink(again.light_id); dup_sink(again.ray); dup_sink(again.color); dup_sink(again.dist);
-  }
   return light_candidates(sc, g, smp, clock, staged, work, energy);
 }
 template <class Smp>
@@ -576,21 +551,9 @@ LUM_DEV LightSample light_candidates(const DeviceScene& sc, const GeoContext& g,
 #ifndef LUM_ABLATE_LANES
 #define LUM_ABLATE_LANES kLightTreeOutputs  // measurement only: fewer resampling lanes evaluated (results are wrong)
 #endif
-  // Experiment (LUM_PREFETCH_RANDOM): a candidate's random pair is a table word and a blue-noise texel - two gathers the iteration waits for right at its top. With the
-  // switch the pair of candidate l + 1 is requested while candidate l is worked on (the raw integers: two registers live across the loop body).
-#ifndef LUM_PREFETCH_RANDOM
-#define LUM_PREFETCH_RANDOM 0
-#endif
-#if LUM_PREFETCH_RANDOM
-  U2 next_pair = smp.raw2(kRndLightGeoRay);
-#endif
 #pragma nounroll
   for (uint32_t lane = 0; lane < LUM_ABLATE_LANES; lane++) {
     LUM_STAT(8, 9);
-#if LUM_PREFETCH_RANDOM
-    const U2 this_pair = next_pair;
-    next_pair = smp.raw2(kRndLightGeoRay + min(lane + 1u, (uint32_t) kLightTreeOutputs - 1u));
-#endif
     const TreePick pick = tree_postpass(sc, g, smp, lane, work);
     if (pick.light_id == kLightIdInvalid) continue;
 #if LUM_LDS_LIGHTS
@@ -603,11 +566,7 @@ LUM_DEV LightSample light_candidates(const DeviceScene& sc, const GeoContext& g,
     const TriLight& tl = entry.tri;
     if (handle.x == g.instance_id && handle.y == g.tri_id) continue;
     V3 ray; float sa;
-#if LUM_PREFETCH_RANDOM
-    const F2 pair = F2{unit_float(this_pair.x), unit_float(this_pair.y)};
-#else
     const F2 pair = smp.next2(kRndLightGeoRay + lane);
-#endif
     if (!sample_tri_solid_angle(g.position, tl, pair, ray, sa)) continue;
     F2 uv;
     const float dist = intersect_triangle(tl.vertex, tl.edge1, tl.edge2, g.position, ray, uv);

@@ -22,61 +22,7 @@ struct alignas(128) Bvh4Node {
 };
 static_assert(sizeof(Bvh4Node) == 128, "BVH4 node must be one cache line");
 
-// 8-wide node with quantised child boxes, the format of the scene's and the particles' trees when LUM_BVH8 is on (the light tree keeps 4-wide
-// nodes). Same 128-byte slot, same child words. Child j's box = origin + q * 2^(e - 127) per axis, lower corners rounded down, upper up.
-// Experiment, measured negative and therefore off (profiles/r02_ab_experiments.txt): node visits per ray fall by 22 % (hall 16.4 -> 12.7), but a visit
-// costs 2.8 x the VALU work (48 byte->float conversions, a 19-comparator sort) and the ray kernels are as much issue- as latency-limited at 4 waves
-// per SIMD: closest-hit +9 %, visibility +10 % time on the hall. Parity tests pass with it on.
-#ifndef LUM_BVH8
-#define LUM_BVH8 0
-#endif
-struct alignas(128) Bvh8Node {
-  float origin[3];
-  uint8_t exp[3], pad0;   // biased exponents of the per-axis scale
-  uint32_t child[8];
-  uint8_t lo_x[8], lo_y[8], lo_z[8], hi_x[8], hi_y[8], hi_z[8];
-  uint32_t pad[8];
-};
-static_assert(sizeof(Bvh8Node) == 128, "BVH8 node must be one cache line");
-
-// 8-wide node with its children in OCTANT SLOTS (LUM_BVH8O; after Ylitie, Karras, Laine: "Efficient Incoherent Ray Traversal on GPUs Through Compressed
-// Wide BVHs", HPG 2017 - the format of the reference's own, unused software traversal: node src/luminary/utils.h:123-138, slot assignment bvh.c:1093-1145,
-// traversal order cuda/bvh.cuh:82-106). The builder puts the child whose centre lies towards octant direction s (bit a set: the +a side of the node's
-// centre) into slot s; a ray whose direction signs are `oct` (bit a set: d_a < 0) meets the slots roughly front to back in the order s ^ oct = 0 ... 7, so
-// a visit needs no distances, no sort and ONE stack entry (the group of children still to be walked) instead of up to seven. 80 bytes of a 128-byte slot:
-//   16 B  origin xyz | biased exponents of the per-axis scale x, y, z | imask (bit s: slot s holds an inner node)
-//   16 B  child_base (the inner children are consecutive nodes, in slot order) | leaf_base | meta[8]: leaf slot s = offset (5 bits) | count - 1 (2 bits):
-//         its primitives are leaf_base + offset ... (the builder reorders the triangles / top-level leaf records node by node); other slots 0
-//   48 B  lo_x[8] lo_y[8] | lo_z[8] hi_x[8] | hi_y[8] hi_z[8]: one byte per slot, child box = origin + q * 2^(e - 127), rounded outwards; empty slots hold
-//         inverted boxes (lo 255, hi 0) and are never entered
-#ifndef LUM_BVH8O
-#define LUM_BVH8O 0
-#endif
-struct alignas(128) Bvh8oNode {
-  float origin[3];
-  uint8_t exp[3], imask;
-  uint32_t child_base, leaf_base;
-  uint8_t meta[8];
-  uint8_t lo_x[8], lo_y[8], lo_z[8], hi_x[8], hi_y[8], hi_z[8];
-  uint32_t pad[12];
-};
-static_assert(sizeof(Bvh8oNode) == 128, "one slot");
-
-// 4-wide node with quantised child boxes in half a cache line (LUM_BVH4Q): same tree, same node indices, same child words as Bvh4Node; child j's box =
-// origin + q * 2^(e - 127) per axis, lower corners rounded down, upper up (the boxes only grow). A visit fetches 64 instead of 112 bytes and the LDS
-// holds twice the nodes; it pays with 24 byte->float conversions. Scene and particle trees; the light tree keeps float boxes.
-#ifndef LUM_BVH4Q
-#define LUM_BVH4Q 0
-#endif
-struct alignas(64) Bvh4QNode {
-  float origin[3];
-  uint8_t exp[3], pad0;   // biased exponents of the per-axis scale
-  uint32_t child[4];
-  uint8_t lo_x[4], lo_y[4], lo_z[4], hi_x[4], hi_y[4], hi_z[4];
-  uint32_t pad[2];
-};
-static_assert(sizeof(Bvh4QNode) == 64, "quantised BVH4 node must be half a cache line");
-constexpr uint32_t kNodeBytes = LUM_BVH4Q ? 64u : 128u, kNodeShift = LUM_BVH4Q ? 6u : 7u;
+constexpr uint32_t kNodeBytes = 128u, kNodeShift = 7u;
 
 constexpr uint32_t kBvhEmpty      = 0xFFFFFFFFu;
 constexpr uint32_t kBvhLeafBit    = 0x80000000u;
@@ -102,10 +48,6 @@ constexpr uint32_t kBvhTriNoTexture = 0xFFFFFFFFu;
 // fetches - the triangle's material id, then the material - before the ray may stop)
 constexpr uint32_t kBvhTriOpaque = 0xFFFFFFFEu;
 static_assert(sizeof(BvhTri) == 48, "48 bytes per triangle");
-
-#ifndef LUM_PHASE_QUEUES
-#define LUM_PHASE_QUEUES 0  // 1: k_trace / k_shadow_rays keep their rays in per-wave LDS pools and regroup them by phase (dev_trace_pool.h)
-#endif
 
 struct DeviceScene {
   // geometry
@@ -199,12 +141,6 @@ struct DeviceScene {
   const BvhTri* particle_tris;
   const float4* particle_leaves;
   uint32_t particle_tlas_num_nodes, particle_num_leaves;
-#if LUM_PHASE_QUEUES
-  // dev_trace_pool.h: per workgroup of the persistent ray kernels and per pool slot, what does not fit LDS - 4 x 16 bytes of query state, the stack
-  // entries beyond the LDS ones. Only the variant build carries the fields (tools/check_variants.sh compiles it).
-  uint4* pool_state;
-  unsigned long long* pool_stack;
-#endif
   // the pass's Sobol / Owen table (dev_sampler.h LUM_SOBOL_TABLE, k_sobol_table): entry (dimension, sample) at [dimension * sobol_stride + (sample - sobol_first)],
   // dimensions 0 .. (max_ray_depth + 1) * kRndTargetCount - 1; nullptr in passes without one (set per pass on the host's copy, wavefront_depths)
   const uint2* sobol_table;
@@ -322,7 +258,7 @@ enum SkyMode : uint32_t { kSkyDefault = 0, kSkyHdri = 1, kSkyConstantColor = 2 }
 // One row per depth. The three words k_shade's waves bump with an atomic per 64 vertices (survivors of the NEXT row, visibility items, light
 // queries) sit on 128-byte lines of their own: a single word takes ~88 atomics per microsecond (MI355X_MICROARCH.md, "dequeue"), and with all
 // three on one line the shade kernel was bound by that (measured: spreading them took 13 % off k_shade). The work cursors of the persistent
-// ray kernels have a line each as well (8 words: LUM_XCD_RANGES experiment; word 0 alone otherwise).
+// ray kernels have a line each as well (8 words apart; word 0 alone is used).
 #ifndef LUM_CTL_LINE
 #define LUM_CTL_LINE 32u  // words between the hot counters (32 words = 128 bytes)
 #endif
@@ -334,23 +270,10 @@ enum CtrlWord : uint32_t {
   kCtlVolumeItems = 2u * LUM_CTL_LINE + 2u,
   kCtlParticleCursor = LUM_CTL_LINE + 8u,  // work cursor of the particle pass of the closest-hit kernel (8 words, like the other cursors)
   kCtlCloudItems = 2u * LUM_CTL_LINE + 3u, kCtlCloudCursor = LUM_CTL_LINE + 24u,  // the cloud marches of a depth: their number and the persistent kernel's cursor
-  kCtlShadeCursor = 3u * LUM_CTL_LINE + 16u  // k_shade's input cursor (LUM_SHADE_DYNAMIC, kernels.h): its waves take the depth's queue entries in chunks
+  kCtlShadeCursor = 3u * LUM_CTL_LINE + 16u  // k_shade's input cursor (kernels.h): its waves take the depth's queue entries in chunks
 };
 static_assert(LUM_CTL_LINE >= 32u, "the fog's control words sit in the second half of the 32-word lines");
 
-#if LUM_PHASE_QUEUES
-#ifndef LUM_TRACE_BLOCK
-#define LUM_TRACE_BLOCK 1024
-#endif
-#ifndef LUM_POOL_SLOTS
-#define LUM_POOL_SLOTS 128  // rays per wave (<= 256: list entries are bytes)
-#endif
-#ifndef LUM_POOL_STACK_ENTRIES
-#define LUM_POOL_STACK_ENTRIES 2  // 8-byte stack entries per slot kept in LDS
-#endif
-// per slot: the LDS part of its stack, three 16-byte state words, one byte in each of the wave's four lists
-#define LUM_LDS_STACK_BYTES ((LUM_POOL_STACK_ENTRIES * 8u + 48u + 4u) * LUM_POOL_SLOTS * (LUM_TRACE_BLOCK / 64u))
-#endif
 #ifndef LUM_LDS_STACK_BYTES
 // Of a ray workgroup's LDS: bytes that hold the oldest entries of its lanes' traversal stacks instead of tree nodes (0: stacks in scratch). Rounds 2-5: 64 KB (8 closest-hit /
 // 16 visibility entries per lane beside 704 staged nodes; round 3 measured 96 KB at 0 / +1 %). Round 6, with the deeper two-triangle-leaf trees: 96 KB (12 / 24 entries, 448 nodes) -

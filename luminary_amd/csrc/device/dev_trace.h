@@ -15,8 +15,8 @@
 // of the launch: a divergent 16-byte lane load costs it one cycle per LANE (7 per node visit that misses the staged top, 3 per triangle), whatever the number of
 // wave instructions that carry them. The kernels sit between the two: every variant that removed lane loads added instructions and became issue-bound (64-byte
 // and 8-wide quantised nodes), every variant that removed instructions per ray or filled the waves left the lane loads in place and gained nothing - round 5's
-// LDS phase queues (dev_trace_pool.h, LUM_PHASE_QUEUES) raise the lane utilisation to 0.68 / 0.76 with a third fewer vector-memory instructions at the SAME number
-// of vector instructions and run 25-80 % slower, because twice the rays per CU halve each ray's share of LDS (stack bottoms, staged nodes). Memory bandwidth is
+// LDS phase queues (retired, docs/HISTORY.md) raised the lane utilisation to 0.68 / 0.76 with a third fewer vector-memory instructions at the SAME number
+// of vector instructions and ran 25-80 % slower, because twice the rays per CU halve each ray's share of LDS (stack bottoms, staged nodes). Memory bandwidth is
 // not the limit (0.52 / 0.38 of 8 TB/s memory-side), latency as such neither (an L1->L2 read returns after ~400 cycles, a tenth of a wave iteration).
 // What an iteration costs:
 //   * (a leaf = at most two triangles, 3 x 16-byte loads each; trees: the builders' binary SAH tree cut into 4-wide nodes by a dynamic programme, bvh_build.cpp CollapsePlan)
@@ -28,10 +28,11 @@
 //   * the first nodes of the array (breadth-first across both levels; 448 of them beside 96 KB of stack bottoms since round 6, 704 beside 64 KB before) are staged in LDS by
 //     every workgroup, the oldest 12 (visibility rays: 24) stack entries of every lane live there too: LDS hit rate of the node visits 0.62 / 0.72 with the 704.
 // Structural alternatives that were built and measured, and lost (profiles/r0*_ab_experiments.txt): 8-wide quantised nodes with a sorting network (twice),
-// 64-byte quantised 4-wide nodes, dual-node visits, speculative traversal past a leaf (LUM_SPECULATE, round 4: +7 % node visits, +16-19 % time),
+// 64-byte quantised 4-wide nodes, dual-node visits, speculative traversal past a leaf (round 4: +7 % node visits, +16-19 % time),
 // physical ray reordering between bounces, per-XCD work ranges, LDS-DMA prefetch, rays regrouped by phase through LDS (round 5, above), an MFMA slab test for packets
 // (tools/microbench/mfma_slab.hip: 0.62 x the vector path). The 8-wide octant-order node (no sort, one group entry per visit) was
 // prototyped as a visit routine and a CPU walk before a rewrite (tools/microbench/node_visit.hip, tools/bvh_quality.cpp BQ_WIDE): see DESIGN.md section 4.
+// None of these is in the sources any more: docs/HISTORY.md, "Retired experiments", says what each was, what it measured and the last commit that holds it.
 #pragma once
 
 #include "dev_light.h"
@@ -67,29 +68,7 @@ constexpr int kStackSize = 128;
 #ifndef LUM_LDS_INSTANCES
 #define LUM_LDS_INSTANCES 64  // top-level leaf records (64 bytes each) a ray workgroup keeps in LDS next to the staged tree top
 #endif
-#ifndef LUM_DEFER_FINISH
-#define LUM_DEFER_FINISH 0  // 1: a finished ray's result is written when its lane takes the next ray (or at the end), not inside the phase loop (see trace_items; measured neutral)
-#endif
-#ifndef LUM_LDS_TURN
-#define LUM_LDS_TURN 0   // lanes on staged nodes get wave iterations of their own while at least this many of them exist (0: off); see the phase vote
-#endif
-#ifndef LUM_LDS_FIRST
-#define LUM_LDS_FIRST 1  // such iterations come before triangle and instance-entry phases (0: only where the node phase would have run anyway)
-#endif
-
-// Speculative traversal (after Aila, Laine: "Understanding the Efficiency of Ray Traversal on GPUs", HPG 2009): a lane that reaches a triangle leaf while
-// the wave goes on visiting nodes does not sit the node phases out. It sets the leaf aside (`postponed`, one register) and takes on the newest stack
-// entry when that is an inner node it may still have to visit; the leaf is tested when the wave's triangle phase comes. Results do not depend on the
-// order in which leaves and nodes are met (closest hits are a minimum, visibility a product / any blocker); what it can cost is visits that the
-// postponed leaf's hit would have culled. 1: closest-hit rays, 2: visibility rays, 3: both.
-#ifndef LUM_SPECULATE
-#define LUM_SPECULATE 0
-#endif
-#ifndef LUM_DUAL_VISIT
-#define LUM_DUAL_VISIT 0  // experiment, measured negative (visibility kernel +18 % on the hall): see visit_two_nodes
-#endif
 struct RayStats { uint32_t nodes, tris, lds_nodes; };
-constexpr uint32_t kPrefetchSinkWords = 64u * 16u;  // one dword per lane for up to 16 waves of a ray workgroup (LUM_PREFETCH)
 
 // Diagnostic build (-DLUM_PHASE_STATS): wave-level iteration counts of the traversal phases, to see where lanes idle.
 //   0 node-phase iterations   1 instance-entry iterations   2 lanes entering   3 triangle-phase iterations   4 lanes in them
@@ -125,20 +104,14 @@ LUM_DEV float vmin2(float a, float b) { float r; asm("v_min_f32 %0, %1, %2" : "=
 struct TRay {
   V3 o, d, inv, noi;  // noi = -(o * inv)
   uint32_t nx, ny, nz, fx, fy, fz;
-  uint32_t oct;       // direction signs, bit a set: inv_a < 0 (the octant-slot nodes of LUM_BVH8O are walked in the order slot ^ oct)
   LUM_DEV void set(V3 origin, V3 dir) {
     o = origin; d = dir;
     inv = v3(safe_inv(dir.x), safe_inv(dir.y), safe_inv(dir.z));
     noi = v3(-(origin.x * inv.x), -(origin.y * inv.y), -(origin.z * inv.z));
-    oct = (inv.x < 0.0f ? 1u : 0u) | (inv.y < 0.0f ? 2u : 0u) | (inv.z < 0.0f ? 4u : 0u);
     nx = (inv.x < 0.0f) ? 48u : 0u;  fx = 48u - nx;    // lo_x at 0, hi_x at 48
     ny = (inv.y < 0.0f) ? 64u : 16u; fy = 80u - ny;    // lo_y at 16, hi_y at 64
     nz = (inv.z < 0.0f) ? 80u : 32u; fz = 112u - nz;   // lo_z at 32, hi_z at 80
   }
-  // the same for an 8-wide quantised node (Bvh8Node, dev_scene.h): lo_x at 48, lo_y 56, lo_z 64, hi_x 72, hi_y 80, hi_z 88
-  LUM_DEV uint32_t nx8() const { return (inv.x < 0.0f) ? 72u : 48u; }
-  LUM_DEV uint32_t ny8() const { return (inv.y < 0.0f) ? 80u : 56u; }
-  LUM_DEV uint32_t nz8() const { return (inv.z < 0.0f) ? 88u : 64u; }
 };
 
 LUM_DEV float4 node_f4(const Bvh4Node* nodes, uint32_t byte_offset) {
@@ -176,31 +149,6 @@ LUM_DEV bool within(float tnear, float tmax) { return tnear <= __builtin_fmaf(tm
 // The first `lds_count` nodes of the array (the top of the tree in breadth-first order, core.hip) are staged in LDS by every
 // workgroup of the persistent ray kernels: a divergent 16-byte LDS read costs a fraction of a divergent L1 access.
 struct NodeSource { const Bvh4Node* global; const char* lds; uint32_t lds_count; };
-
-// Where the sixteen-byte word `i` of the node array sits in the staged copy. A lane reads the same word (say, the near x planes) of whatever node it
-// stands on; unswizzled, that word of every even node lies on the same four LDS banks and of every odd node on four others, so a wave's read of
-// 64 different nodes queued up on eight banks (SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE = 0.5-0.6). XOR-ing the word's position inside its node with
-// bits 1-3 of the node index spreads the same word of sixteen consecutive nodes over all 64 banks. Float-box nodes only (LUM_LDS_SWIZZLE).
-// Measured (profiles/r03_ab_experiments.txt, same box): hall 221.1 / 373.6 ms per 3 steps of the closest-hit / visibility kernel without, 222.3 / 374.0 with
-// it; scan 65.1 / 70.7 against 65.9 / 70.5 - the LDS reads are not on the kernels' critical path. Off: it costs nine instructions per staged visit.
-#ifndef LUM_LDS_SWIZZLE
-#define LUM_LDS_SWIZZLE 0
-#endif
-LUM_DEV uint32_t lds_slot_swizzle(uint32_t word_index) {
-#if LUM_LDS_SWIZZLE
-  return word_index ^ ((word_index >> 4) & 7u);  // word_index = node * 8 + slot: bits 1-3 of the node index are bits 4-6 here
-#else
-  return word_index;
-#endif
-}
-LUM_DEV uint32_t lds_node_swizzle_bytes(uint32_t node) {
-#if LUM_LDS_SWIZZLE
-  return ((node >> 1) & 7u) << 4;
-#else
-  (void) node;
-  return 0u;
-#endif
-}
 
 // Traversal stack entry. Closest-hit rays keep the child's entry distance next to its index so that a pop can drop what lies beyond the hit
 // found meanwhile (8 bytes). A visibility ray's segment never shrinks, every stacked child stays within reach, so its entries are the
@@ -256,10 +204,9 @@ LUM_DEV uint32_t visit_node(const NodeSource& src, uint32_t cur, const TRay& r, 
   uint4 ch;
   if (cur < src.lds_count) {
     const char* p = src.lds + b;
-    const uint32_t z = lds_node_swizzle_bytes(cur);
-    nx = *reinterpret_cast<const float4*>(p + (r.nx ^ z)); ny = *reinterpret_cast<const float4*>(p + (r.ny ^ z)); nz = *reinterpret_cast<const float4*>(p + (r.nz ^ z));
-    fx = *reinterpret_cast<const float4*>(p + (r.fx ^ z)); fy = *reinterpret_cast<const float4*>(p + (r.fy ^ z)); fz = *reinterpret_cast<const float4*>(p + (r.fz ^ z));
-    ch = *reinterpret_cast<const uint4*>(p + (96u ^ z));
+    nx = *reinterpret_cast<const float4*>(p + r.nx); ny = *reinterpret_cast<const float4*>(p + r.ny); nz = *reinterpret_cast<const float4*>(p + r.nz);
+    fx = *reinterpret_cast<const float4*>(p + r.fx); fy = *reinterpret_cast<const float4*>(p + r.fy); fz = *reinterpret_cast<const float4*>(p + r.fz);
+    ch = *reinterpret_cast<const uint4*>(p + 96u);
     st.lds_nodes++;
   }
   else {
@@ -277,240 +224,10 @@ LUM_DEV uint32_t visit_node(const NodeSource& src, uint32_t cur, const TRay& r, 
     cswap(k0, c0, k1, c1); cswap(k2, c2, k3, c3); cswap(k0, c0, k2, c2); cswap(k1, c1, k3, c3); cswap(k1, c1, k2, c2);
   }
   const float inf = __builtin_inff();
-#ifndef LUM_PUSH_COND
-#define LUM_PUSH_COND 1  // measured (hall / scan / example, fast flavour): closest-hit kernel -15 / -13 / -7 %, visibility kernel -4 / -4 / -3 %
-#endif
-#if LUM_PUSH_COND
   // Pushes only what is real. After the sort the children the ray may touch come first, so "child j is real" implies the same of every
   // child before it: one branch skips all three pushes in the common case of at most one child hit, and nothing is written for children the
-  // ray misses (branch-free pushes store 3 entries per visit, used or not: most of the kernel's L2 requests were those stores).
-  if (k1 < inf) {
-    if (k2 < inf) {
-      if (k3 < inf) { stk.store(sp, top); sp++; top = SE::make(c3, k3); }
-      stk.store(sp, top); sp++; top = SE::make(c2, k2);
-    }
-    stk.store(sp, top); sp++; top = SE::make(c1, k1);
-  }
-#else
-  // Branch-free pushes. The newest entry lives in registers (`top`), older ones in scratch: a push spills the old top to a slot
-  // that is only kept if the push is real, so a pop never waits for a scratch load before it can fetch the next node.
-  {
-    const bool v = k3 < inf;
-    stk.store(sp, top); sp += v ? 1 : 0;
-    top = v ? SE::make(c3, k3) : top;
-  }
-  {
-    const bool v = k2 < inf;
-    stk.store(sp, top); sp += v ? 1 : 0;
-    top = v ? SE::make(c2, k2) : top;
-  }
-  {
-    const bool v = k1 < inf;
-    stk.store(sp, top); sp += v ? 1 : 0;
-    top = v ? SE::make(c1, k1) : top;
-  }
-#endif
-  return (k0 < inf) ? c0 : kBvhEmpty;
-}
-
-// ---- 8-wide nodes with quantised child boxes (Bvh8Node): the scene's and the particles' trees ----
-// Eight children per 128-byte line instead of four: 22 % fewer node visits on the hall, the boxes 8-bit offsets from the node's corner in units of a
-// power of two per axis, rounded outwards by the builder (after Ylitie, Karras, Laine 2017, without their octant ordering: the eight entry
-// distances are sorted by a 19-comparator network). Measured twice (rounds 1 and 2): a visit costs 215 instead of 110 vector instructions - 48
-// byte->float conversions and the network's 95 - and the kernels are issue-bound (section 4): closest-hit +9 %, visibility +10 % time. Off.
-LUM_DEV float byte_f(uint32_t w, uint32_t k) { return (float) ((w >> (8u * k)) & 0xFFu); }  // v_cvt_f32_ubyte{k}
-template <bool kOrdered, bool kCull, typename S>
-LUM_DEV uint32_t visit_node8(const NodeSource& src, uint32_t cur, const TRay& r, float tmax, S& stk, int& sp,
-                             typename StackEntry<kCull>::E& top, RayStats& st) {
-  using SE = StackEntry<kCull>;
-  const uint32_t b = cur << 7;
-  const uint32_t onx = r.nx8(), ony = r.ny8(), onz = r.nz8();
-  float4 head;
-  uint4 ca, cb;
-  uint2 qnx, qny, qnz, qfx, qfy, qfz;
-  if (cur < src.lds_count) {
-    const char* p = src.lds + b;
-    head = *reinterpret_cast<const float4*>(p); ca = *reinterpret_cast<const uint4*>(p + 16u); cb = *reinterpret_cast<const uint4*>(p + 32u);
-    qnx = *reinterpret_cast<const uint2*>(p + onx); qny = *reinterpret_cast<const uint2*>(p + ony); qnz = *reinterpret_cast<const uint2*>(p + onz);
-    qfx = *reinterpret_cast<const uint2*>(p + (120u - onx)); qfy = *reinterpret_cast<const uint2*>(p + (136u - ony)); qfz = *reinterpret_cast<const uint2*>(p + (152u - onz));
-    st.lds_nodes++;
-  }
-  else {
-    const char* __restrict__ p = reinterpret_cast<const char*>(src.global) + b;
-    head = *reinterpret_cast<const float4*>(p); ca = *reinterpret_cast<const uint4*>(p + 16u); cb = *reinterpret_cast<const uint4*>(p + 32u);
-    qnx = *reinterpret_cast<const uint2*>(p + onx); qny = *reinterpret_cast<const uint2*>(p + ony); qnz = *reinterpret_cast<const uint2*>(p + onz);
-    qfx = *reinterpret_cast<const uint2*>(p + (120u - onx)); qfy = *reinterpret_cast<const uint2*>(p + (136u - ony)); qfz = *reinterpret_cast<const uint2*>(p + (152u - onz));
-  }
-  // plane distance = (origin + q * scale - o) * inv = q * (scale * inv) + (origin * inv + noi)
-  const uint32_t ew = fbits(head.w);
-  const float sx = bitsf((ew & 0xFFu) << 23) * r.inv.x, sy = bitsf(((ew >> 8) & 0xFFu) << 23) * r.inv.y, sz = bitsf(((ew >> 16) & 0xFFu) << 23) * r.inv.z;
-  const float bx = __builtin_fmaf(head.x, r.inv.x, r.noi.x), by = __builtin_fmaf(head.y, r.inv.y, r.noi.y), bz = __builtin_fmaf(head.z, r.inv.z, r.noi.z);
-  const float inf = __builtin_inff();
-  const float lim = vmin2(tmax, inf);
-  float k[8];
-  uint32_t c[8] = {ca.x, ca.y, ca.z, ca.w, cb.x, cb.y, cb.z, cb.w};
-#pragma unroll
-  for (uint32_t j = 0; j < 8; j++) {
-    const uint32_t wnx = j < 4 ? qnx.x : qnx.y, wny = j < 4 ? qny.x : qny.y, wnz = j < 4 ? qnz.x : qnz.y;
-    const uint32_t wfx = j < 4 ? qfx.x : qfx.y, wfy = j < 4 ? qfy.x : qfy.y, wfz = j < 4 ? qfz.x : qfz.y;
-    const float ax = __builtin_fmaf(byte_f(wnx, j & 3u), sx, bx), ay = __builtin_fmaf(byte_f(wny, j & 3u), sy, by), az = __builtin_fmaf(byte_f(wnz, j & 3u), sz, bz);
-    const float fx = __builtin_fmaf(byte_f(wfx, j & 3u), sx, bx), fy = __builtin_fmaf(byte_f(wfy, j & 3u), sy, by), fz = __builtin_fmaf(byte_f(wfz, j & 3u), sz, bz);
-    const float tn = vmax3(ax, ay, vmax0(az));
-    const float tf = vmin3(fx, fy, vmin2(fz, lim));
-    k[j] = (c[j] != kBvhEmpty && tn <= __builtin_fmaf(tf, 1.000004f, 1e-30f)) ? tn : inf;
-  }
-  if (kOrdered) {  // Batcher's odd-even merge sort, 19 comparators
-    cswap(k[0], c[0], k[1], c[1]); cswap(k[2], c[2], k[3], c[3]); cswap(k[4], c[4], k[5], c[5]); cswap(k[6], c[6], k[7], c[7]);
-    cswap(k[0], c[0], k[2], c[2]); cswap(k[1], c[1], k[3], c[3]); cswap(k[4], c[4], k[6], c[6]); cswap(k[5], c[5], k[7], c[7]);
-    cswap(k[1], c[1], k[2], c[2]); cswap(k[5], c[5], k[6], c[6]);
-    cswap(k[0], c[0], k[4], c[4]); cswap(k[1], c[1], k[5], c[5]); cswap(k[2], c[2], k[6], c[6]); cswap(k[3], c[3], k[7], c[7]);
-    cswap(k[2], c[2], k[4], c[4]); cswap(k[3], c[3], k[5], c[5]);
-    cswap(k[1], c[1], k[2], c[2]); cswap(k[3], c[3], k[4], c[4]); cswap(k[5], c[5], k[6], c[6]);
-    // pushes only what is real, far to near; sorted, so "child j is real" implies the same of every child before it
-    if (k[1] < inf) {
-      if (k[2] < inf) {
-        if (k[3] < inf) {
-          if (k[4] < inf) {
-            if (k[5] < inf) {
-              if (k[6] < inf) {
-                if (k[7] < inf) { stk.store(sp, top); sp++; top = SE::make(c[7], k[7]); }
-                stk.store(sp, top); sp++; top = SE::make(c[6], k[6]);
-              }
-              stk.store(sp, top); sp++; top = SE::make(c[5], k[5]);
-            }
-            stk.store(sp, top); sp++; top = SE::make(c[4], k[4]);
-          }
-          stk.store(sp, top); sp++; top = SE::make(c[3], k[3]);
-        }
-        stk.store(sp, top); sp++; top = SE::make(c[2], k[2]);
-      }
-      stk.store(sp, top); sp++; top = SE::make(c[1], k[1]);
-    }
-    return (k[0] < inf) ? c[0] : kBvhEmpty;
-  }
-  // unordered: continue with the first real child, push the others
-  uint32_t next = kBvhEmpty;
-#pragma unroll
-  for (uint32_t j = 0; j < 8; j++) {
-    if (k[j] < inf) {
-      if (next == kBvhEmpty) next = c[j];
-      else { stk.store(sp, top); sp++; top = SE::make(c[j], k[j]); }
-    }
-  }
-  return next;
-}
-
-// ---- 4-wide nodes with quantised child boxes in 64 bytes (Bvh4QNode) ----
-template <bool kOrdered, bool kCull, typename S>
-LUM_DEV uint32_t visit_node_q(const NodeSource& src, uint32_t cur, const TRay& r, float tmax, S& stk, int& sp,
-                              typename StackEntry<kCull>::E& top, RayStats& st) {
-  using SE = StackEntry<kCull>;
-  const uint32_t b = cur << 6;
-  float4 head;
-  uint4 ch, q0;
-  uint2 q1;
-  if (cur < src.lds_count) {
-    const char* p = src.lds + b;
-    head = *reinterpret_cast<const float4*>(p); ch = *reinterpret_cast<const uint4*>(p + 16u); q0 = *reinterpret_cast<const uint4*>(p + 32u); q1 = *reinterpret_cast<const uint2*>(p + 48u);
-    st.lds_nodes++;
-  }
-  else {
-    const char* __restrict__ p = reinterpret_cast<const char*>(src.global) + b;
-    head = *reinterpret_cast<const float4*>(p); ch = *reinterpret_cast<const uint4*>(p + 16u); q0 = *reinterpret_cast<const uint4*>(p + 32u); q1 = *reinterpret_cast<const uint2*>(p + 48u);
-  }
-  // q0 = lo_x, lo_y, lo_z, hi_x; q1 = hi_y, hi_z; near plane of an axis = the lower one unless the ray runs against it
-  const bool bx_neg = r.inv.x < 0.0f, by_neg = r.inv.y < 0.0f, bz_neg = r.inv.z < 0.0f;
-  const uint32_t wnx = bx_neg ? q0.w : q0.x, wfx = bx_neg ? q0.x : q0.w;
-  const uint32_t wny = by_neg ? q1.x : q0.y, wfy = by_neg ? q0.y : q1.x;
-  const uint32_t wnz = bz_neg ? q1.y : q0.z, wfz = bz_neg ? q0.z : q1.y;
-  // plane distance = (origin + q * scale - o) * inv = q * (scale * inv) + (origin * inv + noi)
-  const uint32_t ew = fbits(head.w);
-  const float sx = bitsf((ew & 0xFFu) << 23) * r.inv.x, sy = bitsf(((ew >> 8) & 0xFFu) << 23) * r.inv.y, sz = bitsf(((ew >> 16) & 0xFFu) << 23) * r.inv.z;
-  const float ox = __builtin_fmaf(head.x, r.inv.x, r.noi.x), oy = __builtin_fmaf(head.y, r.inv.y, r.noi.y), oz = __builtin_fmaf(head.z, r.inv.z, r.noi.z);
-  const float inf = __builtin_inff();
-  float k[4];
-  uint32_t c[4] = {ch.x, ch.y, ch.z, ch.w};
-#pragma unroll
-  for (uint32_t j = 0; j < 4; j++) {
-    const float ax = __builtin_fmaf(byte_f(wnx, j), sx, ox), ay = __builtin_fmaf(byte_f(wny, j), sy, oy), az = __builtin_fmaf(byte_f(wnz, j), sz, oz);
-    const float fx = __builtin_fmaf(byte_f(wfx, j), sx, ox), fy = __builtin_fmaf(byte_f(wfy, j), sy, oy), fz = __builtin_fmaf(byte_f(wfz, j), sz, oz);
-    const float tn = vmax3(ax, ay, vmax0(az));
-    const float tf = vmin3(fx, fy, vmin2(fz, tmax));
-    k[j] = (c[j] != kBvhEmpty && tn <= __builtin_fmaf(tf, 1.000004f, 1e-30f)) ? tn : inf;
-  }
-  float k0 = k[0], k1 = k[1], k2 = k[2], k3 = k[3];
-  uint32_t c0 = c[0], c1 = c[1], c2 = c[2], c3 = c[3];
-  if (kOrdered) { cswap(k0, c0, k1, c1); cswap(k2, c2, k3, c3); cswap(k0, c0, k2, c2); cswap(k1, c1, k3, c3); cswap(k1, c1, k2, c2); }
-  else {  // unordered: real children first (stable), so that the conditional pushes below see them in front
-    cswap(k0, c0, k1, c1); cswap(k2, c2, k3, c3); cswap(k0, c0, k2, c2); cswap(k1, c1, k3, c3); cswap(k1, c1, k2, c2);
-  }
-  if (k1 < inf) {
-    if (k2 < inf) {
-      if (k3 < inf) { stk.store(sp, top); sp++; top = SE::make(c3, k3); }
-      stk.store(sp, top); sp++; top = SE::make(c2, k2);
-    }
-    stk.store(sp, top); sp++; top = SE::make(c1, k1);
-  }
-  return (k0 < inf) ? c0 : kBvhEmpty;
-}
-
-struct NodeData { float4 nx, ny, nz, fx, fy, fz; uint4 ch; };
-LUM_DEV NodeData load_node(const NodeSource& src, uint32_t id, const TRay& r, RayStats& st) {
-  NodeData n;
-  const uint32_t b = id << 7;
-  if (id < src.lds_count) {
-    const char* p = src.lds + b;
-    const uint32_t z = lds_node_swizzle_bytes(id);
-    n.nx = *reinterpret_cast<const float4*>(p + (r.nx ^ z)); n.ny = *reinterpret_cast<const float4*>(p + (r.ny ^ z)); n.nz = *reinterpret_cast<const float4*>(p + (r.nz ^ z));
-    n.fx = *reinterpret_cast<const float4*>(p + (r.fx ^ z)); n.fy = *reinterpret_cast<const float4*>(p + (r.fy ^ z)); n.fz = *reinterpret_cast<const float4*>(p + (r.fz ^ z));
-    n.ch = *reinterpret_cast<const uint4*>(p + (96u ^ z));
-    st.lds_nodes++;
-  }
-  else {
-    const Bvh4Node* __restrict__ nodes = src.global;
-    n.nx = node_f4(nodes, b + r.nx); n.ny = node_f4(nodes, b + r.ny); n.nz = node_f4(nodes, b + r.nz);
-    n.fx = node_f4(nodes, b + r.fx); n.fy = node_f4(nodes, b + r.fy); n.fz = node_f4(nodes, b + r.fz);
-    n.ch = node_u4(nodes, b + 96u);
-  }
-  return n;
-}
-
-// Visibility rays visit every stacked node anyway (their segment never shrinks), so a lane whose newest stack entry is an inner node of the same
-// level takes it along: both nodes' lines are requested before either is tested, which halves the dependent round trips of a ray (the idea of
-// round 2, when the kernels were thought to be bound by those; the counters of round 3 say issue rate and address unit). Measured (LUM_DUAL_VISIT=1): NOT faster - visibility kernel 121.9 -> 144.4 ms per 3 steps
-// on the hall, 32.6 -> 36.1 on the scan: rays that find an occluder have fetched a node they would never have visited (nodes per ray 15.2 -> 16.2),
-// lanes with and without a second node diverge, and the iteration carries twice the registers. Off. `second` = kBvhEmpty for lanes without such an entry. Every child of the second node
-// that the ray may touch is pushed; of the first node's children the nearest is continued with, as in visit_node.
-template <bool kCull, typename S>
-LUM_DEV uint32_t visit_two_nodes(const NodeSource& src, uint32_t cur, uint32_t second, const TRay& r, float tmax, S& stk,
-                                 int& sp, typename StackEntry<kCull>::E& top, RayStats& st) {
-  using SE = StackEntry<kCull>;
-  const float inf = __builtin_inff();
-  const NodeData a = load_node(src, cur, r, st);
-  NodeData b;
-  const bool two = second != kBvhEmpty;
-  if (two) b = load_node(src, second, r, st);
-  {
-    float e0 = inf, e1 = inf, e2 = inf, e3 = inf;
-    uint32_t d0 = kBvhEmpty, d1 = kBvhEmpty, d2 = kBvhEmpty, d3 = kBvhEmpty;
-    if (two) {
-      e0 = child_entry(b.nx.x, b.ny.x, b.nz.x, b.fx.x, b.fy.x, b.fz.x, r, tmax);
-      e1 = child_entry(b.nx.y, b.ny.y, b.nz.y, b.fx.y, b.fy.y, b.fz.y, r, tmax);
-      e2 = child_entry(b.nx.z, b.ny.z, b.nz.z, b.fx.z, b.fy.z, b.fz.z, r, tmax);
-      e3 = child_entry(b.nx.w, b.ny.w, b.nz.w, b.fx.w, b.fy.w, b.fz.w, r, tmax);
-      d0 = b.ch.x; d1 = b.ch.y; d2 = b.ch.z; d3 = b.ch.w;
-      if (e3 < inf) { stk.store(sp, top); sp++; top = SE::make(d3, e3); }
-      if (e2 < inf) { stk.store(sp, top); sp++; top = SE::make(d2, e2); }
-      if (e1 < inf) { stk.store(sp, top); sp++; top = SE::make(d1, e1); }
-      if (e0 < inf) { stk.store(sp, top); sp++; top = SE::make(d0, e0); }
-    }
-  }
-  float k0 = child_entry(a.nx.x, a.ny.x, a.nz.x, a.fx.x, a.fy.x, a.fz.x, r, tmax);
-  float k1 = child_entry(a.nx.y, a.ny.y, a.nz.y, a.fx.y, a.fy.y, a.fz.y, r, tmax);
-  float k2 = child_entry(a.nx.z, a.ny.z, a.nz.z, a.fx.z, a.fy.z, a.fz.z, r, tmax);
-  float k3 = child_entry(a.nx.w, a.ny.w, a.nz.w, a.fx.w, a.fy.w, a.fz.w, r, tmax);
-  uint32_t c0 = a.ch.x, c1 = a.ch.y, c2 = a.ch.z, c3 = a.ch.w;
-  cswap(k0, c0, k1, c1); cswap(k2, c2, k3, c3); cswap(k0, c0, k2, c2); cswap(k1, c1, k3, c3); cswap(k1, c1, k2, c2);
+  // ray misses (branch-free pushes stored 3 entries per visit, used or not: most of the kernel's L2 requests were those stores; measured on hall / scan /
+  // example, fast flavour: closest-hit kernel -15 / -13 / -7 %, visibility kernel -4 / -4 / -3 %).
   if (k1 < inf) {
     if (k2 < inf) {
       if (k3 < inf) { stk.store(sp, top); sp++; top = SE::make(c3, k3); }
@@ -556,19 +273,6 @@ struct LeafTris {
   }
 };
 
-// Experiment (LUM_PREFETCH, off): after a node visit the entry that will be popped next is known (`top`); its 128-byte line is requested with
-// an LDS-DMA load into a per-wave junk area (no destination register, nothing waits for the data), so that the later visit finds it in L1/L2.
-#ifndef LUM_PREFETCH
-#define LUM_PREFETCH 0
-#endif
-LUM_DEV void prefetch_line(const void* p, uint32_t* wave_sink) {
-#if LUM_PREFETCH
-  __builtin_amdgcn_global_load_lds((const void __attribute__((address_space(1)))*) p, (void __attribute__((address_space(3)))*) wave_sink, 4, 0, 0);
-#else
-  (void) p; (void) wave_sink;
-#endif
-}
-
 // ---- the persistent two-level traversal ----
 // A query type Q provides (all per lane):
 //   bool load(sc, idx, origin, dir, tmax)   read item idx; false = nothing to trace
@@ -582,31 +286,21 @@ LUM_DEV void trace_items(const DeviceScene& sc, uint32_t n, uint32_t* __restrict
   if (n == 0u) return;  // wave-uniform (a kernel argument read from the control words): an empty launch - the ambient reuse's fallback list on an opaque scene - stages nothing
   using SE = StackEntry<Q::kCull>;
   using E = typename SE::E;
-  // Dual visits (visit_two_nodes) push all four children of the second node, which is not depth-first any more: the guard below allows them only
-  // while fewer than kDualLimit entries are stacked, after which single visits need at most 3 more per remaining level (<= 126): 256 entries.
-  constexpr int kDualLimit = 120;
-  E stack_in_scratch[(LUM_DUAL_VISIT && Q::kDual) ? 2 * kStackSize : kStackSize];
+  E stack_in_scratch[kStackSize];
   int sp = 0;
   TRay r;
   V3 wo = v3(0.0f, 0.0f, 0.0f), wd = v3(0.0f, 0.0f, 1.0f);
   float tmax = 0.0f;
   uint32_t cur = kTraversalDone, inst = kNoInstance, idx = 0;
-  uint32_t postponed = kBvhEmpty;  // Q::kSpeculate: a leaf of the current instance set aside for the wave's next triangle phase
   r.set(wo, wd);
   bool more = true;
-  // Experiment (LUM_DEFER_FINISH): results are stores, and on this part a store counts on the same in-order counter as the loads (vmcnt): written where
-  // the ray ends, inside the phase loop, it sits in front of the next iteration's node or triangle loads, whose wait then also waits for the store to
-  // be acknowledged - and about one ray of a wave ends per iteration. With the flag a lane keeps its result until it takes its next ray (the stores go
-  // out in the refill, before the new rays' own loads). Measured, same box: hall visibility kernel 373.5 -> 380.5 ms per 3 steps, closest-hit
-  // unchanged; scan 70.9 -> 69.5 and 64.1 -> 63.7: the acknowledgements are not what the iterations wait for. Off.
-  bool unwritten = false;
   const uint32_t lane = threadIdx.x & 63u;
   const unsigned long long below = (1ull << lane) - 1ull;
   // stage the top of the tree
   extern __shared__ float4 lds_top[];
   {
     const float4* __restrict__ g = reinterpret_cast<const float4*>(sc.bvh_nodes);
-    for (uint32_t i = threadIdx.x; i < lds_count * (kNodeBytes / 16u); i += blockDim.x) lds_top[lds_slot_swizzle(i)] = g[i];
+    for (uint32_t i = threadIdx.x; i < lds_count * (kNodeBytes / 16u); i += blockDim.x) lds_top[i] = g[i];
     __syncthreads();
   }
   // ... and the records of the first top-level leaves (the rows of an instance's world->object matrix): entering one of those instances costs no
@@ -621,10 +315,6 @@ LUM_DEV void trace_items(const DeviceScene& sc, uint32_t n, uint32_t* __restrict
   TraversalStack<E> stk{(typename TraversalStack<E>::ScratchPtr) reinterpret_cast<StackW*>(stack_in_scratch),
                         (typename TraversalStack<E>::LdsPtr) (reinterpret_cast<StackW*>(reinterpret_cast<char*>(lds_top) + lds_count * kNodeBytes) + threadIdx.x),
                         (int) (LUM_LDS_STACK_BYTES / (kRayBlockMax * (uint32_t) sizeof(E)))};
-#if LUM_PREFETCH
-  __shared__ uint32_t prefetch_sink[kPrefetchSinkWords];
-  uint32_t* wave_sink = prefetch_sink + (threadIdx.x >> 6) * 64u;
-#endif
 
   E top = SE::make(kTraversalDone, 0.0f);
 #ifdef LUM_PHASE_STATS
@@ -658,17 +348,6 @@ LUM_DEV void trace_items(const DeviceScene& sc, uint32_t n, uint32_t* __restrict
   uint32_t chunk = n / (waves * 2u);
   chunk = (min(max(chunk, 64u), LUM_CHUNK_MAX) + 63u) & ~63u;
   uint32_t chunk_next = 0, chunk_end = 0;
-#ifndef LUM_XCD_RANGES
-#define LUM_XCD_RANGES 0
-#endif
-#if LUM_XCD_RANGES
-  // Experiment: every XCD has its own L2. The queue is cut into 8 contiguous ranges (the queue order is pixel order at depth 0 and stays
-  // roughly that through the compactions), XCD x works on range x first and helps with the others when its own is used up, so that the eight
-  // L2s hold different parts of the scene instead of eight copies of the same hot set. `cursor` then points at 8 words.
-  const uint32_t xcd = __builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20) & 7u;  // HW_REG_XCC_ID
-  const uint32_t range_len = (n + 7u) / 8u;
-  uint32_t ranges_left = 8u, range = xcd;
-#endif
 
   while (true) {
     const unsigned long long idle = __ballot(cur == kTraversalDone);
@@ -678,31 +357,17 @@ LUM_DEV void trace_items(const DeviceScene& sc, uint32_t n, uint32_t* __restrict
 #endif
     if (idle != 0ull && more) {  // wave-uniform
       if (chunk_next >= chunk_end) {
-#if LUM_XCD_RANGES
-        while (ranges_left > 0u) {
-          const uint32_t lo = min(range * range_len, n), hi = min(lo + range_len, n);
-          uint32_t base = 0;
-          if (lane == 0) base = atomicAdd(cursor + range, chunk);
-          base = __builtin_amdgcn_readfirstlane(base) + lo;
-          if (base < hi) { chunk_next = base; chunk_end = min(base + chunk, hi); break; }
-          range = (range + 1u) & 7u;  // this range is handed out completely: help with the next one
-          ranges_left--;
-        }
-        more = ranges_left > 0u;
-#else
         uint32_t base = 0;
         if (lane == 0) base = atomicAdd(cursor, chunk);
         base = __builtin_amdgcn_readfirstlane(base);
         chunk_next = base;
         chunk_end = min(base + chunk, n);
         more = base < n;
-#endif
       }
       if (more) {
         const uint32_t avail = chunk_end - chunk_next, want = (uint32_t) __popcll(idle);
         const uint32_t rank = (uint32_t) __popcll(idle & below);
         if (cur == kTraversalDone && rank < avail) {
-          if (unwritten) { q.finish(sc, idx); unwritten = false; }
           idx = chunk_next + rank;
           if (q.load(sc, idx, wo, wd, tmax)) {
             rays++;
@@ -712,7 +377,7 @@ LUM_DEV void trace_items(const DeviceScene& sc, uint32_t n, uint32_t* __restrict
             const bool finite = (fbits(wo.x) & e) != e && (fbits(wo.y) & e) != e && (fbits(wo.z) & e) != e && (fbits(wd.x) & e) != e && (fbits(wd.y) & e) != e &&
                                 (fbits(wd.z) & e) != e;
             if (finite) { r.set(wo, wd); cur = 0; sp = 0; top = SE::make(kTraversalDone, 0.0f); inst = kNoInstance; }
-            else { if (LUM_DEFER_FINISH) unwritten = true; else q.finish(sc, idx); }
+            else q.finish(sc, idx);
           }
         }
         chunk_next += min(want, avail);
@@ -729,45 +394,18 @@ LUM_DEV void trace_items(const DeviceScene& sc, uint32_t n, uint32_t* __restrict
     // (and the other way round), instead of waiting until every lane has found a leaf: measured lane occupancy of the node phase
     // was 0.33-0.41 with the plain while-while loop.
     while (true) {
-      if (Q::kSpeculate) {
-        // a lane on a leaf of an instance, nothing set aside yet, whose newest stack entry is an inner node within reach (markers, leaves and the
-        // sentinel carry the leaf bit): the leaf waits, the lane walks on. Such an entry always has something below it (the sentinel at least).
-        const uint32_t t = SE::node(top);
-        if (cur != kTraversalDone && (cur & kBvhLeafBit) && inst != kNoInstance && postponed == kBvhEmpty && !(t & kBvhLeafBit) && SE::reachable(top, tmax)) {
-          postponed = cur; cur = t; sp--; top = stk.load(sp);
-        }
-      }
       const bool live = cur != kTraversalDone;
       const bool at_leaf = live && (cur & kBvhLeafBit);
-      // (with speculation: a lane counts for the triangle vote when it cannot go on without the triangle phase; lanes that hold a postponed leaf and a
-      // node take part in both phases)
       const bool want_tris = at_leaf && inst != kNoInstance, want_enter = at_leaf && inst == kNoInstance;
       const uint32_t n_live = (uint32_t) __popcll(__ballot(live)), n_tris = (uint32_t) __popcll(__ballot(want_tris)), n_enter = (uint32_t) __popcll(__ballot(want_enter));
       if (n_live == 0u) break;
       const uint32_t n_nodes = n_live - n_tris - n_enter;
-#if LUM_LDS_TURN
-      // A wave iteration ends when its slowest lane has its data: one lane whose node comes from memory makes all lanes wait a memory round trip
-      // (about 3 us under this kernel's own load), lanes whose node sits in the staged tree top included - and those are 60 % of the node visits.
-      // So while enough lanes stand on staged nodes they get iterations of their own, which issue no vector-memory load at all and take a
-      // quarter of the time; the lanes on other nodes wait those out and are then served together.
-      const bool on_staged = live && ((!at_leaf && cur < lds_count) || (want_enter && (cur & 0x0FFFFFFFu) < staged_leaves));
-      const uint32_t n_staged = (uint32_t) __popcll(__ballot(on_staged));
-      const bool staged_turn = n_staged >= LUM_LDS_TURN && (LUM_LDS_FIRST || n_tris * LUM_VOTE_TRIS < max(n_nodes, n_enter) * LUM_VOTE_NODES) && (LUM_LDS_FIRST || n_enter < n_nodes);
-      const bool run_tris = !staged_turn && n_tris * LUM_VOTE_TRIS >= max(n_nodes, n_enter) * LUM_VOTE_NODES;
-      const bool run_enter = !staged_turn && !run_tris && n_enter >= n_nodes;
-#else
       const bool run_tris = n_tris * LUM_VOTE_TRIS >= max(n_nodes, n_enter) * LUM_VOTE_NODES;
       const bool run_enter = !run_tris && n_enter >= n_nodes;
-#endif
       // Three per-lane conditions of which the vote leaves at most one non-empty. Written as independent divergent ifs on purpose: with
       // wave-uniform if/else-if branches the compiler routed every ray register through a temporary and back at the merge point
       // (about forty v_mov per iteration).
-#if LUM_LDS_TURN
-      const bool do_tris = run_tris && want_tris, do_enter = (run_enter && want_enter) || (staged_turn && want_enter && on_staged),
-                 do_node = !run_tris && !run_enter && live && !at_leaf && (!staged_turn || on_staged);
-#else
-      const bool do_tris = run_tris && (want_tris || (Q::kSpeculate && postponed != kBvhEmpty)), do_enter = run_enter && want_enter, do_node = !run_tris && !run_enter && live && !at_leaf;
-#endif
+      const bool do_tris = run_tris && want_tris, do_enter = run_enter && want_enter, do_node = !run_tris && !run_enter && live && !at_leaf;
       LUM_TIME_BEGIN();
 #ifdef LUM_PHASE_STATS
       const bool memory_node_ = __ballot(do_node && cur >= lds_count) != 0ull;
@@ -775,14 +413,9 @@ LUM_DEV void trace_items(const DeviceScene& sc, uint32_t n, uint32_t* __restrict
       {
         if (do_tris) {
           LUM_PHASE(3); LUM_PHASE_LANES(4);
-          if (Q::kSpeculate && postponed != kBvhEmpty) {  // the leaf set aside first; the lane's place in the traversal (cur, a node or another leaf) stays
-            const uint32_t leaf = postponed;
-            postponed = kBvhEmpty;
-            if (q.on_tris(sc, inst, leaf & 0x0FFFFFFFu, ((leaf >> 28) & 0x7u) + 1u, r.o, r.d, tmax, st)) cur = kTraversalDone;
-          }
-          else if (q.on_tris(sc, inst, cur & 0x0FFFFFFFu, ((cur >> 28) & 0x7u) + 1u, r.o, r.d, tmax, st)) cur = kTraversalDone;
+          if (q.on_tris(sc, inst, cur & 0x0FFFFFFFu, ((cur >> 28) & 0x7u) + 1u, r.o, r.d, tmax, st)) cur = kTraversalDone;
           else pop();
-          if (cur == kTraversalDone) { if (LUM_DEFER_FINISH) unwritten = true; else q.finish(sc, idx); }
+          if (cur == kTraversalDone) q.finish(sc, idx);
         }
       }
       {
@@ -806,43 +439,10 @@ LUM_DEV void trace_items(const DeviceScene& sc, uint32_t n, uint32_t* __restrict
         if (do_node) {
           LUM_PHASE(0);
           st.nodes++;
-#if LUM_DUAL_VISIT
-          if (Q::kDual) {
-            uint32_t second = kBvhEmpty;
-            const uint32_t t = SE::node(top);
-            if (!(t & kBvhLeafBit) && sp < kDualLimit) {  // the newest entry is an inner node (markers and leaves carry the leaf bit): same level as `cur`
-              second = t;
-              st.nodes++;
-              if (sp > 0) { sp--; top = stk.load(sp); }
-              else top = SE::make(kTraversalDone, 0.0f);
-            }
-            cur = visit_two_nodes<Q::kCull>(nodes, cur, second, r, tmax, stk, sp, top, st);
-          }
-          else
-#endif
-#if LUM_BVH8
-          cur = visit_node8<Q::kOrdered, Q::kCull>(nodes, cur, r, tmax, stk, sp, top, st);
-#elif LUM_BVH4Q
-          cur = visit_node_q<Q::kOrdered, Q::kCull>(nodes, cur, r, tmax, stk, sp, top, st);
-#else
           cur = visit_node<Q::kOrdered, Q::kCull, Q::kFarFirst>(nodes, cur, r, tmax, stk, sp, top, st);
-#endif
-#if LUM_PREFETCH
-          {
-            const uint32_t t = SE::node(top);
-            if (!(t & kBvhLeafBit)) { if (t >= lds_count) prefetch_line(sc.bvh_nodes + t, wave_sink); }
-#if LUM_PREFETCH >= 2
-            else if (t < kTraversalDone && inst != kNoInstance) prefetch_line(sc.blas_tris + (t & 0x0FFFFFFFu), wave_sink);
-#endif
-          }
-#endif
           if (cur == kBvhEmpty) {
-            // (with a leaf set aside nothing is popped: the next entry might be the way out of the instance the leaf belongs to)
-            if (Q::kSpeculate && postponed != kBvhEmpty) { cur = postponed; postponed = kBvhEmpty; }
-            else {
-              pop();
-              if (cur == kTraversalDone) { if (LUM_DEFER_FINISH) unwritten = true; else q.finish(sc, idx); }
-            }
+            pop();
+            if (cur == kTraversalDone) q.finish(sc, idx);
           }
         }
       }
@@ -856,7 +456,6 @@ LUM_DEV void trace_items(const DeviceScene& sc, uint32_t n, uint32_t* __restrict
       if (more && n_live < LUM_REFILL) break;
     }
   }
-  if (unwritten) q.finish(sc, idx);  // the lanes' last rays
 #ifdef LUM_PHASE_STATS
   ptime_[10] = __builtin_readcyclecounter() - t_kernel_; ptime_[11] = 1;
   for (int k = 0; k < 8; k++) if (phase_[k]) atomicAdd(&g_phase[k], (unsigned long long) phase_[k]);
@@ -864,21 +463,10 @@ LUM_DEV void trace_items(const DeviceScene& sc, uint32_t n, uint32_t* __restrict
 #endif
 }
 
-LUM_NS_END
-#if LUM_BVH8O
-#include "dev_trace8.h"
-#define LUM_TRACE_ITEMS trace_items8
-#else
-#define LUM_TRACE_ITEMS trace_items
-#endif
-LUM_NS_BEGIN
-
 struct Hit { uint32_t instance_id, tri_id; float t; uint32_t scene_tri; };
 
 // Nearest hit in [0, FLT_MAX); optionally ignoring the triangle the path is leaving (STATE_FLAG_USE_IGNORE_HANDLE).
 struct ClosestState {
-  static constexpr bool kDual = false;
-  static constexpr bool kSpeculate = (LUM_SPECULATE & 1) != 0;
   static constexpr bool kOrdered = true;
   static constexpr int kFarFirst = 0;
   static constexpr bool kCull = true;  // stack entries carry the entry distance: a pop drops children beyond the nearest hit so far
@@ -893,12 +481,9 @@ struct ClosestState {
   uint32_t ign_inst, ign_tri;
   Hit best;
   LUM_DEV void begin(bool ignore, uint32_t inst, uint32_t tri) { use_ignore = ignore; cutout = false; ign_inst = inst; ign_tri = tri; best = Hit{kHitSky, 0u, kFltMax, 0u}; }
-#ifndef LUM_CLOSEST_ALL_SLOTS
-#define LUM_CLOSEST_ALL_SLOTS 0  // 1: the closest-hit rays fetch every leaf slot unconditionally, as the visibility rays do (LeafTris::load)
-#endif
   LUM_DEV bool on_tris(const DeviceScene& sc, uint32_t inst, uint32_t first, uint32_t count, V3 o, V3 d, float& tmax, RayStats& st) {
     LeafTris lt;
-    lt.load<LUM_CLOSEST_ALL_SLOTS != 0>(sc.blas_tris, first, count);
+    lt.load<false>(sc.blas_tris, first, count);
 #pragma unroll
     for (uint32_t j = 0; j < kBvhLeafMaxTri; j++) {
       if (j >= count) break;
@@ -939,12 +524,7 @@ struct ShadowState {
 #define LUM_SHADOW_ORDER 1  // 0 nearest child first, 1 farthest first, 2 farthest first for rays without an end point only, 3 for segments only
 #endif
   static constexpr int kFarFirst = LUM_SHADOW_ORDER;
-#ifndef LUM_SHADOW_CULL
-#define LUM_SHADOW_CULL 0
-#endif
-  static constexpr bool kCull = LUM_SHADOW_CULL != 0;  // the segment never shrinks: 4-byte stack entries (StackEntry<false>)
-  static constexpr bool kDual = true;                  // two nodes per visit where the stack offers a second one (visit_two_nodes)
-  static constexpr bool kSpeculate = (LUM_SPECULATE & 2) != 0;
+  static constexpr bool kCull = false;  // the segment never shrinks: 4-byte stack entries (StackEntry<false>)
   uint32_t tgt_inst, tgt_tri, self_inst, self_tri;
   float dist;
 #if LUM_FAST
@@ -1069,14 +649,7 @@ LUM_DEV uint32_t light_query(const DeviceScene& sc, V3 origin, V3 dir, uint32_t 
 
 // ---- what every translation unit with a persistent ray kernel needs (kernels.h, kernel_shadow.h) ----
 // kTraceBlock (threads per workgroup of the persistent ray kernels) is defined in dev_trace.h, which lays the lanes' traversal stacks out by it
-#ifndef LUM_TRACE_MIN_WAVES
-#define LUM_TRACE_MIN_WAVES 0  // experiment: register budget of the ray kernels as waves per SIMD (0: whatever one workgroup of kTraceBlock threads per CU allows)
-#endif
-#if LUM_TRACE_MIN_WAVES
-#define LUM_TRACE_BOUNDS __launch_bounds__(kTraceBlock, LUM_TRACE_MIN_WAVES)
-#else
 #define LUM_TRACE_BOUNDS __launch_bounds__(kTraceBlock)
-#endif
 
 LUM_DEV void flush_stats(uint64_t* counters, const RayStats& st, uint32_t rays, uint32_t ray_counter, uint32_t node_counter, uint32_t tri_counter,
                          uint32_t lds_counter = kCntCount) {

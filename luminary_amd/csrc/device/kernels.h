@@ -13,7 +13,7 @@
 // Reference schedule: device/device_renderer.c:53-134; per-kernel restatements cite their sources below.
 #pragma once
 
-#include "kernel_shadow.h"  // dev_trace.h (+ dev_trace_pool.h), ShadowQuery, k_shadow_rays
+#include "kernel_shadow.h"  // dev_trace.h, ShadowQuery, k_shadow_rays
 #include "dev_sky.h"
 #include "dev_volume.h"
 #include "dev_particle.h"
@@ -235,16 +235,6 @@ struct TraceQuery : ClosestState {
     o = v3(o4.x, o4.y, o4.z); d = v3(d4.x, d4.y, d4.z); tmax = kFltMax;
     return true;
   }
-  // LUM_PHASE_QUEUES (dev_trace_pool.h): the state a pool slot keeps outside LDS, and the world-space ray again
-  static constexpr uint32_t kMutableVecs = 1;
-  LUM_DEV void save_mutable(uint4* m) const { m[0] = make_uint4(best.instance_id, best.tri_id, best.scene_tri, cutout ? 1u : 0u); }
-  LUM_DEV void load_mutable(const uint4* m, float tmax) { best = Hit{m[0].x, m[0].y, tmax, m[0].z}; cutout = m[0].w != 0u; }
-  LUM_DEV void save_const(uint4& c) const { c = make_uint4(use_ignore ? 1u : 0u, ign_inst, ign_tri, 0u); }
-  LUM_DEV void load_const(uint4 c) { use_ignore = c.x != 0u; ign_inst = c.y; ign_tri = c.z; }
-  LUM_DEV void world_ray(const DeviceScene&, uint32_t i, V3& o, V3& d) const {
-    const float4 o4 = q.origin_t[i], d4 = q.dir_slot[i];
-    o = v3(o4.x, o4.y, o4.z); d = v3(d4.x, d4.y, d4.z);
-  }
   LUM_DEV void finish(const DeviceScene&, uint32_t) {
     const uint32_t i = item;
     const Hit h = result();
@@ -262,11 +252,7 @@ __global__ LUM_TRACE_BOUNDS void k_trace(DeviceScene sc, PathQueue q, const uint
   tq.q = q;
   tq.order = order;
   tq.item = 0;
-#if LUM_PHASE_QUEUES
-  trace_items_pool(sc, ctrl[kCtlPaths], ctrl + kCtlTraceCursor, tq, st, rays, lds_nodes);
-#else
-  LUM_TRACE_ITEMS(sc, ctrl[kCtlPaths], ctrl + kCtlTraceCursor, tq, st, rays, lds_nodes);
-#endif
+  trace_items(sc, ctrl[kCtlPaths], ctrl + kCtlTraceCursor, tq, st, rays, lds_nodes);
   flush_stats(counters, st, rays, kCntTrace, kCntNodes, kCntTris, kCntNodesLds);
 }
 
@@ -442,19 +428,6 @@ LUM_DEV void resolve_vertex(const DeviceScene& sc, const PathQueue& in, const Ne
 // sampled (not CONSTANT).
 // kWater (the scene has an ocean): a path's volume is read from its stack, a vertex under water takes the sun through the surface and its sun and
 // ambient samples get a second visibility segment beyond it (dev_water.h); without an ocean none of that code exists in the kernel.
-// kStage (experiment, LUM_SHADE_STAGED): 0 = the whole vertex in one kernel (the product); 1 = the light sampling alone - context, root pass, the eight
-// candidates, the chosen light's visibility item, the light record and the root sum (parked in the fourth word of the BSDF-direction record) - and
-// 2 = everything else, with the root sum read back: the split the reference's geometry kernel suggests (cuda/geometry.cuh:11-180 calls the light
-// sampling as one block) so that each stage gets its own register budget.
-#ifndef LUM_SHADE_STAGED
-#define LUM_SHADE_STAGED 0
-#endif
-#ifndef LUM_SHADE_STAGE1_WAVES
-#define LUM_SHADE_STAGE1_WAVES 3
-#endif
-#ifndef LUM_SHADE_STAGE2_WAVES
-#define LUM_SHADE_STAGE2_WAVES 4
-#endif
 // Fused resolve (fast flavour with the ambient reuse, lumc_set_fused_resolve): k_resolve_reuse is a stream of 160 bytes per vertex with five loads and a
 // dozen multiply-adds - a kernel that waits - while k_shade computes with idle memory pipes. So the resolve of depth d - 1 rides in k_shade of depth d: every
 // path entry knows the vertex it continues (PathQueue::parent, written with the survivor) and, before anything else touches its result slot, forms that
@@ -465,23 +438,20 @@ LUM_DEV void resolve_vertex(const DeviceScene& sc, const PathQueue& in, const Ne
 // cannot decide (`fallback`: their ambient ray is queued into its own item arrays, traced by a small second pass, resolved by k_resolve_listed - for those
 // the vertex's sum lands after the next depth's emission: the fast flavour's rounding, not the exact flavour's, which never runs this).
 // (struct FusedResolve: dev_scene.h)
-#ifndef LUM_SHADE_DYNAMIC
-#define LUM_SHADE_DYNAMIC (!LUM_SHADE_STAGED)  // k_shade's waves take their input through a cursor (the staged experiment's two kernels would share it: fixed shares there)
-#endif
 constexpr uint32_t kShadeChunkRounds = 16u;  // x 64 queue entries per bump of the cursor at most: ~45 000 atomics on the word per launch of 42 M entries
-template <uint32_t kSkyMode, bool kWater, int kStage = 0, bool kTable = false>
-__global__ __launch_bounds__(kBlock, kStage == 1 ? LUM_SHADE_STAGE1_WAVES : kStage == 2 ? LUM_SHADE_STAGE2_WAVES : (kSkyMode == kSkyConstantColor && !kWater) ? LUM_SHADE_WAVES_CONSTANT_SKY : LUM_SHADE_WAVES) void k_shade(DeviceScene sc, PathQueue in, PathQueue out, NeeQueue nee, ShadowQueue sq, float4* results,
+template <uint32_t kSkyMode, bool kWater, bool kTable = false>
+__global__ __launch_bounds__(kBlock, (kSkyMode == kSkyConstantColor && !kWater) ? LUM_SHADE_WAVES_CONSTANT_SKY : LUM_SHADE_WAVES) void k_shade(DeviceScene sc, PathQueue in, PathQueue out, NeeQueue nee, ShadowQueue sq, float4* results,
                                                                     uint32_t* ctrl, uint32_t depth_const, uint64_t* counters, uint32_t ambient_reuse, const FusedResolve* __restrict__ fused_dev,
                                                                     uint32_t fused_flags) {
   const uint32_t n = ctrl[kCtlPaths];
   uint32_t* count_out = ctrl + kCtlStride + kCtlPaths;
   // fused resolve, fused_flags & 4: the previous depth's vertices that no entry continues (its k_shade listed them) are input too - entries n .. n_input - 1 have
   // a parent and nothing else - instead of a kernel of their own after that depth's visibility pass (k_resolve_ended), which only waited for memory
-  const uint32_t n_input = n + ((LUM_SHADE_DYNAMIC && LUM_FAST && kStage == 0 && !kWater && (fused_flags & 5u) == 5u) ? (ctrl - kCtlStride)[kCtlSkyItems] : 0u);
+  const uint32_t n_input = n + ((LUM_FAST && !kWater && (fused_flags & 5u) == 5u) ? (ctrl - kCtlStride)[kCtlSkyItems] : 0u);
   // (the fast flavour only: the exact flavour's sums land in the reference's order for every vertex, its kernels do not carry the code)
   // (its pointers come through memory, read where they are used: as kernel arguments they sat in scalar registers for the whole kernel, and the spills that
   // caused put 27 more lane reads into every iteration of the candidate loop)
-  const bool resolve_parents = LUM_FAST && kStage == 0 && !kWater && (fused_flags & 1u) != 0u, announce_children = LUM_FAST && kStage == 0 && !kWater && (fused_flags & 2u) != 0u;
+  const bool resolve_parents = LUM_FAST && !kWater && (fused_flags & 1u) != 0u, announce_children = LUM_FAST && !kWater && (fused_flags & 2u) != 0u;
   // ambient_reuse (see AmbientReuse above): the ambient visibility of a surviving path comes from its next closest-hit ray; never with an ocean (the ambient
   // ray then ends at the water surface) or under the procedural sky (no ambient sample)
   const bool reuse_ambient = ambient_reuse != 0u && !kWater && kSkyMode != kSkyDefault;
@@ -490,9 +460,8 @@ __global__ __launch_bounds__(kBlock, kStage == 1 ? LUM_SHADE_STAGE1_WAVES : kSta
   const bool lights_present = sc.light_tree_root != nullptr && sc.num_lights > 0;
   const Col sky = (sc.sky_mode == kSkyConstantColor) ? col(sc.sky_constant_color[0], sc.sky_constant_color[1], sc.sky_constant_color[2]) : splat(0.0f);
   uint32_t vertices = 0;
-#if LUM_SHADE_DYNAMIC
   // Input by cursor: a wave takes the depth's queue entries in chunks through one atomic per chunk, fetched a chunk ahead, until the queue is used up. With a
-  // fixed share per wave (the grid-stride loop below) every wave of the grid ends on a partial batch of surface hits - one batch time per wave, 0.4 ms of a
+  // fixed share per wave (a grid-stride loop) every wave of the grid ends on a partial batch of surface hits - one batch time per wave, 0.4 ms of a
   // 12.7 ms launch with 8 workgroups per resident place, measured as the intercept of time against pass size - and the more waves, the better the balance: with
   // the cursor the balance is the cursor's and the grid is the resident set (core.hip shade_grid). Chunks are guided: half of an equal share of what is left
   // (as far as the wave has seen the cursor), between 1 and kShadeChunkRounds rounds of 64 entries - long chunks while the queue is long (few atomics on one
@@ -525,9 +494,6 @@ __global__ __launch_bounds__(kBlock, kStage == 1 ? LUM_SHADE_STAGE1_WAVES : kSta
   if (!__syncthreads_or((int) (chunk < n_sched))) return;
   next_len = guided(chunk + chunk_len);
   if (lane == 0u) grabbed = atomicAdd(cursor, next_len);
-#else
-  const uint32_t rounds = (n_input + gridDim.x * kBlock - 1) / (gridDim.x * kBlock);
-#endif
   // Paths that left the scene only add the sky term; the surface vertices are two orders of magnitude more work. A wave therefore
   // collects the indices of its surface hits in LDS and shades them 64 at a time, so that misses do not leave lanes idle during the
   // expensive part (the reference sorts tasks by hit type for the same reason, cuda/kernels.cuh:391-484).
@@ -537,7 +503,7 @@ __global__ __launch_bounds__(kBlock, kStage == 1 ? LUM_SHADE_STAGE1_WAVES : kSta
   // the candidate loop's table lines and handles of the first lights, in LDS (dev_light.h StagedLights)
   StagedLights staged_lights{nullptr, nullptr, 0u};
 #if LUM_LDS_LIGHTS
-  if (kStage != 2) {
+  {
     __shared__ LdsF4 lds_light_table[4u * LUM_LDS_LIGHTS];
     __shared__ unsigned long long lds_light_handles[LUM_LDS_LIGHTS];
     const uint32_t staged = lights_present ? min(sc.num_lights, (uint32_t) LUM_LDS_LIGHTS) : 0u;
@@ -554,22 +520,15 @@ __global__ __launch_bounds__(kBlock, kStage == 1 ? LUM_SHADE_STAGE1_WAVES : kSta
   // fused resolve: an entry's parent word and slot are fetched one round ahead (two registers across the batch in between: one dependent round trip less per round)
   uint32_t parent_ahead = 0u, slot_ahead = 0u;
   if (resolve_parents) {
-#if LUM_SHADE_DYNAMIC
     const uint32_t i0 = entry_at(chunk);
-#else
-    const uint32_t i0 = blockIdx.x * kBlock + threadIdx.x;
-#endif
     if (i0 < n) { parent_ahead = in.parent[i0]; slot_ahead = fbits(reinterpret_cast<const float*>(&in.dir_slot[i0])[3]); }
     else if (i0 < n_input) parent_ahead = fused_dev->ended_prev[i0 - n];
   }
-  for (uint32_t round = 0;; round++) {
-#if LUM_SHADE_DYNAMIC
+  // (the counter is unused since the grid-stride form of this loop left; the loop keeps its shape because without the counter's increment block the compiler lays the
+  // kernel out differently - up to 24 bytes more scratch and a few hundred instructions' difference per instance, profiles/retired_variants_isa_identity.txt)
+  for ([[maybe_unused]] uint32_t round = 0;; round++) {
     const bool input_done = chunk >= n_sched;
-#else
-    const bool input_done = round >= rounds;
-#endif
     if (!input_done) {
-#if LUM_SHADE_DYNAMIC
       const uint32_t i = entry_at(chunk + chunk_round * 64u);
       if (++chunk_round * 64u == chunk_len) {  // on to the chunk fetched ahead, and one more on its way
         chunk_round = 0u;
@@ -579,12 +538,6 @@ __global__ __launch_bounds__(kBlock, kStage == 1 ? LUM_SHADE_STAGE1_WAVES : kSta
         if (lane == 0u) grabbed = atomicAdd(cursor, next_len);
       }
       const uint32_t i_ahead = entry_at(chunk + chunk_round * 64u);  // (none once the schedule is used up)
-      const bool have_ahead = true;
-#else
-      const uint32_t i = (round * gridDim.x + blockIdx.x) * kBlock + threadIdx.x;
-      const uint32_t i_ahead = ((round + 1u) * gridDim.x + blockIdx.x) * kBlock + threadIdx.x;
-      const bool have_ahead = round + 1u < rounds;
-#endif
       bool is_hit = false, is_sky = false;
       if (resolve_parents) {  // the vertex this entry continues: its sum, before the entry's own emission or sky term
         const FusedResolve& fused = *fused_dev;
@@ -594,8 +547,8 @@ __global__ __launch_bounds__(kBlock, kStage == 1 ? LUM_SHADE_STAGE1_WAVES : kSta
         const uint32_t p = parent_ahead;
         uint32_t slot = slot_ahead;
         {
-          if (have_ahead && i_ahead < n) { parent_ahead = in.parent[i_ahead]; slot_ahead = fbits(reinterpret_cast<const float*>(&in.dir_slot[i_ahead])[3]); }
-          else if (have_ahead && i_ahead < n_input) parent_ahead = fused.ended_prev[i_ahead - n];  // (its slot: with the vertex's records below)
+          if (i_ahead < n) { parent_ahead = in.parent[i_ahead]; slot_ahead = fbits(reinterpret_cast<const float*>(&in.dir_slot[i_ahead])[3]); }
+          else if (i_ahead < n_input) parent_ahead = fused.ended_prev[i_ahead - n];  // (its slot: with the vertex's records below)
         }
         if (i < n_input) {
           ip = p & kParentMask;
@@ -661,7 +614,7 @@ __global__ __launch_bounds__(kBlock, kStage == 1 ? LUM_SHADE_STAGE1_WAVES : kSta
         const uint32_t hit_type = in.hit_id[i].x;
         if (hit_type == kHitSky) {
           const uint4 aux = in.aux[i];
-          if (kStage != 1 && (aux.w & kStAllowAmbient)) {
+          if (aux.w & kStAllowAmbient) {
             if (kSkyMode == kSkyDefault) is_sky = true;  // the atmosphere is ray-marched by k_sky
             else if (kSkyMode == kSkyHdri) {
               const float4 o4 = in.origin_t[i], d4 = in.dir_slot[i];
@@ -705,19 +658,12 @@ __global__ __launch_bounds__(kBlock, kStage == 1 ? LUM_SHADE_STAGE1_WAVES : kSta
       const uint32_t slot = fbits(d4.w), state = aux.w;
       const Col record_in = record_unpack(U2{aux.x, aux.y});
       {
-        if (kStage != 1) vertices++;
+        vertices++;
         const V3 origin = v3(o4.x, o4.y, o4.z), ray = v3(d4.x, d4.y, d4.z);
         const V3 hit_origin = origin + ray * o4.w;
         SamplerT<kTable> smp{sc.bluenoise_2d, hid.z & 0xFFFFu, hid.z >> 16, path_sample_id(hid.w), depth_const};
-        smp.detect_uniform();
         smp.use_table(sc.sobol_table + (size_t) depth_const * kRndTargetCount * sc.sobol_stride, sc.sobol_stride, sc.sobol_first);  // (kTable: the pass has one)
         const GeoContext g = build_context(sc, hit_origin, ray, state, hid.x, hid.y, in.hit_scene_tri[i] & kHitTriMask, aux.z);
-        if (LUM_DUP & 4) {  // (measurement: see LUM_DUP in dev_light.h)
-          V3 ho = hit_origin; uint32_t tri = hid.y;
-          asm volatile("" : "+v"(ho.x), "+v"(ho.y), "+v"(tri));
-          const GeoContext again = build_context(sc, ho, ray, state, hid.x, tri, in.hit_scene_tri[i] & kHitTriMask, aux.z);
-          dup_sink(again.position); dup_sink(again.normal); dup_sink(again.V); dup_sink(again.params.roughness()); dup_sink(again.params.emission()); dup_sink(again.face_normal_packed);
-        }
         // the volume the vertex is in: without an ocean the stack holds the fog or nothing for the whole path
         const uint32_t top_volume = kWater ? volume_stack_peek(hid.w, false) : (sc.fog_active ? (uint32_t) kVolumeFog : (uint32_t) kVolumeNone);
         const uint32_t second_volume = kWater ? volume_stack_peek(hid.w, true) : (uint32_t) kVolumeNone;
@@ -733,8 +679,7 @@ __global__ __launch_bounds__(kBlock, kStage == 1 ? LUM_SHADE_STAGE1_WAVES : kSta
 #define LUM_ABLATE 0  // measurement only: 1 skips light sampling, 2 the BSDF light direction, 4 the bounce (results are wrong)
 #endif
         float light_root_sum = 0.0f;
-        if (kStage == 2) { if (geo_allowed) light_root_sum = reinterpret_cast<const float*>(&nee.bsdf_weight_sum[i])[3]; }
-        else if (geo_allowed) {
+        if (geo_allowed) {
           LightSample ls;
           if (LUM_ABLATE & 1) { ls.light_id = kLightIdInvalid; ls.root_sum = 1.0f; ls.color = splat(0.0f); ls.ray = v3(0.0f, 0.0f, 1.0f); ls.dist = 1.0f; }
           else ls = sample_light(sc, g, smp, clock, staged_lights);
@@ -748,19 +693,12 @@ __global__ __launch_bounds__(kBlock, kStage == 1 ? LUM_SHADE_STAGE1_WAVES : kSta
             s_geo_ids.x = target.x; s_geo_ids.y = target.y;
           }
         }
-        if (kStage == 1) {
-          st_stream(&nee.geo_color_light[i], geo_cl);
-          if (geo_allowed) reinterpret_cast<float*>(&nee.bsdf_weight_sum[i])[3] = light_root_sum;
-        }
-        else {
         // the shading frame is formed after the light sampling: its thirteen registers need not live through the candidate loop
         const LocalFrame lf = local_frame(sc, g);
-        if (LUM_DUP & 32) { const LocalFrame again = local_frame(sc, dup_launder(g)); dup_sink(again.V); dup_sink(again.face_normal); dup_sink(again.to_z.x); dup_sink(again.energy.conductor); dup_sink(again.energy.glossy); dup_sink(again.energy.dielectric); }
         if (geo_allowed) {
           LightDirSample lb;
           if (LUM_ABLATE & 2) { lb.ray = v3(0.0f, 0.0f, 1.0f); lb.weight = splat(0.0f); lb.probability = 0.0f; }
           else lb = sample_light_direction(lf, g, smp);
-          if (LUM_DUP & 16) { const LightDirSample again = sample_light_direction(lf, dup_launder(g), smp); dup_sink(again.ray); dup_sink(again.weight); dup_sink(again.probability); }
           bs_rp = make_float4(lb.ray.x, lb.ray.y, lb.ray.z, lb.probability);
           if (lb.probability != 0.0f) {
             want_lq = true;
@@ -771,7 +709,6 @@ __global__ __launch_bounds__(kBlock, kStage == 1 ? LUM_SHADE_STAGE1_WAVES : kSta
         BounceSample bounce;
         if (LUM_ABLATE & 4) { bounce.ray = g.normal; bounce.weight = splat(0.5f); bounce.transparent_pass = false; bounce.microfacet_based = false; }
         else bounce = sample_bounce(lf, g, smp, 0);
-        if (LUM_DUP & 8) { const BounceSample again = sample_bounce(lf, dup_launder(g), smp, 0); dup_sink(again.ray); dup_sink(again.weight); dup_sink((uint32_t) again.transparent_pass); }
         uint4 amb = make_uint4(0u, 0u, 0u, 0u);
         if (kSkyMode != kSkyDefault) {  // ambient: the bounce direction doubles as the sample (direct_lighting.cuh:388-405)
           const Col ambient = (kSkyMode == kSkyHdri) ? sky_hdri_color(sc, g.position, bounce.ray, 0u) : sky;
@@ -832,7 +769,7 @@ __global__ __launch_bounds__(kBlock, kStage == 1 ? LUM_SHADE_STAGE1_WAVES : kSta
           st_stream(&nee.sun[i], sun);
           LUM_LAP(clock, 5);
         }
-        if (kStage == 0) st_stream(&nee.geo_color_light[i], geo_cl);
+        st_stream(&nee.geo_color_light[i], geo_cl);
         st_stream(&nee.bsdf_ray_prob[i], bs_rp); st_stream(&nee.bsdf_weight_sum[i], bs_ws);
         st_stream(&nee.ambient[i], amb);
 
@@ -882,23 +819,7 @@ __global__ __launch_bounds__(kBlock, kStage == 1 ? LUM_SHADE_STAGE1_WAVES : kSta
           n_aux = make_uint4(rp.x, rp.y, medium, new_state);
           n_hid = make_uint4(g.instance_id, g.tri_id, hid.z, hid.w);
         }
-        }  // kStage != 1
       }
-    }
-    if (kStage == 1) {  // the one list this stage appends to
-      const unsigned long long bg = __ballot(want_geo);
-      if (bg) {
-        uint32_t base = 0;
-        if (lane == (uint32_t) __builtin_ctzll(bg)) base = atomicAdd(ctrl + kCtlShadowItems, (uint32_t) __popcll(bg));
-        base = __shfl(base, __builtin_ctzll(bg));
-        if (want_geo) {
-          const uint32_t j = base + (uint32_t) __popcll(bg & below);
-          st_stream(&sq.origin_dist[j], make_float4(s_origin.x, s_origin.y, s_origin.z, s_geo_dir.w));
-          st_stream(&sq.dir_out[j], make_float4(s_geo_dir.x, s_geo_dir.y, s_geo_dir.z, bitsf(i)));
-          st_stream(&sq.ids[j], s_geo_ids);
-        }
-      }
-      continue;
     }
     const bool amb_deferred = reuse_ambient && want_amb && survive;  // answered by the path's next closest-hit ray
     if (amb_deferred) { want_amb = false; vertices += 1u << 16; }   // counted in the upper half of the lane's vertex counter (a lane shades a few hundred vertices per launch)
@@ -1260,8 +1181,6 @@ __global__ __launch_bounds__(kBlock) void k_resolve_listed(DeviceScene sc, PathQ
 // space scaled by 1 / particles_scale so that ray parameters stay world distances; a hit closer than the surface hit replaces it. Runs the
 // same traversal on the particle tree (the scene argument carries that tree in place of the surfaces').
 struct ParticleQuery {
-  static constexpr bool kDual = false;
-  static constexpr bool kSpeculate = false;
   static constexpr bool kOrdered = true;
   static constexpr int kFarFirst = 0;
   static constexpr bool kCull = true;
@@ -1323,7 +1242,7 @@ __global__ LUM_TRACE_BOUNDS void k_trace_particles(DeviceScene particle_tree, Pa
   pq.particles_scale = particle_tree.particles_scale; pq.particles_speed = particle_tree.particles_speed;
   pq.direction = v3(particle_tree.particles_direction[0], particle_tree.particles_direction[1], particle_tree.particles_direction[2]);
   pq.bluenoise = particle_tree.bluenoise_2d;
-  LUM_TRACE_ITEMS(particle_tree, ctrl[kCtlPaths], ctrl + kCtlParticleCursor, pq, st, rays, lds_nodes);
+  trace_items(particle_tree, ctrl[kCtlPaths], ctrl + kCtlParticleCursor, pq, st, rays, lds_nodes);
 }
 
 // particle_process_tasks (particle.cuh:7-108): light sample, sun, phase-function bounce whose direction doubles as the ambient sample. The
@@ -2320,7 +2239,7 @@ __global__ LUM_TRACE_BOUNDS void k_trace_rays(DeviceScene sc, uint32_t n, const 
   uint32_t rays = 0;
   RaysQuery q;
   q.origins = origins; q.dirs = dirs; q.ignore = ignore; q.out = out;
-  LUM_TRACE_ITEMS(sc, n, cursor, q, st, rays, lds_nodes);
+  trace_items(sc, n, cursor, q, st, rays, lds_nodes);
   flush_stats(counters, st, rays, kCntTrace, kCntNodes, kCntTris, kCntNodesLds);
 }
 

@@ -42,7 +42,7 @@ struct WavefrontKernels {
   void (*resolve_listed)(uint32_t grid, hipStream_t s, const DeviceScene& sc, const PathQueue& in, const NeeQueue& nee, const ShadowQueue& sq, float4* results, const uint32_t* ctrl);
   void (*resolve_ended)(uint32_t grid, hipStream_t s, const DeviceScene& sc, const PathQueue& in, const NeeQueue& nee, const ShadowQueue& sq, float4* results, const uint32_t* ctrl,
                         const uint32_t* list);
-  bool fused_resolve;  // k_shade resolves the previous depth's vertices itself when asked to (FusedResolve; not in the staged-shade experiment build)
+  bool fused_resolve;  // k_shade resolves the previous depth's vertices itself when asked to (FusedResolve; the fast flavour only)
   // fog (dev_volume.h): light scattered into the rays of a depth, its summation, the scattering events and their bounce
   void (*volume_inscatter)(uint32_t grid, hipStream_t s, const DeviceScene& sc, const PathQueue& in, const VolumeQueue& vq, const ShadowQueue& sq, uint32_t* ctrl,
                            uint32_t depth_const);

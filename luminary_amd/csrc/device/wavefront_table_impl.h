@@ -62,24 +62,13 @@ static void sky_inscattering(uint32_t grid, hipStream_t s, const DeviceScene& sc
 }
 static void shade(uint32_t grid, hipStream_t s, const DeviceScene& sc, const PathQueue& in, const PathQueue& out, const NeeQueue& nee, const ShadowQueue& sq, float4* results,
                   uint32_t* ctrl, uint32_t depth_const, uint64_t* counters, uint32_t ambient_reuse, const FusedResolve* fused_dev, uint32_t fused_flags) {
-#if LUM_SHADE_STAGED
-  auto* k1 = sc.sky_mode == kSkyDefault ? k_shade<kSkyDefault, false, 1> : sc.sky_mode == kSkyHdri ? k_shade<kSkyHdri, false, 1> : k_shade<kSkyConstantColor, false, 1>;
-  auto* k2 = sc.sky_mode == kSkyDefault ? k_shade<kSkyDefault, false, 2> : sc.sky_mode == kSkyHdri ? k_shade<kSkyHdri, false, 2> : k_shade<kSkyConstantColor, false, 2>;
-  if (sc.ocean_active) {
-    k1 = sc.sky_mode == kSkyDefault ? k_shade<kSkyDefault, true, 1> : sc.sky_mode == kSkyHdri ? k_shade<kSkyHdri, true, 1> : k_shade<kSkyConstantColor, true, 1>;
-    k2 = sc.sky_mode == kSkyDefault ? k_shade<kSkyDefault, true, 2> : sc.sky_mode == kSkyHdri ? k_shade<kSkyHdri, true, 2> : k_shade<kSkyConstantColor, true, 2>;
-  }
-  hipLaunchKernelGGL(k1, dim3(grid), dim3(kBlock), 0, s, sc, in, out, nee, sq, results, ctrl, depth_const, counters, ambient_reuse, fused_dev, fused_flags);
-  hipLaunchKernelGGL(k2, dim3(grid), dim3(kBlock), 0, s, sc, in, out, nee, sq, results, ctrl, depth_const, counters, ambient_reuse, fused_dev, fused_flags);
-#else
   auto* k = sc.sky_mode == kSkyDefault ? k_shade<kSkyDefault, false> : sc.sky_mode == kSkyHdri ? k_shade<kSkyHdri, false> : k_shade<kSkyConstantColor, false>;
   if (sc.ocean_active) k = sc.sky_mode == kSkyDefault ? k_shade<kSkyDefault, true> : sc.sky_mode == kSkyHdri ? k_shade<kSkyHdri, true> : k_shade<kSkyConstantColor, true>;
   if (sc.sobol_table) {  // the pass has a Sobol table (dev_sampler.h): the instances that read it instead of hashing
-    k = sc.sky_mode == kSkyDefault ? k_shade<kSkyDefault, false, 0, true> : sc.sky_mode == kSkyHdri ? k_shade<kSkyHdri, false, 0, true> : k_shade<kSkyConstantColor, false, 0, true>;
-    if (sc.ocean_active) k = sc.sky_mode == kSkyDefault ? k_shade<kSkyDefault, true, 0, true> : sc.sky_mode == kSkyHdri ? k_shade<kSkyHdri, true, 0, true> : k_shade<kSkyConstantColor, true, 0, true>;
+    k = sc.sky_mode == kSkyDefault ? k_shade<kSkyDefault, false, true> : sc.sky_mode == kSkyHdri ? k_shade<kSkyHdri, false, true> : k_shade<kSkyConstantColor, false, true>;
+    if (sc.ocean_active) k = sc.sky_mode == kSkyDefault ? k_shade<kSkyDefault, true, true> : sc.sky_mode == kSkyHdri ? k_shade<kSkyHdri, true, true> : k_shade<kSkyConstantColor, true, true>;
   }
   hipLaunchKernelGGL(k, dim3(grid), dim3(kBlock), 0, s, sc, in, out, nee, sq, results, ctrl, depth_const, counters, ambient_reuse, fused_dev, fused_flags);
-#endif
 }
 static void shade_debug(uint32_t grid, hipStream_t s, const DeviceScene& sc, const PathQueue& in, float4* results, const uint32_t* ctrl) {
   hipLaunchKernelGGL(k_shade_debug, dim3(grid), dim3(kBlock), 0, s, sc, in, results, ctrl);
@@ -172,7 +161,7 @@ static void denoise_finish(uint32_t grid, hipStream_t s, const DenoiseArgs& p, c
 }
 
 static const WavefrontKernels kTable = {LUM_FLAVOUR_NAME, (uint32_t) kTraceBlock, set_ray_kernel_lds, init_sampler_seeds, sobol_table, generate,    generate_adaptive, trace,  sky_inscattering, shade,
-                                        shade_debug,      sky,              light_query,        shadow_rays, resolve, resolve_reuse, resolve_listed, resolve_ended, LUM_FAST && !LUM_SHADE_STAGED, volume_inscatter, volume_resolve, volume_events, volume_bounce, trace_particles, particle_shade, trace_ocean, ocean_shade, clouds_list, clouds_march, clouds, trace_rays,
+                                        shade_debug,      sky,              light_query,        shadow_rays, resolve, resolve_reuse, resolve_listed, resolve_ended, LUM_FAST != 0, volume_inscatter, volume_resolve, volume_events, volume_bounce, trace_particles, particle_shade, trace_ocean, ocean_shade, clouds_list, clouds_march, clouds, trace_rays,
                                         camera_rays,      guide,            guide_normalise,    denoise_prepare, denoise_atrous, denoise_finish};
 
 }  // namespace table

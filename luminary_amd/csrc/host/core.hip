@@ -58,7 +58,7 @@ struct LumContext {
   bool has_scene = false;
   uint64_t bvh_stats[4] = {0, 0, 0, 0};
   int ambient_reuse = -1;         // -1 by flavour (fast: on), 0 off, 1 on (lumc_set_ambient_reuse; LUM_AMBIENT_REUSE)
-  uint32_t shade_grid_rounds = LUM_SHADE_DYNAMIC ? 2 : 8;  // k_shade's grid as a multiple of its resident set (0: the common 2048-workgroup cap); LUM_SHADE_GRID
+  uint32_t shade_grid_rounds = 2;  // k_shade's grid as a multiple of its resident set (0: the common 2048-workgroup cap); LUM_SHADE_GRID
   int fused_resolve = 1;          // with the fast flavour's ambient reuse: k_shade resolves the previous depth's vertices itself (lumc_set_fused_resolve; LUM_FUSED_RESOLVE)
   void* fused_block = nullptr;    // what that needs beyond the usual work buffers: a third path queue, the parent words, a second set of NEE records, the fallback rays' items
   bool fused_records_stale = false;  // a queue's planes changed places (ray-sorting mode 3) since the records were written
@@ -67,10 +67,9 @@ struct LumContext {
   size_t sobol_entries = 0;
   int sobol_table = 1;              // LUM_SOBOL_TABLE_RT=0: the sampler hashes every number itself
   uint32_t* d_ended[2] = {nullptr, nullptr};  // a depth's vertices that no entry continues, by the depth's parity (k_shade lists them; the next depth's k_shade resolves them, or k_resolve_ended)
-  // ... the next depth's k_shade (1) or k_resolve_ended after the depth's visibility pass (0; LUM_FUSED_ENDED=0). k_shade only takes the listed vertices
-  // when its input comes through the cursor (kernels.h: LUM_SHADE_DYNAMIC): a build without it keeps the separate kernel, whatever is asked for.
-  int fused_ended = LUM_SHADE_DYNAMIC ? 1 : 0;
-  int fused_ended_default = LUM_SHADE_DYNAMIC ? 1 : 0;  // what lumc_set_fused_resolve(1) goes back to (the environment's choice, if any)
+  // ... the next depth's k_shade (1) or k_resolve_ended after the depth's visibility pass (0; LUM_FUSED_ENDED=0)
+  int fused_ended = 1;
+  int fused_ended_default = 1;  // what lumc_set_fused_resolve(1) goes back to (the environment's choice, if any)
   FusedResolve* d_fused = nullptr;  // six records in device memory: the previous depth's queue (three buffers) and NEE records (two) by depth % 6
   NeeQueue nee2{};
   ShadowQueue fallback{};
@@ -428,16 +427,11 @@ inline uint32_t shade_grid(const LumContext* ctx, uint32_t n) {
   const uint32_t blocks = (n + kBlock - 1) / kBlock;
   const uint32_t resident = ctx->trace_blocks * 3u;  // trace_blocks = the device's CUs (one persistent ray workgroup each)
   // (not with an ocean: k_shade<.., ocean> keeps a scratch frame and its workgroups cost more to start - Example-class scene with an ocean, 8 rounds: shade +2 %)
-#if LUM_SHADE_DYNAMIC
   // input by cursor (kernels.h): twice the resident set. The second half only starts when the queue is used up and leaves at once; what it buys is that every
   // place is taken from the start (hall, k_shade per 3 steps: fixed shares 345 ms | cursor, 1 x resident 337 | 2 x: 333 | 3 x: 331 | 4 x: 332; the scan and
   // the Example-class scene, whose launches are short, are level at 1-2 x and lose 3-5 % at 3-4 x: profiles/r05_ab_experiments.txt). LUM_SHADE_GRID=<rounds>.
   const uint32_t rounds = ctx->shade_grid_rounds;
   const uint32_t cap = resident * (rounds ? rounds : 1u);
-#else
-  const uint32_t rounds = ctx->scene.ocean_active ? 0u : ctx->shade_grid_rounds;
-  const uint32_t cap = rounds ? resident * rounds : 2048u;
-#endif
   return blocks < 1 ? 1 : std::min(blocks, cap);
 }
 
@@ -651,7 +645,7 @@ int lumc_context_create(int device_ordinal, LumContext** out) {
   if (const char* e = getenv("LUM_FUSED_RESOLVE")) ctx->fused_resolve = atoi(e) != 0 ? 1 : 0;
   if (const char* e = getenv("LUM_SHADE_GRID")) ctx->shade_grid_rounds = (uint32_t) atoi(e);
   if (const char* e = getenv("LUM_SOBOL_TABLE_RT")) ctx->sobol_table = atoi(e) != 0 ? 1 : 0;
-  if (const char* e = getenv("LUM_FUSED_ENDED")) ctx->fused_ended = ctx->fused_ended_default = (LUM_SHADE_DYNAMIC && atoi(e) != 0) ? 1 : 0;
+  if (const char* e = getenv("LUM_FUSED_ENDED")) ctx->fused_ended = ctx->fused_ended_default = atoi(e) != 0 ? 1 : 0;
   if (const char* e = getenv("LUM_DENOISE_LDS")) ctx->denoise_lds = atoi(e) != 0 ? 1 : 0;
   if (const char* f = getenv("LUM_FLAVOUR")) ctx->wf = (std::strcmp(f, "exact") == 0) ? wavefront_kernels_exact() : wavefront_kernels_fast();
   *out = ctx;
@@ -703,284 +697,6 @@ void lumc_context_destroy(LumContext* ctx) {
 
 const char* lumc_last_error(const LumContext* ctx) { return ctx ? ctx->error.c_str() : "null context"; }
 uint32_t lumc_scene_view_sizeof(void) { return (uint32_t) sizeof(LumDeviceSceneView); }
-
-// ---- 8-wide quantised nodes (Bvh8Node, dev_scene.h) from a finished 4-wide tree ----
-// Every surviving node absorbs inner children, largest surface area first, while at most eight children result; the absorbed nodes
-// disappear. `keep`: nodes referenced from outside (the root, the roots of the meshes), which survive by construction since nothing has them as
-// a child. Survivors keep their relative order (the 4-wide array is already "top of the tree first"). Returns false when the traversal stack
-// (dev_trace.h kStackSize, up to seven pushes per level) could overflow.
-struct WideChild { float lo[3], hi[3]; uint32_t ref; };
-static float box_area(const WideChild& c) {
-  const float dx = c.hi[0] - c.lo[0], dy = c.hi[1] - c.lo[1], dz = c.hi[2] - c.lo[2];
-  return dx * dy + dy * dz + dz * dx;
-}
-static uint32_t node_children(const Bvh4Node& n, WideChild* out) {
-  uint32_t m = 0;
-  for (int k = 0; k < 4; k++) {
-    if (n.child[k] == kBvhEmpty) continue;
-    out[m] = WideChild{{n.lo_x[k], n.lo_y[k], n.lo_z[k]}, {n.hi_x[k], n.hi_y[k], n.hi_z[k]}, n.child[k]};
-    m++;
-  }
-  return m;
-}
-static bool widen_to_bvh8(const std::vector<Bvh4Node>& in, const std::vector<uint32_t>& keep, std::vector<Bvh8Node>& out, std::vector<uint32_t>& old_to_new,
-                          std::vector<uint32_t>* levels_out) {  // levels_out[r]: levels of the 8-wide tree below keep[r]
-  const size_t n = in.size();
-  std::vector<std::vector<WideChild>> wide(n);
-  std::vector<uint8_t> survives(n, 0);
-  std::vector<uint32_t> level(n, 0), root_of(n, 0);
-  std::vector<uint32_t> queue;
-  for (size_t r = 0; r < keep.size(); r++) if (keep[r] < n && !survives[keep[r]]) { survives[keep[r]] = 1; level[keep[r]] = 1; root_of[keep[r]] = (uint32_t) r; queue.push_back(keep[r]); }
-  std::vector<uint32_t> max_level(keep.size(), 0);
-  for (size_t head = 0; head < queue.size(); head++) {
-    const uint32_t i = queue[head];
-    max_level[root_of[i]] = std::max(max_level[root_of[i]], level[i]);
-    WideChild list[8];
-    uint32_t m = node_children(in[i], list);
-    for (;;) {
-      int best = -1;
-      float best_area = -1.0f;
-      uint32_t best_m = 0;
-      for (uint32_t k = 0; k < m; k++) {
-        const uint32_t ref = list[k].ref;
-        if (ref & kBvhLeafBit) continue;
-        uint32_t cm = 0;
-        for (int j = 0; j < 4; j++) if (in[ref].child[j] != kBvhEmpty) cm++;
-        if (cm == 0 || m - 1 + cm > 8) continue;
-        const float a = box_area(list[k]);
-        if (a > best_area) { best_area = a; best = (int) k; best_m = cm; }
-      }
-      if (best < 0) break;
-      WideChild sub[4];
-      const uint32_t cm = node_children(in[list[best].ref], sub);
-      (void) best_m;
-      list[best] = sub[0];
-      for (uint32_t j = 1; j < cm; j++) list[m++] = sub[j];
-    }
-    wide[i].assign(list, list + m);
-    for (uint32_t k = 0; k < m; k++) {
-      const uint32_t ref = list[k].ref;
-      if (!(ref & kBvhLeafBit) && !survives[ref]) { survives[ref] = 1; level[ref] = level[i] + 1; root_of[ref] = root_of[i]; queue.push_back(ref); }
-    }
-  }
-  old_to_new.assign(n, 0xFFFFFFFFu);
-  uint32_t count = 0;
-  for (size_t i = 0; i < n; i++) if (survives[i]) old_to_new[i] = count++;
-  out.assign(count, Bvh8Node{});
-  for (size_t i = 0; i < n; i++) {
-    if (!survives[i]) continue;
-    Bvh8Node& o = out[old_to_new[i]];
-    std::memset(&o, 0, sizeof(o));
-    const std::vector<WideChild>& ch = wide[i];
-    float lo[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, hi[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
-    for (const WideChild& c : ch) for (int a = 0; a < 3; a++) { lo[a] = std::min(lo[a], c.lo[a]); hi[a] = std::max(hi[a], c.hi[a]); }
-    if (ch.empty()) for (int a = 0; a < 3; a++) { lo[a] = 0.0f; hi[a] = 0.0f; }
-    float scale[3];
-    for (int a = 0; a < 3; a++) {
-      o.origin[a] = lo[a];
-      const float extent = hi[a] - lo[a];
-      int e = -126;
-      if (extent > 0.0f && std::isfinite(extent)) {
-        int ex;
-        std::frexp(extent / 255.0f, &ex);  // extent / 255 = f * 2^ex with f in [0.5, 1): 2^ex >= extent / 255
-        e = std::max(-126, std::min(127, ex));
-      }
-      // the quotient must stay below 256 after the float subtraction's rounding: one step coarser when it does not
-      while (e < 127 && std::ceil((hi[a] - lo[a]) / std::ldexp(1.0f, e)) > 255.0f) e++;
-      o.exp[a] = (uint8_t) (e + 127);
-      scale[a] = std::ldexp(1.0f, e);
-    }
-    uint8_t* qlo[3] = {o.lo_x, o.lo_y, o.lo_z};
-    uint8_t* qhi[3] = {o.hi_x, o.hi_y, o.hi_z};
-    for (uint32_t k = 0; k < 8; k++) {
-      if (k >= ch.size()) {
-        o.child[k] = kBvhEmpty;
-        for (int a = 0; a < 3; a++) { qlo[a][k] = 255; qhi[a][k] = 0; }
-        continue;
-      }
-      const WideChild& c = ch[k];
-      o.child[k] = (c.ref & kBvhLeafBit) ? c.ref : old_to_new[c.ref];
-      for (int a = 0; a < 3; a++) {
-        const float l = std::floor((c.lo[a] - lo[a]) / scale[a]), h = std::ceil((c.hi[a] - lo[a]) / scale[a]);
-        qlo[a][k] = (uint8_t) std::max(0.0f, std::min(255.0f, l));
-        qhi[a][k] = (uint8_t) std::max(0.0f, std::min(255.0f, h));
-      }
-    }
-  }
-  if (levels_out) *levels_out = max_level;
-  return true;
-}
-
-// ---- 8-wide nodes with children in octant slots (Bvh8oNode, dev_scene.h) from a finished 4-wide tree ----
-// Widening as above (a node absorbs its largest inner children while at most eight result). Then, per node: the children take octant slots (greedy:
-// the (child, slot) pair with the largest projection of the child's offset from the node's centre onto the slot's diagonal first, as the reference's
-// bvh.c:1093-1145), the inner children become consecutive nodes in slot order (nodes are numbered in the order the widening queue meets them: the top
-// of the tree first), and the leaf slots' primitives become one consecutive run per node: `leaf_order` is the new order of the leaf items (triangles of
-// the bottom level / records of the top level) as indices into the old one. `is_top[i]`: node i belongs to the top level (its leaves are instance
-// records). Returns false when a node's leaves do not fit the 5-bit offsets (cannot happen with <= 4 primitives per leaf: 8 x 4 = 32).
-struct Bvh8oResult {
-  std::vector<Bvh8oNode> nodes;
-  std::vector<uint32_t> old_to_new;        // for the `keep` roots (others: 0xFFFFFFFF when absorbed)
-  std::vector<uint32_t> tri_order, top_leaf_order;
-  std::vector<uint32_t> levels;            // per keep root
-  uint32_t top_nodes = 0;
-};
-static bool build_bvh8o(const std::vector<Bvh4Node>& in, const std::vector<uint8_t>& is_top, const std::vector<uint32_t>& keep, size_t num_tris, size_t num_top_leaves, Bvh8oResult& out) {
-  const size_t n = in.size();
-  std::vector<std::vector<WideChild>> wide(n);
-  std::vector<uint8_t> survives(n, 0);
-  std::vector<uint32_t> level(n, 0), root_of(n, 0), queue;
-  out.old_to_new.assign(n, 0xFFFFFFFFu);
-  for (size_t r = 0; r < keep.size(); r++) if (keep[r] < n && !survives[keep[r]]) { survives[keep[r]] = 1; level[keep[r]] = 1; root_of[keep[r]] = (uint32_t) r; out.old_to_new[keep[r]] = (uint32_t) queue.size(); queue.push_back(keep[r]); }
-  out.levels.assign(keep.size(), 0);
-  out.tri_order.clear(); out.top_leaf_order.clear();
-  out.tri_order.reserve(num_tris); out.top_leaf_order.reserve(num_top_leaves);
-  out.nodes.clear();
-  out.top_nodes = 0;
-  for (size_t head = 0; head < queue.size(); head++) {
-    const uint32_t i = queue[head];
-    out.levels[root_of[i]] = std::max(out.levels[root_of[i]], level[i]);
-    WideChild list[8];
-    uint32_t m = node_children(in[i], list);
-    for (;;) {
-      int best = -1;
-      float best_area = -1.0f;
-      for (uint32_t k = 0; k < m; k++) {
-        const uint32_t ref = list[k].ref;
-        if (ref & kBvhLeafBit) continue;
-        uint32_t cm = 0;
-        for (int j = 0; j < 4; j++) if (in[ref].child[j] != kBvhEmpty) cm++;
-        if (cm == 0 || m - 1 + cm > 8) continue;
-        const float a = box_area(list[k]);
-        if (a > best_area) { best_area = a; best = (int) k; }
-      }
-      if (best < 0) break;
-      WideChild sub[4];
-      const uint32_t cm = node_children(in[list[best].ref], sub);
-      list[best] = sub[0];
-      for (uint32_t j = 1; j < cm; j++) list[m++] = sub[j];
-    }
-    // the node's box, slots
-    float lo[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, hi[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
-    for (uint32_t k = 0; k < m; k++) for (int a = 0; a < 3; a++) { lo[a] = std::min(lo[a], list[k].lo[a]); hi[a] = std::max(hi[a], list[k].hi[a]); }
-    if (m == 0) for (int a = 0; a < 3; a++) { lo[a] = 0.0f; hi[a] = 0.0f; }
-    int slot_of[8];
-    {
-      float cost[8][8];
-      for (uint32_t k = 0; k < m; k++)
-        for (int sl = 0; sl < 8; sl++) {
-          float c = 0.0f;
-          for (int a = 0; a < 3; a++) c += (((sl >> a) & 1) ? 1.0f : -1.0f) * (0.5f * (list[k].lo[a] + list[k].hi[a]) - 0.5f * (lo[a] + hi[a]));
-          cost[k][sl] = c;
-        }
-      bool used_k[8] = {false, false, false, false, false, false, false, false}, used_s[8] = {false, false, false, false, false, false, false, false};
-      for (uint32_t it = 0; it < m; it++) {
-        int bk = -1, bs = -1;
-        float best = -FLT_MAX;
-        for (uint32_t k = 0; k < m; k++) if (!used_k[k]) for (int sl = 0; sl < 8; sl++) if (!used_s[sl] && (bk < 0 || cost[k][sl] > best)) { best = cost[k][sl]; bk = (int) k; bs = sl; }
-        used_k[bk] = used_s[bs] = true;
-        slot_of[bk] = bs;
-      }
-    }
-    int child_in_slot[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
-    for (uint32_t k = 0; k < m; k++) child_in_slot[slot_of[k]] = (int) k;
-    Bvh8oNode o;
-    std::memset(&o, 0, sizeof(o));
-    float scale[3];
-    for (int a = 0; a < 3; a++) {
-      o.origin[a] = lo[a];
-      const float extent = hi[a] - lo[a];
-      int e = -126;
-      if (extent > 0.0f && std::isfinite(extent)) {
-        int ex;
-        std::frexp(extent / 255.0f, &ex);
-        e = std::max(-126, std::min(127, ex));
-      }
-      while (e < 127 && std::ceil((hi[a] - lo[a]) / std::ldexp(1.0f, e)) > 255.0f) e++;  // the quotient must stay below 256 after the subtraction's rounding
-      o.exp[a] = (uint8_t) (e + 127);
-      scale[a] = std::ldexp(1.0f, e);
-    }
-    uint8_t* qlo[3] = {o.lo_x, o.lo_y, o.lo_z};
-    uint8_t* qhi[3] = {o.hi_x, o.hi_y, o.hi_z};
-    const bool top = is_top[i] != 0;
-    if (top) out.top_nodes++;
-    std::vector<uint32_t>& leaf_order = top ? out.top_leaf_order : out.tri_order;
-    o.leaf_base = (uint32_t) leaf_order.size();
-    o.child_base = (uint32_t) queue.size();  // where this node's first inner child is about to be numbered
-    for (int sl = 0; sl < 8; sl++) {
-      const int k = child_in_slot[sl];
-      if (k < 0) { for (int a = 0; a < 3; a++) { qlo[a][sl] = 255; qhi[a][sl] = 0; } continue; }
-      const WideChild& c = list[k];
-      for (int a = 0; a < 3; a++) {
-        const float l = std::floor((c.lo[a] - lo[a]) / scale[a]), h = std::ceil((c.hi[a] - lo[a]) / scale[a]);
-        qlo[a][sl] = (uint8_t) std::max(0.0f, std::min(255.0f, l));
-        qhi[a][sl] = (uint8_t) std::max(0.0f, std::min(255.0f, h));
-      }
-      if (c.ref & kBvhLeafBit) {
-        const uint32_t first = c.ref & 0x0FFFFFFFu, count = ((c.ref >> 28) & 7u) + 1u;
-        const uint32_t offset = (uint32_t) leaf_order.size() - o.leaf_base;
-        if (offset > 31u || count > 4u) return false;
-        o.meta[sl] = (uint8_t) (offset | ((count - 1u) << 5));
-        for (uint32_t j = 0; j < count; j++) leaf_order.push_back(first + j);
-      }
-      else {
-        o.imask |= (uint8_t) (1u << sl);
-        survives[c.ref] = 1; level[c.ref] = level[i] + 1; root_of[c.ref] = root_of[i];
-        out.old_to_new[c.ref] = (uint32_t) queue.size();
-        queue.push_back(c.ref);
-      }
-    }
-    out.nodes.push_back(o);
-  }
-  return out.tri_order.size() == num_tris && out.top_leaf_order.size() == num_top_leaves;
-}
-
-// ---- 64-byte quantised nodes (Bvh4QNode, dev_scene.h) from a finished 4-wide tree: node for node, same indices ----
-static void quantise_bvh4(std::vector<Bvh4Node>& nodes) {
-  std::vector<Bvh4QNode> out(nodes.size());
-  for (size_t i = 0; i < nodes.size(); i++) {
-    const Bvh4Node& n = nodes[i];
-    Bvh4QNode& o = out[i];
-    std::memset(&o, 0, sizeof(o));
-    float lo[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, hi[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
-    bool any = false;
-    for (int k = 0; k < 4; k++) {
-      if (n.child[k] == kBvhEmpty) continue;
-      any = true;
-      const float clo[3] = {n.lo_x[k], n.lo_y[k], n.lo_z[k]}, chi[3] = {n.hi_x[k], n.hi_y[k], n.hi_z[k]};
-      for (int a = 0; a < 3; a++) { lo[a] = std::min(lo[a], clo[a]); hi[a] = std::max(hi[a], chi[a]); }
-    }
-    if (!any) for (int a = 0; a < 3; a++) { lo[a] = 0.0f; hi[a] = 0.0f; }
-    float scale[3];
-    for (int a = 0; a < 3; a++) {
-      o.origin[a] = lo[a];
-      const float extent = hi[a] - lo[a];
-      int e = -126;
-      if (extent > 0.0f && std::isfinite(extent)) {
-        int ex;
-        std::frexp(extent / 255.0f, &ex);  // extent / 255 = f * 2^ex with f in [0.5, 1): 2^ex >= extent / 255
-        e = std::max(-126, std::min(127, ex));
-      }
-      while (e < 127 && std::ceil((hi[a] - lo[a]) / std::ldexp(1.0f, e)) > 255.0f) e++;  // the quotient must stay below 256 after the subtraction's rounding
-      o.exp[a] = (uint8_t) (e + 127);
-      scale[a] = std::ldexp(1.0f, e);
-    }
-    uint8_t* qlo[3] = {o.lo_x, o.lo_y, o.lo_z};
-    uint8_t* qhi[3] = {o.hi_x, o.hi_y, o.hi_z};
-    for (int k = 0; k < 4; k++) {
-      o.child[k] = n.child[k];
-      if (n.child[k] == kBvhEmpty) { for (int a = 0; a < 3; a++) { qlo[a][k] = 255; qhi[a][k] = 0; } continue; }
-      const float clo[3] = {n.lo_x[k], n.lo_y[k], n.lo_z[k]}, chi[3] = {n.hi_x[k], n.hi_y[k], n.hi_z[k]};
-      for (int a = 0; a < 3; a++) {
-        const float l = std::floor((clo[a] - lo[a]) / scale[a]), h = std::ceil((chi[a] - lo[a]) / scale[a]);
-        qlo[a][k] = (uint8_t) std::max(0.0f, std::min(255.0f, l));
-        qhi[a][k] = (uint8_t) std::max(0.0f, std::min(255.0f, h));
-      }
-    }
-  }
-  // the array keeps its element type for the upload: the first half of it now holds the 64-byte nodes
-  std::memcpy(nodes.data(), out.data(), out.size() * sizeof(Bvh4QNode));
-}
 
 // The clouds' noise textures (device_cloud.c:62-101): shape and detail once per context, the weather map per seed.
 static int ensure_cloud_noise(LumContext* ctx, uint32_t seed) {
@@ -1065,47 +781,6 @@ static int build_particle_tree(LumContext* ctx, const LumDeviceSceneView* v, Dev
     const uint32_t words[4] = {inst, base, 0u, 0u};
     std::memcpy(&leaves[4 * i + 3], words, 16);
   }
-  uint32_t mesh_root_index = base;
-#if LUM_BVH8
-  {
-    std::vector<Bvh8Node> wide;
-    std::vector<uint32_t> map;
-    std::vector<uint32_t> levels;
-    widen_to_bvh8(nodes, {0u, base}, wide, map, &levels);
-    if (7u * (levels[0] + levels[1]) + 4u > (uint32_t) kStackSize) { ctx->error = "particle BVH too deep for the traversal stack"; return 1; }
-    mesh_root_index = map[base];
-    static_assert(sizeof(Bvh8Node) == sizeof(Bvh4Node), "same 128-byte slot");
-    nodes.resize(wide.size());
-    std::memcpy(nodes.data(), wide.data(), wide.size() * sizeof(Bvh8Node));
-    for (size_t i = 0; i < tlas.prims.size(); i++) { const uint32_t words[4] = {tlas.prims[i], mesh_root_index, 0u, 0u}; std::memcpy(&leaves[4 * i + 3], words, 16); }
-  }
-#endif
-#if LUM_BVH8O
-  {
-    std::vector<uint8_t> is_top(nodes.size(), 0);
-    for (uint32_t i = 0; i < base; i++) is_top[i] = 1;
-    Bvh8oResult r8;
-    if (!build_bvh8o(nodes, is_top, {0u, base}, nt, tlas.prims.size(), r8)) { ctx->error = "8-wide conversion of the particle tree failed"; return 1; }
-    if (r8.levels[0] + r8.levels[1] + 8u > (uint32_t) kStackSize) { ctx->error = "particle BVH too deep for the traversal stack"; return 1; }
-    mesh_root_index = r8.old_to_new[base];
-    std::vector<BvhTri> reordered(tris.size());
-    std::memset(reordered.data(), 0, sizeof(BvhTri) * reordered.size());
-    for (size_t i = 0; i < r8.tri_order.size(); i++) reordered[i] = tris[r8.tri_order[i]];
-    tris.swap(reordered);
-    std::vector<float4> moved(leaves.size());
-    for (size_t i = 0; i < r8.top_leaf_order.size(); i++) {
-      for (int k = 0; k < 3; k++) moved[4 * i + k] = leaves[4 * (size_t) r8.top_leaf_order[i] + k];
-      const uint32_t words[4] = {tlas.prims[r8.top_leaf_order[i]], mesh_root_index, 0u, 0u};
-      std::memcpy(&moved[4 * i + 3], words, 16);
-    }
-    leaves.swap(moved);
-    nodes.resize(r8.nodes.size());
-    std::memcpy(nodes.data(), r8.nodes.data(), r8.nodes.size() * sizeof(Bvh8oNode));
-  }
-#endif
-#if LUM_BVH4Q
-  quantise_bvh4(nodes);
-#endif
   if (upload(ctx, nodes.data(), nodes.size(), &sc.particle_bvh_nodes)) return 1;
   if (upload(ctx, tris.data(), tris.size(), &sc.particle_tris)) return 1;
   if (upload(ctx, leaves.data(), leaves.size(), &sc.particle_leaves)) return 1;
@@ -1125,9 +800,6 @@ static int scene_update(LumContext* ctx, const LumDeviceSceneView* v, unsigned d
   if (v->max_ray_depth > 63) { ctx->error = "max_ray_depth exceeds 63 (6-bit field, device_structs.h:9)"; return 1; }
   const uint32_t total_tris = v->num_meshes ? v->mesh_tri_offset[v->num_meshes] : 0;
   if (dirty & LUMC_DIRTY_MESHES) dirty |= LUMC_DIRTY_INSTANCES;  // the assembled node array holds the per-mesh trees
-#if LUM_BVH8O
-  if (dirty & LUMC_DIRTY_INSTANCES) dirty |= LUMC_DIRTY_MESHES;  // (experiment) the 8-wide conversion reorders the triangles by the assembled tree: an instance edit rebuilds all of it
-#endif
   if (dirty & LUMC_DIRTY_PARTICLES) dirty |= LUMC_DIRTY_CONSTANTS;
   const bool dirty_meshes = (dirty & LUMC_DIRTY_MESHES) != 0, dirty_instances = (dirty & LUMC_DIRTY_INSTANCES) != 0, dirty_lights = (dirty & LUMC_DIRTY_LIGHTS) != 0;
   ctx->has_scene = false;  // until this update has gone through
@@ -1302,7 +974,6 @@ static int scene_update(LumContext* ctx, const LumDeviceSceneView* v, unsigned d
   }
   // ---- renumber: the top of the tree first, in breadth-first order across both levels (top-level leaves continue into the root of
   // their mesh), so that "node index < K" selects the K most visited nodes; the ray kernels stage those in LDS ----
-  std::vector<uint8_t> node_is_top;  // after the renumbering: the node belongs to the top level (LUM_BVH8O)
   {
     const size_t n = nodes.size();
     std::vector<uint32_t> order;
@@ -1395,62 +1066,8 @@ static int scene_update(LumContext* ctx, const LumDeviceSceneView* v, unsigned d
     }
     nodes.swap(renum);
     for (uint32_t m = 0; m < v->num_meshes; m++) mesh_root[m] = new_index[mesh_root[m]];
-    node_is_top.resize(n);
-    for (uint32_t i = 0; i < n; i++) node_is_top[i] = order[i] < sc.tlas_num_nodes ? 1 : 0;
   }
   if (total_tris >= (1u << 28) || nodes.size() >= (1u << 25)) { ctx->error = "scene too large for 28-bit leaf ranges / 32-bit node offsets"; return 1; }
-#if LUM_BVH8
-  {
-    std::vector<uint32_t> keep;
-    keep.push_back(0u);
-    for (uint32_t m = 0; m < v->num_meshes; m++) if (v->mesh_tri_offset[m + 1] > v->mesh_tri_offset[m]) keep.push_back(mesh_root[m]);
-    // the two levels are walked one after the other: their depths add up on the stack
-    std::vector<Bvh8Node> wide;
-    std::vector<uint32_t> map;
-    std::vector<uint32_t> levels;
-    widen_to_bvh8(nodes, keep, wide, map, &levels);
-    uint32_t deepest_mesh = 0;
-    for (size_t r = 1; r < levels.size(); r++) deepest_mesh = std::max(deepest_mesh, levels[r]);
-    if (7u * (levels[0] + deepest_mesh) + 4u > (uint32_t) kStackSize) { ctx->error = "BVH too deep for the traversal stack (8-wide nodes)"; return 1; }
-    uint32_t new_tlas_nodes = 0;
-    for (uint32_t i = 0; i < sc.tlas_num_nodes; i++) if (map[i] != 0xFFFFFFFFu) new_tlas_nodes++;
-    sc.tlas_num_nodes = new_tlas_nodes;
-    for (uint32_t m = 0; m < v->num_meshes; m++) if (v->mesh_tri_offset[m + 1] > v->mesh_tri_offset[m]) mesh_root[m] = map[mesh_root[m]];
-    nodes.resize(wide.size());
-    std::memcpy(nodes.data(), wide.data(), wide.size() * sizeof(Bvh8Node));
-    ctx->bvh_stats[2] = new_tlas_nodes;
-  }
-#endif
-#if LUM_BVH8O
-  {
-    std::vector<uint32_t> keep;
-    keep.push_back(0u);
-    for (uint32_t m = 0; m < v->num_meshes; m++) if (v->mesh_tri_offset[m + 1] > v->mesh_tri_offset[m]) keep.push_back(mesh_root[m]);
-    Bvh8oResult r8;
-    if (!build_bvh8o(nodes, node_is_top, keep, total_tris, tlas_order.size(), r8)) { ctx->error = "8-wide conversion failed (leaf offsets / unreferenced leaves)"; return 1; }
-    uint32_t deepest_mesh = 0;
-    for (size_t r = 1; r < r8.levels.size(); r++) deepest_mesh = std::max(deepest_mesh, r8.levels[r]);
-    if (r8.levels[0] + deepest_mesh + 8u > (uint32_t) kStackSize) { ctx->error = "BVH too deep for the traversal stack (8-wide nodes)"; return 1; }  // one group entry per level + an instance's two
-    {  // the triangles and the top-level leaf records in the order the nodes refer to them
-      std::vector<BvhTri> reordered(blas_tris.size());
-      std::memset(reordered.data(), 0, sizeof(BvhTri) * reordered.size());
-      for (size_t i = 0; i < r8.tri_order.size(); i++) reordered[i] = blas_tris[r8.tri_order[i]];
-      blas_tris.swap(reordered);
-      std::vector<uint32_t> tl(tlas_order.size());
-      for (size_t i = 0; i < tl.size(); i++) tl[i] = tlas_order[r8.top_leaf_order[i]];
-      tlas_order.swap(tl);
-    }
-    for (uint32_t m = 0; m < v->num_meshes; m++) if (v->mesh_tri_offset[m + 1] > v->mesh_tri_offset[m]) mesh_root[m] = r8.old_to_new[mesh_root[m]];
-    sc.tlas_num_nodes = r8.top_nodes;
-    ctx->bvh_stats[2] = r8.top_nodes;
-    static_assert(sizeof(Bvh8oNode) == sizeof(Bvh4Node), "same 128-byte slot");
-    nodes.resize(r8.nodes.size());
-    std::memcpy(nodes.data(), r8.nodes.data(), r8.nodes.size() * sizeof(Bvh8oNode));
-  }
-#endif
-#if LUM_BVH4Q
-  quantise_bvh4(nodes);
-#endif
   ctx->alloc_group = LumContext::kGrpInst;
   if (upload(ctx, nodes.data(), nodes.size(), &sc.bvh_nodes)) return 1;
   if (dirty_meshes) { ctx->alloc_group = LumContext::kGrpMesh; if (upload(ctx, blas_tris.data(), blas_tris.size(), &sc.blas_tris)) return 1; ctx->alloc_group = LumContext::kGrpInst; }
@@ -1472,28 +1089,12 @@ static int scene_update(LumContext* ctx, const LumDeviceSceneView* v, unsigned d
     HIP_TRY(ctx, hipGetDeviceProperties(&prop, ctx->device));
     size_t lds_bytes = prop.maxSharedMemoryPerMultiProcessor ? prop.maxSharedMemoryPerMultiProcessor : prop.sharedMemPerBlock;
     // the ray kernels are compiled for 128 VGPRs: 4 waves per SIMD = 16 waves per CU = one workgroup of kTraceBlock = 1024 threads (both flavours since round 4)
-#ifndef LUM_TRACE_BLOCKS_PER_CU
-#define LUM_TRACE_BLOCKS_PER_CU 1  // experiment: more, smaller workgroups per CU (each with its own, smaller LDS copy of the tree top)
-#endif
-    const int blocks_per_cu = LUM_TRACE_BLOCKS_PER_CU;  // one workgroup of kTraceBlock threads per CU
-    lds_bytes = std::min<size_t>(lds_bytes, 160 * 1024) / blocks_per_cu;
-    lds_bytes = lds_bytes > 16384 ? lds_bytes - 8192 : 0;  // margin: the ray kernels' static LDS (the prefetch experiment's sink) and the runtime's own
+    lds_bytes = std::min<size_t>(lds_bytes, 160 * 1024);
+    lds_bytes = lds_bytes > 16384 ? lds_bytes - 8192 : 0;  // margin: the ray kernels' static LDS (the staged top-level leaf records) and the runtime's own
     lds_bytes = lds_bytes > LUM_LDS_STACK_BYTES ? lds_bytes - LUM_LDS_STACK_BYTES : 0;  // the stacks' share (dev_trace.h, TraversalStack)
     ctx->lds_nodes = (uint32_t) std::min<size_t>(lds_bytes / kNodeBytes, nodes.size());
     if (const char* e = getenv("LUM_LDS_NODES")) ctx->lds_nodes = std::min<uint32_t>((uint32_t) atoi(e), ctx->lds_nodes);
-    ctx->trace_blocks = (uint32_t) prop.multiProcessorCount * blocks_per_cu;
-#if LUM_PHASE_QUEUES
-    // dev_trace_pool.h: per persistent workgroup and pool slot 4 x 16 bytes of query state and the stack entries beyond the LDS ones (once per context)
-    if (!sc.pool_state) {
-      const size_t slots = (size_t) ctx->trace_blocks * LUM_POOL_SLOTS * (LUM_TRACE_BLOCK / 64u);
-      void* a = nullptr; void* b = nullptr;
-      HIP_TRY(ctx, hipMalloc(&a, slots * 4u * sizeof(uint4)));
-      ctx->scene_allocs[LumContext::kGrpOnce].push_back(a);
-      HIP_TRY(ctx, hipMalloc(&b, slots * (size_t) kStackSize * sizeof(unsigned long long)));
-      ctx->scene_allocs[LumContext::kGrpOnce].push_back(b);
-      sc.pool_state = (uint4*) a; sc.pool_stack = (unsigned long long*) b;
-    }
-#endif
+    ctx->trace_blocks = (uint32_t) prop.multiProcessorCount;  // one workgroup of kTraceBlock threads per CU
     // The attribute is a property of the kernel, not of a context: it is set to what the largest scene may ask for (the whole budget computed
     // above), never to this scene's need - a second context with a small scene must not lower the cap a first one launches with.
     const size_t dyn = lds_bytes + LUM_LDS_STACK_BYTES;
@@ -2810,7 +2411,7 @@ int lumc_trace_closest(LumContext* ctx, uint32_t n, const float* d_origins, cons
   if (n == 0) return 0;
   hipStream_t stream = (hipStream_t) stream_;
   uint32_t* cursor = ctx->d_ctrl + kCtlStride * (kCtrlRows - 1);
-  HIP_TRY(ctx, hipMemsetAsync(cursor, 0, sizeof(uint32_t) * 8, stream));  // up to 8 work cursors (dev_trace.h LUM_XCD_RANGES)
+  HIP_TRY(ctx, hipMemsetAsync(cursor, 0, sizeof(uint32_t), stream));  // the work cursor of trace_items (dev_trace.h)
   Launch l(ctx, stream, LUMC_KERNEL_TRACE);
   ctx->wf->trace_rays(grid_persistent(ctx, n), (size_t) ctx->lds_nodes * kNodeBytes + LUM_LDS_STACK_BYTES, stream, ctx->scene, n, d_origins, d_dirs, d_ignore, d_out, cursor, ctx->d_counters,
                       ctx->lds_nodes);
@@ -3429,7 +3030,7 @@ int lumc_set_flavour(LumContext* ctx, int flavour) {
 int lumc_set_fused_resolve(LumContext* ctx, int on) {
   if (!ctx) return 1;
   ctx->fused_resolve = on != 0 ? 1 : 0;
-  ctx->fused_ended = on == 2 ? 0 : ctx->fused_ended_default;  // 2: the vertices whose path ended keep their own kernel (k_resolve_ended) - for comparison; 1: the context's default (LUM_FUSED_ENDED, LUM_SHADE_DYNAMIC)
+  ctx->fused_ended = on == 2 ? 0 : ctx->fused_ended_default;  // 2: the vertices whose path ended keep their own kernel (k_resolve_ended) - for comparison; 1: the context's default (LUM_FUSED_ENDED)
   return 0;
 }
 int lumc_set_sobol_table(LumContext* ctx, int on) {

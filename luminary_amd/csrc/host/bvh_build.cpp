@@ -9,6 +9,7 @@
 #include <chrono>
 #include <cstdio>
 #include <memory>
+#include <mutex>
 #include <numeric>
 #include <thread>
 
@@ -766,7 +767,199 @@ Bvh4 build_bvh4(const Aabb* boxes, uint32_t count, uint32_t max_leaf, uint32_t m
   return Bvh4();
 }
 
+// ---- the scene's tree: what the scene upload (core.hip) computes on the host between the per-mesh builds and the copies to the device ----
+Aabb tri_box(const float* a, const float* b, const float* c) {
+  Aabb box;
+  for (int k = 0; k < 3; k++) { box.lo[k] = std::min(a[k], std::min(b[k], c[k])); box.hi[k] = std::max(a[k], std::max(b[k], c[k])); }
+  return box;
+}
+
+// Host twin of the device transform (cuda/math.cuh:393-489) used to bound instances for the top-level BVH.
+// World->object matrix of one instance, float arithmetic in the exact operation order of dev_math.h's xf_rel_inv applied to the
+// unit vectors (column j = xf_rel_inv(e_j)); rows[i] = (m_i0, m_i1, m_i2, translation_i). The kernels map rays with these rows
+// (dev_trace.h traverse_scene); the oracle derives the same 12 numbers on its own (oracle/o_trace.h tracer_init).
+void instance_inverse_rows(const float* p, float4 rows[3]) {
+  uint32_t a, b;
+  std::memcpy(&a, p + 6, 4); std::memcpy(&b, p + 7, 4);
+  const float ux = 1.0f - ((a & 0xFFFFu) * (1.0f / 0x7FFF)), uy = 1.0f - ((a >> 16) * (1.0f / 0x7FFF));
+  const float uz = 1.0f - ((b & 0xFFFFu) * (1.0f / 0x7FFF)), s = ((b >> 16) * (1.0f / 0x7FFF)) - 1.0f;
+  const float inv_scale[3] = {1.0f / p[3], 1.0f / p[4], 1.0f / p[5]};
+  float col[3][3];
+  for (int j = 0; j < 3; j++) {
+    const float vx = (j == 0 ? 1.0f : 0.0f) * inv_scale[0], vy = (j == 1 ? 1.0f : 0.0f) * inv_scale[1], vz = (j == 2 ? 1.0f : 0.0f) * inv_scale[2];
+    const float duv = ux * vx + uy * vy + uz * vz, duu = ux * ux + uy * uy + uz * uz;
+    const float cx = uy * vz - uz * vy, cy = uz * vx - ux * vz, cz = ux * vy - uy * vx;
+    const float k0 = 2.0f * duv, k1 = s * s - duu, k2 = 2.0f * s;
+    col[j][0] = (ux * k0 + vx * k1) + cx * k2;
+    col[j][1] = (uy * k0 + vy * k1) + cy * k2;
+    col[j][2] = (uz * k0 + vz * k1) + cz * k2;
+  }
+  for (int i = 0; i < 3; i++) rows[i] = make_float4(col[0][i], col[1][i], col[2][i], p[i]);
+}
+
+// World box of an object-space box under the inverse of the map above (double precision, then padded): the top-level BVH must
+// bound the geometry exactly where the ray mapping puts it.
+bool instance_world_box(const float4 rows[3], const Aabb& ob, Aabb& wb) {
+  const double m[3][3] = {{rows[0].x, rows[0].y, rows[0].z}, {rows[1].x, rows[1].y, rows[1].z}, {rows[2].x, rows[2].y, rows[2].z}};
+  const double det = m[0][0] * (m[1][1] * m[2][2] - m[1][2] * m[2][1]) - m[0][1] * (m[1][0] * m[2][2] - m[1][2] * m[2][0]) +
+                     m[0][2] * (m[1][0] * m[2][1] - m[1][1] * m[2][0]);
+  if (!(std::fabs(det) > 0.0) || !std::isfinite(det)) return false;
+  double f[3][3];
+  f[0][0] = (m[1][1] * m[2][2] - m[1][2] * m[2][1]) / det; f[0][1] = (m[0][2] * m[2][1] - m[0][1] * m[2][2]) / det; f[0][2] = (m[0][1] * m[1][2] - m[0][2] * m[1][1]) / det;
+  f[1][0] = (m[1][2] * m[2][0] - m[1][0] * m[2][2]) / det; f[1][1] = (m[0][0] * m[2][2] - m[0][2] * m[2][0]) / det; f[1][2] = (m[0][2] * m[1][0] - m[0][0] * m[1][2]) / det;
+  f[2][0] = (m[1][0] * m[2][1] - m[1][1] * m[2][0]) / det; f[2][1] = (m[0][1] * m[2][0] - m[0][0] * m[2][1]) / det; f[2][2] = (m[0][0] * m[1][1] - m[0][1] * m[1][0]) / det;
+  const double t[3] = {rows[0].w, rows[1].w, rows[2].w};
+  double lo[3] = {DBL_MAX, DBL_MAX, DBL_MAX}, hi[3] = {-DBL_MAX, -DBL_MAX, -DBL_MAX};
+  for (int c = 0; c < 8; c++) {
+    const double v[3] = {(c & 1) ? ob.hi[0] : ob.lo[0], (c & 2) ? ob.hi[1] : ob.lo[1], (c & 4) ? ob.hi[2] : ob.lo[2]};
+    for (int k = 0; k < 3; k++) {
+      const double w = f[k][0] * v[0] + f[k][1] * v[1] + f[k][2] * v[2] + t[k];
+      lo[k] = std::min(lo[k], w); hi[k] = std::max(hi[k], w);
+    }
+  }
+  for (int k = 0; k < 3; k++) {
+    // float rounding of the ray mapping (a few ulp of the coordinates involved) is covered by a relative pad
+    const double pad = 4e-6 * std::max(std::fabs(lo[k]), std::fabs(hi[k])) + 4e-6 * std::fabs(t[k]) + 1e-6 * (hi[k] - lo[k]) + 1e-30;
+    wb.lo[k] = (float) (lo[k] - pad); wb.hi[k] = (float) (hi[k] + pad);
+    wb.lo[k] = std::nextafter(wb.lo[k], -FLT_MAX); wb.hi[k] = std::nextafter(wb.hi[k], FLT_MAX);
+  }
+  return true;
+}
+
+Aabb mesh_triangle_boxes(const float* vertices, uint32_t count, Aabb* tri_boxes) {
+  Aabb mesh = empty_box();
+  std::mutex mesh_mutex;
+  host_parallel_for(count, [&](size_t b, size_t e) {
+    Aabb part = empty_box();
+    for (size_t t = b; t < e; t++) {
+      const float* p = vertices + t * 12;
+      tri_boxes[t] = tri_box(p, p + 4, p + 8);
+      grow(part, tri_boxes[t]);
+    }
+    std::lock_guard<std::mutex> lock(mesh_mutex);
+    grow(mesh, part);
+  });
+  return mesh;
+}
+
+void fill_mesh_tris(const float* vertices, uint32_t first_tri, const uint32_t* prims, uint32_t count, BvhTri* out) {
+  host_parallel_for(count, [&](size_t b, size_t e) {
+    // albedo_tex: k_tri_opacity writes the word from the triangle's material (at upload, and again after a material edit)
+    for (size_t i = b; i < e; i++) out[i] = bvh_tri(vertices + (size_t) prims[i] * 12, prims[i], first_tri + prims[i], kBvhTriNoTexture);
+  });
+}
+
+// Depth caps keep the traversal stack bounded (dev_trace.h kStackSize): top level <= 16, bottom levels <= 26 BVH4 levels.
+SceneTree assemble_scene_tree(const LumDeviceSceneView& v, const Bvh4* const* mesh_bvh, const Aabb* mesh_box) {
+  SceneTree out;
+  out.inv_rows.resize(3 * (size_t) v.num_instances + 3);
+  for (uint32_t i = 0; i < v.num_instances; i++) instance_inverse_rows(v.instance_transforms + (size_t) i * 8, &out.inv_rows[3 * (size_t) i]);
+  // ---- the top level over the world boxes of the instances that can be hit ----
+  std::vector<Aabb> boxes;
+  std::vector<uint32_t> ids;
+  for (uint32_t i = 0; i < v.num_instances; i++) {
+    const uint32_t m = v.instance_mesh_ids[i];
+    if (m >= v.num_meshes || v.mesh_tri_offset[m + 1] == v.mesh_tri_offset[m]) continue;
+    Aabb wb;
+    if (!instance_world_box(&out.inv_rows[3 * (size_t) i], mesh_box[m], wb)) continue;  // degenerate transform: nothing to hit
+    boxes.push_back(wb);
+    ids.push_back(i);
+  }
+  out.world = boxes.empty() ? Aabb{{0.0f, 0.0f, 0.0f}, {1.0f, 1.0f, 1.0f}} : empty_box();
+  for (const Aabb& b : boxes) grow(out.world, b);
+  const Bvh4 tlas = build_bvh4(boxes.data(), (uint32_t) boxes.size(), 1, 16);  // one instance per top-level leaf (dev_trace.h)
+  if (tlas.nodes.empty()) return SceneTree();
+  std::vector<uint32_t> tlas_order(tlas.prims.size());  // instance id of every top-level leaf
+  for (size_t i = 0; i < tlas_order.size(); i++) tlas_order[i] = ids[tlas.prims[i]];
+  out.tlas_num_nodes = (uint32_t) tlas.nodes.size();
+  // ---- ONE node array with absolute indices: the top level (root at index 0), then every mesh's tree ----
+  std::vector<Bvh4Node> nodes = tlas.nodes;
+  out.mesh_root.assign((size_t) v.num_meshes + 1, 0);
+  for (uint32_t m = 0; m < v.num_meshes; m++) {
+    const uint32_t t0 = v.mesh_tri_offset[m], base = (uint32_t) nodes.size();
+    out.mesh_root[m] = base;
+    for (Bvh4Node n : mesh_bvh[m]->nodes) {
+      for (int k = 0; k < 4; k++) {
+        if (n.child[k] == kBvhEmpty) continue;
+        if (n.child[k] & kBvhLeafBit) n.child[k] += t0;  // leaf ranges index the scene's traversal triangles directly (28 bits)
+        else n.child[k] += base;
+      }
+      nodes.push_back(n);
+    }
+  }
+  // ---- renumber: the top of the tree first, in breadth-first order across both levels (top-level leaves continue into the root of
+  // their mesh), so that "node index < K" selects the K most visited nodes; the ray kernels stage those in LDS ----
+  const size_t n = nodes.size();
+  std::vector<uint32_t> order{0u};
+  std::vector<uint8_t> seen(n, 0);
+  order.reserve(n);
+  seen[0] = 1;
+  const size_t top_budget = std::min<size_t>(n, 4096);
+  for (size_t head = 0; head < order.size() && order.size() < top_budget; head++) {
+    const uint32_t id = order[head];
+    for (int k = 0; k < 4; k++) {
+      uint32_t next = nodes[id].child[k];
+      if (next == kBvhEmpty) continue;
+      if (next & kBvhLeafBit) {
+        if (id >= out.tlas_num_nodes) continue;
+        next = out.mesh_root[v.instance_mesh_ids[tlas_order[next & 0x0FFFFFFFu]]];
+      }
+      if (!seen[next]) { seen[next] = 1; order.push_back(next); }
+    }
+  }
+  for (uint32_t i = 0; i < n; i++) if (!seen[i]) order.push_back(i);
+  std::vector<uint32_t> new_index(n);
+  for (uint32_t i = 0; i < n; i++) new_index[order[i]] = i;
+  out.nodes.resize(n);
+  for (uint32_t i = 0; i < n; i++) {
+    Bvh4Node node = nodes[order[i]];
+    for (int k = 0; k < 4; k++)
+      if (node.child[k] != kBvhEmpty && !(node.child[k] & kBvhLeafBit)) node.child[k] = new_index[node.child[k]];
+    out.nodes[i] = node;
+  }
+  for (uint32_t m = 0; m < v.num_meshes; m++) out.mesh_root[m] = new_index[out.mesh_root[m]];
+  // ---- the top-level leaf records, and one of padding ----
+  out.tlas_leaves.resize(4 * tlas_order.size() + 4);
+  for (size_t i = 0; i < tlas_order.size(); i++) {
+    const uint32_t inst = tlas_order[i];
+    for (int k = 0; k < 3; k++) out.tlas_leaves[4 * i + k] = out.inv_rows[3 * (size_t) inst + k];
+    const uint32_t words[4] = {inst, out.mesh_root[v.instance_mesh_ids[inst]], 0u, 0u};
+    std::memcpy(&out.tlas_leaves[4 * i + 3], words, 16);
+  }
+  return out;
+}
+
 }  // namespace lum
+
+// lum_core.h lumc_scene_tree_probe: the scene's tree as the upload assembles it, from the host builder's per-mesh trees (tests/test_scene_tree.py)
+extern "C" int lumc_scene_tree_probe(const LumDeviceSceneView* v, uint64_t sizes[4], void* nodes, void* tris, void* leaves, void* rows, uint32_t* mesh_root, float bounds[6]) {
+  using namespace lum;
+  if (!v || !sizes) return 1;
+  const uint32_t total_tris = v->num_meshes ? v->mesh_tri_offset[v->num_meshes] : 0;
+  std::vector<Bvh4> trees(v->num_meshes);
+  std::vector<const Bvh4*> tree_ptrs(v->num_meshes);
+  std::vector<Aabb> mesh_box(v->num_meshes);
+  std::vector<BvhTri> blas_tris((size_t) total_tris + 1, BvhTri{});
+  for (uint32_t m = 0; m < v->num_meshes; m++) {
+    const uint32_t t0 = v->mesh_tri_offset[m], nt = v->mesh_tri_offset[m + 1] - t0;
+    std::vector<Aabb> tri_boxes(nt);
+    mesh_box[m] = mesh_triangle_boxes(v->vertices + (size_t) t0 * 12, nt, tri_boxes.data());
+    trees[m] = build_bvh4(tri_boxes.data(), nt, kBvhLeafMaxTri, 26);
+    if (trees[m].nodes.empty()) return 1;
+    fill_mesh_tris(v->vertices + (size_t) t0 * 12, t0, trees[m].prims.data(), nt, blas_tris.data() + t0);
+    tree_ptrs[m] = &trees[m];
+  }
+  const SceneTree t = assemble_scene_tree(*v, tree_ptrs.data(), mesh_box.data());
+  if (t.nodes.empty()) return 1;
+  sizes[0] = t.nodes.size(); sizes[1] = t.tlas_num_nodes; sizes[2] = t.tlas_leaves.size() / 4; sizes[3] = blas_tris.size();
+  if (nodes) std::memcpy(nodes, t.nodes.data(), sizeof(Bvh4Node) * t.nodes.size());
+  if (tris) std::memcpy(tris, blas_tris.data(), sizeof(BvhTri) * blas_tris.size());
+  if (leaves) std::memcpy(leaves, t.tlas_leaves.data(), sizeof(float4) * t.tlas_leaves.size());
+  if (rows) std::memcpy(rows, t.inv_rows.data(), sizeof(float4) * t.inv_rows.size());
+  if (mesh_root) std::memcpy(mesh_root, t.mesh_root.data(), sizeof(uint32_t) * t.mesh_root.size());
+  if (bounds) std::memcpy(bounds, &t.world, sizeof(Aabb));
+  return 0;
+}
 
 // lum_core.h lumc_host_bvh_probe: the host builder's tree in numbers (tests/test_bvh_collapse.py)
 extern "C" uint32_t lumc_leaf_max_triangles(void) { return lum::kBvhLeafMaxTri; }

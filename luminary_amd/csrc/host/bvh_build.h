@@ -1,12 +1,17 @@
-// Host-side BVH4 builder for the software traversal that replaces the reference's OptiX acceleration structures
+// Host side of the software traversal's trees, which replace the reference's OptiX acceleration structures
 // (reference: src/luminary/device/optix_bvh.c:150-684 builds GAS/IAS through optixAccelBuild).
-// Round-1 builder: binned-SAH binary tree on the CPU, collapsed into 128-byte 4-wide nodes. A GPU LBVH builder is the
-// planned replacement; the node/triangle layout consumed by the kernels does not depend on the builder.
+// The builders - binned SAH on the CPU (bvh_build.cpp; the fallback and the particle / light / top-level trees) and LBVH, PLOC and binned SAH on the GPU
+// (lbvh.hip; the default for meshes) - all collapse a binary tree into 128-byte 4-wide nodes: the node/triangle layout consumed by the kernels does
+// not depend on the builder. Below them, the assembly of the per-mesh trees and the instances into the scene's one node array (bvh_build.cpp; no HIP call).
 #pragma once
 
+#include <cstddef>
+#include <algorithm>
 #include <cstdint>
+#include <thread>
 #include <vector>
 
+#include "../../../include/lum_core.h"
 #include "../device/dev_scene.h"
 
 namespace lum {
@@ -46,5 +51,47 @@ Bvh4 build_bvh4_ploc(const Aabb* boxes, uint32_t count, uint32_t max_leaf = kBvh
 // The host builder's binned SAH, level by level on the device (lbvh.hip): for meshes without degenerate sets the same binary tree and leaf order as
 // build_bvh4, in tens of milliseconds. Empty result when the tree is deeper than `max_depth` 4-wide levels or a HIP call fails (the caller falls back).
 Bvh4 build_bvh4_sah_gpu(const Aabb* boxes, uint32_t count, uint32_t max_leaf = kBvhLeafMaxTri, uint32_t max_depth = 20);
+
+// ---- the scene's tree (scene upload, core.hip; lumc_scene_tree_probe) ----
+// [0, n) in contiguous chunks over the host's cores (per-triangle loops of the scene upload: 10 M triangles are 100 ms each on one core)
+template <class F>
+void host_parallel_for(size_t n, F&& fn) {
+  const unsigned hc = std::thread::hardware_concurrency();
+  const unsigned threads = (unsigned) std::min<size_t>(std::min(std::max(hc, 1u), 32u), std::max<size_t>(n / 65536, 1));
+  if (threads <= 1) { fn((size_t) 0, n); return; }
+  const size_t chunk = (n + threads - 1) / threads;
+  std::vector<std::thread> pool;
+  for (unsigned t = 1; t < threads; t++) pool.emplace_back([&, t] { const size_t b = std::min(n, t * chunk), e = std::min(n, b + chunk); if (b < e) fn(b, e); });
+  fn((size_t) 0, std::min(n, chunk));
+  for (auto& th : pool) th.join();
+}
+Aabb tri_box(const float* a, const float* b, const float* c);
+// Traversal triangle of three float4 vertices (12 floats): the edges by the float subtraction the reference's intersection code performs.
+inline BvhTri bvh_tri(const float* p, uint32_t id, uint32_t scene_index, uint32_t albedo_tex) {
+  BvhTri t;
+  for (int k = 0; k < 3; k++) { t.p0[k] = p[k]; t.e1[k] = p[4 + k] - p[k]; t.e2[k] = p[8 + k] - p[k]; }
+  t.id = id; t.scene_index = scene_index; t.albedo_tex = albedo_tex;
+  return t;
+}
+// rows[i] = (m_i0, m_i1, m_i2, translation_i) of the world->object map of one instance (8 floats: translation, scale, packed rotation); the world box of an
+// object-space box under the inverse of that map (false for a transform that cannot be inverted)
+void instance_inverse_rows(const float* transform, float4 rows[3]);
+bool instance_world_box(const float4 rows[3], const Aabb& object_box, Aabb& world_box);
+// A mesh's `count` triangles (12 floats each): their boxes into tri_boxes (returns the mesh's box); the triangles in the leaf order of the mesh's tree
+// (Bvh4::prims) into out[0, count), id = the triangle's index in the mesh, scene_index = first_tri + id.
+Aabb mesh_triangle_boxes(const float* vertices, uint32_t count, Aabb* tri_boxes);
+void fill_mesh_tris(const float* vertices, uint32_t first_tri, const uint32_t* prims, uint32_t count, BvhTri* out);
+
+struct SceneTree {
+  std::vector<Bvh4Node> nodes;      // top level, then every mesh's tree; absolute indices, the most visited nodes first (breadth first across both levels)
+  uint32_t tlas_num_nodes = 0;      // nodes that belong to the top level (not a range of `nodes` after the renumbering: bookkeeping and the kernels' leaf test)
+  std::vector<float4> tlas_leaves;  // 4 per top-level leaf in traversal order: the instance's rows, then {instance id, root of its mesh, 0, 0}; one record of padding
+  std::vector<float4> inv_rows;     // 3 per instance, by instance id (+ 3 of padding)
+  std::vector<uint32_t> mesh_root;  // node index of every mesh's root (+ 1 of padding)
+  Aabb world;                       // bounds of the top level; the unit cube when nothing can be hit
+};
+// Top-level tree over the instances of `v` that can be hit (mesh id in range, mesh not empty, invertible transform), concatenated with the per-mesh trees
+// (node indices relative to the mesh, leaf ranges relative to its first triangle) and renumbered. Empty (nodes.empty()) when the top level exceeds 16 levels.
+SceneTree assemble_scene_tree(const LumDeviceSceneView& v, const Bvh4* const* mesh_bvh, const Aabb* mesh_box);
 
 }  // namespace lum

@@ -9,7 +9,6 @@
 #include <chrono>
 #include <cmath>
 #include <cfloat>
-#include <queue>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -46,7 +45,6 @@ struct LumContext {
   // device allocations of the scene by the part of it they belong to (lumc_scene_update frees and rebuilds a part at a time)
   enum AllocGroup { kGrpMesh = 0, kGrpInst, kGrpMat, kGrpLight, kGrpTex, kGrpConst, kGrpPart, kGrpOnce, kGrpCount };
   std::vector<void*> scene_allocs[kGrpCount];
-  int alloc_group = kGrpOnce;
   // what a partial update needs again: the per-mesh trees (node indices relative to the mesh, leaf ranges relative to its first triangle) and boxes
   std::vector<std::shared_ptr<const MeshTree>> mesh_bvh;
   std::vector<Aabb> mesh_box;
@@ -74,7 +72,6 @@ struct LumContext {
   NeeQueue nee2{};
   ShadowQueue fallback{};
   int bvh_builder = 3;            // 0 binned SAH on the host, 1 LBVH on the GPU, 2 PLOC on the GPU, 3 binned SAH on the GPU (default since round 4: the host builder's trees in a fifth of its time; a mesh it cannot take falls back to 0) (lumc_set_bvh_builder)
-  bool top_order_by_area = false; // which nodes count as the top of the tree (staged in LDS): breadth first, or best first by box area (LUM_TOP_ORDER=area; measured: mixed)
   double bvh_build_seconds = 0.0; // bottom-level builds of the last lumc_scene_upload
   uint32_t bvh_meshes_by_builder[2] = {0, 0};  // meshes of the last upload built by SAH / by LBVH
   uint32_t lds_nodes = 0;         // nodes of the tree top every ray-kernel workgroup stages in LDS
@@ -189,19 +186,6 @@ namespace {
     }                                                                                                               \
   } while (0)
 
-// [0, n) in contiguous chunks over the host's cores (per-triangle loops of the scene upload: 10 M triangles are 100 ms each on one core)
-template <class F>
-void host_parallel_for(size_t n, F&& fn) {
-  const unsigned hc = std::thread::hardware_concurrency();
-  const unsigned threads = (unsigned) std::min<size_t>(std::min(std::max(hc, 1u), 32u), std::max<size_t>(n / 65536, 1));
-  if (threads <= 1) { fn((size_t) 0, n); return; }
-  const size_t chunk = (n + threads - 1) / threads;
-  std::vector<std::thread> pool;
-  for (unsigned t = 1; t < threads; t++) pool.emplace_back([&, t] { const size_t b = std::min(n, t * chunk), e = std::min(n, b + chunk); if (b < e) fn(b, e); });
-  fn((size_t) 0, std::min(n, chunk));
-  for (auto& th : pool) th.join();
-}
-
 // ---- the process's bottom-level trees by what they were built from: the mesh's triangles (two 64-bit hashes of the vertex words, chunk by chunk so that the
 // value does not depend on the number of threads), the builder asked for and every LUM_* variable of the environment (the builders' knobs) ----
 struct MeshTreeKey {
@@ -251,13 +235,18 @@ static void keep_mesh_tree(const MeshTreeKey& k, const std::shared_ptr<const Mes
   g_mesh_trees[k] = t;
 }
 
+constexpr size_t kCloudNoiseTexels[3] = {(size_t) kCloudShapeRes * kCloudShapeRes * kCloudShapeRes, (size_t) kCloudDetailRes * kCloudDetailRes * kCloudDetailRes,
+                                         (size_t) kCloudWeatherRes * kCloudWeatherRes};  // shape, detail, weather (RGBA8 each)
+constexpr uint32_t kBsdfLutCount[4] = {1024, 1024, 32768, 32768};  // conductor, glossy, dielectric, dielectric_inv
+
+// A scene array on the device, owned by the allocation group it is registered under (free_group).
 template <typename T>
-int upload(LumContext* ctx, const T* host, size_t count, const T** out, bool scene_owned = true) {
+int upload(LumContext* ctx, int group, const T* host, size_t count, const T** out) {
   *out = nullptr;
   if (count == 0 || host == nullptr) return 0;
   void* d = nullptr;
   HIP_TRY(ctx, hipMalloc(&d, sizeof(T) * count));
-  if (scene_owned) ctx->scene_allocs[ctx->alloc_group].push_back(d);
+  ctx->scene_allocs[group].push_back(d);
   HIP_TRY(ctx, hipMemcpy(d, host, sizeof(T) * count, hipMemcpyHostToDevice));
   *out = (const T*) d;
   return 0;
@@ -479,64 +468,6 @@ int resolve_stamps(LumContext* ctx) {
   return 0;
 }
 
-Aabb tri_box(const float* a, const float* b, const float* c) {
-  Aabb box;
-  for (int k = 0; k < 3; k++) { box.lo[k] = std::min(a[k], std::min(b[k], c[k])); box.hi[k] = std::max(a[k], std::max(b[k], c[k])); }
-  return box;
-}
-
-// Host twin of the device transform (cuda/math.cuh:393-489) used to bound instances for the top-level BVH.
-// World->object matrix of one instance, float arithmetic in the exact operation order of dev_math.h's xf_rel_inv applied to the
-// unit vectors (column j = xf_rel_inv(e_j)); rows[i] = (m_i0, m_i1, m_i2, translation_i). The kernels map rays with these rows
-// (dev_trace.h traverse_scene); the oracle derives the same 12 numbers on its own (oracle/o_trace.h tracer_init).
-void instance_inverse_rows(const float* p, float4 rows[3]) {
-  uint32_t a, b;
-  std::memcpy(&a, p + 6, 4); std::memcpy(&b, p + 7, 4);
-  const float ux = 1.0f - ((a & 0xFFFFu) * (1.0f / 0x7FFF)), uy = 1.0f - ((a >> 16) * (1.0f / 0x7FFF));
-  const float uz = 1.0f - ((b & 0xFFFFu) * (1.0f / 0x7FFF)), s = ((b >> 16) * (1.0f / 0x7FFF)) - 1.0f;
-  const float inv_scale[3] = {1.0f / p[3], 1.0f / p[4], 1.0f / p[5]};
-  float col[3][3];
-  for (int j = 0; j < 3; j++) {
-    const float vx = (j == 0 ? 1.0f : 0.0f) * inv_scale[0], vy = (j == 1 ? 1.0f : 0.0f) * inv_scale[1], vz = (j == 2 ? 1.0f : 0.0f) * inv_scale[2];
-    const float duv = ux * vx + uy * vy + uz * vz, duu = ux * ux + uy * uy + uz * uz;
-    const float cx = uy * vz - uz * vy, cy = uz * vx - ux * vz, cz = ux * vy - uy * vx;
-    const float k0 = 2.0f * duv, k1 = s * s - duu, k2 = 2.0f * s;
-    col[j][0] = (ux * k0 + vx * k1) + cx * k2;
-    col[j][1] = (uy * k0 + vy * k1) + cy * k2;
-    col[j][2] = (uz * k0 + vz * k1) + cz * k2;
-  }
-  for (int i = 0; i < 3; i++) rows[i] = make_float4(col[0][i], col[1][i], col[2][i], p[i]);
-}
-
-// World box of an object-space box under the inverse of the map above (double precision, then padded): the top-level BVH must
-// bound the geometry exactly where the ray mapping puts it.
-bool instance_world_box(const float4 rows[3], const Aabb& ob, Aabb& wb) {
-  const double m[3][3] = {{rows[0].x, rows[0].y, rows[0].z}, {rows[1].x, rows[1].y, rows[1].z}, {rows[2].x, rows[2].y, rows[2].z}};
-  const double det = m[0][0] * (m[1][1] * m[2][2] - m[1][2] * m[2][1]) - m[0][1] * (m[1][0] * m[2][2] - m[1][2] * m[2][0]) +
-                     m[0][2] * (m[1][0] * m[2][1] - m[1][1] * m[2][0]);
-  if (!(std::fabs(det) > 0.0) || !std::isfinite(det)) return false;
-  double f[3][3];
-  f[0][0] = (m[1][1] * m[2][2] - m[1][2] * m[2][1]) / det; f[0][1] = (m[0][2] * m[2][1] - m[0][1] * m[2][2]) / det; f[0][2] = (m[0][1] * m[1][2] - m[0][2] * m[1][1]) / det;
-  f[1][0] = (m[1][2] * m[2][0] - m[1][0] * m[2][2]) / det; f[1][1] = (m[0][0] * m[2][2] - m[0][2] * m[2][0]) / det; f[1][2] = (m[0][2] * m[1][0] - m[0][0] * m[1][2]) / det;
-  f[2][0] = (m[1][0] * m[2][1] - m[1][1] * m[2][0]) / det; f[2][1] = (m[0][1] * m[2][0] - m[0][0] * m[2][1]) / det; f[2][2] = (m[0][0] * m[1][1] - m[0][1] * m[1][0]) / det;
-  const double t[3] = {rows[0].w, rows[1].w, rows[2].w};
-  double lo[3] = {DBL_MAX, DBL_MAX, DBL_MAX}, hi[3] = {-DBL_MAX, -DBL_MAX, -DBL_MAX};
-  for (int c = 0; c < 8; c++) {
-    const double v[3] = {(c & 1) ? ob.hi[0] : ob.lo[0], (c & 2) ? ob.hi[1] : ob.lo[1], (c & 4) ? ob.hi[2] : ob.lo[2]};
-    for (int k = 0; k < 3; k++) {
-      const double w = f[k][0] * v[0] + f[k][1] * v[1] + f[k][2] * v[2] + t[k];
-      lo[k] = std::min(lo[k], w); hi[k] = std::max(hi[k], w);
-    }
-  }
-  for (int k = 0; k < 3; k++) {
-    // float rounding of the ray mapping (a few ulp of the coordinates involved) is covered by a relative pad
-    const double pad = 4e-6 * std::max(std::fabs(lo[k]), std::fabs(hi[k])) + 4e-6 * std::fabs(t[k]) + 1e-6 * (hi[k] - lo[k]) + 1e-30;
-    wb.lo[k] = (float) (lo[k] - pad); wb.hi[k] = (float) (hi[k] + pad);
-    wb.lo[k] = std::nextafter(wb.lo[k], -FLT_MAX); wb.hi[k] = std::nextafter(wb.hi[k], FLT_MAX);
-  }
-  return true;
-}
-
 // ---- ray ordering (north star: "ray-sorted wavefront"; the reference sorts its tasks by hit type every depth, cuda/kernels.cuh:391-484) ----
 // Key = Morton code of the ray origin's cell in a 64^3 grid over the scene bounds (18 bits) combined with the direction's octant (3 bits).
 // Flavour-neutral: the order in which a queue is traced never changes a result (every path owns its slots), it only decides which rays
@@ -637,7 +568,6 @@ int lumc_context_create(int device_ordinal, LumContext** out) {
   LumContext* ctx = new LumContext();
   ctx->device = device_ordinal;
   if (const char* b = getenv("LUM_BVH_BUILDER")) ctx->bvh_builder = (std::strcmp(b, "lbvh") == 0) ? 1 : (std::strcmp(b, "ploc") == 0) ? 2 : (std::strcmp(b, "sah") == 0 || std::strcmp(b, "host") == 0) ? 0 : 3;
-  if (const char* o = getenv("LUM_TOP_ORDER")) ctx->top_order_by_area = std::strcmp(o, "area") == 0;
   if (const char* e = getenv("LUM_SORT")) ctx->sort_mode = atoi(e);
   if (const char* e = getenv("LUM_SYNC_DEBUG")) ctx->sync_debug = atoi(e) != 0;
   if (const char* e = getenv("LUM_SORT_KEY")) ctx->sort_key = atoi(e);
@@ -700,10 +630,8 @@ uint32_t lumc_scene_view_sizeof(void) { return (uint32_t) sizeof(LumDeviceSceneV
 
 // The clouds' noise textures (device_cloud.c:62-101): shape and detail once per context, the weather map per seed.
 static int ensure_cloud_noise(LumContext* ctx, uint32_t seed) {
-  const size_t counts[3] = {(size_t) kCloudShapeRes * kCloudShapeRes * kCloudShapeRes, (size_t) kCloudDetailRes * kCloudDetailRes * kCloudDetailRes,
-                            (size_t) kCloudWeatherRes * kCloudWeatherRes};
   for (int k = 0; k < 3; k++)
-    if (!ctx->d_cloud_noise[k]) HIP_TRY(ctx, hipMalloc((void**) &ctx->d_cloud_noise[k], sizeof(uint32_t) * counts[k]));
+    if (!ctx->d_cloud_noise[k]) HIP_TRY(ctx, hipMalloc((void**) &ctx->d_cloud_noise[k], sizeof(uint32_t) * kCloudNoiseTexels[k]));
   if (!ctx->cloud_noise_static) {
     hipLaunchKernelGGL(exact::k_cloud_noise_shape, dim3(2048), dim3(256), 0, 0, ctx->d_cloud_noise[0], (uint32_t) kCloudShapeRes);
     hipLaunchKernelGGL(exact::k_cloud_noise_detail, dim3(128), dim3(256), 0, 0, ctx->d_cloud_noise[1], (uint32_t) kCloudDetailRes);
@@ -723,17 +651,15 @@ int lumc_cloud_noise_generate(LumContext* ctx, uint32_t seed, uint32_t* shape, u
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   if (ensure_cloud_noise(ctx, seed)) return 1;
   uint32_t* out[3] = {shape, detail, weather};
-  const size_t counts[3] = {(size_t) kCloudShapeRes * kCloudShapeRes * kCloudShapeRes, (size_t) kCloudDetailRes * kCloudDetailRes * kCloudDetailRes,
-                            (size_t) kCloudWeatherRes * kCloudWeatherRes};
   for (int k = 0; k < 3; k++)
-    if (out[k]) HIP_TRY(ctx, hipMemcpy(out[k], ctx->d_cloud_noise[k], sizeof(uint32_t) * counts[k], hipMemcpyDeviceToHost));
+    if (out[k]) HIP_TRY(ctx, hipMemcpy(out[k], ctx->d_cloud_noise[k], sizeof(uint32_t) * kCloudNoiseTexels[k], hipMemcpyDeviceToHost));
   return 0;
 }
 
 // The particle tree (device_particle.c:23-131, optix_bvh.c's particle GAS / IAS): one bottom-level tree over the 2 x count triangles of the unit
 // cell, and a top level over its 25 x 25 x 25 integer translations, instance id = (xi * 25 + yi) * 25 + zi as the reference numbers them. The
 // top-level leaves hold the translation as an exact affine map (rows of the identity), so entering an instance is one subtraction per axis.
-static int build_particle_tree(LumContext* ctx, const LumDeviceSceneView* v, DeviceScene& sc) {
+static int build_particle_tree(LumContext* ctx, int group, const LumDeviceSceneView* v, DeviceScene& sc) {
   sc.particle_bvh_nodes = nullptr; sc.particle_tris = nullptr; sc.particle_leaves = nullptr; sc.particle_tlas_num_nodes = 0; sc.particle_normals = nullptr;
   if (!sc.particles_active) return 0;
   if (!v->particle_vertices || !v->particle_normals) { ctx->error = "lumc_scene_upload: active particles without particle_vertices / particle_normals"; return 1; }
@@ -768,9 +694,7 @@ static int build_particle_tree(LumContext* ctx, const LumDeviceSceneView* v, Dev
   std::memset(tris.data(), 0, sizeof(BvhTri) * tris.size());
   for (uint32_t i = 0; i < nt; i++) {
     const uint32_t t = blas.prims[i];
-    const float* p = v->particle_vertices + (size_t) t * 12;
-    for (int k = 0; k < 3; k++) { tris[i].p0[k] = p[k]; tris[i].e1[k] = p[4 + k] - p[k]; tris[i].e2[k] = p[8 + k] - p[k]; }
-    tris[i].id = t; tris[i].scene_index = t; tris[i].albedo_tex = kBvhTriNoTexture;
+    tris[i] = bvh_tri(v->particle_vertices + (size_t) t * 12, t, t, kBvhTriNoTexture);
   }
   std::vector<float4> leaves(4 * tlas.prims.size() + 4);
   for (size_t i = 0; i < tlas.prims.size(); i++) {
@@ -781,352 +705,198 @@ static int build_particle_tree(LumContext* ctx, const LumDeviceSceneView* v, Dev
     const uint32_t words[4] = {inst, base, 0u, 0u};
     std::memcpy(&leaves[4 * i + 3], words, 16);
   }
-  if (upload(ctx, nodes.data(), nodes.size(), &sc.particle_bvh_nodes)) return 1;
-  if (upload(ctx, tris.data(), tris.size(), &sc.particle_tris)) return 1;
-  if (upload(ctx, leaves.data(), leaves.size(), &sc.particle_leaves)) return 1;
-  if (upload(ctx, (const float4*) v->particle_normals, (size_t) sc.particles_count, &sc.particle_normals)) return 1;
+  if (upload(ctx, group, nodes.data(), nodes.size(), &sc.particle_bvh_nodes)) return 1;
+  if (upload(ctx, group, tris.data(), tris.size(), &sc.particle_tris)) return 1;
+  if (upload(ctx, group, leaves.data(), leaves.size(), &sc.particle_leaves)) return 1;
+  if (upload(ctx, group, (const float4*) v->particle_normals, (size_t) sc.particles_count, &sc.particle_normals)) return 1;
   sc.particle_tlas_num_nodes = (uint32_t) tlas.nodes.size();
   sc.particle_num_leaves = (uint32_t) (leaves.size() / 4);
   ctx->particle_lds_nodes = (uint32_t) std::min<size_t>(ctx->lds_nodes, nodes.size());
   return 0;
 }
 
-// The scene on the device, part by part (lumc_scene_update). Every part frees what it allocated before; parts that are not dirty keep their device
-// arrays and the fields of ctx->scene that point at them.
-static int scene_update(LumContext* ctx, const LumDeviceSceneView* v, unsigned dirty) {
-  ctx->guides_valid = false;  // the denoiser's guides were rendered from the scene as it was
+// ---- the scene on the device, part by part (scene_update below runs the parts in this order). A part frees what it allocated before; a part that is not
+// dirty keeps its device arrays and the fields of ctx->scene that point at them. ----
+static uint32_t total_triangles(const LumDeviceSceneView* v) { return v->num_meshes ? v->mesh_tri_offset[v->num_meshes] : 0; }
+
+static int update_mesh_arrays(LumContext* ctx, const LumDeviceSceneView* v) {
   DeviceScene& sc = ctx->scene;
-  if (!v->bluenoise_2d) { ctx->error = "scene has no blue-noise mask"; return 1; }
-  if (v->max_ray_depth > 63) { ctx->error = "max_ray_depth exceeds 63 (6-bit field, device_structs.h:9)"; return 1; }
-  const uint32_t total_tris = v->num_meshes ? v->mesh_tri_offset[v->num_meshes] : 0;
-  if (dirty & LUMC_DIRTY_MESHES) dirty |= LUMC_DIRTY_INSTANCES;  // the assembled node array holds the per-mesh trees
-  if (dirty & LUMC_DIRTY_PARTICLES) dirty |= LUMC_DIRTY_CONSTANTS;
-  const bool dirty_meshes = (dirty & LUMC_DIRTY_MESHES) != 0, dirty_instances = (dirty & LUMC_DIRTY_INSTANCES) != 0, dirty_lights = (dirty & LUMC_DIRTY_LIGHTS) != 0;
-  ctx->has_scene = false;  // until this update has gone through
+  const uint32_t total_tris = total_triangles(v);
+  free_group(ctx, LumContext::kGrpMesh);
+  if (upload(ctx, LumContext::kGrpMesh, v->mesh_tri_offset, (size_t) v->num_meshes + 1, &sc.mesh_tri_offset)) return 1;
+  if (upload(ctx, LumContext::kGrpMesh, (const float4*) v->vertices, (size_t) total_tris * 3, &sc.vertices)) return 1;
+  return upload(ctx, LumContext::kGrpMesh, (const uint4*) v->tri_tex, (size_t) total_tris, &sc.tri_tex);
+}
 
-  if (dirty_meshes) {
-    free_group(ctx, LumContext::kGrpMesh); ctx->alloc_group = LumContext::kGrpMesh;
-    if (upload(ctx, v->mesh_tri_offset, (size_t) v->num_meshes + 1, &sc.mesh_tri_offset)) return 1;
-    if (upload(ctx, (const float4*) v->vertices, (size_t) total_tris * 3, &sc.vertices)) return 1;
-    if (upload(ctx, (const uint4*) v->tri_tex, (size_t) total_tris, &sc.tri_tex)) return 1;
-  }
-  if (dirty_instances) {
-    free_group(ctx, LumContext::kGrpInst); ctx->alloc_group = LumContext::kGrpInst;
-    if (upload(ctx, v->instance_mesh_ids, v->num_instances, &sc.instance_mesh_ids)) return 1;
-    if (upload(ctx, (const float4*) v->instance_transforms, (size_t) v->num_instances * 2, &sc.instance_transforms)) return 1;
-  }
-  if (dirty & LUMC_DIRTY_MATERIALS) {
-    free_group(ctx, LumContext::kGrpMat); ctx->alloc_group = LumContext::kGrpMat;
-    if (upload(ctx, (const uint4*) v->materials, (size_t) v->num_materials * 2, &sc.materials)) return 1;
-  }
-  if (dirty_lights) {
-    free_group(ctx, LumContext::kGrpLight); ctx->alloc_group = LumContext::kGrpLight;
-    sc.light_tree_root = nullptr; sc.light_root_children = nullptr; sc.light_tree_nodes = nullptr; sc.light_tri_handles = nullptr; sc.light_tri_table = nullptr;
-    sc.light_nodes = nullptr; sc.light_tris = nullptr; sc.light_num_nodes = 0;
-  }
-  if (dirty_lights && v->light_tree_root && v->num_lights) {
-    const uint32_t sections = v->light_tree_root[10];
-    if (upload(ctx, (const uint4*) v->light_tree_root, (size_t) 1 + 3 * sections, &sc.light_tree_root)) return 1;
-    {
-      // The root's children as floats (dev_light.h tree_prepass): mean = byte * 2^e + base per axis, sigma = byte * 2^e_sigma, power = the 16-bit
-      // integer - the operations the kernels used to perform per vertex (cuda/light_tree.cuh:133-161, :203-205), every one exact or a single
-      // binary32 rounding, so the table holds the same bits (this translation unit is compiled without contraction).
-      const uint32_t* h = (const uint32_t*) v->light_tree_root;
-      auto bf = [](uint32_t v16) { const uint32_t b = (v16 & 0xFFFFu) << 16; float f; std::memcpy(&f, &b, 4); return f; };
-      const float base[3] = {bf(h[0]), bf(h[0] >> 16), bf(h[1])};
-      const float ex[3] = {std::ldexp(1.0f, (int8_t) (h[3] & 0xFF)), std::ldexp(1.0f, (int8_t) ((h[3] >> 8) & 0xFF)), std::ldexp(1.0f, (int8_t) ((h[3] >> 16) & 0xFF))};
-      const float ev = std::ldexp(1.0f, (int8_t) (h[3] >> 24));
-      std::vector<float> table((size_t) sections * 8 * 8 + 16, 0.0f);  // + one pair of zeros: the pass reads two children per step
-      for (uint32_t s = 0; s < sections; s++) {
-        const uint8_t* sec = (const uint8_t*) (h + 4 + 12 * s);  // 8 x rel mean x, y, z, rel std dev, then 8 x u16 power
-        for (uint32_t c = 0; c < 8; c++) {
-          float* e = &table[((size_t) s * 8 + c) * 8];
-          for (int a = 0; a < 3; a++) { const float q = (float) sec[8 * a + c]; const float scaled = q * ex[a]; e[a] = scaled + base[a]; }
-          e[3] = (float) sec[24 + c] * ev;
-          uint16_t pw; std::memcpy(&pw, sec + 32 + 2 * c, 2);
-          e[4] = (float) pw;
-        }
-      }
-      if (upload(ctx, table.data(), table.size(), &sc.light_root_children)) return 1;
+// (the scene tree's arrays - update_scene_tree - belong to this group too: whenever the instances are dirty both parts run, this one first)
+static int update_instance_arrays(LumContext* ctx, const LumDeviceSceneView* v) {
+  DeviceScene& sc = ctx->scene;
+  free_group(ctx, LumContext::kGrpInst);
+  if (upload(ctx, LumContext::kGrpInst, v->instance_mesh_ids, v->num_instances, &sc.instance_mesh_ids)) return 1;
+  return upload(ctx, LumContext::kGrpInst, (const float4*) v->instance_transforms, (size_t) v->num_instances * 2, &sc.instance_transforms);
+}
+
+static int update_materials(LumContext* ctx, const LumDeviceSceneView* v) {
+  free_group(ctx, LumContext::kGrpMat);
+  return upload(ctx, LumContext::kGrpMat, (const uint4*) v->materials, (size_t) v->num_materials * 2, &ctx->scene.materials);
+}
+
+// The light tree's root children as floats (dev_light.h tree_prepass): mean = byte * 2^e + base per axis, sigma = byte * 2^e_sigma, power = the 16-bit
+// integer - the operations the kernels used to perform per vertex (cuda/light_tree.cuh:133-161, :203-205), every one exact or a single
+// binary32 rounding, so the table holds the same bits (this translation unit is compiled without contraction).
+static int upload_light_root_children(LumContext* ctx, const LumDeviceSceneView* v, uint32_t sections) {
+  const uint32_t* h = (const uint32_t*) v->light_tree_root;
+  auto bf = [](uint32_t v16) { const uint32_t b = (v16 & 0xFFFFu) << 16; float f; std::memcpy(&f, &b, 4); return f; };
+  const float base[3] = {bf(h[0]), bf(h[0] >> 16), bf(h[1])};
+  const float ex[3] = {std::ldexp(1.0f, (int8_t) (h[3] & 0xFF)), std::ldexp(1.0f, (int8_t) ((h[3] >> 8) & 0xFF)), std::ldexp(1.0f, (int8_t) ((h[3] >> 16) & 0xFF))};
+  const float ev = std::ldexp(1.0f, (int8_t) (h[3] >> 24));
+  std::vector<float> table((size_t) sections * 8 * 8 + 16, 0.0f);  // + one pair of zeros: the pass reads two children per step
+  for (uint32_t s = 0; s < sections; s++) {
+    const uint8_t* sec = (const uint8_t*) (h + 4 + 12 * s);  // 8 x rel mean x, y, z, rel std dev, then 8 x u16 power
+    for (uint32_t c = 0; c < 8; c++) {
+      float* e = &table[((size_t) s * 8 + c) * 8];
+      for (int a = 0; a < 3; a++) { const float q = (float) sec[8 * a + c]; const float scaled = q * ex[a]; e[a] = scaled + base[a]; }
+      e[3] = (float) sec[24 + c] * ev;
+      uint16_t pw; std::memcpy(&pw, sec + 32 + 2 * c, 2);
+      e[4] = (float) pw;
     }
-    if (upload(ctx, (const uint4*) v->light_tree_nodes, (size_t) v->num_light_tree_nodes * 4, &sc.light_tree_nodes)) return 1;
-    if (upload(ctx, (const uint2*) v->light_tri_handles, v->num_lights, &sc.light_tri_handles)) return 1;
   }
-  if (!sc.bluenoise_2d) { ctx->alloc_group = LumContext::kGrpOnce; if (upload(ctx, v->bluenoise_2d, 65536, &sc.bluenoise_2d)) return 1; }
-  if (dirty & LUMC_DIRTY_TEXTURES) {
-    free_group(ctx, LumContext::kGrpTex); ctx->alloc_group = LumContext::kGrpTex;
-    sc.num_textures = 0; sc.texture_table = nullptr; sc.texels = nullptr;
-  }
-  if ((dirty & LUMC_DIRTY_TEXTURES) && v->num_textures && v->texture_table && v->texels) {
-    size_t texel_count = 0;
-    for (uint32_t t = 0; t < v->num_textures; t++)
-      texel_count = std::max(texel_count, (size_t) v->texture_table[4 * t] + (size_t) v->texture_table[4 * t + 1] * v->texture_table[4 * t + 2]);
-    if (upload(ctx, (const uint4*) v->texture_table, v->num_textures, &sc.texture_table)) return 1;
-    if (upload(ctx, v->texels, texel_count, &sc.texels)) return 1;
-    sc.num_textures = v->num_textures;
-  }
+  return upload(ctx, LumContext::kGrpLight, table.data(), table.size(), &ctx->scene.light_root_children);
+}
 
-  // ---- top-level BVH over the instances' world boxes + one bottom-level BVH per mesh, in ONE node array with absolute indices ----
-  // Depth caps keep the traversal stack bounded (dev_trace.h kStackSize): top level <= 16, bottom levels <= 26 BVH4 levels.
-  if (dirty_instances) {
-  std::vector<Aabb>& mesh_box = ctx->mesh_box;
-  std::vector<std::vector<Aabb>> tri_boxes(v->num_meshes);
-  if (dirty_meshes) mesh_box.assign(v->num_meshes, Aabb{});
-  if (mesh_box.size() != v->num_meshes || (!dirty_meshes && ctx->mesh_bvh.size() != v->num_meshes)) { ctx->error = "lumc_scene_update: the meshes changed but LUMC_DIRTY_MESHES is not set"; return 1; }
-  for (uint32_t m = 0; dirty_meshes && m < v->num_meshes; m++) {
-    const uint32_t t0 = v->mesh_tri_offset[m], nt = v->mesh_tri_offset[m + 1] - t0;
-    tri_boxes[m].resize(nt);
-    Aabb mb{{FLT_MAX, FLT_MAX, FLT_MAX}, {-FLT_MAX, -FLT_MAX, -FLT_MAX}};
-    std::mutex mb_mutex;
-    host_parallel_for(nt, [&](size_t b, size_t e) {
-      Aabb part{{FLT_MAX, FLT_MAX, FLT_MAX}, {-FLT_MAX, -FLT_MAX, -FLT_MAX}};
-      for (size_t t = b; t < e; t++) {
-        const float* p = v->vertices + ((size_t) t0 + t) * 12;
-        tri_boxes[m][t] = tri_box(p, p + 4, p + 8);
-        for (int k = 0; k < 3; k++) { part.lo[k] = std::min(part.lo[k], tri_boxes[m][t].lo[k]); part.hi[k] = std::max(part.hi[k], tri_boxes[m][t].hi[k]); }
-      }
-      std::lock_guard<std::mutex> lock(mb_mutex);
-      for (int k = 0; k < 3; k++) { mb.lo[k] = std::min(mb.lo[k], part.lo[k]); mb.hi[k] = std::max(mb.hi[k], part.hi[k]); }
-    });
-    mesh_box[m] = mb;
-  }
-  std::vector<float4> inv_rows(3 * (size_t) v->num_instances + 3);
-  for (uint32_t i = 0; i < v->num_instances; i++) instance_inverse_rows(v->instance_transforms + (size_t) i * 8, &inv_rows[3 * (size_t) i]);
-  ctx->alloc_group = LumContext::kGrpInst;  // NOT the group of whatever was uploaded before: a TEXTURES / MATERIALS / LIGHTS-only update frees those groups
-  if (upload(ctx, inv_rows.data(), inv_rows.size(), &sc.instance_rows)) return 1;  // by instance id: the exact flavour's ambient reuse re-tests a ray against a hit's triangle (k_resolve_reuse)
+// (the light BVH and k_light_table's records - update_light_bvh, update_counts_and_tables - belong to this group too and run whenever this part does)
+static int update_light_tree(LumContext* ctx, const LumDeviceSceneView* v) {
+  DeviceScene& sc = ctx->scene;
+  free_group(ctx, LumContext::kGrpLight);
+  sc.light_tree_root = nullptr; sc.light_root_children = nullptr; sc.light_tree_nodes = nullptr; sc.light_tri_handles = nullptr; sc.light_tri_table = nullptr;
+  sc.light_nodes = nullptr; sc.light_tris = nullptr; sc.light_num_nodes = 0;
+  if (!v->light_tree_root || !v->num_lights) return 0;
+  const uint32_t sections = v->light_tree_root[10];
+  if (upload(ctx, LumContext::kGrpLight, (const uint4*) v->light_tree_root, (size_t) 1 + 3 * sections, &sc.light_tree_root)) return 1;
+  if (upload_light_root_children(ctx, v, sections)) return 1;
+  if (upload(ctx, LumContext::kGrpLight, (const uint4*) v->light_tree_nodes, (size_t) v->num_light_tree_nodes * 4, &sc.light_tree_nodes)) return 1;
+  return upload(ctx, LumContext::kGrpLight, (const uint2*) v->light_tri_handles, v->num_lights, &sc.light_tri_handles);
+}
 
-  std::vector<Bvh4Node> nodes;
-  std::vector<uint32_t> tlas_order;  // instance id of every top-level leaf
-  {
-    std::vector<Aabb> boxes;
-    std::vector<uint32_t> ids;
-    for (uint32_t i = 0; i < v->num_instances; i++) {
-      const uint32_t m = v->instance_mesh_ids[i];
-      if (m >= v->num_meshes || v->mesh_tri_offset[m + 1] == v->mesh_tri_offset[m]) continue;
-      Aabb wb;
-      if (!instance_world_box(&inv_rows[3 * (size_t) i], mesh_box[m], wb)) continue;  // degenerate transform: nothing to hit
-      boxes.push_back(wb);
-      ids.push_back(i);
-    }
-    for (int k = 0; k < 3; k++) { ctx->world_lo[k] = FLT_MAX; ctx->world_hi[k] = -FLT_MAX; }
-    for (const Aabb& b : boxes)
-      for (int k = 0; k < 3; k++) { ctx->world_lo[k] = std::min(ctx->world_lo[k], b.lo[k]); ctx->world_hi[k] = std::max(ctx->world_hi[k], b.hi[k]); }
-    if (boxes.empty()) for (int k = 0; k < 3; k++) { ctx->world_lo[k] = 0.0f; ctx->world_hi[k] = 1.0f; }
-    Bvh4 tlas = build_bvh4(boxes.data(), (uint32_t) boxes.size(), 1, 16);  // one instance per top-level leaf (dev_trace.h)
-    if (tlas.nodes.empty()) { ctx->error = "top-level BVH exceeds 16 levels"; return 1; }
-    tlas_order.resize(tlas.prims.size());
-    for (size_t i = 0; i < tlas_order.size(); i++) tlas_order[i] = ids[tlas.prims[i]];
-    nodes = tlas.nodes;  // root at index 0, child indices already absolute
-    sc.tlas_num_nodes = (uint32_t) tlas.nodes.size();
-    ctx->bvh_stats[2] = tlas.nodes.size();
-  }
-  if (dirty_meshes) {
-    ctx->bvh_build_seconds = 0.0;
-    ctx->bvh_meshes_by_builder[0] = ctx->bvh_meshes_by_builder[1] = 0;
-    ctx->mesh_bvh.assign(v->num_meshes, nullptr);
-  }
-  std::vector<BvhTri> blas_tris(dirty_meshes ? (size_t) total_tris + 1 : 0);
-  if (dirty_meshes) std::memset(blas_tris.data(), 0, sizeof(BvhTri) * blas_tris.size());
-  std::vector<uint32_t> mesh_root(v->num_meshes + 1, 0);
+static int update_textures(LumContext* ctx, const LumDeviceSceneView* v) {
+  DeviceScene& sc = ctx->scene;
+  free_group(ctx, LumContext::kGrpTex);
+  sc.num_textures = 0; sc.texture_table = nullptr; sc.texels = nullptr;
+  if (!v->num_textures || !v->texture_table || !v->texels) return 0;
+  size_t texel_count = 0;
+  for (uint32_t t = 0; t < v->num_textures; t++)
+    texel_count = std::max(texel_count, (size_t) v->texture_table[4 * t] + (size_t) v->texture_table[4 * t + 1] * v->texture_table[4 * t + 2]);
+  if (upload(ctx, LumContext::kGrpTex, (const uint4*) v->texture_table, v->num_textures, &sc.texture_table)) return 1;
+  if (upload(ctx, LumContext::kGrpTex, v->texels, texel_count, &sc.texels)) return 1;
+  sc.num_textures = v->num_textures;
+  return 0;
+}
+
+// Every mesh's box, tree (from the process's cache, else built) and traversal triangles: the only part of an upload that takes long; an instance edit skips it.
+static int build_mesh_trees(LumContext* ctx, const LumDeviceSceneView* v, std::vector<BvhTri>& blas_tris) {
+  ctx->bvh_build_seconds = 0.0;
+  ctx->bvh_meshes_by_builder[0] = ctx->bvh_meshes_by_builder[1] = 0;
+  ctx->mesh_bvh.assign(v->num_meshes, nullptr);
+  ctx->mesh_box.assign(v->num_meshes, Aabb{});
+  blas_tris.assign((size_t) total_triangles(v) + 1, BvhTri{});
   for (uint32_t m = 0; m < v->num_meshes; m++) {
     const uint32_t t0 = v->mesh_tri_offset[m], nt = v->mesh_tri_offset[m + 1] - t0;
-    if (dirty_meshes) {  // the only part of an upload that takes long: an instance edit reuses the trees, another device of the host the first one's
-      const auto t_build = std::chrono::steady_clock::now();
-      const MeshTreeKey key = mesh_tree_key(v->vertices + (size_t) t0 * 12, nt, ctx->bvh_builder);
-      std::shared_ptr<const MeshTree> tree = find_mesh_tree(key);
-      if (!tree) {
-        auto built = std::make_shared<MeshTree>();
-        if (ctx->bvh_builder == 1) built->bvh = build_bvh4_lbvh(tri_boxes[m].data(), nt, kBvhLeafMaxTri, 26);
-        else if (ctx->bvh_builder == 2) built->bvh = build_bvh4_ploc(tri_boxes[m].data(), nt, kBvhLeafMaxTri, 26);
-        else if (ctx->bvh_builder == 3) built->bvh = build_bvh4_sah_gpu(tri_boxes[m].data(), nt, kBvhLeafMaxTri, 26);
-        built->built_on_gpu = !built->bvh.nodes.empty();
-        if (!built->built_on_gpu) built->bvh = build_bvh4(tri_boxes[m].data(), nt, kBvhLeafMaxTri, 26);  // the host builder: asked for, or the fallback for a mesh the GPU builders cannot take
-        if (built->bvh.nodes.empty()) { ctx->error = "mesh BVH exceeds 26 levels"; return 1; }
-        tree = built;
-        keep_mesh_tree(key, tree);
-      }
-      ctx->bvh_meshes_by_builder[tree->built_on_gpu ? 1 : 0]++;
-      ctx->bvh_build_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_build).count();
-      ctx->mesh_bvh[m] = std::move(tree);
+    const float* vertices = v->vertices + (size_t) t0 * 12;
+    std::vector<Aabb> tri_boxes(nt);
+    ctx->mesh_box[m] = mesh_triangle_boxes(vertices, nt, tri_boxes.data());
+    const auto t_build = std::chrono::steady_clock::now();
+    const MeshTreeKey key = mesh_tree_key(vertices, nt, ctx->bvh_builder);
+    std::shared_ptr<const MeshTree> tree = find_mesh_tree(key);
+    if (!tree) {
+      auto built = std::make_shared<MeshTree>();
+      if (ctx->bvh_builder == 1) built->bvh = build_bvh4_lbvh(tri_boxes.data(), nt, kBvhLeafMaxTri, 26);
+      else if (ctx->bvh_builder == 2) built->bvh = build_bvh4_ploc(tri_boxes.data(), nt, kBvhLeafMaxTri, 26);
+      else if (ctx->bvh_builder == 3) built->bvh = build_bvh4_sah_gpu(tri_boxes.data(), nt, kBvhLeafMaxTri, 26);
+      built->built_on_gpu = !built->bvh.nodes.empty();
+      if (!built->built_on_gpu) built->bvh = build_bvh4(tri_boxes.data(), nt, kBvhLeafMaxTri, 26);  // the host builder: asked for, or the fallback for a mesh the GPU builders cannot take
+      if (built->bvh.nodes.empty()) { ctx->error = "mesh BVH exceeds 26 levels"; return 1; }
+      tree = built;
+      keep_mesh_tree(key, tree);
     }
-    const Bvh4& bvh = ctx->mesh_bvh[m]->bvh;
-    const uint32_t base = (uint32_t) nodes.size();
-    mesh_root[m] = base;
-    for (Bvh4Node n : bvh.nodes) {
-      for (int k = 0; k < 4; k++) {
-        if (n.child[k] == kBvhEmpty) continue;
-        if (n.child[k] & kBvhLeafBit) n.child[k] += t0;  // leaf ranges index blas_tris directly (28 bits)
-        else n.child[k] += base;
-      }
-      nodes.push_back(n);
-    }
-    if (dirty_meshes) host_parallel_for(nt, [&](size_t b, size_t e) {
-      for (size_t i = b; i < e; i++) {
-        const uint32_t t = bvh.prims[i];
-        const float* p = v->vertices + (size_t) (t0 + t) * 12;
-        BvhTri& bt = blas_tris[(size_t) t0 + i];
-        for (int k = 0; k < 3; k++) { bt.p0[k] = p[k]; bt.e1[k] = p[4 + k] - p[k]; bt.e2[k] = p[8 + k] - p[k]; }
-        bt.id = t; bt.scene_index = t0 + t;
-        bt.albedo_tex = kBvhTriNoTexture;  // k_tri_opacity writes the word from the triangle's material (below; again after a material edit)
-      }
-    });
-    if (dirty_meshes) { tri_boxes[m].clear(); tri_boxes[m].shrink_to_fit(); }
+    ctx->bvh_meshes_by_builder[tree->built_on_gpu ? 1 : 0]++;
+    ctx->bvh_build_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_build).count();
+    fill_mesh_tris(vertices, t0, tree->bvh.prims.data(), nt, blas_tris.data() + t0);
+    ctx->mesh_bvh[m] = std::move(tree);
   }
-  // ---- renumber: the top of the tree first, in breadth-first order across both levels (top-level leaves continue into the root of
-  // their mesh), so that "node index < K" selects the K most visited nodes; the ray kernels stage those in LDS ----
-  {
-    const size_t n = nodes.size();
-    std::vector<uint32_t> order;
-    std::vector<uint8_t> seen(n, 0);
-    order.reserve(n);
-    const size_t top_budget = std::min<size_t>(n, 4096);
-    auto next_of = [&](uint32_t id, int k, uint32_t& next) {
-      const uint32_t c = nodes[id].child[k];
-      if (c == kBvhEmpty) return false;
-      if (c & kBvhLeafBit) {
-        if (id >= sc.tlas_num_nodes) return false;
-        next = mesh_root[v->instance_mesh_ids[tlas_order[c & 0x0FFFFFFFu]]];
-      }
-      else next = c;
-      return true;
-    };
-    if (ctx->top_order_by_area) {
-      // best first: a ray that enters a node's box enters a child's with probability area(child) / area(box) (convex boxes, uniformly
-      // distributed lines), so the product of those ratios down from the root estimates how often a node is visited; a child never
-      // outranks its parent, the order stays top-down
-      auto half_area = [](float dx, float dy, float dz) { return (double) dx * dy + (double) dy * dz + (double) dz * dx; };
-      auto child_shares = [&](const Bvh4Node& node, double share[4]) {
-        float lo[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, hi[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
-        for (int k = 0; k < 4; k++) {
-          if (node.child[k] == kBvhEmpty) continue;
-          lo[0] = std::min(lo[0], node.lo_x[k]); lo[1] = std::min(lo[1], node.lo_y[k]); lo[2] = std::min(lo[2], node.lo_z[k]);
-          hi[0] = std::max(hi[0], node.hi_x[k]); hi[1] = std::max(hi[1], node.hi_y[k]); hi[2] = std::max(hi[2], node.hi_z[k]);
-        }
-        const double whole = half_area(hi[0] - lo[0], hi[1] - lo[1], hi[2] - lo[2]);
-        for (int k = 0; k < 4; k++)
-          share[k] = (node.child[k] == kBvhEmpty) ? 0.0
-                   : (whole > 0.0) ? std::min(half_area(node.hi_x[k] - node.lo_x[k], node.hi_y[k] - node.lo_y[k], node.hi_z[k] - node.lo_z[k]) / whole, 1.0) : 1.0;
-      };
-      // a mesh is entered through every instance of it: its root's estimate is the sum over the top-level leaves that lead to it
-      std::vector<double> root_estimate(n, 0.0);
-      {
-        std::vector<std::pair<uint32_t, double>> walk{{0u, 1.0}};
-        for (size_t head = 0; head < walk.size() && sc.tlas_num_nodes > 0; head++) {
-          const uint32_t id = walk[head].first;
-          double share[4];
-          child_shares(nodes[id], share);
-          for (int k = 0; k < 4; k++) {
-            const uint32_t c = nodes[id].child[k];
-            if (c == kBvhEmpty) continue;
-            uint32_t next;
-            next_of(id, k, next);
-            if (c & kBvhLeafBit) root_estimate[next] += walk[head].second * share[k];
-            else walk.push_back({next, walk[head].second * share[k]});
-          }
-        }
-      }
-      std::priority_queue<std::pair<double, uint32_t>> open;
-      std::vector<uint8_t> queued(n, 0);
-      open.push({DBL_MAX, 0u}); queued[0] = 1;
-      while (!open.empty() && order.size() < top_budget) {
-        const double p = (open.top().first == DBL_MAX) ? 1.0 : open.top().first;
-        const uint32_t id = open.top().second;
-        open.pop();
-        order.push_back(id); seen[id] = 1;
-        double share[4];
-        child_shares(nodes[id], share);
-        for (int k = 0; k < 4; k++) {
-          uint32_t next;
-          if (!next_of(id, k, next) || queued[next]) continue;
-          queued[next] = 1;
-          const bool enters_mesh = (nodes[id].child[k] & kBvhLeafBit) != 0;
-          open.push({enters_mesh ? root_estimate[next] : p * share[k], next});
-        }
-      }
-    }
-    else {
-      order.push_back(0); seen[0] = 1;
-      for (size_t head = 0; head < order.size() && order.size() < top_budget; head++) {
-        const uint32_t id = order[head];
-        for (int k = 0; k < 4; k++) {
-          uint32_t next;
-          if (next_of(id, k, next) && !seen[next]) { seen[next] = 1; order.push_back(next); }
-        }
-      }
-    }
-    for (uint32_t i = 0; i < n; i++) if (!seen[i]) order.push_back(i);
-    std::vector<uint32_t> new_index(n);
-    for (uint32_t i = 0; i < n; i++) new_index[order[i]] = i;
-    std::vector<Bvh4Node> renum(n);
-    for (uint32_t i = 0; i < n; i++) {
-      Bvh4Node node = nodes[order[i]];
-      for (int k = 0; k < 4; k++)
-        if (node.child[k] != kBvhEmpty && !(node.child[k] & kBvhLeafBit)) node.child[k] = new_index[node.child[k]];
-      renum[i] = node;
-    }
-    nodes.swap(renum);
-    for (uint32_t m = 0; m < v->num_meshes; m++) mesh_root[m] = new_index[mesh_root[m]];
-  }
-  if (total_tris >= (1u << 28) || nodes.size() >= (1u << 25)) { ctx->error = "scene too large for 28-bit leaf ranges / 32-bit node offsets"; return 1; }
-  ctx->alloc_group = LumContext::kGrpInst;
-  if (upload(ctx, nodes.data(), nodes.size(), &sc.bvh_nodes)) return 1;
-  if (dirty_meshes) { ctx->alloc_group = LumContext::kGrpMesh; if (upload(ctx, blas_tris.data(), blas_tris.size(), &sc.blas_tris)) return 1; ctx->alloc_group = LumContext::kGrpInst; }
-  {
-    std::vector<float4> leaves(4 * tlas_order.size() + 4);
-    for (size_t i = 0; i < tlas_order.size(); i++) {
-      const uint32_t inst = tlas_order[i];
-      for (int k = 0; k < 3; k++) leaves[4 * i + k] = inv_rows[3 * (size_t) inst + k];
-      const uint32_t words[4] = {inst, mesh_root[v->instance_mesh_ids[inst]], 0u, 0u};
-      std::memcpy(&leaves[4 * i + 3], words, 16);
-    }
-    if (upload(ctx, leaves.data(), leaves.size(), &sc.tlas_leaves)) return 1;
-    sc.tlas_num_leaves = (uint32_t) (leaves.size() / 4);  // records that exist (one of padding included): what a workgroup may stage in LDS
-  }
-  ctx->bvh_stats[0] = nodes.size() - sc.tlas_num_nodes;
-  {
-    // resident workgroups per CU share the LDS: what the device offers minus a margin, 128 B per node
-    hipDeviceProp_t prop;
-    HIP_TRY(ctx, hipGetDeviceProperties(&prop, ctx->device));
-    size_t lds_bytes = prop.maxSharedMemoryPerMultiProcessor ? prop.maxSharedMemoryPerMultiProcessor : prop.sharedMemPerBlock;
-    // the ray kernels are compiled for 128 VGPRs: 4 waves per SIMD = 16 waves per CU = one workgroup of kTraceBlock = 1024 threads (both flavours since round 4)
-    lds_bytes = std::min<size_t>(lds_bytes, 160 * 1024);
-    lds_bytes = lds_bytes > 16384 ? lds_bytes - 8192 : 0;  // margin: the ray kernels' static LDS (the staged top-level leaf records) and the runtime's own
-    lds_bytes = lds_bytes > LUM_LDS_STACK_BYTES ? lds_bytes - LUM_LDS_STACK_BYTES : 0;  // the stacks' share (dev_trace.h, TraversalStack)
-    ctx->lds_nodes = (uint32_t) std::min<size_t>(lds_bytes / kNodeBytes, nodes.size());
-    if (const char* e = getenv("LUM_LDS_NODES")) ctx->lds_nodes = std::min<uint32_t>((uint32_t) atoi(e), ctx->lds_nodes);
-    ctx->trace_blocks = (uint32_t) prop.multiProcessorCount;  // one workgroup of kTraceBlock threads per CU
-    // The attribute is a property of the kernel, not of a context: it is set to what the largest scene may ask for (the whole budget computed
-    // above), never to this scene's need - a second context with a small scene must not lower the cap a first one launches with.
-    const size_t dyn = lds_bytes + LUM_LDS_STACK_BYTES;
-    HIP_TRY(ctx, (hipError_t) wavefront_kernels_exact()->set_ray_kernel_lds(dyn));
-    HIP_TRY(ctx, (hipError_t) wavefront_kernels_fast()->set_ray_kernel_lds(dyn));
-  }
-  }  // dirty_instances
-  // ---- light-only BVH (world-space triangles; reference: optix_bvh.c:382-478) ----
-  if (dirty_lights) {
-    ctx->alloc_group = LumContext::kGrpLight;
-    const uint32_t nl = (v->light_tree_root && v->light_bvh_tris) ? v->num_lights : 0;
-    std::vector<Aabb> boxes(nl);
-    for (uint32_t l = 0; l < nl; l++) { const float* p = v->light_bvh_tris + (size_t) l * 12; boxes[l] = tri_box(p, p + 4, p + 8); }
-    Bvh4 lb = build_bvh4(boxes.data(), nl, kBvhLeafMaxTri, 40);
-    if (lb.nodes.empty()) { ctx->error = "light BVH exceeds 40 levels"; return 1; }
-    std::vector<BvhTri> tris(nl ? nl : 1);
-    std::memset(tris.data(), 0, sizeof(BvhTri) * tris.size());
-    for (uint32_t i = 0; i < nl; i++) {
-      const uint32_t l = lb.prims[i];
-      const float* p = v->light_bvh_tris + (size_t) l * 12;
-      for (int k = 0; k < 3; k++) { tris[i].p0[k] = p[k]; tris[i].e1[k] = p[4 + k] - p[k]; tris[i].e2[k] = p[8 + k] - p[k]; }
-      tris[i].id = l;
-    }
-    if (upload(ctx, lb.nodes.data(), lb.nodes.size(), &sc.light_nodes)) return 1;
-    if (upload(ctx, tris.data(), tris.size(), &sc.light_tris)) return 1;
-    sc.light_num_nodes = (uint32_t) lb.nodes.size();
-    ctx->bvh_stats[3] = lb.nodes.size();
-  }
-  ctx->bvh_stats[1] = total_tris;
+  return 0;
+}
 
-  { const uint32_t nt = sc.num_textures; sc.num_meshes = v->num_meshes; sc.num_instances = v->num_instances; sc.num_materials = v->num_materials; sc.num_lights = v->num_lights; sc.num_textures = nt; }
-  if (total_tris && (dirty_meshes || (dirty & LUMC_DIRTY_MATERIALS))) {  // the triangles' material words: texture id, or whether they stop a visibility ray on their own
+// Top level + every mesh's tree in ONE node array (bvh_build.cpp assemble_scene_tree), in the instances' group; the traversal triangles in the meshes'.
+static int update_scene_tree(LumContext* ctx, const LumDeviceSceneView* v, bool dirty_meshes, size_t* num_nodes) {
+  DeviceScene& sc = ctx->scene;
+  std::vector<BvhTri> blas_tris;
+  if (dirty_meshes && build_mesh_trees(ctx, v, blas_tris)) return 1;
+  if (ctx->mesh_box.size() != v->num_meshes || ctx->mesh_bvh.size() != v->num_meshes) { ctx->error = "lumc_scene_update: the meshes changed but LUMC_DIRTY_MESHES is not set"; return 1; }
+  std::vector<const Bvh4*> mesh_bvh(v->num_meshes);
+  for (uint32_t m = 0; m < v->num_meshes; m++) mesh_bvh[m] = &ctx->mesh_bvh[m]->bvh;
+  const SceneTree tree = assemble_scene_tree(*v, mesh_bvh.data(), ctx->mesh_box.data());
+  if (tree.nodes.empty()) { ctx->error = "top-level BVH exceeds 16 levels"; return 1; }
+  if (total_triangles(v) >= (1u << 28) || tree.nodes.size() >= (1u << 25)) { ctx->error = "scene too large for 28-bit leaf ranges / 32-bit node offsets"; return 1; }
+  // by instance id: the exact flavour's ambient reuse re-tests a ray against a hit's triangle (k_resolve_reuse)
+  if (upload(ctx, LumContext::kGrpInst, tree.inv_rows.data(), tree.inv_rows.size(), &sc.instance_rows)) return 1;
+  if (upload(ctx, LumContext::kGrpInst, tree.nodes.data(), tree.nodes.size(), &sc.bvh_nodes)) return 1;
+  if (dirty_meshes && upload(ctx, LumContext::kGrpMesh, blas_tris.data(), blas_tris.size(), &sc.blas_tris)) return 1;
+  if (upload(ctx, LumContext::kGrpInst, tree.tlas_leaves.data(), tree.tlas_leaves.size(), &sc.tlas_leaves)) return 1;
+  sc.tlas_num_nodes = tree.tlas_num_nodes;
+  sc.tlas_num_leaves = (uint32_t) (tree.tlas_leaves.size() / 4);  // records that exist (one of padding included): what a workgroup may stage in LDS
+  std::memcpy(ctx->world_lo, tree.world.lo, sizeof(ctx->world_lo)); std::memcpy(ctx->world_hi, tree.world.hi, sizeof(ctx->world_hi));
+  ctx->bvh_stats[0] = tree.nodes.size() - tree.tlas_num_nodes;
+  ctx->bvh_stats[2] = tree.tlas_num_nodes;
+  *num_nodes = tree.nodes.size();
+  return 0;
+}
+
+// How many nodes of the scene tree's top every ray-kernel workgroup stages in LDS, and the kernels' dynamic LDS.
+static int update_ray_kernel_lds(LumContext* ctx, size_t num_nodes) {
+  // resident workgroups per CU share the LDS: what the device offers minus a margin, 128 B per node
+  hipDeviceProp_t prop;
+  HIP_TRY(ctx, hipGetDeviceProperties(&prop, ctx->device));
+  size_t lds_bytes = prop.maxSharedMemoryPerMultiProcessor ? prop.maxSharedMemoryPerMultiProcessor : prop.sharedMemPerBlock;
+  // the ray kernels are compiled for 128 VGPRs: 4 waves per SIMD = 16 waves per CU = one workgroup of kTraceBlock = 1024 threads (both flavours since round 4)
+  lds_bytes = std::min<size_t>(lds_bytes, 160 * 1024);
+  lds_bytes = lds_bytes > 16384 ? lds_bytes - 8192 : 0;  // margin: the ray kernels' static LDS (the staged top-level leaf records) and the runtime's own
+  lds_bytes = lds_bytes > LUM_LDS_STACK_BYTES ? lds_bytes - LUM_LDS_STACK_BYTES : 0;  // the stacks' share (dev_trace.h, TraversalStack)
+  ctx->lds_nodes = (uint32_t) std::min<size_t>(lds_bytes / kNodeBytes, num_nodes);
+  if (const char* e = getenv("LUM_LDS_NODES")) ctx->lds_nodes = std::min<uint32_t>((uint32_t) atoi(e), ctx->lds_nodes);
+  ctx->trace_blocks = (uint32_t) prop.multiProcessorCount;  // one workgroup of kTraceBlock threads per CU
+  // The attribute is a property of the kernel, not of a context: it is set to what the largest scene may ask for (the whole budget computed
+  // above), never to this scene's need - a second context with a small scene must not lower the cap a first one launches with.
+  const size_t dyn = lds_bytes + LUM_LDS_STACK_BYTES;
+  HIP_TRY(ctx, (hipError_t) wavefront_kernels_exact()->set_ray_kernel_lds(dyn));
+  HIP_TRY(ctx, (hipError_t) wavefront_kernels_fast()->set_ray_kernel_lds(dyn));
+  return 0;
+}
+
+// Light-only BVH (world-space triangles; reference: optix_bvh.c:382-478), in the light tree's group.
+static int update_light_bvh(LumContext* ctx, const LumDeviceSceneView* v) {
+  DeviceScene& sc = ctx->scene;
+  const uint32_t nl = (v->light_tree_root && v->light_bvh_tris) ? v->num_lights : 0;
+  std::vector<Aabb> boxes(nl);
+  for (uint32_t l = 0; l < nl; l++) { const float* p = v->light_bvh_tris + (size_t) l * 12; boxes[l] = tri_box(p, p + 4, p + 8); }
+  Bvh4 lb = build_bvh4(boxes.data(), nl, kBvhLeafMaxTri, 40);
+  if (lb.nodes.empty()) { ctx->error = "light BVH exceeds 40 levels"; return 1; }
+  std::vector<BvhTri> tris(nl ? nl : 1, BvhTri{});
+  for (uint32_t i = 0; i < nl; i++) tris[i] = bvh_tri(v->light_bvh_tris + (size_t) lb.prims[i] * 12, lb.prims[i], 0u, 0u);
+  if (upload(ctx, LumContext::kGrpLight, lb.nodes.data(), lb.nodes.size(), &sc.light_nodes)) return 1;
+  if (upload(ctx, LumContext::kGrpLight, tris.data(), tris.size(), &sc.light_tris)) return 1;
+  sc.light_num_nodes = (uint32_t) lb.nodes.size();
+  ctx->bvh_stats[3] = lb.nodes.size();
+  return 0;
+}
+
+// The counts, then what two kernels derive from the arrays above: k_tri_opacity (needs the materials and blas_tris), k_light_table (needs the counts).
+static int update_counts_and_tables(LumContext* ctx, const LumDeviceSceneView* v, unsigned dirty) {
+  DeviceScene& sc = ctx->scene;
+  const uint32_t total_tris = total_triangles(v);
+  const bool dirty_lights = (dirty & LUMC_DIRTY_LIGHTS) != 0;
+  ctx->bvh_stats[1] = total_tris;
+  sc.num_meshes = v->num_meshes; sc.num_instances = v->num_instances; sc.num_materials = v->num_materials; sc.num_lights = v->num_lights;  // (num_textures: update_textures)
+  if (total_tris && (dirty & (LUMC_DIRTY_MESHES | LUMC_DIRTY_MATERIALS))) {  // the triangles' material words: texture id, or whether they stop a visibility ray on their own
     hipLaunchKernelGGL(k_tri_opacity, dim3((total_tris + kBlock - 1) / kBlock), dim3(kBlock), 0, 0, sc, const_cast<BvhTri*>(sc.blas_tris), total_tris);
     HIP_TRY(ctx, hipGetLastError());
   }
@@ -1138,9 +908,12 @@ static int scene_update(LumContext* ctx, const LumDeviceSceneView* v, unsigned d
     HIP_TRY(ctx, hipDeviceSynchronize());
     sc.light_tri_table = table;
   }
-  if (dirty & (LUMC_DIRTY_CONSTANTS | LUMC_DIRTY_PARTICLES)) {
-  if (dirty & LUMC_DIRTY_CONSTANTS) { free_group(ctx, LumContext::kGrpConst); }
-  ctx->alloc_group = LumContext::kGrpConst;
+  return 0;
+}
+
+// The scalar fields of the constants' part, with the pointers of that part reset (the functions after this one fill them in again).
+static int copy_constants(LumContext* ctx, const LumDeviceSceneView* v) {
+  DeviceScene& sc = ctx->scene;
   sc.width = v->width; sc.height = v->height; sc.max_ray_depth = v->max_ray_depth; sc.shading_mode = v->shading_mode;
   std::memcpy(sc.cam_pos, v->cam_pos, sizeof(sc.cam_pos));
   std::memcpy(sc.cam_rotation, v->cam_rotation, sizeof(sc.cam_rotation));
@@ -1161,12 +934,6 @@ static int scene_update(LumContext* ctx, const LumDeviceSceneView* v, unsigned d
   sc.sky_moon_tex_offset = v->sky_moon_tex_offset; sc.sky_stars_intensity = v->sky_stars_intensity;
   sc.sky_moon_albedo_tex = v->sky_moon_albedo_tex; sc.sky_moon_normal_tex = v->sky_moon_normal_tex;
   sc.sky_stars_count = 0; sc.sky_stars = nullptr; sc.sky_stars_offsets = nullptr;
-  if (v->sky_stars && v->sky_stars_offsets && v->sky_stars_count) {
-    if (upload(ctx, (const float4*) v->sky_stars, (size_t) v->sky_stars_count, &sc.sky_stars)) return 1;
-    if (upload(ctx, v->sky_stars_offsets, (size_t) 64 * 32 + 1, &sc.sky_stars_offsets)) return 1;
-    sc.sky_stars_count = v->sky_stars_count;
-  }
-  // ---- sky look-up tables: taken from the caller or generated here (device/device_sky.c:64-200), only for the procedural sky ----
   sc.sky_lut_transmittance = nullptr; sc.sky_lut_multiscattering = nullptr;
   sc.sky_hdri = nullptr; sc.sky_hdri_dim = 0;
   sc.sky_aerial_perspective = v->sky_aerial_perspective;
@@ -1188,9 +955,7 @@ static int scene_update(LumContext* ctx, const LumDeviceSceneView* v, unsigned d
   sc.ocean_caustics_domain_scale = v->ocean_caustics_domain_scale;
   sc.ocean_multiscattering = v->ocean_multiscattering ? 1u : 0u;
   sc.ocean_triangle_light_contribution = v->ocean_triangle_light_contribution ? 1u : 0u;
-  if (sc.ocean_active) {
-    if (!(sc.ocean_refractive_index >= 1.0f)) { ctx->error = "lumc_scene_upload: the ocean needs a refractive index of at least 1"; return 1; }
-  }
+  if (sc.ocean_active && !(sc.ocean_refractive_index >= 1.0f)) { ctx->error = "lumc_scene_upload: the ocean needs a refractive index of at least 1"; return 1; }
   // ---- clouds ----
   sc.cloud_active = v->cloud_active ? 1u : 0u;
   sc.cloud_atmosphere_scattering = v->cloud_atmosphere_scattering ? 1u : 0u;
@@ -1200,18 +965,7 @@ static int scene_update(LumContext* ctx, const LumDeviceSceneView* v, unsigned d
   std::memcpy(sc.cloud_phase, v->cloud_phase, sizeof(sc.cloud_phase));
   std::memcpy(sc.cloud_layers, v->cloud_layers, sizeof(sc.cloud_layers));
   sc.cloud_noise_shape = nullptr; sc.cloud_noise_detail = nullptr; sc.cloud_noise_weather = nullptr;
-  if (sc.cloud_active) {
-    if (sc.cloud_steps == 0 || sc.cloud_shadow_steps == 0) { ctx->error = "lumc_scene_upload: clouds need positive step counts"; return 1; }
-    if (v->cloud_noise_shape && v->cloud_noise_detail && v->cloud_noise_weather) {
-      if (upload(ctx, (const uint32_t*) v->cloud_noise_shape, (size_t) kCloudShapeRes * kCloudShapeRes * kCloudShapeRes, &sc.cloud_noise_shape)) return 1;
-      if (upload(ctx, (const uint32_t*) v->cloud_noise_detail, (size_t) kCloudDetailRes * kCloudDetailRes * kCloudDetailRes, &sc.cloud_noise_detail)) return 1;
-      if (upload(ctx, (const uint32_t*) v->cloud_noise_weather, (size_t) kCloudWeatherRes * kCloudWeatherRes, &sc.cloud_noise_weather)) return 1;
-    }
-    else {
-      if (ensure_cloud_noise(ctx, v->cloud_seed)) return 1;
-      sc.cloud_noise_shape = ctx->d_cloud_noise[0]; sc.cloud_noise_detail = ctx->d_cloud_noise[1]; sc.cloud_noise_weather = ctx->d_cloud_noise[2];
-    }
-  }
+  if (sc.cloud_active && (sc.cloud_steps == 0 || sc.cloud_shadow_steps == 0)) { ctx->error = "lumc_scene_upload: clouds need positive step counts"; return 1; }
   // ---- particles ----
   sc.particles_active = (v->particles_active && v->particles_count) ? 1u : 0u;
   sc.particles_count = sc.particles_active ? v->particles_count : 0u;
@@ -1219,51 +973,82 @@ static int scene_update(LumContext* ctx, const LumDeviceSceneView* v, unsigned d
   std::memcpy(sc.particles_albedo, v->particles_albedo, sizeof(sc.particles_albedo));
   std::memcpy(sc.particles_direction, v->particles_direction, sizeof(sc.particles_direction));
   std::memcpy(sc.particles_phase, v->particles_phase, sizeof(sc.particles_phase));
-  if (dirty & LUMC_DIRTY_PARTICLES) {
-    free_group(ctx, LumContext::kGrpPart); ctx->alloc_group = LumContext::kGrpPart;
-    if (build_particle_tree(ctx, v, sc)) return 1;
-    ctx->alloc_group = LumContext::kGrpConst;
+  return 0;
+}
+
+static int update_stars(LumContext* ctx, const LumDeviceSceneView* v) {
+  DeviceScene& sc = ctx->scene;
+  if (!v->sky_stars || !v->sky_stars_offsets || !v->sky_stars_count) return 0;
+  if (upload(ctx, LumContext::kGrpConst, (const float4*) v->sky_stars, (size_t) v->sky_stars_count, &sc.sky_stars)) return 1;
+  if (upload(ctx, LumContext::kGrpConst, v->sky_stars_offsets, (size_t) 64 * 32 + 1, &sc.sky_stars_offsets)) return 1;
+  sc.sky_stars_count = v->sky_stars_count;
+  return 0;
+}
+
+// The clouds' noise textures: the caller's three, or the context's own (ensure_cloud_noise).
+static int update_cloud_noise(LumContext* ctx, const LumDeviceSceneView* v) {
+  DeviceScene& sc = ctx->scene;
+  if (!sc.cloud_active) return 0;
+  if (v->cloud_noise_shape && v->cloud_noise_detail && v->cloud_noise_weather) {
+    if (upload(ctx, LumContext::kGrpConst, (const uint32_t*) v->cloud_noise_shape, kCloudNoiseTexels[0], &sc.cloud_noise_shape)) return 1;
+    if (upload(ctx, LumContext::kGrpConst, (const uint32_t*) v->cloud_noise_detail, kCloudNoiseTexels[1], &sc.cloud_noise_detail)) return 1;
+    return upload(ctx, LumContext::kGrpConst, (const uint32_t*) v->cloud_noise_weather, kCloudNoiseTexels[2], &sc.cloud_noise_weather);
   }
-  if (sc.sky_mode != kSkyConstantColor) {  // HDRI mode bakes from them and samples the sun through them
-    const size_t tm_texels = 2 * (size_t) kSkyTmWidth * kSkyTmHeight, ms_texels = 2 * (size_t) kSkyMsSize * kSkyMsSize;
-    if (v->sky_lut_transmittance && v->sky_lut_multiscattering) {
-      if (upload(ctx, (const float4*) v->sky_lut_transmittance, tm_texels, &sc.sky_lut_transmittance)) return 1;
-      if (upload(ctx, (const float4*) v->sky_lut_multiscattering, ms_texels, &sc.sky_lut_multiscattering)) return 1;
-      ctx->sky_lut_key.clear();
-    }
-    else {
-      // the two tables are functions of the atmosphere's parameters alone (sky.cuh:110-176, :186-332): a camera move or a sun move keeps them
-      std::vector<uint32_t> key;
-      auto put = [&](const void* p, size_t bytes) { const size_t at = key.size(); key.resize(at + (bytes + 3) / 4, 0u); std::memcpy(key.data() + at, p, bytes); };
-      put(&sc.sky_ozone_absorption, sizeof(sc.sky_ozone_absorption));
-      const float params[] = {sc.sky_base_density, sc.sky_rayleigh_density, sc.sky_mie_density, sc.sky_ozone_density, sc.sky_rayleigh_falloff, sc.sky_mie_falloff,
-                              sc.sky_ground_visibility, sc.sky_ozone_layer_thickness, sc.sky_multiscattering_factor, sc.sky_sun_strength};
-      put(params, sizeof(params)); put(sc.sky_mie_phase, sizeof(sc.sky_mie_phase)); put(sc.sky_sun_pos, sizeof(sc.sky_sun_pos)); put(sc.sky_geometry_offset, sizeof(sc.sky_geometry_offset));
-      if (!ctx->d_sky_lut[0]) {
-        HIP_TRY(ctx, hipMalloc((void**) &ctx->d_sky_lut[0], sizeof(float4) * tm_texels));
-        HIP_TRY(ctx, hipMalloc((void**) &ctx->d_sky_lut[1], sizeof(float4) * ms_texels));
-        ctx->sky_lut_key.clear();
-      }
-      if (key != ctx->sky_lut_key) {
-        hipLaunchKernelGGL(k_sky_transmittance_lut, dim3((kSkyTmWidth * kSkyTmHeight + 63) / 64), dim3(64), 0, 0, sc, ctx->d_sky_lut[0]);
-        sc.sky_lut_transmittance = ctx->d_sky_lut[0];  // the multiscattering integration reads the finished transmittance table
-        hipLaunchKernelGGL(k_sky_multiscattering_lut, dim3(kSkyMsSize, kSkyMsSize), dim3(kSkyMsIter), 0, 0, sc, ctx->d_sky_lut[1]);
-        HIP_TRY(ctx, hipGetLastError());
-        HIP_TRY(ctx, hipDeviceSynchronize());
-        ctx->sky_lut_key = key;
-      }
-      sc.sky_lut_transmittance = ctx->d_sky_lut[0];
-      sc.sky_lut_multiscattering = ctx->d_sky_lut[1];
-    }
+  if (ensure_cloud_noise(ctx, v->cloud_seed)) return 1;
+  sc.cloud_noise_shape = ctx->d_cloud_noise[0]; sc.cloud_noise_detail = ctx->d_cloud_noise[1]; sc.cloud_noise_weather = ctx->d_cloud_noise[2];
+  return 0;
+}
+
+static int update_particles(LumContext* ctx, const LumDeviceSceneView* v) {
+  free_group(ctx, LumContext::kGrpPart);
+  return build_particle_tree(ctx, LumContext::kGrpPart, v, ctx->scene);
+}
+
+// Sky look-up tables: the caller's or generated here (device/device_sky.c:64-200); not for a constant sky (HDRI mode bakes from them and samples the sun through them).
+static int update_sky_tables(LumContext* ctx, const LumDeviceSceneView* v) {
+  DeviceScene& sc = ctx->scene;
+  if (sc.sky_mode == kSkyConstantColor) return 0;
+  const size_t tm_texels = 2 * (size_t) kSkyTmWidth * kSkyTmHeight, ms_texels = 2 * (size_t) kSkyMsSize * kSkyMsSize;
+  if (v->sky_lut_transmittance && v->sky_lut_multiscattering) {
+    if (upload(ctx, LumContext::kGrpConst, (const float4*) v->sky_lut_transmittance, tm_texels, &sc.sky_lut_transmittance)) return 1;
+    if (upload(ctx, LumContext::kGrpConst, (const float4*) v->sky_lut_multiscattering, ms_texels, &sc.sky_lut_multiscattering)) return 1;
+    ctx->sky_lut_key.clear();
+    return 0;
   }
-  // ---- BSDF energy tables: taken from the caller or generated here (device/device_bsdf.c:64-130) ----
+  // the two tables are functions of the atmosphere's parameters alone (sky.cuh:110-176, :186-332): a camera move or a sun move keeps them
+  std::vector<uint32_t> key;
+  auto put = [&](const void* p, size_t bytes) { const size_t at = key.size(); key.resize(at + (bytes + 3) / 4, 0u); std::memcpy(key.data() + at, p, bytes); };
+  put(&sc.sky_ozone_absorption, sizeof(sc.sky_ozone_absorption));
+  const float params[] = {sc.sky_base_density, sc.sky_rayleigh_density, sc.sky_mie_density, sc.sky_ozone_density, sc.sky_rayleigh_falloff, sc.sky_mie_falloff,
+                          sc.sky_ground_visibility, sc.sky_ozone_layer_thickness, sc.sky_multiscattering_factor, sc.sky_sun_strength};
+  put(params, sizeof(params)); put(sc.sky_mie_phase, sizeof(sc.sky_mie_phase)); put(sc.sky_sun_pos, sizeof(sc.sky_sun_pos)); put(sc.sky_geometry_offset, sizeof(sc.sky_geometry_offset));
+  if (!ctx->d_sky_lut[0]) {
+    HIP_TRY(ctx, hipMalloc((void**) &ctx->d_sky_lut[0], sizeof(float4) * tm_texels));
+    HIP_TRY(ctx, hipMalloc((void**) &ctx->d_sky_lut[1], sizeof(float4) * ms_texels));
+    ctx->sky_lut_key.clear();
+  }
+  if (key != ctx->sky_lut_key) {
+    hipLaunchKernelGGL(k_sky_transmittance_lut, dim3((kSkyTmWidth * kSkyTmHeight + 63) / 64), dim3(64), 0, 0, sc, ctx->d_sky_lut[0]);
+    sc.sky_lut_transmittance = ctx->d_sky_lut[0];  // the multiscattering integration reads the finished transmittance table
+    hipLaunchKernelGGL(k_sky_multiscattering_lut, dim3(kSkyMsSize, kSkyMsSize), dim3(kSkyMsIter), 0, 0, sc, ctx->d_sky_lut[1]);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    ctx->sky_lut_key = key;
+  }
+  sc.sky_lut_transmittance = ctx->d_sky_lut[0];
+  sc.sky_lut_multiscattering = ctx->d_sky_lut[1];
+  return 0;
+}
+
+// BSDF energy tables: taken from the caller or generated here (device/device_bsdf.c:64-130).
+static int update_bsdf_tables(LumContext* ctx, const LumDeviceSceneView* v, bool full_upload) {
+  DeviceScene& sc = ctx->scene;
   const uint16_t* host_luts[4] = {v->lut_conductor, v->lut_glossy, v->lut_dielectric, v->lut_dielectric_inv};
-  const uint32_t lut_count[4] = {1024, 1024, 32768, 32768};
   const bool have_luts = ctx->d_luts[0] != nullptr;
-  for (int t = 0; t < 4 && !have_luts; t++) HIP_TRY(ctx, hipMalloc((void**) &ctx->d_luts[t], sizeof(uint16_t) * lut_count[t]));
-  if (have_luts && dirty != LUMC_DIRTY_ALL) { /* a partial update keeps the tables the context renders with */ }
+  for (int t = 0; t < 4 && !have_luts; t++) HIP_TRY(ctx, hipMalloc((void**) &ctx->d_luts[t], sizeof(uint16_t) * kBsdfLutCount[t]));
+  if (have_luts && !full_upload) { /* a partial update keeps the tables the context renders with */ }
   else if (host_luts[0] && host_luts[1] && host_luts[2] && host_luts[3]) {
-    for (int t = 0; t < 4; t++) HIP_TRY(ctx, hipMemcpy(ctx->d_luts[t], host_luts[t], sizeof(uint16_t) * lut_count[t], hipMemcpyHostToDevice));
+    for (int t = 0; t < 4; t++) HIP_TRY(ctx, hipMemcpy(ctx->d_luts[t], host_luts[t], sizeof(uint16_t) * kBsdfLutCount[t], hipMemcpyHostToDevice));
   }
   else {
     // The tables are a function of the embedded blue-noise mask alone (65 536 samples per texel, one thread per texel: 0.29 s of GPU time):
@@ -1274,7 +1059,7 @@ static int scene_update(LumContext* ctx, const LumDeviceSceneView* v, unsigned d
     std::lock_guard<std::mutex> lock(lut_mutex);
     const bool cached = !lut_cache[0].empty() && lut_cache_mask.size() == 65536 && std::memcmp(lut_cache_mask.data(), v->bluenoise_2d, sizeof(uint32_t) * 65536) == 0;
     if (cached) {
-      for (int t = 0; t < 4; t++) HIP_TRY(ctx, hipMemcpy(ctx->d_luts[t], lut_cache[t].data(), sizeof(uint16_t) * lut_count[t], hipMemcpyHostToDevice));
+      for (int t = 0; t < 4; t++) HIP_TRY(ctx, hipMemcpy(ctx->d_luts[t], lut_cache[t].data(), sizeof(uint16_t) * kBsdfLutCount[t], hipMemcpyHostToDevice));
     }
     else {
       // the two big tables and the conductor table are independent: side by side on three streams; the glossy table divides by the conductor's
@@ -1283,50 +1068,90 @@ static int scene_update(LumContext* ctx, const LumDeviceSceneView* v, unsigned d
       const int first_wave[3] = {0, 2, 3};
       for (int k = 0; k < 3; k++) {
         const int t = first_wave[k];
-        hipLaunchKernelGGL(k_generate_lut, dim3((lut_count[t] + 63) / 64), dim3(64), 0, streams[k], sc.bluenoise_2d, t, lut_count[t], ctx->d_luts[0], ctx->d_luts[t]);
+        hipLaunchKernelGGL(k_generate_lut, dim3((kBsdfLutCount[t] + 63) / 64), dim3(64), 0, streams[k], sc.bluenoise_2d, t, kBsdfLutCount[t], ctx->d_luts[0], ctx->d_luts[t]);
       }
-      hipLaunchKernelGGL(k_generate_lut, dim3((lut_count[1] + 63) / 64), dim3(64), 0, streams[0], sc.bluenoise_2d, 1, lut_count[1], ctx->d_luts[0], ctx->d_luts[1]);
+      hipLaunchKernelGGL(k_generate_lut, dim3((kBsdfLutCount[1] + 63) / 64), dim3(64), 0, streams[0], sc.bluenoise_2d, 1, kBsdfLutCount[1], ctx->d_luts[0], ctx->d_luts[1]);
       HIP_TRY(ctx, hipGetLastError());
       for (auto& st : streams) { HIP_TRY(ctx, hipStreamSynchronize(st)); (void) hipStreamDestroy(st); }
       for (int t = 0; t < 4; t++) {
-        lut_cache[t].resize(lut_count[t]);
-        HIP_TRY(ctx, hipMemcpy(lut_cache[t].data(), ctx->d_luts[t], sizeof(uint16_t) * lut_count[t], hipMemcpyDeviceToHost));
+        lut_cache[t].resize(kBsdfLutCount[t]);
+        HIP_TRY(ctx, hipMemcpy(lut_cache[t].data(), ctx->d_luts[t], sizeof(uint16_t) * kBsdfLutCount[t], hipMemcpyDeviceToHost));
       }
       lut_cache_mask.assign(v->bluenoise_2d, v->bluenoise_2d + 65536);
     }
   }
   sc.lut_conductor = ctx->d_luts[0]; sc.lut_glossy = ctx->d_luts[1]; sc.lut_dielectric = ctx->d_luts[2]; sc.lut_dielectric_inv = ctx->d_luts[3];
-  // ---- sky panorama (HDRI mode): the caller's, or baked here from the procedural sky as the reference's device manager does when the
-  // sky changes (device_manager.c:351-366, device_sky.c:249-366); lumc_sky_hdri_build re-bakes on request ----
-  if (sc.sky_mode == kSkyHdri) {
-    if (v->sky_hdri && v->sky_hdri_dim) {
-      if (upload(ctx, (const float4*) v->sky_hdri, (size_t) v->sky_hdri_dim * v->sky_hdri_dim, &sc.sky_hdri)) return 1;
-      sc.sky_hdri_dim = v->sky_hdri_dim;
-    }
-    else {
-      ctx->has_scene = true;  // the bake renders this scene's sky
-      if (lumc_sky_hdri_build(ctx, v->sky_hdri_origin, v->sky_hdri_dim, v->sky_hdri_samples ? v->sky_hdri_samples : 1u)) { ctx->has_scene = false; return 1; }
-    }
+  return 0;
+}
+
+// Sky panorama (HDRI mode): the caller's, or baked here from the procedural sky as the reference's device manager does when the sky changes
+// (device_manager.c:351-366, device_sky.c:249-366); lumc_sky_hdri_build re-bakes on request.
+static int update_sky_panorama(LumContext* ctx, const LumDeviceSceneView* v) {
+  DeviceScene& sc = ctx->scene;
+  if (sc.sky_mode != kSkyHdri) return 0;
+  if (v->sky_hdri && v->sky_hdri_dim) {
+    if (upload(ctx, LumContext::kGrpConst, (const float4*) v->sky_hdri, (size_t) v->sky_hdri_dim * v->sky_hdri_dim, &sc.sky_hdri)) return 1;
+    sc.sky_hdri_dim = v->sky_hdri_dim;
+    return 0;
   }
-  }  // constants
-  // ---- bridges to emissive triangles (fog, or an ocean with triangle_light_contribution): the vertex-count table. Decided after EVERY update, not
-  // only when the constants are dirty: a material that becomes emissive (MATERIALS | LIGHTS) gives a fogged scene its first light, and
-  // bridges_vertex_count_importance reads the table without a check. The table lives in the context (5 KB, uploaded once per content). ----
-  {
-    const bool need_bridges = (sc.fog_active || (sc.ocean_active && sc.ocean_triangle_light_contribution)) && sc.num_lights > 0 && sc.light_tree_root;
-    sc.bridge_lut = nullptr;
-    if (need_bridges) {
-      if (!v->bridge_lut) { ctx->error = sc.fog_active ? "lumc_scene_upload: fog with emissive triangles needs bridge_lut" : "lumc_scene_upload: an ocean lit by emissive triangles needs bridge_lut"; return 1; }
-      if (sc.bridge_max_num_vertices == 0) { ctx->error = "lumc_scene_upload: bridge_max_num_vertices must be at least 1"; return 1; }
-      const size_t n = (size_t) 64 * 21;
-      if (!ctx->d_bridge_lut || ctx->bridge_lut_host.size() != n || std::memcmp(ctx->bridge_lut_host.data(), v->bridge_lut, n * sizeof(float)) != 0) {
-        if (!ctx->d_bridge_lut) HIP_TRY(ctx, hipMalloc((void**) &ctx->d_bridge_lut, n * sizeof(float)));
-        HIP_TRY(ctx, hipMemcpy(ctx->d_bridge_lut, v->bridge_lut, n * sizeof(float), hipMemcpyHostToDevice));
-        ctx->bridge_lut_host.assign(v->bridge_lut, v->bridge_lut + n);
-      }
-      sc.bridge_lut = ctx->d_bridge_lut;
-    }
+  ctx->has_scene = true;  // the bake renders this scene's sky
+  if (lumc_sky_hdri_build(ctx, v->sky_hdri_origin, v->sky_hdri_dim, v->sky_hdri_samples ? v->sky_hdri_samples : 1u)) { ctx->has_scene = false; return 1; }
+  return 0;
+}
+
+// Camera, settings, sky, fog, ocean, clouds, particles: the kernels' scalar arguments and the tables derived from them.
+static int update_constants(LumContext* ctx, const LumDeviceSceneView* v, unsigned dirty) {
+  free_group(ctx, LumContext::kGrpConst);
+  if (copy_constants(ctx, v)) return 1;
+  if (update_stars(ctx, v)) return 1;
+  if (update_cloud_noise(ctx, v)) return 1;
+  if ((dirty & LUMC_DIRTY_PARTICLES) && update_particles(ctx, v)) return 1;
+  if (update_sky_tables(ctx, v)) return 1;
+  if (update_bsdf_tables(ctx, v, dirty == LUMC_DIRTY_ALL)) return 1;
+  return update_sky_panorama(ctx, v);
+}
+
+// Bridges to emissive triangles (fog, or an ocean with triangle_light_contribution): the vertex-count table. Decided after EVERY update, not only when
+// the constants are dirty: a material that becomes emissive (MATERIALS | LIGHTS) gives a fogged scene its first light, and bridges_vertex_count_importance
+// reads the table without a check. The table lives in the context (5 KB, uploaded once per content).
+static int update_bridge_table(LumContext* ctx, const LumDeviceSceneView* v) {
+  DeviceScene& sc = ctx->scene;
+  sc.bridge_lut = nullptr;
+  if (!((sc.fog_active || (sc.ocean_active && sc.ocean_triangle_light_contribution)) && sc.num_lights > 0 && sc.light_tree_root)) return 0;
+  if (!v->bridge_lut) { ctx->error = sc.fog_active ? "lumc_scene_upload: fog with emissive triangles needs bridge_lut" : "lumc_scene_upload: an ocean lit by emissive triangles needs bridge_lut"; return 1; }
+  if (sc.bridge_max_num_vertices == 0) { ctx->error = "lumc_scene_upload: bridge_max_num_vertices must be at least 1"; return 1; }
+  const size_t n = (size_t) 64 * 21;
+  if (!ctx->d_bridge_lut || ctx->bridge_lut_host.size() != n || std::memcmp(ctx->bridge_lut_host.data(), v->bridge_lut, n * sizeof(float)) != 0) {
+    if (!ctx->d_bridge_lut) HIP_TRY(ctx, hipMalloc((void**) &ctx->d_bridge_lut, n * sizeof(float)));
+    HIP_TRY(ctx, hipMemcpy(ctx->d_bridge_lut, v->bridge_lut, n * sizeof(float), hipMemcpyHostToDevice));
+    ctx->bridge_lut_host.assign(v->bridge_lut, v->bridge_lut + n);
   }
+  sc.bridge_lut = ctx->d_bridge_lut;
+  return 0;
+}
+
+// The scene on the device: the dirty parts, in the order their kernels and uploads depend on. Until the update has gone through the context has no scene.
+static int scene_update(LumContext* ctx, const LumDeviceSceneView* v, unsigned dirty) {
+  ctx->guides_valid = false;  // the denoiser's guides were rendered from the scene as it was
+  DeviceScene& sc = ctx->scene;
+  if (!v->bluenoise_2d) { ctx->error = "scene has no blue-noise mask"; return 1; }
+  if (v->max_ray_depth > 63) { ctx->error = "max_ray_depth exceeds 63 (6-bit field, device_structs.h:9)"; return 1; }
+  if (dirty & LUMC_DIRTY_MESHES) dirty |= LUMC_DIRTY_INSTANCES;  // the assembled node array holds the per-mesh trees
+  if (dirty & LUMC_DIRTY_PARTICLES) dirty |= LUMC_DIRTY_CONSTANTS;
+  const bool meshes = (dirty & LUMC_DIRTY_MESHES) != 0, instances = (dirty & LUMC_DIRTY_INSTANCES) != 0, lights = (dirty & LUMC_DIRTY_LIGHTS) != 0;
+  ctx->has_scene = false;
+  if (meshes && update_mesh_arrays(ctx, v)) return 1;
+  if (instances && update_instance_arrays(ctx, v)) return 1;
+  if ((dirty & LUMC_DIRTY_MATERIALS) && update_materials(ctx, v)) return 1;
+  if (lights && update_light_tree(ctx, v)) return 1;
+  if (!sc.bluenoise_2d && upload(ctx, LumContext::kGrpOnce, v->bluenoise_2d, 65536, &sc.bluenoise_2d)) return 1;
+  if ((dirty & LUMC_DIRTY_TEXTURES) && update_textures(ctx, v)) return 1;
+  size_t num_nodes = 0;
+  if (instances && (update_scene_tree(ctx, v, meshes, &num_nodes) || update_ray_kernel_lds(ctx, num_nodes))) return 1;
+  if (lights && update_light_bvh(ctx, v)) return 1;
+  if (update_counts_and_tables(ctx, v, dirty)) return 1;
+  if ((dirty & LUMC_DIRTY_CONSTANTS) && update_constants(ctx, v, dirty)) return 1;
+  if (update_bridge_table(ctx, v)) return 1;
   // the moon's texture ids follow the texture pool (the host layer appends the two moon textures behind the scene's own): an added texture moves them
   sc.sky_moon_albedo_tex = v->sky_moon_albedo_tex; sc.sky_moon_normal_tex = v->sky_moon_normal_tex;
   ctx->has_scene = true;
@@ -1353,9 +1178,8 @@ int lumc_scene_update(LumContext* ctx, const LumDeviceSceneView* v, unsigned int
 int lumc_download_luts(LumContext* ctx, uint16_t* conductor, uint16_t* glossy, uint16_t* dielectric, uint16_t* dielectric_inv) {
   if (!ctx || !ctx->has_scene) return 1;
   uint16_t* dst[4] = {conductor, glossy, dielectric, dielectric_inv};
-  const uint32_t lut_count[4] = {1024, 1024, 32768, 32768};
   for (int t = 0; t < 4; t++)
-    if (dst[t]) HIP_TRY(ctx, hipMemcpy(dst[t], ctx->d_luts[t], sizeof(uint16_t) * lut_count[t], hipMemcpyDeviceToHost));
+    if (dst[t]) HIP_TRY(ctx, hipMemcpy(dst[t], ctx->d_luts[t], sizeof(uint16_t) * kBsdfLutCount[t], hipMemcpyDeviceToHost));
   return 0;
 }
 

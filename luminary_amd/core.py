@@ -493,6 +493,38 @@ class Core:
                    out.ctypes.data_as(C.c_void_p))
         return out
 
+    def trace_visibility_host(self, origins, dirs, dist, ids, order=None):
+        """Visibility rays through the active flavour's k_shadow_rays: [n, 3] float32 transparency products (0 = blocked; NaN = a ray nobody answered).
+        ids [n, 4]: target instance, target triangle, self instance, self triangle (0xFFFFFFFF: none); order: the item every work slot traces, or None."""
+        origins = np.ascontiguousarray(origins, dtype=np.float32)
+        dirs = np.ascontiguousarray(dirs, dtype=np.float32)
+        dist = np.ascontiguousarray(dist, dtype=np.float32)
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        n = origins.shape[0]
+        assert origins.shape == dirs.shape == (n, 3) and dist.shape == (n,) and ids.shape == (n, 4)
+        out = np.zeros((n, 3), dtype=np.float32)
+        op = C.c_void_p(0)
+        if order is not None:
+            order = np.ascontiguousarray(order, dtype=np.uint32)
+            assert order.shape == (n,)
+            op = order.ctypes.data_as(C.c_void_p)
+        self._call("lumc_trace_visibility_host", C.c_uint32(n), origins.ctypes.data_as(C.c_void_p), dirs.ctypes.data_as(C.c_void_p), dist.ctypes.data_as(C.c_void_p),
+                   ids.ctypes.data_as(C.c_void_p), op, out.ctypes.data_as(C.c_void_p))
+        return out
+
+    def light_query_host(self, origins, dirs, self_handles, randoms):
+        """The light-BVH query of BSDF-sampled directions on plain rays: (light ids [n] uint32, 0xFFFFFFFF = none; num_hits [n] uint32)."""
+        origins = np.ascontiguousarray(origins, dtype=np.float32)
+        dirs = np.ascontiguousarray(dirs, dtype=np.float32)
+        self_handles = np.ascontiguousarray(self_handles, dtype=np.uint32)
+        randoms = np.ascontiguousarray(randoms, dtype=np.float32)
+        n = origins.shape[0]
+        assert origins.shape == dirs.shape == (n, 3) and self_handles.shape == (n, 2) and randoms.shape == (n,)
+        ids, hits = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint32)
+        self._call("lumc_light_query_host", C.c_uint32(n), origins.ctypes.data_as(C.c_void_p), dirs.ctypes.data_as(C.c_void_p), self_handles.ctypes.data_as(C.c_void_p),
+                   randoms.ctypes.data_as(C.c_void_p), ids.ctypes.data_as(C.c_void_p), hits.ctypes.data_as(C.c_void_p))
+        return ids, hits
+
     def trace_closest_device(self, n, origins_ptr, dirs_ptr, ignore_ptr, out_ptr, stream=0):
         self._call("lumc_trace_closest", C.c_uint32(n), C.c_void_p(origins_ptr), C.c_void_p(dirs_ptr), C.c_void_p(ignore_ptr), C.c_void_p(out_ptr),
                    C.c_void_p(stream))

@@ -534,7 +534,9 @@ struct ShadowState {
 #endif
   Acc tr, tg, tb;
   bool blocked;
-  LUM_DEV void begin(uint4 ids, float d) { tgt_inst = ids.x; tgt_tri = ids.y; self_inst = ids.z; self_tri = ids.w; dist = d; tr = tg = tb = (Acc) 1.0; blocked = false; }
+  // dist is capped at FLT_MAX: intersect_triangle answers a miss with FLT_MAX, which `t < dist` must reject, and under dist = +inf it passed - every triangle of
+  // every leaf the ray visited counted as crossed (tests/test_visibility_truth.py, family "degenerate"). A NaN distance stays NaN: nothing is crossed.
+  LUM_DEV void begin(uint4 ids, float d) { tgt_inst = ids.x; tgt_tri = ids.y; self_inst = ids.z; self_tri = ids.w; dist = (d > kFltMax) ? kFltMax : d; tr = tg = tb = (Acc) 1.0; blocked = false; }
   LUM_DEV bool on_tris(const DeviceScene& sc, uint32_t inst, uint32_t first, uint32_t count, V3 o, V3 d, float&, RayStats& st) {
     LeafTris lt;
     lt.load<true>(sc.blas_tris, first, count);

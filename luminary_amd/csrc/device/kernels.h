@@ -2243,6 +2243,18 @@ __global__ LUM_TRACE_BOUNDS void k_trace_rays(DeviceScene sc, uint32_t n, const 
   flush_stats(counters, st, rays, kCntTrace, kCntNodes, kCntTris, kCntNodesLds);
 }
 
+// ---- standalone light-BVH query for the traversal tests: one ray per thread, light_query exactly as k_light_query calls it ----
+__global__ __launch_bounds__(kBlock) void k_light_query_probe(DeviceScene sc, uint32_t n, const float* origins, const float* dirs, const uint32_t* self, const float* randoms,
+                                                              uint32_t* out_ids, uint32_t* out_num_hits) {
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  RayStats st{0, 0, 0};
+  uint32_t num_hits = 0;
+  const uint32_t id = light_query(sc, v3(origins[3 * i], origins[3 * i + 1], origins[3 * i + 2]), v3(dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2]), self[2 * i], self[2 * i + 1],
+                                  randoms[i], num_hits, st);
+  out_ids[i] = id; out_num_hits[i] = num_hits;
+}
+
 // The Sobol / Owen pairs of one pass (dev_sampler.h LUM_SOBOL_TABLE): one thread per (dimension, sample id).
 __global__ __launch_bounds__(256) void k_sobol_table(uint2* __restrict__ table, uint32_t first_sample, uint32_t count, uint32_t stride, uint32_t dims) {
   const uint32_t t = blockIdx.x * 256u + threadIdx.x;
@@ -2253,6 +2265,21 @@ __global__ __launch_bounds__(256) void k_sobol_table(uint2* __restrict__ table, 
 }
 
 #if !LUM_FAST  // flavour-neutral: compiled once, in the exact translation unit
+// ---- standalone visibility entry (lumc_trace_visibility): plain per-ray arrays into a ShadowQueue whose output index is the ray index, and its answers back ----
+__global__ __launch_bounds__(256) void k_visibility_pack(uint32_t n, const float* origins, const float* dirs, const float* dist, const uint32_t* ids, ShadowQueue sq) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= n) return;
+  sq.origin_dist[i] = make_float4(origins[3 * i], origins[3 * i + 1], origins[3 * i + 2], dist[i]);
+  sq.dir_out[i] = make_float4(dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2], bitsf(i));
+  sq.ids[i] = make_uint4(ids[4 * i], ids[4 * i + 1], ids[4 * i + 2], ids[4 * i + 3]);
+}
+__global__ __launch_bounds__(256) void k_visibility_unpack(uint32_t n, const float4* vis, float* out) {
+  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= n) return;
+  const float4 v = vis[i];
+  out[3 * i] = v.x; out[3 * i + 1] = v.y; out[3 * i + 2] = v.z;
+}
+
 // ---- camera ray of one pixel (first sample id), for pixel queries; valid[0] = 0: the ray did not leave the lens ----
 __global__ void k_pixel_ray(DeviceScene sc, DeviceLens lens, int cam, uint32_t x, uint32_t y, uint32_t sample_id, float* origin, float* dir, uint32_t* valid) {
   if (blockIdx.x != 0 || threadIdx.x != 0) return;

@@ -77,6 +77,9 @@ struct WavefrontKernels {
                           float4* rec_a, uint4* rec_b);
   void (*denoise_atrous)(hipStream_t s, const DenoiseArgs& p, const float4* a_in, const uint4* rec_b, float4* a_out, bool lds);
   void (*denoise_finish)(uint32_t grid, hipStream_t s, const DenoiseArgs& p, const float4* rec_a, const float* guides, float* image);
+  // the light-BVH query of n plain rays, one per thread (k_light_query_probe; device buffers: float3 origins / dirs, uint2 self handles, float randoms)
+  void (*light_query_probe)(hipStream_t s, const DeviceScene& sc, uint32_t n, const float* origins, const float* dirs, const uint32_t* self, const float* randoms, uint32_t* out_ids,
+                            uint32_t* out_num_hits);
 };
 
 const WavefrontKernels* wavefront_kernels_exact();  // csrc/host/core.hip

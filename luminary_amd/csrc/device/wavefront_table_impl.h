@@ -159,10 +159,14 @@ static void denoise_atrous(hipStream_t s, const DenoiseArgs& p, const float4* a_
 static void denoise_finish(uint32_t grid, hipStream_t s, const DenoiseArgs& p, const float4* rec_a, const float* guides, float* image) {
   hipLaunchKernelGGL(k_denoise_finish, dim3(grid), dim3(256), 0, s, p, rec_a, guides, image);
 }
+static void light_query_probe(hipStream_t s, const DeviceScene& sc, uint32_t n, const float* origins, const float* dirs, const uint32_t* self, const float* randoms, uint32_t* out_ids,
+                              uint32_t* out_num_hits) {
+  hipLaunchKernelGGL(k_light_query_probe, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, sc, n, origins, dirs, self, randoms, out_ids, out_num_hits);
+}
 
 static const WavefrontKernels kTable = {LUM_FLAVOUR_NAME, (uint32_t) kTraceBlock, set_ray_kernel_lds, init_sampler_seeds, sobol_table, generate,    generate_adaptive, trace,  sky_inscattering, shade,
                                         shade_debug,      sky,              light_query,        shadow_rays, resolve, resolve_reuse, resolve_listed, resolve_ended, LUM_FAST != 0, volume_inscatter, volume_resolve, volume_events, volume_bounce, trace_particles, particle_shade, trace_ocean, ocean_shade, clouds_list, clouds_march, clouds, trace_rays,
-                                        camera_rays,      guide,            guide_normalise,    denoise_prepare, denoise_atrous, denoise_finish};
+                                        camera_rays,      guide,            guide_normalise,    denoise_prepare, denoise_atrous, denoise_finish, light_query_probe};
 
 }  // namespace table
 LUM_NS_END

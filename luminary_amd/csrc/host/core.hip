@@ -2267,6 +2267,99 @@ int lumc_trace_closest_host(LumContext* ctx, uint32_t n, const float* origins, c
   return rc;
 }
 
+// Visibility rays through the render's own kernel: a temporary ShadowQueue whose output index is the ray index, the item count and the work cursor in the spare
+// control row, the active flavour's k_shadow_rays with the render's grid, LDS size and staged nodes. The answers start as a NaN pattern, so a ray that nobody
+// answered shows. Synchronises the stream (the temporaries are freed before the call returns).
+int lumc_trace_visibility(LumContext* ctx, uint32_t n, const float* d_origins, const float* d_dirs, const float* d_dist, const uint32_t* d_ids, const uint32_t* d_order, float* d_out,
+                          void* stream_) {
+  if (!ctx || !ctx->has_scene) { if (ctx) ctx->error = "lumc_trace_visibility: no scene"; return 1; }
+  if (n == 0) return 0;
+  if (!d_origins || !d_dirs || !d_dist || !d_ids || !d_out) { ctx->error = "lumc_trace_visibility: null argument"; return 1; }
+  hipStream_t stream = (hipStream_t) stream_;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  float4* items = nullptr;  // origin_dist | dir_out | ids | vis, n entries of 16 bytes each
+  HIP_TRY(ctx, hipMalloc((void**) &items, sizeof(float4) * 4 * (size_t) n));
+  ShadowQueue sq{};
+  sq.origin_dist = items; sq.dir_out = items + n; sq.ids = reinterpret_cast<uint4*>(items + 2 * (size_t) n); sq.vis = items + 3 * (size_t) n;
+  sq.capacity = n;
+  uint32_t* ctrl = ctx->d_ctrl + kCtlStride * (kCtrlRows - 2);
+  const uint32_t blocks = (n + 255u) / 256u;
+  hipError_t e = hipMemsetAsync(sq.vis, 0xFF, sizeof(float4) * (size_t) n, stream);
+  if (e == hipSuccess) e = hipMemsetD32Async((hipDeviceptr_t) (ctrl + kCtlShadowItems), (int) n, 1, stream);
+  if (e == hipSuccess) e = hipMemsetAsync(ctrl + kCtlShadowCursor, 0, sizeof(uint32_t), stream);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_visibility_pack, dim3(blocks), dim3(256), 0, stream, n, d_origins, d_dirs, d_dist, d_ids, sq);
+    {
+      Launch l(ctx, stream, LUMC_KERNEL_SHADOW);
+      ctx->wf->shadow_rays(grid_persistent(ctx, n), (size_t) ctx->lds_nodes * kNodeBytes + LUM_LDS_STACK_BYTES, stream, ctx->scene, sq, d_order, ctrl, ctx->d_counters, ctx->lds_nodes);
+    }
+    hipLaunchKernelGGL(k_visibility_unpack, dim3(blocks), dim3(256), 0, stream, n, sq.vis, d_out);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(stream);
+  (void) hipFree(items);
+  if (e != hipSuccess) { ctx->error = hipGetErrorString(e); return 1; }
+  return 0;
+}
+
+// device copy of a host array (nullptr in, nullptr out); false = failed
+static bool to_device_bytes(const void* host, size_t bytes, void** dev) {
+  *dev = nullptr;
+  if (!host) return true;
+  return hipMalloc(dev, bytes) == hipSuccess && hipMemcpy(*dev, host, bytes, hipMemcpyHostToDevice) == hipSuccess;
+}
+
+int lumc_trace_visibility_host(LumContext* ctx, uint32_t n, const float* origins, const float* dirs, const float* dist, const uint32_t* ids, const uint32_t* order, float* out) {
+  if (!ctx || !ctx->has_scene) { if (ctx) ctx->error = "lumc_trace_visibility_host: no scene"; return 1; }
+  if (n == 0) return 0;
+  if (!origins || !dirs || !dist || !ids || !out) { ctx->error = "lumc_trace_visibility_host: null argument"; return 1; }
+  if (order) {  // a slot that names no ray would read outside the queue
+    for (uint32_t i = 0; i < n; i++) if (order[i] >= n) { ctx->error = "lumc_trace_visibility_host: order entry out of range"; return 1; }
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  float *d_o = nullptr, *d_d = nullptr, *d_t = nullptr, *d_out = nullptr;
+  uint32_t *d_i = nullptr, *d_ord = nullptr;
+  int rc = 1;
+  if (to_device_bytes(origins, sizeof(*origins) * 3 * (size_t) n, (void**) &d_o) && to_device_bytes(dirs, sizeof(*dirs) * 3 * (size_t) n, (void**) &d_d) && to_device_bytes(dist, sizeof(*dist) * (size_t) n, (void**) &d_t) && to_device_bytes(ids, sizeof(*ids) * 4 * (size_t) n, (void**) &d_i) &&
+      to_device_bytes(order, sizeof(*order) * (size_t) n, (void**) &d_ord) && hipMalloc((void**) &d_out, sizeof(float) * 3 * (size_t) n) == hipSuccess) {
+    rc = lumc_trace_visibility(ctx, n, d_o, d_d, d_t, d_i, d_ord, d_out, nullptr);
+    if (!rc && hipMemcpy(out, d_out, sizeof(float) * 3 * (size_t) n, hipMemcpyDeviceToHost) != hipSuccess) { ctx->error = "lumc_trace_visibility_host: download failed"; rc = 1; }
+  }
+  else ctx->error = "lumc_trace_visibility_host: upload failed";
+  (void) hipFree(d_o); (void) hipFree(d_d); (void) hipFree(d_t); (void) hipFree(d_i); (void) hipFree(d_ord); (void) hipFree(d_out);
+  return rc;
+}
+
+// The light-BVH query of BSDF-sampled directions (light_query, dev_trace.h) on plain rays, in the active flavour: out_ids = the picked light or 0xFFFFFFFF, out_num_hits = the
+// number of candidates. A scene without lights answers (0xFFFFFFFF, 0) without a launch.
+int lumc_light_query_host(LumContext* ctx, uint32_t n, const float* origins, const float* dirs, const uint32_t* self, const float* randoms, uint32_t* out_ids, uint32_t* out_num_hits) {
+  if (!ctx || !ctx->has_scene) { if (ctx) ctx->error = "lumc_light_query_host: no scene"; return 1; }
+  if (n == 0) return 0;
+  if (!origins || !dirs || !self || !randoms || !out_ids || !out_num_hits) { ctx->error = "lumc_light_query_host: null argument"; return 1; }
+  const DeviceScene& sc = ctx->scene;
+  if (!sc.num_lights || !sc.light_nodes || !sc.light_tris || !sc.light_tri_handles) {
+    for (uint32_t i = 0; i < n; i++) { out_ids[i] = 0xFFFFFFFFu; out_num_hits[i] = 0u; }
+    return 0;
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  float *d_o = nullptr, *d_d = nullptr, *d_r = nullptr;
+  uint32_t *d_s = nullptr, *d_out = nullptr;
+  int rc = 1;
+  if (to_device_bytes(origins, sizeof(*origins) * 3 * (size_t) n, (void**) &d_o) && to_device_bytes(dirs, sizeof(*dirs) * 3 * (size_t) n, (void**) &d_d) && to_device_bytes(self, sizeof(*self) * 2 * (size_t) n, (void**) &d_s) && to_device_bytes(randoms, sizeof(*randoms) * (size_t) n, (void**) &d_r) &&
+      hipMalloc((void**) &d_out, sizeof(uint32_t) * 2 * (size_t) n) == hipSuccess && hipMemset(d_out, 0xFF, sizeof(uint32_t) * 2 * (size_t) n) == hipSuccess) {
+    ctx->wf->light_query_probe(nullptr, sc, n, d_o, d_d, d_s, d_r, d_out, d_out + n);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(out_ids, d_out, sizeof(uint32_t) * (size_t) n, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(out_num_hits, d_out + n, sizeof(uint32_t) * (size_t) n, hipMemcpyDeviceToHost);
+    rc = e == hipSuccess ? 0 : 1;
+    if (rc) ctx->error = hipGetErrorString(e);
+  }
+  else ctx->error = "lumc_light_query_host: upload failed";
+  (void) hipFree(d_o); (void) hipFree(d_d); (void) hipFree(d_s); (void) hipFree(d_r); (void) hipFree(d_out);
+  return rc;
+}
+
 int lumc_pixel_query(LumContext* ctx, uint32_t x, uint32_t y, uint32_t sample_id, uint32_t out[6]) {
   if (!ctx || !ctx->has_scene || !out) { if (ctx) ctx->error = "lumc_pixel_query: no scene"; return 1; }
   if (x >= ctx->scene.width || y >= ctx->scene.height) { ctx->error = "lumc_pixel_query: pixel outside the frame"; return 1; }

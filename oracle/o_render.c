@@ -1067,6 +1067,34 @@ int oracle_trace_closest(
   return 0;
 }
 
+int oracle_trace_shadow(
+  const OracleScene* s, uint32_t num_rays, const float* origins, const float* dirs, const float* dist, const uint32_t* ids, int use_bvh, float* out) {
+  OTracer tr;
+  tracer_init(&tr, s, use_bvh);
+#pragma omp parallel for schedule(dynamic, 256)
+  for (int64_t i = 0; i < (int64_t) num_rays; i++) {
+    const vec3 o = v3(origins[3 * i], origins[3 * i + 1], origins[3 * i + 2]), d = v3(dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2]);
+    const RGBF v = trace_shadow(&tr, o, d, dist[i], ids[4 * i], ids[4 * i + 1], ids[4 * i + 2], ids[4 * i + 3]);
+    out[3 * i] = v.r; out[3 * i + 1] = v.g; out[3 * i + 2] = v.b;
+  }
+  tracer_free(&tr);
+  return 0;
+}
+
+int oracle_trace_light_bvh(
+  const OracleScene* s, uint32_t num_rays, const float* origins, const float* dirs, const uint32_t* self_handles, const float* randoms, int use_bvh,
+  uint32_t* out_ids, uint32_t* out_num_hits) {
+  OTracer tr;
+  tracer_init(&tr, s, use_bvh);
+#pragma omp parallel for schedule(dynamic, 256)
+  for (int64_t i = 0; i < (int64_t) num_rays; i++) {
+    const vec3 o = v3(origins[3 * i], origins[3 * i + 1], origins[3 * i + 2]), d = v3(dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2]);
+    out_ids[i] = trace_light_bvh(&tr, o, d, self_handles[2 * i], self_handles[2 * i + 1], randoms[i], &out_num_hits[i]);
+  }
+  tracer_free(&tr);
+  return 0;
+}
+
 /* ---- BSDF energy LUTs (bsdf_lut.cuh:20-211); pixel (0,0), depth 0, sample id = iteration ---- */
 #define LUT_ITER 0x10000u
 static uint16_t lut_quant(float sum) { return (uint16_t) (1 + (uint16_t) (ceilf(o_saturate(sum) * 0xFFFE))); }

@@ -291,6 +291,7 @@ static inline RGBF trace_shadow(const OTracer* tr, vec3 origin, vec3 dir, float 
    * carried in binary64 (exact for two factors) and rounded to binary32 once; the HIP path does the same. */
   double thr[3] = {1.0, 1.0, 1.0};
   bool blocked = false;
+  if (dist > FLT_MAX) dist = FLT_MAX; /* a miss is th = FLT_MAX, which th < dist must reject: under dist = +inf every triangle counted as crossed */
   for (uint32_t inst = 0; inst < s->num_instances && !blocked; inst++) {
     const uint32_t mesh = s->instance_mesh_ids[inst];
     if (mesh >= s->num_meshes) continue;

@@ -135,6 +135,17 @@ int oracle_trace_closest(
   const OracleScene* scene, uint32_t num_rays, const float* origins, const float* dirs, const uint32_t* ignore_handles, int use_bvh,
   uint32_t* out_hits);
 
+/* Visibility query of the traversal truth tests: per ray a distance (the segment is (eps, dist)) and four handle words (target instance, target triangle, self
+ * instance, self triangle; 0xFFFFFFFF = none); out = the transparency product rgb (3 floats per ray), 0 where an opaque surface is crossed. */
+int oracle_trace_shadow(
+  const OracleScene* scene, uint32_t num_rays, const float* origins, const float* dirs, const float* dist, const uint32_t* ids, int use_bvh, float* out);
+
+/* Light-BVH query of the same tests: per ray a self handle (instance, triangle) and a random number; out_ids = the picked light (0xFFFFFFFF = none),
+ * out_num_hits = the number of candidates. */
+int oracle_trace_light_bvh(
+  const OracleScene* scene, uint32_t num_rays, const float* origins, const float* dirs, const uint32_t* self_handles, const float* randoms, int use_bvh,
+  uint32_t* out_ids, uint32_t* out_num_hits);
+
 /* BSDF energy LUT generation (bsdf_lut.cuh). texel range [first, first+count) of the named table:
  * 0 conductor, 1 glossy (needs conductor), 2 dielectric, 3 dielectric_inv. */
 int oracle_generate_lut(const uint32_t* bluenoise_2d, int table, uint32_t first, uint32_t count, const uint16_t* conductor, uint16_t* dst);

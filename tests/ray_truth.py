@@ -324,3 +324,293 @@ def solve(scene, origins, dirs, ignore=None, block=400_000):
             farther[r0:r1] = np.where(better, base + j, farther[r0:r1])
             far_t = np.where(better, best, far_t)
     return Solution(scene, o, d, ignore_pair, nearest_upper, num_acc, the_acc, farther)
+
+
+# ---- visibility rays: what a segment (eps, dist) certainly crosses, and which transparency products a float32 implementation may answer ----
+# The pairs are classified with _object_ray and _intersect as they stand, nothing added to their bounds. With the float64 distance t, its float32 bound bt,
+# eps = kEps and the float32 dist of the ray, a pair that is neither the target nor self is
+#   certainly crossed      class HIT and t - bt > eps and t + bt < dist,
+#   certainly not crossed  class MISS, or t + bt <= eps, or t - bt >= dist,
+#   ambiguous              otherwise.
+# The factor of a pair is what ShadowState::on_tris (dev_trace.h) multiplies in, restated in float32 on the material words the device reads: alpha 1 is
+# opaque, alpha 0 uncoloured is absent, otherwise 1 - alpha, times the albedo where the material has coloured transparency. A textured material is supported
+# only where every texel of its texture is the same (and its gamma is 1): the bilinear fetch then returns that texel whatever uv is.
+# NOT covered: uv-dependent textured alpha, the ambient-reuse equivalence (a closest-hit ray answering a visibility question), the particle tree.
+K_EPS = float(np.float32(1.1920928955078125e-7))  # dev_math.h kEps
+ABSENT, FACTOR, OPAQUE = 0, 1, 2
+MAX_AMBIGUOUS = 6   # subsets are enumerated up to 2^6 per ray; a ray with more ambiguous pairs is undecided
+MAX_FACTORS = 12    # with factors >= 2^-6 nothing underflows
+DMAT_COLOURED = 0x10
+
+
+def _unorm16(d):
+    return np.asarray(d, dtype=np.uint32).astype(np.float32) * (np.float32(1.0) / np.float32(0xFFFF))
+
+
+def surface_factors(view):
+    """(kind [T] of ABSENT / FACTOR / OPAQUE, factor [T, 3] float32) per scene triangle, from the material words and the textures of a DeviceSceneView."""
+    import ctypes as C
+    import oracle_lib
+    a = oracle_lib.view_arrays(view)
+    m = a["materials"].reshape(-1, 16).astype(np.uint32)
+    coloured = (m[:, 0] & DMAT_COLOURED) != 0
+    albedo, alpha = _unorm16(m[:, 4:7]), _unorm16(m[:, 7])
+    ntex = int(view.num_textures)
+    table = oracle_lib._array(view.texture_table, C.c_uint32, 4 * ntex).reshape(-1, 4)
+    texels = oracle_lib._array(view.texels, C.c_uint32, int((table[:, 0] + table[:, 1] * table[:, 2]).max()) if ntex else 0)
+    for i in range(len(m)):
+        tex = int(m[i, 12])
+        if tex == 0xFFFF:
+            continue
+        if tex >= ntex:
+            albedo[i], alpha[i] = np.float32(0.9), np.float32(1.0)
+            continue
+        first, w, h, gamma = [int(x) for x in table[tex]]
+        tx = texels[first:first + w * h]
+        assert (tx == tx[0]).all() and np.uint32(gamma).view(np.float32) == 1.0, "the truth supports constant-texel textures of gamma 1 only"
+        c = np.array([tx[0] & 0xFF, (tx[0] >> 8) & 0xFF, (tx[0] >> 16) & 0xFF, tx[0] >> 24], dtype=np.uint32).astype(np.float32) * (np.float32(1.0) / np.float32(255.0))
+        albedo[i], alpha[i] = c[0:3], c[3]
+    tp = np.float32(1.0) - alpha
+    f = np.where(coloured[:, None], albedo * tp[:, None], np.repeat(tp[:, None], 3, axis=1)).astype(np.float32)
+    kind = np.where(alpha == 1.0, OPAQUE, np.where((alpha == 0.0) & ~coloured, ABSENT, FACTOR)).astype(np.int8)
+    mat = a["tri_tex"].reshape(-1, 4)[:, 3] & 0xFFFF
+    return kind[mat], f[mat]
+
+
+def _half_ulp32(p):
+    """Half a float32 ulp at the magnitude of the float64 values p (normal range)."""
+    _, e = np.frexp(np.abs(p))
+    return np.where(p == 0.0, 0.0, np.ldexp(1.0, e - 25))
+
+
+class VisibilitySolution:
+    """What the truth knows about a set of visibility rays. `check` is the acceptor."""
+
+    def __init__(self, finite, must_block, may_block, product, k_certain, amb_factors, num_ambiguous, one_factor):
+        self.finite = finite                # the ray's origin and direction are finite (a non-finite ray crosses nothing: (1, 1, 1))
+        self.must_block = must_block        # an opaque pair is certainly crossed
+        self.may_block = may_block          # an opaque pair is ambiguous
+        self.product = product              # [R, 3] longdouble: product of the certainly crossed factors
+        self.k_certain = k_certain          # their number
+        self.amb_factors = amb_factors      # per ray: list of float32 [3] factors of the ambiguous non-opaque pairs
+        self.num_ambiguous = num_ambiguous  # ambiguous pairs, the opaque ones included
+        self.one_factor = one_factor        # [R, 3] float32: one of the certainly crossed factors (1 where there is none), for mutation tests
+        self.undecided = num_ambiguous > MAX_AMBIGUOUS
+        self.decisive = (num_ambiguous == 0) | ~finite
+
+    def expected(self):
+        """The one acceptable answer of every decisive ray: the product rounded once ([R, 3] float32; 0 where blocked)."""
+        p = np.where(self.must_block[:, None], 0.0, self.product.astype(np.float64)).astype(np.float32)
+        p[~self.finite] = 1.0
+        return p
+
+    def check(self, answers, fast=False):
+        """answers [R, 3] float32. Returns (ok [R], reason [R]). Zero is required where an opaque pair is certainly crossed and allowed where one is ambiguous;
+        otherwise all three channels must be the certainly crossed product times the factors of ONE subset of the ambiguous pairs: within half a float32 ulp plus
+        2^-50 relative (the exact flavour: a binary64 product rounded once), or within (k - 1) u / (1 - (k - 1) u), u = 2^-24, for k factors (`fast`: a binary32
+        product in any order)."""
+        ans = np.ascontiguousarray(answers, dtype=np.float32).astype(np.float64)
+        n = len(ans)
+        ok = np.zeros(n, dtype=bool)
+        reason = np.full(n, None, dtype=object)
+        for i in range(n):
+            a = ans[i]
+            if not np.all(np.isfinite(a)):
+                reason[i] = "not a number: %s (a ray nobody answered keeps the NaN pattern)" % a
+                continue
+            if not self.finite[i]:
+                ok[i] = bool(np.all(a == 1.0))
+                reason[i] = None if ok[i] else "a non-finite ray crosses nothing: (1, 1, 1), not %s" % a
+                continue
+            if self.undecided[i]:
+                ok[i] = True
+                continue
+            zero = bool(np.all(a == 0.0))
+            if self.must_block[i]:
+                ok[i] = zero
+                reason[i] = None if zero else "an opaque surface is certainly crossed, answer %s" % a
+                continue
+            if zero and self.may_block[i]:
+                ok[i] = True
+                continue
+            fs = self.amb_factors[i]
+            best = None
+            for subset in range(1 << len(fs)):
+                p = self.product[i].copy()
+                k = int(self.k_certain[i])
+                for j in range(len(fs)):
+                    if subset >> j & 1:
+                        p = p * fs[j].astype(np.longdouble)
+                        k += 1
+                p = p.astype(np.float64)
+                if fast:
+                    ku = max(k - 1, 0) * U
+                    tol = np.abs(p) * (ku / (1.0 - ku))
+                else:
+                    tol = _half_ulp32(p) + np.abs(p) * 2.0 ** -50
+                err = np.abs(a - p)
+                if np.all(err <= tol):
+                    ok[i] = True
+                    break
+                if best is None or err.max() < best[0]:
+                    best = (err.max(), p, tol, k)
+            if not ok[i]:
+                reason[i] = "answer %s; nearest admissible product %s (k = %d, tolerance %s), %d ambiguous pair(s)%s" % (
+                    a, best[1], best[3], best[2], int(self.num_ambiguous[i]), ", zero only if blocked" if zero else "")
+        return ok, reason
+
+
+def solve_visibility(scene, kind, factor, origins, dirs, dist, ids, block=400_000):
+    """Brute force over every pair, like solve. kind / factor: surface_factors; dist [R] float32; ids [R, 4]: target and self handles."""
+    o32, d32 = np.ascontiguousarray(origins, dtype=np.float32), np.ascontiguousarray(dirs, dtype=np.float32)
+    finite = np.isfinite(o32).all(axis=1) & np.isfinite(d32).all(axis=1)
+    o = np.where(finite[:, None], o32, 0.0).astype(np.float64)
+    d = np.where(finite[:, None], d32, 1.0).astype(np.float64)
+    dist = np.ascontiguousarray(dist, dtype=np.float32).astype(np.float64)
+    ids = np.ascontiguousarray(ids, dtype=np.uint32)
+    n = o.shape[0]
+    tgt, slf = scene.pair_of(ids[:, 0], ids[:, 1]), scene.pair_of(ids[:, 2], ids[:, 3])
+    must = np.zeros(n, dtype=bool)
+    may = np.zeros(n, dtype=bool)
+    product = np.ones((n, 3), dtype=np.longdouble)
+    k_certain = np.zeros(n, dtype=np.int64)
+    num_amb = np.zeros(n, dtype=np.int64)
+    amb = [[] for _ in range(n)]
+    one = np.ones((n, 3), dtype=np.float32)
+    step = max(1, block // max(scene.num_pairs, 1))
+    for r0 in range(0, n, step):
+        r1 = min(n, r0 + step)
+        for (_, first, count, rows, tr, base) in scene.instances:
+            oo, od = _object_ray(rows, tr, o[r0:r1], d[r0:r1])
+            sl = slice(first, first + count)
+            cls, t, bt = _intersect(oo, od, scene.p0[None, sl], scene.e1[None, sl], scene.e2[None, sl])
+            pair = (base + np.arange(count))[None, :]
+            skipped = (tgt[r0:r1, None] == pair) | (slf[r0:r1, None] == pair) | (kind[sl] == ABSENT)[None, :] | ~finite[r0:r1, None]
+            dd = dist[r0:r1, None]
+            with np.errstate(invalid="ignore"):
+                crossed = (cls == HIT) & (t - bt > K_EPS) & (t + bt < dd) & ~skipped
+                out = (cls == MISS) | (t + bt <= K_EPS) | (t - bt >= dd) | skipped
+            ambiguous = ~crossed & ~out
+            opaque = (kind[sl] == OPAQUE)[None, :]
+            must[r0:r1] |= (crossed & opaque).any(axis=1)
+            may[r0:r1] |= (ambiguous & opaque).any(axis=1)
+            fc = crossed & ~opaque
+            take = fc.any(axis=1) & (k_certain[r0:r1] == 0)
+            one[r0:r1][take] = factor[sl][fc.argmax(axis=1)[take]]
+            k_certain[r0:r1] += fc.sum(axis=1)
+            for ch in range(3):
+                product[r0:r1, ch] *= np.where(fc, factor[sl, ch][None, :].astype(np.longdouble), np.longdouble(1.0)).prod(axis=1)
+            num_amb[r0:r1] += ambiguous.sum(axis=1)
+            for (r, j) in zip(*np.nonzero(ambiguous & ~opaque)):
+                if len(amb[r0 + r]) <= MAX_AMBIGUOUS:
+                    amb[r0 + r].append(factor[first + j])
+    return VisibilitySolution(finite, must, may, product, k_certain, amb, num_amb, one)
+
+
+# ---- light queries: which lights the reservoir of light_query (dev_trace.h) may count, and which one it may pick ----
+# The light triangles are world-space (light_bvh_tris, no instance map): the ray enters _intersect as it is. A light that is neither `self` nor fully
+# transparent and uncoloured is certainly hit (class HIT, t - bt > eps), certainly not (class MISS or t + bt <= eps) or ambiguous. The opaque ones bracket
+# t*, the distance of the nearest opaque light: t* <= hi = min (t + bt) over the certainly hit opaque lights, t* >= lo = min (t - bt) over the possibly hit
+# ones. A transparent light is certainly a candidate (t <= t*) where it is certainly hit with t + bt < lo, possibly one where it is possibly hit with
+# t - bt <= hi. An opaque light is a candidate only as THE nearest opaque one: possibly where t - bt <= hi, certainly where it is certainly hit and no
+# other opaque light is possibly that near. NOT covered: uv-dependent textured alpha, the particle tree.
+LIGHT_INVALID = 0xFFFFFFFF
+
+
+def squares32(key, counter):
+    """dev_sampler.h squares32 on uint32 arrays."""
+    key, counter = np.uint64(key), np.asarray(counter, dtype=np.uint64) & np.uint64(0xFFFFFFFF)
+    m = np.uint64(0xFFFFFFFF)
+
+    def swap(a):
+        return ((a >> np.uint64(16)) | (a << np.uint64(16))) & m
+    x = (counter * key) & m
+    y = x
+    z = (y + key) & m
+    x = swap((x * x + y) & m)
+    x = swap((x * x + z) & m)
+    x = swap((x * x + y) & m)
+    x = (x * x + z) & m
+    t = x
+    x = swap(x)
+    return (t ^ ((x * x + y) & m)).astype(np.uint32)
+
+
+def light_pick(ids, random_bits):
+    """The light the reservoir keeps among `ids`: the minimum of squares32(0xfcbd6e15, 0x9E3779B9 * id + bits(random)), ties to the lower id."""
+    ids = np.sort(np.asarray(ids, dtype=np.uint64))
+    keys = squares32(0xfcbd6e15, (np.uint64(0x9E3779B9) * ids + np.uint64(random_bits)) & np.uint64(0xFFFFFFFF))
+    return int(ids[np.argmin(keys)])  # argmin returns the first minimum: the lower id
+
+
+class LightSolution:
+    def __init__(self, finite, certain, possible, randoms):
+        self.finite, self.certain, self.possible = finite, certain, possible  # [R, L] bool
+        self.random_bits = np.ascontiguousarray(randoms, dtype=np.float32).view(np.uint32)
+        self.decisive = (certain == possible).all(axis=1)
+
+    def expected(self):
+        """(id, num_hits) of every decisive ray; meaningless elsewhere."""
+        n = len(self.finite)
+        ids, hits = np.full(n, LIGHT_INVALID, dtype=np.uint32), self.certain.sum(axis=1).astype(np.uint32)
+        for i in np.nonzero(hits)[0]:
+            ids[i] = light_pick(np.nonzero(self.certain[i])[0], self.random_bits[i])
+        return ids, hits
+
+    def check(self, ids, hits):
+        """num_hits must lie in [|certain|, |possible|]; the id must be a possible candidate, or invalid only where no candidate is certain. On decisive rays
+        both are determined: the hash pick is restated here."""
+        ids, hits = np.asarray(ids, dtype=np.uint32), np.asarray(hits, dtype=np.uint32)
+        n = len(ids)
+        ok = np.zeros(n, dtype=bool)
+        reason = np.full(n, None, dtype=object)
+        lo, hi = self.certain.sum(axis=1), self.possible.sum(axis=1)
+        want_ids, _ = self.expected()
+        for i in range(n):
+            if not (lo[i] <= hits[i] <= hi[i]):
+                reason[i] = "num_hits %d outside [%d, %d]" % (hits[i], lo[i], hi[i])
+            elif ids[i] == LIGHT_INVALID:
+                if lo[i] > 0 or hits[i] > 0:
+                    reason[i] = "no light picked although %d are counted (%d certain)" % (hits[i], lo[i])
+                else:
+                    ok[i] = True
+            elif ids[i] >= self.possible.shape[1] or not self.possible[i, ids[i]]:
+                reason[i] = "light %d is no possible candidate" % ids[i]
+            elif hits[i] == 0:
+                reason[i] = "light %d picked from none" % ids[i]
+            elif self.decisive[i] and ids[i] != want_ids[i]:
+                reason[i] = "light %d picked, the hash picks %d of %s" % (ids[i], want_ids[i], list(np.nonzero(self.certain[i])[0]))
+            else:
+                ok[i] = True
+        return ok, reason
+
+
+def solve_lights(view, origins, dirs, self_handles, randoms):
+    import oracle_lib
+    a = oracle_lib.view_arrays(view)
+    kind_tri, _ = surface_factors(view)
+    handles = a["light_tri_handles"].reshape(-1, 2).astype(np.int64)
+    v = _f32(a["light_bvh_tris"]).reshape(-1, 3, 4)[:, :, 0:3]
+    p0 = v[:, 0, :].astype(np.float64)[None]
+    e1, e2 = (v[:, 1, :] - v[:, 0, :]).astype(np.float64)[None], (v[:, 2, :] - v[:, 0, :]).astype(np.float64)[None]
+    mesh = np.asarray(a["instance_mesh_ids"], dtype=np.int64)[handles[:, 0]]
+    kind = kind_tri[np.asarray(a["mesh_tri_offset"], dtype=np.int64)[mesh] + handles[:, 1]]
+    o32, d32 = np.ascontiguousarray(origins, dtype=np.float32), np.ascontiguousarray(dirs, dtype=np.float32)
+    finite = np.isfinite(o32).all(axis=1) & np.isfinite(d32).all(axis=1)
+    o = np.where(finite[:, None], o32, 0.0).astype(np.float64)
+    d = np.where(finite[:, None], d32, 1.0).astype(np.float64)
+    oo, od = [_exact(o[:, k:k + 1]) for k in range(3)], [_exact(d[:, k:k + 1]) for k in range(3)]
+    cls, t, bt = _intersect(oo, od, p0, e1, e2)
+    sh = np.ascontiguousarray(self_handles, dtype=np.uint32).astype(np.int64)
+    skipped = ((sh[:, 0:1] == handles[None, :, 0]) & (sh[:, 1:2] == handles[None, :, 1])) | (kind == ABSENT)[None, :] | ~finite[:, None]
+    with np.errstate(invalid="ignore"):
+        hit = (cls == HIT) & (t - bt > K_EPS) & ~skipped
+        maybe = ~((cls == MISS) | (t + bt <= K_EPS) | skipped)
+        opaque = (kind == OPAQUE)[None, :]
+        hi = np.where(hit & opaque, t + bt, np.inf).min(axis=1, keepdims=True)
+        lo = np.where(maybe & opaque, t - bt, np.inf).min(axis=1, keepdims=True)
+        near_opaque = maybe & opaque & (t - bt <= hi)   # the opaque lights that may be the nearest one
+        only = near_opaque.sum(axis=1, keepdims=True) == 1
+        certain = np.where(opaque, near_opaque & hit & only, hit & (t + bt < lo))
+        possible = np.where(opaque, near_opaque, maybe & (t - bt <= hi))
+    return LightSolution(finite, certain, possible, randoms)

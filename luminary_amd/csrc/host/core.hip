@@ -26,165 +26,12 @@
 #include "../device/dev_adaptive.h"
 #include "../device/wavefront_table_impl.h"  // this translation unit holds the exact flavour; the fast one is csrc/device/wavefront_fast.hip
 #include <hipcub/hipcub.hpp>
-#include <rccl/rccl.h>
-#include "bvh_build.h"
+#include "context.h"
+#include "tiles.h"
 
-using namespace lum;
-
-// A mesh's bottom-level tree (node indices relative to the mesh, leaf ranges relative to its first triangle). The contexts of one process share them: a host
-// with several devices hands every context the same meshes, the first one builds a mesh's tree, the others - and a later upload of the same mesh - take it
-// from find_mesh_tree (below), and it is released with the last context that holds it.
-struct MeshTree { Bvh4 bvh; bool built_on_gpu = false; };
-
-struct LumContext {
-  int device = 0;
-  std::string error;
-  const WavefrontKernels* wf = wavefront_kernels_fast();  // flavour of the wavefront kernels (lumc_set_flavour; LUM_FLAVOUR=exact|fast overrides the default)
-  int camera = kCamThinLens;  // CameraKind of the camera-ray kernels (lumc_set_physical_camera)
-  DeviceLens lens{};          // the physical camera's lens, an argument of those kernels
-  // device allocations of the scene by the part of it they belong to (lumc_scene_update frees and rebuilds a part at a time)
-  enum AllocGroup { kGrpMesh = 0, kGrpInst, kGrpMat, kGrpLight, kGrpTex, kGrpConst, kGrpPart, kGrpOnce, kGrpCount };
-  std::vector<void*> scene_allocs[kGrpCount];
-  // what a partial update needs again: the per-mesh trees (node indices relative to the mesh, leaf ranges relative to its first triangle) and boxes
-  std::vector<std::shared_ptr<const MeshTree>> mesh_bvh;
-  std::vector<Aabb> mesh_box;
-  std::vector<uint32_t> sky_lut_key;  // the sky parameters the two sky tables were generated from
-  float* d_bridge_lut = nullptr;      // the bridge sampler's vertex-count table (context-owned: scene.bridge_lut points here while bridges are possible)
-  std::vector<float> bridge_lut_host; // its content, to notice a caller that hands over another table
-  float4* d_sky_lut[2] = {nullptr, nullptr};
-  DeviceScene scene{};
-  bool has_scene = false;
-  uint64_t bvh_stats[4] = {0, 0, 0, 0};
-  int ambient_reuse = -1;         // -1 by flavour (fast: on), 0 off, 1 on (lumc_set_ambient_reuse; LUM_AMBIENT_REUSE)
-  uint32_t shade_grid_rounds = 2;  // k_shade's grid as a multiple of its resident set (0: the common 2048-workgroup cap); LUM_SHADE_GRID
-  int fused_resolve = 1;          // with the fast flavour's ambient reuse: k_shade resolves the previous depth's vertices itself (lumc_set_fused_resolve; LUM_FUSED_RESOLVE)
-  void* fused_block = nullptr;    // what that needs beyond the usual work buffers: a third path queue, the parent words, a second set of NEE records, the fallback rays' items
-  bool fused_records_stale = false;  // a queue's planes changed places (ray-sorting mode 3) since the records were written
-  uint32_t fused_capacity = 0, fused_refused_capacity = 0;  // (the capacity its allocation last failed for: not tried again)
-  uint2* d_sobol = nullptr;         // the pass's Sobol / Owen table (dev_sampler.h LUM_SOBOL_TABLE; wavefront_depths fills it)
-  size_t sobol_entries = 0;
-  int sobol_table = 1;              // LUM_SOBOL_TABLE_RT=0: the sampler hashes every number itself
-  uint32_t* d_ended[2] = {nullptr, nullptr};  // a depth's vertices that no entry continues, by the depth's parity (k_shade lists them; the next depth's k_shade resolves them, or k_resolve_ended)
-  // ... the next depth's k_shade (1) or k_resolve_ended after the depth's visibility pass (0; LUM_FUSED_ENDED=0)
-  int fused_ended = 1;
-  int fused_ended_default = 1;  // what lumc_set_fused_resolve(1) goes back to (the environment's choice, if any)
-  FusedResolve* d_fused = nullptr;  // six records in device memory: the previous depth's queue (three buffers) and NEE records (two) by depth % 6
-  NeeQueue nee2{};
-  ShadowQueue fallback{};
-  int bvh_builder = 3;            // 0 binned SAH on the host, 1 LBVH on the GPU, 2 PLOC on the GPU, 3 binned SAH on the GPU (default since round 4: the host builder's trees in a fifth of its time; a mesh it cannot take falls back to 0) (lumc_set_bvh_builder)
-  double bvh_build_seconds = 0.0; // bottom-level builds of the last lumc_scene_upload
-  uint32_t bvh_meshes_by_builder[2] = {0, 0};  // meshes of the last upload built by SAH / by LBVH
-  uint32_t lds_nodes = 0;         // nodes of the tree top every ray-kernel workgroup stages in LDS
-  uint32_t trace_blocks = 256;    // persistent grid of the ray kernels
-  // LUTs owned by the context when generated here
-  uint16_t* d_luts[4] = {nullptr, nullptr, nullptr, nullptr};
-  // pixels and accumulators
-  uint32_t* d_pixels = nullptr;
-  uint32_t num_pixels = 0;
-  uint64_t pixels_hash = 0;       // of the pixel list in its order (lumc_set_pixels): the tile gather checks that the set IS the share of the deal it assumes
-  float* d_first_moment = nullptr;
-  float* d_second_moment = nullptr;
-  // work buffers (sized for capacity paths)
-  uint32_t capacity = 0;
-  void* work_block = nullptr;
-  PathQueue queue[3]{};           // [2]: only with the fused resolve (ensure_fused)
-  NeeQueue nee{};
-  ShadowQueue shadow{};
-  uint32_t particle_lds_nodes = 0;
-  VolumeQueue volume{};           // fog (dev_volume.h); allocated with the work block when the scene's fog is active
-  CloudQueue cloud{};             // the cloud marches of a depth (kernels.h k_clouds_*); allocated with the work block when clouds are marched
-  uint32_t work_shadow_kinds = 0; // visibility-ray kinds per path the work block was sized for (4, or 17 with fog)
-  float4* d_results = nullptr;
-  float* d_frame_output = nullptr;  // display-referred planes of the output chain [3 * W * H]
-  uint32_t frame_output_pixels = 0;
-  uint16_t* d_bluenoise_1d = nullptr;
-  uint32_t* d_argb8 = nullptr;
-  uint32_t argb8_pixels = 0;
-  // adaptive sampling (dev_adaptive.h)
-  struct Adaptive {
-    bool active = false;
-    LumAdaptiveParams params{};
-    uint32_t blocks_x = 0, blocks_y = 0, num_blocks = 0;
-    uint32_t stage_id = 0;
-    uint32_t executions[kAdaptiveStages + 1] = {0, 0, 0, 0, 0};
-    uint32_t* d_stage_counts = nullptr;
-    uint32_t* d_block_tasks = nullptr;
-    uint32_t* d_block_task_end = nullptr;
-    float* d_block_variance = nullptr;
-    float* d_partial = nullptr;   // chunk sums, then the total in the last element
-    void* d_scan_temp = nullptr;
-    size_t scan_temp_bytes = 0;
-    std::vector<uint32_t> task_end;  // host copy of d_block_task_end: passes are cut at block boundaries
-    float variance_total = 0.0f;
-    uint8_t* d_block_mask = nullptr; // image-tile partition over GPUs: blocks this context renders (nullptr = all)
-    bool build_pending = false;      // partitioned: a stage is due and waits for the block variances of all ranks
-  } adaptive;
-  uint32_t* d_cloud_noise[3] = {nullptr, nullptr, nullptr};  // the clouds' shape / detail / weather textures generated here (kept across scene uploads)
-  bool cloud_noise_static = false;  // shape and detail do not depend on the seed
-  uint32_t cloud_noise_seed = 0;
-  bool cloud_noise_weather_valid = false;
-  float4* d_sky_hdri = nullptr;     // baked sky (lumc_sky_hdri_build): dim x dim equirectangular, rgb + 0
-  uint32_t sky_hdri_dim = 0;
-  std::vector<float*> bloom_mips;  // mip chain of lumc_post_bloom, level i of (width >> (i + 1)) x (height >> (i + 1))
-  uint32_t bloom_width = 0, bloom_height = 0;
-  uint32_t* d_undersampling_pixels = nullptr;  // pixel list of the current undersampling iteration (lumc_render_undersampled)
-  uint32_t undersampling_capacity = 0;
-  std::vector<uint32_t> sky_hdri_key;  // what the bake was made from (sky parameters, origin, dim, samples): an unchanged key reuses it
-  float* d_frame_result = nullptr;  // mean radiance planes of lumc_generate_result [3 * W * H]
-  uint32_t frame_result_pixels = 0;
-  // denoiser (dev_denoise.h): the guide planes (9 while they are summed, then albedo[3] normal[3] depth), the filter's records (A twice: ping-pong, B once)
-  float* d_guides = nullptr;
-  uint32_t guide_pixels = 0;
-  bool guides_valid = false;
-  void* d_denoise_rec[3] = {nullptr, nullptr, nullptr};
-  uint32_t denoise_pixels = 0;
-  int denoise_lds = 1;              // a-trous steps 1 and 2 stage their tile in LDS (lumc_set_denoise_form; LUM_DENOISE_LDS=0|1)
-  // ray ordering (N1): keys + permutation, double-buffered for hipcub's radix sort; sized for the visibility items (4 per path)
-  bool sync_debug = false;
-  int sort_mode = 0;              // 0 queue order, 1 closest-hit rays of depth >= 1 traced through a sorted permutation, 2 visibility rays too, 3 the path queue physically reordered (lumc_set_ray_sorting, LUM_SORT)
-  PathQueue sort_queue{};         // mode 3: the four state planes the reorder pass writes; swapped with the queue's own afterwards
-  void* sort_planes[4] = {nullptr, nullptr, nullptr, nullptr};  // what was allocated for them (after swaps sort_queue may point into the work block)
-  uint32_t sort_queue_capacity = 0;
-  int sort_key = 0;               // 0 position-major (Morton cell | direction octant), 1 direction-major
-  uint32_t* d_sort_keys[2] = {nullptr, nullptr};
-  uint32_t* d_sort_vals[2] = {nullptr, nullptr};
-  void* d_sort_temp = nullptr;
-  size_t sort_temp_bytes = 0;
-  uint32_t sort_capacity = 0;
-  float world_lo[3] = {0, 0, 0}, world_hi[3] = {1, 1, 1};  // bounds of the top-level BVH
-  // image-tile multi-GPU (lumc_comm_*, lumc_frame_assemble*): this rank's communicator and its [4][frame pixels] assembly buffer
-  ncclComm_t comm = nullptr;
-  int comm_rank = 0, comm_world = 1;
-  float* d_frame = nullptr;
-  uint32_t frame_capacity = 0;
-  // tile gather (lumc_frame_gather*): this rank's padded [4][gather_stride] send buffer; on the root the [world][4][gather_stride] receive buffer and every
-  // rank's pixel list [world][gather_stride] (0xFFFFFFFF = padding), keyed by (width, height, world)
-  float* d_gather_send = nullptr;
-  float* d_gather_recv = nullptr;
-  uint32_t* d_gather_pixels = nullptr;
-  uint32_t gather_stride = 0, gather_key[3] = {0, 0, 0};
-  size_t gather_recv_floats = 0;
-  bool use_frame = false;         // the result / output entry points read the assembled frame instead of this context's own accumulators
-  uint32_t* d_ctrl = nullptr;     // kCtlStride control words per depth (+1 row), zeroed per pass; last row: cursor of lumc_trace_closest
-  uint64_t* d_counters = nullptr;
-  // profiling
-  bool profiling = false;
-  struct Stamp { hipEvent_t a, b; int kernel; };
-  std::vector<Stamp> stamps;
-  double kernel_ms[LUMC_KERNEL_COUNT] = {};
-  uint32_t kernel_launches[LUMC_KERNEL_COUNT] = {};
-};
+static_assert(kLaunchBlock == (uint32_t) kBlock, "grid_for (context.h) counts kernels.h's workgroups");
 
 namespace {
-
-#define HIP_TRY(ctx, expr)                                                                                          \
-  do {                                                                                                              \
-    const hipError_t e__ = (expr);                                                                                  \
-    if (e__ != hipSuccess) {                                                                                        \
-      (ctx)->error = std::string(#expr) + " failed: " + hipGetErrorString(e__);                                     \
-      return 1;                                                                                                     \
-    }                                                                                                               \
-  } while (0)
 
 // ---- the process's bottom-level trees by what they were built from: the mesh's triangles (two 64-bit hashes of the vertex words, chunk by chunk so that the
 // value does not depend on the number of threads), the builder asked for and every LUM_* variable of the environment (the builders' knobs) ----
@@ -285,9 +132,8 @@ void free_work(LumContext* ctx) {
   ctx->capacity = 0;
   ctx->work_shadow_kinds = 0;
   ctx->cloud = CloudQueue{};
-  // the reorder pass's planes (ray-sorting mode 3) trade places with the queues' own: they go with them
-  for (int k = 0; k < 4; k++) { if (ctx->sort_planes[k]) (void) hipFree(ctx->sort_planes[k]); ctx->sort_planes[k] = nullptr; }
-  ctx->sort_queue = PathQueue{}; ctx->sort_queue_capacity = 0;
+  // the reorder pass's planes (ray-sorting mode 3) trade places with the queues' own: they go with them (and with them the sort's keys, sized by the pass too)
+  free_sort(ctx);
   if (ctx->d_sobol) (void) hipFree(ctx->d_sobol);
   ctx->d_sobol = nullptr; ctx->sobol_entries = 0;
 }
@@ -403,11 +249,6 @@ int ensure_fused(LumContext* ctx, hipStream_t stream) {
 
 constexpr uint32_t kCtrlRows = 68;  // depths 0..63, one row past the last depth, spare, lumc_trace_closest
 
-inline uint32_t grid_for(uint32_t n) {
-  const uint32_t blocks = (n + kBlock - 1) / kBlock;
-  return blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks);  // 256 CUs x 8 resident blocks, grid-stride beyond that
-}
-
 // k_shade: its workgroups are grid-stride loops of equal length, three of them resident per CU (3 waves per SIMD). With the common cap of 2048 workgroups that
 // was 2.67 rounds of the 768 resident places, paid as 3; the grid is now a whole number of rounds, and eight of them: the shorter a workgroup, the shorter the
 // kernel's tail (hall, k_shade per 3 steps: 2048 workgroups 380 ms | 1 round 399 | 2: 383 | 3: 376 | 4: 372 | 6: 369 | 8: 368 | 12: 366 | 24: 371; the Example-class
@@ -424,36 +265,6 @@ inline uint32_t shade_grid(const LumContext* ctx, uint32_t n) {
   return blocks < 1 ? 1 : std::min(blocks, cap);
 }
 
-// Persistent ray kernels: one workgroup per CU (kTraceBlock threads, its own LDS copy of the tree top); waves pull work from a cursor.
-inline uint32_t grid_persistent(const LumContext* ctx, uint32_t n) {
-  const uint32_t tb = ctx->wf->trace_block;
-  const uint32_t blocks = (n + tb - 1) / tb;
-  return blocks < 1 ? 1 : (blocks > ctx->trace_blocks ? ctx->trace_blocks : blocks);
-}
-
-struct Launch {
-  LumContext* ctx;
-  hipStream_t stream;
-  int kernel;
-  size_t idx = (size_t) -1;
-  Launch(LumContext* c, hipStream_t s, int k) : ctx(c), stream(s), kernel(k) {
-    if (!ctx->profiling) return;
-    LumContext::Stamp st;
-    st.kernel = k;
-    if (hipEventCreate(&st.a) != hipSuccess || hipEventCreate(&st.b) != hipSuccess) return;
-    (void) hipEventRecord(st.a, stream);
-    ctx->stamps.push_back(st);
-    idx = ctx->stamps.size() - 1;
-  }
-  ~Launch() {
-    if (idx != (size_t) -1) (void) hipEventRecord(ctx->stamps[idx].b, stream);
-    if (ctx->sync_debug) {  // LUM_SYNC_DEBUG=1: name the launch group a device fault belongs to
-      const hipError_t e = hipStreamSynchronize(stream);
-      std::fprintf(stderr, "[lum] launch group %d: %s\n", kernel, hipGetErrorString(e));
-    }
-  }
-};
-
 int resolve_stamps(LumContext* ctx) {
   for (auto& st : ctx->stamps) {
     float ms = 0.0f;
@@ -468,96 +279,6 @@ int resolve_stamps(LumContext* ctx) {
   return 0;
 }
 
-// ---- ray ordering (north star: "ray-sorted wavefront"; the reference sorts its tasks by hit type every depth, cuda/kernels.cuh:391-484) ----
-// Key = Morton code of the ray origin's cell in a 64^3 grid over the scene bounds (18 bits) combined with the direction's octant (3 bits).
-// Flavour-neutral: the order in which a queue is traced never changes a result (every path owns its slots), it only decides which rays
-// share a wave, a CU's L1 and an XCD's L2.
-struct SortGrid { float lo[3], scale[3]; uint32_t direction_major; };
-
-__device__ __forceinline__ uint32_t spread6(uint32_t v) {  // 6 bits -> every third bit
-  v &= 0x3Fu;
-  v = (v | (v << 8)) & 0x300Fu;
-  v = (v | (v << 4)) & 0x30C3u;
-  v = (v | (v << 2)) & 0x9249u;
-  return v;
-}
-
-__global__ __launch_bounds__(256) void k_ray_sort_keys(const float4* __restrict__ origin, const float4* __restrict__ dir, const uint32_t* __restrict__ count, uint32_t capacity,
-                                                       SortGrid g, uint32_t* __restrict__ keys, uint32_t* __restrict__ vals) {
-  const uint32_t n = min(*count, capacity);
-  for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < capacity; i += gridDim.x * 256u) {
-    uint32_t key = 0x200000u;  // beyond the live items: above every live key (21 bits), so they sort to the end whether or not the sort is stable
-    if (i < n) {
-      const float4 o = origin[i], d = dir[i];
-      const uint32_t cx = (uint32_t) fminf(fmaxf((o.x - g.lo[0]) * g.scale[0], 0.0f), 63.0f), cy = (uint32_t) fminf(fmaxf((o.y - g.lo[1]) * g.scale[1], 0.0f), 63.0f),
-                     cz = (uint32_t) fminf(fmaxf((o.z - g.lo[2]) * g.scale[2], 0.0f), 63.0f);
-      const uint32_t morton = spread6(cx) | (spread6(cy) << 1) | (spread6(cz) << 2);
-      const uint32_t octant = (d.x < 0.0f ? 1u : 0u) | (d.y < 0.0f ? 2u : 0u) | (d.z < 0.0f ? 4u : 0u);
-      key = g.direction_major ? ((octant << 18) | morton) : ((morton << 3) | octant);
-    }
-    keys[i] = key;
-    vals[i] = i;
-  }
-}
-
-int ensure_sort(LumContext* ctx, uint32_t items) {
-  if (items <= ctx->sort_capacity) return 0;
-  for (int k = 0; k < 2; k++) {
-    if (ctx->d_sort_keys[k]) (void) hipFree(ctx->d_sort_keys[k]);
-    if (ctx->d_sort_vals[k]) (void) hipFree(ctx->d_sort_vals[k]);
-    ctx->d_sort_keys[k] = ctx->d_sort_vals[k] = nullptr;
-  }
-  if (ctx->d_sort_temp) (void) hipFree(ctx->d_sort_temp);
-  ctx->d_sort_temp = nullptr; ctx->sort_capacity = 0;
-  for (int k = 0; k < 2; k++) {
-    HIP_TRY(ctx, hipMalloc((void**) &ctx->d_sort_keys[k], sizeof(uint32_t) * (size_t) items));
-    HIP_TRY(ctx, hipMalloc((void**) &ctx->d_sort_vals[k], sizeof(uint32_t) * (size_t) items));
-  }
-  hipcub::DoubleBuffer<uint32_t> keys(ctx->d_sort_keys[0], ctx->d_sort_keys[1]), vals(ctx->d_sort_vals[0], ctx->d_sort_vals[1]);
-  HIP_TRY(ctx, hipcub::DeviceRadixSort::SortPairs(nullptr, ctx->sort_temp_bytes, keys, vals, (int) items, 0, 22, (hipStream_t) 0));
-  HIP_TRY(ctx, hipMalloc(&ctx->d_sort_temp, std::max<size_t>(ctx->sort_temp_bytes, 16)));
-  ctx->sort_capacity = items;
-  return 0;
-}
-
-// Mode 3: the path state of the live paths gathered through the sorted permutation into a second set of planes, written in order - the pass every
-// later kernel of the depth then reads coherently (trace, shade, and through the order of the appends the visibility rays and the next depth).
-__global__ __launch_bounds__(256) void k_permute_queue(PathQueue src, PathQueue dst, const uint32_t* __restrict__ order, const uint32_t* __restrict__ count, uint32_t capacity) {
-  const uint32_t n = min(*count, capacity);
-  for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) {
-    const uint32_t j = order[i];
-    const float4 o = src.origin_t[j], d = src.dir_slot[j];
-    const uint4 a = src.aux[j], h = src.hit_id[j];
-    dst.origin_t[i] = o; dst.dir_slot[i] = d; dst.aux[i] = a; dst.hit_id[i] = h;
-  }
-}
-
-int ensure_sort_queue(LumContext* ctx, uint32_t items) {
-  if (items == ctx->sort_queue_capacity) return 0;
-  for (int k = 0; k < 4; k++) { if (ctx->sort_planes[k]) (void) hipFree(ctx->sort_planes[k]); ctx->sort_planes[k] = nullptr; }
-  ctx->sort_queue = PathQueue{}; ctx->sort_queue_capacity = 0;
-  for (int k = 0; k < 4; k++) HIP_TRY(ctx, hipMalloc(&ctx->sort_planes[k], 16 * (size_t) items));
-  ctx->sort_queue.origin_t = (float4*) ctx->sort_planes[0]; ctx->sort_queue.dir_slot = (float4*) ctx->sort_planes[1];
-  ctx->sort_queue.aux = (uint4*) ctx->sort_planes[2]; ctx->sort_queue.hit_id = (uint4*) ctx->sort_planes[3];
-  ctx->sort_queue_capacity = items;
-  return 0;
-}
-
-// Sorted order of the first *count items of (origin, dir); returns the permutation (device pointer) or nullptr on failure.
-const uint32_t* sort_rays(LumContext* ctx, hipStream_t stream, const float4* origin, const float4* dir, const uint32_t* count, uint32_t capacity) {
-  if (ensure_sort(ctx, capacity)) return nullptr;
-  SortGrid g;
-  for (int k = 0; k < 3; k++) { g.lo[k] = ctx->world_lo[k]; const float e = ctx->world_hi[k] - ctx->world_lo[k]; g.scale[k] = e > 0.0f ? 64.0f / e : 0.0f; }
-  g.direction_major = ctx->sort_key == 1 ? 1u : 0u;
-  Launch l(ctx, stream, LUMC_KERNEL_SORT);
-  const uint32_t blocks = std::min<uint32_t>((capacity + 255u) / 256u, 4096u);
-  hipLaunchKernelGGL(k_ray_sort_keys, dim3(blocks ? blocks : 1), dim3(256), 0, stream, origin, dir, count, capacity, g, ctx->d_sort_keys[0], ctx->d_sort_vals[0]);
-  hipcub::DoubleBuffer<uint32_t> keys(ctx->d_sort_keys[0], ctx->d_sort_keys[1]), vals(ctx->d_sort_vals[0], ctx->d_sort_vals[1]);
-  size_t bytes = ctx->sort_temp_bytes;
-  if (hipcub::DeviceRadixSort::SortPairs(ctx->d_sort_temp, bytes, keys, vals, (int) capacity, 0, 22, stream) != hipSuccess) return nullptr;
-  return vals.Current();
-}
-
 }  // namespace
 
 extern "C" {
@@ -568,9 +289,9 @@ int lumc_context_create(int device_ordinal, LumContext** out) {
   LumContext* ctx = new LumContext();
   ctx->device = device_ordinal;
   if (const char* b = getenv("LUM_BVH_BUILDER")) ctx->bvh_builder = (std::strcmp(b, "lbvh") == 0) ? 1 : (std::strcmp(b, "ploc") == 0) ? 2 : (std::strcmp(b, "sah") == 0 || std::strcmp(b, "host") == 0) ? 0 : 3;
-  if (const char* e = getenv("LUM_SORT")) ctx->sort_mode = atoi(e);
+  if (const char* e = getenv("LUM_SORT")) ctx->sort.mode = atoi(e);
   if (const char* e = getenv("LUM_SYNC_DEBUG")) ctx->sync_debug = atoi(e) != 0;
-  if (const char* e = getenv("LUM_SORT_KEY")) ctx->sort_key = atoi(e);
+  if (const char* e = getenv("LUM_SORT_KEY")) ctx->sort.key = atoi(e);
   if (const char* e = getenv("LUM_AMBIENT_REUSE")) ctx->ambient_reuse = atoi(e) != 0 ? 1 : 0;
   if (const char* e = getenv("LUM_FUSED_RESOLVE")) ctx->fused_resolve = atoi(e) != 0 ? 1 : 0;
   if (const char* e = getenv("LUM_SHADE_GRID")) ctx->shade_grid_rounds = (uint32_t) atoi(e);
@@ -602,11 +323,8 @@ void lumc_context_destroy(LumContext* ctx) {
   if (ctx->d_pixels) (void) hipFree(ctx->d_pixels);
   if (ctx->d_first_moment) (void) hipFree(ctx->d_first_moment);
   if (ctx->d_second_moment) (void) hipFree(ctx->d_second_moment);
-  if (ctx->comm) { (void) ncclCommDestroy(ctx->comm); ctx->comm = nullptr; }
-  if (ctx->d_frame) (void) hipFree(ctx->d_frame);
+  free_exchange(ctx);
   if (ctx->d_ctrl) (void) hipFree(ctx->d_ctrl);
-  for (int k = 0; k < 2; k++) { if (ctx->d_sort_keys[k]) (void) hipFree(ctx->d_sort_keys[k]); if (ctx->d_sort_vals[k]) (void) hipFree(ctx->d_sort_vals[k]); }
-  if (ctx->d_sort_temp) (void) hipFree(ctx->d_sort_temp);
   if (ctx->d_frame_output) (void) hipFree(ctx->d_frame_output);
   if (ctx->d_bluenoise_1d) (void) hipFree(ctx->d_bluenoise_1d);
   if (ctx->d_argb8) (void) hipFree(ctx->d_argb8);
@@ -614,9 +332,6 @@ void lumc_context_destroy(LumContext* ctx) {
   if (ctx->d_frame_result) (void) hipFree(ctx->d_frame_result);
   if (ctx->d_guides) (void) hipFree(ctx->d_guides);
   for (void* r : ctx->d_denoise_rec) if (r) (void) hipFree(r);
-  if (ctx->d_gather_send) (void) hipFree(ctx->d_gather_send);
-  if (ctx->d_gather_recv) (void) hipFree(ctx->d_gather_recv);
-  if (ctx->d_gather_pixels) (void) hipFree(ctx->d_gather_pixels);
   if (ctx->d_sky_hdri) (void) hipFree(ctx->d_sky_hdri);
   for (uint32_t*& t : ctx->d_cloud_noise) { if (t) (void) hipFree(t); t = nullptr; }
   if (ctx->d_undersampling_pixels) (void) hipFree(ctx->d_undersampling_pixels);
@@ -844,7 +559,7 @@ static int update_scene_tree(LumContext* ctx, const LumDeviceSceneView* v, bool 
   if (upload(ctx, LumContext::kGrpInst, tree.tlas_leaves.data(), tree.tlas_leaves.size(), &sc.tlas_leaves)) return 1;
   sc.tlas_num_nodes = tree.tlas_num_nodes;
   sc.tlas_num_leaves = (uint32_t) (tree.tlas_leaves.size() / 4);  // records that exist (one of padding included): what a workgroup may stage in LDS
-  std::memcpy(ctx->world_lo, tree.world.lo, sizeof(ctx->world_lo)); std::memcpy(ctx->world_hi, tree.world.hi, sizeof(ctx->world_hi));
+  std::memcpy(ctx->sort.world_lo, tree.world.lo, sizeof(ctx->sort.world_lo)); std::memcpy(ctx->sort.world_hi, tree.world.hi, sizeof(ctx->sort.world_hi));
   ctx->bvh_stats[0] = tree.nodes.size() - tree.tlas_num_nodes;
   ctx->bvh_stats[2] = tree.tlas_num_nodes;
   *num_nodes = tree.nodes.size();
@@ -1246,7 +961,7 @@ int lumc_sky_hdri_download(LumContext* ctx, float* rgba, uint32_t* dim) {
 }
 
 // FNV-1a over a pixel list (null: 0, 1, 2 ... n - 1): the identity of a context's pixel set and of its ORDER
-static uint64_t pixel_list_hash(const uint32_t* pixels, uint32_t n) {
+uint64_t pixel_list_hash(const uint32_t* pixels, uint32_t n) {
   uint64_t h = 1469598103934665603ull;
   for (uint32_t i = 0; i < n; i++) { h ^= pixels ? pixels[i] : i; h *= 1099511628211ull; }
   return h;
@@ -1297,7 +1012,227 @@ static bool ambient_reuse_active(const LumContext* ctx) {
   // cheap rays they save (hall: visibility kernel -29 ms, resolve +61 ms per step), so it is not its default.
   const bool wanted = ctx->ambient_reuse < 0 ? (ctx->wf == wavefront_kernels_fast()) : ctx->ambient_reuse != 0;
   return wanted && ctx->has_scene && sc.sky_mode != kSkyDefault && !sc.fog_active && !sc.ocean_active && !sc.particles_active && !sc.cloud_active &&
-         !sc.sky_aerial_perspective && ctx->sort_mode == 0 && sc.shading_mode == 0u;
+         !sc.sky_aerial_perspective && ctx->sort.mode == 0 && sc.shading_mode == 0u;
+}
+
+// The Sobol / Owen pairs of this pass's sample ids for every dimension k_shade can ask for (dev_sampler.h LUM_SOBOL_TABLE): 1.3 MB at 32 ids and 8 bounces
+static void prepare_sobol_table(LumContext* ctx, hipStream_t stream, DeviceScene& sc, uint32_t first_sample, uint32_t sample_count) {
+  sc.sobol_table = nullptr;
+  if (!(ctx->sobol_table && sample_count > 0 && sample_count <= kSobolTableMaxSamples && sc.shading_mode == 0u)) return;
+  const uint32_t stride = (sample_count + 15u) & ~15u, dims = (sc.max_ray_depth + 1u) * kRndTargetCount;
+  const size_t entries = (size_t) stride * dims;
+  if (ctx->sobol_entries < entries) {
+    if (ctx->d_sobol) (void) hipFree(ctx->d_sobol);
+    ctx->d_sobol = nullptr; ctx->sobol_entries = 0;
+    if (hipMalloc((void**) &ctx->d_sobol, entries * sizeof(uint2)) == hipSuccess) ctx->sobol_entries = entries;
+    else (void) hipGetLastError();  // no room: the sampler hashes
+  }
+  if (ctx->d_sobol) {
+    ctx->wf->sobol_table(stream, ctx->d_sobol, first_sample, sample_count, stride, dims);
+    sc.sobol_table = ctx->d_sobol; sc.sobol_first = first_sample; sc.sobol_count = sample_count; sc.sobol_stride = stride;
+  }
+}
+
+static size_t ray_kernel_lds(const LumContext* ctx) { return (size_t) ctx->lds_nodes * kNodeBytes + LUM_LDS_STACK_BYTES; }
+static bool render_volumes(const DeviceScene& sc) { return sc.fog_active || sc.ocean_active; }  // device_manager.c:478
+
+// Debug shading modes: one closest-hit pass and a colour per path (device_renderer.c:136-181)
+static void debug_pass(LumContext* ctx, hipStream_t stream, const DeviceScene& sc, uint32_t N) {
+  const WavefrontKernels& wf = *ctx->wf;
+  {
+    Launch l(ctx, stream, LUMC_KERNEL_TRACE);
+    wf.trace(grid_persistent(ctx, N), ray_kernel_lds(ctx), stream, sc, ctx->queue[0], nullptr, ctx->d_ctrl, ctx->d_counters, ctx->lds_nodes);
+  }
+  if (sc.particles_active) trace_particles(ctx, stream, ctx->queue[0], ctx->d_ctrl, N);
+  if (sc.ocean_active) {
+    Launch l(ctx, stream, LUMC_KERNEL_TRACE);
+    wf.trace_ocean(grid_for(N), stream, sc, ctx->queue[0], (const uint32_t*) ctx->d_ctrl);
+  }
+  if (render_volumes(sc)) {  // the debug queue keeps volume_process_events (device_renderer.c:145-147)
+    Launch l(ctx, stream, LUMC_KERNEL_VOLUME);
+    wf.volume_events(grid_for(N), stream, sc, ctx->queue[0], ctx->volume, ctx->d_results, ctx->d_ctrl, 0u);
+  }
+  if (sc.sky_aerial_perspective && sc.sky_mode != kSkyConstantColor) {  // the debug queue keeps the in-scattering events (device_renderer.c:150-154)
+    Launch l(ctx, stream, LUMC_KERNEL_SKY);
+    wf.sky_inscattering(grid_for(N), stream, sc, ctx->queue[0], ctx->d_results, (const uint32_t*) ctx->d_ctrl, 0u);
+  }
+  Launch l(ctx, stream, LUMC_KERNEL_SHADE);
+  wf.shade_debug(grid_for(N), stream, sc, ctx->queue[0], ctx->d_results, (const uint32_t*) ctx->d_ctrl);
+}
+
+// How the vertices of a depth get their sums (the visibility answers applied to the NEE records):
+//   kResolvePlain: k_resolve after the depth's visibility pass.
+//   kResolveReuse - ambient-visibility reuse (lumc_set_ambient_reuse; AmbientReuse in kernels.h): the vertices of depth d leave their ambient sample to the
+//     closest-hit pass of depth d + 1, which is followed by a second, small visibility pass (what the closest hit could not decide) and only then by the resolve
+//     of depth d - still before k_shade of depth d + 1 touches the result slots, so the order of the sums is the usual one.
+//   kResolveFused - fused resolve (FusedResolve, kernels.h): with the fast flavour's reuse the resolve of depth d is done by k_shade of depth d + 1 for the
+//     vertices an entry continues, by k_resolve_ended for the others; the queues rotate through three buffers and the NEE records through two, so that depth d
+//     is intact while depth d + 1 is shaded. The exact flavour's (provable) reuse keeps its own kernel: its sums must land in the reference's order.
+enum ResolveScheme { kResolvePlain, kResolveReuse, kResolveFused };
+
+// What one depth reads and writes. Only depth_buffers knows how the queues and record sets rotate.
+struct DepthBuffers {
+  PathQueue& cur;        // the depth's paths
+  PathQueue& next;       // where its shading kernels append the next depth's
+  PathQueue& prev;       // the depth before (kResolveReuse, kResolveFused: not yet resolved when this depth is traced)
+  NeeQueue& nee;         // the depth's NEE records
+  NeeQueue& nee_before;  // the depth before's (kResolveFused)
+  uint32_t* ctrl;        // the depth's control words; the depth before's are ctrl - kCtlStride
+  const FusedResolve* fused_records;  // kResolveFused: the device record k_shade reads the depth before through
+  uint32_t* ended;       // kResolveFused: the list of the depth's vertices that no entry continues
+  uint32_t depth, depth_const;
+  bool last;             // depth == max_ray_depth
+};
+
+static DepthBuffers depth_buffers(LumContext* ctx, ResolveScheme scheme, uint32_t depth, uint32_t max_depth) {
+  // (cur == depth % 3 and the record set == depth & 1 below: what the six device records assume)
+  const bool fused = scheme == kResolveFused;
+  const int cur = fused ? (int) (depth % 3u) : (int) (depth & 1u);
+  const int next_q = fused ? (cur + 1) % 3 : (cur ^ 1), prev_q = fused ? (cur + 2) % 3 : (cur ^ 1);
+  const bool second_set = fused && (depth & 1u);
+  // the sampler's depth constant is not advanced before the last pass (device_renderer.c:126-130)
+  const uint32_t depth_const = (depth == max_depth && depth > 0) ? depth - 1 : depth;
+  return DepthBuffers{ctx->queue[cur], ctx->queue[next_q], ctx->queue[prev_q], second_set ? ctx->nee2 : ctx->nee, second_set ? ctx->nee : ctx->nee2,
+                      ctx->d_ctrl + kCtlStride * depth, fused ? ctx->d_fused + depth % 6u : nullptr, fused ? ctx->d_ended[depth & 1u] : nullptr, depth, depth_const,
+                      depth == max_depth};
+}
+
+// The closest hits of a depth; with kResolveReuse they also answer the ambient samples of the depth before, which is resolved here.
+static int closest_hits(LumContext* ctx, hipStream_t stream, const DeviceScene& sc, ResolveScheme scheme, const DepthBuffers& d, uint32_t N) {
+  const WavefrontKernels& wf = *ctx->wf;
+  // camera rays leave k_generate in pixel order, which is as coherent as rays get; later depths are sorted on request
+  const uint32_t* order = nullptr;
+  if (ctx->sort.mode >= 1 && d.depth >= 1 && sort_closest_rays(ctx, stream, d.cur, d.ctrl, N, &order)) return 1;
+  {
+    Launch l(ctx, stream, LUMC_KERNEL_TRACE);
+    wf.trace(grid_persistent(ctx, N), ray_kernel_lds(ctx), stream, sc, d.cur, order, d.ctrl, ctx->d_counters, ctx->lds_nodes);
+  }
+  if (scheme == kResolveReuse && d.depth > 0) {  // the previous depth's resolve: ambient samples answered by the pass above; what it cannot answer is traced (the control words of the fog's visibility pass: no fog here) and resolved after
+    uint32_t* prev = d.ctrl - kCtlStride;
+    {
+      Launch l(ctx, stream, LUMC_KERNEL_RESOLVE);
+      wf.resolve_reuse(grid_for(N), stream, sc, d.prev, d.cur, d.nee, ctx->shadow, ctx->d_results, prev, ctx->d_counters);
+    }
+    {
+      Launch l(ctx, stream, LUMC_KERNEL_SHADOW);
+      wf.shadow_rays(ctx->trace_blocks, ray_kernel_lds(ctx), stream, sc, ctx->shadow, nullptr, prev + kCtlVolumeShift, ctx->d_counters, ctx->lds_nodes);
+    }
+    Launch l(ctx, stream, LUMC_KERNEL_RESOLVE);
+    wf.resolve_listed(std::min<uint32_t>(grid_for(N), 1024u), stream, sc, d.prev, d.nee, ctx->shadow, ctx->d_results, (const uint32_t*) prev);
+  }
+  return 0;
+}
+
+// What lies between the surfaces: particles, ocean, volumes, clouds, aerial perspective.
+static void media_passes(LumContext* ctx, hipStream_t stream, const DeviceScene& sc, const DepthBuffers& d, uint32_t N) {
+  const WavefrontKernels& wf = *ctx->wf;
+  if (sc.particles_active) trace_particles(ctx, stream, d.cur, d.ctrl, N);  // optix_kernel_raytrace.cu:171
+  if (sc.ocean_active) {  // optix_kernel_raytrace.cu:134-144, :172
+    Launch l(ctx, stream, LUMC_KERNEL_TRACE);
+    wf.trace_ocean(grid_for(N), stream, sc, d.cur, (const uint32_t*) d.ctrl);
+  }
+  if (render_volumes(sc)) {  // device_renderer.c:64-76: in-scattering with its own visibility pass, then the scattering events
+    {
+      Launch l(ctx, stream, LUMC_KERNEL_VOLUME);
+      wf.volume_inscatter(grid_for(N), stream, sc, d.cur, ctx->volume, ctx->shadow, d.ctrl, d.depth_const);
+    }
+    {
+      Launch l(ctx, stream, LUMC_KERNEL_SHADOW);
+      wf.shadow_rays(grid_persistent(ctx, N), ray_kernel_lds(ctx), stream, sc, ctx->shadow, nullptr, d.ctrl + kCtlVolumeShift, ctx->d_counters, ctx->lds_nodes);
+    }
+    Launch l(ctx, stream, LUMC_KERNEL_VOLUME);
+    wf.volume_resolve(grid_for(N), stream, sc, d.cur, ctx->volume, ctx->shadow, ctx->d_results, (const uint32_t*) d.ctrl);
+    wf.volume_events(grid_for(N), stream, sc, d.cur, ctx->volume, ctx->d_results, d.ctrl, d.depth_const);
+  }
+  if (sc.cloud_active && sc.sky_mode == kSkyDefault && sc.cloud_noise_shape) {  // device_manager.c:474, device_renderer.c:78-82
+    Launch l(ctx, stream, LUMC_KERNEL_SKY);
+#if LUM_CLOUD_PERSISTENT
+    wf.clouds_list(grid_for(N), stream, sc, d.cur, ctx->cloud, d.ctrl);
+    wf.clouds_march(ctx->trace_blocks * 4u, stream, sc, d.cur, ctx->cloud, d.ctrl, d.depth_const);  // persistent: 4 workgroups of 256 per CU
+#endif
+    wf.clouds(grid_for(N), stream, sc, d.cur, ctx->cloud, ctx->d_results, (const uint32_t*) d.ctrl, d.depth_const);
+  }
+  if (sc.sky_aerial_perspective && sc.sky_mode != kSkyConstantColor) {  // device_manager.c:475, device_renderer.c:84-88
+    Launch l(ctx, stream, LUMC_KERNEL_SKY);
+    wf.sky_inscattering(grid_for(N), stream, sc, d.cur, ctx->d_results, (const uint32_t*) d.ctrl, d.depth_const);
+  }
+}
+
+// k_shade; with kResolveFused it resolves the depth before, and what it could not is finished here.
+static void shade_depth(LumContext* ctx, hipStream_t stream, const DeviceScene& sc, ResolveScheme scheme, const DepthBuffers& d, uint32_t N) {
+  const WavefrontKernels& wf = *ctx->wf;
+  const bool fused = scheme == kResolveFused;
+  {
+    Launch l(ctx, stream, LUMC_KERNEL_SHADE);
+    wf.shade(shade_grid(ctx, N), stream, sc, d.cur, d.next, d.nee, ctx->shadow, ctx->d_results, d.ctrl, d.depth_const, ctx->d_counters,
+             (scheme != kResolvePlain && !d.last) ? 1u : 0u, d.fused_records,
+             fused ? ((d.depth > 0 ? 1u : 0u) | (!d.last ? 2u : 0u) | (ctx->fused_ended ? 4u : 0u)) : 0u);
+  }
+  if (fused && d.depth > 0) {  // the samples of depth - 1 their paths' closest hits could not decide: traced now, their vertices resolved (before this depth's visibility pass reuses the words)
+    {
+      Launch l(ctx, stream, LUMC_KERNEL_SHADOW);
+      wf.shadow_rays(ctx->trace_blocks, ray_kernel_lds(ctx), stream, sc, ctx->fallback, nullptr, d.ctrl + kCtlVolumeShift, ctx->d_counters, ctx->lds_nodes);
+    }
+    Launch l(ctx, stream, LUMC_KERNEL_RESOLVE);
+    wf.resolve_listed(std::min<uint32_t>(grid_for(N), 1024u), stream, sc, d.prev, d.nee_before, ctx->fallback, ctx->d_results, (const uint32_t*) d.ctrl);
+  }
+}
+
+// The shading of what k_shade leaves to others: particle hits, water-surface hits, paths that left into the procedural sky.
+static void feature_shading(LumContext* ctx, hipStream_t stream, const DeviceScene& sc, const DepthBuffers& d, uint32_t N) {
+  const WavefrontKernels& wf = *ctx->wf;
+  if (sc.particles_active) {  // device_renderer.c:99-103
+    Launch l(ctx, stream, LUMC_KERNEL_SHADE);
+    wf.particle_shade(grid_for(N), stream, sc, d.cur, d.next, d.nee, ctx->shadow, d.ctrl, d.depth_const);
+  }
+  if (sc.ocean_active) {  // device_renderer.c:104-108
+    Launch l(ctx, stream, LUMC_KERNEL_SHADE);
+    wf.ocean_shade(grid_for(N), stream, sc, d.cur, d.next, d.nee, ctx->shadow, d.ctrl, d.depth_const);
+  }
+  if (sc.sky_mode == kSkyDefault) {  // paths that left the scene into the procedural sky (listed by k_shade)
+    Launch l(ctx, stream, LUMC_KERNEL_SKY);
+    wf.sky(grid_for(N), stream, sc, d.cur, ctx->shadow, ctx->d_results, (const uint32_t*) d.ctrl, d.depth_const);
+  }
+}
+
+// Light query, visibility rays, and the depth's resolve where the scheme does it at this point.
+static int visibility_and_resolve(LumContext* ctx, hipStream_t stream, const DeviceScene& sc, ResolveScheme scheme, const DepthBuffers& d, uint32_t N) {
+  const WavefrontKernels& wf = *ctx->wf;
+  {
+    Launch l(ctx, stream, LUMC_KERNEL_LIGHT_QUERY);
+    // (one resident round of its workgroups - four per CU: the kernel's workgroups are dear to start (a 1 KB stack per lane in scratch); 2 rounds, the common cap:
+    //  Example-class 4.6 -> 4.0 ms per 3 steps, scan 3.9 -> 3.6, hall equal; 4 / 8 / 16 rounds on the hall: 30.2 / 32.8 / 44.5 ms against 29.9)
+    wf.light_query(std::min<uint32_t>(grid_for(N), ctx->trace_blocks * 4u), stream, sc, d.cur, d.nee, ctx->shadow, d.ctrl, d.depth_const, ctx->d_counters);
+  }
+  const uint32_t* shadow_order = nullptr;
+  if (ctx->sort.mode == 2) {
+    shadow_order = sort_rays(ctx, stream, ctx->shadow.origin_dist, ctx->shadow.dir_out, d.ctrl + kCtlShadowItems,
+                             (sc.ocean_active ? kSurfaceShadowKindsWater : 4u) * (ctx->shadow.capacity < N ? ctx->shadow.capacity : N));
+    if (!shadow_order) { ctx->error = "ray sorting failed"; return 1; }
+  }
+  {
+    Launch l(ctx, stream, LUMC_KERNEL_SHADOW);
+    wf.shadow_rays(grid_persistent(ctx, N), ray_kernel_lds(ctx), stream, sc, ctx->shadow, shadow_order, d.ctrl, ctx->d_counters, ctx->lds_nodes);
+  }
+  if (d.last || scheme == kResolvePlain) {
+    Launch l(ctx, stream, LUMC_KERNEL_RESOLVE);
+    wf.resolve(grid_for(N), stream, sc, d.cur, d.nee, ctx->shadow, ctx->d_results, (const uint32_t*) d.ctrl);
+  }
+  else if (scheme == kResolveFused) {  // the vertices no entry of the next depth continues; the others are resolved by those entries, in k_shade - and so are these, as its last input (fused_flags & 4)
+    if (!ctx->fused_ended) {
+      Launch l(ctx, stream, LUMC_KERNEL_RESOLVE);
+      wf.resolve_ended(std::min<uint32_t>(grid_for(N), 4096u), stream, sc, d.cur, d.nee, ctx->shadow, ctx->d_results, (const uint32_t*) d.ctrl, d.ended);
+    }
+  }
+  // (kResolveReuse: the depth's resolve waits for the next depth's closest-hit pass, closest_hits)
+  return 0;
+}
+
+static void volume_bounce(LumContext* ctx, hipStream_t stream, const DeviceScene& sc, const DepthBuffers& d, uint32_t N) {
+  if (render_volumes(sc) && !d.last) {  // device_renderer.c:114-118
+    Launch l(ctx, stream, LUMC_KERNEL_VOLUME);
+    ctx->wf->volume_bounce(grid_for(N), stream, sc, d.cur, d.next, ctx->volume, d.ctrl, d.depth_const);
+  }
 }
 
 // The depth loop of one wavefront pass over the paths k_generate* left in queue[0] (at most N of them, counted on the device).
@@ -1305,192 +1240,24 @@ static bool ambient_reuse_active(const LumContext* ctx) {
 static int wavefront_depths(LumContext* ctx, hipStream_t stream, uint32_t N, uint32_t first_sample = 0, uint32_t sample_count = 0) {
   DeviceScene sc = ctx->scene;
   const uint32_t max_depth = sc.max_ray_depth;
-  sc.sobol_table = nullptr;
-  if (ctx->sobol_table && sample_count > 0 && sample_count <= kSobolTableMaxSamples && sc.shading_mode == 0u) {
-    // the Sobol / Owen pairs of this pass's sample ids for every dimension k_shade can ask for (dev_sampler.h LUM_SOBOL_TABLE): 1.3 MB at 32 ids and 8 bounces
-    const uint32_t stride = (sample_count + 15u) & ~15u, dims = (max_depth + 1u) * kRndTargetCount;
-    const size_t entries = (size_t) stride * dims;
-    if (ctx->sobol_entries < entries) {
-      if (ctx->d_sobol) (void) hipFree(ctx->d_sobol);
-      ctx->d_sobol = nullptr; ctx->sobol_entries = 0;
-      if (hipMalloc((void**) &ctx->d_sobol, entries * sizeof(uint2)) == hipSuccess) ctx->sobol_entries = entries;
-      else (void) hipGetLastError();  // no room: the sampler hashes
-    }
-    if (ctx->d_sobol) {
-      ctx->wf->sobol_table(stream, ctx->d_sobol, first_sample, sample_count, stride, dims);
-      sc.sobol_table = ctx->d_sobol; sc.sobol_first = first_sample; sc.sobol_count = sample_count; sc.sobol_stride = stride;
+  prepare_sobol_table(ctx, stream, sc, first_sample, sample_count);
+  if (sc.shading_mode != 0u) { debug_pass(ctx, stream, sc, N); return 0; }
+  ResolveScheme scheme = ambient_reuse_active(ctx) ? kResolveReuse : kResolvePlain;
+  if (scheme == kResolveReuse && ctx->wf->fused_resolve && ctx->fused_resolve != 0 && ctx->wf == wavefront_kernels_fast() && max_depth > 0) {
+    if (ensure_fused(ctx, stream) == 0) scheme = kResolveFused;
+    else {  // no room for its buffers (a third of the work buffers again): the separate resolve kernel does the same sums
+      (void) hipGetLastError();
+      ctx->error.clear();
     }
   }
-  const size_t lds_dyn = (size_t) ctx->lds_nodes * kNodeBytes + LUM_LDS_STACK_BYTES;
-  int cur = 0;
-  const WavefrontKernels& wf = *ctx->wf;
-  const bool render_volumes = sc.fog_active || sc.ocean_active;  // device_manager.c:478
-  if (sc.shading_mode != 0u) {  // debug shading modes: one closest-hit pass and a colour per path (device_renderer.c:136-181)
-    {
-      Launch l(ctx, stream, LUMC_KERNEL_TRACE);
-      wf.trace(grid_persistent(ctx, N), lds_dyn, stream, sc, ctx->queue[0], nullptr, ctx->d_ctrl, ctx->d_counters, ctx->lds_nodes);
-    }
-    if (sc.particles_active) trace_particles(ctx, stream, ctx->queue[0], ctx->d_ctrl, N);
-    if (sc.ocean_active) {
-      Launch l(ctx, stream, LUMC_KERNEL_TRACE);
-      wf.trace_ocean(grid_for(N), stream, sc, ctx->queue[0], (const uint32_t*) ctx->d_ctrl);
-    }
-    if (render_volumes) {  // the debug queue keeps volume_process_events (device_renderer.c:145-147)
-      Launch l(ctx, stream, LUMC_KERNEL_VOLUME);
-      wf.volume_events(grid_for(N), stream, sc, ctx->queue[0], ctx->volume, ctx->d_results, ctx->d_ctrl, 0u);
-    }
-    if (sc.sky_aerial_perspective && sc.sky_mode != kSkyConstantColor) {  // the debug queue keeps the in-scattering events (device_renderer.c:150-154)
-      Launch l(ctx, stream, LUMC_KERNEL_SKY);
-      wf.sky_inscattering(grid_for(N), stream, sc, ctx->queue[0], ctx->d_results, (const uint32_t*) ctx->d_ctrl, 0u);
-    }
-    Launch l(ctx, stream, LUMC_KERNEL_SHADE);
-    wf.shade_debug(grid_for(N), stream, sc, ctx->queue[0], ctx->d_results, (const uint32_t*) ctx->d_ctrl);
-    return 0;
-  }
-  // Ambient-visibility reuse (lumc_set_ambient_reuse; AmbientReuse in kernels.h): the vertices of depth d leave their ambient sample to the closest-hit
-  // pass of depth d + 1, which is followed by a second, small visibility pass (what the closest hit could not decide) and only then by the resolve of
-  // depth d - still before k_shade of depth d + 1 touches the result slots, so the order of the sums is the usual one.
-  const bool reuse = ambient_reuse_active(ctx);
-  // Fused resolve (FusedResolve, kernels.h): with the fast flavour's reuse the resolve of depth d is done by k_shade of depth d + 1 for the vertices an entry
-  // continues, by k_resolve_ended for the others; the queues rotate through three buffers and the NEE records through two, so that depth d is intact while
-  // depth d + 1 is shaded. The exact flavour's (provable) reuse keeps its own kernel: its sums must land in the reference's order.
-  bool fused = reuse && wf.fused_resolve && ctx->fused_resolve != 0 && ctx->wf == wavefront_kernels_fast() && max_depth > 0;
-  if (fused && ensure_fused(ctx, stream)) {  // no room for its buffers (a third of the work buffers again): the separate resolve kernel does the same sums
-    (void) hipGetLastError();
-    ctx->error.clear();
-    fused = false;
-  }
-  // (cur == depth % 3 and the record set == depth & 1 below: what the six device records assume)
-  bool resolve_pending = false;  // the previous depth's resolve waits for this depth's closest-hit pass
   for (uint32_t depth = 0; depth <= max_depth; depth++) {
-    // the sampler's depth constant is not advanced before the last pass (device_renderer.c:126-130)
-    const uint32_t depth_const = (depth == max_depth && depth > 0) ? depth - 1 : depth;
-    uint32_t* ctrl = ctx->d_ctrl + kCtlStride * depth;
-    // camera rays leave k_generate in pixel order, which is as coherent as rays get; later depths are sorted on request
-    const uint32_t* order = nullptr;
-    if (ctx->sort_mode >= 1 && depth >= 1) {
-      order = sort_rays(ctx, stream, ctx->queue[cur].origin_t, ctx->queue[cur].dir_slot, ctrl + kCtlPaths, N);
-      if (!order) { ctx->error = "ray sorting failed"; return 1; }
-      if (ctx->sort_mode == 3) {  // physical reorder: the planes change places, the permutation is spent
-        if (ensure_sort_queue(ctx, ctx->capacity)) return 1;
-        Launch l(ctx, stream, LUMC_KERNEL_SORT);
-        PathQueue& q = ctx->queue[cur];
-        hipLaunchKernelGGL(k_permute_queue, dim3(std::min<uint32_t>((N + 255u) / 256u, 65536u)), dim3(256), 0, stream, q, ctx->sort_queue, order, ctrl + kCtlPaths, N);
-        std::swap(q.origin_t, ctx->sort_queue.origin_t); std::swap(q.dir_slot, ctx->sort_queue.dir_slot);
-        std::swap(q.aux, ctx->sort_queue.aux); std::swap(q.hit_id, ctx->sort_queue.hit_id);
-        ctx->fused_records_stale = true;  // (the fused resolve does not run with ray sorting; a later pass without it must not read the old planes)
-        order = nullptr;
-      }
-    }
-    {
-      Launch l(ctx, stream, LUMC_KERNEL_TRACE);
-      wf.trace(grid_persistent(ctx, N), lds_dyn, stream, sc, ctx->queue[cur], order, ctrl, ctx->d_counters, ctx->lds_nodes);
-    }
-    const int next_q = fused ? (cur + 1) % 3 : (cur ^ 1), prev_q = fused ? (cur + 2) % 3 : (cur ^ 1);
-    NeeQueue& nee = (fused && (depth & 1u)) ? ctx->nee2 : ctx->nee;
-    NeeQueue& nee_before = (fused && (depth & 1u)) ? ctx->nee : ctx->nee2;
-    if (resolve_pending) {  // the previous depth's resolve: ambient samples answered by the pass above; what it cannot answer is traced (the control words of the fog's visibility pass: no fog here) and resolved after
-      uint32_t* prev = ctrl - kCtlStride;
-      {
-        Launch l(ctx, stream, LUMC_KERNEL_RESOLVE);
-        wf.resolve_reuse(grid_for(N), stream, sc, ctx->queue[cur ^ 1], ctx->queue[cur], ctx->nee, ctx->shadow, ctx->d_results, prev, ctx->d_counters);
-      }
-      {
-        Launch l(ctx, stream, LUMC_KERNEL_SHADOW);
-        wf.shadow_rays(ctx->trace_blocks, lds_dyn, stream, sc, ctx->shadow, nullptr, prev + kCtlVolumeShift, ctx->d_counters, ctx->lds_nodes);
-      }
-      Launch l(ctx, stream, LUMC_KERNEL_RESOLVE);
-      wf.resolve_listed(std::min<uint32_t>(grid_for(N), 1024u), stream, sc, ctx->queue[cur ^ 1], ctx->nee, ctx->shadow, ctx->d_results, (const uint32_t*) prev);
-      resolve_pending = false;
-    }
-    if (sc.particles_active) trace_particles(ctx, stream, ctx->queue[cur], ctrl, N);  // optix_kernel_raytrace.cu:171
-    if (sc.ocean_active) {  // optix_kernel_raytrace.cu:134-144, :172
-      Launch l(ctx, stream, LUMC_KERNEL_TRACE);
-      wf.trace_ocean(grid_for(N), stream, sc, ctx->queue[cur], (const uint32_t*) ctrl);
-    }
-    if (render_volumes) {  // device_renderer.c:64-76: in-scattering with its own visibility pass, then the scattering events
-      {
-        Launch l(ctx, stream, LUMC_KERNEL_VOLUME);
-        wf.volume_inscatter(grid_for(N), stream, sc, ctx->queue[cur], ctx->volume, ctx->shadow, ctrl, depth_const);
-      }
-      {
-        Launch l(ctx, stream, LUMC_KERNEL_SHADOW);
-        wf.shadow_rays(grid_persistent(ctx, N), lds_dyn, stream, sc, ctx->shadow, nullptr, ctrl + kCtlVolumeShift, ctx->d_counters, ctx->lds_nodes);
-      }
-      Launch l(ctx, stream, LUMC_KERNEL_VOLUME);
-      wf.volume_resolve(grid_for(N), stream, sc, ctx->queue[cur], ctx->volume, ctx->shadow, ctx->d_results, (const uint32_t*) ctrl);
-      wf.volume_events(grid_for(N), stream, sc, ctx->queue[cur], ctx->volume, ctx->d_results, ctrl, depth_const);
-    }
-    if (sc.cloud_active && sc.sky_mode == kSkyDefault && sc.cloud_noise_shape) {  // device_manager.c:474, device_renderer.c:78-82
-      Launch l(ctx, stream, LUMC_KERNEL_SKY);
-#if LUM_CLOUD_PERSISTENT
-      wf.clouds_list(grid_for(N), stream, sc, ctx->queue[cur], ctx->cloud, ctrl);
-      wf.clouds_march(ctx->trace_blocks * 4u, stream, sc, ctx->queue[cur], ctx->cloud, ctrl, depth_const);  // persistent: 4 workgroups of 256 per CU
-#endif
-      wf.clouds(grid_for(N), stream, sc, ctx->queue[cur], ctx->cloud, ctx->d_results, (const uint32_t*) ctrl, depth_const);
-    }
-    if (sc.sky_aerial_perspective && sc.sky_mode != kSkyConstantColor) {  // device_manager.c:475, device_renderer.c:84-88
-      Launch l(ctx, stream, LUMC_KERNEL_SKY);
-      wf.sky_inscattering(grid_for(N), stream, sc, ctx->queue[cur], ctx->d_results, (const uint32_t*) ctrl, depth_const);
-    }
-    {
-      Launch l(ctx, stream, LUMC_KERNEL_SHADE);
-      wf.shade(shade_grid(ctx, N), stream, sc, ctx->queue[cur], ctx->queue[next_q], nee, ctx->shadow, ctx->d_results, ctrl, depth_const, ctx->d_counters,
-               (reuse && depth < max_depth) ? 1u : 0u, fused ? ctx->d_fused + depth % 6u : nullptr,
-               fused ? ((depth > 0 ? 1u : 0u) | (depth < max_depth ? 2u : 0u) | (ctx->fused_ended ? 4u : 0u)) : 0u);
-    }
-    if (fused && depth > 0) {  // the samples of depth - 1 their paths' closest hits could not decide: traced now, their vertices resolved (before this depth's visibility pass reuses the words)
-      {
-        Launch l(ctx, stream, LUMC_KERNEL_SHADOW);
-        wf.shadow_rays(ctx->trace_blocks, lds_dyn, stream, sc, ctx->fallback, nullptr, ctrl + kCtlVolumeShift, ctx->d_counters, ctx->lds_nodes);
-      }
-      Launch l(ctx, stream, LUMC_KERNEL_RESOLVE);
-      wf.resolve_listed(std::min<uint32_t>(grid_for(N), 1024u), stream, sc, ctx->queue[prev_q], nee_before, ctx->fallback, ctx->d_results, (const uint32_t*) ctrl);
-    }
-    if (sc.particles_active) {  // device_renderer.c:99-103
-      Launch l(ctx, stream, LUMC_KERNEL_SHADE);
-      wf.particle_shade(grid_for(N), stream, sc, ctx->queue[cur], ctx->queue[cur ^ 1], ctx->nee, ctx->shadow, ctrl, depth_const);
-    }
-    if (sc.ocean_active) {  // device_renderer.c:104-108
-      Launch l(ctx, stream, LUMC_KERNEL_SHADE);
-      wf.ocean_shade(grid_for(N), stream, sc, ctx->queue[cur], ctx->queue[cur ^ 1], ctx->nee, ctx->shadow, ctrl, depth_const);
-    }
-    if (sc.sky_mode == kSkyDefault) {  // paths that left the scene into the procedural sky (listed by k_shade)
-      Launch l(ctx, stream, LUMC_KERNEL_SKY);
-      wf.sky(grid_for(N), stream, sc, ctx->queue[cur], ctx->shadow, ctx->d_results, (const uint32_t*) ctrl, depth_const);
-    }
-    {
-      Launch l(ctx, stream, LUMC_KERNEL_LIGHT_QUERY);
-      // (one resident round of its workgroups - four per CU: the kernel's workgroups are dear to start (a 1 KB stack per lane in scratch); 2 rounds, the common cap:
-      //  Example-class 4.6 -> 4.0 ms per 3 steps, scan 3.9 -> 3.6, hall equal; 4 / 8 / 16 rounds on the hall: 30.2 / 32.8 / 44.5 ms against 29.9)
-      wf.light_query(std::min<uint32_t>(grid_for(N), ctx->trace_blocks * 4u), stream, sc, ctx->queue[cur], nee, ctx->shadow, ctrl, depth_const, ctx->d_counters);
-    }
-    const uint32_t* shadow_order = nullptr;
-    if (ctx->sort_mode == 2) {
-      shadow_order = sort_rays(ctx, stream, ctx->shadow.origin_dist, ctx->shadow.dir_out, ctrl + kCtlShadowItems,
-                               (sc.ocean_active ? kSurfaceShadowKindsWater : 4u) * (ctx->shadow.capacity < N ? ctx->shadow.capacity : N));
-      if (!shadow_order) { ctx->error = "ray sorting failed"; return 1; }
-    }
-    {
-      Launch l(ctx, stream, LUMC_KERNEL_SHADOW);
-      wf.shadow_rays(grid_persistent(ctx, N), lds_dyn, stream, sc, ctx->shadow, shadow_order, ctrl, ctx->d_counters, ctx->lds_nodes);
-    }
-    if (fused && depth < max_depth) {  // the vertices no entry of the next depth continues; the others are resolved by those entries, in k_shade - and so are these, as its last input (fused_flags & 4)
-      if (!ctx->fused_ended) {
-        Launch l(ctx, stream, LUMC_KERNEL_RESOLVE);
-        wf.resolve_ended(std::min<uint32_t>(grid_for(N), 4096u), stream, sc, ctx->queue[cur], nee, ctx->shadow, ctx->d_results, (const uint32_t*) ctrl, ctx->d_ended[depth & 1u]);
-      }
-    }
-    else if (reuse && depth < max_depth) resolve_pending = true;
-    else {
-      Launch l(ctx, stream, LUMC_KERNEL_RESOLVE);
-      wf.resolve(grid_for(N), stream, sc, ctx->queue[cur], nee, ctx->shadow, ctx->d_results, (const uint32_t*) ctrl);
-    }
-    if (render_volumes && depth != max_depth) {  // device_renderer.c:114-118
-      Launch l(ctx, stream, LUMC_KERNEL_VOLUME);
-      wf.volume_bounce(grid_for(N), stream, sc, ctx->queue[cur], ctx->queue[cur ^ 1], ctx->volume, ctrl, depth_const);
-    }
-    cur = next_q;
+    const DepthBuffers d = depth_buffers(ctx, scheme, depth, max_depth);
+    if (closest_hits(ctx, stream, sc, scheme, d, N)) return 1;
+    media_passes(ctx, stream, sc, d, N);
+    shade_depth(ctx, stream, sc, scheme, d, N);
+    feature_shading(ctx, stream, sc, d, N);
+    if (visibility_and_resolve(ctx, stream, sc, scheme, d, N)) return 1;
+    volume_bounce(ctx, stream, sc, d, N);
   }
   return 0;
 }
@@ -1529,25 +1296,6 @@ int lumc_render(LumContext* ctx, uint32_t first_sample, uint32_t num_samples, ui
     HIP_TRY(ctx, hipGetLastError());
   }
   return 0;
-}
-
-// The pixels of one iteration of the undersampling preview (tasks_create, cuda/kernels.cuh:47-95, whole-frame window): one per block of
-// 2^stage pixels, at the block's corner or half a block in, by the iteration's two bits.
-static std::vector<uint32_t> undersampling_pixels(uint32_t width, uint32_t height, uint32_t stage, uint32_t iteration) {
-  const uint32_t scale = 1u << stage;
-  const uint32_t uw = (width + scale - 1) >> stage, uh = (height + scale - 1) >> stage;
-  std::vector<uint32_t> px;
-  px.reserve((size_t) uw * uh);
-  for (uint32_t id = 0; id < uw * uh; id++) {
-    uint32_t y = id / uw, x = id - y * uw;
-    if (scale > 1) {
-      x = x * scale + ((iteration & 1u) ? 0u : scale >> 1);
-      y = y * scale + ((iteration & 2u) ? 0u : scale >> 1);
-    }
-    if (x >= width || y >= height) continue;
-    px.push_back(x + y * width);
-  }
-  return px;
 }
 
 int lumc_render_undersampled(LumContext* ctx, uint32_t stage, uint32_t iteration, void* stream_) {
@@ -1840,7 +1588,7 @@ int lumc_adaptive_end(LumContext* ctx) {
 
 int lumc_generate_result(LumContext* ctx, uint32_t mode, uint32_t local_error_minimization, uint32_t uniform_samples, float exposure, const LumOutputParams* tone,
                          float* d_result, void* stream_) {
-  const bool framed = ctx && ctx->use_frame && ctx->d_frame && ctx->has_scene && ctx->frame_capacity == ctx->scene.width * ctx->scene.height;
+  const bool framed = ctx && ctx->exchange.use_frame && ctx->exchange.d_frame && ctx->has_scene && ctx->exchange.frame_capacity == ctx->scene.width * ctx->scene.height;
   if (!ctx || !ctx->has_scene || (!framed && (!ctx->d_first_moment || ctx->d_pixels || ctx->num_pixels != ctx->scene.width * ctx->scene.height))) {
     if (ctx) ctx->error = "lumc_generate_result: needs the full-frame accumulators";
     return 1;
@@ -1848,8 +1596,8 @@ int lumc_generate_result(LumContext* ctx, uint32_t mode, uint32_t local_error_mi
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   hipStream_t stream = (hipStream_t) stream_;
   const uint32_t n = ctx->scene.width * ctx->scene.height;
-  const float* src_fm = framed ? ctx->d_frame : ctx->d_first_moment;
-  const float* src_sm = framed ? ctx->d_frame + 3 * (size_t) n : ctx->d_second_moment;
+  const float* src_fm = framed ? ctx->exchange.d_frame : ctx->d_first_moment;
+  const float* src_sm = framed ? ctx->exchange.d_frame + 3 * (size_t) n : ctx->d_second_moment;
   if (!d_result) {
     if (ctx->frame_result_pixels != n) {
       if (ctx->d_frame_result) (void) hipFree(ctx->d_frame_result);
@@ -2064,7 +1812,7 @@ int lumc_denoise(LumContext* ctx, const LumDenoiseParams* params, float* d_image
   if (!ctx || !params || !ctx->has_scene) { if (ctx) ctx->error = "lumc_denoise: no scene or null argument"; return 1; }
   const uint32_t n = ctx->scene.width * ctx->scene.height;
   if (!ctx->guides_valid || ctx->guide_pixels != n) { ctx->error = "lumc_denoise: no guides for this frame (lumc_render_guides)"; return 1; }
-  const bool framed = ctx->use_frame && ctx->d_frame && ctx->frame_capacity == n;
+  const bool framed = ctx->exchange.use_frame && ctx->exchange.d_frame && ctx->exchange.frame_capacity == n;
   if (!framed && (!ctx->d_first_moment || ctx->d_pixels || ctx->num_pixels != n)) { ctx->error = "lumc_denoise: needs the full-frame accumulators"; return 1; }
   if (!d_image) d_image = (ctx->frame_result_pixels == n) ? ctx->d_frame_result : nullptr;
   if (!d_image) { ctx->error = "lumc_denoise: no image"; return 1; }
@@ -2078,8 +1826,8 @@ int lumc_denoise(LumContext* ctx, const LumDenoiseParams* params, float* d_image
     for (void*& r : ctx->d_denoise_rec) HIP_TRY(ctx, hipMalloc(&r, 16 * (size_t) n));
     ctx->denoise_pixels = n;
   }
-  const float* src_fm = framed ? ctx->d_frame : ctx->d_first_moment;
-  const float* src_sm = framed ? ctx->d_frame + 3 * (size_t) n : ctx->d_second_moment;
+  const float* src_fm = framed ? ctx->exchange.d_frame : ctx->d_first_moment;
+  const float* src_sm = framed ? ctx->exchange.d_frame + 3 * (size_t) n : ctx->d_second_moment;
   AdaptiveView view;
   std::memset(&view, 0, sizeof(view));
   if (ctx->adaptive.active) view = adaptive_view(ctx);
@@ -2443,487 +2191,6 @@ extern "C" int lumc_debug_phase_stats(uint64_t out[16], int reset) {
 }
 #endif
 
-// ---- multi-GPU: the image is dealt to the GPUs in 32x32 tiles, every GPU accumulates its own pixels, and ONE reduce per output assembles
-// the four moment planes on the display GPU. Replaces the reference's sample partition with host-staged sums
-// (device/device_result_interface.c:107-299, at most four devices). Transport: RCCL over xGMI - one communicator rank per context, created
-// either per process (lumc_comm_init_rank, launched as one process per GPU) or for all GPUs of one process (lumc_comm_init_all). ----
-namespace {
-__global__ __launch_bounds__(256) void k_frame_scatter(const float* __restrict__ fm, const float* __restrict__ sm, const uint32_t* __restrict__ pixels, uint32_t n,
-                                                       uint32_t frame_pixels, float* __restrict__ frame) {
-  for (uint32_t p = blockIdx.x * 256u + threadIdx.x; p < n; p += gridDim.x * 256u) {
-    const uint32_t index = pixels ? pixels[p] : p;
-    if (index >= frame_pixels) continue;
-    frame[index] = fm[p]; frame[frame_pixels + index] = fm[n + p]; frame[2u * frame_pixels + index] = fm[2u * n + p];
-    frame[3u * frame_pixels + index] = sm[p];
-  }
-}
-__global__ __launch_bounds__(256) void k_frame_add(const float4* __restrict__ src, float4* __restrict__ dst, uint32_t count4) {  // buffer_add, cuda/kernels.cuh:646-675
-  for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < count4; i += gridDim.x * 256u) {
-    const float4 a = src[i]; float4 b = dst[i];
-    b.x += a.x; b.y += a.y; b.z += a.z; b.w += a.w;
-    dst[i] = b;
-  }
-}
-#define NCCL_TRY(ctx, expr)                                                                          \
-  do {                                                                                               \
-    const ncclResult_t r__ = (expr);                                                                 \
-    if (r__ != ncclSuccess) { (ctx)->error = std::string(#expr) + " failed: " + ncclGetErrorString(r__); return 1; } \
-  } while (0)
-
-// this context's pixels scattered into its zeroed [4][frame_pixels] frame buffer
-int frame_scatter(LumContext* ctx, uint32_t frame_pixels, hipStream_t stream) {
-  if (!ctx->d_first_moment || ctx->num_pixels == 0) { ctx->error = "lumc_frame_assemble: no accumulators (lumc_set_pixels)"; return 1; }
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const uint32_t padded = frame_pixels;  // 4 planes of n floats = n float4s: the add kernel walks the whole buffer, planes keep stride n
-  if (ctx->frame_capacity != padded) {
-    if (ctx->d_frame) (void) hipFree(ctx->d_frame);
-    ctx->d_frame = nullptr; ctx->frame_capacity = 0;
-    HIP_TRY(ctx, hipMalloc((void**) &ctx->d_frame, sizeof(float) * 4 * (size_t) padded));
-    ctx->frame_capacity = padded;
-  }
-  HIP_TRY(ctx, hipMemsetAsync(ctx->d_frame, 0, sizeof(float) * 4 * (size_t) ctx->frame_capacity, stream));
-  hipLaunchKernelGGL(k_frame_scatter, dim3(grid_for(ctx->num_pixels)), dim3(256), 0, stream, (const float*) ctx->d_first_moment, (const float*) ctx->d_second_moment,
-                     (const uint32_t*) ctx->d_pixels, ctx->num_pixels, ctx->frame_capacity, ctx->d_frame);
-  HIP_TRY(ctx, hipGetLastError());
-  return 0;
-}
-}  // namespace
-
-int lumc_device_count(void) {
-  int n = 0;
-  return hipGetDeviceCount(&n) == hipSuccess ? n : 0;
-}
-
-// The tile deal ("block -> GPU by interleaved round-robin for load balance"). Round 5: a rank-1 lattice instead of t % world over the
-// row-major grid. The old deal is periodic in x with period `world` tiles whenever the tile row length is a multiple of `world` - at 3840 px (120 tiles)
-// and 8 ranks every rank owned vertical 32-pixel stripes. Now tile (x, y) belongs to rank (x + k * y) % world, with k chosen among the steps COPRIME to
-// `world` so that a rank's tiles form the most isotropic lattice: k maximises the shortest distance between two tiles of one rank (world 8: k = 3, nearest
-// own tiles at (2, 2) and (1, -3); world 2: the checkerboard; world 4 and 6: k = 1, the diagonals). Coprime (round 6, advisor): the row offset k * y then
-// runs through every residue, so the tiles a row has beyond a multiple of `world` go to every rank in turn - with k = 2 at 4 ranks (round 5's choice, more
-// isotropic) they always went to the same half (1376 x 1080: max / mean share 1.023). Balance bound: over any `world` consecutive tile rows every rank owns
-// the same number of tiles; a frame's shares differ by at most (tiles_y % world) tiles (+ the clipped tiles of the right and bottom edge).
-// LUM_TILE_DEAL=rowmajor restores t % world (A/B of the load-balance table, profiles/r05_load_balance.json).
-uint32_t lumc_tile_lattice_step(uint32_t world) {
-  if (world < 2) return 0;
-  auto gcd = [](uint32_t a, uint32_t b) { while (b) { const uint32_t t = a % b; a = b; b = t; } return a; };
-  uint32_t best_k = 1; int64_t best = -1;
-  for (uint32_t k = 1; k < world; k++) {
-    if (gcd(k, world) != 1u) continue;
-    int64_t shortest = INT64_MAX;
-    for (int64_t b = -(int64_t) world; b <= (int64_t) world; b++)
-      for (int64_t a = -(int64_t) world; a <= (int64_t) world; a++) {
-        if ((a == 0 && b == 0) || ((a + (int64_t) k * b) % (int64_t) world) != 0) continue;
-        shortest = std::min(shortest, a * a + b * b);
-      }
-    if (shortest > best) { best = shortest; best_k = k; }
-  }
-  return best_k;
-}
-
-static bool tile_deal_rowmajor() {
-  static const bool v = [] { const char* e = std::getenv("LUM_TILE_DEAL"); return e && std::strcmp(e, "rowmajor") == 0; }();
-  return v;
-}
-
-// the step of a world size, computed once per size (the search is cubic in `world`; the host's render threads call this concurrently)
-static uint32_t tile_lattice_step_cached(uint32_t world) {
-  static uint32_t step_of[65];
-  static std::once_flag once;
-  std::call_once(once, [] { for (uint32_t w = 0; w <= 64; w++) step_of[w] = lumc_tile_lattice_step(w); });
-  if (world <= 64) return step_of[world];
-  static std::mutex m;
-  static std::map<uint32_t, uint32_t> beyond;
-  std::lock_guard<std::mutex> lock(m);
-  auto it = beyond.find(world);
-  if (it == beyond.end()) it = beyond.emplace(world, lumc_tile_lattice_step(world)).first;
-  return it->second;
-}
-
-uint32_t lumc_tile_owner(uint32_t tile_x, uint32_t tile_y, uint32_t tiles_x, uint32_t world) {
-  if (world < 2) return 0;
-  if (tile_deal_rowmajor()) return (uint32_t) (((uint64_t) tile_y * tiles_x + tile_x) % world);
-  return (uint32_t) (((uint64_t) tile_x + (uint64_t) tile_lattice_step_cached(world) * tile_y) % world);
-}
-
-// Writes the rank's pixel indices (x + y * width): its tiles in row-major tile order, rows within a tile; `out` may be NULL to query the count.
-int lumc_tile_pixels(uint32_t width, uint32_t height, uint32_t rank, uint32_t world, uint32_t tile, uint32_t* out, uint32_t* count) {
-  if (!count || world == 0 || rank >= world || tile == 0) return 1;
-  const uint32_t tx = (width + tile - 1) / tile, ty = (height + tile - 1) / tile;
-  uint32_t n = 0;
-  for (uint32_t j = 0; j < ty; j++)
-    for (uint32_t i = 0; i < tx; i++) {
-      if (lumc_tile_owner(i, j, tx, world) != rank) continue;
-      const uint32_t x0 = i * tile, y0 = j * tile;
-      for (uint32_t y = y0; y < std::min(y0 + tile, height); y++)
-        for (uint32_t x = x0; x < std::min(x0 + tile, width); x++) { if (out) out[n] = x + y * width; n++; }
-    }
-  *count = n;
-  return 0;
-}
-
-int lumc_comm_unique_id(uint8_t id[LUMC_COMM_ID_BYTES]) {
-  static_assert(sizeof(ncclUniqueId) <= LUMC_COMM_ID_BYTES, "unique id does not fit");
-  if (!id) return 1;
-  ncclUniqueId u;
-  if (ncclGetUniqueId(&u) != ncclSuccess) return 1;
-  std::memset(id, 0, LUMC_COMM_ID_BYTES);
-  std::memcpy(id, &u, sizeof(u));
-  return 0;
-}
-
-int lumc_comm_init_rank(LumContext* ctx, int world, int rank, const uint8_t id[LUMC_COMM_ID_BYTES]) {
-  if (!ctx || !id || world < 1 || rank < 0 || rank >= world) { if (ctx) ctx->error = "lumc_comm_init_rank: bad arguments"; return 1; }
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  if (ctx->comm) { (void) ncclCommDestroy(ctx->comm); ctx->comm = nullptr; }
-  ncclUniqueId u;
-  std::memcpy(&u, id, sizeof(u));
-  NCCL_TRY(ctx, ncclCommInitRank(&ctx->comm, world, u, rank));
-  ctx->comm_rank = rank; ctx->comm_world = world;
-  return 0;
-}
-
-int lumc_comm_init_all(LumContext** ctxs, int n) {
-  if (!ctxs || n < 1) return 1;
-  std::vector<int> devices(n);
-  for (int i = 0; i < n; i++) {
-    if (!ctxs[i]) return 1;
-    devices[i] = ctxs[i]->device;
-    for (int j = 0; j < i; j++)
-      if (devices[j] == devices[i]) { ctxs[0]->error = "lumc_comm_init_all: two contexts on one device (RCCL needs one GPU per rank)"; return 1; }
-  }
-  std::vector<ncclComm_t> comms(n, nullptr);
-  NCCL_TRY(ctxs[0], ncclCommInitAll(comms.data(), n, devices.data()));
-  for (int i = 0; i < n; i++) {
-    if (ctxs[i]->comm) (void) ncclCommDestroy(ctxs[i]->comm);
-    ctxs[i]->comm = comms[i]; ctxs[i]->comm_rank = i; ctxs[i]->comm_world = n;
-  }
-  return 0;
-}
-
-void lumc_comm_destroy(LumContext* ctx) {
-  if (ctx && ctx->comm) { (void) hipSetDevice(ctx->device); (void) ncclCommDestroy(ctx->comm); ctx->comm = nullptr; ctx->comm_world = 1; ctx->comm_rank = 0; }
-}
-
-// One process per GPU: this rank's pixels into its frame buffer, then ncclReduce(SUM) to `root` (every pixel has one owner, so the sum is
-// a gather: 16 bytes per pixel and rank, once per output). Without a communicator (single GPU) the scatter alone is the frame.
-int lumc_frame_assemble(LumContext* ctx, uint32_t frame_pixels, int root, void* stream_, float** d_frame_out) {
-  if (!ctx) return 1;
-  hipStream_t stream = (hipStream_t) stream_;
-  if (frame_scatter(ctx, frame_pixels, stream)) return 1;
-  if (ctx->comm) {
-    if (root < 0 || root >= ctx->comm_world) { ctx->error = "lumc_frame_assemble: bad root"; return 1; }
-    NCCL_TRY(ctx, ncclReduce(ctx->d_frame, ctx->d_frame, 4 * (size_t) ctx->frame_capacity, ncclFloat, ncclSum, root, ctx->comm, stream));
-  }
-  if (d_frame_out) *d_frame_out = ctx->d_frame;
-  return 0;
-}
-
-// One process, several GPUs: all contexts scatter, then one grouped ncclReduce to `root` (lumc_comm_init_all). Contexts without a common
-// communicator (RCCL unavailable, or test set-ups with two contexts on one device) are summed through peer copies and the add kernel
-// instead - the reference's own transport (device_result_interface.c:177-215), kept as the fallback.
-int lumc_frame_assemble_all(LumContext** ctxs, int n, uint32_t frame_pixels, int root, float** d_frame_root) {
-  if (!ctxs || n < 1 || root < 0 || root >= n) return 1;
-  bool rccl = n > 1;
-  for (int i = 0; i < n; i++) {
-    if (!ctxs[i]) return 1;
-    if (frame_scatter(ctxs[i], frame_pixels, (hipStream_t) 0)) { if (i) ctxs[0]->error = ctxs[i]->error; return 1; }
-    rccl = rccl && ctxs[i]->comm && ctxs[i]->comm_world == n && ctxs[i]->comm_rank == i;
-  }
-  LumContext* r = ctxs[root];
-  if (rccl) {
-    NCCL_TRY(r, ncclGroupStart());
-    for (int i = 0; i < n; i++) {
-      (void) hipSetDevice(ctxs[i]->device);
-      const ncclResult_t e = ncclReduce(ctxs[i]->d_frame, ctxs[i]->d_frame, 4 * (size_t) ctxs[i]->frame_capacity, ncclFloat, ncclSum, root, ctxs[i]->comm, (hipStream_t) 0);
-      if (e != ncclSuccess) { (void) ncclGroupEnd(); r->error = std::string("ncclReduce failed: ") + ncclGetErrorString(e); return 1; }
-    }
-    NCCL_TRY(r, ncclGroupEnd());
-    for (int i = 0; i < n; i++) { HIP_TRY(r, hipSetDevice(ctxs[i]->device)); HIP_TRY(r, hipDeviceSynchronize()); }
-  }
-  else if (n > 1) {
-    float* staging = nullptr;
-    HIP_TRY(r, hipSetDevice(r->device));
-    const size_t bytes = sizeof(float) * 4 * (size_t) r->frame_capacity;
-    HIP_TRY(r, hipMalloc((void**) &staging, bytes));
-    for (int i = 0; i < n; i++) {
-      if (i == root) continue;
-      HIP_TRY(r, hipSetDevice(ctxs[i]->device));
-      HIP_TRY(r, hipDeviceSynchronize());
-      HIP_TRY(r, hipSetDevice(r->device));
-      HIP_TRY(r, hipMemcpyPeer(staging, r->device, ctxs[i]->d_frame, ctxs[i]->device, bytes));
-      hipLaunchKernelGGL(k_frame_add, dim3(grid_for(r->frame_capacity)), dim3(256), 0, 0, (const float4*) staging, (float4*) r->d_frame, r->frame_capacity);
-      HIP_TRY(r, hipGetLastError());
-    }
-    HIP_TRY(r, hipDeviceSynchronize());
-    (void) hipFree(staging);
-  }
-  if (d_frame_root) *d_frame_root = r->d_frame;
-  return 0;
-}
-
-// ---- tile gather: the frame assembled from the ranks' own pixels instead of a reduce over whole frames ----
-// Every pixel has one owner, so summing the ranks' zero-padded full frames (lumc_frame_assemble: 16 bytes per FRAME pixel from every rank, 133 MB per
-// rank at 4K) moves `world` times what is needed: a rank's contribution is the 16 bytes of each pixel it OWNS. Where the ranks' pixel sets are the tile
-// deal of lumc_tile_pixels (32 x 32 tiles dealt by lumc_tile_owner's lattice - what bench.py and the host API's tiled render loop use), every rank can compute every other
-// rank's pixel list, so nothing but the sums travels: each rank packs its [3][P] + [P] accumulators into a [4][M] buffer (M = the largest tile share,
-// zero padded: the deal's shares differ by at most tiles_y % world tiles, see lumc_tile_lattice_step), ONE ncclGather brings the `world` buffers to the root, and a scatter kernel on the root puts every
-// value at its pixel. Reference: device_result_interface.c:107-299 (sample partition, sums staged through pinned host memory).
-namespace {
-__global__ __launch_bounds__(256) void k_gather_pack(const float* __restrict__ fm, const float* __restrict__ sm, uint32_t n, uint32_t stride, float* __restrict__ send) {
-  for (uint32_t p = blockIdx.x * 256u + threadIdx.x; p < stride; p += gridDim.x * 256u) {
-    const bool in = p < n;
-    send[p] = in ? fm[p] : 0.0f; send[stride + p] = in ? fm[n + p] : 0.0f; send[2u * stride + p] = in ? fm[2u * n + p] : 0.0f; send[3u * stride + p] = in ? sm[p] : 0.0f;
-  }
-}
-__global__ __launch_bounds__(256) void k_gather_unpack(const float* __restrict__ recv, const uint32_t* __restrict__ pixels, uint32_t world, uint32_t stride, uint32_t frame_pixels,
-                                                       float* __restrict__ frame) {
-  const uint32_t total = world * stride;
-  for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < total; i += gridDim.x * 256u) {
-    const uint32_t index = pixels[i];
-    if (index >= frame_pixels) continue;  // padding
-    const uint32_t r = i / stride, p = i - r * stride;
-    const float* src = recv + (size_t) r * 4u * stride;
-    frame[index] = src[p]; frame[frame_pixels + index] = src[stride + p]; frame[2u * frame_pixels + index] = src[2u * stride + p]; frame[3u * frame_pixels + index] = src[3u * stride + p];
-  }
-}
-
-constexpr uint32_t kGatherTile = 32u;  // the deal bench.py, luminary_amd/distributed.py and the host API use
-
-// Sizes this context's gather buffers for (width, height, world): the send buffer on every rank, the receive buffer and the pixel lists on the root.
-// Fails when this context's pixel count is not its share of the deal (the gather is only for the standard deal; anything else reduces).
-int gather_prepare(LumContext* ctx, uint32_t width, uint32_t height, int world, int rank, bool is_root) {
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  uint32_t share = 0, stride = 0;
-  for (int r = 0; r < world; r++) {
-    uint32_t c = 0;
-    if (lumc_tile_pixels(width, height, (uint32_t) r, (uint32_t) world, kGatherTile, nullptr, &c)) { ctx->error = "lumc_frame_gather: bad deal"; return 1; }
-    if (r == rank) share = c;
-    stride = std::max(stride, c);
-  }
-  bool is_share = ctx->d_first_moment && ctx->num_pixels == share;
-  if (is_share) {  // ... and the same pixels in the same order: the root scatters the rank's sums through the list IT derives from the deal
-    std::vector<uint32_t> mine(share ? share : 1);
-    uint32_t c = 0;
-    (void) lumc_tile_pixels(width, height, (uint32_t) rank, (uint32_t) world, kGatherTile, mine.data(), &c);
-    is_share = pixel_list_hash(mine.data(), share) == ctx->pixels_hash;
-  }
-  if (!is_share) {
-    ctx->error = "lumc_frame_gather: this context's pixel set is not its share of the 32x32 tile deal, in the deal's order (use lumc_frame_assemble for other partitions)";
-    return 1;
-  }
-  stride = (stride + 3u) & ~3u;
-  const bool same = ctx->gather_key[0] == width && ctx->gather_key[1] == height && ctx->gather_key[2] == (uint32_t) world && ctx->gather_stride == stride && ctx->d_gather_send;
-  if (!same) {
-    if (ctx->d_gather_send) (void) hipFree(ctx->d_gather_send);
-    if (ctx->d_gather_pixels) (void) hipFree(ctx->d_gather_pixels);
-    ctx->d_gather_send = nullptr; ctx->d_gather_pixels = nullptr;
-    HIP_TRY(ctx, hipMalloc((void**) &ctx->d_gather_send, sizeof(float) * 4 * (size_t) stride));
-    ctx->gather_stride = stride; ctx->gather_key[0] = width; ctx->gather_key[1] = height; ctx->gather_key[2] = (uint32_t) world;
-  }
-  if (is_root) {
-    const size_t need = (size_t) world * 4 * stride;
-    if (ctx->gather_recv_floats < need) {
-      if (ctx->d_gather_recv) (void) hipFree(ctx->d_gather_recv);
-      ctx->d_gather_recv = nullptr; ctx->gather_recv_floats = 0;
-      HIP_TRY(ctx, hipMalloc((void**) &ctx->d_gather_recv, sizeof(float) * need));
-      ctx->gather_recv_floats = need;
-    }
-    if (!ctx->d_gather_pixels) {
-      std::vector<uint32_t> lists((size_t) world * stride, 0xFFFFFFFFu);
-      for (int r = 0; r < world; r++) { uint32_t c = 0; (void) lumc_tile_pixels(width, height, (uint32_t) r, (uint32_t) world, kGatherTile, lists.data() + (size_t) r * stride, &c); }
-      HIP_TRY(ctx, hipMalloc((void**) &ctx->d_gather_pixels, sizeof(uint32_t) * lists.size()));
-      HIP_TRY(ctx, hipMemcpy(ctx->d_gather_pixels, lists.data(), sizeof(uint32_t) * lists.size(), hipMemcpyHostToDevice));
-    }
-    const uint32_t frame_pixels = width * height;
-    if (ctx->frame_capacity != frame_pixels) {
-      if (ctx->d_frame) (void) hipFree(ctx->d_frame);
-      ctx->d_frame = nullptr; ctx->frame_capacity = 0;
-      HIP_TRY(ctx, hipMalloc((void**) &ctx->d_frame, sizeof(float) * 4 * (size_t) frame_pixels));
-      ctx->frame_capacity = frame_pixels;
-    }
-  }
-  return 0;
-}
-int gather_pack(LumContext* ctx, hipStream_t stream) {
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipLaunchKernelGGL(k_gather_pack, dim3(grid_for(ctx->gather_stride)), dim3(256), 0, stream, (const float*) ctx->d_first_moment, (const float*) ctx->d_second_moment, ctx->num_pixels,
-                     ctx->gather_stride, ctx->d_gather_send);
-  HIP_TRY(ctx, hipGetLastError());
-  return 0;
-}
-int gather_unpack(LumContext* root, int world, hipStream_t stream) {
-  HIP_TRY(root, hipSetDevice(root->device));
-  hipLaunchKernelGGL(k_gather_unpack, dim3(grid_for((uint32_t) world * root->gather_stride)), dim3(256), 0, stream, (const float*) root->d_gather_recv, (const uint32_t*) root->d_gather_pixels,
-                     (uint32_t) world, root->gather_stride, root->frame_capacity, root->d_frame);
-  HIP_TRY(root, hipGetLastError());
-  return 0;
-}
-}  // namespace
-
-// One process per GPU (lumc_comm_init_rank): pack, one ncclGather to `root`, scatter on the root. Without a communicator (one rank) the pack is copied.
-int lumc_frame_gather(LumContext* ctx, uint32_t width, uint32_t height, int root, void* stream_, float** d_frame_out) {
-  if (!ctx) return 1;
-  hipStream_t stream = (hipStream_t) stream_;
-  const int world = ctx->comm ? ctx->comm_world : 1, rank = ctx->comm ? ctx->comm_rank : 0;
-  if (root < 0 || root >= world) { ctx->error = "lumc_frame_gather: bad root"; return 1; }
-  if (gather_prepare(ctx, width, height, world, rank, rank == root)) return 1;
-  if (gather_pack(ctx, stream)) return 1;
-  const size_t count = 4 * (size_t) ctx->gather_stride;
-  if (ctx->comm) NCCL_TRY(ctx, ncclGather(ctx->d_gather_send, rank == root ? ctx->d_gather_recv : nullptr, count, ncclFloat, root, ctx->comm, stream));
-  else HIP_TRY(ctx, hipMemcpyAsync(ctx->d_gather_recv, ctx->d_gather_send, sizeof(float) * count, hipMemcpyDeviceToDevice, stream));
-  if (rank == root && gather_unpack(ctx, world, stream)) return 1;
-  if (d_frame_out) *d_frame_out = rank == root ? ctx->d_frame : nullptr;
-  return 0;
-}
-
-// One process, several GPUs (ctxs[i] holds share i of the deal over n): a grouped ncclGather when the contexts share a communicator
-// (lumc_comm_init_all), peer copies of the packed buffers into the root's receive buffer otherwise.
-int lumc_frame_gather_all(LumContext** ctxs, int n, uint32_t width, uint32_t height, int root, float** d_frame_root) {
-  if (!ctxs || n < 1 || root < 0 || root >= n) return 1;
-  bool rccl = n > 1;
-  for (int i = 0; i < n; i++) {
-    if (!ctxs[i]) return 1;
-    if (gather_prepare(ctxs[i], width, height, n, i, i == root) || gather_pack(ctxs[i], (hipStream_t) 0)) { if (i) ctxs[0]->error = ctxs[i]->error; return 1; }
-    rccl = rccl && ctxs[i]->comm && ctxs[i]->comm_world == n && ctxs[i]->comm_rank == i;
-  }
-  LumContext* r = ctxs[root];
-  const size_t count = 4 * (size_t) r->gather_stride;
-  if (rccl) {
-    NCCL_TRY(r, ncclGroupStart());
-    for (int i = 0; i < n; i++) {
-      (void) hipSetDevice(ctxs[i]->device);
-      const ncclResult_t e = ncclGather(ctxs[i]->d_gather_send, i == root ? r->d_gather_recv : nullptr, count, ncclFloat, root, ctxs[i]->comm, (hipStream_t) 0);
-      if (e != ncclSuccess) { (void) ncclGroupEnd(); r->error = std::string("ncclGather failed: ") + ncclGetErrorString(e); return 1; }
-    }
-    NCCL_TRY(r, ncclGroupEnd());
-    for (int i = 0; i < n; i++) { HIP_TRY(r, hipSetDevice(ctxs[i]->device)); HIP_TRY(r, hipDeviceSynchronize()); }
-  }
-  else {
-    for (int i = 0; i < n; i++) {
-      HIP_TRY(r, hipSetDevice(ctxs[i]->device));
-      HIP_TRY(r, hipDeviceSynchronize());
-      HIP_TRY(r, hipSetDevice(r->device));
-      HIP_TRY(r, hipMemcpyPeer(r->d_gather_recv + (size_t) i * count, r->device, ctxs[i]->d_gather_send, ctxs[i]->device, sizeof(float) * count));
-    }
-  }
-  if (gather_unpack(r, n, (hipStream_t) 0)) return 1;
-  HIP_TRY(r, hipDeviceSynchronize());
-  if (d_frame_root) *d_frame_root = r->d_frame;
-  return 0;
-}
-
-// ---- one process, several GPUs: what the tiled render loop of the host API needs beyond the frame assembly ----
-namespace {
-// this context's accumulators <- the frame's values at its pixels; with an adaptive partition only inside the blocks it owns
-__global__ __launch_bounds__(256) void k_accumulators_from_frame(const float* __restrict__ frame, uint32_t frame_pixels, const uint32_t* __restrict__ pixels, uint32_t n,
-                                                                 const uint8_t* __restrict__ block_mask, uint32_t width, uint32_t blocks_x, float* __restrict__ fm, float* __restrict__ sm) {
-  for (uint32_t p = blockIdx.x * 256u + threadIdx.x; p < n; p += gridDim.x * 256u) {
-    const uint32_t index = pixels ? pixels[p] : p;
-    bool mine = index < frame_pixels;
-    if (mine && block_mask) { const uint32_t y = index / width, x = index - y * width; mine = block_mask[(y >> 2) * blocks_x + (x >> 2)] != 0; }
-    fm[p] = mine ? frame[index] : 0.0f; fm[n + p] = mine ? frame[frame_pixels + index] : 0.0f; fm[2u * n + p] = mine ? frame[2u * frame_pixels + index] : 0.0f;
-    sm[p] = mine ? frame[3u * frame_pixels + index] : 0.0f;
-  }
-}
-}  // namespace
-
-// The accumulators of `dst` (whatever its pixel set: a tile list, or the full frame with an adaptive partition) take the values the frame buffer of
-// `src` holds at dst's pixels (lumc_frame_assemble on src first: its own full-frame accumulators, scattered). This is how the first sample of a
-// frame, rendered coarse to fine on the main device alone (the undersampling preview, device.c:392-420), is handed to the devices that go on with
-// the frame's tiles: every pixel's sums continue where the preview left them, so the tiled frame equals the single-device frame bit for bit.
-int lumc_accumulators_from_frame(LumContext* dst, LumContext* src) {
-  if (!dst || !src || !src->d_frame || !dst->d_first_moment || dst->num_pixels == 0) { if (dst) dst->error = "lumc_accumulators_from_frame: no frame on the source or no accumulators on the destination"; return 1; }
-  const uint32_t frame_pixels = src->frame_capacity;
-  const float* frame = src->d_frame;
-  float* staging = nullptr;
-  HIP_TRY(dst, hipSetDevice(src->device));
-  HIP_TRY(dst, hipDeviceSynchronize());
-  HIP_TRY(dst, hipSetDevice(dst->device));
-  if (dst != src) {  // another context (another GPU, or the same one in test set-ups): a copy of the frame on dst's device
-    const size_t bytes = sizeof(float) * 4 * (size_t) frame_pixels;
-    HIP_TRY(dst, hipMalloc((void**) &staging, bytes));
-    HIP_TRY(dst, hipMemcpyPeer(staging, dst->device, src->d_frame, src->device, bytes));
-    frame = staging;
-  }
-  const LumContext::Adaptive& a = dst->adaptive;
-  hipLaunchKernelGGL(k_accumulators_from_frame, dim3(grid_for(dst->num_pixels)), dim3(256), 0, 0, frame, frame_pixels, (const uint32_t*) dst->d_pixels, dst->num_pixels,
-                     a.active ? (const uint8_t*) a.d_block_mask : nullptr, dst->scene.width, a.active ? a.blocks_x : 0u, dst->d_first_moment, dst->d_second_moment);
-  HIP_TRY(dst, hipGetLastError());
-  HIP_TRY(dst, hipDeviceSynchronize());
-  if (staging) (void) hipFree(staging);
-  return 0;
-}
-
-// A stage build of adaptive rendering tiled over the contexts of one process (lumc_adaptive_set_partition on each): every context computes the
-// variances of its blocks, ONE all-reduce of 4 bytes per block makes the array complete everywhere (every block has one owner: the sum is a gather and
-// exact), every context derives the same rates. Grouped ncclAllReduce when the contexts share a communicator (lumc_comm_init_all); otherwise - two
-// contexts on one device in tests, or no RCCL - the arrays are summed on the host in context order.
-int lumc_adaptive_exchange_all(LumContext** ctxs, int n) {
-  if (!ctxs || n < 1) return 1;
-  bool rccl = n > 1;
-  for (int i = 0; i < n; i++) {
-    if (!ctxs[i] || !ctxs[i]->adaptive.active) { if (ctxs[0]) ctxs[0]->error = "lumc_adaptive_exchange_all: adaptive mode is not active on every context"; return 1; }
-    if (ctxs[i]->adaptive.num_blocks != ctxs[0]->adaptive.num_blocks) { ctxs[0]->error = "lumc_adaptive_exchange_all: contexts of different frames"; return 1; }
-    HIP_TRY(ctxs[0], hipSetDevice(ctxs[i]->device));
-    if (adaptive_compute_variance(ctxs[i], (hipStream_t) 0)) { ctxs[0]->error = ctxs[i]->error; return 1; }
-    rccl = rccl && ctxs[i]->comm && ctxs[i]->comm_world == n && ctxs[i]->comm_rank == i;
-  }
-  const uint32_t nb = ctxs[0]->adaptive.num_blocks;
-  if (rccl) {
-    NCCL_TRY(ctxs[0], ncclGroupStart());
-    for (int i = 0; i < n; i++) {
-      (void) hipSetDevice(ctxs[i]->device);
-      const ncclResult_t e = ncclAllReduce(ctxs[i]->adaptive.d_block_variance, ctxs[i]->adaptive.d_block_variance, nb, ncclFloat, ncclSum, ctxs[i]->comm, (hipStream_t) 0);
-      if (e != ncclSuccess) { (void) ncclGroupEnd(); ctxs[0]->error = std::string("ncclAllReduce failed: ") + ncclGetErrorString(e); return 1; }
-    }
-    NCCL_TRY(ctxs[0], ncclGroupEnd());
-  }
-  else if (n > 1) {
-    std::vector<float> sum(nb, 0.0f), part(nb);
-    for (int i = 0; i < n; i++) {
-      HIP_TRY(ctxs[0], hipSetDevice(ctxs[i]->device));
-      HIP_TRY(ctxs[0], hipMemcpy(part.data(), ctxs[i]->adaptive.d_block_variance, sizeof(float) * nb, hipMemcpyDeviceToHost));
-      for (uint32_t b = 0; b < nb; b++) sum[b] += part[b];
-    }
-    for (int i = 0; i < n; i++) {
-      HIP_TRY(ctxs[0], hipSetDevice(ctxs[i]->device));
-      HIP_TRY(ctxs[0], hipMemcpy(ctxs[i]->adaptive.d_block_variance, sum.data(), sizeof(float) * nb, hipMemcpyHostToDevice));
-    }
-  }
-  for (int i = 0; i < n; i++) {
-    HIP_TRY(ctxs[0], hipSetDevice(ctxs[i]->device));
-    if (ctxs[i]->adaptive.stage_id >= kAdaptiveStages) { ctxs[0]->error = "lumc_adaptive_exchange_all: the last stage is already running"; return 1; }
-    if (adaptive_finish_build(ctxs[i], (hipStream_t) 0)) { ctxs[0]->error = ctxs[i]->error; return 1; }
-  }
-  return 0;
-}
-// Ranks of the communicator this context belongs to (1 without one): what a launcher prints to show that RCCL saw every GPU.
-int lumc_comm_count(const LumContext* ctx) {
-  if (!ctx || !ctx->comm) return 1;
-  int count = 1;
-  return ncclCommCount(ctx->comm, &count) == ncclSuccess ? count : 1;
-}
-
-// The assembled frame of this context (valid on the root after lumc_frame_assemble*): planar first moment [3][frame_pixels] and second moment.
-int lumc_frame_download(LumContext* ctx, uint32_t frame_pixels, float* first_moment, float* second_moment) {
-  if (!ctx || !ctx->d_frame || frame_pixels > ctx->frame_capacity) { if (ctx) ctx->error = "lumc_frame_download: no assembled frame"; return 1; }
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  HIP_TRY(ctx, hipDeviceSynchronize());
-  const size_t cap = ctx->frame_capacity;
-  if (first_moment)
-    for (int c = 0; c < 3; c++) HIP_TRY(ctx, hipMemcpy(first_moment + (size_t) c * frame_pixels, ctx->d_frame + (size_t) c * cap, sizeof(float) * frame_pixels, hipMemcpyDeviceToHost));
-  if (second_moment) HIP_TRY(ctx, hipMemcpy(second_moment, ctx->d_frame + 3 * cap, sizeof(float) * frame_pixels, hipMemcpyDeviceToHost));
-  return 0;
-}
-uint32_t lumc_frame_plane_stride(const LumContext* ctx) { return ctx ? ctx->frame_capacity : 0; }
-// The display entry points of this context (lumc_generate_result*, and through them the output chain) read the assembled full frame instead
-// of the context's own accumulators: what the display GPU of a tiled render shows.
-int lumc_use_assembled_frame(LumContext* ctx, int on) {
-  if (!ctx) return 1;
-  if (on && (!ctx->d_frame || !ctx->has_scene || ctx->frame_capacity != ctx->scene.width * ctx->scene.height)) { ctx->error = "lumc_use_assembled_frame: no assembled frame of this scene's size"; return 1; }
-  ctx->use_frame = on != 0;
-  return 0;
-}
 int lumc_device_name(int ordinal, char* out, size_t size) {
   if (!out || size == 0) return 1;
   hipDeviceProp_t prop;
@@ -2931,13 +2198,6 @@ int lumc_device_name(int ordinal, char* out, size_t size) {
   std::snprintf(out, size, "%s", prop.name);
   return 0;
 }
-
-int lumc_set_ray_sorting(LumContext* ctx, int mode) {
-  if (!ctx || mode < 0 || mode > 3) { if (ctx) ctx->error = "lumc_set_ray_sorting: 0 (queue order), 1 (closest-hit rays sorted), 2 (visibility rays too), 3 (path queue physically reordered)"; return 1; }
-  ctx->sort_mode = mode;
-  return 0;
-}
-int lumc_get_ray_sorting(const LumContext* ctx) { return ctx ? ctx->sort_mode : 0; }
 
 int lumc_set_flavour(LumContext* ctx, int flavour) {
   if (!ctx || flavour < 0 || flavour > 1) { if (ctx) ctx->error = "lumc_set_flavour: 0 (exact) or 1 (fast)"; return 1; }

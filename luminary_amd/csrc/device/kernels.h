@@ -20,10 +20,10 @@
 #include "dev_water.h"
 #include "dev_cloud_march.h"
 #include "dev_camera.h"
+#include "dev_wave.h"  // kBlock; the wave64 idioms: append, batch loop, visibility record, roulette
 
 LUM_NS_BEGIN
 
-constexpr int kBlock = 256;
 #ifndef LUM_SHADE_WAVES
 #define LUM_SHADE_WAVES 3  // minimum waves per SIMD the shade kernel is compiled for (register budget 512 / waves); round 4: 3 for every sky mode, ocean and flavour (2 before: procedural sky -3.6 % / -10 % of the kernel's time fast / exact, ocean scenes -6 %)
 #endif
@@ -31,12 +31,6 @@ constexpr int kBlock = 256;
 // The kernel has shrunk since: now they spill 26-30, 73-112 with an ocean, and every instantiation is faster at 3 waves; profiles/r04_ab_experiments.txt.)
 #ifndef LUM_CLOUD_WAVES
 #define LUM_CLOUD_WAVES 4  // k_clouds: waves per SIMD it is compiled for (2 / 3 / 4 measured: 1602 / 1369 / 1283 ms, profiles/r02_ab_experiments.txt)
-#endif
-#ifndef LUM_CLOUD_PERSISTENT
-#define LUM_CLOUD_PERSISTENT 1  // 0 (measurement only): one lane per path marches its three layers inside k_clouds, no list and no persistent lanes
-#endif
-#ifndef LUM_HIT_COMPACT
-#define LUM_HIT_COMPACT 1  // 0 (measurement only): k_ocean_shade / k_particle_shade shade what every round finds, partial waves and all
 #endif
 #ifndef LUM_FEATURE_WAVES
 #define LUM_FEATURE_WAVES 3  // the shading kernels of particles, ocean surface and volumes (without a bound k_particle_shade took 266 registers: one wave per SIMD)
@@ -991,8 +985,7 @@ __global__ __launch_bounds__(kBlock, LUM_FEATURE_WAVES) void k_sky_inscattering(
 __global__ __launch_bounds__(kBlock) void k_light_query(DeviceScene sc, PathQueue in, NeeQueue nee, ShadowQueue sq, uint32_t* ctrl, uint32_t depth_const,
                                                         uint64_t* counters) {
   const uint32_t n = ctrl[kCtlLightItems];
-  const uint32_t lane = threadIdx.x & 63;
-  const unsigned long long below = (1ull << lane) - 1ull;
+  const Wave w;
   RayStats st{0, 0, 0};
   uint32_t light_queries = 0;
   const uint32_t rounds = (n + gridDim.x * kBlock - 1) / (gridDim.x * kBlock);
@@ -1043,13 +1036,8 @@ __global__ __launch_bounds__(kBlock) void k_light_query(DeviceScene sc, PathQueu
     }
     const unsigned long long bw = __ballot(want);
     if (bw) {
-      uint32_t base = 0;
-      if (lane == 0) base = atomicAdd(ctrl + kCtlShadowItems, (uint32_t) __popcll(bw));
-      base = __builtin_amdgcn_readfirstlane(base);
-      if (want) {
-        const uint32_t j = base + (uint32_t) __popcll(bw & below);
-        sq.origin_dist[j] = s_origin; sq.dir_out[j] = s_dir; sq.ids[j] = s_ids;
-      }
+      const uint32_t base = w.reserve(ctrl + kCtlShadowItems, Wave::count(bw));
+      if (want) push_visibility(sq, base + w.rank(bw), s_origin, s_dir, s_ids);
     }
   }
 #pragma unroll
@@ -1250,12 +1238,12 @@ __global__ LUM_TRACE_BOUNDS void k_trace_particles(DeviceScene particle_tree, Pa
 __global__ __launch_bounds__(kBlock, LUM_FEATURE_WAVES) void k_particle_shade(DeviceScene sc, PathQueue in, PathQueue out, NeeQueue nee, ShadowQueue sq, uint32_t* ctrl, uint32_t depth_const) {
   const uint32_t n = ctrl[kCtlPaths];
   uint32_t* count_out = ctrl + kCtlStride + kCtlPaths;
-  const uint32_t lane = threadIdx.x & 63;
-  const unsigned long long below = (1ull << lane) - 1ull;
+  const Wave w;
   const bool lights_present = sc.light_tree_root != nullptr && sc.num_lights > 0;
   const bool sun_allowed = sc.sky_mode != kSkyConstantColor && sc.sky_lut_transmittance != nullptr && sc.sky_lut_multiscattering != nullptr;
   const Col albedo = particles_albedo(sc);
-  // Particle hits are a sparse subset of the queue: a wave collects their indices in LDS and shades them 64 at a time (as k_shade does with surface hits)
+  // Particle hits are a sparse subset of the queue: shaded 64 at a time. The loop of Wave::for_each_batch and, below, the roulette of dev_wave.h, written
+  // out: on the helpers the kernel came out with another register allocation, and no benchmark configuration has particles to time it with
   __shared__ uint32_t pending_hits[kBlock / 64][128];
   uint32_t* pending = pending_hits[threadIdx.x >> 6];
   uint32_t num_pending = 0;  // wave-uniform
@@ -1266,18 +1254,18 @@ __global__ __launch_bounds__(kBlock, LUM_FEATURE_WAVES) void k_particle_shade(De
       const uint32_t idx = (round * gridDim.x + blockIdx.x) * kBlock + threadIdx.x;
       const bool is_hit = idx < n && particle_is_hit(in.hit_id[idx].x);
       const unsigned long long bh = __ballot(is_hit);
-      if (is_hit) pending[num_pending + (uint32_t) __popcll(bh & below)] = idx;
-      num_pending += (uint32_t) __popcll(bh);
+      if (is_hit) pending[num_pending + w.rank(bh)] = idx;
+      num_pending += Wave::count(bh);
     }
-    if (num_pending < (LUM_HIT_COMPACT ? 64u : 1u) && !(input_done && num_pending > 0u)) {
+    if (num_pending < 64u && !(input_done && num_pending > 0u)) {
       if (input_done) break;
       continue;
     }
     __builtin_amdgcn_wave_barrier();
     const uint32_t take = min(num_pending, 64u);
     num_pending -= take;
-    const bool valid = lane < take;
-    const uint32_t i = valid ? pending[num_pending + lane] : 0u;
+    const bool valid = w.lane < take;
+    const uint32_t i = valid ? pending[num_pending + w.lane] : 0u;
     __builtin_amdgcn_wave_barrier();
     bool survive = false, want_geo = false, want_amb = false, want_sun = false, want_amb2 = false, want_sun2 = false;
     float4 n_o, n_d; uint4 n_aux, n_hid;
@@ -1368,7 +1356,7 @@ __global__ __launch_bounds__(kBlock, LUM_FEATURE_WAVES) void k_particle_shade(De
       if (sc.sky_mode != kSkyDefault) new_state &= ~kStAllowAmbient; else new_state |= kStAllowAmbient;
       Col record = record_unpack(U2{aux.x, aux.y}) * albedo;
       survive = true;
-      if ((state & kStDeltaPath) == 0) {  // directives.cuh:11-32
+      if ((state & kStDeltaPath) == 0) {  // roulette() of dev_wave.h
         const float value = importance(record);
         if (value < sc.cam_rr_threshold) {
           const float p = (value > 0.0f) ? fmaxf(value / sc.cam_rr_threshold, 1.0f / 8.0f) : 0.0f;
@@ -1386,57 +1374,29 @@ __global__ __launch_bounds__(kBlock, LUM_FEATURE_WAVES) void k_particle_shade(De
     }
     const unsigned long long ballot = __ballot(survive);
     if (ballot) {
-      uint32_t base = 0;
-      if (lane == 0) base = atomicAdd(count_out, (uint32_t) __popcll(ballot));
-      base = __builtin_amdgcn_readfirstlane(base);
+      const uint32_t base = w.reserve(count_out, Wave::count(ballot));
       if (survive) {
-        const uint32_t j = base + (uint32_t) __popcll(ballot & below);
+        const uint32_t j = base + w.rank(ballot);
         out.origin_t[j] = n_o; out.dir_slot[j] = n_d; out.aux[j] = n_aux; out.hit_id[j] = n_hid;
       }
     }
+    // one run of visibility rays for the three kinds: sampled light, ambient, sun
     const unsigned long long bg = __ballot(want_geo), ba = __ballot(want_amb), bn = __ballot(want_sun);
-    if (bg | ba | bn) {
-      const uint32_t ng = (uint32_t) __popcll(bg), na = (uint32_t) __popcll(ba);
-      uint32_t base = 0;
-      if (lane == 0) base = atomicAdd(ctrl + kCtlShadowItems, ng + na + (uint32_t) __popcll(bn));
-      base = __builtin_amdgcn_readfirstlane(base);
-      if (want_geo) {
-        const uint32_t j = base + (uint32_t) __popcll(bg & below);
-        sq.origin_dist[j] = make_float4(s_origin.x, s_origin.y, s_origin.z, s_geo_dir.w);
-        sq.dir_out[j] = make_float4(s_geo_dir.x, s_geo_dir.y, s_geo_dir.z, bitsf(i));
-        sq.ids[j] = s_geo_ids;
-      }
-      if (want_amb) {
-        const uint32_t j = base + ng + (uint32_t) __popcll(ba & below);
-        sq.origin_dist[j] = make_float4(s_origin.x, s_origin.y, s_origin.z, s_amb_dir.w);
-        sq.dir_out[j] = make_float4(s_amb_dir.x, s_amb_dir.y, s_amb_dir.z, bitsf(2u * sq.capacity + i));
-        sq.ids[j] = make_uint4(0xFFFFFFFFu, 0u, s_geo_ids.z, s_geo_ids.w);
-      }
-      if (want_sun) {
-        const uint32_t j = base + ng + na + (uint32_t) __popcll(bn & below);
-        sq.origin_dist[j] = make_float4(s_origin.x, s_origin.y, s_origin.z, s_sun_dir.w);
-        sq.dir_out[j] = make_float4(s_sun_dir.x, s_sun_dir.y, s_sun_dir.z, bitsf(3u * sq.capacity + i));
-        sq.ids[j] = make_uint4(0xFFFFFFFFu, 0u, s_geo_ids.z, s_geo_ids.w);
-      }
+    const uint32_t ng = Wave::count(bg), na = Wave::count(ba), nn = Wave::count(bn);
+    if (ng + na + nn) {
+      const uint32_t base = w.reserve(ctrl + kCtlShadowItems, ng + na + nn);
+      const uint4 open_ids = make_uint4(0xFFFFFFFFu, 0u, s_geo_ids.z, s_geo_ids.w);
+      if (want_geo) push_visibility(sq, base + w.rank(bg), s_origin, s_geo_dir, i, s_geo_ids);
+      if (want_amb) push_visibility(sq, base + ng + w.rank(ba), s_origin, s_amb_dir, 2u * sq.capacity + i, open_ids);
+      if (want_sun) push_visibility(sq, base + ng + na + w.rank(bn), s_origin, s_sun_dir, 3u * sq.capacity + i, open_ids);
     }
+    // ... and one for the second segments beyond the water surface
     const unsigned long long b2a = __ballot(want_amb2), b2s = __ballot(want_sun2);
-    if (b2a | b2s) {  // second segments beyond the water surface
-      const uint32_t na2 = (uint32_t) __popcll(b2a);
-      uint32_t base = 0;
-      if (lane == 0) base = atomicAdd(ctrl + kCtlShadowItems, na2 + (uint32_t) __popcll(b2s));
-      base = __builtin_amdgcn_readfirstlane(base);
-      if (want_amb2) {
-        const uint32_t j = base + (uint32_t) __popcll(b2a & below);
-        sq.origin_dist[j] = s_amb2_o;
-        sq.dir_out[j] = make_float4(s_amb2_d.x, s_amb2_d.y, s_amb2_d.z, bitsf(kShadowKindAmbient2 * sq.capacity + i));
-        sq.ids[j] = make_uint4(0xFFFFFFFFu, 0u, 0xFFFFFFFFu, 0u);
-      }
-      if (want_sun2) {
-        const uint32_t j = base + na2 + (uint32_t) __popcll(b2s & below);
-        sq.origin_dist[j] = s_sun2_o;
-        sq.dir_out[j] = make_float4(s_sun2_d.x, s_sun2_d.y, s_sun2_d.z, bitsf(kShadowKindSun2 * sq.capacity + i));
-        sq.ids[j] = make_uint4(0xFFFFFFFFu, 0u, 0xFFFFFFFFu, 0u);
-      }
+    const uint32_t na2 = Wave::count(b2a), ns2 = Wave::count(b2s);
+    if (na2 + ns2) {
+      const uint32_t base = w.reserve(ctrl + kCtlShadowItems, na2 + ns2);
+      if (want_amb2) push_second_segment(sq, base + w.rank(b2a), v3(s_amb2_o.x, s_amb2_o.y, s_amb2_o.z), v3(s_amb2_d.x, s_amb2_d.y, s_amb2_d.z), kShadowKindAmbient2 * sq.capacity + i);
+      if (want_sun2) push_second_segment(sq, base + na2 + w.rank(b2s), v3(s_sun2_o.x, s_sun2_o.y, s_sun2_o.z), v3(s_sun2_d.x, s_sun2_d.y, s_sun2_d.z), kShadowKindSun2 * sq.capacity + i);
     }
   }
 }
@@ -1463,34 +1423,12 @@ __global__ __launch_bounds__(kBlock) void k_trace_ocean(DeviceScene sc, PathQueu
 __global__ __launch_bounds__(kBlock, LUM_FEATURE_WAVES) void k_ocean_shade(DeviceScene sc, PathQueue in, PathQueue out, NeeQueue nee, ShadowQueue sq, uint32_t* ctrl, uint32_t depth_const) {
   const uint32_t n = ctrl[kCtlPaths];
   uint32_t* count_out = ctrl + kCtlStride + kCtlPaths;
-  const uint32_t lane = threadIdx.x & 63;
-  const unsigned long long below = (1ull << lane) - 1ull;
+  const Wave w;
   const bool lights_present = sc.light_tree_root != nullptr && sc.num_lights > 0;
   const bool sun_allowed = sc.sky_mode != kSkyConstantColor && sc.sky_lut_transmittance != nullptr && sc.sky_lut_multiscattering != nullptr;
-  // Water-surface hits are a sparse subset of the queue: a wave collects their indices in LDS and shades them 64 at a time (as k_shade does with surface hits)
+  // Water-surface hits are a sparse subset of the queue: shaded 64 at a time (Wave::for_each_batch)
   __shared__ uint32_t pending_hits[kBlock / 64][128];
-  uint32_t* pending = pending_hits[threadIdx.x >> 6];
-  uint32_t num_pending = 0;  // wave-uniform
-  const uint32_t rounds = (n + gridDim.x * kBlock - 1) / (gridDim.x * kBlock);
-  for (uint32_t round = 0;; round++) {
-    const bool input_done = round >= rounds;
-    if (!input_done) {
-      const uint32_t idx = (round * gridDim.x + blockIdx.x) * kBlock + threadIdx.x;
-      const bool is_hit = idx < n && in.hit_id[idx].x == kHitOcean;
-      const unsigned long long bh = __ballot(is_hit);
-      if (is_hit) pending[num_pending + (uint32_t) __popcll(bh & below)] = idx;
-      num_pending += (uint32_t) __popcll(bh);
-    }
-    if (num_pending < (LUM_HIT_COMPACT ? 64u : 1u) && !(input_done && num_pending > 0u)) {
-      if (input_done) break;
-      continue;
-    }
-    __builtin_amdgcn_wave_barrier();
-    const uint32_t take = min(num_pending, 64u);
-    num_pending -= take;
-    const bool valid = lane < take;
-    const uint32_t i = valid ? pending[num_pending + lane] : 0u;
-    __builtin_amdgcn_wave_barrier();
+  w.for_each_batch(n, pending_hits[threadIdx.x >> 6], [&](uint32_t idx) { return in.hit_id[idx].x == kHitOcean; }, [&](bool valid, uint32_t i) {
     bool survive = false, want_sun = false, want_lq = false;
     float4 n_o, n_d; uint4 n_aux, n_hid;
     float4 s_origin, s_sun_dir;
@@ -1535,15 +1473,7 @@ __global__ __launch_bounds__(kBlock, LUM_FEATURE_WAVES) void k_ocean_shade(Devic
       const float shift_length = 8.0f * kEps * (1.0f + sc.ocean_amplitude) * (1.0f + fabsf(sc.ocean_height));  // ocean_shift_vector, ocean_utils.cuh:519-523
       const V3 bounce_pos = g.position + g.normal * (bounce.transparent_pass ? -shift_length : shift_length);
       const uint32_t new_state = state & ~(kStCameraDirection | kStAllowEmission | kStUseIgnoreHandle);
-      survive = true;
-      if ((state & kStDeltaPath) == 0) {  // directives.cuh:11-32
-        const float value = importance(record);
-        if (value < sc.cam_rr_threshold) {
-          const float p = (value > 0.0f) ? fmaxf(value / sc.cam_rr_threshold, 1.0f / 8.0f) : 0.0f;
-          if (smp.next1(kRndRussianRoulette) > p) survive = false;
-          else record = record * (1.0f / p);
-        }
-      }
+      survive = roulette(sc, state, smp, record);
       if (survive) {
         uint32_t medium = aux.z, volumes = hid.w;
         if (bounce.transparent_pass) {
@@ -1558,36 +1488,10 @@ __global__ __launch_bounds__(kBlock, LUM_FEATURE_WAVES) void k_ocean_shade(Devic
         n_hid = make_uint4(0u, 0u, hid.z, volumes);
       }
     }
-    const unsigned long long ballot = __ballot(survive);
-    if (ballot) {
-      uint32_t base = 0;
-      if (lane == 0) base = atomicAdd(count_out, (uint32_t) __popcll(ballot));
-      base = __builtin_amdgcn_readfirstlane(base);
-      if (survive) {
-        const uint32_t j = base + (uint32_t) __popcll(ballot & below);
-        out.origin_t[j] = n_o; out.dir_slot[j] = n_d; out.aux[j] = n_aux; out.hit_id[j] = n_hid;
-      }
-    }
-    const unsigned long long bn = __ballot(want_sun);
-    if (bn) {
-      uint32_t base = 0;
-      if (lane == 0) base = atomicAdd(ctrl + kCtlShadowItems, (uint32_t) __popcll(bn));
-      base = __builtin_amdgcn_readfirstlane(base);
-      if (want_sun) {
-        const uint32_t j = base + (uint32_t) __popcll(bn & below);
-        sq.origin_dist[j] = make_float4(s_origin.x, s_origin.y, s_origin.z, s_sun_dir.w);
-        sq.dir_out[j] = make_float4(s_sun_dir.x, s_sun_dir.y, s_sun_dir.z, bitsf(3u * sq.capacity + i));
-        sq.ids[j] = make_uint4(0xFFFFFFFFu, 0u, kHitOcean, 0u);
-      }
-    }
-    const unsigned long long bl = __ballot(want_lq);
-    if (bl) {
-      uint32_t base = 0;
-      if (lane == 0) base = atomicAdd(ctrl + kCtlLightItems, (uint32_t) __popcll(bl));
-      base = __builtin_amdgcn_readfirstlane(base);
-      if (want_lq) sq.light_items[base + (uint32_t) __popcll(bl & below)] = i;
-    }
-  }
+    w.append(survive, count_out, [&](uint32_t j) { out.origin_t[j] = n_o; out.dir_slot[j] = n_d; out.aux[j] = n_aux; out.hit_id[j] = n_hid; });
+    w.append(want_sun, ctrl + kCtlShadowItems, [&](uint32_t j) { push_visibility(sq, j, s_origin, s_sun_dir, 3u * sq.capacity + i, make_uint4(0xFFFFFFFFu, 0u, kHitOcean, 0u)); });
+    w.append(want_lq, ctrl + kCtlLightItems, [&](uint32_t j) { sq.light_items[j] = i; });
+  });
 }
 
 // ---- clouds ----
@@ -1601,8 +1505,7 @@ __global__ __launch_bounds__(kBlock, LUM_FEATURE_WAVES) void k_ocean_shade(Devic
 __global__ __launch_bounds__(kBlock) void k_clouds_list(DeviceScene sc, PathQueue in, CloudQueue cq, uint32_t* ctrl) {
   const uint32_t n = ctrl[kCtlPaths];
   const SkyView sky = sky_view(sc);
-  const uint32_t lane = threadIdx.x & 63;
-  const unsigned long long below = (1ull << lane) - 1ull;
+  const Wave w;
   const uint32_t rounds = (n + gridDim.x * kBlock - 1) / (gridDim.x * kBlock);
   // one list reservation per 8 rounds of a wave (three per round, one per layer, kept the counter's atomic unit busier than the kernel's own work)
   constexpr uint32_t kListRounds = 8;
@@ -1622,18 +1525,16 @@ __global__ __launch_bounds__(kBlock) void k_clouds_list(DeviceScene sc, PathQueu
     if (slot + 1u == kListRounds || round + 1u == rounds) {
       uint32_t total = 0;
 #pragma unroll
-      for (uint32_t b = 0; b < 3u * kListRounds; b++) total += (uint32_t) __popcll(__ballot((masks >> b) & 1u));
+      for (uint32_t b = 0; b < 3u * kListRounds; b++) total += Wave::count(__ballot((masks >> b) & 1u));
       if (total) {
-        uint32_t base = 0;
-        if (lane == 0) base = atomicAdd(ctrl + kCtlCloudItems, total);
-        base = __builtin_amdgcn_readfirstlane(base);
+        uint32_t base = w.reserve(ctrl + kCtlCloudItems, total);
         const uint32_t group_start = round - slot;
 #pragma unroll
         for (uint32_t b = 0; b < 3u * kListRounds; b++) {
           const bool want = (masks >> b) & 1u;
           const unsigned long long bal = __ballot(want);
-          if (want) cq.items[base + (uint32_t) __popcll(bal & below)] = (((group_start + b / 3u) * gridDim.x + blockIdx.x) * kBlock + threadIdx.x) | ((b % 3u) << 30);
-          base += (uint32_t) __popcll(bal);
+          if (want) cq.items[base + w.rank(bal)] = (((group_start + b / 3u) * gridDim.x + blockIdx.x) * kBlock + threadIdx.x) | ((b % 3u) << 30);
+          base += Wave::count(bal);
         }
       }
       masks = 0;
@@ -1645,8 +1546,7 @@ __global__ __launch_bounds__(kBlock, LUM_CLOUD_WAVES) void k_clouds_march(Device
   const uint32_t n = ctrl[kCtlCloudItems];
   uint32_t* cursor = ctrl + kCtlCloudCursor;
   const SkyView sky = sky_view(sc);
-  const uint32_t lane = threadIdx.x & 63;
-  const unsigned long long below = (1ull << lane) - 1ull;
+  const Wave w;
   CloudMarch m;
   uint32_t slot = 0;      // where this lane's result goes
   bool active = false;
@@ -1657,16 +1557,14 @@ __global__ __launch_bounds__(kBlock, LUM_CLOUD_WAVES) void k_clouds_march(Device
     unsigned long long idle = __ballot(!active);
     while (idle != 0ull && more) {
       if (chunk_next >= chunk_end) {
-        uint32_t base = 0;
-        if (lane == 0) base = atomicAdd(cursor, 64u);
-        base = __builtin_amdgcn_readfirstlane(base);
+        const uint32_t base = w.reserve(cursor, 64u);
         chunk_next = base;
         chunk_end = min(base + 64u, n);
         more = base < n;
         if (!more) break;
       }
-      const uint32_t avail = chunk_end - chunk_next, want = (uint32_t) __popcll(idle);
-      const uint32_t rank = (uint32_t) __popcll(idle & below);
+      const uint32_t avail = chunk_end - chunk_next, want = Wave::count(idle);
+      const uint32_t rank = w.rank(idle);
       if (!active && rank < avail) {
         const uint32_t item = cq.items[chunk_next + rank];
         const uint32_t i = item & 0x3FFFFFFFu;
@@ -1704,7 +1602,8 @@ __global__ __launch_bounds__(kBlock, LUM_CLOUD_WAVES) void k_clouds(DeviceScene 
   const uint32_t lane = threadIdx.x & 63;
   const unsigned long long below = (1ull << lane) - 1ull;
   // Only the paths whose ray reached a layer have something to compose (with atmosphere_scattering: an aerial-perspective march per layer entered);
-  // a wave collects them in LDS and handles them 64 at a time.
+  // a wave collects them in LDS and handles them 64 at a time. (The loop is dev_wave.h's Wave::for_each_batch written out: on the helper this kernel measured
+  // 0.1-0.7 % slower than before, profiles/wave_helpers_feature_cost.txt.)
   __shared__ uint32_t pending_marches[kBlock / 64][128];
   uint32_t* pending = pending_marches[threadIdx.x >> 6];
   uint32_t num_pending = 0;  // wave-uniform
@@ -1748,14 +1647,10 @@ __global__ __launch_bounds__(kBlock, LUM_CLOUD_WAVES) void k_clouds(DeviceScene 
       float cloud_transmittance = 1.0f;
       const float cloud_offset = clouds_render_with(sc, sky, smp, world_to_sky(sky, origin), ray, o4.w * 0.001f, color, record, cloud_transmittance,
                                                     [&](int l, float start, float dist) {
-#if LUM_CLOUD_PERSISTENT
                                                       (void) dist;
                                                       if (start == kFltMax) return CloudResult{splat(0.0f), 1.0f, start};  // not reached: clouds_compute's empty result
                                                       const float4 r = cq.result[(uint32_t) l * cq.capacity + i];
                                                       return CloudResult{col(r.x, r.y, r.z), r.w, cq.hit_dist[(uint32_t) l * cq.capacity + i]};
-#else
-                                                      return clouds_compute(sc, sky, smp, world_to_sky(sky, origin), ray, start, dist, l);
-#endif
                                                     });
       if (sc.cloud_atmosphere_scattering && cloud_offset != kFltMax && cloud_offset > 0.0f) {
         const float cloud_world_offset = cloud_offset * 1000.0f;
@@ -1862,46 +1757,22 @@ __global__ __launch_bounds__(256) void k_sky_hdri(DeviceScene sc, float ox, floa
 // ray. The visibility rays go through the ShadowQueue (17 kinds per path), k_volume_resolve sums up (optix_kernel_shadow_volume.cu:13-98).
 __global__ __launch_bounds__(kBlock, LUM_VOLUME_WAVES) void k_volume_inscatter(DeviceScene sc, PathQueue in, VolumeQueue vq, ShadowQueue sq, uint32_t* ctrl, uint32_t depth_const) {
   const uint32_t n = ctrl[kCtlPaths];
-  const uint32_t lane = threadIdx.x & 63;
-  const unsigned long long below = (1ull << lane) - 1ull;
+  const Wave w;
   const bool lights_present = sc.light_tree_root != nullptr && sc.num_lights > 0;
   const bool sun_allowed = sc.sky_mode != kSkyConstantColor && sc.sky_lut_transmittance != nullptr && sc.sky_lut_multiscattering != nullptr;
-#ifndef LUM_INSCATTER_COMPACT
-#define LUM_INSCATTER_COMPACT 1  // 0 (measurement only): every round works on what it finds, partial waves and all
-#endif
-  // With an ocean only the paths inside a volume have work here (a fog holds every path): their indices are collected per wave in LDS and handled 64 at a
-  // time, the others get their empty records right away.
+  // With an ocean only the paths inside a volume have work here (a fog holds every path): they are handled 64 at a time (Wave::for_each_batch), the
+  // others get their empty records right away.
   __shared__ uint32_t pending_paths[kBlock / 64][128];
-  uint32_t* pending = pending_paths[threadIdx.x >> 6];
-  uint32_t num_pending = 0;  // wave-uniform
-  const uint32_t rounds = (n + gridDim.x * kBlock - 1) / (gridDim.x * kBlock);
-  for (uint32_t round = 0;; round++) {
-    const bool input_done = round >= rounds;
-    if (!input_done) {
-      const uint32_t idx = (round * gridDim.x + blockIdx.x) * kBlock + threadIdx.x;
-      bool in_volume = false;
-      if (idx < n) {
-        in_volume = volume_stack_peek(in.hit_id[idx].w, false) != kVolumeNone;
-        if (!in_volume) {
-          vq.bridge[idx] = make_float4(0.0f, 0.0f, 0.0f, bitsf(0u));
-          vq.sky[idx] = make_uint4(0u, 0u, 0u, 0u);
-          vq.weight[idx] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        }
-      }
-      const unsigned long long bv = __ballot(in_volume);
-      if (in_volume) pending[num_pending + (uint32_t) __popcll(bv & below)] = idx;
-      num_pending += (uint32_t) __popcll(bv);
+  auto in_a_volume = [&](uint32_t idx) {
+    const bool in_volume = volume_stack_peek(in.hit_id[idx].w, false) != kVolumeNone;
+    if (!in_volume) {
+      vq.bridge[idx] = make_float4(0.0f, 0.0f, 0.0f, bitsf(0u));
+      vq.sky[idx] = make_uint4(0u, 0u, 0u, 0u);
+      vq.weight[idx] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     }
-    if (num_pending < (LUM_INSCATTER_COMPACT ? 64u : 1u) && !(input_done && num_pending > 0u)) {
-      if (input_done) break;
-      continue;
-    }
-    __builtin_amdgcn_wave_barrier();
-    const uint32_t take = min(num_pending, 64u);
-    num_pending -= take;
-    const bool valid = lane < take;
-    const uint32_t i = valid ? pending[num_pending + lane] : 0u;
-    __builtin_amdgcn_wave_barrier();
+    return in_volume;
+  };
+  w.for_each_batch(n, pending_paths[threadIdx.x >> 6], in_a_volume, [&](bool valid, uint32_t i) {
     uint32_t segments = 0;
     BridgeWalk walk;
     bool want_sun = false, want_amb = false, want_sun2 = false, want_amb2 = false;
@@ -1929,10 +1800,10 @@ __global__ __launch_bounds__(kBlock, LUM_VOLUME_WAVES) void k_volume_inscatter(D
           bridge = make_float4(bs.color.r, bs.color.g, bs.color.b, bitsf(segments));
         }
       }
-      Col w = splat(0.0f);
+      Col vertex_weight = splat(0.0f);
       uint4 sky_words = make_uint4(0u, 0u, 0u, 0u);
       if (top_volume != kVolumeNone) {
-        w = volume_sky_initial_vertex(ctx, smp);  // the vertex the sun and the ambient sample start from
+        vertex_weight = volume_sky_initial_vertex(ctx, smp);  // the vertex the sun and the ambient sample start from
         sky_origin = make_float4(ctx.position.x, ctx.position.y, ctx.position.z, kFltMax);
         if (sun_allowed) {
           Col lc; V3 dir;
@@ -1970,58 +1841,39 @@ __global__ __launch_bounds__(kBlock, LUM_VOLUME_WAVES) void k_volume_inscatter(D
       }
       vq.bridge[i] = bridge;
       vq.sky[i] = sky_words;
-      vq.weight[i] = make_float4(w.r, w.g, w.b, 0.0f);
+      vq.weight[i] = make_float4(vertex_weight.r, vertex_weight.g, vertex_weight.b, 0.0f);
     }
     // Visibility rays: ONE reservation per batch for everything its lanes ask for - a lane's bridge segments (1..15), sun, ambient and their second
-    // segments - and every lane writes its own run. (One atomic per kind and bridge segment, as at first, made the camera rays' pass - every lane a
-    // bridge - wait for up to 17 same-address atomics per batch: they, not the arithmetic, were most of its time; profiles/r02_ab_experiments.txt.)
+    // segments - and every lane writes its own run: an inclusive scan instead of Wave::append's ranks, which count one entry per lane and kind. (One atomic
+    // per kind and bridge segment, as at first, made the camera rays' pass - every lane a bridge - wait for up to 17 same-address atomics per batch: they,
+    // not the arithmetic, were most of its time; profiles/r02_ab_experiments.txt.)
     {
       const uint32_t mine = segments + (want_sun ? 1u : 0u) + (want_amb ? 1u : 0u) + (want_sun2 ? 1u : 0u) + (want_amb2 ? 1u : 0u);
       uint32_t prefix = mine;  // inclusive scan over the wave
 #pragma unroll
       for (int off = 1; off < 64; off <<= 1) {
         const uint32_t v = __shfl_up(prefix, off);
-        if ((int) lane >= off) prefix += v;
+        if ((int) w.lane >= off) prefix += v;
       }
       const uint32_t total = __shfl(prefix, 63);
       if (total) {
         uint32_t base = 0;
-        if (lane == 0) base = atomicAdd(ctrl + kCtlVolumeShadowItems, total);
+        if (w.lane == 0) base = atomicAdd(ctrl + kCtlVolumeShadowItems, total);
         base = __builtin_amdgcn_readfirstlane(base);
         uint32_t j = base + prefix - mine;
+        const uint4 open_ray = make_uint4(0xFFFFFFFFu, 0u, 0xFFFFFFFFu, 0u);
+        const V3 vertex = v3(sky_origin.x, sky_origin.y, sky_origin.z);
         for (uint32_t k = 0; k < segments; k++) {
-          sq.origin_dist[j] = make_float4(walk.vertex.x, walk.vertex.y, walk.vertex.z, walk.dist);
-          sq.dir_out[j] = make_float4(walk.dir.x, walk.dir.y, walk.dir.z, bitsf(k * sq.capacity + i));
-          sq.ids[j] = make_uint4(walk.light.x, walk.light.y, 0xFFFFFFFFu, 0u);  // the segment that reaches the light leaves that light out
-          j++;
+          push_visibility(sq, j++, walk.vertex, walk.dir, walk.dist, k * sq.capacity + i, make_uint4(walk.light.x, walk.light.y, 0xFFFFFFFFu, 0u));  // the segment that reaches the light leaves that light out
           if (k + 1 < segments) bridge_walk_next(walk, smp, k + 1);
         }
-        if (want_sun) {
-          sq.origin_dist[j] = make_float4(sky_origin.x, sky_origin.y, sky_origin.z, sun_limit);
-          sq.dir_out[j] = make_float4(sun_dir.x, sun_dir.y, sun_dir.z, bitsf(kVolumeKindSun * sq.capacity + i));
-          sq.ids[j] = make_uint4(0xFFFFFFFFu, 0u, 0xFFFFFFFFu, 0u);
-          j++;
-        }
-        if (want_amb) {
-          sq.origin_dist[j] = make_float4(sky_origin.x, sky_origin.y, sky_origin.z, amb_limit);
-          sq.dir_out[j] = make_float4(amb_dir.x, amb_dir.y, amb_dir.z, bitsf(kVolumeKindAmbient * sq.capacity + i));
-          sq.ids[j] = make_uint4(0xFFFFFFFFu, 0u, 0xFFFFFFFFu, 0u);
-          j++;
-        }
-        if (want_sun2) {  // second segments beyond the water surface
-          sq.origin_dist[j] = make_float4(sun2_o.x, sun2_o.y, sun2_o.z, kFltMax);
-          sq.dir_out[j] = make_float4(sun2_d.x, sun2_d.y, sun2_d.z, bitsf(kVolumeKindSun2 * sq.capacity + i));
-          sq.ids[j] = make_uint4(0xFFFFFFFFu, 0u, 0xFFFFFFFFu, 0u);
-          j++;
-        }
-        if (want_amb2) {
-          sq.origin_dist[j] = make_float4(amb2_o.x, amb2_o.y, amb2_o.z, kFltMax);
-          sq.dir_out[j] = make_float4(amb2_d.x, amb2_d.y, amb2_d.z, bitsf(kVolumeKindAmbient2 * sq.capacity + i));
-          sq.ids[j] = make_uint4(0xFFFFFFFFu, 0u, 0xFFFFFFFFu, 0u);
-        }
+        if (want_sun) push_visibility(sq, j++, vertex, sun_dir, sun_limit, kVolumeKindSun * sq.capacity + i, open_ray);
+        if (want_amb) push_visibility(sq, j++, vertex, amb_dir, amb_limit, kVolumeKindAmbient * sq.capacity + i, open_ray);
+        if (want_sun2) push_second_segment(sq, j++, sun2_o, sun2_d, kVolumeKindSun2 * sq.capacity + i);  // second segments beyond the water surface
+        if (want_amb2) push_second_segment(sq, j, amb2_o, amb2_d, kVolumeKindAmbient2 * sq.capacity + i);
       }
     }
-  }
+  });
 }
 
 // optix_kernel_shadow_volume.cu:38-97: bridge colour x the visibilities of its segments, + (sun + ambient) x the weight of their vertex, x throughput
@@ -2061,8 +1913,7 @@ __global__ __launch_bounds__(kBlock) void k_volume_resolve(DeviceScene sc, PathQ
 // non-procedural sky modes a ray that left the scene adds the sky here and ends ("sky fast path").
 __global__ __launch_bounds__(kBlock) void k_volume_events(DeviceScene sc, PathQueue in, VolumeQueue vq, float4* results, uint32_t* ctrl, uint32_t depth_const) {
   const uint32_t n = ctrl[kCtlPaths];
-  const uint32_t lane = threadIdx.x & 63;
-  const unsigned long long below = (1ull << lane) - 1ull;
+  const Wave w;
   const uint32_t rounds = (n + gridDim.x * kBlock - 1) / (gridDim.x * kBlock);
   // The scattering events are listed for k_volume_bounce with one reservation per 8 rounds of a wave (one per round saturated the counter's atomic unit)
   constexpr uint32_t kListRounds = 8;
@@ -2119,16 +1970,14 @@ __global__ __launch_bounds__(kBlock) void k_volume_events(DeviceScene sc, PathQu
       unsigned long long b[kListRounds];
       uint32_t total = 0;
 #pragma unroll
-      for (uint32_t r = 0; r < kListRounds; r++) { b[r] = __ballot((scattered_mask >> r) & 1u); total += (uint32_t) __popcll(b[r]); }
+      for (uint32_t r = 0; r < kListRounds; r++) { b[r] = __ballot((scattered_mask >> r) & 1u); total += Wave::count(b[r]); }
       if (total) {
-        uint32_t base = 0;
-        if (lane == 0) base = atomicAdd(ctrl + kCtlVolumeItems, total);
-        base = __builtin_amdgcn_readfirstlane(base);
+        uint32_t base = w.reserve(ctrl + kCtlVolumeItems, total);
         const uint32_t group_start = round - slot;
 #pragma unroll
         for (uint32_t r = 0; r < kListRounds; r++) {
-          if ((scattered_mask >> r) & 1u) vq.items[base + (uint32_t) __popcll(b[r] & below)] = ((group_start + r) * gridDim.x + blockIdx.x) * kBlock + threadIdx.x;
-          base += (uint32_t) __popcll(b[r]);
+          if ((scattered_mask >> r) & 1u) vq.items[base + w.rank(b[r])] = ((group_start + r) * gridDim.x + blockIdx.x) * kBlock + threadIdx.x;
+          base += Wave::count(b[r]);
         }
       }
       scattered_mask = 0;

@@ -1146,10 +1146,8 @@ static void media_passes(LumContext* ctx, hipStream_t stream, const DeviceScene&
   }
   if (sc.cloud_active && sc.sky_mode == kSkyDefault && sc.cloud_noise_shape) {  // device_manager.c:474, device_renderer.c:78-82
     Launch l(ctx, stream, LUMC_KERNEL_SKY);
-#if LUM_CLOUD_PERSISTENT
     wf.clouds_list(grid_for(N), stream, sc, d.cur, ctx->cloud, d.ctrl);
     wf.clouds_march(ctx->trace_blocks * 4u, stream, sc, d.cur, ctx->cloud, d.ctrl, d.depth_const);  // persistent: 4 workgroups of 256 per CU
-#endif
     wf.clouds(grid_for(N), stream, sc, d.cur, ctx->cloud, ctx->d_results, (const uint32_t*) d.ctrl, d.depth_const);
   }
   if (sc.sky_aerial_perspective && sc.sky_mode != kSkyConstantColor) {  // device_manager.c:475, device_renderer.c:84-88

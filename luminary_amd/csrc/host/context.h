@@ -1,6 +1,7 @@
 // The host layer's context and the helpers its translation units share. Private to csrc/host: core.hip (the exact flavour's device code, scene upload,
-// render schedule), ray_sort.hip, multi_gpu.hip. Everything here is a plain layout or host code; kernels.h is not included, so a unit that includes this
-// header gets none of the flavoured kernels (their device symbols - the sampler's seed table, the phase counters - exist per translation unit).
+// render schedule), ray_sort.hip, multi_gpu.hip. The context owns its device memory through DeviceBuffer members (device_buffer.h): deleting it frees them.
+// Its other pointers - DeviceScene, the queues, d_results, d_ended, d_fused - are views into those buffers. kernels.h is not included, so a unit that includes
+// this header gets none of the flavoured kernels (their device symbols - the sampler's seed table, the phase counters - exist per translation unit).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -14,6 +15,7 @@
 #include "../device/dev_scene.h"
 #include "../device/wavefront_table.h"
 #include "bvh_build.h"
+#include "device_buffer.h"
 
 using namespace lum;
 
@@ -32,25 +34,24 @@ struct LumContext {
   DeviceLens lens{};          // the physical camera's lens, an argument of those kernels
   // device allocations of the scene by the part of it they belong to (lumc_scene_update frees and rebuilds a part at a time)
   enum AllocGroup { kGrpMesh = 0, kGrpInst, kGrpMat, kGrpLight, kGrpTex, kGrpConst, kGrpPart, kGrpOnce, kGrpCount };
-  std::vector<void*> scene_allocs[kGrpCount];
+  std::vector<DeviceBuffer<char>> scene_allocs[kGrpCount];
   // what a partial update needs again: the per-mesh trees (node indices relative to the mesh, leaf ranges relative to its first triangle) and boxes
   std::vector<std::shared_ptr<const MeshTree>> mesh_bvh;
   std::vector<Aabb> mesh_box;
   std::vector<uint32_t> sky_lut_key;  // the sky parameters the two sky tables were generated from
-  float* d_bridge_lut = nullptr;      // the bridge sampler's vertex-count table (context-owned: scene.bridge_lut points here while bridges are possible)
+  DeviceBuffer<float> d_bridge_lut;   // the bridge sampler's vertex-count table (context-owned: scene.bridge_lut points here while bridges are possible)
   std::vector<float> bridge_lut_host; // its content, to notice a caller that hands over another table
-  float4* d_sky_lut[2] = {nullptr, nullptr};
+  DeviceBuffer<float4> d_sky_lut[2];
   DeviceScene scene{};
   bool has_scene = false;
   uint64_t bvh_stats[4] = {0, 0, 0, 0};
   int ambient_reuse = -1;         // -1 by flavour (fast: on), 0 off, 1 on (lumc_set_ambient_reuse; LUM_AMBIENT_REUSE)
   uint32_t shade_grid_rounds = 2;  // k_shade's grid as a multiple of its resident set (0: the common 2048-workgroup cap); LUM_SHADE_GRID
   int fused_resolve = 1;          // with the fast flavour's ambient reuse: k_shade resolves the previous depth's vertices itself (lumc_set_fused_resolve; LUM_FUSED_RESOLVE)
-  void* fused_block = nullptr;    // what that needs beyond the usual work buffers: a third path queue, the parent words, a second set of NEE records, the fallback rays' items
+  DeviceBuffer<char> fused_block; // what that needs beyond the usual work buffers: a third path queue, the parent words, a second set of NEE records, the fallback rays' items
   bool fused_records_stale = false;  // a queue's planes changed places (ray-sorting mode 3) since the records were written
   uint32_t fused_capacity = 0, fused_refused_capacity = 0;  // (the capacity its allocation last failed for: not tried again)
-  uint2* d_sobol = nullptr;         // the pass's Sobol / Owen table (dev_sampler.h LUM_SOBOL_TABLE; wavefront_depths fills it)
-  size_t sobol_entries = 0;
+  DeviceBuffer<uint2> d_sobol;      // the pass's Sobol / Owen table (dev_sampler.h LUM_SOBOL_TABLE; wavefront_depths fills it)
   int sobol_table = 1;              // LUM_SOBOL_TABLE_RT=0: the sampler hashes every number itself
   uint32_t* d_ended[2] = {nullptr, nullptr};  // a depth's vertices that no entry continues, by the depth's parity (k_shade lists them; the next depth's k_shade resolves them, or k_resolve_ended)
   // ... the next depth's k_shade (1) or k_resolve_ended after the depth's visibility pass (0; LUM_FUSED_ENDED=0)
@@ -65,16 +66,15 @@ struct LumContext {
   uint32_t lds_nodes = 0;         // nodes of the tree top every ray-kernel workgroup stages in LDS
   uint32_t trace_blocks = 256;    // persistent grid of the ray kernels
   // LUTs owned by the context when generated here
-  uint16_t* d_luts[4] = {nullptr, nullptr, nullptr, nullptr};
+  DeviceBuffer<uint16_t> d_luts[4];
   // pixels and accumulators
-  uint32_t* d_pixels = nullptr;
+  DeviceBuffer<uint32_t> d_pixels;
   uint32_t num_pixels = 0;
   uint64_t pixels_hash = 0;       // of the pixel list in its order (lumc_set_pixels): the tile gather checks that the set IS the share of the deal it assumes
-  float* d_first_moment = nullptr;
-  float* d_second_moment = nullptr;
+  DeviceBuffer<float> d_first_moment, d_second_moment;
   // work buffers (sized for capacity paths)
   uint32_t capacity = 0;
-  void* work_block = nullptr;
+  DeviceBuffer<char> work_block;
   PathQueue queue[3]{};           // [2]: only with the fused resolve (ensure_fused)
   NeeQueue nee{};
   ShadowQueue shadow{};
@@ -83,11 +83,9 @@ struct LumContext {
   CloudQueue cloud{};             // the cloud marches of a depth (kernels.h k_clouds_*); allocated with the work block when clouds are marched
   uint32_t work_shadow_kinds = 0; // visibility-ray kinds per path the work block was sized for (4, or 17 with fog)
   float4* d_results = nullptr;
-  float* d_frame_output = nullptr;  // display-referred planes of the output chain [3 * W * H]
-  uint32_t frame_output_pixels = 0;
-  uint16_t* d_bluenoise_1d = nullptr;
-  uint32_t* d_argb8 = nullptr;
-  uint32_t argb8_pixels = 0;
+  DeviceBuffer<float> d_frame_output;  // display-referred planes of the output chain [3 * W * H]
+  DeviceBuffer<uint16_t> d_bluenoise_1d;
+  DeviceBuffer<uint32_t> d_argb8;
   // adaptive sampling (dev_adaptive.h)
   struct Adaptive {
     bool active = false;
@@ -95,70 +93,59 @@ struct LumContext {
     uint32_t blocks_x = 0, blocks_y = 0, num_blocks = 0;
     uint32_t stage_id = 0;
     uint32_t executions[kAdaptiveStages + 1] = {0, 0, 0, 0, 0};
-    uint32_t* d_stage_counts = nullptr;
-    uint32_t* d_block_tasks = nullptr;
-    uint32_t* d_block_task_end = nullptr;
-    float* d_block_variance = nullptr;
-    float* d_partial = nullptr;   // chunk sums, then the total in the last element
-    void* d_scan_temp = nullptr;
+    DeviceBuffer<uint32_t> d_stage_counts, d_block_tasks, d_block_task_end;
+    DeviceBuffer<float> d_block_variance;
+    DeviceBuffer<float> d_partial;  // chunk sums, then the total in the last element
+    DeviceBuffer<char> d_scan_temp;
     size_t scan_temp_bytes = 0;
     std::vector<uint32_t> task_end;  // host copy of d_block_task_end: passes are cut at block boundaries
     float variance_total = 0.0f;
-    uint8_t* d_block_mask = nullptr; // image-tile partition over GPUs: blocks this context renders (nullptr = all)
+    DeviceBuffer<uint8_t> d_block_mask;  // image-tile partition over GPUs: blocks this context renders (empty = all)
     bool build_pending = false;      // partitioned: a stage is due and waits for the block variances of all ranks
   } adaptive;
-  uint32_t* d_cloud_noise[3] = {nullptr, nullptr, nullptr};  // the clouds' shape / detail / weather textures generated here (kept across scene uploads)
+  DeviceBuffer<uint32_t> d_cloud_noise[3];  // the clouds' shape / detail / weather textures generated here (kept across scene uploads)
   bool cloud_noise_static = false;  // shape and detail do not depend on the seed
   uint32_t cloud_noise_seed = 0;
   bool cloud_noise_weather_valid = false;
-  float4* d_sky_hdri = nullptr;     // baked sky (lumc_sky_hdri_build): dim x dim equirectangular, rgb + 0
+  DeviceBuffer<float4> d_sky_hdri;  // baked sky (lumc_sky_hdri_build): dim x dim equirectangular, rgb + 0
   uint32_t sky_hdri_dim = 0;
-  std::vector<float*> bloom_mips;  // mip chain of lumc_post_bloom, level i of (width >> (i + 1)) x (height >> (i + 1))
-  uint32_t bloom_width = 0, bloom_height = 0;
-  uint32_t* d_undersampling_pixels = nullptr;  // pixel list of the current undersampling iteration (lumc_render_undersampled)
-  uint32_t undersampling_capacity = 0;
+  std::vector<DeviceBuffer<float>> bloom_mips;  // mip chain of lumc_post_bloom, level i of (width >> (i + 1)) x (height >> (i + 1))
+  uint32_t bloom_width = 0, bloom_height = 0;  // what the chain was allocated for
+  DeviceBuffer<uint32_t> d_undersampling_pixels;  // pixel list of the current undersampling iteration (lumc_render_undersampled)
   std::vector<uint32_t> sky_hdri_key;  // what the bake was made from (sky parameters, origin, dim, samples): an unchanged key reuses it
-  float* d_frame_result = nullptr;  // mean radiance planes of lumc_generate_result [3 * W * H]
-  uint32_t frame_result_pixels = 0;
+  DeviceBuffer<float> d_frame_result;  // mean radiance planes of lumc_generate_result [3 * W * H]
   // denoiser (dev_denoise.h): the guide planes (9 while they are summed, then albedo[3] normal[3] depth), the filter's records (A twice: ping-pong, B once)
-  float* d_guides = nullptr;
-  uint32_t guide_pixels = 0;
+  DeviceBuffer<float> d_guides;
   bool guides_valid = false;
-  void* d_denoise_rec[3] = {nullptr, nullptr, nullptr};
-  uint32_t denoise_pixels = 0;
+  DeviceBuffer<float4> d_denoise_rec[3];  // one 16-byte record per pixel each
   int denoise_lds = 1;              // a-trous steps 1 and 2 stage their tile in LDS (lumc_set_denoise_form; LUM_DENOISE_LDS=0|1)
   // ray ordering (N1): keys + permutation, double-buffered for hipcub's radix sort; sized for the visibility items (4 per path)
-  struct RaySort {  // owned by ray_sort.hip (free_sort)
+  struct RaySort {  // ray_sort.hip
     int mode = 0;              // 0 queue order, 1 closest-hit rays of depth >= 1 traced through a sorted permutation, 2 visibility rays too, 3 the path queue physically reordered (lumc_set_ray_sorting, LUM_SORT)
     PathQueue queue{};         // mode 3: the four state planes the reorder pass writes; swapped with the queue's own afterwards
-    void* planes[4] = {nullptr, nullptr, nullptr, nullptr};  // what was allocated for them (after swaps queue may point into the work block)
-    uint32_t queue_capacity = 0;
+    DeviceBuffer<float4> planes[4];  // what was allocated for them, one 16-byte entry per path (after swaps queue may point into the work block)
     int key = 0;               // 0 position-major (Morton cell | direction octant), 1 direction-major
-    uint32_t* d_keys[2] = {nullptr, nullptr};
-    uint32_t* d_vals[2] = {nullptr, nullptr};
-    void* d_temp = nullptr;
+    DeviceBuffer<uint32_t> d_keys[2], d_vals[2];
+    DeviceBuffer<char> d_temp;  // allocated last: with it the keys and values are complete
     size_t temp_bytes = 0;
-    uint32_t capacity = 0;
     float world_lo[3] = {0, 0, 0}, world_hi[3] = {1, 1, 1};  // bounds of the top-level BVH
   } sort;
   bool sync_debug = false;
   // image-tile multi-GPU (lumc_comm_*, lumc_frame_assemble*): this rank's communicator and its [4][frame pixels] assembly buffer
-  struct Exchange {  // owned by multi_gpu.hip (free_exchange)
+  struct Exchange {  // multi_gpu.hip (free_exchange ends the communicator)
     ncclComm_t comm = nullptr;
     int comm_rank = 0, comm_world = 1;
-    float* d_frame = nullptr;
-    uint32_t frame_capacity = 0;
+    DeviceBuffer<float> d_frame;
+    uint32_t frame_pixels() const { return (uint32_t) (d_frame.count() / 4); }  // the planes' stride
     // tile gather (lumc_frame_gather*): this rank's padded [4][gather_stride] send buffer; on the root the [world][4][gather_stride] receive buffer and every
     // rank's pixel list [world][gather_stride] (0xFFFFFFFF = padding), keyed by (width, height, world)
-    float* d_gather_send = nullptr;
-    float* d_gather_recv = nullptr;
-    uint32_t* d_gather_pixels = nullptr;
+    DeviceBuffer<float> d_gather_send, d_gather_recv;
+    DeviceBuffer<uint32_t> d_gather_pixels;
     uint32_t gather_stride = 0, gather_key[3] = {0, 0, 0};
-    size_t gather_recv_floats = 0;
     bool use_frame = false;         // the result / output entry points read the assembled frame instead of this context's own accumulators
   } exchange;
-  uint32_t* d_ctrl = nullptr;     // kCtlStride control words per depth (+1 row), zeroed per pass; last row: cursor of lumc_trace_closest
-  uint64_t* d_counters = nullptr;
+  DeviceBuffer<uint32_t> d_ctrl;  // kCtlStride control words per depth (+1 row), zeroed per pass; last row: cursor of lumc_trace_closest
+  DeviceBuffer<uint64_t> d_counters;
   // profiling
   bool profiling = false;
   struct Stamp { hipEvent_t a, b; int kernel; };
@@ -217,7 +204,7 @@ struct Launch {
 // what the units call of each other
 const uint32_t* sort_rays(LumContext* ctx, hipStream_t stream, const float4* origin, const float4* dir, const uint32_t* count, uint32_t capacity);  // ray_sort.hip
 int sort_closest_rays(LumContext* ctx, hipStream_t stream, PathQueue& queue, uint32_t* ctrl, uint32_t N, const uint32_t** order);
-void free_sort(LumContext* ctx);
+void free_sort(LumContext* ctx);  // the buffers of every mode; the settings and the scene's bounds stay
 void free_exchange(LumContext* ctx);  // multi_gpu.hip
 extern "C" uint64_t pixel_list_hash(const uint32_t* pixels, uint32_t n);  // core.hip, among the entry points that use it
 

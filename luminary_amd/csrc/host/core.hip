@@ -86,46 +86,30 @@ constexpr size_t kCloudNoiseTexels[3] = {(size_t) kCloudShapeRes * kCloudShapeRe
                                          (size_t) kCloudWeatherRes * kCloudWeatherRes};  // shape, detail, weather (RGBA8 each)
 constexpr uint32_t kBsdfLutCount[4] = {1024, 1024, 32768, 32768};  // conductor, glossy, dielectric, dielectric_inv
 
-// A scene array on the device, owned by the allocation group it is registered under (free_group).
+// A scene array on the device, owned by the allocation group it is registered under.
 template <typename T>
 int upload(LumContext* ctx, int group, const T* host, size_t count, const T** out) {
   *out = nullptr;
-  if (count == 0 || host == nullptr) return 0;
-  void* d = nullptr;
-  HIP_TRY(ctx, hipMalloc(&d, sizeof(T) * count));
-  ctx->scene_allocs[group].push_back(d);
-  HIP_TRY(ctx, hipMemcpy(d, host, sizeof(T) * count, hipMemcpyHostToDevice));
-  *out = (const T*) d;
+  DeviceBuffer<char> d;
+  HIP_TRY(ctx, d.assign(reinterpret_cast<const char*>(host), sizeof(T) * count));
+  *out = reinterpret_cast<const T*>(d.get());
+  if (d) ctx->scene_allocs[group].push_back(std::move(d));
   return 0;
 }
 
-void free_group(LumContext* ctx, int group) {
-  for (void* p : ctx->scene_allocs[group]) (void) hipFree(p);
-  ctx->scene_allocs[group].clear();
-}
 void free_scene(LumContext* ctx) {
-  for (int g = 0; g < LumContext::kGrpCount; g++) free_group(ctx, g);
-  for (int i = 0; i < 4; i++) { if (ctx->d_luts[i]) (void) hipFree(ctx->d_luts[i]); ctx->d_luts[i] = nullptr; }
-  for (int i = 0; i < 2; i++) { if (ctx->d_sky_lut[i]) (void) hipFree(ctx->d_sky_lut[i]); ctx->d_sky_lut[i] = nullptr; }
+  for (auto& group : ctx->scene_allocs) group.clear();
+  for (auto& t : ctx->d_luts) t.reset();
+  for (auto& t : ctx->d_sky_lut) t.reset();
   ctx->sky_lut_key.clear();
-  if (ctx->d_bridge_lut) (void) hipFree(ctx->d_bridge_lut);
-  ctx->d_bridge_lut = nullptr; ctx->bridge_lut_host.clear();
+  ctx->d_bridge_lut.reset(); ctx->bridge_lut_host.clear();
   ctx->mesh_bvh.clear(); ctx->mesh_box.clear();
   ctx->has_scene = false;
 }
 
-void free_adaptive(LumContext* ctx) {
-  LumContext::Adaptive& a = ctx->adaptive;
-  void* bufs[] = {a.d_stage_counts, a.d_block_tasks, a.d_block_task_end, a.d_block_variance, a.d_partial, a.d_scan_temp, a.d_block_mask};
-  for (void* b : bufs) if (b) (void) hipFree(b);
-  a = LumContext::Adaptive();
-}
-
 void free_work(LumContext* ctx) {
-  if (ctx->work_block) (void) hipFree(ctx->work_block);
-  ctx->work_block = nullptr;
-  if (ctx->fused_block) (void) hipFree(ctx->fused_block);
-  ctx->fused_block = nullptr; ctx->fused_capacity = 0; ctx->d_fused = nullptr;
+  ctx->work_block.reset();
+  ctx->fused_block.reset(); ctx->fused_capacity = 0; ctx->d_fused = nullptr;
   ctx->fused_refused_capacity = 0;  // memory may have been freed since the refusal: the next pass asks again
   ctx->queue[2] = PathQueue{}; ctx->nee2 = NeeQueue{}; ctx->fallback = ShadowQueue{};
   for (int k = 0; k < 3; k++) ctx->queue[k].parent = nullptr;
@@ -134,8 +118,7 @@ void free_work(LumContext* ctx) {
   ctx->cloud = CloudQueue{};
   // the reorder pass's planes (ray-sorting mode 3) trade places with the queues' own: they go with them (and with them the sort's keys, sized by the pass too)
   free_sort(ctx);
-  if (ctx->d_sobol) (void) hipFree(ctx->d_sobol);
-  ctx->d_sobol = nullptr; ctx->sobol_entries = 0;
+  ctx->d_sobol.reset();
 }
 
 int ensure_work(LumContext* ctx, uint32_t paths) {
@@ -152,8 +135,8 @@ int ensure_work(LumContext* ctx, uint32_t paths) {
   // (+ the volumes' 96 B of in-scattering records, 4 B scattering-event index and 48 B of water-surface factors of the surface vertices)
   const size_t n = paths;
   const size_t bytes = n * (2 * 68 + 84 + 16 + (size_t) kinds * 64 + 4 + (kinds > 4u ? 100 + 48 : 0) + (clouds ? 3 * (4 + 16 + 4) : 0)) + 56 * 256;
-  HIP_TRY(ctx, hipMalloc(&ctx->work_block, bytes));
-  char* p = (char*) ctx->work_block;
+  HIP_TRY(ctx, ctx->work_block.resize(bytes));
+  char* p = ctx->work_block.get();
   auto take = [&](size_t sz) { char* r = p; p += (sz + 255) & ~(size_t) 255; return r; };  // keeps every array 256-byte aligned
   for (int k = 0; k < 2; k++) {
     ctx->queue[k].origin_t = (float4*) take(n * 16);
@@ -221,12 +204,11 @@ int upload_fused_records(LumContext* ctx, hipStream_t stream) {
 int ensure_fused(LumContext* ctx, hipStream_t stream) {
   if (ctx->fused_block && ctx->fused_capacity == ctx->capacity) return ctx->fused_records_stale ? upload_fused_records(ctx, stream) : 0;
   if (ctx->fused_refused_capacity == ctx->capacity) return 1;
-  if (ctx->fused_block) (void) hipFree(ctx->fused_block);
-  ctx->fused_block = nullptr; ctx->fused_capacity = 0;
+  ctx->fused_capacity = 0;
   const size_t n = ctx->capacity;
   const size_t bytes = n * (68 + 3 * 4 + 84 + 48 + 4 + 2 * 4) + 27 * 256 + 6 * sizeof(FusedResolve);
-  if (hipMalloc(&ctx->fused_block, bytes) != hipSuccess) { ctx->fused_block = nullptr; ctx->fused_refused_capacity = ctx->capacity; return 1; }
-  char* p = (char*) ctx->fused_block;
+  if (ctx->fused_block.resize(bytes) != hipSuccess) { ctx->fused_refused_capacity = ctx->capacity; return 1; }
+  char* p = ctx->fused_block.get();
   auto take = [&](size_t sz) { char* r = p; p += (sz + 255) & ~(size_t) 255; return r; };
   PathQueue& q = ctx->queue[2];
   q.origin_t = (float4*) take(n * 16); q.dir_slot = (float4*) take(n * 16); q.aux = (uint4*) take(n * 16); q.hit_id = (uint4*) take(n * 16);
@@ -306,10 +288,10 @@ int lumc_context_create(int device_ordinal, LumContext** out) {
   HIP_TRY(ctx, hipSetDevice(device_ordinal));
   HIP_TRY(ctx, (hipError_t) wavefront_kernels_exact()->init_sampler_seeds());  // per device: module globals live on each GPU
   HIP_TRY(ctx, (hipError_t) wavefront_kernels_fast()->init_sampler_seeds());
-  HIP_TRY(ctx, hipMalloc((void**) &ctx->d_ctrl, sizeof(uint32_t) * kCtlStride * kCtrlRows));
-  HIP_TRY(ctx, hipMemset(ctx->d_ctrl, 0, sizeof(uint32_t) * kCtlStride * kCtrlRows));
-  HIP_TRY(ctx, hipMalloc((void**) &ctx->d_counters, sizeof(uint64_t) * LUMC_CNT_COUNT));
-  HIP_TRY(ctx, hipMemset(ctx->d_counters, 0, sizeof(uint64_t) * LUMC_CNT_COUNT));
+  HIP_TRY(ctx, ctx->d_ctrl.resize(kCtlStride * kCtrlRows));
+  HIP_TRY(ctx, hipMemset(ctx->d_ctrl.get(), 0, sizeof(uint32_t) * kCtlStride * kCtrlRows));
+  HIP_TRY(ctx, ctx->d_counters.resize(LUMC_CNT_COUNT));
+  HIP_TRY(ctx, hipMemset(ctx->d_counters.get(), 0, sizeof(uint64_t) * LUMC_CNT_COUNT));
   return 0;
 }
 
@@ -318,25 +300,7 @@ void lumc_context_destroy(LumContext* ctx) {
   (void) hipSetDevice(ctx->device);
   (void) hipDeviceSynchronize();
   resolve_stamps(ctx);
-  free_scene(ctx);
-  free_work(ctx);
-  if (ctx->d_pixels) (void) hipFree(ctx->d_pixels);
-  if (ctx->d_first_moment) (void) hipFree(ctx->d_first_moment);
-  if (ctx->d_second_moment) (void) hipFree(ctx->d_second_moment);
   free_exchange(ctx);
-  if (ctx->d_ctrl) (void) hipFree(ctx->d_ctrl);
-  if (ctx->d_frame_output) (void) hipFree(ctx->d_frame_output);
-  if (ctx->d_bluenoise_1d) (void) hipFree(ctx->d_bluenoise_1d);
-  if (ctx->d_argb8) (void) hipFree(ctx->d_argb8);
-  if (ctx->d_counters) (void) hipFree(ctx->d_counters);
-  if (ctx->d_frame_result) (void) hipFree(ctx->d_frame_result);
-  if (ctx->d_guides) (void) hipFree(ctx->d_guides);
-  for (void* r : ctx->d_denoise_rec) if (r) (void) hipFree(r);
-  if (ctx->d_sky_hdri) (void) hipFree(ctx->d_sky_hdri);
-  for (uint32_t*& t : ctx->d_cloud_noise) { if (t) (void) hipFree(t); t = nullptr; }
-  if (ctx->d_undersampling_pixels) (void) hipFree(ctx->d_undersampling_pixels);
-  for (float* m : ctx->bloom_mips) (void) hipFree(m);
-  free_adaptive(ctx);
   delete ctx;
 }
 
@@ -346,15 +310,15 @@ uint32_t lumc_scene_view_sizeof(void) { return (uint32_t) sizeof(LumDeviceSceneV
 // The clouds' noise textures (device_cloud.c:62-101): shape and detail once per context, the weather map per seed.
 static int ensure_cloud_noise(LumContext* ctx, uint32_t seed) {
   for (int k = 0; k < 3; k++)
-    if (!ctx->d_cloud_noise[k]) HIP_TRY(ctx, hipMalloc((void**) &ctx->d_cloud_noise[k], sizeof(uint32_t) * kCloudNoiseTexels[k]));
+    if (!ctx->d_cloud_noise[k]) HIP_TRY(ctx, ctx->d_cloud_noise[k].resize(kCloudNoiseTexels[k]));
   if (!ctx->cloud_noise_static) {
-    hipLaunchKernelGGL(exact::k_cloud_noise_shape, dim3(2048), dim3(256), 0, 0, ctx->d_cloud_noise[0], (uint32_t) kCloudShapeRes);
-    hipLaunchKernelGGL(exact::k_cloud_noise_detail, dim3(128), dim3(256), 0, 0, ctx->d_cloud_noise[1], (uint32_t) kCloudDetailRes);
+    hipLaunchKernelGGL(exact::k_cloud_noise_shape, dim3(2048), dim3(256), 0, 0, ctx->d_cloud_noise[0].get(), (uint32_t) kCloudShapeRes);
+    hipLaunchKernelGGL(exact::k_cloud_noise_detail, dim3(128), dim3(256), 0, 0, ctx->d_cloud_noise[1].get(), (uint32_t) kCloudDetailRes);
     HIP_TRY(ctx, hipGetLastError());
     ctx->cloud_noise_static = true;
   }
   if (!ctx->cloud_noise_weather_valid || ctx->cloud_noise_seed != seed) {
-    hipLaunchKernelGGL(exact::k_cloud_noise_weather, dim3(2048), dim3(256), 0, 0, ctx->d_cloud_noise[2], (uint32_t) kCloudWeatherRes, (float) seed);
+    hipLaunchKernelGGL(exact::k_cloud_noise_weather, dim3(2048), dim3(256), 0, 0, ctx->d_cloud_noise[2].get(), (uint32_t) kCloudWeatherRes, (float) seed);
     HIP_TRY(ctx, hipGetLastError());
     ctx->cloud_noise_seed = seed; ctx->cloud_noise_weather_valid = true;
   }
@@ -367,7 +331,7 @@ int lumc_cloud_noise_generate(LumContext* ctx, uint32_t seed, uint32_t* shape, u
   if (ensure_cloud_noise(ctx, seed)) return 1;
   uint32_t* out[3] = {shape, detail, weather};
   for (int k = 0; k < 3; k++)
-    if (out[k]) HIP_TRY(ctx, hipMemcpy(out[k], ctx->d_cloud_noise[k], sizeof(uint32_t) * kCloudNoiseTexels[k], hipMemcpyDeviceToHost));
+    if (out[k]) HIP_TRY(ctx, hipMemcpy(out[k], ctx->d_cloud_noise[k].get(), sizeof(uint32_t) * kCloudNoiseTexels[k], hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -437,7 +401,7 @@ static uint32_t total_triangles(const LumDeviceSceneView* v) { return v->num_mes
 static int update_mesh_arrays(LumContext* ctx, const LumDeviceSceneView* v) {
   DeviceScene& sc = ctx->scene;
   const uint32_t total_tris = total_triangles(v);
-  free_group(ctx, LumContext::kGrpMesh);
+  ctx->scene_allocs[LumContext::kGrpMesh].clear();
   if (upload(ctx, LumContext::kGrpMesh, v->mesh_tri_offset, (size_t) v->num_meshes + 1, &sc.mesh_tri_offset)) return 1;
   if (upload(ctx, LumContext::kGrpMesh, (const float4*) v->vertices, (size_t) total_tris * 3, &sc.vertices)) return 1;
   return upload(ctx, LumContext::kGrpMesh, (const uint4*) v->tri_tex, (size_t) total_tris, &sc.tri_tex);
@@ -446,13 +410,13 @@ static int update_mesh_arrays(LumContext* ctx, const LumDeviceSceneView* v) {
 // (the scene tree's arrays - update_scene_tree - belong to this group too: whenever the instances are dirty both parts run, this one first)
 static int update_instance_arrays(LumContext* ctx, const LumDeviceSceneView* v) {
   DeviceScene& sc = ctx->scene;
-  free_group(ctx, LumContext::kGrpInst);
+  ctx->scene_allocs[LumContext::kGrpInst].clear();
   if (upload(ctx, LumContext::kGrpInst, v->instance_mesh_ids, v->num_instances, &sc.instance_mesh_ids)) return 1;
   return upload(ctx, LumContext::kGrpInst, (const float4*) v->instance_transforms, (size_t) v->num_instances * 2, &sc.instance_transforms);
 }
 
 static int update_materials(LumContext* ctx, const LumDeviceSceneView* v) {
-  free_group(ctx, LumContext::kGrpMat);
+  ctx->scene_allocs[LumContext::kGrpMat].clear();
   return upload(ctx, LumContext::kGrpMat, (const uint4*) v->materials, (size_t) v->num_materials * 2, &ctx->scene.materials);
 }
 
@@ -482,7 +446,7 @@ static int upload_light_root_children(LumContext* ctx, const LumDeviceSceneView*
 // (the light BVH and k_light_table's records - update_light_bvh, update_counts_and_tables - belong to this group too and run whenever this part does)
 static int update_light_tree(LumContext* ctx, const LumDeviceSceneView* v) {
   DeviceScene& sc = ctx->scene;
-  free_group(ctx, LumContext::kGrpLight);
+  ctx->scene_allocs[LumContext::kGrpLight].clear();
   sc.light_tree_root = nullptr; sc.light_root_children = nullptr; sc.light_tree_nodes = nullptr; sc.light_tri_handles = nullptr; sc.light_tri_table = nullptr;
   sc.light_nodes = nullptr; sc.light_tris = nullptr; sc.light_num_nodes = 0;
   if (!v->light_tree_root || !v->num_lights) return 0;
@@ -495,7 +459,7 @@ static int update_light_tree(LumContext* ctx, const LumDeviceSceneView* v) {
 
 static int update_textures(LumContext* ctx, const LumDeviceSceneView* v) {
   DeviceScene& sc = ctx->scene;
-  free_group(ctx, LumContext::kGrpTex);
+  ctx->scene_allocs[LumContext::kGrpTex].clear();
   sc.num_textures = 0; sc.texture_table = nullptr; sc.texels = nullptr;
   if (!v->num_textures || !v->texture_table || !v->texels) return 0;
   size_t texel_count = 0;
@@ -617,7 +581,12 @@ static int update_counts_and_tables(LumContext* ctx, const LumDeviceSceneView* v
   }
   if ((dirty_lights || ((dirty & (LUMC_DIRTY_MATERIALS | LUMC_DIRTY_INSTANCES | LUMC_DIRTY_MESHES)) && sc.light_tri_table)) && sc.light_tree_root && sc.num_lights) {  // the emissive triangles in world space with what their material says, one record per light (load_tri_light_table)
     float4* table = const_cast<float4*>(sc.light_tri_table);  // a material edit alone refills the table in place (same lights)
-    if (dirty_lights) { HIP_TRY(ctx, hipMalloc((void**) &table, sizeof(float4) * 4 * (size_t) sc.num_lights)); ctx->scene_allocs[LumContext::kGrpLight].push_back(table); }
+    if (dirty_lights) {
+      DeviceBuffer<char> records;
+      HIP_TRY(ctx, records.resize(sizeof(float4) * 4 * (size_t) sc.num_lights));
+      table = (float4*) records.get();
+      ctx->scene_allocs[LumContext::kGrpLight].push_back(std::move(records));
+    }
     hipLaunchKernelGGL(k_light_table, dim3((sc.num_lights + kBlock - 1) / kBlock), dim3(kBlock), 0, 0, sc, table);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipDeviceSynchronize());
@@ -710,12 +679,12 @@ static int update_cloud_noise(LumContext* ctx, const LumDeviceSceneView* v) {
     return upload(ctx, LumContext::kGrpConst, (const uint32_t*) v->cloud_noise_weather, kCloudNoiseTexels[2], &sc.cloud_noise_weather);
   }
   if (ensure_cloud_noise(ctx, v->cloud_seed)) return 1;
-  sc.cloud_noise_shape = ctx->d_cloud_noise[0]; sc.cloud_noise_detail = ctx->d_cloud_noise[1]; sc.cloud_noise_weather = ctx->d_cloud_noise[2];
+  sc.cloud_noise_shape = ctx->d_cloud_noise[0].get(); sc.cloud_noise_detail = ctx->d_cloud_noise[1].get(); sc.cloud_noise_weather = ctx->d_cloud_noise[2].get();
   return 0;
 }
 
 static int update_particles(LumContext* ctx, const LumDeviceSceneView* v) {
-  free_group(ctx, LumContext::kGrpPart);
+  ctx->scene_allocs[LumContext::kGrpPart].clear();
   return build_particle_tree(ctx, LumContext::kGrpPart, v, ctx->scene);
 }
 
@@ -738,20 +707,20 @@ static int update_sky_tables(LumContext* ctx, const LumDeviceSceneView* v) {
                           sc.sky_ground_visibility, sc.sky_ozone_layer_thickness, sc.sky_multiscattering_factor, sc.sky_sun_strength};
   put(params, sizeof(params)); put(sc.sky_mie_phase, sizeof(sc.sky_mie_phase)); put(sc.sky_sun_pos, sizeof(sc.sky_sun_pos)); put(sc.sky_geometry_offset, sizeof(sc.sky_geometry_offset));
   if (!ctx->d_sky_lut[0]) {
-    HIP_TRY(ctx, hipMalloc((void**) &ctx->d_sky_lut[0], sizeof(float4) * tm_texels));
-    HIP_TRY(ctx, hipMalloc((void**) &ctx->d_sky_lut[1], sizeof(float4) * ms_texels));
+    HIP_TRY(ctx, ctx->d_sky_lut[0].resize(tm_texels));
+    HIP_TRY(ctx, ctx->d_sky_lut[1].resize(ms_texels));
     ctx->sky_lut_key.clear();
   }
   if (key != ctx->sky_lut_key) {
-    hipLaunchKernelGGL(k_sky_transmittance_lut, dim3((kSkyTmWidth * kSkyTmHeight + 63) / 64), dim3(64), 0, 0, sc, ctx->d_sky_lut[0]);
-    sc.sky_lut_transmittance = ctx->d_sky_lut[0];  // the multiscattering integration reads the finished transmittance table
-    hipLaunchKernelGGL(k_sky_multiscattering_lut, dim3(kSkyMsSize, kSkyMsSize), dim3(kSkyMsIter), 0, 0, sc, ctx->d_sky_lut[1]);
+    hipLaunchKernelGGL(k_sky_transmittance_lut, dim3((kSkyTmWidth * kSkyTmHeight + 63) / 64), dim3(64), 0, 0, sc, ctx->d_sky_lut[0].get());
+    sc.sky_lut_transmittance = ctx->d_sky_lut[0].get();  // the multiscattering integration reads the finished transmittance table
+    hipLaunchKernelGGL(k_sky_multiscattering_lut, dim3(kSkyMsSize, kSkyMsSize), dim3(kSkyMsIter), 0, 0, sc, ctx->d_sky_lut[1].get());
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipDeviceSynchronize());
     ctx->sky_lut_key = key;
   }
-  sc.sky_lut_transmittance = ctx->d_sky_lut[0];
-  sc.sky_lut_multiscattering = ctx->d_sky_lut[1];
+  sc.sky_lut_transmittance = ctx->d_sky_lut[0].get();
+  sc.sky_lut_multiscattering = ctx->d_sky_lut[1].get();
   return 0;
 }
 
@@ -759,11 +728,11 @@ static int update_sky_tables(LumContext* ctx, const LumDeviceSceneView* v) {
 static int update_bsdf_tables(LumContext* ctx, const LumDeviceSceneView* v, bool full_upload) {
   DeviceScene& sc = ctx->scene;
   const uint16_t* host_luts[4] = {v->lut_conductor, v->lut_glossy, v->lut_dielectric, v->lut_dielectric_inv};
-  const bool have_luts = ctx->d_luts[0] != nullptr;
-  for (int t = 0; t < 4 && !have_luts; t++) HIP_TRY(ctx, hipMalloc((void**) &ctx->d_luts[t], sizeof(uint16_t) * kBsdfLutCount[t]));
+  const bool have_luts = bool(ctx->d_luts[0]);
+  for (int t = 0; t < 4 && !have_luts; t++) HIP_TRY(ctx, ctx->d_luts[t].resize(kBsdfLutCount[t]));
   if (have_luts && !full_upload) { /* a partial update keeps the tables the context renders with */ }
   else if (host_luts[0] && host_luts[1] && host_luts[2] && host_luts[3]) {
-    for (int t = 0; t < 4; t++) HIP_TRY(ctx, hipMemcpy(ctx->d_luts[t], host_luts[t], sizeof(uint16_t) * kBsdfLutCount[t], hipMemcpyHostToDevice));
+    for (int t = 0; t < 4; t++) HIP_TRY(ctx, hipMemcpy(ctx->d_luts[t].get(), host_luts[t], sizeof(uint16_t) * kBsdfLutCount[t], hipMemcpyHostToDevice));
   }
   else {
     // The tables are a function of the embedded blue-noise mask alone (65 536 samples per texel, one thread per texel: 0.29 s of GPU time):
@@ -774,7 +743,7 @@ static int update_bsdf_tables(LumContext* ctx, const LumDeviceSceneView* v, bool
     std::lock_guard<std::mutex> lock(lut_mutex);
     const bool cached = !lut_cache[0].empty() && lut_cache_mask.size() == 65536 && std::memcmp(lut_cache_mask.data(), v->bluenoise_2d, sizeof(uint32_t) * 65536) == 0;
     if (cached) {
-      for (int t = 0; t < 4; t++) HIP_TRY(ctx, hipMemcpy(ctx->d_luts[t], lut_cache[t].data(), sizeof(uint16_t) * kBsdfLutCount[t], hipMemcpyHostToDevice));
+      for (int t = 0; t < 4; t++) HIP_TRY(ctx, hipMemcpy(ctx->d_luts[t].get(), lut_cache[t].data(), sizeof(uint16_t) * kBsdfLutCount[t], hipMemcpyHostToDevice));
     }
     else {
       // the two big tables and the conductor table are independent: side by side on three streams; the glossy table divides by the conductor's
@@ -783,19 +752,19 @@ static int update_bsdf_tables(LumContext* ctx, const LumDeviceSceneView* v, bool
       const int first_wave[3] = {0, 2, 3};
       for (int k = 0; k < 3; k++) {
         const int t = first_wave[k];
-        hipLaunchKernelGGL(k_generate_lut, dim3((kBsdfLutCount[t] + 63) / 64), dim3(64), 0, streams[k], sc.bluenoise_2d, t, kBsdfLutCount[t], ctx->d_luts[0], ctx->d_luts[t]);
+        hipLaunchKernelGGL(k_generate_lut, dim3((kBsdfLutCount[t] + 63) / 64), dim3(64), 0, streams[k], sc.bluenoise_2d, t, kBsdfLutCount[t], ctx->d_luts[0].get(), ctx->d_luts[t].get());
       }
-      hipLaunchKernelGGL(k_generate_lut, dim3((kBsdfLutCount[1] + 63) / 64), dim3(64), 0, streams[0], sc.bluenoise_2d, 1, kBsdfLutCount[1], ctx->d_luts[0], ctx->d_luts[1]);
+      hipLaunchKernelGGL(k_generate_lut, dim3((kBsdfLutCount[1] + 63) / 64), dim3(64), 0, streams[0], sc.bluenoise_2d, 1, kBsdfLutCount[1], ctx->d_luts[0].get(), ctx->d_luts[1].get());
       HIP_TRY(ctx, hipGetLastError());
       for (auto& st : streams) { HIP_TRY(ctx, hipStreamSynchronize(st)); (void) hipStreamDestroy(st); }
       for (int t = 0; t < 4; t++) {
         lut_cache[t].resize(kBsdfLutCount[t]);
-        HIP_TRY(ctx, hipMemcpy(lut_cache[t].data(), ctx->d_luts[t], sizeof(uint16_t) * kBsdfLutCount[t], hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(lut_cache[t].data(), ctx->d_luts[t].get(), sizeof(uint16_t) * kBsdfLutCount[t], hipMemcpyDeviceToHost));
       }
       lut_cache_mask.assign(v->bluenoise_2d, v->bluenoise_2d + 65536);
     }
   }
-  sc.lut_conductor = ctx->d_luts[0]; sc.lut_glossy = ctx->d_luts[1]; sc.lut_dielectric = ctx->d_luts[2]; sc.lut_dielectric_inv = ctx->d_luts[3];
+  sc.lut_conductor = ctx->d_luts[0].get(); sc.lut_glossy = ctx->d_luts[1].get(); sc.lut_dielectric = ctx->d_luts[2].get(); sc.lut_dielectric_inv = ctx->d_luts[3].get();
   return 0;
 }
 
@@ -816,7 +785,7 @@ static int update_sky_panorama(LumContext* ctx, const LumDeviceSceneView* v) {
 
 // Camera, settings, sky, fog, ocean, clouds, particles: the kernels' scalar arguments and the tables derived from them.
 static int update_constants(LumContext* ctx, const LumDeviceSceneView* v, unsigned dirty) {
-  free_group(ctx, LumContext::kGrpConst);
+  ctx->scene_allocs[LumContext::kGrpConst].clear();
   if (copy_constants(ctx, v)) return 1;
   if (update_stars(ctx, v)) return 1;
   if (update_cloud_noise(ctx, v)) return 1;
@@ -837,11 +806,11 @@ static int update_bridge_table(LumContext* ctx, const LumDeviceSceneView* v) {
   if (sc.bridge_max_num_vertices == 0) { ctx->error = "lumc_scene_upload: bridge_max_num_vertices must be at least 1"; return 1; }
   const size_t n = (size_t) 64 * 21;
   if (!ctx->d_bridge_lut || ctx->bridge_lut_host.size() != n || std::memcmp(ctx->bridge_lut_host.data(), v->bridge_lut, n * sizeof(float)) != 0) {
-    if (!ctx->d_bridge_lut) HIP_TRY(ctx, hipMalloc((void**) &ctx->d_bridge_lut, n * sizeof(float)));
-    HIP_TRY(ctx, hipMemcpy(ctx->d_bridge_lut, v->bridge_lut, n * sizeof(float), hipMemcpyHostToDevice));
+    if (!ctx->d_bridge_lut) HIP_TRY(ctx, ctx->d_bridge_lut.resize(n));
+    HIP_TRY(ctx, hipMemcpy(ctx->d_bridge_lut.get(), v->bridge_lut, n * sizeof(float), hipMemcpyHostToDevice));
     ctx->bridge_lut_host.assign(v->bridge_lut, v->bridge_lut + n);
   }
-  sc.bridge_lut = ctx->d_bridge_lut;
+  sc.bridge_lut = ctx->d_bridge_lut.get();
   return 0;
 }
 
@@ -894,7 +863,7 @@ int lumc_download_luts(LumContext* ctx, uint16_t* conductor, uint16_t* glossy, u
   if (!ctx || !ctx->has_scene) return 1;
   uint16_t* dst[4] = {conductor, glossy, dielectric, dielectric_inv};
   for (int t = 0; t < 4; t++)
-    if (dst[t]) HIP_TRY(ctx, hipMemcpy(dst[t], ctx->d_luts[t], sizeof(uint16_t) * kBsdfLutCount[t], hipMemcpyDeviceToHost));
+    if (dst[t]) HIP_TRY(ctx, hipMemcpy(dst[t], ctx->d_luts[t].get(), sizeof(uint16_t) * kBsdfLutCount[t], hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -934,29 +903,25 @@ int lumc_sky_hdri_build(LumContext* ctx, const float origin[3], uint32_t dim, ui
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   std::vector<uint32_t> key = sky_hdri_key(ctx->scene, ctx->cloud_noise_seed, origin, dim, samples);
   if (ctx->d_sky_hdri && key == ctx->sky_hdri_key) {
-    if (ctx->scene.sky_mode == kSkyHdri) { ctx->scene.sky_hdri = ctx->d_sky_hdri; ctx->scene.sky_hdri_dim = dim; }
+    if (ctx->scene.sky_mode == kSkyHdri) { ctx->scene.sky_hdri = ctx->d_sky_hdri.get(); ctx->scene.sky_hdri_dim = dim; }
     return 0;
   }
   ctx->sky_hdri_key.clear();
-  if (ctx->sky_hdri_dim != dim) {
-    if (ctx->d_sky_hdri) (void) hipFree(ctx->d_sky_hdri);
-    ctx->d_sky_hdri = nullptr; ctx->sky_hdri_dim = 0;
-    HIP_TRY(ctx, hipMalloc((void**) &ctx->d_sky_hdri, sizeof(float4) * (size_t) dim * dim));
-    ctx->sky_hdri_dim = dim;
-  }
+  if (ctx->d_sky_hdri.count() != (size_t) dim * dim) HIP_TRY(ctx, ctx->d_sky_hdri.resize((size_t) dim * dim));
+  ctx->sky_hdri_dim = dim;
   const uint64_t threads = (uint64_t) dim * dim * 32u;
-  hipLaunchKernelGGL(k_sky_hdri, dim3((uint32_t) ((threads + 255) / 256)), dim3(256), 0, 0, ctx->scene, origin[0], origin[1], origin[2], dim, samples, ctx->d_sky_hdri);
+  hipLaunchKernelGGL(k_sky_hdri, dim3((uint32_t) ((threads + 255) / 256)), dim3(256), 0, 0, ctx->scene, origin[0], origin[1], origin[2], dim, samples, ctx->d_sky_hdri.get());
   HIP_TRY(ctx, hipGetLastError());
   HIP_TRY(ctx, hipDeviceSynchronize());
   ctx->sky_hdri_key = std::move(key);
-  if (ctx->scene.sky_mode == kSkyHdri) { ctx->scene.sky_hdri = ctx->d_sky_hdri; ctx->scene.sky_hdri_dim = dim; }
+  if (ctx->scene.sky_mode == kSkyHdri) { ctx->scene.sky_hdri = ctx->d_sky_hdri.get(); ctx->scene.sky_hdri_dim = dim; }
   return 0;
 }
 
 int lumc_sky_hdri_download(LumContext* ctx, float* rgba, uint32_t* dim) {
   if (!ctx || !ctx->d_sky_hdri) { if (ctx) ctx->error = "lumc_sky_hdri_download: no baked sky"; return 1; }
   if (dim) *dim = ctx->sky_hdri_dim;
-  if (rgba) HIP_TRY(ctx, hipMemcpy(rgba, ctx->d_sky_hdri, sizeof(float4) * (size_t) ctx->sky_hdri_dim * ctx->sky_hdri_dim, hipMemcpyDeviceToHost));
+  if (rgba) HIP_TRY(ctx, hipMemcpy(rgba, ctx->d_sky_hdri.get(), sizeof(float4) * (size_t) ctx->sky_hdri_dim * ctx->sky_hdri_dim, hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -971,26 +936,21 @@ int lumc_set_pixels(LumContext* ctx, const uint32_t* pixels, uint32_t num_pixels
   if (!ctx || !ctx->has_scene) { if (ctx) ctx->error = "lumc_set_pixels: no scene"; return 1; }
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   if (!pixels) num_pixels = ctx->scene.width * ctx->scene.height;
-  free_adaptive(ctx);
-  if (ctx->d_pixels) { (void) hipFree(ctx->d_pixels); ctx->d_pixels = nullptr; }
-  if (ctx->d_first_moment) { (void) hipFree(ctx->d_first_moment); ctx->d_first_moment = nullptr; }
-  if (ctx->d_second_moment) { (void) hipFree(ctx->d_second_moment); ctx->d_second_moment = nullptr; }
+  ctx->adaptive = LumContext::Adaptive();
+  ctx->d_pixels.reset(); ctx->d_first_moment.reset(); ctx->d_second_moment.reset();
   ctx->num_pixels = num_pixels;
   ctx->pixels_hash = pixel_list_hash(pixels, num_pixels);  // what lumc_frame_gather checks the set against (a null list = the frame in row-major order)
   if (num_pixels == 0) return 0;
-  if (pixels) {
-    HIP_TRY(ctx, hipMalloc((void**) &ctx->d_pixels, sizeof(uint32_t) * num_pixels));
-    HIP_TRY(ctx, hipMemcpy(ctx->d_pixels, pixels, sizeof(uint32_t) * num_pixels, hipMemcpyHostToDevice));
-  }
-  HIP_TRY(ctx, hipMalloc((void**) &ctx->d_first_moment, sizeof(float) * 3 * (size_t) num_pixels));
-  HIP_TRY(ctx, hipMalloc((void**) &ctx->d_second_moment, sizeof(float) * (size_t) num_pixels));
+  HIP_TRY(ctx, ctx->d_pixels.assign(pixels, num_pixels));  // (no list: the frame in row-major order, and no buffer)
+  HIP_TRY(ctx, ctx->d_first_moment.resize(3 * (size_t) num_pixels));
+  HIP_TRY(ctx, ctx->d_second_moment.resize(num_pixels));
   return lumc_clear_accumulators(ctx);
 }
 
 int lumc_clear_accumulators(LumContext* ctx) {
   if (!ctx || !ctx->d_first_moment) return 1;
-  HIP_TRY(ctx, hipMemset(ctx->d_first_moment, 0, sizeof(float) * 3 * (size_t) ctx->num_pixels));
-  HIP_TRY(ctx, hipMemset(ctx->d_second_moment, 0, sizeof(float) * (size_t) ctx->num_pixels));
+  HIP_TRY(ctx, hipMemset(ctx->d_first_moment.get(), 0, sizeof(float) * 3 * (size_t) ctx->num_pixels));
+  HIP_TRY(ctx, hipMemset(ctx->d_second_moment.get(), 0, sizeof(float) * (size_t) ctx->num_pixels));
   return 0;
 }
 
@@ -1021,15 +981,10 @@ static void prepare_sobol_table(LumContext* ctx, hipStream_t stream, DeviceScene
   if (!(ctx->sobol_table && sample_count > 0 && sample_count <= kSobolTableMaxSamples && sc.shading_mode == 0u)) return;
   const uint32_t stride = (sample_count + 15u) & ~15u, dims = (sc.max_ray_depth + 1u) * kRndTargetCount;
   const size_t entries = (size_t) stride * dims;
-  if (ctx->sobol_entries < entries) {
-    if (ctx->d_sobol) (void) hipFree(ctx->d_sobol);
-    ctx->d_sobol = nullptr; ctx->sobol_entries = 0;
-    if (hipMalloc((void**) &ctx->d_sobol, entries * sizeof(uint2)) == hipSuccess) ctx->sobol_entries = entries;
-    else (void) hipGetLastError();  // no room: the sampler hashes
-  }
+  if (ctx->d_sobol.count() < entries && ctx->d_sobol.resize(entries) != hipSuccess) (void) hipGetLastError();  // no room: the sampler hashes
   if (ctx->d_sobol) {
-    ctx->wf->sobol_table(stream, ctx->d_sobol, first_sample, sample_count, stride, dims);
-    sc.sobol_table = ctx->d_sobol; sc.sobol_first = first_sample; sc.sobol_count = sample_count; sc.sobol_stride = stride;
+    ctx->wf->sobol_table(stream, ctx->d_sobol.get(), first_sample, sample_count, stride, dims);
+    sc.sobol_table = ctx->d_sobol.get(); sc.sobol_first = first_sample; sc.sobol_count = sample_count; sc.sobol_stride = stride;
   }
 }
 
@@ -1041,23 +996,23 @@ static void debug_pass(LumContext* ctx, hipStream_t stream, const DeviceScene& s
   const WavefrontKernels& wf = *ctx->wf;
   {
     Launch l(ctx, stream, LUMC_KERNEL_TRACE);
-    wf.trace(grid_persistent(ctx, N), ray_kernel_lds(ctx), stream, sc, ctx->queue[0], nullptr, ctx->d_ctrl, ctx->d_counters, ctx->lds_nodes);
+    wf.trace(grid_persistent(ctx, N), ray_kernel_lds(ctx), stream, sc, ctx->queue[0], nullptr, ctx->d_ctrl.get(), ctx->d_counters.get(), ctx->lds_nodes);
   }
-  if (sc.particles_active) trace_particles(ctx, stream, ctx->queue[0], ctx->d_ctrl, N);
+  if (sc.particles_active) trace_particles(ctx, stream, ctx->queue[0], ctx->d_ctrl.get(), N);
   if (sc.ocean_active) {
     Launch l(ctx, stream, LUMC_KERNEL_TRACE);
-    wf.trace_ocean(grid_for(N), stream, sc, ctx->queue[0], (const uint32_t*) ctx->d_ctrl);
+    wf.trace_ocean(grid_for(N), stream, sc, ctx->queue[0], (const uint32_t*) ctx->d_ctrl.get());
   }
   if (render_volumes(sc)) {  // the debug queue keeps volume_process_events (device_renderer.c:145-147)
     Launch l(ctx, stream, LUMC_KERNEL_VOLUME);
-    wf.volume_events(grid_for(N), stream, sc, ctx->queue[0], ctx->volume, ctx->d_results, ctx->d_ctrl, 0u);
+    wf.volume_events(grid_for(N), stream, sc, ctx->queue[0], ctx->volume, ctx->d_results, ctx->d_ctrl.get(), 0u);
   }
   if (sc.sky_aerial_perspective && sc.sky_mode != kSkyConstantColor) {  // the debug queue keeps the in-scattering events (device_renderer.c:150-154)
     Launch l(ctx, stream, LUMC_KERNEL_SKY);
-    wf.sky_inscattering(grid_for(N), stream, sc, ctx->queue[0], ctx->d_results, (const uint32_t*) ctx->d_ctrl, 0u);
+    wf.sky_inscattering(grid_for(N), stream, sc, ctx->queue[0], ctx->d_results, (const uint32_t*) ctx->d_ctrl.get(), 0u);
   }
   Launch l(ctx, stream, LUMC_KERNEL_SHADE);
-  wf.shade_debug(grid_for(N), stream, sc, ctx->queue[0], ctx->d_results, (const uint32_t*) ctx->d_ctrl);
+  wf.shade_debug(grid_for(N), stream, sc, ctx->queue[0], ctx->d_results, (const uint32_t*) ctx->d_ctrl.get());
 }
 
 // How the vertices of a depth get their sums (the visibility answers applied to the NEE records):
@@ -1093,7 +1048,7 @@ static DepthBuffers depth_buffers(LumContext* ctx, ResolveScheme scheme, uint32_
   // the sampler's depth constant is not advanced before the last pass (device_renderer.c:126-130)
   const uint32_t depth_const = (depth == max_depth && depth > 0) ? depth - 1 : depth;
   return DepthBuffers{ctx->queue[cur], ctx->queue[next_q], ctx->queue[prev_q], second_set ? ctx->nee2 : ctx->nee, second_set ? ctx->nee : ctx->nee2,
-                      ctx->d_ctrl + kCtlStride * depth, fused ? ctx->d_fused + depth % 6u : nullptr, fused ? ctx->d_ended[depth & 1u] : nullptr, depth, depth_const,
+                      ctx->d_ctrl.get() + kCtlStride * depth, fused ? ctx->d_fused + depth % 6u : nullptr, fused ? ctx->d_ended[depth & 1u] : nullptr, depth, depth_const,
                       depth == max_depth};
 }
 
@@ -1105,17 +1060,17 @@ static int closest_hits(LumContext* ctx, hipStream_t stream, const DeviceScene& 
   if (ctx->sort.mode >= 1 && d.depth >= 1 && sort_closest_rays(ctx, stream, d.cur, d.ctrl, N, &order)) return 1;
   {
     Launch l(ctx, stream, LUMC_KERNEL_TRACE);
-    wf.trace(grid_persistent(ctx, N), ray_kernel_lds(ctx), stream, sc, d.cur, order, d.ctrl, ctx->d_counters, ctx->lds_nodes);
+    wf.trace(grid_persistent(ctx, N), ray_kernel_lds(ctx), stream, sc, d.cur, order, d.ctrl, ctx->d_counters.get(), ctx->lds_nodes);
   }
   if (scheme == kResolveReuse && d.depth > 0) {  // the previous depth's resolve: ambient samples answered by the pass above; what it cannot answer is traced (the control words of the fog's visibility pass: no fog here) and resolved after
     uint32_t* prev = d.ctrl - kCtlStride;
     {
       Launch l(ctx, stream, LUMC_KERNEL_RESOLVE);
-      wf.resolve_reuse(grid_for(N), stream, sc, d.prev, d.cur, d.nee, ctx->shadow, ctx->d_results, prev, ctx->d_counters);
+      wf.resolve_reuse(grid_for(N), stream, sc, d.prev, d.cur, d.nee, ctx->shadow, ctx->d_results, prev, ctx->d_counters.get());
     }
     {
       Launch l(ctx, stream, LUMC_KERNEL_SHADOW);
-      wf.shadow_rays(ctx->trace_blocks, ray_kernel_lds(ctx), stream, sc, ctx->shadow, nullptr, prev + kCtlVolumeShift, ctx->d_counters, ctx->lds_nodes);
+      wf.shadow_rays(ctx->trace_blocks, ray_kernel_lds(ctx), stream, sc, ctx->shadow, nullptr, prev + kCtlVolumeShift, ctx->d_counters.get(), ctx->lds_nodes);
     }
     Launch l(ctx, stream, LUMC_KERNEL_RESOLVE);
     wf.resolve_listed(std::min<uint32_t>(grid_for(N), 1024u), stream, sc, d.prev, d.nee, ctx->shadow, ctx->d_results, (const uint32_t*) prev);
@@ -1138,7 +1093,7 @@ static void media_passes(LumContext* ctx, hipStream_t stream, const DeviceScene&
     }
     {
       Launch l(ctx, stream, LUMC_KERNEL_SHADOW);
-      wf.shadow_rays(grid_persistent(ctx, N), ray_kernel_lds(ctx), stream, sc, ctx->shadow, nullptr, d.ctrl + kCtlVolumeShift, ctx->d_counters, ctx->lds_nodes);
+      wf.shadow_rays(grid_persistent(ctx, N), ray_kernel_lds(ctx), stream, sc, ctx->shadow, nullptr, d.ctrl + kCtlVolumeShift, ctx->d_counters.get(), ctx->lds_nodes);
     }
     Launch l(ctx, stream, LUMC_KERNEL_VOLUME);
     wf.volume_resolve(grid_for(N), stream, sc, d.cur, ctx->volume, ctx->shadow, ctx->d_results, (const uint32_t*) d.ctrl);
@@ -1162,14 +1117,14 @@ static void shade_depth(LumContext* ctx, hipStream_t stream, const DeviceScene& 
   const bool fused = scheme == kResolveFused;
   {
     Launch l(ctx, stream, LUMC_KERNEL_SHADE);
-    wf.shade(shade_grid(ctx, N), stream, sc, d.cur, d.next, d.nee, ctx->shadow, ctx->d_results, d.ctrl, d.depth_const, ctx->d_counters,
+    wf.shade(shade_grid(ctx, N), stream, sc, d.cur, d.next, d.nee, ctx->shadow, ctx->d_results, d.ctrl, d.depth_const, ctx->d_counters.get(),
              (scheme != kResolvePlain && !d.last) ? 1u : 0u, d.fused_records,
              fused ? ((d.depth > 0 ? 1u : 0u) | (!d.last ? 2u : 0u) | (ctx->fused_ended ? 4u : 0u)) : 0u);
   }
   if (fused && d.depth > 0) {  // the samples of depth - 1 their paths' closest hits could not decide: traced now, their vertices resolved (before this depth's visibility pass reuses the words)
     {
       Launch l(ctx, stream, LUMC_KERNEL_SHADOW);
-      wf.shadow_rays(ctx->trace_blocks, ray_kernel_lds(ctx), stream, sc, ctx->fallback, nullptr, d.ctrl + kCtlVolumeShift, ctx->d_counters, ctx->lds_nodes);
+      wf.shadow_rays(ctx->trace_blocks, ray_kernel_lds(ctx), stream, sc, ctx->fallback, nullptr, d.ctrl + kCtlVolumeShift, ctx->d_counters.get(), ctx->lds_nodes);
     }
     Launch l(ctx, stream, LUMC_KERNEL_RESOLVE);
     wf.resolve_listed(std::min<uint32_t>(grid_for(N), 1024u), stream, sc, d.prev, d.nee_before, ctx->fallback, ctx->d_results, (const uint32_t*) d.ctrl);
@@ -1200,7 +1155,7 @@ static int visibility_and_resolve(LumContext* ctx, hipStream_t stream, const Dev
     Launch l(ctx, stream, LUMC_KERNEL_LIGHT_QUERY);
     // (one resident round of its workgroups - four per CU: the kernel's workgroups are dear to start (a 1 KB stack per lane in scratch); 2 rounds, the common cap:
     //  Example-class 4.6 -> 4.0 ms per 3 steps, scan 3.9 -> 3.6, hall equal; 4 / 8 / 16 rounds on the hall: 30.2 / 32.8 / 44.5 ms against 29.9)
-    wf.light_query(std::min<uint32_t>(grid_for(N), ctx->trace_blocks * 4u), stream, sc, d.cur, d.nee, ctx->shadow, d.ctrl, d.depth_const, ctx->d_counters);
+    wf.light_query(std::min<uint32_t>(grid_for(N), ctx->trace_blocks * 4u), stream, sc, d.cur, d.nee, ctx->shadow, d.ctrl, d.depth_const, ctx->d_counters.get());
   }
   const uint32_t* shadow_order = nullptr;
   if (ctx->sort.mode == 2) {
@@ -1210,7 +1165,7 @@ static int visibility_and_resolve(LumContext* ctx, hipStream_t stream, const Dev
   }
   {
     Launch l(ctx, stream, LUMC_KERNEL_SHADOW);
-    wf.shadow_rays(grid_persistent(ctx, N), ray_kernel_lds(ctx), stream, sc, ctx->shadow, shadow_order, d.ctrl, ctx->d_counters, ctx->lds_nodes);
+    wf.shadow_rays(grid_persistent(ctx, N), ray_kernel_lds(ctx), stream, sc, ctx->shadow, shadow_order, d.ctrl, ctx->d_counters.get(), ctx->lds_nodes);
   }
   if (d.last || scheme == kResolvePlain) {
     Launch l(ctx, stream, LUMC_KERNEL_RESOLVE);
@@ -1265,7 +1220,7 @@ int lumc_render(LumContext* ctx, uint32_t first_sample, uint32_t num_samples, ui
   if (ctx->num_pixels == 0) return 0;
   hipStream_t stream = (hipStream_t) stream_;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  if (!d_fm) { d_fm = ctx->d_first_moment; d_sm = ctx->d_second_moment; }
+  if (!d_fm) { d_fm = ctx->d_first_moment.get(); d_sm = ctx->d_second_moment.get(); }
   if (samples_per_pass == 0) samples_per_pass = 1;
   // sample ids beyond 2^20 would duplicate earlier ones (cuda/kernels.cuh:103-105)
   if (first_sample >= kMaxGlobalSamples) return 0;
@@ -1280,11 +1235,11 @@ int lumc_render(LumContext* ctx, uint32_t first_sample, uint32_t num_samples, ui
   for (uint32_t done = 0; done < num_samples; done += samples_per_pass) {
     const uint32_t batch = std::min(samples_per_pass, num_samples - done);
     const uint32_t N = P * batch;
-    PassParams pp{ctx->d_pixels, P, batch, first_sample + done};
-    HIP_TRY(ctx, hipMemsetAsync(ctx->d_ctrl, 0, sizeof(uint32_t) * kCtlStride * (max_depth + 2), stream));
+    PassParams pp{ctx->d_pixels.get(), P, batch, first_sample + done};
+    HIP_TRY(ctx, hipMemsetAsync(ctx->d_ctrl.get(), 0, sizeof(uint32_t) * kCtlStride * (max_depth + 2), stream));
     {
       Launch l(ctx, stream, LUMC_KERNEL_GENERATE);
-      ctx->wf->generate(grid_for(N), stream, sc, pp, ctx->queue[0], ctx->d_results, ctx->d_ctrl + kCtlPaths, ctx->lens, ctx->camera);
+      ctx->wf->generate(grid_for(N), stream, sc, pp, ctx->queue[0], ctx->d_results, ctx->d_ctrl.get() + kCtlPaths, ctx->lens, ctx->camera);
     }
     if (wavefront_depths(ctx, stream, N, first_sample + done, batch)) return 1;
     {
@@ -1308,26 +1263,21 @@ int lumc_render_undersampled(LumContext* ctx, uint32_t stage, uint32_t iteration
   const std::vector<uint32_t> px = undersampling_pixels(sc.width, sc.height, stage, iteration);
   const uint32_t n = (uint32_t) px.size();
   if (n == 0) return 0;
-  if (ctx->undersampling_capacity < n) {
-    if (ctx->d_undersampling_pixels) (void) hipFree(ctx->d_undersampling_pixels);
-    ctx->d_undersampling_pixels = nullptr; ctx->undersampling_capacity = 0;
-    HIP_TRY(ctx, hipMalloc((void**) &ctx->d_undersampling_pixels, sizeof(uint32_t) * (size_t) n));
-    ctx->undersampling_capacity = n;
-  }
-  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_undersampling_pixels, px.data(), sizeof(uint32_t) * (size_t) n, hipMemcpyHostToDevice, stream));
+  if (ctx->d_undersampling_pixels.count() < n) HIP_TRY(ctx, ctx->d_undersampling_pixels.resize(n));
+  HIP_TRY(ctx, hipMemcpyAsync(ctx->d_undersampling_pixels.get(), px.data(), sizeof(uint32_t) * (size_t) n, hipMemcpyHostToDevice, stream));
   HIP_TRY(ctx, hipStreamSynchronize(stream));  // the list leaves scope
   if (ensure_work(ctx, n)) return 1;
-  PassParams pp{ctx->d_undersampling_pixels, n, 1u, 0u};  // every pixel's first sample
-  HIP_TRY(ctx, hipMemsetAsync(ctx->d_ctrl, 0, sizeof(uint32_t) * kCtlStride * (sc.max_ray_depth + 2), stream));
+  PassParams pp{ctx->d_undersampling_pixels.get(), n, 1u, 0u};  // every pixel's first sample
+  HIP_TRY(ctx, hipMemsetAsync(ctx->d_ctrl.get(), 0, sizeof(uint32_t) * kCtlStride * (sc.max_ray_depth + 2), stream));
   {
     Launch l(ctx, stream, LUMC_KERNEL_GENERATE);
-    ctx->wf->generate(grid_for(n), stream, sc, pp, ctx->queue[0], ctx->d_results, ctx->d_ctrl + kCtlPaths, ctx->lens, ctx->camera);
+    ctx->wf->generate(grid_for(n), stream, sc, pp, ctx->queue[0], ctx->d_results, ctx->d_ctrl.get() + kCtlPaths, ctx->lens, ctx->camera);
   }
   if (wavefront_depths(ctx, stream, n)) return 1;
   {
     Launch l(ctx, stream, LUMC_KERNEL_ACCUMULATE);
-    hipLaunchKernelGGL(k_accumulate_scatter, dim3(grid_for(n)), dim3(kBlock), 0, stream, (const float4*) ctx->d_results, (const uint32_t*) ctx->d_undersampling_pixels, n,
-                       ctx->num_pixels, ctx->d_first_moment, ctx->d_second_moment);
+    hipLaunchKernelGGL(k_accumulate_scatter, dim3(grid_for(n)), dim3(kBlock), 0, stream, (const float4*) ctx->d_results, (const uint32_t*) ctx->d_undersampling_pixels.get(), n,
+                       ctx->num_pixels, ctx->d_first_moment.get(), ctx->d_second_moment.get());
   }
   HIP_TRY(ctx, hipGetLastError());
   return 0;
@@ -1339,7 +1289,7 @@ namespace {
 AdaptiveView adaptive_view(const LumContext* ctx) {
   const LumContext::Adaptive& a = ctx->adaptive;
   AdaptiveView v;
-  v.stage_counts = a.d_stage_counts; v.block_task_end = a.d_block_task_end;
+  v.stage_counts = a.d_stage_counts.get(); v.block_task_end = a.d_block_task_end.get();
   v.blocks_x = a.blocks_x; v.blocks_y = a.blocks_y; v.num_blocks = a.num_blocks;
   for (uint32_t s = 0; s <= kAdaptiveStages; s++) v.executions[s] = a.executions[s];
   v.stage_id = a.stage_id;
@@ -1361,7 +1311,7 @@ int adaptive_compute_variance(LumContext* ctx, hipStream_t stream) {
   const AdaptiveView view = adaptive_view(ctx);
   const OutputParams op = tone_params(&a.params.tone);
   hipLaunchKernelGGL(k_adaptive_block_variance, dim3((a.num_blocks * 16 + 255) / 256), dim3(256), 0, stream, view, op, sc.width, sc.height, a.params.exposure,
-                     (const float*) ctx->d_first_moment, (const float*) ctx->d_second_moment, a.d_block_variance);
+                     (const float*) ctx->d_first_moment.get(), (const float*) ctx->d_second_moment.get(), a.d_block_variance.get());
   HIP_TRY(ctx, hipGetLastError());
   return 0;
 }
@@ -1370,9 +1320,9 @@ int adaptive_compute_variance(LumContext* ctx, hipStream_t stream) {
 int adaptive_task_prefix(LumContext* ctx, hipStream_t stream) {
   LumContext::Adaptive& a = ctx->adaptive;
   const uint32_t nb = a.num_blocks;
-  HIP_TRY(ctx, hipcub::DeviceScan::InclusiveSum(a.d_scan_temp, a.scan_temp_bytes, a.d_block_tasks, a.d_block_task_end, (int) nb, stream));
+  HIP_TRY(ctx, hipcub::DeviceScan::InclusiveSum(a.d_scan_temp.get(), a.scan_temp_bytes, a.d_block_tasks.get(), a.d_block_task_end.get(), (int) nb, stream));
   a.task_end.resize(nb);
-  HIP_TRY(ctx, hipMemcpyAsync(a.task_end.data(), a.d_block_task_end, sizeof(uint32_t) * nb, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(ctx, hipMemcpyAsync(a.task_end.data(), a.d_block_task_end.get(), sizeof(uint32_t) * nb, hipMemcpyDeviceToHost, stream));
   HIP_TRY(ctx, hipStreamSynchronize(stream));
   return 0;
 }
@@ -1380,12 +1330,12 @@ int adaptive_task_prefix(LumContext* ctx, hipStream_t stream) {
 int adaptive_finish_build(LumContext* ctx, hipStream_t stream) {
   LumContext::Adaptive& a = ctx->adaptive;
   const uint32_t nb = a.num_blocks, chunks = (nb + kAdaptiveSumChunk - 1) / kAdaptiveSumChunk;
-  hipLaunchKernelGGL(k_adaptive_sum_chunks, dim3((chunks + 63) / 64), dim3(64), 0, stream, (const float*) a.d_block_variance, nb, a.d_partial);
-  hipLaunchKernelGGL(k_adaptive_sum_total, dim3(1), dim3(1), 0, stream, (const float*) a.d_partial, chunks, a.d_partial + chunks);
-  hipLaunchKernelGGL(k_adaptive_stage_counts, dim3((nb + 255) / 256), dim3(256), 0, stream, (const float*) a.d_block_variance, (const float*) (a.d_partial + chunks), nb,
-                     a.stage_id, a.params.max_sampling_rate, a.params.avg_sampling_rate, a.d_stage_counts, a.d_block_tasks, (const uint8_t*) a.d_block_mask);
+  hipLaunchKernelGGL(k_adaptive_sum_chunks, dim3((chunks + 63) / 64), dim3(64), 0, stream, (const float*) a.d_block_variance.get(), nb, a.d_partial.get());
+  hipLaunchKernelGGL(k_adaptive_sum_total, dim3(1), dim3(1), 0, stream, (const float*) a.d_partial.get(), chunks, a.d_partial.get() + chunks);
+  hipLaunchKernelGGL(k_adaptive_stage_counts, dim3((nb + 255) / 256), dim3(256), 0, stream, (const float*) a.d_block_variance.get(), (const float*) (a.d_partial.get() + chunks), nb,
+                     a.stage_id, a.params.max_sampling_rate, a.params.avg_sampling_rate, a.d_stage_counts.get(), a.d_block_tasks.get(), (const uint8_t*) a.d_block_mask.get());
   HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipMemcpyAsync(&a.variance_total, a.d_partial + chunks, sizeof(float), hipMemcpyDeviceToHost, stream));
+  HIP_TRY(ctx, hipMemcpyAsync(&a.variance_total, a.d_partial.get() + chunks, sizeof(float), hipMemcpyDeviceToHost, stream));
   if (adaptive_task_prefix(ctx, stream)) return 1;
   a.stage_id++;
   a.build_pending = false;
@@ -1420,16 +1370,16 @@ int adaptive_execute(LumContext* ctx, hipStream_t stream, uint32_t merged) {
     pass.task_end = a.task_end[end - 1] * merged;
     const uint32_t N = pass.task_end - pass.task_begin;
     if (ensure_work(ctx, N)) return 1;
-    HIP_TRY(ctx, hipMemsetAsync(ctx->d_ctrl, 0, sizeof(uint32_t) * kCtlStride * (sc.max_ray_depth + 2), stream));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->d_ctrl.get(), 0, sizeof(uint32_t) * kCtlStride * (sc.max_ray_depth + 2), stream));
     {
       Launch l(ctx, stream, LUMC_KERNEL_GENERATE);
-      ctx->wf->generate_adaptive(grid_for(N), stream, sc, view, pass, ctx->queue[0], ctx->d_results, ctx->d_ctrl + kCtlPaths, ctx->lens, ctx->camera);
+      ctx->wf->generate_adaptive(grid_for(N), stream, sc, view, pass, ctx->queue[0], ctx->d_results, ctx->d_ctrl.get() + kCtlPaths, ctx->lens, ctx->camera);
     }
     if (wavefront_depths(ctx, stream, N)) return 1;
     {
       Launch l(ctx, stream, LUMC_KERNEL_ACCUMULATE);
       hipLaunchKernelGGL(k_accumulate_adaptive, dim3(grid_for((end - block) * 16)), dim3(kBlock), 0, stream, view, pass, sc.width, sc.height, (const float4*) ctx->d_results,
-                         ctx->d_first_moment, ctx->d_second_moment);
+                         ctx->d_first_moment.get(), ctx->d_second_moment.get());
     }
     HIP_TRY(ctx, hipGetLastError());
     block = end;
@@ -1447,7 +1397,7 @@ int lumc_adaptive_begin(LumContext* ctx, const LumAdaptiveParams* params) {
     return 1;
   }
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  free_adaptive(ctx);
+  ctx->adaptive = LumContext::Adaptive();
   LumContext::Adaptive& a = ctx->adaptive;
   a.params = *params;
   // adaptive_sampler_setup, device_adaptive_sampler.c:40-58
@@ -1458,15 +1408,15 @@ int lumc_adaptive_begin(LumContext* ctx, const LumAdaptiveParams* params) {
   a.blocks_y = (ctx->scene.height + 3u) >> kAdaptiveBlockLog;
   a.num_blocks = a.blocks_x * a.blocks_y;
   const uint32_t nb = a.num_blocks, chunks = (nb + kAdaptiveSumChunk - 1) / kAdaptiveSumChunk;
-  HIP_TRY(ctx, hipMalloc((void**) &a.d_stage_counts, sizeof(uint32_t) * nb));
-  HIP_TRY(ctx, hipMalloc((void**) &a.d_block_tasks, sizeof(uint32_t) * nb));
-  HIP_TRY(ctx, hipMalloc((void**) &a.d_block_task_end, sizeof(uint32_t) * nb));
-  HIP_TRY(ctx, hipMalloc((void**) &a.d_block_variance, sizeof(float) * nb));
-  HIP_TRY(ctx, hipMalloc((void**) &a.d_partial, sizeof(float) * (chunks + 1)));
-  HIP_TRY(ctx, hipMemset(a.d_stage_counts, 0, sizeof(uint32_t) * nb));
-  HIP_TRY(ctx, hipMemset(a.d_block_variance, 0, sizeof(float) * nb));
-  HIP_TRY(ctx, hipcub::DeviceScan::InclusiveSum(nullptr, a.scan_temp_bytes, a.d_block_tasks, a.d_block_task_end, (int) nb, (hipStream_t) 0));
-  HIP_TRY(ctx, hipMalloc(&a.d_scan_temp, std::max<size_t>(a.scan_temp_bytes, 16)));
+  HIP_TRY(ctx, a.d_stage_counts.resize(nb));
+  HIP_TRY(ctx, a.d_block_tasks.resize(nb));
+  HIP_TRY(ctx, a.d_block_task_end.resize(nb));
+  HIP_TRY(ctx, a.d_block_variance.resize(nb));
+  HIP_TRY(ctx, a.d_partial.resize(chunks + 1));
+  HIP_TRY(ctx, hipMemset(a.d_stage_counts.get(), 0, sizeof(uint32_t) * nb));
+  HIP_TRY(ctx, hipMemset(a.d_block_variance.get(), 0, sizeof(float) * nb));
+  HIP_TRY(ctx, hipcub::DeviceScan::InclusiveSum(nullptr, a.scan_temp_bytes, a.d_block_tasks.get(), a.d_block_task_end.get(), (int) nb, (hipStream_t) 0));
+  HIP_TRY(ctx, a.d_scan_temp.resize(std::max<size_t>(a.scan_temp_bytes, 16)));
   a.active = true;
   return lumc_clear_accumulators(ctx);
 }
@@ -1530,9 +1480,9 @@ int lumc_adaptive_set_partition(LumContext* ctx, const uint8_t* block_mask) {
   for (uint32_t s = 0; s <= kAdaptiveStages; s++)
     if (a.executions[s]) { ctx->error = "lumc_adaptive_set_partition: call it before the first execution"; return 1; }
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  if (!a.d_block_mask) HIP_TRY(ctx, hipMalloc((void**) &a.d_block_mask, a.num_blocks));
-  HIP_TRY(ctx, hipMemcpy(a.d_block_mask, block_mask, a.num_blocks, hipMemcpyHostToDevice));
-  hipLaunchKernelGGL(k_adaptive_uniform_tasks, dim3((a.num_blocks + 255) / 256), dim3(256), 0, 0, (const uint8_t*) a.d_block_mask, a.num_blocks, a.d_block_tasks);
+  if (!a.d_block_mask) HIP_TRY(ctx, a.d_block_mask.resize(a.num_blocks));
+  HIP_TRY(ctx, hipMemcpy(a.d_block_mask.get(), block_mask, a.num_blocks, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_adaptive_uniform_tasks, dim3((a.num_blocks + 255) / 256), dim3(256), 0, 0, (const uint8_t*) a.d_block_mask.get(), a.num_blocks, a.d_block_tasks.get());
   HIP_TRY(ctx, hipGetLastError());
   return adaptive_task_prefix(ctx, (hipStream_t) 0);
 }
@@ -1541,7 +1491,7 @@ int lumc_adaptive_variance(LumContext* ctx, float* block_variance) {
   if (!ctx || !ctx->adaptive.active || !block_variance) { if (ctx) ctx->error = "lumc_adaptive_variance: adaptive mode is not active or null buffer"; return 1; }
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   if (adaptive_compute_variance(ctx, (hipStream_t) 0)) return 1;
-  HIP_TRY(ctx, hipMemcpy(block_variance, ctx->adaptive.d_block_variance, sizeof(float) * ctx->adaptive.num_blocks, hipMemcpyDeviceToHost));
+  HIP_TRY(ctx, hipMemcpy(block_variance, ctx->adaptive.d_block_variance.get(), sizeof(float) * ctx->adaptive.num_blocks, hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -1550,7 +1500,7 @@ int lumc_adaptive_build_from(LumContext* ctx, const float* block_variance) {
   LumContext::Adaptive& a = ctx->adaptive;
   if (a.stage_id >= kAdaptiveStages) { ctx->error = "lumc_adaptive_build_from: the last stage is already running"; return 1; }
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  HIP_TRY(ctx, hipMemcpy(a.d_block_variance, block_variance, sizeof(float) * a.num_blocks, hipMemcpyHostToDevice));
+  HIP_TRY(ctx, hipMemcpy(a.d_block_variance.get(), block_variance, sizeof(float) * a.num_blocks, hipMemcpyHostToDevice));
   return adaptive_finish_build(ctx, (hipStream_t) 0);
 }
 
@@ -1571,8 +1521,8 @@ int lumc_adaptive_download(LumContext* ctx, uint32_t* stage_counts, float* block
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   HIP_TRY(ctx, hipDeviceSynchronize());
   const LumContext::Adaptive& a = ctx->adaptive;
-  if (stage_counts) HIP_TRY(ctx, hipMemcpy(stage_counts, a.d_stage_counts, sizeof(uint32_t) * a.num_blocks, hipMemcpyDeviceToHost));
-  if (block_variance) HIP_TRY(ctx, hipMemcpy(block_variance, a.d_block_variance, sizeof(float) * a.num_blocks, hipMemcpyDeviceToHost));
+  if (stage_counts) HIP_TRY(ctx, hipMemcpy(stage_counts, a.d_stage_counts.get(), sizeof(uint32_t) * a.num_blocks, hipMemcpyDeviceToHost));
+  if (block_variance) HIP_TRY(ctx, hipMemcpy(block_variance, a.d_block_variance.get(), sizeof(float) * a.num_blocks, hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -1580,13 +1530,20 @@ int lumc_adaptive_end(LumContext* ctx) {
   if (!ctx) return 1;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   HIP_TRY(ctx, hipDeviceSynchronize());
-  free_adaptive(ctx);
+  ctx->adaptive = LumContext::Adaptive();
+  return 0;
+}
+
+// The context's result image of n pixels: what lumc_generate_result* write when the caller passes no image of its own.
+static int result_image(LumContext* ctx, uint32_t n, float** out) {
+  if (ctx->d_frame_result.count() != 3 * (size_t) n) HIP_TRY(ctx, ctx->d_frame_result.resize(3 * (size_t) n));
+  *out = ctx->d_frame_result.get();
   return 0;
 }
 
 int lumc_generate_result(LumContext* ctx, uint32_t mode, uint32_t local_error_minimization, uint32_t uniform_samples, float exposure, const LumOutputParams* tone,
                          float* d_result, void* stream_) {
-  const bool framed = ctx && ctx->exchange.use_frame && ctx->exchange.d_frame && ctx->has_scene && ctx->exchange.frame_capacity == ctx->scene.width * ctx->scene.height;
+  const bool framed = ctx && ctx->exchange.use_frame && ctx->exchange.d_frame && ctx->has_scene && ctx->exchange.frame_pixels() == ctx->scene.width * ctx->scene.height;
   if (!ctx || !ctx->has_scene || (!framed && (!ctx->d_first_moment || ctx->d_pixels || ctx->num_pixels != ctx->scene.width * ctx->scene.height))) {
     if (ctx) ctx->error = "lumc_generate_result: needs the full-frame accumulators";
     return 1;
@@ -1594,17 +1551,9 @@ int lumc_generate_result(LumContext* ctx, uint32_t mode, uint32_t local_error_mi
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   hipStream_t stream = (hipStream_t) stream_;
   const uint32_t n = ctx->scene.width * ctx->scene.height;
-  const float* src_fm = framed ? ctx->exchange.d_frame : ctx->d_first_moment;
-  const float* src_sm = framed ? ctx->exchange.d_frame + 3 * (size_t) n : ctx->d_second_moment;
-  if (!d_result) {
-    if (ctx->frame_result_pixels != n) {
-      if (ctx->d_frame_result) (void) hipFree(ctx->d_frame_result);
-      ctx->d_frame_result = nullptr; ctx->frame_result_pixels = 0;
-      HIP_TRY(ctx, hipMalloc((void**) &ctx->d_frame_result, sizeof(float) * 3 * (size_t) n));
-      ctx->frame_result_pixels = n;
-    }
-    d_result = ctx->d_frame_result;
-  }
+  const float* src_fm = framed ? ctx->exchange.d_frame.get() : ctx->d_first_moment.get();
+  const float* src_sm = framed ? ctx->exchange.d_frame.get() + 3 * (size_t) n : ctx->d_second_moment.get();
+  if (!d_result && result_image(ctx, n, &d_result)) return 1;
   AdaptiveView view;
   std::memset(&view, 0, sizeof(view));
   if (ctx->adaptive.active) view = adaptive_view(ctx);
@@ -1625,7 +1574,7 @@ int lumc_generate_result_host(LumContext* ctx, uint32_t mode, uint32_t local_err
   if (!ctx || !result) { if (ctx) ctx->error = "lumc_generate_result_host: null argument"; return 1; }
   if (lumc_generate_result(ctx, mode, local_error_minimization, uniform_samples, exposure, tone, nullptr, nullptr)) return 1;
   HIP_TRY(ctx, hipDeviceSynchronize());
-  HIP_TRY(ctx, hipMemcpy(result, ctx->d_frame_result, sizeof(float) * 3 * (size_t) ctx->scene.width * ctx->scene.height, hipMemcpyDeviceToHost));
+  HIP_TRY(ctx, hipMemcpy(result, ctx->d_frame_result.get(), sizeof(float) * 3 * (size_t) ctx->scene.width * ctx->scene.height, hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -1638,20 +1587,12 @@ int lumc_generate_result_undersampled(LumContext* ctx, uint32_t stage, uint32_t 
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   hipStream_t stream = (hipStream_t) stream_;
   const uint32_t n = ctx->num_pixels;
-  if (!d_result) {
-    if (ctx->frame_result_pixels != n) {
-      if (ctx->d_frame_result) (void) hipFree(ctx->d_frame_result);
-      ctx->d_frame_result = nullptr; ctx->frame_result_pixels = 0;
-      HIP_TRY(ctx, hipMalloc((void**) &ctx->d_frame_result, sizeof(float) * 3 * (size_t) n));
-      ctx->frame_result_pixels = n;
-    }
-    d_result = ctx->d_frame_result;
-  }
+  if (!d_result && result_image(ctx, n, &d_result)) return 1;
   const uint32_t compact = (ctx->scene.width >> stage) * (ctx->scene.height >> stage);
   if (compact == 0) return 0;
   {
     Launch l(ctx, stream, LUMC_KERNEL_OUTPUT);
-    hipLaunchKernelGGL(k_result_undersampled, dim3(grid_for(compact)), dim3(256), 0, stream, (const float*) ctx->d_first_moment, ctx->scene.width, ctx->scene.height, stage, iteration,
+    hipLaunchKernelGGL(k_result_undersampled, dim3(grid_for(compact)), dim3(256), 0, stream, (const float*) ctx->d_first_moment.get(), ctx->scene.width, ctx->scene.height, stage, iteration,
                        d_result);
   }
   HIP_TRY(ctx, hipGetLastError());
@@ -1663,23 +1604,23 @@ int lumc_generate_result_undersampled_host(LumContext* ctx, uint32_t stage, uint
   if (lumc_generate_result_undersampled(ctx, stage, iteration, nullptr, nullptr)) return 1;
   HIP_TRY(ctx, hipDeviceSynchronize());
   const size_t compact = (size_t) (ctx->scene.width >> stage) * (ctx->scene.height >> stage);
-  HIP_TRY(ctx, hipMemcpy(result, ctx->d_frame_result, sizeof(float) * 3 * compact, hipMemcpyDeviceToHost));
+  HIP_TRY(ctx, hipMemcpy(result, ctx->d_frame_result.get(), sizeof(float) * 3 * compact, hipMemcpyDeviceToHost));
   return 0;
 }
 
 int lumc_download_result_image(LumContext* ctx, float* result) {
-  if (!ctx || !result || !ctx->d_frame_result || !ctx->has_scene || ctx->frame_result_pixels != ctx->scene.width * ctx->scene.height) { if (ctx) ctx->error = "lumc_download_result_image: no result image"; return 1; }
+  if (!ctx || !result || !ctx->d_frame_result || !ctx->has_scene || ctx->d_frame_result.count() != 3 * (size_t) (ctx->scene.width * ctx->scene.height)) { if (ctx) ctx->error = "lumc_download_result_image: no result image"; return 1; }
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   HIP_TRY(ctx, hipDeviceSynchronize());
-  HIP_TRY(ctx, hipMemcpy(result, ctx->d_frame_result, sizeof(float) * 3 * (size_t) ctx->frame_result_pixels, hipMemcpyDeviceToHost));
+  HIP_TRY(ctx, hipMemcpy(result, ctx->d_frame_result.get(), sizeof(float) * ctx->d_frame_result.count(), hipMemcpyDeviceToHost));
   return 0;
 }
-const float* lumc_result_image(LumContext* ctx) { return ctx ? ctx->d_frame_result : nullptr; }
+const float* lumc_result_image(LumContext* ctx) { return ctx ? ctx->d_frame_result.get() : nullptr; }
 
 // _device_post_bloom_apply, device/device_post.c:56-139
 int lumc_post_bloom(LumContext* ctx, float* d_image, uint32_t full_width, uint32_t full_height, uint32_t undersampling_stage, float blend, void* stream_) {
   if (!ctx) return 1;
-  if (!d_image) d_image = ctx->d_frame_result;
+  if (!d_image) d_image = ctx->d_frame_result.get();
   if (!d_image || full_width == 0 || full_height == 0) { ctx->error = "lumc_post_bloom: no image"; return 1; }
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   hipStream_t stream = (hipStream_t) stream_;
@@ -1687,12 +1628,11 @@ int lumc_post_bloom(LumContext* ctx, float* d_image, uint32_t full_width, uint32
   for (uint32_t m = std::min(full_width, full_height); m > 1; m >>= 1) chain++;
   if (undersampling_stage + 1 >= chain) return 0;  // too coarse for a mip chain (device_post.c:62-64)
   if (ctx->bloom_width != full_width || ctx->bloom_height != full_height) {
-    for (float* m : ctx->bloom_mips) (void) hipFree(m);
     ctx->bloom_mips.clear(); ctx->bloom_width = ctx->bloom_height = 0;
     for (uint32_t i = 0; i < chain; i++) {
-      float* m = nullptr;
-      HIP_TRY(ctx, hipMalloc((void**) &m, sizeof(float) * (size_t) (full_width >> (i + 1)) * (full_height >> (i + 1))));
-      ctx->bloom_mips.push_back(m);
+      DeviceBuffer<float> m;
+      HIP_TRY(ctx, m.resize((size_t) (full_width >> (i + 1)) * (full_height >> (i + 1))));
+      ctx->bloom_mips.push_back(std::move(m));
     }
     ctx->bloom_width = full_width; ctx->bloom_height = full_height;
   }
@@ -1701,15 +1641,15 @@ int lumc_post_bloom(LumContext* ctx, float* d_image, uint32_t full_width, uint32
   Launch l(ctx, stream, LUMC_KERNEL_OUTPUT);
   for (uint32_t c = 0; c < 3; c++) {
     float* image = d_image + c * plane;
-    std::vector<float*>& mip = ctx->bloom_mips;
-    hipLaunchKernelGGL(k_post_downsample, dim3(grid_for((width >> 1) * (height >> 1))), dim3(256), 0, stream, (const float*) image, width, height, mip[0], width >> 1, height >> 1);
+    const std::vector<DeviceBuffer<float>>& mip = ctx->bloom_mips;
+    hipLaunchKernelGGL(k_post_downsample, dim3(grid_for((width >> 1) * (height >> 1))), dim3(256), 0, stream, (const float*) image, width, height, mip[0].get(), width >> 1, height >> 1);
     for (uint32_t i = 0; i + 1 < mips; i++)
-      hipLaunchKernelGGL(k_post_downsample, dim3(grid_for((width >> (i + 2)) * (height >> (i + 2)))), dim3(256), 0, stream, (const float*) mip[i], width >> (i + 1), height >> (i + 1),
-                         mip[i + 1], width >> (i + 2), height >> (i + 2));
+      hipLaunchKernelGGL(k_post_downsample, dim3(grid_for((width >> (i + 2)) * (height >> (i + 2)))), dim3(256), 0, stream, (const float*) mip[i].get(), width >> (i + 1), height >> (i + 1),
+                         mip[i + 1].get(), width >> (i + 2), height >> (i + 2));
     for (uint32_t i = mips - 1; i > 0; i--)
-      hipLaunchKernelGGL(k_post_upsample, dim3(grid_for((width >> i) * (height >> i))), dim3(256), 0, stream, (const float*) mip[i], width >> (i + 1), height >> (i + 1), mip[i - 1],
+      hipLaunchKernelGGL(k_post_upsample, dim3(grid_for((width >> i) * (height >> i))), dim3(256), 0, stream, (const float*) mip[i].get(), width >> (i + 1), height >> (i + 1), mip[i - 1].get(),
                          width >> i, height >> i, 1.0f, 1.0f);
-    hipLaunchKernelGGL(k_post_upsample, dim3(grid_for(width * height)), dim3(256), 0, stream, (const float*) mip[0], width >> 1, height >> 1, image, width, height, blend / mips,
+    hipLaunchKernelGGL(k_post_upsample, dim3(grid_for(width * height)), dim3(256), 0, stream, (const float*) mip[0].get(), width >> 1, height >> 1, image, width, height, blend / mips,
                        1.0f - blend);
   }
   HIP_TRY(ctx, hipGetLastError());
@@ -1719,19 +1659,18 @@ int lumc_post_bloom(LumContext* ctx, float* d_image, uint32_t full_width, uint32
 int lumc_post_bloom_host(LumContext* ctx, float* image, uint32_t full_width, uint32_t full_height, uint32_t undersampling_stage, float blend) {
   if (!ctx || !image) { if (ctx) ctx->error = "lumc_post_bloom_host: null argument"; return 1; }
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const size_t bytes = sizeof(float) * 3 * (size_t) (full_width >> undersampling_stage) * (full_height >> undersampling_stage);
-  float* d = nullptr;
-  HIP_TRY(ctx, hipMalloc((void**) &d, bytes));
-  int rc = 1;
-  if (hipMemcpy(d, image, bytes, hipMemcpyHostToDevice) == hipSuccess && lumc_post_bloom(ctx, d, full_width, full_height, undersampling_stage, blend, nullptr) == 0 &&
-      hipDeviceSynchronize() == hipSuccess && hipMemcpy(image, d, bytes, hipMemcpyDeviceToHost) == hipSuccess)
-    rc = 0;
-  else if (ctx->error.empty()) ctx->error = "lumc_post_bloom_host: transfer failed";
-  (void) hipFree(d);
-  return rc;
+  const size_t count = 3 * (size_t) (full_width >> undersampling_stage) * (full_height >> undersampling_stage);
+  DeviceBuffer<float> d;
+  HIP_TRY(ctx, d.assign(image, count));
+  if (lumc_post_bloom(ctx, d.get(), full_width, full_height, undersampling_stage, blend, nullptr)) return 1;
+  HIP_TRY(ctx, hipDeviceSynchronize());
+  HIP_TRY(ctx, hipMemcpy(image, d.get(), sizeof(float) * count, hipMemcpyDeviceToHost));
+  return 0;
 }
 
 // ---- denoiser (dev_denoise.h) ----
+static size_t guide_pixels(const LumContext* ctx) { return ctx->d_guides.count() / kGuideSumPlanes; }  // the frame the guide planes were allocated for
+
 int lumc_render_guides(LumContext* ctx, uint32_t num_samples, void* stream_) {
   if (!ctx || !ctx->has_scene) { if (ctx) ctx->error = "lumc_render_guides: no scene"; return 1; }
   if (num_samples == 0) num_samples = 4;
@@ -1743,39 +1682,33 @@ int lumc_render_guides(LumContext* ctx, uint32_t num_samples, void* stream_) {
   const uint32_t n = sc.width * sc.height;
   if (n == 0 || sc.width > 0xFFFFu || sc.height > 0xFFFFu) { ctx->error = "lumc_render_guides: frame size"; return 1; }
   ctx->guides_valid = false;
-  if (ctx->guide_pixels != n) {
-    if (ctx->d_guides) (void) hipFree(ctx->d_guides);
-    ctx->d_guides = nullptr; ctx->guide_pixels = 0;
-    HIP_TRY(ctx, hipMalloc((void**) &ctx->d_guides, sizeof(float) * kGuideSumPlanes * (size_t) n));
-    ctx->guide_pixels = n;
-  }
+  if (guide_pixels(ctx) != n) HIP_TRY(ctx, ctx->d_guides.resize(kGuideSumPlanes * (size_t) n));
   if (ensure_work(ctx, n)) return 1;
-  HIP_TRY(ctx, hipMemsetAsync(ctx->d_guides, 0, sizeof(float) * kGuideSumPlanes * (size_t) n, stream));
+  HIP_TRY(ctx, hipMemsetAsync(ctx->d_guides.get(), 0, sizeof(float) * kGuideSumPlanes * (size_t) n, stream));
   const WavefrontKernels& wf = *ctx->wf;
-  const size_t lds_dyn = (size_t) ctx->lds_nodes * kNodeBytes + LUM_LDS_STACK_BYTES;
   // one sample id of every pixel per pass: the closest-hit pass of the debug shading modes (wavefront_depths), then k_guide adds into the planes
   for (uint32_t s = 0; s < num_samples; s++) {
     PassParams pp{nullptr, n, 1u, s};
-    HIP_TRY(ctx, hipMemsetAsync(ctx->d_ctrl, 0, sizeof(uint32_t) * kCtlStride * (sc.max_ray_depth + 2), stream));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->d_ctrl.get(), 0, sizeof(uint32_t) * kCtlStride * (sc.max_ray_depth + 2), stream));
     {
       Launch l(ctx, stream, LUMC_KERNEL_GENERATE);
-      wf.generate(grid_for(n), stream, sc, pp, ctx->queue[0], ctx->d_results, ctx->d_ctrl + kCtlPaths, ctx->lens, ctx->camera);
+      wf.generate(grid_for(n), stream, sc, pp, ctx->queue[0], ctx->d_results, ctx->d_ctrl.get() + kCtlPaths, ctx->lens, ctx->camera);
     }
     {
       Launch l(ctx, stream, LUMC_KERNEL_TRACE);
-      wf.trace(grid_persistent(ctx, n), lds_dyn, stream, sc, ctx->queue[0], nullptr, ctx->d_ctrl, ctx->d_counters, ctx->lds_nodes);
+      wf.trace(grid_persistent(ctx, n), ray_kernel_lds(ctx), stream, sc, ctx->queue[0], nullptr, ctx->d_ctrl.get(), ctx->d_counters.get(), ctx->lds_nodes);
     }
-    if (sc.particles_active) trace_particles(ctx, stream, ctx->queue[0], ctx->d_ctrl, n);
+    if (sc.particles_active) trace_particles(ctx, stream, ctx->queue[0], ctx->d_ctrl.get(), n);
     if (sc.ocean_active) {
       Launch l(ctx, stream, LUMC_KERNEL_TRACE);
-      wf.trace_ocean(grid_for(n), stream, sc, ctx->queue[0], (const uint32_t*) ctx->d_ctrl);
+      wf.trace_ocean(grid_for(n), stream, sc, ctx->queue[0], (const uint32_t*) ctx->d_ctrl.get());
     }
     Launch l(ctx, stream, LUMC_KERNEL_OUTPUT);
-    wf.guide(grid_for(n), stream, sc, ctx->queue[0], (const uint32_t*) ctx->d_ctrl, ctx->d_guides, n);
+    wf.guide(grid_for(n), stream, sc, ctx->queue[0], (const uint32_t*) ctx->d_ctrl.get(), ctx->d_guides.get(), n);
   }
   {
     Launch l(ctx, stream, LUMC_KERNEL_OUTPUT);
-    wf.guide_normalise(grid_for(n), stream, ctx->d_guides, n, num_samples);
+    wf.guide_normalise(grid_for(n), stream, ctx->d_guides.get(), n, num_samples);
   }
   HIP_TRY(ctx, hipGetLastError());
   ctx->guides_valid = true;
@@ -1786,10 +1719,10 @@ int lumc_download_guides(LumContext* ctx, float* albedo, float* normal, float* d
   if (!ctx || !ctx->guides_valid) { if (ctx) ctx->error = "lumc_download_guides: no guides (lumc_render_guides)"; return 1; }
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   HIP_TRY(ctx, hipDeviceSynchronize());
-  const size_t n = ctx->guide_pixels;
-  if (albedo) HIP_TRY(ctx, hipMemcpy(albedo, ctx->d_guides, sizeof(float) * 3 * n, hipMemcpyDeviceToHost));
-  if (normal) HIP_TRY(ctx, hipMemcpy(normal, ctx->d_guides + 3 * n, sizeof(float) * 3 * n, hipMemcpyDeviceToHost));
-  if (depth) HIP_TRY(ctx, hipMemcpy(depth, ctx->d_guides + 6 * n, sizeof(float) * n, hipMemcpyDeviceToHost));
+  const size_t n = guide_pixels(ctx);
+  if (albedo) HIP_TRY(ctx, hipMemcpy(albedo, ctx->d_guides.get(), sizeof(float) * 3 * n, hipMemcpyDeviceToHost));
+  if (normal) HIP_TRY(ctx, hipMemcpy(normal, ctx->d_guides.get() + 3 * n, sizeof(float) * 3 * n, hipMemcpyDeviceToHost));
+  if (depth) HIP_TRY(ctx, hipMemcpy(depth, ctx->d_guides.get() + 6 * n, sizeof(float) * n, hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -1809,39 +1742,37 @@ int lumc_set_denoise_form(LumContext* ctx, int lds) {
 int lumc_denoise(LumContext* ctx, const LumDenoiseParams* params, float* d_image, void* stream_) {
   if (!ctx || !params || !ctx->has_scene) { if (ctx) ctx->error = "lumc_denoise: no scene or null argument"; return 1; }
   const uint32_t n = ctx->scene.width * ctx->scene.height;
-  if (!ctx->guides_valid || ctx->guide_pixels != n) { ctx->error = "lumc_denoise: no guides for this frame (lumc_render_guides)"; return 1; }
-  const bool framed = ctx->exchange.use_frame && ctx->exchange.d_frame && ctx->exchange.frame_capacity == n;
+  if (!ctx->guides_valid || guide_pixels(ctx) != n) { ctx->error = "lumc_denoise: no guides for this frame (lumc_render_guides)"; return 1; }
+  const bool framed = ctx->exchange.use_frame && ctx->exchange.d_frame && ctx->exchange.frame_pixels() == n;
   if (!framed && (!ctx->d_first_moment || ctx->d_pixels || ctx->num_pixels != n)) { ctx->error = "lumc_denoise: needs the full-frame accumulators"; return 1; }
-  if (!d_image) d_image = (ctx->frame_result_pixels == n) ? ctx->d_frame_result : nullptr;
+  if (!d_image) d_image = (ctx->d_frame_result.count() == 3 * (size_t) n) ? ctx->d_frame_result.get() : nullptr;
   if (!d_image) { ctx->error = "lumc_denoise: no image"; return 1; }
   if (!ctx->adaptive.active && params->uniform_samples == 0) { ctx->error = "lumc_denoise: no samples"; return 1; }
   if (!(params->sigma_luminance > 0.0f) || !(params->sigma_normal >= 0.0f) || !(params->sigma_depth > 0.0f)) { ctx->error = "lumc_denoise: sigmas must be positive"; return 1; }
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   hipStream_t stream = (hipStream_t) stream_;
-  if (ctx->denoise_pixels != n) {
-    for (void*& r : ctx->d_denoise_rec) { if (r) (void) hipFree(r); r = nullptr; }
-    ctx->denoise_pixels = 0;
-    for (void*& r : ctx->d_denoise_rec) HIP_TRY(ctx, hipMalloc(&r, 16 * (size_t) n));
-    ctx->denoise_pixels = n;
+  if (ctx->d_denoise_rec[2].count() != n) {  // (the last of the three: a set that was not completed is allocated again)
+    for (auto& r : ctx->d_denoise_rec) r.reset();
+    for (auto& r : ctx->d_denoise_rec) HIP_TRY(ctx, r.resize(n));
   }
-  const float* src_fm = framed ? ctx->exchange.d_frame : ctx->d_first_moment;
-  const float* src_sm = framed ? ctx->exchange.d_frame + 3 * (size_t) n : ctx->d_second_moment;
+  const float* src_fm = framed ? ctx->exchange.d_frame.get() : ctx->d_first_moment.get();
+  const float* src_sm = framed ? ctx->exchange.d_frame.get() + 3 * (size_t) n : ctx->d_second_moment.get();
   AdaptiveView view;
   std::memset(&view, 0, sizeof(view));
   if (ctx->adaptive.active) view = adaptive_view(ctx);
   DenoiseArgs args{ctx->scene.width, ctx->scene.height, 1u, params->uniform_samples, params->sigma_luminance, params->sigma_normal, params->sigma_depth};
   const uint32_t iterations = std::min(params->iterations, 6u);
-  float4* rec_a[2] = {(float4*) ctx->d_denoise_rec[0], (float4*) ctx->d_denoise_rec[1]};
-  uint4* rec_b = (uint4*) ctx->d_denoise_rec[2];
+  float4* rec_a[2] = {ctx->d_denoise_rec[0].get(), ctx->d_denoise_rec[1].get()};
+  uint4* rec_b = (uint4*) ctx->d_denoise_rec[2].get();
   const WavefrontKernels& wf = *ctx->wf;
   Launch l(ctx, stream, LUMC_KERNEL_OUTPUT);
-  wf.denoise_prepare(grid_for(n), stream, view, args, src_fm, src_sm, d_image, ctx->d_guides, rec_a[0], rec_b);
+  wf.denoise_prepare(grid_for(n), stream, view, args, src_fm, src_sm, d_image, ctx->d_guides.get(), rec_a[0], rec_b);
   uint32_t cur = 0;
   for (uint32_t i = 0; i < iterations; i++, cur ^= 1u) {
     args.step = 1u << i;
     wf.denoise_atrous(stream, args, rec_a[cur], rec_b, rec_a[cur ^ 1u], ctx->denoise_lds != 0);
   }
-  wf.denoise_finish(grid_for(n), stream, args, rec_a[cur], ctx->d_guides, d_image);
+  wf.denoise_finish(grid_for(n), stream, args, rec_a[cur], ctx->d_guides.get(), d_image);
   HIP_TRY(ctx, hipGetLastError());
   return 0;
 }
@@ -1849,16 +1780,13 @@ int lumc_denoise(LumContext* ctx, const LumDenoiseParams* params, float* d_image
 int lumc_denoise_host(LumContext* ctx, const LumDenoiseParams* params, float* image) {
   if (!ctx || !image || !ctx->has_scene) { if (ctx) ctx->error = "lumc_denoise_host: null argument"; return 1; }
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const size_t bytes = sizeof(float) * 3 * (size_t) ctx->scene.width * ctx->scene.height;
-  float* d = nullptr;
-  HIP_TRY(ctx, hipMalloc((void**) &d, bytes));
-  int rc = 1;
-  if (hipMemcpy(d, image, bytes, hipMemcpyHostToDevice) == hipSuccess && lumc_denoise(ctx, params, d, nullptr) == 0 && hipDeviceSynchronize() == hipSuccess &&
-      hipMemcpy(image, d, bytes, hipMemcpyDeviceToHost) == hipSuccess)
-    rc = 0;
-  else if (ctx->error.empty()) ctx->error = "lumc_denoise_host: transfer failed";
-  (void) hipFree(d);
-  return rc;
+  const size_t count = 3 * (size_t) ctx->scene.width * ctx->scene.height;
+  DeviceBuffer<float> d;
+  HIP_TRY(ctx, d.assign(image, count));
+  if (lumc_denoise(ctx, params, d.get(), nullptr)) return 1;
+  HIP_TRY(ctx, hipDeviceSynchronize());
+  HIP_TRY(ctx, hipMemcpy(image, d.get(), sizeof(float) * count, hipMemcpyDeviceToHost));
+  return 0;
 }
 
 int lumc_synchronize(LumContext* ctx) {
@@ -1871,20 +1799,20 @@ int lumc_synchronize(LumContext* ctx) {
 int lumc_download_accumulators(LumContext* ctx, float* first_moment, float* second_moment) {
   if (!ctx || !ctx->d_first_moment) return 1;
   HIP_TRY(ctx, hipDeviceSynchronize());
-  if (first_moment) HIP_TRY(ctx, hipMemcpy(first_moment, ctx->d_first_moment, sizeof(float) * 3 * (size_t) ctx->num_pixels, hipMemcpyDeviceToHost));
-  if (second_moment) HIP_TRY(ctx, hipMemcpy(second_moment, ctx->d_second_moment, sizeof(float) * (size_t) ctx->num_pixels, hipMemcpyDeviceToHost));
+  if (first_moment) HIP_TRY(ctx, hipMemcpy(first_moment, ctx->d_first_moment.get(), sizeof(float) * 3 * (size_t) ctx->num_pixels, hipMemcpyDeviceToHost));
+  if (second_moment) HIP_TRY(ctx, hipMemcpy(second_moment, ctx->d_second_moment.get(), sizeof(float) * (size_t) ctx->num_pixels, hipMemcpyDeviceToHost));
   return 0;
 }
 
 int lumc_counters(LumContext* ctx, uint64_t out[LUMC_CNT_COUNT]) {
   if (!ctx) return 1;
   HIP_TRY(ctx, hipDeviceSynchronize());
-  HIP_TRY(ctx, hipMemcpy(out, ctx->d_counters, sizeof(uint64_t) * LUMC_CNT_COUNT, hipMemcpyDeviceToHost));
+  HIP_TRY(ctx, hipMemcpy(out, ctx->d_counters.get(), sizeof(uint64_t) * LUMC_CNT_COUNT, hipMemcpyDeviceToHost));
   return 0;
 }
 int lumc_reset_counters(LumContext* ctx) {
   if (!ctx) return 1;
-  HIP_TRY(ctx, hipMemset(ctx->d_counters, 0, sizeof(uint64_t) * LUMC_CNT_COUNT));
+  HIP_TRY(ctx, hipMemset(ctx->d_counters.get(), 0, sizeof(uint64_t) * LUMC_CNT_COUNT));
   return 0;
 }
 int lumc_set_profiling(LumContext* ctx, int enabled) {
@@ -1919,25 +1847,19 @@ int lumc_generate_output(LumContext* ctx, const LumOutputParams* params, const f
   if (!d_first_moment) {
     if (p.undersampling_stage) { ctx->error = "lumc_generate_output: an undersampled image must be passed explicitly (lumc_result_image)"; return 1; }
     if (!ctx->d_first_moment || ctx->d_pixels || ctx->num_pixels != ns) { ctx->error = "lumc_generate_output: the context does not hold a full frame of this size"; return 1; }
-    d_first_moment = ctx->d_first_moment;
+    d_first_moment = ctx->d_first_moment.get();
   }
   if (!ctx->d_bluenoise_1d) {
     const size_t bytes = (size_t) (lum_embedded_bluenoise_1d_end - lum_embedded_bluenoise_1d);
     if (bytes != 65536 * sizeof(uint16_t)) { ctx->error = "embedded 1D blue-noise mask has the wrong size"; return 1; }
-    HIP_TRY(ctx, hipMalloc((void**) &ctx->d_bluenoise_1d, bytes));
-    HIP_TRY(ctx, hipMemcpy(ctx->d_bluenoise_1d, lum_embedded_bluenoise_1d, bytes, hipMemcpyHostToDevice));
+    HIP_TRY(ctx, ctx->d_bluenoise_1d.assign((const uint16_t*) lum_embedded_bluenoise_1d, 65536));
   }
-  if (ctx->frame_output_pixels < ns) {
-    if (ctx->d_frame_output) (void) hipFree(ctx->d_frame_output);
-    ctx->d_frame_output = nullptr;
-    HIP_TRY(ctx, hipMalloc((void**) &ctx->d_frame_output, sizeof(float) * 3 * (size_t) ns));
-    ctx->frame_output_pixels = ns;
-  }
+  if (ctx->d_frame_output.count() < 3 * (size_t) ns) HIP_TRY(ctx, ctx->d_frame_output.resize(3 * (size_t) ns));
   {
     Launch l(ctx, stream, LUMC_KERNEL_OUTPUT);
-    hipLaunchKernelGGL(k_final_image, dim3(grid_for(n_out)), dim3(256), 0, stream, p, d_first_moment, ctx->d_frame_output);
-    hipLaunchKernelGGL(k_to_argb8, dim3(grid_for(p.dst_width * p.dst_height)), dim3(256), 0, stream, p, (const float*) ctx->d_frame_output,
-                       (const uint16_t*) ctx->d_bluenoise_1d, d_argb8);
+    hipLaunchKernelGGL(k_final_image, dim3(grid_for(n_out)), dim3(256), 0, stream, p, d_first_moment, ctx->d_frame_output.get());
+    hipLaunchKernelGGL(k_to_argb8, dim3(grid_for(p.dst_width * p.dst_height)), dim3(256), 0, stream, p, (const float*) ctx->d_frame_output.get(),
+                       (const uint16_t*) ctx->d_bluenoise_1d.get(), d_argb8);
   }
   HIP_TRY(ctx, hipGetLastError());
   return 0;
@@ -1947,18 +1869,13 @@ int lumc_generate_output_host(LumContext* ctx, const LumOutputParams* params, co
   if (!ctx || !params || !argb8) { if (ctx) ctx->error = "lumc_generate_output_host: null argument"; return 1; }
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   const uint32_t n = params->dst_width * params->dst_height;
-  if (ctx->argb8_pixels < n) {
-    if (ctx->d_argb8) (void) hipFree(ctx->d_argb8);
-    ctx->d_argb8 = nullptr;
-    HIP_TRY(ctx, hipMalloc((void**) &ctx->d_argb8, sizeof(uint32_t) * (size_t) n));
-    ctx->argb8_pixels = n;
-  }
-  if (lumc_generate_output(ctx, params, d_first_moment, ctx->d_argb8, nullptr)) return 1;
+  if (ctx->d_argb8.count() < n) HIP_TRY(ctx, ctx->d_argb8.resize(n));
+  if (lumc_generate_output(ctx, params, d_first_moment, ctx->d_argb8.get(), nullptr)) return 1;
   HIP_TRY(ctx, hipDeviceSynchronize());
-  HIP_TRY(ctx, hipMemcpy(argb8, ctx->d_argb8, sizeof(uint32_t) * (size_t) n, hipMemcpyDeviceToHost));
+  HIP_TRY(ctx, hipMemcpy(argb8, ctx->d_argb8.get(), sizeof(uint32_t) * (size_t) n, hipMemcpyDeviceToHost));
   if (frame_output) {
     const uint32_t uo = std::max(params->undersampling_stage, params->supersampling);
-    HIP_TRY(ctx, hipMemcpy(frame_output, ctx->d_frame_output, sizeof(float) * 3 * (size_t) (params->src_width >> uo) * (params->src_height >> uo), hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(frame_output, ctx->d_frame_output.get(), sizeof(float) * 3 * (size_t) (params->src_width >> uo) * (params->src_height >> uo), hipMemcpyDeviceToHost));
   }
   return 0;
 }
@@ -1966,24 +1883,19 @@ int lumc_generate_output_host(LumContext* ctx, const LumOutputParams* params, co
 int lumc_generate_output_from_host(LumContext* ctx, const LumOutputParams* params, const float* first_moment, uint32_t* argb8, float* frame_output) {
   if (!ctx || !params || !first_moment || !argb8) { if (ctx) ctx->error = "lumc_generate_output_from_host: null argument"; return 1; }
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const size_t bytes = sizeof(float) * 3 * (size_t) (params->src_width >> params->undersampling_stage) * (params->src_height >> params->undersampling_stage);
-  float* d = nullptr;
-  HIP_TRY(ctx, hipMalloc((void**) &d, bytes));
-  int rc = 1;
-  if (hipMemcpy(d, first_moment, bytes, hipMemcpyHostToDevice) == hipSuccess) rc = lumc_generate_output_host(ctx, params, d, argb8, frame_output);
-  else ctx->error = "lumc_generate_output_from_host: upload failed";
-  (void) hipFree(d);
-  return rc;
+  DeviceBuffer<float> d;
+  HIP_TRY(ctx, d.assign(first_moment, 3 * (size_t) (params->src_width >> params->undersampling_stage) * (params->src_height >> params->undersampling_stage)));
+  return lumc_generate_output_host(ctx, params, d.get(), argb8, frame_output);
 }
 
 int lumc_trace_closest(LumContext* ctx, uint32_t n, const float* d_origins, const float* d_dirs, const uint32_t* d_ignore, uint32_t* d_out, void* stream_) {
   if (!ctx || !ctx->has_scene) { if (ctx) ctx->error = "lumc_trace_closest: no scene"; return 1; }
   if (n == 0) return 0;
   hipStream_t stream = (hipStream_t) stream_;
-  uint32_t* cursor = ctx->d_ctrl + kCtlStride * (kCtrlRows - 1);
+  uint32_t* cursor = ctx->d_ctrl.get() + kCtlStride * (kCtrlRows - 1);
   HIP_TRY(ctx, hipMemsetAsync(cursor, 0, sizeof(uint32_t), stream));  // the work cursor of trace_items (dev_trace.h)
   Launch l(ctx, stream, LUMC_KERNEL_TRACE);
-  ctx->wf->trace_rays(grid_persistent(ctx, n), (size_t) ctx->lds_nodes * kNodeBytes + LUM_LDS_STACK_BYTES, stream, ctx->scene, n, d_origins, d_dirs, d_ignore, d_out, cursor, ctx->d_counters,
+  ctx->wf->trace_rays(grid_persistent(ctx, n), ray_kernel_lds(ctx), stream, ctx->scene, n, d_origins, d_dirs, d_ignore, d_out, cursor, ctx->d_counters.get(),
                       ctx->lds_nodes);
   HIP_TRY(ctx, hipGetLastError());
   return 0;
@@ -1992,25 +1904,15 @@ int lumc_trace_closest(LumContext* ctx, uint32_t n, const float* d_origins, cons
 int lumc_trace_closest_host(LumContext* ctx, uint32_t n, const float* origins, const float* dirs, const uint32_t* ignore, uint32_t* out) {
   if (!ctx || !ctx->has_scene) { if (ctx) ctx->error = "lumc_trace_closest_host: no scene"; return 1; }
   if (n == 0) return 0;
-  float *d_o = nullptr, *d_d = nullptr;
-  uint32_t *d_i = nullptr, *d_out = nullptr;
-  HIP_TRY(ctx, hipMalloc((void**) &d_o, sizeof(float) * 3 * (size_t) n));
-  HIP_TRY(ctx, hipMalloc((void**) &d_d, sizeof(float) * 3 * (size_t) n));
-  HIP_TRY(ctx, hipMalloc((void**) &d_out, sizeof(uint32_t) * 3 * (size_t) n));
-  HIP_TRY(ctx, hipMemcpy(d_o, origins, sizeof(float) * 3 * (size_t) n, hipMemcpyHostToDevice));
-  HIP_TRY(ctx, hipMemcpy(d_d, dirs, sizeof(float) * 3 * (size_t) n, hipMemcpyHostToDevice));
-  if (ignore) {
-    HIP_TRY(ctx, hipMalloc((void**) &d_i, sizeof(uint32_t) * 2 * (size_t) n));
-    HIP_TRY(ctx, hipMemcpy(d_i, ignore, sizeof(uint32_t) * 2 * (size_t) n, hipMemcpyHostToDevice));
-  }
-  int rc = lumc_trace_closest(ctx, n, d_o, d_d, d_i, d_out, nullptr);
-  if (!rc) {
-    const hipError_t e = hipMemcpy(out, d_out, sizeof(uint32_t) * 3 * (size_t) n, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) { ctx->error = hipGetErrorString(e); rc = 1; }
-  }
-  (void) hipFree(d_o); (void) hipFree(d_d); (void) hipFree(d_out);
-  if (d_i) (void) hipFree(d_i);
-  return rc;
+  DeviceBuffer<float> d_o, d_d;
+  DeviceBuffer<uint32_t> d_i, d_out;
+  HIP_TRY(ctx, d_o.assign(origins, 3 * (size_t) n));
+  HIP_TRY(ctx, d_d.assign(dirs, 3 * (size_t) n));
+  HIP_TRY(ctx, d_out.resize(3 * (size_t) n));
+  HIP_TRY(ctx, d_i.assign(ignore, 2 * (size_t) n));
+  if (lumc_trace_closest(ctx, n, d_o.get(), d_d.get(), d_i.get(), d_out.get(), nullptr)) return 1;
+  HIP_TRY(ctx, hipMemcpy(out, d_out.get(), sizeof(uint32_t) * 3 * (size_t) n, hipMemcpyDeviceToHost));
+  return 0;
 }
 
 // Visibility rays through the render's own kernel: a temporary ShadowQueue whose output index is the ray index, the item count and the work cursor in the spare
@@ -2023,36 +1925,26 @@ int lumc_trace_visibility(LumContext* ctx, uint32_t n, const float* d_origins, c
   if (!d_origins || !d_dirs || !d_dist || !d_ids || !d_out) { ctx->error = "lumc_trace_visibility: null argument"; return 1; }
   hipStream_t stream = (hipStream_t) stream_;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  float4* items = nullptr;  // origin_dist | dir_out | ids | vis, n entries of 16 bytes each
-  HIP_TRY(ctx, hipMalloc((void**) &items, sizeof(float4) * 4 * (size_t) n));
+  DeviceBuffer<float4> buffer;  // origin_dist | dir_out | ids | vis, n entries of 16 bytes each
+  HIP_TRY(ctx, buffer.resize(4 * (size_t) n));
+  float4* items = buffer.get();
   ShadowQueue sq{};
   sq.origin_dist = items; sq.dir_out = items + n; sq.ids = reinterpret_cast<uint4*>(items + 2 * (size_t) n); sq.vis = items + 3 * (size_t) n;
   sq.capacity = n;
-  uint32_t* ctrl = ctx->d_ctrl + kCtlStride * (kCtrlRows - 2);
+  uint32_t* ctrl = ctx->d_ctrl.get() + kCtlStride * (kCtrlRows - 2);
   const uint32_t blocks = (n + 255u) / 256u;
-  hipError_t e = hipMemsetAsync(sq.vis, 0xFF, sizeof(float4) * (size_t) n, stream);
-  if (e == hipSuccess) e = hipMemsetD32Async((hipDeviceptr_t) (ctrl + kCtlShadowItems), (int) n, 1, stream);
-  if (e == hipSuccess) e = hipMemsetAsync(ctrl + kCtlShadowCursor, 0, sizeof(uint32_t), stream);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(k_visibility_pack, dim3(blocks), dim3(256), 0, stream, n, d_origins, d_dirs, d_dist, d_ids, sq);
-    {
-      Launch l(ctx, stream, LUMC_KERNEL_SHADOW);
-      ctx->wf->shadow_rays(grid_persistent(ctx, n), (size_t) ctx->lds_nodes * kNodeBytes + LUM_LDS_STACK_BYTES, stream, ctx->scene, sq, d_order, ctrl, ctx->d_counters, ctx->lds_nodes);
-    }
-    hipLaunchKernelGGL(k_visibility_unpack, dim3(blocks), dim3(256), 0, stream, n, sq.vis, d_out);
-    e = hipGetLastError();
+  HIP_TRY(ctx, hipMemsetAsync(sq.vis, 0xFF, sizeof(float4) * (size_t) n, stream));
+  HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t) (ctrl + kCtlShadowItems), (int) n, 1, stream));
+  HIP_TRY(ctx, hipMemsetAsync(ctrl + kCtlShadowCursor, 0, sizeof(uint32_t), stream));
+  hipLaunchKernelGGL(k_visibility_pack, dim3(blocks), dim3(256), 0, stream, n, d_origins, d_dirs, d_dist, d_ids, sq);
+  {
+    Launch l(ctx, stream, LUMC_KERNEL_SHADOW);
+    ctx->wf->shadow_rays(grid_persistent(ctx, n), ray_kernel_lds(ctx), stream, ctx->scene, sq, d_order, ctrl, ctx->d_counters.get(), ctx->lds_nodes);
   }
-  if (e == hipSuccess) e = hipStreamSynchronize(stream);
-  (void) hipFree(items);
-  if (e != hipSuccess) { ctx->error = hipGetErrorString(e); return 1; }
+  hipLaunchKernelGGL(k_visibility_unpack, dim3(blocks), dim3(256), 0, stream, n, sq.vis, d_out);
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipStreamSynchronize(stream));
   return 0;
-}
-
-// device copy of a host array (nullptr in, nullptr out); false = failed
-static bool to_device_bytes(const void* host, size_t bytes, void** dev) {
-  *dev = nullptr;
-  if (!host) return true;
-  return hipMalloc(dev, bytes) == hipSuccess && hipMemcpy(*dev, host, bytes, hipMemcpyHostToDevice) == hipSuccess;
 }
 
 int lumc_trace_visibility_host(LumContext* ctx, uint32_t n, const float* origins, const float* dirs, const float* dist, const uint32_t* ids, const uint32_t* order, float* out) {
@@ -2063,17 +1955,17 @@ int lumc_trace_visibility_host(LumContext* ctx, uint32_t n, const float* origins
     for (uint32_t i = 0; i < n; i++) if (order[i] >= n) { ctx->error = "lumc_trace_visibility_host: order entry out of range"; return 1; }
   }
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  float *d_o = nullptr, *d_d = nullptr, *d_t = nullptr, *d_out = nullptr;
-  uint32_t *d_i = nullptr, *d_ord = nullptr;
-  int rc = 1;
-  if (to_device_bytes(origins, sizeof(*origins) * 3 * (size_t) n, (void**) &d_o) && to_device_bytes(dirs, sizeof(*dirs) * 3 * (size_t) n, (void**) &d_d) && to_device_bytes(dist, sizeof(*dist) * (size_t) n, (void**) &d_t) && to_device_bytes(ids, sizeof(*ids) * 4 * (size_t) n, (void**) &d_i) &&
-      to_device_bytes(order, sizeof(*order) * (size_t) n, (void**) &d_ord) && hipMalloc((void**) &d_out, sizeof(float) * 3 * (size_t) n) == hipSuccess) {
-    rc = lumc_trace_visibility(ctx, n, d_o, d_d, d_t, d_i, d_ord, d_out, nullptr);
-    if (!rc && hipMemcpy(out, d_out, sizeof(float) * 3 * (size_t) n, hipMemcpyDeviceToHost) != hipSuccess) { ctx->error = "lumc_trace_visibility_host: download failed"; rc = 1; }
-  }
-  else ctx->error = "lumc_trace_visibility_host: upload failed";
-  (void) hipFree(d_o); (void) hipFree(d_d); (void) hipFree(d_t); (void) hipFree(d_i); (void) hipFree(d_ord); (void) hipFree(d_out);
-  return rc;
+  DeviceBuffer<float> d_o, d_d, d_t, d_out;
+  DeviceBuffer<uint32_t> d_i, d_ord;
+  HIP_TRY(ctx, d_o.assign(origins, 3 * (size_t) n));
+  HIP_TRY(ctx, d_d.assign(dirs, 3 * (size_t) n));
+  HIP_TRY(ctx, d_t.assign(dist, n));
+  HIP_TRY(ctx, d_i.assign(ids, 4 * (size_t) n));
+  HIP_TRY(ctx, d_ord.assign(order, n));
+  HIP_TRY(ctx, d_out.resize(3 * (size_t) n));
+  if (lumc_trace_visibility(ctx, n, d_o.get(), d_d.get(), d_t.get(), d_i.get(), d_ord.get(), d_out.get(), nullptr)) return 1;
+  HIP_TRY(ctx, hipMemcpy(out, d_out.get(), sizeof(float) * 3 * (size_t) n, hipMemcpyDeviceToHost));
+  return 0;
 }
 
 // The light-BVH query of BSDF-sampled directions (light_query, dev_trace.h) on plain rays, in the active flavour: out_ids = the picked light or 0xFFFFFFFF, out_num_hits = the
@@ -2088,40 +1980,38 @@ int lumc_light_query_host(LumContext* ctx, uint32_t n, const float* origins, con
     return 0;
   }
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  float *d_o = nullptr, *d_d = nullptr, *d_r = nullptr;
-  uint32_t *d_s = nullptr, *d_out = nullptr;
-  int rc = 1;
-  if (to_device_bytes(origins, sizeof(*origins) * 3 * (size_t) n, (void**) &d_o) && to_device_bytes(dirs, sizeof(*dirs) * 3 * (size_t) n, (void**) &d_d) && to_device_bytes(self, sizeof(*self) * 2 * (size_t) n, (void**) &d_s) && to_device_bytes(randoms, sizeof(*randoms) * (size_t) n, (void**) &d_r) &&
-      hipMalloc((void**) &d_out, sizeof(uint32_t) * 2 * (size_t) n) == hipSuccess && hipMemset(d_out, 0xFF, sizeof(uint32_t) * 2 * (size_t) n) == hipSuccess) {
-    ctx->wf->light_query_probe(nullptr, sc, n, d_o, d_d, d_s, d_r, d_out, d_out + n);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(out_ids, d_out, sizeof(uint32_t) * (size_t) n, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(out_num_hits, d_out + n, sizeof(uint32_t) * (size_t) n, hipMemcpyDeviceToHost);
-    rc = e == hipSuccess ? 0 : 1;
-    if (rc) ctx->error = hipGetErrorString(e);
-  }
-  else ctx->error = "lumc_light_query_host: upload failed";
-  (void) hipFree(d_o); (void) hipFree(d_d); (void) hipFree(d_s); (void) hipFree(d_r); (void) hipFree(d_out);
-  return rc;
+  DeviceBuffer<float> d_o, d_d, d_r;
+  DeviceBuffer<uint32_t> d_s, d_out;
+  HIP_TRY(ctx, d_o.assign(origins, 3 * (size_t) n));
+  HIP_TRY(ctx, d_d.assign(dirs, 3 * (size_t) n));
+  HIP_TRY(ctx, d_s.assign(self, 2 * (size_t) n));
+  HIP_TRY(ctx, d_r.assign(randoms, n));
+  HIP_TRY(ctx, d_out.resize(2 * (size_t) n));
+  HIP_TRY(ctx, hipMemset(d_out.get(), 0xFF, sizeof(uint32_t) * 2 * (size_t) n));
+  ctx->wf->light_query_probe(nullptr, sc, n, d_o.get(), d_d.get(), d_s.get(), d_r.get(), d_out.get(), d_out.get() + n);
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipDeviceSynchronize());
+  HIP_TRY(ctx, hipMemcpy(out_ids, d_out.get(), sizeof(uint32_t) * (size_t) n, hipMemcpyDeviceToHost));
+  HIP_TRY(ctx, hipMemcpy(out_num_hits, d_out.get() + n, sizeof(uint32_t) * (size_t) n, hipMemcpyDeviceToHost));
+  return 0;
 }
 
 int lumc_pixel_query(LumContext* ctx, uint32_t x, uint32_t y, uint32_t sample_id, uint32_t out[6]) {
   if (!ctx || !ctx->has_scene || !out) { if (ctx) ctx->error = "lumc_pixel_query: no scene"; return 1; }
   if (x >= ctx->scene.width || y >= ctx->scene.height) { ctx->error = "lumc_pixel_query: pixel outside the frame"; return 1; }
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  float* d = nullptr;
-  HIP_TRY(ctx, hipMalloc((void**) &d, sizeof(float) * 10));
+  DeviceBuffer<float> buffer;  // origin[3] direction[3] hit[3] valid
+  HIP_TRY(ctx, buffer.resize(10));
+  float* d = buffer.get();
   hipLaunchKernelGGL(k_pixel_ray, dim3(1), dim3(64), 0, 0, ctx->scene, ctx->lens, ctx->camera, x, y, sample_id, d, d + 3, (uint32_t*) (d + 9));
   uint32_t valid = 0;
-  int rc = (hipMemcpy(&valid, d + 9, 4, hipMemcpyDeviceToHost) != hipSuccess) ? 1 : 0;
-  if (rc) ctx->error = "lumc_pixel_query: device error";
-  else if (valid) rc = lumc_trace_closest(ctx, 1, d, d + 3, nullptr, (uint32_t*) (d + 6), nullptr);
-  if (!rc && (hipDeviceSynchronize() != hipSuccess || (valid && hipMemcpy(out, d + 6, 12, hipMemcpyDeviceToHost) != hipSuccess) ||
-              hipMemcpy(out + 3, d + 3, 12, hipMemcpyDeviceToHost) != hipSuccess)) { ctx->error = "lumc_pixel_query: device error"; rc = 1; }
-  if (!rc && !valid) { out[0] = 0xFFFFFFFFu; out[1] = 0u; std::memcpy(&out[2], &kFltMax, 4); }  // the ray did not leave the lens: nothing is hit
-  (void) hipFree(d);
-  return rc;
+  HIP_TRY(ctx, hipMemcpy(&valid, d + 9, 4, hipMemcpyDeviceToHost));
+  if (valid && lumc_trace_closest(ctx, 1, d, d + 3, nullptr, (uint32_t*) (d + 6), nullptr)) return 1;
+  HIP_TRY(ctx, hipDeviceSynchronize());
+  if (valid) HIP_TRY(ctx, hipMemcpy(out, d + 6, 12, hipMemcpyDeviceToHost));
+  else { out[0] = 0xFFFFFFFFu; out[1] = 0u; std::memcpy(&out[2], &kFltMax, 4); }  // the ray did not leave the lens: nothing is hit
+  HIP_TRY(ctx, hipMemcpy(out + 3, d + 3, 12, hipMemcpyDeviceToHost));
+  return 0;
 }
 
 int lumc_set_physical_camera(LumContext* ctx, const LumPhysicalCamera* c) {
@@ -2164,21 +2054,19 @@ int lumc_camera_rays(LumContext* ctx, const uint32_t* pixels, uint32_t n, uint32
   for (uint32_t p = 0; p < n; p++)
     if (pixels[p] >= ctx->scene.width * ctx->scene.height) { ctx->error = "lumc_camera_rays: pixel outside the frame"; return 1; }
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  uint32_t* d_px = nullptr;
-  float* d = nullptr;
-  HIP_TRY(ctx, hipMalloc((void**) &d_px, sizeof(uint32_t) * (size_t) n));
-  if (hipMalloc((void**) &d, sizeof(float) * 7 * (size_t) total) != hipSuccess) { (void) hipFree(d_px); ctx->error = "lumc_camera_rays: out of device memory"; return 1; }
-  int rc = 0;
-  if (hipMemcpy(d_px, pixels, sizeof(uint32_t) * (size_t) n, hipMemcpyHostToDevice) != hipSuccess) rc = 1;
-  if (!rc) {
-    ctx->wf->camera_rays(grid_for((uint32_t) total), 0, ctx->scene, ctx->lens, ctx->camera, d_px, n, first_sample, samples, d, d + 3 * total, d + 6 * total);
-    if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess || hipMemcpy(out_origin, d, sizeof(float) * 3 * total, hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(out_dir, d + 3 * total, sizeof(float) * 3 * total, hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(out_weight, d + 6 * total, sizeof(float) * total, hipMemcpyDeviceToHost) != hipSuccess) rc = 1;
-  }
-  if (rc) ctx->error = "lumc_camera_rays: device error";
-  (void) hipFree(d_px); (void) hipFree(d);
-  return rc;
+  DeviceBuffer<uint32_t> d_px;
+  DeviceBuffer<float> rays;  // origin[3 * total] direction[3 * total] weight[total]
+  HIP_TRY(ctx, d_px.resize(n));
+  HIP_TRY(ctx, rays.resize(7 * (size_t) total));
+  HIP_TRY(ctx, hipMemcpy(d_px.get(), pixels, sizeof(uint32_t) * (size_t) n, hipMemcpyHostToDevice));
+  float* d = rays.get();
+  ctx->wf->camera_rays(grid_for((uint32_t) total), 0, ctx->scene, ctx->lens, ctx->camera, d_px.get(), n, first_sample, samples, d, d + 3 * total, d + 6 * total);
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipDeviceSynchronize());
+  HIP_TRY(ctx, hipMemcpy(out_origin, d, sizeof(float) * 3 * total, hipMemcpyDeviceToHost));
+  HIP_TRY(ctx, hipMemcpy(out_dir, d + 3 * total, sizeof(float) * 3 * total, hipMemcpyDeviceToHost));
+  HIP_TRY(ctx, hipMemcpy(out_weight, d + 6 * total, sizeof(float) * total, hipMemcpyDeviceToHost));
+  return 0;
 }
 
 #ifdef LUM_PHASE_STATS

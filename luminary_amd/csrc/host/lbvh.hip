@@ -22,6 +22,7 @@
 #include <algorithm>
 
 #include "bvh_build.h"
+#include "device_buffer.h"
 
 namespace lum {
 namespace {
@@ -353,120 +354,118 @@ Bvh4 build_on_device(const Aabb* boxes, uint32_t count, uint32_t max_leaf, uint3
       const float c = 0.5f * (boxes[i].lo[a] + boxes[i].hi[a]);
       bounds.lo[a] = std::min(bounds.lo[a], c); bounds.hi[a] = std::max(bounds.hi[a], c);
     }
-  BinBox* d_boxes = nullptr; BinBox* d_node_box = nullptr;
-  uint64_t* d_codes = nullptr; uint64_t* d_codes_sorted = nullptr;
-  uint32_t* d_ids = nullptr; uint32_t* d_ids_sorted = nullptr; uint32_t* d_arrivals = nullptr; uint32_t* d_counters = nullptr;
-  int2* d_children = nullptr; int2* d_ranges = nullptr; int* d_parent = nullptr;
-  uint32_t* d_count = nullptr; uint32_t* d_prims = nullptr; int* d_clusters[2] = {nullptr, nullptr}; int* d_nearest = nullptr;
-  uint2* d_flags = nullptr; uint2* d_offsets = nullptr; uint2* d_totals = nullptr; void* d_scan_temp = nullptr;
+  DeviceBuffer<BinBox> d_boxes, d_node_box;
+  DeviceBuffer<uint64_t> d_codes, d_codes_sorted;
+  DeviceBuffer<uint32_t> d_ids, d_ids_sorted, d_arrivals, d_counters;
+  DeviceBuffer<int2> d_children, d_ranges;
+  DeviceBuffer<int> d_parent;
+  DeviceBuffer<uint32_t> d_count, d_prims;
+  DeviceBuffer<int> d_clusters[2], d_nearest;
+  DeviceBuffer<uint2> d_flags, d_offsets, d_totals;
+  DeviceBuffer<char> d_scan_temp, d_temp;
   size_t scan_bytes = 0;
-  CollapseItem* d_queue[2] = {nullptr, nullptr};
-  Bvh4Node* d_nodes = nullptr;
-  int* d_plan_done = nullptr; float4* d_plan = nullptr;
+  DeviceBuffer<CollapseItem> d_queue[2];
+  DeviceBuffer<Bvh4Node> d_nodes;
+  DeviceBuffer<int> d_plan_done;
+  DeviceBuffer<float4> d_plan;
   const bool optimal = collapse_rule_optimal();
-  void* d_temp = nullptr;
   size_t temp_bytes = 0;
   bool ok = true;
   uint32_t node_count = 1, level_count = 1, depth = 0;
   const uint32_t max_nodes = count;  // a 4-wide node has at least two children, so fewer nodes than primitives
   const int threads = 256;
-  LBVH_TRY(hipMalloc((void**) &d_boxes, sizeof(BinBox) * count));
-  LBVH_TRY(hipMalloc((void**) &d_node_box, sizeof(BinBox) * (2 * (size_t) count - 1)));
-  LBVH_TRY(hipMalloc((void**) &d_codes, sizeof(uint64_t) * count));
-  LBVH_TRY(hipMalloc((void**) &d_codes_sorted, sizeof(uint64_t) * count));
-  LBVH_TRY(hipMalloc((void**) &d_ids, sizeof(uint32_t) * count));
-  LBVH_TRY(hipMalloc((void**) &d_ids_sorted, sizeof(uint32_t) * count));
-  LBVH_TRY(hipMalloc((void**) &d_arrivals, sizeof(uint32_t) * count));
-  LBVH_TRY(hipMalloc((void**) &d_counters, sizeof(uint32_t) * 4));
-  LBVH_TRY(hipMalloc((void**) &d_children, sizeof(int2) * count));
-  LBVH_TRY(hipMalloc((void**) &d_ranges, sizeof(int2) * (2 * (size_t) count - 1)));
-  LBVH_TRY(hipMalloc((void**) &d_parent, sizeof(int) * (2 * (size_t) count - 1)));
-  LBVH_TRY(hipMalloc((void**) &d_queue[0], sizeof(CollapseItem) * count));
-  LBVH_TRY(hipMalloc((void**) &d_queue[1], sizeof(CollapseItem) * count));
-  LBVH_TRY(hipMalloc((void**) &d_nodes, sizeof(Bvh4Node) * max_nodes));
-  LBVH_TRY(hipMemcpy(d_boxes, boxes, sizeof(BinBox) * count, hipMemcpyHostToDevice));
-  LBVH_TRY(hipMemset(d_arrivals, 0, sizeof(uint32_t) * count));
-  hipLaunchKernelGGL(k_lbvh_codes, dim3((count + threads - 1) / threads), dim3(threads), 0, 0, (const BinBox*) d_boxes, count, bounds, d_codes, d_ids);
-  LBVH_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, temp_bytes, d_codes, d_codes_sorted, d_ids, d_ids_sorted, n, 0, 63));
-  LBVH_TRY(hipMalloc(&d_temp, temp_bytes ? temp_bytes : 16));
-  LBVH_TRY(hipcub::DeviceRadixSort::SortPairs(d_temp, temp_bytes, d_codes, d_codes_sorted, d_ids, d_ids_sorted, n, 0, 63));
+  LBVH_TRY(d_boxes.resize(count));
+  LBVH_TRY(d_node_box.resize(2 * (size_t) count - 1));
+  LBVH_TRY(d_codes.resize(count));
+  LBVH_TRY(d_codes_sorted.resize(count));
+  LBVH_TRY(d_ids.resize(count));
+  LBVH_TRY(d_ids_sorted.resize(count));
+  LBVH_TRY(d_arrivals.resize(count));
+  LBVH_TRY(d_counters.resize(4));
+  LBVH_TRY(d_children.resize(count));
+  LBVH_TRY(d_ranges.resize(2 * (size_t) count - 1));
+  LBVH_TRY(d_parent.resize(2 * (size_t) count - 1));
+  LBVH_TRY(d_queue[0].resize(count));
+  LBVH_TRY(d_queue[1].resize(count));
+  LBVH_TRY(d_nodes.resize(max_nodes));
+  LBVH_TRY(hipMemcpy(d_boxes.get(), boxes, sizeof(BinBox) * count, hipMemcpyHostToDevice));
+  LBVH_TRY(hipMemset(d_arrivals.get(), 0, sizeof(uint32_t) * count));
+  hipLaunchKernelGGL(k_lbvh_codes, dim3((count + threads - 1) / threads), dim3(threads), 0, 0, (const BinBox*) d_boxes.get(), count, bounds, d_codes.get(), d_ids.get());
+  LBVH_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, temp_bytes, d_codes.get(), d_codes_sorted.get(), d_ids.get(), d_ids_sorted.get(), n, 0, 63));
+  LBVH_TRY(d_temp.resize(temp_bytes ? temp_bytes : 16));
+  LBVH_TRY(hipcub::DeviceRadixSort::SortPairs(d_temp.get(), temp_bytes, d_codes.get(), d_codes_sorted.get(), d_ids.get(), d_ids_sorted.get(), n, 0, 63));
   if (!ploc) {
-    hipLaunchKernelGGL(k_lbvh_hierarchy, dim3((count + threads - 1) / threads), dim3(threads), 0, 0, (const uint64_t*) d_codes_sorted, n, d_children, d_ranges, d_parent);
-    hipLaunchKernelGGL(k_lbvh_fit, dim3((count + threads - 1) / threads), dim3(threads), 0, 0, (const BinBox*) d_boxes, (const uint32_t*) d_ids_sorted, n,
-                       (const int2*) d_children, (const int*) d_parent, d_node_box, d_arrivals, d_ranges);
+    hipLaunchKernelGGL(k_lbvh_hierarchy, dim3((count + threads - 1) / threads), dim3(threads), 0, 0, (const uint64_t*) d_codes_sorted.get(), n, d_children.get(), d_ranges.get(), d_parent.get());
+    hipLaunchKernelGGL(k_lbvh_fit, dim3((count + threads - 1) / threads), dim3(threads), 0, 0, (const BinBox*) d_boxes.get(), (const uint32_t*) d_ids_sorted.get(), n,
+                       (const int2*) d_children.get(), (const int*) d_parent.get(), d_node_box.get(), d_arrivals.get(), d_ranges.get());
     LBVH_TRY(hipGetLastError());
   }
   else {
-    LBVH_TRY(hipMalloc((void**) &d_count, sizeof(uint32_t) * (2 * (size_t) count - 1)));
-    LBVH_TRY(hipMalloc((void**) &d_prims, sizeof(uint32_t) * count));
-    LBVH_TRY(hipMalloc((void**) &d_clusters[0], sizeof(int) * count));
-    LBVH_TRY(hipMalloc((void**) &d_clusters[1], sizeof(int) * count));
-    LBVH_TRY(hipMalloc((void**) &d_nearest, sizeof(int) * count));
-    LBVH_TRY(hipMalloc((void**) &d_flags, sizeof(uint2) * count));
-    LBVH_TRY(hipMalloc((void**) &d_offsets, sizeof(uint2) * count));
-    LBVH_TRY(hipMalloc((void**) &d_totals, sizeof(uint2)));
-    LBVH_TRY(hipcub::DeviceScan::ExclusiveScan(nullptr, scan_bytes, d_flags, d_offsets, AddPair(), make_uint2(0u, 0u), n));
-    LBVH_TRY(hipMalloc(&d_scan_temp, scan_bytes ? scan_bytes : 16));
-    hipLaunchKernelGGL(k_ploc_init, dim3((count + threads - 1) / threads), dim3(threads), 0, 0, (const BinBox*) d_boxes, (const uint32_t*) d_ids_sorted, n, d_node_box, d_count,
-                       d_clusters[0], d_parent);
+    LBVH_TRY(d_count.resize(2 * (size_t) count - 1));
+    LBVH_TRY(d_prims.resize(count));
+    LBVH_TRY(d_clusters[0].resize(count));
+    LBVH_TRY(d_clusters[1].resize(count));
+    LBVH_TRY(d_nearest.resize(count));
+    LBVH_TRY(d_flags.resize(count));
+    LBVH_TRY(d_offsets.resize(count));
+    LBVH_TRY(d_totals.resize(1));
+    LBVH_TRY(hipcub::DeviceScan::ExclusiveScan(nullptr, scan_bytes, d_flags.get(), d_offsets.get(), AddPair(), make_uint2(0u, 0u), n));
+    LBVH_TRY(d_scan_temp.resize(scan_bytes ? scan_bytes : 16));
+    hipLaunchKernelGGL(k_ploc_init, dim3((count + threads - 1) / threads), dim3(threads), 0, 0, (const BinBox*) d_boxes.get(), (const uint32_t*) d_ids_sorted.get(), n, d_node_box.get(), d_count.get(),
+                       d_clusters[0].get(), d_parent.get());
     int m = n, cur = 0;
     uint32_t merges = 0;
     while (m > 1) {
       const uint32_t blocks = (uint32_t) (m + threads - 1) / threads;
-      hipLaunchKernelGGL(k_ploc_nearest, dim3((m + kPlocBlock - 1) / kPlocBlock), dim3(kPlocBlock), 0, 0, (const int*) d_clusters[cur], m, (const BinBox*) d_node_box, d_nearest);
-      hipLaunchKernelGGL(k_ploc_flags, dim3(blocks), dim3(threads), 0, 0, (const int*) d_nearest, m, d_flags);
+      hipLaunchKernelGGL(k_ploc_nearest, dim3((m + kPlocBlock - 1) / kPlocBlock), dim3(kPlocBlock), 0, 0, (const int*) d_clusters[cur].get(), m, (const BinBox*) d_node_box.get(), d_nearest.get());
+      hipLaunchKernelGGL(k_ploc_flags, dim3(blocks), dim3(threads), 0, 0, (const int*) d_nearest.get(), m, d_flags.get());
       size_t bytes = scan_bytes;
-      LBVH_TRY(hipcub::DeviceScan::ExclusiveScan(d_scan_temp, bytes, d_flags, d_offsets, AddPair(), make_uint2(0u, 0u), m));
-      hipLaunchKernelGGL(k_ploc_merge, dim3(blocks), dim3(threads), 0, 0, (const int*) d_clusters[cur], (const int*) d_nearest, (const uint2*) d_flags, (const uint2*) d_offsets, m, n,
-                         merges, d_children, d_parent, d_node_box, d_count, d_clusters[cur ^ 1], d_totals);
+      LBVH_TRY(hipcub::DeviceScan::ExclusiveScan(d_scan_temp.get(), bytes, d_flags.get(), d_offsets.get(), AddPair(), make_uint2(0u, 0u), m));
+      hipLaunchKernelGGL(k_ploc_merge, dim3(blocks), dim3(threads), 0, 0, (const int*) d_clusters[cur].get(), (const int*) d_nearest.get(), (const uint2*) d_flags.get(), (const uint2*) d_offsets.get(), m, n,
+                         merges, d_children.get(), d_parent.get(), d_node_box.get(), d_count.get(), d_clusters[cur ^ 1].get(), d_totals.get());
       uint2 totals;
-      LBVH_TRY(hipMemcpy(&totals, d_totals, sizeof(totals), hipMemcpyDeviceToHost));
+      LBVH_TRY(hipMemcpy(&totals, d_totals.get(), sizeof(totals), hipMemcpyDeviceToHost));
       if (totals.x == 0u || (int) totals.y >= m) { ok = false; goto done; }  // cannot happen: the pair with the smallest union is always mutual
       merges += totals.x;
       m = (int) totals.y;
       cur ^= 1;
     }
     if (merges != count - 1u) { ok = false; goto done; }
-    hipLaunchKernelGGL(k_ploc_ranges, dim3((2 * count - 1 + threads - 1) / threads), dim3(threads), 0, 0, n, (const int2*) d_children, (const int*) d_parent, (const uint32_t*) d_count,
-                       (const uint32_t*) d_ids_sorted, d_ranges, d_prims);
+    hipLaunchKernelGGL(k_ploc_ranges, dim3((2 * count - 1 + threads - 1) / threads), dim3(threads), 0, 0, n, (const int2*) d_children.get(), (const int*) d_parent.get(), (const uint32_t*) d_count.get(),
+                       (const uint32_t*) d_ids_sorted.get(), d_ranges.get(), d_prims.get());
     LBVH_TRY(hipGetLastError());
   }
   {
     const CollapseItem root{0, 0u};
-    LBVH_TRY(hipMemcpy(d_queue[0], &root, sizeof(root), hipMemcpyHostToDevice));
+    LBVH_TRY(hipMemcpy(d_queue[0].get(), &root, sizeof(root), hipMemcpyHostToDevice));
     const uint32_t init[4] = {0u, 1u, 0u, 0u};  // [0] next level's queue length, [1] nodes allocated
-    LBVH_TRY(hipMemcpy(d_counters, init, sizeof(init), hipMemcpyHostToDevice));
+    LBVH_TRY(hipMemcpy(d_counters.get(), init, sizeof(init), hipMemcpyHostToDevice));
   }
   if (optimal) {
     const int total = 2 * n - 1;
-    LBVH_TRY(hipMalloc((void**) &d_plan_done, sizeof(int) * (size_t) total));
-    LBVH_TRY(hipMalloc((void**) &d_plan, sizeof(float4) * (size_t) total));
-    if (!make_collapse_plan(total, d_children, d_ranges, d_node_box, max_leaf, d_plan_done, d_plan)) { ok = false; goto done; }
+    LBVH_TRY(d_plan_done.resize((size_t) total));
+    LBVH_TRY(d_plan.resize((size_t) total));
+    if (!make_collapse_plan(total, d_children.get(), d_ranges.get(), d_node_box.get(), max_leaf, d_plan_done.get(), d_plan.get())) { ok = false; goto done; }
   }
   for (int cur = 0; level_count > 0; cur ^= 1) {
     depth++;
     if (depth > max_depth) { ok = false; goto done; }  // deeper than the traversal stack allows: the caller falls back to the host builder
-    hipLaunchKernelGGL(k_lbvh_collapse, dim3((level_count + threads - 1) / threads), dim3(threads), 0, 0, n, (const int2*) d_children, (const int2*) d_ranges,
-                       (const BinBox*) d_node_box, max_leaf, (const CollapseItem*) d_queue[cur], level_count, d_queue[cur ^ 1], d_counters, d_counters + 1, d_nodes,
-                       (const float4*) d_plan);
+    hipLaunchKernelGGL(k_lbvh_collapse, dim3((level_count + threads - 1) / threads), dim3(threads), 0, 0, n, (const int2*) d_children.get(), (const int2*) d_ranges.get(),
+                       (const BinBox*) d_node_box.get(), max_leaf, (const CollapseItem*) d_queue[cur].get(), level_count, d_queue[cur ^ 1].get(), d_counters.get(), d_counters.get() + 1, d_nodes.get(),
+                       (const float4*) d_plan.get());
     uint32_t host_counters[2];
-    LBVH_TRY(hipMemcpy(host_counters, d_counters, sizeof(host_counters), hipMemcpyDeviceToHost));
+    LBVH_TRY(hipMemcpy(host_counters, d_counters.get(), sizeof(host_counters), hipMemcpyDeviceToHost));
     level_count = host_counters[0];
     node_count = host_counters[1];
     if (node_count > max_nodes) { ok = false; goto done; }
-    LBVH_TRY(hipMemset(d_counters, 0, sizeof(uint32_t)));
+    LBVH_TRY(hipMemset(d_counters.get(), 0, sizeof(uint32_t)));
   }
   result.nodes.resize(node_count);
   result.prims.resize(count);
-  LBVH_TRY(hipMemcpy(result.nodes.data(), d_nodes, sizeof(Bvh4Node) * node_count, hipMemcpyDeviceToHost));
-  LBVH_TRY(hipMemcpy(result.prims.data(), ploc ? d_prims : d_ids_sorted, sizeof(uint32_t) * count, hipMemcpyDeviceToHost));
+  LBVH_TRY(hipMemcpy(result.nodes.data(), d_nodes.get(), sizeof(Bvh4Node) * node_count, hipMemcpyDeviceToHost));
+  LBVH_TRY(hipMemcpy(result.prims.data(), ploc ? d_prims.get() : d_ids_sorted.get(), sizeof(uint32_t) * count, hipMemcpyDeviceToHost));
   result.max_depth = depth;
 done:
-  {
-    void* bufs[] = {d_boxes, d_node_box, d_codes, d_codes_sorted, d_ids, d_ids_sorted, d_arrivals, d_counters, d_children, d_ranges, d_parent, d_queue[0], d_queue[1], d_nodes, d_temp,
-                    d_count, d_prims, d_clusters[0], d_clusters[1], d_nearest, d_flags, d_offsets, d_totals, d_scan_temp, d_plan_done, d_plan};
-    for (void* b : bufs) if (b) (void) hipFree(b);
-  }
   if (!ok) return Bvh4();
   return result;
 }
@@ -696,7 +695,7 @@ Bvh4 build_bvh4_sah_gpu(const Aabb* boxes, uint32_t count, uint32_t max_leaf, ui
   CollapseItem* d_queue[2] = {nullptr, nullptr}; Bvh4Node* d_nodes = nullptr;
   int* d_plan_done = nullptr; float4* d_plan = nullptr;
   const bool optimal = collapse_rule_optimal();
-  char* d_pool = nullptr;
+  DeviceBuffer<char> pool;
   size_t scan_bytes = 0;
   bool ok = true;
   const int threads = 256;
@@ -717,7 +716,8 @@ Bvh4 build_bvh4_sah_gpu(const Aabb* boxes, uint32_t count, uint32_t max_leaf, ui
     const size_t o_children = reserve(sizeof(int2) * max_nodes2), o_ranges = reserve(sizeof(int2) * max_nodes2), o_node_box = reserve(sizeof(BinBox) * max_nodes2);
     const size_t o_nodes = reserve(sizeof(Bvh4Node) * max_nodes4), o_scan = reserve(scan_bytes ? scan_bytes : 16);
     const size_t o_plan_done = reserve(optimal ? sizeof(int) * max_nodes2 : 0), o_plan = reserve(optimal ? sizeof(float4) * max_nodes2 : 0);
-    LBVH_TRY(hipMalloc((void**) &d_pool, total));
+    LBVH_TRY(pool.resize(total));
+    char* const d_pool = pool.get();
     if (optimal) { d_plan_done = (int*) (d_pool + o_plan_done); d_plan = (float4*) (d_pool + o_plan); }
     for (int k = 0; k < 2; k++) {
       d_boxes[k] = (BinBox*) (d_pool + o_boxes[k]); d_ids[k] = (uint32_t*) (d_pool + o_ids[k]); d_owner[k] = (int*) (d_pool + o_owner[k]);
@@ -806,9 +806,6 @@ Bvh4 build_bvh4_sah_gpu(const Aabb* boxes, uint32_t count, uint32_t max_leaf, ui
   LBVH_TRY(hipMemcpy(result.prims.data(), d_ids[cur], sizeof(uint32_t) * count, hipMemcpyDeviceToHost));
   result.max_depth = depth;
 done:
-  {
-    if (d_pool) (void) hipFree(d_pool);
-  }
   if (!ok) return Bvh4();
   return result;
 }

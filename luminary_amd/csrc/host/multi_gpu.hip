@@ -41,15 +41,10 @@ int frame_scatter(LumContext* ctx, uint32_t frame_pixels, hipStream_t stream) {
   if (!ctx->d_first_moment || ctx->num_pixels == 0) { ctx->error = "lumc_frame_assemble: no accumulators (lumc_set_pixels)"; return 1; }
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   const uint32_t padded = frame_pixels;  // 4 planes of n floats = n float4s: the add kernel walks the whole buffer, planes keep stride n
-  if (ctx->exchange.frame_capacity != padded) {
-    if (ctx->exchange.d_frame) (void) hipFree(ctx->exchange.d_frame);
-    ctx->exchange.d_frame = nullptr; ctx->exchange.frame_capacity = 0;
-    HIP_TRY(ctx, hipMalloc((void**) &ctx->exchange.d_frame, sizeof(float) * 4 * (size_t) padded));
-    ctx->exchange.frame_capacity = padded;
-  }
-  HIP_TRY(ctx, hipMemsetAsync(ctx->exchange.d_frame, 0, sizeof(float) * 4 * (size_t) ctx->exchange.frame_capacity, stream));
-  hipLaunchKernelGGL(k_frame_scatter, dim3(grid_for(ctx->num_pixels)), dim3(256), 0, stream, (const float*) ctx->d_first_moment, (const float*) ctx->d_second_moment,
-                     (const uint32_t*) ctx->d_pixels, ctx->num_pixels, ctx->exchange.frame_capacity, ctx->exchange.d_frame);
+  if (ctx->exchange.frame_pixels() != padded) HIP_TRY(ctx, ctx->exchange.d_frame.resize(4 * (size_t) padded));
+  HIP_TRY(ctx, hipMemsetAsync(ctx->exchange.d_frame.get(), 0, sizeof(float) * 4 * (size_t) ctx->exchange.frame_pixels(), stream));
+  hipLaunchKernelGGL(k_frame_scatter, dim3(grid_for(ctx->num_pixels)), dim3(256), 0, stream, (const float*) ctx->d_first_moment.get(), (const float*) ctx->d_second_moment.get(),
+                     (const uint32_t*) ctx->d_pixels.get(), ctx->num_pixels, ctx->exchange.frame_pixels(), ctx->exchange.d_frame.get());
   HIP_TRY(ctx, hipGetLastError());
   return 0;
 }
@@ -111,9 +106,9 @@ int lumc_frame_assemble(LumContext* ctx, uint32_t frame_pixels, int root, void* 
   if (frame_scatter(ctx, frame_pixels, stream)) return 1;
   if (ctx->exchange.comm) {
     if (root < 0 || root >= ctx->exchange.comm_world) { ctx->error = "lumc_frame_assemble: bad root"; return 1; }
-    NCCL_TRY(ctx, ncclReduce(ctx->exchange.d_frame, ctx->exchange.d_frame, 4 * (size_t) ctx->exchange.frame_capacity, ncclFloat, ncclSum, root, ctx->exchange.comm, stream));
+    NCCL_TRY(ctx, ncclReduce(ctx->exchange.d_frame.get(), ctx->exchange.d_frame.get(), 4 * (size_t) ctx->exchange.frame_pixels(), ncclFloat, ncclSum, root, ctx->exchange.comm, stream));
   }
-  if (d_frame_out) *d_frame_out = ctx->exchange.d_frame;
+  if (d_frame_out) *d_frame_out = ctx->exchange.d_frame.get();
   return 0;
 }
 
@@ -133,30 +128,29 @@ int lumc_frame_assemble_all(LumContext** ctxs, int n, uint32_t frame_pixels, int
     NCCL_TRY(r, ncclGroupStart());
     for (int i = 0; i < n; i++) {
       (void) hipSetDevice(ctxs[i]->device);
-      const ncclResult_t e = ncclReduce(ctxs[i]->exchange.d_frame, ctxs[i]->exchange.d_frame, 4 * (size_t) ctxs[i]->exchange.frame_capacity, ncclFloat, ncclSum, root, ctxs[i]->exchange.comm, (hipStream_t) 0);
+      const ncclResult_t e = ncclReduce(ctxs[i]->exchange.d_frame.get(), ctxs[i]->exchange.d_frame.get(), 4 * (size_t) ctxs[i]->exchange.frame_pixels(), ncclFloat, ncclSum, root, ctxs[i]->exchange.comm, (hipStream_t) 0);
       if (e != ncclSuccess) { (void) ncclGroupEnd(); r->error = std::string("ncclReduce failed: ") + ncclGetErrorString(e); return 1; }
     }
     NCCL_TRY(r, ncclGroupEnd());
     for (int i = 0; i < n; i++) { HIP_TRY(r, hipSetDevice(ctxs[i]->device)); HIP_TRY(r, hipDeviceSynchronize()); }
   }
   else if (n > 1) {
-    float* staging = nullptr;
     HIP_TRY(r, hipSetDevice(r->device));
-    const size_t bytes = sizeof(float) * 4 * (size_t) r->exchange.frame_capacity;
-    HIP_TRY(r, hipMalloc((void**) &staging, bytes));
+    const size_t bytes = sizeof(float) * r->exchange.d_frame.count();
+    DeviceBuffer<float> staging;
+    HIP_TRY(r, staging.resize(r->exchange.d_frame.count()));
     for (int i = 0; i < n; i++) {
       if (i == root) continue;
       HIP_TRY(r, hipSetDevice(ctxs[i]->device));
       HIP_TRY(r, hipDeviceSynchronize());
       HIP_TRY(r, hipSetDevice(r->device));
-      HIP_TRY(r, hipMemcpyPeer(staging, r->device, ctxs[i]->exchange.d_frame, ctxs[i]->device, bytes));
-      hipLaunchKernelGGL(k_frame_add, dim3(grid_for(r->exchange.frame_capacity)), dim3(256), 0, 0, (const float4*) staging, (float4*) r->exchange.d_frame, r->exchange.frame_capacity);
+      HIP_TRY(r, hipMemcpyPeer(staging.get(), r->device, ctxs[i]->exchange.d_frame.get(), ctxs[i]->device, bytes));
+      hipLaunchKernelGGL(k_frame_add, dim3(grid_for(r->exchange.frame_pixels())), dim3(256), 0, 0, (const float4*) staging.get(), (float4*) r->exchange.d_frame.get(), r->exchange.frame_pixels());
       HIP_TRY(r, hipGetLastError());
     }
     HIP_TRY(r, hipDeviceSynchronize());
-    (void) hipFree(staging);
   }
-  if (d_frame_root) *d_frame_root = r->exchange.d_frame;
+  if (d_frame_root) *d_frame_root = r->exchange.d_frame.get();
   return 0;
 }
 
@@ -211,49 +205,36 @@ int gather_prepare(LumContext* ctx, uint32_t width, uint32_t height, int world, 
     return 1;
   }
   stride = (stride + 3u) & ~3u;
-  const bool same = ctx->exchange.gather_key[0] == width && ctx->exchange.gather_key[1] == height && ctx->exchange.gather_key[2] == (uint32_t) world && ctx->exchange.gather_stride == stride && ctx->exchange.d_gather_send;
+  const bool same = ctx->exchange.gather_key[0] == width && ctx->exchange.gather_key[1] == height && ctx->exchange.gather_key[2] == (uint32_t) world && ctx->exchange.gather_stride == stride && ctx->exchange.d_gather_send.get();
   if (!same) {
-    if (ctx->exchange.d_gather_send) (void) hipFree(ctx->exchange.d_gather_send);
-    if (ctx->exchange.d_gather_pixels) (void) hipFree(ctx->exchange.d_gather_pixels);
-    ctx->exchange.d_gather_send = nullptr; ctx->exchange.d_gather_pixels = nullptr;
-    HIP_TRY(ctx, hipMalloc((void**) &ctx->exchange.d_gather_send, sizeof(float) * 4 * (size_t) stride));
+    ctx->exchange.d_gather_pixels.reset();
+    HIP_TRY(ctx, ctx->exchange.d_gather_send.resize(4 * (size_t) stride));
     ctx->exchange.gather_stride = stride; ctx->exchange.gather_key[0] = width; ctx->exchange.gather_key[1] = height; ctx->exchange.gather_key[2] = (uint32_t) world;
   }
   if (is_root) {
     const size_t need = (size_t) world * 4 * stride;
-    if (ctx->exchange.gather_recv_floats < need) {
-      if (ctx->exchange.d_gather_recv) (void) hipFree(ctx->exchange.d_gather_recv);
-      ctx->exchange.d_gather_recv = nullptr; ctx->exchange.gather_recv_floats = 0;
-      HIP_TRY(ctx, hipMalloc((void**) &ctx->exchange.d_gather_recv, sizeof(float) * need));
-      ctx->exchange.gather_recv_floats = need;
-    }
+    if (ctx->exchange.d_gather_recv.count() < need) HIP_TRY(ctx, ctx->exchange.d_gather_recv.resize(need));
     if (!ctx->exchange.d_gather_pixels) {
       std::vector<uint32_t> lists((size_t) world * stride, 0xFFFFFFFFu);
       for (int r = 0; r < world; r++) { uint32_t c = 0; (void) lumc_tile_pixels(width, height, (uint32_t) r, (uint32_t) world, kGatherTile, lists.data() + (size_t) r * stride, &c); }
-      HIP_TRY(ctx, hipMalloc((void**) &ctx->exchange.d_gather_pixels, sizeof(uint32_t) * lists.size()));
-      HIP_TRY(ctx, hipMemcpy(ctx->exchange.d_gather_pixels, lists.data(), sizeof(uint32_t) * lists.size(), hipMemcpyHostToDevice));
+      HIP_TRY(ctx, ctx->exchange.d_gather_pixels.assign(lists.data(), lists.size()));
     }
     const uint32_t frame_pixels = width * height;
-    if (ctx->exchange.frame_capacity != frame_pixels) {
-      if (ctx->exchange.d_frame) (void) hipFree(ctx->exchange.d_frame);
-      ctx->exchange.d_frame = nullptr; ctx->exchange.frame_capacity = 0;
-      HIP_TRY(ctx, hipMalloc((void**) &ctx->exchange.d_frame, sizeof(float) * 4 * (size_t) frame_pixels));
-      ctx->exchange.frame_capacity = frame_pixels;
-    }
+    if (ctx->exchange.frame_pixels() != frame_pixels) HIP_TRY(ctx, ctx->exchange.d_frame.resize(4 * (size_t) frame_pixels));
   }
   return 0;
 }
 int gather_pack(LumContext* ctx, hipStream_t stream) {
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  hipLaunchKernelGGL(k_gather_pack, dim3(grid_for(ctx->exchange.gather_stride)), dim3(256), 0, stream, (const float*) ctx->d_first_moment, (const float*) ctx->d_second_moment, ctx->num_pixels,
-                     ctx->exchange.gather_stride, ctx->exchange.d_gather_send);
+  hipLaunchKernelGGL(k_gather_pack, dim3(grid_for(ctx->exchange.gather_stride)), dim3(256), 0, stream, (const float*) ctx->d_first_moment.get(), (const float*) ctx->d_second_moment.get(), ctx->num_pixels,
+                     ctx->exchange.gather_stride, ctx->exchange.d_gather_send.get());
   HIP_TRY(ctx, hipGetLastError());
   return 0;
 }
 int gather_unpack(LumContext* root, int world, hipStream_t stream) {
   HIP_TRY(root, hipSetDevice(root->device));
-  hipLaunchKernelGGL(k_gather_unpack, dim3(grid_for((uint32_t) world * root->exchange.gather_stride)), dim3(256), 0, stream, (const float*) root->exchange.d_gather_recv, (const uint32_t*) root->exchange.d_gather_pixels,
-                     (uint32_t) world, root->exchange.gather_stride, root->exchange.frame_capacity, root->exchange.d_frame);
+  hipLaunchKernelGGL(k_gather_unpack, dim3(grid_for((uint32_t) world * root->exchange.gather_stride)), dim3(256), 0, stream, (const float*) root->exchange.d_gather_recv.get(), (const uint32_t*) root->exchange.d_gather_pixels.get(),
+                     (uint32_t) world, root->exchange.gather_stride, root->exchange.frame_pixels(), root->exchange.d_frame.get());
   HIP_TRY(root, hipGetLastError());
   return 0;
 }
@@ -268,10 +249,10 @@ int lumc_frame_gather(LumContext* ctx, uint32_t width, uint32_t height, int root
   if (gather_prepare(ctx, width, height, world, rank, rank == root)) return 1;
   if (gather_pack(ctx, stream)) return 1;
   const size_t count = 4 * (size_t) ctx->exchange.gather_stride;
-  if (ctx->exchange.comm) NCCL_TRY(ctx, ncclGather(ctx->exchange.d_gather_send, rank == root ? ctx->exchange.d_gather_recv : nullptr, count, ncclFloat, root, ctx->exchange.comm, stream));
-  else HIP_TRY(ctx, hipMemcpyAsync(ctx->exchange.d_gather_recv, ctx->exchange.d_gather_send, sizeof(float) * count, hipMemcpyDeviceToDevice, stream));
+  if (ctx->exchange.comm) NCCL_TRY(ctx, ncclGather(ctx->exchange.d_gather_send.get(), rank == root ? ctx->exchange.d_gather_recv.get() : nullptr, count, ncclFloat, root, ctx->exchange.comm, stream));
+  else HIP_TRY(ctx, hipMemcpyAsync(ctx->exchange.d_gather_recv.get(), ctx->exchange.d_gather_send.get(), sizeof(float) * count, hipMemcpyDeviceToDevice, stream));
   if (rank == root && gather_unpack(ctx, world, stream)) return 1;
-  if (d_frame_out) *d_frame_out = rank == root ? ctx->exchange.d_frame : nullptr;
+  if (d_frame_out) *d_frame_out = rank == root ? ctx->exchange.d_frame.get() : nullptr;
   return 0;
 }
 
@@ -291,7 +272,7 @@ int lumc_frame_gather_all(LumContext** ctxs, int n, uint32_t width, uint32_t hei
     NCCL_TRY(r, ncclGroupStart());
     for (int i = 0; i < n; i++) {
       (void) hipSetDevice(ctxs[i]->device);
-      const ncclResult_t e = ncclGather(ctxs[i]->exchange.d_gather_send, i == root ? r->exchange.d_gather_recv : nullptr, count, ncclFloat, root, ctxs[i]->exchange.comm, (hipStream_t) 0);
+      const ncclResult_t e = ncclGather(ctxs[i]->exchange.d_gather_send.get(), i == root ? r->exchange.d_gather_recv.get() : nullptr, count, ncclFloat, root, ctxs[i]->exchange.comm, (hipStream_t) 0);
       if (e != ncclSuccess) { (void) ncclGroupEnd(); r->error = std::string("ncclGather failed: ") + ncclGetErrorString(e); return 1; }
     }
     NCCL_TRY(r, ncclGroupEnd());
@@ -302,12 +283,12 @@ int lumc_frame_gather_all(LumContext** ctxs, int n, uint32_t width, uint32_t hei
       HIP_TRY(r, hipSetDevice(ctxs[i]->device));
       HIP_TRY(r, hipDeviceSynchronize());
       HIP_TRY(r, hipSetDevice(r->device));
-      HIP_TRY(r, hipMemcpyPeer(r->exchange.d_gather_recv + (size_t) i * count, r->device, ctxs[i]->exchange.d_gather_send, ctxs[i]->device, sizeof(float) * count));
+      HIP_TRY(r, hipMemcpyPeer(r->exchange.d_gather_recv.get() + (size_t) i * count, r->device, ctxs[i]->exchange.d_gather_send.get(), ctxs[i]->device, sizeof(float) * count));
     }
   }
   if (gather_unpack(r, n, (hipStream_t) 0)) return 1;
   HIP_TRY(r, hipDeviceSynchronize());
-  if (d_frame_root) *d_frame_root = r->exchange.d_frame;
+  if (d_frame_root) *d_frame_root = r->exchange.d_frame.get();
   return 0;
 }
 
@@ -332,24 +313,23 @@ __global__ __launch_bounds__(256) void k_accumulators_from_frame(const float* __
 // the frame's tiles: every pixel's sums continue where the preview left them, so the tiled frame equals the single-device frame bit for bit.
 int lumc_accumulators_from_frame(LumContext* dst, LumContext* src) {
   if (!dst || !src || !src->exchange.d_frame || !dst->d_first_moment || dst->num_pixels == 0) { if (dst) dst->error = "lumc_accumulators_from_frame: no frame on the source or no accumulators on the destination"; return 1; }
-  const uint32_t frame_pixels = src->exchange.frame_capacity;
-  const float* frame = src->exchange.d_frame;
-  float* staging = nullptr;
+  const uint32_t frame_pixels = src->exchange.frame_pixels();
+  const float* frame = src->exchange.d_frame.get();
+  DeviceBuffer<float> staging;
   HIP_TRY(dst, hipSetDevice(src->device));
   HIP_TRY(dst, hipDeviceSynchronize());
   HIP_TRY(dst, hipSetDevice(dst->device));
   if (dst != src) {  // another context (another GPU, or the same one in test set-ups): a copy of the frame on dst's device
     const size_t bytes = sizeof(float) * 4 * (size_t) frame_pixels;
-    HIP_TRY(dst, hipMalloc((void**) &staging, bytes));
-    HIP_TRY(dst, hipMemcpyPeer(staging, dst->device, src->exchange.d_frame, src->device, bytes));
-    frame = staging;
+    HIP_TRY(dst, staging.resize(4 * (size_t) frame_pixels));
+    HIP_TRY(dst, hipMemcpyPeer(staging.get(), dst->device, src->exchange.d_frame.get(), src->device, bytes));
+    frame = staging.get();
   }
   const LumContext::Adaptive& a = dst->adaptive;
-  hipLaunchKernelGGL(k_accumulators_from_frame, dim3(grid_for(dst->num_pixels)), dim3(256), 0, 0, frame, frame_pixels, (const uint32_t*) dst->d_pixels, dst->num_pixels,
-                     a.active ? (const uint8_t*) a.d_block_mask : nullptr, dst->scene.width, a.active ? a.blocks_x : 0u, dst->d_first_moment, dst->d_second_moment);
+  hipLaunchKernelGGL(k_accumulators_from_frame, dim3(grid_for(dst->num_pixels)), dim3(256), 0, 0, frame, frame_pixels, (const uint32_t*) dst->d_pixels.get(), dst->num_pixels,
+                     a.active ? (const uint8_t*) a.d_block_mask.get() : nullptr, dst->scene.width, a.active ? a.blocks_x : 0u, dst->d_first_moment.get(), dst->d_second_moment.get());
   HIP_TRY(dst, hipGetLastError());
   HIP_TRY(dst, hipDeviceSynchronize());
-  if (staging) (void) hipFree(staging);
   return 0;
 }
 
@@ -372,7 +352,7 @@ int lumc_adaptive_exchange_all(LumContext** ctxs, int n) {
     NCCL_TRY(ctxs[0], ncclGroupStart());
     for (int i = 0; i < n; i++) {
       (void) hipSetDevice(ctxs[i]->device);
-      const ncclResult_t e = ncclAllReduce(ctxs[i]->adaptive.d_block_variance, ctxs[i]->adaptive.d_block_variance, nb, ncclFloat, ncclSum, ctxs[i]->exchange.comm, (hipStream_t) 0);
+      const ncclResult_t e = ncclAllReduce(ctxs[i]->adaptive.d_block_variance.get(), ctxs[i]->adaptive.d_block_variance.get(), nb, ncclFloat, ncclSum, ctxs[i]->exchange.comm, (hipStream_t) 0);
       if (e != ncclSuccess) { (void) ncclGroupEnd(); ctxs[0]->error = std::string("ncclAllReduce failed: ") + ncclGetErrorString(e); return 1; }
     }
     NCCL_TRY(ctxs[0], ncclGroupEnd());
@@ -381,12 +361,12 @@ int lumc_adaptive_exchange_all(LumContext** ctxs, int n) {
     std::vector<float> sum(nb, 0.0f), part(nb);
     for (int i = 0; i < n; i++) {
       HIP_TRY(ctxs[0], hipSetDevice(ctxs[i]->device));
-      HIP_TRY(ctxs[0], hipMemcpy(part.data(), ctxs[i]->adaptive.d_block_variance, sizeof(float) * nb, hipMemcpyDeviceToHost));
+      HIP_TRY(ctxs[0], hipMemcpy(part.data(), ctxs[i]->adaptive.d_block_variance.get(), sizeof(float) * nb, hipMemcpyDeviceToHost));
       for (uint32_t b = 0; b < nb; b++) sum[b] += part[b];
     }
     for (int i = 0; i < n; i++) {
       HIP_TRY(ctxs[0], hipSetDevice(ctxs[i]->device));
-      HIP_TRY(ctxs[0], hipMemcpy(ctxs[i]->adaptive.d_block_variance, sum.data(), sizeof(float) * nb, hipMemcpyHostToDevice));
+      HIP_TRY(ctxs[0], hipMemcpy(ctxs[i]->adaptive.d_block_variance.get(), sum.data(), sizeof(float) * nb, hipMemcpyHostToDevice));
     }
   }
   for (int i = 0; i < n; i++) {
@@ -405,21 +385,21 @@ int lumc_comm_count(const LumContext* ctx) {
 
 // The assembled frame of this context (valid on the root after lumc_frame_assemble*): planar first moment [3][frame_pixels] and second moment.
 int lumc_frame_download(LumContext* ctx, uint32_t frame_pixels, float* first_moment, float* second_moment) {
-  if (!ctx || !ctx->exchange.d_frame || frame_pixels > ctx->exchange.frame_capacity) { if (ctx) ctx->error = "lumc_frame_download: no assembled frame"; return 1; }
+  if (!ctx || !ctx->exchange.d_frame || frame_pixels > ctx->exchange.frame_pixels()) { if (ctx) ctx->error = "lumc_frame_download: no assembled frame"; return 1; }
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   HIP_TRY(ctx, hipDeviceSynchronize());
-  const size_t cap = ctx->exchange.frame_capacity;
+  const size_t cap = ctx->exchange.frame_pixels();
   if (first_moment)
-    for (int c = 0; c < 3; c++) HIP_TRY(ctx, hipMemcpy(first_moment + (size_t) c * frame_pixels, ctx->exchange.d_frame + (size_t) c * cap, sizeof(float) * frame_pixels, hipMemcpyDeviceToHost));
-  if (second_moment) HIP_TRY(ctx, hipMemcpy(second_moment, ctx->exchange.d_frame + 3 * cap, sizeof(float) * frame_pixels, hipMemcpyDeviceToHost));
+    for (int c = 0; c < 3; c++) HIP_TRY(ctx, hipMemcpy(first_moment + (size_t) c * frame_pixels, ctx->exchange.d_frame.get() + (size_t) c * cap, sizeof(float) * frame_pixels, hipMemcpyDeviceToHost));
+  if (second_moment) HIP_TRY(ctx, hipMemcpy(second_moment, ctx->exchange.d_frame.get() + 3 * cap, sizeof(float) * frame_pixels, hipMemcpyDeviceToHost));
   return 0;
 }
-uint32_t lumc_frame_plane_stride(const LumContext* ctx) { return ctx ? ctx->exchange.frame_capacity : 0; }
+uint32_t lumc_frame_plane_stride(const LumContext* ctx) { return ctx ? ctx->exchange.frame_pixels() : 0; }
 // The display entry points of this context (lumc_generate_result*, and through them the output chain) read the assembled full frame instead
 // of the context's own accumulators: what the display GPU of a tiled render shows.
 int lumc_use_assembled_frame(LumContext* ctx, int on) {
   if (!ctx) return 1;
-  if (on && (!ctx->exchange.d_frame || !ctx->has_scene || ctx->exchange.frame_capacity != ctx->scene.width * ctx->scene.height)) { ctx->error = "lumc_use_assembled_frame: no assembled frame of this scene's size"; return 1; }
+  if (on && (!ctx->exchange.d_frame || !ctx->has_scene || ctx->exchange.frame_pixels() != ctx->scene.width * ctx->scene.height)) { ctx->error = "lumc_use_assembled_frame: no assembled frame of this scene's size"; return 1; }
   ctx->exchange.use_frame = on != 0;
   return 0;
 }
@@ -428,7 +408,5 @@ int lumc_use_assembled_frame(LumContext* ctx, int on) {
 void free_exchange(LumContext* ctx) {
   LumContext::Exchange& x = ctx->exchange;
   if (x.comm) (void) ncclCommDestroy(x.comm);
-  void* bufs[] = {x.d_frame, x.d_gather_send, x.d_gather_recv, x.d_gather_pixels};
-  for (void* b : bufs) if (b) (void) hipFree(b);
   x = LumContext::Exchange();
 }

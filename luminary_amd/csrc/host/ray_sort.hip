@@ -40,22 +40,17 @@ __global__ __launch_bounds__(256) void k_ray_sort_keys(const float4* __restrict_
 }
 
 int ensure_sort(LumContext* ctx, uint32_t items) {
-  if (items <= ctx->sort.capacity) return 0;
+  LumContext::RaySort& s = ctx->sort;
+  if (s.d_temp && items <= s.d_keys[0].count()) return 0;
+  for (int k = 0; k < 2; k++) { s.d_keys[k].reset(); s.d_vals[k].reset(); }
+  s.d_temp.reset();
   for (int k = 0; k < 2; k++) {
-    if (ctx->sort.d_keys[k]) (void) hipFree(ctx->sort.d_keys[k]);
-    if (ctx->sort.d_vals[k]) (void) hipFree(ctx->sort.d_vals[k]);
-    ctx->sort.d_keys[k] = ctx->sort.d_vals[k] = nullptr;
+    HIP_TRY(ctx, s.d_keys[k].resize(items));
+    HIP_TRY(ctx, s.d_vals[k].resize(items));
   }
-  if (ctx->sort.d_temp) (void) hipFree(ctx->sort.d_temp);
-  ctx->sort.d_temp = nullptr; ctx->sort.capacity = 0;
-  for (int k = 0; k < 2; k++) {
-    HIP_TRY(ctx, hipMalloc((void**) &ctx->sort.d_keys[k], sizeof(uint32_t) * (size_t) items));
-    HIP_TRY(ctx, hipMalloc((void**) &ctx->sort.d_vals[k], sizeof(uint32_t) * (size_t) items));
-  }
-  hipcub::DoubleBuffer<uint32_t> keys(ctx->sort.d_keys[0], ctx->sort.d_keys[1]), vals(ctx->sort.d_vals[0], ctx->sort.d_vals[1]);
-  HIP_TRY(ctx, hipcub::DeviceRadixSort::SortPairs(nullptr, ctx->sort.temp_bytes, keys, vals, (int) items, 0, 22, (hipStream_t) 0));
-  HIP_TRY(ctx, hipMalloc(&ctx->sort.d_temp, std::max<size_t>(ctx->sort.temp_bytes, 16)));
-  ctx->sort.capacity = items;
+  hipcub::DoubleBuffer<uint32_t> keys(s.d_keys[0].get(), s.d_keys[1].get()), vals(s.d_vals[0].get(), s.d_vals[1].get());
+  HIP_TRY(ctx, hipcub::DeviceRadixSort::SortPairs(nullptr, s.temp_bytes, keys, vals, (int) items, 0, 22, (hipStream_t) 0));
+  HIP_TRY(ctx, s.d_temp.resize(std::max<size_t>(s.temp_bytes, 16)));
   return 0;
 }
 
@@ -72,13 +67,13 @@ __global__ __launch_bounds__(256) void k_permute_queue(PathQueue src, PathQueue 
 }
 
 int ensure_sort_queue(LumContext* ctx, uint32_t items) {
-  if (items == ctx->sort.queue_capacity) return 0;
-  for (int k = 0; k < 4; k++) { if (ctx->sort.planes[k]) (void) hipFree(ctx->sort.planes[k]); ctx->sort.planes[k] = nullptr; }
-  ctx->sort.queue = PathQueue{}; ctx->sort.queue_capacity = 0;
-  for (int k = 0; k < 4; k++) HIP_TRY(ctx, hipMalloc(&ctx->sort.planes[k], 16 * (size_t) items));
-  ctx->sort.queue.origin_t = (float4*) ctx->sort.planes[0]; ctx->sort.queue.dir_slot = (float4*) ctx->sort.planes[1];
-  ctx->sort.queue.aux = (uint4*) ctx->sort.planes[2]; ctx->sort.queue.hit_id = (uint4*) ctx->sort.planes[3];
-  ctx->sort.queue_capacity = items;
+  LumContext::RaySort& s = ctx->sort;
+  if (items == s.planes[3].count()) return 0;  // (the last of the four: a set that was not completed is allocated again)
+  for (auto& plane : s.planes) plane.reset();
+  s.queue = PathQueue{};
+  for (auto& plane : s.planes) HIP_TRY(ctx, plane.resize(items));
+  s.queue.origin_t = s.planes[0].get(); s.queue.dir_slot = s.planes[1].get();
+  s.queue.aux = (uint4*) s.planes[2].get(); s.queue.hit_id = (uint4*) s.planes[3].get();
   return 0;
 }
 
@@ -92,10 +87,10 @@ const uint32_t* sort_rays(LumContext* ctx, hipStream_t stream, const float4* ori
   g.direction_major = ctx->sort.key == 1 ? 1u : 0u;
   Launch l(ctx, stream, LUMC_KERNEL_SORT);
   const uint32_t blocks = std::min<uint32_t>((capacity + 255u) / 256u, 4096u);
-  hipLaunchKernelGGL(k_ray_sort_keys, dim3(blocks ? blocks : 1), dim3(256), 0, stream, origin, dir, count, capacity, g, ctx->sort.d_keys[0], ctx->sort.d_vals[0]);
-  hipcub::DoubleBuffer<uint32_t> keys(ctx->sort.d_keys[0], ctx->sort.d_keys[1]), vals(ctx->sort.d_vals[0], ctx->sort.d_vals[1]);
+  hipLaunchKernelGGL(k_ray_sort_keys, dim3(blocks ? blocks : 1), dim3(256), 0, stream, origin, dir, count, capacity, g, ctx->sort.d_keys[0].get(), ctx->sort.d_vals[0].get());
+  hipcub::DoubleBuffer<uint32_t> keys(ctx->sort.d_keys[0].get(), ctx->sort.d_keys[1].get()), vals(ctx->sort.d_vals[0].get(), ctx->sort.d_vals[1].get());
   size_t bytes = ctx->sort.temp_bytes;
-  if (hipcub::DeviceRadixSort::SortPairs(ctx->sort.d_temp, bytes, keys, vals, (int) capacity, 0, 22, stream) != hipSuccess) return nullptr;
+  if (hipcub::DeviceRadixSort::SortPairs(ctx->sort.d_temp.get(), bytes, keys, vals, (int) capacity, 0, 22, stream) != hipSuccess) return nullptr;
   return vals.Current();
 }
 
@@ -124,15 +119,10 @@ int sort_closest_rays(LumContext* ctx, hipStream_t stream, PathQueue& queue, uin
 // The buffers of every mode; the settings (mode, key) and the scene's bounds stay.
 void free_sort(LumContext* ctx) {
   LumContext::RaySort& s = ctx->sort;
-  for (int k = 0; k < 4; k++) { if (s.planes[k]) (void) hipFree(s.planes[k]); s.planes[k] = nullptr; }
-  s.queue = PathQueue{}; s.queue_capacity = 0;
-  for (int k = 0; k < 2; k++) {
-    if (s.d_keys[k]) (void) hipFree(s.d_keys[k]);
-    if (s.d_vals[k]) (void) hipFree(s.d_vals[k]);
-    s.d_keys[k] = s.d_vals[k] = nullptr;
-  }
-  if (s.d_temp) (void) hipFree(s.d_temp);
-  s.d_temp = nullptr; s.capacity = 0;
+  for (auto& plane : s.planes) plane.reset();
+  s.queue = PathQueue{};
+  for (int k = 0; k < 2; k++) { s.d_keys[k].reset(); s.d_vals[k].reset(); }
+  s.d_temp.reset();
 }
 
 extern "C" {

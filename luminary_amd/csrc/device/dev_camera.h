@@ -172,4 +172,47 @@ LUM_DEV const DeviceLens& stage_lens(const DeviceLens& arg, DeviceLens* lds) {
   else return arg;
 }
 
+// ---- thin-lens camera (cuda/camera_thin_lens.cuh:8-86, cuda/camera.cuh:29-35) ----
+LUM_DEV void camera_ray(const DeviceScene& sc, const Sampler& smp, V3& origin, V3& ray) {
+  const U2 jq = smp.raw2_at(kRndCameraJitter, 0, 0, 0);  // same jitter for every pixel of a sample (camera_utils.cuh:23-27)
+  const float jx = unit_float(jq.x), jy = unit_float(jq.y);
+  const float step = 2.0f * (sc.cam_fov / sc.width);
+  const float vfov = step * sc.height * 0.5f;
+  const V3 sensor = v3(sc.cam_fov - step * (smp.px + jx), -vfov + step * (smp.py + jy), 1.0f);
+  const V3 to_focal = normalize(v3(0.0f, 0.0f, 0.0f) - sensor);
+  const float focal = fmaxf(sc.cam_object_distance * (1.0f / 0.001f), 0.01f);
+  const V3 focal_point = to_focal * (-focal / to_focal.z);
+  V3 aperture = v3(0.0f, 0.0f, 0.0f);
+  if (sc.cam_aperture_size != 0.0f) {
+    const F2 r = smp.next2(kRndLens);
+    const float asz = sc.cam_aperture_size * (1.0f / 0.001f);
+    if (sc.cam_aperture_shape == 1) {
+      const int blade = (int) (smp.next1(kRndLensBlade) * sc.cam_aperture_blade_count);
+      const float alpha = sqrtf(r.x), beta = r.y;
+      const float u = 1.0f - alpha, v = alpha * beta;
+      const float astep = (2.0f * kPi) / sc.cam_aperture_blade_count;
+      float s1, c1, s2, c2;
+      sincos_det(astep * blade, s1, c1); sincos_det(astep * (blade + 1), s2, c2);
+      aperture = v3((s1 * u + s2 * v) * asz, (c1 * u + c2 * v) * asz, 0.0f);
+    }
+    else {
+      const float alpha = r.x * 2.0f * kPi, beta = sqrtf(r.y) * asz;
+      float sa, ca; sincos_det(alpha, sa, ca);
+      aperture = v3(ca * beta, sa * beta, 0.0f);
+    }
+  }
+  const Quat q{sc.cam_rotation[0], sc.cam_rotation[1], sc.cam_rotation[2], sc.cam_rotation[3]};
+  V3 o = qapply(q, aperture);
+  o = o * (sc.cam_scale * 0.001f);
+  origin = o + v3(sc.cam_pos[0], sc.cam_pos[1], sc.cam_pos[2]);
+  ray = qapply(q, normalize(focal_point - aperture));
+}
+
+// The camera ray of a sample by camera kind; returns its weight (the thin lens's is 1).
+template <int kCam>
+LUM_DEV float camera_sample(const DeviceScene& sc, const DeviceLens& lens, const Sampler& smp, V3& o, V3& d) {
+  if constexpr (kCam == kCamThinLens) { camera_ray(sc, smp, o, d); return 1.0f; }
+  else return camera_sample_physical<kCam == kCamPhysicalReflections>(sc, lens, smp, o, d);
+}
+
 LUM_NS_END

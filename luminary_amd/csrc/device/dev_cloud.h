@@ -123,77 +123,6 @@ LUM_DEV float dilate_perlin_worley(float p, float w, float x) {
 LUM_DEV uint32_t cloud_pack(float a, float b, float c, float d) {  // make_uchar4 of float products: the conversion truncates
   return ((uint32_t) a & 0xFFu) | (((uint32_t) b & 0xFFu) << 8) | (((uint32_t) c & 0xFFu) << 16) | (((uint32_t) d & 0xFFu) << 24);
 }
-__global__ void k_cloud_noise_shape(uint32_t* dst, uint32_t dim) {
-  const uint32_t amount = dim * dim * dim;
-  const float sc = 1.0f / dim;
-  for (uint32_t id = blockIdx.x * blockDim.x + threadIdx.x; id < amount; id += gridDim.x * blockDim.x) {
-    const uint32_t z = id / (dim * dim), y = (id - z * (dim * dim)) / dim, x = id - y * dim - z * dim * dim;
-    const V3 s = v3(x * sc, y * sc, z * sc);
-    const float size_scale = 1.0f;
-    float perlin_dilate = perlin_octaves(s, 4.0f * size_scale, 7, true);
-    float worley_dilate = worley_octaves(s, 6.0f * size_scale, 3, 0.0f, 0.3f);
-    float worley_large = worley_octaves(s, 6.0f * size_scale, 3, 0.0f, 0.3f);
-    float worley_medium = worley_octaves(s, 12.0f * size_scale, 3, 0.0f, 0.3f);
-    float worley_small = worley_octaves(s, 24.0f * size_scale, 3, 0.0f, 0.3f);
-    perlin_dilate = c_remap01(perlin_dilate, 0.3f, 1.4f);
-    worley_dilate = c_remap01(worley_dilate, -0.3f, 1.3f);
-    worley_large = c_remap01(worley_large, -0.4f, 1.0f);
-    worley_medium = c_remap01(worley_medium, -0.4f, 1.0f);
-    worley_small = c_remap01(worley_small, -0.4f, 1.0f);
-    const float perlin_worley = dilate_perlin_worley(perlin_dilate, worley_dilate, 0.3f);
-    dst[id] = cloud_pack(saturate(perlin_worley) * 255.0f, saturate(worley_large) * 255.0f, saturate(worley_medium) * 255.0f, saturate(worley_small) * 255.0f);
-  }
-}
-__global__ void k_cloud_noise_detail(uint32_t* dst, uint32_t dim) {
-  const uint32_t amount = dim * dim * dim;
-  const float sc = 1.0f / dim;
-  for (uint32_t id = blockIdx.x * blockDim.x + threadIdx.x; id < amount; id += gridDim.x * blockDim.x) {
-    const uint32_t z = id / (dim * dim), y = (id - z * (dim * dim)) / dim, x = id - y * dim - z * dim * dim;
-    const V3 s = v3(x * sc, y * sc, z * sc);
-    const float size_scale = 0.5f;
-    float worley_large = worley_octaves(s, 10.0f * size_scale, 3, 0.0f, 0.3f);
-    float worley_medium = worley_octaves(s, 15.0f * size_scale, 3, 0.0f, 0.3f);
-    float worley_small = worley_octaves(s, 20.0f * size_scale, 3, 0.0f, 0.3f);
-    worley_large = c_remap01(worley_large, -1.0f, 1.0f);
-    worley_medium = c_remap01(worley_medium, -1.0f, 1.0f);
-    worley_small = c_remap01(worley_small, -1.0f, 1.0f);
-    dst[id] = cloud_pack(saturate(worley_large) * 255.0f, saturate(worley_medium) * 255.0f, saturate(worley_small) * 255.0f, 255.0f);
-  }
-}
-__global__ void k_cloud_noise_weather(uint32_t* dst, uint32_t dim, float seed) {
-  const uint32_t amount = dim * dim;
-  const float sc = 1.0f / dim;
-  for (uint32_t id = blockIdx.x * blockDim.x + threadIdx.x; id < amount; id += gridDim.x * blockDim.x) {
-    const uint32_t y = id / dim, x = id - y * dim;
-    const float sx = x * sc, sy = y * sc;
-    const float size_scale = 3.0f, coverage_perlin_worley_diff = 0.4f, remap_low = 0.5f, remap_high = 1.3f;
-    float perlin1 = perlin_octaves(v3(sx, sy, 0.0f), 2.0f * size_scale, 7, true);
-    float worley1 = worley_octaves(v3(sx, sy, 0.0f), 3.0f * size_scale, 2, seed, 0.25f);
-    float perlin2 = perlin_octaves(v3(sx, sy, 500.0f), 4.0f * size_scale, 7, true);
-    float perlin3 = perlin_octaves(v3(sx, sy, 100.0f), 2.0f * size_scale, 7, true);
-    float perlin4 = perlin_octaves(v3(sx, sy, 200.0f), 3.0f * size_scale, 7, true);
-    perlin1 = c_remap01(perlin1, remap_low, remap_high);
-    worley1 = c_remap01(worley1, remap_low, remap_high);
-    perlin2 = c_remap01(perlin2, remap_low, remap_high);
-    perlin3 = c_remap01(perlin3, remap_low, remap_high);
-    perlin4 = c_remap01(perlin4, remap_low, remap_high);
-    perlin1 = pow_det(perlin1, 1.0f);
-    worley1 = pow_det(worley1, 0.75f);
-    perlin2 = pow_det(perlin2, 2.0f);
-    perlin3 = pow_det(perlin3, 3.0f);
-    perlin4 = pow_det(perlin4, 1.0f);
-    perlin1 = saturate(perlin1 * 1.2f) * 0.4f + 0.1f;
-    worley1 = saturate(1.0f - worley1 * 2.0f);
-    perlin2 = saturate(perlin2) * 0.5f;
-    perlin3 = saturate(1.0f - perlin3 * 3.0f);
-    perlin4 = saturate(1.0f - perlin4 * 1.5f);
-    perlin4 = dilate_perlin_worley(worley1, perlin4, coverage_perlin_worley_diff);
-    perlin1 -= perlin4;
-    perlin2 -= perlin4 * perlin4;
-    perlin1 = c_remap01(2.0f * perlin1, 0.05f, 1.0f);
-    dst[id] = cloud_pack(saturate(perlin1) * 255.0f, saturate(perlin2) * 255.0f, saturate(perlin3) * 255.0f, saturate(perlin4) * 255.0f);
-  }
-}
 
 // ---- texture lookups ----
 LUM_DEV float4 cloud_texel(uint32_t t) {

@@ -16,15 +16,12 @@
 
 LUM_NS_BEGIN
 
-constexpr uint32_t kGuidePlanes = 7;     // albedo[3], normal[3], depth
-constexpr uint32_t kGuideSumPlanes = 9;  // + samples that hit something, samples that had a path at all
+// (kGuidePlanes, kGuideSumPlanes, struct DenoiseArgs: dev_scene.h)
 constexpr uint32_t kDenoiseTileX = 32, kDenoiseTileY = 8;  // a workgroup of 256: each wave's two rows are 32 consecutive records (512 B per tap)
 constexpr uint32_t kDenoiseMaxLdsStep = 2;
 constexpr uint32_t kDenoiseLdsRecords = (kDenoiseTileX + 4 * kDenoiseMaxLdsStep) * (kDenoiseTileY + 4 * kDenoiseMaxLdsStep);  // 40 x 16: 20 KB with both records
 constexpr float kDenoiseAlbedoFloor = 1e-3f;
 constexpr float kDenoiseCutoff = -30.0f;  // taps below 2^-30 of their B3 weight are skipped
-
-// (struct DenoiseArgs: dev_scene.h)
 
 // ---- guides ----
 __global__ __launch_bounds__(kBlock) void k_guide(DeviceScene sc, PathQueue in, const uint32_t* ctrl, float* planes, uint32_t n) {

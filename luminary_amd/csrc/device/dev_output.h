@@ -182,57 +182,6 @@ LUM_DEV Col display_transform(const OutputParams& p, Col px, uint32_t x, uint32_
   return tonemap_curve(p, px);
 }
 
-#if !LUM_FAST  // flavour-neutral: compiled once, in the exact translation unit
-// generate_final_image, kernels.cuh:503-556 (with accumulation_generate_result's division by the sample count folded in): planar input
-// image of (src >> stage) pixels -> planar display-referred RGB of (src >> max(stage, supersampling)) pixels; every output pixel is the
-// mean of the output_scale^2 tone-mapped input pixels below it, summed row by row.
-__global__ __launch_bounds__(256) void k_final_image(OutputParams p, const float* __restrict__ input, float* __restrict__ frame_output) {
-  const uint32_t ui = p.undersampling_stage, uo = max(ui, p.supersampling);
-  const uint32_t output_scale = 1u << (uo - ui);
-  const uint32_t out_w = p.src_width >> uo, out_h = p.src_height >> uo, in_w = p.src_width >> ui, in_h = p.src_height >> ui;
-  const uint32_t n = out_w * out_h, n_in = in_w * in_h;
-  const float norm = 1.0f / (output_scale * output_scale);
-  for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
-    const uint32_t y = i / out_w, x = i - y * out_w;
-    const uint32_t source_x = x * output_scale, source_y = y * output_scale;
-    Col color = splat(0.0f);
-    for (uint32_t yi = 0; yi < output_scale; yi++) {
-      for (uint32_t xi = 0; xi < output_scale; xi++) {
-        const uint32_t px_x = min(source_x + xi, in_w - 1), px_y = min(source_y + yi, in_h - 1);
-        const uint32_t index = px_x + px_y * in_w;
-        Col px = col(input[index] * p.inv_sample_count, input[n_in + index] * p.inv_sample_count, input[2 * n_in + index] * p.inv_sample_count);
-        color = color + display_transform(p, px, px_x, px_y);
-      }
-    }
-    color = color * norm;
-    frame_output[i] = color.r; frame_output[n + i] = color.g; frame_output[2 * n + i] = color.b;
-  }
-}
-#endif
-
-#if !LUM_FAST  // flavour-neutral: compiled once, in the exact translation unit
-// accumulation_generate_result_undersampling, accumulation.cuh:192-254: while the first sample is rendered coarse to fine, block (x, y) of
-// 2^stage pixels shows the mean of the 4 - iteration pixels of it that exist so far (pattern of kernels.cuh:20-45). Output: compact
-// planar image of (width >> stage) x (height >> stage).
-__global__ __launch_bounds__(256) void k_result_undersampled(const float* __restrict__ first_moment, uint32_t width, uint32_t height, uint32_t stage, uint32_t iteration,
-                                                             float* __restrict__ result) {
-  const uint32_t scale = 1u << stage, w = width >> stage, h = height >> stage, n = w * h, frame = width * height;
-  const float color_scale = 1.0f / (4 - iteration);
-  for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
-    const uint32_t dst_y = i / w, dst_x = i - dst_y * w;
-    const uint32_t base_x = dst_x << stage, base_y = dst_y << stage;
-    Col sum = splat(0.0f);
-    for (uint32_t id = iteration; id < 4; id++) {
-      const uint32_t px = min(base_x + ((id & 1u) ? 0u : scale >> 1), width - 1), py = min(base_y + ((id & 2u) ? 0u : scale >> 1), height - 1);
-      const uint32_t index = px + py * width;
-      sum = sum + col(first_moment[index], first_moment[frame + index], first_moment[2 * frame + index]);
-    }
-    sum = sum * color_scale;
-    result[i] = sum.r; result[n + i] = sum.g; result[2 * n + i] = sum.b;
-  }
-}
-#endif
-
 // post_sample_buffer_clamp, post_common.cuh:6-59. `width`/`height` are the nominal output size; a coarser image in memory is addressed
 // through mem_scale = 2^-k, whose index arithmetic the reference carries out in float (kept: it decides the rounding of the row offset).
 // `last`: index of the plane's last element. A frame that is not a multiple of the coarse block makes the reference read past the coarse
@@ -274,57 +223,6 @@ LUM_DEV float sample_plane_border(const float* __restrict__ plane, float x, floa
   r += p11 * (fx * fy);
   return r * weight;
 }
-#if !LUM_FAST  // flavour-neutral: compiled once, in the exact translation unit
-__global__ __launch_bounds__(256) void k_post_downsample(const float* __restrict__ src, uint32_t sw, uint32_t sh, float* __restrict__ dst, uint32_t tw, uint32_t th) {
-  const float scale_x = 1.0f / (tw - 1), scale_y = 1.0f / (th - 1), step_x = 1.0f / (sw - 1), step_y = 1.0f / (sh - 1);
-  const uint32_t n = tw * th;
-  for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
-    const uint32_t y = i / tw, x = i - y * tw;
-    const float sx = scale_x * x, sy = scale_y * y;
-    float p = 0.0f;
-    p += sample_plane_border(src, sx - 0.5f * step_x, sy - 0.5f * step_y, sw, sh, 1.0f);
-    p += sample_plane_border(src, sx + 0.5f * step_x, sy - 0.5f * step_y, sw, sh, 1.0f);
-    p += sample_plane_border(src, sx - 0.5f * step_x, sy + 0.5f * step_y, sw, sh, 1.0f);
-    p += sample_plane_border(src, sx + 0.5f * step_x, sy + 0.5f * step_y, sw, sh, 1.0f);
-    p += sample_plane_border(src, sx, sy, sw, sh, 1.0f);
-    p += sample_plane_border(src, sx, sy - step_y, sw, sh, 0.5f);
-    p += sample_plane_border(src, sx - step_x, sy, sw, sh, 0.5f);
-    p += sample_plane_border(src, sx + step_x, sy, sw, sh, 0.5f);
-    p += sample_plane_border(src, sx, sy + step_y, sw, sh, 0.5f);
-    p += sample_plane_border(src, sx - step_x, sy - step_y, sw, sh, 0.25f);
-    p += sample_plane_border(src, sx + step_x, sy - step_y, sw, sh, 0.25f);
-    p += sample_plane_border(src, sx - step_x, sy + step_y, sw, sh, 0.25f);
-    p += sample_plane_border(src, sx + step_x, sy + step_y, sw, sh, 0.25f);
-    p *= 1.0f / 8.0f;
-    dst[i] = fmaxf(p, 0.0f);  // threshold 0 (device_post.c:82)
-  }
-}
-#endif
-#if !LUM_FAST  // flavour-neutral: compiled once, in the exact translation unit
-// dst may be the base image (every thread reads only its own base pixel)
-__global__ __launch_bounds__(256) void k_post_upsample(const float* __restrict__ src, uint32_t sw, uint32_t sh, float* dst, uint32_t tw, uint32_t th, float sa, float sb) {
-  const float scale_x = 1.0f / (tw - 1), scale_y = 1.0f / (th - 1), step_x = 1.0f / (sw - 1), step_y = 1.0f / (sh - 1);
-  const uint32_t n = tw * th;
-  for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
-    const uint32_t y = i / tw, x = i - y * tw;
-    const float sx = scale_x * x, sy = scale_y * y;
-    float p = sample_plane_border(src, sx - step_x, sy - step_y, sw, sh, 1.0f);
-    p += sample_plane_border(src, sx, sy - step_y, sw, sh, 2.0f);
-    p += sample_plane_border(src, sx + step_x, sy - step_y, sw, sh, 1.0f);
-    p += sample_plane_border(src, sx - step_x, sy, sw, sh, 2.0f);
-    p += sample_plane_border(src, sx, sy, sw, sh, 4.0f);
-    p += sample_plane_border(src, sx + step_x, sy, sw, sh, 2.0f);
-    p += sample_plane_border(src, sx - step_x, sy + step_y, sw, sh, 1.0f);
-    p += sample_plane_border(src, sx, sy + step_y, sw, sh, 2.0f);
-    p += sample_plane_border(src, sx + step_x, sy + step_y, sw, sh, 1.0f);
-    p *= 1.0f / 20.0f;
-    p *= sa;
-    float base = dst[i];
-    base *= sb;
-    dst[i] = p + base;
-  }
-}
-#endif
 
 LUM_DEV float dither_mask(const uint16_t* __restrict__ bluenoise_1d, uint32_t x, uint32_t y) { return unit_float16(bluenoise_1d[(x & 255u) + (y & 255u) * 256u]); }
 
@@ -362,38 +260,5 @@ LUM_DEV Col apply_filter(const OutputParams& p, const uint16_t* __restrict__ bn,
     default: return px;
   }
 }
-
-#if !LUM_FAST  // flavour-neutral: compiled once, in the exact translation unit
-// convert_RGBF_to_ARGB8, kernels.cuh:558-644 (bytes b, g, r, a)
-__global__ __launch_bounds__(256) void k_to_argb8(OutputParams p, const float* __restrict__ frame_output, const uint16_t* __restrict__ bluenoise_1d,
-                                                  uint32_t* __restrict__ dst) {
-  const uint32_t uo = max(p.undersampling_stage, p.supersampling), um = uo - p.supersampling;
-  const uint32_t nominal_w = p.src_width >> p.supersampling, nominal_h = p.src_height >> p.supersampling;  // the size the frame is rendered for
-  const uint32_t mem_w = p.src_width >> uo, mem_h = p.src_height >> uo, ns = mem_w * mem_h;                // the image in memory
-  const uint32_t n = p.dst_width * p.dst_height;
-  const float scale_x = 1.0f / (p.dst_width - 1), scale_y = 1.0f / (p.dst_height - 1);
-  const float mem_scale = 1.0f / (1u << um);
-  const bool scaled = p.dst_width != nominal_w || p.dst_height != nominal_h;
-  for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
-    const uint32_t y = i / p.dst_width, x = i - y * p.dst_width;
-    Col px;
-    if (scaled) {
-      const float sx = x * scale_x, sy = y * scale_y;
-      px = col(sample_plane(frame_output, sx, sy, nominal_w, nominal_h, mem_scale, ns - 1), sample_plane(frame_output + ns, sx, sy, nominal_w, nominal_h, mem_scale, ns - 1),
-               sample_plane(frame_output + 2 * ns, sx, sy, nominal_w, nominal_h, mem_scale, ns - 1));
-    }
-    else {
-      const uint32_t src = min(x >> um, mem_w - 1) + min(y >> um, mem_h - 1) * mem_w;  // the edge repeats where the reference reads past the coarse image
-      px = col(frame_output[src], frame_output[ns + src], frame_output[2 * ns + src]);
-    }
-    px = apply_filter(p, bluenoise_1d, px, x, y);
-    const float dither = p.dithering ? dither_mask(bluenoise_1d, x, y) : 0.5f;
-    const float r = fmaxf(0.0f, fminf(255.9999f, dither + 255.0f * linear_to_srgb(px.r)));
-    const float g = fmaxf(0.0f, fminf(255.9999f, dither + 255.0f * linear_to_srgb(px.g)));
-    const float b = fmaxf(0.0f, fminf(255.9999f, dither + 255.0f * linear_to_srgb(px.b)));
-    dst[i] = 0xFF000000u | (f2u_sat(r) << 16) | (f2u_sat(g) << 8) | f2u_sat(b);
-  }
-}
-#endif
 
 LUM_NS_END

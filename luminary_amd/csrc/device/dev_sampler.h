@@ -3,6 +3,8 @@
 // :232-287 Sobol/Owen, :309-368 blue noise + wrappers) and cuda/utils.cuh:147-178 (PathID is kept unpacked here).
 #pragma once
 
+#include <vector>
+
 #include "dev_math.h"
 
 LUM_NS_BEGIN
@@ -42,10 +44,28 @@ LUM_DEV uint32_t sobol_second_dim(uint32_t v) {
 }
 // squares32(key, dimension) for every dimension a path can ask for (target + depth * kRndTargetCount, depth < 64): a random number's dimension is
 // the same in every lane of every wave, so its seed is one scalar load from this table instead of six 32-bit multiplies (quarter-rate instructions) and
-// a dozen other vector instructions per random number and lane - the hash was a twelfth of the shading kernel. Filled per device and flavour by
-// init_sampler_seeds() (wavefront_table_impl.h) with the same integer function.
+// a dozen other vector instructions per random number and lane - the hash was a twelfth of the shading kernel. The table exists once per translation unit
+// that includes this header; upload_sampler_seeds() fills the including unit's copy on the current device with the same integer function. Every unit whose
+// kernels draw random numbers calls it per device: each flavour's table (init_sampler_seeds, wavefront_table_impl.h) and core.hip (lumc_context_create).
 constexpr uint32_t kSeedTableSize = 64u * kRndTargetCount;
 __constant__ uint32_t g_sampler_seeds[kSeedTableSize];
+static int upload_sampler_seeds() {  // returns a hipError_t
+  static std::vector<uint32_t> seeds;  // squares32(0xfcbd6e15, dimension), random.cuh:172-194 - the device function's integer arithmetic on the host
+  if (seeds.empty()) {
+    seeds.resize(kSeedTableSize);
+    auto swap_h = [](uint32_t a) { return (a >> 16) | (a << 16); };
+    const uint32_t key = 0xfcbd6e15u;
+    for (uint32_t d = 0; d < kSeedTableSize; d++) {
+      uint32_t x = d * key, y = d * key, z = y + key;
+      x = x * x + y; x = swap_h(x);
+      x = x * x + z; x = swap_h(x);
+      x = x * x + y; x = swap_h(x);
+      x = x * x + z; z = x; x = swap_h(x);
+      seeds[d] = z ^ (x * x + y);
+    }
+  }
+  return (int) hipMemcpyToSymbol(HIP_SYMBOL(g_sampler_seeds), seeds.data(), sizeof(uint32_t) * kSeedTableSize);
+}
 LUM_DEV U2 sobol_owen(uint32_t index, uint32_t dimension) {
   const uint32_t seed = g_sampler_seeds[dimension];
   const uint32_t j    = laine_karras(__brev(index), seed);

@@ -229,6 +229,9 @@ struct AdaptiveView {
   uint32_t stage_id;
 };
 struct AdaptivePass { uint32_t task_begin, task_end, block_begin, block_end, executions; };
+// The denoiser's guide planes (dev_denoise.h); the host layer sizes their buffer
+constexpr uint32_t kGuidePlanes = 7;     // albedo[3], normal[3], depth
+constexpr uint32_t kGuideSumPlanes = 9;  // + samples that hit something, samples that had a path at all
 // One launch of the denoiser's kernels (dev_denoise.h): the frame, the a-trous iteration's tap distance, the sample count outside adaptive mode, the edge weights.
 struct DenoiseArgs {
   uint32_t width, height, step, uniform_samples;

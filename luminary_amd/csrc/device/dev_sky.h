@@ -255,26 +255,6 @@ LUM_DEV Spectrum sky_optical_depth(const SkyView& s, float r, float mu) {
   }
   return depth;
 }
-#if !LUM_FAST  // flavour-neutral: compiled once, in the exact translation unit
-__global__ __launch_bounds__(64) void k_sky_transmittance_lut(DeviceScene sc, float4* __restrict__ dst) {
-  const int id = blockIdx.x * 64 + threadIdx.x;
-  if (id >= kSkyTmWidth * kSkyTmHeight) return;
-  const SkyView s = sky_view(sc);
-  const int y = id / kSkyTmWidth, x = id - y * kSkyTmWidth;
-  float fx = ((float) x + 0.5f) / kSkyTmWidth, fy = ((float) y + 0.5f) / kSkyTmHeight;
-  fx = sky_sub_to_unit_uv(fx, kSkyTmWidth); fy = sky_sub_to_unit_uv(fy, kSkyTmHeight);
-  const float H = sqrtf(kSkyAtmoRadius * kSkyAtmoRadius - kSkyEarthRadius * kSkyEarthRadius);
-  const float rho = H * fy;
-  const float r = sqrtf(rho * rho + kSkyEarthRadius * kSkyEarthRadius);
-  const float d_min = kSkyAtmoRadius - r, d_max = rho + H;
-  const float d = d_min + fx * (d_max - d_min);
-  float mu = (d == 0.0f) ? 1.0f : (H * H - rho * rho - d * d) / (2.0f * r * d);
-  mu = fminf(1.0f, fmaxf(-1.0f, mu));
-  const Spectrum t = sp_exp(sp_scale(sky_optical_depth(s, r, mu), -1.0f));
-  dst[id] = make_float4(t.v[0], t.v[1], t.v[2], t.v[3]);
-  dst[kSkyTmWidth * kSkyTmHeight + id] = make_float4(t.v[4], t.v[5], t.v[6], t.v[7]);
-}
-#endif
 
 struct SkyMsResult { Spectrum L, ms_as_1; };
 // sky_compute_multiscattering_integration, sky.cuh:186-273
@@ -316,40 +296,6 @@ LUM_DEV SkyMsResult sky_multiscattering_integration(const SkyView& s, V3 origin,
   }
   return res;
 }
-#if !LUM_FAST  // flavour-neutral: compiled once, in the exact translation unit
-// sky_compute_multiscattering_lut, sky.cuh:276-332: one workgroup of 256 directions per texel, shared-memory tree reduction
-__global__ __launch_bounds__(256) void k_sky_multiscattering_lut(DeviceScene sc, float4* __restrict__ dst) {
-  __shared__ Spectrum lum_shared[kSkyMsIter], ms_shared[kSkyMsIter];
-  const SkyView s = sky_view(sc);
-  const int x = blockIdx.x, y = blockIdx.y;
-  float fx = ((float) x + 0.5f) / kSkyMsSize, fy = ((float) y + 0.5f) / kSkyMsSize;
-  fx = sky_sub_to_unit_uv(fx, kSkyMsSize); fy = sky_sub_to_unit_uv(fy, kSkyMsSize);
-  const float cos_angle = fx * 2.0f - 1.0f;
-  const V3 sun_dir = v3(0.0f, cos_angle, sqrtf(saturate(1.0f - cos_angle * cos_angle)));
-  const float height = kSkyEarthRadius + saturate(fy + kSkyHeightOffset) * (kSkyAtmoHeight - kSkyHeightOffset);
-  const V3 pos = v3(0.0f, height, 0.0f), sun_pos = sun_dir * kSkySunDistance;
-  const float sqrt_sample = (float) kSkyMsBase;
-  const float a = (float) (threadIdx.x / kSkyMsBase), b = (float) (threadIdx.x - (threadIdx.x / kSkyMsBase) * kSkyMsBase);
-  const V3 ray = sample_ray_sphere(2.0f * (a / sqrt_sample) - 1.0f, b / sqrt_sample);
-  const SkyMsResult r = sky_multiscattering_integration(s, pos, ray, sun_pos);
-  lum_shared[threadIdx.x] = r.L; ms_shared[threadIdx.x] = r.ms_as_1;
-  for (int i = kSkyMsIter >> 1; i > 0; i >>= 1) {
-    __syncthreads();
-    if ((int) threadIdx.x < i) {
-      lum_shared[threadIdx.x] = sp_add(lum_shared[threadIdx.x], lum_shared[threadIdx.x + i]);
-      ms_shared[threadIdx.x] = sp_add(ms_shared[threadIdx.x], ms_shared[threadIdx.x + i]);
-    }
-  }
-  if (threadIdx.x > 0) return;
-  const Spectrum luminance = sp_scale(lum_shared[0], 1.0f / (sqrt_sample * sqrt_sample));
-  const Spectrum multiscattering = sp_scale(ms_shared[0], 1.0f / (sqrt_sample * sqrt_sample));
-  const Spectrum contribution = sp_inv(sp_sub(sp_set1(1.0f), multiscattering));
-  const Spectrum L = sp_scale(sp_mul(luminance, contribution), s.multiscattering_factor);
-  const int id = x + y * kSkyMsSize;
-  dst[id] = make_float4(L.v[0], L.v[1], L.v[2], L.v[3]);
-  dst[kSkyMsSize * kSkyMsSize + id] = make_float4(L.v[4], L.v[5], L.v[6], L.v[7]);
-}
-#endif
 
 LUM_DEV Spectrum sky_moon_solar_flux() { return Spectrum{{1.7f, 1.8f, 2.0f, 1.9f, 1.87f, 1.7f, 1.65f, 1.55f}}; }  // sky_utils.cuh:272
 // math.cuh:781-789
@@ -484,7 +430,7 @@ LUM_DEV float sky_hdri_median_of_means(float* buckets, uint32_t num_buckets) {  
   for (uint32_t b = c; b < num_buckets - c; b++) output += buckets[b];
   return output / (float) (num_buckets - 2u * c);
 }
-// (the bake kernel k_sky_hdri is in kernels.h: it marches the clouds, dev_cloud_march.h)
+// (the bake kernel k_sky_hdri is in kernels_shared.h: it marches the clouds, dev_cloud_march.h)
 
 // ---- sun next-event estimation (cuda/direct_lighting.cuh:21-119, :352-383; cuda/bsdf.cuh:355-458) ----
 LUM_DEV bool sphere_hit(V3 ray, V3 origin, V3 p, float r) {  // math.cuh:679-696

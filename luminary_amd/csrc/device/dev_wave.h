@@ -12,7 +12,7 @@
 
 LUM_NS_BEGIN
 
-constexpr int kBlock = 256;  // threads per workgroup of every kernel in kernels.h (context.h's kLaunchBlock on the host side)
+constexpr int kBlock = 256;  // threads per workgroup of every kernel in kernels.h and kernels_shared.h (context.h's kLaunchBlock on the host side)
 
 struct Wave {
   uint32_t lane;              // 0..63

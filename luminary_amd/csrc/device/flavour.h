@@ -1,4 +1,4 @@
-// Arithmetic flavour of the device code. The same headers are compiled twice into libluminary_amd.so:
+// Arithmetic flavour of the device code. The same headers are compiled twice into libluminary_amd.so (wavefront_exact.hip, wavefront_fast.hip):
 //   exact  (LUM_FAST=0, -ffp-contract=off, correctly rounded / and sqrt, fixed polynomial sin/cos/atan2/exp2/log2): every sample is a
 //          pure, bit-reproducible function of (scene, pixel, sample id); HIP == oracle bit for bit. All parity tests run this flavour.
 //   fast   (LUM_FAST=1, -ffp-contract=fast, v_rcp_f32 / v_rsq_f32 / v_sqrt_f32 / v_sin_f32 / v_exp_f32 / v_log_f32): what the reference

@@ -19,6 +19,7 @@
 #include "dev_particle.h"
 #include "dev_water.h"
 #include "dev_cloud_march.h"
+#include "dev_adaptive.h"  // AdaptiveView bookkeeping of k_generate_adaptive
 #include "dev_camera.h"
 #include "dev_wave.h"  // kBlock; the wave64 idioms: append, batch loop, visibility record, roulette
 
@@ -42,42 +43,7 @@ LUM_NS_BEGIN
 #define LUM_SHADE_WAVES_CONSTANT_SKY 3  // both flavours (round 4: the exact flavour's kernel at 3 waves - 168 registers, 8 spilled - instead of 2: -11.5 % of its time, +6 % samples/s)
 #endif
 
-// ---- tasks_create (cuda/kernels.cuh:45-193) + thin-lens camera (cuda/camera_thin_lens.cuh:8-86, cuda/camera.cuh:29-35) ----
-LUM_DEV void camera_ray(const DeviceScene& sc, const Sampler& smp, V3& origin, V3& ray) {
-  const U2 jq = smp.raw2_at(kRndCameraJitter, 0, 0, 0);  // same jitter for every pixel of a sample (camera_utils.cuh:23-27)
-  const float jx = unit_float(jq.x), jy = unit_float(jq.y);
-  const float step = 2.0f * (sc.cam_fov / sc.width);
-  const float vfov = step * sc.height * 0.5f;
-  const V3 sensor = v3(sc.cam_fov - step * (smp.px + jx), -vfov + step * (smp.py + jy), 1.0f);
-  const V3 to_focal = normalize(v3(0.0f, 0.0f, 0.0f) - sensor);
-  const float focal = fmaxf(sc.cam_object_distance * (1.0f / 0.001f), 0.01f);
-  const V3 focal_point = to_focal * (-focal / to_focal.z);
-  V3 aperture = v3(0.0f, 0.0f, 0.0f);
-  if (sc.cam_aperture_size != 0.0f) {
-    const F2 r = smp.next2(kRndLens);
-    const float asz = sc.cam_aperture_size * (1.0f / 0.001f);
-    if (sc.cam_aperture_shape == 1) {
-      const int blade = (int) (smp.next1(kRndLensBlade) * sc.cam_aperture_blade_count);
-      const float alpha = sqrtf(r.x), beta = r.y;
-      const float u = 1.0f - alpha, v = alpha * beta;
-      const float astep = (2.0f * kPi) / sc.cam_aperture_blade_count;
-      float s1, c1, s2, c2;
-      sincos_det(astep * blade, s1, c1); sincos_det(astep * (blade + 1), s2, c2);
-      aperture = v3((s1 * u + s2 * v) * asz, (c1 * u + c2 * v) * asz, 0.0f);
-    }
-    else {
-      const float alpha = r.x * 2.0f * kPi, beta = sqrtf(r.y) * asz;
-      float sa, ca; sincos_det(alpha, sa, ca);
-      aperture = v3(ca * beta, sa * beta, 0.0f);
-    }
-  }
-  const Quat q{sc.cam_rotation[0], sc.cam_rotation[1], sc.cam_rotation[2], sc.cam_rotation[3]};
-  V3 o = qapply(q, aperture);
-  o = o * (sc.cam_scale * 0.001f);
-  origin = o + v3(sc.cam_pos[0], sc.cam_pos[1], sc.cam_pos[2]);
-  ray = qapply(q, normalize(focal_point - aperture));
-}
-
+// ---- tasks_create (cuda/kernels.cuh:45-193); the thin-lens camera and camera_sample: dev_camera.h ----
 // kernels.cuh:146, :172-186: the medium the camera is in (bsdf_refraction_index_ambient, bsdf_utils.cuh:128-133) and the volumes around it, in the
 // upper bits of the sample-id word (dev_volume.h)
 LUM_DEV uint32_t initial_medium(const DeviceScene& sc, V3 origin) {
@@ -88,13 +54,6 @@ LUM_DEV uint32_t initial_volumes(const DeviceScene& sc, V3 origin, uint32_t samp
   if (sc.fog_active) w = volume_stack_modify(w, kVolumeFog, true);
   if (sc.ocean_active && ocean_is_underwater(sc, origin)) w = volume_stack_modify(w, kVolumeOcean, true);
   return w;
-}
-
-// The camera ray of a sample by camera kind; returns its weight (the thin lens's is 1).
-template <int kCam>
-LUM_DEV float camera_sample(const DeviceScene& sc, const DeviceLens& lens, const Sampler& smp, V3& o, V3& d) {
-  if constexpr (kCam == kCamThinLens) { camera_ray(sc, smp, o, d); return 1.0f; }
-  else return camera_sample_physical<kCam == kCamPhysicalReflections>(sc, lens, smp, o, d);
 }
 
 // One camera path of k_generate<physical> / k_generate_adaptive: the lanes whose ray is valid append it to the queue, one atomic per wave
@@ -171,6 +130,50 @@ __global__ __launch_bounds__(kBlock) void k_generate(DeviceScene sc, PassParams 
       }
       generate_path<kCam>(sc, lens, q, count, active, x, y, pp.first_sample + b, i);
     }
+  }
+}
+
+// tasks_create_adaptive_sampling (cuda/kernels.cuh:195-355): task -> (block, pixel of the block, sample of this execution).
+// Result slot = task id; paths are appended compacted (tasks outside the frame or beyond the last sample id create nothing).
+// One pass covers the tasks [task_begin, task_end) = all tasks of the blocks [block_begin, block_end); slots are relative to task_begin.
+// `executions` consecutive executions of the stage share the pass: a pixel then takes executions * rate consecutive sample ids, which
+// are added in the same order as one execution after the other would add them. Task numbers are in units of the merged pass
+// (block_task_end * executions).
+// (struct AdaptivePass: dev_scene.h)
+
+template <int kCam>
+__global__ __launch_bounds__(256) void k_generate_adaptive(DeviceScene sc, AdaptiveView a, AdaptivePass pass, PathQueue q, float4* results, uint32_t* count,
+                                                          DeviceLens lens_arg) {
+  __shared__ DeviceLens lds_lens;
+  const DeviceLens& lens = stage_lens<kCam>(lens_arg, &lds_lens);
+  const uint32_t pass_tasks = pass.task_end - pass.task_begin;
+  const uint32_t rounds = (pass_tasks + gridDim.x * 256u - 1u) / (gridDim.x * 256u);
+  for (uint32_t round = 0; round < rounds; round++) {
+    const uint32_t slot = (round * gridDim.x + blockIdx.x) * 256u + threadIdx.x;
+    const uint32_t t = pass.task_begin + slot;
+    bool valid = false;
+    uint32_t x = 0, y = 0, sample_id = 0;
+    if (slot < pass_tasks) {
+      // adaptive_sampling_find_block (adaptive_sampling.cuh:24-47): first block whose end lies beyond the task
+      uint32_t lo = pass.block_begin, hi = pass.block_end - 1u;
+      while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (t < a.block_task_end[mid] * pass.executions) hi = mid; else lo = mid + 1u;
+      }
+      const uint32_t block = lo;
+      const uint32_t base = block ? a.block_task_end[block - 1u] * pass.executions : 0u;
+      const uint32_t packed = a.stage_counts[block];
+      const uint32_t per_pixel = adaptive_stage_count(packed, a.stage_id) * pass.executions;
+      const uint32_t local = t - base;
+      const uint32_t local_pixel = local / per_pixel, local_sample = local - local_pixel * per_pixel;
+      const uint32_t by = block / a.blocks_x, bx = block - by * a.blocks_x;
+      x = (bx << kAdaptiveBlockLog) + (local_pixel & 3u);
+      y = (by << kAdaptiveBlockLog) + (local_pixel >> kAdaptiveBlockLog);
+      sample_id = adaptive_pixel_samples(a, packed) + local_sample;
+      valid = x < sc.width && y < sc.height && sample_id < kMaxGlobalSamples;
+      results[slot] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    }
+    generate_path<kCam>(sc, lens, q, count, valid, x, y, sample_id, slot);
   }
 }
 
@@ -1667,89 +1670,6 @@ __global__ __launch_bounds__(kBlock, LUM_CLOUD_WAVES) void k_clouds(DeviceScene 
   }
 }
 
-// ---- HDRI bake (cuda/sky_hdri.cuh:13-160, device/device_sky.c:283-316): the sky without celestial bodies - and with the clouds, when active - seen from
-// `origin`, as an equirectangular dim x dim image. 32 lanes per texel share its samples; their means go through the reference's trimmed mean. ----
-#if !LUM_FAST  // flavour-neutral: compiled once, in the exact translation unit
-// The material word of the traversal triangles (dev_scene.h): the albedo texture's id, or - untextured - whether a visibility ray cannot pass
-// (kBvhTriOpaque: the decision of optix_anyhit.cuh:49-139 for alpha 1), taken once per triangle with the kernels' own material decoding; run at
-// scene upload and again after a material edit.
-__global__ __launch_bounds__(kBlock) void k_tri_opacity(DeviceScene sc, BvhTri* tris, uint32_t count) {
-  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-  if (i >= count) return;
-  const uint32_t material = sc.tri_tex[tris[i].scene_index].w & 0xFFFFu;
-  uint32_t word = kBvhTriNoTexture;
-  if (material < sc.num_materials) {
-    const Material m = load_material(sc, material);
-    word = (m.albedo_tex != kTextureNone) ? m.albedo_tex : ((m.alpha == 1.0f) ? kBvhTriOpaque : kBvhTriNoTexture);  // textured: the texel decides
-  }
-  tris[i].albedo_tex = word;
-}
-
-// The emissive triangles in world space, one record per light id (load_tri_light_table, dev_light.h): light_triangle_init's result
-// (light_triangle.cuh:37-72) evaluated once per light at scene upload instead of once per candidate and vertex.
-__global__ __launch_bounds__(kBlock) void k_light_table(DeviceScene sc, float4* table) {
-  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
-  if (i >= sc.num_lights) return;
-  const uint2 handle = sc.light_tri_handles[i];
-  const TriLight t = load_tri_light(sc, handle.x, handle.y);
-  const Material m = load_material(sc, t.material_id);
-  const bool textured = m.luminance_tex != kTextureNone || m.albedo_tex != kTextureNone;
-  const Col color = textured ? splat(0.0f) : tri_light_color(sc, t, F2{0.0f, 0.0f});  // without textures the colour does not depend on the point
-  table[4u * i] = make_float4(t.vertex.x, t.vertex.y, t.vertex.z, bitsf(t.material_id | (t.bidirectional ? 0x10000u : 0u)));
-  table[4u * i + 1u] = make_float4(t.edge1.x, t.edge1.y, t.edge1.z, bitsf(t.scene_tri));
-  table[4u * i + 2u] = make_float4(t.edge2.x, t.edge2.y, t.edge2.z, tri_light_area(t));
-  table[4u * i + 3u] = make_float4(color.r, color.g, color.b, bitsf(textured ? 1u : 0u));
-}
-#endif
-
-#if !LUM_FAST  // flavour-neutral: compiled once, in the exact translation unit
-__global__ __launch_bounds__(256) void k_sky_hdri(DeviceScene sc, float ox, float oy, float oz, uint32_t dim, uint32_t sample_count, float4* __restrict__ dst) {
-  __shared__ float values[256];
-  const uint32_t pixel = (blockIdx.x * 256u + threadIdx.x) >> 5, lane = threadIdx.x & 31u;
-  const bool in_range = pixel < dim * dim;
-  const uint32_t y = in_range ? pixel / dim : 0u, x = in_range ? pixel - y * dim : 0u;
-  const SkyView sky = sky_view(sc);
-  const float step_size = 1.0f / (float) (dim - 1u);
-  Col color = splat(0.0f);
-  float alpha = 0.0f;
-  uint32_t num_samples = 0;
-  const bool clouds = sc.cloud_active && sc.cloud_noise_shape != nullptr;
-  if (in_range) {
-    for (uint32_t sample_id = lane; sample_id < sample_count; sample_id += 32u) {
-      const Sampler smp{sc.bluenoise_2d, x, y, sample_id, 0};
-      const F2 jitter = smp.next2(kRndCameraJitter);
-      const float u = ((float) x + jitter.x) * step_size, v = 1.0f - ((float) y + jitter.y) * step_size;
-      const float altitude = kPi * v - 0.5f * kPi, azimuth = 2.0f * kPi * u - kPi;
-      const V3 ray = angles_to_direction(altitude, azimuth);
-      Col sky_color = splat(0.0f), transmittance = splat(1.0f);
-      float cloud_transmittance = 1.0f;
-      V3 sky_origin = world_to_sky(sky, v3(ox, oy, oz));
-      if (clouds) {  // sky_hdri.cuh:88-92: the clouds in front, the sky behind them dimmed by their transmittance
-        const float offset = clouds_render(sc, sky, smp, sky_origin, ray, kFltMax, sky_color, transmittance, cloud_transmittance);
-        sky_origin = sky_origin + ray * offset;
-      }
-      const Col behind = sky_get_color(sc, sky, sky_origin, ray, kFltMax, false, (int) sky.steps, smp.next1(kRndSkyStepOffset));
-      sky_color = sky_color + behind * transmittance;
-      color = color + sky_color;
-      alpha += cloud_transmittance;
-      num_samples++;
-    }
-  }
-  const uint32_t buckets = min(32u, sample_count);
-  float* group = values + (threadIdx.x & ~31u);
-  float out[4];
-  const float mean[4] = {num_samples ? color.r / (float) num_samples : 0.0f, num_samples ? color.g / (float) num_samples : 0.0f, num_samples ? color.b / (float) num_samples : 0.0f,
-                         num_samples ? alpha / (float) num_samples : 0.0f};
-#pragma unroll
-  for (int ch = 0; ch < 4; ch++) {
-    __syncthreads();
-    values[threadIdx.x] = mean[ch];
-    __syncthreads();
-    out[ch] = (lane == 0u && in_range) ? sky_hdri_median_of_means(group, buckets) : 0.0f;
-  }
-  if (lane == 0u && in_range) dst[x + y * dim] = make_float4(out[0], out[1], out[2], out[3]);  // .w: the clouds' own transmittance (the reference's separate shadow texture), 1 without clouds
-}
-#endif
 
 // ---- fog (cuda/volume.cuh; queue order device/device_renderer.c:64-76, :114-118) ----
 // volume_process_inscattering (volume.cuh:31-98): what the fog scatters into the ray between its origin and its end point (the hit, or infinity
@@ -2037,36 +1957,6 @@ __global__ __launch_bounds__(kBlock) void k_volume_bounce(DeviceScene sc, PathQu
   }
 }
 
-#if !LUM_FAST  // flavour-neutral: compiled once, in the exact translation unit
-// ---- accumulation (cuda/accumulation.cuh:63-84): samples of a pixel are added in sample order ----
-__global__ __launch_bounds__(kBlock) void k_accumulate(const float4* results, uint32_t num_pixels, uint32_t batch, float* first_moment, float* second_moment) {
-  for (uint32_t p = blockIdx.x * kBlock + threadIdx.x; p < num_pixels; p += gridDim.x * kBlock) {
-    float r = first_moment[p], g = first_moment[num_pixels + p], b = first_moment[2 * num_pixels + p];
-    float s = second_moment ? second_moment[p] : 0.0f;
-    for (uint32_t k = 0; k < batch; k++) {
-      const float4 v = results[k * num_pixels + p];
-      r += v.x; g += v.y; b += v.z;
-      s += luminance(col(v.x * v.x, v.y * v.y, v.z * v.z));
-    }
-    first_moment[p] = r; first_moment[num_pixels + p] = g; first_moment[2 * num_pixels + p] = b;
-    if (second_moment) second_moment[p] = s;
-  }
-}
-
-// One sample of a subset of the frame's pixels (an iteration of the undersampling preview, kernels.cuh:47-95): result p belongs to frame
-// pixel pixels[p]. accumulation_collect_results, accumulation.cuh:36-61, with one result per pixel.
-__global__ __launch_bounds__(kBlock) void k_accumulate_scatter(const float4* results, const uint32_t* pixels, uint32_t count, uint32_t frame_pixels, float* first_moment,
-                                                               float* second_moment) {
-  for (uint32_t p = blockIdx.x * kBlock + threadIdx.x; p < count; p += gridDim.x * kBlock) {
-    const uint32_t index = pixels[p];
-    const float4 v = results[p];
-    first_moment[index] += v.x; first_moment[frame_pixels + index] += v.y; first_moment[2 * frame_pixels + index] += v.z;
-    if (second_moment) second_moment[index] += luminance(col(v.x * v.x, v.y * v.y, v.z * v.z));
-  }
-}
-
-#endif
-
 // ---- standalone closest-hit entry for traversal tests and the trace micro-benchmark ----
 struct RaysQuery : ClosestState {
   const float* origins; const float* dirs; const uint32_t* ignore; uint32_t* out;
@@ -2112,88 +2002,5 @@ __global__ __launch_bounds__(256) void k_sobol_table(uint2* __restrict__ table, 
   const U2 q = sobol_owen(first_sample + s, dim);
   table[t] = make_uint2(q.x, q.y);
 }
-
-#if !LUM_FAST  // flavour-neutral: compiled once, in the exact translation unit
-// ---- standalone visibility entry (lumc_trace_visibility): plain per-ray arrays into a ShadowQueue whose output index is the ray index, and its answers back ----
-__global__ __launch_bounds__(256) void k_visibility_pack(uint32_t n, const float* origins, const float* dirs, const float* dist, const uint32_t* ids, ShadowQueue sq) {
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  if (i >= n) return;
-  sq.origin_dist[i] = make_float4(origins[3 * i], origins[3 * i + 1], origins[3 * i + 2], dist[i]);
-  sq.dir_out[i] = make_float4(dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2], bitsf(i));
-  sq.ids[i] = make_uint4(ids[4 * i], ids[4 * i + 1], ids[4 * i + 2], ids[4 * i + 3]);
-}
-__global__ __launch_bounds__(256) void k_visibility_unpack(uint32_t n, const float4* vis, float* out) {
-  const uint32_t i = blockIdx.x * 256u + threadIdx.x;
-  if (i >= n) return;
-  const float4 v = vis[i];
-  out[3 * i] = v.x; out[3 * i + 1] = v.y; out[3 * i + 2] = v.z;
-}
-
-// ---- camera ray of one pixel (first sample id), for pixel queries; valid[0] = 0: the ray did not leave the lens ----
-__global__ void k_pixel_ray(DeviceScene sc, DeviceLens lens, int cam, uint32_t x, uint32_t y, uint32_t sample_id, float* origin, float* dir, uint32_t* valid) {
-  if (blockIdx.x != 0 || threadIdx.x != 0) return;
-  const Sampler smp{sc.bluenoise_2d, x, y, sample_id, 0};
-  V3 o, d;
-  float w = 1.0f;
-  if (cam == kCamThinLens) camera_ray(sc, smp, o, d);
-  else if (cam == kCamPhysical) w = camera_sample<kCamPhysical>(sc, lens, smp, o, d);
-  else w = camera_sample<kCamPhysicalReflections>(sc, lens, smp, o, d);
-  origin[0] = o.x; origin[1] = o.y; origin[2] = o.z;
-  dir[0] = d.x; dir[1] = d.y; dir[2] = d.z;
-  valid[0] = w > 0.0f ? 1u : 0u;
-}
-
-// ---- BSDF energy LUTs (cuda/bsdf_lut.cuh:20-211): pixel (0,0), depth 0, sample id = iteration ----
-LUM_DEV uint16_t quantise_energy(float sum) { return (uint16_t) (1 + (uint16_t) (ceilf(saturate(sum) * 0xFFFE))); }
-
-__global__ void k_generate_lut(const uint32_t* bluenoise, int table, uint32_t count, const uint16_t* conductor, uint16_t* dst) {
-  const uint32_t id = blockIdx.x * blockDim.x + threadIdx.x;
-  if (id >= count) return;
-  uint32_t x, y, z = 0;
-  if (table < 2) { y = id / 32; x = id - y * 32; }
-  else { z = id / 1024; y = (id - z * 1024) / 32; x = id - y * 32 - z * 1024; }
-  const float NdotV = fmaxf(32.0f * kEps, x * (1.0f / 31));
-  const float roughness = y * (1.0f / 31);
-  const V3 V = normalize(v3(0.0f, sqrtf(1.0f - NdotV * NdotV), NdotV));
-  Sampler smp{bluenoise, 0, 0, 0, 0};
-  float sum = 0.0f;
-  if (table < 2) {
-    const Col f0 = col(0.04f, 0.04f, 0.04f);
-    for (uint32_t i = 0; i < 0x10000u; i++) {
-      smp.sample_id = i;
-      const V3 H = sample_vndf_bounded(V, roughness, smp.next2(kRndBsdfReflection));
-      const V3 R = reflect(V, H);
-      if (R.z > 0.0f) {
-        float v = eval_microfacet_over_vndf(V, roughness, R.z, NdotV);
-        if (table == 1) v = v * luminance(fresnel_schlick(f0, shadowed_f90(f0), fabsf(dot(H, V))));
-        sum += v;
-      }
-    }
-    sum /= 0x10000u;
-    if (table == 1) sum /= conductor[id] * (1.0f / 0xFFFF);
-  }
-  else {
-    const float ior_base = 1.0f + z * (1.0f / 31) * 2.0f;
-    const float ior = (table == 2) ? 1.0f / ior_base : ior_base;
-    for (uint32_t i = 0; i < 0x10000u; i++) {
-      smp.sample_id = i;
-      bool tot;
-      V3 H = sample_vndf_bounded(V, roughness, smp.next2(kRndBsdfReflection));
-      const V3 R = reflect(V, H);
-      V3 T = refract(V, H, ior, tot);
-      float fres = tot ? 1.0f : fresnel_dielectric(H, V, T, ior);
-      if (R.z > 0.0f) sum += eval_microfacet_over_vndf(V, roughness, R.z, NdotV) * fres;
-      H = sample_vndf_caps(V, roughness, smp.next2(kRndBsdfRefraction));
-      T = refract(V, H, ior, tot);
-      fres = tot ? ((table == 2) ? 1.0f : 0.0f) : fresnel_dielectric(H, V, T, ior);
-      const float NdotR = -T.z;
-      if (NdotR > 0.0f) sum += ggx_g2_over_g1(pow4(roughness), NdotR, NdotV) * (1.0f - fres);
-    }
-    sum /= 0x10000u;
-  }
-  dst[id] = quantise_energy(sum);
-}
-
-#endif
 
 LUM_NS_END

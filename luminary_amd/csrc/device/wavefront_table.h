@@ -1,7 +1,7 @@
 // The wavefront kernels as a table of launchers, one table per arithmetic flavour (flavour.h). The host side (csrc/host/core.hip) picks a
 // table per context (lumc_set_flavour) and launches through it; everything in the signatures is a plain layout from dev_scene.h.
 // Kernels that produce data both flavours must agree on (BSDF / sky tables, panorama bake), bookkeeping (accumulation, adaptive rates) and
-// the display chain exist once, in the exact flavour.
+// the display chain exist once, in the exact flavour's namespace: kernels_shared.h, compiled in and launched directly by core.hip.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -82,7 +82,7 @@ struct WavefrontKernels {
                             uint32_t* out_num_hits);
 };
 
-const WavefrontKernels* wavefront_kernels_exact();  // csrc/host/core.hip
+const WavefrontKernels* wavefront_kernels_exact();  // csrc/device/wavefront_exact.hip
 const WavefrontKernels* wavefront_kernels_fast();   // csrc/device/wavefront_fast.hip
 
 }  // namespace lum

@@ -1,7 +1,5 @@
-// Defines this translation unit's WavefrontKernels table (include once, after kernels.h and dev_adaptive.h).
+// Defines this translation unit's WavefrontKernels table: the whole of a flavour's main unit (wavefront_exact.hip, wavefront_fast.hip).
 #pragma once
-
-#include <vector>
 
 #include "dev_adaptive.h"
 #include "dev_denoise.h"
@@ -17,23 +15,7 @@ static int set_ray_kernel_lds(size_t bytes) {
   if (e == hipSuccess) e = hipFuncSetAttribute((const void*) k_trace_particles, hipFuncAttributeMaxDynamicSharedMemorySize, (int) bytes);
   return (int) e;
 }
-static int init_sampler_seeds() {
-  static std::vector<uint32_t> seeds;  // squares32(0xfcbd6e15, dimension), random.cuh:172-194 - the device function's integer arithmetic on the host
-  if (seeds.empty()) {
-    seeds.resize(kSeedTableSize);
-    auto swap_h = [](uint32_t a) { return (a >> 16) | (a << 16); };
-    const uint32_t key = 0xfcbd6e15u;
-    for (uint32_t d = 0; d < kSeedTableSize; d++) {
-      uint32_t x = d * key, y = d * key, z = y + key;
-      x = x * x + y; x = swap_h(x);
-      x = x * x + z; x = swap_h(x);
-      x = x * x + y; x = swap_h(x);
-      x = x * x + z; z = x; x = swap_h(x);
-      seeds[d] = z ^ (x * x + y);
-    }
-  }
-  return (int) hipMemcpyToSymbol(HIP_SYMBOL(g_sampler_seeds), seeds.data(), sizeof(uint32_t) * kSeedTableSize);
-}
+static int init_sampler_seeds() { return upload_sampler_seeds(); }
 static void sobol_table(hipStream_t s, uint2* table, uint32_t first_sample, uint32_t count, uint32_t stride, uint32_t dims) {
   hipLaunchKernelGGL(k_sobol_table, dim3((dims * stride + 255u) / 256u), dim3(256), 0, s, table, first_sample, count, stride, dims);
 }
@@ -164,15 +146,29 @@ static void light_query_probe(hipStream_t s, const DeviceScene& sc, uint32_t n, 
   hipLaunchKernelGGL(k_light_query_probe, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, sc, n, origins, dirs, self, randoms, out_ids, out_num_hits);
 }
 
-static const WavefrontKernels kTable = {LUM_FLAVOUR_NAME, (uint32_t) kTraceBlock, set_ray_kernel_lds, init_sampler_seeds, sobol_table, generate,    generate_adaptive, trace,  sky_inscattering, shade,
-                                        shade_debug,      sky,              light_query,        shadow_rays, resolve, resolve_reuse, resolve_listed, resolve_ended, LUM_FAST != 0, volume_inscatter, volume_resolve, volume_events, volume_bounce, trace_particles, particle_shade, trace_ocean, ocean_shade, clouds_list, clouds_march, clouds, trace_rays,
-                                        camera_rays,      guide,            guide_normalise,    denoise_prepare, denoise_atrous, denoise_finish, light_query_probe};
+// Filled by member name: neighbouring members share a function-pointer type (resolve / resolve_listed, particle_shade / ocean_shade, sky_inscattering / clouds),
+// so a positional list with two of them swapped would compile. tests/test_build_units.py checks that no member stays null.
+static constexpr WavefrontKernels make_table() {
+  WavefrontKernels t{};
+  t.flavour = LUM_FLAVOUR_NAME; t.trace_block = (uint32_t) kTraceBlock; t.set_ray_kernel_lds = set_ray_kernel_lds; t.init_sampler_seeds = init_sampler_seeds;
+  t.sobol_table = sobol_table; t.generate = generate; t.generate_adaptive = generate_adaptive; t.trace = trace; t.sky_inscattering = sky_inscattering;
+  t.shade = shade; t.shade_debug = shade_debug; t.sky = sky; t.light_query = light_query;
+  t.shadow_rays = shadow_rays; t.resolve = resolve; t.resolve_reuse = resolve_reuse; t.resolve_listed = resolve_listed; t.resolve_ended = resolve_ended; t.fused_resolve = LUM_FAST != 0;
+  t.volume_inscatter = volume_inscatter; t.volume_resolve = volume_resolve; t.volume_events = volume_events; t.volume_bounce = volume_bounce;
+  t.trace_particles = trace_particles; t.particle_shade = particle_shade; t.trace_ocean = trace_ocean; t.ocean_shade = ocean_shade;
+  t.clouds_list = clouds_list; t.clouds_march = clouds_march; t.clouds = clouds; t.trace_rays = trace_rays;
+  t.camera_rays = camera_rays; t.guide = guide;
+  t.guide_normalise = guide_normalise; t.denoise_prepare = denoise_prepare; t.denoise_atrous = denoise_atrous; t.denoise_finish = denoise_finish; t.light_query_probe = light_query_probe;
+  return t;
+}
+static constexpr WavefrontKernels kTable = make_table();
 
 }  // namespace table
 LUM_NS_END
 
-#if defined(LUM_PHASE_STATS) && LUM_FAST
-// the fast flavour's own counter block (dev_math.h); the exact flavour's is read by lumc_debug_phase_stats (core.hip)
+#ifdef LUM_PHASE_STATS
+// each flavour's own counter blocks (dev_math.h), read by tools/phase_stats.py
+#if LUM_FAST
 extern "C" int lumc_debug_phase_stats_fast(uint64_t out[16], int reset) {
   if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_phase), sizeof(uint64_t) * 16) != hipSuccess) return 1;
   if (reset) { const uint64_t zero[16] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(g_phase), zero, sizeof(zero)) != hipSuccess) return 1; }
@@ -193,6 +189,13 @@ extern "C" int lumc_debug_shade_times_fast(uint64_t out[16], int reset) {
   if (reset) { const uint64_t zero[16] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(g_shade_time), zero, sizeof(zero)) != hipSuccess) return 1; }
   return 0;
 }
+#else
+extern "C" int lumc_debug_phase_stats(uint64_t out[16], int reset) {
+  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_phase), sizeof(uint64_t) * 16) != hipSuccess) return 1;
+  if (reset) { const uint64_t zero[16] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(g_phase), zero, sizeof(zero)) != hipSuccess) return 1; }
+  return 0;
+}
+#endif
 #endif
 
 namespace lum {

@@ -1,5 +1,5 @@
-// The host layer's context and the helpers its translation units share. Private to csrc/host: core.hip (the exact flavour's device code, scene upload,
-// render schedule), ray_sort.hip, multi_gpu.hip. The context owns its device memory through DeviceBuffer members (device_buffer.h): deleting it frees them.
+// The host layer's context and the helpers its translation units share. Private to csrc/host: core.hip (scene upload, render schedule, the
+// flavour-neutral kernels of kernels_shared.h), ray_sort.hip, multi_gpu.hip. The context owns its device memory through DeviceBuffer members (device_buffer.h): deleting it frees them.
 // Its other pointers - DeviceScene, the queues, d_results, d_ended, d_fused - are views into those buffers. kernels.h is not included, so a unit that includes
 // this header gets none of the flavoured kernels (their device symbols - the sampler's seed table, the phase counters - exist per translation unit).
 #pragma once
@@ -165,7 +165,7 @@ struct LumContext {
 
 #pragma GCC visibility push(hidden)  // nothing below is part of the library's interface
 
-constexpr uint32_t kLaunchBlock = 256;  // kernels.h's kBlock (core.hip asserts it)
+constexpr uint32_t kLaunchBlock = 256;  // dev_wave.h's kBlock (core.hip asserts it)
 inline uint32_t grid_for(uint32_t n) {
   const uint32_t blocks = (n + kLaunchBlock - 1) / kLaunchBlock;
   return blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks);  // 256 CUs x 8 resident blocks, grid-stride beyond that

@@ -21,15 +21,12 @@
 #include <vector>
 
 #include "../../../include/lum_core.h"
-#include "../device/kernels.h"
-#include "../device/dev_output.h"
-#include "../device/dev_adaptive.h"
-#include "../device/wavefront_table_impl.h"  // this translation unit holds the exact flavour; the fast one is csrc/device/wavefront_fast.hip
+#include "../device/kernels_shared.h"  // the flavour-neutral kernels; the wavefront kernels are csrc/device/wavefront_exact.hip and wavefront_fast.hip
 #include <hipcub/hipcub.hpp>
 #include "context.h"
 #include "tiles.h"
 
-static_assert(kLaunchBlock == (uint32_t) kBlock, "grid_for (context.h) counts kernels.h's workgroups");
+static_assert(kLaunchBlock == (uint32_t) kBlock, "grid_for (context.h) counts the kernels' workgroups");
 
 namespace {
 
@@ -288,6 +285,7 @@ int lumc_context_create(int device_ordinal, LumContext** out) {
   HIP_TRY(ctx, hipSetDevice(device_ordinal));
   HIP_TRY(ctx, (hipError_t) wavefront_kernels_exact()->init_sampler_seeds());  // per device: module globals live on each GPU
   HIP_TRY(ctx, (hipError_t) wavefront_kernels_fast()->init_sampler_seeds());
+  HIP_TRY(ctx, (hipError_t) exact::upload_sampler_seeds());  // this unit's own table: k_sky_hdri, k_generate_lut and k_pixel_ray draw random numbers
   HIP_TRY(ctx, ctx->d_ctrl.resize(kCtlStride * kCtrlRows));
   HIP_TRY(ctx, hipMemset(ctx->d_ctrl.get(), 0, sizeof(uint32_t) * kCtlStride * kCtrlRows));
   HIP_TRY(ctx, ctx->d_counters.resize(LUMC_CNT_COUNT));
@@ -2068,14 +2066,6 @@ int lumc_camera_rays(LumContext* ctx, const uint32_t* pixels, uint32_t n, uint32
   HIP_TRY(ctx, hipMemcpy(out_weight, d + 6 * total, sizeof(float) * total, hipMemcpyDeviceToHost));
   return 0;
 }
-
-#ifdef LUM_PHASE_STATS
-extern "C" int lumc_debug_phase_stats(uint64_t out[16], int reset) {
-  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_phase), sizeof(uint64_t) * 16) != hipSuccess) return 1;
-  if (reset) { const uint64_t zero[16] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(g_phase), zero, sizeof(zero)) != hipSuccess) return 1; }
-  return 0;
-}
-#endif
 
 int lumc_device_name(int ordinal, char* out, size_t size) {
   if (!out || size == 0) return 1;

@@ -1,0 +1,80 @@
+"""Which translation unit compiles which kernel (luminary_amd/build.py HIP_SOURCES), read off the objects the build leaves in luminary_amd/lib/obj, and the
+launcher table every flavour fills (csrc/device/wavefront_table_impl.h).
+
+A kernel compiled into two units would exist twice on the device with two seed tables and two sets of attributes; a wavefront kernel that found its way
+back into a host unit would make every host edit recompile it. Needs no GPU: nm over the objects, and the sources' text."""
+import functools
+import os
+import re
+import subprocess
+
+from luminary_amd import build as lum_build
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+DEVICE = os.path.join(ROOT, "luminary_amd", "csrc", "device")
+STUB = re.compile(r"^(?:void )?lum::(?:exact|fast)::__device_stub__(k_\w+)")  # "void": the demangler names a template instance's return type
+
+
+@functools.lru_cache(maxsize=None)
+def _stubs():
+    """{demangled kernel with its flavour and arguments: [objects that define its host stub]}, {object: source}"""
+    lum_build.build()
+    source_of = {os.path.basename(s) + ".o": s for s, _ in lum_build.HIP_SOURCES}
+    defined = {}
+    for obj in sorted(source_of):
+        out = subprocess.run(["nm", "-C", "--defined-only", os.path.join(lum_build.OBJ_DIR, obj)], stdout=subprocess.PIPE, text=True, check=True).stdout
+        for line in out.splitlines():
+            parts = line.split(" ", 2)
+            if len(parts) == 3 and parts[1] in "TW" and STUB.match(parts[2]):
+                defined.setdefault(parts[2].replace("__device_stub__", ""), []).append(obj)
+    return defined, source_of
+
+
+def test_every_kernel_is_compiled_in_exactly_one_unit():
+    defined, source_of = _stubs()
+    names = {STUB.match(k.replace("::k_", "::__device_stub__k_", 1)).group(1) for k in defined}
+    # a sample of what must have been seen at all: wavefront kernels, a template among them, and shared kernels
+    assert {"k_trace", "k_shade", "k_shadow_rays", "k_generate_adaptive", "k_pixel_ray", "k_generate_lut", "k_sky_hdri", "k_accumulate", "k_to_argb8", "k_cloud_noise_shape"} <= names, sorted(names)
+    twice = {k: objs for k, objs in defined.items() if len(objs) != 1}
+    assert not twice, twice
+    # the wavefront kernels belong to the flavours' own units: no object built from csrc/host/ holds one
+    in_host = sorted(k for k, objs in defined.items() if source_of[objs[0]].startswith("host/") and re.search(r"::(k_shade\w*|k_trace)[<(]", k))
+    assert not in_host, in_host
+    shade = [k for k in defined if re.search(r"::k_shade<", k)]
+    assert {source_of[defined[k][0]] for k in shade} == {"device/wavefront_exact.hip", "device/wavefront_fast.hip"}
+
+
+def test_the_flavour_neutral_kernels_exist_in_the_exact_namespace_of_core_alone():
+    defined, source_of = _stubs()
+    text = open(os.path.join(DEVICE, "kernels_shared.h")).read()
+    shared = set(re.findall(r"^__global__[^\n]*?\bvoid (k_\w+)\(", text, re.M))
+    assert len(shared) >= 22, sorted(shared)
+    for name in sorted(shared):
+        where = {k: objs for k, objs in defined.items() if re.search(r"::%s\(" % name, k)}
+        assert list(where.values()) == [["core.hip.o"]] and next(iter(where)).startswith("lum::exact::"), (name, where)
+
+
+def test_kernels_h_has_no_switch_that_places_a_kernel():
+    """kernels.h and the dev_*.h it includes hold no `#if !LUM_FAST` around a kernel: where something is compiled is decided by which unit includes it."""
+    for f in sorted(os.listdir(DEVICE)):
+        if f.endswith(".h"):
+            assert not re.search(r"^#if\s+!\s*LUM_FAST", open(os.path.join(DEVICE, f)).read(), re.M), f
+    core = open(os.path.join(ROOT, "luminary_amd", "csrc", "host", "core.hip")).read()
+    assert not re.search(r'#include\s+"[^"]*\b(kernels|wavefront_table_impl)\.h"', core)
+
+
+def test_the_launcher_table_assigns_every_member_by_name():
+    """A member make_table() leaves out stays null and would be called through at run time; a member assigned another launcher's name is a swap."""
+    decl = open(os.path.join(DEVICE, "wavefront_table.h")).read()
+    struct = decl[decl.index("struct WavefrontKernels {"):decl.index("};", decl.index("struct WavefrontKernels {"))]
+    code = "\n".join(line.split("//")[0] for line in struct.splitlines())
+    pointers = re.findall(r"\(\*(\w+)\)\(", code)
+    plain = re.findall(r"^\s*(?:const char\*|uint32_t|bool)\s+(\w+);", code, re.M)
+    assert len(pointers) == 35 and plain == ["flavour", "trace_block", "fused_resolve"], (len(pointers), plain)
+    impl = open(os.path.join(DEVICE, "wavefront_table_impl.h")).read()
+    body = impl[impl.index("make_table() {"):impl.index("return t;")]
+    assigned = dict(re.findall(r"\bt\.(\w+) = ([^;]+);", body))
+    assert sorted(assigned) == sorted(pointers + plain)
+    assert all(assigned[p] == p for p in pointers), {p: assigned[p] for p in pointers if assigned[p] != p}
+    for p in pointers:  # each name is a launcher defined in the same header
+        assert re.search(r"^static (?:int|void) %s\(" % p, impl, re.M), p

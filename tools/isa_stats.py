@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Static instruction mix per kernel from a gfx950 assembly dump.
 
-  hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-fast-math -S --cuda-device-only -o /tmp/core.s luminary_amd/csrc/host/core.hip
-  python tools/isa_stats.py /tmp/core.s
+  hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-fast-math -S --cuda-device-only -DLUM_SHADOW_KERNEL_EXTERN=1 -o /tmp/exact.s \
+      luminary_amd/csrc/device/wavefront_exact.hip
+  python tools/isa_stats.py /tmp/exact.s
 """
 import re
 import sys

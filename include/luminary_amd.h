@@ -377,6 +377,24 @@ LUMINARY_API LuminaryResult luminary_ext_add_material(LuminaryHost* host, const 
 /* The host-level mesh back (borrowed pointers into the host's store, valid until the mesh list changes): what an independent encoder starts from. */
 LUMINARY_API LuminaryResult luminary_ext_get_mesh(LuminaryHost* host, uint32_t mesh_id, const float** positions, const float** normals, const float** uvs,
                                                   const uint16_t** material_ids, uint32_t* triangle_count);
+/* Deformable meshes. New positions (9 floats per triangle) and normals (9 per triangle, or NULL = face normals by the loader's rule for a file without normals)
+ * for a mesh the host already holds. triangle_count must equal the mesh's; order, uvs and material ids stay. The host mesh is overwritten in place (the
+ * luminary_ext_get_mesh pointers stay valid). Restarts the integration. LUMINARY_ERROR_INVALID_API_ARGUMENT, and nothing changes: a mesh id the host does not have,
+ * another triangle count, NULL positions, a position that is not finite. On the devices only the vertices are uploaded and the mesh's tree is refitted there. */
+LUMINARY_API LuminaryResult luminary_ext_set_mesh_positions(LuminaryHost* host, uint32_t mesh_id, const float* positions, const float* normals, uint32_t triangle_count);
+/* mode 0 (default): refit the mesh's tree; 1: build it again. max_cost_growth > 0: in mode 0, build again when the tree's cost (the sum over all nodes and occupied
+ * child slots of the child box's half surface area) has grown beyond this factor of its cost when it was last BUILT; 0 = never. No default threshold is built in:
+ * the stats report the growth. Images do not depend on any of it. */
+LUMINARY_API LuminaryResult luminary_ext_set_mesh_refit(LuminaryHost* host, uint32_t mode, float max_cost_growth);
+typedef struct LuminaryMeshRefitStats {
+  uint64_t refits, rebuilds;           /* meshes refitted / built again by the main device's context since it was created (uploads do not reset them) */
+  uint32_t last_refits, last_rebuilds; /* ... by the last update */
+  double max_cost_growth;              /* largest cost growth among the meshes the last update refitted (0: none) */
+  double seconds;                      /* the last update's mesh part on the main device */
+  double seconds_upload, seconds_refit, seconds_rebuild, seconds_assemble;
+  double seconds_hash, seconds_download, seconds_lights; /* as LumMeshRefitStats (include/lum_core.h) */
+} LuminaryMeshRefitStats;
+LUMINARY_API LuminaryResult luminary_ext_get_mesh_refit_stats(LuminaryHost* host, LuminaryMeshRefitStats* out);
 /* Converts the current scene to the device format (device_structs.c conversions + light tree build). The view and everything it points
  * to stay valid until the next call or host destruction. Needs no GPU. */
 /* Whether replacing `old` by `input` restarts the integration (camera.c:80-147, settings.c:45-72) or only changes the outputs.

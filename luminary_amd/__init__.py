@@ -162,6 +162,13 @@ class Image(C.Structure):
 OUTPUT_HANDLE_INVALID = 0xFFFFFFFF
 
 
+class MeshRefitStats(C.Structure):
+    """LuminaryMeshRefitStats"""
+    _fields_ = [("refits", C.c_uint64), ("rebuilds", C.c_uint64), ("last_refits", C.c_uint32), ("last_rebuilds", C.c_uint32), ("max_cost_growth", C.c_double),
+                ("seconds", C.c_double), ("seconds_upload", C.c_double), ("seconds_refit", C.c_double), ("seconds_rebuild", C.c_double), ("seconds_assemble", C.c_double),
+                ("seconds_hash", C.c_double), ("seconds_download", C.c_double), ("seconds_lights", C.c_double)]
+
+
 class Instance(C.Structure):
     _fields_ = [("id", C.c_uint32), ("mesh_id", C.c_uint32), ("position", Vec3), ("rotation", Vec3), ("scale", Vec3)]
 
@@ -485,6 +492,27 @@ class Host:
         _call("luminary_ext_add_mesh", self._h, positions.ctypes.data_as(C.c_void_p), npt, upt, material_ids.ctypes.data_as(C.c_void_p),
               C.c_uint32(n), C.byref(mid))
         return mid.value
+
+    def set_mesh_positions(self, mesh_id, positions, normals=None):
+        """luminary_ext_set_mesh_positions: new positions [n, 9] (and normals [n, 9], or None = face normals) for a mesh the host holds; the devices refit its tree."""
+        import numpy as np
+        positions = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1)
+        npt = C.c_void_p(0)
+        if normals is not None:
+            normals = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1)
+            assert normals.size == positions.size
+            npt = normals.ctypes.data_as(C.c_void_p)
+        _call("luminary_ext_set_mesh_positions", self._h, C.c_uint32(mesh_id), positions.ctypes.data_as(C.c_void_p), npt, C.c_uint32(positions.size // 9))
+
+    def set_mesh_refit(self, mode=0, max_cost_growth=0.0):
+        """luminary_ext_set_mesh_refit: 0 = refit a moved mesh's tree, 1 = build it again; max_cost_growth > 0: build again when the cost grew beyond this factor."""
+        _call("luminary_ext_set_mesh_refit", self._h, C.c_uint32(mode), C.c_float(max_cost_growth))
+
+    def mesh_refit_stats(self):
+        """luminary_ext_get_mesh_refit_stats of the main device: a dict of refits, rebuilds, last_refits, last_rebuilds, max_cost_growth and the seconds."""
+        s = MeshRefitStats()
+        _call("luminary_ext_get_mesh_refit_stats", self._h, C.byref(s))
+        return {name: getattr(s, name) for name, _ in s._fields_}
 
     def get_mesh(self, mesh_id):
         """luminary_ext_get_mesh: the host-level mesh (copies): positions [n, 9], normals [n, 9], uvs [n, 6], material ids [n]."""

@@ -6,6 +6,8 @@ import numpy as np
 from . import DeviceSceneView, _lib
 
 DIRTY_CONSTANTS, DIRTY_MATERIALS, DIRTY_INSTANCES, DIRTY_LIGHTS, DIRTY_MESHES, DIRTY_TEXTURES, DIRTY_PARTICLES, DIRTY_ALL = 1, 2, 4, 8, 16, 32, 64, 127
+DIRTY_MESH_POSITIONS = 128  # moved vertices: refit (not part of DIRTY_ALL, which builds)
+BVH_BUILDERS = {"sah": 0, "lbvh": 1, "ploc": 2, "sah_gpu": 3}
 CNT_TRACE, CNT_SHADOW, CNT_LIGHT_BVH, CNT_VERTICES, CNT_NODES, CNT_TRIS, CNT_NODES_SHADOW, CNT_TRIS_SHADOW, CNT_NODES_LIGHT, CNT_TRIS_LIGHT, CNT_NODES_LDS, CNT_NODES_LDS_SHADOW, CNT_AMBIENT_DEFERRED, CNT_AMBIENT_FALLBACK = range(14)
 CNT_COUNT = 16  # LUMC_CNT_COUNT
 KERNELS = ("generate", "trace", "shade", "shadow", "accumulate", "light_query", "resolve", "output", "sky", "sort", "volume")
@@ -88,6 +90,34 @@ def default_denoise_params(uniform_samples=0, **fields):
     for k, v in fields.items():
         setattr(p, k, v)
     return p
+
+
+class MeshRefitStats(C.Structure):
+    """LumMeshRefitStats"""
+    _fields_ = [("refits", C.c_uint64), ("rebuilds", C.c_uint64), ("last_refits", C.c_uint32), ("last_rebuilds", C.c_uint32), ("max_cost_growth", C.c_double),
+                ("seconds", C.c_double), ("seconds_upload", C.c_double), ("seconds_refit", C.c_double), ("seconds_rebuild", C.c_double), ("seconds_assemble", C.c_double),
+                ("seconds_hash", C.c_double), ("seconds_download", C.c_double), ("seconds_lights", C.c_double)]
+
+
+def bvh_refit_probe(built_boxes, refit_boxes, builder="sah", on_gpu=False):
+    """lumc_bvh_refit_probe: a tree over built_boxes [n, 6] by `builder`, refitted to refit_boxes [m, 6] on the host or on the device. Returns a dict: built / refit
+    (node arrays as [nodes, 32] uint32 words: 24 box floats, 4 child words, 4 of padding; refit None when the tree cannot be refitted), host_refit (the host's refit of
+    the same tree), prims, cost (built, refit, host refit), valid."""
+    lib = _lib()
+    fn = lib.lumc_bvh_refit_probe
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
+    a = np.ascontiguousarray(built_boxes, dtype=np.float32)
+    b = np.ascontiguousarray(refit_boxes, dtype=np.float32)
+    assert a.ndim == 2 and a.shape[1] == 6 and b.ndim == 2 and b.shape[1] == 6
+    n = a.shape[0]
+    sizes, cost, valid = (C.c_uint64 * 3)(), (C.c_double * 3)(), C.c_uint64()
+    built, refit, host_refit, prims = np.zeros((n, 32), np.uint32), np.zeros((n, 32), np.uint32), np.zeros((n, 32), np.uint32), np.zeros(n, np.uint32)
+    if fn(a.ctypes.data, b.ctypes.data, n, b.shape[0], BVH_BUILDERS[builder], int(bool(on_gpu)), sizes, built.ctypes.data, refit.ctypes.data, host_refit.ctypes.data, prims.ctypes.data, cost, C.byref(valid)) != 0:
+        raise CoreError("lumc_bvh_refit_probe failed (builder %s)" % builder)
+    return {"built": built[:sizes[0]].copy(), "refit": refit[:sizes[2]].copy() if sizes[2] else None, "host_refit": host_refit[:sizes[0]].copy() if b.shape[0] == sizes[1] else None,
+            "prims": prims[:sizes[1]].copy(), "cost": (cost[0], cost[1], cost[2]),
+            "valid": int(valid.value)}
 
 
 class Core:
@@ -464,6 +494,15 @@ class Core:
         fn = self._lib.lumc_lds_stack_bytes
         fn.restype = C.c_uint
         return int(fn())
+
+    def set_mesh_refit(self, mode=0, max_cost_growth=0.0):
+        """lumc_set_mesh_refit: how DIRTY_MESH_POSITIONS updates take a moved mesh over: 0 refit, 1 build again; max_cost_growth > 0: build again beyond it."""
+        self._call("lumc_set_mesh_refit", C.c_uint32(mode), C.c_float(max_cost_growth))
+
+    def mesh_refit_stats(self):
+        out = MeshRefitStats()
+        self._call("lumc_mesh_refit_stats", C.byref(out))
+        return out
 
     def bvh_build_seconds(self):
         fn = self._lib.lumc_bvh_build_seconds

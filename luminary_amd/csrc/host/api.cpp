@@ -41,6 +41,9 @@ struct LuminaryHost {
   // move re-encodes and re-uploads nothing but constants, a material edit the material array, an instance edit the top-level tree.
   uint32_t scene_dirty = LUMC_DIRTY_ALL;  // parts of `device_scene` that are out of date
   uint32_t core_dirty = LUMC_DIRTY_ALL;   // parts the main device's context has not taken over yet
+  std::vector<uint32_t> moved_meshes;     // meshes luminary_ext_set_mesh_positions moved since `device_scene` was last brought up to date
+  uint32_t refit_mode = 0;                // luminary_ext_set_mesh_refit: handed to every context before it takes a scene
+  float refit_max_cost_growth = 0.0f;
   bool device_scene_valid = false;
   bool core_scene_valid = false;
   uint32_t core_width = 0, core_height = 0;  // frame size the main context's pixel set was made for
@@ -167,6 +170,8 @@ LuminaryResult ensure_device_scene(LuminaryHost* h) {
     h->hdri_origin_pending = false;
   }
   static const std::vector<uint32_t> bluenoise = embedded_bluenoise();
+  h->device_scene.moved_meshes = std::move(h->moved_meshes);
+  h->moved_meshes.clear();
   const std::string err = lum::update_device_scene(h->scene, bluenoise, h->scene_dirty, &h->device_scene);
   if (!err.empty()) { h->log.push_back(err); std::fprintf(stderr, "[luminary_amd] %s\n", err.c_str()); h->scene_dirty = h->core_dirty = LUMC_DIRTY_ALL; return LUMINARY_ERROR_API_EXCEPTION; }
   // what was re-encoded is what the devices have to take over (the encoder may add a part: the texture pool when the sky mode moves the moon in or out)
@@ -201,6 +206,7 @@ LuminaryResult ensure_core(LuminaryHost* h) {
   const LuminaryResult r = ensure_device_scene(h);
   if (r) return r;
   if (!h->core_scene_valid) {
+    lumc_set_mesh_refit(h->core, h->refit_mode, h->refit_max_cost_growth);
     if (lumc_scene_update(h->core, &h->device_scene.view, h->core_dirty)) { std::fprintf(stderr, "[luminary_amd] %s\n", lumc_last_error(h->core)); h->core_dirty = LUMC_DIRTY_ALL; return LUMINARY_ERROR_CUDA; }
     h->core_dirty = 0;
     h->core_scene_valid = true;
@@ -242,6 +248,7 @@ LuminaryResult ensure_partition_cores(LuminaryHost* h, std::vector<LumContext*>*
       slot->scene_valid = false;
     }
     if (!slot->scene_valid) {
+      lumc_set_mesh_refit(slot->core, h->refit_mode, h->refit_max_cost_growth);
       if (lumc_scene_update(slot->core, &h->device_scene.view, slot->dirty)) { std::fprintf(stderr, "[luminary_amd] device %d: %s\n", slot->ordinal, lumc_last_error(slot->core)); slot->dirty = LUMC_DIRTY_ALL; return LUMINARY_ERROR_CUDA; }
       slot->dirty = 0;
       slot->scene_valid = true;
@@ -762,6 +769,50 @@ LuminaryResult luminary_ext_add_mesh(LuminaryHost* host, const float* positions,
   host->scene.meshes.push_back(std::move(m));
   if (mesh_id) *mesh_id = (uint32_t) host->scene.meshes.size() - 1;
   invalidate(host, LUMC_DIRTY_MESHES | LUMC_DIRTY_INSTANCES | LUMC_DIRTY_LIGHTS);
+  return LUMINARY_SUCCESS;
+}
+static void face_normals(const float* positions, uint32_t triangle_count, float* normals) {  // as the .obj path does for files without `vn` (wavefront.c:918-929; loaders.cpp)
+  for (uint32_t t = 0; t < triangle_count; t++) {
+    const float* p = positions + 9 * (size_t) t;
+    const float e1[3] = {p[3] - p[0], p[4] - p[1], p[5] - p[2]}, e2[3] = {p[6] - p[0], p[7] - p[1], p[8] - p[2]};
+    float n[3] = {e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0]};
+    const float rl = 1.0f / std::sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+    if (!std::isnan(rl) && !std::isinf(rl)) { n[0] *= rl; n[1] *= rl; n[2] *= rl; }
+    const float rl2 = 1.0f / std::sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);  // the loader normalises every vertex normal it stores, the face normal included
+    if (!std::isnan(rl2) && !std::isinf(rl2)) { n[0] *= rl2; n[1] *= rl2; n[2] *= rl2; }
+    for (int k = 0; k < 3; k++) std::memcpy(normals + 9 * (size_t) t + 3 * k, n, sizeof(n));
+  }
+}
+LuminaryResult luminary_ext_set_mesh_positions(LuminaryHost* host, uint32_t mesh_id, const float* positions, const float* normals, uint32_t triangle_count) {
+  CHECK_NULL(host);
+  ApiLock lock(host);
+  if (!positions || mesh_id >= host->scene.meshes.size() || host->scene.meshes[mesh_id].triangle_count() != triangle_count) return LUMINARY_ERROR_INVALID_API_ARGUMENT;
+  for (size_t i = 0; i < 9 * (size_t) triangle_count; i++) if (!std::isfinite(positions[i])) return LUMINARY_ERROR_INVALID_API_ARGUMENT;
+  lum::HostMesh& m = host->scene.meshes[mesh_id];
+  // in place (std::copy into the vectors as they are): the pointers luminary_ext_get_mesh handed out stay valid. The caller may pass those very pointers.
+  if (normals) std::memmove(m.normals.data(), normals, sizeof(float) * 9 * (size_t) triangle_count);
+  std::memmove(m.positions.data(), positions, sizeof(float) * 9 * (size_t) triangle_count);
+  if (!normals) face_normals(m.positions.data(), triangle_count, m.normals.data());
+  if (std::find(host->moved_meshes.begin(), host->moved_meshes.end(), mesh_id) == host->moved_meshes.end()) host->moved_meshes.push_back(mesh_id);
+  invalidate(host, LUMC_DIRTY_MESH_POSITIONS | LUMC_DIRTY_LIGHTS);  // the vertices and the mesh's tree; the light tree follows moved emitters
+  return LUMINARY_SUCCESS;
+}
+LuminaryResult luminary_ext_set_mesh_refit(LuminaryHost* host, uint32_t mode, float max_cost_growth) {
+  CHECK_NULL(host);
+  ApiLock lock(host);
+  if (mode > 1 || !(max_cost_growth >= 0.0f) || !std::isfinite(max_cost_growth)) return LUMINARY_ERROR_INVALID_API_ARGUMENT;
+  host->refit_mode = mode; host->refit_max_cost_growth = max_cost_growth;  // (decides how the next moved mesh is taken over: no restart)
+  return LUMINARY_SUCCESS;
+}
+LuminaryResult luminary_ext_get_mesh_refit_stats(LuminaryHost* host, LuminaryMeshRefitStats* out) {
+  CHECK_NULL(host); CHECK_NULL(out);
+  ApiLock lock(host);
+  std::memset(out, 0, sizeof(*out));
+  if (!host->core) return LUMINARY_SUCCESS;
+  LumMeshRefitStats s;
+  if (lumc_mesh_refit_stats(host->core, &s)) return LUMINARY_ERROR_API_EXCEPTION;
+  static_assert(sizeof(LuminaryMeshRefitStats) == sizeof(LumMeshRefitStats), "the public struct mirrors the core's");
+  std::memcpy(out, &s, sizeof(s));
   return LUMINARY_SUCCESS;
 }
 // The host-level mesh as the loaders left it (the reference's Mesh / TriangleGeomData, mesh.h:8-14): borrowed pointers, valid until the mesh list changes. What an

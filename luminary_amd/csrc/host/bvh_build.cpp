@@ -767,6 +767,107 @@ Bvh4 build_bvh4(const Aabb* boxes, uint32_t count, uint32_t max_leaf, uint32_t m
   return Bvh4();
 }
 
+// ---- refit (bvh_build.h) ----
+bool bvh4_levels(const Bvh4& tree, uint32_t count, std::vector<uint32_t>& level_nodes, std::vector<uint32_t>& level_first) {
+  level_nodes.clear(); level_first.clear();
+  const size_t n = tree.nodes.size();
+  if (n == 0 || tree.prims.size() != count) return false;
+  std::vector<uint8_t> seen(n, 0);
+  level_nodes.reserve(n);
+  level_nodes.push_back(0u); seen[0] = 1;
+  level_first.push_back(0u);
+  size_t head = 0;
+  while (head < level_nodes.size()) {
+    const size_t end = level_nodes.size();
+    for (; head < end; head++) {
+      const Bvh4Node& node = tree.nodes[level_nodes[head]];
+      for (int k = 0; k < 4; k++) {
+        const uint32_t c = node.child[k];
+        if (c == kBvhEmpty) continue;
+        if (c & kBvhLeafBit) { if ((size_t) (c & 0x0FFFFFFFu) + ((c >> 28) & 7u) + 1u > count) return false; continue; }
+        if (c >= n || seen[c]) return false;
+        seen[c] = 1;
+        level_nodes.push_back(c);
+      }
+    }
+    level_first.push_back((uint32_t) end);
+  }
+  return level_nodes.size() == n;  // (a node nothing points at would keep stale boxes)
+}
+
+Bvh4 refit_bvh4(const Bvh4& tree, const Aabb* boxes, uint32_t count, Aabb* root_box) {
+  std::vector<uint32_t> level_nodes, level_first;
+  if (!bvh4_levels(tree, count, level_nodes, level_first)) return Bvh4();
+  for (uint32_t p : tree.prims) if (p >= count) return Bvh4();
+  Bvh4 out;
+  out.nodes = tree.nodes; out.prims = tree.prims; out.max_depth = tree.max_depth;
+  std::vector<Aabb> exact(tree.nodes.size());
+  for (size_t i = level_nodes.size(); i-- > 0;) {  // deepest level first: a child's exact box is there before its parent reads it
+    const uint32_t id = level_nodes[i];
+    Bvh4Node& node = out.nodes[id];
+    Aabb all = empty_box();
+    for (int k = 0; k < 4; k++) {
+      const uint32_t c = node.child[k];
+      if (c == kBvhEmpty) continue;
+      Aabb box;
+      if (c & kBvhLeafBit) {
+        box = empty_box();
+        const uint32_t first = c & 0x0FFFFFFFu, cnt = ((c >> 28) & 7u) + 1u;
+        for (uint32_t j = 0; j < cnt; j++) grow(box, boxes[tree.prims[first + j]]);
+      }
+      else box = exact[c];
+      set_child_box(node, k, box);
+      grow(all, box);
+    }
+    exact[id] = all;
+  }
+  if (root_box) *root_box = exact[0];
+  return out;
+}
+
+double bvh4_cost(const Bvh4& tree) {
+  double cost = 0.0;
+  for (const Bvh4Node& n : tree.nodes)
+    for (int k = 0; k < 4; k++) {
+      if (n.child[k] == kBvhEmpty) continue;
+      const double dx = (double) n.hi_x[k] - (double) n.lo_x[k], dy = (double) n.hi_y[k] - (double) n.lo_y[k], dz = (double) n.hi_z[k] - (double) n.lo_z[k];
+      cost += dx * dy + dy * dz + dz * dx;
+    }
+  return cost;
+}
+
+bool bvh4_valid(const Bvh4& tree, const Aabb* boxes, uint32_t count) {
+  std::vector<uint32_t> level_nodes, level_first;
+  if (!bvh4_levels(tree, count, level_nodes, level_first)) return false;
+  std::vector<uint32_t> seen(count, 0);
+  std::vector<Aabb> below(tree.nodes.size(), empty_box());
+  for (size_t i = level_nodes.size(); i-- > 0;) {
+    const Bvh4Node& n = tree.nodes[level_nodes[i]];
+    Aabb all = empty_box();
+    for (int k = 0; k < 4; k++) {
+      const uint32_t c = n.child[k];
+      if (c == kBvhEmpty) continue;
+      Aabb content = empty_box();
+      if (c & kBvhLeafBit) {
+        const uint32_t first = c & 0x0FFFFFFFu, cnt = ((c >> 28) & 7u) + 1u;
+        for (uint32_t j = 0; j < cnt; j++) {
+          const uint32_t p = tree.prims[first + j];
+          if (p >= count) return false;
+          seen[p]++;
+          grow(content, boxes[p]);
+        }
+      }
+      else content = below[c];
+      const Aabb cb{{n.lo_x[k], n.lo_y[k], n.lo_z[k]}, {n.hi_x[k], n.hi_y[k], n.hi_z[k]}};
+      for (int a = 0; a < 3; a++) if (!(cb.lo[a] <= content.lo[a]) || !(cb.hi[a] >= content.hi[a])) return false;
+      grow(all, cb);
+    }
+    below[level_nodes[i]] = all;
+  }
+  for (uint32_t i = 0; i < count; i++) if (seen[i] != 1u) return false;
+  return true;
+}
+
 // ---- the scene's tree: what the scene upload (core.hip) computes on the host between the per-mesh builds and the copies to the device ----
 Aabb tri_box(const float* a, const float* b, const float* c) {
   Aabb box;

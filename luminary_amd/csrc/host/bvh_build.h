@@ -52,6 +52,20 @@ Bvh4 build_bvh4_ploc(const Aabb* boxes, uint32_t count, uint32_t max_leaf = kBvh
 // build_bvh4, in tens of milliseconds. Empty result when the tree is deeper than `max_depth` 4-wide levels or a HIP call fails (the caller falls back).
 Bvh4 build_bvh4_sah_gpu(const Aabb* boxes, uint32_t count, uint32_t max_leaf = kBvhLeafMaxTri, uint32_t max_depth = 20);
 
+// ---- refit: new boxes under an unchanged topology (moved vertices, luminary_ext_set_mesh_positions) ----
+// The tree with the same child words, prims and max_depth; every occupied child box = the builders' pad of the exact union (min / max) of the primitive boxes
+// below it, empty slots keep their +-FLT_MAX boxes. root_box: the exact union of everything. A tree with prims.size() != count (spatial splits: clipped
+// reference boxes are not a function of the primitives' boxes) cannot be refitted: the result is empty and the caller builds. Host twin of bvh_refit.hip.
+Bvh4 refit_bvh4(const Bvh4& tree, const Aabb* boxes, uint32_t count, Aabb* root_box = nullptr);
+// Sum over all nodes, in node order, and their occupied child slots of the child box's half surface area, in double from the stored (padded) floats: what the
+// expected number of node visits of a random ray is proportional to. Defined for any tree; a refit is judged by its growth over the tree as built.
+double bvh4_cost(const Bvh4& tree);
+// Every primitive of [0, count) sits in exactly one leaf, every child index and leaf range is in bounds, every child box holds what is below it.
+bool bvh4_valid(const Bvh4& tree, const Aabb* boxes, uint32_t count);
+// The nodes of `tree` by 4-wide level, root first (one breadth-first walk; the GPU builders number nodes through atomics, so levels are not index ranges):
+// level l = level_nodes[level_first[l], level_first[l + 1]). False when a child index or a leaf range is out of bounds or a node is reached twice.
+bool bvh4_levels(const Bvh4& tree, uint32_t count, std::vector<uint32_t>& level_nodes, std::vector<uint32_t>& level_first);
+
 // ---- the scene's tree (scene upload, core.hip; lumc_scene_tree_probe) ----
 // [0, n) in contiguous chunks over the host's cores (per-triangle loops of the scene upload: 10 M triangles are 100 ms each on one core)
 template <class F>

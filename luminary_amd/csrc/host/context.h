@@ -15,6 +15,7 @@
 #include "../device/dev_scene.h"
 #include "../device/wavefront_table.h"
 #include "bvh_build.h"
+#include "bvh_refit.h"
 #include "device_buffer.h"
 
 using namespace lum;
@@ -25,6 +26,14 @@ typedef struct ncclComm* ncclComm_t;  // as rccl.h declares it; only multi_gpu.h
 // with several devices hands every context the same meshes, the first one builds a mesh's tree, the others - and a later upload of the same mesh - take it
 // from find_mesh_tree (below), and it is released with the last context that holds it.
 struct MeshTree { Bvh4 bvh; bool built_on_gpu = false; };
+
+// What a context keeps per mesh for LUMC_DIRTY_MESH_POSITIONS updates.
+struct MeshRefit {
+  RefitPlan plan;                  // the held tree's topology on the device, from the mesh's first refit until it is built again
+  std::shared_ptr<MeshTree> own;   // the refitted tree (LumContext::mesh_bvh holds the same object): private, never in the process's tree cache
+  uint64_t fit_hash[2] = {0, 0};   // of the vertices the held tree was built from or last fitted to (mesh_tree_key)
+  double built_cost = 0.0;         // bvh4_cost of the tree as last built (0: not computed yet)
+};
 
 struct LumContext {
   int device = 0;
@@ -38,6 +47,11 @@ struct LumContext {
   // what a partial update needs again: the per-mesh trees (node indices relative to the mesh, leaf ranges relative to its first triangle) and boxes
   std::vector<std::shared_ptr<const MeshTree>> mesh_bvh;
   std::vector<Aabb> mesh_box;
+  std::vector<MeshRefit> mesh_refit;         // by mesh, as long as mesh_bvh
+  std::vector<uint32_t> mesh_tri_offset;     // the offsets the trees were built for: a LUMC_DIRTY_MESH_POSITIONS update must bring the same
+  uint32_t refit_mode = 0;                   // lumc_set_mesh_refit
+  float refit_max_cost_growth = 0.0f;
+  LumMeshRefitStats refit_stats{};
   std::vector<uint32_t> sky_lut_key;  // the sky parameters the two sky tables were generated from
   DeviceBuffer<float> d_bridge_lut;   // the bridge sampler's vertex-count table (context-owned: scene.bridge_lut points here while bridges are possible)
   std::vector<float> bridge_lut_host; // its content, to notice a caller that hands over another table

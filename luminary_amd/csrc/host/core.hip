@@ -100,7 +100,7 @@ void free_scene(LumContext* ctx) {
   for (auto& t : ctx->d_sky_lut) t.reset();
   ctx->sky_lut_key.clear();
   ctx->d_bridge_lut.reset(); ctx->bridge_lut_host.clear();
-  ctx->mesh_bvh.clear(); ctx->mesh_box.clear();
+  ctx->mesh_bvh.clear(); ctx->mesh_box.clear(); ctx->mesh_refit.clear(); ctx->mesh_tri_offset.clear();
   ctx->has_scene = false;
 }
 
@@ -469,12 +469,30 @@ static int update_textures(LumContext* ctx, const LumDeviceSceneView* v) {
   return 0;
 }
 
+// A mesh's tree from the process's cache, else built by the context's builder and entered there; null (ctx->error set) for a mesh no builder can take.
+static std::shared_ptr<const MeshTree> cached_or_built_mesh_tree(LumContext* ctx, const MeshTreeKey& key, const Aabb* tri_boxes, uint32_t nt) {
+  std::shared_ptr<const MeshTree> tree = find_mesh_tree(key);
+  if (tree) return tree;
+  auto built = std::make_shared<MeshTree>();
+  if (ctx->bvh_builder == 1) built->bvh = build_bvh4_lbvh(tri_boxes, nt, kBvhLeafMaxTri, 26);
+  else if (ctx->bvh_builder == 2) built->bvh = build_bvh4_ploc(tri_boxes, nt, kBvhLeafMaxTri, 26);
+  else if (ctx->bvh_builder == 3) built->bvh = build_bvh4_sah_gpu(tri_boxes, nt, kBvhLeafMaxTri, 26);
+  built->built_on_gpu = !built->bvh.nodes.empty();
+  if (!built->built_on_gpu) built->bvh = build_bvh4(tri_boxes, nt, kBvhLeafMaxTri, 26);  // the host builder: asked for, or the fallback for a mesh the GPU builders cannot take
+  if (built->bvh.nodes.empty()) { ctx->error = "mesh BVH exceeds 26 levels"; return nullptr; }
+  tree = built;
+  keep_mesh_tree(key, tree);
+  return tree;
+}
+
 // Every mesh's box, tree (from the process's cache, else built) and traversal triangles: the only part of an upload that takes long; an instance edit skips it.
 static int build_mesh_trees(LumContext* ctx, const LumDeviceSceneView* v, std::vector<BvhTri>& blas_tris) {
   ctx->bvh_build_seconds = 0.0;
   ctx->bvh_meshes_by_builder[0] = ctx->bvh_meshes_by_builder[1] = 0;
   ctx->mesh_bvh.assign(v->num_meshes, nullptr);
   ctx->mesh_box.assign(v->num_meshes, Aabb{});
+  ctx->mesh_refit.clear(); ctx->mesh_refit.resize(v->num_meshes);
+  ctx->mesh_tri_offset.assign(v->mesh_tri_offset, v->mesh_tri_offset + v->num_meshes + 1);
   blas_tris.assign((size_t) total_triangles(v) + 1, BvhTri{});
   for (uint32_t m = 0; m < v->num_meshes; m++) {
     const uint32_t t0 = v->mesh_tri_offset[m], nt = v->mesh_tri_offset[m + 1] - t0;
@@ -483,23 +501,99 @@ static int build_mesh_trees(LumContext* ctx, const LumDeviceSceneView* v, std::v
     ctx->mesh_box[m] = mesh_triangle_boxes(vertices, nt, tri_boxes.data());
     const auto t_build = std::chrono::steady_clock::now();
     const MeshTreeKey key = mesh_tree_key(vertices, nt, ctx->bvh_builder);
-    std::shared_ptr<const MeshTree> tree = find_mesh_tree(key);
-    if (!tree) {
-      auto built = std::make_shared<MeshTree>();
-      if (ctx->bvh_builder == 1) built->bvh = build_bvh4_lbvh(tri_boxes.data(), nt, kBvhLeafMaxTri, 26);
-      else if (ctx->bvh_builder == 2) built->bvh = build_bvh4_ploc(tri_boxes.data(), nt, kBvhLeafMaxTri, 26);
-      else if (ctx->bvh_builder == 3) built->bvh = build_bvh4_sah_gpu(tri_boxes.data(), nt, kBvhLeafMaxTri, 26);
-      built->built_on_gpu = !built->bvh.nodes.empty();
-      if (!built->built_on_gpu) built->bvh = build_bvh4(tri_boxes.data(), nt, kBvhLeafMaxTri, 26);  // the host builder: asked for, or the fallback for a mesh the GPU builders cannot take
-      if (built->bvh.nodes.empty()) { ctx->error = "mesh BVH exceeds 26 levels"; return 1; }
-      tree = built;
-      keep_mesh_tree(key, tree);
-    }
+    std::shared_ptr<const MeshTree> tree = cached_or_built_mesh_tree(ctx, key, tri_boxes.data(), nt);
+    if (!tree) return 1;
     ctx->bvh_meshes_by_builder[tree->built_on_gpu ? 1 : 0]++;
     ctx->bvh_build_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_build).count();
     fill_mesh_tris(vertices, t0, tree->bvh.prims.data(), nt, blas_tris.data() + t0);
     ctx->mesh_bvh[m] = std::move(tree);
+    ctx->mesh_refit[m].fit_hash[0] = key.h0; ctx->mesh_refit[m].fit_hash[1] = key.h1;
   }
+  return 0;
+}
+
+// LUMC_DIRTY_MESH_POSITIONS: the vertex arrays of the same meshes again - the traversal triangles stay on the device (update_mesh_arrays frees its group) -, then
+// every mesh whose vertices differ from those its held tree was fitted to gets a tree for them: refitted on the device (bvh_refit.hip; the tree becomes
+// private to this context, the shared one it came from is not touched and the cache never sees the refitted one) or, where the mode, the cost's growth or a
+// tree that cannot be refitted says so, from the cache / the builder like an upload. *rebuilt: a mesh's traversal triangles were written anew (k_tri_opacity).
+static int refit_mesh_trees(LumContext* ctx, const LumDeviceSceneView* v, bool* rebuilt) {
+  using clock = std::chrono::steady_clock;
+  auto since = [](clock::time_point t) { return std::chrono::duration<double>(clock::now() - t).count(); };
+  DeviceScene& sc = ctx->scene;
+  LumMeshRefitStats& st = ctx->refit_stats;
+  st.last_refits = st.last_rebuilds = 0; st.max_cost_growth = st.seconds = st.seconds_upload = st.seconds_refit = st.seconds_rebuild = st.seconds_assemble = 0.0;
+  st.seconds_hash = st.seconds_download = st.seconds_lights = 0.0;
+  *rebuilt = false;
+  if (ctx->mesh_bvh.size() != v->num_meshes || ctx->mesh_refit.size() != v->num_meshes || ctx->mesh_tri_offset.size() != (size_t) v->num_meshes + 1 ||
+      std::memcmp(ctx->mesh_tri_offset.data(), v->mesh_tri_offset, sizeof(uint32_t) * ((size_t) v->num_meshes + 1)) != 0) {
+    ctx->error = "lumc_scene_update: LUMC_DIRTY_MESH_POSITIONS with other meshes or triangle counts than the scene on the device";
+    return 1;
+  }
+  const auto t_all = clock::now();
+  auto& group = ctx->scene_allocs[LumContext::kGrpMesh];
+  DeviceBuffer<char> tris_buffer;
+  for (auto& b : group) if (b.get() == reinterpret_cast<const char*>(sc.blas_tris)) tris_buffer = std::move(b);
+  if (!tris_buffer) { ctx->error = "lumc_scene_update: the scene on the device has no traversal triangles"; return 1; }
+  BvhTri* d_tris = reinterpret_cast<BvhTri*>(tris_buffer.get());
+  const int failed = update_mesh_arrays(ctx, v);
+  group.push_back(std::move(tris_buffer));
+  if (failed) return 1;
+  HIP_TRY(ctx, hipDeviceSynchronize());
+  st.seconds_upload = since(t_all);
+  for (uint32_t m = 0; m < v->num_meshes; m++) {
+    const uint32_t t0 = v->mesh_tri_offset[m], nt = v->mesh_tri_offset[m + 1] - t0;
+    if (nt == 0) continue;
+    const float* vertices = v->vertices + (size_t) t0 * 12;
+    MeshRefit& mr = ctx->mesh_refit[m];
+    const auto t_hash = clock::now();
+    const MeshTreeKey key = mesh_tree_key(vertices, nt, ctx->bvh_builder);
+    st.seconds_hash += since(t_hash);
+    if (key.h0 == mr.fit_hash[0] && key.h1 == mr.fit_hash[1]) continue;  // the held tree fits these vertices
+    bool build = ctx->refit_mode == 1;
+    if (!build) {
+      const auto t_refit = clock::now();
+      if (mr.built_cost == 0.0) mr.built_cost = bvh4_cost(ctx->mesh_bvh[m]->bvh);  // (no refit yet: the held tree is the built one)
+      if (!mr.plan.nodes) {
+        const hipError_t e = refit_plan_create(mr.plan, ctx->mesh_bvh[m]->bvh, nt);
+        if (e == hipErrorInvalidValue) build = true;  // spatial splits: more references than triangles
+        else HIP_TRY(ctx, e);
+      }
+      if (!build) {
+        if (!mr.own) {
+          mr.own = std::make_shared<MeshTree>();
+          mr.own->bvh.prims = ctx->mesh_bvh[m]->bvh.prims; mr.own->bvh.max_depth = ctx->mesh_bvh[m]->bvh.max_depth; mr.own->built_on_gpu = ctx->mesh_bvh[m]->built_on_gpu;
+          mr.own->bvh.nodes.resize(mr.plan.num_nodes);
+        }
+        Aabb box;
+        double download = 0.0;
+        HIP_TRY(ctx, refit_run(mr.plan, sc.vertices + 3 * (size_t) t0, d_tris + t0, nullptr, mr.own->bvh.nodes.data(), &box, &download));
+        st.seconds_download += download;
+        const double growth = mr.built_cost > 0.0 ? bvh4_cost(mr.own->bvh) / mr.built_cost : 1.0;
+        st.max_cost_growth = std::max(st.max_cost_growth, growth);
+        if (ctx->refit_max_cost_growth > 0.0f && growth > (double) ctx->refit_max_cost_growth) build = true;
+        else { ctx->mesh_bvh[m] = mr.own; ctx->mesh_box[m] = box; st.refits++; st.last_refits++; }
+      }
+      st.seconds_refit += since(t_refit);
+    }
+    if (build) {
+      const auto t_build = clock::now();
+      std::vector<Aabb> tri_boxes(nt);
+      ctx->mesh_box[m] = mesh_triangle_boxes(vertices, nt, tri_boxes.data());
+      std::shared_ptr<const MeshTree> tree = cached_or_built_mesh_tree(ctx, key, tri_boxes.data(), nt);
+      if (!tree) return 1;
+      std::vector<BvhTri> tris(nt);
+      fill_mesh_tris(vertices, t0, tree->bvh.prims.data(), nt, tris.data());
+      HIP_TRY(ctx, hipMemcpy(d_tris + t0, tris.data(), sizeof(BvhTri) * nt, hipMemcpyHostToDevice));
+      mr.plan.reset(); mr.own.reset();
+      mr.built_cost = bvh4_cost(tree->bvh);
+      ctx->mesh_bvh[m] = std::move(tree);
+      *rebuilt = true;
+      st.rebuilds++; st.last_rebuilds++;
+      st.seconds_rebuild += since(t_build);
+    }
+    mr.fit_hash[0] = key.h0; mr.fit_hash[1] = key.h1;
+  }
+  st.seconds = since(t_all);
   return 0;
 }
 
@@ -566,6 +660,8 @@ static int update_light_bvh(LumContext* ctx, const LumDeviceSceneView* v) {
   return 0;
 }
 
+constexpr unsigned kDirtyTrianglesRewritten = 1u << 30;  // scene_update's own: a LUMC_DIRTY_MESH_POSITIONS update built a mesh again, its traversal triangles are new
+
 // The counts, then what two kernels derive from the arrays above: k_tri_opacity (needs the materials and blas_tris), k_light_table (needs the counts).
 static int update_counts_and_tables(LumContext* ctx, const LumDeviceSceneView* v, unsigned dirty) {
   DeviceScene& sc = ctx->scene;
@@ -573,7 +669,7 @@ static int update_counts_and_tables(LumContext* ctx, const LumDeviceSceneView* v
   const bool dirty_lights = (dirty & LUMC_DIRTY_LIGHTS) != 0;
   ctx->bvh_stats[1] = total_tris;
   sc.num_meshes = v->num_meshes; sc.num_instances = v->num_instances; sc.num_materials = v->num_materials; sc.num_lights = v->num_lights;  // (num_textures: update_textures)
-  if (total_tris && (dirty & (LUMC_DIRTY_MESHES | LUMC_DIRTY_MATERIALS))) {  // the triangles' material words: texture id, or whether they stop a visibility ray on their own
+  if (total_tris && (dirty & (LUMC_DIRTY_MESHES | LUMC_DIRTY_MATERIALS | kDirtyTrianglesRewritten))) {  // the triangles' material words: texture id, or whether they stop a visibility ray on their own
     hipLaunchKernelGGL(k_tri_opacity, dim3((total_tris + kBlock - 1) / kBlock), dim3(kBlock), 0, 0, sc, const_cast<BvhTri*>(sc.blas_tris), total_tris);
     HIP_TRY(ctx, hipGetLastError());
   }
@@ -818,20 +914,34 @@ static int scene_update(LumContext* ctx, const LumDeviceSceneView* v, unsigned d
   DeviceScene& sc = ctx->scene;
   if (!v->bluenoise_2d) { ctx->error = "scene has no blue-noise mask"; return 1; }
   if (v->max_ray_depth > 63) { ctx->error = "max_ray_depth exceeds 63 (6-bit field, device_structs.h:9)"; return 1; }
-  if (dirty & LUMC_DIRTY_MESHES) dirty |= LUMC_DIRTY_INSTANCES;  // the assembled node array holds the per-mesh trees
+  if (dirty & LUMC_DIRTY_MESHES) dirty &= ~(unsigned) LUMC_DIRTY_MESH_POSITIONS;  // a full rebuild of the meshes covers moved vertices
+  if (dirty & (LUMC_DIRTY_MESHES | LUMC_DIRTY_MESH_POSITIONS)) dirty |= LUMC_DIRTY_INSTANCES;  // the assembled node array holds the per-mesh trees
   if (dirty & LUMC_DIRTY_PARTICLES) dirty |= LUMC_DIRTY_CONSTANTS;
   const bool meshes = (dirty & LUMC_DIRTY_MESHES) != 0, instances = (dirty & LUMC_DIRTY_INSTANCES) != 0, lights = (dirty & LUMC_DIRTY_LIGHTS) != 0;
   ctx->has_scene = false;
   if (meshes && update_mesh_arrays(ctx, v)) return 1;
+  if (dirty & LUMC_DIRTY_MESH_POSITIONS) {
+    bool rebuilt = false;
+    if (refit_mesh_trees(ctx, v, &rebuilt)) return 1;
+    if (rebuilt) dirty |= kDirtyTrianglesRewritten;
+  }
   if (instances && update_instance_arrays(ctx, v)) return 1;
   if ((dirty & LUMC_DIRTY_MATERIALS) && update_materials(ctx, v)) return 1;
+  const bool time_lights = (dirty & LUMC_DIRTY_MESH_POSITIONS) != 0;
+  auto lights_since = [&](std::chrono::steady_clock::time_point t) { if (time_lights) ctx->refit_stats.seconds_lights += std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count(); };
+  auto t_lights = std::chrono::steady_clock::now();
   if (lights && update_light_tree(ctx, v)) return 1;
+  lights_since(t_lights);
   if (!sc.bluenoise_2d && upload(ctx, LumContext::kGrpOnce, v->bluenoise_2d, 65536, &sc.bluenoise_2d)) return 1;
   if ((dirty & LUMC_DIRTY_TEXTURES) && update_textures(ctx, v)) return 1;
   size_t num_nodes = 0;
+  const auto t_assemble = std::chrono::steady_clock::now();
   if (instances && (update_scene_tree(ctx, v, meshes, &num_nodes) || update_ray_kernel_lds(ctx, num_nodes))) return 1;
+  if (dirty & LUMC_DIRTY_MESH_POSITIONS) ctx->refit_stats.seconds_assemble = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_assemble).count();
+  t_lights = std::chrono::steady_clock::now();
   if (lights && update_light_bvh(ctx, v)) return 1;
   if (update_counts_and_tables(ctx, v, dirty)) return 1;
+  lights_since(t_lights);
   if ((dirty & LUMC_DIRTY_CONSTANTS) && update_constants(ctx, v, dirty)) return 1;
   if (update_bridge_table(ctx, v)) return 1;
   // the moon's texture ids follow the texture pool (the host layer appends the two moon textures behind the scene's own): an added texture moves them
@@ -853,7 +963,20 @@ int lumc_scene_update(LumContext* ctx, const LumDeviceSceneView* v, unsigned int
   if (!ctx->has_scene || (dirty & LUMC_DIRTY_ALL) == LUMC_DIRTY_ALL) return lumc_scene_upload(ctx, v);
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   HIP_TRY(ctx, hipDeviceSynchronize());  // nothing renders from the arrays that are about to be freed
-  if (scene_update(ctx, v, dirty & LUMC_DIRTY_ALL)) { free_scene(ctx); return 1; }  // a failed partial update leaves no half-updated scene behind
+  if (scene_update(ctx, v, dirty & (LUMC_DIRTY_ALL | LUMC_DIRTY_MESH_POSITIONS))) { free_scene(ctx); return 1; }  // a failed partial update leaves no half-updated scene behind
+  return 0;
+}
+
+int lumc_set_mesh_refit(LumContext* ctx, uint32_t mode, float max_cost_growth) {
+  if (!ctx) return 1;
+  if (mode > 1 || !(max_cost_growth >= 0.0f) || !std::isfinite(max_cost_growth)) { ctx->error = "lumc_set_mesh_refit: mode is 0 or 1, max_cost_growth >= 0"; return 1; }
+  ctx->refit_mode = mode; ctx->refit_max_cost_growth = max_cost_growth;
+  return 0;
+}
+
+int lumc_mesh_refit_stats(const LumContext* ctx, LumMeshRefitStats* out) {
+  if (!ctx || !out) return 1;
+  *out = ctx->refit_stats;
   return 0;
 }
 

@@ -999,6 +999,17 @@ std::string update_device_scene(const HostScene& scene, const std::vector<uint32
 
   DeviceSceneBuffers& b = *out;
   if (b.bluenoise.size() != 65536) { b.bluenoise = bluenoise; dirty = LUMC_DIRTY_ALL; }  // first build
+  auto encode_vertices = [&](size_t m) {  // device_structs.c:351-361
+    const HostMesh& mesh = scene.meshes[m];
+    for (uint32_t t = 0; t < mesh.triangle_count(); t++) {
+      const size_t g = (size_t) b.mesh_tri_offset[m] + t;
+      for (int k = 0; k < 3; k++) {
+        float* v = b.vertices.data() + (g * 3 + k) * 4;
+        v[0] = mesh.positions[9 * (size_t) t + 3 * k]; v[1] = mesh.positions[9 * (size_t) t + 3 * k + 1]; v[2] = mesh.positions[9 * (size_t) t + 3 * k + 2];
+        v[3] = bits_float(pack_normal(mesh.normals.data() + 9 * (size_t) t + 3 * k));
+      }
+    }
+  };
   if (dirty & LUMC_DIRTY_MESHES) {
   b.mesh_tri_offset.assign(scene.meshes.size() + 1, 0);
   size_t total = 0;
@@ -1008,13 +1019,9 @@ std::string update_device_scene(const HostScene& scene, const std::vector<uint32
   b.tri_tex.resize(total * 4);
   for (size_t m = 0; m < scene.meshes.size(); m++) {
     const HostMesh& mesh = scene.meshes[m];
+    encode_vertices(m);
     for (uint32_t t = 0; t < mesh.triangle_count(); t++) {
       const size_t g = (size_t) b.mesh_tri_offset[m] + t;
-      for (int k = 0; k < 3; k++) {  // device_structs.c:351-361
-        float* v = b.vertices.data() + (g * 3 + k) * 4;
-        v[0] = mesh.positions[9 * (size_t) t + 3 * k]; v[1] = mesh.positions[9 * (size_t) t + 3 * k + 1]; v[2] = mesh.positions[9 * (size_t) t + 3 * k + 2];
-        v[3] = bits_float(pack_normal(mesh.normals.data() + 9 * (size_t) t + 3 * k));
-      }
       uint32_t* tt = b.tri_tex.data() + g * 4;  // device_structs.c:363-374
       tt[0] = pack_uv(mesh.uvs[6 * (size_t) t + 0], mesh.uvs[6 * (size_t) t + 1]);
       tt[1] = pack_uv(mesh.uvs[6 * (size_t) t + 2], mesh.uvs[6 * (size_t) t + 3]);
@@ -1023,6 +1030,11 @@ std::string update_device_scene(const HostScene& scene, const std::vector<uint32
     }
   }
   }
+  else if (dirty & LUMC_DIRTY_MESH_POSITIONS) {  // moved vertices (luminary_ext_set_mesh_positions): only those meshes' vertices; offsets, tri_tex and instances stay
+    for (uint32_t m : b.moved_meshes)
+      if (m < scene.meshes.size() && b.mesh_tri_offset.size() == scene.meshes.size() + 1 && (size_t) b.mesh_tri_offset[m] + scene.meshes[m].triangle_count() == b.mesh_tri_offset[m + 1]) encode_vertices(m);
+  }
+  b.moved_meshes.clear();
   if (dirty & (LUMC_DIRTY_INSTANCES | LUMC_DIRTY_MESHES)) {
   // inactive instances keep their slot (ids are stable) but point at no mesh
   b.instance_mesh_ids.resize(scene.instances.size());

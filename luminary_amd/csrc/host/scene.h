@@ -92,6 +92,7 @@ struct DeviceSceneBuffers {
   // texture pool bookkeeping that outlives a partial update
   uint32_t num_textures = 0, moon_albedo_tex = 0xFFFFFFFFu, moon_normal_tex = 0xFFFFFFFFu;
   bool moon_in_pool = false;
+  std::vector<uint32_t> moved_meshes;  // in: the meshes whose vertices a LUMC_DIRTY_MESH_POSITIONS update re-encodes (cleared by update_device_scene)
   uint32_t rebuilt = 0;  // LUMC_DIRTY_* parts the last update_device_scene rebuilt (what the core has to take over)
   // the camera the contexts render with besides the view (lumc_set_physical_camera): valid when use_physical_camera
   bool use_physical_camera = false;

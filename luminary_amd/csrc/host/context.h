@@ -1,6 +1,7 @@
-// The host layer's context and the helpers its translation units share. Private to csrc/host: core.hip (scene upload, render schedule, the
-// flavour-neutral kernels of kernels_shared.h), ray_sort.hip, multi_gpu.hip. The context owns its device memory through DeviceBuffer members (device_buffer.h): deleting it frees them.
-// Its other pointers - DeviceScene, the queues, d_results, d_ended, d_fused - are views into those buffers. kernels.h is not included, so a unit that includes
+// The host layer's context and the helpers its translation units share. Private to csrc/host: core.hip (the context, the work buffers, the render schedule, the
+// adaptive sampler, the output chain and the ray queries, with the flavour-neutral kernels of kernels_shared.h), scene_device.hip (the scene on the device, with the
+// kernels of kernels_scene.h), ray_sort.hip, multi_gpu.hip. The context owns its device memory through DeviceBuffer members (device_buffer.h): deleting it frees them.
+// Its other pointers - DeviceScene, the work buffers' arrays (work_layout.h) - are views into those buffers. kernels.h is not included, so a unit that includes
 // this header gets none of the flavoured kernels (their device symbols - the sampler's seed table, the phase counters - exist per translation unit).
 #pragma once
 
@@ -17,6 +18,7 @@
 #include "bvh_build.h"
 #include "bvh_refit.h"
 #include "device_buffer.h"
+#include "work_layout.h"
 
 using namespace lum;
 
@@ -62,18 +64,15 @@ struct LumContext {
   int ambient_reuse = -1;         // -1 by flavour (fast: on), 0 off, 1 on (lumc_set_ambient_reuse; LUM_AMBIENT_REUSE)
   uint32_t shade_grid_rounds = 2;  // k_shade's grid as a multiple of its resident set (0: the common 2048-workgroup cap); LUM_SHADE_GRID
   int fused_resolve = 1;          // with the fast flavour's ambient reuse: k_shade resolves the previous depth's vertices itself (lumc_set_fused_resolve; LUM_FUSED_RESOLVE)
-  DeviceBuffer<char> fused_block; // what that needs beyond the usual work buffers: a third path queue, the parent words, a second set of NEE records, the fallback rays' items
-  bool fused_records_stale = false;  // a queue's planes changed places (ray-sorting mode 3) since the records were written
-  uint32_t fused_capacity = 0, fused_refused_capacity = 0;  // (the capacity its allocation last failed for: not tried again)
+  struct Fused : FusedBuffers {   // what that needs beyond the usual work buffers (work_layout.h lay_out_fused)
+    DeviceBuffer<char> block;
+    bool records_stale = false;     // a queue's planes changed places (ray-sorting mode 3) since the records were written
+    uint32_t refused_capacity = 0;  // the capacity its allocation last failed for: not tried again
+  } fused;
   DeviceBuffer<uint2> d_sobol;      // the pass's Sobol / Owen table (dev_sampler.h LUM_SOBOL_TABLE; wavefront_depths fills it)
   int sobol_table = 1;              // LUM_SOBOL_TABLE_RT=0: the sampler hashes every number itself
-  uint32_t* d_ended[2] = {nullptr, nullptr};  // a depth's vertices that no entry continues, by the depth's parity (k_shade lists them; the next depth's k_shade resolves them, or k_resolve_ended)
-  // ... the next depth's k_shade (1) or k_resolve_ended after the depth's visibility pass (0; LUM_FUSED_ENDED=0)
-  int fused_ended = 1;
+  int fused_ended = 1;  // the vertices that no entry continues (Fused::ended) are resolved by the next depth's k_shade (1) or by k_resolve_ended after the depth's visibility pass (0; LUM_FUSED_ENDED=0)
   int fused_ended_default = 1;  // what lumc_set_fused_resolve(1) goes back to (the environment's choice, if any)
-  FusedResolve* d_fused = nullptr;  // six records in device memory: the previous depth's queue (three buffers) and NEE records (two) by depth % 6
-  NeeQueue nee2{};
-  ShadowQueue fallback{};
   int bvh_builder = 3;            // 0 binned SAH on the host, 1 LBVH on the GPU, 2 PLOC on the GPU, 3 binned SAH on the GPU (default since round 4: the host builder's trees in a fifth of its time; a mesh it cannot take falls back to 0) (lumc_set_bvh_builder)
   double bvh_build_seconds = 0.0; // bottom-level builds of the last lumc_scene_upload
   uint32_t bvh_meshes_by_builder[2] = {0, 0};  // meshes of the last upload built by SAH / by LBVH
@@ -86,17 +85,8 @@ struct LumContext {
   uint32_t num_pixels = 0;
   uint64_t pixels_hash = 0;       // of the pixel list in its order (lumc_set_pixels): the tile gather checks that the set IS the share of the deal it assumes
   DeviceBuffer<float> d_first_moment, d_second_moment;
-  // work buffers (sized for capacity paths)
-  uint32_t capacity = 0;
-  DeviceBuffer<char> work_block;
-  PathQueue queue[3]{};           // [2]: only with the fused resolve (ensure_fused)
-  NeeQueue nee{};
-  ShadowQueue shadow{};
+  struct Work : WorkBuffers { DeviceBuffer<char> block; } work;  // the work buffers, laid out for work.capacity paths (work_layout.h lay_out_work)
   uint32_t particle_lds_nodes = 0;
-  VolumeQueue volume{};           // fog (dev_volume.h); allocated with the work block when the scene's fog is active
-  CloudQueue cloud{};             // the cloud marches of a depth (kernels.h k_clouds_*); allocated with the work block when clouds are marched
-  uint32_t work_shadow_kinds = 0; // visibility-ray kinds per path the work block was sized for (4, or 17 with fog)
-  float4* d_results = nullptr;
   DeviceBuffer<float> d_frame_output;  // display-referred planes of the output chain [3 * W * H]
   DeviceBuffer<uint16_t> d_bluenoise_1d;
   DeviceBuffer<uint32_t> d_argb8;
@@ -220,6 +210,7 @@ const uint32_t* sort_rays(LumContext* ctx, hipStream_t stream, const float4* ori
 int sort_closest_rays(LumContext* ctx, hipStream_t stream, PathQueue& queue, uint32_t* ctrl, uint32_t N, const uint32_t** order);
 void free_sort(LumContext* ctx);  // the buffers of every mode; the settings and the scene's bounds stay
 void free_exchange(LumContext* ctx);  // multi_gpu.hip
+int scene_device_init();  // scene_device.hip: that unit's copy of the sampler's seed table, per device (a hipError_t; lumc_context_create)
 extern "C" uint64_t pixel_list_hash(const uint32_t* pixels, uint32_t n);  // core.hip, among the entry points that use it
 
 #pragma GCC visibility pop

@@ -1,4 +1,5 @@
-// C ABI of the path-tracing core (include/lum_core.h): context, scene upload, BVH construction, pass scheduling.
+// C ABI of the path-tracing core (include/lum_core.h): the context, the work buffers, the render schedule, the adaptive sampler, the result / output / bloom /
+// denoise entry points, the ray queries and the setters. The scene on the device is scene_device.hip, the ray sort ray_sort.hip, the multi-GPU exchange multi_gpu.hip.
 // Host-side counterpart of the reference's device layer for the hot path only:
 //   device/device.c (context, streams, constant memory), device/device_work_buffers.c:54-117 (task/result buffers),
 //   device/device_renderer.c:53-134, :488-575 (per-depth kernel queue), device/device_result_interface.c (moments).
@@ -6,18 +7,11 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <cmath>
-#include <cfloat>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <map>
-#include <memory>
-#include <mutex>
 #include <string>
-#include <thread>
-#include <tuple>
 #include <vector>
 
 #include "../../../include/lum_core.h"
@@ -30,89 +24,9 @@ static_assert(kLaunchBlock == (uint32_t) kBlock, "grid_for (context.h) counts th
 
 namespace {
 
-// ---- the process's bottom-level trees by what they were built from: the mesh's triangles (two 64-bit hashes of the vertex words, chunk by chunk so that the
-// value does not depend on the number of threads), the builder asked for and every LUM_* variable of the environment (the builders' knobs) ----
-struct MeshTreeKey {
-  uint64_t h0, h1, env;
-  uint32_t tris; int builder;
-  bool operator<(const MeshTreeKey& o) const { return std::tie(h0, h1, env, tris, builder) < std::tie(o.h0, o.h1, o.env, o.tris, o.builder); }
-};
-static std::mutex g_mesh_tree_mutex;
-static std::map<MeshTreeKey, std::weak_ptr<const MeshTree>> g_mesh_trees;
-extern "C" char** environ;
-
-static MeshTreeKey mesh_tree_key(const float* tri_vertices, uint32_t tris, int builder) {
-  constexpr size_t kChunk = 65536;  // triangles (12 floats each)
-  const size_t chunks = ((size_t) tris + kChunk - 1) / kChunk;
-  std::vector<uint64_t> part(2 * chunks);
-  host_parallel_for(chunks, [&](size_t b, size_t e) {
-    for (size_t c = b; c < e; c++) {
-      const size_t first = c * kChunk, last = std::min<size_t>((size_t) tris, first + kChunk);
-      uint64_t a = 0x9E3779B97F4A7C15ull ^ c, z = 0xC2B2AE3D27D4EB4Full + c;
-      for (size_t w = first * 6; w < last * 6; w++) {
-        uint64_t x;
-        std::memcpy(&x, reinterpret_cast<const char*>(tri_vertices) + w * 8, 8);
-        a = (a ^ x) * 0x100000001B3ull; a ^= a >> 29;
-        z = (z + x) * 0xFF51AFD7ED558CCDull; z ^= z >> 32;
-      }
-      part[2 * c] = a; part[2 * c + 1] = z;
-    }
-  });
-  MeshTreeKey k{0xCBF29CE484222325ull, 0x84222325CBF29CE4ull, 0xCBF29CE484222325ull, tris, builder};
-  for (size_t c = 0; c < chunks; c++) { k.h0 = (k.h0 ^ part[2 * c]) * 0x100000001B3ull; k.h1 = (k.h1 + part[2 * c + 1]) * 0xFF51AFD7ED558CCDull; k.h1 ^= k.h1 >> 32; }
-  for (char** e = environ; e && *e; e++)
-    if (std::strncmp(*e, "LUM_", 4) == 0) for (const char* p = *e; *p; p++) k.env = (k.env ^ (uint8_t) *p) * 0x100000001B3ull;
-  return k;
-}
-static std::shared_ptr<const MeshTree> find_mesh_tree(const MeshTreeKey& k) {
-  if (const char* e = getenv("LUM_BVH_SHARE")) if (atoi(e) == 0) return nullptr;  // every upload builds (tools/lbvh_bench.py times the builders this way)
-  std::lock_guard<std::mutex> lock(g_mesh_tree_mutex);
-  auto it = g_mesh_trees.find(k);
-  if (it == g_mesh_trees.end()) return nullptr;
-  std::shared_ptr<const MeshTree> t = it->second.lock();
-  if (!t) g_mesh_trees.erase(it);
-  return t;
-}
-static void keep_mesh_tree(const MeshTreeKey& k, const std::shared_ptr<const MeshTree>& t) {
-  std::lock_guard<std::mutex> lock(g_mesh_tree_mutex);
-  for (auto it = g_mesh_trees.begin(); it != g_mesh_trees.end();) it = it->second.expired() ? g_mesh_trees.erase(it) : std::next(it);
-  g_mesh_trees[k] = t;
-}
-
-constexpr size_t kCloudNoiseTexels[3] = {(size_t) kCloudShapeRes * kCloudShapeRes * kCloudShapeRes, (size_t) kCloudDetailRes * kCloudDetailRes * kCloudDetailRes,
-                                         (size_t) kCloudWeatherRes * kCloudWeatherRes};  // shape, detail, weather (RGBA8 each)
-constexpr uint32_t kBsdfLutCount[4] = {1024, 1024, 32768, 32768};  // conductor, glossy, dielectric, dielectric_inv
-
-// A scene array on the device, owned by the allocation group it is registered under.
-template <typename T>
-int upload(LumContext* ctx, int group, const T* host, size_t count, const T** out) {
-  *out = nullptr;
-  DeviceBuffer<char> d;
-  HIP_TRY(ctx, d.assign(reinterpret_cast<const char*>(host), sizeof(T) * count));
-  *out = reinterpret_cast<const T*>(d.get());
-  if (d) ctx->scene_allocs[group].push_back(std::move(d));
-  return 0;
-}
-
-void free_scene(LumContext* ctx) {
-  for (auto& group : ctx->scene_allocs) group.clear();
-  for (auto& t : ctx->d_luts) t.reset();
-  for (auto& t : ctx->d_sky_lut) t.reset();
-  ctx->sky_lut_key.clear();
-  ctx->d_bridge_lut.reset(); ctx->bridge_lut_host.clear();
-  ctx->mesh_bvh.clear(); ctx->mesh_box.clear(); ctx->mesh_refit.clear(); ctx->mesh_tri_offset.clear();
-  ctx->has_scene = false;
-}
-
 void free_work(LumContext* ctx) {
-  ctx->work_block.reset();
-  ctx->fused_block.reset(); ctx->fused_capacity = 0; ctx->d_fused = nullptr;
-  ctx->fused_refused_capacity = 0;  // memory may have been freed since the refusal: the next pass asks again
-  ctx->queue[2] = PathQueue{}; ctx->nee2 = NeeQueue{}; ctx->fallback = ShadowQueue{};
-  for (int k = 0; k < 3; k++) ctx->queue[k].parent = nullptr;
-  ctx->capacity = 0;
-  ctx->work_shadow_kinds = 0;
-  ctx->cloud = CloudQueue{};
+  ctx->work = LumContext::Work{};
+  ctx->fused = LumContext::Fused{};  // (its refusal too: memory may have been freed since, the next pass asks again)
   // the reorder pass's planes (ray-sorting mode 3) trade places with the queues' own: they go with them (and with them the sort's keys, sized by the pass too)
   free_sort(ctx);
   ctx->d_sobol.reset();
@@ -125,104 +39,47 @@ int ensure_work(LumContext* ctx, uint32_t paths) {
   const uint32_t kinds = volumes ? kVolumeShadowKinds : 4u;
   const bool clouds = ctx->scene.cloud_active && ctx->scene.sky_mode == kSkyDefault;
   if (clouds && paths >= (1u << 30)) { ctx->error = "pass too large for the cloud march list (2^30 paths)"; return 1; }
-  if (paths <= ctx->capacity && kinds <= ctx->work_shadow_kinds && (!clouds || ctx->cloud.items)) return 0;
-  if (paths < ctx->capacity) paths = ctx->capacity;
+  if (paths <= ctx->work.capacity && kinds <= ctx->work.shadow_kinds && (!clouds || ctx->work.cloud.items)) return 0;
+  if (paths < ctx->work.capacity) paths = ctx->work.capacity;
   free_work(ctx);
-  // per path: 2 queues x 68 B + NEE 84 B + result 16 B + up to `kinds` visibility rays x (48 B + 16 B result) + 4 B light-query index
-  // (+ the volumes' 96 B of in-scattering records, 4 B scattering-event index and 48 B of water-surface factors of the surface vertices)
-  const size_t n = paths;
-  const size_t bytes = n * (2 * 68 + 84 + 16 + (size_t) kinds * 64 + 4 + (kinds > 4u ? 100 + 48 : 0) + (clouds ? 3 * (4 + 16 + 4) : 0)) + 56 * 256;
-  HIP_TRY(ctx, ctx->work_block.resize(bytes));
-  char* p = ctx->work_block.get();
-  auto take = [&](size_t sz) { char* r = p; p += (sz + 255) & ~(size_t) 255; return r; };  // keeps every array 256-byte aligned
-  for (int k = 0; k < 2; k++) {
-    ctx->queue[k].origin_t = (float4*) take(n * 16);
-    ctx->queue[k].dir_slot = (float4*) take(n * 16);
-    ctx->queue[k].aux      = (uint4*) take(n * 16);
-    ctx->queue[k].hit_id   = (uint4*) take(n * 16);
-    ctx->queue[k].hit_scene_tri = (uint32_t*) take(n * 4);
-  }
-  ctx->nee.geo_color_light = (float4*) take(n * 16);
-  ctx->nee.bsdf_ray_prob   = (float4*) take(n * 16);
-  ctx->nee.bsdf_weight_sum = (float4*) take(n * 16);
-  ctx->nee.ambient         = (uint4*) take(n * 16);
-  ctx->nee.sun             = (uint4*) take(n * 16);
-  ctx->nee.amb_path        = (uint32_t*) take(n * 4);
-  ctx->d_results           = (float4*) take(n * 16);
-  ctx->shadow.origin_dist  = (float4*) take(kinds * n * 16);
-  ctx->shadow.dir_out      = (float4*) take(kinds * n * 16);
-  ctx->shadow.ids          = (uint4*) take(kinds * n * 16);
-  ctx->shadow.vis          = (float4*) take(kinds * n * 16);
-  ctx->shadow.light_items  = (uint32_t*) take(n * 4);
-  ctx->shadow.capacity     = paths;
-  ctx->volume = VolumeQueue{};
-  ctx->nee.sun_water = nullptr; ctx->nee.amb_t1 = nullptr; ctx->nee.amb_t2 = nullptr;
-  if (kinds > 4u) {
-    ctx->volume.bridge = (float4*) take(n * 16);
-    ctx->volume.sky    = (uint4*) take(n * 16);
-    ctx->volume.weight = (float4*) take(n * 16);
-    ctx->volume.sun_water = (float4*) take(n * 16);
-    ctx->volume.amb_t1 = (float4*) take(n * 16);
-    ctx->volume.amb_t2 = (float4*) take(n * 16);
-    ctx->volume.items  = (uint32_t*) take(n * 4);
-    ctx->nee.sun_water = (float4*) take(n * 16);
-    ctx->nee.amb_t1    = (float4*) take(n * 16);
-    ctx->nee.amb_t2    = (float4*) take(n * 16);
-  }
-  ctx->cloud = CloudQueue{};
-  if (clouds) {  // per path up to three marches: list entry, result, distance of the first cloud
-    ctx->cloud.items    = (uint32_t*) take(3 * n * 4);
-    ctx->cloud.result   = (float4*) take(3 * n * 16);
-    ctx->cloud.hit_dist = (float*) take(3 * n * 4);
-    ctx->cloud.capacity = paths;
-  }
-  ctx->work_shadow_kinds = kinds;
-  ctx->capacity = paths;
+  WorkBuffers sized;
+  ArenaCarver size(nullptr);  // the first pass counts, the second points into the block
+  lay_out_work(size, paths, kinds, clouds, sized);
+  HIP_TRY(ctx, ctx->work.block.resize(size.used));
+  ArenaCarver arena(ctx->work.block.get());
+  lay_out_work(arena, paths, kinds, clouds, ctx->work);
   return 0;
 }
 
-// The fused resolve's own buffers (FusedResolve, kernels.h), sized like the work buffers: per path a third queue entry (68 B), three parent words, a second
-// set of NEE records (84 B) and one fallback ray (48 B + its vertex's index).
 // The six records k_shade reads the previous depth through (device memory): rewritten whenever a queue's planes move.
 int upload_fused_records(LumContext* ctx, hipStream_t stream) {
   FusedResolve by_depth[6];
   for (int d = 0; d < 6; d++) {  // depth d is shaded from queue d % 3 with the records d & 1: the depth before it lives in queue (d + 2) % 3 and the other record set
-    by_depth[d].prev = ctx->queue[(d + 2) % 3];
-    by_depth[d].nee_prev = (d & 1) ? ctx->nee : ctx->nee2;
-    by_depth[d].fallback = ctx->fallback;
-    by_depth[d].ended = ctx->d_ended[d & 1];
-    by_depth[d].ended_prev = ctx->d_ended[(d & 1) ^ 1];
+    by_depth[d].prev = ctx->work.queue[(d + 2) % 3];
+    by_depth[d].nee_prev = (d & 1) ? ctx->work.nee : ctx->fused.nee;
+    by_depth[d].fallback = ctx->fused.fallback;
+    by_depth[d].ended = ctx->fused.ended[d & 1];
+    by_depth[d].ended_prev = ctx->fused.ended[(d & 1) ^ 1];
   }
   HIP_TRY(ctx, hipStreamSynchronize(stream));  // a pass still reading the old records on a non-blocking stream is not ordered against the null-stream copy below
-  HIP_TRY(ctx, hipMemcpy(ctx->d_fused, by_depth, sizeof(by_depth), hipMemcpyHostToDevice));
-  ctx->fused_records_stale = false;
+  HIP_TRY(ctx, hipMemcpy(ctx->fused.records, by_depth, sizeof(by_depth), hipMemcpyHostToDevice));
+  ctx->fused.records_stale = false;
   return 0;
 }
+// The fused resolve's own buffers (lay_out_fused), for as many paths as the work buffers.
 int ensure_fused(LumContext* ctx, hipStream_t stream) {
-  if (ctx->fused_block && ctx->fused_capacity == ctx->capacity) return ctx->fused_records_stale ? upload_fused_records(ctx, stream) : 0;
-  if (ctx->fused_refused_capacity == ctx->capacity) return 1;
-  ctx->fused_capacity = 0;
-  const size_t n = ctx->capacity;
-  const size_t bytes = n * (68 + 3 * 4 + 84 + 48 + 4 + 2 * 4) + 27 * 256 + 6 * sizeof(FusedResolve);
-  if (ctx->fused_block.resize(bytes) != hipSuccess) { ctx->fused_refused_capacity = ctx->capacity; return 1; }
-  char* p = ctx->fused_block.get();
-  auto take = [&](size_t sz) { char* r = p; p += (sz + 255) & ~(size_t) 255; return r; };
-  PathQueue& q = ctx->queue[2];
-  q.origin_t = (float4*) take(n * 16); q.dir_slot = (float4*) take(n * 16); q.aux = (uint4*) take(n * 16); q.hit_id = (uint4*) take(n * 16);
-  q.hit_scene_tri = (uint32_t*) take(n * 4);
-  for (int k = 0; k < 3; k++) ctx->queue[k].parent = (uint32_t*) take(n * 4);
-  NeeQueue& e = ctx->nee2;
-  e = NeeQueue{};
-  e.geo_color_light = (float4*) take(n * 16); e.bsdf_ray_prob = (float4*) take(n * 16); e.bsdf_weight_sum = (float4*) take(n * 16);
-  e.ambient = (uint4*) take(n * 16); e.sun = (uint4*) take(n * 16); e.amb_path = (uint32_t*) take(n * 4);
-  ShadowQueue& f = ctx->fallback;
-  f.origin_dist = (float4*) take(n * 16); f.dir_out = (float4*) take(n * 16); f.ids = (uint4*) take(n * 16);
-  f.light_items = (uint32_t*) take(n * 4);
-  f.vis = ctx->shadow.vis;  // the undecided samples' answers go where the depth's own ambient answers went: kind 2 of the previous depth's words
-  f.capacity = ctx->shadow.capacity;
-  ctx->d_ended[0] = (uint32_t*) take(n * 4); ctx->d_ended[1] = (uint32_t*) take(n * 4);
-  ctx->d_fused = (FusedResolve*) take(6 * sizeof(FusedResolve));
-  ctx->fused_capacity = ctx->capacity;
+  LumContext::Fused& f = ctx->fused;
+  const uint32_t paths = ctx->work.capacity;
+  if (f.block && f.capacity == paths) return f.records_stale ? upload_fused_records(ctx, stream) : 0;
+  if (f.refused_capacity == paths) return 1;
+  FusedBuffers sized;
+  ArenaCarver size(nullptr);
+  lay_out_fused(size, paths, ctx->work, sized);
+  if (f.block.resize(size.used) != hipSuccess) { f.refused_capacity = paths; return 1; }
+  ArenaCarver arena(f.block.get());
+  lay_out_fused(arena, paths, ctx->work, f);
+  ctx->work.queue[2] = f.queue;
+  for (int k = 0; k < 3; k++) ctx->work.queue[k].parent = f.parent[k];
   return upload_fused_records(ctx, stream);
 }
 
@@ -285,7 +142,8 @@ int lumc_context_create(int device_ordinal, LumContext** out) {
   HIP_TRY(ctx, hipSetDevice(device_ordinal));
   HIP_TRY(ctx, (hipError_t) wavefront_kernels_exact()->init_sampler_seeds());  // per device: module globals live on each GPU
   HIP_TRY(ctx, (hipError_t) wavefront_kernels_fast()->init_sampler_seeds());
-  HIP_TRY(ctx, (hipError_t) exact::upload_sampler_seeds());  // this unit's own table: k_sky_hdri, k_generate_lut and k_pixel_ray draw random numbers
+  HIP_TRY(ctx, (hipError_t) exact::upload_sampler_seeds());  // this unit's own table: k_pixel_ray draws random numbers
+  HIP_TRY(ctx, (hipError_t) scene_device_init());
   HIP_TRY(ctx, ctx->d_ctrl.resize(kCtlStride * kCtrlRows));
   HIP_TRY(ctx, hipMemset(ctx->d_ctrl.get(), 0, sizeof(uint32_t) * kCtlStride * kCtrlRows));
   HIP_TRY(ctx, ctx->d_counters.resize(LUMC_CNT_COUNT));
@@ -304,747 +162,6 @@ void lumc_context_destroy(LumContext* ctx) {
 
 const char* lumc_last_error(const LumContext* ctx) { return ctx ? ctx->error.c_str() : "null context"; }
 uint32_t lumc_scene_view_sizeof(void) { return (uint32_t) sizeof(LumDeviceSceneView); }
-
-// The clouds' noise textures (device_cloud.c:62-101): shape and detail once per context, the weather map per seed.
-static int ensure_cloud_noise(LumContext* ctx, uint32_t seed) {
-  for (int k = 0; k < 3; k++)
-    if (!ctx->d_cloud_noise[k]) HIP_TRY(ctx, ctx->d_cloud_noise[k].resize(kCloudNoiseTexels[k]));
-  if (!ctx->cloud_noise_static) {
-    hipLaunchKernelGGL(exact::k_cloud_noise_shape, dim3(2048), dim3(256), 0, 0, ctx->d_cloud_noise[0].get(), (uint32_t) kCloudShapeRes);
-    hipLaunchKernelGGL(exact::k_cloud_noise_detail, dim3(128), dim3(256), 0, 0, ctx->d_cloud_noise[1].get(), (uint32_t) kCloudDetailRes);
-    HIP_TRY(ctx, hipGetLastError());
-    ctx->cloud_noise_static = true;
-  }
-  if (!ctx->cloud_noise_weather_valid || ctx->cloud_noise_seed != seed) {
-    hipLaunchKernelGGL(exact::k_cloud_noise_weather, dim3(2048), dim3(256), 0, 0, ctx->d_cloud_noise[2].get(), (uint32_t) kCloudWeatherRes, (float) seed);
-    HIP_TRY(ctx, hipGetLastError());
-    ctx->cloud_noise_seed = seed; ctx->cloud_noise_weather_valid = true;
-  }
-  HIP_TRY(ctx, hipDeviceSynchronize());
-  return 0;
-}
-int lumc_cloud_noise_generate(LumContext* ctx, uint32_t seed, uint32_t* shape, uint32_t* detail, uint32_t* weather) {
-  if (!ctx) return 1;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  if (ensure_cloud_noise(ctx, seed)) return 1;
-  uint32_t* out[3] = {shape, detail, weather};
-  for (int k = 0; k < 3; k++)
-    if (out[k]) HIP_TRY(ctx, hipMemcpy(out[k], ctx->d_cloud_noise[k].get(), sizeof(uint32_t) * kCloudNoiseTexels[k], hipMemcpyDeviceToHost));
-  return 0;
-}
-
-// The particle tree (device_particle.c:23-131, optix_bvh.c's particle GAS / IAS): one bottom-level tree over the 2 x count triangles of the unit
-// cell, and a top level over its 25 x 25 x 25 integer translations, instance id = (xi * 25 + yi) * 25 + zi as the reference numbers them. The
-// top-level leaves hold the translation as an exact affine map (rows of the identity), so entering an instance is one subtraction per axis.
-static int build_particle_tree(LumContext* ctx, int group, const LumDeviceSceneView* v, DeviceScene& sc) {
-  sc.particle_bvh_nodes = nullptr; sc.particle_tris = nullptr; sc.particle_leaves = nullptr; sc.particle_tlas_num_nodes = 0; sc.particle_normals = nullptr;
-  if (!sc.particles_active) return 0;
-  if (!v->particle_vertices || !v->particle_normals) { ctx->error = "lumc_scene_upload: active particles without particle_vertices / particle_normals"; return 1; }
-  const uint32_t nt = 2u * sc.particles_count;
-  std::vector<Aabb> tri_boxes(nt);
-  Aabb cell{{FLT_MAX, FLT_MAX, FLT_MAX}, {-FLT_MAX, -FLT_MAX, -FLT_MAX}};
-  for (uint32_t t = 0; t < nt; t++) {
-    const float* p = v->particle_vertices + (size_t) t * 12;
-    tri_boxes[t] = tri_box(p, p + 4, p + 8);
-    for (int k = 0; k < 3; k++) { cell.lo[k] = std::min(cell.lo[k], tri_boxes[t].lo[k]); cell.hi[k] = std::max(cell.hi[k], tri_boxes[t].hi[k]); }
-  }
-  constexpr int kDim = 25;  // PARTICLES_BLOCK_DIM
-  std::vector<Aabb> boxes((size_t) kDim * kDim * kDim);
-  std::vector<float> offsets(3 * boxes.size());
-  uint32_t id = 0;
-  for (int xi = 0; xi < kDim; xi++)
-    for (int yi = 0; yi < kDim; yi++)
-      for (int zi = 0; zi < kDim; zi++, id++) {
-        const float off[3] = {(float) (xi - (kDim >> 1)), (float) (yi - (kDim >> 1)), (float) (zi - (kDim >> 1))};
-        for (int k = 0; k < 3; k++) { offsets[3 * id + k] = off[k]; boxes[id].lo[k] = cell.lo[k] + off[k] - 1e-5f; boxes[id].hi[k] = cell.hi[k] + off[k] + 1e-5f; }
-      }
-  Bvh4 tlas = build_bvh4(boxes.data(), (uint32_t) boxes.size(), 1, 16);
-  Bvh4 blas = build_bvh4(tri_boxes.data(), nt, kBvhLeafMaxTri, 26);
-  if (tlas.nodes.empty() || blas.nodes.empty()) { ctx->error = "particle BVH exceeds the traversal's depth limits"; return 1; }
-  std::vector<Bvh4Node> nodes = tlas.nodes;
-  const uint32_t base = (uint32_t) nodes.size();
-  for (Bvh4Node n : blas.nodes) {
-    for (int k = 0; k < 4; k++) if (n.child[k] != kBvhEmpty && !(n.child[k] & kBvhLeafBit)) n.child[k] += base;
-    nodes.push_back(n);
-  }
-  std::vector<BvhTri> tris((size_t) nt + 1);
-  std::memset(tris.data(), 0, sizeof(BvhTri) * tris.size());
-  for (uint32_t i = 0; i < nt; i++) {
-    const uint32_t t = blas.prims[i];
-    tris[i] = bvh_tri(v->particle_vertices + (size_t) t * 12, t, t, kBvhTriNoTexture);
-  }
-  std::vector<float4> leaves(4 * tlas.prims.size() + 4);
-  for (size_t i = 0; i < tlas.prims.size(); i++) {
-    const uint32_t inst = tlas.prims[i];
-    leaves[4 * i + 0] = make_float4(1.0f, 0.0f, 0.0f, offsets[3 * inst + 0]);
-    leaves[4 * i + 1] = make_float4(0.0f, 1.0f, 0.0f, offsets[3 * inst + 1]);
-    leaves[4 * i + 2] = make_float4(0.0f, 0.0f, 1.0f, offsets[3 * inst + 2]);
-    const uint32_t words[4] = {inst, base, 0u, 0u};
-    std::memcpy(&leaves[4 * i + 3], words, 16);
-  }
-  if (upload(ctx, group, nodes.data(), nodes.size(), &sc.particle_bvh_nodes)) return 1;
-  if (upload(ctx, group, tris.data(), tris.size(), &sc.particle_tris)) return 1;
-  if (upload(ctx, group, leaves.data(), leaves.size(), &sc.particle_leaves)) return 1;
-  if (upload(ctx, group, (const float4*) v->particle_normals, (size_t) sc.particles_count, &sc.particle_normals)) return 1;
-  sc.particle_tlas_num_nodes = (uint32_t) tlas.nodes.size();
-  sc.particle_num_leaves = (uint32_t) (leaves.size() / 4);
-  ctx->particle_lds_nodes = (uint32_t) std::min<size_t>(ctx->lds_nodes, nodes.size());
-  return 0;
-}
-
-// ---- the scene on the device, part by part (scene_update below runs the parts in this order). A part frees what it allocated before; a part that is not
-// dirty keeps its device arrays and the fields of ctx->scene that point at them. ----
-static uint32_t total_triangles(const LumDeviceSceneView* v) { return v->num_meshes ? v->mesh_tri_offset[v->num_meshes] : 0; }
-
-static int update_mesh_arrays(LumContext* ctx, const LumDeviceSceneView* v) {
-  DeviceScene& sc = ctx->scene;
-  const uint32_t total_tris = total_triangles(v);
-  ctx->scene_allocs[LumContext::kGrpMesh].clear();
-  if (upload(ctx, LumContext::kGrpMesh, v->mesh_tri_offset, (size_t) v->num_meshes + 1, &sc.mesh_tri_offset)) return 1;
-  if (upload(ctx, LumContext::kGrpMesh, (const float4*) v->vertices, (size_t) total_tris * 3, &sc.vertices)) return 1;
-  return upload(ctx, LumContext::kGrpMesh, (const uint4*) v->tri_tex, (size_t) total_tris, &sc.tri_tex);
-}
-
-// (the scene tree's arrays - update_scene_tree - belong to this group too: whenever the instances are dirty both parts run, this one first)
-static int update_instance_arrays(LumContext* ctx, const LumDeviceSceneView* v) {
-  DeviceScene& sc = ctx->scene;
-  ctx->scene_allocs[LumContext::kGrpInst].clear();
-  if (upload(ctx, LumContext::kGrpInst, v->instance_mesh_ids, v->num_instances, &sc.instance_mesh_ids)) return 1;
-  return upload(ctx, LumContext::kGrpInst, (const float4*) v->instance_transforms, (size_t) v->num_instances * 2, &sc.instance_transforms);
-}
-
-static int update_materials(LumContext* ctx, const LumDeviceSceneView* v) {
-  ctx->scene_allocs[LumContext::kGrpMat].clear();
-  return upload(ctx, LumContext::kGrpMat, (const uint4*) v->materials, (size_t) v->num_materials * 2, &ctx->scene.materials);
-}
-
-// The light tree's root children as floats (dev_light.h tree_prepass): mean = byte * 2^e + base per axis, sigma = byte * 2^e_sigma, power = the 16-bit
-// integer - the operations the kernels used to perform per vertex (cuda/light_tree.cuh:133-161, :203-205), every one exact or a single
-// binary32 rounding, so the table holds the same bits (this translation unit is compiled without contraction).
-static int upload_light_root_children(LumContext* ctx, const LumDeviceSceneView* v, uint32_t sections) {
-  const uint32_t* h = (const uint32_t*) v->light_tree_root;
-  auto bf = [](uint32_t v16) { const uint32_t b = (v16 & 0xFFFFu) << 16; float f; std::memcpy(&f, &b, 4); return f; };
-  const float base[3] = {bf(h[0]), bf(h[0] >> 16), bf(h[1])};
-  const float ex[3] = {std::ldexp(1.0f, (int8_t) (h[3] & 0xFF)), std::ldexp(1.0f, (int8_t) ((h[3] >> 8) & 0xFF)), std::ldexp(1.0f, (int8_t) ((h[3] >> 16) & 0xFF))};
-  const float ev = std::ldexp(1.0f, (int8_t) (h[3] >> 24));
-  std::vector<float> table((size_t) sections * 8 * 8 + 16, 0.0f);  // + one pair of zeros: the pass reads two children per step
-  for (uint32_t s = 0; s < sections; s++) {
-    const uint8_t* sec = (const uint8_t*) (h + 4 + 12 * s);  // 8 x rel mean x, y, z, rel std dev, then 8 x u16 power
-    for (uint32_t c = 0; c < 8; c++) {
-      float* e = &table[((size_t) s * 8 + c) * 8];
-      for (int a = 0; a < 3; a++) { const float q = (float) sec[8 * a + c]; const float scaled = q * ex[a]; e[a] = scaled + base[a]; }
-      e[3] = (float) sec[24 + c] * ev;
-      uint16_t pw; std::memcpy(&pw, sec + 32 + 2 * c, 2);
-      e[4] = (float) pw;
-    }
-  }
-  return upload(ctx, LumContext::kGrpLight, table.data(), table.size(), &ctx->scene.light_root_children);
-}
-
-// (the light BVH and k_light_table's records - update_light_bvh, update_counts_and_tables - belong to this group too and run whenever this part does)
-static int update_light_tree(LumContext* ctx, const LumDeviceSceneView* v) {
-  DeviceScene& sc = ctx->scene;
-  ctx->scene_allocs[LumContext::kGrpLight].clear();
-  sc.light_tree_root = nullptr; sc.light_root_children = nullptr; sc.light_tree_nodes = nullptr; sc.light_tri_handles = nullptr; sc.light_tri_table = nullptr;
-  sc.light_nodes = nullptr; sc.light_tris = nullptr; sc.light_num_nodes = 0;
-  if (!v->light_tree_root || !v->num_lights) return 0;
-  const uint32_t sections = v->light_tree_root[10];
-  if (upload(ctx, LumContext::kGrpLight, (const uint4*) v->light_tree_root, (size_t) 1 + 3 * sections, &sc.light_tree_root)) return 1;
-  if (upload_light_root_children(ctx, v, sections)) return 1;
-  if (upload(ctx, LumContext::kGrpLight, (const uint4*) v->light_tree_nodes, (size_t) v->num_light_tree_nodes * 4, &sc.light_tree_nodes)) return 1;
-  return upload(ctx, LumContext::kGrpLight, (const uint2*) v->light_tri_handles, v->num_lights, &sc.light_tri_handles);
-}
-
-static int update_textures(LumContext* ctx, const LumDeviceSceneView* v) {
-  DeviceScene& sc = ctx->scene;
-  ctx->scene_allocs[LumContext::kGrpTex].clear();
-  sc.num_textures = 0; sc.texture_table = nullptr; sc.texels = nullptr;
-  if (!v->num_textures || !v->texture_table || !v->texels) return 0;
-  size_t texel_count = 0;
-  for (uint32_t t = 0; t < v->num_textures; t++)
-    texel_count = std::max(texel_count, (size_t) v->texture_table[4 * t] + (size_t) v->texture_table[4 * t + 1] * v->texture_table[4 * t + 2]);
-  if (upload(ctx, LumContext::kGrpTex, (const uint4*) v->texture_table, v->num_textures, &sc.texture_table)) return 1;
-  if (upload(ctx, LumContext::kGrpTex, v->texels, texel_count, &sc.texels)) return 1;
-  sc.num_textures = v->num_textures;
-  return 0;
-}
-
-// A mesh's tree from the process's cache, else built by the context's builder and entered there; null (ctx->error set) for a mesh no builder can take.
-static std::shared_ptr<const MeshTree> cached_or_built_mesh_tree(LumContext* ctx, const MeshTreeKey& key, const Aabb* tri_boxes, uint32_t nt) {
-  std::shared_ptr<const MeshTree> tree = find_mesh_tree(key);
-  if (tree) return tree;
-  auto built = std::make_shared<MeshTree>();
-  if (ctx->bvh_builder == 1) built->bvh = build_bvh4_lbvh(tri_boxes, nt, kBvhLeafMaxTri, 26);
-  else if (ctx->bvh_builder == 2) built->bvh = build_bvh4_ploc(tri_boxes, nt, kBvhLeafMaxTri, 26);
-  else if (ctx->bvh_builder == 3) built->bvh = build_bvh4_sah_gpu(tri_boxes, nt, kBvhLeafMaxTri, 26);
-  built->built_on_gpu = !built->bvh.nodes.empty();
-  if (!built->built_on_gpu) built->bvh = build_bvh4(tri_boxes, nt, kBvhLeafMaxTri, 26);  // the host builder: asked for, or the fallback for a mesh the GPU builders cannot take
-  if (built->bvh.nodes.empty()) { ctx->error = "mesh BVH exceeds 26 levels"; return nullptr; }
-  tree = built;
-  keep_mesh_tree(key, tree);
-  return tree;
-}
-
-// Every mesh's box, tree (from the process's cache, else built) and traversal triangles: the only part of an upload that takes long; an instance edit skips it.
-static int build_mesh_trees(LumContext* ctx, const LumDeviceSceneView* v, std::vector<BvhTri>& blas_tris) {
-  ctx->bvh_build_seconds = 0.0;
-  ctx->bvh_meshes_by_builder[0] = ctx->bvh_meshes_by_builder[1] = 0;
-  ctx->mesh_bvh.assign(v->num_meshes, nullptr);
-  ctx->mesh_box.assign(v->num_meshes, Aabb{});
-  ctx->mesh_refit.clear(); ctx->mesh_refit.resize(v->num_meshes);
-  ctx->mesh_tri_offset.assign(v->mesh_tri_offset, v->mesh_tri_offset + v->num_meshes + 1);
-  blas_tris.assign((size_t) total_triangles(v) + 1, BvhTri{});
-  for (uint32_t m = 0; m < v->num_meshes; m++) {
-    const uint32_t t0 = v->mesh_tri_offset[m], nt = v->mesh_tri_offset[m + 1] - t0;
-    const float* vertices = v->vertices + (size_t) t0 * 12;
-    std::vector<Aabb> tri_boxes(nt);
-    ctx->mesh_box[m] = mesh_triangle_boxes(vertices, nt, tri_boxes.data());
-    const auto t_build = std::chrono::steady_clock::now();
-    const MeshTreeKey key = mesh_tree_key(vertices, nt, ctx->bvh_builder);
-    std::shared_ptr<const MeshTree> tree = cached_or_built_mesh_tree(ctx, key, tri_boxes.data(), nt);
-    if (!tree) return 1;
-    ctx->bvh_meshes_by_builder[tree->built_on_gpu ? 1 : 0]++;
-    ctx->bvh_build_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_build).count();
-    fill_mesh_tris(vertices, t0, tree->bvh.prims.data(), nt, blas_tris.data() + t0);
-    ctx->mesh_bvh[m] = std::move(tree);
-    ctx->mesh_refit[m].fit_hash[0] = key.h0; ctx->mesh_refit[m].fit_hash[1] = key.h1;
-  }
-  return 0;
-}
-
-// LUMC_DIRTY_MESH_POSITIONS: the vertex arrays of the same meshes again - the traversal triangles stay on the device (update_mesh_arrays frees its group) -, then
-// every mesh whose vertices differ from those its held tree was fitted to gets a tree for them: refitted on the device (bvh_refit.hip; the tree becomes
-// private to this context, the shared one it came from is not touched and the cache never sees the refitted one) or, where the mode, the cost's growth or a
-// tree that cannot be refitted says so, from the cache / the builder like an upload. *rebuilt: a mesh's traversal triangles were written anew (k_tri_opacity).
-static int refit_mesh_trees(LumContext* ctx, const LumDeviceSceneView* v, bool* rebuilt) {
-  using clock = std::chrono::steady_clock;
-  auto since = [](clock::time_point t) { return std::chrono::duration<double>(clock::now() - t).count(); };
-  DeviceScene& sc = ctx->scene;
-  LumMeshRefitStats& st = ctx->refit_stats;
-  st.last_refits = st.last_rebuilds = 0; st.max_cost_growth = st.seconds = st.seconds_upload = st.seconds_refit = st.seconds_rebuild = st.seconds_assemble = 0.0;
-  st.seconds_hash = st.seconds_download = st.seconds_lights = 0.0;
-  *rebuilt = false;
-  if (ctx->mesh_bvh.size() != v->num_meshes || ctx->mesh_refit.size() != v->num_meshes || ctx->mesh_tri_offset.size() != (size_t) v->num_meshes + 1 ||
-      std::memcmp(ctx->mesh_tri_offset.data(), v->mesh_tri_offset, sizeof(uint32_t) * ((size_t) v->num_meshes + 1)) != 0) {
-    ctx->error = "lumc_scene_update: LUMC_DIRTY_MESH_POSITIONS with other meshes or triangle counts than the scene on the device";
-    return 1;
-  }
-  const auto t_all = clock::now();
-  auto& group = ctx->scene_allocs[LumContext::kGrpMesh];
-  DeviceBuffer<char> tris_buffer;
-  for (auto& b : group) if (b.get() == reinterpret_cast<const char*>(sc.blas_tris)) tris_buffer = std::move(b);
-  if (!tris_buffer) { ctx->error = "lumc_scene_update: the scene on the device has no traversal triangles"; return 1; }
-  BvhTri* d_tris = reinterpret_cast<BvhTri*>(tris_buffer.get());
-  const int failed = update_mesh_arrays(ctx, v);
-  group.push_back(std::move(tris_buffer));
-  if (failed) return 1;
-  HIP_TRY(ctx, hipDeviceSynchronize());
-  st.seconds_upload = since(t_all);
-  for (uint32_t m = 0; m < v->num_meshes; m++) {
-    const uint32_t t0 = v->mesh_tri_offset[m], nt = v->mesh_tri_offset[m + 1] - t0;
-    if (nt == 0) continue;
-    const float* vertices = v->vertices + (size_t) t0 * 12;
-    MeshRefit& mr = ctx->mesh_refit[m];
-    const auto t_hash = clock::now();
-    const MeshTreeKey key = mesh_tree_key(vertices, nt, ctx->bvh_builder);
-    st.seconds_hash += since(t_hash);
-    if (key.h0 == mr.fit_hash[0] && key.h1 == mr.fit_hash[1]) continue;  // the held tree fits these vertices
-    bool build = ctx->refit_mode == 1;
-    if (!build) {
-      const auto t_refit = clock::now();
-      if (mr.built_cost == 0.0) mr.built_cost = bvh4_cost(ctx->mesh_bvh[m]->bvh);  // (no refit yet: the held tree is the built one)
-      if (!mr.plan.nodes) {
-        const hipError_t e = refit_plan_create(mr.plan, ctx->mesh_bvh[m]->bvh, nt);
-        if (e == hipErrorInvalidValue) build = true;  // spatial splits: more references than triangles
-        else HIP_TRY(ctx, e);
-      }
-      if (!build) {
-        if (!mr.own) {
-          mr.own = std::make_shared<MeshTree>();
-          mr.own->bvh.prims = ctx->mesh_bvh[m]->bvh.prims; mr.own->bvh.max_depth = ctx->mesh_bvh[m]->bvh.max_depth; mr.own->built_on_gpu = ctx->mesh_bvh[m]->built_on_gpu;
-          mr.own->bvh.nodes.resize(mr.plan.num_nodes);
-        }
-        Aabb box;
-        double download = 0.0;
-        HIP_TRY(ctx, refit_run(mr.plan, sc.vertices + 3 * (size_t) t0, d_tris + t0, nullptr, mr.own->bvh.nodes.data(), &box, &download));
-        st.seconds_download += download;
-        const double growth = mr.built_cost > 0.0 ? bvh4_cost(mr.own->bvh) / mr.built_cost : 1.0;
-        st.max_cost_growth = std::max(st.max_cost_growth, growth);
-        if (ctx->refit_max_cost_growth > 0.0f && growth > (double) ctx->refit_max_cost_growth) build = true;
-        else { ctx->mesh_bvh[m] = mr.own; ctx->mesh_box[m] = box; st.refits++; st.last_refits++; }
-      }
-      st.seconds_refit += since(t_refit);
-    }
-    if (build) {
-      const auto t_build = clock::now();
-      std::vector<Aabb> tri_boxes(nt);
-      ctx->mesh_box[m] = mesh_triangle_boxes(vertices, nt, tri_boxes.data());
-      std::shared_ptr<const MeshTree> tree = cached_or_built_mesh_tree(ctx, key, tri_boxes.data(), nt);
-      if (!tree) return 1;
-      std::vector<BvhTri> tris(nt);
-      fill_mesh_tris(vertices, t0, tree->bvh.prims.data(), nt, tris.data());
-      HIP_TRY(ctx, hipMemcpy(d_tris + t0, tris.data(), sizeof(BvhTri) * nt, hipMemcpyHostToDevice));
-      mr.plan.reset(); mr.own.reset();
-      mr.built_cost = bvh4_cost(tree->bvh);
-      ctx->mesh_bvh[m] = std::move(tree);
-      *rebuilt = true;
-      st.rebuilds++; st.last_rebuilds++;
-      st.seconds_rebuild += since(t_build);
-    }
-    mr.fit_hash[0] = key.h0; mr.fit_hash[1] = key.h1;
-  }
-  st.seconds = since(t_all);
-  return 0;
-}
-
-// Top level + every mesh's tree in ONE node array (bvh_build.cpp assemble_scene_tree), in the instances' group; the traversal triangles in the meshes'.
-static int update_scene_tree(LumContext* ctx, const LumDeviceSceneView* v, bool dirty_meshes, size_t* num_nodes) {
-  DeviceScene& sc = ctx->scene;
-  std::vector<BvhTri> blas_tris;
-  if (dirty_meshes && build_mesh_trees(ctx, v, blas_tris)) return 1;
-  if (ctx->mesh_box.size() != v->num_meshes || ctx->mesh_bvh.size() != v->num_meshes) { ctx->error = "lumc_scene_update: the meshes changed but LUMC_DIRTY_MESHES is not set"; return 1; }
-  std::vector<const Bvh4*> mesh_bvh(v->num_meshes);
-  for (uint32_t m = 0; m < v->num_meshes; m++) mesh_bvh[m] = &ctx->mesh_bvh[m]->bvh;
-  const SceneTree tree = assemble_scene_tree(*v, mesh_bvh.data(), ctx->mesh_box.data());
-  if (tree.nodes.empty()) { ctx->error = "top-level BVH exceeds 16 levels"; return 1; }
-  if (total_triangles(v) >= (1u << 28) || tree.nodes.size() >= (1u << 25)) { ctx->error = "scene too large for 28-bit leaf ranges / 32-bit node offsets"; return 1; }
-  // by instance id: the exact flavour's ambient reuse re-tests a ray against a hit's triangle (k_resolve_reuse)
-  if (upload(ctx, LumContext::kGrpInst, tree.inv_rows.data(), tree.inv_rows.size(), &sc.instance_rows)) return 1;
-  if (upload(ctx, LumContext::kGrpInst, tree.nodes.data(), tree.nodes.size(), &sc.bvh_nodes)) return 1;
-  if (dirty_meshes && upload(ctx, LumContext::kGrpMesh, blas_tris.data(), blas_tris.size(), &sc.blas_tris)) return 1;
-  if (upload(ctx, LumContext::kGrpInst, tree.tlas_leaves.data(), tree.tlas_leaves.size(), &sc.tlas_leaves)) return 1;
-  sc.tlas_num_nodes = tree.tlas_num_nodes;
-  sc.tlas_num_leaves = (uint32_t) (tree.tlas_leaves.size() / 4);  // records that exist (one of padding included): what a workgroup may stage in LDS
-  std::memcpy(ctx->sort.world_lo, tree.world.lo, sizeof(ctx->sort.world_lo)); std::memcpy(ctx->sort.world_hi, tree.world.hi, sizeof(ctx->sort.world_hi));
-  ctx->bvh_stats[0] = tree.nodes.size() - tree.tlas_num_nodes;
-  ctx->bvh_stats[2] = tree.tlas_num_nodes;
-  *num_nodes = tree.nodes.size();
-  return 0;
-}
-
-// How many nodes of the scene tree's top every ray-kernel workgroup stages in LDS, and the kernels' dynamic LDS.
-static int update_ray_kernel_lds(LumContext* ctx, size_t num_nodes) {
-  // resident workgroups per CU share the LDS: what the device offers minus a margin, 128 B per node
-  hipDeviceProp_t prop;
-  HIP_TRY(ctx, hipGetDeviceProperties(&prop, ctx->device));
-  size_t lds_bytes = prop.maxSharedMemoryPerMultiProcessor ? prop.maxSharedMemoryPerMultiProcessor : prop.sharedMemPerBlock;
-  // the ray kernels are compiled for 128 VGPRs: 4 waves per SIMD = 16 waves per CU = one workgroup of kTraceBlock = 1024 threads (both flavours since round 4)
-  lds_bytes = std::min<size_t>(lds_bytes, 160 * 1024);
-  lds_bytes = lds_bytes > 16384 ? lds_bytes - 8192 : 0;  // margin: the ray kernels' static LDS (the staged top-level leaf records) and the runtime's own
-  lds_bytes = lds_bytes > LUM_LDS_STACK_BYTES ? lds_bytes - LUM_LDS_STACK_BYTES : 0;  // the stacks' share (dev_trace.h, TraversalStack)
-  ctx->lds_nodes = (uint32_t) std::min<size_t>(lds_bytes / kNodeBytes, num_nodes);
-  if (const char* e = getenv("LUM_LDS_NODES")) ctx->lds_nodes = std::min<uint32_t>((uint32_t) atoi(e), ctx->lds_nodes);
-  ctx->trace_blocks = (uint32_t) prop.multiProcessorCount;  // one workgroup of kTraceBlock threads per CU
-  // The attribute is a property of the kernel, not of a context: it is set to what the largest scene may ask for (the whole budget computed
-  // above), never to this scene's need - a second context with a small scene must not lower the cap a first one launches with.
-  const size_t dyn = lds_bytes + LUM_LDS_STACK_BYTES;
-  HIP_TRY(ctx, (hipError_t) wavefront_kernels_exact()->set_ray_kernel_lds(dyn));
-  HIP_TRY(ctx, (hipError_t) wavefront_kernels_fast()->set_ray_kernel_lds(dyn));
-  return 0;
-}
-
-// Light-only BVH (world-space triangles; reference: optix_bvh.c:382-478), in the light tree's group.
-static int update_light_bvh(LumContext* ctx, const LumDeviceSceneView* v) {
-  DeviceScene& sc = ctx->scene;
-  const uint32_t nl = (v->light_tree_root && v->light_bvh_tris) ? v->num_lights : 0;
-  std::vector<Aabb> boxes(nl);
-  for (uint32_t l = 0; l < nl; l++) { const float* p = v->light_bvh_tris + (size_t) l * 12; boxes[l] = tri_box(p, p + 4, p + 8); }
-  Bvh4 lb = build_bvh4(boxes.data(), nl, kBvhLeafMaxTri, 40);
-  if (lb.nodes.empty()) { ctx->error = "light BVH exceeds 40 levels"; return 1; }
-  std::vector<BvhTri> tris(nl ? nl : 1, BvhTri{});
-  for (uint32_t i = 0; i < nl; i++) tris[i] = bvh_tri(v->light_bvh_tris + (size_t) lb.prims[i] * 12, lb.prims[i], 0u, 0u);
-  if (upload(ctx, LumContext::kGrpLight, lb.nodes.data(), lb.nodes.size(), &sc.light_nodes)) return 1;
-  if (upload(ctx, LumContext::kGrpLight, tris.data(), tris.size(), &sc.light_tris)) return 1;
-  sc.light_num_nodes = (uint32_t) lb.nodes.size();
-  ctx->bvh_stats[3] = lb.nodes.size();
-  return 0;
-}
-
-constexpr unsigned kDirtyTrianglesRewritten = 1u << 30;  // scene_update's own: a LUMC_DIRTY_MESH_POSITIONS update built a mesh again, its traversal triangles are new
-
-// The counts, then what two kernels derive from the arrays above: k_tri_opacity (needs the materials and blas_tris), k_light_table (needs the counts).
-static int update_counts_and_tables(LumContext* ctx, const LumDeviceSceneView* v, unsigned dirty) {
-  DeviceScene& sc = ctx->scene;
-  const uint32_t total_tris = total_triangles(v);
-  const bool dirty_lights = (dirty & LUMC_DIRTY_LIGHTS) != 0;
-  ctx->bvh_stats[1] = total_tris;
-  sc.num_meshes = v->num_meshes; sc.num_instances = v->num_instances; sc.num_materials = v->num_materials; sc.num_lights = v->num_lights;  // (num_textures: update_textures)
-  if (total_tris && (dirty & (LUMC_DIRTY_MESHES | LUMC_DIRTY_MATERIALS | kDirtyTrianglesRewritten))) {  // the triangles' material words: texture id, or whether they stop a visibility ray on their own
-    hipLaunchKernelGGL(k_tri_opacity, dim3((total_tris + kBlock - 1) / kBlock), dim3(kBlock), 0, 0, sc, const_cast<BvhTri*>(sc.blas_tris), total_tris);
-    HIP_TRY(ctx, hipGetLastError());
-  }
-  if ((dirty_lights || ((dirty & (LUMC_DIRTY_MATERIALS | LUMC_DIRTY_INSTANCES | LUMC_DIRTY_MESHES)) && sc.light_tri_table)) && sc.light_tree_root && sc.num_lights) {  // the emissive triangles in world space with what their material says, one record per light (load_tri_light_table)
-    float4* table = const_cast<float4*>(sc.light_tri_table);  // a material edit alone refills the table in place (same lights)
-    if (dirty_lights) {
-      DeviceBuffer<char> records;
-      HIP_TRY(ctx, records.resize(sizeof(float4) * 4 * (size_t) sc.num_lights));
-      table = (float4*) records.get();
-      ctx->scene_allocs[LumContext::kGrpLight].push_back(std::move(records));
-    }
-    hipLaunchKernelGGL(k_light_table, dim3((sc.num_lights + kBlock - 1) / kBlock), dim3(kBlock), 0, 0, sc, table);
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipDeviceSynchronize());
-    sc.light_tri_table = table;
-  }
-  return 0;
-}
-
-// The scalar fields of the constants' part, with the pointers of that part reset (the functions after this one fill them in again).
-static int copy_constants(LumContext* ctx, const LumDeviceSceneView* v) {
-  DeviceScene& sc = ctx->scene;
-  sc.width = v->width; sc.height = v->height; sc.max_ray_depth = v->max_ray_depth; sc.shading_mode = v->shading_mode;
-  std::memcpy(sc.cam_pos, v->cam_pos, sizeof(sc.cam_pos));
-  std::memcpy(sc.cam_rotation, v->cam_rotation, sizeof(sc.cam_rotation));
-  sc.cam_fov = v->cam_fov; sc.cam_aperture_size = v->cam_aperture_size; sc.cam_object_distance = v->cam_object_distance;
-  sc.cam_scale = v->cam_scale; sc.cam_rr_threshold = v->cam_rr_threshold;
-  sc.cam_aperture_shape = v->cam_aperture_shape; sc.cam_aperture_blade_count = v->cam_aperture_blade_count;
-  sc.sky_mode = v->sky_mode;
-  std::memcpy(sc.sky_constant_color, v->sky_constant_color, sizeof(sc.sky_constant_color));
-  sc.sky_steps = v->sky_steps; sc.sky_ozone_absorption = v->sky_ozone_absorption;
-  std::memcpy(sc.sky_geometry_offset, v->sky_geometry_offset, sizeof(sc.sky_geometry_offset));
-  sc.sky_sun_strength = v->sky_sun_strength; sc.sky_base_density = v->sky_base_density; sc.sky_rayleigh_density = v->sky_rayleigh_density;
-  sc.sky_mie_density = v->sky_mie_density; sc.sky_ozone_density = v->sky_ozone_density; sc.sky_rayleigh_falloff = v->sky_rayleigh_falloff;
-  sc.sky_mie_falloff = v->sky_mie_falloff; sc.sky_ground_visibility = v->sky_ground_visibility; sc.sky_ozone_layer_thickness = v->sky_ozone_layer_thickness;
-  sc.sky_multiscattering_factor = v->sky_multiscattering_factor;
-  std::memcpy(sc.sky_sun_pos, v->sky_sun_pos, sizeof(sc.sky_sun_pos));
-  std::memcpy(sc.sky_mie_phase, v->sky_mie_phase, sizeof(sc.sky_mie_phase));
-  std::memcpy(sc.sky_moon_pos, v->sky_moon_pos, sizeof(sc.sky_moon_pos));
-  sc.sky_moon_tex_offset = v->sky_moon_tex_offset; sc.sky_stars_intensity = v->sky_stars_intensity;
-  sc.sky_moon_albedo_tex = v->sky_moon_albedo_tex; sc.sky_moon_normal_tex = v->sky_moon_normal_tex;
-  sc.sky_stars_count = 0; sc.sky_stars = nullptr; sc.sky_stars_offsets = nullptr;
-  sc.sky_lut_transmittance = nullptr; sc.sky_lut_multiscattering = nullptr;
-  sc.sky_hdri = nullptr; sc.sky_hdri_dim = 0;
-  sc.sky_aerial_perspective = v->sky_aerial_perspective;
-  // ---- fog ----
-  sc.fog_active = v->fog_active ? 1u : 0u;
-  sc.fog_density = v->fog_density; sc.fog_dist = v->fog_dist; sc.fog_height = v->fog_height;
-  std::memcpy(sc.fog_phase, v->fog_phase, sizeof(sc.fog_phase));
-  sc.bridge_max_num_vertices = v->bridge_max_num_vertices;
-  if (sc.fog_active && !(sc.fog_density > 0.0f)) { ctx->error = "lumc_scene_upload: fog needs a positive density"; return 1; }
-  // ---- ocean ----
-  sc.ocean_active = v->ocean_active ? 1u : 0u;
-  sc.ocean_height = v->ocean_height; sc.ocean_amplitude = v->ocean_amplitude; sc.ocean_frequency = v->ocean_frequency;
-  sc.ocean_refractive_index = v->ocean_refractive_index;
-  std::memcpy(sc.ocean_scattering, v->ocean_scattering, sizeof(sc.ocean_scattering));
-  std::memcpy(sc.ocean_absorption, v->ocean_absorption, sizeof(sc.ocean_absorption));
-  sc.ocean_molecular_weight = v->ocean_molecular_weight;
-  sc.ocean_caustics_active = v->ocean_caustics_active ? 1u : 0u;
-  sc.ocean_caustics_ris_sample_count = v->ocean_caustics_ris_sample_count;
-  sc.ocean_caustics_domain_scale = v->ocean_caustics_domain_scale;
-  sc.ocean_multiscattering = v->ocean_multiscattering ? 1u : 0u;
-  sc.ocean_triangle_light_contribution = v->ocean_triangle_light_contribution ? 1u : 0u;
-  if (sc.ocean_active && !(sc.ocean_refractive_index >= 1.0f)) { ctx->error = "lumc_scene_upload: the ocean needs a refractive index of at least 1"; return 1; }
-  // ---- clouds ----
-  sc.cloud_active = v->cloud_active ? 1u : 0u;
-  sc.cloud_atmosphere_scattering = v->cloud_atmosphere_scattering ? 1u : 0u;
-  sc.cloud_steps = v->cloud_steps & 0x3FFu; sc.cloud_shadow_steps = v->cloud_shadow_steps & 0x3FFu; sc.cloud_octaves = v->cloud_octaves & 0xFu;  // DeviceCloud's bit fields
-  sc.cloud_offset_x = v->cloud_offset_x; sc.cloud_offset_z = v->cloud_offset_z; sc.cloud_density = v->cloud_density;
-  sc.cloud_noise_shape_scale = v->cloud_noise_shape_scale; sc.cloud_noise_detail_scale = v->cloud_noise_detail_scale; sc.cloud_noise_weather_scale = v->cloud_noise_weather_scale;
-  std::memcpy(sc.cloud_phase, v->cloud_phase, sizeof(sc.cloud_phase));
-  std::memcpy(sc.cloud_layers, v->cloud_layers, sizeof(sc.cloud_layers));
-  sc.cloud_noise_shape = nullptr; sc.cloud_noise_detail = nullptr; sc.cloud_noise_weather = nullptr;
-  if (sc.cloud_active && (sc.cloud_steps == 0 || sc.cloud_shadow_steps == 0)) { ctx->error = "lumc_scene_upload: clouds need positive step counts"; return 1; }
-  // ---- particles ----
-  sc.particles_active = (v->particles_active && v->particles_count) ? 1u : 0u;
-  sc.particles_count = sc.particles_active ? v->particles_count : 0u;
-  sc.particles_scale = v->particles_scale; sc.particles_speed = v->particles_speed;
-  std::memcpy(sc.particles_albedo, v->particles_albedo, sizeof(sc.particles_albedo));
-  std::memcpy(sc.particles_direction, v->particles_direction, sizeof(sc.particles_direction));
-  std::memcpy(sc.particles_phase, v->particles_phase, sizeof(sc.particles_phase));
-  return 0;
-}
-
-static int update_stars(LumContext* ctx, const LumDeviceSceneView* v) {
-  DeviceScene& sc = ctx->scene;
-  if (!v->sky_stars || !v->sky_stars_offsets || !v->sky_stars_count) return 0;
-  if (upload(ctx, LumContext::kGrpConst, (const float4*) v->sky_stars, (size_t) v->sky_stars_count, &sc.sky_stars)) return 1;
-  if (upload(ctx, LumContext::kGrpConst, v->sky_stars_offsets, (size_t) 64 * 32 + 1, &sc.sky_stars_offsets)) return 1;
-  sc.sky_stars_count = v->sky_stars_count;
-  return 0;
-}
-
-// The clouds' noise textures: the caller's three, or the context's own (ensure_cloud_noise).
-static int update_cloud_noise(LumContext* ctx, const LumDeviceSceneView* v) {
-  DeviceScene& sc = ctx->scene;
-  if (!sc.cloud_active) return 0;
-  if (v->cloud_noise_shape && v->cloud_noise_detail && v->cloud_noise_weather) {
-    if (upload(ctx, LumContext::kGrpConst, (const uint32_t*) v->cloud_noise_shape, kCloudNoiseTexels[0], &sc.cloud_noise_shape)) return 1;
-    if (upload(ctx, LumContext::kGrpConst, (const uint32_t*) v->cloud_noise_detail, kCloudNoiseTexels[1], &sc.cloud_noise_detail)) return 1;
-    return upload(ctx, LumContext::kGrpConst, (const uint32_t*) v->cloud_noise_weather, kCloudNoiseTexels[2], &sc.cloud_noise_weather);
-  }
-  if (ensure_cloud_noise(ctx, v->cloud_seed)) return 1;
-  sc.cloud_noise_shape = ctx->d_cloud_noise[0].get(); sc.cloud_noise_detail = ctx->d_cloud_noise[1].get(); sc.cloud_noise_weather = ctx->d_cloud_noise[2].get();
-  return 0;
-}
-
-static int update_particles(LumContext* ctx, const LumDeviceSceneView* v) {
-  ctx->scene_allocs[LumContext::kGrpPart].clear();
-  return build_particle_tree(ctx, LumContext::kGrpPart, v, ctx->scene);
-}
-
-// Sky look-up tables: the caller's or generated here (device/device_sky.c:64-200); not for a constant sky (HDRI mode bakes from them and samples the sun through them).
-static int update_sky_tables(LumContext* ctx, const LumDeviceSceneView* v) {
-  DeviceScene& sc = ctx->scene;
-  if (sc.sky_mode == kSkyConstantColor) return 0;
-  const size_t tm_texels = 2 * (size_t) kSkyTmWidth * kSkyTmHeight, ms_texels = 2 * (size_t) kSkyMsSize * kSkyMsSize;
-  if (v->sky_lut_transmittance && v->sky_lut_multiscattering) {
-    if (upload(ctx, LumContext::kGrpConst, (const float4*) v->sky_lut_transmittance, tm_texels, &sc.sky_lut_transmittance)) return 1;
-    if (upload(ctx, LumContext::kGrpConst, (const float4*) v->sky_lut_multiscattering, ms_texels, &sc.sky_lut_multiscattering)) return 1;
-    ctx->sky_lut_key.clear();
-    return 0;
-  }
-  // the two tables are functions of the atmosphere's parameters alone (sky.cuh:110-176, :186-332): a camera move or a sun move keeps them
-  std::vector<uint32_t> key;
-  auto put = [&](const void* p, size_t bytes) { const size_t at = key.size(); key.resize(at + (bytes + 3) / 4, 0u); std::memcpy(key.data() + at, p, bytes); };
-  put(&sc.sky_ozone_absorption, sizeof(sc.sky_ozone_absorption));
-  const float params[] = {sc.sky_base_density, sc.sky_rayleigh_density, sc.sky_mie_density, sc.sky_ozone_density, sc.sky_rayleigh_falloff, sc.sky_mie_falloff,
-                          sc.sky_ground_visibility, sc.sky_ozone_layer_thickness, sc.sky_multiscattering_factor, sc.sky_sun_strength};
-  put(params, sizeof(params)); put(sc.sky_mie_phase, sizeof(sc.sky_mie_phase)); put(sc.sky_sun_pos, sizeof(sc.sky_sun_pos)); put(sc.sky_geometry_offset, sizeof(sc.sky_geometry_offset));
-  if (!ctx->d_sky_lut[0]) {
-    HIP_TRY(ctx, ctx->d_sky_lut[0].resize(tm_texels));
-    HIP_TRY(ctx, ctx->d_sky_lut[1].resize(ms_texels));
-    ctx->sky_lut_key.clear();
-  }
-  if (key != ctx->sky_lut_key) {
-    hipLaunchKernelGGL(k_sky_transmittance_lut, dim3((kSkyTmWidth * kSkyTmHeight + 63) / 64), dim3(64), 0, 0, sc, ctx->d_sky_lut[0].get());
-    sc.sky_lut_transmittance = ctx->d_sky_lut[0].get();  // the multiscattering integration reads the finished transmittance table
-    hipLaunchKernelGGL(k_sky_multiscattering_lut, dim3(kSkyMsSize, kSkyMsSize), dim3(kSkyMsIter), 0, 0, sc, ctx->d_sky_lut[1].get());
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipDeviceSynchronize());
-    ctx->sky_lut_key = key;
-  }
-  sc.sky_lut_transmittance = ctx->d_sky_lut[0].get();
-  sc.sky_lut_multiscattering = ctx->d_sky_lut[1].get();
-  return 0;
-}
-
-// BSDF energy tables: taken from the caller or generated here (device/device_bsdf.c:64-130).
-static int update_bsdf_tables(LumContext* ctx, const LumDeviceSceneView* v, bool full_upload) {
-  DeviceScene& sc = ctx->scene;
-  const uint16_t* host_luts[4] = {v->lut_conductor, v->lut_glossy, v->lut_dielectric, v->lut_dielectric_inv};
-  const bool have_luts = bool(ctx->d_luts[0]);
-  for (int t = 0; t < 4 && !have_luts; t++) HIP_TRY(ctx, ctx->d_luts[t].resize(kBsdfLutCount[t]));
-  if (have_luts && !full_upload) { /* a partial update keeps the tables the context renders with */ }
-  else if (host_luts[0] && host_luts[1] && host_luts[2] && host_luts[3]) {
-    for (int t = 0; t < 4; t++) HIP_TRY(ctx, hipMemcpy(ctx->d_luts[t].get(), host_luts[t], sizeof(uint16_t) * kBsdfLutCount[t], hipMemcpyHostToDevice));
-  }
-  else {
-    // The tables are a function of the embedded blue-noise mask alone (65 536 samples per texel, one thread per texel: 0.29 s of GPU time):
-    // generated once per process, every later upload copies them.
-    static std::mutex lut_mutex;
-    static std::vector<uint16_t> lut_cache[4];
-    static std::vector<uint32_t> lut_cache_mask;
-    std::lock_guard<std::mutex> lock(lut_mutex);
-    const bool cached = !lut_cache[0].empty() && lut_cache_mask.size() == 65536 && std::memcmp(lut_cache_mask.data(), v->bluenoise_2d, sizeof(uint32_t) * 65536) == 0;
-    if (cached) {
-      for (int t = 0; t < 4; t++) HIP_TRY(ctx, hipMemcpy(ctx->d_luts[t].get(), lut_cache[t].data(), sizeof(uint16_t) * kBsdfLutCount[t], hipMemcpyHostToDevice));
-    }
-    else {
-      // the two big tables and the conductor table are independent: side by side on three streams; the glossy table divides by the conductor's
-      hipStream_t streams[3];
-      for (auto& st : streams) HIP_TRY(ctx, hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-      const int first_wave[3] = {0, 2, 3};
-      for (int k = 0; k < 3; k++) {
-        const int t = first_wave[k];
-        hipLaunchKernelGGL(k_generate_lut, dim3((kBsdfLutCount[t] + 63) / 64), dim3(64), 0, streams[k], sc.bluenoise_2d, t, kBsdfLutCount[t], ctx->d_luts[0].get(), ctx->d_luts[t].get());
-      }
-      hipLaunchKernelGGL(k_generate_lut, dim3((kBsdfLutCount[1] + 63) / 64), dim3(64), 0, streams[0], sc.bluenoise_2d, 1, kBsdfLutCount[1], ctx->d_luts[0].get(), ctx->d_luts[1].get());
-      HIP_TRY(ctx, hipGetLastError());
-      for (auto& st : streams) { HIP_TRY(ctx, hipStreamSynchronize(st)); (void) hipStreamDestroy(st); }
-      for (int t = 0; t < 4; t++) {
-        lut_cache[t].resize(kBsdfLutCount[t]);
-        HIP_TRY(ctx, hipMemcpy(lut_cache[t].data(), ctx->d_luts[t].get(), sizeof(uint16_t) * kBsdfLutCount[t], hipMemcpyDeviceToHost));
-      }
-      lut_cache_mask.assign(v->bluenoise_2d, v->bluenoise_2d + 65536);
-    }
-  }
-  sc.lut_conductor = ctx->d_luts[0].get(); sc.lut_glossy = ctx->d_luts[1].get(); sc.lut_dielectric = ctx->d_luts[2].get(); sc.lut_dielectric_inv = ctx->d_luts[3].get();
-  return 0;
-}
-
-// Sky panorama (HDRI mode): the caller's, or baked here from the procedural sky as the reference's device manager does when the sky changes
-// (device_manager.c:351-366, device_sky.c:249-366); lumc_sky_hdri_build re-bakes on request.
-static int update_sky_panorama(LumContext* ctx, const LumDeviceSceneView* v) {
-  DeviceScene& sc = ctx->scene;
-  if (sc.sky_mode != kSkyHdri) return 0;
-  if (v->sky_hdri && v->sky_hdri_dim) {
-    if (upload(ctx, LumContext::kGrpConst, (const float4*) v->sky_hdri, (size_t) v->sky_hdri_dim * v->sky_hdri_dim, &sc.sky_hdri)) return 1;
-    sc.sky_hdri_dim = v->sky_hdri_dim;
-    return 0;
-  }
-  ctx->has_scene = true;  // the bake renders this scene's sky
-  if (lumc_sky_hdri_build(ctx, v->sky_hdri_origin, v->sky_hdri_dim, v->sky_hdri_samples ? v->sky_hdri_samples : 1u)) { ctx->has_scene = false; return 1; }
-  return 0;
-}
-
-// Camera, settings, sky, fog, ocean, clouds, particles: the kernels' scalar arguments and the tables derived from them.
-static int update_constants(LumContext* ctx, const LumDeviceSceneView* v, unsigned dirty) {
-  ctx->scene_allocs[LumContext::kGrpConst].clear();
-  if (copy_constants(ctx, v)) return 1;
-  if (update_stars(ctx, v)) return 1;
-  if (update_cloud_noise(ctx, v)) return 1;
-  if ((dirty & LUMC_DIRTY_PARTICLES) && update_particles(ctx, v)) return 1;
-  if (update_sky_tables(ctx, v)) return 1;
-  if (update_bsdf_tables(ctx, v, dirty == LUMC_DIRTY_ALL)) return 1;
-  return update_sky_panorama(ctx, v);
-}
-
-// Bridges to emissive triangles (fog, or an ocean with triangle_light_contribution): the vertex-count table. Decided after EVERY update, not only when
-// the constants are dirty: a material that becomes emissive (MATERIALS | LIGHTS) gives a fogged scene its first light, and bridges_vertex_count_importance
-// reads the table without a check. The table lives in the context (5 KB, uploaded once per content).
-static int update_bridge_table(LumContext* ctx, const LumDeviceSceneView* v) {
-  DeviceScene& sc = ctx->scene;
-  sc.bridge_lut = nullptr;
-  if (!((sc.fog_active || (sc.ocean_active && sc.ocean_triangle_light_contribution)) && sc.num_lights > 0 && sc.light_tree_root)) return 0;
-  if (!v->bridge_lut) { ctx->error = sc.fog_active ? "lumc_scene_upload: fog with emissive triangles needs bridge_lut" : "lumc_scene_upload: an ocean lit by emissive triangles needs bridge_lut"; return 1; }
-  if (sc.bridge_max_num_vertices == 0) { ctx->error = "lumc_scene_upload: bridge_max_num_vertices must be at least 1"; return 1; }
-  const size_t n = (size_t) 64 * 21;
-  if (!ctx->d_bridge_lut || ctx->bridge_lut_host.size() != n || std::memcmp(ctx->bridge_lut_host.data(), v->bridge_lut, n * sizeof(float)) != 0) {
-    if (!ctx->d_bridge_lut) HIP_TRY(ctx, ctx->d_bridge_lut.resize(n));
-    HIP_TRY(ctx, hipMemcpy(ctx->d_bridge_lut.get(), v->bridge_lut, n * sizeof(float), hipMemcpyHostToDevice));
-    ctx->bridge_lut_host.assign(v->bridge_lut, v->bridge_lut + n);
-  }
-  sc.bridge_lut = ctx->d_bridge_lut.get();
-  return 0;
-}
-
-// The scene on the device: the dirty parts, in the order their kernels and uploads depend on. Until the update has gone through the context has no scene.
-static int scene_update(LumContext* ctx, const LumDeviceSceneView* v, unsigned dirty) {
-  ctx->guides_valid = false;  // the denoiser's guides were rendered from the scene as it was
-  DeviceScene& sc = ctx->scene;
-  if (!v->bluenoise_2d) { ctx->error = "scene has no blue-noise mask"; return 1; }
-  if (v->max_ray_depth > 63) { ctx->error = "max_ray_depth exceeds 63 (6-bit field, device_structs.h:9)"; return 1; }
-  if (dirty & LUMC_DIRTY_MESHES) dirty &= ~(unsigned) LUMC_DIRTY_MESH_POSITIONS;  // a full rebuild of the meshes covers moved vertices
-  if (dirty & (LUMC_DIRTY_MESHES | LUMC_DIRTY_MESH_POSITIONS)) dirty |= LUMC_DIRTY_INSTANCES;  // the assembled node array holds the per-mesh trees
-  if (dirty & LUMC_DIRTY_PARTICLES) dirty |= LUMC_DIRTY_CONSTANTS;
-  const bool meshes = (dirty & LUMC_DIRTY_MESHES) != 0, instances = (dirty & LUMC_DIRTY_INSTANCES) != 0, lights = (dirty & LUMC_DIRTY_LIGHTS) != 0;
-  ctx->has_scene = false;
-  if (meshes && update_mesh_arrays(ctx, v)) return 1;
-  if (dirty & LUMC_DIRTY_MESH_POSITIONS) {
-    bool rebuilt = false;
-    if (refit_mesh_trees(ctx, v, &rebuilt)) return 1;
-    if (rebuilt) dirty |= kDirtyTrianglesRewritten;
-  }
-  if (instances && update_instance_arrays(ctx, v)) return 1;
-  if ((dirty & LUMC_DIRTY_MATERIALS) && update_materials(ctx, v)) return 1;
-  const bool time_lights = (dirty & LUMC_DIRTY_MESH_POSITIONS) != 0;
-  auto lights_since = [&](std::chrono::steady_clock::time_point t) { if (time_lights) ctx->refit_stats.seconds_lights += std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count(); };
-  auto t_lights = std::chrono::steady_clock::now();
-  if (lights && update_light_tree(ctx, v)) return 1;
-  lights_since(t_lights);
-  if (!sc.bluenoise_2d && upload(ctx, LumContext::kGrpOnce, v->bluenoise_2d, 65536, &sc.bluenoise_2d)) return 1;
-  if ((dirty & LUMC_DIRTY_TEXTURES) && update_textures(ctx, v)) return 1;
-  size_t num_nodes = 0;
-  const auto t_assemble = std::chrono::steady_clock::now();
-  if (instances && (update_scene_tree(ctx, v, meshes, &num_nodes) || update_ray_kernel_lds(ctx, num_nodes))) return 1;
-  if (dirty & LUMC_DIRTY_MESH_POSITIONS) ctx->refit_stats.seconds_assemble = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_assemble).count();
-  t_lights = std::chrono::steady_clock::now();
-  if (lights && update_light_bvh(ctx, v)) return 1;
-  if (update_counts_and_tables(ctx, v, dirty)) return 1;
-  lights_since(t_lights);
-  if ((dirty & LUMC_DIRTY_CONSTANTS) && update_constants(ctx, v, dirty)) return 1;
-  if (update_bridge_table(ctx, v)) return 1;
-  // the moon's texture ids follow the texture pool (the host layer appends the two moon textures behind the scene's own): an added texture moves them
-  sc.sky_moon_albedo_tex = v->sky_moon_albedo_tex; sc.sky_moon_normal_tex = v->sky_moon_normal_tex;
-  ctx->has_scene = true;
-  return 0;
-}
-
-int lumc_scene_upload(LumContext* ctx, const LumDeviceSceneView* v) {
-  if (!ctx || !v) return 1;
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  free_scene(ctx);
-  std::memset(&ctx->scene, 0, sizeof(ctx->scene));
-  return scene_update(ctx, v, LUMC_DIRTY_ALL);
-}
-
-int lumc_scene_update(LumContext* ctx, const LumDeviceSceneView* v, unsigned int dirty) {
-  if (!ctx || !v) return 1;
-  if (!ctx->has_scene || (dirty & LUMC_DIRTY_ALL) == LUMC_DIRTY_ALL) return lumc_scene_upload(ctx, v);
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  HIP_TRY(ctx, hipDeviceSynchronize());  // nothing renders from the arrays that are about to be freed
-  if (scene_update(ctx, v, dirty & (LUMC_DIRTY_ALL | LUMC_DIRTY_MESH_POSITIONS))) { free_scene(ctx); return 1; }  // a failed partial update leaves no half-updated scene behind
-  return 0;
-}
-
-int lumc_set_mesh_refit(LumContext* ctx, uint32_t mode, float max_cost_growth) {
-  if (!ctx) return 1;
-  if (mode > 1 || !(max_cost_growth >= 0.0f) || !std::isfinite(max_cost_growth)) { ctx->error = "lumc_set_mesh_refit: mode is 0 or 1, max_cost_growth >= 0"; return 1; }
-  ctx->refit_mode = mode; ctx->refit_max_cost_growth = max_cost_growth;
-  return 0;
-}
-
-int lumc_mesh_refit_stats(const LumContext* ctx, LumMeshRefitStats* out) {
-  if (!ctx || !out) return 1;
-  *out = ctx->refit_stats;
-  return 0;
-}
-
-int lumc_download_luts(LumContext* ctx, uint16_t* conductor, uint16_t* glossy, uint16_t* dielectric, uint16_t* dielectric_inv) {
-  if (!ctx || !ctx->has_scene) return 1;
-  uint16_t* dst[4] = {conductor, glossy, dielectric, dielectric_inv};
-  for (int t = 0; t < 4; t++)
-    if (dst[t]) HIP_TRY(ctx, hipMemcpy(dst[t], ctx->d_luts[t].get(), sizeof(uint16_t) * kBsdfLutCount[t], hipMemcpyDeviceToHost));
-  return 0;
-}
-
-int lumc_download_sky_luts(LumContext* ctx, float* transmittance, float* multiscattering) {
-  if (!ctx || !ctx->has_scene || !ctx->scene.sky_lut_transmittance) { if (ctx) ctx->error = "lumc_download_sky_luts: the scene has no procedural sky"; return 1; }
-  if (transmittance) HIP_TRY(ctx, hipMemcpy(transmittance, ctx->scene.sky_lut_transmittance, sizeof(float4) * 2 * kSkyTmWidth * kSkyTmHeight, hipMemcpyDeviceToHost));
-  if (multiscattering) HIP_TRY(ctx, hipMemcpy(multiscattering, ctx->scene.sky_lut_multiscattering, sizeof(float4) * 2 * kSkyMsSize * kSkyMsSize, hipMemcpyDeviceToHost));
-  return 0;
-}
-
-// Everything the bake reads: the sky's parameters (not its tables: they are functions of the parameters), the star field's size, the moon.
-static std::vector<uint32_t> sky_hdri_key(const DeviceScene& sc, uint32_t ctx_cloud_seed, const float origin[3], uint32_t dim, uint32_t samples) {
-  std::vector<uint32_t> key;
-  auto put = [&](const void* p, size_t bytes) { const size_t at = key.size(); key.resize(at + (bytes + 3) / 4, 0u); std::memcpy(key.data() + at, p, bytes); };
-  put(&sc.sky_steps, sizeof(sc.sky_steps)); put(&sc.sky_ozone_absorption, sizeof(sc.sky_ozone_absorption));
-  put(sc.sky_geometry_offset, sizeof(sc.sky_geometry_offset));
-  const float params[] = {sc.sky_sun_strength, sc.sky_base_density, sc.sky_rayleigh_density, sc.sky_mie_density, sc.sky_ozone_density, sc.sky_rayleigh_falloff, sc.sky_mie_falloff,
-                          sc.sky_ground_visibility, sc.sky_ozone_layer_thickness, sc.sky_multiscattering_factor, sc.sky_moon_tex_offset, sc.sky_stars_intensity};
-  put(params, sizeof(params));
-  put(sc.sky_sun_pos, sizeof(sc.sky_sun_pos)); put(sc.sky_mie_phase, sizeof(sc.sky_mie_phase)); put(sc.sky_moon_pos, sizeof(sc.sky_moon_pos));
-  put(&sc.sky_stars_count, sizeof(sc.sky_stars_count));
-  put(&sc.cloud_active, sizeof(sc.cloud_active));
-  if (sc.cloud_active) {  // the clouds are baked in (sky_hdri.cuh:88-92)
-    const uint32_t ints[] = {sc.cloud_atmosphere_scattering, sc.cloud_steps, sc.cloud_shadow_steps, sc.cloud_octaves};
-    const float floats[] = {sc.cloud_offset_x, sc.cloud_offset_z, sc.cloud_density, sc.cloud_noise_shape_scale, sc.cloud_noise_detail_scale, sc.cloud_noise_weather_scale};
-    put(ints, sizeof(ints)); put(floats, sizeof(floats)); put(sc.cloud_phase, sizeof(sc.cloud_phase)); put(sc.cloud_layers, sizeof(sc.cloud_layers));
-    const uint64_t tex[] = {(uint64_t) (uintptr_t) sc.cloud_noise_shape, (uint64_t) (uintptr_t) sc.cloud_noise_weather, (uint64_t) ctx_cloud_seed};
-    put(tex, sizeof(tex));
-  }
-  put(origin, 3 * sizeof(float)); put(&dim, sizeof(dim)); put(&samples, sizeof(samples));
-  return key;
-}
-
-int lumc_sky_hdri_build(LumContext* ctx, const float origin[3], uint32_t dim, uint32_t samples) {
-  if (!ctx || !origin || !ctx->has_scene || !ctx->scene.sky_lut_transmittance) { if (ctx) ctx->error = "lumc_sky_hdri_build: the scene has no atmosphere (constant-colour sky)"; return 1; }
-  if (dim < 2 || dim > 16384 || samples == 0) { ctx->error = "lumc_sky_hdri_build: dim must be in [2, 16384] and samples positive"; return 1; }
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  std::vector<uint32_t> key = sky_hdri_key(ctx->scene, ctx->cloud_noise_seed, origin, dim, samples);
-  if (ctx->d_sky_hdri && key == ctx->sky_hdri_key) {
-    if (ctx->scene.sky_mode == kSkyHdri) { ctx->scene.sky_hdri = ctx->d_sky_hdri.get(); ctx->scene.sky_hdri_dim = dim; }
-    return 0;
-  }
-  ctx->sky_hdri_key.clear();
-  if (ctx->d_sky_hdri.count() != (size_t) dim * dim) HIP_TRY(ctx, ctx->d_sky_hdri.resize((size_t) dim * dim));
-  ctx->sky_hdri_dim = dim;
-  const uint64_t threads = (uint64_t) dim * dim * 32u;
-  hipLaunchKernelGGL(k_sky_hdri, dim3((uint32_t) ((threads + 255) / 256)), dim3(256), 0, 0, ctx->scene, origin[0], origin[1], origin[2], dim, samples, ctx->d_sky_hdri.get());
-  HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipDeviceSynchronize());
-  ctx->sky_hdri_key = std::move(key);
-  if (ctx->scene.sky_mode == kSkyHdri) { ctx->scene.sky_hdri = ctx->d_sky_hdri.get(); ctx->scene.sky_hdri_dim = dim; }
-  return 0;
-}
-
-int lumc_sky_hdri_download(LumContext* ctx, float* rgba, uint32_t* dim) {
-  if (!ctx || !ctx->d_sky_hdri) { if (ctx) ctx->error = "lumc_sky_hdri_download: no baked sky"; return 1; }
-  if (dim) *dim = ctx->sky_hdri_dim;
-  if (rgba) HIP_TRY(ctx, hipMemcpy(rgba, ctx->d_sky_hdri.get(), sizeof(float4) * (size_t) ctx->sky_hdri_dim * ctx->sky_hdri_dim, hipMemcpyDeviceToHost));
-  return 0;
-}
 
 // FNV-1a over a pixel list (null: 0, 1, 2 ... n - 1): the identity of a context's pixel set and of its ORDER
 uint64_t pixel_list_hash(const uint32_t* pixels, uint32_t n) {
@@ -1112,28 +229,34 @@ static void prepare_sobol_table(LumContext* ctx, hipStream_t stream, DeviceScene
 static size_t ray_kernel_lds(const LumContext* ctx) { return (size_t) ctx->lds_nodes * kNodeBytes + LUM_LDS_STACK_BYTES; }
 static bool render_volumes(const DeviceScene& sc) { return sc.fog_active || sc.ocean_active; }  // device_manager.c:478
 
-// Debug shading modes: one closest-hit pass and a colour per path (device_renderer.c:136-181)
-static void debug_pass(LumContext* ctx, hipStream_t stream, const DeviceScene& sc, uint32_t N) {
+// The first hits of the camera rays in queue[0], where nothing else happens between the passes (the depth loop has closest_hits and media_passes): surfaces, particles, ocean.
+static void first_hits(LumContext* ctx, hipStream_t stream, const DeviceScene& sc, uint32_t N) {
   const WavefrontKernels& wf = *ctx->wf;
   {
     Launch l(ctx, stream, LUMC_KERNEL_TRACE);
-    wf.trace(grid_persistent(ctx, N), ray_kernel_lds(ctx), stream, sc, ctx->queue[0], nullptr, ctx->d_ctrl.get(), ctx->d_counters.get(), ctx->lds_nodes);
+    wf.trace(grid_persistent(ctx, N), ray_kernel_lds(ctx), stream, sc, ctx->work.queue[0], nullptr, ctx->d_ctrl.get(), ctx->d_counters.get(), ctx->lds_nodes);
   }
-  if (sc.particles_active) trace_particles(ctx, stream, ctx->queue[0], ctx->d_ctrl.get(), N);
+  if (sc.particles_active) trace_particles(ctx, stream, ctx->work.queue[0], ctx->d_ctrl.get(), N);
   if (sc.ocean_active) {
     Launch l(ctx, stream, LUMC_KERNEL_TRACE);
-    wf.trace_ocean(grid_for(N), stream, sc, ctx->queue[0], (const uint32_t*) ctx->d_ctrl.get());
+    wf.trace_ocean(grid_for(N), stream, sc, ctx->work.queue[0], (const uint32_t*) ctx->d_ctrl.get());
   }
+}
+
+// Debug shading modes: one closest-hit pass and a colour per path (device_renderer.c:136-181)
+static void debug_pass(LumContext* ctx, hipStream_t stream, const DeviceScene& sc, uint32_t N) {
+  const WavefrontKernels& wf = *ctx->wf;
+  first_hits(ctx, stream, sc, N);
   if (render_volumes(sc)) {  // the debug queue keeps volume_process_events (device_renderer.c:145-147)
     Launch l(ctx, stream, LUMC_KERNEL_VOLUME);
-    wf.volume_events(grid_for(N), stream, sc, ctx->queue[0], ctx->volume, ctx->d_results, ctx->d_ctrl.get(), 0u);
+    wf.volume_events(grid_for(N), stream, sc, ctx->work.queue[0], ctx->work.volume, ctx->work.results, ctx->d_ctrl.get(), 0u);
   }
   if (sc.sky_aerial_perspective && sc.sky_mode != kSkyConstantColor) {  // the debug queue keeps the in-scattering events (device_renderer.c:150-154)
     Launch l(ctx, stream, LUMC_KERNEL_SKY);
-    wf.sky_inscattering(grid_for(N), stream, sc, ctx->queue[0], ctx->d_results, (const uint32_t*) ctx->d_ctrl.get(), 0u);
+    wf.sky_inscattering(grid_for(N), stream, sc, ctx->work.queue[0], ctx->work.results, (const uint32_t*) ctx->d_ctrl.get(), 0u);
   }
   Launch l(ctx, stream, LUMC_KERNEL_SHADE);
-  wf.shade_debug(grid_for(N), stream, sc, ctx->queue[0], ctx->d_results, (const uint32_t*) ctx->d_ctrl.get());
+  wf.shade_debug(grid_for(N), stream, sc, ctx->work.queue[0], ctx->work.results, (const uint32_t*) ctx->d_ctrl.get());
 }
 
 // How the vertices of a depth get their sums (the visibility answers applied to the NEE records):
@@ -1168,8 +291,8 @@ static DepthBuffers depth_buffers(LumContext* ctx, ResolveScheme scheme, uint32_
   const bool second_set = fused && (depth & 1u);
   // the sampler's depth constant is not advanced before the last pass (device_renderer.c:126-130)
   const uint32_t depth_const = (depth == max_depth && depth > 0) ? depth - 1 : depth;
-  return DepthBuffers{ctx->queue[cur], ctx->queue[next_q], ctx->queue[prev_q], second_set ? ctx->nee2 : ctx->nee, second_set ? ctx->nee : ctx->nee2,
-                      ctx->d_ctrl.get() + kCtlStride * depth, fused ? ctx->d_fused + depth % 6u : nullptr, fused ? ctx->d_ended[depth & 1u] : nullptr, depth, depth_const,
+  return DepthBuffers{ctx->work.queue[cur], ctx->work.queue[next_q], ctx->work.queue[prev_q], second_set ? ctx->fused.nee : ctx->work.nee, second_set ? ctx->work.nee : ctx->fused.nee,
+                      ctx->d_ctrl.get() + kCtlStride * depth, fused ? ctx->fused.records + depth % 6u : nullptr, fused ? ctx->fused.ended[depth & 1u] : nullptr, depth, depth_const,
                       depth == max_depth};
 }
 
@@ -1187,14 +310,14 @@ static int closest_hits(LumContext* ctx, hipStream_t stream, const DeviceScene& 
     uint32_t* prev = d.ctrl - kCtlStride;
     {
       Launch l(ctx, stream, LUMC_KERNEL_RESOLVE);
-      wf.resolve_reuse(grid_for(N), stream, sc, d.prev, d.cur, d.nee, ctx->shadow, ctx->d_results, prev, ctx->d_counters.get());
+      wf.resolve_reuse(grid_for(N), stream, sc, d.prev, d.cur, d.nee, ctx->work.shadow, ctx->work.results, prev, ctx->d_counters.get());
     }
     {
       Launch l(ctx, stream, LUMC_KERNEL_SHADOW);
-      wf.shadow_rays(ctx->trace_blocks, ray_kernel_lds(ctx), stream, sc, ctx->shadow, nullptr, prev + kCtlVolumeShift, ctx->d_counters.get(), ctx->lds_nodes);
+      wf.shadow_rays(ctx->trace_blocks, ray_kernel_lds(ctx), stream, sc, ctx->work.shadow, nullptr, prev + kCtlVolumeShift, ctx->d_counters.get(), ctx->lds_nodes);
     }
     Launch l(ctx, stream, LUMC_KERNEL_RESOLVE);
-    wf.resolve_listed(std::min<uint32_t>(grid_for(N), 1024u), stream, sc, d.prev, d.nee, ctx->shadow, ctx->d_results, (const uint32_t*) prev);
+    wf.resolve_listed(std::min<uint32_t>(grid_for(N), 1024u), stream, sc, d.prev, d.nee, ctx->work.shadow, ctx->work.results, (const uint32_t*) prev);
   }
   return 0;
 }
@@ -1210,25 +333,25 @@ static void media_passes(LumContext* ctx, hipStream_t stream, const DeviceScene&
   if (render_volumes(sc)) {  // device_renderer.c:64-76: in-scattering with its own visibility pass, then the scattering events
     {
       Launch l(ctx, stream, LUMC_KERNEL_VOLUME);
-      wf.volume_inscatter(grid_for(N), stream, sc, d.cur, ctx->volume, ctx->shadow, d.ctrl, d.depth_const);
+      wf.volume_inscatter(grid_for(N), stream, sc, d.cur, ctx->work.volume, ctx->work.shadow, d.ctrl, d.depth_const);
     }
     {
       Launch l(ctx, stream, LUMC_KERNEL_SHADOW);
-      wf.shadow_rays(grid_persistent(ctx, N), ray_kernel_lds(ctx), stream, sc, ctx->shadow, nullptr, d.ctrl + kCtlVolumeShift, ctx->d_counters.get(), ctx->lds_nodes);
+      wf.shadow_rays(grid_persistent(ctx, N), ray_kernel_lds(ctx), stream, sc, ctx->work.shadow, nullptr, d.ctrl + kCtlVolumeShift, ctx->d_counters.get(), ctx->lds_nodes);
     }
     Launch l(ctx, stream, LUMC_KERNEL_VOLUME);
-    wf.volume_resolve(grid_for(N), stream, sc, d.cur, ctx->volume, ctx->shadow, ctx->d_results, (const uint32_t*) d.ctrl);
-    wf.volume_events(grid_for(N), stream, sc, d.cur, ctx->volume, ctx->d_results, d.ctrl, d.depth_const);
+    wf.volume_resolve(grid_for(N), stream, sc, d.cur, ctx->work.volume, ctx->work.shadow, ctx->work.results, (const uint32_t*) d.ctrl);
+    wf.volume_events(grid_for(N), stream, sc, d.cur, ctx->work.volume, ctx->work.results, d.ctrl, d.depth_const);
   }
   if (sc.cloud_active && sc.sky_mode == kSkyDefault && sc.cloud_noise_shape) {  // device_manager.c:474, device_renderer.c:78-82
     Launch l(ctx, stream, LUMC_KERNEL_SKY);
-    wf.clouds_list(grid_for(N), stream, sc, d.cur, ctx->cloud, d.ctrl);
-    wf.clouds_march(ctx->trace_blocks * 4u, stream, sc, d.cur, ctx->cloud, d.ctrl, d.depth_const);  // persistent: 4 workgroups of 256 per CU
-    wf.clouds(grid_for(N), stream, sc, d.cur, ctx->cloud, ctx->d_results, (const uint32_t*) d.ctrl, d.depth_const);
+    wf.clouds_list(grid_for(N), stream, sc, d.cur, ctx->work.cloud, d.ctrl);
+    wf.clouds_march(ctx->trace_blocks * 4u, stream, sc, d.cur, ctx->work.cloud, d.ctrl, d.depth_const);  // persistent: 4 workgroups of 256 per CU
+    wf.clouds(grid_for(N), stream, sc, d.cur, ctx->work.cloud, ctx->work.results, (const uint32_t*) d.ctrl, d.depth_const);
   }
   if (sc.sky_aerial_perspective && sc.sky_mode != kSkyConstantColor) {  // device_manager.c:475, device_renderer.c:84-88
     Launch l(ctx, stream, LUMC_KERNEL_SKY);
-    wf.sky_inscattering(grid_for(N), stream, sc, d.cur, ctx->d_results, (const uint32_t*) d.ctrl, d.depth_const);
+    wf.sky_inscattering(grid_for(N), stream, sc, d.cur, ctx->work.results, (const uint32_t*) d.ctrl, d.depth_const);
   }
 }
 
@@ -1238,17 +361,17 @@ static void shade_depth(LumContext* ctx, hipStream_t stream, const DeviceScene& 
   const bool fused = scheme == kResolveFused;
   {
     Launch l(ctx, stream, LUMC_KERNEL_SHADE);
-    wf.shade(shade_grid(ctx, N), stream, sc, d.cur, d.next, d.nee, ctx->shadow, ctx->d_results, d.ctrl, d.depth_const, ctx->d_counters.get(),
+    wf.shade(shade_grid(ctx, N), stream, sc, d.cur, d.next, d.nee, ctx->work.shadow, ctx->work.results, d.ctrl, d.depth_const, ctx->d_counters.get(),
              (scheme != kResolvePlain && !d.last) ? 1u : 0u, d.fused_records,
              fused ? ((d.depth > 0 ? 1u : 0u) | (!d.last ? 2u : 0u) | (ctx->fused_ended ? 4u : 0u)) : 0u);
   }
   if (fused && d.depth > 0) {  // the samples of depth - 1 their paths' closest hits could not decide: traced now, their vertices resolved (before this depth's visibility pass reuses the words)
     {
       Launch l(ctx, stream, LUMC_KERNEL_SHADOW);
-      wf.shadow_rays(ctx->trace_blocks, ray_kernel_lds(ctx), stream, sc, ctx->fallback, nullptr, d.ctrl + kCtlVolumeShift, ctx->d_counters.get(), ctx->lds_nodes);
+      wf.shadow_rays(ctx->trace_blocks, ray_kernel_lds(ctx), stream, sc, ctx->fused.fallback, nullptr, d.ctrl + kCtlVolumeShift, ctx->d_counters.get(), ctx->lds_nodes);
     }
     Launch l(ctx, stream, LUMC_KERNEL_RESOLVE);
-    wf.resolve_listed(std::min<uint32_t>(grid_for(N), 1024u), stream, sc, d.prev, d.nee_before, ctx->fallback, ctx->d_results, (const uint32_t*) d.ctrl);
+    wf.resolve_listed(std::min<uint32_t>(grid_for(N), 1024u), stream, sc, d.prev, d.nee_before, ctx->fused.fallback, ctx->work.results, (const uint32_t*) d.ctrl);
   }
 }
 
@@ -1257,15 +380,15 @@ static void feature_shading(LumContext* ctx, hipStream_t stream, const DeviceSce
   const WavefrontKernels& wf = *ctx->wf;
   if (sc.particles_active) {  // device_renderer.c:99-103
     Launch l(ctx, stream, LUMC_KERNEL_SHADE);
-    wf.particle_shade(grid_for(N), stream, sc, d.cur, d.next, d.nee, ctx->shadow, d.ctrl, d.depth_const);
+    wf.particle_shade(grid_for(N), stream, sc, d.cur, d.next, d.nee, ctx->work.shadow, d.ctrl, d.depth_const);
   }
   if (sc.ocean_active) {  // device_renderer.c:104-108
     Launch l(ctx, stream, LUMC_KERNEL_SHADE);
-    wf.ocean_shade(grid_for(N), stream, sc, d.cur, d.next, d.nee, ctx->shadow, d.ctrl, d.depth_const);
+    wf.ocean_shade(grid_for(N), stream, sc, d.cur, d.next, d.nee, ctx->work.shadow, d.ctrl, d.depth_const);
   }
   if (sc.sky_mode == kSkyDefault) {  // paths that left the scene into the procedural sky (listed by k_shade)
     Launch l(ctx, stream, LUMC_KERNEL_SKY);
-    wf.sky(grid_for(N), stream, sc, d.cur, ctx->shadow, ctx->d_results, (const uint32_t*) d.ctrl, d.depth_const);
+    wf.sky(grid_for(N), stream, sc, d.cur, ctx->work.shadow, ctx->work.results, (const uint32_t*) d.ctrl, d.depth_const);
   }
 }
 
@@ -1276,26 +399,26 @@ static int visibility_and_resolve(LumContext* ctx, hipStream_t stream, const Dev
     Launch l(ctx, stream, LUMC_KERNEL_LIGHT_QUERY);
     // (one resident round of its workgroups - four per CU: the kernel's workgroups are dear to start (a 1 KB stack per lane in scratch); 2 rounds, the common cap:
     //  Example-class 4.6 -> 4.0 ms per 3 steps, scan 3.9 -> 3.6, hall equal; 4 / 8 / 16 rounds on the hall: 30.2 / 32.8 / 44.5 ms against 29.9)
-    wf.light_query(std::min<uint32_t>(grid_for(N), ctx->trace_blocks * 4u), stream, sc, d.cur, d.nee, ctx->shadow, d.ctrl, d.depth_const, ctx->d_counters.get());
+    wf.light_query(std::min<uint32_t>(grid_for(N), ctx->trace_blocks * 4u), stream, sc, d.cur, d.nee, ctx->work.shadow, d.ctrl, d.depth_const, ctx->d_counters.get());
   }
   const uint32_t* shadow_order = nullptr;
   if (ctx->sort.mode == 2) {
-    shadow_order = sort_rays(ctx, stream, ctx->shadow.origin_dist, ctx->shadow.dir_out, d.ctrl + kCtlShadowItems,
-                             (sc.ocean_active ? kSurfaceShadowKindsWater : 4u) * (ctx->shadow.capacity < N ? ctx->shadow.capacity : N));
+    shadow_order = sort_rays(ctx, stream, ctx->work.shadow.origin_dist, ctx->work.shadow.dir_out, d.ctrl + kCtlShadowItems,
+                             (sc.ocean_active ? kSurfaceShadowKindsWater : 4u) * (ctx->work.shadow.capacity < N ? ctx->work.shadow.capacity : N));
     if (!shadow_order) { ctx->error = "ray sorting failed"; return 1; }
   }
   {
     Launch l(ctx, stream, LUMC_KERNEL_SHADOW);
-    wf.shadow_rays(grid_persistent(ctx, N), ray_kernel_lds(ctx), stream, sc, ctx->shadow, shadow_order, d.ctrl, ctx->d_counters.get(), ctx->lds_nodes);
+    wf.shadow_rays(grid_persistent(ctx, N), ray_kernel_lds(ctx), stream, sc, ctx->work.shadow, shadow_order, d.ctrl, ctx->d_counters.get(), ctx->lds_nodes);
   }
   if (d.last || scheme == kResolvePlain) {
     Launch l(ctx, stream, LUMC_KERNEL_RESOLVE);
-    wf.resolve(grid_for(N), stream, sc, d.cur, d.nee, ctx->shadow, ctx->d_results, (const uint32_t*) d.ctrl);
+    wf.resolve(grid_for(N), stream, sc, d.cur, d.nee, ctx->work.shadow, ctx->work.results, (const uint32_t*) d.ctrl);
   }
   else if (scheme == kResolveFused) {  // the vertices no entry of the next depth continues; the others are resolved by those entries, in k_shade - and so are these, as its last input (fused_flags & 4)
     if (!ctx->fused_ended) {
       Launch l(ctx, stream, LUMC_KERNEL_RESOLVE);
-      wf.resolve_ended(std::min<uint32_t>(grid_for(N), 4096u), stream, sc, d.cur, d.nee, ctx->shadow, ctx->d_results, (const uint32_t*) d.ctrl, d.ended);
+      wf.resolve_ended(std::min<uint32_t>(grid_for(N), 4096u), stream, sc, d.cur, d.nee, ctx->work.shadow, ctx->work.results, (const uint32_t*) d.ctrl, d.ended);
     }
   }
   // (kResolveReuse: the depth's resolve waits for the next depth's closest-hit pass, closest_hits)
@@ -1305,7 +428,7 @@ static int visibility_and_resolve(LumContext* ctx, hipStream_t stream, const Dev
 static void volume_bounce(LumContext* ctx, hipStream_t stream, const DeviceScene& sc, const DepthBuffers& d, uint32_t N) {
   if (render_volumes(sc) && !d.last) {  // device_renderer.c:114-118
     Launch l(ctx, stream, LUMC_KERNEL_VOLUME);
-    ctx->wf->volume_bounce(grid_for(N), stream, sc, d.cur, d.next, ctx->volume, d.ctrl, d.depth_const);
+    ctx->wf->volume_bounce(grid_for(N), stream, sc, d.cur, d.next, ctx->work.volume, d.ctrl, d.depth_const);
   }
 }
 
@@ -1360,12 +483,12 @@ int lumc_render(LumContext* ctx, uint32_t first_sample, uint32_t num_samples, ui
     HIP_TRY(ctx, hipMemsetAsync(ctx->d_ctrl.get(), 0, sizeof(uint32_t) * kCtlStride * (max_depth + 2), stream));
     {
       Launch l(ctx, stream, LUMC_KERNEL_GENERATE);
-      ctx->wf->generate(grid_for(N), stream, sc, pp, ctx->queue[0], ctx->d_results, ctx->d_ctrl.get() + kCtlPaths, ctx->lens, ctx->camera);
+      ctx->wf->generate(grid_for(N), stream, sc, pp, ctx->work.queue[0], ctx->work.results, ctx->d_ctrl.get() + kCtlPaths, ctx->lens, ctx->camera);
     }
     if (wavefront_depths(ctx, stream, N, first_sample + done, batch)) return 1;
     {
       Launch l(ctx, stream, LUMC_KERNEL_ACCUMULATE);
-      hipLaunchKernelGGL(k_accumulate, dim3(grid_for(P)), dim3(kBlock), 0, stream, (const float4*) ctx->d_results, P, batch, d_fm, d_sm);
+      hipLaunchKernelGGL(k_accumulate, dim3(grid_for(P)), dim3(kBlock), 0, stream, (const float4*) ctx->work.results, P, batch, d_fm, d_sm);
     }
     HIP_TRY(ctx, hipGetLastError());
   }
@@ -1392,12 +515,12 @@ int lumc_render_undersampled(LumContext* ctx, uint32_t stage, uint32_t iteration
   HIP_TRY(ctx, hipMemsetAsync(ctx->d_ctrl.get(), 0, sizeof(uint32_t) * kCtlStride * (sc.max_ray_depth + 2), stream));
   {
     Launch l(ctx, stream, LUMC_KERNEL_GENERATE);
-    ctx->wf->generate(grid_for(n), stream, sc, pp, ctx->queue[0], ctx->d_results, ctx->d_ctrl.get() + kCtlPaths, ctx->lens, ctx->camera);
+    ctx->wf->generate(grid_for(n), stream, sc, pp, ctx->work.queue[0], ctx->work.results, ctx->d_ctrl.get() + kCtlPaths, ctx->lens, ctx->camera);
   }
   if (wavefront_depths(ctx, stream, n)) return 1;
   {
     Launch l(ctx, stream, LUMC_KERNEL_ACCUMULATE);
-    hipLaunchKernelGGL(k_accumulate_scatter, dim3(grid_for(n)), dim3(kBlock), 0, stream, (const float4*) ctx->d_results, (const uint32_t*) ctx->d_undersampling_pixels.get(), n,
+    hipLaunchKernelGGL(k_accumulate_scatter, dim3(grid_for(n)), dim3(kBlock), 0, stream, (const float4*) ctx->work.results, (const uint32_t*) ctx->d_undersampling_pixels.get(), n,
                        ctx->num_pixels, ctx->d_first_moment.get(), ctx->d_second_moment.get());
   }
   HIP_TRY(ctx, hipGetLastError());
@@ -1494,12 +617,12 @@ int adaptive_execute(LumContext* ctx, hipStream_t stream, uint32_t merged) {
     HIP_TRY(ctx, hipMemsetAsync(ctx->d_ctrl.get(), 0, sizeof(uint32_t) * kCtlStride * (sc.max_ray_depth + 2), stream));
     {
       Launch l(ctx, stream, LUMC_KERNEL_GENERATE);
-      ctx->wf->generate_adaptive(grid_for(N), stream, sc, view, pass, ctx->queue[0], ctx->d_results, ctx->d_ctrl.get() + kCtlPaths, ctx->lens, ctx->camera);
+      ctx->wf->generate_adaptive(grid_for(N), stream, sc, view, pass, ctx->work.queue[0], ctx->work.results, ctx->d_ctrl.get() + kCtlPaths, ctx->lens, ctx->camera);
     }
     if (wavefront_depths(ctx, stream, N)) return 1;
     {
       Launch l(ctx, stream, LUMC_KERNEL_ACCUMULATE);
-      hipLaunchKernelGGL(k_accumulate_adaptive, dim3(grid_for((end - block) * 16)), dim3(kBlock), 0, stream, view, pass, sc.width, sc.height, (const float4*) ctx->d_results,
+      hipLaunchKernelGGL(k_accumulate_adaptive, dim3(grid_for((end - block) * 16)), dim3(kBlock), 0, stream, view, pass, sc.width, sc.height, (const float4*) ctx->work.results,
                          ctx->d_first_moment.get(), ctx->d_second_moment.get());
     }
     HIP_TRY(ctx, hipGetLastError());
@@ -1655,6 +778,18 @@ int lumc_adaptive_end(LumContext* ctx) {
   return 0;
 }
 
+// What the result and the denoiser read: the full frame's moments - the assembled frame's (multi_gpu.hip) or this context's own accumulators - and the
+// adaptive sampler's bookkeeping (none: zeros). usable: there is such a frame of n = width * height pixels.
+struct FrameMoments { bool usable; const float* first; const float* second; AdaptiveView view; };
+static FrameMoments frame_moments(const LumContext* ctx, uint32_t n) {
+  const bool framed = ctx->exchange.use_frame && ctx->exchange.d_frame && ctx->exchange.frame_pixels() == n;
+  FrameMoments m{framed || (ctx->d_first_moment && !ctx->d_pixels && ctx->num_pixels == n), framed ? ctx->exchange.d_frame.get() : ctx->d_first_moment.get(),
+                 framed ? ctx->exchange.d_frame.get() + 3 * (size_t) n : ctx->d_second_moment.get(), {}};
+  std::memset(&m.view, 0, sizeof(m.view));
+  if (ctx->adaptive.active) m.view = adaptive_view(ctx);
+  return m;
+}
+
 // The context's result image of n pixels: what lumc_generate_result* write when the caller passes no image of its own.
 static int result_image(LumContext* ctx, uint32_t n, float** out) {
   if (ctx->d_frame_result.count() != 3 * (size_t) n) HIP_TRY(ctx, ctx->d_frame_result.resize(3 * (size_t) n));
@@ -1664,27 +799,24 @@ static int result_image(LumContext* ctx, uint32_t n, float** out) {
 
 int lumc_generate_result(LumContext* ctx, uint32_t mode, uint32_t local_error_minimization, uint32_t uniform_samples, float exposure, const LumOutputParams* tone,
                          float* d_result, void* stream_) {
-  const bool framed = ctx && ctx->exchange.use_frame && ctx->exchange.d_frame && ctx->has_scene && ctx->exchange.frame_pixels() == ctx->scene.width * ctx->scene.height;
-  if (!ctx || !ctx->has_scene || (!framed && (!ctx->d_first_moment || ctx->d_pixels || ctx->num_pixels != ctx->scene.width * ctx->scene.height))) {
+  const uint32_t n = (ctx && ctx->has_scene) ? ctx->scene.width * ctx->scene.height : 0u;
+  FrameMoments src{};
+  if (n) src = frame_moments(ctx, n);
+  if (!src.usable) {
     if (ctx) ctx->error = "lumc_generate_result: needs the full-frame accumulators";
     return 1;
   }
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   hipStream_t stream = (hipStream_t) stream_;
-  const uint32_t n = ctx->scene.width * ctx->scene.height;
-  const float* src_fm = framed ? ctx->exchange.d_frame.get() : ctx->d_first_moment.get();
-  const float* src_sm = framed ? ctx->exchange.d_frame.get() + 3 * (size_t) n : ctx->d_second_moment.get();
   if (!d_result && result_image(ctx, n, &d_result)) return 1;
-  AdaptiveView view;
-  std::memset(&view, 0, sizeof(view));
-  if (ctx->adaptive.active) view = adaptive_view(ctx);
-  else { view.blocks_x = (ctx->scene.width + 3u) >> kAdaptiveBlockLog; view.blocks_y = (ctx->scene.height + 3u) >> kAdaptiveBlockLog; view.num_blocks = view.blocks_x * view.blocks_y; }
+  AdaptiveView view = src.view;
+  if (!ctx->adaptive.active) { view.blocks_x = (ctx->scene.width + 3u) >> kAdaptiveBlockLog; view.blocks_y = (ctx->scene.height + 3u) >> kAdaptiveBlockLog; view.num_blocks = view.blocks_x * view.blocks_y; }
   if (!ctx->adaptive.active && uniform_samples == 0) { ctx->error = "lumc_generate_result: no samples"; return 1; }
   ResultParams rp{ctx->scene.width, ctx->scene.height, mode, local_error_minimization, uniform_samples, exposure};
   const OutputParams op = tone_params(tone);
   {
     Launch l(ctx, stream, LUMC_KERNEL_OUTPUT);
-    hipLaunchKernelGGL(k_generate_result, dim3(grid_for(n)), dim3(256), 0, stream, view, rp, op, src_fm, src_sm, d_result);
+    hipLaunchKernelGGL(k_generate_result, dim3(grid_for(n)), dim3(256), 0, stream, view, rp, op, src.first, src.second, d_result);
   }
   HIP_TRY(ctx, hipGetLastError());
   return 0;
@@ -1813,19 +945,11 @@ int lumc_render_guides(LumContext* ctx, uint32_t num_samples, void* stream_) {
     HIP_TRY(ctx, hipMemsetAsync(ctx->d_ctrl.get(), 0, sizeof(uint32_t) * kCtlStride * (sc.max_ray_depth + 2), stream));
     {
       Launch l(ctx, stream, LUMC_KERNEL_GENERATE);
-      wf.generate(grid_for(n), stream, sc, pp, ctx->queue[0], ctx->d_results, ctx->d_ctrl.get() + kCtlPaths, ctx->lens, ctx->camera);
+      wf.generate(grid_for(n), stream, sc, pp, ctx->work.queue[0], ctx->work.results, ctx->d_ctrl.get() + kCtlPaths, ctx->lens, ctx->camera);
     }
-    {
-      Launch l(ctx, stream, LUMC_KERNEL_TRACE);
-      wf.trace(grid_persistent(ctx, n), ray_kernel_lds(ctx), stream, sc, ctx->queue[0], nullptr, ctx->d_ctrl.get(), ctx->d_counters.get(), ctx->lds_nodes);
-    }
-    if (sc.particles_active) trace_particles(ctx, stream, ctx->queue[0], ctx->d_ctrl.get(), n);
-    if (sc.ocean_active) {
-      Launch l(ctx, stream, LUMC_KERNEL_TRACE);
-      wf.trace_ocean(grid_for(n), stream, sc, ctx->queue[0], (const uint32_t*) ctx->d_ctrl.get());
-    }
+    first_hits(ctx, stream, sc, n);
     Launch l(ctx, stream, LUMC_KERNEL_OUTPUT);
-    wf.guide(grid_for(n), stream, sc, ctx->queue[0], (const uint32_t*) ctx->d_ctrl.get(), ctx->d_guides.get(), n);
+    wf.guide(grid_for(n), stream, sc, ctx->work.queue[0], (const uint32_t*) ctx->d_ctrl.get(), ctx->d_guides.get(), n);
   }
   {
     Launch l(ctx, stream, LUMC_KERNEL_OUTPUT);
@@ -1864,8 +988,8 @@ int lumc_denoise(LumContext* ctx, const LumDenoiseParams* params, float* d_image
   if (!ctx || !params || !ctx->has_scene) { if (ctx) ctx->error = "lumc_denoise: no scene or null argument"; return 1; }
   const uint32_t n = ctx->scene.width * ctx->scene.height;
   if (!ctx->guides_valid || guide_pixels(ctx) != n) { ctx->error = "lumc_denoise: no guides for this frame (lumc_render_guides)"; return 1; }
-  const bool framed = ctx->exchange.use_frame && ctx->exchange.d_frame && ctx->exchange.frame_pixels() == n;
-  if (!framed && (!ctx->d_first_moment || ctx->d_pixels || ctx->num_pixels != n)) { ctx->error = "lumc_denoise: needs the full-frame accumulators"; return 1; }
+  const FrameMoments src = frame_moments(ctx, n);
+  if (!src.usable) { ctx->error = "lumc_denoise: needs the full-frame accumulators"; return 1; }
   if (!d_image) d_image = (ctx->d_frame_result.count() == 3 * (size_t) n) ? ctx->d_frame_result.get() : nullptr;
   if (!d_image) { ctx->error = "lumc_denoise: no image"; return 1; }
   if (!ctx->adaptive.active && params->uniform_samples == 0) { ctx->error = "lumc_denoise: no samples"; return 1; }
@@ -1876,18 +1000,13 @@ int lumc_denoise(LumContext* ctx, const LumDenoiseParams* params, float* d_image
     for (auto& r : ctx->d_denoise_rec) r.reset();
     for (auto& r : ctx->d_denoise_rec) HIP_TRY(ctx, r.resize(n));
   }
-  const float* src_fm = framed ? ctx->exchange.d_frame.get() : ctx->d_first_moment.get();
-  const float* src_sm = framed ? ctx->exchange.d_frame.get() + 3 * (size_t) n : ctx->d_second_moment.get();
-  AdaptiveView view;
-  std::memset(&view, 0, sizeof(view));
-  if (ctx->adaptive.active) view = adaptive_view(ctx);
   DenoiseArgs args{ctx->scene.width, ctx->scene.height, 1u, params->uniform_samples, params->sigma_luminance, params->sigma_normal, params->sigma_depth};
   const uint32_t iterations = std::min(params->iterations, 6u);
   float4* rec_a[2] = {ctx->d_denoise_rec[0].get(), ctx->d_denoise_rec[1].get()};
   uint4* rec_b = (uint4*) ctx->d_denoise_rec[2].get();
   const WavefrontKernels& wf = *ctx->wf;
   Launch l(ctx, stream, LUMC_KERNEL_OUTPUT);
-  wf.denoise_prepare(grid_for(n), stream, view, args, src_fm, src_sm, d_image, ctx->d_guides.get(), rec_a[0], rec_b);
+  wf.denoise_prepare(grid_for(n), stream, src.view, args, src.first, src.second, d_image, ctx->d_guides.get(), rec_a[0], rec_b);
   uint32_t cur = 0;
   for (uint32_t i = 0; i < iterations; i++, cur ^= 1u) {
     args.step = 1u << i;
@@ -2223,23 +1342,5 @@ int lumc_get_ambient_reuse(const LumContext* ctx) { return (ctx && ambient_reuse
 int lumc_get_flavour(const LumContext* ctx) { return (ctx && ctx->wf == wavefront_kernels_exact()) ? LUMC_FLAVOUR_EXACT : LUMC_FLAVOUR_FAST; }
 
 unsigned int lumc_lds_stack_bytes(void) { return LUM_LDS_STACK_BYTES; }
-
-int lumc_set_bvh_builder(LumContext* ctx, int builder) {
-  if (!ctx || builder < 0 || builder > 3) { if (ctx) ctx->error = "lumc_set_bvh_builder: 0 (SAH, host), 1 (LBVH, GPU), 2 (PLOC, GPU) or 3 (SAH, GPU)"; return 1; }
-  ctx->bvh_builder = builder;
-  return 0;
-}
-double lumc_bvh_build_seconds(const LumContext* ctx) { return ctx ? ctx->bvh_build_seconds : 0.0; }
-int lumc_bvh_meshes_by_builder(const LumContext* ctx, uint32_t out[2]) {
-  if (!ctx || !out) return 1;
-  out[0] = ctx->bvh_meshes_by_builder[0]; out[1] = ctx->bvh_meshes_by_builder[1];
-  return 0;
-}
-
-int lumc_bvh_stats(LumContext* ctx, uint64_t out[4]) {
-  if (!ctx) return 1;
-  for (int k = 0; k < 4; k++) out[k] = ctx->bvh_stats[k];
-  return 0;
-}
 
 }  // extern "C"

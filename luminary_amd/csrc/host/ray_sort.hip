@@ -96,12 +96,12 @@ const uint32_t* sort_rays(LumContext* ctx, hipStream_t stream, const float4* ori
 
 // Mode 3, the physical reorder: the planes change places, the permutation is spent.
 static int reorder_queue(LumContext* ctx, hipStream_t stream, PathQueue& q, const uint32_t* order, uint32_t* ctrl, uint32_t N) {
-  if (ensure_sort_queue(ctx, ctx->capacity)) return 1;
+  if (ensure_sort_queue(ctx, ctx->work.capacity)) return 1;
   Launch l(ctx, stream, LUMC_KERNEL_SORT);
   hipLaunchKernelGGL(k_permute_queue, dim3(std::min<uint32_t>((N + 255u) / 256u, 65536u)), dim3(256), 0, stream, q, ctx->sort.queue, order, ctrl + kCtlPaths, N);
   std::swap(q.origin_t, ctx->sort.queue.origin_t); std::swap(q.dir_slot, ctx->sort.queue.dir_slot);
   std::swap(q.aux, ctx->sort.queue.aux); std::swap(q.hit_id, ctx->sort.queue.hit_id);
-  ctx->fused_records_stale = true;  // (the fused resolve does not run with ray sorting; a later pass without it must not read the old planes)
+  ctx->fused.records_stale = true;  // (the fused resolve does not run with ray sorting; a later pass without it must not read the old planes)
   return 0;
 }
 

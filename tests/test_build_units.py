@@ -45,13 +45,17 @@ def test_every_kernel_is_compiled_in_exactly_one_unit():
 
 
 def test_the_flavour_neutral_kernels_exist_in_the_exact_namespace_of_core_alone():
+    """kernels_shared.h belongs to core.hip, kernels_scene.h to scene_device.hip: every kernel of either header is defined by that unit's object and no other."""
     defined, source_of = _stubs()
-    text = open(os.path.join(DEVICE, "kernels_shared.h")).read()
-    shared = set(re.findall(r"^__global__[^\n]*?\bvoid (k_\w+)\(", text, re.M))
-    assert len(shared) >= 22, sorted(shared)
-    for name in sorted(shared):
-        where = {k: objs for k, objs in defined.items() if re.search(r"::%s\(" % name, k)}
-        assert list(where.values()) == [["core.hip.o"]] and next(iter(where)).startswith("lum::exact::"), (name, where)
+    for header, unit, count in (("kernels_shared.h", "core.hip", 17), ("kernels_scene.h", "scene_device.hip", 9)):
+        text = open(os.path.join(DEVICE, header)).read()
+        kernels = set(re.findall(r"^__global__[^\n]*?\bvoid (k_\w+)\(", text, re.M))
+        assert len(kernels) == count, (header, sorted(kernels))
+        for name in sorted(kernels):
+            where = {k: objs for k, objs in defined.items() if re.search(r"::%s\(" % name, k)}
+            assert list(where.values()) == [[unit + ".o"]] and next(iter(where)).startswith("lum::exact::"), (name, where)
+        including = sorted(s for s, _ in lum_build.HIP_SOURCES if re.search(r'#include\s+"[^"]*\b%s"' % re.escape(header), open(os.path.join(lum_build.CSRC, s)).read()))
+        assert including == ["host/" + unit], (header, including)
 
 
 def test_kernels_h_has_no_switch_that_places_a_kernel():
@@ -59,8 +63,9 @@ def test_kernels_h_has_no_switch_that_places_a_kernel():
     for f in sorted(os.listdir(DEVICE)):
         if f.endswith(".h"):
             assert not re.search(r"^#if\s+!\s*LUM_FAST", open(os.path.join(DEVICE, f)).read(), re.M), f
-    core = open(os.path.join(ROOT, "luminary_amd", "csrc", "host", "core.hip")).read()
-    assert not re.search(r'#include\s+"[^"]*\b(kernels|wavefront_table_impl)\.h"', core)
+    for unit in ("core.hip", "scene_device.hip"):
+        text = open(os.path.join(ROOT, "luminary_amd", "csrc", "host", unit)).read()
+        assert not re.search(r'#include\s+"[^"]*\b(kernels|wavefront_table_impl)\.h"', text), unit
 
 
 def test_the_launcher_table_assigns_every_member_by_name():

@@ -3,7 +3,7 @@
 # drive - for gfx950 (device code only, nothing is linked or run), so that they do not rot unbuilt. Experiments that were measured negative are not here: they
 # left the sources (docs/HISTORY.md, "Retired experiments"). Runs without a GPU: bash tools/check_variants.sh [jobs] > profiles/variants_compile.txt
 # A variant is a set of -D flags; it is compiled into the fast flavour's two translation units (wavefront_fast.hip, wavefront_fast_shadow.hip), and - where the
-# host side takes part (leaf size, diagnostic counters) - into the exact flavour's unit (wavefront_exact.hip) and core.hip with the exact flags.
+# host side takes part (leaf size, diagnostic counters) - into the exact flavour's unit (wavefront_exact.hip), core.hip and scene_device.hip with the exact flags.
 cd "$(dirname "$0")/.." || exit 1
 JOBS=${1:-4}
 HIPCC=${ROCM_PATH:-/opt/rocm}/bin/hipcc
@@ -23,7 +23,7 @@ one() {
   local flags=${rest%%:*} extra=${rest#*:}
   local ok=1 log
   for unit in "luminary_amd/csrc/device/wavefront_fast.hip $FAST -DLUM_SHADOW_KERNEL_EXTERN=1" "luminary_amd/csrc/device/wavefront_fast_shadow.hip $FAST" \
-              ${extra:+"luminary_amd/csrc/device/wavefront_exact.hip $EXACT -DLUM_SHADOW_KERNEL_EXTERN=1"} ${extra:+"luminary_amd/csrc/host/core.hip $EXACT"}; do
+              ${extra:+"luminary_amd/csrc/device/wavefront_exact.hip $EXACT -DLUM_SHADOW_KERNEL_EXTERN=1"} ${extra:+"luminary_amd/csrc/host/core.hip $EXACT"} ${extra:+"luminary_amd/csrc/host/scene_device.hip $EXACT"}; do
     # shellcheck disable=SC2086
     if ! log=$($HIPCC $COMMON $flags ${unit#* } ${unit%% *} 2>&1); then ok=0; echo "---- $name: ${unit%% *}"; echo "$log" | grep -E "error|Error" | head -5; fi
   done

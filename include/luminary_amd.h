@@ -395,6 +395,23 @@ typedef struct LuminaryMeshRefitStats {
   double seconds_hash, seconds_download, seconds_lights; /* as LumMeshRefitStats (include/lum_core.h) */
 } LuminaryMeshRefitStats;
 LUMINARY_API LuminaryResult luminary_ext_get_mesh_refit_stats(LuminaryHost* host, LuminaryMeshRefitStats* out);
+/* Rigidly moving instances, in bulk. For each of the `count` entries: `id` names an existing, active instance (one that points at a mesh the host holds), `mesh_id`
+ * must equal its current mesh (changing the mesh stays luminary_host_set_instance's job), position, rotation and scale must be finite. Restarts the integration.
+ * LUMINARY_ERROR_INVALID_API_ARGUMENT, and nothing changes - not for the entries before the offending one either: NULL instances with a count, an unknown id, an
+ * inactive instance, another mesh_id, a value that is not finite. On the devices only the 32-byte transforms are uploaded: rows, world boxes, the top-level tree
+ * and its leaf records are derived from them there, the mesh trees stay where they are (luminary_ext_set_instance_update). */
+LUMINARY_API LuminaryResult luminary_ext_set_instance_transforms(LuminaryHost* host, const LuminaryInstance* instances, uint32_t count);
+/* mode 0 (default): moved instances are taken over on the device; 1: as luminary_host_set_instance's edits are - the scene tree is assembled on the host and
+ * uploaded (for comparison; also what a single update falls back to when the device path cannot take it). Images do not depend on it. */
+LUMINARY_API LuminaryResult luminary_ext_set_instance_update(LuminaryHost* host, uint32_t mode);
+typedef struct LuminaryInstanceUpdateStats {
+  uint64_t device_updates, fallbacks, relayouts; /* moved-instance updates of the main device's context that ran on the device / fell back to the host's path / laid
+                                                    the node array out anew, since it was created */
+  uint32_t tlas_nodes, tlas_depth, tlas_capacity, hittable; /* the last device update's top level: nodes, 4-wide levels, the node slots reserved for it, instances that can be hit */
+  double seconds;                                /* the last update's instance part on the main device */
+  double seconds_relayout, seconds_upload, seconds_boxes, seconds_build, seconds_leaves; /* as LumInstanceUpdateStats (include/lum_core.h) */
+} LuminaryInstanceUpdateStats;
+LUMINARY_API LuminaryResult luminary_ext_get_instance_update_stats(LuminaryHost* host, LuminaryInstanceUpdateStats* out);
 /* Converts the current scene to the device format (device_structs.c conversions + light tree build). The view and everything it points
  * to stay valid until the next call or host destruction. Needs no GPU. */
 /* Whether replacing `old` by `input` restarts the integration (camera.c:80-147, settings.c:45-72) or only changes the outputs.

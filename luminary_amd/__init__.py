@@ -169,6 +169,13 @@ class MeshRefitStats(C.Structure):
                 ("seconds_hash", C.c_double), ("seconds_download", C.c_double), ("seconds_lights", C.c_double)]
 
 
+class InstanceUpdateStats(C.Structure):
+    """LuminaryInstanceUpdateStats"""
+    _fields_ = [("device_updates", C.c_uint64), ("fallbacks", C.c_uint64), ("relayouts", C.c_uint64), ("tlas_nodes", C.c_uint32), ("tlas_depth", C.c_uint32),
+                ("tlas_capacity", C.c_uint32), ("hittable", C.c_uint32), ("seconds", C.c_double), ("seconds_relayout", C.c_double), ("seconds_upload", C.c_double),
+                ("seconds_boxes", C.c_double), ("seconds_build", C.c_double), ("seconds_leaves", C.c_double)]
+
+
 class Instance(C.Structure):
     _fields_ = [("id", C.c_uint32), ("mesh_id", C.c_uint32), ("position", Vec3), ("rotation", Vec3), ("scale", Vec3)]
 
@@ -512,6 +519,25 @@ class Host:
         """luminary_ext_get_mesh_refit_stats of the main device: a dict of refits, rebuilds, last_refits, last_rebuilds, max_cost_growth and the seconds."""
         s = MeshRefitStats()
         _call("luminary_ext_get_mesh_refit_stats", self._h, C.byref(s))
+        return {name: getattr(s, name) for name, _ in s._fields_}
+
+    def set_instance_transforms(self, instances):
+        """luminary_ext_set_instance_transforms: new position / rotation / scale for existing instances, in bulk: a sequence of Instance (id and mesh_id as the
+        host holds them); the devices rebuild the top-level tree, the mesh trees stay."""
+        instances = list(instances)
+        arr = (Instance * max(len(instances), 1))()
+        for k, inst in enumerate(instances):
+            arr[k] = inst
+        _call("luminary_ext_set_instance_transforms", self._h, arr, C.c_uint32(len(instances)))
+
+    def set_instance_update(self, mode=0):
+        """luminary_ext_set_instance_update: 0 = moved instances are taken over on the device, 1 = the scene tree is assembled on the host and uploaded."""
+        _call("luminary_ext_set_instance_update", self._h, C.c_uint32(mode))
+
+    def instance_update_stats(self):
+        """luminary_ext_get_instance_update_stats of the main device: a dict of device_updates, fallbacks, relayouts, the last top level's sizes and the seconds."""
+        s = InstanceUpdateStats()
+        _call("luminary_ext_get_instance_update_stats", self._h, C.byref(s))
         return {name: getattr(s, name) for name, _ in s._fields_}
 
     def get_mesh(self, mesh_id):

@@ -39,7 +39,7 @@ if os.environ.get("LUM_FAST_FLAGS") is not None:  # diagnosis only (tools/flavou
 # (csrc/device/kernel_shadow.h, profiles/r05_ab_experiments.txt); LUM_FAST_SHADOW_SCHED= (empty) in the environment builds it with the default scheduler
 SHADOW_SCHED = os.environ.get("LUM_FAST_SHADOW_SCHED", "max-ilp")
 SHADOW_FLAGS = (["-mllvm", "-amdgpu-sched-strategy=" + SHADOW_SCHED] if SHADOW_SCHED else [])
-HIP_SOURCES = [("host/core.hip", EXACT), ("host/scene_device.hip", EXACT), ("host/ray_sort.hip", EXACT), ("host/multi_gpu.hip", EXACT), ("host/lbvh.hip", EXACT), ("host/bvh_refit.hip", EXACT),
+HIP_SOURCES = [("host/core.hip", EXACT), ("host/scene_device.hip", EXACT), ("host/ray_sort.hip", EXACT), ("host/multi_gpu.hip", EXACT), ("host/lbvh.hip", EXACT), ("host/bvh_refit.hip", EXACT), ("host/instance_update.hip", EXACT),
                ("device/wavefront_exact.hip", EXACT + ["-DLUM_SHADOW_KERNEL_EXTERN=1"]), ("device/wavefront_fast.hip", FAST + ["-DLUM_SHADOW_KERNEL_EXTERN=1"]),
                ("device/wavefront_fast_shadow.hip", FAST + SHADOW_FLAGS), ("device/wavefront_exact_shadow.hip", EXACT + SHADOW_FLAGS)]
 STAMP = os.path.join(LIB_DIR, "build_flags.txt")

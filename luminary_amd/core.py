@@ -7,6 +7,7 @@ from . import DeviceSceneView, _lib
 
 DIRTY_CONSTANTS, DIRTY_MATERIALS, DIRTY_INSTANCES, DIRTY_LIGHTS, DIRTY_MESHES, DIRTY_TEXTURES, DIRTY_PARTICLES, DIRTY_ALL = 1, 2, 4, 8, 16, 32, 64, 127
 DIRTY_MESH_POSITIONS = 128  # moved vertices: refit (not part of DIRTY_ALL, which builds)
+DIRTY_INSTANCE_TRANSFORMS = 256  # moved instances: the top level is rebuilt on the device, the mesh trees stay (not part of DIRTY_ALL)
 BVH_BUILDERS = {"sah": 0, "lbvh": 1, "ploc": 2, "sah_gpu": 3}
 CNT_TRACE, CNT_SHADOW, CNT_LIGHT_BVH, CNT_VERTICES, CNT_NODES, CNT_TRIS, CNT_NODES_SHADOW, CNT_TRIS_SHADOW, CNT_NODES_LIGHT, CNT_TRIS_LIGHT, CNT_NODES_LDS, CNT_NODES_LDS_SHADOW, CNT_AMBIENT_DEFERRED, CNT_AMBIENT_FALLBACK = range(14)
 CNT_COUNT = 16  # LUMC_CNT_COUNT
@@ -97,6 +98,42 @@ class MeshRefitStats(C.Structure):
     _fields_ = [("refits", C.c_uint64), ("rebuilds", C.c_uint64), ("last_refits", C.c_uint32), ("last_rebuilds", C.c_uint32), ("max_cost_growth", C.c_double),
                 ("seconds", C.c_double), ("seconds_upload", C.c_double), ("seconds_refit", C.c_double), ("seconds_rebuild", C.c_double), ("seconds_assemble", C.c_double),
                 ("seconds_hash", C.c_double), ("seconds_download", C.c_double), ("seconds_lights", C.c_double)]
+
+
+class InstanceUpdateStats(C.Structure):
+    """LumInstanceUpdateStats"""
+    _fields_ = [("device_updates", C.c_uint64), ("fallbacks", C.c_uint64), ("relayouts", C.c_uint64), ("tlas_nodes", C.c_uint32), ("tlas_depth", C.c_uint32),
+                ("tlas_capacity", C.c_uint32), ("hittable", C.c_uint32), ("seconds", C.c_double), ("seconds_relayout", C.c_double), ("seconds_upload", C.c_double),
+                ("seconds_boxes", C.c_double), ("seconds_build", C.c_double), ("seconds_leaves", C.c_double)]
+
+
+def instance_boxes_probe(view, mesh_boxes, on_gpu=False):
+    """lumc_instance_boxes_probe: (rows [n, 3, 4] float32, boxes [n, 6] float32, hittable [n] uint32) of the instances of `view` over the meshes' object-space
+    boxes mesh_boxes [num_meshes, 6], by the host's functions or by the device's kernel."""
+    fn = _lib().lumc_instance_boxes_probe
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    mb = np.ascontiguousarray(mesh_boxes, dtype=np.float32).reshape(-1, 6)
+    assert mb.shape[0] == view.num_meshes
+    n = view.num_instances
+    rows, boxes, hittable = np.zeros((n, 3, 4), np.float32), np.zeros((n, 6), np.float32), np.zeros(n, np.uint32)
+    if fn(C.addressof(view), mb.ctypes.data, int(bool(on_gpu)), rows.ctypes.data, boxes.ctypes.data, hittable.ctypes.data) != 0:
+        raise CoreError("lumc_instance_boxes_probe failed")
+    return rows, boxes, hittable
+
+
+def host_bvh_nodes_probe(boxes, max_leaf=1, max_depth=16):
+    """lumc_host_bvh_nodes_probe: the host builder's tree over boxes [n, 6]: (nodes [nodes, 32] uint32 words, prims [n] uint32, 4-wide levels)."""
+    fn = _lib().lumc_host_bvh_nodes_probe
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p]
+    b = np.ascontiguousarray(boxes, dtype=np.float32).reshape(-1, 6)
+    n = b.shape[0]
+    sizes = (C.c_uint64 * 3)()
+    nodes, prims = np.zeros((max(n, 1), 32), np.uint32), np.zeros(max(n, 1), np.uint32)
+    if fn(b.ctypes.data, n, max_leaf, max_depth, sizes, nodes.ctypes.data, prims.ctypes.data) != 0:
+        raise CoreError("lumc_host_bvh_nodes_probe failed")
+    return nodes[:sizes[0]].copy(), prims[:sizes[1]].copy(), int(sizes[2])
 
 
 def bvh_refit_probe(built_boxes, refit_boxes, builder="sah", on_gpu=False):
@@ -503,6 +540,26 @@ class Core:
         out = MeshRefitStats()
         self._call("lumc_mesh_refit_stats", C.byref(out))
         return out
+
+    def set_instance_update(self, mode=0):
+        """lumc_set_instance_update: how DIRTY_INSTANCE_TRANSFORMS updates are taken over: 0 on the device, 1 as DIRTY_INSTANCES (the host assembles the scene tree)."""
+        self._call("lumc_set_instance_update", C.c_uint32(mode))
+
+    def instance_update_stats(self):
+        out = InstanceUpdateStats()
+        self._call("lumc_instance_update_stats", C.byref(out))
+        return out
+
+    def resident_tree_probe(self, num_instances, num_meshes):
+        """lumc_resident_tree_probe: a dict of the resident layout after a device update: C, M, T, depth, top [C, 32] uint32 words (24 box floats, 4 child words, 4 of
+        padding), leaves [records, 4, 4] uint32 words (one record of padding included), mesh_root [num_meshes], mesh_hash."""
+        sizes, h = (C.c_uint64 * 5)(), C.c_uint64()
+        self._call("lumc_resident_tree_probe", sizes, C.c_void_p(0), C.c_void_p(0), C.c_void_p(0), C.c_void_p(0))
+        top, leaves = np.zeros((int(sizes[0]), 32), np.uint32), np.zeros((num_instances + 1, 4, 4), np.uint32)
+        roots = np.zeros(max(num_meshes, 1), np.uint32)
+        self._call("lumc_resident_tree_probe", sizes, top.ctypes.data_as(C.c_void_p), leaves.ctypes.data_as(C.c_void_p), roots.ctypes.data_as(C.c_void_p), C.byref(h))
+        return {"C": int(sizes[0]), "M": int(sizes[1]), "T": int(sizes[2]), "depth": int(sizes[4]), "top": top, "leaves": leaves[:int(sizes[3])].copy(),
+                "mesh_root": roots[:num_meshes].copy(), "mesh_hash": int(h.value)}
 
     def bvh_build_seconds(self):
         fn = self._lib.lumc_bvh_build_seconds

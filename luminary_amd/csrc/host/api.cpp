@@ -44,6 +44,7 @@ struct LuminaryHost {
   std::vector<uint32_t> moved_meshes;     // meshes luminary_ext_set_mesh_positions moved since `device_scene` was last brought up to date
   uint32_t refit_mode = 0;                // luminary_ext_set_mesh_refit: handed to every context before it takes a scene
   float refit_max_cost_growth = 0.0f;
+  uint32_t instance_update_mode = 0;      // luminary_ext_set_instance_update: likewise
   bool device_scene_valid = false;
   bool core_scene_valid = false;
   uint32_t core_width = 0, core_height = 0;  // frame size the main context's pixel set was made for
@@ -207,6 +208,7 @@ LuminaryResult ensure_core(LuminaryHost* h) {
   if (r) return r;
   if (!h->core_scene_valid) {
     lumc_set_mesh_refit(h->core, h->refit_mode, h->refit_max_cost_growth);
+    lumc_set_instance_update(h->core, h->instance_update_mode);
     if (lumc_scene_update(h->core, &h->device_scene.view, h->core_dirty)) { std::fprintf(stderr, "[luminary_amd] %s\n", lumc_last_error(h->core)); h->core_dirty = LUMC_DIRTY_ALL; return LUMINARY_ERROR_CUDA; }
     h->core_dirty = 0;
     h->core_scene_valid = true;
@@ -249,6 +251,7 @@ LuminaryResult ensure_partition_cores(LuminaryHost* h, std::vector<LumContext*>*
     }
     if (!slot->scene_valid) {
       lumc_set_mesh_refit(slot->core, h->refit_mode, h->refit_max_cost_growth);
+      lumc_set_instance_update(slot->core, h->instance_update_mode);
       if (lumc_scene_update(slot->core, &h->device_scene.view, slot->dirty)) { std::fprintf(stderr, "[luminary_amd] device %d: %s\n", slot->ordinal, lumc_last_error(slot->core)); slot->dirty = LUMC_DIRTY_ALL; return LUMINARY_ERROR_CUDA; }
       slot->dirty = 0;
       slot->scene_valid = true;
@@ -812,6 +815,45 @@ LuminaryResult luminary_ext_get_mesh_refit_stats(LuminaryHost* host, LuminaryMes
   LumMeshRefitStats s;
   if (lumc_mesh_refit_stats(host->core, &s)) return LUMINARY_ERROR_API_EXCEPTION;
   static_assert(sizeof(LuminaryMeshRefitStats) == sizeof(LumMeshRefitStats), "the public struct mirrors the core's");
+  std::memcpy(out, &s, sizeof(s));
+  return LUMINARY_SUCCESS;
+}
+LuminaryResult luminary_ext_set_instance_transforms(LuminaryHost* host, const LuminaryInstance* instances, uint32_t count) {
+  CHECK_NULL(host);
+  ApiLock lock(host);
+  if (!instances && count) return LUMINARY_ERROR_INVALID_API_ARGUMENT;
+  const lum::HostScene& sc = host->scene;
+  for (uint32_t k = 0; k < count; k++) {  // all of them before anything changes
+    const LuminaryInstance& in = instances[k];
+    if (in.id >= sc.instances.size()) return LUMINARY_ERROR_INVALID_API_ARGUMENT;
+    const lum::HostInstance& i = sc.instances[in.id];
+    if (!i.active || i.mesh_id >= sc.meshes.size() || in.mesh_id != i.mesh_id) return LUMINARY_ERROR_INVALID_API_ARGUMENT;  // (an instance that points at no mesh is inactive: scene.cpp)
+    const float f[9] = {in.position.x, in.position.y, in.position.z, in.rotation.x, in.rotation.y, in.rotation.z, in.scale.x, in.scale.y, in.scale.z};
+    for (float x : f) if (!std::isfinite(x)) return LUMINARY_ERROR_INVALID_API_ARGUMENT;
+  }
+  if (count == 0) return LUMINARY_SUCCESS;
+  for (uint32_t k = 0; k < count; k++) {
+    lum::HostInstance& i = host->scene.instances[instances[k].id];
+    i.translation = instances[k].position; i.rotation = instances[k].rotation; i.scale = instances[k].scale;
+  }
+  invalidate(host, LUMC_DIRTY_INSTANCE_TRANSFORMS | LUMC_DIRTY_LIGHTS);  // the transforms and the top-level tree; the light tree follows moved emitters
+  return LUMINARY_SUCCESS;
+}
+LuminaryResult luminary_ext_set_instance_update(LuminaryHost* host, uint32_t mode) {
+  CHECK_NULL(host);
+  ApiLock lock(host);
+  if (mode > 1) return LUMINARY_ERROR_INVALID_API_ARGUMENT;
+  host->instance_update_mode = mode;  // (decides how the next moved instances are taken over: no restart)
+  return LUMINARY_SUCCESS;
+}
+LuminaryResult luminary_ext_get_instance_update_stats(LuminaryHost* host, LuminaryInstanceUpdateStats* out) {
+  CHECK_NULL(host); CHECK_NULL(out);
+  ApiLock lock(host);
+  std::memset(out, 0, sizeof(*out));
+  if (!host->core) return LUMINARY_SUCCESS;
+  LumInstanceUpdateStats s;
+  if (lumc_instance_update_stats(host->core, &s)) return LUMINARY_ERROR_API_EXCEPTION;
+  static_assert(sizeof(LuminaryInstanceUpdateStats) == sizeof(LumInstanceUpdateStats), "the public struct mirrors the core's");
   std::memcpy(out, &s, sizeof(s));
   return LUMINARY_SUCCESS;
 }

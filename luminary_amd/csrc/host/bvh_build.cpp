@@ -1030,7 +1030,70 @@ SceneTree assemble_scene_tree(const LumDeviceSceneView& v, const Bvh4* const* me
   return out;
 }
 
+void layout_resident_nodes(const LumDeviceSceneView& v, const Bvh4* const* mesh_bvh, uint32_t capacity, std::vector<Bvh4Node>& out, std::vector<uint32_t>& mesh_root) {
+  // ---- every mesh's tree behind one another, indices relative to the first of them ----
+  std::vector<Bvh4Node> nodes;
+  std::vector<uint32_t> base((size_t) v.num_meshes + 1, 0);
+  for (uint32_t m = 0; m < v.num_meshes; m++) {
+    const uint32_t t0 = v.mesh_tri_offset[m];
+    base[m] = (uint32_t) nodes.size();
+    for (Bvh4Node n : mesh_bvh[m]->nodes) {
+      for (int k = 0; k < 4; k++) {
+        if (n.child[k] == kBvhEmpty) continue;
+        if (n.child[k] & kBvhLeafBit) n.child[k] += t0;
+        else n.child[k] += base[m];
+      }
+      nodes.push_back(n);
+    }
+  }
+  base[v.num_meshes] = (uint32_t) nodes.size();
+  // ---- the tops of the meshes first ----
+  const size_t n = nodes.size();
+  const size_t budget = std::min<size_t>(n, capacity < 4096u ? 4096u - capacity : 0u);
+  std::vector<uint32_t> order;
+  std::vector<uint8_t> seen(n, 0);
+  order.reserve(n);
+  for (uint32_t m = 0; m < v.num_meshes && order.size() < budget; m++)
+    if (base[m + 1] > base[m]) { seen[base[m]] = 1; order.push_back(base[m]); }
+  for (size_t head = 0; head < order.size() && order.size() < budget; head++)
+    for (int k = 0; k < 4; k++) {
+      const uint32_t next = nodes[order[head]].child[k];
+      if (next == kBvhEmpty || (next & kBvhLeafBit) || next >= n) continue;
+      if (!seen[next]) { seen[next] = 1; order.push_back(next); }
+    }
+  for (uint32_t i = 0; i < n; i++) if (!seen[i]) order.push_back(i);
+  std::vector<uint32_t> new_index(n);
+  for (uint32_t i = 0; i < n; i++) new_index[order[i]] = i;
+  Bvh4Node empty;
+  for (int k = 0; k < 4; k++) {
+    empty.child[k] = kBvhEmpty; empty.pad[k] = 0;
+    empty.lo_x[k] = empty.lo_y[k] = empty.lo_z[k] = FLT_MAX;
+    empty.hi_x[k] = empty.hi_y[k] = empty.hi_z[k] = -FLT_MAX;
+  }
+  out.assign((size_t) capacity + n, empty);
+  for (uint32_t i = 0; i < n; i++) {
+    Bvh4Node node = nodes[order[i]];
+    for (int k = 0; k < 4; k++)
+      if (node.child[k] != kBvhEmpty && !(node.child[k] & kBvhLeafBit)) node.child[k] = capacity + new_index[node.child[k]];
+    out[(size_t) capacity + i] = node;
+  }
+  mesh_root.assign((size_t) v.num_meshes + 1, capacity);
+  for (uint32_t m = 0; m < v.num_meshes; m++) if (base[m + 1] > base[m]) mesh_root[m] = capacity + new_index[base[m]];
+}
+
 }  // namespace lum
+
+// lum_core.h lumc_host_bvh_nodes_probe: the host builder's nodes themselves (tests/test_instance_update_gpu.py: the top level a device update must reproduce)
+extern "C" int lumc_host_bvh_nodes_probe(const float* boxes, uint32_t count, uint32_t max_leaf, uint32_t max_depth, uint64_t sizes[3], void* nodes, uint32_t* prims) {
+  using namespace lum;
+  if (!sizes || (count && !boxes)) return 1;
+  const Bvh4 t = build_bvh4(reinterpret_cast<const Aabb*>(boxes), count, max_leaf, max_depth);
+  if (t.nodes.empty() || t.nodes.size() > std::max<size_t>(count, 1) || t.prims.size() > count) return 1;
+  sizes[0] = t.nodes.size(); sizes[1] = t.prims.size(); sizes[2] = t.max_depth;
+  if (nodes) std::memcpy(nodes, t.nodes.data(), sizeof(Bvh4Node) * t.nodes.size());
+  if (prims && !t.prims.empty()) std::memcpy(prims, t.prims.data(), sizeof(uint32_t) * t.prims.size());
+  return 0;
+}
 
 // lum_core.h lumc_scene_tree_probe: the scene's tree as the upload assembles it, from the host builder's per-mesh trees (tests/test_scene_tree.py)
 extern "C" int lumc_scene_tree_probe(const LumDeviceSceneView* v, uint64_t sizes[4], void* nodes, void* tris, void* leaves, void* rows, uint32_t* mesh_root, float bounds[6]) {

@@ -51,6 +51,11 @@ Bvh4 build_bvh4_ploc(const Aabb* boxes, uint32_t count, uint32_t max_leaf = kBvh
 // The host builder's binned SAH, level by level on the device (lbvh.hip): for meshes without degenerate sets the same binary tree and leaf order as
 // build_bvh4, in tens of milliseconds. Empty result when the tree is deeper than `max_depth` 4-wide levels or a HIP call fails (the caller falls back).
 Bvh4 build_bvh4_sah_gpu(const Aabb* boxes, uint32_t count, uint32_t max_leaf = kBvhLeafMaxTri, uint32_t max_depth = 20);
+// Its device-in / device-out core (build_bvh4_sah_gpu is upload + this + download): count >= 2 boxes already on the current device; the nodes are left on the
+// device at d_nodes_out[0, *num_nodes) (false, and nothing written, when they are more than node_capacity), the primitive ids in leaf order at d_prims_out[0, count).
+// False when the tree is deeper than max_depth or a HIP call fails. Synchronises the device (one counter download per level).
+bool build_bvh4_sah_device(const Aabb* d_boxes, uint32_t count, uint32_t max_leaf, uint32_t max_depth, Bvh4Node* d_nodes_out, uint32_t node_capacity, uint32_t* d_prims_out,
+                           uint32_t* num_nodes, uint32_t* depth);
 
 // ---- refit: new boxes under an unchanged topology (moved vertices, luminary_ext_set_mesh_positions) ----
 // The tree with the same child words, prims and max_depth; every occupied child box = the builders' pad of the exact union (min / max) of the primitive boxes
@@ -107,5 +112,11 @@ struct SceneTree {
 // Top-level tree over the instances of `v` that can be hit (mesh id in range, mesh not empty, invertible transform), concatenated with the per-mesh trees
 // (node indices relative to the mesh, leaf ranges relative to its first triangle) and renumbered. Empty (nodes.empty()) when the top level exceeds 16 levels.
 SceneTree assemble_scene_tree(const LumDeviceSceneView& v, const Bvh4* const* mesh_bvh, const Aabb* mesh_box);
+
+// The resident layout of the scene's node array (LUMC_DIRTY_INSTANCE_TRANSFORMS, instance_update.hip): slots [0, capacity) are the top level's - empty nodes here -,
+// [capacity, capacity + M) hold every mesh's tree with absolute child indices and leaf ranges rebased by mesh_tri_offset, ordered so that the tops of the meshes
+// come first (one breadth-first walk from the mesh roots while capacity + nodes stays within the 4096 of assemble_scene_tree, the rest in mesh order).
+// mesh_root: num_meshes + 1 absolute indices.
+void layout_resident_nodes(const LumDeviceSceneView& v, const Bvh4* const* mesh_bvh, uint32_t capacity, std::vector<Bvh4Node>& nodes, std::vector<uint32_t>& mesh_root);
 
 }  // namespace lum

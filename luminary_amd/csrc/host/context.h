@@ -18,6 +18,7 @@
 #include "bvh_build.h"
 #include "bvh_refit.h"
 #include "device_buffer.h"
+#include "instance_update.h"
 #include "work_layout.h"
 
 using namespace lum;
@@ -54,6 +55,11 @@ struct LumContext {
   uint32_t refit_mode = 0;                   // lumc_set_mesh_refit
   float refit_max_cost_growth = 0.0f;
   LumMeshRefitStats refit_stats{};
+  // LUMC_DIRTY_INSTANCE_TRANSFORMS updates (instance_update.hip; scene_device.hip update_instance_transforms)
+  InstanceUpdate instance_update;            // the resident layout's bookkeeping and the device path's scratch
+  std::vector<uint32_t> instance_mesh_ids;   // of the scene on the device: such an update must bring the same
+  uint32_t instance_update_mode = 0;         // lumc_set_instance_update
+  LumInstanceUpdateStats instance_stats{};
   std::vector<uint32_t> sky_lut_key;  // the sky parameters the two sky tables were generated from
   DeviceBuffer<float> d_bridge_lut;   // the bridge sampler's vertex-count table (context-owned: scene.bridge_lut points here while bridges are possible)
   std::vector<float> bridge_lut_host; // its content, to notice a caller that hands over another table

@@ -681,9 +681,11 @@ __global__ void k_sah_export(const SahNode* __restrict__ nodes, uint32_t count, 
 
 }  // namespace
 
-Bvh4 build_bvh4_sah_gpu(const Aabb* boxes, uint32_t count, uint32_t max_leaf, uint32_t max_depth) {
-  Bvh4 result;
-  if (count < 2) return build_bvh4(boxes, count, max_leaf, max_depth);
+namespace {
+// The build itself, everything on the device: `boxes` (count >= 2 of them, host or device memory as `boxes_kind` says) in; out, inside `pool` (which this call
+// allocates and the caller frees): the 4-wide nodes, the primitive ids in leaf order, their counts. False when the tree is deeper than max_depth or a HIP call fails.
+bool sah_build_on_device(const Aabb* boxes, hipMemcpyKind boxes_kind, uint32_t count, uint32_t max_leaf, uint32_t max_depth, DeviceBuffer<char>& pool,
+                         const Bvh4Node** out_nodes, const uint32_t** out_prims, uint32_t* out_node_count, uint32_t* out_depth) {
   max_leaf = max_leaf < 1 ? 1 : (max_leaf > kBvhLeafMaxTri ? kBvhLeafMaxTri : max_leaf);
   const uint32_t n = count;
   const size_t max_nodes2 = 2 * (size_t) count + 2;  // binary nodes
@@ -695,7 +697,6 @@ Bvh4 build_bvh4_sah_gpu(const Aabb* boxes, uint32_t count, uint32_t max_leaf, ui
   CollapseItem* d_queue[2] = {nullptr, nullptr}; Bvh4Node* d_nodes = nullptr;
   int* d_plan_done = nullptr; float4* d_plan = nullptr;
   const bool optimal = collapse_rule_optimal();
-  DeviceBuffer<char> pool;
   size_t scan_bytes = 0;
   bool ok = true;
   const int threads = 256;
@@ -728,7 +729,7 @@ Bvh4 build_bvh4_sah_gpu(const Aabb* boxes, uint32_t count, uint32_t max_leaf, ui
     d_children = (int2*) (d_pool + o_children); d_ranges = (int2*) (d_pool + o_ranges); d_node_box = (BinBox*) (d_pool + o_node_box);
     d_nodes = (Bvh4Node*) (d_pool + o_nodes); d_scan_temp = (void*) (d_pool + o_scan);
   }
-  LBVH_TRY(hipMemcpy(d_boxes[0], boxes, sizeof(BinBox) * n, hipMemcpyHostToDevice));
+  LBVH_TRY(hipMemcpy(d_boxes[0], boxes, sizeof(BinBox) * n, boxes_kind));
   {
     std::vector<uint32_t> ids(n);
     for (uint32_t i = 0; i < n; i++) ids[i] = i;
@@ -800,14 +801,36 @@ Bvh4 build_bvh4_sah_gpu(const Aabb* boxes, uint32_t count, uint32_t max_leaf, ui
     if (node_count > max_nodes4) { ok = false; goto done; }
     LBVH_TRY(hipMemset(d_counters, 0, sizeof(uint32_t)));
   }
+  *out_nodes = d_nodes; *out_prims = d_ids[cur]; *out_node_count = node_count; *out_depth = depth;
+done:
+  return ok;
+}
+}  // namespace
+
+Bvh4 build_bvh4_sah_gpu(const Aabb* boxes, uint32_t count, uint32_t max_leaf, uint32_t max_depth) {
+  if (count < 2) return build_bvh4(boxes, count, max_leaf, max_depth);
+  Bvh4 result;
+  DeviceBuffer<char> pool;
+  const Bvh4Node* d_nodes = nullptr; const uint32_t* d_prims = nullptr;
+  uint32_t node_count = 0, depth = 0;
+  if (!sah_build_on_device(boxes, hipMemcpyHostToDevice, count, max_leaf, max_depth, pool, &d_nodes, &d_prims, &node_count, &depth)) return Bvh4();
   result.nodes.resize(node_count);
   result.prims.resize(count);
-  LBVH_TRY(hipMemcpy(result.nodes.data(), d_nodes, sizeof(Bvh4Node) * node_count, hipMemcpyDeviceToHost));
-  LBVH_TRY(hipMemcpy(result.prims.data(), d_ids[cur], sizeof(uint32_t) * count, hipMemcpyDeviceToHost));
+  if (hipMemcpy(result.nodes.data(), d_nodes, sizeof(Bvh4Node) * node_count, hipMemcpyDeviceToHost) != hipSuccess) return Bvh4();
+  if (hipMemcpy(result.prims.data(), d_prims, sizeof(uint32_t) * count, hipMemcpyDeviceToHost) != hipSuccess) return Bvh4();
   result.max_depth = depth;
-done:
-  if (!ok) return Bvh4();
   return result;
+}
+
+bool build_bvh4_sah_device(const Aabb* d_boxes, uint32_t count, uint32_t max_leaf, uint32_t max_depth, Bvh4Node* d_nodes_out, uint32_t node_capacity, uint32_t* d_prims_out,
+                           uint32_t* num_nodes, uint32_t* depth) {
+  if (count < 2 || !d_boxes || !d_nodes_out || !d_prims_out) return false;
+  DeviceBuffer<char> pool;
+  const Bvh4Node* d_nodes = nullptr; const uint32_t* d_prims = nullptr;
+  if (!sah_build_on_device(d_boxes, hipMemcpyDeviceToDevice, count, max_leaf, max_depth, pool, &d_nodes, &d_prims, num_nodes, depth)) return false;
+  if (*num_nodes > node_capacity) return false;
+  if (hipMemcpy(d_nodes_out, d_nodes, sizeof(Bvh4Node) * *num_nodes, hipMemcpyDeviceToDevice) != hipSuccess) return false;
+  return hipMemcpy(d_prims_out, d_prims, sizeof(uint32_t) * count, hipMemcpyDeviceToDevice) == hipSuccess;
 }
 
 Bvh4 build_bvh4_lbvh(const Aabb* boxes, uint32_t count, uint32_t max_leaf, uint32_t max_depth) { return build_on_device(boxes, count, max_leaf, max_depth, false); }

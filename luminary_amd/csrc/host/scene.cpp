@@ -1045,6 +1045,10 @@ std::string update_device_scene(const HostScene& scene, const std::vector<uint32
     encode_transform(inst, b.instance_transforms.data() + 8 * i);
   }
   }
+  else if (dirty & LUMC_DIRTY_INSTANCE_TRANSFORMS) {  // moved instances (luminary_ext_set_instance_transforms): the transforms and nothing else of the instance part
+    if (b.instance_transforms.size() == scene.instances.size() * 8)
+      for (size_t i = 0; i < scene.instances.size(); i++) encode_transform(scene.instances[i], b.instance_transforms.data() + 8 * i);
+  }
   if (dirty & LUMC_DIRTY_MATERIALS) {
     b.materials.resize(scene.materials.size() * 16);
     for (size_t i = 0; i < scene.materials.size(); i++) encode_material(scene.materials[i], b.materials.data() + 16 * i);

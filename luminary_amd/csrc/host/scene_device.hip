@@ -90,6 +90,7 @@ void free_scene(LumContext* ctx) {
   ctx->sky_lut_key.clear();
   ctx->d_bridge_lut.reset(); ctx->bridge_lut_host.clear();
   ctx->mesh_bvh.clear(); ctx->mesh_box.clear(); ctx->mesh_refit.clear(); ctx->mesh_tri_offset.clear();
+  ctx->instance_update.reset(); ctx->instance_mesh_ids.clear();
   ctx->has_scene = false;
 }
 
@@ -203,6 +204,8 @@ static int update_mesh_arrays(LumContext* ctx, const LumDeviceSceneView* v) {
 static int update_instance_arrays(LumContext* ctx, const LumDeviceSceneView* v) {
   DeviceScene& sc = ctx->scene;
   ctx->scene_allocs[LumContext::kGrpInst].clear();
+  ctx->instance_update.resident = ctx->instance_update.prepared = false;  // (the node array and the leaf records went with the group; the meshes' boxes may have changed)
+  ctx->instance_mesh_ids.assign(v->instance_mesh_ids, v->instance_mesh_ids + v->num_instances);
   if (upload(ctx, LumContext::kGrpInst, v->instance_mesh_ids, v->num_instances, &sc.instance_mesh_ids)) return 1;
   return upload(ctx, LumContext::kGrpInst, (const float4*) v->instance_transforms, (size_t) v->num_instances * 2, &sc.instance_transforms);
 }
@@ -399,6 +402,7 @@ static int update_scene_tree(LumContext* ctx, const LumDeviceSceneView* v, bool 
   if (ctx->mesh_box.size() != v->num_meshes || ctx->mesh_bvh.size() != v->num_meshes) { ctx->error = "lumc_scene_update: the meshes changed but LUMC_DIRTY_MESHES is not set"; return 1; }
   std::vector<const Bvh4*> mesh_bvh(v->num_meshes);
   for (uint32_t m = 0; m < v->num_meshes; m++) mesh_bvh[m] = &ctx->mesh_bvh[m]->bvh;
+  ctx->instance_update.resident = false;
   const SceneTree tree = assemble_scene_tree(*v, mesh_bvh.data(), ctx->mesh_box.data());
   if (tree.nodes.empty()) { ctx->error = "top-level BVH exceeds 16 levels"; return 1; }
   if (total_triangles(v) >= (1u << 28) || tree.nodes.size() >= (1u << 25)) { ctx->error = "scene too large for 28-bit leaf ranges / 32-bit node offsets"; return 1; }
@@ -437,6 +441,101 @@ static int update_ray_kernel_lds(LumContext* ctx, size_t num_nodes) {
   return 0;
 }
 
+// ---- LUMC_DIRTY_INSTANCE_TRANSFORMS (lum_core.h lumc_set_instance_update; instance_update.hip) ----
+// The resident layout: the node array laid out once on the host so that the top level has a range of its own, [0, C), and the mesh trees, [C, C + M), need not
+// be written again; the leaf records get room for every instance. Replaces both arrays in the instances' group; costs what an instance edit costs.
+static int relayout_resident(LumContext* ctx, const LumDeviceSceneView* v) {
+  DeviceScene& sc = ctx->scene;
+  InstanceUpdate& u = ctx->instance_update;
+  u.resident = false;
+  const uint32_t n = v->num_instances, capacity = std::max<uint32_t>(1u, n > 0 ? n - 1u : 0u);
+  std::vector<const Bvh4*> mesh_bvh(v->num_meshes);
+  for (uint32_t m = 0; m < v->num_meshes; m++) mesh_bvh[m] = &ctx->mesh_bvh[m]->bvh;
+  std::vector<Bvh4Node> nodes;
+  std::vector<uint32_t> mesh_root;
+  layout_resident_nodes(*v, mesh_bvh.data(), capacity, nodes, mesh_root);
+  if (total_triangles(v) >= (1u << 28) || nodes.size() >= (1u << 25)) { ctx->error = "scene too large for 28-bit leaf ranges / 32-bit node offsets"; return 1; }
+  auto& group = ctx->scene_allocs[LumContext::kGrpInst];
+  group.erase(std::remove_if(group.begin(), group.end(), [&](const DeviceBuffer<char>& b) {
+    return b.get() == reinterpret_cast<const char*>(sc.bvh_nodes) || b.get() == reinterpret_cast<const char*>(sc.tlas_leaves); }), group.end());
+  sc.bvh_nodes = nullptr; sc.tlas_leaves = nullptr;
+  if (upload(ctx, LumContext::kGrpInst, nodes.data(), nodes.size(), &sc.bvh_nodes)) return 1;
+  DeviceBuffer<char> leaves;
+  HIP_TRY(ctx, leaves.resize(sizeof(float4) * 4 * ((size_t) n + 1)));
+  HIP_TRY(ctx, hipMemset(leaves.get(), 0, sizeof(float4) * 4 * ((size_t) n + 1)));
+  sc.tlas_leaves = reinterpret_cast<const float4*>(leaves.get());
+  group.push_back(std::move(leaves));
+  HIP_TRY(ctx, u.mesh_root.assign(mesh_root.data(), v->num_meshes));
+  u.capacity = capacity; u.mesh_nodes = (uint32_t) (nodes.size() - capacity); u.tlas_nodes = 0;
+  if (update_ray_kernel_lds(ctx, nodes.size())) return 1;
+  u.resident = true;
+  return 0;
+}
+
+// One update on the device: the transforms into the array that is there, then rows, boxes, top level and leaf records derived from them in place. *fell_back: the
+// device path could not take this update (fewer than two instances that can be hit, a top level deeper than 16, a failed allocation): nothing the scene points
+// at is left half written that the host path, which the caller runs then, does not replace.
+static int update_instance_transforms(LumContext* ctx, const LumDeviceSceneView* v, bool* fell_back) {
+  using clock = std::chrono::steady_clock;
+  auto since = [](clock::time_point t) { return std::chrono::duration<double>(clock::now() - t).count(); };
+  DeviceScene& sc = ctx->scene;
+  InstanceUpdate& u = ctx->instance_update;
+  LumInstanceUpdateStats& st = ctx->instance_stats;
+  st.seconds = st.seconds_relayout = st.seconds_upload = st.seconds_boxes = st.seconds_build = st.seconds_leaves = 0.0;
+  *fell_back = false;
+  const uint32_t n = v->num_instances;
+  if (n != sc.num_instances || ctx->instance_mesh_ids.size() != n || ctx->mesh_bvh.size() != v->num_meshes || ctx->mesh_box.size() != v->num_meshes ||
+      (n && std::memcmp(ctx->instance_mesh_ids.data(), v->instance_mesh_ids, sizeof(uint32_t) * n) != 0)) {
+    ctx->error = "lumc_scene_update: LUMC_DIRTY_INSTANCE_TRANSFORMS with another instance count or other mesh ids than the scene on the device";
+    return 1;
+  }
+  const auto t_all = clock::now();
+  if (!u.prepared || u.num_instances != n || u.num_meshes != v->num_meshes) {  // (every path that changes the meshes or the instance count drops `prepared`)
+    u.reset();
+    if (instance_update_prepare(u, n, v->num_meshes, ctx->mesh_box.data()) != hipSuccess) { (void) hipGetLastError(); u.reset(); *fell_back = true; return 0; }
+  }
+  auto t = clock::now();
+  if (n) HIP_TRY(ctx, hipMemcpy(const_cast<float4*>(sc.instance_transforms), v->instance_transforms, sizeof(float4) * 2 * (size_t) n, hipMemcpyHostToDevice));
+  HIP_TRY(ctx, hipDeviceSynchronize());
+  st.seconds_upload = since(t);
+  t = clock::now();
+  uint32_t hittable = 0;
+  Aabb world;
+  HIP_TRY(ctx, instance_update_boxes(u, sc.instance_transforms, sc.instance_mesh_ids, sc.mesh_tri_offset, const_cast<float4*>(sc.instance_rows), &hittable, &world));
+  st.seconds_boxes = since(t);
+  if (hittable < 2) { *fell_back = true; return 0; }  // (before the layout: a scene of one instance never pays for one)
+  if (!u.resident) {
+    t = clock::now();
+    if (relayout_resident(ctx, v)) { (void) hipGetLastError(); ctx->error.clear(); *fell_back = true; return 0; }  // (the host path replaces whatever this left, or fails for the same reason)
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    st.relayouts++;
+    st.seconds_relayout = since(t);
+  }
+  t = clock::now();
+  uint32_t num_nodes = 0, depth = 0;
+  Bvh4Node* d_nodes = const_cast<Bvh4Node*>(sc.bvh_nodes);
+  if (!build_bvh4_sah_device(u.dense_boxes.get(), hittable, 1, 16, d_nodes, u.capacity, u.prims.get(), &num_nodes, &depth)) {
+    (void) hipGetLastError();
+    *fell_back = true;
+    return 0;
+  }
+  st.seconds_build = since(t);
+  t = clock::now();
+  HIP_TRY(ctx, instance_update_leaves(u, hittable, sc.instance_rows, sc.instance_mesh_ids, const_cast<float4*>(sc.tlas_leaves), d_nodes, num_nodes, std::max(num_nodes, u.tlas_nodes)));
+  HIP_TRY(ctx, hipDeviceSynchronize());
+  st.seconds_leaves = since(t);
+  u.tlas_nodes = num_nodes;
+  sc.tlas_num_nodes = num_nodes;
+  sc.tlas_num_leaves = hittable + 1u;  // (one of padding)
+  std::memcpy(ctx->sort.world_lo, world.lo, sizeof(ctx->sort.world_lo)); std::memcpy(ctx->sort.world_hi, world.hi, sizeof(ctx->sort.world_hi));
+  ctx->bvh_stats[0] = u.mesh_nodes;
+  ctx->bvh_stats[2] = num_nodes;
+  st.device_updates++;
+  st.tlas_nodes = num_nodes; st.tlas_depth = depth; st.tlas_capacity = u.capacity; st.hittable = hittable;
+  st.seconds = since(t_all);
+  return 0;
+}
+
 // Light-only BVH (world-space triangles; reference: optix_bvh.c:382-478), in the light tree's group.
 static int update_light_bvh(LumContext* ctx, const LumDeviceSceneView* v) {
   DeviceScene& sc = ctx->scene;
@@ -467,7 +566,7 @@ static int update_counts_and_tables(LumContext* ctx, const LumDeviceSceneView* v
     hipLaunchKernelGGL(k_tri_opacity, dim3((total_tris + kBlock - 1) / kBlock), dim3(kBlock), 0, 0, sc, const_cast<BvhTri*>(sc.blas_tris), total_tris);
     HIP_TRY(ctx, hipGetLastError());
   }
-  if ((dirty_lights || ((dirty & (LUMC_DIRTY_MATERIALS | LUMC_DIRTY_INSTANCES | LUMC_DIRTY_MESHES)) && sc.light_tri_table)) && sc.light_tree_root && sc.num_lights) {  // the emissive triangles in world space with what their material says, one record per light (load_tri_light_table)
+  if ((dirty_lights || ((dirty & (LUMC_DIRTY_MATERIALS | LUMC_DIRTY_INSTANCES | LUMC_DIRTY_INSTANCE_TRANSFORMS | LUMC_DIRTY_MESHES)) && sc.light_tri_table)) && sc.light_tree_root && sc.num_lights) {  // the emissive triangles in world space with what their material says, one record per light (load_tri_light_table)
     float4* table = const_cast<float4*>(sc.light_tri_table);  // a material edit alone refills the table in place (same lights)
     if (dirty_lights) {
       DeviceBuffer<char> records;
@@ -711,6 +810,10 @@ static int scene_update(LumContext* ctx, const LumDeviceSceneView* v, unsigned d
   if (dirty & LUMC_DIRTY_MESHES) dirty &= ~(unsigned) LUMC_DIRTY_MESH_POSITIONS;  // a full rebuild of the meshes covers moved vertices
   if (dirty & (LUMC_DIRTY_MESHES | LUMC_DIRTY_MESH_POSITIONS)) dirty |= LUMC_DIRTY_INSTANCES;  // the assembled node array holds the per-mesh trees
   if (dirty & LUMC_DIRTY_PARTICLES) dirty |= LUMC_DIRTY_CONSTANTS;
+  if (dirty & (LUMC_DIRTY_INSTANCES | LUMC_DIRTY_MESHES)) dirty &= ~(unsigned) LUMC_DIRTY_INSTANCE_TRANSFORMS;  // the instance part covers moved instances
+  const bool moved_by_host = (dirty & LUMC_DIRTY_INSTANCE_TRANSFORMS) && ctx->instance_update_mode == 1;  // mode 1: exactly LUMC_DIRTY_INSTANCES; its time is reported
+  if (moved_by_host) { dirty = (dirty & ~(unsigned) LUMC_DIRTY_INSTANCE_TRANSFORMS) | LUMC_DIRTY_INSTANCES; ctx->instance_stats.seconds = ctx->instance_stats.seconds_relayout = ctx->instance_stats.seconds_upload = ctx->instance_stats.seconds_boxes = ctx->instance_stats.seconds_build = ctx->instance_stats.seconds_leaves = 0.0; }
+  auto host_path_since = [&](std::chrono::steady_clock::time_point t) { if (moved_by_host) ctx->instance_stats.seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count(); };
   const bool meshes = (dirty & LUMC_DIRTY_MESHES) != 0, instances = (dirty & LUMC_DIRTY_INSTANCES) != 0, lights = (dirty & LUMC_DIRTY_LIGHTS) != 0;
   ctx->has_scene = false;
   if (meshes && update_mesh_arrays(ctx, v)) return 1;
@@ -719,7 +822,9 @@ static int scene_update(LumContext* ctx, const LumDeviceSceneView* v, unsigned d
     if (refit_mesh_trees(ctx, v, &rebuilt)) return 1;
     if (rebuilt) dirty |= kDirtyTrianglesRewritten;
   }
+  const auto t_arrays = std::chrono::steady_clock::now();
   if (instances && update_instance_arrays(ctx, v)) return 1;
+  host_path_since(t_arrays);
   if ((dirty & LUMC_DIRTY_MATERIALS) && update_materials(ctx, v)) return 1;
   const bool time_lights = (dirty & LUMC_DIRTY_MESH_POSITIONS) != 0;
   auto lights_since = [&](std::chrono::steady_clock::time_point t) { if (time_lights) ctx->refit_stats.seconds_lights += std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count(); };
@@ -731,6 +836,18 @@ static int scene_update(LumContext* ctx, const LumDeviceSceneView* v, unsigned d
   size_t num_nodes = 0;
   const auto t_assemble = std::chrono::steady_clock::now();
   if (instances && (update_scene_tree(ctx, v, meshes, &num_nodes) || update_ray_kernel_lds(ctx, num_nodes))) return 1;
+  if (moved_by_host) { HIP_TRY(ctx, hipDeviceSynchronize()); host_path_since(t_assemble); }
+  if (dirty & LUMC_DIRTY_INSTANCE_TRANSFORMS) {
+    bool fell_back = false;
+    if (update_instance_transforms(ctx, v, &fell_back)) return 1;
+    if (fell_back) {  // this one update by the host's path, as LUMC_DIRTY_INSTANCES
+      const bool prepared = ctx->instance_update.prepared;  // (the meshes did not change: the scratch and their boxes serve the next update)
+      if (update_instance_arrays(ctx, v) || update_scene_tree(ctx, v, false, &num_nodes) || update_ray_kernel_lds(ctx, num_nodes)) return 1;
+      ctx->instance_update.prepared = prepared;
+      ctx->instance_stats.fallbacks++;
+      ctx->instance_stats.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_assemble).count();
+    }
+  }
   if (dirty & LUMC_DIRTY_MESH_POSITIONS) ctx->refit_stats.seconds_assemble = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_assemble).count();
   t_lights = std::chrono::steady_clock::now();
   if (lights && update_light_bvh(ctx, v)) return 1;
@@ -757,7 +874,7 @@ int lumc_scene_update(LumContext* ctx, const LumDeviceSceneView* v, unsigned int
   if (!ctx->has_scene || (dirty & LUMC_DIRTY_ALL) == LUMC_DIRTY_ALL) return lumc_scene_upload(ctx, v);
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   HIP_TRY(ctx, hipDeviceSynchronize());  // nothing renders from the arrays that are about to be freed
-  if (scene_update(ctx, v, dirty & (LUMC_DIRTY_ALL | LUMC_DIRTY_MESH_POSITIONS))) { free_scene(ctx); return 1; }  // a failed partial update leaves no half-updated scene behind
+  if (scene_update(ctx, v, dirty & (LUMC_DIRTY_ALL | LUMC_DIRTY_MESH_POSITIONS | LUMC_DIRTY_INSTANCE_TRANSFORMS))) { free_scene(ctx); return 1; }  // a failed partial update leaves no half-updated scene behind
   return 0;
 }
 
@@ -771,6 +888,40 @@ int lumc_set_mesh_refit(LumContext* ctx, uint32_t mode, float max_cost_growth) {
 int lumc_mesh_refit_stats(const LumContext* ctx, LumMeshRefitStats* out) {
   if (!ctx || !out) return 1;
   *out = ctx->refit_stats;
+  return 0;
+}
+
+int lumc_set_instance_update(LumContext* ctx, uint32_t mode) {
+  if (!ctx) return 1;
+  if (mode > 1) { ctx->error = "lumc_set_instance_update: mode is 0 (device) or 1 (host assembly)"; return 1; }
+  ctx->instance_update_mode = mode;
+  return 0;
+}
+
+int lumc_instance_update_stats(const LumContext* ctx, LumInstanceUpdateStats* out) {
+  if (!ctx || !out) return 1;
+  *out = ctx->instance_stats;
+  return 0;
+}
+
+int lumc_resident_tree_probe(LumContext* ctx, uint64_t sizes[5], void* top_nodes, void* leaves, uint32_t* mesh_root, uint64_t* mesh_hash) {
+  if (!ctx || !sizes) return 1;
+  const InstanceUpdate& u = ctx->instance_update;
+  if (!ctx->has_scene || !u.resident) { ctx->error = "lumc_resident_tree_probe: the context has no resident layout"; return 1; }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const DeviceScene& sc = ctx->scene;
+  sizes[0] = u.capacity; sizes[1] = u.mesh_nodes; sizes[2] = sc.tlas_num_nodes; sizes[3] = sc.tlas_num_leaves; sizes[4] = ctx->instance_stats.tlas_depth;
+  if (sc.tlas_num_leaves > u.num_instances + 1u) { ctx->error = "lumc_resident_tree_probe: more leaf records than instances"; return 1; }
+  if (top_nodes) HIP_TRY(ctx, hipMemcpy(top_nodes, sc.bvh_nodes, sizeof(Bvh4Node) * u.capacity, hipMemcpyDeviceToHost));
+  if (leaves) HIP_TRY(ctx, hipMemcpy(leaves, sc.tlas_leaves, sizeof(float4) * 4 * (size_t) sc.tlas_num_leaves, hipMemcpyDeviceToHost));
+  if (mesh_root && u.num_meshes) HIP_TRY(ctx, hipMemcpy(mesh_root, u.mesh_root.get(), sizeof(uint32_t) * u.num_meshes, hipMemcpyDeviceToHost));
+  if (mesh_hash) {
+    std::vector<uint64_t> words((size_t) u.mesh_nodes * (sizeof(Bvh4Node) / 8));
+    if (!words.empty()) HIP_TRY(ctx, hipMemcpy(words.data(), sc.bvh_nodes + u.capacity, sizeof(Bvh4Node) * u.mesh_nodes, hipMemcpyDeviceToHost));
+    uint64_t h = 0xCBF29CE484222325ull;
+    for (uint64_t w : words) { h = (h ^ w) * 0x100000001B3ull; h ^= h >> 29; }
+    *mesh_hash = h;
+  }
   return 0;
 }
 

@@ -19,6 +19,7 @@
 #include "bvh_refit.h"
 #include "device_buffer.h"
 #include "instance_update.h"
+#include "scene_arrays.h"
 #include "work_layout.h"
 
 using namespace lum;
@@ -44,9 +45,7 @@ struct LumContext {
   const WavefrontKernels* wf = wavefront_kernels_fast();  // flavour of the wavefront kernels (lumc_set_flavour; LUM_FLAVOUR=exact|fast overrides the default)
   int camera = kCamThinLens;  // CameraKind of the camera-ray kernels (lumc_set_physical_camera)
   DeviceLens lens{};          // the physical camera's lens, an argument of those kernels
-  // device allocations of the scene by the part of it they belong to (lumc_scene_update frees and rebuilds a part at a time)
-  enum AllocGroup { kGrpMesh = 0, kGrpInst, kGrpMat, kGrpLight, kGrpTex, kGrpConst, kGrpPart, kGrpOnce, kGrpCount };
-  std::vector<DeviceBuffer<char>> scene_allocs[kGrpCount];
+  SceneArrays arrays;  // the scene's device arrays by the part of it they belong to (lumc_scene_update frees and rebuilds a part at a time); `scene` views them
   // what a partial update needs again: the per-mesh trees (node indices relative to the mesh, leaf ranges relative to its first triangle) and boxes
   std::vector<std::shared_ptr<const MeshTree>> mesh_bvh;
   std::vector<Aabb> mesh_box;

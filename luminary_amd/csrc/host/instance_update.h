@@ -1,5 +1,5 @@
 // Moved instances on the device (instance_update.hip): what a context keeps for LUMC_DIRTY_INSTANCE_TRANSFORMS updates, and the calls of the scene update
-// (scene_device.hip). The node array itself, the leaf records, the rows and the transforms belong to the scene (the instances' allocation group).
+// (scene_device.hip). The node array itself, the leaf records, the rows and the transforms belong to the scene (SceneArrays::inst).
 #pragma once
 
 #include <hip/hip_runtime_api.h>

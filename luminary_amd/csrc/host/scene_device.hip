@@ -72,19 +72,38 @@ constexpr size_t kCloudNoiseTexels[3] = {(size_t) kCloudShapeRes * kCloudShapeRe
                                          (size_t) kCloudWeatherRes * kCloudWeatherRes};  // shape, detail, weather (RGBA8 each)
 constexpr uint32_t kBsdfLutCount[4] = {1024, 1024, 32768, 32768};  // conductor, glossy, dielectric, dielectric_inv
 
-// A scene array on the device, owned by the allocation group it is registered under.
+// A scene array on the device: a copy of the host's in its owner (ctx->arrays), with the scene's view of it. No host array or no elements: empty and null.
 template <typename T>
-int upload(LumContext* ctx, int group, const T* host, size_t count, const T** out) {
-  *out = nullptr;
-  DeviceBuffer<char> d;
-  HIP_TRY(ctx, d.assign(reinterpret_cast<const char*>(host), sizeof(T) * count));
-  *out = reinterpret_cast<const T*>(d.get());
-  if (d) ctx->scene_allocs[group].push_back(std::move(d));
+int upload(LumContext* ctx, DeviceBuffer<T>& owner, const T* host, size_t count, const T** view) {
+  *view = nullptr;
+  HIP_TRY(ctx, owner.assign(host, count));
+  *view = owner.get();
   return 0;
 }
 
+// A part's views from its owners: null for a part of ctx->arrays that was just released (`arrays.lights = {}`), its arrays for a filled one.
+void point_views(DeviceScene& sc, const SceneArrays::Mesh& a) { sc.mesh_tri_offset = a.tri_offset.get(); sc.vertices = a.vertices.get(); sc.tri_tex = a.tri_tex.get(); sc.blas_tris = a.blas_tris.get(); }
+void point_views(DeviceScene& sc, const SceneArrays::Inst& a) {
+  sc.instance_mesh_ids = a.mesh_ids.get(); sc.instance_transforms = a.transforms.get(); sc.instance_rows = a.rows.get(); sc.tlas_leaves = a.tlas_leaves.get(); sc.bvh_nodes = a.nodes.get();
+}
+void point_views(DeviceScene& sc, const SceneArrays::Lights& a) {
+  sc.light_tree_root = a.tree_root.get(); sc.light_tree_nodes = a.tree_nodes.get(); sc.light_root_children = a.root_children.get(); sc.light_tri_handles = a.tri_handles.get();
+  sc.light_tri_table = a.tri_table.get(); sc.light_nodes = a.bvh_nodes.get(); sc.light_tris = a.bvh_tris.get();
+}
+void point_views(DeviceScene& sc, const SceneArrays::Textures& a) { sc.texture_table = a.table.get(); sc.texels = a.texels.get(); }
+void point_views(DeviceScene& sc, const SceneArrays::Constants& a) {  // (the caller's copies; where there is none update_constants' functions point at the context's own tables)
+  sc.sky_stars = a.stars.get(); sc.sky_stars_offsets = a.stars_offsets.get(); sc.sky_hdri = a.sky_hdri.get();
+  sc.cloud_noise_shape = a.cloud_noise[0].get(); sc.cloud_noise_detail = a.cloud_noise[1].get(); sc.cloud_noise_weather = a.cloud_noise[2].get();
+  sc.sky_lut_transmittance = a.sky_lut[0].get(); sc.sky_lut_multiscattering = a.sky_lut[1].get();
+}
+void point_views(DeviceScene& sc, const SceneArrays::Particles& a) {
+  sc.particle_bvh_nodes = a.nodes.get(); sc.particle_tris = a.tris.get(); sc.particle_leaves = a.leaves.get(); sc.particle_normals = a.normals.get();
+}
+
+void mesh_boxes_changed(LumContext* ctx) { ctx->instance_update.prepared = false; }  // the moved instances' scratch holds a copy of ctx->mesh_box
+
 void free_scene(LumContext* ctx) {
-  for (auto& group : ctx->scene_allocs) group.clear();
+  ctx->arrays = SceneArrays{};
   for (auto& t : ctx->d_luts) t.reset();
   for (auto& t : ctx->d_sky_lut) t.reset();
   ctx->sky_lut_key.clear();
@@ -131,8 +150,10 @@ int lumc_cloud_noise_generate(LumContext* ctx, uint32_t seed, uint32_t* shape, u
 // The particle tree (device_particle.c:23-131, optix_bvh.c's particle GAS / IAS): one bottom-level tree over the 2 x count triangles of the unit
 // cell, and a top level over its 25 x 25 x 25 integer translations, instance id = (xi * 25 + yi) * 25 + zi as the reference numbers them. The
 // top-level leaves hold the translation as an exact affine map (rows of the identity), so entering an instance is one subtraction per axis.
-static int build_particle_tree(LumContext* ctx, int group, const LumDeviceSceneView* v, DeviceScene& sc) {
-  sc.particle_bvh_nodes = nullptr; sc.particle_tris = nullptr; sc.particle_leaves = nullptr; sc.particle_tlas_num_nodes = 0; sc.particle_normals = nullptr;
+static int build_particle_tree(LumContext* ctx, const LumDeviceSceneView* v, DeviceScene& sc) {
+  SceneArrays::Particles& a = ctx->arrays.particles;
+  a = {}; point_views(sc, a);
+  sc.particle_tlas_num_nodes = 0;
   if (!sc.particles_active) return 0;
   if (!v->particle_vertices || !v->particle_normals) { ctx->error = "lumc_scene_upload: active particles without particle_vertices / particle_normals"; return 1; }
   const uint32_t nt = 2u * sc.particles_count;
@@ -177,10 +198,10 @@ static int build_particle_tree(LumContext* ctx, int group, const LumDeviceSceneV
     const uint32_t words[4] = {inst, base, 0u, 0u};
     std::memcpy(&leaves[4 * i + 3], words, 16);
   }
-  if (upload(ctx, group, nodes.data(), nodes.size(), &sc.particle_bvh_nodes)) return 1;
-  if (upload(ctx, group, tris.data(), tris.size(), &sc.particle_tris)) return 1;
-  if (upload(ctx, group, leaves.data(), leaves.size(), &sc.particle_leaves)) return 1;
-  if (upload(ctx, group, (const float4*) v->particle_normals, (size_t) sc.particles_count, &sc.particle_normals)) return 1;
+  if (upload(ctx, a.nodes, nodes.data(), nodes.size(), &sc.particle_bvh_nodes)) return 1;
+  if (upload(ctx, a.tris, tris.data(), tris.size(), &sc.particle_tris)) return 1;
+  if (upload(ctx, a.leaves, leaves.data(), leaves.size(), &sc.particle_leaves)) return 1;
+  if (upload(ctx, a.normals, (const float4*) v->particle_normals, (size_t) sc.particles_count, &sc.particle_normals)) return 1;
   sc.particle_tlas_num_nodes = (uint32_t) tlas.nodes.size();
   sc.particle_num_leaves = (uint32_t) (leaves.size() / 4);
   ctx->particle_lds_nodes = (uint32_t) std::min<size_t>(ctx->lds_nodes, nodes.size());
@@ -191,28 +212,31 @@ static int build_particle_tree(LumContext* ctx, int group, const LumDeviceSceneV
 // dirty keeps its device arrays and the fields of ctx->scene that point at them. ----
 static uint32_t total_triangles(const LumDeviceSceneView* v) { return v->num_meshes ? v->mesh_tri_offset[v->num_meshes] : 0; }
 
+// The meshes' vertex arrays. The traversal triangles stay: new meshes bring new ones (scene_update has released them, update_scene_tree uploads them), moved
+// vertices are written into the ones that are there (refit_mesh_trees).
 static int update_mesh_arrays(LumContext* ctx, const LumDeviceSceneView* v) {
   DeviceScene& sc = ctx->scene;
+  SceneArrays::Mesh& a = ctx->arrays.mesh;
   const uint32_t total_tris = total_triangles(v);
-  ctx->scene_allocs[LumContext::kGrpMesh].clear();
-  if (upload(ctx, LumContext::kGrpMesh, v->mesh_tri_offset, (size_t) v->num_meshes + 1, &sc.mesh_tri_offset)) return 1;
-  if (upload(ctx, LumContext::kGrpMesh, (const float4*) v->vertices, (size_t) total_tris * 3, &sc.vertices)) return 1;
-  return upload(ctx, LumContext::kGrpMesh, (const uint4*) v->tri_tex, (size_t) total_tris, &sc.tri_tex);
+  a.tri_offset.reset(); a.vertices.reset(); a.tri_tex.reset(); point_views(sc, a);
+  if (upload(ctx, a.tri_offset, v->mesh_tri_offset, (size_t) v->num_meshes + 1, &sc.mesh_tri_offset)) return 1;
+  if (upload(ctx, a.vertices, (const float4*) v->vertices, (size_t) total_tris * 3, &sc.vertices)) return 1;
+  return upload(ctx, a.tri_tex, (const uint4*) v->tri_tex, (size_t) total_tris, &sc.tri_tex);
 }
 
-// (the scene tree's arrays - update_scene_tree - belong to this group too: whenever the instances are dirty both parts run, this one first)
+// Releases the whole part; update_scene_tree, which runs whenever this does, uploads the rows, the node array and the leaf records.
 static int update_instance_arrays(LumContext* ctx, const LumDeviceSceneView* v) {
   DeviceScene& sc = ctx->scene;
-  ctx->scene_allocs[LumContext::kGrpInst].clear();
-  ctx->instance_update.resident = ctx->instance_update.prepared = false;  // (the node array and the leaf records went with the group; the meshes' boxes may have changed)
+  SceneArrays::Inst& a = ctx->arrays.inst;
+  a = {}; point_views(sc, a);
   ctx->instance_mesh_ids.assign(v->instance_mesh_ids, v->instance_mesh_ids + v->num_instances);
-  if (upload(ctx, LumContext::kGrpInst, v->instance_mesh_ids, v->num_instances, &sc.instance_mesh_ids)) return 1;
-  return upload(ctx, LumContext::kGrpInst, (const float4*) v->instance_transforms, (size_t) v->num_instances * 2, &sc.instance_transforms);
+  if (upload(ctx, a.mesh_ids, v->instance_mesh_ids, v->num_instances, &sc.instance_mesh_ids)) return 1;
+  return upload(ctx, a.transforms, (const float4*) v->instance_transforms, (size_t) v->num_instances * 2, &sc.instance_transforms);
 }
 
 static int update_materials(LumContext* ctx, const LumDeviceSceneView* v) {
-  ctx->scene_allocs[LumContext::kGrpMat].clear();
-  return upload(ctx, LumContext::kGrpMat, (const uint4*) v->materials, (size_t) v->num_materials * 2, &ctx->scene.materials);
+  ctx->arrays.materials = {};
+  return upload(ctx, ctx->arrays.materials.materials, (const uint4*) v->materials, (size_t) v->num_materials * 2, &ctx->scene.materials);
 }
 
 // The light tree's root children as floats (dev_light.h tree_prepass): mean = byte * 2^e + base per axis, sigma = byte * 2^e_sigma, power = the 16-bit
@@ -235,33 +259,34 @@ static int upload_light_root_children(LumContext* ctx, const LumDeviceSceneView*
       e[4] = (float) pw;
     }
   }
-  return upload(ctx, LumContext::kGrpLight, table.data(), table.size(), &ctx->scene.light_root_children);
+  return upload(ctx, ctx->arrays.lights.root_children, table.data(), table.size(), &ctx->scene.light_root_children);
 }
 
-// (the light BVH and k_light_table's records - update_light_bvh, update_counts_and_tables - belong to this group too and run whenever this part does)
+// Releases the whole part; update_light_bvh and update_counts_and_tables, which run whenever this does, bring the light BVH and k_light_table's records.
 static int update_light_tree(LumContext* ctx, const LumDeviceSceneView* v) {
   DeviceScene& sc = ctx->scene;
-  ctx->scene_allocs[LumContext::kGrpLight].clear();
-  sc.light_tree_root = nullptr; sc.light_root_children = nullptr; sc.light_tree_nodes = nullptr; sc.light_tri_handles = nullptr; sc.light_tri_table = nullptr;
-  sc.light_nodes = nullptr; sc.light_tris = nullptr; sc.light_num_nodes = 0;
+  SceneArrays::Lights& a = ctx->arrays.lights;
+  a = {}; point_views(sc, a);
+  sc.light_num_nodes = 0;
   if (!v->light_tree_root || !v->num_lights) return 0;
   const uint32_t sections = v->light_tree_root[10];
-  if (upload(ctx, LumContext::kGrpLight, (const uint4*) v->light_tree_root, (size_t) 1 + 3 * sections, &sc.light_tree_root)) return 1;
+  if (upload(ctx, a.tree_root, (const uint4*) v->light_tree_root, (size_t) 1 + 3 * sections, &sc.light_tree_root)) return 1;
   if (upload_light_root_children(ctx, v, sections)) return 1;
-  if (upload(ctx, LumContext::kGrpLight, (const uint4*) v->light_tree_nodes, (size_t) v->num_light_tree_nodes * 4, &sc.light_tree_nodes)) return 1;
-  return upload(ctx, LumContext::kGrpLight, (const uint2*) v->light_tri_handles, v->num_lights, &sc.light_tri_handles);
+  if (upload(ctx, a.tree_nodes, (const uint4*) v->light_tree_nodes, (size_t) v->num_light_tree_nodes * 4, &sc.light_tree_nodes)) return 1;
+  return upload(ctx, a.tri_handles, (const uint2*) v->light_tri_handles, v->num_lights, &sc.light_tri_handles);
 }
 
 static int update_textures(LumContext* ctx, const LumDeviceSceneView* v) {
   DeviceScene& sc = ctx->scene;
-  ctx->scene_allocs[LumContext::kGrpTex].clear();
-  sc.num_textures = 0; sc.texture_table = nullptr; sc.texels = nullptr;
+  SceneArrays::Textures& a = ctx->arrays.textures;
+  a = {}; point_views(sc, a);
+  sc.num_textures = 0;
   if (!v->num_textures || !v->texture_table || !v->texels) return 0;
   size_t texel_count = 0;
   for (uint32_t t = 0; t < v->num_textures; t++)
     texel_count = std::max(texel_count, (size_t) v->texture_table[4 * t] + (size_t) v->texture_table[4 * t + 1] * v->texture_table[4 * t + 2]);
-  if (upload(ctx, LumContext::kGrpTex, (const uint4*) v->texture_table, v->num_textures, &sc.texture_table)) return 1;
-  if (upload(ctx, LumContext::kGrpTex, v->texels, texel_count, &sc.texels)) return 1;
+  if (upload(ctx, a.table, (const uint4*) v->texture_table, v->num_textures, &sc.texture_table)) return 1;
+  if (upload(ctx, a.texels, v->texels, texel_count, &sc.texels)) return 1;
   sc.num_textures = v->num_textures;
   return 0;
 }
@@ -288,6 +313,7 @@ static int build_mesh_trees(LumContext* ctx, const LumDeviceSceneView* v, std::v
   ctx->bvh_meshes_by_builder[0] = ctx->bvh_meshes_by_builder[1] = 0;
   ctx->mesh_bvh.assign(v->num_meshes, nullptr);
   ctx->mesh_box.assign(v->num_meshes, Aabb{});
+  mesh_boxes_changed(ctx);
   ctx->mesh_refit.clear(); ctx->mesh_refit.resize(v->num_meshes);
   ctx->mesh_tri_offset.assign(v->mesh_tri_offset, v->mesh_tri_offset + v->num_meshes + 1);
   blas_tris.assign((size_t) total_triangles(v) + 1, BvhTri{});
@@ -309,7 +335,7 @@ static int build_mesh_trees(LumContext* ctx, const LumDeviceSceneView* v, std::v
   return 0;
 }
 
-// LUMC_DIRTY_MESH_POSITIONS: the vertex arrays of the same meshes again - the traversal triangles stay on the device (update_mesh_arrays frees its group) -, then
+// LUMC_DIRTY_MESH_POSITIONS: the vertex arrays of the same meshes again - the traversal triangles stay on the device (update_mesh_arrays) -, then
 // every mesh whose vertices differ from those its held tree was fitted to gets a tree for them: refitted on the device (bvh_refit.hip; the tree becomes
 // private to this context, the shared one it came from is not touched and the cache never sees the refitted one) or, where the mode, the cost's growth or a
 // tree that cannot be refitted says so, from the cache / the builder like an upload. *rebuilt: a mesh's traversal triangles were written anew (k_tri_opacity).
@@ -327,14 +353,9 @@ static int refit_mesh_trees(LumContext* ctx, const LumDeviceSceneView* v, bool* 
     return 1;
   }
   const auto t_all = clock::now();
-  auto& group = ctx->scene_allocs[LumContext::kGrpMesh];
-  DeviceBuffer<char> tris_buffer;
-  for (auto& b : group) if (b.get() == reinterpret_cast<const char*>(sc.blas_tris)) tris_buffer = std::move(b);
-  if (!tris_buffer) { ctx->error = "lumc_scene_update: the scene on the device has no traversal triangles"; return 1; }
-  BvhTri* d_tris = reinterpret_cast<BvhTri*>(tris_buffer.get());
-  const int failed = update_mesh_arrays(ctx, v);
-  group.push_back(std::move(tris_buffer));
-  if (failed) return 1;
+  BvhTri* d_tris = ctx->arrays.mesh.blas_tris.get();
+  if (!d_tris) { ctx->error = "lumc_scene_update: the scene on the device has no traversal triangles"; return 1; }
+  if (update_mesh_arrays(ctx, v)) return 1;
   HIP_TRY(ctx, hipDeviceSynchronize());
   st.seconds_upload = since(t_all);
   for (uint32_t m = 0; m < v->num_meshes; m++) {
@@ -368,7 +389,7 @@ static int refit_mesh_trees(LumContext* ctx, const LumDeviceSceneView* v, bool* 
         const double growth = mr.built_cost > 0.0 ? bvh4_cost(mr.own->bvh) / mr.built_cost : 1.0;
         st.max_cost_growth = std::max(st.max_cost_growth, growth);
         if (ctx->refit_max_cost_growth > 0.0f && growth > (double) ctx->refit_max_cost_growth) build = true;
-        else { ctx->mesh_bvh[m] = mr.own; ctx->mesh_box[m] = box; st.refits++; st.last_refits++; }
+        else { ctx->mesh_bvh[m] = mr.own; ctx->mesh_box[m] = box; mesh_boxes_changed(ctx); st.refits++; st.last_refits++; }
       }
       st.seconds_refit += since(t_refit);
     }
@@ -376,6 +397,7 @@ static int refit_mesh_trees(LumContext* ctx, const LumDeviceSceneView* v, bool* 
       const auto t_build = clock::now();
       std::vector<Aabb> tri_boxes(nt);
       ctx->mesh_box[m] = mesh_triangle_boxes(vertices, nt, tri_boxes.data());
+      mesh_boxes_changed(ctx);
       std::shared_ptr<const MeshTree> tree = cached_or_built_mesh_tree(ctx, key, tri_boxes.data(), nt);
       if (!tree) return 1;
       std::vector<BvhTri> tris(nt);
@@ -394,7 +416,7 @@ static int refit_mesh_trees(LumContext* ctx, const LumDeviceSceneView* v, bool* 
   return 0;
 }
 
-// Top level + every mesh's tree in ONE node array (bvh_build.cpp assemble_scene_tree), in the instances' group; the traversal triangles in the meshes'.
+// Top level + every mesh's tree in ONE node array (bvh_build.cpp assemble_scene_tree), of the instances' part; the traversal triangles are of the meshes'.
 static int update_scene_tree(LumContext* ctx, const LumDeviceSceneView* v, bool dirty_meshes, size_t* num_nodes) {
   DeviceScene& sc = ctx->scene;
   std::vector<BvhTri> blas_tris;
@@ -402,15 +424,15 @@ static int update_scene_tree(LumContext* ctx, const LumDeviceSceneView* v, bool 
   if (ctx->mesh_box.size() != v->num_meshes || ctx->mesh_bvh.size() != v->num_meshes) { ctx->error = "lumc_scene_update: the meshes changed but LUMC_DIRTY_MESHES is not set"; return 1; }
   std::vector<const Bvh4*> mesh_bvh(v->num_meshes);
   for (uint32_t m = 0; m < v->num_meshes; m++) mesh_bvh[m] = &ctx->mesh_bvh[m]->bvh;
-  ctx->instance_update.resident = false;
   const SceneTree tree = assemble_scene_tree(*v, mesh_bvh.data(), ctx->mesh_box.data());
   if (tree.nodes.empty()) { ctx->error = "top-level BVH exceeds 16 levels"; return 1; }
   if (total_triangles(v) >= (1u << 28) || tree.nodes.size() >= (1u << 25)) { ctx->error = "scene too large for 28-bit leaf ranges / 32-bit node offsets"; return 1; }
   // by instance id: the exact flavour's ambient reuse re-tests a ray against a hit's triangle (k_resolve_reuse)
-  if (upload(ctx, LumContext::kGrpInst, tree.inv_rows.data(), tree.inv_rows.size(), &sc.instance_rows)) return 1;
-  if (upload(ctx, LumContext::kGrpInst, tree.nodes.data(), tree.nodes.size(), &sc.bvh_nodes)) return 1;
-  if (dirty_meshes && upload(ctx, LumContext::kGrpMesh, blas_tris.data(), blas_tris.size(), &sc.blas_tris)) return 1;
-  if (upload(ctx, LumContext::kGrpInst, tree.tlas_leaves.data(), tree.tlas_leaves.size(), &sc.tlas_leaves)) return 1;
+  if (upload(ctx, ctx->arrays.inst.rows, tree.inv_rows.data(), tree.inv_rows.size(), &sc.instance_rows)) return 1;
+  ctx->instance_update.resident = false;  // the one place: the node array in assemble_scene_tree's order, not relayout_resident's
+  if (upload(ctx, ctx->arrays.inst.nodes, tree.nodes.data(), tree.nodes.size(), &sc.bvh_nodes)) return 1;
+  if (dirty_meshes && upload(ctx, ctx->arrays.mesh.blas_tris, blas_tris.data(), blas_tris.size(), &sc.blas_tris)) return 1;
+  if (upload(ctx, ctx->arrays.inst.tlas_leaves, tree.tlas_leaves.data(), tree.tlas_leaves.size(), &sc.tlas_leaves)) return 1;
   sc.tlas_num_nodes = tree.tlas_num_nodes;
   sc.tlas_num_leaves = (uint32_t) (tree.tlas_leaves.size() / 4);  // records that exist (one of padding included): what a workgroup may stage in LDS
   std::memcpy(ctx->sort.world_lo, tree.world.lo, sizeof(ctx->sort.world_lo)); std::memcpy(ctx->sort.world_hi, tree.world.hi, sizeof(ctx->sort.world_hi));
@@ -443,11 +465,11 @@ static int update_ray_kernel_lds(LumContext* ctx, size_t num_nodes) {
 
 // ---- LUMC_DIRTY_INSTANCE_TRANSFORMS (lum_core.h lumc_set_instance_update; instance_update.hip) ----
 // The resident layout: the node array laid out once on the host so that the top level has a range of its own, [0, C), and the mesh trees, [C, C + M), need not
-// be written again; the leaf records get room for every instance. Replaces both arrays in the instances' group; costs what an instance edit costs.
+// be written again; the leaf records get room for every instance. Replaces both arrays of the instances' part; costs what an instance edit costs.
 static int relayout_resident(LumContext* ctx, const LumDeviceSceneView* v) {
   DeviceScene& sc = ctx->scene;
   InstanceUpdate& u = ctx->instance_update;
-  u.resident = false;
+  SceneArrays::Inst& a = ctx->arrays.inst;
   const uint32_t n = v->num_instances, capacity = std::max<uint32_t>(1u, n > 0 ? n - 1u : 0u);
   std::vector<const Bvh4*> mesh_bvh(v->num_meshes);
   for (uint32_t m = 0; m < v->num_meshes; m++) mesh_bvh[m] = &ctx->mesh_bvh[m]->bvh;
@@ -455,16 +477,11 @@ static int relayout_resident(LumContext* ctx, const LumDeviceSceneView* v) {
   std::vector<uint32_t> mesh_root;
   layout_resident_nodes(*v, mesh_bvh.data(), capacity, nodes, mesh_root);
   if (total_triangles(v) >= (1u << 28) || nodes.size() >= (1u << 25)) { ctx->error = "scene too large for 28-bit leaf ranges / 32-bit node offsets"; return 1; }
-  auto& group = ctx->scene_allocs[LumContext::kGrpInst];
-  group.erase(std::remove_if(group.begin(), group.end(), [&](const DeviceBuffer<char>& b) {
-    return b.get() == reinterpret_cast<const char*>(sc.bvh_nodes) || b.get() == reinterpret_cast<const char*>(sc.tlas_leaves); }), group.end());
-  sc.bvh_nodes = nullptr; sc.tlas_leaves = nullptr;
-  if (upload(ctx, LumContext::kGrpInst, nodes.data(), nodes.size(), &sc.bvh_nodes)) return 1;
-  DeviceBuffer<char> leaves;
-  HIP_TRY(ctx, leaves.resize(sizeof(float4) * 4 * ((size_t) n + 1)));
-  HIP_TRY(ctx, hipMemset(leaves.get(), 0, sizeof(float4) * 4 * ((size_t) n + 1)));
-  sc.tlas_leaves = reinterpret_cast<const float4*>(leaves.get());
-  group.push_back(std::move(leaves));
+  a.nodes.reset(); a.tlas_leaves.reset(); point_views(sc, a);
+  if (upload(ctx, a.nodes, nodes.data(), nodes.size(), &sc.bvh_nodes)) return 1;
+  HIP_TRY(ctx, a.tlas_leaves.resize(4 * ((size_t) n + 1)));
+  sc.tlas_leaves = a.tlas_leaves.get();
+  HIP_TRY(ctx, hipMemset(a.tlas_leaves.get(), 0, sizeof(float4) * 4 * ((size_t) n + 1)));
   HIP_TRY(ctx, u.mesh_root.assign(mesh_root.data(), v->num_meshes));
   u.capacity = capacity; u.mesh_nodes = (uint32_t) (nodes.size() - capacity); u.tlas_nodes = 0;
   if (update_ray_kernel_lds(ctx, nodes.size())) return 1;
@@ -480,6 +497,7 @@ static int update_instance_transforms(LumContext* ctx, const LumDeviceSceneView*
   auto since = [](clock::time_point t) { return std::chrono::duration<double>(clock::now() - t).count(); };
   DeviceScene& sc = ctx->scene;
   InstanceUpdate& u = ctx->instance_update;
+  SceneArrays::Inst& a = ctx->arrays.inst;
   LumInstanceUpdateStats& st = ctx->instance_stats;
   st.seconds = st.seconds_relayout = st.seconds_upload = st.seconds_boxes = st.seconds_build = st.seconds_leaves = 0.0;
   *fell_back = false;
@@ -490,18 +508,18 @@ static int update_instance_transforms(LumContext* ctx, const LumDeviceSceneView*
     return 1;
   }
   const auto t_all = clock::now();
-  if (!u.prepared || u.num_instances != n || u.num_meshes != v->num_meshes) {  // (every path that changes the meshes or the instance count drops `prepared`)
+  if (!u.prepared || u.num_instances != n || u.num_meshes != v->num_meshes) {  // (whoever writes ctx->mesh_box drops `prepared`: mesh_boxes_changed)
     u.reset();
     if (instance_update_prepare(u, n, v->num_meshes, ctx->mesh_box.data()) != hipSuccess) { (void) hipGetLastError(); u.reset(); *fell_back = true; return 0; }
   }
   auto t = clock::now();
-  if (n) HIP_TRY(ctx, hipMemcpy(const_cast<float4*>(sc.instance_transforms), v->instance_transforms, sizeof(float4) * 2 * (size_t) n, hipMemcpyHostToDevice));
+  if (n) HIP_TRY(ctx, hipMemcpy(a.transforms.get(), v->instance_transforms, sizeof(float4) * 2 * (size_t) n, hipMemcpyHostToDevice));
   HIP_TRY(ctx, hipDeviceSynchronize());
   st.seconds_upload = since(t);
   t = clock::now();
   uint32_t hittable = 0;
   Aabb world;
-  HIP_TRY(ctx, instance_update_boxes(u, sc.instance_transforms, sc.instance_mesh_ids, sc.mesh_tri_offset, const_cast<float4*>(sc.instance_rows), &hittable, &world));
+  HIP_TRY(ctx, instance_update_boxes(u, sc.instance_transforms, sc.instance_mesh_ids, sc.mesh_tri_offset, a.rows.get(), &hittable, &world));
   st.seconds_boxes = since(t);
   if (hittable < 2) { *fell_back = true; return 0; }  // (before the layout: a scene of one instance never pays for one)
   if (!u.resident) {
@@ -513,7 +531,7 @@ static int update_instance_transforms(LumContext* ctx, const LumDeviceSceneView*
   }
   t = clock::now();
   uint32_t num_nodes = 0, depth = 0;
-  Bvh4Node* d_nodes = const_cast<Bvh4Node*>(sc.bvh_nodes);
+  Bvh4Node* d_nodes = a.nodes.get();  // (after the layout, which replaces the array)
   if (!build_bvh4_sah_device(u.dense_boxes.get(), hittable, 1, 16, d_nodes, u.capacity, u.prims.get(), &num_nodes, &depth)) {
     (void) hipGetLastError();
     *fell_back = true;
@@ -521,7 +539,7 @@ static int update_instance_transforms(LumContext* ctx, const LumDeviceSceneView*
   }
   st.seconds_build = since(t);
   t = clock::now();
-  HIP_TRY(ctx, instance_update_leaves(u, hittable, sc.instance_rows, sc.instance_mesh_ids, const_cast<float4*>(sc.tlas_leaves), d_nodes, num_nodes, std::max(num_nodes, u.tlas_nodes)));
+  HIP_TRY(ctx, instance_update_leaves(u, hittable, sc.instance_rows, sc.instance_mesh_ids, a.tlas_leaves.get(), d_nodes, num_nodes, std::max(num_nodes, u.tlas_nodes)));
   HIP_TRY(ctx, hipDeviceSynchronize());
   st.seconds_leaves = since(t);
   u.tlas_nodes = num_nodes;
@@ -536,7 +554,7 @@ static int update_instance_transforms(LumContext* ctx, const LumDeviceSceneView*
   return 0;
 }
 
-// Light-only BVH (world-space triangles; reference: optix_bvh.c:382-478), in the light tree's group.
+// Light-only BVH (world-space triangles; reference: optix_bvh.c:382-478), of the lights' part.
 static int update_light_bvh(LumContext* ctx, const LumDeviceSceneView* v) {
   DeviceScene& sc = ctx->scene;
   const uint32_t nl = (v->light_tree_root && v->light_bvh_tris) ? v->num_lights : 0;
@@ -546,8 +564,8 @@ static int update_light_bvh(LumContext* ctx, const LumDeviceSceneView* v) {
   if (lb.nodes.empty()) { ctx->error = "light BVH exceeds 40 levels"; return 1; }
   std::vector<BvhTri> tris(nl ? nl : 1, BvhTri{});
   for (uint32_t i = 0; i < nl; i++) tris[i] = bvh_tri(v->light_bvh_tris + (size_t) lb.prims[i] * 12, lb.prims[i], 0u, 0u);
-  if (upload(ctx, LumContext::kGrpLight, lb.nodes.data(), lb.nodes.size(), &sc.light_nodes)) return 1;
-  if (upload(ctx, LumContext::kGrpLight, tris.data(), tris.size(), &sc.light_tris)) return 1;
+  if (upload(ctx, ctx->arrays.lights.bvh_nodes, lb.nodes.data(), lb.nodes.size(), &sc.light_nodes)) return 1;
+  if (upload(ctx, ctx->arrays.lights.bvh_tris, tris.data(), tris.size(), &sc.light_tris)) return 1;
   sc.light_num_nodes = (uint32_t) lb.nodes.size();
   ctx->bvh_stats[3] = lb.nodes.size();
   return 0;
@@ -563,26 +581,21 @@ static int update_counts_and_tables(LumContext* ctx, const LumDeviceSceneView* v
   ctx->bvh_stats[1] = total_tris;
   sc.num_meshes = v->num_meshes; sc.num_instances = v->num_instances; sc.num_materials = v->num_materials; sc.num_lights = v->num_lights;  // (num_textures: update_textures)
   if (total_tris && (dirty & (LUMC_DIRTY_MESHES | LUMC_DIRTY_MATERIALS | kDirtyTrianglesRewritten))) {  // the triangles' material words: texture id, or whether they stop a visibility ray on their own
-    hipLaunchKernelGGL(k_tri_opacity, dim3((total_tris + kBlock - 1) / kBlock), dim3(kBlock), 0, 0, sc, const_cast<BvhTri*>(sc.blas_tris), total_tris);
+    hipLaunchKernelGGL(k_tri_opacity, dim3((total_tris + kBlock - 1) / kBlock), dim3(kBlock), 0, 0, sc, ctx->arrays.mesh.blas_tris.get(), total_tris);
     HIP_TRY(ctx, hipGetLastError());
   }
   if ((dirty_lights || ((dirty & (LUMC_DIRTY_MATERIALS | LUMC_DIRTY_INSTANCES | LUMC_DIRTY_INSTANCE_TRANSFORMS | LUMC_DIRTY_MESHES)) && sc.light_tri_table)) && sc.light_tree_root && sc.num_lights) {  // the emissive triangles in world space with what their material says, one record per light (load_tri_light_table)
-    float4* table = const_cast<float4*>(sc.light_tri_table);  // a material edit alone refills the table in place (same lights)
-    if (dirty_lights) {
-      DeviceBuffer<char> records;
-      HIP_TRY(ctx, records.resize(sizeof(float4) * 4 * (size_t) sc.num_lights));
-      table = (float4*) records.get();
-      ctx->scene_allocs[LumContext::kGrpLight].push_back(std::move(records));
-    }
-    hipLaunchKernelGGL(k_light_table, dim3((sc.num_lights + kBlock - 1) / kBlock), dim3(kBlock), 0, 0, sc, table);
+    DeviceBuffer<float4>& table = ctx->arrays.lights.tri_table;  // a material edit alone refills the table in place (same lights)
+    if (dirty_lights) HIP_TRY(ctx, table.resize(4 * (size_t) sc.num_lights));
+    hipLaunchKernelGGL(k_light_table, dim3((sc.num_lights + kBlock - 1) / kBlock), dim3(kBlock), 0, 0, sc, table.get());
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipDeviceSynchronize());
-    sc.light_tri_table = table;
+    sc.light_tri_table = table.get();
   }
   return 0;
 }
 
-// The scalar fields of the constants' part, with the pointers of that part reset (the functions after this one fill them in again).
+// The scalar fields of the constants' part.
 static int copy_constants(LumContext* ctx, const LumDeviceSceneView* v) {
   DeviceScene& sc = ctx->scene;
   sc.width = v->width; sc.height = v->height; sc.max_ray_depth = v->max_ray_depth; sc.shading_mode = v->shading_mode;
@@ -604,9 +617,7 @@ static int copy_constants(LumContext* ctx, const LumDeviceSceneView* v) {
   std::memcpy(sc.sky_moon_pos, v->sky_moon_pos, sizeof(sc.sky_moon_pos));
   sc.sky_moon_tex_offset = v->sky_moon_tex_offset; sc.sky_stars_intensity = v->sky_stars_intensity;
   sc.sky_moon_albedo_tex = v->sky_moon_albedo_tex; sc.sky_moon_normal_tex = v->sky_moon_normal_tex;
-  sc.sky_stars_count = 0; sc.sky_stars = nullptr; sc.sky_stars_offsets = nullptr;
-  sc.sky_lut_transmittance = nullptr; sc.sky_lut_multiscattering = nullptr;
-  sc.sky_hdri = nullptr; sc.sky_hdri_dim = 0;
+  sc.sky_stars_count = 0; sc.sky_hdri_dim = 0;
   sc.sky_aerial_perspective = v->sky_aerial_perspective;
   // ---- fog ----
   sc.fog_active = v->fog_active ? 1u : 0u;
@@ -635,7 +646,6 @@ static int copy_constants(LumContext* ctx, const LumDeviceSceneView* v) {
   sc.cloud_noise_shape_scale = v->cloud_noise_shape_scale; sc.cloud_noise_detail_scale = v->cloud_noise_detail_scale; sc.cloud_noise_weather_scale = v->cloud_noise_weather_scale;
   std::memcpy(sc.cloud_phase, v->cloud_phase, sizeof(sc.cloud_phase));
   std::memcpy(sc.cloud_layers, v->cloud_layers, sizeof(sc.cloud_layers));
-  sc.cloud_noise_shape = nullptr; sc.cloud_noise_detail = nullptr; sc.cloud_noise_weather = nullptr;
   if (sc.cloud_active && (sc.cloud_steps == 0 || sc.cloud_shadow_steps == 0)) { ctx->error = "lumc_scene_upload: clouds need positive step counts"; return 1; }
   // ---- particles ----
   sc.particles_active = (v->particles_active && v->particles_count) ? 1u : 0u;
@@ -650,8 +660,8 @@ static int copy_constants(LumContext* ctx, const LumDeviceSceneView* v) {
 static int update_stars(LumContext* ctx, const LumDeviceSceneView* v) {
   DeviceScene& sc = ctx->scene;
   if (!v->sky_stars || !v->sky_stars_offsets || !v->sky_stars_count) return 0;
-  if (upload(ctx, LumContext::kGrpConst, (const float4*) v->sky_stars, (size_t) v->sky_stars_count, &sc.sky_stars)) return 1;
-  if (upload(ctx, LumContext::kGrpConst, v->sky_stars_offsets, (size_t) 64 * 32 + 1, &sc.sky_stars_offsets)) return 1;
+  if (upload(ctx, ctx->arrays.constants.stars, (const float4*) v->sky_stars, (size_t) v->sky_stars_count, &sc.sky_stars)) return 1;
+  if (upload(ctx, ctx->arrays.constants.stars_offsets, v->sky_stars_offsets, (size_t) 64 * 32 + 1, &sc.sky_stars_offsets)) return 1;
   sc.sky_stars_count = v->sky_stars_count;
   return 0;
 }
@@ -661,18 +671,14 @@ static int update_cloud_noise(LumContext* ctx, const LumDeviceSceneView* v) {
   DeviceScene& sc = ctx->scene;
   if (!sc.cloud_active) return 0;
   if (v->cloud_noise_shape && v->cloud_noise_detail && v->cloud_noise_weather) {
-    if (upload(ctx, LumContext::kGrpConst, (const uint32_t*) v->cloud_noise_shape, kCloudNoiseTexels[0], &sc.cloud_noise_shape)) return 1;
-    if (upload(ctx, LumContext::kGrpConst, (const uint32_t*) v->cloud_noise_detail, kCloudNoiseTexels[1], &sc.cloud_noise_detail)) return 1;
-    return upload(ctx, LumContext::kGrpConst, (const uint32_t*) v->cloud_noise_weather, kCloudNoiseTexels[2], &sc.cloud_noise_weather);
+    DeviceBuffer<uint32_t>* a = ctx->arrays.constants.cloud_noise;
+    if (upload(ctx, a[0], (const uint32_t*) v->cloud_noise_shape, kCloudNoiseTexels[0], &sc.cloud_noise_shape)) return 1;
+    if (upload(ctx, a[1], (const uint32_t*) v->cloud_noise_detail, kCloudNoiseTexels[1], &sc.cloud_noise_detail)) return 1;
+    return upload(ctx, a[2], (const uint32_t*) v->cloud_noise_weather, kCloudNoiseTexels[2], &sc.cloud_noise_weather);
   }
   if (ensure_cloud_noise(ctx, v->cloud_seed)) return 1;
   sc.cloud_noise_shape = ctx->d_cloud_noise[0].get(); sc.cloud_noise_detail = ctx->d_cloud_noise[1].get(); sc.cloud_noise_weather = ctx->d_cloud_noise[2].get();
   return 0;
-}
-
-static int update_particles(LumContext* ctx, const LumDeviceSceneView* v) {
-  ctx->scene_allocs[LumContext::kGrpPart].clear();
-  return build_particle_tree(ctx, LumContext::kGrpPart, v, ctx->scene);
 }
 
 // Sky look-up tables: the caller's or generated here (device/device_sky.c:64-200); not for a constant sky (HDRI mode bakes from them and samples the sun through them).
@@ -681,8 +687,8 @@ static int update_sky_tables(LumContext* ctx, const LumDeviceSceneView* v) {
   if (sc.sky_mode == kSkyConstantColor) return 0;
   const size_t tm_texels = 2 * (size_t) kSkyTmWidth * kSkyTmHeight, ms_texels = 2 * (size_t) kSkyMsSize * kSkyMsSize;
   if (v->sky_lut_transmittance && v->sky_lut_multiscattering) {
-    if (upload(ctx, LumContext::kGrpConst, (const float4*) v->sky_lut_transmittance, tm_texels, &sc.sky_lut_transmittance)) return 1;
-    if (upload(ctx, LumContext::kGrpConst, (const float4*) v->sky_lut_multiscattering, ms_texels, &sc.sky_lut_multiscattering)) return 1;
+    if (upload(ctx, ctx->arrays.constants.sky_lut[0], (const float4*) v->sky_lut_transmittance, tm_texels, &sc.sky_lut_transmittance)) return 1;
+    if (upload(ctx, ctx->arrays.constants.sky_lut[1], (const float4*) v->sky_lut_multiscattering, ms_texels, &sc.sky_lut_multiscattering)) return 1;
     ctx->sky_lut_key.clear();
     return 0;
   }
@@ -761,7 +767,7 @@ static int update_sky_panorama(LumContext* ctx, const LumDeviceSceneView* v) {
   DeviceScene& sc = ctx->scene;
   if (sc.sky_mode != kSkyHdri) return 0;
   if (v->sky_hdri && v->sky_hdri_dim) {
-    if (upload(ctx, LumContext::kGrpConst, (const float4*) v->sky_hdri, (size_t) v->sky_hdri_dim * v->sky_hdri_dim, &sc.sky_hdri)) return 1;
+    if (upload(ctx, ctx->arrays.constants.sky_hdri, (const float4*) v->sky_hdri, (size_t) v->sky_hdri_dim * v->sky_hdri_dim, &sc.sky_hdri)) return 1;
     sc.sky_hdri_dim = v->sky_hdri_dim;
     return 0;
   }
@@ -772,11 +778,11 @@ static int update_sky_panorama(LumContext* ctx, const LumDeviceSceneView* v) {
 
 // Camera, settings, sky, fog, ocean, clouds, particles: the kernels' scalar arguments and the tables derived from them.
 static int update_constants(LumContext* ctx, const LumDeviceSceneView* v, unsigned dirty) {
-  ctx->scene_allocs[LumContext::kGrpConst].clear();
+  ctx->arrays.constants = {}; point_views(ctx->scene, ctx->arrays.constants);
   if (copy_constants(ctx, v)) return 1;
   if (update_stars(ctx, v)) return 1;
   if (update_cloud_noise(ctx, v)) return 1;
-  if ((dirty & LUMC_DIRTY_PARTICLES) && update_particles(ctx, v)) return 1;
+  if ((dirty & LUMC_DIRTY_PARTICLES) && build_particle_tree(ctx, v, ctx->scene)) return 1;
   if (update_sky_tables(ctx, v)) return 1;
   if (update_bsdf_tables(ctx, v, dirty == LUMC_DIRTY_ALL)) return 1;
   return update_sky_panorama(ctx, v);
@@ -816,6 +822,7 @@ static int scene_update(LumContext* ctx, const LumDeviceSceneView* v, unsigned d
   auto host_path_since = [&](std::chrono::steady_clock::time_point t) { if (moved_by_host) ctx->instance_stats.seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count(); };
   const bool meshes = (dirty & LUMC_DIRTY_MESHES) != 0, instances = (dirty & LUMC_DIRTY_INSTANCES) != 0, lights = (dirty & LUMC_DIRTY_LIGHTS) != 0;
   ctx->has_scene = false;
+  if (meshes) ctx->arrays.mesh = {};  // the traversal triangles too
   if (meshes && update_mesh_arrays(ctx, v)) return 1;
   if (dirty & LUMC_DIRTY_MESH_POSITIONS) {
     bool rebuilt = false;
@@ -831,7 +838,7 @@ static int scene_update(LumContext* ctx, const LumDeviceSceneView* v, unsigned d
   auto t_lights = std::chrono::steady_clock::now();
   if (lights && update_light_tree(ctx, v)) return 1;
   lights_since(t_lights);
-  if (!sc.bluenoise_2d && upload(ctx, LumContext::kGrpOnce, v->bluenoise_2d, 65536, &sc.bluenoise_2d)) return 1;
+  if (!sc.bluenoise_2d && upload(ctx, ctx->arrays.bluenoise_2d, v->bluenoise_2d, 65536, &sc.bluenoise_2d)) return 1;
   if ((dirty & LUMC_DIRTY_TEXTURES) && update_textures(ctx, v)) return 1;
   size_t num_nodes = 0;
   const auto t_assemble = std::chrono::steady_clock::now();
@@ -841,9 +848,7 @@ static int scene_update(LumContext* ctx, const LumDeviceSceneView* v, unsigned d
     bool fell_back = false;
     if (update_instance_transforms(ctx, v, &fell_back)) return 1;
     if (fell_back) {  // this one update by the host's path, as LUMC_DIRTY_INSTANCES
-      const bool prepared = ctx->instance_update.prepared;  // (the meshes did not change: the scratch and their boxes serve the next update)
       if (update_instance_arrays(ctx, v) || update_scene_tree(ctx, v, false, &num_nodes) || update_ray_kernel_lds(ctx, num_nodes)) return 1;
-      ctx->instance_update.prepared = prepared;
       ctx->instance_stats.fallbacks++;
       ctx->instance_stats.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_assemble).count();
     }

@@ -380,7 +380,8 @@ LUMINARY_API LuminaryResult luminary_ext_get_mesh(LuminaryHost* host, uint32_t m
 /* Deformable meshes. New positions (9 floats per triangle) and normals (9 per triangle, or NULL = face normals by the loader's rule for a file without normals)
  * for a mesh the host already holds. triangle_count must equal the mesh's; order, uvs and material ids stay. The host mesh is overwritten in place (the
  * luminary_ext_get_mesh pointers stay valid). Restarts the integration. LUMINARY_ERROR_INVALID_API_ARGUMENT, and nothing changes: a mesh id the host does not have,
- * another triangle count, NULL positions, a position that is not finite. On the devices only the vertices are uploaded and the mesh's tree is refitted there. */
+ * another triangle count, NULL positions, a position that is not finite. On the devices only the vertices are uploaded and the mesh's tree is refitted there
+ * (luminary_ext_set_mesh_refit_in_place: in the scene's node array itself, which then keeps its layout). */
 LUMINARY_API LuminaryResult luminary_ext_set_mesh_positions(LuminaryHost* host, uint32_t mesh_id, const float* positions, const float* normals, uint32_t triangle_count);
 /* mode 0 (default): refit the mesh's tree; 1: build it again. max_cost_growth > 0: in mode 0, build again when the tree's cost (the sum over all nodes and occupied
  * child slots of the child box's half surface area) has grown beyond this factor of its cost when it was last BUILT; 0 = never. No default threshold is built in:
@@ -412,6 +413,21 @@ typedef struct LuminaryInstanceUpdateStats {
   double seconds_relayout, seconds_upload, seconds_boxes, seconds_build, seconds_leaves; /* as LumInstanceUpdateStats (include/lum_core.h) */
 } LuminaryInstanceUpdateStats;
 LUMINARY_API LuminaryResult luminary_ext_get_instance_update_stats(LuminaryHost* host, LuminaryInstanceUpdateStats* out);
+/* Deformable meshes under moving instances. on = 0 (default): moved vertices are refitted in a copy of the mesh's tree and the host assembles and uploads the scene's
+ * node array again. on = 1: with luminary_ext_set_mesh_refit in mode 0 and luminary_ext_set_instance_update in mode 0, moved vertices - alone or in the same frame as
+ * moved instances - are refitted where the nodes live on the device: only the vertices (and the 32-byte transforms) go up, a few dozen bytes come back, the node
+ * array keeps its layout and only the top level is rebuilt. An update the device path cannot take (a mesh built with spatial splits, fewer than two instances that
+ * can be hit, a failed allocation, a cost growth beyond max_cost_growth) takes the other path, counted as a fallback. LUMINARY_ERROR_INVALID_API_ARGUMENT for another
+ * value. Images do not depend on it. */
+LUMINARY_API LuminaryResult luminary_ext_set_mesh_refit_in_place(LuminaryHost* host, uint32_t on);
+typedef struct LuminaryResidentRefitStats {
+  uint64_t updates, fallbacks;          /* moved-vertices updates of the main device's context that ran in place / fell back, since it was created */
+  uint32_t last_meshes, last_launches;  /* the last in-place update: meshes refitted, kernels launched for them */
+  uint64_t last_bytes_downloaded;       /* ... bytes that came back for the meshes and the instances' bounds */
+  double seconds;                       /* ... from the vertex upload to the finished top level on the main device */
+  double seconds_upload, seconds_hash, seconds_refit, seconds_cost, seconds_top_level; /* as LumResidentRefitStats (include/lum_core.h) */
+} LuminaryResidentRefitStats;
+LUMINARY_API LuminaryResult luminary_ext_get_resident_refit_stats(LuminaryHost* host, LuminaryResidentRefitStats* out);
 /* Converts the current scene to the device format (device_structs.c conversions + light tree build). The view and everything it points
  * to stay valid until the next call or host destruction. Needs no GPU. */
 /* Whether replacing `old` by `input` restarts the integration (camera.c:80-147, settings.c:45-72) or only changes the outputs.

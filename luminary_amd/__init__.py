@@ -176,6 +176,13 @@ class InstanceUpdateStats(C.Structure):
                 ("seconds_boxes", C.c_double), ("seconds_build", C.c_double), ("seconds_leaves", C.c_double)]
 
 
+class ResidentRefitStats(C.Structure):
+    """LuminaryResidentRefitStats"""
+    _fields_ = [("updates", C.c_uint64), ("fallbacks", C.c_uint64), ("last_meshes", C.c_uint32), ("last_launches", C.c_uint32), ("last_bytes_downloaded", C.c_uint64),
+                ("seconds", C.c_double), ("seconds_upload", C.c_double), ("seconds_hash", C.c_double), ("seconds_refit", C.c_double), ("seconds_cost", C.c_double),
+                ("seconds_top_level", C.c_double)]
+
+
 class Instance(C.Structure):
     _fields_ = [("id", C.c_uint32), ("mesh_id", C.c_uint32), ("position", Vec3), ("rotation", Vec3), ("scale", Vec3)]
 
@@ -538,6 +545,17 @@ class Host:
         """luminary_ext_get_instance_update_stats of the main device: a dict of device_updates, fallbacks, relayouts, the last top level's sizes and the seconds."""
         s = InstanceUpdateStats()
         _call("luminary_ext_get_instance_update_stats", self._h, C.byref(s))
+        return {name: getattr(s, name) for name, _ in s._fields_}
+
+    def set_mesh_refit_in_place(self, on=1):
+        """luminary_ext_set_mesh_refit_in_place: 1 = moved vertices, alone or in one frame with moved instances, are refitted in the devices' node arrays, which keep
+        their layout; 0 (default) = in a copy of the mesh's tree, and the host assembles and uploads the node array again."""
+        _call("luminary_ext_set_mesh_refit_in_place", self._h, C.c_uint32(on))
+
+    def resident_refit_stats(self):
+        """luminary_ext_get_resident_refit_stats of the main device: a dict of updates, fallbacks, the last update's meshes, launches, bytes downloaded and seconds."""
+        s = ResidentRefitStats()
+        _call("luminary_ext_get_resident_refit_stats", self._h, C.byref(s))
         return {name: getattr(s, name) for name, _ in s._fields_}
 
     def get_mesh(self, mesh_id):

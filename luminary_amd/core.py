@@ -107,6 +107,13 @@ class InstanceUpdateStats(C.Structure):
                 ("seconds_boxes", C.c_double), ("seconds_build", C.c_double), ("seconds_leaves", C.c_double)]
 
 
+class ResidentRefitStats(C.Structure):
+    """LumResidentRefitStats"""
+    _fields_ = [("updates", C.c_uint64), ("fallbacks", C.c_uint64), ("last_meshes", C.c_uint32), ("last_launches", C.c_uint32), ("last_bytes_downloaded", C.c_uint64),
+                ("seconds", C.c_double), ("seconds_upload", C.c_double), ("seconds_hash", C.c_double), ("seconds_refit", C.c_double), ("seconds_cost", C.c_double),
+                ("seconds_top_level", C.c_double)]
+
+
 def instance_boxes_probe(view, mesh_boxes, on_gpu=False):
     """lumc_instance_boxes_probe: (rows [n, 3, 4] float32, boxes [n, 6] float32, hittable [n] uint32) of the instances of `view` over the meshes' object-space
     boxes mesh_boxes [num_meshes, 6], by the host's functions or by the device's kernel."""
@@ -549,6 +556,23 @@ class Core:
         out = InstanceUpdateStats()
         self._call("lumc_instance_update_stats", C.byref(out))
         return out
+
+    def set_mesh_refit_in_place(self, on=1):
+        """lumc_set_mesh_refit_in_place: 1 = DIRTY_MESH_POSITIONS updates (alone or with DIRTY_INSTANCE_TRANSFORMS) refit in the resident node array and keep its layout."""
+        self._call("lumc_set_mesh_refit_in_place", C.c_uint32(on))
+
+    def resident_refit_stats(self):
+        out = ResidentRefitStats()
+        self._call("lumc_resident_refit_stats", C.byref(out))
+        return out
+
+    def resident_mesh_nodes_probe(self):
+        """lumc_resident_mesh_nodes_probe: the nodes of [C, C + M) of the resident layout as [M, 32] uint32 words (24 box floats, 4 child words, 4 of padding)."""
+        sizes = (C.c_uint64 * 5)()
+        self._call("lumc_resident_tree_probe", sizes, C.c_void_p(0), C.c_void_p(0), C.c_void_p(0), C.c_void_p(0))
+        nodes = np.zeros((int(sizes[1]), 32), np.uint32)
+        self._call("lumc_resident_mesh_nodes_probe", nodes.ctypes.data_as(C.c_void_p))
+        return nodes
 
     def resident_tree_probe(self, num_instances, num_meshes):
         """lumc_resident_tree_probe: a dict of the resident layout after a device update: C, M, T, depth, top [C, 32] uint32 words (24 box floats, 4 child words, 4 of

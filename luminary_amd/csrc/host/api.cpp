@@ -45,6 +45,7 @@ struct LuminaryHost {
   uint32_t refit_mode = 0;                // luminary_ext_set_mesh_refit: handed to every context before it takes a scene
   float refit_max_cost_growth = 0.0f;
   uint32_t instance_update_mode = 0;      // luminary_ext_set_instance_update: likewise
+  uint32_t refit_in_place = 0;            // luminary_ext_set_mesh_refit_in_place: likewise
   bool device_scene_valid = false;
   bool core_scene_valid = false;
   uint32_t core_width = 0, core_height = 0;  // frame size the main context's pixel set was made for
@@ -209,6 +210,7 @@ LuminaryResult ensure_core(LuminaryHost* h) {
   if (!h->core_scene_valid) {
     lumc_set_mesh_refit(h->core, h->refit_mode, h->refit_max_cost_growth);
     lumc_set_instance_update(h->core, h->instance_update_mode);
+    lumc_set_mesh_refit_in_place(h->core, h->refit_in_place);
     if (lumc_scene_update(h->core, &h->device_scene.view, h->core_dirty)) { std::fprintf(stderr, "[luminary_amd] %s\n", lumc_last_error(h->core)); h->core_dirty = LUMC_DIRTY_ALL; return LUMINARY_ERROR_CUDA; }
     h->core_dirty = 0;
     h->core_scene_valid = true;
@@ -252,6 +254,7 @@ LuminaryResult ensure_partition_cores(LuminaryHost* h, std::vector<LumContext*>*
     if (!slot->scene_valid) {
       lumc_set_mesh_refit(slot->core, h->refit_mode, h->refit_max_cost_growth);
       lumc_set_instance_update(slot->core, h->instance_update_mode);
+      lumc_set_mesh_refit_in_place(slot->core, h->refit_in_place);
       if (lumc_scene_update(slot->core, &h->device_scene.view, slot->dirty)) { std::fprintf(stderr, "[luminary_amd] device %d: %s\n", slot->ordinal, lumc_last_error(slot->core)); slot->dirty = LUMC_DIRTY_ALL; return LUMINARY_ERROR_CUDA; }
       slot->dirty = 0;
       slot->scene_valid = true;
@@ -854,6 +857,24 @@ LuminaryResult luminary_ext_get_instance_update_stats(LuminaryHost* host, Lumina
   LumInstanceUpdateStats s;
   if (lumc_instance_update_stats(host->core, &s)) return LUMINARY_ERROR_API_EXCEPTION;
   static_assert(sizeof(LuminaryInstanceUpdateStats) == sizeof(LumInstanceUpdateStats), "the public struct mirrors the core's");
+  std::memcpy(out, &s, sizeof(s));
+  return LUMINARY_SUCCESS;
+}
+LuminaryResult luminary_ext_set_mesh_refit_in_place(LuminaryHost* host, uint32_t on) {
+  CHECK_NULL(host);
+  ApiLock lock(host);
+  if (on > 1) return LUMINARY_ERROR_INVALID_API_ARGUMENT;
+  host->refit_in_place = on;  // (decides how the next moved vertices are taken over: no restart)
+  return LUMINARY_SUCCESS;
+}
+LuminaryResult luminary_ext_get_resident_refit_stats(LuminaryHost* host, LuminaryResidentRefitStats* out) {
+  CHECK_NULL(host); CHECK_NULL(out);
+  ApiLock lock(host);
+  std::memset(out, 0, sizeof(*out));
+  if (!host->core) return LUMINARY_SUCCESS;
+  LumResidentRefitStats s;
+  if (lumc_resident_refit_stats(host->core, &s)) return LUMINARY_ERROR_API_EXCEPTION;
+  static_assert(sizeof(LuminaryResidentRefitStats) == sizeof(LumResidentRefitStats), "the public struct mirrors the core's");
   std::memcpy(out, &s, sizeof(s));
   return LUMINARY_SUCCESS;
 }

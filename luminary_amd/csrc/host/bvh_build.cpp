@@ -1030,7 +1030,8 @@ SceneTree assemble_scene_tree(const LumDeviceSceneView& v, const Bvh4* const* me
   return out;
 }
 
-void layout_resident_nodes(const LumDeviceSceneView& v, const Bvh4* const* mesh_bvh, uint32_t capacity, std::vector<Bvh4Node>& out, std::vector<uint32_t>& mesh_root) {
+void layout_resident_nodes(const LumDeviceSceneView& v, const Bvh4* const* mesh_bvh, uint32_t capacity, std::vector<Bvh4Node>& out, std::vector<uint32_t>& mesh_root,
+                           std::vector<std::vector<uint32_t>>* mesh_slots) {
   // ---- every mesh's tree behind one another, indices relative to the first of them ----
   std::vector<Bvh4Node> nodes;
   std::vector<uint32_t> base((size_t) v.num_meshes + 1, 0);
@@ -1079,6 +1080,21 @@ void layout_resident_nodes(const LumDeviceSceneView& v, const Bvh4* const* mesh_
   }
   mesh_root.assign((size_t) v.num_meshes + 1, capacity);
   for (uint32_t m = 0; m < v.num_meshes; m++) if (base[m + 1] > base[m]) mesh_root[m] = capacity + new_index[base[m]];
+  if (mesh_slots) {
+    mesh_slots->assign(v.num_meshes, std::vector<uint32_t>());
+    for (uint32_t m = 0; m < v.num_meshes; m++) {
+      std::vector<uint32_t>& slots = (*mesh_slots)[m];
+      slots.resize(base[m + 1] - base[m]);
+      for (uint32_t i = 0; i < slots.size(); i++) slots[i] = capacity + new_index[base[m] + i];
+    }
+  }
+}
+
+bool resident_depth_slots(const Bvh4& tree, uint32_t count, const std::vector<uint32_t>& slots, std::vector<uint32_t>& depth_slots, std::vector<uint32_t>& depth_first) {
+  depth_slots.clear();
+  if (slots.size() != tree.nodes.size() || !bvh4_levels(tree, count, depth_slots, depth_first)) { depth_slots.clear(); depth_first.clear(); return false; }
+  for (uint32_t& id : depth_slots) id = slots[id];
+  return true;
 }
 
 }  // namespace lum

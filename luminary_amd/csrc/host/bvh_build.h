@@ -116,7 +116,13 @@ SceneTree assemble_scene_tree(const LumDeviceSceneView& v, const Bvh4* const* me
 // The resident layout of the scene's node array (LUMC_DIRTY_INSTANCE_TRANSFORMS, instance_update.hip): slots [0, capacity) are the top level's - empty nodes here -,
 // [capacity, capacity + M) hold every mesh's tree with absolute child indices and leaf ranges rebased by mesh_tri_offset, ordered so that the tops of the meshes
 // come first (one breadth-first walk from the mesh roots while capacity + nodes stays within the 4096 of assemble_scene_tree, the rest in mesh order).
-// mesh_root: num_meshes + 1 absolute indices.
-void layout_resident_nodes(const LumDeviceSceneView& v, const Bvh4* const* mesh_bvh, uint32_t capacity, std::vector<Bvh4Node>& nodes, std::vector<uint32_t>& mesh_root);
+// mesh_root: num_meshes + 1 absolute indices. mesh_slots (optional): per mesh, the absolute slot of every mesh-relative node id - a mesh's nodes are NOT a range of
+// the array: the tops of all meshes come first.
+void layout_resident_nodes(const LumDeviceSceneView& v, const Bvh4* const* mesh_bvh, uint32_t capacity, std::vector<Bvh4Node>& nodes, std::vector<uint32_t>& mesh_root,
+                           std::vector<std::vector<uint32_t>>* mesh_slots = nullptr);
+// A mesh's slots in the resident array by depth below the mesh's root, root first (bvh4_levels through the slot map of layout_resident_nodes): depth d =
+// depth_slots[depth_first[d], depth_first[d + 1]). What the refit in the resident array walks, deepest first (bvh_refit.hip k_refit_level_resident). False for a
+// tree that cannot be refitted (bvh4_levels) or a slot map of another size.
+bool resident_depth_slots(const Bvh4& tree, uint32_t count, const std::vector<uint32_t>& slots, std::vector<uint32_t>& depth_slots, std::vector<uint32_t>& depth_first);
 
 }  // namespace lum

@@ -7,6 +7,15 @@
 //   k_refit_level       one thread per node of ONE level, deepest level first, one launch per level: the kernel boundary is what makes a level's exact
 //                       boxes (a per-node scratch array) visible to the level above - no in-launch hand-off, no counters. At most 26 launches.
 // The per-level node lists come from one breadth-first walk on the host (bvh4_levels): the GPU builders number nodes through atomics, levels are no ranges.
+//
+// The same refit where the nodes live (resident_refit_run): the scene's node array in the resident layout of instance_update.h holds every
+// mesh's nodes with absolute child words at slots that are no range, so no node is copied, downloaded or uploaded.
+//   k_refit_level_resident  one thread per node slot of ONE depth below the mesh roots, over ALL moved meshes of the update (grid y = the mesh's row in a job
+//                           table): one launch per depth, deepest first, at most 27 however many meshes moved. Writes the padded child boxes into the resident
+//                           node, its own exact box into a per-slot scratch; child words, pad and empty slots are not touched
+//   k_resident_mesh_boxes   one thread per moved mesh: its root's exact box into the moved instances' mesh boxes (instance_update.h) and the results
+//   k_bvh4_cost             bvh4_cost of every moved mesh's nodes as they stand in the array: per node the occupied slots' half areas in double, in slot order,
+//                           summed per workgroup in a fixed tree; k_bvh4_cost_sum adds a mesh's workgroup sums. No atomics: the same sum every time
 // The reference has nothing like it: optixAccelBuild with OPTIX_BUILD_OPERATION_UPDATE would be its counterpart, and it does not use it (optix_bvh.c:150-684).
 #include <hip/hip_runtime.h>
 
@@ -81,6 +90,105 @@ __global__ __launch_bounds__(kRefitBlock) void k_refit_level(Bvh4Node* __restric
   node_box[id] = all;
 }
 
+// ---- in the resident node array ----
+// nodes: the scene's node array; a job's slots, the inner child words and (through first_tri) the leaf ranges are absolute. slot_box: by slot - capacity.
+__global__ __launch_bounds__(kRefitBlock) void k_refit_level_resident(Bvh4Node* __restrict__ nodes, uint32_t capacity, uint32_t mesh_nodes, const ResidentJob* __restrict__ jobs,
+                                                                      uint32_t num_jobs, uint32_t depth, Aabb* slot_box) {
+  if (blockIdx.y >= num_jobs) return;
+  const ResidentJob& job = jobs[blockIdx.y];
+  if (depth >= job.depths || depth >= kResidentMaxDepths) return;
+  const uint32_t first = job.depth_first[depth], end = job.depth_first[depth + 1];
+  const uint32_t i = blockIdx.x * kRefitBlock + threadIdx.x;
+  if (end > job.num_nodes || first > end || i >= end - first) return;
+  const uint32_t slot = job.slots[first + i];
+  if (slot < capacity || slot - capacity >= mesh_nodes) return;
+  Bvh4Node& node = nodes[slot];
+  Aabb all = empty_box();
+  for (int k = 0; k < 4; k++) {
+    const uint32_t c = node.child[k];
+    if (c == kBvhEmpty) continue;
+    Aabb box;
+    if (c & kBvhLeafBit) {
+      box = empty_box();
+      const uint32_t tri = c & 0x0FFFFFFFu, cnt = ((c >> 28) & 7u) + 1u;
+      if (tri < job.first_tri) continue;
+      const uint32_t rel = tri - job.first_tri;  // (the range was rebased by the mesh's first triangle)
+      for (uint32_t j = 0; j < cnt && rel + j < job.count; j++) grow(box, job.prim_box[rel + j]);
+    }
+    else {
+      if (c < capacity || c - capacity >= mesh_nodes) continue;
+      box = slot_box[c - capacity];
+    }
+    float lo[3], hi[3];
+    for (int a = 0; a < 3; a++) {  // bvh_build.cpp set_child_box
+      const float pad = 1e-5f * fmaxf(fmaxf(fabsf(box.lo[a]), fabsf(box.hi[a])), 1e-20f) + 1e-30f;
+      lo[a] = box.lo[a] - pad; hi[a] = box.hi[a] + pad;
+    }
+    node.lo_x[k] = lo[0]; node.lo_y[k] = lo[1]; node.lo_z[k] = lo[2];
+    node.hi_x[k] = hi[0]; node.hi_y[k] = hi[1]; node.hi_z[k] = hi[2];
+    grow(all, box);
+  }
+  slot_box[slot - capacity] = all;
+}
+
+__global__ __launch_bounds__(kRefitBlock) void k_resident_mesh_boxes(const ResidentJob* __restrict__ jobs, uint32_t num_jobs, uint32_t capacity, uint32_t mesh_nodes,
+                                                                     const Aabb* __restrict__ slot_box, Aabb* __restrict__ mesh_box, uint32_t num_meshes,
+                                                                     ResidentResult* __restrict__ results) {
+  const uint32_t j = blockIdx.x * kRefitBlock + threadIdx.x;
+  if (j >= num_jobs) return;
+  const uint32_t root = jobs[j].root_slot, m = jobs[j].mesh;
+  if (root < capacity || root - capacity >= mesh_nodes || m >= num_meshes) return;
+  const Aabb box = slot_box[root - capacity];
+  mesh_box[m] = box;
+  results[j].box = box;
+}
+
+// The sum of a workgroup's values in a fixed order (a tree over the thread index): thread 0 returns it.
+__device__ __forceinline__ double block_sum(double v, double* shared) {
+  shared[threadIdx.x] = v;
+  __syncthreads();
+  for (uint32_t w = kRefitBlock / 2; w > 0; w >>= 1) {
+    if (threadIdx.x < w) shared[threadIdx.x] += shared[threadIdx.x + w];
+    __syncthreads();
+  }
+  return shared[0];
+}
+
+// bvh_build.cpp bvh4_cost, a node per thread: every workgroup of a job's row writes its sum (0 behind the job's last node), stride per job.
+__global__ __launch_bounds__(kRefitBlock) void k_bvh4_cost(const Bvh4Node* __restrict__ nodes, uint32_t capacity, uint32_t mesh_nodes, const ResidentJob* __restrict__ jobs,
+                                                           uint32_t num_jobs, double* __restrict__ partials, uint32_t stride) {
+  __shared__ double shared[kRefitBlock];
+  if (blockIdx.y >= num_jobs || blockIdx.x >= stride) return;  // (uniform per workgroup)
+  const ResidentJob& job = jobs[blockIdx.y];
+  const uint32_t i = blockIdx.x * kRefitBlock + threadIdx.x;
+  double term = 0.0;
+  if (i < job.num_nodes) {
+    const uint32_t slot = job.slots[i];
+    if (slot >= capacity && slot - capacity < mesh_nodes) {
+      const Bvh4Node& n = nodes[slot];
+      for (int k = 0; k < 4; k++) {
+        if (n.child[k] == kBvhEmpty) continue;
+        const double dx = (double) n.hi_x[k] - (double) n.lo_x[k], dy = (double) n.hi_y[k] - (double) n.lo_y[k], dz = (double) n.hi_z[k] - (double) n.lo_z[k];
+        term += dx * dy + dy * dz + dz * dx;
+      }
+    }
+  }
+  const double sum = block_sum(term, shared);
+  if (threadIdx.x == 0) partials[(size_t) blockIdx.y * stride + blockIdx.x] = sum;
+}
+
+// One workgroup per job: the job's workgroup sums, thread t those of t, t + 256, ... in that order, then the tree.
+__global__ __launch_bounds__(kRefitBlock) void k_bvh4_cost_sum(const double* __restrict__ partials, uint32_t stride, const ResidentJob* __restrict__ jobs, uint32_t num_jobs,
+                                                               ResidentResult* __restrict__ results) {
+  __shared__ double shared[kRefitBlock];
+  if (blockIdx.x >= num_jobs) return;
+  const uint32_t blocks = (jobs[blockIdx.x].num_nodes + kRefitBlock - 1) / kRefitBlock;
+  double v = 0.0;
+  for (uint32_t b = threadIdx.x; b < blocks && b < stride; b += kRefitBlock) v += partials[(size_t) blockIdx.x * stride + b];
+  const double sum = block_sum(v, shared);
+  if (threadIdx.x == 0) results[blockIdx.x].cost = sum;
+}
+
 }  // namespace
 
 hipError_t refit_plan_create(RefitPlan& plan, const Bvh4& tree, uint32_t count) {
@@ -124,6 +232,94 @@ hipError_t refit_run(RefitPlan& plan, const float4* d_vertices, BvhTri* d_tris, 
   if ((e = hipMemcpy(out_nodes, plan.nodes.get(), sizeof(Bvh4Node) * plan.num_nodes, hipMemcpyDeviceToHost)) != hipSuccess) return e;  // (waits for the launches)
   e = hipMemcpy(root_box, plan.node_box.get(), sizeof(Aabb), hipMemcpyDeviceToHost);
   if (download_seconds) *download_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_download).count();
+  return e;
+}
+
+hipError_t resident_mesh_create(ResidentMesh& rm, const Bvh4& tree, uint32_t count, const std::vector<uint32_t>& slots) {
+  rm.reset();
+  std::vector<uint32_t> depth_slots;
+  if (count == 0 || !resident_depth_slots(tree, count, slots, depth_slots, rm.depth_first) || rm.depth_first.size() < 2 || rm.depth_first.size() > kResidentMaxDepths + 1) {
+    rm.reset();
+    return hipErrorInvalidValue;
+  }
+  for (uint32_t p : tree.prims) if (p >= count) { rm.reset(); return hipErrorInvalidValue; }
+  hipError_t e;
+  if ((e = rm.slots.assign(depth_slots.data(), depth_slots.size())) != hipSuccess || (e = rm.prims.assign(tree.prims.data(), tree.prims.size())) != hipSuccess ||
+      (e = rm.prim_box.resize(count)) != hipSuccess) {
+    rm.reset();
+    return e;
+  }
+  rm.num_nodes = (uint32_t) tree.nodes.size(); rm.count = count;
+  return hipSuccess;
+}
+
+hipError_t resident_refit_prepare(ResidentRefit& r, const std::vector<uint32_t>& moved, const uint32_t* mesh_tri_offset, uint32_t mesh_nodes) {
+  if (moved.empty() || moved.size() > 65535u || !mesh_nodes) return hipErrorInvalidValue;  // (the job table is the grid's y)
+  hipError_t e;
+  if (r.slot_box.count() != mesh_nodes && (e = r.slot_box.resize(mesh_nodes)) != hipSuccess) return e;
+  if (moved == r.batch && r.jobs && r.results && r.partials) return hipSuccess;
+  r.batch.clear(); r.batch_first_tri.clear();
+  std::vector<ResidentJob> jobs(moved.size());
+  uint32_t stride = 1, widest = 1, depths = 0;
+  for (size_t j = 0; j < moved.size(); j++) {
+    const uint32_t m = moved[j];
+    if (m >= r.mesh.size() || m >= r.mesh_slots.size() || !r.mesh[m].slots || r.mesh_slots[m].empty()) return hipErrorInvalidValue;
+    const ResidentMesh& rm = r.mesh[m];
+    ResidentJob& job = jobs[j];
+    std::memset(&job, 0, sizeof(job));
+    job.slots = rm.slots.get(); job.prim_box = rm.prim_box.get();
+    job.depths = (uint32_t) rm.depth_first.size() - 1u;
+    for (size_t d = 0; d < rm.depth_first.size(); d++) job.depth_first[d] = rm.depth_first[d];
+    for (uint32_t d = 0; d < job.depths; d++) widest = std::max(widest, job.depth_first[d + 1] - job.depth_first[d]);
+    job.num_nodes = rm.num_nodes; job.first_tri = mesh_tri_offset[m]; job.count = rm.count; job.mesh = m; job.root_slot = r.mesh_slots[m][0];
+    stride = std::max(stride, (rm.num_nodes + kRefitBlock - 1) / kRefitBlock);
+    depths = std::max(depths, job.depths);
+  }
+  if ((e = r.jobs.assign(jobs.data(), jobs.size())) != hipSuccess || (e = r.results.resize(jobs.size())) != hipSuccess ||
+      (e = r.partials.resize((size_t) stride * jobs.size())) != hipSuccess)
+    return e;
+  r.partial_stride = stride; r.widest = widest; r.depths = depths;
+  r.batch = moved;
+  for (const ResidentJob& job : jobs) r.batch_first_tri.push_back(job.first_tri);
+  return hipSuccess;
+}
+
+hipError_t resident_refit_run(ResidentRefit& r, const float4* d_vertices, BvhTri* d_tris, Bvh4Node* d_nodes, uint32_t capacity, uint32_t mesh_nodes, Aabb* d_mesh_box,
+                              uint32_t num_meshes, ResidentResult* out, uint32_t* launches, double seconds[2]) {
+  using clock = std::chrono::steady_clock;
+  const uint32_t jobs = (uint32_t) r.batch.size();
+  if (!jobs || r.batch_first_tri.size() != jobs || !r.jobs || !r.results || !r.partials || r.slot_box.count() != mesh_nodes || !d_vertices || !d_tris || !d_nodes || !d_mesh_box || !out) return hipErrorInvalidValue;
+  hipError_t e;
+  *launches = 0;
+  auto t = clock::now();
+  for (uint32_t j = 0; j < jobs; j++) {
+    const ResidentMesh& rm = r.mesh[r.batch[j]];
+    const uint32_t first_tri = r.batch_first_tri[j];
+    hipLaunchKernelGGL(k_refit_tri_boxes, dim3((rm.count + kRefitBlock - 1) / kRefitBlock), dim3(kRefitBlock), 0, 0, d_vertices + 3 * (size_t) first_tri, rm.prims.get(), rm.count,
+                       d_tris + first_tri, rm.prim_box.get());
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    (*launches)++;
+  }
+  for (uint32_t d = r.depths; d-- > 0;) {  // deepest first; launches on one stream run in order
+    hipLaunchKernelGGL(k_refit_level_resident, dim3((r.widest + kRefitBlock - 1) / kRefitBlock, jobs), dim3(kRefitBlock), 0, 0, d_nodes, capacity, mesh_nodes,
+                       (const ResidentJob*) r.jobs.get(), jobs, d, r.slot_box.get());
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    (*launches)++;
+  }
+  hipLaunchKernelGGL(k_resident_mesh_boxes, dim3((jobs + kRefitBlock - 1) / kRefitBlock), dim3(kRefitBlock), 0, 0, (const ResidentJob*) r.jobs.get(), jobs, capacity, mesh_nodes,
+                     (const Aabb*) r.slot_box.get(), d_mesh_box, num_meshes, r.results.get());
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  (*launches)++;
+  if ((e = hipDeviceSynchronize()) != hipSuccess) return e;
+  seconds[0] = std::chrono::duration<double>(clock::now() - t).count();
+  t = clock::now();
+  hipLaunchKernelGGL(k_bvh4_cost, dim3(r.partial_stride, jobs), dim3(kRefitBlock), 0, 0, (const Bvh4Node*) d_nodes, capacity, mesh_nodes, (const ResidentJob*) r.jobs.get(), jobs,
+                     r.partials.get(), r.partial_stride);
+  hipLaunchKernelGGL(k_bvh4_cost_sum, dim3(jobs), dim3(kRefitBlock), 0, 0, (const double*) r.partials.get(), r.partial_stride, (const ResidentJob*) r.jobs.get(), jobs, r.results.get());
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  *launches += 2;
+  e = hipMemcpy(out, r.results.get(), sizeof(ResidentResult) * jobs, hipMemcpyDeviceToHost);  // (waits for the launches)
+  seconds[1] = std::chrono::duration<double>(clock::now() - t).count();
   return e;
 }
 

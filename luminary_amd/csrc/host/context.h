@@ -37,6 +37,7 @@ struct MeshRefit {
   std::shared_ptr<MeshTree> own;   // the refitted tree (LumContext::mesh_bvh holds the same object): private, never in the process's tree cache
   uint64_t fit_hash[2] = {0, 0};   // of the vertices the held tree was built from or last fitted to (mesh_tree_key)
   double built_cost = 0.0;         // bvh4_cost of the tree as last built (0: not computed yet)
+  bool stale = false;              // the mesh was refitted in the resident node array since: the host's nodes hold the boxes of earlier vertices (restore_stale_meshes)
 };
 
 struct LumContext {
@@ -59,6 +60,11 @@ struct LumContext {
   std::vector<uint32_t> instance_mesh_ids;   // of the scene on the device: such an update must bring the same
   uint32_t instance_update_mode = 0;         // lumc_set_instance_update
   LumInstanceUpdateStats instance_stats{};
+  // LUMC_DIRTY_MESH_POSITIONS updates in the resident node array (lumc_set_mesh_refit_in_place; bvh_refit.hip, scene_device.hip refit_in_place)
+  uint32_t refit_in_place = 0;
+  ResidentRefit resident_refit;              // the layout's slot maps, the per-mesh slot lists and the scratch; dropped with the layout
+  uint32_t stale_meshes = 0;                 // meshes of mesh_refit marked stale
+  LumResidentRefitStats resident_stats{};
   std::vector<uint32_t> sky_lut_key;  // the sky parameters the two sky tables were generated from
   DeviceBuffer<float> d_bridge_lut;   // the bridge sampler's vertex-count table (context-owned: scene.bridge_lut points here while bridges are possible)
   std::vector<float> bridge_lut_host; // its content, to notice a caller that hands over another table

@@ -110,7 +110,44 @@ void free_scene(LumContext* ctx) {
   ctx->d_bridge_lut.reset(); ctx->bridge_lut_host.clear();
   ctx->mesh_bvh.clear(); ctx->mesh_box.clear(); ctx->mesh_refit.clear(); ctx->mesh_tri_offset.clear();
   ctx->instance_update.reset(); ctx->instance_mesh_ids.clear();
+  ctx->resident_refit.drop_layout(); ctx->stale_meshes = 0;
   ctx->has_scene = false;
+}
+
+// Host copies after refits in the resident node array (refit_in_place below): ctx->mesh_bvh[m] of a mesh marked stale holds the boxes of earlier vertices, and a
+// tree assembled or laid out from them would lose hits. Every reader of those nodes calls this first: the mesh part of the node array comes down, the box floats
+// go through the layout's slot map into a tree private to this context (created as refit_mesh_trees creates it: the shared, cached tree is never written), the mark
+// goes. Needs the layout the refits ran in: whoever drops it calls this before.
+int restore_stale_meshes(LumContext* ctx) {
+  if (!ctx->stale_meshes) return 0;
+  const ResidentRefit& rr = ctx->resident_refit;
+  const DeviceBuffer<Bvh4Node>& d_nodes = ctx->arrays.inst.nodes;
+  if (rr.mesh_slots.size() != ctx->mesh_bvh.size() || ctx->mesh_refit.size() != ctx->mesh_bvh.size() || !rr.mesh_nodes || d_nodes.count() != (size_t) rr.capacity + rr.mesh_nodes) {
+    ctx->error = "meshes refitted in the resident node array, and the layout they were refitted in is gone";
+    return 1;
+  }
+  std::vector<Bvh4Node> nodes(rr.mesh_nodes);
+  HIP_TRY(ctx, hipMemcpy(nodes.data(), d_nodes.get() + rr.capacity, sizeof(Bvh4Node) * rr.mesh_nodes, hipMemcpyDeviceToHost));
+  for (size_t m = 0; m < ctx->mesh_refit.size(); m++) {
+    MeshRefit& mr = ctx->mesh_refit[m];
+    if (!mr.stale) continue;
+    const std::vector<uint32_t>& slots = rr.mesh_slots[m];
+    const Bvh4& held = ctx->mesh_bvh[m]->bvh;
+    if (slots.size() != held.nodes.size()) { ctx->error = "the resident layout's slot map does not fit the mesh's tree"; return 1; }
+    if (!mr.own || mr.own.get() != ctx->mesh_bvh[m].get()) {
+      mr.own = std::make_shared<MeshTree>();
+      mr.own->bvh.prims = held.prims; mr.own->bvh.max_depth = held.max_depth; mr.own->built_on_gpu = ctx->mesh_bvh[m]->built_on_gpu;
+      mr.own->bvh.nodes = held.nodes;
+    }
+    for (size_t i = 0; i < slots.size(); i++) {
+      if (slots[i] < rr.capacity || slots[i] - rr.capacity >= rr.mesh_nodes) { ctx->error = "the resident layout's slot map points outside the mesh part"; return 1; }
+      std::memcpy(&mr.own->bvh.nodes[i], &nodes[slots[i] - rr.capacity], offsetof(Bvh4Node, child));  // the 24 box floats; the child words stay relative to the mesh
+    }
+    ctx->mesh_bvh[m] = mr.own;
+    mr.stale = false;
+  }
+  ctx->stale_meshes = 0;
+  return 0;
 }
 
 }  // namespace
@@ -228,6 +265,7 @@ static int update_mesh_arrays(LumContext* ctx, const LumDeviceSceneView* v) {
 static int update_instance_arrays(LumContext* ctx, const LumDeviceSceneView* v) {
   DeviceScene& sc = ctx->scene;
   SceneArrays::Inst& a = ctx->arrays.inst;
+  if (restore_stale_meshes(ctx)) return 1;  // (the node array goes: what was refitted in it comes down first)
   a = {}; point_views(sc, a);
   ctx->instance_mesh_ids.assign(v->instance_mesh_ids, v->instance_mesh_ids + v->num_instances);
   if (upload(ctx, a.mesh_ids, v->instance_mesh_ids, v->num_instances, &sc.instance_mesh_ids)) return 1;
@@ -314,7 +352,7 @@ static int build_mesh_trees(LumContext* ctx, const LumDeviceSceneView* v, std::v
   ctx->mesh_bvh.assign(v->num_meshes, nullptr);
   ctx->mesh_box.assign(v->num_meshes, Aabb{});
   mesh_boxes_changed(ctx);
-  ctx->mesh_refit.clear(); ctx->mesh_refit.resize(v->num_meshes);
+  ctx->mesh_refit.clear(); ctx->mesh_refit.resize(v->num_meshes); ctx->stale_meshes = 0;
   ctx->mesh_tri_offset.assign(v->mesh_tri_offset, v->mesh_tri_offset + v->num_meshes + 1);
   blas_tris.assign((size_t) total_triangles(v) + 1, BvhTri{});
   for (uint32_t m = 0; m < v->num_meshes; m++) {
@@ -339,7 +377,7 @@ static int build_mesh_trees(LumContext* ctx, const LumDeviceSceneView* v, std::v
 // every mesh whose vertices differ from those its held tree was fitted to gets a tree for them: refitted on the device (bvh_refit.hip; the tree becomes
 // private to this context, the shared one it came from is not touched and the cache never sees the refitted one) or, where the mode, the cost's growth or a
 // tree that cannot be refitted says so, from the cache / the builder like an upload. *rebuilt: a mesh's traversal triangles were written anew (k_tri_opacity).
-static int refit_mesh_trees(LumContext* ctx, const LumDeviceSceneView* v, bool* rebuilt) {
+static int refit_mesh_trees(LumContext* ctx, const LumDeviceSceneView* v, bool* rebuilt, bool arrays_uploaded = false) {
   using clock = std::chrono::steady_clock;
   auto since = [](clock::time_point t) { return std::chrono::duration<double>(clock::now() - t).count(); };
   DeviceScene& sc = ctx->scene;
@@ -347,6 +385,7 @@ static int refit_mesh_trees(LumContext* ctx, const LumDeviceSceneView* v, bool* 
   st.last_refits = st.last_rebuilds = 0; st.max_cost_growth = st.seconds = st.seconds_upload = st.seconds_refit = st.seconds_rebuild = st.seconds_assemble = 0.0;
   st.seconds_hash = st.seconds_download = st.seconds_lights = 0.0;
   *rebuilt = false;
+  if (restore_stale_meshes(ctx)) return 1;
   if (ctx->mesh_bvh.size() != v->num_meshes || ctx->mesh_refit.size() != v->num_meshes || ctx->mesh_tri_offset.size() != (size_t) v->num_meshes + 1 ||
       std::memcmp(ctx->mesh_tri_offset.data(), v->mesh_tri_offset, sizeof(uint32_t) * ((size_t) v->num_meshes + 1)) != 0) {
     ctx->error = "lumc_scene_update: LUMC_DIRTY_MESH_POSITIONS with other meshes or triangle counts than the scene on the device";
@@ -355,7 +394,7 @@ static int refit_mesh_trees(LumContext* ctx, const LumDeviceSceneView* v, bool* 
   const auto t_all = clock::now();
   BvhTri* d_tris = ctx->arrays.mesh.blas_tris.get();
   if (!d_tris) { ctx->error = "lumc_scene_update: the scene on the device has no traversal triangles"; return 1; }
-  if (update_mesh_arrays(ctx, v)) return 1;
+  if (!arrays_uploaded && update_mesh_arrays(ctx, v)) return 1;  // (a fallback from refit_in_place has uploaded them)
   HIP_TRY(ctx, hipDeviceSynchronize());
   st.seconds_upload = since(t_all);
   for (uint32_t m = 0; m < v->num_meshes; m++) {
@@ -420,6 +459,7 @@ static int refit_mesh_trees(LumContext* ctx, const LumDeviceSceneView* v, bool* 
 static int update_scene_tree(LumContext* ctx, const LumDeviceSceneView* v, bool dirty_meshes, size_t* num_nodes) {
   DeviceScene& sc = ctx->scene;
   std::vector<BvhTri> blas_tris;
+  if (!dirty_meshes && restore_stale_meshes(ctx)) return 1;  // (new meshes: build_mesh_trees replaces every tree and mark)
   if (dirty_meshes && build_mesh_trees(ctx, v, blas_tris)) return 1;
   if (ctx->mesh_box.size() != v->num_meshes || ctx->mesh_bvh.size() != v->num_meshes) { ctx->error = "lumc_scene_update: the meshes changed but LUMC_DIRTY_MESHES is not set"; return 1; }
   std::vector<const Bvh4*> mesh_bvh(v->num_meshes);
@@ -430,6 +470,7 @@ static int update_scene_tree(LumContext* ctx, const LumDeviceSceneView* v, bool 
   // by instance id: the exact flavour's ambient reuse re-tests a ray against a hit's triangle (k_resolve_reuse)
   if (upload(ctx, ctx->arrays.inst.rows, tree.inv_rows.data(), tree.inv_rows.size(), &sc.instance_rows)) return 1;
   ctx->instance_update.resident = false;  // the one place: the node array in assemble_scene_tree's order, not relayout_resident's
+  ctx->resident_refit.drop_layout();      // ... and with the layout the slot lists of the refits in it
   if (upload(ctx, ctx->arrays.inst.nodes, tree.nodes.data(), tree.nodes.size(), &sc.bvh_nodes)) return 1;
   if (dirty_meshes && upload(ctx, ctx->arrays.mesh.blas_tris, blas_tris.data(), blas_tris.size(), &sc.blas_tris)) return 1;
   if (upload(ctx, ctx->arrays.inst.tlas_leaves, tree.tlas_leaves.data(), tree.tlas_leaves.size(), &sc.tlas_leaves)) return 1;
@@ -471,11 +512,14 @@ static int relayout_resident(LumContext* ctx, const LumDeviceSceneView* v) {
   InstanceUpdate& u = ctx->instance_update;
   SceneArrays::Inst& a = ctx->arrays.inst;
   const uint32_t n = v->num_instances, capacity = std::max<uint32_t>(1u, n > 0 ? n - 1u : 0u);
+  if (restore_stale_meshes(ctx)) return 1;
+  ResidentRefit& rr = ctx->resident_refit;
+  rr.drop_layout();
   std::vector<const Bvh4*> mesh_bvh(v->num_meshes);
   for (uint32_t m = 0; m < v->num_meshes; m++) mesh_bvh[m] = &ctx->mesh_bvh[m]->bvh;
   std::vector<Bvh4Node> nodes;
   std::vector<uint32_t> mesh_root;
-  layout_resident_nodes(*v, mesh_bvh.data(), capacity, nodes, mesh_root);
+  layout_resident_nodes(*v, mesh_bvh.data(), capacity, nodes, mesh_root, ctx->refit_in_place ? &rr.mesh_slots : nullptr);
   if (total_triangles(v) >= (1u << 28) || nodes.size() >= (1u << 25)) { ctx->error = "scene too large for 28-bit leaf ranges / 32-bit node offsets"; return 1; }
   a.nodes.reset(); a.tlas_leaves.reset(); point_views(sc, a);
   if (upload(ctx, a.nodes, nodes.data(), nodes.size(), &sc.bvh_nodes)) return 1;
@@ -484,6 +528,7 @@ static int relayout_resident(LumContext* ctx, const LumDeviceSceneView* v) {
   HIP_TRY(ctx, hipMemset(a.tlas_leaves.get(), 0, sizeof(float4) * 4 * ((size_t) n + 1)));
   HIP_TRY(ctx, u.mesh_root.assign(mesh_root.data(), v->num_meshes));
   u.capacity = capacity; u.mesh_nodes = (uint32_t) (nodes.size() - capacity); u.tlas_nodes = 0;
+  rr.capacity = u.capacity; rr.mesh_nodes = u.mesh_nodes;
   if (update_ray_kernel_lds(ctx, nodes.size())) return 1;
   u.resident = true;
   return 0;
@@ -492,7 +537,9 @@ static int relayout_resident(LumContext* ctx, const LumDeviceSceneView* v) {
 // One update on the device: the transforms into the array that is there, then rows, boxes, top level and leaf records derived from them in place. *fell_back: the
 // device path could not take this update (fewer than two instances that can be hit, a top level deeper than 16, a failed allocation): nothing the scene points
 // at is left half written that the host path, which the caller runs then, does not replace.
-static int update_instance_transforms(LumContext* ctx, const LumDeviceSceneView* v, bool* fell_back) {
+// layout_only: stops once the scratch and the resident layout are there (refit_in_place, before it refits in that layout: the top level follows in a second call);
+// upload = false: the transforms on the device are the update's (they did not move, or that first call uploaded them).
+static int update_instance_transforms(LumContext* ctx, const LumDeviceSceneView* v, bool* fell_back, bool layout_only = false, bool upload = true) {
   using clock = std::chrono::steady_clock;
   auto since = [](clock::time_point t) { return std::chrono::duration<double>(clock::now() - t).count(); };
   DeviceScene& sc = ctx->scene;
@@ -513,7 +560,7 @@ static int update_instance_transforms(LumContext* ctx, const LumDeviceSceneView*
     if (instance_update_prepare(u, n, v->num_meshes, ctx->mesh_box.data()) != hipSuccess) { (void) hipGetLastError(); u.reset(); *fell_back = true; return 0; }
   }
   auto t = clock::now();
-  if (n) HIP_TRY(ctx, hipMemcpy(a.transforms.get(), v->instance_transforms, sizeof(float4) * 2 * (size_t) n, hipMemcpyHostToDevice));
+  if (n && upload) HIP_TRY(ctx, hipMemcpy(a.transforms.get(), v->instance_transforms, sizeof(float4) * 2 * (size_t) n, hipMemcpyHostToDevice));
   HIP_TRY(ctx, hipDeviceSynchronize());
   st.seconds_upload = since(t);
   t = clock::now();
@@ -529,6 +576,7 @@ static int update_instance_transforms(LumContext* ctx, const LumDeviceSceneView*
     st.relayouts++;
     st.seconds_relayout = since(t);
   }
+  if (layout_only) return 0;
   t = clock::now();
   uint32_t num_nodes = 0, depth = 0;
   Bvh4Node* d_nodes = a.nodes.get();  // (after the layout, which replaces the array)
@@ -551,6 +599,106 @@ static int update_instance_transforms(LumContext* ctx, const LumDeviceSceneView*
   st.device_updates++;
   st.tlas_nodes = num_nodes; st.tlas_depth = depth; st.tlas_capacity = u.capacity; st.hittable = hittable;
   st.seconds = since(t_all);
+  return 0;
+}
+
+// ---- LUMC_DIRTY_MESH_POSITIONS where the nodes live (lum_core.h lumc_set_mesh_refit_in_place; bvh_refit.hip) ----
+// The mesh part of such an update: the vertex arrays, the meshes that moved (by their hashes), then - in the resident layout, laid out first if there is none -
+// their triangle boxes, their node boxes in [C, C + M), their root boxes into the moved instances' scratch and their costs. No node leaves or enters the device;
+// the host's copies of the moved meshes' nodes become stale (restore_stale_meshes). The top level follows in scene_update (update_instance_transforms).
+// *fell_back: this update takes refit_mesh_trees' path instead (a moved mesh that cannot be refitted, fewer than two instances that can be hit, a failed
+// allocation or layout, a cost growth beyond the threshold); the vertex arrays are uploaded, the context is consistent: nothing else was written, or what was
+// written in place is marked stale.
+static int refit_in_place(LumContext* ctx, const LumDeviceSceneView* v, bool* fell_back) {
+  using clock = std::chrono::steady_clock;
+  auto since = [](clock::time_point t) { return std::chrono::duration<double>(clock::now() - t).count(); };
+  DeviceScene& sc = ctx->scene;
+  InstanceUpdate& u = ctx->instance_update;
+  ResidentRefit& rr = ctx->resident_refit;
+  LumMeshRefitStats& st = ctx->refit_stats;
+  LumResidentRefitStats& rs = ctx->resident_stats;
+  st.last_refits = st.last_rebuilds = 0; st.max_cost_growth = st.seconds = st.seconds_upload = st.seconds_refit = st.seconds_rebuild = st.seconds_assemble = 0.0;
+  st.seconds_hash = st.seconds_download = st.seconds_lights = 0.0;
+  rs.last_meshes = rs.last_launches = 0; rs.last_bytes_downloaded = 0;
+  rs.seconds = rs.seconds_upload = rs.seconds_hash = rs.seconds_refit = rs.seconds_cost = rs.seconds_top_level = 0.0;
+  *fell_back = false;
+  if (ctx->mesh_bvh.size() != v->num_meshes || ctx->mesh_refit.size() != v->num_meshes || ctx->mesh_tri_offset.size() != (size_t) v->num_meshes + 1 ||
+      std::memcmp(ctx->mesh_tri_offset.data(), v->mesh_tri_offset, sizeof(uint32_t) * ((size_t) v->num_meshes + 1)) != 0) {
+    ctx->error = "lumc_scene_update: LUMC_DIRTY_MESH_POSITIONS with other meshes or triangle counts than the scene on the device";
+    return 1;
+  }
+  const auto t_all = clock::now();
+  BvhTri* d_tris = ctx->arrays.mesh.blas_tris.get();
+  if (!d_tris) { ctx->error = "lumc_scene_update: the scene on the device has no traversal triangles"; return 1; }
+  if (update_mesh_arrays(ctx, v)) return 1;
+  HIP_TRY(ctx, hipDeviceSynchronize());
+  rs.seconds_upload = st.seconds_upload = since(t_all);
+  // the meshes that moved
+  auto t = clock::now();
+  std::vector<uint32_t> moved;
+  std::vector<MeshTreeKey> keys;
+  for (uint32_t m = 0; m < v->num_meshes; m++) {
+    const uint32_t t0 = v->mesh_tri_offset[m], nt = v->mesh_tri_offset[m + 1] - t0;
+    if (nt == 0) continue;
+    const MeshTreeKey key = mesh_tree_key(v->vertices + (size_t) t0 * 12, nt, ctx->bvh_builder);
+    if (key.h0 == ctx->mesh_refit[m].fit_hash[0] && key.h1 == ctx->mesh_refit[m].fit_hash[1]) continue;  // the held tree fits these vertices
+    if (ctx->mesh_bvh[m]->bvh.prims.size() != nt) { *fell_back = true; return 0; }  // spatial splits: the other path builds it
+    moved.push_back(m); keys.push_back(key);
+  }
+  rs.seconds_hash = st.seconds_hash = since(t);
+  t = clock::now();
+  // the layout, and the moved instances' scratch with the meshes' boxes in it
+  if (!u.resident || !u.prepared || u.num_instances != v->num_instances || u.num_meshes != v->num_meshes || rr.mesh_slots.size() != v->num_meshes) {
+    if (u.resident && rr.mesh_slots.size() != v->num_meshes) {  // laid out while the switch was off: once more, for the slot map
+      if (restore_stale_meshes(ctx)) return 1;
+      u.resident = false;
+    }
+    if (update_instance_transforms(ctx, v, fell_back, true)) return 1;
+    if (*fell_back) return 0;
+    if (!u.resident || !u.prepared || rr.mesh_slots.size() != v->num_meshes) { *fell_back = true; return 0; }
+  }
+  if (moved.empty()) { rs.seconds = since(t_all); st.seconds = rs.seconds; return 0; }  // (nothing to refit: the top level alone)
+  // everything that can fail, before a node is written
+  if (rr.mesh.size() != v->num_meshes) { rr.mesh.clear(); rr.mesh.resize(v->num_meshes); rr.batch.clear(); }
+  for (uint32_t m : moved) {
+    MeshRefit& mr = ctx->mesh_refit[m];
+    if (mr.built_cost == 0.0) mr.built_cost = bvh4_cost(ctx->mesh_bvh[m]->bvh);  // (no refit yet: the held tree is the built one, and not stale)
+    if (rr.mesh[m].slots) continue;
+    const hipError_t e = resident_mesh_create(rr.mesh[m], ctx->mesh_bvh[m]->bvh, v->mesh_tri_offset[m + 1] - v->mesh_tri_offset[m], rr.mesh_slots[m]);
+    if (e != hipSuccess) { (void) hipGetLastError(); *fell_back = true; return 0; }
+  }
+  if (resident_refit_prepare(rr, moved, v->mesh_tri_offset, u.mesh_nodes) != hipSuccess) { (void) hipGetLastError(); *fell_back = true; return 0; }
+  // the refit
+  std::vector<ResidentResult> results(moved.size());
+  uint32_t launches = 0;
+  double seconds[2] = {0.0, 0.0};
+  HIP_TRY(ctx, resident_refit_run(rr, sc.vertices, d_tris, ctx->arrays.inst.nodes.get(), u.capacity, u.mesh_nodes, u.mesh_box.get(), u.num_meshes, results.data(), &launches, seconds));
+  for (uint32_t m : moved) if (!ctx->mesh_refit[m].stale) { ctx->mesh_refit[m].stale = true; ctx->stale_meshes++; }  // from here on the device's nodes are ahead of the host's
+  rs.seconds_cost = seconds[1];
+  rs.seconds_refit = since(t) - seconds[1];
+  double max_growth = 0.0;
+  bool grown = false;
+  for (size_t j = 0; j < moved.size(); j++) {
+    const MeshRefit& mr = ctx->mesh_refit[moved[j]];
+    const double growth = mr.built_cost > 0.0 ? results[j].cost / mr.built_cost : 1.0;
+    max_growth = std::max(max_growth, growth);
+    if (ctx->refit_max_cost_growth > 0.0f && growth > (double) ctx->refit_max_cost_growth) grown = true;
+  }
+  if (grown) {  // the other path refits from the restored nodes, measures the same growth and builds the mesh again; it writes ctx->mesh_box and drops `prepared`
+    *fell_back = true;
+    return 0;
+  }
+  for (size_t j = 0; j < moved.size(); j++) {
+    MeshRefit& mr = ctx->mesh_refit[moved[j]];
+    ctx->mesh_box[moved[j]] = results[j].box;  // (u.mesh_box on the device holds it already: `prepared` stays)
+    mr.fit_hash[0] = keys[j].h0; mr.fit_hash[1] = keys[j].h1;
+    st.refits++; st.last_refits++;
+  }
+  st.max_cost_growth = max_growth;
+  st.seconds_refit = rs.seconds_refit + rs.seconds_cost;
+  rs.last_meshes = (uint32_t) moved.size(); rs.last_launches = launches;
+  rs.last_bytes_downloaded = sizeof(ResidentResult) * moved.size();
+  rs.seconds = st.seconds = since(t_all);
   return 0;
 }
 
@@ -814,19 +962,35 @@ static int scene_update(LumContext* ctx, const LumDeviceSceneView* v, unsigned d
   if (!v->bluenoise_2d) { ctx->error = "scene has no blue-noise mask"; return 1; }
   if (v->max_ray_depth > 63) { ctx->error = "max_ray_depth exceeds 63 (6-bit field, device_structs.h:9)"; return 1; }
   if (dirty & LUMC_DIRTY_MESHES) dirty &= ~(unsigned) LUMC_DIRTY_MESH_POSITIONS;  // a full rebuild of the meshes covers moved vertices
-  if (dirty & (LUMC_DIRTY_MESHES | LUMC_DIRTY_MESH_POSITIONS)) dirty |= LUMC_DIRTY_INSTANCES;  // the assembled node array holds the per-mesh trees
+  // lumc_set_mesh_refit_in_place: moved vertices alone or with moved instances, both modes 0 - the refit happens in the resident node array, the top level follows as for moved instances
+  bool in_place = ctx->refit_in_place && (dirty & LUMC_DIRTY_MESH_POSITIONS) && !(dirty & (LUMC_DIRTY_MESHES | LUMC_DIRTY_INSTANCES)) && ctx->refit_mode == 0 && ctx->instance_update_mode == 0;
+  const bool instances_moved = (dirty & LUMC_DIRTY_INSTANCE_TRANSFORMS) != 0;
+  if (in_place) dirty |= LUMC_DIRTY_INSTANCE_TRANSFORMS;
+  else if (dirty & (LUMC_DIRTY_MESHES | LUMC_DIRTY_MESH_POSITIONS)) dirty |= LUMC_DIRTY_INSTANCES;  // the assembled node array holds the per-mesh trees
   if (dirty & LUMC_DIRTY_PARTICLES) dirty |= LUMC_DIRTY_CONSTANTS;
   if (dirty & (LUMC_DIRTY_INSTANCES | LUMC_DIRTY_MESHES)) dirty &= ~(unsigned) LUMC_DIRTY_INSTANCE_TRANSFORMS;  // the instance part covers moved instances
   const bool moved_by_host = (dirty & LUMC_DIRTY_INSTANCE_TRANSFORMS) && ctx->instance_update_mode == 1;  // mode 1: exactly LUMC_DIRTY_INSTANCES; its time is reported
   if (moved_by_host) { dirty = (dirty & ~(unsigned) LUMC_DIRTY_INSTANCE_TRANSFORMS) | LUMC_DIRTY_INSTANCES; ctx->instance_stats.seconds = ctx->instance_stats.seconds_relayout = ctx->instance_stats.seconds_upload = ctx->instance_stats.seconds_boxes = ctx->instance_stats.seconds_build = ctx->instance_stats.seconds_leaves = 0.0; }
   auto host_path_since = [&](std::chrono::steady_clock::time_point t) { if (moved_by_host) ctx->instance_stats.seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count(); };
-  const bool meshes = (dirty & LUMC_DIRTY_MESHES) != 0, instances = (dirty & LUMC_DIRTY_INSTANCES) != 0, lights = (dirty & LUMC_DIRTY_LIGHTS) != 0;
+  const bool meshes = (dirty & LUMC_DIRTY_MESHES) != 0, lights = (dirty & LUMC_DIRTY_LIGHTS) != 0;
+  bool instances = (dirty & LUMC_DIRTY_INSTANCES) != 0;
   ctx->has_scene = false;
   if (meshes) ctx->arrays.mesh = {};  // the traversal triangles too
   if (meshes && update_mesh_arrays(ctx, v)) return 1;
-  if (dirty & LUMC_DIRTY_MESH_POSITIONS) {
+  bool arrays_uploaded = false;
+  if (in_place) {
+    bool fell_back = false;
+    if (refit_in_place(ctx, v, &fell_back)) return 1;
+    if (fell_back) {  // this one update by the other path, as it would have run with the switch off
+      ctx->resident_stats.fallbacks++;
+      in_place = false; arrays_uploaded = true;
+      dirty = (dirty & ~(unsigned) LUMC_DIRTY_INSTANCE_TRANSFORMS) | LUMC_DIRTY_INSTANCES;
+      instances = true;
+    }
+  }
+  if ((dirty & LUMC_DIRTY_MESH_POSITIONS) && !in_place) {
     bool rebuilt = false;
-    if (refit_mesh_trees(ctx, v, &rebuilt)) return 1;
+    if (refit_mesh_trees(ctx, v, &rebuilt, arrays_uploaded)) return 1;
     if (rebuilt) dirty |= kDirtyTrianglesRewritten;
   }
   const auto t_arrays = std::chrono::steady_clock::now();
@@ -846,11 +1010,18 @@ static int scene_update(LumContext* ctx, const LumDeviceSceneView* v, unsigned d
   if (moved_by_host) { HIP_TRY(ctx, hipDeviceSynchronize()); host_path_since(t_assemble); }
   if (dirty & LUMC_DIRTY_INSTANCE_TRANSFORMS) {
     bool fell_back = false;
-    if (update_instance_transforms(ctx, v, &fell_back)) return 1;
+    if (update_instance_transforms(ctx, v, &fell_back, false, instances_moved || !in_place)) return 1;
     if (fell_back) {  // this one update by the host's path, as LUMC_DIRTY_INSTANCES
-      if (update_instance_arrays(ctx, v) || update_scene_tree(ctx, v, false, &num_nodes) || update_ray_kernel_lds(ctx, num_nodes)) return 1;
+      if (update_instance_arrays(ctx, v) || update_scene_tree(ctx, v, false, &num_nodes) || update_ray_kernel_lds(ctx, num_nodes)) return 1;  // (update_scene_tree brings meshes refitted in place back to the host first)
       ctx->instance_stats.fallbacks++;
       ctx->instance_stats.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_assemble).count();
+    }
+    if (in_place) {
+      LumResidentRefitStats& rs = ctx->resident_stats;
+      if (fell_back) rs.fallbacks++; else rs.updates++;
+      rs.seconds_top_level = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_assemble).count();
+      rs.seconds += rs.seconds_top_level;
+      rs.last_bytes_downloaded += 28;  // instance_update_boxes: the bounds and the count
     }
   }
   if (dirty & LUMC_DIRTY_MESH_POSITIONS) ctx->refit_stats.seconds_assemble = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_assemble).count();
@@ -906,6 +1077,29 @@ int lumc_set_instance_update(LumContext* ctx, uint32_t mode) {
 int lumc_instance_update_stats(const LumContext* ctx, LumInstanceUpdateStats* out) {
   if (!ctx || !out) return 1;
   *out = ctx->instance_stats;
+  return 0;
+}
+
+int lumc_set_mesh_refit_in_place(LumContext* ctx, uint32_t on) {
+  if (!ctx) return 1;
+  if (on > 1) { ctx->error = "lumc_set_mesh_refit_in_place: on is 0 or 1"; return 1; }
+  ctx->refit_in_place = on;
+  return 0;
+}
+
+int lumc_resident_refit_stats(const LumContext* ctx, LumResidentRefitStats* out) {
+  if (!ctx || !out) return 1;
+  *out = ctx->resident_stats;
+  return 0;
+}
+
+int lumc_resident_mesh_nodes_probe(LumContext* ctx, void* nodes) {
+  if (!ctx || !nodes) return 1;
+  const InstanceUpdate& u = ctx->instance_update;
+  if (!ctx->has_scene || !u.resident) { ctx->error = "lumc_resident_mesh_nodes_probe: the context has no resident layout"; return 1; }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (ctx->arrays.inst.nodes.count() != (size_t) u.capacity + u.mesh_nodes) { ctx->error = "lumc_resident_mesh_nodes_probe: the node array is not the layout's"; return 1; }
+  if (u.mesh_nodes) HIP_TRY(ctx, hipMemcpy(nodes, ctx->scene.bvh_nodes + u.capacity, sizeof(Bvh4Node) * u.mesh_nodes, hipMemcpyDeviceToHost));
   return 0;
 }
 

@@ -264,6 +264,16 @@ class Core:
         fn.restype = C.c_int
         return bool(fn(self._ctx))
 
+    def set_single_level(self, mode):
+        """-1 auto, 0 never, 1 when eligible: the ray kernels walk a scene of one hittable instance from its mesh root (lumc_set_single_level; bit-identical)"""
+        self._call("lumc_set_single_level", C.c_int(mode))
+
+    def get_single_level(self):
+        """1 when the next ray-kernel launch takes the single-level form for the uploaded scene (lumc_get_single_level: by mode and scene), else 0"""
+        fn = self._lib.lumc_get_single_level
+        fn.restype = C.c_int
+        return int(fn(self._ctx))
+
     def set_physical_camera(self, camera):
         """lumc_set_physical_camera: a PhysicalCamera, or None for the scene's thin lens"""
         self._call("lumc_set_physical_camera", C.byref(camera) if camera is not None else C.c_void_p(0))

@@ -24,6 +24,17 @@
 //     24 fma, v_max3/v_min3, a 5-comparator sorting network on (entry distance, child) pairs and conditional pushes: ~110 vector instructions;
 //   * every wave iteration runs ONE phase - node visit, instance entry or triangle tests - chosen by a vote over its lanes, so a
 //     lane that holds a leaf does not wait for the slowest lane of the wave to find one (plain while-while: 0.33-0.41 lane occupancy);
+//   * TWO FORMS of the walk (trace_items<Q, kSingleLevel>), chosen by the launchers at every launch (single_level_scene, wavefront_table.h). The two-level form is
+//     the one described here. The single-level form is for a scene of ONE hittable instance - one mesh placed once, like the hall: the top level of such a scene
+//     decides nothing the mesh tree's root does not decide on its first visit, yet every ray visited top-level node 0, waited for the voted instance-entry phase,
+//     pushed the kLeaveInstance marker (one of its 12 / 24 LDS stack slots for the whole walk), popped it in an extra turn of the pop loop and rebuilt the
+//     world-space ray when it was finished anyway. There the wave reads leaf record 0 once into scalar registers, a ray is mapped to object space where it is
+//     loaded and starts at the mesh root; two phases, two ballots per vote, no wo / wd / inst in registers (fast flavour: k_trace 114 -> 96 VGPRs, k_shadow_rays 111 -> 93).
+//     Measured on the hall against the parent commit, same box, ms per 3 steps of 64 ids (profiles/single_level_ab.txt): k_trace 408.5 -> 363.1 (-11.1 %),
+//     k_shadow_rays 322.6 -> 287.9 (-10.7 %), 2.832e8 -> 3.004e8 samples/s (+6.1 %); node visits per ray drop by exactly one (CNT_NODES, CNT_NODES_SHADOW and the
+//     LDS-hit counters with them). Every output keeps its bits (tests/test_single_level.py); the fast flavour takes the form only for an identity transform
+//     (csrc/host/context.h single_level_allowed: under -ffp-contract=fast two instantiations of the map round differently). The two-level kernels' code is the
+//     parent's to the instruction (profiles/single_level_isa_identity.txt): what a scene of several instances runs did not change;
 //   * persistent waves fetch rays from a global cursor and refill idle lanes when too few are still traversing;
 //   * the first nodes of the array (breadth-first across both levels; 448 of them beside 96 KB of stack bottoms since round 6, 704 beside 64 KB before) are staged in LDS by
 //     every workgroup, the oldest 12 (visibility rays: 24) stack entries of every lane live there too: LDS hit rate of the node visits 0.62 / 0.72 with the 704.
@@ -273,6 +284,13 @@ struct LeafTris {
   }
 };
 
+// The one instance of a single-level walk (trace_items<Q, true>): leaf record 0 - the rows of its world->object matrix, its id and its mesh tree's root - in
+// wave-uniform registers. The two-level form has no such thing: an empty type, so that nothing of it reaches that instantiation's code.
+template <bool kSingleLevel> struct OneInstance {};
+template <> struct OneInstance<true> { float4 r0, r1, r2; uint32_t inst, root; };
+LUM_DEV uint32_t instance_of(const OneInstance<false>&, uint32_t entered) { return entered; }
+LUM_DEV uint32_t instance_of(const OneInstance<true>& one, uint32_t) { return one.inst; }
+
 // ---- the persistent two-level traversal ----
 // A query type Q provides (all per lane):
 //   bool load(sc, idx, origin, dir, tmax)   read item idx; false = nothing to trace
@@ -281,7 +299,12 @@ struct LeafTris {
 //   void finish(sc, idx)                    write the result of the finished ray
 // Top-level leaves hold exactly one instance; entering it pushes a marker and maps the ray with the instance's world->object
 // matrix (an affine map preserves distances along the ray, so tmax and the stacked entry distances stay valid across levels).
-template <class Q>
+// kSingleLevel (the launchers pick it per launch for a scene of ONE hittable instance: single_level_scene, wavefront_table.h): the top level of such a scene
+// decides nothing the mesh tree's root does not decide on its first visit. The wave reads leaf record 0 once, a ray is mapped to object space where it is loaded
+// (the expressions of the instance-entry phase below, in their order) and starts at the mesh root: no visit of top-level node 0, no entry phase, no marker on
+// the stack, no restore of the world-space ray, two phases to vote on. Same triangles tested in the same order per lane: every output keeps its bits
+// (tests/test_single_level.py); CNT_NODES and the LDS-hit count drop by one per ray.
+template <class Q, bool kSingleLevel = false>
 LUM_DEV void trace_items(const DeviceScene& sc, uint32_t n, uint32_t* __restrict__ cursor, Q& q, RayStats& st, uint32_t& rays, uint32_t lds_count) {
   if (n == 0u) return;  // wave-uniform (a kernel argument read from the control words): an empty launch - the ambient reuse's fallback list on an opaque scene - stages nothing
   using SE = StackEntry<Q::kCull>;
@@ -305,10 +328,19 @@ LUM_DEV void trace_items(const DeviceScene& sc, uint32_t n, uint32_t* __restrict
   }
   // ... and the records of the first top-level leaves (the rows of an instance's world->object matrix): entering one of those instances costs no
   // memory round trip. A scene of one mesh, like the hall, has one; 72 instances are 4.5 KB.
-  __shared__ float4 lds_leaves[4u * LUM_LDS_INSTANCES];
-  const uint32_t staged_leaves = min(sc.tlas_num_leaves, (uint32_t) LUM_LDS_INSTANCES);
-  for (uint32_t i = threadIdx.x; i < 4u * staged_leaves; i += blockDim.x) lds_leaves[i] = sc.tlas_leaves[i];
-  __syncthreads();
+  // (the single-level form reads the one record into wave-uniform registers instead and stages nothing)
+  __shared__ float4 lds_leaves[kSingleLevel ? 1u : 4u * LUM_LDS_INSTANCES];
+  const uint32_t staged_leaves = kSingleLevel ? 0u : min(sc.tlas_num_leaves, (uint32_t) LUM_LDS_INSTANCES);
+  if constexpr (!kSingleLevel) {
+    for (uint32_t i = threadIdx.x; i < 4u * staged_leaves; i += blockDim.x) lds_leaves[i] = sc.tlas_leaves[i];
+    __syncthreads();
+  }
+  [[maybe_unused]] OneInstance<kSingleLevel> one;
+  if constexpr (kSingleLevel) {  // wave-uniform: the address is a kernel argument
+    const float4* __restrict__ leaf = sc.tlas_leaves;
+    const float4 meta = leaf[3];
+    one.r0 = leaf[0]; one.r1 = leaf[1]; one.r2 = leaf[2]; one.inst = fbits(meta.x); one.root = fbits(meta.y);
+  }
   const NodeSource nodes{sc.bvh_nodes, reinterpret_cast<const char*>(lds_top), lds_count};
   typedef typename TraversalStack<E>::W StackW;
   static_assert(sizeof(StackW) == sizeof(E), "a stack entry is one machine word");
@@ -329,6 +361,17 @@ LUM_DEV void trace_items(const DeviceScene& sc, uint32_t n, uint32_t* __restrict
     // any other entry has something below it.
     bool left_instance = false, again;
     E e;
+    if constexpr (kSingleLevel) {  // no marker on the stack, nothing to restore
+      do {
+        e = top;
+        const bool done = SE::node(e) == kTraversalDone;
+        if (!done) { sp--; top = stk.load(sp); }
+        again = !done && !SE::reachable(e, tmax);
+      } while (again);
+      cur = SE::node(e);
+      (void) left_instance;
+      return;
+    }
     do {
       e = top;
       const bool done = SE::node(e) == kTraversalDone, leave = SE::node(e) == kLeaveInstance;
@@ -376,8 +419,21 @@ LUM_DEV void trace_items(const DeviceScene& sc, uint32_t n, uint32_t* __restrict
             const uint32_t e = 0x7F800000u;
             const bool finite = (fbits(wo.x) & e) != e && (fbits(wo.y) & e) != e && (fbits(wo.z) & e) != e && (fbits(wd.x) & e) != e && (fbits(wd.y) & e) != e &&
                                 (fbits(wd.z) & e) != e;
-            if (finite) { r.set(wo, wd); cur = 0; sp = 0; top = SE::make(kTraversalDone, 0.0f); inst = kNoInstance; }
-            else q.finish(sc, idx);
+            if constexpr (kSingleLevel) {
+              if (finite) {  // the instance-entry phase's map, expression for expression
+                const float4 r0 = one.r0, r1 = one.r1, r2 = one.r2;
+                const float px = wo.x - r0.w, py = wo.y - r1.w, pz = wo.z - r2.w;
+                const V3 oo = v3(mat_row_apply(r0.x, r0.y, r0.z, px, py, pz), mat_row_apply(r1.x, r1.y, r1.z, px, py, pz), mat_row_apply(r2.x, r2.y, r2.z, px, py, pz));
+                const V3 od = v3(mat_row_apply(r0.x, r0.y, r0.z, wd.x, wd.y, wd.z), mat_row_apply(r1.x, r1.y, r1.z, wd.x, wd.y, wd.z),
+                                 mat_row_apply(r2.x, r2.y, r2.z, wd.x, wd.y, wd.z));
+                r.set(oo, od); cur = one.root; sp = 0; top = SE::make(kTraversalDone, 0.0f);
+              }
+              else q.finish(sc, idx);
+            }
+            else {
+              if (finite) { r.set(wo, wd); cur = 0; sp = 0; top = SE::make(kTraversalDone, 0.0f); inst = kNoInstance; }
+              else q.finish(sc, idx);
+            }
           }
         }
         chunk_next += min(want, avail);
@@ -396,12 +452,14 @@ LUM_DEV void trace_items(const DeviceScene& sc, uint32_t n, uint32_t* __restrict
     while (true) {
       const bool live = cur != kTraversalDone;
       const bool at_leaf = live && (cur & kBvhLeafBit);
-      const bool want_tris = at_leaf && inst != kNoInstance, want_enter = at_leaf && inst == kNoInstance;
-      const uint32_t n_live = (uint32_t) __popcll(__ballot(live)), n_tris = (uint32_t) __popcll(__ballot(want_tris)), n_enter = (uint32_t) __popcll(__ballot(want_enter));
+      // (single level: a leaf is a triangle leaf, nobody enters anything - two phases, two ballots)
+      const bool want_tris = at_leaf && (kSingleLevel || inst != kNoInstance), want_enter = !kSingleLevel && at_leaf && inst == kNoInstance;
+      const uint32_t n_live = (uint32_t) __popcll(__ballot(live)), n_tris = (uint32_t) __popcll(__ballot(want_tris)),
+                     n_enter = kSingleLevel ? 0u : (uint32_t) __popcll(__ballot(want_enter));
       if (n_live == 0u) break;
       const uint32_t n_nodes = n_live - n_tris - n_enter;
       const bool run_tris = n_tris * LUM_VOTE_TRIS >= max(n_nodes, n_enter) * LUM_VOTE_NODES;
-      const bool run_enter = !run_tris && n_enter >= n_nodes;
+      const bool run_enter = !kSingleLevel && !run_tris && n_enter >= n_nodes;
       // Three per-lane conditions of which the vote leaves at most one non-empty. Written as independent divergent ifs on purpose: with
       // wave-uniform if/else-if branches the compiler routed every ray register through a temporary and back at the merge point
       // (about forty v_mov per iteration).
@@ -413,12 +471,12 @@ LUM_DEV void trace_items(const DeviceScene& sc, uint32_t n, uint32_t* __restrict
       {
         if (do_tris) {
           LUM_PHASE(3); LUM_PHASE_LANES(4);
-          if (q.on_tris(sc, inst, cur & 0x0FFFFFFFu, ((cur >> 28) & 0x7u) + 1u, r.o, r.d, tmax, st)) cur = kTraversalDone;
+          if (q.on_tris(sc, instance_of(one, inst), cur & 0x0FFFFFFFu, ((cur >> 28) & 0x7u) + 1u, r.o, r.d, tmax, st)) cur = kTraversalDone;
           else pop();
           if (cur == kTraversalDone) q.finish(sc, idx);
         }
       }
-      {
+      if constexpr (!kSingleLevel) {
         if (do_enter) {
           LUM_PHASE(1); LUM_PHASE_LANES(2);
           const uint32_t leaf_index = cur & 0x0FFFFFFFu;

@@ -36,8 +36,13 @@ struct ShadowQuery : ShadowState {
   }
 };
 
+// Two forms (trace_items, dev_trace.h): the plain kernel walks both levels, the template's one instance <true> a scene of one hittable instance from its mesh
+// root; the launcher picks one per launch. Both live in the defining unit, under its scheduler option.
+template <bool kSingleLevel>
+__global__ LUM_TRACE_BOUNDS void k_shadow_rays(DeviceScene sc, ShadowQueue sq, const uint32_t* order, uint32_t* ctrl, uint64_t* counters, uint32_t lds_nodes);
 #if LUM_SHADOW_KERNEL_EXTERN
 __global__ LUM_TRACE_BOUNDS void k_shadow_rays(DeviceScene sc, ShadowQueue sq, const uint32_t* order, uint32_t* ctrl, uint64_t* counters, uint32_t lds_nodes);
+extern template __global__ void k_shadow_rays<true>(DeviceScene sc, ShadowQueue sq, const uint32_t* order, uint32_t* ctrl, uint64_t* counters, uint32_t lds_nodes);
 #else
 __global__ LUM_TRACE_BOUNDS void k_shadow_rays(DeviceScene sc, ShadowQueue sq, const uint32_t* order, uint32_t* ctrl, uint64_t* counters, uint32_t lds_nodes) {
   RayStats st{0, 0, 0};
@@ -48,6 +53,18 @@ __global__ LUM_TRACE_BOUNDS void k_shadow_rays(DeviceScene sc, ShadowQueue sq, c
   trace_items(sc, ctrl[kCtlShadowItems], ctrl + kCtlShadowCursor, q, st, rays, lds_nodes);
   flush_stats(counters, st, rays, kCntShadow, kCntNodesShadow, kCntTrisShadow, kCntNodesLdsShadow);
 }
+template <bool kSingleLevel>
+__global__ LUM_TRACE_BOUNDS void k_shadow_rays(DeviceScene sc, ShadowQueue sq, const uint32_t* order, uint32_t* ctrl, uint64_t* counters, uint32_t lds_nodes) {
+  static_assert(kSingleLevel, "the two-level form is the plain kernel of this name");
+  RayStats st{0, 0, 0};
+  uint32_t rays = 0;
+  ShadowQuery q;
+  q.sq = sq;
+  q.order = order;
+  trace_items<ShadowQuery, true>(sc, ctrl[kCtlShadowItems], ctrl + kCtlShadowCursor, q, st, rays, lds_nodes);
+  flush_stats(counters, st, rays, kCntShadow, kCntNodesShadow, kCntTrisShadow, kCntNodesLdsShadow);
+}
+template __global__ void k_shadow_rays<true>(DeviceScene sc, ShadowQueue sq, const uint32_t* order, uint32_t* ctrl, uint64_t* counters, uint32_t lds_nodes);
 #endif
 
 LUM_NS_END

@@ -252,6 +252,20 @@ __global__ LUM_TRACE_BOUNDS void k_trace(DeviceScene sc, PathQueue q, const uint
   trace_items(sc, ctrl[kCtlPaths], ctrl + kCtlTraceCursor, tq, st, rays, lds_nodes);
   flush_stats(counters, st, rays, kCntTrace, kCntNodes, kCntTris, kCntNodesLds);
 }
+// The same pass over a scene of one hittable instance (trace_items<Q, true>, dev_trace.h); the launcher picks one of the two per launch. The two-level
+// kernel keeps its plain name: the single-level one is the only instance of a template of that name, so that whatever matches kernels by name finds both.
+template <bool kSingleLevel>
+__global__ LUM_TRACE_BOUNDS void k_trace(DeviceScene sc, PathQueue q, const uint32_t* order, uint32_t* ctrl, uint64_t* counters, uint32_t lds_nodes) {
+  static_assert(kSingleLevel, "the two-level form is the plain kernel of this name");
+  RayStats st{0, 0, 0};
+  uint32_t rays = 0;
+  TraceQuery tq;
+  tq.q = q;
+  tq.order = order;
+  tq.item = 0;
+  trace_items<TraceQuery, true>(sc, ctrl[kCtlPaths], ctrl + kCtlTraceCursor, tq, st, rays, lds_nodes);
+  flush_stats(counters, st, rays, kCntTrace, kCntNodes, kCntTris, kCntNodesLds);
+}
 
 // ---- surface context (cuda/geometry_utils.cuh:13-221, untextured) ----
 LUM_DEV GeoContext build_context(const DeviceScene& sc, V3 hit_origin, V3 ray_world, uint32_t state, uint32_t inst, uint32_t tri, uint32_t tbase, uint32_t medium) {
@@ -1979,6 +1993,18 @@ __global__ LUM_TRACE_BOUNDS void k_trace_rays(DeviceScene sc, uint32_t n, const 
   RaysQuery q;
   q.origins = origins; q.dirs = dirs; q.ignore = ignore; q.out = out;
   trace_items(sc, n, cursor, q, st, rays, lds_nodes);
+  flush_stats(counters, st, rays, kCntTrace, kCntNodes, kCntTris, kCntNodesLds);
+}
+// ... and its single-level form, selected as k_trace's is: the truth tests cover what the renderer runs
+template <bool kSingleLevel>
+__global__ LUM_TRACE_BOUNDS void k_trace_rays(DeviceScene sc, uint32_t n, const float* origins, const float* dirs, const uint32_t* ignore,
+                                                           uint32_t* out, uint32_t* cursor, uint64_t* counters, uint32_t lds_nodes) {
+  static_assert(kSingleLevel, "the two-level form is the plain kernel of this name");
+  RayStats st{0, 0, 0};
+  uint32_t rays = 0;
+  RaysQuery q;
+  q.origins = origins; q.dirs = dirs; q.ignore = ignore; q.out = out;
+  trace_items<RaysQuery, true>(sc, n, cursor, q, st, rays, lds_nodes);
   flush_stats(counters, st, rays, kCntTrace, kCntNodes, kCntTris, kCntNodesLds);
 }
 

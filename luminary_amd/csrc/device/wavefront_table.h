@@ -10,6 +10,11 @@
 
 namespace lum {
 
+// The ray kernels have a single-level form for a scene of one hittable instance (trace_items, dev_trace.h): its top level is node 0 with one child and two leaf
+// records, the instance's and the padding record. The launchers of trace, shadow_rays and trace_rays ask this at EVERY launch, so a scene update that adds or
+// removes instances needs no invalidation; `single_level` in their signatures is the context's switch (lumc_set_single_level), never the decision itself.
+inline bool single_level_scene(const DeviceScene& sc) { return sc.tlas_num_nodes == 1u && sc.tlas_num_leaves == 2u; }
+
 struct WavefrontKernels {
   const char* flavour;
   uint32_t trace_block;  // threads per workgroup of the persistent ray kernels (one workgroup per CU)
@@ -25,7 +30,7 @@ struct WavefrontKernels {
   void (*generate_adaptive)(uint32_t grid, hipStream_t s, const DeviceScene& sc, const AdaptiveView& a, const AdaptivePass& pass, const PathQueue& q, float4* results,
                             uint32_t* count, const DeviceLens& lens, int cam);
   void (*trace)(uint32_t grid, size_t lds, hipStream_t s, const DeviceScene& sc, const PathQueue& q, const uint32_t* order, uint32_t* ctrl, uint64_t* counters,
-                uint32_t lds_nodes);
+                uint32_t lds_nodes, bool single_level);
   void (*sky_inscattering)(uint32_t grid, hipStream_t s, const DeviceScene& sc, const PathQueue& in, float4* results, const uint32_t* ctrl, uint32_t depth_const);
   void (*shade)(uint32_t grid, hipStream_t s, const DeviceScene& sc, const PathQueue& in, const PathQueue& out, const NeeQueue& nee, const ShadowQueue& sq, float4* results,
                 uint32_t* ctrl, uint32_t depth_const, uint64_t* counters, uint32_t ambient_reuse, const FusedResolve* fused_dev, uint32_t fused_flags);  // fused_dev: device memory; flags: 1 resolve the entries' parents, 2 announce the survivors' entries
@@ -34,7 +39,7 @@ struct WavefrontKernels {
   void (*light_query)(uint32_t grid, hipStream_t s, const DeviceScene& sc, const PathQueue& in, const NeeQueue& nee, const ShadowQueue& sq, uint32_t* ctrl, uint32_t depth_const,
                       uint64_t* counters);
   void (*shadow_rays)(uint32_t grid, size_t lds, hipStream_t s, const DeviceScene& sc, const ShadowQueue& sq, const uint32_t* order, uint32_t* ctrl, uint64_t* counters,
-                      uint32_t lds_nodes);
+                      uint32_t lds_nodes, bool single_level);
   void (*resolve)(uint32_t grid, hipStream_t s, const DeviceScene& sc, const PathQueue& in, const NeeQueue& nee, const ShadowQueue& sq, float4* results, const uint32_t* ctrl);
   // ambient-visibility reuse (kernels.h, above TraceQuery): the resolve of a depth after the NEXT depth's closest-hit pass over `next`, and of the vertices it listed
   void (*resolve_reuse)(uint32_t grid, hipStream_t s, const DeviceScene& sc, const PathQueue& in, const PathQueue& next, const NeeQueue& nee, const ShadowQueue& sq, float4* results,
@@ -65,7 +70,7 @@ struct WavefrontKernels {
   void (*clouds_march)(uint32_t grid, hipStream_t s, const DeviceScene& sc, const PathQueue& in, const CloudQueue& cq, uint32_t* ctrl, uint32_t depth_const);
   void (*clouds)(uint32_t grid, hipStream_t s, const DeviceScene& sc, const PathQueue& in, const CloudQueue& cq, float4* results, const uint32_t* ctrl, uint32_t depth_const);
   void (*trace_rays)(uint32_t grid, size_t lds, hipStream_t s, const DeviceScene& sc, uint32_t n, const float* origins, const float* dirs, const uint32_t* ignore, uint32_t* out,
-                     uint32_t* cursor, uint64_t* counters, uint32_t lds_nodes);
+                     uint32_t* cursor, uint64_t* counters, uint32_t lds_nodes, bool single_level);
   // every camera ray of `samples` sample ids of n pixels (device buffers; origin / dir float3, weight float), the invalid ones included (k_camera_rays)
   void (*camera_rays)(uint32_t grid, hipStream_t s, const DeviceScene& sc, const DeviceLens& lens, int cam, const uint32_t* pixels, uint32_t n, uint32_t first_sample,
                       uint32_t samples, float* origin, float* dir, float* weight);

@@ -8,10 +8,21 @@
 LUM_NS_BEGIN
 namespace table {
 
+// The ray kernels by form: the plain kernel walks both levels, the template's instance <true> of the same name is the single-level form (kernels.h, kernel_shadow.h).
+typedef void (*TraceKernel)(DeviceScene, PathQueue, const uint32_t*, uint32_t*, uint64_t*, uint32_t);
+typedef void (*ShadowKernel)(DeviceScene, ShadowQueue, const uint32_t*, uint32_t*, uint64_t*, uint32_t);
+typedef void (*TraceRaysKernel)(DeviceScene, uint32_t, const float*, const float*, const uint32_t*, uint32_t*, uint32_t*, uint64_t*, uint32_t);
+static TraceKernel trace_kernel(bool single) { return single ? k_trace<true> : static_cast<TraceKernel>(k_trace); }
+static ShadowKernel shadow_kernel(bool single) { return single ? k_shadow_rays<true> : static_cast<ShadowKernel>(k_shadow_rays); }
+static TraceRaysKernel trace_rays_kernel(bool single) { return single ? k_trace_rays<true> : static_cast<TraceRaysKernel>(k_trace_rays); }
+
 static int set_ray_kernel_lds(size_t bytes) {
-  hipError_t e = hipFuncSetAttribute((const void*) k_trace, hipFuncAttributeMaxDynamicSharedMemorySize, (int) bytes);
-  if (e == hipSuccess) e = hipFuncSetAttribute((const void*) k_shadow_rays, hipFuncAttributeMaxDynamicSharedMemorySize, (int) bytes);
-  if (e == hipSuccess) e = hipFuncSetAttribute((const void*) k_trace_rays, hipFuncAttributeMaxDynamicSharedMemorySize, (int) bytes);
+  hipError_t e = hipSuccess;
+  for (int single = 0; single < 2 && e == hipSuccess; single++) {
+    e = hipFuncSetAttribute((const void*) trace_kernel(single != 0), hipFuncAttributeMaxDynamicSharedMemorySize, (int) bytes);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*) shadow_kernel(single != 0), hipFuncAttributeMaxDynamicSharedMemorySize, (int) bytes);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*) trace_rays_kernel(single != 0), hipFuncAttributeMaxDynamicSharedMemorySize, (int) bytes);
+  }
   if (e == hipSuccess) e = hipFuncSetAttribute((const void*) k_trace_particles, hipFuncAttributeMaxDynamicSharedMemorySize, (int) bytes);
   return (int) e;
 }
@@ -36,8 +47,8 @@ static void camera_rays(uint32_t grid, hipStream_t s, const DeviceScene& sc, con
   hipLaunchKernelGGL(k, dim3(grid), dim3(kBlock), 0, s, sc, lens, pixels, n, first_sample, samples, origin, dir, weight);
 }
 static void trace(uint32_t grid, size_t lds, hipStream_t s, const DeviceScene& sc, const PathQueue& q, const uint32_t* order, uint32_t* ctrl, uint64_t* counters,
-                  uint32_t lds_nodes) {
-  hipLaunchKernelGGL(k_trace, dim3(grid), dim3(kTraceBlock), lds, s, sc, q, order, ctrl, counters, lds_nodes);
+                  uint32_t lds_nodes, bool single_level) {
+  hipLaunchKernelGGL(trace_kernel(single_level && single_level_scene(sc)), dim3(grid), dim3(kTraceBlock), lds, s, sc, q, order, ctrl, counters, lds_nodes);
 }
 static void sky_inscattering(uint32_t grid, hipStream_t s, const DeviceScene& sc, const PathQueue& in, float4* results, const uint32_t* ctrl, uint32_t depth_const) {
   hipLaunchKernelGGL(k_sky_inscattering, dim3(grid), dim3(kBlock), 0, s, sc, in, results, ctrl, depth_const);
@@ -63,8 +74,8 @@ static void light_query(uint32_t grid, hipStream_t s, const DeviceScene& sc, con
   hipLaunchKernelGGL(k_light_query, dim3(grid), dim3(kBlock), 0, s, sc, in, nee, sq, ctrl, depth_const, counters);
 }
 static void shadow_rays(uint32_t grid, size_t lds, hipStream_t s, const DeviceScene& sc, const ShadowQueue& sq, const uint32_t* order, uint32_t* ctrl, uint64_t* counters,
-                        uint32_t lds_nodes) {
-  hipLaunchKernelGGL(k_shadow_rays, dim3(grid), dim3(kTraceBlock), lds, s, sc, sq, order, ctrl, counters, lds_nodes);
+                        uint32_t lds_nodes, bool single_level) {
+  hipLaunchKernelGGL(shadow_kernel(single_level && single_level_scene(sc)), dim3(grid), dim3(kTraceBlock), lds, s, sc, sq, order, ctrl, counters, lds_nodes);
 }
 static void resolve(uint32_t grid, hipStream_t s, const DeviceScene& sc, const PathQueue& in, const NeeQueue& nee, const ShadowQueue& sq, float4* results, const uint32_t* ctrl) {
   hipLaunchKernelGGL(k_resolve, dim3(grid), dim3(kBlock), 0, s, sc, in, nee, sq, results, ctrl);
@@ -120,8 +131,9 @@ static void clouds(uint32_t grid, hipStream_t s, const DeviceScene& sc, const Pa
   hipLaunchKernelGGL(k_clouds, dim3(grid), dim3(kBlock), 0, s, sc, in, cq, results, ctrl, depth_const);
 }
 static void trace_rays(uint32_t grid, size_t lds, hipStream_t s, const DeviceScene& sc, uint32_t n, const float* origins, const float* dirs, const uint32_t* ignore, uint32_t* out,
-                       uint32_t* cursor, uint64_t* counters, uint32_t lds_nodes) {
-  hipLaunchKernelGGL(k_trace_rays, dim3(grid), dim3(kTraceBlock), lds, s, sc, n, origins, dirs, ignore, out, cursor, counters, lds_nodes);
+                       uint32_t* cursor, uint64_t* counters, uint32_t lds_nodes, bool single_level) {
+  hipLaunchKernelGGL(trace_rays_kernel(single_level && single_level_scene(sc)), dim3(grid), dim3(kTraceBlock), lds, s, sc, n, origins, dirs, ignore, out, cursor, counters,
+                     lds_nodes);
 }
 static void guide(uint32_t grid, hipStream_t s, const DeviceScene& sc, const PathQueue& in, const uint32_t* ctrl, float* planes, uint32_t n) {
   hipLaunchKernelGGL(k_guide, dim3(grid), dim3(kBlock), 0, s, sc, in, ctrl, planes, n);

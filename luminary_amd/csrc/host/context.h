@@ -73,6 +73,8 @@ struct LumContext {
   bool has_scene = false;
   uint64_t bvh_stats[4] = {0, 0, 0, 0};
   int ambient_reuse = -1;         // -1 by flavour (fast: on), 0 off, 1 on (lumc_set_ambient_reuse; LUM_AMBIENT_REUSE)
+  int single_level = -1;          // the ray kernels' single-level form on a scene of one hittable instance: -1 auto (on), 0 never, 1 when eligible (lumc_set_single_level; LUM_SINGLE_LEVEL)
+  bool first_leaf_identity = false;  // leaf record 0 of the top level maps a ray onto itself (update_scene_tree): see single_level_allowed
   uint32_t shade_grid_rounds = 2;  // k_shade's grid as a multiple of its resident set (0: the common 2048-workgroup cap); LUM_SHADE_GRID
   int fused_resolve = 1;          // with the fast flavour's ambient reuse: k_shade resolves the previous depth's vertices itself (lumc_set_fused_resolve; LUM_FUSED_RESOLVE)
   struct Fused : FusedBuffers {   // what that needs beyond the usual work buffers (work_layout.h lay_out_fused)
@@ -184,6 +186,15 @@ constexpr uint32_t kLaunchBlock = 256;  // dev_wave.h's kBlock (core.hip asserts
 inline uint32_t grid_for(uint32_t n) {
   const uint32_t blocks = (n + kLaunchBlock - 1) / kLaunchBlock;
   return blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks);  // 256 CUs x 8 resident blocks, grid-stride beyond that
+}
+
+// What the launchers of the ray kernels are told besides the scene (single_level_scene, wavefront_table.h): the switch, and in the fast flavour that the one
+// instance's world->object map is the identity. The single-level form maps a ray with the expressions of the instance-entry phase, but under the fast flavour's
+// -ffp-contract=fast the compiler decides per place which product of a row goes into which fma (it differs between the rows of ONE kernel), so another
+// instantiation rounds another way. With rows of 1 and 0 and no translation every product and sum is exact in any arrangement: the outputs keep their bits.
+// The exact flavour compiles without contraction and takes every transform.
+inline bool single_level_allowed(const LumContext* ctx) {
+  return ctx->single_level != 0 && (ctx->wf != wavefront_kernels_fast() || ctx->first_leaf_identity);
 }
 
 // Persistent ray kernels: one workgroup per CU (kTraceBlock threads, its own LDS copy of the tree top); waves pull work from a cursor.

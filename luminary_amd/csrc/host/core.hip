@@ -129,6 +129,7 @@ int lumc_context_create(int device_ordinal, LumContext** out) {
   if (const char* e = getenv("LUM_SYNC_DEBUG")) ctx->sync_debug = atoi(e) != 0;
   if (const char* e = getenv("LUM_SORT_KEY")) ctx->sort.key = atoi(e);
   if (const char* e = getenv("LUM_AMBIENT_REUSE")) ctx->ambient_reuse = atoi(e) != 0 ? 1 : 0;
+  if (const char* e = getenv("LUM_SINGLE_LEVEL")) ctx->single_level = atoi(e) != 0 ? 1 : 0;
   if (const char* e = getenv("LUM_FUSED_RESOLVE")) ctx->fused_resolve = atoi(e) != 0 ? 1 : 0;
   if (const char* e = getenv("LUM_SHADE_GRID")) ctx->shade_grid_rounds = (uint32_t) atoi(e);
   if (const char* e = getenv("LUM_SOBOL_TABLE_RT")) ctx->sobol_table = atoi(e) != 0 ? 1 : 0;
@@ -234,7 +235,7 @@ static void first_hits(LumContext* ctx, hipStream_t stream, const DeviceScene& s
   const WavefrontKernels& wf = *ctx->wf;
   {
     Launch l(ctx, stream, LUMC_KERNEL_TRACE);
-    wf.trace(grid_persistent(ctx, N), ray_kernel_lds(ctx), stream, sc, ctx->work.queue[0], nullptr, ctx->d_ctrl.get(), ctx->d_counters.get(), ctx->lds_nodes);
+    wf.trace(grid_persistent(ctx, N), ray_kernel_lds(ctx), stream, sc, ctx->work.queue[0], nullptr, ctx->d_ctrl.get(), ctx->d_counters.get(), ctx->lds_nodes, single_level_allowed(ctx));
   }
   if (sc.particles_active) trace_particles(ctx, stream, ctx->work.queue[0], ctx->d_ctrl.get(), N);
   if (sc.ocean_active) {
@@ -304,7 +305,7 @@ static int closest_hits(LumContext* ctx, hipStream_t stream, const DeviceScene& 
   if (ctx->sort.mode >= 1 && d.depth >= 1 && sort_closest_rays(ctx, stream, d.cur, d.ctrl, N, &order)) return 1;
   {
     Launch l(ctx, stream, LUMC_KERNEL_TRACE);
-    wf.trace(grid_persistent(ctx, N), ray_kernel_lds(ctx), stream, sc, d.cur, order, d.ctrl, ctx->d_counters.get(), ctx->lds_nodes);
+    wf.trace(grid_persistent(ctx, N), ray_kernel_lds(ctx), stream, sc, d.cur, order, d.ctrl, ctx->d_counters.get(), ctx->lds_nodes, single_level_allowed(ctx));
   }
   if (scheme == kResolveReuse && d.depth > 0) {  // the previous depth's resolve: ambient samples answered by the pass above; what it cannot answer is traced (the control words of the fog's visibility pass: no fog here) and resolved after
     uint32_t* prev = d.ctrl - kCtlStride;
@@ -314,7 +315,7 @@ static int closest_hits(LumContext* ctx, hipStream_t stream, const DeviceScene& 
     }
     {
       Launch l(ctx, stream, LUMC_KERNEL_SHADOW);
-      wf.shadow_rays(ctx->trace_blocks, ray_kernel_lds(ctx), stream, sc, ctx->work.shadow, nullptr, prev + kCtlVolumeShift, ctx->d_counters.get(), ctx->lds_nodes);
+      wf.shadow_rays(ctx->trace_blocks, ray_kernel_lds(ctx), stream, sc, ctx->work.shadow, nullptr, prev + kCtlVolumeShift, ctx->d_counters.get(), ctx->lds_nodes, single_level_allowed(ctx));
     }
     Launch l(ctx, stream, LUMC_KERNEL_RESOLVE);
     wf.resolve_listed(std::min<uint32_t>(grid_for(N), 1024u), stream, sc, d.prev, d.nee, ctx->work.shadow, ctx->work.results, (const uint32_t*) prev);
@@ -337,7 +338,7 @@ static void media_passes(LumContext* ctx, hipStream_t stream, const DeviceScene&
     }
     {
       Launch l(ctx, stream, LUMC_KERNEL_SHADOW);
-      wf.shadow_rays(grid_persistent(ctx, N), ray_kernel_lds(ctx), stream, sc, ctx->work.shadow, nullptr, d.ctrl + kCtlVolumeShift, ctx->d_counters.get(), ctx->lds_nodes);
+      wf.shadow_rays(grid_persistent(ctx, N), ray_kernel_lds(ctx), stream, sc, ctx->work.shadow, nullptr, d.ctrl + kCtlVolumeShift, ctx->d_counters.get(), ctx->lds_nodes, single_level_allowed(ctx));
     }
     Launch l(ctx, stream, LUMC_KERNEL_VOLUME);
     wf.volume_resolve(grid_for(N), stream, sc, d.cur, ctx->work.volume, ctx->work.shadow, ctx->work.results, (const uint32_t*) d.ctrl);
@@ -368,7 +369,7 @@ static void shade_depth(LumContext* ctx, hipStream_t stream, const DeviceScene& 
   if (fused && d.depth > 0) {  // the samples of depth - 1 their paths' closest hits could not decide: traced now, their vertices resolved (before this depth's visibility pass reuses the words)
     {
       Launch l(ctx, stream, LUMC_KERNEL_SHADOW);
-      wf.shadow_rays(ctx->trace_blocks, ray_kernel_lds(ctx), stream, sc, ctx->fused.fallback, nullptr, d.ctrl + kCtlVolumeShift, ctx->d_counters.get(), ctx->lds_nodes);
+      wf.shadow_rays(ctx->trace_blocks, ray_kernel_lds(ctx), stream, sc, ctx->fused.fallback, nullptr, d.ctrl + kCtlVolumeShift, ctx->d_counters.get(), ctx->lds_nodes, single_level_allowed(ctx));
     }
     Launch l(ctx, stream, LUMC_KERNEL_RESOLVE);
     wf.resolve_listed(std::min<uint32_t>(grid_for(N), 1024u), stream, sc, d.prev, d.nee_before, ctx->fused.fallback, ctx->work.results, (const uint32_t*) d.ctrl);
@@ -409,7 +410,7 @@ static int visibility_and_resolve(LumContext* ctx, hipStream_t stream, const Dev
   }
   {
     Launch l(ctx, stream, LUMC_KERNEL_SHADOW);
-    wf.shadow_rays(grid_persistent(ctx, N), ray_kernel_lds(ctx), stream, sc, ctx->work.shadow, shadow_order, d.ctrl, ctx->d_counters.get(), ctx->lds_nodes);
+    wf.shadow_rays(grid_persistent(ctx, N), ray_kernel_lds(ctx), stream, sc, ctx->work.shadow, shadow_order, d.ctrl, ctx->d_counters.get(), ctx->lds_nodes, single_level_allowed(ctx));
   }
   if (d.last || scheme == kResolvePlain) {
     Launch l(ctx, stream, LUMC_KERNEL_RESOLVE);
@@ -1136,7 +1137,7 @@ int lumc_trace_closest(LumContext* ctx, uint32_t n, const float* d_origins, cons
   HIP_TRY(ctx, hipMemsetAsync(cursor, 0, sizeof(uint32_t), stream));  // the work cursor of trace_items (dev_trace.h)
   Launch l(ctx, stream, LUMC_KERNEL_TRACE);
   ctx->wf->trace_rays(grid_persistent(ctx, n), ray_kernel_lds(ctx), stream, ctx->scene, n, d_origins, d_dirs, d_ignore, d_out, cursor, ctx->d_counters.get(),
-                      ctx->lds_nodes);
+                      ctx->lds_nodes, single_level_allowed(ctx));
   HIP_TRY(ctx, hipGetLastError());
   return 0;
 }
@@ -1179,7 +1180,7 @@ int lumc_trace_visibility(LumContext* ctx, uint32_t n, const float* d_origins, c
   hipLaunchKernelGGL(k_visibility_pack, dim3(blocks), dim3(256), 0, stream, n, d_origins, d_dirs, d_dist, d_ids, sq);
   {
     Launch l(ctx, stream, LUMC_KERNEL_SHADOW);
-    ctx->wf->shadow_rays(grid_persistent(ctx, n), ray_kernel_lds(ctx), stream, ctx->scene, sq, d_order, ctrl, ctx->d_counters.get(), ctx->lds_nodes);
+    ctx->wf->shadow_rays(grid_persistent(ctx, n), ray_kernel_lds(ctx), stream, ctx->scene, sq, d_order, ctrl, ctx->d_counters.get(), ctx->lds_nodes, single_level_allowed(ctx));
   }
   hipLaunchKernelGGL(k_visibility_unpack, dim3(blocks), dim3(256), 0, stream, n, sq.vis, d_out);
   HIP_TRY(ctx, hipGetLastError());
@@ -1339,6 +1340,14 @@ int lumc_set_ambient_reuse(LumContext* ctx, int mode) {
   return 0;
 }
 int lumc_get_ambient_reuse(const LumContext* ctx) { return (ctx && ambient_reuse_active(ctx)) ? 1 : 0; }
+
+int lumc_set_single_level(LumContext* ctx, int mode) {
+  if (!ctx || mode < -1 || mode > 1) { if (ctx) ctx->error = "lumc_set_single_level: -1 (auto), 0 (never) or 1 (when the scene is eligible)"; return 1; }
+  ctx->single_level = mode;
+  return 0;
+}
+// what the launchers will decide for the uploaded scene's surfaces (the particle pass has no single-level form)
+int lumc_get_single_level(const LumContext* ctx) { return (ctx && ctx->has_scene && single_level_allowed(ctx) && single_level_scene(ctx->scene)) ? 1 : 0; }
 int lumc_get_flavour(const LumContext* ctx) { return (ctx && ctx->wf == wavefront_kernels_exact()) ? LUMC_FLAVOUR_EXACT : LUMC_FLAVOUR_FAST; }
 
 unsigned int lumc_lds_stack_bytes(void) { return LUM_LDS_STACK_BYTES; }

@@ -476,6 +476,15 @@ static int update_scene_tree(LumContext* ctx, const LumDeviceSceneView* v, bool 
   if (upload(ctx, ctx->arrays.inst.tlas_leaves, tree.tlas_leaves.data(), tree.tlas_leaves.size(), &sc.tlas_leaves)) return 1;
   sc.tlas_num_nodes = tree.tlas_num_nodes;
   sc.tlas_num_leaves = (uint32_t) (tree.tlas_leaves.size() / 4);  // records that exist (one of padding included): what a workgroup may stage in LDS
+  {  // does leaf record 0 map a ray onto itself (rows of 1 and +-0, no translation)? What the fast flavour's single-level form asks for (context.h single_level_allowed)
+    bool identity = tree.tlas_leaves.size() >= 4;
+    for (int k = 0; k < 3 && identity; k++) {
+      const float4 r = tree.tlas_leaves[k];
+      const float row[4] = {r.x, r.y, r.z, r.w};
+      for (int c = 0; c < 4; c++) identity = identity && row[c] == (c == k ? 1.0f : 0.0f);
+    }
+    ctx->first_leaf_identity = identity;
+  }
   std::memcpy(ctx->sort.world_lo, tree.world.lo, sizeof(ctx->sort.world_lo)); std::memcpy(ctx->sort.world_hi, tree.world.hi, sizeof(ctx->sort.world_hi));
   ctx->bvh_stats[0] = tree.nodes.size() - tree.tlas_num_nodes;
   ctx->bvh_stats[2] = tree.tlas_num_nodes;
@@ -593,6 +602,7 @@ static int update_instance_transforms(LumContext* ctx, const LumDeviceSceneView*
   u.tlas_nodes = num_nodes;
   sc.tlas_num_nodes = num_nodes;
   sc.tlas_num_leaves = hittable + 1u;  // (one of padding)
+  ctx->first_leaf_identity = false;    // (two instances or more: never asked)
   std::memcpy(ctx->sort.world_lo, world.lo, sizeof(ctx->sort.world_lo)); std::memcpy(ctx->sort.world_hi, world.hi, sizeof(ctx->sort.world_hi));
   ctx->bvh_stats[0] = u.mesh_nodes;
   ctx->bvh_stats[2] = num_nodes;

@@ -428,6 +428,31 @@ typedef struct LuminaryResidentRefitStats {
   double seconds_upload, seconds_hash, seconds_refit, seconds_cost, seconds_top_level; /* as LumResidentRefitStats (include/lum_core.h) */
 } LuminaryResidentRefitStats;
 LUMINARY_API LuminaryResult luminary_ext_get_resident_refit_stats(LuminaryHost* host, LuminaryResidentRefitStats* out);
+/* Skinned meshes: the host takes bones, the devices pose the vertices (include/lum_core.h lumc_mesh_skin_bind).
+ *   luminary_ext_bind_mesh_skin    binds a mesh the host holds to four bone ids and four weights per corner (12 of each per triangle, corner-major; a slot of weight 0
+ *                                  is skipped) over bone_count (1 ... 1024) bones. The rest pose is the host mesh as it is now, copied. While a mesh is bound,
+ *                                  luminary_ext_set_mesh_positions on it is refused. Binding again replaces (the rest pose is then the current pose).
+ *   luminary_ext_set_mesh_pose     12 floats per bone, row-major 3 x 4, all finite; bone_count the binding's. Restarts the integration. The devices get 48 bytes per
+ *                                  bone and write the mesh's vertices themselves: linear blend skinning in binary32, normals through the bones' 3 x 3 part as it is
+ *                                  (right for rotations and uniform scale only), normalised. A mesh with an emissive triangle is also posed on the host at once and
+ *                                  the light tree rebuilt; for any other mesh the host mesh is brought up to date - by the same function on the CPU, the same
+ *                                  bytes - only when something reads it: luminary_ext_get_mesh, luminary_ext_build_device_scene, a change of the mesh list,
+ *                                  a light tree build, the unbind. A pose whose result is not finite fails the next render (LUMINARY_ERROR_CUDA).
+ *   luminary_ext_unbind_mesh_skin  the host mesh becomes the current pose, and plain again.
+ * LUMINARY_ERROR_INVALID_API_ARGUMENT, and nothing changes: a mesh id the host does not have, another triangle count, NULL arrays, a weight that is negative or not
+ * finite, an id >= bone_count, bone_count 0 or above 1024, a pose or an unbind for a mesh that is not bound, another bone_count, a matrix entry that is not finite. */
+LUMINARY_API LuminaryResult luminary_ext_bind_mesh_skin(LuminaryHost* host, uint32_t mesh_id, const uint16_t* bone_ids, const float* weights, uint32_t triangle_count,
+                                                        uint32_t bone_count);
+LUMINARY_API LuminaryResult luminary_ext_unbind_mesh_skin(LuminaryHost* host, uint32_t mesh_id);
+LUMINARY_API LuminaryResult luminary_ext_set_mesh_pose(LuminaryHost* host, uint32_t mesh_id, const float* bones, uint32_t bone_count);
+typedef struct LuminaryMeshSkinStats {
+  uint64_t poses, rebuild_downloads;    /* poses the main device's context applied / posed meshes it downloaded for a rebuild, since it was created */
+  uint32_t last_meshes, last_launches;  /* its last update that skinned: meshes with a new pose, skinning kernels launched */
+  uint64_t last_bytes_uploaded;         /* ... bytes that went up for them */
+  double seconds, seconds_upload, seconds_skin; /* as LumMeshSkinStats (include/lum_core.h) */
+  uint64_t host_materialisations;       /* times the host posed a mesh on the CPU because something read it, since the host was created */
+} LuminaryMeshSkinStats;
+LUMINARY_API LuminaryResult luminary_ext_get_mesh_skin_stats(LuminaryHost* host, LuminaryMeshSkinStats* out);
 /* Converts the current scene to the device format (device_structs.c conversions + light tree build). The view and everything it points
  * to stay valid until the next call or host destruction. Needs no GPU. */
 /* Whether replacing `old` by `input` restarts the integration (camera.c:80-147, settings.c:45-72) or only changes the outputs.

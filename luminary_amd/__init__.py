@@ -183,6 +183,12 @@ class ResidentRefitStats(C.Structure):
                 ("seconds_top_level", C.c_double)]
 
 
+class MeshSkinStats(C.Structure):
+    """LuminaryMeshSkinStats"""
+    _fields_ = [("poses", C.c_uint64), ("rebuild_downloads", C.c_uint64), ("last_meshes", C.c_uint32), ("last_launches", C.c_uint32), ("last_bytes_uploaded", C.c_uint64),
+                ("seconds", C.c_double), ("seconds_upload", C.c_double), ("seconds_skin", C.c_double), ("host_materialisations", C.c_uint64)]
+
+
 class Instance(C.Structure):
     _fields_ = [("id", C.c_uint32), ("mesh_id", C.c_uint32), ("position", Vec3), ("rotation", Vec3), ("scale", Vec3)]
 
@@ -556,6 +562,31 @@ class Host:
         """luminary_ext_get_resident_refit_stats of the main device: a dict of updates, fallbacks, the last update's meshes, launches, bytes downloaded and seconds."""
         s = ResidentRefitStats()
         _call("luminary_ext_get_resident_refit_stats", self._h, C.byref(s))
+        return {name: getattr(s, name) for name, _ in s._fields_}
+
+    def bind_mesh_skin(self, mesh_id, bone_ids, weights, bone_count):
+        """luminary_ext_bind_mesh_skin: bone ids and weights [n, 12] (four slots per corner) over bone_count bones; the rest pose is the host mesh as it is now."""
+        import numpy as np
+        ids = np.ascontiguousarray(bone_ids, dtype=np.uint16).reshape(-1)
+        w = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)
+        assert ids.size == w.size and ids.size % 12 == 0
+        _call("luminary_ext_bind_mesh_skin", self._h, C.c_uint32(mesh_id), ids.ctypes.data_as(C.c_void_p), w.ctypes.data_as(C.c_void_p), C.c_uint32(ids.size // 12), C.c_uint32(bone_count))
+
+    def unbind_mesh_skin(self, mesh_id):
+        """luminary_ext_unbind_mesh_skin: the host mesh becomes the current pose, and plain again."""
+        _call("luminary_ext_unbind_mesh_skin", self._h, C.c_uint32(mesh_id))
+
+    def set_mesh_pose(self, mesh_id, bones):
+        """luminary_ext_set_mesh_pose: bones [b, 12], row-major 3 x 4; the devices pose the bound mesh's vertices and refit its tree."""
+        import numpy as np
+        b = np.ascontiguousarray(bones, dtype=np.float32).reshape(-1)
+        assert b.size % 12 == 0
+        _call("luminary_ext_set_mesh_pose", self._h, C.c_uint32(mesh_id), b.ctypes.data_as(C.c_void_p), C.c_uint32(b.size // 12))
+
+    def mesh_skin_stats(self):
+        """luminary_ext_get_mesh_skin_stats: the main device's skinning stats and host_materialisations, as a dict."""
+        s = MeshSkinStats()
+        _call("luminary_ext_get_mesh_skin_stats", self._h, C.byref(s))
         return {name: getattr(s, name) for name, _ in s._fields_}
 
     def get_mesh(self, mesh_id):

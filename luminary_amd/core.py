@@ -8,6 +8,7 @@ from . import DeviceSceneView, _lib
 DIRTY_CONSTANTS, DIRTY_MATERIALS, DIRTY_INSTANCES, DIRTY_LIGHTS, DIRTY_MESHES, DIRTY_TEXTURES, DIRTY_PARTICLES, DIRTY_ALL = 1, 2, 4, 8, 16, 32, 64, 127
 DIRTY_MESH_POSITIONS = 128  # moved vertices: refit (not part of DIRTY_ALL, which builds)
 DIRTY_INSTANCE_TRANSFORMS = 256  # moved instances: the top level is rebuilt on the device, the mesh trees stay (not part of DIRTY_ALL)
+DIRTY_MESH_SKIN = 512  # bound meshes posed (Core.mesh_skin_pose): their vertices are written on the device, then they are refitted (not part of DIRTY_ALL)
 BVH_BUILDERS = {"sah": 0, "lbvh": 1, "ploc": 2, "sah_gpu": 3}
 CNT_TRACE, CNT_SHADOW, CNT_LIGHT_BVH, CNT_VERTICES, CNT_NODES, CNT_TRIS, CNT_NODES_SHADOW, CNT_TRIS_SHADOW, CNT_NODES_LIGHT, CNT_TRIS_LIGHT, CNT_NODES_LDS, CNT_NODES_LDS_SHADOW, CNT_AMBIENT_DEFERRED, CNT_AMBIENT_FALLBACK = range(14)
 CNT_COUNT = 16  # LUMC_CNT_COUNT
@@ -112,6 +113,35 @@ class ResidentRefitStats(C.Structure):
     _fields_ = [("updates", C.c_uint64), ("fallbacks", C.c_uint64), ("last_meshes", C.c_uint32), ("last_launches", C.c_uint32), ("last_bytes_downloaded", C.c_uint64),
                 ("seconds", C.c_double), ("seconds_upload", C.c_double), ("seconds_hash", C.c_double), ("seconds_refit", C.c_double), ("seconds_cost", C.c_double),
                 ("seconds_top_level", C.c_double)]
+
+
+class MeshSkinStats(C.Structure):
+    """LumMeshSkinStats"""
+    _fields_ = [("poses", C.c_uint64), ("rebuild_downloads", C.c_uint64), ("last_meshes", C.c_uint32), ("last_launches", C.c_uint32), ("last_bytes_uploaded", C.c_uint64),
+                ("seconds", C.c_double), ("seconds_upload", C.c_double), ("seconds_skin", C.c_double)]
+
+
+def _skin_arrays(rest_positions, rest_normals, bone_ids, weights):
+    p = np.ascontiguousarray(rest_positions, dtype=np.float32).reshape(-1, 9)
+    n = np.ascontiguousarray(rest_normals, dtype=np.float32).reshape(-1, 9)
+    i = np.ascontiguousarray(bone_ids, dtype=np.uint16).reshape(-1, 12)
+    w = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1, 12)
+    assert len(p) == len(n) == len(i) == len(w), "9 position floats, 9 normal floats, 12 ids and 12 weights per triangle"
+    return p, n, i, w
+
+
+def skin_host(rest_positions, rest_normals, bone_ids, weights, bones):
+    """lumc_skin_host, no device needed: the host twin of the skinning kernel over triangles of rest positions / normals [n, 9], bone ids / weights [n, 12] (four
+    slots per corner) and bones [b, 12] (row-major 3 x 4). Returns (positions [n, 9] float32, normals [n, 9] float32, packed normal words [n, 3] uint32)."""
+    fn = _lib().lumc_skin_host
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+    p, n, i, w = _skin_arrays(rest_positions, rest_normals, bone_ids, weights)
+    b = np.ascontiguousarray(bones, dtype=np.float32).reshape(-1, 12)
+    op, on, pk = np.zeros_like(p), np.zeros_like(n), np.zeros((len(p), 3), np.uint32)
+    if fn(p.ctypes.data, n.ctypes.data, i.ctypes.data, w.ctypes.data, len(p), b.ctypes.data, len(b), op.ctypes.data, on.ctypes.data, pk.ctypes.data) != 0:
+        raise CoreError("lumc_skin_host refused its arguments (bone count 1 ... 1024, ids below it)")
+    return op, on, pk
 
 
 def instance_boxes_probe(view, mesh_boxes, on_gpu=False):
@@ -574,6 +604,31 @@ class Core:
     def resident_refit_stats(self):
         out = ResidentRefitStats()
         self._call("lumc_resident_refit_stats", C.byref(out))
+        return out
+
+    def mesh_skin_bind(self, mesh, rest_positions, rest_normals, bone_ids, weights, bone_count):
+        """lumc_mesh_skin_bind: rest positions / normals [n, 9], bone ids / weights [n, 12] of a mesh of the scene on the device become resident."""
+        p, n, i, w = _skin_arrays(rest_positions, rest_normals, bone_ids, weights)
+        self._call("lumc_mesh_skin_bind", C.c_uint32(mesh), C.c_void_p(p.ctypes.data), C.c_void_p(n.ctypes.data), C.c_void_p(i.ctypes.data), C.c_void_p(w.ctypes.data),
+                   C.c_uint32(len(p)), C.c_uint32(bone_count))
+
+    def mesh_skin_unbind(self, mesh):
+        self._call("lumc_mesh_skin_unbind", C.c_uint32(mesh))
+
+    def mesh_skin_pose(self, mesh, bones):
+        """lumc_mesh_skin_pose: bones [b, 12]; pending until the next update with DIRTY_MESH_SKIN."""
+        b = np.ascontiguousarray(bones, dtype=np.float32).reshape(-1, 12)
+        self._call("lumc_mesh_skin_pose", C.c_uint32(mesh), C.c_void_p(b.ctypes.data), C.c_uint32(len(b)))
+
+    def mesh_skin_stats(self):
+        out = MeshSkinStats()
+        self._call("lumc_mesh_skin_stats", C.byref(out))
+        return out
+
+    def mesh_vertices_probe(self, mesh, triangles):
+        """lumc_mesh_vertices_probe: the mesh's [3 * triangles, 4] vertex records as uint32 words, from the device."""
+        out = np.zeros((3 * triangles, 4), np.uint32)
+        self._call("lumc_mesh_vertices_probe", C.c_uint32(mesh), C.c_void_p(out.ctypes.data))
         return out
 
     def resident_mesh_nodes_probe(self):

@@ -13,8 +13,10 @@
 #include <cfloat>
 #include <chrono>
 #include <condition_variable>
+#include <cstddef>
 #include <cstdio>
 #include <cstring>
+#include <map>
 #include <mutex>
 #include <thread>
 #include <type_traits>
@@ -23,8 +25,11 @@
 
 #include "../../../include/lum_core.h"
 #include "../../../include/luminary_amd.h"
+#include "bvh_build.h"  // host_parallel_for
 #include "loaders.h"
 #include "scene.h"
+#define LUM_SKIN_HOST_ONLY 1  // the host twin's declaration only: this unit touches no device
+#include "mesh_skin.h"
 
 extern "C" const unsigned char lum_embedded_bluenoise_2d[];
 extern "C" const unsigned char lum_embedded_bluenoise_2d_end[];
@@ -33,8 +38,24 @@ extern "C" const unsigned char lum_embedded_bluenoise_2d_end[];
 
 struct LuminaryPath { std::string value; };
 
+// A bound mesh (luminary_ext_bind_mesh_skin): the rest pose and the corners' bones, the last pose, and who holds it. The serials are values of the host's
+// skin_serial counter: a context that has seen the counter at a smaller value gets the binding / the pose before it takes the scene.
+struct HostSkin {
+  std::vector<float> rest_positions, rest_normals, weights;
+  std::vector<uint16_t> bone_ids;
+  uint32_t bone_count = 0;
+  std::vector<float> palette;     // the last pose, 12 floats per bone (empty: none yet)
+  uint64_t bind_serial = 0, pose_serial = 0;
+  bool host_current = true;       // HostMesh::positions / normals hold the last pose (false: brought up to date by the host twin before anything reads them)
+  bool view_current = true;       // ... and so do the device scene's vertices of the mesh (the contexts never read those of a posed mesh)
+};
+
 struct LuminaryHost {
   lum::HostScene scene;
+  std::map<uint32_t, HostSkin> skins;  // by mesh
+  uint64_t skin_serial = 0;            // counts binds and poses
+  uint64_t core_skin_seen = 0;         // the counter when the main context last took bindings and poses over
+  uint64_t host_materialisations = 0;
   lum::DeviceSceneBuffers device_scene;
   // Which parts of the scene edits have touched since the device scene / a device's copy of it was last brought up to date (LUMC_DIRTY_*; the
   // reference keeps such flags per entity, scene.h:42-63, and its device manager uploads by them, device_manager.c:311-320, :424-450): a camera
@@ -52,7 +73,7 @@ struct LuminaryHost {
   LumContext* core = nullptr;        // context of the main device: renders (its tiles) and produces every output
   int device_ordinal = 0;            // HIP ordinal of the main device
   // every visible device (device_manager.c:776-862 creates one Device per masked id); the frame is tiled over the enabled ones
-  struct DeviceSlot { int ordinal = 0; bool enabled = false; LumContext* core = nullptr; bool scene_valid = false; uint32_t dirty = LUMC_DIRTY_ALL; };
+  struct DeviceSlot { int ordinal = 0; bool enabled = false; LumContext* core = nullptr; bool scene_valid = false; uint32_t dirty = LUMC_DIRTY_ALL; uint64_t skin_seen = 0; };
   std::vector<DeviceSlot> devices;
   uint32_t main_slot = 0;
   uint32_t partition_n = 0;          // devices the current accumulation is tiled over (0 or 1: the main device renders every pixel)
@@ -164,8 +185,62 @@ template <typename T> bool change_restarts(const T&, const T&) { return true; } 
 inline bool change_restarts(const LuminaryCamera& in, const LuminaryCamera& old) { return camera_change_restarts(in, old); }
 inline bool change_restarts(const LuminaryRendererSettings& in, const LuminaryRendererSettings& old) { return settings_change_restarts(in, old); }
 
+// ---- skinned meshes: the lazy host mesh ----
+// HostMesh::positions / normals of a posed mesh from the host twin of the devices' kernel (in place: the pointers luminary_ext_get_mesh handed out stay valid).
+void materialise(LuminaryHost* h, uint32_t mesh) {
+  const auto it = h->skins.find(mesh);
+  if (it == h->skins.end() || it->second.host_current || mesh >= h->scene.meshes.size()) return;
+  HostSkin& k = it->second;
+  lum::HostMesh& m = h->scene.meshes[mesh];
+  lum::host_parallel_for(m.triangle_count(), [&](size_t b, size_t e) {  // (a corner's bytes do not depend on the chunks)
+    lum::skin_host(k.rest_positions.data() + 9 * b, k.rest_normals.data() + 9 * b, k.bone_ids.data() + 12 * b, k.weights.data() + 12 * b, (uint32_t) (e - b), k.palette.data(),
+                   k.bone_count, m.positions.data() + 9 * b, m.normals.data() + 9 * b, nullptr, nullptr);
+  });
+  k.host_current = true;
+  h->host_materialisations++;
+}
+bool mesh_emits(const LuminaryHost* h, uint32_t mesh) {
+  for (uint16_t id : h->scene.meshes[mesh].material_ids)
+    if (id < h->scene.materials.size() && h->scene.materials[id].emission_active) return true;
+  return false;
+}
+
+// Bindings and poses a context has not seen, before it takes the scene (lumc_scene_update with `dirty`); after an update that rebuilt the meshes - which drops the
+// context's bindings - all of them again, and the poses applied in a second, vertex-only update. *seen: the context's mark (LuminaryHost::skin_serial then).
+int update_context_scene(LuminaryHost* h, LumContext* core, uint32_t dirty, uint64_t* seen) {
+  auto bind = [&](uint32_t mesh, const HostSkin& k) {
+    return lumc_mesh_skin_bind(core, mesh, k.rest_positions.data(), k.rest_normals.data(), k.bone_ids.data(), k.weights.data(), (uint32_t) (k.bone_ids.size() / 12), k.bone_count);
+  };
+  const bool rebuilds_meshes = (dirty & LUMC_DIRTY_MESHES) != 0;
+  if (!rebuilds_meshes)
+    for (const auto& kv : h->skins) {
+      const HostSkin& k = kv.second;
+      if (k.bind_serial > *seen && bind(kv.first, k)) return 1;
+      if (!k.palette.empty() && (k.bind_serial > *seen || k.pose_serial > *seen) && lumc_mesh_skin_pose(core, kv.first, k.palette.data(), k.bone_count)) return 1;
+    }
+  if (lumc_scene_update(core, &h->device_scene.view, dirty)) return 1;
+  if (rebuilds_meshes) {
+    bool posed = false;
+    for (const auto& kv : h->skins) {
+      const HostSkin& k = kv.second;
+      if (bind(kv.first, k)) return 1;
+      if (k.palette.empty()) continue;
+      if (lumc_mesh_skin_pose(core, kv.first, k.palette.data(), k.bone_count)) return 1;
+      posed = true;
+    }
+    if (posed && lumc_scene_update(core, &h->device_scene.view, LUMC_DIRTY_MESH_SKIN)) return 1;
+  }
+  *seen = h->skin_serial;
+  return 0;
+}
+
 LuminaryResult ensure_device_scene(LuminaryHost* h) {
   if (h->device_scene_valid) return LUMINARY_SUCCESS;
+  // what the encoders read of a posed mesh is brought up to date first: every mesh for encode_vertices, the emitters for build_light_tree
+  for (auto& kv : h->skins) {
+    if (h->scene_dirty & LUMC_DIRTY_MESHES) { materialise(h, kv.first); kv.second.view_current = true; }
+    else if ((h->scene_dirty & LUMC_DIRTY_LIGHTS) && kv.first < h->scene.meshes.size() && mesh_emits(h, kv.first)) materialise(h, kv.first);
+  }
   if (h->hdri_origin_pending) {  // sky_hdri_update (device/device_sky.c:249-266): the panorama follows the camera only when the sky is dirty
     const LuminaryVec3 p = h->scene.camera.pos;
     h->scene.hdri_origin[0] = p.x; h->scene.hdri_origin[1] = p.y; h->scene.hdri_origin[2] = p.z;
@@ -211,7 +286,7 @@ LuminaryResult ensure_core(LuminaryHost* h) {
     lumc_set_mesh_refit(h->core, h->refit_mode, h->refit_max_cost_growth);
     lumc_set_instance_update(h->core, h->instance_update_mode);
     lumc_set_mesh_refit_in_place(h->core, h->refit_in_place);
-    if (lumc_scene_update(h->core, &h->device_scene.view, h->core_dirty)) { std::fprintf(stderr, "[luminary_amd] %s\n", lumc_last_error(h->core)); h->core_dirty = LUMC_DIRTY_ALL; return LUMINARY_ERROR_CUDA; }
+    if (update_context_scene(h, h->core, h->core_dirty, &h->core_skin_seen)) { std::fprintf(stderr, "[luminary_amd] %s\n", lumc_last_error(h->core)); h->core_dirty = LUMC_DIRTY_ALL; return LUMINARY_ERROR_CUDA; }
     h->core_dirty = 0;
     h->core_scene_valid = true;
     // The accumulation starts over. With the frame size unchanged the pixel sets of the devices stay as they are and only their accumulators
@@ -255,7 +330,7 @@ LuminaryResult ensure_partition_cores(LuminaryHost* h, std::vector<LumContext*>*
       lumc_set_mesh_refit(slot->core, h->refit_mode, h->refit_max_cost_growth);
       lumc_set_instance_update(slot->core, h->instance_update_mode);
       lumc_set_mesh_refit_in_place(slot->core, h->refit_in_place);
-      if (lumc_scene_update(slot->core, &h->device_scene.view, slot->dirty)) { std::fprintf(stderr, "[luminary_amd] device %d: %s\n", slot->ordinal, lumc_last_error(slot->core)); slot->dirty = LUMC_DIRTY_ALL; return LUMINARY_ERROR_CUDA; }
+      if (update_context_scene(h, slot->core, slot->dirty, &slot->skin_seen)) { std::fprintf(stderr, "[luminary_amd] device %d: %s\n", slot->ordinal, lumc_last_error(slot->core)); slot->dirty = LUMC_DIRTY_ALL; return LUMINARY_ERROR_CUDA; }
       slot->dirty = 0;
       slot->scene_valid = true;
       h->partition_n = 0;  // the accumulation restarts: the render loop deals the tiles again (which also clears every device's accumulators)
@@ -793,6 +868,7 @@ LuminaryResult luminary_ext_set_mesh_positions(LuminaryHost* host, uint32_t mesh
   CHECK_NULL(host);
   ApiLock lock(host);
   if (!positions || mesh_id >= host->scene.meshes.size() || host->scene.meshes[mesh_id].triangle_count() != triangle_count) return LUMINARY_ERROR_INVALID_API_ARGUMENT;
+  if (host->skins.count(mesh_id)) return LUMINARY_ERROR_INVALID_API_ARGUMENT;  // a bound mesh moves by its bones (luminary_ext_set_mesh_pose)
   for (size_t i = 0; i < 9 * (size_t) triangle_count; i++) if (!std::isfinite(positions[i])) return LUMINARY_ERROR_INVALID_API_ARGUMENT;
   lum::HostMesh& m = host->scene.meshes[mesh_id];
   // in place (std::copy into the vectors as they are): the pointers luminary_ext_get_mesh handed out stay valid. The caller may pass those very pointers.
@@ -801,6 +877,76 @@ LuminaryResult luminary_ext_set_mesh_positions(LuminaryHost* host, uint32_t mesh
   if (!normals) face_normals(m.positions.data(), triangle_count, m.normals.data());
   if (std::find(host->moved_meshes.begin(), host->moved_meshes.end(), mesh_id) == host->moved_meshes.end()) host->moved_meshes.push_back(mesh_id);
   invalidate(host, LUMC_DIRTY_MESH_POSITIONS | LUMC_DIRTY_LIGHTS);  // the vertices and the mesh's tree; the light tree follows moved emitters
+  return LUMINARY_SUCCESS;
+}
+LuminaryResult luminary_ext_bind_mesh_skin(LuminaryHost* host, uint32_t mesh_id, const uint16_t* bone_ids, const float* weights, uint32_t triangle_count, uint32_t bone_count) {
+  CHECK_NULL(host);
+  ApiLock lock(host);
+  if (!bone_ids || !weights || mesh_id >= host->scene.meshes.size() || host->scene.meshes[mesh_id].triangle_count() != triangle_count) return LUMINARY_ERROR_INVALID_API_ARGUMENT;
+  if (bone_count == 0 || bone_count > lum::kSkinMaxBones) return LUMINARY_ERROR_INVALID_API_ARGUMENT;
+  for (size_t i = 0; i < 12 * (size_t) triangle_count; i++)
+    if (bone_ids[i] >= bone_count || !(weights[i] >= 0.0f) || !std::isfinite(weights[i])) return LUMINARY_ERROR_INVALID_API_ARGUMENT;
+  materialise(host, mesh_id);  // (bound before: the rest pose is the current pose)
+  const lum::HostMesh& m = host->scene.meshes[mesh_id];
+  HostSkin k;
+  k.rest_positions = m.positions; k.rest_normals = m.normals;
+  k.bone_ids.assign(bone_ids, bone_ids + 12 * (size_t) triangle_count);
+  k.weights.assign(weights, weights + 12 * (size_t) triangle_count);
+  k.bone_count = bone_count;
+  k.bind_serial = ++host->skin_serial;
+  const auto old = host->skins.find(mesh_id);
+  const bool stale_view = old != host->skins.end() && !old->second.view_current;
+  host->skins[mesh_id] = std::move(k);  // (the vertices stay where they are: nothing restarts; the contexts get the binding before their next update)
+  if (stale_view) {  // bound and posed before: a context trusts the view's vertices of a mesh until its first pose under the new binding, so they are encoded again
+    if (std::find(host->moved_meshes.begin(), host->moved_meshes.end(), mesh_id) == host->moved_meshes.end()) host->moved_meshes.push_back(mesh_id);
+    invalidate(host, LUMC_DIRTY_MESH_POSITIONS);
+  }
+  return LUMINARY_SUCCESS;
+}
+LuminaryResult luminary_ext_set_mesh_pose(LuminaryHost* host, uint32_t mesh_id, const float* bones, uint32_t bone_count) {
+  CHECK_NULL(host);
+  ApiLock lock(host);
+  const auto it = host->skins.find(mesh_id);
+  if (!bones || it == host->skins.end() || bone_count != it->second.bone_count) return LUMINARY_ERROR_INVALID_API_ARGUMENT;
+  for (size_t i = 0; i < 12 * (size_t) bone_count; i++) if (!std::isfinite(bones[i])) return LUMINARY_ERROR_INVALID_API_ARGUMENT;
+  HostSkin& k = it->second;
+  k.palette.assign(bones, bones + 12 * (size_t) bone_count);
+  k.pose_serial = ++host->skin_serial;
+  k.host_current = false; k.view_current = false;
+  uint32_t dirty = LUMC_DIRTY_MESH_SKIN;
+  if (mesh_emits(host, mesh_id)) { materialise(host, mesh_id); dirty |= LUMC_DIRTY_LIGHTS; }  // the light tree is built from the host mesh: the existing path
+  invalidate(host, dirty);
+  return LUMINARY_SUCCESS;
+}
+LuminaryResult luminary_ext_unbind_mesh_skin(LuminaryHost* host, uint32_t mesh_id) {
+  CHECK_NULL(host);
+  ApiLock lock(host);
+  const auto it = host->skins.find(mesh_id);
+  if (it == host->skins.end()) return LUMINARY_ERROR_INVALID_API_ARGUMENT;
+  materialise(host, mesh_id);
+  const bool view_current = it->second.view_current;
+  host->skins.erase(it);
+  // every context that holds the binding drops it (one that never got it refuses: nothing to drop); the devices' vertices are the pose the host mesh now holds
+  if (host->core) (void) lumc_mesh_skin_unbind(host->core, mesh_id);
+  for (uint32_t i = 0; i < host->devices.size(); i++)
+    if (i != host->main_slot && host->devices[i].core) (void) lumc_mesh_skin_unbind(host->devices[i].core, mesh_id);
+  if (!view_current) {  // the device scene's vertices of the mesh are re-encoded from the host mesh, as for moved vertices
+    if (std::find(host->moved_meshes.begin(), host->moved_meshes.end(), mesh_id) == host->moved_meshes.end()) host->moved_meshes.push_back(mesh_id);
+    invalidate(host, LUMC_DIRTY_MESH_POSITIONS);
+  }
+  return LUMINARY_SUCCESS;
+}
+LuminaryResult luminary_ext_get_mesh_skin_stats(LuminaryHost* host, LuminaryMeshSkinStats* out) {
+  CHECK_NULL(host); CHECK_NULL(out);
+  ApiLock lock(host);
+  std::memset(out, 0, sizeof(*out));
+  out->host_materialisations = host->host_materialisations;
+  if (!host->core) return LUMINARY_SUCCESS;
+  LumMeshSkinStats s;
+  if (lumc_mesh_skin_stats(host->core, &s)) return LUMINARY_ERROR_API_EXCEPTION;
+  static_assert(sizeof(LuminaryMeshSkinStats) == sizeof(LumMeshSkinStats) + sizeof(uint64_t) && offsetof(LuminaryMeshSkinStats, host_materialisations) == sizeof(LumMeshSkinStats),
+                "the public struct mirrors the core's, host_materialisations behind it");
+  std::memcpy(out, &s, sizeof(s));
   return LUMINARY_SUCCESS;
 }
 LuminaryResult luminary_ext_set_mesh_refit(LuminaryHost* host, uint32_t mode, float max_cost_growth) {
@@ -885,6 +1031,7 @@ LuminaryResult luminary_ext_get_mesh(LuminaryHost* host, uint32_t mesh_id, const
   CHECK_NULL(host); CHECK_NULL(triangle_count);
   ApiLock lock(host);
   if (mesh_id >= host->scene.meshes.size()) return LUMINARY_ERROR_INVALID_API_ARGUMENT;
+  materialise(host, mesh_id);  // (a posed mesh: the host mesh is lazy)
   const lum::HostMesh& m = host->scene.meshes[mesh_id];
   if (positions) *positions = m.positions.data();
   if (normals) *normals = m.normals.data();
@@ -908,6 +1055,18 @@ LuminaryResult luminary_ext_build_device_scene(LuminaryHost* host, const LumDevi
   ApiLock lock(host);
   const LuminaryResult r = ensure_device_scene(host);
   if (r) return r;
+  // An independent consumer sees a current view: the vertices of posed meshes, which the contexts never read and the render path therefore leaves stale, are
+  // encoded from the materialised host meshes. Nothing the contexts hold changes: no dirty flag, no restart.
+  for (auto& kv : host->skins) {
+    if (kv.second.view_current) continue;
+    materialise(host, kv.first);
+    host->device_scene.moved_meshes.push_back(kv.first);
+    kv.second.view_current = true;
+  }
+  if (!host->device_scene.moved_meshes.empty()) {
+    const std::string err = lum::update_device_scene(host->scene, host->device_scene.bluenoise, LUMC_DIRTY_MESH_POSITIONS, &host->device_scene);
+    if (!err.empty()) return LUMINARY_ERROR_API_EXCEPTION;
+  }
   *view = &host->device_scene.view;
   return LUMINARY_SUCCESS;
 }

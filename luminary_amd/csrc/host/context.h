@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
+#include <map>
 #include <memory>
 #include <string>
 #include <vector>
@@ -19,6 +20,7 @@
 #include "bvh_refit.h"
 #include "device_buffer.h"
 #include "instance_update.h"
+#include "mesh_skin.h"
 #include "scene_arrays.h"
 #include "work_layout.h"
 
@@ -38,6 +40,7 @@ struct MeshRefit {
   uint64_t fit_hash[2] = {0, 0};   // of the vertices the held tree was built from or last fitted to (mesh_tree_key)
   double built_cost = 0.0;         // bvh4_cost of the tree as last built (0: not computed yet)
   bool stale = false;              // the mesh was refitted in the resident node array since: the host's nodes hold the boxes of earlier vertices (restore_stale_meshes)
+  bool fit_to_pose = false;        // the held tree was last fitted to vertices k_skin_mesh wrote: no host vertices hash to that, fit_hash is not compared
 };
 
 struct LumContext {
@@ -65,6 +68,16 @@ struct LumContext {
   ResidentRefit resident_refit;              // the layout's slot maps, the per-mesh slot lists and the scratch; dropped with the layout
   uint32_t stale_meshes = 0;                 // meshes of mesh_refit marked stale
   LumResidentRefitStats resident_stats{};
+  // skinned meshes (lumc_mesh_skin_*; mesh_skin.hip, scene_device.hip skin_meshes)
+  std::map<uint32_t, MeshSkin> mesh_skin;    // by mesh; dropped with the meshes
+  DeviceBuffer<uint32_t> d_skin_flags;       // one word of kSkinFlag* bits per launch of an update
+  LumMeshSkinStats skin_stats{};
+  struct SkinUpdate {                        // of the scene update that is running (scene_update resets it)
+    bool done = false;                       // the skinning step ran: a fallback that takes the other path does not run it again
+    bool view_uploaded = false;              // the vertex arrays came from the view: the hashes that find moved meshes run
+    std::vector<uint32_t> moved;             // the meshes a new pose was applied to: moved, whatever the hashes say
+    bool is_moved(uint32_t m) const { for (uint32_t x : moved) if (x == m) return true; return false; }
+  } skin_update;
   std::vector<uint32_t> sky_lut_key;  // the sky parameters the two sky tables were generated from
   DeviceBuffer<float> d_bridge_lut;   // the bridge sampler's vertex-count table (context-owned: scene.bridge_lut points here while bridges are possible)
   std::vector<float> bridge_lut_host; // its content, to notice a caller that hands over another table

@@ -10,6 +10,7 @@
 #include <cfloat>
 #include <cstring>
 #include <map>
+#include <string>
 #include <mutex>
 #include <tuple>
 
@@ -111,6 +112,7 @@ void free_scene(LumContext* ctx) {
   ctx->mesh_bvh.clear(); ctx->mesh_box.clear(); ctx->mesh_refit.clear(); ctx->mesh_tri_offset.clear();
   ctx->instance_update.reset(); ctx->instance_mesh_ids.clear();
   ctx->resident_refit.drop_layout(); ctx->stale_meshes = 0;
+  ctx->mesh_skin.clear(); ctx->d_skin_flags.reset();
   ctx->has_scene = false;
 }
 
@@ -373,11 +375,86 @@ static int build_mesh_trees(LumContext* ctx, const LumDeviceSceneView* v, std::v
   return 0;
 }
 
+// ---- skinned meshes (lum_core.h lumc_mesh_skin_bind; mesh_skin.hip) ----
+static bool skin_posed(const LumContext* ctx, uint32_t m) {
+  const auto it = ctx->mesh_skin.find(m);
+  return it != ctx->mesh_skin.end() && it->second.posed;
+}
+
+// The skinning step of an update that touches vertices, once per update, after the vertex arrays are in place and before anything reads them: every pending
+// palette goes up and k_skin_mesh writes its mesh's range of the scene's vertices (those meshes are moved: ctx->skin_update.moved); after an upload of the vertex
+// arrays from the view (view_uploaded) every other bound mesh that has been posed is written again from the palette it holds - the same bits as before the upload,
+// so its tree still fits. One launch per mesh. Then the launches' flag words come back: a posed position that is not finite fails the update.
+static int skin_meshes(LumContext* ctx, bool view_uploaded) {
+  using clock = std::chrono::steady_clock;
+  auto since = [](clock::time_point t) { return std::chrono::duration<double>(clock::now() - t).count(); };
+  LumContext::SkinUpdate& su = ctx->skin_update;
+  if (su.done) return 0;
+  su.done = true; su.view_uploaded = view_uploaded;
+  std::vector<uint32_t> jobs;
+  for (const auto& kv : ctx->mesh_skin)
+    if (!kv.second.pending.empty() || (view_uploaded && kv.second.posed)) jobs.push_back(kv.first);
+  if (jobs.empty()) return 0;
+  LumMeshSkinStats& st = ctx->skin_stats;
+  st.last_meshes = st.last_launches = 0; st.last_bytes_uploaded = 0; st.seconds = st.seconds_upload = st.seconds_skin = 0.0;
+  DeviceBuffer<float4>& vertices = ctx->arrays.mesh.vertices;
+  for (uint32_t m : jobs) {  // every range a kernel will write, against the array that is there
+    const MeshSkin& skin = ctx->mesh_skin[m];
+    if ((size_t) m + 1 >= ctx->mesh_tri_offset.size() || ctx->mesh_tri_offset[m + 1] - ctx->mesh_tri_offset[m] != skin.triangles ||
+        3 * (size_t) ctx->mesh_tri_offset[m + 1] > vertices.count()) {
+      ctx->error = "lumc_scene_update: mesh " + std::to_string(m) + " is bound to a skin of another triangle count than the scene on the device";
+      return 1;
+    }
+  }
+  const auto t_all = clock::now();
+  if (ctx->d_skin_flags.count() < jobs.size()) HIP_TRY(ctx, ctx->d_skin_flags.resize(jobs.size()));
+  HIP_TRY(ctx, hipMemset(ctx->d_skin_flags.get(), 0, sizeof(uint32_t) * jobs.size()));
+  for (uint32_t m : jobs) {
+    MeshSkin& skin = ctx->mesh_skin[m];
+    if (skin.pending.empty()) continue;
+    HIP_TRY(ctx, hipMemcpy(skin.palette.get(), skin.pending.data(), sizeof(float) * skin.pending.size(), hipMemcpyHostToDevice));
+    st.last_bytes_uploaded += sizeof(float) * skin.pending.size();
+  }
+  HIP_TRY(ctx, hipDeviceSynchronize());
+  st.seconds_upload = since(t_all);
+  const auto t_skin = clock::now();
+  for (size_t j = 0; j < jobs.size(); j++) {
+    HIP_TRY(ctx, mesh_skin_launch(ctx->mesh_skin[jobs[j]], vertices.get() + 3 * (size_t) ctx->mesh_tri_offset[jobs[j]], ctx->d_skin_flags.get() + j));
+    st.last_launches++;
+  }
+  std::vector<uint32_t> flags(jobs.size());
+  HIP_TRY(ctx, hipMemcpy(flags.data(), ctx->d_skin_flags.get(), sizeof(uint32_t) * jobs.size(), hipMemcpyDeviceToHost));  // (waits for the launches)
+  st.seconds_skin = since(t_skin);
+  st.seconds = since(t_all);
+  for (size_t j = 0; j < jobs.size(); j++) {
+    if (flags[j] & kSkinFlagBadBone) { ctx->error = "lumc_scene_update: mesh " + std::to_string(jobs[j]) + ": a bone id beyond the palette reached the skinning kernel"; return 1; }
+    if (flags[j] & kSkinFlagNotFinite) { ctx->error = "lumc_scene_update: mesh " + std::to_string(jobs[j]) + ": the pose gives a position that is not finite"; return 1; }
+  }
+  for (uint32_t m : jobs) {
+    MeshSkin& skin = ctx->mesh_skin[m];
+    if (skin.pending.empty()) continue;
+    skin.pending.clear(); skin.posed = true;
+    su.moved.push_back(m);
+    st.poses++; st.last_meshes++;
+  }
+  return 0;
+}
+
+// A posed mesh's vertices for a builder: its 3 * nt records as the device holds them, the layout of the view's `vertices`. Counted.
+static int download_posed_vertices(LumContext* ctx, uint32_t t0, uint32_t nt, std::vector<float>& out) {
+  out.resize(12 * (size_t) nt);
+  if (3 * ((size_t) t0 + nt) > ctx->arrays.mesh.vertices.count()) { ctx->error = "lumc_scene_update: a posed mesh lies outside the vertex array"; return 1; }
+  HIP_TRY(ctx, hipMemcpy(out.data(), ctx->arrays.mesh.vertices.get() + 3 * (size_t) t0, sizeof(float) * out.size(), hipMemcpyDeviceToHost));
+  ctx->skin_stats.rebuild_downloads++;
+  return 0;
+}
+
 // LUMC_DIRTY_MESH_POSITIONS: the vertex arrays of the same meshes again - the traversal triangles stay on the device (update_mesh_arrays) -, then
 // every mesh whose vertices differ from those its held tree was fitted to gets a tree for them: refitted on the device (bvh_refit.hip; the tree becomes
 // private to this context, the shared one it came from is not touched and the cache never sees the refitted one) or, where the mode, the cost's growth or a
 // tree that cannot be refitted says so, from the cache / the builder like an upload. *rebuilt: a mesh's traversal triangles were written anew (k_tri_opacity).
-static int refit_mesh_trees(LumContext* ctx, const LumDeviceSceneView* v, bool* rebuilt, bool arrays_uploaded = false) {
+// upload_view: the view's vertex arrays are taken over (false: a LUMC_DIRTY_MESH_SKIN update alone - only posed meshes move, the view's vertices are not read).
+static int refit_mesh_trees(LumContext* ctx, const LumDeviceSceneView* v, bool* rebuilt, bool arrays_uploaded = false, bool upload_view = true) {
   using clock = std::chrono::steady_clock;
   auto since = [](clock::time_point t) { return std::chrono::duration<double>(clock::now() - t).count(); };
   DeviceScene& sc = ctx->scene;
@@ -394,18 +471,26 @@ static int refit_mesh_trees(LumContext* ctx, const LumDeviceSceneView* v, bool* 
   const auto t_all = clock::now();
   BvhTri* d_tris = ctx->arrays.mesh.blas_tris.get();
   if (!d_tris) { ctx->error = "lumc_scene_update: the scene on the device has no traversal triangles"; return 1; }
-  if (!arrays_uploaded && update_mesh_arrays(ctx, v)) return 1;  // (a fallback from refit_in_place has uploaded them)
+  if (!arrays_uploaded && upload_view && update_mesh_arrays(ctx, v)) return 1;  // (a fallback from refit_in_place has uploaded them)
   HIP_TRY(ctx, hipDeviceSynchronize());
   st.seconds_upload = since(t_all);
+  if (skin_meshes(ctx, upload_view)) return 1;  // (once per update: that fallback has run it)
+  const LumContext::SkinUpdate& su = ctx->skin_update;
+  std::vector<float> posed_vertices;
   for (uint32_t m = 0; m < v->num_meshes; m++) {
     const uint32_t t0 = v->mesh_tri_offset[m], nt = v->mesh_tri_offset[m + 1] - t0;
     if (nt == 0) continue;
+    const bool posed = su.is_moved(m);  // moved by a pose: no hash, and the view's vertices of it are never read
+    if (!posed && (!su.view_uploaded || skin_posed(ctx, m))) continue;
     const float* vertices = v->vertices + (size_t) t0 * 12;
     MeshRefit& mr = ctx->mesh_refit[m];
-    const auto t_hash = clock::now();
-    const MeshTreeKey key = mesh_tree_key(vertices, nt, ctx->bvh_builder);
-    st.seconds_hash += since(t_hash);
-    if (key.h0 == mr.fit_hash[0] && key.h1 == mr.fit_hash[1]) continue;  // the held tree fits these vertices
+    MeshTreeKey key{};
+    if (!posed) {
+      const auto t_hash = clock::now();
+      key = mesh_tree_key(vertices, nt, ctx->bvh_builder);
+      st.seconds_hash += since(t_hash);
+      if (!mr.fit_to_pose && key.h0 == mr.fit_hash[0] && key.h1 == mr.fit_hash[1]) continue;  // the held tree fits these vertices
+    }
     bool build = ctx->refit_mode == 1;
     if (!build) {
       const auto t_refit = clock::now();
@@ -434,6 +519,11 @@ static int refit_mesh_trees(LumContext* ctx, const LumDeviceSceneView* v, bool* 
     }
     if (build) {
       const auto t_build = clock::now();
+      if (posed) {  // the builder reads host vertices: the posed ones come down (the view's layout), and with them the key of the process's tree cache
+        if (download_posed_vertices(ctx, t0, nt, posed_vertices)) return 1;
+        vertices = posed_vertices.data();
+        key = mesh_tree_key(vertices, nt, ctx->bvh_builder);
+      }
       std::vector<Aabb> tri_boxes(nt);
       ctx->mesh_box[m] = mesh_triangle_boxes(vertices, nt, tri_boxes.data());
       mesh_boxes_changed(ctx);
@@ -449,7 +539,8 @@ static int refit_mesh_trees(LumContext* ctx, const LumDeviceSceneView* v, bool* 
       st.rebuilds++; st.last_rebuilds++;
       st.seconds_rebuild += since(t_build);
     }
-    mr.fit_hash[0] = key.h0; mr.fit_hash[1] = key.h1;
+    mr.fit_to_pose = posed;
+    mr.fit_hash[0] = posed ? 0 : key.h0; mr.fit_hash[1] = posed ? 0 : key.h1;
   }
   st.seconds = since(t_all);
   return 0;
@@ -619,7 +710,7 @@ static int update_instance_transforms(LumContext* ctx, const LumDeviceSceneView*
 // *fell_back: this update takes refit_mesh_trees' path instead (a moved mesh that cannot be refitted, fewer than two instances that can be hit, a failed
 // allocation or layout, a cost growth beyond the threshold); the vertex arrays are uploaded, the context is consistent: nothing else was written, or what was
 // written in place is marked stale.
-static int refit_in_place(LumContext* ctx, const LumDeviceSceneView* v, bool* fell_back) {
+static int refit_in_place(LumContext* ctx, const LumDeviceSceneView* v, bool* fell_back, bool upload_view = true) {
   using clock = std::chrono::steady_clock;
   auto since = [](clock::time_point t) { return std::chrono::duration<double>(clock::now() - t).count(); };
   DeviceScene& sc = ctx->scene;
@@ -640,22 +731,29 @@ static int refit_in_place(LumContext* ctx, const LumDeviceSceneView* v, bool* fe
   const auto t_all = clock::now();
   BvhTri* d_tris = ctx->arrays.mesh.blas_tris.get();
   if (!d_tris) { ctx->error = "lumc_scene_update: the scene on the device has no traversal triangles"; return 1; }
-  if (update_mesh_arrays(ctx, v)) return 1;
+  if (upload_view && update_mesh_arrays(ctx, v)) return 1;  // (a LUMC_DIRTY_MESH_SKIN update alone: the arrays stay, only posed meshes move)
   HIP_TRY(ctx, hipDeviceSynchronize());
   rs.seconds_upload = st.seconds_upload = since(t_all);
-  // the meshes that moved
+  if (skin_meshes(ctx, upload_view)) return 1;
+  const LumContext::SkinUpdate& su = ctx->skin_update;
+  // the meshes that moved: by a pose, or - among the others, where the view's vertices were taken over - by their hashes
   auto t = clock::now();
   std::vector<uint32_t> moved;
   std::vector<MeshTreeKey> keys;
   for (uint32_t m = 0; m < v->num_meshes; m++) {
     const uint32_t t0 = v->mesh_tri_offset[m], nt = v->mesh_tri_offset[m + 1] - t0;
     if (nt == 0) continue;
-    const MeshTreeKey key = mesh_tree_key(v->vertices + (size_t) t0 * 12, nt, ctx->bvh_builder);
-    if (key.h0 == ctx->mesh_refit[m].fit_hash[0] && key.h1 == ctx->mesh_refit[m].fit_hash[1]) continue;  // the held tree fits these vertices
+    const bool posed = su.is_moved(m);
+    if (!posed && (!su.view_uploaded || skin_posed(ctx, m))) continue;
+    MeshTreeKey key{};
+    if (!posed) {
+      key = mesh_tree_key(v->vertices + (size_t) t0 * 12, nt, ctx->bvh_builder);
+      if (!ctx->mesh_refit[m].fit_to_pose && key.h0 == ctx->mesh_refit[m].fit_hash[0] && key.h1 == ctx->mesh_refit[m].fit_hash[1]) continue;  // the held tree fits these vertices
+    }
     if (ctx->mesh_bvh[m]->bvh.prims.size() != nt) { *fell_back = true; return 0; }  // spatial splits: the other path builds it
     moved.push_back(m); keys.push_back(key);
   }
-  rs.seconds_hash = st.seconds_hash = since(t);
+  rs.seconds_hash = st.seconds_hash = su.view_uploaded ? since(t) : 0.0;
   t = clock::now();
   // the layout, and the moved instances' scratch with the meshes' boxes in it
   if (!u.resident || !u.prepared || u.num_instances != v->num_instances || u.num_meshes != v->num_meshes || rr.mesh_slots.size() != v->num_meshes) {
@@ -701,7 +799,8 @@ static int refit_in_place(LumContext* ctx, const LumDeviceSceneView* v, bool* fe
   for (size_t j = 0; j < moved.size(); j++) {
     MeshRefit& mr = ctx->mesh_refit[moved[j]];
     ctx->mesh_box[moved[j]] = results[j].box;  // (u.mesh_box on the device holds it already: `prepared` stays)
-    mr.fit_hash[0] = keys[j].h0; mr.fit_hash[1] = keys[j].h1;
+    mr.fit_to_pose = su.is_moved(moved[j]);
+    mr.fit_hash[0] = keys[j].h0; mr.fit_hash[1] = keys[j].h1;  // (zeros for a posed mesh)
     st.refits++; st.last_refits++;
   }
   st.max_cost_growth = max_growth;
@@ -971,7 +1070,16 @@ static int scene_update(LumContext* ctx, const LumDeviceSceneView* v, unsigned d
   DeviceScene& sc = ctx->scene;
   if (!v->bluenoise_2d) { ctx->error = "scene has no blue-noise mask"; return 1; }
   if (v->max_ray_depth > 63) { ctx->error = "max_ray_depth exceeds 63 (6-bit field, device_structs.h:9)"; return 1; }
-  if (dirty & LUMC_DIRTY_MESHES) dirty &= ~(unsigned) LUMC_DIRTY_MESH_POSITIONS;  // a full rebuild of the meshes covers moved vertices
+  if (dirty & LUMC_DIRTY_MESHES) dirty &= ~(unsigned) (LUMC_DIRTY_MESH_POSITIONS | LUMC_DIRTY_MESH_SKIN);  // a full rebuild of the meshes covers moved vertices
+  // LUMC_DIRTY_MESH_SKIN: the meshes with a pending pose move, by the path moved vertices take - but the view's vertex arrays are uploaded only if the caller says they moved too
+  ctx->skin_update = LumContext::SkinUpdate{};
+  const bool upload_view = (dirty & LUMC_DIRTY_MESH_POSITIONS) != 0;
+  if (dirty & LUMC_DIRTY_MESH_SKIN) {
+    bool pending = false;
+    for (const auto& kv : ctx->mesh_skin) pending = pending || !kv.second.pending.empty();
+    dirty &= ~(unsigned) LUMC_DIRTY_MESH_SKIN;
+    if (pending) dirty |= LUMC_DIRTY_MESH_POSITIONS;
+  }
   // lumc_set_mesh_refit_in_place: moved vertices alone or with moved instances, both modes 0 - the refit happens in the resident node array, the top level follows as for moved instances
   bool in_place = ctx->refit_in_place && (dirty & LUMC_DIRTY_MESH_POSITIONS) && !(dirty & (LUMC_DIRTY_MESHES | LUMC_DIRTY_INSTANCES)) && ctx->refit_mode == 0 && ctx->instance_update_mode == 0;
   const bool instances_moved = (dirty & LUMC_DIRTY_INSTANCE_TRANSFORMS) != 0;
@@ -985,12 +1093,12 @@ static int scene_update(LumContext* ctx, const LumDeviceSceneView* v, unsigned d
   const bool meshes = (dirty & LUMC_DIRTY_MESHES) != 0, lights = (dirty & LUMC_DIRTY_LIGHTS) != 0;
   bool instances = (dirty & LUMC_DIRTY_INSTANCES) != 0;
   ctx->has_scene = false;
-  if (meshes) ctx->arrays.mesh = {};  // the traversal triangles too
+  if (meshes) { ctx->arrays.mesh = {}; ctx->mesh_skin.clear(); }  // the traversal triangles too; new meshes: the bindings go, the caller binds again
   if (meshes && update_mesh_arrays(ctx, v)) return 1;
   bool arrays_uploaded = false;
   if (in_place) {
     bool fell_back = false;
-    if (refit_in_place(ctx, v, &fell_back)) return 1;
+    if (refit_in_place(ctx, v, &fell_back, upload_view)) return 1;
     if (fell_back) {  // this one update by the other path, as it would have run with the switch off
       ctx->resident_stats.fallbacks++;
       in_place = false; arrays_uploaded = true;
@@ -1000,7 +1108,7 @@ static int scene_update(LumContext* ctx, const LumDeviceSceneView* v, unsigned d
   }
   if ((dirty & LUMC_DIRTY_MESH_POSITIONS) && !in_place) {
     bool rebuilt = false;
-    if (refit_mesh_trees(ctx, v, &rebuilt, arrays_uploaded)) return 1;
+    if (refit_mesh_trees(ctx, v, &rebuilt, arrays_uploaded, upload_view)) return 1;
     if (rebuilt) dirty |= kDirtyTrianglesRewritten;
   }
   const auto t_arrays = std::chrono::steady_clock::now();
@@ -1060,7 +1168,7 @@ int lumc_scene_update(LumContext* ctx, const LumDeviceSceneView* v, unsigned int
   if (!ctx->has_scene || (dirty & LUMC_DIRTY_ALL) == LUMC_DIRTY_ALL) return lumc_scene_upload(ctx, v);
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   HIP_TRY(ctx, hipDeviceSynchronize());  // nothing renders from the arrays that are about to be freed
-  if (scene_update(ctx, v, dirty & (LUMC_DIRTY_ALL | LUMC_DIRTY_MESH_POSITIONS | LUMC_DIRTY_INSTANCE_TRANSFORMS))) { free_scene(ctx); return 1; }  // a failed partial update leaves no half-updated scene behind
+  if (scene_update(ctx, v, dirty & (LUMC_DIRTY_ALL | LUMC_DIRTY_MESH_POSITIONS | LUMC_DIRTY_INSTANCE_TRANSFORMS | LUMC_DIRTY_MESH_SKIN))) { free_scene(ctx); return 1; }  // a failed partial update leaves no half-updated scene behind
   return 0;
 }
 
@@ -1100,6 +1208,62 @@ int lumc_set_mesh_refit_in_place(LumContext* ctx, uint32_t on) {
 int lumc_resident_refit_stats(const LumContext* ctx, LumResidentRefitStats* out) {
   if (!ctx || !out) return 1;
   *out = ctx->resident_stats;
+  return 0;
+}
+
+int lumc_mesh_skin_bind(LumContext* ctx, uint32_t mesh, const float* rest_positions, const float* rest_normals, const uint16_t* bone_ids, const float* weights,
+                        uint32_t triangle_count, uint32_t bone_count) {
+  if (!ctx) return 1;
+  if (!ctx->has_scene || (size_t) mesh + 1 >= ctx->mesh_tri_offset.size() || ctx->mesh_tri_offset[mesh + 1] - ctx->mesh_tri_offset[mesh] != triangle_count) {
+    ctx->error = "lumc_mesh_skin_bind: mesh " + std::to_string(mesh) + " is not in the scene on the device with that triangle count";
+    return 1;
+  }
+  if (!rest_positions || !rest_normals || !bone_ids || !weights) { ctx->error = "lumc_mesh_skin_bind: a NULL array"; return 1; }
+  if (bone_count == 0 || bone_count > kSkinMaxBones) { ctx->error = "lumc_mesh_skin_bind: bone_count is 1 ... 1024"; return 1; }
+  for (size_t i = 0; i < 12 * (size_t) triangle_count; i++) {
+    if (bone_ids[i] >= bone_count) { ctx->error = "lumc_mesh_skin_bind: a bone id is not below bone_count"; return 1; }
+    if (!(weights[i] >= 0.0f) || !std::isfinite(weights[i])) { ctx->error = "lumc_mesh_skin_bind: a weight is negative or not finite"; return 1; }
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  MeshSkin skin;
+  HIP_TRY(ctx, mesh_skin_upload(skin, rest_positions, rest_normals, bone_ids, weights, triangle_count, bone_count));
+  ctx->mesh_skin[mesh] = std::move(skin);
+  return 0;
+}
+
+int lumc_mesh_skin_unbind(LumContext* ctx, uint32_t mesh) {
+  if (!ctx) return 1;
+  const auto it = ctx->mesh_skin.find(mesh);
+  if (it == ctx->mesh_skin.end()) { ctx->error = "lumc_mesh_skin_unbind: mesh " + std::to_string(mesh) + " is not bound"; return 1; }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  ctx->mesh_skin.erase(it);
+  return 0;
+}
+
+int lumc_mesh_skin_pose(LumContext* ctx, uint32_t mesh, const float* bones, uint32_t bone_count) {
+  if (!ctx) return 1;
+  const auto it = ctx->mesh_skin.find(mesh);
+  if (it == ctx->mesh_skin.end()) { ctx->error = "lumc_mesh_skin_pose: mesh " + std::to_string(mesh) + " is not bound"; return 1; }
+  if (!bones || bone_count != it->second.bone_count) { ctx->error = "lumc_mesh_skin_pose: mesh " + std::to_string(mesh) + " is bound to another bone count"; return 1; }
+  for (size_t i = 0; i < 12 * (size_t) bone_count; i++)
+    if (!std::isfinite(bones[i])) { ctx->error = "lumc_mesh_skin_pose: a matrix entry is not finite"; return 1; }
+  it->second.pending.assign(bones, bones + 12 * (size_t) bone_count);
+  return 0;
+}
+
+int lumc_mesh_skin_stats(const LumContext* ctx, LumMeshSkinStats* out) {
+  if (!ctx || !out) return 1;
+  *out = ctx->skin_stats;
+  return 0;
+}
+
+int lumc_mesh_vertices_probe(LumContext* ctx, uint32_t mesh, void* out) {
+  if (!ctx || !out) return 1;
+  if (!ctx->has_scene || (size_t) mesh + 1 >= ctx->mesh_tri_offset.size()) { ctx->error = "lumc_mesh_vertices_probe: no such mesh in the scene on the device"; return 1; }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const uint32_t t0 = ctx->mesh_tri_offset[mesh], nt = ctx->mesh_tri_offset[mesh + 1] - t0;
+  if (3 * ((size_t) t0 + nt) > ctx->arrays.mesh.vertices.count()) { ctx->error = "lumc_mesh_vertices_probe: the mesh lies outside the vertex array"; return 1; }
+  if (nt) HIP_TRY(ctx, hipMemcpy(out, ctx->arrays.mesh.vertices.get() + 3 * (size_t) t0, sizeof(float4) * 3 * (size_t) nt, hipMemcpyDeviceToHost));
   return 0;
 }
 

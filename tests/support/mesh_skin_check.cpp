@@ -1,0 +1,72 @@
+// Stand-alone check of the skinning twin (csrc/host/mesh_skin.cpp), built with the address and undefined-behaviour sanitizers by tests/test_mesh_skin.py: triangle
+// counts on either side of a wave and of a workgroup of corners, one bone and 1024 bones, ids that name the last bone, outputs that alias the inputs, outputs left
+// out, refused arguments. What it computes is held to numpy there; here every access is.
+#define LUM_SKIN_HOST_ONLY 1
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "../../luminary_amd/csrc/host/mesh_skin.h"
+
+static int fail(const char* what, unsigned triangles, unsigned bones) {
+  std::printf("mesh_skin_check: %s (triangles %u, bones %u)\n", what, triangles, bones);
+  return 1;
+}
+
+static float rnd(unsigned& s) { s = s * 1664525u + 1013904223u; return (float) (s >> 8) * (1.0f / 8388608.0f) - 1.0f; }
+
+int main() {
+  const unsigned counts[] = {1, 21, 22, 85, 86}, bone_counts[] = {1, 1024};
+  for (unsigned nt : counts)
+    for (unsigned nb : bone_counts) {
+      unsigned seed = nt * 7919u + nb;
+      const size_t corners = 3 * (size_t) nt;
+      std::vector<float> p(3 * corners), n(3 * corners), w(4 * corners), bones(12 * (size_t) nb, 0.0f);
+      std::vector<uint16_t> ids(4 * corners);
+      for (float& x : p) x = 10.0f * rnd(seed);
+      for (size_t c = 0; c < corners; c++) { n[3 * c] = 0.0f; n[3 * c + 1] = 0.6f; n[3 * c + 2] = -0.8f; }
+      // every bone a translation by its own offset: the weights 1/2 + 1/2 (exact) of two slots that name the same bone give p + t, one rounding
+      for (unsigned b = 0; b < nb; b++) {
+        float* m = bones.data() + 12 * (size_t) b;
+        m[0] = m[5] = m[10] = 1.0f;
+        m[3] = (float) b * 0.25f; m[7] = -1.0f; m[11] = 2.0f;
+      }
+      for (size_t c = 0; c < corners; c++) {
+        const uint16_t b = (uint16_t) ((c % 3 == 0) ? nb - 1 : (c * 2654435761u) % nb);  // the first corner of every triangle names the last bone
+        ids[4 * c] = b; ids[4 * c + 1] = (uint16_t) (nb - 1); ids[4 * c + 2] = b; ids[4 * c + 3] = 0;
+        w[4 * c] = 0.5f; w[4 * c + 1] = 0.0f; w[4 * c + 2] = 0.5f; w[4 * c + 3] = -0.0f;
+      }
+      std::vector<float> op(3 * corners), on(3 * corners);
+      std::vector<uint32_t> packed(corners);
+      uint64_t bad = 7;
+      if (lum::skin_host(p.data(), n.data(), ids.data(), w.data(), nt, bones.data(), nb, op.data(), on.data(), packed.data(), &bad)) return fail("refused valid arguments", nt, nb);
+      if (bad != 0) return fail("finite poses counted as not finite", nt, nb);
+      for (size_t c = 0; c < corners; c++) {
+        const float* m = bones.data() + 12 * (size_t) ids[4 * c];
+        for (int k = 0; k < 3; k++) {
+          const float t = p[3 * c + k] + m[4 * k + 3], want = (0.0f + 0.5f * t) + 0.5f * t;
+          if (std::memcmp(&want, &op[3 * c + k], 4) != 0) return fail("a translated position differs", nt, nb);
+        }
+        if (packed[c] != lum::skin_pack_normal(on.data() + 3 * c)) return fail("a packed word is not that of the normal", nt, nb);
+      }
+      // in place, and with outputs left out
+      std::vector<float> p2 = p, n2 = n;
+      if (lum::skin_host(p2.data(), n2.data(), ids.data(), w.data(), nt, bones.data(), nb, p2.data(), n2.data(), nullptr, nullptr)) return fail("refused in place", nt, nb);
+      if (p2 != op || n2 != on) return fail("in place differs", nt, nb);
+      if (lum::skin_host(p.data(), n.data(), ids.data(), w.data(), nt, bones.data(), nb, nullptr, nullptr, nullptr, nullptr)) return fail("refused without outputs", nt, nb);
+      // refused: an id one beyond the palette, no bones, too many
+      ids[4 * (corners - 1) + 3] = (uint16_t) nb;
+      std::vector<float> untouched = op;
+      if (!lum::skin_host(p.data(), n.data(), ids.data(), w.data(), nt, bones.data(), nb, op.data(), on.data(), packed.data(), nullptr)) return fail("an id beyond the palette was taken", nt, nb);
+      if (untouched != op) return fail("a refused call wrote", nt, nb);
+      ids[4 * (corners - 1) + 3] = 0;
+      if (!lum::skin_host(p.data(), n.data(), ids.data(), w.data(), nt, bones.data(), 0, op.data(), on.data(), packed.data(), nullptr)) return fail("no bones taken", nt, nb);
+      if (!lum::skin_host(p.data(), n.data(), ids.data(), w.data(), nt, bones.data(), 1025, op.data(), on.data(), packed.data(), nullptr)) return fail("1025 bones taken", nt, nb);
+      // a palette that overflows is counted, not a fault
+      for (float& x : bones) x *= 3e38f;
+      if (lum::skin_host(p.data(), n.data(), ids.data(), w.data(), nt, bones.data(), nb, op.data(), on.data(), packed.data(), &bad) || bad == 0) return fail("an overflowing palette went unnoticed", nt, nb);
+    }
+  std::printf("mesh_skin_check: ok\n");
+  return 0;
+}

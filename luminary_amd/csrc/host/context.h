@@ -58,7 +58,7 @@ struct LumContext {
   uint32_t refit_mode = 0;                   // lumc_set_mesh_refit
   float refit_max_cost_growth = 0.0f;
   LumMeshRefitStats refit_stats{};
-  // LUMC_DIRTY_INSTANCE_TRANSFORMS updates (instance_update.hip; scene_device.hip update_instance_transforms)
+  // LUMC_DIRTY_INSTANCE_TRANSFORMS updates (instance_update.hip; scene_device.hip instance_boxes, ensure_resident_layout, build_top_level)
   InstanceUpdate instance_update;            // the resident layout's bookkeeping and the device path's scratch
   std::vector<uint32_t> instance_mesh_ids;   // of the scene on the device: such an update must bring the same
   uint32_t instance_update_mode = 0;         // lumc_set_instance_update
@@ -72,12 +72,6 @@ struct LumContext {
   std::map<uint32_t, MeshSkin> mesh_skin;    // by mesh; dropped with the meshes
   DeviceBuffer<uint32_t> d_skin_flags;       // one word of kSkinFlag* bits per launch of an update
   LumMeshSkinStats skin_stats{};
-  struct SkinUpdate {                        // of the scene update that is running (scene_update resets it)
-    bool done = false;                       // the skinning step ran: a fallback that takes the other path does not run it again
-    bool view_uploaded = false;              // the vertex arrays came from the view: the hashes that find moved meshes run
-    std::vector<uint32_t> moved;             // the meshes a new pose was applied to: moved, whatever the hashes say
-    bool is_moved(uint32_t m) const { for (uint32_t x : moved) if (x == m) return true; return false; }
-  } skin_update;
   std::vector<uint32_t> sky_lut_key;  // the sky parameters the two sky tables were generated from
   DeviceBuffer<float> d_bridge_lut;   // the bridge sampler's vertex-count table (context-owned: scene.bridge_lut points here while bridges are possible)
   std::vector<float> bridge_lut_host; // its content, to notice a caller that hands over another table

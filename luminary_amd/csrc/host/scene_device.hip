@@ -17,8 +17,26 @@
 #include "../../../include/lum_core.h"
 #include "../device/kernels_scene.h"
 #include "context.h"
+#include "update_plan.h"
 
 namespace {
+
+// Wall time since it was made, in seconds (`t = Stopwatch{}` starts it again).
+struct Stopwatch {
+  std::chrono::steady_clock::time_point start = std::chrono::steady_clock::now();
+  double seconds() const { return std::chrono::duration<double>(std::chrono::steady_clock::now() - start).count(); }
+};
+
+// What the stats of an update say about that update alone, before it runs; the counts since the context was created stay.
+void reset_update(LumMeshRefitStats& st) {
+  st.last_refits = st.last_rebuilds = 0; st.max_cost_growth = st.seconds = st.seconds_upload = st.seconds_refit = st.seconds_rebuild = st.seconds_assemble = 0.0;
+  st.seconds_hash = st.seconds_download = st.seconds_lights = 0.0;
+}
+void reset_update(LumResidentRefitStats& rs) {
+  rs.last_meshes = rs.last_launches = 0; rs.last_bytes_downloaded = 0;
+  rs.seconds = rs.seconds_upload = rs.seconds_hash = rs.seconds_refit = rs.seconds_cost = rs.seconds_top_level = 0.0;
+}
+void reset_update(LumInstanceUpdateStats& st) { st.seconds = st.seconds_relayout = st.seconds_upload = st.seconds_boxes = st.seconds_build = st.seconds_leaves = 0.0; }
 
 // ---- the process's bottom-level trees by what they were built from: the mesh's triangles (two 64-bit hashes of the vertex words, chunk by chunk so that the
 // value does not depend on the number of threads), the builder asked for and every LUM_* variable of the environment (the builders' knobs) ----
@@ -116,10 +134,22 @@ void free_scene(LumContext* ctx) {
   ctx->has_scene = false;
 }
 
+// Mesh m's tree as a copy private to this context, made from the held one if it has none: what a refit writes (the shared, cached tree is never written, and the
+// cache never sees this one). Becomes the held tree when the caller says so (ctx->mesh_bvh[m] = ctx->mesh_refit[m].own).
+MeshTree& private_tree_of(LumContext* ctx, size_t m) {
+  MeshRefit& mr = ctx->mesh_refit[m];
+  if (!mr.own || mr.own.get() != ctx->mesh_bvh[m].get()) {
+    const Bvh4& held = ctx->mesh_bvh[m]->bvh;
+    mr.own = std::make_shared<MeshTree>();
+    mr.own->bvh.prims = held.prims; mr.own->bvh.max_depth = held.max_depth; mr.own->built_on_gpu = ctx->mesh_bvh[m]->built_on_gpu;
+    mr.own->bvh.nodes = held.nodes;
+  }
+  return *mr.own;
+}
+
 // Host copies after refits in the resident node array (refit_in_place below): ctx->mesh_bvh[m] of a mesh marked stale holds the boxes of earlier vertices, and a
 // tree assembled or laid out from them would lose hits. Every reader of those nodes calls this first: the mesh part of the node array comes down, the box floats
-// go through the layout's slot map into a tree private to this context (created as refit_mesh_trees creates it: the shared, cached tree is never written), the mark
-// goes. Needs the layout the refits ran in: whoever drops it calls this before.
+// go through the layout's slot map into the mesh's private tree (private_tree_of), the mark goes. Needs the layout the refits ran in: whoever drops it calls this before.
 int restore_stale_meshes(LumContext* ctx) {
   if (!ctx->stale_meshes) return 0;
   const ResidentRefit& rr = ctx->resident_refit;
@@ -134,16 +164,11 @@ int restore_stale_meshes(LumContext* ctx) {
     MeshRefit& mr = ctx->mesh_refit[m];
     if (!mr.stale) continue;
     const std::vector<uint32_t>& slots = rr.mesh_slots[m];
-    const Bvh4& held = ctx->mesh_bvh[m]->bvh;
-    if (slots.size() != held.nodes.size()) { ctx->error = "the resident layout's slot map does not fit the mesh's tree"; return 1; }
-    if (!mr.own || mr.own.get() != ctx->mesh_bvh[m].get()) {
-      mr.own = std::make_shared<MeshTree>();
-      mr.own->bvh.prims = held.prims; mr.own->bvh.max_depth = held.max_depth; mr.own->built_on_gpu = ctx->mesh_bvh[m]->built_on_gpu;
-      mr.own->bvh.nodes = held.nodes;
-    }
+    if (slots.size() != ctx->mesh_bvh[m]->bvh.nodes.size()) { ctx->error = "the resident layout's slot map does not fit the mesh's tree"; return 1; }
+    Bvh4& own = private_tree_of(ctx, m).bvh;
     for (size_t i = 0; i < slots.size(); i++) {
       if (slots[i] < rr.capacity || slots[i] - rr.capacity >= rr.mesh_nodes) { ctx->error = "the resident layout's slot map points outside the mesh part"; return 1; }
-      std::memcpy(&mr.own->bvh.nodes[i], &nodes[slots[i] - rr.capacity], offsetof(Bvh4Node, child));  // the 24 box floats; the child words stay relative to the mesh
+      std::memcpy(&own.nodes[i], &nodes[slots[i] - rr.capacity], offsetof(Bvh4Node, child));  // the 24 box floats; the child words stay relative to the mesh
     }
     ctx->mesh_bvh[m] = mr.own;
     mr.stale = false;
@@ -250,9 +275,14 @@ static int build_particle_tree(LumContext* ctx, const LumDeviceSceneView* v, Dev
 // ---- the scene on the device, part by part (scene_update below runs the parts in this order). A part frees what it allocated before; a part that is not
 // dirty keeps its device arrays and the fields of ctx->scene that point at them. ----
 static uint32_t total_triangles(const LumDeviceSceneView* v) { return v->num_meshes ? v->mesh_tri_offset[v->num_meshes] : 0; }
+static bool scene_too_large(LumContext* ctx, const LumDeviceSceneView* v, size_t num_nodes) {
+  if (total_triangles(v) < (1u << 28) && num_nodes < (1u << 25)) return false;
+  ctx->error = "scene too large for 28-bit leaf ranges / 32-bit node offsets";
+  return true;
+}
 
 // The meshes' vertex arrays. The traversal triangles stay: new meshes bring new ones (scene_update has released them, update_scene_tree uploads them), moved
-// vertices are written into the ones that are there (refit_mesh_trees).
+// vertices are written into the ones that are there (refit_mesh_copies, refit_in_place).
 static int update_mesh_arrays(LumContext* ctx, const LumDeviceSceneView* v) {
   DeviceScene& sc = ctx->scene;
   SceneArrays::Mesh& a = ctx->arrays.mesh;
@@ -362,12 +392,12 @@ static int build_mesh_trees(LumContext* ctx, const LumDeviceSceneView* v, std::v
     const float* vertices = v->vertices + (size_t) t0 * 12;
     std::vector<Aabb> tri_boxes(nt);
     ctx->mesh_box[m] = mesh_triangle_boxes(vertices, nt, tri_boxes.data());
-    const auto t_build = std::chrono::steady_clock::now();
+    const Stopwatch t_build;
     const MeshTreeKey key = mesh_tree_key(vertices, nt, ctx->bvh_builder);
     std::shared_ptr<const MeshTree> tree = cached_or_built_mesh_tree(ctx, key, tri_boxes.data(), nt);
     if (!tree) return 1;
     ctx->bvh_meshes_by_builder[tree->built_on_gpu ? 1 : 0]++;
-    ctx->bvh_build_seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t_build).count();
+    ctx->bvh_build_seconds += t_build.seconds();
     fill_mesh_tris(vertices, t0, tree->bvh.prims.data(), nt, blas_tris.data() + t0);
     ctx->mesh_bvh[m] = std::move(tree);
     ctx->mesh_refit[m].fit_hash[0] = key.h0; ctx->mesh_refit[m].fit_hash[1] = key.h1;
@@ -381,16 +411,11 @@ static bool skin_posed(const LumContext* ctx, uint32_t m) {
   return it != ctx->mesh_skin.end() && it->second.posed;
 }
 
-// The skinning step of an update that touches vertices, once per update, after the vertex arrays are in place and before anything reads them: every pending
-// palette goes up and k_skin_mesh writes its mesh's range of the scene's vertices (those meshes are moved: ctx->skin_update.moved); after an upload of the vertex
+// The skinning step of an update that touches vertices (find_moved_meshes runs it, once), after the vertex arrays are in place and before anything reads them: every
+// pending palette goes up and k_skin_mesh writes its mesh's range of the scene's vertices (those meshes are moved: *posed, ascending); after an upload of the vertex
 // arrays from the view (view_uploaded) every other bound mesh that has been posed is written again from the palette it holds - the same bits as before the upload,
 // so its tree still fits. One launch per mesh. Then the launches' flag words come back: a posed position that is not finite fails the update.
-static int skin_meshes(LumContext* ctx, bool view_uploaded) {
-  using clock = std::chrono::steady_clock;
-  auto since = [](clock::time_point t) { return std::chrono::duration<double>(clock::now() - t).count(); };
-  LumContext::SkinUpdate& su = ctx->skin_update;
-  if (su.done) return 0;
-  su.done = true; su.view_uploaded = view_uploaded;
+static int skin_meshes(LumContext* ctx, bool view_uploaded, std::vector<uint32_t>* posed) {
   std::vector<uint32_t> jobs;
   for (const auto& kv : ctx->mesh_skin)
     if (!kv.second.pending.empty() || (view_uploaded && kv.second.posed)) jobs.push_back(kv.first);
@@ -406,7 +431,7 @@ static int skin_meshes(LumContext* ctx, bool view_uploaded) {
       return 1;
     }
   }
-  const auto t_all = clock::now();
+  const Stopwatch t_all;
   if (ctx->d_skin_flags.count() < jobs.size()) HIP_TRY(ctx, ctx->d_skin_flags.resize(jobs.size()));
   HIP_TRY(ctx, hipMemset(ctx->d_skin_flags.get(), 0, sizeof(uint32_t) * jobs.size()));
   for (uint32_t m : jobs) {
@@ -416,16 +441,16 @@ static int skin_meshes(LumContext* ctx, bool view_uploaded) {
     st.last_bytes_uploaded += sizeof(float) * skin.pending.size();
   }
   HIP_TRY(ctx, hipDeviceSynchronize());
-  st.seconds_upload = since(t_all);
-  const auto t_skin = clock::now();
+  st.seconds_upload = t_all.seconds();
+  const Stopwatch t_skin;
   for (size_t j = 0; j < jobs.size(); j++) {
     HIP_TRY(ctx, mesh_skin_launch(ctx->mesh_skin[jobs[j]], vertices.get() + 3 * (size_t) ctx->mesh_tri_offset[jobs[j]], ctx->d_skin_flags.get() + j));
     st.last_launches++;
   }
   std::vector<uint32_t> flags(jobs.size());
   HIP_TRY(ctx, hipMemcpy(flags.data(), ctx->d_skin_flags.get(), sizeof(uint32_t) * jobs.size(), hipMemcpyDeviceToHost));  // (waits for the launches)
-  st.seconds_skin = since(t_skin);
-  st.seconds = since(t_all);
+  st.seconds_skin = t_skin.seconds();
+  st.seconds = t_all.seconds();
   for (size_t j = 0; j < jobs.size(); j++) {
     if (flags[j] & kSkinFlagBadBone) { ctx->error = "lumc_scene_update: mesh " + std::to_string(jobs[j]) + ": a bone id beyond the palette reached the skinning kernel"; return 1; }
     if (flags[j] & kSkinFlagNotFinite) { ctx->error = "lumc_scene_update: mesh " + std::to_string(jobs[j]) + ": the pose gives a position that is not finite"; return 1; }
@@ -434,7 +459,7 @@ static int skin_meshes(LumContext* ctx, bool view_uploaded) {
     MeshSkin& skin = ctx->mesh_skin[m];
     if (skin.pending.empty()) continue;
     skin.pending.clear(); skin.posed = true;
-    su.moved.push_back(m);
+    posed->push_back(m);
     st.poses++; st.last_meshes++;
   }
   return 0;
@@ -449,51 +474,75 @@ static int download_posed_vertices(LumContext* ctx, uint32_t t0, uint32_t nt, st
   return 0;
 }
 
-// LUMC_DIRTY_MESH_POSITIONS: the vertex arrays of the same meshes again - the traversal triangles stay on the device (update_mesh_arrays) -, then
-// every mesh whose vertices differ from those its held tree was fitted to gets a tree for them: refitted on the device (bvh_refit.hip; the tree becomes
-// private to this context, the shared one it came from is not touched and the cache never sees the refitted one) or, where the mode, the cost's growth or a
-// tree that cannot be refitted says so, from the cache / the builder like an upload. *rebuilt: a mesh's traversal triangles were written anew (k_tri_opacity).
-// upload_view: the view's vertex arrays are taken over (false: a LUMC_DIRTY_MESH_SKIN update alone - only posed meshes move, the view's vertices are not read).
-static int refit_mesh_trees(LumContext* ctx, const LumDeviceSceneView* v, bool* rebuilt, bool arrays_uploaded = false, bool upload_view = true) {
-  using clock = std::chrono::steady_clock;
-  auto since = [](clock::time_point t) { return std::chrono::duration<double>(clock::now() - t).count(); };
-  DeviceScene& sc = ctx->scene;
+// ---- moved vertices (LUMC_DIRTY_MESH_POSITIONS, LUMC_DIRTY_MESH_SKIN with a pending pose): the meshes that moved are found once, then one of two paths gives
+// each a tree for its vertices - refit_in_place in the resident node array, refit_mesh_copies in copies on the host ----
+struct MovedMeshes {
+  std::vector<uint32_t> meshes;   // ascending
+  std::vector<MeshTreeKey> keys;  // of the view's vertices; zeros for a posed mesh (no host vertices hash to what k_skin_mesh wrote)
+  std::vector<bool> posed;        // moved by a pose: no hash, and the view's vertices of it are never read
+  bool refittable = true;         // every one's tree has one reference per triangle (false - spatial splits -: refit_mesh_copies builds that mesh again)
+  double seconds = 0.0;           // what finding them took, uploads and skinning included: the head of either path's `seconds`
+};
+
+// The front end of both paths: the vertex arrays of the same meshes again - the traversal triangles stay on the device (update_mesh_arrays) -, the skinning step,
+// then the meshes whose vertices differ from those their held tree was fitted to: by a pose, or - among the others, where the view's vertices were taken over -
+// by their hashes. upload_view: the view's vertex arrays are taken over (false: poses alone - only posed meshes move, the view's vertices are not read).
+static int find_moved_meshes(LumContext* ctx, const LumDeviceSceneView* v, bool upload_view, MovedMeshes* out) {
   LumMeshRefitStats& st = ctx->refit_stats;
-  st.last_refits = st.last_rebuilds = 0; st.max_cost_growth = st.seconds = st.seconds_upload = st.seconds_refit = st.seconds_rebuild = st.seconds_assemble = 0.0;
-  st.seconds_hash = st.seconds_download = st.seconds_lights = 0.0;
-  *rebuilt = false;
-  if (restore_stale_meshes(ctx)) return 1;
+  reset_update(st);
   if (ctx->mesh_bvh.size() != v->num_meshes || ctx->mesh_refit.size() != v->num_meshes || ctx->mesh_tri_offset.size() != (size_t) v->num_meshes + 1 ||
       std::memcmp(ctx->mesh_tri_offset.data(), v->mesh_tri_offset, sizeof(uint32_t) * ((size_t) v->num_meshes + 1)) != 0) {
     ctx->error = "lumc_scene_update: LUMC_DIRTY_MESH_POSITIONS with other meshes or triangle counts than the scene on the device";
     return 1;
   }
-  const auto t_all = clock::now();
-  BvhTri* d_tris = ctx->arrays.mesh.blas_tris.get();
-  if (!d_tris) { ctx->error = "lumc_scene_update: the scene on the device has no traversal triangles"; return 1; }
-  if (!arrays_uploaded && upload_view && update_mesh_arrays(ctx, v)) return 1;  // (a fallback from refit_in_place has uploaded them)
+  const Stopwatch t_all;
+  if (!ctx->arrays.mesh.blas_tris.get()) { ctx->error = "lumc_scene_update: the scene on the device has no traversal triangles"; return 1; }
+  if (upload_view && update_mesh_arrays(ctx, v)) return 1;
   HIP_TRY(ctx, hipDeviceSynchronize());
-  st.seconds_upload = since(t_all);
-  if (skin_meshes(ctx, upload_view)) return 1;  // (once per update: that fallback has run it)
-  const LumContext::SkinUpdate& su = ctx->skin_update;
-  std::vector<float> posed_vertices;
+  st.seconds_upload = t_all.seconds();
+  std::vector<uint32_t> posed;
+  if (skin_meshes(ctx, upload_view, &posed)) return 1;
   for (uint32_t m = 0; m < v->num_meshes; m++) {
     const uint32_t t0 = v->mesh_tri_offset[m], nt = v->mesh_tri_offset[m + 1] - t0;
     if (nt == 0) continue;
-    const bool posed = su.is_moved(m);  // moved by a pose: no hash, and the view's vertices of it are never read
-    if (!posed && (!su.view_uploaded || skin_posed(ctx, m))) continue;
-    const float* vertices = v->vertices + (size_t) t0 * 12;
-    MeshRefit& mr = ctx->mesh_refit[m];
+    const bool by_pose = std::binary_search(posed.begin(), posed.end(), m);
+    if (!by_pose && (!upload_view || skin_posed(ctx, m))) continue;
     MeshTreeKey key{};
-    if (!posed) {
-      const auto t_hash = clock::now();
-      key = mesh_tree_key(vertices, nt, ctx->bvh_builder);
-      st.seconds_hash += since(t_hash);
+    if (!by_pose) {
+      const Stopwatch t_hash;
+      key = mesh_tree_key(v->vertices + (size_t) t0 * 12, nt, ctx->bvh_builder);
+      st.seconds_hash += t_hash.seconds();
+      const MeshRefit& mr = ctx->mesh_refit[m];
       if (!mr.fit_to_pose && key.h0 == mr.fit_hash[0] && key.h1 == mr.fit_hash[1]) continue;  // the held tree fits these vertices
     }
+    out->meshes.push_back(m); out->keys.push_back(key); out->posed.push_back(by_pose);
+    if (ctx->mesh_bvh[m]->bvh.prims.size() != nt) out->refittable = false;
+  }
+  out->seconds = t_all.seconds();
+  return 0;
+}
+
+// The moved meshes' trees in copies on the host: refitted on the device (bvh_refit.hip; the tree becomes private to this context, the shared one it came from is
+// not touched and the cache never sees the refitted one) or, where the mode, the cost's growth or a tree that cannot be refitted says so, from the cache / the
+// builder like an upload; scene_update assembles the node array from them. Also what an in-place update that fell back goes on with: the meshes refitted in the
+// resident array come back to the host first. *rebuilt: a mesh's traversal triangles were written anew (k_tri_opacity).
+static int refit_mesh_copies(LumContext* ctx, const LumDeviceSceneView* v, const MovedMeshes& moved, bool* rebuilt) {
+  DeviceScene& sc = ctx->scene;
+  LumMeshRefitStats& st = ctx->refit_stats;
+  *rebuilt = false;
+  if (restore_stale_meshes(ctx)) return 1;
+  const Stopwatch t_all;
+  BvhTri* d_tris = ctx->arrays.mesh.blas_tris.get();
+  std::vector<float> posed_vertices;
+  for (size_t j = 0; j < moved.meshes.size(); j++) {
+    const uint32_t m = moved.meshes[j], t0 = v->mesh_tri_offset[m], nt = v->mesh_tri_offset[m + 1] - t0;
+    const bool posed = moved.posed[j];
+    MeshTreeKey key = moved.keys[j];
+    const float* vertices = v->vertices + (size_t) t0 * 12;
+    MeshRefit& mr = ctx->mesh_refit[m];
     bool build = ctx->refit_mode == 1;
     if (!build) {
-      const auto t_refit = clock::now();
+      const Stopwatch t_refit;
       if (mr.built_cost == 0.0) mr.built_cost = bvh4_cost(ctx->mesh_bvh[m]->bvh);  // (no refit yet: the held tree is the built one)
       if (!mr.plan.nodes) {
         const hipError_t e = refit_plan_create(mr.plan, ctx->mesh_bvh[m]->bvh, nt);
@@ -501,24 +550,20 @@ static int refit_mesh_trees(LumContext* ctx, const LumDeviceSceneView* v, bool* 
         else HIP_TRY(ctx, e);
       }
       if (!build) {
-        if (!mr.own) {
-          mr.own = std::make_shared<MeshTree>();
-          mr.own->bvh.prims = ctx->mesh_bvh[m]->bvh.prims; mr.own->bvh.max_depth = ctx->mesh_bvh[m]->bvh.max_depth; mr.own->built_on_gpu = ctx->mesh_bvh[m]->built_on_gpu;
-          mr.own->bvh.nodes.resize(mr.plan.num_nodes);
-        }
+        MeshTree& own = private_tree_of(ctx, m);
         Aabb box;
         double download = 0.0;
-        HIP_TRY(ctx, refit_run(mr.plan, sc.vertices + 3 * (size_t) t0, d_tris + t0, nullptr, mr.own->bvh.nodes.data(), &box, &download));
+        HIP_TRY(ctx, refit_run(mr.plan, sc.vertices + 3 * (size_t) t0, d_tris + t0, nullptr, own.bvh.nodes.data(), &box, &download));
         st.seconds_download += download;
-        const double growth = mr.built_cost > 0.0 ? bvh4_cost(mr.own->bvh) / mr.built_cost : 1.0;
+        const double growth = mr.built_cost > 0.0 ? bvh4_cost(own.bvh) / mr.built_cost : 1.0;
         st.max_cost_growth = std::max(st.max_cost_growth, growth);
         if (ctx->refit_max_cost_growth > 0.0f && growth > (double) ctx->refit_max_cost_growth) build = true;
         else { ctx->mesh_bvh[m] = mr.own; ctx->mesh_box[m] = box; mesh_boxes_changed(ctx); st.refits++; st.last_refits++; }
       }
-      st.seconds_refit += since(t_refit);
+      st.seconds_refit += t_refit.seconds();
     }
     if (build) {
-      const auto t_build = clock::now();
+      const Stopwatch t_build;
       if (posed) {  // the builder reads host vertices: the posed ones come down (the view's layout), and with them the key of the process's tree cache
         if (download_posed_vertices(ctx, t0, nt, posed_vertices)) return 1;
         vertices = posed_vertices.data();
@@ -537,12 +582,12 @@ static int refit_mesh_trees(LumContext* ctx, const LumDeviceSceneView* v, bool* 
       ctx->mesh_bvh[m] = std::move(tree);
       *rebuilt = true;
       st.rebuilds++; st.last_rebuilds++;
-      st.seconds_rebuild += since(t_build);
+      st.seconds_rebuild += t_build.seconds();
     }
     mr.fit_to_pose = posed;
     mr.fit_hash[0] = posed ? 0 : key.h0; mr.fit_hash[1] = posed ? 0 : key.h1;
   }
-  st.seconds = since(t_all);
+  st.seconds = moved.seconds + t_all.seconds();
   return 0;
 }
 
@@ -557,7 +602,7 @@ static int update_scene_tree(LumContext* ctx, const LumDeviceSceneView* v, bool 
   for (uint32_t m = 0; m < v->num_meshes; m++) mesh_bvh[m] = &ctx->mesh_bvh[m]->bvh;
   const SceneTree tree = assemble_scene_tree(*v, mesh_bvh.data(), ctx->mesh_box.data());
   if (tree.nodes.empty()) { ctx->error = "top-level BVH exceeds 16 levels"; return 1; }
-  if (total_triangles(v) >= (1u << 28) || tree.nodes.size() >= (1u << 25)) { ctx->error = "scene too large for 28-bit leaf ranges / 32-bit node offsets"; return 1; }
+  if (scene_too_large(ctx, v, tree.nodes.size())) return 1;
   // by instance id: the exact flavour's ambient reuse re-tests a ray against a hit's triangle (k_resolve_reuse)
   if (upload(ctx, ctx->arrays.inst.rows, tree.inv_rows.data(), tree.inv_rows.size(), &sc.instance_rows)) return 1;
   ctx->instance_update.resident = false;  // the one place: the node array in assemble_scene_tree's order, not relayout_resident's
@@ -620,7 +665,7 @@ static int relayout_resident(LumContext* ctx, const LumDeviceSceneView* v) {
   std::vector<Bvh4Node> nodes;
   std::vector<uint32_t> mesh_root;
   layout_resident_nodes(*v, mesh_bvh.data(), capacity, nodes, mesh_root, ctx->refit_in_place ? &rr.mesh_slots : nullptr);
-  if (total_triangles(v) >= (1u << 28) || nodes.size() >= (1u << 25)) { ctx->error = "scene too large for 28-bit leaf ranges / 32-bit node offsets"; return 1; }
+  if (scene_too_large(ctx, v, nodes.size())) return 1;
   a.nodes.reset(); a.tlas_leaves.reset(); point_views(sc, a);
   if (upload(ctx, a.nodes, nodes.data(), nodes.size(), &sc.bvh_nodes)) return 1;
   HIP_TRY(ctx, a.tlas_leaves.resize(4 * ((size_t) n + 1)));
@@ -634,50 +679,65 @@ static int relayout_resident(LumContext* ctx, const LumDeviceSceneView* v) {
   return 0;
 }
 
-// One update on the device: the transforms into the array that is there, then rows, boxes, top level and leaf records derived from them in place. *fell_back: the
-// device path could not take this update (fewer than two instances that can be hit, a top level deeper than 16, a failed allocation): nothing the scene points
-// at is left half written that the host path, which the caller runs then, does not replace.
-// layout_only: stops once the scratch and the resident layout are there (refit_in_place, before it refits in that layout: the top level follows in a second call);
-// upload = false: the transforms on the device are the update's (they did not move, or that first call uploaded them).
-static int update_instance_transforms(LumContext* ctx, const LumDeviceSceneView* v, bool* fell_back, bool layout_only = false, bool upload = true) {
-  using clock = std::chrono::steady_clock;
-  auto since = [](clock::time_point t) { return std::chrono::duration<double>(clock::now() - t).count(); };
+// One update of the top level on the device, in three steps: the instances' boxes from the transforms in the array that is there, the resident layout if there is
+// none, then top level and leaf records built in place. The caller sets *fell_back to false first; a step that sets it says that the device path could not take
+// this update (fewer than two instances that can be hit, a top level deeper than 16, a failed allocation): nothing the scene points at is left half written that
+// the host path, which the caller runs then, does not replace.
+struct InstanceBoxes {
+  uint32_t hittable = 0;  // instances that can be hit
+  Aabb world;             // their bounds
+  Stopwatch since_start;  // LumInstanceUpdateStats::seconds runs from here
+};
+
+// Step 1, which starts the update's timers: the moved instances' scratch, the transforms (upload_transforms = false: those on the device are the update's - they
+// did not move, or an earlier step of this update uploaded them), then rows and boxes derived from them.
+static int instance_boxes(LumContext* ctx, const LumDeviceSceneView* v, bool upload_transforms, InstanceBoxes* out, bool* fell_back) {
   DeviceScene& sc = ctx->scene;
   InstanceUpdate& u = ctx->instance_update;
   SceneArrays::Inst& a = ctx->arrays.inst;
   LumInstanceUpdateStats& st = ctx->instance_stats;
-  st.seconds = st.seconds_relayout = st.seconds_upload = st.seconds_boxes = st.seconds_build = st.seconds_leaves = 0.0;
-  *fell_back = false;
+  reset_update(st);
   const uint32_t n = v->num_instances;
   if (n != sc.num_instances || ctx->instance_mesh_ids.size() != n || ctx->mesh_bvh.size() != v->num_meshes || ctx->mesh_box.size() != v->num_meshes ||
       (n && std::memcmp(ctx->instance_mesh_ids.data(), v->instance_mesh_ids, sizeof(uint32_t) * n) != 0)) {
     ctx->error = "lumc_scene_update: LUMC_DIRTY_INSTANCE_TRANSFORMS with another instance count or other mesh ids than the scene on the device";
     return 1;
   }
-  const auto t_all = clock::now();
+  out->since_start = Stopwatch{};
   if (!u.prepared || u.num_instances != n || u.num_meshes != v->num_meshes) {  // (whoever writes ctx->mesh_box drops `prepared`: mesh_boxes_changed)
     u.reset();
     if (instance_update_prepare(u, n, v->num_meshes, ctx->mesh_box.data()) != hipSuccess) { (void) hipGetLastError(); u.reset(); *fell_back = true; return 0; }
   }
-  auto t = clock::now();
-  if (n && upload) HIP_TRY(ctx, hipMemcpy(a.transforms.get(), v->instance_transforms, sizeof(float4) * 2 * (size_t) n, hipMemcpyHostToDevice));
+  Stopwatch t;
+  if (n && upload_transforms) HIP_TRY(ctx, hipMemcpy(a.transforms.get(), v->instance_transforms, sizeof(float4) * 2 * (size_t) n, hipMemcpyHostToDevice));
   HIP_TRY(ctx, hipDeviceSynchronize());
-  st.seconds_upload = since(t);
-  t = clock::now();
-  uint32_t hittable = 0;
-  Aabb world;
-  HIP_TRY(ctx, instance_update_boxes(u, sc.instance_transforms, sc.instance_mesh_ids, sc.mesh_tri_offset, a.rows.get(), &hittable, &world));
-  st.seconds_boxes = since(t);
-  if (hittable < 2) { *fell_back = true; return 0; }  // (before the layout: a scene of one instance never pays for one)
-  if (!u.resident) {
-    t = clock::now();
-    if (relayout_resident(ctx, v)) { (void) hipGetLastError(); ctx->error.clear(); *fell_back = true; return 0; }  // (the host path replaces whatever this left, or fails for the same reason)
-    HIP_TRY(ctx, hipDeviceSynchronize());
-    st.relayouts++;
-    st.seconds_relayout = since(t);
-  }
-  if (layout_only) return 0;
-  t = clock::now();
+  st.seconds_upload = t.seconds();
+  t = Stopwatch{};
+  HIP_TRY(ctx, instance_update_boxes(u, sc.instance_transforms, sc.instance_mesh_ids, sc.mesh_tri_offset, a.rows.get(), &out->hittable, &out->world));
+  st.seconds_boxes = t.seconds();
+  if (out->hittable < 2) *fell_back = true;  // (before the layout: a scene of one instance never pays for one)
+  return 0;
+}
+
+// Step 2: the resident layout exists.
+static int ensure_resident_layout(LumContext* ctx, const LumDeviceSceneView* v, bool* fell_back) {
+  if (ctx->instance_update.resident) return 0;
+  const Stopwatch t;
+  if (relayout_resident(ctx, v)) { (void) hipGetLastError(); ctx->error.clear(); *fell_back = true; return 0; }  // (the host path replaces whatever this left, or fails for the same reason)
+  HIP_TRY(ctx, hipDeviceSynchronize());
+  ctx->instance_stats.relayouts++;
+  ctx->instance_stats.seconds_relayout = t.seconds();
+  return 0;
+}
+
+// Step 3: the top level over the boxes into [0, C) of the node array, the leaf records, the scene's counts.
+static int build_top_level(LumContext* ctx, const InstanceBoxes& boxes, bool* fell_back) {
+  DeviceScene& sc = ctx->scene;
+  InstanceUpdate& u = ctx->instance_update;
+  SceneArrays::Inst& a = ctx->arrays.inst;
+  LumInstanceUpdateStats& st = ctx->instance_stats;
+  const uint32_t hittable = boxes.hittable;
+  Stopwatch t;
   uint32_t num_nodes = 0, depth = 0;
   Bvh4Node* d_nodes = a.nodes.get();  // (after the layout, which replaces the array)
   if (!build_bvh4_sah_device(u.dense_boxes.get(), hittable, 1, 16, d_nodes, u.capacity, u.prims.get(), &num_nodes, &depth)) {
@@ -685,109 +745,76 @@ static int update_instance_transforms(LumContext* ctx, const LumDeviceSceneView*
     *fell_back = true;
     return 0;
   }
-  st.seconds_build = since(t);
-  t = clock::now();
+  st.seconds_build = t.seconds();
+  t = Stopwatch{};
   HIP_TRY(ctx, instance_update_leaves(u, hittable, sc.instance_rows, sc.instance_mesh_ids, a.tlas_leaves.get(), d_nodes, num_nodes, std::max(num_nodes, u.tlas_nodes)));
   HIP_TRY(ctx, hipDeviceSynchronize());
-  st.seconds_leaves = since(t);
+  st.seconds_leaves = t.seconds();
   u.tlas_nodes = num_nodes;
   sc.tlas_num_nodes = num_nodes;
   sc.tlas_num_leaves = hittable + 1u;  // (one of padding)
   ctx->first_leaf_identity = false;    // (two instances or more: never asked)
-  std::memcpy(ctx->sort.world_lo, world.lo, sizeof(ctx->sort.world_lo)); std::memcpy(ctx->sort.world_hi, world.hi, sizeof(ctx->sort.world_hi));
+  std::memcpy(ctx->sort.world_lo, boxes.world.lo, sizeof(ctx->sort.world_lo)); std::memcpy(ctx->sort.world_hi, boxes.world.hi, sizeof(ctx->sort.world_hi));
   ctx->bvh_stats[0] = u.mesh_nodes;
   ctx->bvh_stats[2] = num_nodes;
   st.device_updates++;
   st.tlas_nodes = num_nodes; st.tlas_depth = depth; st.tlas_capacity = u.capacity; st.hittable = hittable;
-  st.seconds = since(t_all);
+  st.seconds = boxes.since_start.seconds();
   return 0;
 }
 
-// ---- LUMC_DIRTY_MESH_POSITIONS where the nodes live (lum_core.h lumc_set_mesh_refit_in_place; bvh_refit.hip) ----
-// The mesh part of such an update: the vertex arrays, the meshes that moved (by their hashes), then - in the resident layout, laid out first if there is none -
-// their triangle boxes, their node boxes in [C, C + M), their root boxes into the moved instances' scratch and their costs. No node leaves or enters the device;
-// the host's copies of the moved meshes' nodes become stale (restore_stale_meshes). The top level follows in scene_update (update_instance_transforms).
-// *fell_back: this update takes refit_mesh_trees' path instead (a moved mesh that cannot be refitted, fewer than two instances that can be hit, a failed
-// allocation or layout, a cost growth beyond the threshold); the vertex arrays are uploaded, the context is consistent: nothing else was written, or what was
-// written in place is marked stale.
-static int refit_in_place(LumContext* ctx, const LumDeviceSceneView* v, bool* fell_back, bool upload_view = true) {
-  using clock = std::chrono::steady_clock;
-  auto since = [](clock::time_point t) { return std::chrono::duration<double>(clock::now() - t).count(); };
+// ---- moved vertices where the nodes live (lum_core.h lumc_set_mesh_refit_in_place; bvh_refit.hip) ----
+// The mesh part of such an update, for the meshes find_moved_meshes found: in the resident layout, laid out first if there is none (steps 1 and 2 above), their
+// triangle boxes, their node boxes in [C, C + M), their root boxes into the moved instances' scratch and their costs. No node leaves or enters the device; the
+// host's copies of the moved meshes' nodes become stale (restore_stale_meshes). The top level follows in scene_update (steps 1 and 3).
+// *fell_back: this update takes refit_mesh_copies' path instead (a moved mesh that cannot be refitted, fewer than two instances that can be hit, a failed
+// allocation or layout, a cost growth beyond the threshold); the context is consistent: nothing was written, or what was written in place is marked stale.
+static int refit_in_place(LumContext* ctx, const LumDeviceSceneView* v, const MovedMeshes& moved, bool* fell_back) {
   DeviceScene& sc = ctx->scene;
   InstanceUpdate& u = ctx->instance_update;
   ResidentRefit& rr = ctx->resident_refit;
   LumMeshRefitStats& st = ctx->refit_stats;
   LumResidentRefitStats& rs = ctx->resident_stats;
-  st.last_refits = st.last_rebuilds = 0; st.max_cost_growth = st.seconds = st.seconds_upload = st.seconds_refit = st.seconds_rebuild = st.seconds_assemble = 0.0;
-  st.seconds_hash = st.seconds_download = st.seconds_lights = 0.0;
-  rs.last_meshes = rs.last_launches = 0; rs.last_bytes_downloaded = 0;
-  rs.seconds = rs.seconds_upload = rs.seconds_hash = rs.seconds_refit = rs.seconds_cost = rs.seconds_top_level = 0.0;
+  reset_update(rs);
+  rs.seconds_upload = st.seconds_upload; rs.seconds_hash = st.seconds_hash;
   *fell_back = false;
-  if (ctx->mesh_bvh.size() != v->num_meshes || ctx->mesh_refit.size() != v->num_meshes || ctx->mesh_tri_offset.size() != (size_t) v->num_meshes + 1 ||
-      std::memcmp(ctx->mesh_tri_offset.data(), v->mesh_tri_offset, sizeof(uint32_t) * ((size_t) v->num_meshes + 1)) != 0) {
-    ctx->error = "lumc_scene_update: LUMC_DIRTY_MESH_POSITIONS with other meshes or triangle counts than the scene on the device";
-    return 1;
-  }
-  const auto t_all = clock::now();
-  BvhTri* d_tris = ctx->arrays.mesh.blas_tris.get();
-  if (!d_tris) { ctx->error = "lumc_scene_update: the scene on the device has no traversal triangles"; return 1; }
-  if (upload_view && update_mesh_arrays(ctx, v)) return 1;  // (a LUMC_DIRTY_MESH_SKIN update alone: the arrays stay, only posed meshes move)
-  HIP_TRY(ctx, hipDeviceSynchronize());
-  rs.seconds_upload = st.seconds_upload = since(t_all);
-  if (skin_meshes(ctx, upload_view)) return 1;
-  const LumContext::SkinUpdate& su = ctx->skin_update;
-  // the meshes that moved: by a pose, or - among the others, where the view's vertices were taken over - by their hashes
-  auto t = clock::now();
-  std::vector<uint32_t> moved;
-  std::vector<MeshTreeKey> keys;
-  for (uint32_t m = 0; m < v->num_meshes; m++) {
-    const uint32_t t0 = v->mesh_tri_offset[m], nt = v->mesh_tri_offset[m + 1] - t0;
-    if (nt == 0) continue;
-    const bool posed = su.is_moved(m);
-    if (!posed && (!su.view_uploaded || skin_posed(ctx, m))) continue;
-    MeshTreeKey key{};
-    if (!posed) {
-      key = mesh_tree_key(v->vertices + (size_t) t0 * 12, nt, ctx->bvh_builder);
-      if (!ctx->mesh_refit[m].fit_to_pose && key.h0 == ctx->mesh_refit[m].fit_hash[0] && key.h1 == ctx->mesh_refit[m].fit_hash[1]) continue;  // the held tree fits these vertices
-    }
-    if (ctx->mesh_bvh[m]->bvh.prims.size() != nt) { *fell_back = true; return 0; }  // spatial splits: the other path builds it
-    moved.push_back(m); keys.push_back(key);
-  }
-  rs.seconds_hash = st.seconds_hash = su.view_uploaded ? since(t) : 0.0;
-  t = clock::now();
+  if (!moved.refittable) { *fell_back = true; return 0; }  // spatial splits: the other path builds that mesh
+  const Stopwatch t;
   // the layout, and the moved instances' scratch with the meshes' boxes in it
   if (!u.resident || !u.prepared || u.num_instances != v->num_instances || u.num_meshes != v->num_meshes || rr.mesh_slots.size() != v->num_meshes) {
     if (u.resident && rr.mesh_slots.size() != v->num_meshes) {  // laid out while the switch was off: once more, for the slot map
       if (restore_stale_meshes(ctx)) return 1;
       u.resident = false;
     }
-    if (update_instance_transforms(ctx, v, fell_back, true)) return 1;
+    InstanceBoxes boxes;
+    if (instance_boxes(ctx, v, true, &boxes, fell_back)) return 1;
+    if (!*fell_back && ensure_resident_layout(ctx, v, fell_back)) return 1;
     if (*fell_back) return 0;
     if (!u.resident || !u.prepared || rr.mesh_slots.size() != v->num_meshes) { *fell_back = true; return 0; }
   }
-  if (moved.empty()) { rs.seconds = since(t_all); st.seconds = rs.seconds; return 0; }  // (nothing to refit: the top level alone)
+  if (moved.meshes.empty()) { rs.seconds = st.seconds = moved.seconds + t.seconds(); return 0; }  // (nothing to refit: the top level alone)
   // everything that can fail, before a node is written
   if (rr.mesh.size() != v->num_meshes) { rr.mesh.clear(); rr.mesh.resize(v->num_meshes); rr.batch.clear(); }
-  for (uint32_t m : moved) {
+  for (uint32_t m : moved.meshes) {
     MeshRefit& mr = ctx->mesh_refit[m];
     if (mr.built_cost == 0.0) mr.built_cost = bvh4_cost(ctx->mesh_bvh[m]->bvh);  // (no refit yet: the held tree is the built one, and not stale)
     if (rr.mesh[m].slots) continue;
     const hipError_t e = resident_mesh_create(rr.mesh[m], ctx->mesh_bvh[m]->bvh, v->mesh_tri_offset[m + 1] - v->mesh_tri_offset[m], rr.mesh_slots[m]);
     if (e != hipSuccess) { (void) hipGetLastError(); *fell_back = true; return 0; }
   }
-  if (resident_refit_prepare(rr, moved, v->mesh_tri_offset, u.mesh_nodes) != hipSuccess) { (void) hipGetLastError(); *fell_back = true; return 0; }
+  if (resident_refit_prepare(rr, moved.meshes, v->mesh_tri_offset, u.mesh_nodes) != hipSuccess) { (void) hipGetLastError(); *fell_back = true; return 0; }
   // the refit
-  std::vector<ResidentResult> results(moved.size());
+  std::vector<ResidentResult> results(moved.meshes.size());
   uint32_t launches = 0;
   double seconds[2] = {0.0, 0.0};
-  HIP_TRY(ctx, resident_refit_run(rr, sc.vertices, d_tris, ctx->arrays.inst.nodes.get(), u.capacity, u.mesh_nodes, u.mesh_box.get(), u.num_meshes, results.data(), &launches, seconds));
-  for (uint32_t m : moved) if (!ctx->mesh_refit[m].stale) { ctx->mesh_refit[m].stale = true; ctx->stale_meshes++; }  // from here on the device's nodes are ahead of the host's
+  HIP_TRY(ctx, resident_refit_run(rr, sc.vertices, ctx->arrays.mesh.blas_tris.get(), ctx->arrays.inst.nodes.get(), u.capacity, u.mesh_nodes, u.mesh_box.get(), u.num_meshes, results.data(), &launches, seconds));
+  for (uint32_t m : moved.meshes) if (!ctx->mesh_refit[m].stale) { ctx->mesh_refit[m].stale = true; ctx->stale_meshes++; }  // from here on the device's nodes are ahead of the host's
   rs.seconds_cost = seconds[1];
-  rs.seconds_refit = since(t) - seconds[1];
+  rs.seconds_refit = t.seconds() - seconds[1];
   double max_growth = 0.0;
   bool grown = false;
-  for (size_t j = 0; j < moved.size(); j++) {
-    const MeshRefit& mr = ctx->mesh_refit[moved[j]];
+  for (size_t j = 0; j < moved.meshes.size(); j++) {
+    const MeshRefit& mr = ctx->mesh_refit[moved.meshes[j]];
     const double growth = mr.built_cost > 0.0 ? results[j].cost / mr.built_cost : 1.0;
     max_growth = std::max(max_growth, growth);
     if (ctx->refit_max_cost_growth > 0.0f && growth > (double) ctx->refit_max_cost_growth) grown = true;
@@ -796,18 +823,18 @@ static int refit_in_place(LumContext* ctx, const LumDeviceSceneView* v, bool* fe
     *fell_back = true;
     return 0;
   }
-  for (size_t j = 0; j < moved.size(); j++) {
-    MeshRefit& mr = ctx->mesh_refit[moved[j]];
-    ctx->mesh_box[moved[j]] = results[j].box;  // (u.mesh_box on the device holds it already: `prepared` stays)
-    mr.fit_to_pose = su.is_moved(moved[j]);
-    mr.fit_hash[0] = keys[j].h0; mr.fit_hash[1] = keys[j].h1;  // (zeros for a posed mesh)
+  for (size_t j = 0; j < moved.meshes.size(); j++) {
+    MeshRefit& mr = ctx->mesh_refit[moved.meshes[j]];
+    ctx->mesh_box[moved.meshes[j]] = results[j].box;  // (u.mesh_box on the device holds it already: `prepared` stays)
+    mr.fit_to_pose = moved.posed[j];
+    mr.fit_hash[0] = moved.keys[j].h0; mr.fit_hash[1] = moved.keys[j].h1;  // (zeros for a posed mesh)
     st.refits++; st.last_refits++;
   }
   st.max_cost_growth = max_growth;
   st.seconds_refit = rs.seconds_refit + rs.seconds_cost;
-  rs.last_meshes = (uint32_t) moved.size(); rs.last_launches = launches;
-  rs.last_bytes_downloaded = sizeof(ResidentResult) * moved.size();
-  rs.seconds = st.seconds = since(t_all);
+  rs.last_meshes = (uint32_t) moved.meshes.size(); rs.last_launches = launches;
+  rs.last_bytes_downloaded = sizeof(ResidentResult) * moved.meshes.size();
+  rs.seconds = st.seconds = moved.seconds + t.seconds();
   return 0;
 }
 
@@ -828,20 +855,19 @@ static int update_light_bvh(LumContext* ctx, const LumDeviceSceneView* v) {
   return 0;
 }
 
-constexpr unsigned kDirtyTrianglesRewritten = 1u << 30;  // scene_update's own: a LUMC_DIRTY_MESH_POSITIONS update built a mesh again, its traversal triangles are new
-
 // The counts, then what two kernels derive from the arrays above: k_tri_opacity (needs the materials and blas_tris), k_light_table (needs the counts).
-static int update_counts_and_tables(LumContext* ctx, const LumDeviceSceneView* v, unsigned dirty) {
+// triangles_rewritten: a moved-vertices update built a mesh again, its traversal triangles are new.
+static int update_counts_and_tables(LumContext* ctx, const LumDeviceSceneView* v, const UpdatePlan& plan, bool triangles_rewritten) {
   DeviceScene& sc = ctx->scene;
   const uint32_t total_tris = total_triangles(v);
-  const bool dirty_lights = (dirty & LUMC_DIRTY_LIGHTS) != 0;
+  const bool dirty_lights = plan.lights;
   ctx->bvh_stats[1] = total_tris;
   sc.num_meshes = v->num_meshes; sc.num_instances = v->num_instances; sc.num_materials = v->num_materials; sc.num_lights = v->num_lights;  // (num_textures: update_textures)
-  if (total_tris && (dirty & (LUMC_DIRTY_MESHES | LUMC_DIRTY_MATERIALS | kDirtyTrianglesRewritten))) {  // the triangles' material words: texture id, or whether they stop a visibility ray on their own
+  if (total_tris && plan.tri_opacity(triangles_rewritten)) {  // the triangles' material words: texture id, or whether they stop a visibility ray on their own
     hipLaunchKernelGGL(k_tri_opacity, dim3((total_tris + kBlock - 1) / kBlock), dim3(kBlock), 0, 0, sc, ctx->arrays.mesh.blas_tris.get(), total_tris);
     HIP_TRY(ctx, hipGetLastError());
   }
-  if ((dirty_lights || ((dirty & (LUMC_DIRTY_MATERIALS | LUMC_DIRTY_INSTANCES | LUMC_DIRTY_INSTANCE_TRANSFORMS | LUMC_DIRTY_MESHES)) && sc.light_tri_table)) && sc.light_tree_root && sc.num_lights) {  // the emissive triangles in world space with what their material says, one record per light (load_tri_light_table)
+  if ((dirty_lights || (plan.light_table_inputs() && sc.light_tri_table)) && sc.light_tree_root && sc.num_lights) {  // the emissive triangles in world space with what their material says, one record per light (load_tri_light_table)
     DeviceBuffer<float4>& table = ctx->arrays.lights.tri_table;  // a material edit alone refills the table in place (same lights)
     if (dirty_lights) HIP_TRY(ctx, table.resize(4 * (size_t) sc.num_lights));
     hipLaunchKernelGGL(k_light_table, dim3((sc.num_lights + kBlock - 1) / kBlock), dim3(kBlock), 0, 0, sc, table.get());
@@ -1034,14 +1060,14 @@ static int update_sky_panorama(LumContext* ctx, const LumDeviceSceneView* v) {
 }
 
 // Camera, settings, sky, fog, ocean, clouds, particles: the kernels' scalar arguments and the tables derived from them.
-static int update_constants(LumContext* ctx, const LumDeviceSceneView* v, unsigned dirty) {
+static int update_constants(LumContext* ctx, const LumDeviceSceneView* v, const UpdatePlan& plan) {
   ctx->arrays.constants = {}; point_views(ctx->scene, ctx->arrays.constants);
   if (copy_constants(ctx, v)) return 1;
   if (update_stars(ctx, v)) return 1;
   if (update_cloud_noise(ctx, v)) return 1;
-  if ((dirty & LUMC_DIRTY_PARTICLES) && build_particle_tree(ctx, v, ctx->scene)) return 1;
+  if (plan.particles && build_particle_tree(ctx, v, ctx->scene)) return 1;
   if (update_sky_tables(ctx, v)) return 1;
-  if (update_bsdf_tables(ctx, v, dirty == LUMC_DIRTY_ALL)) return 1;
+  if (update_bsdf_tables(ctx, v, plan.full_upload)) return 1;
   return update_sky_panorama(ctx, v);
 }
 
@@ -1064,90 +1090,71 @@ static int update_bridge_table(LumContext* ctx, const LumDeviceSceneView* v) {
   return 0;
 }
 
-// The scene on the device: the dirty parts, in the order their kernels and uploads depend on. Until the update has gone through the context has no scene.
+// The scene on the device: the plan of this update (update_plan.h), then its parts in the order their kernels and uploads depend on. Until the update has gone
+// through the context has no scene.
 static int scene_update(LumContext* ctx, const LumDeviceSceneView* v, unsigned dirty) {
   ctx->guides_valid = false;  // the denoiser's guides were rendered from the scene as it was
   DeviceScene& sc = ctx->scene;
   if (!v->bluenoise_2d) { ctx->error = "scene has no blue-noise mask"; return 1; }
   if (v->max_ray_depth > 63) { ctx->error = "max_ray_depth exceeds 63 (6-bit field, device_structs.h:9)"; return 1; }
-  if (dirty & LUMC_DIRTY_MESHES) dirty &= ~(unsigned) (LUMC_DIRTY_MESH_POSITIONS | LUMC_DIRTY_MESH_SKIN);  // a full rebuild of the meshes covers moved vertices
-  // LUMC_DIRTY_MESH_SKIN: the meshes with a pending pose move, by the path moved vertices take - but the view's vertex arrays are uploaded only if the caller says they moved too
-  ctx->skin_update = LumContext::SkinUpdate{};
-  const bool upload_view = (dirty & LUMC_DIRTY_MESH_POSITIONS) != 0;
-  if (dirty & LUMC_DIRTY_MESH_SKIN) {
-    bool pending = false;
-    for (const auto& kv : ctx->mesh_skin) pending = pending || !kv.second.pending.empty();
-    dirty &= ~(unsigned) LUMC_DIRTY_MESH_SKIN;
-    if (pending) dirty |= LUMC_DIRTY_MESH_POSITIONS;
-  }
-  // lumc_set_mesh_refit_in_place: moved vertices alone or with moved instances, both modes 0 - the refit happens in the resident node array, the top level follows as for moved instances
-  bool in_place = ctx->refit_in_place && (dirty & LUMC_DIRTY_MESH_POSITIONS) && !(dirty & (LUMC_DIRTY_MESHES | LUMC_DIRTY_INSTANCES)) && ctx->refit_mode == 0 && ctx->instance_update_mode == 0;
-  const bool instances_moved = (dirty & LUMC_DIRTY_INSTANCE_TRANSFORMS) != 0;
-  if (in_place) dirty |= LUMC_DIRTY_INSTANCE_TRANSFORMS;
-  else if (dirty & (LUMC_DIRTY_MESHES | LUMC_DIRTY_MESH_POSITIONS)) dirty |= LUMC_DIRTY_INSTANCES;  // the assembled node array holds the per-mesh trees
-  if (dirty & LUMC_DIRTY_PARTICLES) dirty |= LUMC_DIRTY_CONSTANTS;
-  if (dirty & (LUMC_DIRTY_INSTANCES | LUMC_DIRTY_MESHES)) dirty &= ~(unsigned) LUMC_DIRTY_INSTANCE_TRANSFORMS;  // the instance part covers moved instances
-  const bool moved_by_host = (dirty & LUMC_DIRTY_INSTANCE_TRANSFORMS) && ctx->instance_update_mode == 1;  // mode 1: exactly LUMC_DIRTY_INSTANCES; its time is reported
-  if (moved_by_host) { dirty = (dirty & ~(unsigned) LUMC_DIRTY_INSTANCE_TRANSFORMS) | LUMC_DIRTY_INSTANCES; ctx->instance_stats.seconds = ctx->instance_stats.seconds_relayout = ctx->instance_stats.seconds_upload = ctx->instance_stats.seconds_boxes = ctx->instance_stats.seconds_build = ctx->instance_stats.seconds_leaves = 0.0; }
-  auto host_path_since = [&](std::chrono::steady_clock::time_point t) { if (moved_by_host) ctx->instance_stats.seconds += std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count(); };
-  const bool meshes = (dirty & LUMC_DIRTY_MESHES) != 0, lights = (dirty & LUMC_DIRTY_LIGHTS) != 0;
-  bool instances = (dirty & LUMC_DIRTY_INSTANCES) != 0;
+  bool pose_pending = false;
+  for (const auto& kv : ctx->mesh_skin) pose_pending = pose_pending || !kv.second.pending.empty();
+  UpdatePlan plan = plan_update(dirty, ctx->refit_in_place != 0, ctx->refit_mode, ctx->instance_update_mode, pose_pending);
+  if (plan.moved_by_host) reset_update(ctx->instance_stats);
+  auto host_path_since = [&](const Stopwatch& t) { if (plan.moved_by_host) ctx->instance_stats.seconds += t.seconds(); };
+  auto lights_since = [&](const Stopwatch& t) { if (plan.time_lights) ctx->refit_stats.seconds_lights += t.seconds(); };
   ctx->has_scene = false;
-  if (meshes) { ctx->arrays.mesh = {}; ctx->mesh_skin.clear(); }  // the traversal triangles too; new meshes: the bindings go, the caller binds again
-  if (meshes && update_mesh_arrays(ctx, v)) return 1;
-  bool arrays_uploaded = false;
-  if (in_place) {
-    bool fell_back = false;
-    if (refit_in_place(ctx, v, &fell_back, upload_view)) return 1;
-    if (fell_back) {  // this one update by the other path, as it would have run with the switch off
-      ctx->resident_stats.fallbacks++;
-      in_place = false; arrays_uploaded = true;
-      dirty = (dirty & ~(unsigned) LUMC_DIRTY_INSTANCE_TRANSFORMS) | LUMC_DIRTY_INSTANCES;
-      instances = true;
+  if (plan.meshes) { ctx->arrays.mesh = {}; ctx->mesh_skin.clear(); }  // the traversal triangles too; new meshes: the bindings go, the caller binds again
+  if (plan.meshes && update_mesh_arrays(ctx, v)) return 1;
+  bool triangles_rewritten = false;
+  if (plan.positions) {
+    MovedMeshes moved;
+    if (find_moved_meshes(ctx, v, plan.upload_view, &moved)) return 1;
+    if (plan.in_place) {
+      bool fell_back = false;
+      if (refit_in_place(ctx, v, moved, &fell_back)) return 1;
+      if (fell_back) { ctx->resident_stats.fallbacks++; plan.take_copies_path(); }
     }
+    if (!plan.in_place && refit_mesh_copies(ctx, v, moved, &triangles_rewritten)) return 1;
   }
-  if ((dirty & LUMC_DIRTY_MESH_POSITIONS) && !in_place) {
-    bool rebuilt = false;
-    if (refit_mesh_trees(ctx, v, &rebuilt, arrays_uploaded, upload_view)) return 1;
-    if (rebuilt) dirty |= kDirtyTrianglesRewritten;
-  }
-  const auto t_arrays = std::chrono::steady_clock::now();
-  if (instances && update_instance_arrays(ctx, v)) return 1;
+  const Stopwatch t_arrays;
+  if (plan.instances && update_instance_arrays(ctx, v)) return 1;
   host_path_since(t_arrays);
-  if ((dirty & LUMC_DIRTY_MATERIALS) && update_materials(ctx, v)) return 1;
-  const bool time_lights = (dirty & LUMC_DIRTY_MESH_POSITIONS) != 0;
-  auto lights_since = [&](std::chrono::steady_clock::time_point t) { if (time_lights) ctx->refit_stats.seconds_lights += std::chrono::duration<double>(std::chrono::steady_clock::now() - t).count(); };
-  auto t_lights = std::chrono::steady_clock::now();
-  if (lights && update_light_tree(ctx, v)) return 1;
+  if (plan.materials && update_materials(ctx, v)) return 1;
+  Stopwatch t_lights;
+  if (plan.lights && update_light_tree(ctx, v)) return 1;
   lights_since(t_lights);
   if (!sc.bluenoise_2d && upload(ctx, ctx->arrays.bluenoise_2d, v->bluenoise_2d, 65536, &sc.bluenoise_2d)) return 1;
-  if ((dirty & LUMC_DIRTY_TEXTURES) && update_textures(ctx, v)) return 1;
+  if (plan.textures && update_textures(ctx, v)) return 1;
   size_t num_nodes = 0;
-  const auto t_assemble = std::chrono::steady_clock::now();
-  if (instances && (update_scene_tree(ctx, v, meshes, &num_nodes) || update_ray_kernel_lds(ctx, num_nodes))) return 1;
-  if (moved_by_host) { HIP_TRY(ctx, hipDeviceSynchronize()); host_path_since(t_assemble); }
-  if (dirty & LUMC_DIRTY_INSTANCE_TRANSFORMS) {
+  const Stopwatch t_assemble;
+  if (plan.instances && (update_scene_tree(ctx, v, plan.meshes, &num_nodes) || update_ray_kernel_lds(ctx, num_nodes))) return 1;
+  if (plan.moved_by_host) { HIP_TRY(ctx, hipDeviceSynchronize()); host_path_since(t_assemble); }
+  if (plan.transforms_on_device) {
     bool fell_back = false;
-    if (update_instance_transforms(ctx, v, &fell_back, false, instances_moved || !in_place)) return 1;
+    InstanceBoxes boxes;
+    if (instance_boxes(ctx, v, plan.instances_moved || !plan.in_place, &boxes, &fell_back)) return 1;  // (in place: the transforms are on the device unless they moved)
+    if (!fell_back && ensure_resident_layout(ctx, v, &fell_back)) return 1;
+    if (!fell_back && build_top_level(ctx, boxes, &fell_back)) return 1;
     if (fell_back) {  // this one update by the host's path, as LUMC_DIRTY_INSTANCES
       if (update_instance_arrays(ctx, v) || update_scene_tree(ctx, v, false, &num_nodes) || update_ray_kernel_lds(ctx, num_nodes)) return 1;  // (update_scene_tree brings meshes refitted in place back to the host first)
       ctx->instance_stats.fallbacks++;
-      ctx->instance_stats.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_assemble).count();
+      ctx->instance_stats.seconds = t_assemble.seconds();
     }
-    if (in_place) {
+    if (plan.in_place) {
       LumResidentRefitStats& rs = ctx->resident_stats;
       if (fell_back) rs.fallbacks++; else rs.updates++;
-      rs.seconds_top_level = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_assemble).count();
+      rs.seconds_top_level = t_assemble.seconds();
       rs.seconds += rs.seconds_top_level;
       rs.last_bytes_downloaded += 28;  // instance_update_boxes: the bounds and the count
     }
   }
-  if (dirty & LUMC_DIRTY_MESH_POSITIONS) ctx->refit_stats.seconds_assemble = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_assemble).count();
-  t_lights = std::chrono::steady_clock::now();
-  if (lights && update_light_bvh(ctx, v)) return 1;
-  if (update_counts_and_tables(ctx, v, dirty)) return 1;
+  if (plan.positions) ctx->refit_stats.seconds_assemble = t_assemble.seconds();
+  t_lights = Stopwatch{};
+  if (plan.lights && update_light_bvh(ctx, v)) return 1;
+  if (update_counts_and_tables(ctx, v, plan, triangles_rewritten)) return 1;
   lights_since(t_lights);
-  if ((dirty & LUMC_DIRTY_CONSTANTS) && update_constants(ctx, v, dirty)) return 1;
+  if (plan.constants && update_constants(ctx, v, plan)) return 1;
   if (update_bridge_table(ctx, v)) return 1;
   // the moon's texture ids follow the texture pool (the host layer appends the two moon textures behind the scene's own): an added texture moves them
   sc.sky_moon_albedo_tex = v->sky_moon_albedo_tex; sc.sky_moon_normal_tex = v->sky_moon_normal_tex;

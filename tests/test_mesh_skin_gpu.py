@@ -269,6 +269,46 @@ def test_a_rebuild_downloads_the_posed_vertices():
         core.close(); host.close(); twin.close()
 
 
+# ---- a fallback in the middle of an in-place update that carries a pose ----
+def test_a_fallback_in_the_middle_of_an_in_place_update_skins_once():
+    """The pose grows its mesh's cost beyond the threshold after the in-place path has refitted both meshes where the nodes live: the update goes on by the
+    other path, from the vertices the one skinning launch wrote. The counter literals are what the commit before the one-front-end refactor gave for this test."""
+    host, twin, core = _small_zoo(), _small_zoo(), _core(in_place=1)
+    try:
+        core.upload(_view(host))
+        ma, mb = _plain_meshes(host, 2)
+        skinned = Skinned(core, host, twin, mb)
+        pa = host.get_mesh(ma)[0]
+        core.set_mesh_refit(0, 1.0 + 1e-6)
+        skinned.pose(1.4, 0.5)
+        for h in (host, twin):
+            h.set_mesh_positions(ma, bend(pa, 0.2, 0.4))
+        before, downloads = _counts(core), core.mesh_skin_stats().rebuild_downloads
+        core.update(_view(host), DIRTY_MESH_POSITIONS | DIRTY_MESH_SKIN | DIRTY_LIGHTS)  # (host's view: mesh a moved, mesh b at rest)
+        stats, refit, after = core.mesh_skin_stats(), core.mesh_refit_stats(), _counts(core)
+        print("fallback: poses %d, last_meshes %d, last_launches %d; refits %d, rebuilds %d, downloads %d, growth %.6f; %s -> %s" % (
+            stats.poses, stats.last_meshes, stats.last_launches, refit.last_refits, refit.last_rebuilds, stats.rebuild_downloads - downloads, refit.max_cost_growth, before, after))
+        assert (stats.poses, stats.last_meshes, stats.last_launches) == (1, 1, 1), "skinning ran once across the fallback"
+        assert after["fallbacks"] == before["fallbacks"] + 1 and after["updates"] == before["updates"]
+        assert refit.max_cost_growth > 1.0 + 1e-6, "the pose must grow the cost beyond the threshold"
+        assert (refit.last_refits, refit.last_rebuilds) == (0, 2) and stats.rebuild_downloads - downloads == 1, "the bend grows mesh a's cost too: both are built again, the posed one from a download"
+        skinned.check("fallback")
+        _against_oracle(core, _view(twin), "fallback")
+        # a mild update without a threshold runs in place again, in a layout of its own
+        core.set_mesh_refit(0, 0.0)
+        skinned.pose(0.3, 0.1)
+        before = after
+        core.update(_view(host), DIRTY_MESH_SKIN | DIRTY_LIGHTS)
+        after = _counts(core)
+        print("in place again: %s -> %s" % (before, after))
+        assert after == {"relayouts": before["relayouts"] + 1, "instance fallbacks": before["instance fallbacks"], "updates": before["updates"] + 1, "fallbacks": before["fallbacks"]}
+        assert core.mesh_skin_stats().poses == 2
+        skinned.check("in place again")
+        _against_oracle(core, _view(twin), "in place again")
+    finally:
+        core.close(); host.close(); twin.close()
+
+
 # ---- lights ----
 def test_a_posed_emitter_with_its_light_arrays():
     host, twin, core = _small_zoo(), _small_zoo(), _core()

@@ -453,6 +453,37 @@ typedef struct LuminaryMeshSkinStats {
   uint64_t host_materialisations;       /* times the host posed a mesh on the CPU because something read it, since the host was created */
 } LuminaryMeshSkinStats;
 LUMINARY_API LuminaryResult luminary_ext_get_mesh_skin_stats(LuminaryHost* host, LuminaryMeshSkinStats* out);
+/* Morph targets / blend shapes: the host takes 4 bytes per target, the devices blend the vertices (include/lum_core.h lumc_mesh_morph_bind).
+ *   luminary_ext_bind_mesh_morph    binds a mesh the host holds to target_count (1 ... 1024) sparse targets, target-major: offsets[target_count + 1] into
+ *                                   corners[E] (a corner is 3 * triangle + 0 ... 2; strictly increasing within a target), delta_positions[3E] and delta_normals[3E]
+ *                                   (NULL: zero). All weights start at 0. While a mesh is bound, luminary_ext_set_mesh_positions on it is refused.
+ *   luminary_ext_set_mesh_weights   target_count (the binding's) finite floats; negative weights and weights above 1 are ordinary. Restarts the integration. Per corner
+ *                                   the entries are added in ascending target order in binary32 (weight * delta, then the add; a weight of 0 skips the entry), and
+ *                                   the normal of a corner something was added to is normalised. A mesh with an emissive triangle is also blended on the host at
+ *                                   once and the light tree rebuilt; for any other mesh the host mesh is brought up to date - by the same function on the CPU,
+ *                                   the same bytes, counted in host_materialisations - only when something reads it, as for a pose. Weights whose result is not
+ *                                   finite fail the next render (LUMINARY_ERROR_CUDA).
+ *   luminary_ext_unbind_mesh_morph  drops the targets.
+ * A mesh has ONE rest shape, whether it is skinned, morphed or both: the first binding of either kind copies the host mesh as it is now; binding the other kind
+ * while one is bound shares that copy; binding a kind again while the other is bound keeps it (for a mesh that holds one kind alone, binding that kind again makes
+ * the current shape the rest, as before). A mesh that holds both is morphed first and the skin poses the result - its un-normalised position and normal - in one
+ * kernel; until its first pose the morph alone shapes it. Unbinding one of two leaves what the other makes of the rest shape; unbinding the last makes the host mesh
+ * the current shape, and plain again.
+ * LUMINARY_ERROR_INVALID_API_ARGUMENT, and nothing changes: a mesh id the host does not have, another triangle count, NULL arrays, target_count 0 or above 1024,
+ * offsets that do not start at 0 or decrease, a corner >= 3 * triangle_count, corners of a target that are not strictly increasing, a delta or a weight that is not
+ * finite, weights or an unbind for a mesh without a morph, another target_count. */
+LUMINARY_API LuminaryResult luminary_ext_bind_mesh_morph(LuminaryHost* host, uint32_t mesh_id, uint32_t triangle_count, uint32_t target_count, const uint32_t* offsets,
+                                                         const uint32_t* corners, const float* delta_positions, const float* delta_normals);
+LUMINARY_API LuminaryResult luminary_ext_unbind_mesh_morph(LuminaryHost* host, uint32_t mesh_id);
+LUMINARY_API LuminaryResult luminary_ext_set_mesh_weights(LuminaryHost* host, uint32_t mesh_id, const float* weights, uint32_t target_count);
+typedef struct LuminaryMeshMorphStats {
+  uint64_t applied, rebuild_downloads;  /* weight sets the main device's context applied / morphed meshes it downloaded for a rebuild, since it was created */
+  uint32_t last_meshes, last_launches;  /* its last update that morphed: meshes with new weights, morph kernels launched */
+  uint64_t last_bytes_uploaded;         /* ... bytes that went up for them */
+  double seconds, seconds_upload, seconds_morph; /* as LumMeshMorphStats (include/lum_core.h) */
+  uint64_t host_materialisations;       /* the counter of LuminaryMeshSkinStats: times the host posed or blended a mesh on the CPU because something read it */
+} LuminaryMeshMorphStats;
+LUMINARY_API LuminaryResult luminary_ext_get_mesh_morph_stats(LuminaryHost* host, LuminaryMeshMorphStats* out);
 /* Converts the current scene to the device format (device_structs.c conversions + light tree build). The view and everything it points
  * to stay valid until the next call or host destruction. Needs no GPU. */
 /* Whether replacing `old` by `input` restarts the integration (camera.c:80-147, settings.c:45-72) or only changes the outputs.

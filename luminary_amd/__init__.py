@@ -189,6 +189,12 @@ class MeshSkinStats(C.Structure):
                 ("seconds", C.c_double), ("seconds_upload", C.c_double), ("seconds_skin", C.c_double), ("host_materialisations", C.c_uint64)]
 
 
+class MeshMorphStats(C.Structure):
+    """LuminaryMeshMorphStats"""
+    _fields_ = [("applied", C.c_uint64), ("rebuild_downloads", C.c_uint64), ("last_meshes", C.c_uint32), ("last_launches", C.c_uint32), ("last_bytes_uploaded", C.c_uint64),
+                ("seconds", C.c_double), ("seconds_upload", C.c_double), ("seconds_morph", C.c_double), ("host_materialisations", C.c_uint64)]
+
+
 class Instance(C.Structure):
     _fields_ = [("id", C.c_uint32), ("mesh_id", C.c_uint32), ("position", Vec3), ("rotation", Vec3), ("scale", Vec3)]
 
@@ -587,6 +593,34 @@ class Host:
         """luminary_ext_get_mesh_skin_stats: the main device's skinning stats and host_materialisations, as a dict."""
         s = MeshSkinStats()
         _call("luminary_ext_get_mesh_skin_stats", self._h, C.byref(s))
+        return {name: getattr(s, name) for name, _ in s._fields_}
+
+    def bind_mesh_morph(self, mesh_id, triangle_count, offsets, corners, delta_positions, delta_normals=None):
+        """luminary_ext_bind_mesh_morph: sparse target-major deltas - offsets [T + 1] into corners [E], delta positions [E, 3], delta normals [E, 3] or None - over the
+        host mesh of triangle_count triangles as it is now (or over the rest shape it shares with a bound skin); all weights 0."""
+        import numpy as np
+        o = np.ascontiguousarray(offsets, dtype=np.uint32).reshape(-1)
+        c = np.ascontiguousarray(corners, dtype=np.uint32).reshape(-1)
+        dp = np.ascontiguousarray(delta_positions, dtype=np.float32).reshape(-1)
+        dn = None if delta_normals is None else np.ascontiguousarray(delta_normals, dtype=np.float32).reshape(-1)
+        assert o.size >= 2 and dp.size == 3 * c.size and (dn is None or dn.size == dp.size) and int(o.max()) <= c.size
+        _call("luminary_ext_bind_mesh_morph", self._h, C.c_uint32(mesh_id), C.c_uint32(triangle_count), C.c_uint32(o.size - 1), o.ctypes.data_as(C.c_void_p),
+              c.ctypes.data_as(C.c_void_p), dp.ctypes.data_as(C.c_void_p), dn.ctypes.data_as(C.c_void_p) if dn is not None else C.c_void_p(0))
+
+    def unbind_mesh_morph(self, mesh_id):
+        """luminary_ext_unbind_mesh_morph: drops the targets; with no skin bound the host mesh becomes the current shape, and plain again."""
+        _call("luminary_ext_unbind_mesh_morph", self._h, C.c_uint32(mesh_id))
+
+    def set_mesh_weights(self, mesh_id, weights):
+        """luminary_ext_set_mesh_weights: weights [T]; the devices blend the bound mesh's vertices and refit its tree."""
+        import numpy as np
+        w = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)
+        _call("luminary_ext_set_mesh_weights", self._h, C.c_uint32(mesh_id), w.ctypes.data_as(C.c_void_p), C.c_uint32(w.size))
+
+    def mesh_morph_stats(self):
+        """luminary_ext_get_mesh_morph_stats: the main device's morph stats and host_materialisations, as a dict."""
+        s = MeshMorphStats()
+        _call("luminary_ext_get_mesh_morph_stats", self._h, C.byref(s))
         return {name: getattr(s, name) for name, _ in s._fields_}
 
     def get_mesh(self, mesh_id):

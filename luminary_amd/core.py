@@ -144,6 +144,51 @@ def skin_host(rest_positions, rest_normals, bone_ids, weights, bones):
     return op, on, pk
 
 
+class MeshMorphStats(C.Structure):
+    """LumMeshMorphStats"""
+    _fields_ = [("applied", C.c_uint64), ("rebuild_downloads", C.c_uint64), ("last_meshes", C.c_uint32), ("last_launches", C.c_uint32), ("last_bytes_uploaded", C.c_uint64),
+                ("seconds", C.c_double), ("seconds_upload", C.c_double), ("seconds_morph", C.c_double)]
+
+
+def _morph_arrays(base_positions, base_normals, offsets, corners, delta_positions, delta_normals):
+    p = np.ascontiguousarray(base_positions, dtype=np.float32).reshape(-1, 9)
+    n = np.ascontiguousarray(base_normals, dtype=np.float32).reshape(-1, 9)
+    o = np.ascontiguousarray(offsets, dtype=np.uint32).reshape(-1)
+    c = np.ascontiguousarray(corners, dtype=np.uint32).reshape(-1)
+    dp = np.ascontiguousarray(delta_positions, dtype=np.float32).reshape(-1, 3)
+    dn = None if delta_normals is None else np.ascontiguousarray(delta_normals, dtype=np.float32).reshape(-1, 3)
+    assert len(p) == len(n), "9 position floats and 9 normal floats per triangle"
+    assert len(o) >= 2 and len(c) == len(dp) and (dn is None or len(dn) == len(dp)) and int(o.max()) <= len(c), "offsets [T + 1] into corners [E], deltas [E, 3]"
+    return p, n, o, c, dp, dn
+
+
+def _addr(a):
+    return C.c_void_p(a.ctypes.data if a is not None and a.size else None)
+
+
+def morph_host(base_positions, base_normals, offsets, corners, delta_positions, delta_normals, weights, bone_ids=None, skin_weights=None, bones=None):
+    """lumc_morph_host, no device needed: the host twin of the morph kernel over triangles of base positions / normals [n, 9], sparse target-major deltas (offsets
+    [T + 1] into corners [E], delta positions [E, 3], delta normals [E, 3] or None) and weights [T]; with bones [b, 12] also bone ids / skin weights [n, 12]: the
+    combined result. Returns (positions [n, 9] float32, normals [n, 9] float32, packed normal words [n, 3] uint32)."""
+    fn = _lib().lumc_morph_host
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32] + [C.c_void_p] * 8 + [C.c_uint32] + [C.c_void_p] * 3
+    p, n, o, c, dp, dn = _morph_arrays(base_positions, base_normals, offsets, corners, delta_positions, delta_normals)
+    w = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)
+    assert len(w) == len(o) - 1, "one weight per target"
+    i = sw = b = None
+    if bones is not None:
+        i = np.ascontiguousarray(bone_ids, dtype=np.uint16).reshape(-1, 12)
+        sw = np.ascontiguousarray(skin_weights, dtype=np.float32).reshape(-1, 12)
+        b = np.ascontiguousarray(bones, dtype=np.float32).reshape(-1, 12)
+        assert len(i) == len(sw) == len(p)
+    op, on, pk = np.zeros_like(p), np.zeros_like(n), np.zeros((len(p), 3), np.uint32)
+    if fn(p.ctypes.data, n.ctypes.data, len(p), len(w), o.ctypes.data, _addr(c), _addr(dp), _addr(dn), w.ctypes.data, _addr(i), _addr(sw), _addr(b), 0 if b is None else len(b),
+          op.ctypes.data, on.ctypes.data, pk.ctypes.data) != 0:
+        raise CoreError("lumc_morph_host refused its arguments (1 ... 1024 targets, offsets from 0 that do not decrease, corners of a target strictly increasing and below 3 n, finite deltas and weights)")
+    return op, on, pk
+
+
 def instance_boxes_probe(view, mesh_boxes, on_gpu=False):
     """lumc_instance_boxes_probe: (rows [n, 3, 4] float32, boxes [n, 6] float32, hittable [n] uint32) of the instances of `view` over the meshes' object-space
     boxes mesh_boxes [num_meshes, 6], by the host's functions or by the device's kernel."""
@@ -623,6 +668,26 @@ class Core:
     def mesh_skin_stats(self):
         out = MeshSkinStats()
         self._call("lumc_mesh_skin_stats", C.byref(out))
+        return out
+
+    def mesh_morph_bind(self, mesh, base_positions, base_normals, offsets, corners, delta_positions, delta_normals=None):
+        """lumc_mesh_morph_bind: base positions / normals [n, 9] and sparse target-major deltas (offsets [T + 1] into corners [E], delta positions / normals [E, 3])
+        of a mesh of the scene on the device become resident, all weights 0."""
+        p, n, o, c, dp, dn = _morph_arrays(base_positions, base_normals, offsets, corners, delta_positions, delta_normals)
+        self._call("lumc_mesh_morph_bind", C.c_uint32(mesh), C.c_void_p(p.ctypes.data), C.c_void_p(n.ctypes.data), C.c_uint32(len(p)), C.c_uint32(len(o) - 1),
+                   C.c_void_p(o.ctypes.data), _addr(c), _addr(dp), _addr(dn))
+
+    def mesh_morph_unbind(self, mesh):
+        self._call("lumc_mesh_morph_unbind", C.c_uint32(mesh))
+
+    def mesh_morph_weights(self, mesh, weights):
+        """lumc_mesh_morph_weights: weights [T]; pending until the next update with DIRTY_MESH_SKIN."""
+        w = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1)
+        self._call("lumc_mesh_morph_weights", C.c_uint32(mesh), C.c_void_p(w.ctypes.data), C.c_uint32(len(w)))
+
+    def mesh_morph_stats(self):
+        out = MeshMorphStats()
+        self._call("lumc_mesh_morph_stats", C.byref(out))
         return out
 
     def mesh_vertices_probe(self, mesh, triangles):

@@ -29,6 +29,7 @@
 #include "loaders.h"
 #include "scene.h"
 #define LUM_SKIN_HOST_ONLY 1  // the host twin's declaration only: this unit touches no device
+#include "mesh_morph.h"
 #include "mesh_skin.h"
 
 extern "C" const unsigned char lum_embedded_bluenoise_2d[];
@@ -40,14 +41,27 @@ struct LuminaryPath { std::string value; };
 
 // A bound mesh (luminary_ext_bind_mesh_skin): the rest pose and the corners' bones, the last pose, and who holds it. The serials are values of the host's
 // skin_serial counter: a context that has seen the counter at a smaller value gets the binding / the pose before it takes the scene.
+// A mesh has ONE rest shape, whichever of the two kinds of binding it holds (luminary_ext_bind_mesh_morph: DESIGN.md section 12): the first binding of either kind
+// copies the host mesh, the other kind shares that copy, and the entry lives until the last of the two is unbound.
 struct HostSkin {
   std::vector<float> rest_positions, rest_normals, weights;
   std::vector<uint16_t> bone_ids;
-  uint32_t bone_count = 0;
+  uint32_t bone_count = 0;        // 0: no skin is bound (then a morph is)
   std::vector<float> palette;     // the last pose, 12 floats per bone (empty: none yet)
   uint64_t bind_serial = 0, pose_serial = 0;
+  // the morph targets as the caller gave them (what a context is bound to) and as the corner-major rows the host twin walks
+  uint32_t target_count = 0;      // 0: no morph is bound
+  std::vector<uint32_t> morph_offsets, morph_corners;
+  std::vector<float> morph_delta_positions, morph_delta_normals;  // (the normals' empty: zero)
+  lum::MorphCsr morph_csr;
+  std::vector<float> morph_weights;  // the last weights, target_count floats (zeros until the first call)
+  uint64_t morph_bind_serial = 0, morph_weights_serial = 0;  // (weights_serial 0: none set yet)
   bool host_current = true;       // HostMesh::positions / normals hold the last pose (false: brought up to date by the host twin before anything reads them)
   bool view_current = true;       // ... and so do the device scene's vertices of the mesh (the contexts never read those of a posed mesh)
+  bool has_skin() const { return bone_count != 0; }
+  bool has_morph() const { return target_count != 0; }
+  bool posed() const { return has_skin() && !palette.empty(); }
+  bool weighted() const { return has_morph() && morph_weights_serial != 0; }
 };
 
 struct LuminaryHost {
@@ -185,16 +199,24 @@ template <typename T> bool change_restarts(const T&, const T&) { return true; } 
 inline bool change_restarts(const LuminaryCamera& in, const LuminaryCamera& old) { return camera_change_restarts(in, old); }
 inline bool change_restarts(const LuminaryRendererSettings& in, const LuminaryRendererSettings& old) { return settings_change_restarts(in, old); }
 
-// ---- skinned meshes: the lazy host mesh ----
-// HostMesh::positions / normals of a posed mesh from the host twin of the devices' kernel (in place: the pointers luminary_ext_get_mesh handed out stay valid).
+// ---- skinned and morphed meshes: the lazy host mesh ----
+// HostMesh::positions / normals of a posed or morphed mesh from the host twin of the devices' kernel (in place: the pointers luminary_ext_get_mesh handed out
+// stay valid): skin_host for a mesh that is only skinned, the morph's twin - with the skin once that has a pose - for a morphed one.
 void materialise(LuminaryHost* h, uint32_t mesh) {
   const auto it = h->skins.find(mesh);
   if (it == h->skins.end() || it->second.host_current || mesh >= h->scene.meshes.size()) return;
   HostSkin& k = it->second;
   lum::HostMesh& m = h->scene.meshes[mesh];
   lum::host_parallel_for(m.triangle_count(), [&](size_t b, size_t e) {  // (a corner's bytes do not depend on the chunks)
-    lum::skin_host(k.rest_positions.data() + 9 * b, k.rest_normals.data() + 9 * b, k.bone_ids.data() + 12 * b, k.weights.data() + 12 * b, (uint32_t) (e - b), k.palette.data(),
-                   k.bone_count, m.positions.data() + 9 * b, m.normals.data() + 9 * b, nullptr, nullptr);
+    if (k.has_morph()) {
+      const bool posed = k.posed();
+      lum::morph_host_csr(k.rest_positions.data() + 9 * b, k.rest_normals.data() + 9 * b, k.morph_csr, 3 * b, 3 * (e - b), k.morph_weights.data(),
+                          posed ? k.bone_ids.data() + 12 * b : nullptr, posed ? k.weights.data() + 12 * b : nullptr, posed ? k.palette.data() : nullptr,
+                          m.positions.data() + 9 * b, m.normals.data() + 9 * b, nullptr, nullptr);
+    }
+    else
+      lum::skin_host(k.rest_positions.data() + 9 * b, k.rest_normals.data() + 9 * b, k.bone_ids.data() + 12 * b, k.weights.data() + 12 * b, (uint32_t) (e - b), k.palette.data(),
+                     k.bone_count, m.positions.data() + 9 * b, m.normals.data() + 9 * b, nullptr, nullptr);
   });
   k.host_current = true;
   h->host_materialisations++;
@@ -205,30 +227,38 @@ bool mesh_emits(const LuminaryHost* h, uint32_t mesh) {
   return false;
 }
 
-// Bindings and poses a context has not seen, before it takes the scene (lumc_scene_update with `dirty`); after an update that rebuilt the meshes - which drops the
-// context's bindings - all of them again, and the poses applied in a second, vertex-only update. *seen: the context's mark (LuminaryHost::skin_serial then).
+// Bindings, poses and weights a context has not seen, before it takes the scene (lumc_scene_update with `dirty`); after an update that rebuilt the meshes - which
+// drops the context's bindings - all of them again, and the poses and weights applied in a second, vertex-only update. *seen: the context's mark
+// (LuminaryHost::skin_serial then).
 int update_context_scene(LuminaryHost* h, LumContext* core, uint32_t dirty, uint64_t* seen) {
-  auto bind = [&](uint32_t mesh, const HostSkin& k) {
-    return lumc_mesh_skin_bind(core, mesh, k.rest_positions.data(), k.rest_normals.data(), k.bone_ids.data(), k.weights.data(), (uint32_t) (k.bone_ids.size() / 12), k.bone_count);
+  // one mesh's share; `all`: whatever the context has seen. Returns nonzero on failure; *pending: a pose or weights were handed over.
+  auto hand_over = [&](uint32_t mesh, const HostSkin& k, bool all, bool* pending) {
+    const uint32_t triangles = (uint32_t) (k.rest_positions.size() / 9);
+    const bool new_skin = k.has_skin() && (all || k.bind_serial > *seen), new_morph = k.has_morph() && (all || k.morph_bind_serial > *seen);
+    if (new_skin && lumc_mesh_skin_bind(core, mesh, k.rest_positions.data(), k.rest_normals.data(), k.bone_ids.data(), k.weights.data(), triangles, k.bone_count)) return 1;
+    if (new_morph && lumc_mesh_morph_bind(core, mesh, k.rest_positions.data(), k.rest_normals.data(), triangles, k.target_count, k.morph_offsets.data(), k.morph_corners.data(),
+                                          k.morph_delta_positions.data(), k.morph_delta_normals.empty() ? nullptr : k.morph_delta_normals.data()))
+      return 1;
+    if (k.posed() && (new_skin || k.pose_serial > *seen)) {
+      if (lumc_mesh_skin_pose(core, mesh, k.palette.data(), k.bone_count)) return 1;
+      *pending = true;
+    }
+    if (k.weighted() && (new_morph || k.morph_weights_serial > *seen)) {
+      if (lumc_mesh_morph_weights(core, mesh, k.morph_weights.data(), k.target_count)) return 1;
+      *pending = true;
+    }
+    return 0;
   };
   const bool rebuilds_meshes = (dirty & LUMC_DIRTY_MESHES) != 0;
+  bool pending = false;
   if (!rebuilds_meshes)
-    for (const auto& kv : h->skins) {
-      const HostSkin& k = kv.second;
-      if (k.bind_serial > *seen && bind(kv.first, k)) return 1;
-      if (!k.palette.empty() && (k.bind_serial > *seen || k.pose_serial > *seen) && lumc_mesh_skin_pose(core, kv.first, k.palette.data(), k.bone_count)) return 1;
-    }
+    for (const auto& kv : h->skins)
+      if (hand_over(kv.first, kv.second, false, &pending)) return 1;
   if (lumc_scene_update(core, &h->device_scene.view, dirty)) return 1;
   if (rebuilds_meshes) {
-    bool posed = false;
-    for (const auto& kv : h->skins) {
-      const HostSkin& k = kv.second;
-      if (bind(kv.first, k)) return 1;
-      if (k.palette.empty()) continue;
-      if (lumc_mesh_skin_pose(core, kv.first, k.palette.data(), k.bone_count)) return 1;
-      posed = true;
-    }
-    if (posed && lumc_scene_update(core, &h->device_scene.view, LUMC_DIRTY_MESH_SKIN)) return 1;
+    for (const auto& kv : h->skins)
+      if (hand_over(kv.first, kv.second, true, &pending)) return 1;
+    if (pending && lumc_scene_update(core, &h->device_scene.view, LUMC_DIRTY_MESH_SKIN)) return 1;
   }
   *seen = h->skin_serial;
   return 0;
@@ -879,6 +909,63 @@ LuminaryResult luminary_ext_set_mesh_positions(LuminaryHost* host, uint32_t mesh
   invalidate(host, LUMC_DIRTY_MESH_POSITIONS | LUMC_DIRTY_LIGHTS);  // the vertices and the mesh's tree; the light tree follows moved emitters
   return LUMINARY_SUCCESS;
 }
+static void mark_moved(LuminaryHost* host, uint32_t mesh_id) {
+  if (std::find(host->moved_meshes.begin(), host->moved_meshes.end(), mesh_id) == host->moved_meshes.end()) host->moved_meshes.push_back(mesh_id);
+}
+// A bound mesh got a new pose or new weights: the devices write its vertices, the host mesh follows when something reads it.
+static void deformed(LuminaryHost* host, uint32_t mesh_id, HostSkin& k) {
+  k.host_current = false; k.view_current = false;
+  uint32_t dirty = LUMC_DIRTY_MESH_SKIN;
+  if (mesh_emits(host, mesh_id)) { materialise(host, mesh_id); dirty |= LUMC_DIRTY_LIGHTS; }  // the light tree is built from the host mesh: the existing path
+  invalidate(host, dirty);
+}
+// One of a mesh's two bindings went, or was replaced, while the other stays, and the one that went had shaped the mesh: the mesh is what the other one makes of the
+// shared rest shape. Its pose or weights are handed to every context again (which marks the mesh moved there); with neither, the rest shape itself goes up as moved
+// vertices.
+static void rebound(LuminaryHost* host, uint32_t mesh_id, HostSkin& k) {
+  if (k.posed()) k.pose_serial = ++host->skin_serial;
+  if (k.weighted()) k.morph_weights_serial = ++host->skin_serial;
+  if (k.posed() || k.weighted()) { deformed(host, mesh_id, k); return; }
+  lum::HostMesh& m = host->scene.meshes[mesh_id];
+  std::copy(k.rest_positions.begin(), k.rest_positions.end(), m.positions.begin());  // in place: the pointers luminary_ext_get_mesh handed out stay valid
+  std::copy(k.rest_normals.begin(), k.rest_normals.end(), m.normals.begin());
+  k.host_current = true; k.view_current = true;
+  mark_moved(host, mesh_id);
+  invalidate(host, LUMC_DIRTY_MESH_POSITIONS | (mesh_emits(host, mesh_id) ? LUMC_DIRTY_LIGHTS : 0));
+}
+// The first binding of a mesh, or another of the only kind it holds: the rest shape is the host mesh as it is now (bound before: the current pose).
+static HostSkin& bind_fresh(LuminaryHost* host, uint32_t mesh_id) {
+  materialise(host, mesh_id);
+  const lum::HostMesh& m = host->scene.meshes[mesh_id];
+  HostSkin k;
+  k.rest_positions = m.positions; k.rest_normals = m.normals;
+  const auto old = host->skins.find(mesh_id);
+  const bool stale_view = old != host->skins.end() && !old->second.view_current;
+  host->skins[mesh_id] = std::move(k);  // (the vertices stay where they are: nothing restarts; the contexts get the binding before their next update)
+  if (stale_view) {  // bound and posed before: a context trusts the view's vertices of a mesh until its first pose under the new binding, so they are encoded again
+    mark_moved(host, mesh_id);
+    invalidate(host, LUMC_DIRTY_MESH_POSITIONS);
+  }
+  return host->skins[mesh_id];
+}
+static void unbind_in_contexts(LuminaryHost* host, uint32_t mesh_id, int (*unbind)(LumContext*, uint32_t)) {
+  // every context that holds the binding drops it (one that never got it refuses: nothing to drop)
+  if (host->core) (void) unbind(host->core, mesh_id);
+  for (uint32_t i = 0; i < host->devices.size(); i++)
+    if (i != host->main_slot && host->devices[i].core) (void) unbind(host->devices[i].core, mesh_id);
+}
+// The last of a mesh's bindings goes: the host mesh becomes the current pose, and plain again.
+static void unbind_last(LuminaryHost* host, uint32_t mesh_id) {
+  materialise(host, mesh_id);
+  const auto it = host->skins.find(mesh_id);
+  const bool view_current = it->second.view_current;
+  host->skins.erase(it);
+  if (!view_current) {  // the device scene's vertices of the mesh are re-encoded from the host mesh, as for moved vertices; the devices' are that pose already
+    mark_moved(host, mesh_id);
+    invalidate(host, LUMC_DIRTY_MESH_POSITIONS);
+  }
+}
+
 LuminaryResult luminary_ext_bind_mesh_skin(LuminaryHost* host, uint32_t mesh_id, const uint16_t* bone_ids, const float* weights, uint32_t triangle_count, uint32_t bone_count) {
   CHECK_NULL(host);
   ApiLock lock(host);
@@ -886,54 +973,111 @@ LuminaryResult luminary_ext_bind_mesh_skin(LuminaryHost* host, uint32_t mesh_id,
   if (bone_count == 0 || bone_count > lum::kSkinMaxBones) return LUMINARY_ERROR_INVALID_API_ARGUMENT;
   for (size_t i = 0; i < 12 * (size_t) triangle_count; i++)
     if (bone_ids[i] >= bone_count || !(weights[i] >= 0.0f) || !std::isfinite(weights[i])) return LUMINARY_ERROR_INVALID_API_ARGUMENT;
-  materialise(host, mesh_id);  // (bound before: the rest pose is the current pose)
-  const lum::HostMesh& m = host->scene.meshes[mesh_id];
-  HostSkin k;
-  k.rest_positions = m.positions; k.rest_normals = m.normals;
+  const auto old = host->skins.find(mesh_id);
+  const bool shares_rest = old != host->skins.end() && old->second.has_morph();  // a morph is bound: its rest shape is the skin's
+  const bool was_posed = shares_rest && old->second.posed();
+  HostSkin& k = shares_rest ? old->second : bind_fresh(host, mesh_id);
   k.bone_ids.assign(bone_ids, bone_ids + 12 * (size_t) triangle_count);
   k.weights.assign(weights, weights + 12 * (size_t) triangle_count);
   k.bone_count = bone_count;
+  k.palette.clear(); k.pose_serial = 0;
   k.bind_serial = ++host->skin_serial;
-  const auto old = host->skins.find(mesh_id);
-  const bool stale_view = old != host->skins.end() && !old->second.view_current;
-  host->skins[mesh_id] = std::move(k);  // (the vertices stay where they are: nothing restarts; the contexts get the binding before their next update)
-  if (stale_view) {  // bound and posed before: a context trusts the view's vertices of a mesh until its first pose under the new binding, so they are encoded again
-    if (std::find(host->moved_meshes.begin(), host->moved_meshes.end(), mesh_id) == host->moved_meshes.end()) host->moved_meshes.push_back(mesh_id);
-    invalidate(host, LUMC_DIRTY_MESH_POSITIONS);
-  }
+  if (was_posed) rebound(host, mesh_id, k);
   return LUMINARY_SUCCESS;
 }
 LuminaryResult luminary_ext_set_mesh_pose(LuminaryHost* host, uint32_t mesh_id, const float* bones, uint32_t bone_count) {
   CHECK_NULL(host);
   ApiLock lock(host);
   const auto it = host->skins.find(mesh_id);
-  if (!bones || it == host->skins.end() || bone_count != it->second.bone_count) return LUMINARY_ERROR_INVALID_API_ARGUMENT;
+  if (!bones || it == host->skins.end() || !it->second.has_skin() || bone_count != it->second.bone_count) return LUMINARY_ERROR_INVALID_API_ARGUMENT;
   for (size_t i = 0; i < 12 * (size_t) bone_count; i++) if (!std::isfinite(bones[i])) return LUMINARY_ERROR_INVALID_API_ARGUMENT;
   HostSkin& k = it->second;
   k.palette.assign(bones, bones + 12 * (size_t) bone_count);
   k.pose_serial = ++host->skin_serial;
-  k.host_current = false; k.view_current = false;
-  uint32_t dirty = LUMC_DIRTY_MESH_SKIN;
-  if (mesh_emits(host, mesh_id)) { materialise(host, mesh_id); dirty |= LUMC_DIRTY_LIGHTS; }  // the light tree is built from the host mesh: the existing path
-  invalidate(host, dirty);
+  deformed(host, mesh_id, k);
   return LUMINARY_SUCCESS;
 }
 LuminaryResult luminary_ext_unbind_mesh_skin(LuminaryHost* host, uint32_t mesh_id) {
   CHECK_NULL(host);
   ApiLock lock(host);
   const auto it = host->skins.find(mesh_id);
-  if (it == host->skins.end()) return LUMINARY_ERROR_INVALID_API_ARGUMENT;
-  materialise(host, mesh_id);
-  const bool view_current = it->second.view_current;
-  host->skins.erase(it);
-  // every context that holds the binding drops it (one that never got it refuses: nothing to drop); the devices' vertices are the pose the host mesh now holds
-  if (host->core) (void) lumc_mesh_skin_unbind(host->core, mesh_id);
-  for (uint32_t i = 0; i < host->devices.size(); i++)
-    if (i != host->main_slot && host->devices[i].core) (void) lumc_mesh_skin_unbind(host->devices[i].core, mesh_id);
-  if (!view_current) {  // the device scene's vertices of the mesh are re-encoded from the host mesh, as for moved vertices
-    if (std::find(host->moved_meshes.begin(), host->moved_meshes.end(), mesh_id) == host->moved_meshes.end()) host->moved_meshes.push_back(mesh_id);
-    invalidate(host, LUMC_DIRTY_MESH_POSITIONS);
+  if (it == host->skins.end() || !it->second.has_skin()) return LUMINARY_ERROR_INVALID_API_ARGUMENT;
+  if (!it->second.has_morph()) unbind_last(host, mesh_id);
+  unbind_in_contexts(host, mesh_id, lumc_mesh_skin_unbind);
+  if (host->skins.count(mesh_id)) {  // the morph stays, over the same rest shape
+    HostSkin& k = it->second;
+    const bool was_posed = k.posed();
+    k.bone_ids.clear(); k.weights.clear(); k.palette.clear();
+    k.bone_count = 0; k.bind_serial = k.pose_serial = 0;
+    if (was_posed) rebound(host, mesh_id, k);
   }
+  return LUMINARY_SUCCESS;
+}
+LuminaryResult luminary_ext_bind_mesh_morph(LuminaryHost* host, uint32_t mesh_id, uint32_t triangle_count, uint32_t target_count, const uint32_t* offsets, const uint32_t* corners,
+                                            const float* delta_positions, const float* delta_normals) {
+  CHECK_NULL(host);
+  ApiLock lock(host);
+  if (mesh_id >= host->scene.meshes.size() || host->scene.meshes[mesh_id].triangle_count() != triangle_count) return LUMINARY_ERROR_INVALID_API_ARGUMENT;
+  if (lum::morph_check(triangle_count, target_count, offsets, corners, delta_positions, delta_normals)) return LUMINARY_ERROR_INVALID_API_ARGUMENT;
+  const auto old = host->skins.find(mesh_id);
+  const bool shares_rest = old != host->skins.end() && old->second.has_skin();  // a skin is bound: its rest pose is the morph's base shape
+  const bool was_weighted = shares_rest && old->second.weighted();
+  HostSkin& k = shares_rest ? old->second : bind_fresh(host, mesh_id);
+  const size_t entries = offsets[target_count];
+  k.target_count = target_count;
+  k.morph_offsets.assign(offsets, offsets + target_count + 1);
+  k.morph_corners.clear(); k.morph_delta_positions.clear(); k.morph_delta_normals.clear();
+  if (entries) {
+    k.morph_corners.assign(corners, corners + entries);
+    k.morph_delta_positions.assign(delta_positions, delta_positions + 3 * entries);
+    if (delta_normals) k.morph_delta_normals.assign(delta_normals, delta_normals + 3 * entries);
+  }
+  lum::morph_csr(triangle_count, target_count, offsets, corners, delta_positions, delta_normals, &k.morph_csr);
+  k.morph_weights.assign(target_count, 0.0f); k.morph_weights_serial = 0;
+  k.morph_bind_serial = ++host->skin_serial;
+  if (was_weighted) rebound(host, mesh_id, k);
+  return LUMINARY_SUCCESS;
+}
+LuminaryResult luminary_ext_set_mesh_weights(LuminaryHost* host, uint32_t mesh_id, const float* weights, uint32_t target_count) {
+  CHECK_NULL(host);
+  ApiLock lock(host);
+  const auto it = host->skins.find(mesh_id);
+  if (!weights || it == host->skins.end() || !it->second.has_morph() || target_count != it->second.target_count) return LUMINARY_ERROR_INVALID_API_ARGUMENT;
+  for (uint32_t t = 0; t < target_count; t++) if (!std::isfinite(weights[t])) return LUMINARY_ERROR_INVALID_API_ARGUMENT;
+  HostSkin& k = it->second;
+  k.morph_weights.assign(weights, weights + target_count);
+  k.morph_weights_serial = ++host->skin_serial;
+  deformed(host, mesh_id, k);
+  return LUMINARY_SUCCESS;
+}
+LuminaryResult luminary_ext_unbind_mesh_morph(LuminaryHost* host, uint32_t mesh_id) {
+  CHECK_NULL(host);
+  ApiLock lock(host);
+  const auto it = host->skins.find(mesh_id);
+  if (it == host->skins.end() || !it->second.has_morph()) return LUMINARY_ERROR_INVALID_API_ARGUMENT;
+  if (!it->second.has_skin()) unbind_last(host, mesh_id);
+  unbind_in_contexts(host, mesh_id, lumc_mesh_morph_unbind);
+  if (host->skins.count(mesh_id)) {  // the skin stays, over the same rest pose
+    HostSkin& k = it->second;
+    const bool was_weighted = k.weighted();
+    k.morph_offsets.clear(); k.morph_corners.clear(); k.morph_delta_positions.clear(); k.morph_delta_normals.clear(); k.morph_weights.clear();
+    k.morph_csr = lum::MorphCsr{};
+    k.target_count = 0; k.morph_bind_serial = k.morph_weights_serial = 0;
+    if (was_weighted) rebound(host, mesh_id, k);
+  }
+  return LUMINARY_SUCCESS;
+}
+LuminaryResult luminary_ext_get_mesh_morph_stats(LuminaryHost* host, LuminaryMeshMorphStats* out) {
+  CHECK_NULL(host); CHECK_NULL(out);
+  ApiLock lock(host);
+  std::memset(out, 0, sizeof(*out));
+  out->host_materialisations = host->host_materialisations;
+  if (!host->core) return LUMINARY_SUCCESS;
+  LumMeshMorphStats s;
+  if (lumc_mesh_morph_stats(host->core, &s)) return LUMINARY_ERROR_API_EXCEPTION;
+  static_assert(sizeof(LuminaryMeshMorphStats) == sizeof(LumMeshMorphStats) + sizeof(uint64_t) && offsetof(LuminaryMeshMorphStats, host_materialisations) == sizeof(LumMeshMorphStats),
+                "the public struct mirrors the core's, host_materialisations behind it");
+  std::memcpy(out, &s, sizeof(s));
   return LUMINARY_SUCCESS;
 }
 LuminaryResult luminary_ext_get_mesh_skin_stats(LuminaryHost* host, LuminaryMeshSkinStats* out) {

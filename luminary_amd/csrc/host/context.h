@@ -20,6 +20,7 @@
 #include "bvh_refit.h"
 #include "device_buffer.h"
 #include "instance_update.h"
+#include "mesh_morph.h"
 #include "mesh_skin.h"
 #include "scene_arrays.h"
 #include "work_layout.h"
@@ -72,6 +73,9 @@ struct LumContext {
   std::map<uint32_t, MeshSkin> mesh_skin;    // by mesh; dropped with the meshes
   DeviceBuffer<uint32_t> d_skin_flags;       // one word of kSkinFlag* bits per launch of an update
   LumMeshSkinStats skin_stats{};
+  // morphed meshes (lumc_mesh_morph_*; mesh_morph.hip, scene_device.hip skin_meshes): a mesh may hold both, then one kernel blends and poses it
+  std::map<uint32_t, MeshMorph> mesh_morph;  // by mesh; dropped with the meshes
+  LumMeshMorphStats morph_stats{};
   std::vector<uint32_t> sky_lut_key;  // the sky parameters the two sky tables were generated from
   DeviceBuffer<float> d_bridge_lut;   // the bridge sampler's vertex-count table (context-owned: scene.bridge_lut points here while bridges are possible)
   std::vector<float> bridge_lut_host; // its content, to notice a caller that hands over another table

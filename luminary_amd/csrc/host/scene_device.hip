@@ -130,7 +130,7 @@ void free_scene(LumContext* ctx) {
   ctx->mesh_bvh.clear(); ctx->mesh_box.clear(); ctx->mesh_refit.clear(); ctx->mesh_tri_offset.clear();
   ctx->instance_update.reset(); ctx->instance_mesh_ids.clear();
   ctx->resident_refit.drop_layout(); ctx->stale_meshes = 0;
-  ctx->mesh_skin.clear(); ctx->d_skin_flags.reset();
+  ctx->mesh_skin.clear(); ctx->mesh_morph.clear(); ctx->d_skin_flags.reset();
   ctx->has_scene = false;
 }
 
@@ -405,72 +405,112 @@ static int build_mesh_trees(LumContext* ctx, const LumDeviceSceneView* v, std::v
   return 0;
 }
 
-// ---- skinned meshes (lum_core.h lumc_mesh_skin_bind; mesh_skin.hip) ----
-static bool skin_posed(const LumContext* ctx, uint32_t m) {
+// ---- skinned and morphed meshes (lum_core.h lumc_mesh_skin_bind, lumc_mesh_morph_bind; mesh_skin.hip, mesh_morph.hip; DESIGN.md sections 11 and 12) ----
+// A kernel wrote the scene's vertices of mesh m: the view's vertices of it are never trusted.
+static bool written_on_device(const LumContext* ctx, uint32_t m) {
   const auto it = ctx->mesh_skin.find(m);
-  return it != ctx->mesh_skin.end() && it->second.posed;
+  if (it != ctx->mesh_skin.end() && it->second.posed) return true;
+  const auto im = ctx->mesh_morph.find(m);
+  return im != ctx->mesh_morph.end() && im->second.applied;
 }
 
 // The skinning step of an update that touches vertices (find_moved_meshes runs it, once), after the vertex arrays are in place and before anything reads them: every
-// pending palette goes up and k_skin_mesh writes its mesh's range of the scene's vertices (those meshes are moved: *posed, ascending); after an upload of the vertex
-// arrays from the view (view_uploaded) every other bound mesh that has been posed is written again from the palette it holds - the same bits as before the upload,
-// so its tree still fits. One launch per mesh. Then the launches' flag words come back: a posed position that is not finite fails the update.
+// pending palette and every pending weight set goes up and a kernel writes its mesh's range of the scene's vertices (those meshes are moved: *posed, ascending) -
+// k_skin_mesh for a mesh that is only skinned, k_morph_mesh for a morphed one, with the mesh's skin once that has a palette; after an upload of the vertex arrays
+// from the view (view_uploaded) every other bound mesh a kernel has written is written again from the palette and the weights it holds - the same bits as before
+// the upload, so its tree still fits. One launch per mesh. Then the launches' flag words come back: a position that is not finite fails the update.
 static int skin_meshes(LumContext* ctx, bool view_uploaded, std::vector<uint32_t>* posed) {
-  std::vector<uint32_t> jobs;
-  for (const auto& kv : ctx->mesh_skin)
-    if (!kv.second.pending.empty() || (view_uploaded && kv.second.posed)) jobs.push_back(kv.first);
+  struct Job { uint32_t mesh; MeshSkin* skin; MeshMorph* morph; bool new_pose, new_weights; };
+  std::vector<uint32_t> bound;
+  for (const auto& kv : ctx->mesh_skin) bound.push_back(kv.first);
+  for (const auto& kv : ctx->mesh_morph) bound.push_back(kv.first);
+  std::sort(bound.begin(), bound.end());
+  bound.erase(std::unique(bound.begin(), bound.end()), bound.end());
+  std::vector<Job> jobs;
+  bool any_skin = false, any_morph = false;
+  for (uint32_t m : bound) {
+    const auto is = ctx->mesh_skin.find(m);
+    const auto im = ctx->mesh_morph.find(m);
+    Job job{m, is != ctx->mesh_skin.end() ? &is->second : nullptr, im != ctx->mesh_morph.end() ? &im->second : nullptr, false, false};
+    job.new_pose = job.skin && !job.skin->pending.empty();
+    job.new_weights = job.morph && !job.morph->pending.empty();
+    if (!job.new_pose && !job.new_weights && !(view_uploaded && written_on_device(ctx, m))) continue;
+    if (job.skin && !job.skin->posed && !job.new_pose) job.skin = nullptr;  // (no palette yet: the morph alone writes the mesh)
+    if (!job.skin && !job.morph) continue;
+    any_skin = any_skin || !job.morph || job.new_pose;
+    any_morph = any_morph || job.morph;
+    jobs.push_back(job);
+  }
   if (jobs.empty()) return 0;
   LumMeshSkinStats& st = ctx->skin_stats;
-  st.last_meshes = st.last_launches = 0; st.last_bytes_uploaded = 0; st.seconds = st.seconds_upload = st.seconds_skin = 0.0;
+  LumMeshMorphStats& mst = ctx->morph_stats;
+  if (any_skin) { st.last_meshes = st.last_launches = 0; st.last_bytes_uploaded = 0; st.seconds = st.seconds_upload = st.seconds_skin = 0.0; }
+  if (any_morph) { mst.last_meshes = mst.last_launches = 0; mst.last_bytes_uploaded = 0; mst.seconds = mst.seconds_upload = mst.seconds_morph = 0.0; }
   DeviceBuffer<float4>& vertices = ctx->arrays.mesh.vertices;
-  for (uint32_t m : jobs) {  // every range a kernel will write, against the array that is there
-    const MeshSkin& skin = ctx->mesh_skin[m];
-    if ((size_t) m + 1 >= ctx->mesh_tri_offset.size() || ctx->mesh_tri_offset[m + 1] - ctx->mesh_tri_offset[m] != skin.triangles ||
-        3 * (size_t) ctx->mesh_tri_offset[m + 1] > vertices.count()) {
-      ctx->error = "lumc_scene_update: mesh " + std::to_string(m) + " is bound to a skin of another triangle count than the scene on the device";
+  for (const Job& job : jobs) {  // every range a kernel will write, against the array that is there
+    const uint32_t m = job.mesh;
+    if ((size_t) m + 1 >= ctx->mesh_tri_offset.size() || 3 * (size_t) ctx->mesh_tri_offset[m + 1] > vertices.count() ||
+        (job.skin && ctx->mesh_tri_offset[m + 1] - ctx->mesh_tri_offset[m] != job.skin->triangles) ||
+        (job.morph && ctx->mesh_tri_offset[m + 1] - ctx->mesh_tri_offset[m] != job.morph->triangles)) {
+      ctx->error = "lumc_scene_update: mesh " + std::to_string(m) + " is bound to a " + (job.morph ? "morph" : "skin") + " of another triangle count than the scene on the device";
       return 1;
     }
   }
   const Stopwatch t_all;
   if (ctx->d_skin_flags.count() < jobs.size()) HIP_TRY(ctx, ctx->d_skin_flags.resize(jobs.size()));
   HIP_TRY(ctx, hipMemset(ctx->d_skin_flags.get(), 0, sizeof(uint32_t) * jobs.size()));
-  for (uint32_t m : jobs) {
-    MeshSkin& skin = ctx->mesh_skin[m];
-    if (skin.pending.empty()) continue;
-    HIP_TRY(ctx, hipMemcpy(skin.palette.get(), skin.pending.data(), sizeof(float) * skin.pending.size(), hipMemcpyHostToDevice));
-    st.last_bytes_uploaded += sizeof(float) * skin.pending.size();
+  for (const Job& job : jobs) {
+    if (job.new_pose) {
+      HIP_TRY(ctx, hipMemcpy(job.skin->palette.get(), job.skin->pending.data(), sizeof(float) * job.skin->pending.size(), hipMemcpyHostToDevice));
+      st.last_bytes_uploaded += sizeof(float) * job.skin->pending.size();
+    }
+    if (job.new_weights) {
+      if (job.morph->pending.size() != job.morph->weights.count()) { ctx->error = "lumc_scene_update: mesh " + std::to_string(job.mesh) + " holds weights of another target count"; return 1; }
+      HIP_TRY(ctx, hipMemcpy(job.morph->weights.get(), job.morph->pending.data(), sizeof(float) * job.morph->pending.size(), hipMemcpyHostToDevice));
+      mst.last_bytes_uploaded += sizeof(float) * job.morph->pending.size();
+    }
   }
   HIP_TRY(ctx, hipDeviceSynchronize());
-  st.seconds_upload = t_all.seconds();
+  const double seconds_upload = t_all.seconds();
   const Stopwatch t_skin;
   for (size_t j = 0; j < jobs.size(); j++) {
-    HIP_TRY(ctx, mesh_skin_launch(ctx->mesh_skin[jobs[j]], vertices.get() + 3 * (size_t) ctx->mesh_tri_offset[jobs[j]], ctx->d_skin_flags.get() + j));
-    st.last_launches++;
+    const Job& job = jobs[j];
+    float4* first = vertices.get() + 3 * (size_t) ctx->mesh_tri_offset[job.mesh];
+    if (job.morph) {
+      HIP_TRY(ctx, mesh_morph_launch(*job.morph, job.skin, first, ctx->d_skin_flags.get() + j));
+      mst.last_launches++;
+      if (job.new_pose) st.last_launches++;
+    }
+    else {
+      HIP_TRY(ctx, mesh_skin_launch(*job.skin, first, ctx->d_skin_flags.get() + j));
+      st.last_launches++;
+    }
   }
   std::vector<uint32_t> flags(jobs.size());
   HIP_TRY(ctx, hipMemcpy(flags.data(), ctx->d_skin_flags.get(), sizeof(uint32_t) * jobs.size(), hipMemcpyDeviceToHost));  // (waits for the launches)
-  st.seconds_skin = t_skin.seconds();
-  st.seconds = t_all.seconds();
+  if (any_skin) { st.seconds_upload = seconds_upload; st.seconds_skin = t_skin.seconds(); st.seconds = t_all.seconds(); }
+  if (any_morph) { mst.seconds_upload = seconds_upload; mst.seconds_morph = t_skin.seconds(); mst.seconds = t_all.seconds(); }
   for (size_t j = 0; j < jobs.size(); j++) {
-    if (flags[j] & kSkinFlagBadBone) { ctx->error = "lumc_scene_update: mesh " + std::to_string(jobs[j]) + ": a bone id beyond the palette reached the skinning kernel"; return 1; }
-    if (flags[j] & kSkinFlagNotFinite) { ctx->error = "lumc_scene_update: mesh " + std::to_string(jobs[j]) + ": the pose gives a position that is not finite"; return 1; }
+    const std::string mesh = "lumc_scene_update: mesh " + std::to_string(jobs[j].mesh);
+    if (flags[j] & kSkinFlagBadBone) { ctx->error = mesh + ": a bone id beyond the palette reached the skinning kernel"; return 1; }
+    if (flags[j] & kMorphFlagBadLayout) { ctx->error = mesh + ": a target id or a row beyond the binding reached the morph kernel"; return 1; }
+    if (flags[j] & kSkinFlagNotFinite) { ctx->error = mesh + (jobs[j].morph ? ": the weights give a position that is not finite" : ": the pose gives a position that is not finite"); return 1; }
   }
-  for (uint32_t m : jobs) {
-    MeshSkin& skin = ctx->mesh_skin[m];
-    if (skin.pending.empty()) continue;
-    skin.pending.clear(); skin.posed = true;
-    posed->push_back(m);
-    st.poses++; st.last_meshes++;
+  for (const Job& job : jobs) {
+    if (job.new_pose) { job.skin->pending.clear(); job.skin->posed = true; st.poses++; st.last_meshes++; }
+    if (job.new_weights) { job.morph->pending.clear(); job.morph->applied = true; mst.applied++; mst.last_meshes++; }
+    if (job.new_pose || job.new_weights) posed->push_back(job.mesh);
   }
   return 0;
 }
 
 // A posed mesh's vertices for a builder: its 3 * nt records as the device holds them, the layout of the view's `vertices`. Counted.
-static int download_posed_vertices(LumContext* ctx, uint32_t t0, uint32_t nt, std::vector<float>& out) {
+static int download_posed_vertices(LumContext* ctx, uint32_t m, uint32_t t0, uint32_t nt, std::vector<float>& out) {
   out.resize(12 * (size_t) nt);
   if (3 * ((size_t) t0 + nt) > ctx->arrays.mesh.vertices.count()) { ctx->error = "lumc_scene_update: a posed mesh lies outside the vertex array"; return 1; }
   HIP_TRY(ctx, hipMemcpy(out.data(), ctx->arrays.mesh.vertices.get() + 3 * (size_t) t0, sizeof(float) * out.size(), hipMemcpyDeviceToHost));
-  ctx->skin_stats.rebuild_downloads++;
+  if (ctx->mesh_morph.count(m)) ctx->morph_stats.rebuild_downloads++;  // (LumMeshSkinStats keeps its meaning for meshes that are only skinned)
+  else ctx->skin_stats.rebuild_downloads++;
   return 0;
 }
 
@@ -506,7 +546,7 @@ static int find_moved_meshes(LumContext* ctx, const LumDeviceSceneView* v, bool 
     const uint32_t t0 = v->mesh_tri_offset[m], nt = v->mesh_tri_offset[m + 1] - t0;
     if (nt == 0) continue;
     const bool by_pose = std::binary_search(posed.begin(), posed.end(), m);
-    if (!by_pose && (!upload_view || skin_posed(ctx, m))) continue;
+    if (!by_pose && (!upload_view || written_on_device(ctx, m))) continue;
     MeshTreeKey key{};
     if (!by_pose) {
       const Stopwatch t_hash;
@@ -565,7 +605,7 @@ static int refit_mesh_copies(LumContext* ctx, const LumDeviceSceneView* v, const
     if (build) {
       const Stopwatch t_build;
       if (posed) {  // the builder reads host vertices: the posed ones come down (the view's layout), and with them the key of the process's tree cache
-        if (download_posed_vertices(ctx, t0, nt, posed_vertices)) return 1;
+        if (download_posed_vertices(ctx, m, t0, nt, posed_vertices)) return 1;
         vertices = posed_vertices.data();
         key = mesh_tree_key(vertices, nt, ctx->bvh_builder);
       }
@@ -1099,12 +1139,13 @@ static int scene_update(LumContext* ctx, const LumDeviceSceneView* v, unsigned d
   if (v->max_ray_depth > 63) { ctx->error = "max_ray_depth exceeds 63 (6-bit field, device_structs.h:9)"; return 1; }
   bool pose_pending = false;
   for (const auto& kv : ctx->mesh_skin) pose_pending = pose_pending || !kv.second.pending.empty();
+  for (const auto& kv : ctx->mesh_morph) pose_pending = pose_pending || !kv.second.pending.empty();  // pending weights are a pending pose
   UpdatePlan plan = plan_update(dirty, ctx->refit_in_place != 0, ctx->refit_mode, ctx->instance_update_mode, pose_pending);
   if (plan.moved_by_host) reset_update(ctx->instance_stats);
   auto host_path_since = [&](const Stopwatch& t) { if (plan.moved_by_host) ctx->instance_stats.seconds += t.seconds(); };
   auto lights_since = [&](const Stopwatch& t) { if (plan.time_lights) ctx->refit_stats.seconds_lights += t.seconds(); };
   ctx->has_scene = false;
-  if (plan.meshes) { ctx->arrays.mesh = {}; ctx->mesh_skin.clear(); }  // the traversal triangles too; new meshes: the bindings go, the caller binds again
+  if (plan.meshes) { ctx->arrays.mesh = {}; ctx->mesh_skin.clear(); ctx->mesh_morph.clear(); }  // the traversal triangles too; new meshes: the bindings go, the caller binds again
   if (plan.meshes && update_mesh_arrays(ctx, v)) return 1;
   bool triangles_rewritten = false;
   if (plan.positions) {
@@ -1261,6 +1302,48 @@ int lumc_mesh_skin_pose(LumContext* ctx, uint32_t mesh, const float* bones, uint
 int lumc_mesh_skin_stats(const LumContext* ctx, LumMeshSkinStats* out) {
   if (!ctx || !out) return 1;
   *out = ctx->skin_stats;
+  return 0;
+}
+
+int lumc_mesh_morph_bind(LumContext* ctx, uint32_t mesh, const float* base_positions, const float* base_normals, uint32_t triangle_count, uint32_t target_count,
+                         const uint32_t* offsets, const uint32_t* corners, const float* delta_positions, const float* delta_normals) {
+  if (!ctx) return 1;
+  if (!ctx->has_scene || (size_t) mesh + 1 >= ctx->mesh_tri_offset.size() || ctx->mesh_tri_offset[mesh + 1] - ctx->mesh_tri_offset[mesh] != triangle_count) {
+    ctx->error = "lumc_mesh_morph_bind: mesh " + std::to_string(mesh) + " is not in the scene on the device with that triangle count";
+    return 1;
+  }
+  if (!base_positions || !base_normals) { ctx->error = "lumc_mesh_morph_bind: a NULL array"; return 1; }
+  if (const char* why = morph_check(triangle_count, target_count, offsets, corners, delta_positions, delta_normals)) { ctx->error = std::string("lumc_mesh_morph_bind: ") + why; return 1; }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  MeshMorph morph;
+  HIP_TRY(ctx, mesh_morph_upload(morph, base_positions, base_normals, triangle_count, target_count, offsets, corners, delta_positions, delta_normals));
+  ctx->mesh_morph[mesh] = std::move(morph);
+  return 0;
+}
+
+int lumc_mesh_morph_unbind(LumContext* ctx, uint32_t mesh) {
+  if (!ctx) return 1;
+  const auto it = ctx->mesh_morph.find(mesh);
+  if (it == ctx->mesh_morph.end()) { ctx->error = "lumc_mesh_morph_unbind: mesh " + std::to_string(mesh) + " is not bound"; return 1; }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  ctx->mesh_morph.erase(it);
+  return 0;
+}
+
+int lumc_mesh_morph_weights(LumContext* ctx, uint32_t mesh, const float* weights, uint32_t target_count) {
+  if (!ctx) return 1;
+  const auto it = ctx->mesh_morph.find(mesh);
+  if (it == ctx->mesh_morph.end()) { ctx->error = "lumc_mesh_morph_weights: mesh " + std::to_string(mesh) + " is not bound"; return 1; }
+  if (!weights || target_count != it->second.target_count) { ctx->error = "lumc_mesh_morph_weights: mesh " + std::to_string(mesh) + " is bound to another target count"; return 1; }
+  for (uint32_t t = 0; t < target_count; t++)
+    if (!std::isfinite(weights[t])) { ctx->error = "lumc_mesh_morph_weights: a weight is not finite"; return 1; }
+  it->second.pending.assign(weights, weights + target_count);
+  return 0;
+}
+
+int lumc_mesh_morph_stats(const LumContext* ctx, LumMeshMorphStats* out) {
+  if (!ctx || !out) return 1;
+  *out = ctx->morph_stats;
   return 0;
 }
 

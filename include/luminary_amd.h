@@ -274,6 +274,7 @@ LUMINARY_API LuminaryResult luminary_host_request_sky_hdri_build(LuminaryHost* h
 
 /* ---- additive extension (not in the reference) ---- */
 struct LumDeviceSceneView;
+struct LumLightRefitPlan;
 /* ---- "extra utils" frontends link against: reference include/luminary/{host_memory,array,queue,ringbuffer,thread_status,log,name_strings}.h ---- */
 #define host_malloc(ptr, size) _host_malloc((void**) (ptr), (size), (const char*) #ptr, (const char*) __func__, __LINE__)
 #define host_realloc(ptr, size) _host_realloc((void**) (ptr), (size), (const char*) #ptr, (const char*) __func__, __LINE__)
@@ -512,6 +513,25 @@ LUMINARY_API LuminaryResult luminary_ext_path_extend(const char* base_file, cons
 /* rotation_euler_angles_to_quaternion (src/luminary/host_math.c:6-21), x y z w */
 LUMINARY_API LuminaryResult luminary_ext_euler_to_quaternion(const float rotation[3], float quaternion[4]);
 LUMINARY_API LuminaryResult luminary_ext_build_device_scene(LuminaryHost* host, const struct LumDeviceSceneView** view);
+/* Refit of the light tree on the devices (include/lum_core.h lumc_light_refit_bind). Off (the default): every edit that moves an emissive
+ * triangle - luminary_ext_set_mesh_positions, luminary_ext_set_instance_transforms, luminary_ext_set_mesh_pose, luminary_ext_set_mesh_weights - builds the light
+ * tree again on the host, and a posed or blended mesh that emits is brought up to date on the CPU at once. On: the tree of the last host build keeps its topology
+ * and every device computes its statistics, the light BVH and the light table again from the vertices it holds; a posed or blended emitter stays lazy on the host.
+ * Where a device cannot refit - a triangle collapsed or stopped being finite, or the root's cost grew beyond max_cost_growth (0: never rebuild for quality) - the
+ * host builds the tree again, as with the switch off. The setting is remembered across uploads. The view of luminary_ext_build_device_scene holds the light
+ * arrays as the devices hold them. */
+LUMINARY_API LuminaryResult luminary_ext_set_light_refit(LuminaryHost* host, uint32_t on, float max_cost_growth);
+typedef struct LuminaryLightRefitStats {
+  uint64_t refits, fallbacks;           /* updates of the main device's context that refitted the lights / that asked for a rebuild, since it was created */
+  uint32_t last_launches, last_flags;   /* its last such update: kernels launched; why it fell back (LUMC_LIGHT_REFIT_*) */
+  uint64_t last_bytes_uploaded, last_bytes_downloaded;
+  double seconds, seconds_fragments, seconds_stats, seconds_nodes, seconds_light_bvh, seconds_table, cost_growth; /* as LumLightRefitStats (include/lum_core.h) */
+  uint64_t host_rebuilds;               /* times the host built the light tree again because a device asked for it, since the host was created */
+} LuminaryLightRefitStats;
+LUMINARY_API LuminaryResult luminary_ext_get_light_refit_stats(LuminaryHost* host, LuminaryLightRefitStats* out);
+/* What the last build of the light tree left behind for its refit on a device (lum_core.h LumLightRefitPlan, lumc_light_refit_bind, lumc_light_refit_host): it
+ * belongs to the light arrays of the view luminary_ext_build_device_scene returns. The pointers stay valid until the host builds the light tree again. */
+LUMINARY_API LuminaryResult luminary_ext_get_light_refit_plan(LuminaryHost* host, struct LumLightRefitPlan* plan);
 /* Synchronous batch rendering of sample ids [first_sample, first_sample + num_samples) of `pixels` (NULL = all) on this process' GPU. */
 LUMINARY_API LuminaryResult luminary_ext_render_samples(
   LuminaryHost* host, const uint32_t* pixels, uint32_t num_pixels, uint32_t first_sample, uint32_t num_samples, uint32_t samples_per_pass);

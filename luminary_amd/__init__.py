@@ -183,6 +183,13 @@ class ResidentRefitStats(C.Structure):
                 ("seconds_top_level", C.c_double)]
 
 
+class LightRefitStats(C.Structure):
+    """LuminaryLightRefitStats"""
+    _fields_ = [("refits", C.c_uint64), ("fallbacks", C.c_uint64), ("last_launches", C.c_uint32), ("last_flags", C.c_uint32), ("last_bytes_uploaded", C.c_uint64),
+                ("last_bytes_downloaded", C.c_uint64), ("seconds", C.c_double), ("seconds_fragments", C.c_double), ("seconds_stats", C.c_double), ("seconds_nodes", C.c_double),
+                ("seconds_light_bvh", C.c_double), ("seconds_table", C.c_double), ("cost_growth", C.c_double), ("host_rebuilds", C.c_uint64)]
+
+
 class MeshSkinStats(C.Structure):
     """LuminaryMeshSkinStats"""
     _fields_ = [("poses", C.c_uint64), ("rebuild_downloads", C.c_uint64), ("last_meshes", C.c_uint32), ("last_launches", C.c_uint32), ("last_bytes_uploaded", C.c_uint64),
@@ -657,6 +664,26 @@ class Host:
         view = p.contents
         view._owner = self  # the buffers behind the pointers live in the host
         return view
+
+    def set_light_refit(self, on=1, max_cost_growth=0.0):
+        """luminary_ext_set_light_refit: 1 = edits that move an emissive triangle refit the light tree on the devices instead of building it again on the host;
+        max_cost_growth > 0: build again when the root's cost grew beyond this factor."""
+        _call("luminary_ext_set_light_refit", self._h, C.c_uint32(on), C.c_float(max_cost_growth))
+
+    def light_refit_stats(self):
+        """luminary_ext_get_light_refit_stats: the main device's refit stats and host_rebuilds, as a dict."""
+        s = LightRefitStats()
+        _call("luminary_ext_get_light_refit_stats", self._h, C.byref(s))
+        return {name: getattr(s, name) for name, _ in s._fields_}
+
+    def light_refit_plan(self):
+        """luminary_ext_get_light_refit_plan: the core.LightRefitPlan of the light arrays of device_scene() (its pointers are valid until the host builds the light
+        tree again; .copy() gives one that owns its arrays). Needs no GPU."""
+        from .core import LightRefitPlan
+        plan = LightRefitPlan()
+        _call("luminary_ext_get_light_refit_plan", self._h, C.byref(plan))
+        plan._owner = self
+        return plan
 
     def render_samples(self, first_sample, num_samples, pixels=None, samples_per_pass=1):
         import numpy as np

@@ -9,6 +9,7 @@ DIRTY_CONSTANTS, DIRTY_MATERIALS, DIRTY_INSTANCES, DIRTY_LIGHTS, DIRTY_MESHES, D
 DIRTY_MESH_POSITIONS = 128  # moved vertices: refit (not part of DIRTY_ALL, which builds)
 DIRTY_INSTANCE_TRANSFORMS = 256  # moved instances: the top level is rebuilt on the device, the mesh trees stay (not part of DIRTY_ALL)
 DIRTY_MESH_SKIN = 512  # bound meshes posed (Core.mesh_skin_pose): their vertices are written on the device, then they are refitted (not part of DIRTY_ALL)
+DIRTY_LIGHT_POSITIONS = 1024  # emissive triangles moved: the bound light tree is refitted on the device (Core.light_refit_bind; not part of DIRTY_ALL)
 BVH_BUILDERS = {"sah": 0, "lbvh": 1, "ploc": 2, "sah_gpu": 3}
 CNT_TRACE, CNT_SHADOW, CNT_LIGHT_BVH, CNT_VERTICES, CNT_NODES, CNT_TRIS, CNT_NODES_SHADOW, CNT_TRIS_SHADOW, CNT_NODES_LIGHT, CNT_TRIS_LIGHT, CNT_NODES_LDS, CNT_NODES_LDS_SHADOW, CNT_AMBIENT_DEFERRED, CNT_AMBIENT_FALLBACK = range(14)
 CNT_COUNT = 16  # LUMC_CNT_COUNT
@@ -187,6 +188,101 @@ def morph_host(base_positions, base_normals, offsets, corners, delta_positions, 
           op.ctypes.data, on.ctypes.data, pk.ctypes.data) != 0:
         raise CoreError("lumc_morph_host refused its arguments (1 ... 1024 targets, offsets from 0 that do not decrease, corners of a target strictly increasing and below 3 n, finite deltas and weights)")
     return op, on, pk
+
+
+class LightRefitPlan(C.Structure):
+    """LumLightRefitPlan: what the last build of the light tree left behind for its refit (Host.light_refit_plan). fragments: [n, 8] uint32 words (instance, mesh,
+    triangle, light id, transform, intensity and average intensity as float bits, 0); transforms: [t, 10] float32 (q, scale, offset); slots: [128 + 8 nodes, 2]."""
+    _fields_ = [("fragments", C.c_void_p), ("transforms", C.c_void_p), ("transform_instances", C.c_void_p), ("slots", C.c_void_p), ("num_fragments", C.c_uint32),
+                ("num_transforms", C.c_uint32), ("num_nodes", C.c_uint32), ("reserved", C.c_uint32), ("root_cost", C.c_double)]
+
+    @classmethod
+    def from_arrays(cls, fragments, transforms, transform_instances, slots, root_cost):
+        """A plan over copies of the arrays (kept alive by the plan)."""
+        f = np.ascontiguousarray(fragments, dtype=np.uint32).reshape(-1, 8).copy()
+        t = np.ascontiguousarray(transforms, dtype=np.float32).reshape(-1, 10).copy()
+        ti = np.ascontiguousarray(transform_instances, dtype=np.uint32).reshape(-1).copy()
+        sl = np.ascontiguousarray(slots, dtype=np.uint32).reshape(-1, 2).copy()
+        assert len(sl) >= 128 and (len(sl) - 128) % 8 == 0 and len(t) == len(ti)
+        plan = cls(f.ctypes.data, t.ctypes.data, ti.ctypes.data, sl.ctypes.data, len(f), len(t), (len(sl) - 128) // 8, 0, float(root_cost))
+        plan._keepalive = (f, t, ti, sl)
+        return plan
+
+    def arrays(self):
+        """Copies: (fragments [n, 8] uint32, transforms [t, 10] float32, transform_instances [t] uint32, slots [128 + 8 nodes, 2] uint32)."""
+        def take(ptr, count, dtype, shape):
+            if not ptr or not count:
+                return np.zeros(shape, dtype)
+            return np.frombuffer(C.string_at(ptr, count * np.dtype(dtype).itemsize), dtype=dtype).reshape(shape).copy()
+        n, t, s = self.num_fragments, self.num_transforms, 128 + 8 * self.num_nodes
+        return (take(self.fragments, 8 * n, np.uint32, (n, 8)), take(self.transforms, 10 * t, np.float32, (t, 10)), take(self.transform_instances, t, np.uint32, (t,)),
+                take(self.slots, 2 * s, np.uint32, (s, 2)))
+
+    def copy(self):
+        return LightRefitPlan.from_arrays(*self.arrays(), self.root_cost)
+
+
+class LightRefitReport(C.Structure):
+    """LumLightRefitReport"""
+    _fields_ = [("refitted", C.c_uint32), ("flags", C.c_uint32), ("cost", C.c_double), ("cost_growth", C.c_double)]
+
+
+class LightRefitStats(C.Structure):
+    """LumLightRefitStats"""
+    _fields_ = [("refits", C.c_uint64), ("fallbacks", C.c_uint64), ("last_launches", C.c_uint32), ("last_flags", C.c_uint32), ("last_bytes_uploaded", C.c_uint64),
+                ("last_bytes_downloaded", C.c_uint64), ("seconds", C.c_double), ("seconds_fragments", C.c_double), ("seconds_stats", C.c_double), ("seconds_nodes", C.c_double),
+                ("seconds_light_bvh", C.c_double), ("seconds_table", C.c_double), ("cost_growth", C.c_double)]
+
+
+LIGHT_REFIT_ZERO_AREA, LIGHT_REFIT_NOT_FINITE = 1, 2
+
+
+def light_refit_host(plan, vertices, mesh_tri_offset, root, root_children, nodes):
+    """lumc_light_refit_host, no device needed: the host twin of the light tree's refit kernels - the definition of their bytes. vertices: the view's vertex records
+    [corners, 4] (float32, or their uint32 words); root / root_children / nodes: the last build's arrays (copied, not changed). Returns a dict: root, root_children,
+    nodes (uint8 / float32 / uint8 [n, 64]), light_bvh_tris [lights, 12] float32, slot_stats [slots, 8] float32, report (LightRefitReport). With report.refitted == 0
+    the arrays are the inputs."""
+    fn = _lib().lumc_light_refit_host
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p] * 9
+    v = np.ascontiguousarray(vertices)
+    assert v.dtype.itemsize == 4 and v.size % 12 == 0
+    off = np.ascontiguousarray(mesh_tri_offset, dtype=np.uint32)
+    r = np.ascontiguousarray(root, dtype=np.uint8).reshape(-1).copy()
+    rc = np.ascontiguousarray(root_children, dtype=np.float32).reshape(-1).copy()
+    nd = np.ascontiguousarray(nodes, dtype=np.uint8).reshape(-1, 64).copy()
+    tris = np.zeros((plan.num_fragments, 12), np.float32)
+    stats = np.zeros((128 + 8 * plan.num_nodes, 8), np.float32)
+    report = LightRefitReport()
+    if fn(C.addressof(plan), v.ctypes.data, off.ctypes.data, _addr(r), _addr(rc), _addr(nd), _addr(tris), stats.ctypes.data, C.addressof(report)) != 0:
+        raise CoreError("lumc_light_refit_host refused its arguments")
+    return {"root": r, "root_children": rc, "nodes": nd, "light_bvh_tris": tris, "slot_stats": stats, "report": report}
+
+
+def light_refit_ceil_log2(x):
+    """lumc_light_refit_ceil_log2: the exact ceil(log2(x)) of a finite float32 x > 0, as the refit's quantiser takes it."""
+    fn = _lib().lumc_light_refit_ceil_log2
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_float]
+    return int(fn(float(np.float32(x))))
+
+
+def light_root_children(root):
+    """The float table of a root's children as an upload makes it (64 floats per section + 16): mean = byte * 2^e + base per axis, sigma = byte * 2^e_sigma, power."""
+    root = np.ascontiguousarray(root, dtype=np.uint8).reshape(-1)
+    sections = int(root[10])
+    base = (root[:6].view(np.uint16).astype(np.uint32) << 16).view(np.float32)
+    e = root[12:16].view(np.int8).astype(np.int32)
+    table = np.zeros(sections * 64 + 16, np.float32)
+    for s in range(sections):
+        sec = root[16 + 48 * s:16 + 48 * (s + 1)]
+        for c in range(8):
+            o = (s * 8 + c) * 8
+            for a in range(3):
+                table[o + a] = np.float32(np.float32(sec[8 * a + c]) * np.ldexp(np.float32(1), e[a])) + base[a]
+            table[o + 3] = np.float32(sec[24 + c]) * np.ldexp(np.float32(1), e[3])
+            table[o + 4] = np.float32(sec[32 + 2 * c:34 + 2 * c].view(np.uint16)[0])
+    return table
 
 
 def instance_boxes_probe(view, mesh_boxes, on_gpu=False):
@@ -688,6 +784,40 @@ class Core:
     def mesh_morph_stats(self):
         out = MeshMorphStats()
         self._call("lumc_mesh_morph_stats", C.byref(out))
+        return out
+
+    def set_light_refit(self, max_cost_growth=0.0):
+        """lumc_set_light_refit: DIRTY_LIGHT_POSITIONS updates leave the lights alone (needs_rebuild) beyond this growth of the root's cost; 0: never for quality."""
+        self._call("lumc_set_light_refit", C.c_float(max_cost_growth))
+
+    def light_refit_bind(self, plan):
+        """lumc_light_refit_bind: right after an update that took DIRTY_LIGHTS, the plan of the light tree it uploaded (Host.light_refit_plan)."""
+        self._call("lumc_light_refit_bind", C.byref(plan))
+
+    def light_refit_transforms(self, transforms):
+        """lumc_light_refit_transforms: the plan's transform table again [t, 10] (moved instances); pending until the next DIRTY_LIGHT_POSITIONS update."""
+        t = np.ascontiguousarray(transforms, dtype=np.float32).reshape(-1, 10)
+        self._call("lumc_light_refit_transforms", C.c_void_p(t.ctypes.data), C.c_uint32(len(t)))
+
+    def light_refit_needs_rebuild(self):
+        fn = self._lib.lumc_light_refit_needs_rebuild
+        fn.restype = C.c_int
+        return bool(fn(self._ctx))
+
+    def light_refit_stats(self):
+        out = LightRefitStats()
+        self._call("lumc_light_refit_stats", C.byref(out))
+        return out
+
+    def light_arrays_probe(self):
+        """lumc_light_arrays_probe: the light structures as the device holds them: a dict of root (uint8), root_children (float32), nodes (uint8 [n, 64]), table
+        ([lights, 16] uint32 words), bvh_nodes ([n, 32] uint32 words), bvh_tris ([n, 12] uint32 words)."""
+        sizes = (C.c_uint64 * 6)()
+        null = C.c_void_p(0)
+        self._call("lumc_light_arrays_probe", sizes, null, null, null, null, null, null)
+        out = {"root": np.zeros(int(sizes[0]), np.uint8), "root_children": np.zeros(int(sizes[1]), np.float32), "nodes": np.zeros((int(sizes[2]) // 64, 64), np.uint8),
+               "table": np.zeros((int(sizes[3]) // 4, 16), np.uint32), "bvh_nodes": np.zeros((int(sizes[4]), 32), np.uint32), "bvh_tris": np.zeros((int(sizes[5]), 12), np.uint32)}
+        self._call("lumc_light_arrays_probe", sizes, *[_addr(out[k]) for k in ("root", "root_children", "nodes", "table", "bvh_nodes", "bvh_tris")])
         return out
 
     def mesh_vertices_probe(self, mesh, triangles):

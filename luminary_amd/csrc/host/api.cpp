@@ -29,6 +29,7 @@
 #include "loaders.h"
 #include "scene.h"
 #define LUM_SKIN_HOST_ONLY 1  // the host twin's declaration only: this unit touches no device
+#include "light_refit.h"
 #include "mesh_morph.h"
 #include "mesh_skin.h"
 
@@ -81,6 +82,10 @@ struct LuminaryHost {
   float refit_max_cost_growth = 0.0f;
   uint32_t instance_update_mode = 0;      // luminary_ext_set_instance_update: likewise
   uint32_t refit_in_place = 0;            // luminary_ext_set_mesh_refit_in_place: likewise
+  uint32_t light_refit = 0;               // luminary_ext_set_light_refit: moved emitters refit the light tree on the devices (remembered across uploads)
+  float light_refit_max_cost_growth = 0.0f;
+  bool view_lights_stale = false;         // the devices refitted their light trees since `device_scene`'s light arrays were made: brought up to date when something reads them
+  uint64_t light_rebuilds = 0;            // times a device asked for a rebuild of the light tree and the host built it
   bool device_scene_valid = false;
   bool core_scene_valid = false;
   uint32_t core_width = 0, core_height = 0;  // frame size the main context's pixel set was made for
@@ -136,6 +141,10 @@ std::vector<uint32_t> embedded_bluenoise() {
   std::memcpy(v.data(), lum_embedded_bluenoise_2d, v.size() * 4);
   return v;
 }
+
+// What an edit that moves an emissive triangle marks: the light tree is built again on the host (the default), or - luminary_ext_set_light_refit - refitted on
+// the devices.
+uint32_t moved_emitter_bit(const LuminaryHost* h) { return h->light_refit ? LUMC_DIRTY_LIGHT_POSITIONS : LUMC_DIRTY_LIGHTS; }
 
 void invalidate(LuminaryHost* h, uint32_t dirty = LUMC_DIRTY_ALL) {
   h->scene_dirty |= dirty; h->core_dirty |= dirty;
@@ -227,6 +236,32 @@ bool mesh_emits(const LuminaryHost* h, uint32_t mesh) {
   return false;
 }
 
+// The view's light arrays and the plan built again from the scene as it stands, the posed and blended emitters brought up to date first (today's path of a moved
+// emitter). Nonzero on failure.
+int build_view_lights(LuminaryHost* h) {
+  for (auto& kv : h->skins)
+    if (kv.first < h->scene.meshes.size() && mesh_emits(h, kv.first)) materialise(h, kv.first);
+  const std::string err = lum::update_device_scene(h->scene, h->device_scene.bluenoise, LUMC_DIRTY_LIGHTS, &h->device_scene);
+  if (!err.empty()) { h->log.push_back(err); return 1; }
+  h->view_lights_stale = false;
+  return 0;
+}
+
+// While the devices refit, the view's light arrays and the plan's transforms are those of the last host build. A context that is about to take the lights' part
+// from the view - a new main context, a slot that was just enabled, a pending LUMC_DIRTY_LIGHTS - would get that tree over the moved vertices, so the tree is
+// built first from the scene as it stands, and every context takes it: all devices sample with the same tree.
+int resolve_stale_lights(LuminaryHost* h, bool partition) {  // partition: the enabled slots are about to render too
+  if (!h->view_lights_stale) return 0;
+  bool taken = (h->core_dirty & LUMC_DIRTY_LIGHTS) != 0;
+  for (uint32_t i = 0; partition && i < h->devices.size(); i++)
+    if (i != h->main_slot && h->devices[i].enabled && (!h->devices[i].core || (h->devices[i].dirty & LUMC_DIRTY_LIGHTS))) taken = true;
+  if (!taken) return 0;
+  if (build_view_lights(h)) return 1;
+  h->core_dirty |= LUMC_DIRTY_LIGHTS; h->core_scene_valid = false;
+  for (auto& slot : h->devices) { slot.dirty |= LUMC_DIRTY_LIGHTS; slot.scene_valid = false; }
+  return 0;
+}
+
 // Bindings, poses and weights a context has not seen, before it takes the scene (lumc_scene_update with `dirty`); after an update that rebuilt the meshes - which
 // drops the context's bindings - all of them again, and the poses and weights applied in a second, vertex-only update. *seen: the context's mark
 // (LuminaryHost::skin_serial then).
@@ -250,15 +285,42 @@ int update_context_scene(LuminaryHost* h, LumContext* core, uint32_t dirty, uint
     return 0;
   };
   const bool rebuilds_meshes = (dirty & LUMC_DIRTY_MESHES) != 0;
+  const bool refits_lights = h->light_refit && (dirty & LUMC_DIRTY_LIGHT_POSITIONS) && !(dirty & LUMC_DIRTY_LIGHTS);
+  // the plan of the light arrays the context just took, right after an update that took LUMC_DIRTY_LIGHTS
+  auto bind_lights = [&]() {
+    if (!h->light_refit) return 0;
+    const LumLightRefitPlan plan = h->device_scene.light_refit_plan.view();
+    return (lumc_set_light_refit(core, h->light_refit_max_cost_growth) || lumc_light_refit_bind(core, &plan)) ? 1 : 0;
+  };
+  if (refits_lights && (dirty & LUMC_DIRTY_INSTANCE_TRANSFORMS)) {  // 40 bytes per emitting instance
+    lum::refresh_light_refit_transforms(h->scene, &h->device_scene.light_refit_plan);
+    const auto& t = h->device_scene.light_refit_plan.transforms;
+    if (!t.empty() && lumc_light_refit_transforms(core, t.data(), (uint32_t) t.size())) return 1;
+  }
   bool pending = false;
   if (!rebuilds_meshes)
     for (const auto& kv : h->skins)
       if (hand_over(kv.first, kv.second, false, &pending)) return 1;
   if (lumc_scene_update(core, &h->device_scene.view, dirty)) return 1;
+  if ((dirty & LUMC_DIRTY_LIGHTS) && bind_lights()) return 1;
+  // a device that could not refit asked for a rebuild: today's path - the emitters on the host, the tree built again, the lights' part uploaded - for every
+  // device, so that all sample with the same tree
+  auto rebuild_lights_if_asked = [&]() {
+    if (!h->light_refit || !lumc_light_refit_needs_rebuild(core)) return 0;
+    if (build_view_lights(h)) return 1;
+    h->light_rebuilds++;
+    if (core != h->core) { h->core_dirty |= LUMC_DIRTY_LIGHTS; h->core_scene_valid = false; }
+    for (auto& slot : h->devices)
+      if (slot.core != core) { slot.dirty |= LUMC_DIRTY_LIGHTS; slot.scene_valid = false; }
+    return (lumc_scene_update(core, &h->device_scene.view, LUMC_DIRTY_LIGHTS) || bind_lights()) ? 1 : 0;
+  };
+  if (refits_lights && rebuild_lights_if_asked()) return 1;
   if (rebuilds_meshes) {
     for (const auto& kv : h->skins)
       if (hand_over(kv.first, kv.second, true, &pending)) return 1;
-    if (pending && lumc_scene_update(core, &h->device_scene.view, LUMC_DIRTY_MESH_SKIN)) return 1;
+    // (the pose moves an emitter after the tree was uploaded: with the switch on the devices refit for it as for any pose)
+    if (pending && lumc_scene_update(core, &h->device_scene.view, LUMC_DIRTY_MESH_SKIN | (h->light_refit ? LUMC_DIRTY_LIGHT_POSITIONS : 0))) return 1;
+    if (pending && rebuild_lights_if_asked()) return 1;
   }
   *seen = h->skin_serial;
   return 0;
@@ -284,6 +346,8 @@ LuminaryResult ensure_device_scene(LuminaryHost* h) {
   // what was re-encoded is what the devices have to take over (the encoder may add a part: the texture pool when the sky mode moves the moon in or out)
   h->core_dirty |= h->device_scene.rebuilt;
   for (auto& slot : h->devices) slot.dirty |= h->device_scene.rebuilt;
+  if (h->scene_dirty & LUMC_DIRTY_LIGHTS) h->view_lights_stale = false;
+  else if (h->scene_dirty & LUMC_DIRTY_LIGHT_POSITIONS) h->view_lights_stale = true;  // the devices refit; the view's light arrays follow when something reads them
   h->scene_dirty = 0;
   h->device_scene_valid = true;
   h->core_scene_valid = false;
@@ -312,10 +376,12 @@ LuminaryResult ensure_core(LuminaryHost* h) {
   }
   const LuminaryResult r = ensure_device_scene(h);
   if (r) return r;
+  if (resolve_stale_lights(h, false)) return LUMINARY_ERROR_API_EXCEPTION;
   if (!h->core_scene_valid) {
     lumc_set_mesh_refit(h->core, h->refit_mode, h->refit_max_cost_growth);
     lumc_set_instance_update(h->core, h->instance_update_mode);
     lumc_set_mesh_refit_in_place(h->core, h->refit_in_place);
+    lumc_set_light_refit(h->core, h->light_refit_max_cost_growth);
     if (update_context_scene(h, h->core, h->core_dirty, &h->core_skin_seen)) { std::fprintf(stderr, "[luminary_amd] %s\n", lumc_last_error(h->core)); h->core_dirty = LUMC_DIRTY_ALL; return LUMINARY_ERROR_CUDA; }
     h->core_dirty = 0;
     h->core_scene_valid = true;
@@ -341,6 +407,8 @@ std::vector<LuminaryHost::DeviceSlot*> enabled_slots(LuminaryHost* h) {
 
 // Contexts with the current scene on every device of the partition; slot 0 of the result is the main device (h->core).
 LuminaryResult ensure_partition_cores(LuminaryHost* h, std::vector<LumContext*>* cores) {
+  if (const LuminaryResult rs = ensure_device_scene(h)) return rs;
+  if (resolve_stale_lights(h, true)) return LUMINARY_ERROR_API_EXCEPTION;  // (before the main context takes its update: every slot gets the same tree)
   const LuminaryResult r = ensure_core(h);
   if (r) return r;
   cores->clear();
@@ -360,6 +428,7 @@ LuminaryResult ensure_partition_cores(LuminaryHost* h, std::vector<LumContext*>*
       lumc_set_mesh_refit(slot->core, h->refit_mode, h->refit_max_cost_growth);
       lumc_set_instance_update(slot->core, h->instance_update_mode);
       lumc_set_mesh_refit_in_place(slot->core, h->refit_in_place);
+      lumc_set_light_refit(slot->core, h->light_refit_max_cost_growth);
       if (update_context_scene(h, slot->core, slot->dirty, &slot->skin_seen)) { std::fprintf(stderr, "[luminary_amd] device %d: %s\n", slot->ordinal, lumc_last_error(slot->core)); slot->dirty = LUMC_DIRTY_ALL; return LUMINARY_ERROR_CUDA; }
       slot->dirty = 0;
       slot->scene_valid = true;
@@ -906,7 +975,7 @@ LuminaryResult luminary_ext_set_mesh_positions(LuminaryHost* host, uint32_t mesh
   std::memmove(m.positions.data(), positions, sizeof(float) * 9 * (size_t) triangle_count);
   if (!normals) face_normals(m.positions.data(), triangle_count, m.normals.data());
   if (std::find(host->moved_meshes.begin(), host->moved_meshes.end(), mesh_id) == host->moved_meshes.end()) host->moved_meshes.push_back(mesh_id);
-  invalidate(host, LUMC_DIRTY_MESH_POSITIONS | LUMC_DIRTY_LIGHTS);  // the vertices and the mesh's tree; the light tree follows moved emitters
+  invalidate(host, LUMC_DIRTY_MESH_POSITIONS | moved_emitter_bit(host));  // the vertices and the mesh's tree; the light tree follows moved emitters
   return LUMINARY_SUCCESS;
 }
 static void mark_moved(LuminaryHost* host, uint32_t mesh_id) {
@@ -916,7 +985,10 @@ static void mark_moved(LuminaryHost* host, uint32_t mesh_id) {
 static void deformed(LuminaryHost* host, uint32_t mesh_id, HostSkin& k) {
   k.host_current = false; k.view_current = false;
   uint32_t dirty = LUMC_DIRTY_MESH_SKIN;
-  if (mesh_emits(host, mesh_id)) { materialise(host, mesh_id); dirty |= LUMC_DIRTY_LIGHTS; }  // the light tree is built from the host mesh: the existing path
+  if (mesh_emits(host, mesh_id)) {
+    if (host->light_refit) dirty |= LUMC_DIRTY_LIGHT_POSITIONS;  // the devices refit the light tree from the vertices they write: the host mesh stays lazy
+    else { materialise(host, mesh_id); dirty |= LUMC_DIRTY_LIGHTS; }  // the light tree is built from the host mesh
+  }
   invalidate(host, dirty);
 }
 // One of a mesh's two bindings went, or was replaced, while the other stays, and the one that went had shaped the mesh: the mesh is what the other one makes of the
@@ -931,7 +1003,7 @@ static void rebound(LuminaryHost* host, uint32_t mesh_id, HostSkin& k) {
   std::copy(k.rest_normals.begin(), k.rest_normals.end(), m.normals.begin());
   k.host_current = true; k.view_current = true;
   mark_moved(host, mesh_id);
-  invalidate(host, LUMC_DIRTY_MESH_POSITIONS | (mesh_emits(host, mesh_id) ? LUMC_DIRTY_LIGHTS : 0));
+  invalidate(host, LUMC_DIRTY_MESH_POSITIONS | (mesh_emits(host, mesh_id) ? moved_emitter_bit(host) : 0));
 }
 // The first binding of a mesh, or another of the only kind it holds: the rest shape is the host mesh as it is now (bound before: the current pose).
 static HostSkin& bind_fresh(LuminaryHost* host, uint32_t mesh_id) {
@@ -1129,7 +1201,7 @@ LuminaryResult luminary_ext_set_instance_transforms(LuminaryHost* host, const Lu
     lum::HostInstance& i = host->scene.instances[instances[k].id];
     i.translation = instances[k].position; i.rotation = instances[k].rotation; i.scale = instances[k].scale;
   }
-  invalidate(host, LUMC_DIRTY_INSTANCE_TRANSFORMS | LUMC_DIRTY_LIGHTS);  // the transforms and the top-level tree; the light tree follows moved emitters
+  invalidate(host, LUMC_DIRTY_INSTANCE_TRANSFORMS | moved_emitter_bit(host));  // the transforms and the top-level tree; the light tree follows moved emitters
   return LUMINARY_SUCCESS;
 }
 LuminaryResult luminary_ext_set_instance_update(LuminaryHost* host, uint32_t mode) {
@@ -1211,7 +1283,61 @@ LuminaryResult luminary_ext_build_device_scene(LuminaryHost* host, const LumDevi
     const std::string err = lum::update_device_scene(host->scene, host->device_scene.bluenoise, LUMC_DIRTY_MESH_POSITIONS, &host->device_scene);
     if (!err.empty()) return LUMINARY_ERROR_API_EXCEPTION;
   }
+  if (host->view_lights_stale) {
+    // the view's light arrays as the devices now hold them: the twin of their kernels over the view's vertices; where that reports a fragment that left the set
+    // of lights (the devices asked for a rebuild, or will) the tree is built again
+    lum::DeviceSceneBuffers& b = host->device_scene;
+    lum::refresh_light_refit_transforms(host->scene, &b.light_refit_plan);
+    const LumLightRefitPlan plan = b.light_refit_plan.view();
+    LumLightRefitReport report{};
+    bool refitted = false;
+    if (plan.num_fragments >= 2 && !b.light_tree_root.empty()) {
+      std::vector<float> table((size_t) b.light_tree_root[10] * 64 + 16, 0.0f);
+      refitted = lum::light_refit_host(&plan, b.vertices.data(), b.mesh_tri_offset.data(), b.light_tree_root.data(), table.data(), b.light_tree_nodes.data(), b.light_bvh_tris.data(),
+                                       nullptr, &report) == 0 && report.refitted;
+    }
+    if (!refitted && plan.num_fragments) {
+      const std::string err = lum::update_device_scene(host->scene, b.bluenoise, LUMC_DIRTY_LIGHTS, &b);
+      if (!err.empty()) return LUMINARY_ERROR_API_EXCEPTION;
+      host->core_dirty |= LUMC_DIRTY_LIGHTS; host->core_scene_valid = false;
+      for (auto& slot : host->devices) { slot.dirty |= LUMC_DIRTY_LIGHTS; slot.scene_valid = false; }
+    }
+    host->view_lights_stale = false;
+  }
   *view = &host->device_scene.view;
+  return LUMINARY_SUCCESS;
+}
+LuminaryResult luminary_ext_set_light_refit(LuminaryHost* host, uint32_t on, float max_cost_growth) {
+  CHECK_NULL(host);
+  ApiLock lock(host);
+  if (on > 1 || !(max_cost_growth >= 0.0f) || !std::isfinite(max_cost_growth)) return LUMINARY_ERROR_INVALID_API_ARGUMENT;
+  const bool switched = (on != 0) != (host->light_refit != 0);
+  host->light_refit = on; host->light_refit_max_cost_growth = max_cost_growth;
+  // Switched on: the contexts get the plan with their next LUMC_DIRTY_LIGHTS update, so the lights' part is handed over once more. Switched off: the tree is built
+  // from the scene as it stands and every context takes it, which drops its binding - from there on every path is the one without the switch, whatever was refitted
+  // or still pending before.
+  if (switched) invalidate(host, LUMC_DIRTY_LIGHTS);
+  return LUMINARY_SUCCESS;
+}
+LuminaryResult luminary_ext_get_light_refit_stats(LuminaryHost* host, LuminaryLightRefitStats* out) {
+  CHECK_NULL(host); CHECK_NULL(out);
+  ApiLock lock(host);
+  std::memset(out, 0, sizeof(*out));
+  out->host_rebuilds = host->light_rebuilds;
+  if (!host->core) return LUMINARY_SUCCESS;
+  LumLightRefitStats s;
+  if (lumc_light_refit_stats(host->core, &s)) return LUMINARY_ERROR_API_EXCEPTION;
+  static_assert(sizeof(LuminaryLightRefitStats) == sizeof(LumLightRefitStats) + sizeof(uint64_t) && offsetof(LuminaryLightRefitStats, host_rebuilds) == sizeof(LumLightRefitStats),
+                "the public struct mirrors the core's, host_rebuilds behind it");
+  std::memcpy(out, &s, sizeof(s));
+  return LUMINARY_SUCCESS;
+}
+LuminaryResult luminary_ext_get_light_refit_plan(LuminaryHost* host, LumLightRefitPlan* plan) {
+  CHECK_NULL(host); CHECK_NULL(plan);
+  ApiLock lock(host);
+  const LuminaryResult r = ensure_device_scene(host);
+  if (r) return r;
+  *plan = host->device_scene.light_refit_plan.view();
   return LUMINARY_SUCCESS;
 }
 namespace {

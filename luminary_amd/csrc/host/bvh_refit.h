@@ -28,7 +28,7 @@ struct RefitPlan {
 hipError_t refit_plan_create(RefitPlan& plan, const Bvh4& tree, uint32_t count);
 // One refit on the current device. The primitives' boxes come from d_vertices (the mesh's first vertex in the device scene: 3 float4 per triangle), in which
 // case the 9 geometry floats of the mesh's traversal triangles d_tris (leaf order) are rewritten too, or - d_vertices null - from host_boxes (by primitive id).
-// out_nodes receives plan.num_nodes refitted nodes, root_box the exact box of everything. Synchronises the device. download_seconds (optional): the host's wall
+// out_nodes - host memory, or device memory of the current device - receives plan.num_nodes refitted nodes, root_box the exact box of everything. Synchronises the device. download_seconds (optional): the host's wall
 // clock from the last launch to the end of the copies, i.e. the wait for the kernels and the download.
 hipError_t refit_run(RefitPlan& plan, const float4* d_vertices, BvhTri* d_tris, const Aabb* host_boxes, Bvh4Node* out_nodes, Aabb* root_box, double* download_seconds = nullptr);
 

@@ -229,7 +229,7 @@ hipError_t refit_run(RefitPlan& plan, const float4* d_vertices, BvhTri* d_tris, 
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
   const auto t_download = std::chrono::steady_clock::now();
-  if ((e = hipMemcpy(out_nodes, plan.nodes.get(), sizeof(Bvh4Node) * plan.num_nodes, hipMemcpyDeviceToHost)) != hipSuccess) return e;  // (waits for the launches)
+  if ((e = hipMemcpy(out_nodes, plan.nodes.get(), sizeof(Bvh4Node) * plan.num_nodes, hipMemcpyDefault)) != hipSuccess) return e;  // (waits for the launches; out_nodes may be device memory)
   e = hipMemcpy(root_box, plan.node_box.get(), sizeof(Aabb), hipMemcpyDeviceToHost);
   if (download_seconds) *download_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_download).count();
   return e;

@@ -20,6 +20,7 @@
 #include "bvh_refit.h"
 #include "device_buffer.h"
 #include "instance_update.h"
+#include "light_refit.h"
 #include "mesh_morph.h"
 #include "mesh_skin.h"
 #include "scene_arrays.h"
@@ -76,6 +77,13 @@ struct LumContext {
   // morphed meshes (lumc_mesh_morph_*; mesh_morph.hip, scene_device.hip skin_meshes): a mesh may hold both, then one kernel blends and poses it
   std::map<uint32_t, MeshMorph> mesh_morph;  // by mesh; dropped with the meshes
   LumMeshMorphStats morph_stats{};
+  // the light tree's refit (lumc_light_refit_*; light_refit.hip, scene_device.hip refit_lights)
+  LightRefit light_refit;                    // the bound plan; dropped by every update that takes new lights or new meshes
+  Bvh4 light_bvh;                            // the light BVH as the last LUMC_DIRTY_LIGHTS update built it: what a bind makes the refit's topology from
+  float light_refit_max_cost_growth = 0.0f;  // lumc_set_light_refit (0: never rebuild for quality)
+  bool light_refit_needs_rebuild = false;    // the last LUMC_DIRTY_LIGHT_POSITIONS update left the lights alone
+  bool lights_refitted = false;              // within an update: refit_lights ran, k_light_table follows
+  LumLightRefitStats light_refit_stats{};
   std::vector<uint32_t> sky_lut_key;  // the sky parameters the two sky tables were generated from
   DeviceBuffer<float> d_bridge_lut;   // the bridge sampler's vertex-count table (context-owned: scene.bridge_lut points here while bridges are possible)
   std::vector<float> bridge_lut_host; // its content, to notice a caller that hands over another table

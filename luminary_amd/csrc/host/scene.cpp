@@ -356,6 +356,7 @@ struct Fragment {  // device_light.h LightTreeFragment
   float w0 = 0.0f, w1 = 0.0f, w2 = 0.0f, wm = 0.0f;
   float power;
   uint32_t instance_id, tri_id;
+  uint32_t plan_id = 0;  // its entry of build_light_tree's fragment table as it was made: the partition moves whole records, so the plan follows it for free
 };
 
 struct BinaryNode {  // device_light.c:40-58 (fields that are used)
@@ -368,7 +369,7 @@ struct TreeNode {  // device_light.c:60-76
   float left_variance = 0.0f, right_variance = 0.0f, left_power = 0.0f, right_power = 0.0f;
   uint32_t child_ptr = kNull, light_ptr = 0, light_count = 0;
 };
-struct ChildNode { F3 mean{0, 0, 0}; float variance = 0.0f, power = 0.0f; bool is_leaf = false; };
+struct ChildNode { F3 mean{0, 0, 0}; float variance = 0.0f, power = 0.0f; bool is_leaf = false; uint32_t first = 0, count = 0; };  // first, count: the fragments it summarises (LightRefitPlan)
 
 // vec128_rotate_quaternion, host_intrinsics.h:202-213
 F3 rotate_q(F3 a, const float q[4]) {
@@ -547,6 +548,7 @@ struct Collapse {
   std::vector<uint32_t> jobs;
   std::vector<uint32_t> new_fragments;
   uint32_t triangles_ptr = 0;
+  void range_of(ChildNode& c, uint32_t node) const { c.first = (*bn)[node].light_ptr; c.count = (*bn)[node].light_count; }
 
   // device_light.c:664-848
   void collapse_node(const TreeNode& base, ChildNode* children, uint32_t* cbi, uint32_t max_children, uint32_t* light_ptr, uint32_t* child_count_out,
@@ -555,14 +557,14 @@ struct Collapse {
     uint32_t child_count = 0;
     bool work = false;
     if (base.light_count > 1) {
-      ChildNode l; l.mean = base.left_mean; l.variance = base.left_variance; l.power = base.left_power;
+      ChildNode l; l.mean = base.left_mean; l.variance = base.left_variance; l.power = base.left_power; range_of(l, base.child_ptr);
       cbi[child_count] = base.child_ptr; children[child_count++] = l;
-      ChildNode r; r.mean = base.right_mean; r.variance = base.right_variance; r.power = base.right_power;
+      ChildNode r; r.mean = base.right_mean; r.variance = base.right_variance; r.power = base.right_power; range_of(r, base.child_ptr + 1);
       cbi[child_count] = base.child_ptr + 1; children[child_count++] = r;
       work = child_count < max_children;
     }
     else {  // single light in the scene
-      ChildNode c; c.is_leaf = true; c.power = 1.0f;
+      ChildNode c; c.is_leaf = true; c.power = 1.0f; range_of(c, 0);
       cbi[child_count] = 0; children[child_count++] = c;
     }
     while (work) {
@@ -578,9 +580,9 @@ struct Collapse {
       }
       if (!work) break;
       const TreeNode n = nodes[cbi[selected]];
-      ChildNode l; l.mean = n.left_mean; l.variance = n.left_variance; l.power = n.left_power;
+      ChildNode l; l.mean = n.left_mean; l.variance = n.left_variance; l.power = n.left_power; range_of(l, n.child_ptr);
       cbi[selected] = n.child_ptr; children[selected] = l;
-      ChildNode r; r.mean = n.right_mean; r.variance = n.right_variance; r.power = n.right_power;
+      ChildNode r; r.mean = n.right_mean; r.variance = n.right_variance; r.power = n.right_power; range_of(r, n.child_ptr + 1);
       uint32_t slot = 0;
       for (; slot < max_children; slot++) if (cbi[slot] == kNull) break;
       cbi[slot] = n.child_ptr + 1; children[slot] = r;
@@ -784,10 +786,23 @@ QuantChild quantise_child(const Quantiser& q, const ChildNode& c, float max_powe
 
 }  // namespace
 
+// An instance's transform as the fragments are made with it: the conjugate of the Euler angles' quaternion, the scale, the translation (device_light.c:2020-2040).
+static LumLightTransform light_transform_of(const HostInstance& inst) {
+  float qf[4];
+  euler_to_quaternion(inst.rotation, qf);
+  return LumLightTransform{{-qf[0], -qf[1], -qf[2], qf[3]}, {inst.scale.x, inst.scale.y, inst.scale.z}, {inst.translation.x, inst.translation.y, inst.translation.z}};
+}
+
+void refresh_light_refit_transforms(const HostScene& scene, LightRefitPlan* plan) {
+  for (size_t k = 0; k < plan->transforms.size(); k++)
+    if (plan->transform_instances[k] < scene.instances.size()) plan->transforms[k] = light_transform_of(scene.instances[plan->transform_instances[k]]);
+}
+
 void build_light_tree(const HostScene& scene, LightTreeOutput* out) {
-  out->root.clear(); out->nodes.clear(); out->tri_handles.clear(); out->bvh_tris.clear();
+  out->root.clear(); out->nodes.clear(); out->tri_handles.clear(); out->bvh_tris.clear(); out->plan = LightRefitPlan{};
   // ---- fragments (device_light.c:2020-2113): world-space emissive triangles, grouped per instance by material slot ----
   std::vector<Fragment> frags;
+  std::vector<LumLightFragment> plan_frags;  // by instance and triangle until the tree is built
   std::map<std::pair<uint64_t, uint32_t>, float> intensity_cache;  // (mesh, triangle), texture -> integrated maximum; instances share it
   auto textured_intensity = [&](uint32_t mesh_id, uint32_t tri, uint32_t tex) {
     const auto key = std::make_pair(((uint64_t) mesh_id << 32) | tri, tex);
@@ -801,10 +816,9 @@ void build_light_tree(const HostScene& scene, LightTreeOutput* out) {
     const HostInstance& inst = scene.instances[inst_id];
     if (!inst.active || inst.mesh_id >= scene.meshes.size()) continue;
     const HostMesh& mesh = scene.meshes[inst.mesh_id];
-    float qf[4];
-    euler_to_quaternion(inst.rotation, qf);
-    const float q[4] = {-qf[0], -qf[1], -qf[2], qf[3]};
-    const F3 offset = f3(inst.translation.x, inst.translation.y, inst.translation.z), scale = f3(inst.scale.x, inst.scale.y, inst.scale.z);
+    const LumLightTransform tr = light_transform_of(inst);
+    const float* q = tr.q;
+    const F3 offset = f3(tr.offset[0], tr.offset[1], tr.offset[2]), scale = f3(tr.scale[0], tr.scale[1], tr.scale[2]);
     // material slots in order of first appearance (device_light.c:1648-1672)
     std::vector<uint16_t> slots;
     for (uint32_t t = 0; t < mesh.triangle_count(); t++)
@@ -835,15 +849,23 @@ void build_light_tree(const HostScene& scene, LightTreeOutput* out) {
         f.w0 = rotate_q_w(f3(p[0], p[1], p[2]), q); f.w1 = rotate_q_w(f3(p[3], p[4], p[5]), q); f.w2 = rotate_q_w(f3(p[6], p[7], p[8]), q);
         f.wm = (f.w0 + (f.w1 + f.w2)) * (1.0f / 3.0f);
         f.power = intensity * area * average_intensity;
-        f.instance_id = inst_id; f.tri_id = t;
+        f.instance_id = inst_id; f.tri_id = t; f.plan_id = (uint32_t) plan_frags.size();
         frags.push_back(f);
+        if (out->plan.transform_instances.empty() || out->plan.transform_instances.back() != inst_id) {
+          out->plan.transforms.push_back(tr); out->plan.transform_instances.push_back(inst_id);
+        }
+        plan_frags.push_back(LumLightFragment{inst_id, inst.mesh_id, t, 0u, (uint32_t) out->plan.transforms.size() - 1u, intensity, average_intensity, 0u});
       }
     }
   }
-  if (frags.empty()) return;
+  if (frags.empty()) { out->plan = LightRefitPlan{}; return; }
 
   std::vector<BinaryNode> binary;
   build_binary(frags, binary);
+  // the plan's fragment table in the order build_binary left
+  out->plan.fragments.resize(frags.size());
+  for (size_t i = 0; i < frags.size(); i++) out->plan.fragments[i] = plan_frags[frags[i].plan_id];
+  out->plan.slots.assign(128, LumLightSlot{0u, 0u});
 
   // ---- traversal structure (device_light.c:586-649) ----
   std::vector<TreeNode> tree(binary.size());
@@ -888,6 +910,10 @@ void build_light_tree(const HostScene& scene, LightTreeOutput* out) {
       std::memcpy(s + 32 + 2 * k, &pw, 2);
     }
     for (uint32_t c = 0; c < child_count; c++) if (cbi[c] != kNull) cw.jobs.push_back(cbi[c]);
+    for (uint32_t c = 0; c < child_count; c++) {
+      out->plan.slots[c] = LumLightSlot{children[c].first, children[c].count};
+      out->plan.root_cost += (double) children[c].power * children[c].variance;
+    }
   }
   for (size_t job = 0; job < cw.jobs.size(); job++) {
     ChildNode children[8];
@@ -911,6 +937,7 @@ void build_light_tree(const HostScene& scene, LightTreeOutput* out) {
       n[24 + c] = qc.mx; n[32 + c] = qc.my; n[40 + c] = qc.mz; n[48 + c] = qc.sd; n[56 + c] = (uint8_t) qc.power;
     }
     out->nodes.insert(out->nodes.end(), n, n + 64);
+    for (uint32_t c = 0; c < 8; c++) out->plan.slots.push_back(c < child_count ? LumLightSlot{children[c].first, children[c].count} : LumLightSlot{0u, 0u});
     for (uint32_t c = 0; c < child_count; c++) if (cbi[c] != kNull) cw.jobs.push_back(cbi[c]);
   }
 
@@ -921,6 +948,7 @@ void build_light_tree(const HostScene& scene, LightTreeOutput* out) {
   for (size_t id = 0; id < nl; id++) {
     const Fragment& f = frags[cw.new_fragments[id]];
     out->tri_handles[2 * id] = f.instance_id; out->tri_handles[2 * id + 1] = f.tri_id;
+    out->plan.fragments[cw.new_fragments[id]].light_id = (uint32_t) id;
     float* t = out->bvh_tris.data() + 12 * id;
     t[0] = f.v0.x; t[1] = f.v0.y; t[2] = f.v0.z; t[4] = f.v1.x; t[5] = f.v1.y; t[6] = f.v1.z; t[8] = f.v2.x; t[9] = f.v2.y; t[10] = f.v2.z;
     t[3] = f.w0; t[7] = f.w1; t[11] = f.w2;  // LightTreeBVHTriangle is three Vec128: the lanes no kernel reads (vertex stride 16, optix_bvh.c:382-478) hold what the arithmetic left
@@ -1057,6 +1085,7 @@ std::string update_device_scene(const HostScene& scene, const std::vector<uint32
     LightTreeOutput lt;
     build_light_tree(scene, &lt);
     b.light_tree_root = lt.root; b.light_tree_nodes = lt.nodes; b.light_tri_handles = lt.tri_handles; b.light_bvh_tris = lt.bvh_tris;
+    b.light_refit_plan = std::move(lt.plan);
   }
 
   LumDeviceSceneView& v = b.view;

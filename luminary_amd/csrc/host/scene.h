@@ -71,6 +71,19 @@ void encode_material(const LuminaryMaterial& m, uint16_t out[16]);
 void euler_to_quaternion(const LuminaryVec3& r, float q[4]);
 void encode_transform(const HostInstance& inst, float out[8]);
 
+// What a build of the light tree leaves behind for its refit on the device (lum_core.h LumLightRefitPlan; light_refit.h): the storage behind that struct's pointers.
+struct LightRefitPlan {
+  std::vector<LumLightFragment> fragments;
+  std::vector<LumLightTransform> transforms;
+  std::vector<uint32_t> transform_instances;
+  std::vector<LumLightSlot> slots;
+  double root_cost = 0.0;
+  LumLightRefitPlan view() const {
+    return LumLightRefitPlan{fragments.data(), transforms.data(), transform_instances.data(), slots.data(), (uint32_t) fragments.size(), (uint32_t) transforms.size(),
+                             slots.size() >= 128 ? (uint32_t) ((slots.size() - 128) / 8) : 0u, 0u, root_cost};
+  }
+};
+
 // Device-format scene plus the storage behind its pointers.
 struct DeviceSceneBuffers {
   LumDeviceSceneView view;
@@ -83,6 +96,7 @@ struct DeviceSceneBuffers {
   std::vector<uint8_t> light_tree_root, light_tree_nodes;
   std::vector<uint32_t> light_tri_handles;
   std::vector<float> light_bvh_tris;
+  LightRefitPlan light_refit_plan;         // of the build that made the four light arrays above (not part of the view)
   std::vector<uint32_t> bluenoise;
   std::vector<uint32_t> texture_table, texels;
   std::vector<float> sky_stars;            // 4 floats per star, grid order
@@ -107,10 +121,13 @@ std::string build_device_scene(const HostScene& scene, const std::vector<uint32_
 
 // Light tree build (device_light.c:2236-2265). Exposed for tests.
 struct LightTreeOutput {
+  LightRefitPlan plan;
   std::vector<uint8_t> root, nodes;
   std::vector<uint32_t> tri_handles;  // 2 per light
   std::vector<float> bvh_tris;        // 12 per light
 };
 void build_light_tree(const HostScene& scene, LightTreeOutput* out);
+// The plan's transform table again, from the instances as they now stand (moved instances; the same bits a build would form).
+void refresh_light_refit_transforms(const HostScene& scene, LightRefitPlan* plan);
 
 }  // namespace lum

@@ -131,6 +131,7 @@ void free_scene(LumContext* ctx) {
   ctx->instance_update.reset(); ctx->instance_mesh_ids.clear();
   ctx->resident_refit.drop_layout(); ctx->stale_meshes = 0;
   ctx->mesh_skin.clear(); ctx->mesh_morph.clear(); ctx->d_skin_flags.reset();
+  ctx->light_refit.reset(); ctx->light_bvh = Bvh4{}; ctx->light_refit_needs_rebuild = false;
   ctx->has_scene = false;
 }
 
@@ -892,28 +893,96 @@ static int update_light_bvh(LumContext* ctx, const LumDeviceSceneView* v) {
   if (upload(ctx, ctx->arrays.lights.bvh_tris, tris.data(), tris.size(), &sc.light_tris)) return 1;
   sc.light_num_nodes = (uint32_t) lb.nodes.size();
   ctx->bvh_stats[3] = lb.nodes.size();
+  ctx->light_bvh = std::move(lb);  // what lumc_light_refit_bind makes the refit's topology from
+  return 0;
+}
+
+// The bound light tree from the vertices as they now stand on the device (LUMC_DIRTY_LIGHT_POSITIONS; light_refit.hip): fragments and slot statistics into scratch,
+// then - only once the flag word has come back clean and the cost is within the bound - the statistics' bytes of the root, its float table and the nodes in place,
+// and the light BVH refitted from the lights' world-space triangles into the resident arrays. update_counts_and_tables, which follows, runs k_light_table. A
+// fallback (no binding, a flag, the cost) touches nothing of the lights' part and is reported (lumc_light_refit_needs_rebuild); the view's light arrays are not read.
+static int refit_lights(LumContext* ctx, const LumDeviceSceneView* v) {
+  LightRefit& r = ctx->light_refit;
+  LumLightRefitStats& st = ctx->light_refit_stats;
+  DeviceScene& sc = ctx->scene;
+  SceneArrays::Lights& a = ctx->arrays.lights;
+  st.last_launches = st.last_flags = 0; st.last_bytes_uploaded = st.last_bytes_downloaded = 0;
+  st.seconds = st.seconds_fragments = st.seconds_stats = st.seconds_nodes = st.seconds_light_bvh = st.seconds_table = st.cost_growth = 0.0;
+  auto fall_back = [&]() { st.fallbacks++; ctx->light_refit_needs_rebuild = true; return 0; };
+  if (!r.bound || r.num_fragments != sc.num_lights || !a.tree_root || !a.root_children || !a.bvh_nodes || !a.bvh_tris || a.bvh_tris.count() < r.num_fragments ||
+      a.bvh_nodes.count() != r.bvh.num_nodes || a.tree_nodes.count() != 4 * (size_t) r.num_nodes || a.tree_root.count() != 1 + 3 * (size_t) r.sections ||
+      a.root_children.count() != (size_t) r.sections * 64 + 16 || ctx->mesh_tri_offset.size() != (size_t) v->num_meshes + 1)
+    return fall_back();
+  // the per-part seconds cost a synchronisation each: only on request (LUM_LIGHT_REFIT_TIMING=1; tools/light_refit_bench.py). Otherwise the refit waits once, for the flag word.
+  static const bool timed = [] { const char* e = getenv("LUM_LIGHT_REFIT_TIMING"); return e && atoi(e) != 0; }();
+  const Stopwatch t_all;
+  if (!r.pending.empty()) {
+    HIP_TRY(ctx, hipMemcpy(r.transforms.get(), r.pending.data(), sizeof(LumLightTransform) * r.pending.size(), hipMemcpyHostToDevice));
+    st.last_bytes_uploaded = sizeof(LumLightTransform) * r.pending.size();
+    r.pending.clear();
+  }
+  const size_t corners = ctx->arrays.mesh.vertices.count();
+  if (corners > 0xFFFFFFFFull) return fall_back();
+  HIP_TRY(ctx, light_refit_fragments(r, ctx->arrays.mesh.vertices.get(), ctx->arrays.mesh.tri_offset.get(), v->num_meshes, (uint32_t) corners));
+  if (timed) { HIP_TRY(ctx, hipDeviceSynchronize()); st.seconds_fragments = t_all.seconds(); }
+  const Stopwatch t_stats;
+  HIP_TRY(ctx, light_refit_stats(r));
+  st.last_launches = 2;
+  uint32_t flags = 0;
+  float result[2 * kLightRootSlots];
+  HIP_TRY(ctx, hipMemcpy(&flags, r.flags.get(), sizeof(flags), hipMemcpyDeviceToHost));  // (waits for the launches)
+  HIP_TRY(ctx, hipMemcpy(result, r.result.get(), sizeof(result), hipMemcpyDeviceToHost));
+  st.last_bytes_downloaded = sizeof(flags) + sizeof(result);
+  if (timed) st.seconds_stats = t_stats.seconds();
+  st.last_flags = flags;
+  if (flags & kLightRefitFlagBadPlan) { ctx->error = "lumc_scene_update: an index of the light refit plan beyond the scene reached a kernel"; return 1; }
+  double cost = 0.0;
+  for (uint32_t c = 0; c < 8 * r.sections; c++) cost += (double) result[2 * c] * (double) result[2 * c + 1];
+  st.cost_growth = r.root_cost > 0.0 ? cost / r.root_cost : 0.0;
+  if (flags || (ctx->light_refit_max_cost_growth > 0.0f && st.cost_growth > (double) ctx->light_refit_max_cost_growth)) { st.seconds = t_all.seconds(); return fall_back(); }
+  const Stopwatch t_nodes;
+  HIP_TRY(ctx, light_refit_nodes(r, (uint8_t*) a.tree_root.get(), a.root_children.get(), (uint8_t*) a.tree_nodes.get()));
+  st.last_launches++;
+  if (timed) { HIP_TRY(ctx, hipDeviceSynchronize()); st.seconds_nodes = t_nodes.seconds(); }
+  const Stopwatch t_bvh;
+  Aabb root_box;
+  HIP_TRY(ctx, refit_run(r.bvh, r.tris.get(), a.bvh_tris.get(), nullptr, a.bvh_nodes.get(), &root_box));
+  st.last_launches += 1 + (uint32_t) r.bvh.level_first.size() - 1;
+  st.last_bytes_downloaded += sizeof(Aabb);
+  if (timed) st.seconds_light_bvh = t_bvh.seconds();
+  st.seconds = t_all.seconds();
+  st.refits++;
+  ctx->lights_refitted = true;
+  ctx->light_refit_needs_rebuild = false;
   return 0;
 }
 
 // The counts, then what two kernels derive from the arrays above: k_tri_opacity (needs the materials and blas_tris), k_light_table (needs the counts).
 // triangles_rewritten: a moved-vertices update built a mesh again, its traversal triangles are new.
-static int update_counts_and_tables(LumContext* ctx, const LumDeviceSceneView* v, const UpdatePlan& plan, bool triangles_rewritten) {
+// keep_light_count: the caller said LUMC_DIRTY_LIGHT_POSITIONS without new lights - the view's light arrays and their count are not read, the device's stay.
+static int update_counts_and_tables(LumContext* ctx, const LumDeviceSceneView* v, const UpdatePlan& plan, bool triangles_rewritten, bool keep_light_count) {
   DeviceScene& sc = ctx->scene;
   const uint32_t total_tris = total_triangles(v);
   const bool dirty_lights = plan.lights;
+  const bool lights_refitted = ctx->lights_refitted;
+  ctx->lights_refitted = false;
   ctx->bvh_stats[1] = total_tris;
-  sc.num_meshes = v->num_meshes; sc.num_instances = v->num_instances; sc.num_materials = v->num_materials; sc.num_lights = v->num_lights;  // (num_textures: update_textures)
+  sc.num_meshes = v->num_meshes; sc.num_instances = v->num_instances; sc.num_materials = v->num_materials;  // (num_textures: update_textures)
+  if (!keep_light_count) sc.num_lights = v->num_lights;
   if (total_tris && plan.tri_opacity(triangles_rewritten)) {  // the triangles' material words: texture id, or whether they stop a visibility ray on their own
     hipLaunchKernelGGL(k_tri_opacity, dim3((total_tris + kBlock - 1) / kBlock), dim3(kBlock), 0, 0, sc, ctx->arrays.mesh.blas_tris.get(), total_tris);
     HIP_TRY(ctx, hipGetLastError());
   }
-  if ((dirty_lights || (plan.light_table_inputs() && sc.light_tri_table)) && sc.light_tree_root && sc.num_lights) {  // the emissive triangles in world space with what their material says, one record per light (load_tri_light_table)
+  const bool lights_left_alone = keep_light_count && !lights_refitted;  // a refit that fell back: the table stays with the tree it belongs to until the caller's rebuild
+  if (!lights_left_alone && (dirty_lights || ((plan.light_table_inputs() || lights_refitted) && sc.light_tri_table)) && sc.light_tree_root && sc.num_lights) {  // the emissive triangles in world space with what their material says, one record per light (load_tri_light_table)
     DeviceBuffer<float4>& table = ctx->arrays.lights.tri_table;  // a material edit alone refills the table in place (same lights)
+    const Stopwatch t_table;
     if (dirty_lights) HIP_TRY(ctx, table.resize(4 * (size_t) sc.num_lights));
     hipLaunchKernelGGL(k_light_table, dim3((sc.num_lights + kBlock - 1) / kBlock), dim3(kBlock), 0, 0, sc, table.get());
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipDeviceSynchronize());
     sc.light_tri_table = table.get();
+    if (lights_refitted) { ctx->light_refit_stats.last_launches++; ctx->light_refit_stats.seconds_table = t_table.seconds(); ctx->light_refit_stats.seconds += t_table.seconds(); }
   }
   return 0;
 }
@@ -1140,11 +1209,13 @@ static int scene_update(LumContext* ctx, const LumDeviceSceneView* v, unsigned d
   bool pose_pending = false;
   for (const auto& kv : ctx->mesh_skin) pose_pending = pose_pending || !kv.second.pending.empty();
   for (const auto& kv : ctx->mesh_morph) pose_pending = pose_pending || !kv.second.pending.empty();  // pending weights are a pending pose
-  UpdatePlan plan = plan_update(dirty, ctx->refit_in_place != 0, ctx->refit_mode, ctx->instance_update_mode, pose_pending);
+  UpdatePlan plan = plan_update(dirty, ctx->refit_in_place != 0, ctx->refit_mode, ctx->instance_update_mode, pose_pending, ctx->light_refit.bound);
   if (plan.moved_by_host) reset_update(ctx->instance_stats);
   auto host_path_since = [&](const Stopwatch& t) { if (plan.moved_by_host) ctx->instance_stats.seconds += t.seconds(); };
   auto lights_since = [&](const Stopwatch& t) { if (plan.time_lights) ctx->refit_stats.seconds_lights += t.seconds(); };
   ctx->has_scene = false;
+  ctx->lights_refitted = false;
+  if (plan.lights || plan.meshes) { ctx->light_refit.reset(); ctx->light_refit_needs_rebuild = false; }  // new lights: the plan's topology is not theirs, the caller binds again
   if (plan.meshes) { ctx->arrays.mesh = {}; ctx->mesh_skin.clear(); ctx->mesh_morph.clear(); }  // the traversal triangles too; new meshes: the bindings go, the caller binds again
   if (plan.meshes && update_mesh_arrays(ctx, v)) return 1;
   bool triangles_rewritten = false;
@@ -1193,7 +1264,9 @@ static int scene_update(LumContext* ctx, const LumDeviceSceneView* v, unsigned d
   if (plan.positions) ctx->refit_stats.seconds_assemble = t_assemble.seconds();
   t_lights = Stopwatch{};
   if (plan.lights && update_light_bvh(ctx, v)) return 1;
-  if (update_counts_and_tables(ctx, v, plan, triangles_rewritten)) return 1;
+  if (plan.light_positions && refit_lights(ctx, v)) return 1;
+  if ((dirty & LUMC_DIRTY_LIGHT_POSITIONS) && !plan.lights && !plan.meshes && !ctx->light_refit.bound) { ctx->light_refit_stats.fallbacks++; ctx->light_refit_needs_rebuild = true; }  // no binding: reported, nothing touched
+  if (update_counts_and_tables(ctx, v, plan, triangles_rewritten, (dirty & LUMC_DIRTY_LIGHT_POSITIONS) && !plan.lights && !plan.meshes)) return 1;
   lights_since(t_lights);
   if (plan.constants && update_constants(ctx, v, plan)) return 1;
   if (update_bridge_table(ctx, v)) return 1;
@@ -1216,7 +1289,7 @@ int lumc_scene_update(LumContext* ctx, const LumDeviceSceneView* v, unsigned int
   if (!ctx->has_scene || (dirty & LUMC_DIRTY_ALL) == LUMC_DIRTY_ALL) return lumc_scene_upload(ctx, v);
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   HIP_TRY(ctx, hipDeviceSynchronize());  // nothing renders from the arrays that are about to be freed
-  if (scene_update(ctx, v, dirty & (LUMC_DIRTY_ALL | LUMC_DIRTY_MESH_POSITIONS | LUMC_DIRTY_INSTANCE_TRANSFORMS | LUMC_DIRTY_MESH_SKIN))) { free_scene(ctx); return 1; }  // a failed partial update leaves no half-updated scene behind
+  if (scene_update(ctx, v, dirty & (LUMC_DIRTY_ALL | LUMC_DIRTY_MESH_POSITIONS | LUMC_DIRTY_INSTANCE_TRANSFORMS | LUMC_DIRTY_MESH_SKIN | LUMC_DIRTY_LIGHT_POSITIONS))) { free_scene(ctx); return 1; }  // a failed partial update leaves no half-updated scene behind
   return 0;
 }
 
@@ -1354,6 +1427,99 @@ int lumc_mesh_vertices_probe(LumContext* ctx, uint32_t mesh, void* out) {
   const uint32_t t0 = ctx->mesh_tri_offset[mesh], nt = ctx->mesh_tri_offset[mesh + 1] - t0;
   if (3 * ((size_t) t0 + nt) > ctx->arrays.mesh.vertices.count()) { ctx->error = "lumc_mesh_vertices_probe: the mesh lies outside the vertex array"; return 1; }
   if (nt) HIP_TRY(ctx, hipMemcpy(out, ctx->arrays.mesh.vertices.get() + 3 * (size_t) t0, sizeof(float4) * 3 * (size_t) nt, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int lumc_set_light_refit(LumContext* ctx, float max_cost_growth) {
+  if (!ctx) return 1;
+  if (!(max_cost_growth >= 0.0f) || !std::isfinite(max_cost_growth)) { ctx->error = "lumc_set_light_refit: max_cost_growth >= 0"; return 1; }
+  ctx->light_refit_max_cost_growth = max_cost_growth;
+  return 0;
+}
+
+int lumc_light_refit_bind(LumContext* ctx, const LumLightRefitPlan* plan) {
+  if (!ctx || !plan) return 1;
+  ctx->light_refit.reset();
+  const DeviceScene& sc = ctx->scene;
+  if (!ctx->has_scene) { ctx->error = "lumc_light_refit_bind: the context has no scene"; return 1; }
+  if (plan->num_fragments != sc.num_lights) { ctx->error = "lumc_light_refit_bind: the plan's fragments are not the lights of the scene on the device"; return 1; }
+  if (plan->num_fragments < 2) return 0;  // no light: nothing to refit; one light: its tree is constant and not refitted - a move takes the rebuild (no binding)
+  const uint32_t n = plan->num_fragments;
+  const size_t num_slots = kLightRootSlots + (size_t) kLightNodeSlots * plan->num_nodes;
+  const SceneArrays::Lights& a = ctx->arrays.lights;
+  if (!plan->fragments || !plan->transforms || !plan->slots || plan->num_transforms == 0 || !a.tree_root || a.tree_nodes.count() != 4 * (size_t) plan->num_nodes ||
+      ctx->light_bvh.nodes.empty() || ctx->light_bvh.prims.size() != n || ctx->mesh_tri_offset.empty()) {
+    ctx->error = "lumc_light_refit_bind: the plan does not belong to the light tree on the device (bind right after the LUMC_DIRTY_LIGHTS update that uploaded it)";
+    return 1;
+  }
+  const uint32_t num_meshes = (uint32_t) ctx->mesh_tri_offset.size() - 1;
+  std::vector<bool> seen(n, false);
+  for (uint32_t i = 0; i < n; i++) {
+    const LumLightFragment& f = plan->fragments[i];
+    if (f.mesh >= num_meshes || f.triangle >= ctx->mesh_tri_offset[f.mesh + 1] - ctx->mesh_tri_offset[f.mesh] || f.transform >= plan->num_transforms || f.light_id >= n ||
+        seen[f.light_id] || f.instance >= sc.num_instances) {
+      ctx->error = "lumc_light_refit_bind: fragment " + std::to_string(i) + " names a mesh, triangle, instance, transform or light id the scene on the device does not have";
+      return 1;
+    }
+    seen[f.light_id] = true;
+  }
+  for (size_t s = 0; s < num_slots; s++)
+    if (plan->slots[s].first > n || plan->slots[s].count > n - plan->slots[s].first) { ctx->error = "lumc_light_refit_bind: a slot's range lies outside the fragments"; return 1; }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  uint8_t header[16];
+  HIP_TRY(ctx, hipMemcpy(header, a.tree_root.get(), sizeof(header), hipMemcpyDeviceToHost));
+  const uint32_t sections = header[10];
+  if (sections == 0 || sections > kLightRootSlots / 8 || a.tree_root.count() != 1 + 3 * (size_t) sections) { ctx->error = "lumc_light_refit_bind: the root on the device has no sections"; return 1; }
+  for (uint32_t c = 8 * sections; c < kLightRootSlots; c++)
+    if (plan->slots[c].count) { ctx->error = "lumc_light_refit_bind: the plan has more root children than the root on the device"; return 1; }
+  LightRefit& r = ctx->light_refit;
+  hipError_t e = light_refit_upload(r, *plan, sections);
+  if (e == hipSuccess) e = refit_plan_create(r.bvh, ctx->light_bvh, n);
+  if (e != hipSuccess) { r.reset(); ctx->error = std::string("lumc_light_refit_bind: ") + hipGetErrorString(e); return 1; }
+  r.bound = true;
+  return 0;
+}
+
+int lumc_light_refit_transforms(LumContext* ctx, const LumLightTransform* transforms, uint32_t num_transforms) {
+  if (!ctx || !transforms) return 1;
+  LightRefit& r = ctx->light_refit;
+  if (!r.bound) return 0;  // (the update that follows reports that the lights need a rebuild)
+  if (num_transforms != r.num_transforms) { ctx->error = "lumc_light_refit_transforms: another number of transforms than the bound plan's"; return 1; }
+  for (uint32_t i = 0; i < num_transforms; i++) {
+    const LumLightTransform& t = transforms[i];
+    bool finite = true;
+    for (float x : t.q) finite = finite && std::isfinite(x);
+    for (float x : t.scale) finite = finite && std::isfinite(x);
+    for (float x : t.offset) finite = finite && std::isfinite(x);
+    if (!finite) { ctx->error = "lumc_light_refit_transforms: a value that is not finite"; return 1; }
+  }
+  r.pending.assign(transforms, transforms + num_transforms);
+  return 0;
+}
+
+int lumc_light_refit_needs_rebuild(const LumContext* ctx) { return ctx && ctx->light_refit_needs_rebuild ? 1 : 0; }
+
+int lumc_light_refit_stats(const LumContext* ctx, LumLightRefitStats* out) {
+  if (!ctx || !out) return 1;
+  *out = ctx->light_refit_stats;
+  return 0;
+}
+
+int lumc_light_arrays_probe(LumContext* ctx, uint64_t sizes[6], void* root, void* root_children, void* nodes, void* table, void* bvh_nodes, void* bvh_tris) {
+  if (!ctx || !sizes) return 1;
+  if (!ctx->has_scene) { ctx->error = "lumc_light_arrays_probe: the context has no scene"; return 1; }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipDeviceSynchronize());
+  const SceneArrays::Lights& a = ctx->arrays.lights;
+  sizes[0] = a.tree_root.count() * sizeof(uint4); sizes[1] = a.root_children.count(); sizes[2] = a.tree_nodes.count() * sizeof(uint4); sizes[3] = a.tri_table.count();
+  sizes[4] = a.bvh_nodes.count(); sizes[5] = a.bvh_tris.count();
+  auto down = [&](void* out, const void* src, size_t bytes) { return (out && bytes) ? hipMemcpy(out, src, bytes, hipMemcpyDeviceToHost) : hipSuccess; };
+  HIP_TRY(ctx, down(root, a.tree_root.get(), sizes[0]));
+  HIP_TRY(ctx, down(root_children, a.root_children.get(), sizes[1] * sizeof(float)));
+  HIP_TRY(ctx, down(nodes, a.tree_nodes.get(), sizes[2]));
+  HIP_TRY(ctx, down(table, a.tri_table.get(), sizes[3] * sizeof(float4)));
+  HIP_TRY(ctx, down(bvh_nodes, a.bvh_nodes.get(), sizes[4] * sizeof(Bvh4Node)));
+  HIP_TRY(ctx, down(bvh_tris, a.bvh_tris.get(), sizes[5] * sizeof(BvhTri)));
   return 0;
 }
 

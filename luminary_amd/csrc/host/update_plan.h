@@ -17,6 +17,7 @@ struct UpdatePlan {
   bool moved_by_host = false;         // moved instances under lumc_set_instance_update(1): the host's path, timed into the instance stats
   bool materials = false, lights = false, textures = false, constants = false, particles = false;
   bool full_upload = false;           // every part of LUMC_DIRTY_ALL: the BSDF tables are taken from the caller or generated again
+  bool light_positions = false;       // the bound light tree is refitted on the device from the final vertices (never with `lights`)
   bool time_lights = false;           // the lights' share of a moved-vertices update is timed (LumMeshRefitStats::seconds_lights)
 
   // update_counts_and_tables' two conditions: the triangles' material words are derived again; the light table is (always with new lights, else only if there is one)
@@ -29,8 +30,9 @@ struct UpdatePlan {
   void take_copies_path() { in_place = false; transforms_on_device = false; instances = true; }
 };
 
-// pose_pending: a bound mesh holds a pose that no update has applied yet (LUMC_DIRTY_MESH_SKIN moves something).
-inline UpdatePlan plan_update(unsigned dirty, bool refit_in_place, uint32_t refit_mode, uint32_t instance_update_mode, bool pose_pending) {
+// pose_pending: a bound mesh holds a pose that no update has applied yet (LUMC_DIRTY_MESH_SKIN moves something). light_refit_bound: the context holds a light
+// refit plan (lumc_light_refit_bind); without one LUMC_DIRTY_LIGHT_POSITIONS plans nothing (scene_update reports that the lights need a rebuild).
+inline UpdatePlan plan_update(unsigned dirty, bool refit_in_place, uint32_t refit_mode, uint32_t instance_update_mode, bool pose_pending, bool light_refit_bound = false) {
   auto has = [dirty](unsigned bits) { return (dirty & bits) != 0; };
   UpdatePlan p;
   p.meshes = has(LUMC_DIRTY_MESHES);  // a full rebuild of the meshes covers moved vertices and poses
@@ -47,6 +49,7 @@ inline UpdatePlan plan_update(unsigned dirty, bool refit_in_place, uint32_t refi
   p.particles = has(LUMC_DIRTY_PARTICLES);
   p.constants = has(LUMC_DIRTY_CONSTANTS) || p.particles;
   p.full_upload = p.constants && p.materials && p.instances && p.lights && p.meshes && p.textures && p.particles;
+  p.light_positions = !p.lights && !p.meshes && light_refit_bound && has(LUMC_DIRTY_LIGHT_POSITIONS);
   p.time_lights = p.positions;
   return p;
 }

@@ -28,10 +28,9 @@
 #include "bvh_build.h"  // host_parallel_for
 #include "loaders.h"
 #include "scene.h"
-#define LUM_SKIN_HOST_ONLY 1  // the host twin's declaration only: this unit touches no device
+#define LUM_DEFORM_HOST_ONLY 1  // the host twin's declaration only: this unit touches no device
 #include "light_refit.h"
-#include "mesh_morph.h"
-#include "mesh_skin.h"
+#include "mesh_deform.h"
 
 extern "C" const unsigned char lum_embedded_bluenoise_2d[];
 extern "C" const unsigned char lum_embedded_bluenoise_2d_end[];
@@ -210,22 +209,17 @@ inline bool change_restarts(const LuminaryRendererSettings& in, const LuminaryRe
 
 // ---- skinned and morphed meshes: the lazy host mesh ----
 // HostMesh::positions / normals of a posed or morphed mesh from the host twin of the devices' kernel (in place: the pointers luminary_ext_get_mesh handed out
-// stay valid): skin_host for a mesh that is only skinned, the morph's twin - with the skin once that has a pose - for a morphed one.
+// stay valid): the morph once one is bound, the skin once it has a pose.
 void materialise(LuminaryHost* h, uint32_t mesh) {
   const auto it = h->skins.find(mesh);
   if (it == h->skins.end() || it->second.host_current || mesh >= h->scene.meshes.size()) return;
   HostSkin& k = it->second;
   lum::HostMesh& m = h->scene.meshes[mesh];
   lum::host_parallel_for(m.triangle_count(), [&](size_t b, size_t e) {  // (a corner's bytes do not depend on the chunks)
-    if (k.has_morph()) {
-      const bool posed = k.posed();
-      lum::morph_host_csr(k.rest_positions.data() + 9 * b, k.rest_normals.data() + 9 * b, k.morph_csr, 3 * b, 3 * (e - b), k.morph_weights.data(),
-                          posed ? k.bone_ids.data() + 12 * b : nullptr, posed ? k.weights.data() + 12 * b : nullptr, posed ? k.palette.data() : nullptr,
-                          m.positions.data() + 9 * b, m.normals.data() + 9 * b, nullptr, nullptr);
-    }
-    else
-      lum::skin_host(k.rest_positions.data() + 9 * b, k.rest_normals.data() + 9 * b, k.bone_ids.data() + 12 * b, k.weights.data() + 12 * b, (uint32_t) (e - b), k.palette.data(),
-                     k.bone_count, m.positions.data() + 9 * b, m.normals.data() + 9 * b, nullptr, nullptr);
+    const bool posed = k.posed();
+    lum::deform_host(k.rest_positions.data() + 9 * b, k.rest_normals.data() + 9 * b, k.has_morph() ? &k.morph_csr : nullptr, 3 * b, 3 * (e - b), k.morph_weights.data(),
+                     posed ? k.bone_ids.data() + 12 * b : nullptr, posed ? k.weights.data() + 12 * b : nullptr, posed ? k.palette.data() : nullptr,
+                     m.positions.data() + 9 * b, m.normals.data() + 9 * b, nullptr, nullptr);
   });
   k.host_current = true;
   h->host_materialisations++;
@@ -963,6 +957,9 @@ static void face_normals(const float* positions, uint32_t triangle_count, float*
     for (int k = 0; k < 3; k++) std::memcpy(normals + 9 * (size_t) t + 3 * k, n, sizeof(n));
   }
 }
+static void mark_moved(LuminaryHost* host, uint32_t mesh_id) {
+  if (std::find(host->moved_meshes.begin(), host->moved_meshes.end(), mesh_id) == host->moved_meshes.end()) host->moved_meshes.push_back(mesh_id);
+}
 LuminaryResult luminary_ext_set_mesh_positions(LuminaryHost* host, uint32_t mesh_id, const float* positions, const float* normals, uint32_t triangle_count) {
   CHECK_NULL(host);
   ApiLock lock(host);
@@ -974,12 +971,9 @@ LuminaryResult luminary_ext_set_mesh_positions(LuminaryHost* host, uint32_t mesh
   if (normals) std::memmove(m.normals.data(), normals, sizeof(float) * 9 * (size_t) triangle_count);
   std::memmove(m.positions.data(), positions, sizeof(float) * 9 * (size_t) triangle_count);
   if (!normals) face_normals(m.positions.data(), triangle_count, m.normals.data());
-  if (std::find(host->moved_meshes.begin(), host->moved_meshes.end(), mesh_id) == host->moved_meshes.end()) host->moved_meshes.push_back(mesh_id);
+  mark_moved(host, mesh_id);
   invalidate(host, LUMC_DIRTY_MESH_POSITIONS | moved_emitter_bit(host));  // the vertices and the mesh's tree; the light tree follows moved emitters
   return LUMINARY_SUCCESS;
-}
-static void mark_moved(LuminaryHost* host, uint32_t mesh_id) {
-  if (std::find(host->moved_meshes.begin(), host->moved_meshes.end(), mesh_id) == host->moved_meshes.end()) host->moved_meshes.push_back(mesh_id);
 }
 // A bound mesh got a new pose or new weights: the devices write its vertices, the host mesh follows when something reads it.
 static void deformed(LuminaryHost* host, uint32_t mesh_id, HostSkin& k) {

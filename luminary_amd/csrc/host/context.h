@@ -21,8 +21,7 @@
 #include "device_buffer.h"
 #include "instance_update.h"
 #include "light_refit.h"
-#include "mesh_morph.h"
-#include "mesh_skin.h"
+#include "mesh_deform.h"
 #include "scene_arrays.h"
 #include "work_layout.h"
 
@@ -42,7 +41,7 @@ struct MeshRefit {
   uint64_t fit_hash[2] = {0, 0};   // of the vertices the held tree was built from or last fitted to (mesh_tree_key)
   double built_cost = 0.0;         // bvh4_cost of the tree as last built (0: not computed yet)
   bool stale = false;              // the mesh was refitted in the resident node array since: the host's nodes hold the boxes of earlier vertices (restore_stale_meshes)
-  bool fit_to_pose = false;        // the held tree was last fitted to vertices k_skin_mesh wrote: no host vertices hash to that, fit_hash is not compared
+  bool fit_to_pose = false;        // the held tree was last fitted to vertices k_deform_mesh wrote: no host vertices hash to that, fit_hash is not compared
 };
 
 struct LumContext {
@@ -70,12 +69,10 @@ struct LumContext {
   ResidentRefit resident_refit;              // the layout's slot maps, the per-mesh slot lists and the scratch; dropped with the layout
   uint32_t stale_meshes = 0;                 // meshes of mesh_refit marked stale
   LumResidentRefitStats resident_stats{};
-  // skinned meshes (lumc_mesh_skin_*; mesh_skin.hip, scene_device.hip skin_meshes)
-  std::map<uint32_t, MeshSkin> mesh_skin;    // by mesh; dropped with the meshes
-  DeviceBuffer<uint32_t> d_skin_flags;       // one word of kSkinFlag* bits per launch of an update
+  // skinned and morphed meshes (lumc_mesh_skin_*, lumc_mesh_morph_*; mesh_deform.hip, scene_device.hip skin_meshes): a mesh may hold both, then one launch blends and poses it
+  std::map<uint32_t, MeshDeform> mesh_deform;  // by mesh, a record while it holds a part; dropped with the meshes
+  DeviceBuffer<uint32_t> d_skin_flags;       // one word of kSkinFlag* / kMorphFlag* bits per launch of an update
   LumMeshSkinStats skin_stats{};
-  // morphed meshes (lumc_mesh_morph_*; mesh_morph.hip, scene_device.hip skin_meshes): a mesh may hold both, then one kernel blends and poses it
-  std::map<uint32_t, MeshMorph> mesh_morph;  // by mesh; dropped with the meshes
   LumMeshMorphStats morph_stats{};
   // the light tree's refit (lumc_light_refit_*; light_refit.hip, scene_device.hip refit_lights)
   LightRefit light_refit;                    // the bound plan; dropped by every update that takes new lights or new meshes

@@ -130,7 +130,7 @@ void free_scene(LumContext* ctx) {
   ctx->mesh_bvh.clear(); ctx->mesh_box.clear(); ctx->mesh_refit.clear(); ctx->mesh_tri_offset.clear();
   ctx->instance_update.reset(); ctx->instance_mesh_ids.clear();
   ctx->resident_refit.drop_layout(); ctx->stale_meshes = 0;
-  ctx->mesh_skin.clear(); ctx->mesh_morph.clear(); ctx->d_skin_flags.reset();
+  ctx->mesh_deform.clear(); ctx->d_skin_flags.reset();
   ctx->light_refit.reset(); ctx->light_bvh = Bvh4{}; ctx->light_refit_needs_rebuild = false;
   ctx->has_scene = false;
 }
@@ -406,41 +406,27 @@ static int build_mesh_trees(LumContext* ctx, const LumDeviceSceneView* v, std::v
   return 0;
 }
 
-// ---- skinned and morphed meshes (lum_core.h lumc_mesh_skin_bind, lumc_mesh_morph_bind; mesh_skin.hip, mesh_morph.hip; DESIGN.md sections 11 and 12) ----
+// ---- skinned and morphed meshes (lum_core.h lumc_mesh_skin_bind, lumc_mesh_morph_bind; mesh_deform.hip; DESIGN.md sections 11 and 12) ----
 // A kernel wrote the scene's vertices of mesh m: the view's vertices of it are never trusted.
 static bool written_on_device(const LumContext* ctx, uint32_t m) {
-  const auto it = ctx->mesh_skin.find(m);
-  if (it != ctx->mesh_skin.end() && it->second.posed) return true;
-  const auto im = ctx->mesh_morph.find(m);
-  return im != ctx->mesh_morph.end() && im->second.applied;
+  const auto it = ctx->mesh_deform.find(m);
+  return it != ctx->mesh_deform.end() && it->second.written_on_device();
 }
 
 // The skinning step of an update that touches vertices (find_moved_meshes runs it, once), after the vertex arrays are in place and before anything reads them: every
-// pending palette and every pending weight set goes up and a kernel writes its mesh's range of the scene's vertices (those meshes are moved: *posed, ascending) -
-// k_skin_mesh for a mesh that is only skinned, k_morph_mesh for a morphed one, with the mesh's skin once that has a palette; after an upload of the vertex arrays
+// pending palette and every pending weight set goes up and k_deform_mesh writes its mesh's range of the scene's vertices (those meshes are moved: *posed,
+// ascending) - with the mesh's morph if it has one, and with its skin once that has a palette; after an upload of the vertex arrays
 // from the view (view_uploaded) every other bound mesh a kernel has written is written again from the palette and the weights it holds - the same bits as before
 // the upload, so its tree still fits. One launch per mesh. Then the launches' flag words come back: a position that is not finite fails the update.
 static int skin_meshes(LumContext* ctx, bool view_uploaded, std::vector<uint32_t>* posed) {
-  struct Job { uint32_t mesh; MeshSkin* skin; MeshMorph* morph; bool new_pose, new_weights; };
-  std::vector<uint32_t> bound;
-  for (const auto& kv : ctx->mesh_skin) bound.push_back(kv.first);
-  for (const auto& kv : ctx->mesh_morph) bound.push_back(kv.first);
-  std::sort(bound.begin(), bound.end());
-  bound.erase(std::unique(bound.begin(), bound.end()), bound.end());
-  std::vector<Job> jobs;
+  std::vector<std::pair<uint32_t, MeshDeform*>> jobs;  // ascending
   bool any_skin = false, any_morph = false;
-  for (uint32_t m : bound) {
-    const auto is = ctx->mesh_skin.find(m);
-    const auto im = ctx->mesh_morph.find(m);
-    Job job{m, is != ctx->mesh_skin.end() ? &is->second : nullptr, im != ctx->mesh_morph.end() ? &im->second : nullptr, false, false};
-    job.new_pose = job.skin && !job.skin->pending.empty();
-    job.new_weights = job.morph && !job.morph->pending.empty();
-    if (!job.new_pose && !job.new_weights && !(view_uploaded && written_on_device(ctx, m))) continue;
-    if (job.skin && !job.skin->posed && !job.new_pose) job.skin = nullptr;  // (no palette yet: the morph alone writes the mesh)
-    if (!job.skin && !job.morph) continue;
-    any_skin = any_skin || !job.morph || job.new_pose;
-    any_morph = any_morph || job.morph;
-    jobs.push_back(job);
+  for (auto& kv : ctx->mesh_deform) {
+    MeshDeform& d = kv.second;
+    if (!d.pending() && !(view_uploaded && d.written_on_device())) continue;
+    any_skin = any_skin || !d.morph || d.new_pose();
+    any_morph = any_morph || d.morph;
+    jobs.emplace_back(kv.first, &d);
   }
   if (jobs.empty()) return 0;
   LumMeshSkinStats& st = ctx->skin_stats;
@@ -448,59 +434,51 @@ static int skin_meshes(LumContext* ctx, bool view_uploaded, std::vector<uint32_t
   if (any_skin) { st.last_meshes = st.last_launches = 0; st.last_bytes_uploaded = 0; st.seconds = st.seconds_upload = st.seconds_skin = 0.0; }
   if (any_morph) { mst.last_meshes = mst.last_launches = 0; mst.last_bytes_uploaded = 0; mst.seconds = mst.seconds_upload = mst.seconds_morph = 0.0; }
   DeviceBuffer<float4>& vertices = ctx->arrays.mesh.vertices;
-  for (const Job& job : jobs) {  // every range a kernel will write, against the array that is there
-    const uint32_t m = job.mesh;
+  for (const auto& [m, d] : jobs) {  // every range a kernel will write, against the array that is there
     if ((size_t) m + 1 >= ctx->mesh_tri_offset.size() || 3 * (size_t) ctx->mesh_tri_offset[m + 1] > vertices.count() ||
-        (job.skin && ctx->mesh_tri_offset[m + 1] - ctx->mesh_tri_offset[m] != job.skin->triangles) ||
-        (job.morph && ctx->mesh_tri_offset[m + 1] - ctx->mesh_tri_offset[m] != job.morph->triangles)) {
-      ctx->error = "lumc_scene_update: mesh " + std::to_string(m) + " is bound to a " + (job.morph ? "morph" : "skin") + " of another triangle count than the scene on the device";
+        (d->skin_writes() && ctx->mesh_tri_offset[m + 1] - ctx->mesh_tri_offset[m] != d->skin->triangles) ||
+        (d->morph && ctx->mesh_tri_offset[m + 1] - ctx->mesh_tri_offset[m] != d->morph->triangles)) {
+      ctx->error = "lumc_scene_update: mesh " + std::to_string(m) + " is bound to a " + (d->morph ? "morph" : "skin") + " of another triangle count than the scene on the device";
       return 1;
     }
   }
   const Stopwatch t_all;
   if (ctx->d_skin_flags.count() < jobs.size()) HIP_TRY(ctx, ctx->d_skin_flags.resize(jobs.size()));
   HIP_TRY(ctx, hipMemset(ctx->d_skin_flags.get(), 0, sizeof(uint32_t) * jobs.size()));
-  for (const Job& job : jobs) {
-    if (job.new_pose) {
-      HIP_TRY(ctx, hipMemcpy(job.skin->palette.get(), job.skin->pending.data(), sizeof(float) * job.skin->pending.size(), hipMemcpyHostToDevice));
-      st.last_bytes_uploaded += sizeof(float) * job.skin->pending.size();
+  for (const auto& [m, d] : jobs) {
+    if (d->new_pose()) {
+      HIP_TRY(ctx, hipMemcpy(d->skin->palette.get(), d->skin->pending.data(), sizeof(float) * d->skin->pending.size(), hipMemcpyHostToDevice));
+      st.last_bytes_uploaded += sizeof(float) * d->skin->pending.size();
     }
-    if (job.new_weights) {
-      if (job.morph->pending.size() != job.morph->weights.count()) { ctx->error = "lumc_scene_update: mesh " + std::to_string(job.mesh) + " holds weights of another target count"; return 1; }
-      HIP_TRY(ctx, hipMemcpy(job.morph->weights.get(), job.morph->pending.data(), sizeof(float) * job.morph->pending.size(), hipMemcpyHostToDevice));
-      mst.last_bytes_uploaded += sizeof(float) * job.morph->pending.size();
+    if (d->new_weights()) {
+      if (d->morph->pending.size() != d->morph->weights.count()) { ctx->error = "lumc_scene_update: mesh " + std::to_string(m) + " holds weights of another target count"; return 1; }
+      HIP_TRY(ctx, hipMemcpy(d->morph->weights.get(), d->morph->pending.data(), sizeof(float) * d->morph->pending.size(), hipMemcpyHostToDevice));
+      mst.last_bytes_uploaded += sizeof(float) * d->morph->pending.size();
     }
   }
   HIP_TRY(ctx, hipDeviceSynchronize());
   const double seconds_upload = t_all.seconds();
   const Stopwatch t_skin;
   for (size_t j = 0; j < jobs.size(); j++) {
-    const Job& job = jobs[j];
-    float4* first = vertices.get() + 3 * (size_t) ctx->mesh_tri_offset[job.mesh];
-    if (job.morph) {
-      HIP_TRY(ctx, mesh_morph_launch(*job.morph, job.skin, first, ctx->d_skin_flags.get() + j));
-      mst.last_launches++;
-      if (job.new_pose) st.last_launches++;
-    }
-    else {
-      HIP_TRY(ctx, mesh_skin_launch(*job.skin, first, ctx->d_skin_flags.get() + j));
-      st.last_launches++;
-    }
+    const MeshDeform& d = *jobs[j].second;
+    HIP_TRY(ctx, mesh_deform_launch(d, vertices.get() + 3 * (size_t) ctx->mesh_tri_offset[jobs[j].first], ctx->d_skin_flags.get() + j));
+    if (d.morph) mst.last_launches++;
+    if (!d.morph || d.new_pose()) st.last_launches++;
   }
   std::vector<uint32_t> flags(jobs.size());
   HIP_TRY(ctx, hipMemcpy(flags.data(), ctx->d_skin_flags.get(), sizeof(uint32_t) * jobs.size(), hipMemcpyDeviceToHost));  // (waits for the launches)
   if (any_skin) { st.seconds_upload = seconds_upload; st.seconds_skin = t_skin.seconds(); st.seconds = t_all.seconds(); }
   if (any_morph) { mst.seconds_upload = seconds_upload; mst.seconds_morph = t_skin.seconds(); mst.seconds = t_all.seconds(); }
   for (size_t j = 0; j < jobs.size(); j++) {
-    const std::string mesh = "lumc_scene_update: mesh " + std::to_string(jobs[j].mesh);
+    const std::string mesh = "lumc_scene_update: mesh " + std::to_string(jobs[j].first);
     if (flags[j] & kSkinFlagBadBone) { ctx->error = mesh + ": a bone id beyond the palette reached the skinning kernel"; return 1; }
     if (flags[j] & kMorphFlagBadLayout) { ctx->error = mesh + ": a target id or a row beyond the binding reached the morph kernel"; return 1; }
-    if (flags[j] & kSkinFlagNotFinite) { ctx->error = mesh + (jobs[j].morph ? ": the weights give a position that is not finite" : ": the pose gives a position that is not finite"); return 1; }
+    if (flags[j] & kSkinFlagNotFinite) { ctx->error = mesh + (jobs[j].second->morph ? ": the weights give a position that is not finite" : ": the pose gives a position that is not finite"); return 1; }
   }
-  for (const Job& job : jobs) {
-    if (job.new_pose) { job.skin->pending.clear(); job.skin->posed = true; st.poses++; st.last_meshes++; }
-    if (job.new_weights) { job.morph->pending.clear(); job.morph->applied = true; mst.applied++; mst.last_meshes++; }
-    if (job.new_pose || job.new_weights) posed->push_back(job.mesh);
+  for (const auto& [m, d] : jobs) {
+    if (d->pending()) posed->push_back(m);
+    if (d->new_pose()) { d->skin->pending.clear(); d->skin->posed = true; st.poses++; st.last_meshes++; }
+    if (d->new_weights()) { d->morph->pending.clear(); d->morph->applied = true; mst.applied++; mst.last_meshes++; }
   }
   return 0;
 }
@@ -510,7 +488,8 @@ static int download_posed_vertices(LumContext* ctx, uint32_t m, uint32_t t0, uin
   out.resize(12 * (size_t) nt);
   if (3 * ((size_t) t0 + nt) > ctx->arrays.mesh.vertices.count()) { ctx->error = "lumc_scene_update: a posed mesh lies outside the vertex array"; return 1; }
   HIP_TRY(ctx, hipMemcpy(out.data(), ctx->arrays.mesh.vertices.get() + 3 * (size_t) t0, sizeof(float) * out.size(), hipMemcpyDeviceToHost));
-  if (ctx->mesh_morph.count(m)) ctx->morph_stats.rebuild_downloads++;  // (LumMeshSkinStats keeps its meaning for meshes that are only skinned)
+  const auto it = ctx->mesh_deform.find(m);
+  if (it != ctx->mesh_deform.end() && it->second.morph) ctx->morph_stats.rebuild_downloads++;  // (LumMeshSkinStats keeps its meaning for meshes that are only skinned)
   else ctx->skin_stats.rebuild_downloads++;
   return 0;
 }
@@ -519,7 +498,7 @@ static int download_posed_vertices(LumContext* ctx, uint32_t m, uint32_t t0, uin
 // each a tree for its vertices - refit_in_place in the resident node array, refit_mesh_copies in copies on the host ----
 struct MovedMeshes {
   std::vector<uint32_t> meshes;   // ascending
-  std::vector<MeshTreeKey> keys;  // of the view's vertices; zeros for a posed mesh (no host vertices hash to what k_skin_mesh wrote)
+  std::vector<MeshTreeKey> keys;  // of the view's vertices; zeros for a posed mesh (no host vertices hash to what k_deform_mesh wrote)
   std::vector<bool> posed;        // moved by a pose: no hash, and the view's vertices of it are never read
   bool refittable = true;         // every one's tree has one reference per triangle (false - spatial splits -: refit_mesh_copies builds that mesh again)
   double seconds = 0.0;           // what finding them took, uploads and skinning included: the head of either path's `seconds`
@@ -1207,8 +1186,7 @@ static int scene_update(LumContext* ctx, const LumDeviceSceneView* v, unsigned d
   if (!v->bluenoise_2d) { ctx->error = "scene has no blue-noise mask"; return 1; }
   if (v->max_ray_depth > 63) { ctx->error = "max_ray_depth exceeds 63 (6-bit field, device_structs.h:9)"; return 1; }
   bool pose_pending = false;
-  for (const auto& kv : ctx->mesh_skin) pose_pending = pose_pending || !kv.second.pending.empty();
-  for (const auto& kv : ctx->mesh_morph) pose_pending = pose_pending || !kv.second.pending.empty();  // pending weights are a pending pose
+  for (const auto& kv : ctx->mesh_deform) pose_pending = pose_pending || kv.second.pending();  // pending weights are a pending pose
   UpdatePlan plan = plan_update(dirty, ctx->refit_in_place != 0, ctx->refit_mode, ctx->instance_update_mode, pose_pending, ctx->light_refit.bound);
   if (plan.moved_by_host) reset_update(ctx->instance_stats);
   auto host_path_since = [&](const Stopwatch& t) { if (plan.moved_by_host) ctx->instance_stats.seconds += t.seconds(); };
@@ -1216,7 +1194,7 @@ static int scene_update(LumContext* ctx, const LumDeviceSceneView* v, unsigned d
   ctx->has_scene = false;
   ctx->lights_refitted = false;
   if (plan.lights || plan.meshes) { ctx->light_refit.reset(); ctx->light_refit_needs_rebuild = false; }  // new lights: the plan's topology is not theirs, the caller binds again
-  if (plan.meshes) { ctx->arrays.mesh = {}; ctx->mesh_skin.clear(); ctx->mesh_morph.clear(); }  // the traversal triangles too; new meshes: the bindings go, the caller binds again
+  if (plan.meshes) { ctx->arrays.mesh = {}; ctx->mesh_deform.clear(); }  // the traversal triangles too; new meshes: the bindings go, the caller binds again
   if (plan.meshes && update_mesh_arrays(ctx, v)) return 1;
   bool triangles_rewritten = false;
   if (plan.positions) {
@@ -1348,27 +1326,28 @@ int lumc_mesh_skin_bind(LumContext* ctx, uint32_t mesh, const float* rest_positi
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   MeshSkin skin;
   HIP_TRY(ctx, mesh_skin_upload(skin, rest_positions, rest_normals, bone_ids, weights, triangle_count, bone_count));
-  ctx->mesh_skin[mesh] = std::move(skin);
+  ctx->mesh_deform[mesh].skin = std::move(skin);  // (the morph, if any, stays)
   return 0;
 }
 
 int lumc_mesh_skin_unbind(LumContext* ctx, uint32_t mesh) {
   if (!ctx) return 1;
-  const auto it = ctx->mesh_skin.find(mesh);
-  if (it == ctx->mesh_skin.end()) { ctx->error = "lumc_mesh_skin_unbind: mesh " + std::to_string(mesh) + " is not bound"; return 1; }
+  const auto it = ctx->mesh_deform.find(mesh);
+  if (it == ctx->mesh_deform.end() || !it->second.skin) { ctx->error = "lumc_mesh_skin_unbind: mesh " + std::to_string(mesh) + " is not bound"; return 1; }
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  ctx->mesh_skin.erase(it);
+  it->second.skin.reset();
+  if (it->second.empty()) ctx->mesh_deform.erase(it);
   return 0;
 }
 
 int lumc_mesh_skin_pose(LumContext* ctx, uint32_t mesh, const float* bones, uint32_t bone_count) {
   if (!ctx) return 1;
-  const auto it = ctx->mesh_skin.find(mesh);
-  if (it == ctx->mesh_skin.end()) { ctx->error = "lumc_mesh_skin_pose: mesh " + std::to_string(mesh) + " is not bound"; return 1; }
-  if (!bones || bone_count != it->second.bone_count) { ctx->error = "lumc_mesh_skin_pose: mesh " + std::to_string(mesh) + " is bound to another bone count"; return 1; }
+  const auto it = ctx->mesh_deform.find(mesh);
+  if (it == ctx->mesh_deform.end() || !it->second.skin) { ctx->error = "lumc_mesh_skin_pose: mesh " + std::to_string(mesh) + " is not bound"; return 1; }
+  if (!bones || bone_count != it->second.skin->bone_count) { ctx->error = "lumc_mesh_skin_pose: mesh " + std::to_string(mesh) + " is bound to another bone count"; return 1; }
   for (size_t i = 0; i < 12 * (size_t) bone_count; i++)
     if (!std::isfinite(bones[i])) { ctx->error = "lumc_mesh_skin_pose: a matrix entry is not finite"; return 1; }
-  it->second.pending.assign(bones, bones + 12 * (size_t) bone_count);
+  it->second.skin->pending.assign(bones, bones + 12 * (size_t) bone_count);
   return 0;
 }
 
@@ -1390,27 +1369,28 @@ int lumc_mesh_morph_bind(LumContext* ctx, uint32_t mesh, const float* base_posit
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   MeshMorph morph;
   HIP_TRY(ctx, mesh_morph_upload(morph, base_positions, base_normals, triangle_count, target_count, offsets, corners, delta_positions, delta_normals));
-  ctx->mesh_morph[mesh] = std::move(morph);
+  ctx->mesh_deform[mesh].morph = std::move(morph);  // (the skin, if any, stays)
   return 0;
 }
 
 int lumc_mesh_morph_unbind(LumContext* ctx, uint32_t mesh) {
   if (!ctx) return 1;
-  const auto it = ctx->mesh_morph.find(mesh);
-  if (it == ctx->mesh_morph.end()) { ctx->error = "lumc_mesh_morph_unbind: mesh " + std::to_string(mesh) + " is not bound"; return 1; }
+  const auto it = ctx->mesh_deform.find(mesh);
+  if (it == ctx->mesh_deform.end() || !it->second.morph) { ctx->error = "lumc_mesh_morph_unbind: mesh " + std::to_string(mesh) + " is not bound"; return 1; }
   HIP_TRY(ctx, hipSetDevice(ctx->device));
-  ctx->mesh_morph.erase(it);
+  it->second.morph.reset();
+  if (it->second.empty()) ctx->mesh_deform.erase(it);
   return 0;
 }
 
 int lumc_mesh_morph_weights(LumContext* ctx, uint32_t mesh, const float* weights, uint32_t target_count) {
   if (!ctx) return 1;
-  const auto it = ctx->mesh_morph.find(mesh);
-  if (it == ctx->mesh_morph.end()) { ctx->error = "lumc_mesh_morph_weights: mesh " + std::to_string(mesh) + " is not bound"; return 1; }
-  if (!weights || target_count != it->second.target_count) { ctx->error = "lumc_mesh_morph_weights: mesh " + std::to_string(mesh) + " is bound to another target count"; return 1; }
+  const auto it = ctx->mesh_deform.find(mesh);
+  if (it == ctx->mesh_deform.end() || !it->second.morph) { ctx->error = "lumc_mesh_morph_weights: mesh " + std::to_string(mesh) + " is not bound"; return 1; }
+  if (!weights || target_count != it->second.morph->target_count) { ctx->error = "lumc_mesh_morph_weights: mesh " + std::to_string(mesh) + " is bound to another target count"; return 1; }
   for (uint32_t t = 0; t < target_count; t++)
     if (!std::isfinite(weights[t])) { ctx->error = "lumc_mesh_morph_weights: a weight is not finite"; return 1; }
-  it->second.pending.assign(weights, weights + target_count);
+  it->second.morph->pending.assign(weights, weights + target_count);
   return 0;
 }
 

@@ -1,15 +1,15 @@
-// Stand-alone check of the morph twin (csrc/host/mesh_morph.cpp), built with the address and undefined-behaviour sanitizers by tests/test_mesh_morph.py: triangle
+// Stand-alone check of the morph twin (csrc/host/mesh_deform.cpp), built with the address and undefined-behaviour sanitizers by tests/test_mesh_morph.py: triangle
 // counts on either side of a wave and of a workgroup of corners; 1, 3 and 1024 targets with the last target named; a corner with an entry in every target, one
 // with a single entry, one with none; with and without normal deltas, with and without a skin of 1 and 1024 bones; outputs that alias the inputs, outputs left
 // out, refused arguments. What it computes is held to numpy there; here every access is.
-#define LUM_SKIN_HOST_ONLY 1
+#define LUM_DEFORM_HOST_ONLY 1
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
 
-#include "../../luminary_amd/csrc/host/mesh_morph.h"
+#include "../../luminary_amd/csrc/host/mesh_deform.h"
 
 static int fail(const char* what, unsigned triangles, unsigned targets) {
   std::printf("mesh_morph_check: %s (triangles %u, targets %u)\n", what, triangles, targets);

@@ -1,13 +1,13 @@
-// Stand-alone check of the skinning twin (csrc/host/mesh_skin.cpp), built with the address and undefined-behaviour sanitizers by tests/test_mesh_skin.py: triangle
+// Stand-alone check of the skinning twin (csrc/host/mesh_deform.cpp), built with the address and undefined-behaviour sanitizers by tests/test_mesh_skin.py: triangle
 // counts on either side of a wave and of a workgroup of corners, one bone and 1024 bones, ids that name the last bone, outputs that alias the inputs, outputs left
 // out, refused arguments. What it computes is held to numpy there; here every access is.
-#define LUM_SKIN_HOST_ONLY 1
+#define LUM_DEFORM_HOST_ONLY 1
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
 
-#include "../../luminary_amd/csrc/host/mesh_skin.h"
+#include "../../luminary_amd/csrc/host/mesh_deform.h"
 
 static int fail(const char* what, unsigned triangles, unsigned bones) {
   std::printf("mesh_skin_check: %s (triangles %u, bones %u)\n", what, triangles, bones);

@@ -1,5 +1,5 @@
-"""Morph targets on the host side (include/lum_core.h lumc_morph_host; include/luminary_amd.h luminary_ext_bind_mesh_morph / _set_mesh_weights; csrc/host/mesh_morph.h,
-mesh_morph.cpp, api.cpp), no GPU.
+"""Morph targets on the host side (include/lum_core.h lumc_morph_host; include/luminary_amd.h luminary_ext_bind_mesh_morph / _set_mesh_weights; csrc/host/mesh_deform.h,
+mesh_deform.cpp, api.cpp), no GPU.
 
 morph(base, deltas, weights) is one function compiled twice; this file holds the host's compilation - the twin - to a numpy restatement of the definition, float32 one
 operation at a time with the normal packed in float64, byte for byte, and to a float64 evaluation within the rounding bound; tests/test_mesh_morph_gpu.py holds the
@@ -509,7 +509,7 @@ def test_stand_alone_program_under_address_and_undefined_behaviour_sanitizers(tm
     exe = str(tmp_path / "mesh_morph_check")
     host = os.path.join(ROOT, "luminary_amd", "csrc", "host")
     cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-static-libasan", "-static-libubsan", "-ffp-contract=off",
-           os.path.join(ROOT, "tests", "support", "mesh_morph_check.cpp"), os.path.join(host, "mesh_morph.cpp"), os.path.join(host, "mesh_skin.cpp"), "-o", exe]
+           os.path.join(ROOT, "tests", "support", "mesh_morph_check.cpp"), os.path.join(host, "mesh_deform.cpp"), "-o", exe]
     built = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     assert built.returncode == 0, built.stdout
     ran = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)  # (the runtimes are linked statically: the program needs nothing preloaded)

@@ -1,4 +1,4 @@
-"""Morph targets on the device: lumc_mesh_morph_bind / lumc_mesh_morph_weights -> LUMC_DIRTY_MESH_SKIN -> csrc/host/mesh_morph.hip k_morph_mesh, scene_device.hip
+"""Morph targets on the device: lumc_mesh_morph_bind / lumc_mesh_morph_weights -> LUMC_DIRTY_MESH_SKIN -> csrc/host/mesh_deform.hip k_deform_mesh, scene_device.hip
 skin_meshes.
 
 The kernel's vertex records are held to the host twin's (lumc_morph_host; tests/test_mesh_morph.py holds that to the definition) byte for byte, the packed normal word
@@ -9,7 +9,7 @@ import pytest
 
 import oracle_lib
 from luminary_amd import Host, scenes
-from luminary_amd.core import DIRTY_LIGHTS, DIRTY_MESH_POSITIONS, DIRTY_MESH_SKIN, CoreError, morph_host
+from luminary_amd.core import DIRTY_LIGHTS, DIRTY_MESH_POSITIONS, DIRTY_MESH_SKIN, CoreError, morph_host, skin_host
 from test_instance_transforms_api import moved_instances
 from test_instance_update_gpu import _against_oracle, _same
 from test_mesh_morph import bulge_targets, random_morph, random_weights
@@ -101,7 +101,7 @@ def test_weights_move_the_vertices_on_the_device_and_render_like_the_oracle():
 
 # ---- sizes at which the kernel can go wrong ----
 # SOUPS (tests/test_mesh_skin_gpu.py): 3, 63, 66 corners (a wave), 255, 258 (a workgroup), 513 (two workgroups and one), 262146 (the whole grid once, and two
-# corners): k_morph_mesh has k_skin_mesh's block (256) and grid cap (1024), so the sizes are its sizes.
+# corners): k_deform_mesh has one block (256) and one grid cap (1024) for all three of its forms, so the sizes are its sizes.
 @pytest.fixture(scope="module")
 def soups():
     rng = np.random.RandomState(5)
@@ -463,3 +463,89 @@ def test_the_host_api_end_to_end(slots, monkeypatch):
         _same(sm, osm, "%d slots, unbound and moved by the host route: second moment vs oracle" % slots)
     finally:
         host.close()
+
+
+# ---- one binding goes, the other stays ----
+def test_a_part_that_is_unbound_leaves_the_other_and_the_last_takes_the_binding_along():
+    """22 and 86 triangles (66 corners: just over a wave; 258: just over a workgroup), 3 bones, 3 targets; the skin's rest shape is NOT the morph's base. After every
+    update the vertices are the twin's, byte for byte, and the two stats structs count what skin_meshes is documented to count."""
+    rng = np.random.RandomState(11)
+    sizes = [22, 86]
+    host = Host()
+    scenes.apply_benchmark_settings(host, 16, 16, 2, sky=(0.5, 0.5, 0.5))
+    mat = host.add_material(scenes._material((0.6, 0.6, 0.6), 0.6))
+    core = _core()
+    try:
+        base = [(soup(rng, n).reshape(n, 9), unit_normals(rng, n)) for n in sizes]
+        rest = [(soup(rng, n).reshape(n, 9), unit_normals(rng, n)) for n in sizes]
+        assert all(not np.array_equal(b[0], r[0]) and not np.array_equal(b[1], r[1]) for b, r in zip(base, rest)), "two shapes per mesh"
+        for k, (t, nrm) in enumerate(base):
+            host.new_instance(host.add_mesh(t, np.full(len(t), mat, dtype=np.uint16), normals=nrm), position=(3.0 * k, 0.0, 0.0))
+        scenes.set_camera(host, (0.0, 0.0, 40.0), (0.0, 0.0, 0.0))
+        view = _view(host)
+        core.upload(view)
+        skins = [random_skin(rng, n, 3) for n in sizes]
+        morphs = [random_morph(rng, n, 3) for n in sizes]
+        meshes = range(len(sizes))
+
+        def updated(where, want, skin_counts, morph_counts):
+            core.update(view, DIRTY_MESH_SKIN)
+            for m in meshes:
+                p, _, packed = want(m)
+                got, records = core.mesh_vertices_probe(m, sizes[m]), _records(p, packed)
+                assert np.array_equal(got, records), "%s: %d of %d words of mesh %d differ from the twin's" % (where, int((got != records).sum()), got.size, m)
+            s, ms = core.mesh_skin_stats(), core.mesh_morph_stats()
+            assert (s.poses, s.last_meshes, s.last_launches, s.last_bytes_uploaded) == skin_counts, (where, "skin")
+            assert (ms.applied, ms.last_meshes, ms.last_launches, ms.last_bytes_uploaded) == morph_counts, (where, "morph")
+            assert (s.rebuild_downloads, ms.rebuild_downloads) == (0, 0), where
+
+        def new_pose():
+            bones = random_bones(rng, 3, scale=True)
+            for m in meshes:
+                core.mesh_skin_pose(m, bones)
+            return bones
+
+        def new_weights():
+            w = random_weights(rng, 3)
+            for m in meshes:
+                core.mesh_morph_weights(m, w)
+            return w
+
+        # 1. a skin and a pose: the skin's own rest shape
+        for m in meshes:
+            core.mesh_skin_bind(m, *rest[m], *skins[m], 3)
+        bones = new_pose()
+        updated("skin alone", lambda m: skin_host(*rest[m], *skins[m], bones), (2, 2, 2, 2 * 144), (0, 0, 0, 0))
+        # 2. a morph next to it: the morph's base under the kept palette, the skin's rest shape is not read; no new pose, so the skin's stats are the last update's
+        for m in meshes:
+            core.mesh_morph_bind(m, *base[m], *morphs[m].lists)
+        w = new_weights()
+        updated("morph and skin", lambda m: morph_host(*base[m], *morphs[m].lists, w, *skins[m], bones), (2, 2, 2, 2 * 144), (2, 2, 2, 2 * 12))
+        # 3. the skin goes, the morph stays
+        for m in meshes:
+            core.mesh_skin_unbind(m)
+        w = new_weights()
+        updated("skin unbound", lambda m: morph_host(*base[m], *morphs[m].lists, w), (2, 2, 2, 2 * 144), (4, 2, 2, 2 * 12))
+        # 4. a skin again, without a pose: the morph alone writes
+        for m in meshes:
+            core.mesh_skin_bind(m, *rest[m], *skins[m], 3)
+        w = new_weights()
+        updated("skin bound again, no pose yet", lambda m: morph_host(*base[m], *morphs[m].lists, w), (2, 2, 2, 2 * 144), (6, 2, 2, 2 * 12))
+        # 5. the morph goes, the skin stays and gets a pose: its own rest shape again
+        for m in meshes:
+            core.mesh_morph_unbind(m)
+        bones = new_pose()
+        updated("morph unbound", lambda m: skin_host(*rest[m], *skins[m], bones), (4, 2, 2, 2 * 144), (6, 2, 2, 2 * 12))
+        with pytest.raises(CoreError, match="not bound"):
+            core.mesh_morph_weights(0, np.zeros(3, F))
+        # 6. the last part takes the binding along
+        for m in meshes:
+            core.mesh_skin_unbind(m)
+            with pytest.raises(CoreError, match="not bound"):
+                core.mesh_skin_pose(m, bones)
+            with pytest.raises(CoreError, match="not bound"):
+                core.mesh_skin_unbind(m)
+            with pytest.raises(CoreError, match="not bound"):
+                core.mesh_morph_unbind(m)
+    finally:
+        core.close(); host.close()

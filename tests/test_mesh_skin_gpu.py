@@ -1,4 +1,4 @@
-"""Skinned meshes on the device: lumc_mesh_skin_bind / lumc_mesh_skin_pose -> LUMC_DIRTY_MESH_SKIN -> csrc/host/mesh_skin.hip k_skin_mesh, scene_device.hip skin_meshes.
+"""Skinned meshes on the device: lumc_mesh_skin_bind / lumc_mesh_skin_pose -> LUMC_DIRTY_MESH_SKIN -> csrc/host/mesh_deform.hip k_deform_mesh, scene_device.hip skin_meshes.
 
 The kernel's vertex records are held to the host twin's (lumc_skin_host; tests/test_mesh_skin.py holds that to the definition) byte for byte, the packed normal word
 included; what the update leaves in the node array to a second context that was given the same vertices through LUMC_DIRTY_MESH_POSITIONS; what is rendered over it

@@ -6,7 +6,7 @@
 The scene is the hall of tools/mesh_skin_bench.py (one mesh, 1.43 M triangles, and a second, small instance so that two instances can be hit), the refit in the
 resident node array on. Eight targets, each a bulge over a region of the large mesh, with weights animated over the frames. Two cases, each with two hosts of this
 process that take every frame:
-  morph       luminary_ext_bind_mesh_morph once, then luminary_ext_set_mesh_weights per frame: 32 bytes go to the device, k_morph_mesh writes the vertices there
+  morph       luminary_ext_bind_mesh_morph once, then luminary_ext_set_mesh_weights per frame: 32 bytes go to the device, k_deform_mesh writes the vertices there
   morph+skin  the same mesh also bound to the two-bone bend of tools/mesh_skin_bench.py: weights and a pose per frame, 32 + 96 bytes, one kernel
   baseline    the route before there was one: the same positions and normals - from lumc_morph_host, the same bytes - handed to luminary_ext_set_mesh_positions
 A frame's update is the edit call(s) plus the host call that brings the device up to date, luminary_ext_render_samples of one sample of a small frame (the same on

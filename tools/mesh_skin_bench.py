@@ -5,7 +5,7 @@
 
 The scene is the hall of tools/resident_refit_bench.py (one mesh, 1.43 M triangles, and a second, small instance so that two instances can be hit), the refit in
 the resident node array on. The motion is a two-bone bend of the large mesh whose angle grows over the frames. Two hosts of this process take every frame:
-  skin      luminary_ext_bind_mesh_skin once, then luminary_ext_set_mesh_pose per frame: 96 bytes go to the device, k_skin_mesh writes the vertices there
+  skin      luminary_ext_bind_mesh_skin once, then luminary_ext_set_mesh_pose per frame: 96 bytes go to the device, k_deform_mesh writes the vertices there
   baseline  the route before there was one: the same positions and normals - from lumc_skin_host, the same bytes - handed to luminary_ext_set_mesh_positions
 A frame's update is the edit call plus the host call that brings the device up to date, luminary_ext_render_samples of one sample of a small frame (the same on
 both hosts; its own time is measured on an unchanged scene and reported as render_s), wall clock. The CPU skinning that the baseline's caller has to do is timed

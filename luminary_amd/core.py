@@ -445,6 +445,16 @@ class Core:
         fn.restype = C.c_int
         return int(fn(self._ctx))
 
+    def set_plain_form(self, mode):
+        """-1 auto, 0 never, 1 when eligible: the shading kernel's form without refraction, light-tree descent and textured lights (lumc_set_plain_form)"""
+        self._call("lumc_set_plain_form", C.c_int(mode))
+
+    def get_plain_form(self):
+        """1 when the next launch of the shading kernel takes the plain form for the uploaded scene (lumc_get_plain_form: by mode and scene), else 0"""
+        fn = self._lib.lumc_get_plain_form
+        fn.restype = C.c_int
+        return int(fn(self._ctx))
+
     def set_physical_camera(self, camera):
         """lumc_set_physical_camera: a PhysicalCamera, or None for the scene's thin lens"""
         self._call("lumc_set_physical_camera", C.byref(camera) if camera is not None else C.c_void_p(0))

@@ -274,8 +274,9 @@ LUM_DEV TreeWork tree_prepass(const DeviceScene& sc, const Ctx& g, const Smp& sm
 
 struct TreePick { uint32_t light_id; float weight; };
 
-// Descent of one lane through the 8-wide nodes (light_tree.cuh:257-320).
-template <class Ctx, class Smp>
+// Descent of one lane through the 8-wide nodes (light_tree.cuh:257-320). kPlain (k_shade's plain form, kernels.h): the tree is flat - every root child is a
+// light - so the lane's pick is the light or nothing, and the descent is not compiled in.
+template <bool kPlain = false, class Ctx, class Smp>
 LUM_DEV TreePick tree_postpass(const DeviceScene& sc, const Ctx& g, const Smp& smp, uint32_t lane, const TreeWork& w) {
   const uint32_t cont = w.cont[lane];
   const float cp = (cont >> 9) * (1.0f / 1048575.0f) * kLightTreeOutputs;
@@ -285,6 +286,7 @@ LUM_DEV TreePick tree_postpass(const DeviceScene& sc, const Ctx& g, const Smp& s
   if (cp == 0.0f) return r;
   const uint32_t index = (cont >> 1) & 0xFFu;
   if (cont & 1u) { r.light_id = index; return r; }
+  if (kPlain) return r;
   uint32_t node_id = index;
   Reservoir rv;
   rv.random = smp.next1(TreeTargets<Ctx>::kPostpass + lane);
@@ -355,18 +357,18 @@ LUM_DEV TableLight load_tri_light_table(const DeviceScene& sc, uint32_t light_id
 // and a handle per candidate through an index it has just computed - five dependent 16-byte gathers, eight times per vertex, from a table of a few KB that every
 // lane of every wave reads. From LDS they cost the address unit nothing and return in a quarter of an L1 hit's time. Lights beyond the staged ones are read from
 // memory as before (one branch per candidate); the values are the same words either way.
-#ifndef LUM_LDS_LIGHTS
-#define LUM_LDS_LIGHTS 256
-#endif
+// (LUM_LDS_LIGHTS: dev_scene.h - the launcher of k_shade's plain form asks for a scene whose lights are all staged)
 typedef float LdsF4 __attribute__((ext_vector_type(4)));
 struct StagedLights {
   const __attribute__((address_space(3))) LdsF4* table;
   const __attribute__((address_space(3))) unsigned long long* handles;
   uint32_t count;
 };
+// kPlain: every light of the scene is staged (num_lights <= LUM_LDS_LIGHTS), the arm that reads memory is not compiled in.
+template <bool kPlain = false>
 LUM_DEV TableLight load_tri_light_table(const DeviceScene& sc, const StagedLights& sl, uint32_t light_id, uint2& handle) {
   float4 a, b, c, d;
-  if (light_id < sl.count) {
+  if (kPlain || light_id < sl.count) {
     const LdsF4 va = sl.table[4u * light_id], vb = sl.table[4u * light_id + 1u], vc = sl.table[4u * light_id + 2u], vd = sl.table[4u * light_id + 3u];
     const unsigned long long h = sl.handles[light_id];
     a = make_float4(va.x, va.y, va.z, va.w); b = make_float4(vb.x, vb.y, vb.z, vb.w); c = make_float4(vc.x, vc.y, vc.z, vc.w); d = make_float4(vd.x, vd.y, vd.z, vd.w);
@@ -386,6 +388,15 @@ LUM_DEV TableLight load_tri_light_table(const DeviceScene& sc, const StagedLight
   e.color = col(d.x, d.y, d.z);
   e.textured = fbits(d.w) != 0u;
   return e;
+}
+// A light's handle alone (k_shade, for the light the candidate loop chose): the staged word where the light is staged, the same word from memory otherwise.
+template <bool kPlain = false>
+LUM_DEV uint2 light_handle(const DeviceScene& sc, const StagedLights& sl, uint32_t light_id) {
+  if (kPlain || light_id < sl.count) {
+    const unsigned long long h = sl.handles[light_id];
+    return make_uint2((uint32_t) h, (uint32_t) (h >> 32));
+  }
+  return sc.light_tri_handles[light_id];
 }
 LUM_DEV float tri_light_solid_angle(const TriLight& t, V3 origin) {  // light_triangle.cuh:94-108
   const V3 a = normalize(t.vertex - origin), b = normalize((t.vertex + t.edge1) - origin), c = normalize((t.vertex + t.edge2) - origin);
@@ -526,18 +537,19 @@ LUM_DEV float light_direction_probability_terms(const MatParams& p, V3 Vl, const
 // ---- light sampling (light.cuh:84-159) ----
 struct LightSample { uint32_t light_id; V3 ray; Col color; float dist, root_sum; };
 
-template <class Smp>
+// kPlain (k_shade's plain form, kernels.h; threaded like the sampler's kTable): a flat light tree whose lights are all staged in LDS and none of them textured.
+template <bool kPlain = false, class Smp>
 LUM_DEV LightSample light_candidates(const DeviceScene& sc, const GeoContext& g, const Smp& smp, ShadeClock& clock, const StagedLights& staged, const TreeWork& work,
                                      const Energy& energy);
-template <class Smp>
+template <bool kPlain = false, class Smp>
 LUM_DEV LightSample sample_light(const DeviceScene& sc, const GeoContext& g, const Smp& smp, ShadeClock& clock, const StagedLights& staged) {
   LUM_STAT(14, 15);
   const TreeWork work = tree_prepass(sc, g, smp);
   const Energy energy = energy_terms(sc, g.params, world_ndotv(g));
   LUM_LAP(clock, 1);
-  return light_candidates(sc, g, smp, clock, staged, work, energy);
+  return light_candidates<kPlain>(sc, g, smp, clock, staged, work, energy);
 }
-template <class Smp>
+template <bool kPlain, class Smp>
 LUM_DEV LightSample light_candidates(const DeviceScene& sc, const GeoContext& g, const Smp& smp, ShadeClock& clock, const StagedLights& staged, const TreeWork& work,
                                      const Energy& energy) {
   LightSample out;
@@ -554,11 +566,11 @@ LUM_DEV LightSample light_candidates(const DeviceScene& sc, const GeoContext& g,
 #pragma nounroll
   for (uint32_t lane = 0; lane < LUM_ABLATE_LANES; lane++) {
     LUM_STAT(8, 9);
-    const TreePick pick = tree_postpass(sc, g, smp, lane, work);
+    const TreePick pick = tree_postpass<kPlain>(sc, g, smp, lane, work);
     if (pick.light_id == kLightIdInvalid) continue;
 #if LUM_LDS_LIGHTS
     uint2 handle;
-    const TableLight entry = load_tri_light_table(sc, staged, pick.light_id, handle);
+    const TableLight entry = load_tri_light_table<kPlain>(sc, staged, pick.light_id, handle);
 #else
     const uint2 handle = sc.light_tri_handles[pick.light_id];
     const TableLight entry = load_tri_light_table(sc, pick.light_id);
@@ -573,7 +585,7 @@ LUM_DEV LightSample light_candidates(const DeviceScene& sc, const GeoContext& g,
     if (dist == kFltMax) continue;
     LUM_STAT(10, 11);
     LUM_LAP(clock, 10);
-    Col lc = entry.textured ? tri_light_color(sc, tl, uv) : entry.color;
+    Col lc = (!kPlain && entry.textured) ? tri_light_color(sc, tl, uv) : entry.color;
     bool is_refraction;
 #ifndef LUM_ABLATE_LIGHT_DEFINED_BELOW
 #define LUM_ABLATE_LIGHT_DEFINED_BELOW

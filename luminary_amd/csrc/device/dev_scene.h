@@ -49,6 +49,19 @@ constexpr uint32_t kBvhTriNoTexture = 0xFFFFFFFFu;
 constexpr uint32_t kBvhTriOpaque = 0xFFFFFFFEu;
 static_assert(sizeof(BvhTri) == 48, "48 bytes per triangle");
 
+// Lights whose table lines and handles every workgroup of k_shade stages in LDS (dev_light.h StagedLights); 0: none, the candidate loop reads memory.
+#ifndef LUM_LDS_LIGHTS
+#define LUM_LDS_LIGHTS 256
+#endif
+
+// Facts about the scene's content that hold from an upload to the next update of the part they come from (DeviceScene::traits; plain_scene, wavefront_table.h):
+enum SceneTrait : uint32_t {
+  kTraitNoTranslucent = 1u,   // no material has the translucent substrate
+  kTraitFlatLightTree = 2u,   // every child of the light tree's root is a light (or there are no lights): nothing descends
+  kTraitPlainEmitters = 4u,   // no light's material has an emission or albedo texture: the light table's colour is the light's colour
+  kTraitsPlain = kTraitNoTranslucent | kTraitFlatLightTree | kTraitPlainEmitters
+};
+
 struct DeviceScene {
   // geometry
   const uint32_t* mesh_tri_offset;
@@ -145,6 +158,9 @@ struct DeviceScene {
   // dimensions 0 .. (max_ray_depth + 1) * kRndTargetCount - 1; nullptr in passes without one (set per pass on the host's copy, wavefront_depths)
   const uint2* sobol_table;
   uint32_t sobol_first, sobol_count, sobol_stride;
+  // SceneTrait bits (above), computed on the host from what it uploads (scene_device.hip scene_traits) and read by the launchers, not by kernels. Last, in what was
+  // the struct's tail padding: no kernel argument moves.
+  uint32_t traits;
 };
 
 // Path state, one entry per live path, structure-of-arrays of 16-byte words (coalesced 16 B/lane accesses).

@@ -15,6 +15,16 @@ namespace lum {
 // removes instances needs no invalidation; `single_level` in their signatures is the context's switch (lumc_set_single_level), never the decision itself.
 inline bool single_level_scene(const DeviceScene& sc) { return sc.tlas_num_nodes == 1u && sc.tlas_num_leaves == 2u; }
 
+// k_shade has a plain form (kernels.h k_shade<.., kPlain>) for a scene without translucent materials, with a flat light tree whose lights are all staged in LDS
+// (dev_light.h LUM_LDS_LIGHTS) and untextured, without an ocean, under a constant-colour or HDRI sky: the refraction halves of the BSDF code, the light tree's
+// descent, the textured light colour and the lights' reads from memory are not compiled into it. The scene's side of that is DeviceScene::traits, kept by every
+// update of the parts it comes from (scene_device.hip scene_traits); the `shade` launcher asks at EVERY launch, `plain_form` in its signature is the context's
+// switch (lumc_set_plain_form), never the decision itself.
+inline bool plain_scene(const DeviceScene& sc) {
+  return (sc.traits & kTraitsPlain) == kTraitsPlain && sc.num_lights <= (uint32_t) LUM_LDS_LIGHTS && !sc.ocean_active &&
+         (sc.sky_mode == kSkyConstantColor || sc.sky_mode == kSkyHdri);
+}
+
 struct WavefrontKernels {
   const char* flavour;
   uint32_t trace_block;  // threads per workgroup of the persistent ray kernels (one workgroup per CU)
@@ -33,7 +43,8 @@ struct WavefrontKernels {
                 uint32_t lds_nodes, bool single_level);
   void (*sky_inscattering)(uint32_t grid, hipStream_t s, const DeviceScene& sc, const PathQueue& in, float4* results, const uint32_t* ctrl, uint32_t depth_const);
   void (*shade)(uint32_t grid, hipStream_t s, const DeviceScene& sc, const PathQueue& in, const PathQueue& out, const NeeQueue& nee, const ShadowQueue& sq, float4* results,
-                uint32_t* ctrl, uint32_t depth_const, uint64_t* counters, uint32_t ambient_reuse, const FusedResolve* fused_dev, uint32_t fused_flags);  // fused_dev: device memory; flags: 1 resolve the entries' parents, 2 announce the survivors' entries
+                uint32_t* ctrl, uint32_t depth_const, uint64_t* counters, uint32_t ambient_reuse, const FusedResolve* fused_dev, uint32_t fused_flags,
+                bool plain_form);  // fused_dev: device memory; flags: 1 resolve the entries' parents, 2 announce the survivors' entries; plain_form: the switch (plain_scene above)
   void (*shade_debug)(uint32_t grid, hipStream_t s, const DeviceScene& sc, const PathQueue& in, float4* results, const uint32_t* ctrl);
   void (*sky)(uint32_t grid, hipStream_t s, const DeviceScene& sc, const PathQueue& in, const ShadowQueue& sq, float4* results, const uint32_t* ctrl, uint32_t depth_const);
   void (*light_query)(uint32_t grid, hipStream_t s, const DeviceScene& sc, const PathQueue& in, const NeeQueue& nee, const ShadowQueue& sq, uint32_t* ctrl, uint32_t depth_const,

@@ -54,12 +54,16 @@ static void sky_inscattering(uint32_t grid, hipStream_t s, const DeviceScene& sc
   hipLaunchKernelGGL(k_sky_inscattering, dim3(grid), dim3(kBlock), 0, s, sc, in, results, ctrl, depth_const);
 }
 static void shade(uint32_t grid, hipStream_t s, const DeviceScene& sc, const PathQueue& in, const PathQueue& out, const NeeQueue& nee, const ShadowQueue& sq, float4* results,
-                  uint32_t* ctrl, uint32_t depth_const, uint64_t* counters, uint32_t ambient_reuse, const FusedResolve* fused_dev, uint32_t fused_flags) {
+                  uint32_t* ctrl, uint32_t depth_const, uint64_t* counters, uint32_t ambient_reuse, const FusedResolve* fused_dev, uint32_t fused_flags, bool plain_form) {
   auto* k = sc.sky_mode == kSkyDefault ? k_shade<kSkyDefault, false> : sc.sky_mode == kSkyHdri ? k_shade<kSkyHdri, false> : k_shade<kSkyConstantColor, false>;
   if (sc.ocean_active) k = sc.sky_mode == kSkyDefault ? k_shade<kSkyDefault, true> : sc.sky_mode == kSkyHdri ? k_shade<kSkyHdri, true> : k_shade<kSkyConstantColor, true>;
   if (sc.sobol_table) {  // the pass has a Sobol table (dev_sampler.h): the instances that read it instead of hashing
     k = sc.sky_mode == kSkyDefault ? k_shade<kSkyDefault, false, true> : sc.sky_mode == kSkyHdri ? k_shade<kSkyHdri, false, true> : k_shade<kSkyConstantColor, false, true>;
     if (sc.ocean_active) k = sc.sky_mode == kSkyDefault ? k_shade<kSkyDefault, true, true> : sc.sky_mode == kSkyHdri ? k_shade<kSkyHdri, true, true> : k_shade<kSkyConstantColor, true, true>;
+  }
+  if (plain_form && plain_scene(sc)) {  // the plain form (plain_scene, wavefront_table.h): no ocean, one of these two sky modes
+    if (sc.sobol_table) k = sc.sky_mode == kSkyHdri ? k_shade<kSkyHdri, false, true, true> : k_shade<kSkyConstantColor, false, true, true>;
+    else k = sc.sky_mode == kSkyHdri ? k_shade<kSkyHdri, false, false, true> : k_shade<kSkyConstantColor, false, false, true>;
   }
   hipLaunchKernelGGL(k, dim3(grid), dim3(kBlock), 0, s, sc, in, out, nee, sq, results, ctrl, depth_const, counters, ambient_reuse, fused_dev, fused_flags);
 }

@@ -62,6 +62,11 @@ struct LumContext {
   // LUMC_DIRTY_INSTANCE_TRANSFORMS updates (instance_update.hip; scene_device.hip instance_boxes, ensure_resident_layout, build_top_level)
   InstanceUpdate instance_update;            // the resident layout's bookkeeping and the device path's scratch
   std::vector<uint32_t> instance_mesh_ids;   // of the scene on the device: such an update must bring the same
+  // what DeviceScene::traits is computed from (scene_device.hip scene_traits): the host's words of the parts an update may leave alone
+  std::vector<uint16_t> tri_material;        // material id by scene triangle (update_mesh_arrays)
+  std::vector<uint16_t> material_words;      // 16 per material, as uploaded (update_materials)
+  std::vector<uint32_t> light_handles;       // instance, triangle per light (update_light_tree)
+  bool light_tree_flat = true;               // the light tree has no nodes below its root: every root child is a light (update_light_tree)
   uint32_t instance_update_mode = 0;         // lumc_set_instance_update
   LumInstanceUpdateStats instance_stats{};
   // LUMC_DIRTY_MESH_POSITIONS updates in the resident node array (lumc_set_mesh_refit_in_place; bvh_refit.hip, scene_device.hip refit_in_place)
@@ -90,6 +95,7 @@ struct LumContext {
   uint64_t bvh_stats[4] = {0, 0, 0, 0};
   int ambient_reuse = -1;         // -1 by flavour (fast: on), 0 off, 1 on (lumc_set_ambient_reuse; LUM_AMBIENT_REUSE)
   int single_level = -1;          // the ray kernels' single-level form on a scene of one hittable instance: -1 auto (on), 0 never, 1 when eligible (lumc_set_single_level; LUM_SINGLE_LEVEL)
+  int plain_form = -1;            // k_shade's plain form on a scene that has nothing it leaves out (plain_scene, wavefront_table.h): -1 auto (on), 0 never, 1 when eligible (lumc_set_plain_form; LUM_PLAIN_FORM)
   bool first_leaf_identity = false;  // leaf record 0 of the top level maps a ray onto itself (update_scene_tree): see single_level_allowed
   uint32_t shade_grid_rounds = 2;  // k_shade's grid as a multiple of its resident set (0: the common 2048-workgroup cap); LUM_SHADE_GRID
   int fused_resolve = 1;          // with the fast flavour's ambient reuse: k_shade resolves the previous depth's vertices itself (lumc_set_fused_resolve; LUM_FUSED_RESOLVE)

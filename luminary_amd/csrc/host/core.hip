@@ -130,6 +130,7 @@ int lumc_context_create(int device_ordinal, LumContext** out) {
   if (const char* e = getenv("LUM_SORT_KEY")) ctx->sort.key = atoi(e);
   if (const char* e = getenv("LUM_AMBIENT_REUSE")) ctx->ambient_reuse = atoi(e) != 0 ? 1 : 0;
   if (const char* e = getenv("LUM_SINGLE_LEVEL")) ctx->single_level = atoi(e) != 0 ? 1 : 0;
+  if (const char* e = getenv("LUM_PLAIN_FORM")) ctx->plain_form = atoi(e) != 0 ? 1 : 0;
   if (const char* e = getenv("LUM_FUSED_RESOLVE")) ctx->fused_resolve = atoi(e) != 0 ? 1 : 0;
   if (const char* e = getenv("LUM_SHADE_GRID")) ctx->shade_grid_rounds = (uint32_t) atoi(e);
   if (const char* e = getenv("LUM_SOBOL_TABLE_RT")) ctx->sobol_table = atoi(e) != 0 ? 1 : 0;
@@ -364,7 +365,7 @@ static void shade_depth(LumContext* ctx, hipStream_t stream, const DeviceScene& 
     Launch l(ctx, stream, LUMC_KERNEL_SHADE);
     wf.shade(shade_grid(ctx, N), stream, sc, d.cur, d.next, d.nee, ctx->work.shadow, ctx->work.results, d.ctrl, d.depth_const, ctx->d_counters.get(),
              (scheme != kResolvePlain && !d.last) ? 1u : 0u, d.fused_records,
-             fused ? ((d.depth > 0 ? 1u : 0u) | (!d.last ? 2u : 0u) | (ctx->fused_ended ? 4u : 0u)) : 0u);
+             fused ? ((d.depth > 0 ? 1u : 0u) | (!d.last ? 2u : 0u) | (ctx->fused_ended ? 4u : 0u)) : 0u, ctx->plain_form != 0);
   }
   if (fused && d.depth > 0) {  // the samples of depth - 1 their paths' closest hits could not decide: traced now, their vertices resolved (before this depth's visibility pass reuses the words)
     {
@@ -1348,6 +1349,14 @@ int lumc_set_single_level(LumContext* ctx, int mode) {
 }
 // what the launchers will decide for the uploaded scene's surfaces (the particle pass has no single-level form)
 int lumc_get_single_level(const LumContext* ctx) { return (ctx && ctx->has_scene && single_level_allowed(ctx) && single_level_scene(ctx->scene)) ? 1 : 0; }
+
+int lumc_set_plain_form(LumContext* ctx, int mode) {
+  if (!ctx || mode < -1 || mode > 1) { if (ctx) ctx->error = "lumc_set_plain_form: -1 (auto), 0 (never) or 1 (when the scene is eligible)"; return 1; }
+  ctx->plain_form = mode;
+  return 0;
+}
+
+int lumc_get_plain_form(const LumContext* ctx) { return (ctx && ctx->has_scene && ctx->plain_form != 0 && plain_scene(ctx->scene)) ? 1 : 0; }
 int lumc_get_flavour(const LumContext* ctx) { return (ctx && ctx->wf == wavefront_kernels_exact()) ? LUMC_FLAVOUR_EXACT : LUMC_FLAVOUR_FAST; }
 
 unsigned int lumc_lds_stack_bytes(void) { return LUM_LDS_STACK_BYTES; }

@@ -129,6 +129,7 @@ void free_scene(LumContext* ctx) {
   ctx->d_bridge_lut.reset(); ctx->bridge_lut_host.clear();
   ctx->mesh_bvh.clear(); ctx->mesh_box.clear(); ctx->mesh_refit.clear(); ctx->mesh_tri_offset.clear();
   ctx->instance_update.reset(); ctx->instance_mesh_ids.clear();
+  ctx->tri_material.clear(); ctx->material_words.clear(); ctx->light_handles.clear(); ctx->light_tree_flat = true;
   ctx->resident_refit.drop_layout(); ctx->stale_meshes = 0;
   ctx->mesh_deform.clear(); ctx->d_skin_flags.reset();
   ctx->light_refit.reset(); ctx->light_bvh = Bvh4{}; ctx->light_refit_needs_rebuild = false;
@@ -291,6 +292,8 @@ static int update_mesh_arrays(LumContext* ctx, const LumDeviceSceneView* v) {
   a.tri_offset.reset(); a.vertices.reset(); a.tri_tex.reset(); point_views(sc, a);
   if (upload(ctx, a.tri_offset, v->mesh_tri_offset, (size_t) v->num_meshes + 1, &sc.mesh_tri_offset)) return 1;
   if (upload(ctx, a.vertices, (const float4*) v->vertices, (size_t) total_tris * 3, &sc.vertices)) return 1;
+  ctx->tri_material.resize(total_tris);
+  for (uint32_t t = 0; t < total_tris; t++) ctx->tri_material[t] = (uint16_t) (v->tri_tex[4 * (size_t) t + 3] & 0xFFFFu);  // (scene_traits)
   return upload(ctx, a.tri_tex, (const uint4*) v->tri_tex, (size_t) total_tris, &sc.tri_tex);
 }
 
@@ -307,6 +310,7 @@ static int update_instance_arrays(LumContext* ctx, const LumDeviceSceneView* v) 
 
 static int update_materials(LumContext* ctx, const LumDeviceSceneView* v) {
   ctx->arrays.materials = {};
+  ctx->material_words.assign(v->materials, v->materials + 16 * (size_t) v->num_materials);  // (scene_traits)
   return upload(ctx, ctx->arrays.materials.materials, (const uint4*) v->materials, (size_t) v->num_materials * 2, &ctx->scene.materials);
 }
 
@@ -339,7 +343,10 @@ static int update_light_tree(LumContext* ctx, const LumDeviceSceneView* v) {
   SceneArrays::Lights& a = ctx->arrays.lights;
   a = {}; point_views(sc, a);
   sc.light_num_nodes = 0;
+  ctx->light_handles.clear(); ctx->light_tree_flat = true;  // (scene_traits)
   if (!v->light_tree_root || !v->num_lights) return 0;
+  ctx->light_handles.assign(v->light_tri_handles, v->light_tri_handles + 2 * (size_t) v->num_lights);
+  ctx->light_tree_flat = v->num_light_tree_nodes == 0;  // the builder makes a node for every root child that is not a light (scene.cpp: the collapse's jobs)
   const uint32_t sections = v->light_tree_root[10];
   if (upload(ctx, a.tree_root, (const uint4*) v->light_tree_root, (size_t) 1 + 3 * sections, &sc.light_tree_root)) return 1;
   if (upload_light_root_children(ctx, v, sections)) return 1;
@@ -936,6 +943,30 @@ static int refit_lights(LumContext* ctx, const LumDeviceSceneView* v) {
   return 0;
 }
 
+// DeviceScene::traits (dev_scene.h SceneTrait; plain_scene, wavefront_table.h) from the host's words of the materials, the light tree and the lights' triangles:
+// nothing is read back. Called by every update after its parts have run, so an edited material, new lights or new meshes under the lights are seen; a light
+// refit keeps the tree's topology and the lights' triangles, a flat tree stays flat across it.
+static uint32_t scene_traits(const LumContext* ctx) {
+  uint32_t traits = kTraitNoTranslucent | kTraitPlainEmitters;
+  const size_t num_materials = ctx->material_words.size() / 16;
+  for (size_t m = 0; m < num_materials; m++)
+    if ((ctx->material_words[16 * m] & exact::kDMatSubstrateMask) != 0) traits &= ~(uint32_t) kTraitNoTranslucent;
+  if (ctx->light_tree_flat) traits |= kTraitFlatLightTree;
+  for (size_t l = 0; l < ctx->light_handles.size() / 2; l++) {  // the material k_light_table finds for the light: handle -> mesh -> scene triangle -> material id
+    const uint32_t inst = ctx->light_handles[2 * l], tri = ctx->light_handles[2 * l + 1];
+    bool plain = false;
+    if (inst < ctx->instance_mesh_ids.size() && (size_t) ctx->instance_mesh_ids[inst] + 1 < ctx->mesh_tri_offset.size()) {
+      const size_t scene_tri = (size_t) ctx->mesh_tri_offset[ctx->instance_mesh_ids[inst]] + tri;
+      if (scene_tri < ctx->tri_material.size() && ctx->tri_material[scene_tri] < num_materials) {
+        const uint16_t* w = &ctx->material_words[16 * (size_t) ctx->tri_material[scene_tri]];
+        plain = w[12] == exact::kTextureNone && w[13] == exact::kTextureNone;  // albedo and emission texture (dev_bsdf.h load_material: b.z)
+      }
+    }
+    if (!plain) traits &= ~(uint32_t) kTraitPlainEmitters;
+  }
+  return traits;
+}
+
 // The counts, then what two kernels derive from the arrays above: k_tri_opacity (needs the materials and blas_tris), k_light_table (needs the counts).
 // triangles_rewritten: a moved-vertices update built a mesh again, its traversal triangles are new.
 // keep_light_count: the caller said LUMC_DIRTY_LIGHT_POSITIONS without new lights - the view's light arrays and their count are not read, the device's stay.
@@ -1248,6 +1279,7 @@ static int scene_update(LumContext* ctx, const LumDeviceSceneView* v, unsigned d
   lights_since(t_lights);
   if (plan.constants && update_constants(ctx, v, plan)) return 1;
   if (update_bridge_table(ctx, v)) return 1;
+  sc.traits = scene_traits(ctx);
   // the moon's texture ids follow the texture pool (the host layer appends the two moon textures behind the scene's own): an added texture moves them
   sc.sky_moon_albedo_tex = v->sky_moon_albedo_tex; sc.sky_moon_normal_tex = v->sky_moon_normal_tex;
   ctx->has_scene = true;

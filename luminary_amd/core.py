@@ -915,6 +915,20 @@ class Core:
                    randoms.ctypes.data_as(C.c_void_p), ids.ctypes.data_as(C.c_void_p), hits.ctypes.data_as(C.c_void_p))
         return ids, hits
 
+    LIGHT_PROBE_VERTEX_WORDS, LIGHT_PROBE_WORDS = 20, 154
+    LIGHT_PROBE_FORMS = {"general": 0, "plain": 1, "unstaged": 2}
+
+    def light_sample_probe_host(self, vertices, first_sample, samples, form="general"):
+        """sample_light on caller-made vertices (lumc_light_sample_probe_host): vertices [V, 20] uint32 words, out [V, samples, 154] uint32 words - the sample, the
+        root pass and the eight lanes' stages as include/lum_core.h lays them out."""
+        vertices = np.ascontiguousarray(vertices, dtype=np.uint32)
+        nv = vertices.shape[0]
+        assert vertices.shape == (nv, self.LIGHT_PROBE_VERTEX_WORDS)
+        out = np.zeros((nv, samples, self.LIGHT_PROBE_WORDS), dtype=np.uint32)
+        self._call("lumc_light_sample_probe_host", C.c_uint32(nv), vertices.ctypes.data_as(C.c_void_p), C.c_uint32(first_sample), C.c_uint32(samples),
+                   C.c_int(self.LIGHT_PROBE_FORMS[form]), out.ctypes.data_as(C.c_void_p))
+        return out
+
     def trace_closest_device(self, n, origins_ptr, dirs_ptr, ignore_ptr, out_ptr, stream=0):
         self._call("lumc_trace_closest", C.c_uint32(n), C.c_void_p(origins_ptr), C.c_void_p(dirs_ptr), C.c_void_p(ignore_ptr), C.c_void_p(out_ptr),
                    C.c_void_p(stream))

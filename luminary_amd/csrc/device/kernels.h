@@ -1597,6 +1597,109 @@ __global__ __launch_bounds__(kBlock) void k_light_query_probe(DeviceScene sc, ui
   out_ids[i] = id; out_num_hits[i] = num_hits;
 }
 
+// ---- standalone light sampling for tests/test_light_sample_truth.py: one thread per (vertex, sample id), sample_light exactly as k_shade calls it ----
+// The vertex is caller-made, as the oracle's probe_context makes it: 20 words {position, normal, V, albedo, opacity, roughness, ior ratio, material flags, self instance,
+// self triangle, pixel x, pixel y}; state 0, the sampler the unseeded one at depth 0. Every workgroup stages the light lines and handles the way kernel_shade_body.h
+// does (`stage` 0: nothing staged, every light is read from memory; kPlain stages them all). Per thread kLightProbeWords words:
+//   [0..9)   the LightSample of the one real call: light id, ray, colour, dist, root_sum
+//   [9..18)  tree_prepass: the eight cont words, root_sum
+//   [18 + 17 lane ..) per lane: TreePick light id, TreePick weight, status, ray[3], solid angle, dist, emitted colour[3], BSDF weight[3], the direction probability
+//            handed to mis_base, the MIS weight, the reservoir target
+// The per-lane words are a second walk over the loop of light_candidates with the functions that loop calls on the arguments it passes them: shipped code is untouched.
+// Words a lane does not reach keep what the caller put there.
+constexpr uint32_t kLightProbeVertexWords = 20, kLightProbeLaneWords = 17, kLightProbeHeadWords = 18;
+constexpr uint32_t kLightProbeWords = kLightProbeHeadWords + kLightTreeOutputs * kLightProbeLaneWords;
+enum LightProbeStatus : uint32_t { kLightProbeNoPick = 0, kLightProbeSelf = 1, kLightProbeRefused = 2, kLightProbeMissed = 3, kLightProbeEvaluated = 4 };
+template <bool kPlain>
+__global__ __launch_bounds__(kBlock) void k_light_sample_probe(DeviceScene sc, uint32_t n, uint32_t samples, uint32_t first_sample, uint32_t stage, const uint32_t* vertices,
+                                                               uint32_t* out) {
+  StagedLights staged_lights{nullptr, nullptr, 0u};
+#if LUM_LDS_LIGHTS
+  {
+    __shared__ LdsF4 lds_light_table[4u * LUM_LDS_LIGHTS];
+    __shared__ unsigned long long lds_light_handles[LUM_LDS_LIGHTS];
+    const uint32_t staged = (kPlain || stage) ? min(sc.num_lights, (uint32_t) LUM_LDS_LIGHTS) : 0u;
+    for (uint32_t k = threadIdx.x; k < 4u * staged; k += kBlock) { const float4 v = sc.light_tri_table[k]; const LdsF4 t = {v.x, v.y, v.z, v.w}; lds_light_table[k] = t; }
+    for (uint32_t k = threadIdx.x; k < staged; k += kBlock) { const uint2 h = sc.light_tri_handles[k]; lds_light_handles[k] = (unsigned long long) h.x | ((unsigned long long) h.y << 32); }
+    __syncthreads();
+    staged_lights.table = (const __attribute__((address_space(3))) LdsF4*) lds_light_table;
+    staged_lights.handles = (const __attribute__((address_space(3))) unsigned long long*) lds_light_handles;
+    staged_lights.count = staged;
+  }
+#endif
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t* vw = vertices + (size_t) (i / samples) * kLightProbeVertexWords;
+  uint32_t* o = out + (size_t) i * kLightProbeWords;
+  GeoContext g;
+  g.instance_id = vw[16]; g.tri_id = vw[17];
+  g.position = v3(bitsf(vw[0]), bitsf(vw[1]), bitsf(vw[2]));
+  g.normal = normalize(v3(bitsf(vw[3]), bitsf(vw[4]), bitsf(vw[5])));
+  g.V = normalize(v3(bitsf(vw[6]), bitsf(vw[7]), bitsf(vw[8])));
+  g.face_normal_packed = normal_pack(g.normal);
+  g.state = 0;
+  g.params.flags = vw[15];
+  g.params.set(col(bitsf(vw[9]), bitsf(vw[10]), bitsf(vw[11])), bitsf(vw[12]), bitsf(vw[13]), splat(0.0f), bitsf(vw[14]));
+  const SamplerT<false> smp{sc.bluenoise_2d, vw[18], vw[19], first_sample + i % samples, 0u};
+  ShadeClock clock;
+  clock.start();
+  const LightSample ls = sample_light<kPlain>(sc, g, smp, clock, staged_lights);
+  o[0] = ls.light_id; o[1] = fbits(ls.ray.x); o[2] = fbits(ls.ray.y); o[3] = fbits(ls.ray.z);
+  o[4] = fbits(ls.color.r); o[5] = fbits(ls.color.g); o[6] = fbits(ls.color.b); o[7] = fbits(ls.dist); o[8] = fbits(ls.root_sum);
+  // the second walk
+  const TreeWork work = tree_prepass(sc, g, smp);
+  const Energy energy = energy_terms(sc, g.params, world_ndotv(g));
+#pragma unroll
+  for (uint32_t l = 0; l < kLightTreeOutputs; l++) o[9 + l] = work.cont[l];
+  o[17] = fbits(work.root_sum);
+#if LUM_FAST
+  const V3 view_local = normalize(qapply(rotation_to_z(g.normal), g.V));
+#endif
+#pragma nounroll
+  for (uint32_t lane = 0; lane < kLightTreeOutputs; lane++) {
+    uint32_t* w = o + kLightProbeHeadWords + lane * kLightProbeLaneWords;
+    const TreePick pick = tree_postpass<kPlain>(sc, g, smp, lane, work);
+    w[0] = pick.light_id; w[1] = fbits(pick.weight); w[2] = kLightProbeNoPick;
+    if (pick.light_id == kLightIdInvalid) continue;
+#if LUM_LDS_LIGHTS
+    uint2 handle;
+    const TableLight entry = load_tri_light_table<kPlain>(sc, staged_lights, pick.light_id, handle);
+#else
+    const uint2 handle = sc.light_tri_handles[pick.light_id];
+    const TableLight entry = load_tri_light_table(sc, pick.light_id);
+#endif
+    const TriLight& tl = entry.tri;
+    w[2] = kLightProbeSelf;
+    if (handle.x == g.instance_id && handle.y == g.tri_id) continue;
+    V3 ray; float sa;
+    const F2 pair = smp.next2(kRndLightGeoRay + lane);
+    w[2] = kLightProbeRefused;
+    if (!sample_tri_solid_angle(g.position, tl, pair, ray, sa)) continue;
+    w[3] = fbits(ray.x); w[4] = fbits(ray.y); w[5] = fbits(ray.z); w[6] = fbits(sa);
+    F2 uv;
+    const float dist = intersect_triangle(tl.vertex, tl.edge1, tl.edge2, g.position, ray, uv);
+    w[2] = kLightProbeMissed;
+    if (dist == kFltMax) continue;
+    w[7] = fbits(dist);
+    Col lc = (!kPlain && entry.textured) ? tri_light_color(sc, tl, uv) : entry.color;
+    w[8] = fbits(lc.r); w[9] = fbits(lc.g); w[10] = fbits(lc.b);
+#if LUM_FAST
+    const RayTerms terms = analyze_direction(g.params, g.normal, g.V, ray);
+    const Col bw = eval_with_face_normal(energy, g.params, terms, kHintGeneral, ray, normal_unpack(g.face_normal_packed), 1.0f);
+    const float dir_prob = light_direction_probability_terms(g.params, view_local, terms);
+    const float mis = 1.0f - mis_base(dir_prob, sa, importance(lc) * entry.area, dist * dist, work.root_sum);
+#else
+    bool is_refraction;
+    const Col bw = eval_bsdf(energy, g, ray, kHintGeneral, is_refraction, 1.0f);
+    const float dir_prob = light_direction_probability(g, ray);
+    const float mis = mis_for_light_sample(g, ray, entry.area, lc, dist, sa, work.root_sum);
+#endif
+    lc = (lc * bw) * mis;
+    w[2] = kLightProbeEvaluated;
+    w[11] = fbits(bw.r); w[12] = fbits(bw.g); w[13] = fbits(bw.b); w[14] = fbits(dir_prob); w[15] = fbits(mis); w[16] = fbits(importance(lc));
+  }
+}
+
 // The Sobol / Owen pairs of one pass (dev_sampler.h LUM_SOBOL_TABLE): one thread per (dimension, sample id).
 __global__ __launch_bounds__(256) void k_sobol_table(uint2* __restrict__ table, uint32_t first_sample, uint32_t count, uint32_t stride, uint32_t dims) {
   const uint32_t t = blockIdx.x * 256u + threadIdx.x;

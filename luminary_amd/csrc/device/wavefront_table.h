@@ -97,8 +97,19 @@ struct WavefrontKernels {
   void (*light_query_probe)(hipStream_t s, const DeviceScene& sc, uint32_t n, const float* origins, const float* dirs, const uint32_t* self, const float* randoms, uint32_t* out_ids,
                             uint32_t* out_num_hits);
 };
+// Probes that only the tests launch and whose signatures follow a test's needs live in a table of their own, one per flavour like the kernels': the render's launcher
+// table above keeps its shape when a probe comes or goes.
+struct WavefrontProbes {
+  // sample_light on n_vertices caller-made vertices x `samples` sample ids, one per thread (k_light_sample_probe, kernels.h: 20 words in per vertex, 154 out per thread);
+  // form: 0 the general form, 1 the plain form (the caller has asked plain_scene), 2 the general form with no light staged in LDS
+  void (*light_sample_probe)(hipStream_t s, const DeviceScene& sc, uint32_t n_vertices, uint32_t samples, uint32_t first_sample, uint32_t form, const uint32_t* vertices,
+                             uint32_t* out);
+};
+constexpr uint32_t kLightSampleProbeVertexWords = 20, kLightSampleProbeWords = 154;  // that probe's words per vertex (in) and per thread (out)
 
 const WavefrontKernels* wavefront_kernels_exact();  // csrc/device/wavefront_exact.hip
 const WavefrontKernels* wavefront_kernels_fast();   // csrc/device/wavefront_fast.hip
+const WavefrontProbes* wavefront_probes_exact();
+const WavefrontProbes* wavefront_probes_fast();
 
 }  // namespace lum

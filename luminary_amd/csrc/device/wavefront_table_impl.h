@@ -161,6 +161,13 @@ static void light_query_probe(hipStream_t s, const DeviceScene& sc, uint32_t n, 
                               uint32_t* out_num_hits) {
   hipLaunchKernelGGL(k_light_query_probe, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, sc, n, origins, dirs, self, randoms, out_ids, out_num_hits);
 }
+static void light_sample_probe(hipStream_t s, const DeviceScene& sc, uint32_t n_vertices, uint32_t samples, uint32_t first_sample, uint32_t form, const uint32_t* vertices,
+                               uint32_t* out) {
+  static_assert(kLightProbeVertexWords == kLightSampleProbeVertexWords && kLightProbeWords == kLightSampleProbeWords, "the host layer sizes the probe's buffers by these");
+  const uint32_t n = n_vertices * samples;
+  if (form == 1u) hipLaunchKernelGGL(k_light_sample_probe<true>, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, sc, n, samples, first_sample, 1u, vertices, out);
+  else hipLaunchKernelGGL(k_light_sample_probe<false>, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, sc, n, samples, first_sample, form == 2u ? 0u : 1u, vertices, out);
+}
 
 // Filled by member name: neighbouring members share a function-pointer type (resolve / resolve_listed, particle_shade / ocean_shade, sky_inscattering / clouds),
 // so a positional list with two of them swapped would compile. tests/test_build_units.py checks that no member stays null.
@@ -178,6 +185,12 @@ static constexpr WavefrontKernels make_table() {
   return t;
 }
 static constexpr WavefrontKernels kTable = make_table();
+static constexpr WavefrontProbes make_probes() {
+  WavefrontProbes p{};
+  p.light_sample_probe = light_sample_probe;
+  return p;
+}
+static constexpr WavefrontProbes kProbes = make_probes();
 
 }  // namespace table
 LUM_NS_END
@@ -217,7 +230,9 @@ extern "C" int lumc_debug_phase_stats(uint64_t out[16], int reset) {
 namespace lum {
 #if LUM_FAST
 const WavefrontKernels* wavefront_kernels_fast() { return &fast::table::kTable; }
+const WavefrontProbes* wavefront_probes_fast() { return &fast::table::kProbes; }
 #else
 const WavefrontKernels* wavefront_kernels_exact() { return &exact::table::kTable; }
+const WavefrontProbes* wavefront_probes_exact() { return &exact::table::kProbes; }
 #endif
 }  // namespace lum

@@ -1238,6 +1238,36 @@ int lumc_light_query_host(LumContext* ctx, uint32_t n, const float* origins, con
   return 0;
 }
 
+// sample_light (dev_light.h) on caller-made vertices in the active flavour: num_vertices records of LUMC_LIGHT_PROBE_VERTEX_WORDS words, each sampled with the sample ids
+// first_sample .. first_sample + samples - 1; out: LUMC_LIGHT_PROBE_WORDS words per (vertex, sample id), zero where a lane did not get that far (k_light_sample_probe,
+// kernels.h). form: LUMC_LIGHT_PROBE_GENERAL, _PLAIN (refused unless the scene is one k_shade's plain form shades and no vertex is translucent), _UNSTAGED.
+int lumc_light_sample_probe_host(LumContext* ctx, uint32_t num_vertices, const uint32_t* vertices, uint32_t first_sample, uint32_t samples, int form, uint32_t* out) {
+  static_assert(LUMC_LIGHT_PROBE_VERTEX_WORDS == kLightSampleProbeVertexWords && LUMC_LIGHT_PROBE_WORDS == kLightSampleProbeWords, "lum_core.h and wavefront_table.h");
+  if (!ctx || !ctx->has_scene) { if (ctx) ctx->error = "lumc_light_sample_probe_host: no scene"; return 1; }
+  if (num_vertices == 0 || samples == 0) return 0;
+  if (!vertices || !out) { ctx->error = "lumc_light_sample_probe_host: null argument"; return 1; }
+  if (form < LUMC_LIGHT_PROBE_GENERAL || form > LUMC_LIGHT_PROBE_UNSTAGED) { ctx->error = "lumc_light_sample_probe_host: unknown form"; return 1; }
+  const DeviceScene& sc = ctx->scene;
+  if (!sc.num_lights || !sc.light_tree_root || !sc.light_root_children || !sc.light_tri_table || !sc.light_tri_handles) { ctx->error = "lumc_light_sample_probe_host: the scene has no lights"; return 1; }
+  const size_t n = (size_t) num_vertices * samples;
+  if (n > (1u << 24)) { ctx->error = "lumc_light_sample_probe_host: more than 2^24 threads"; return 1; }
+  if (form == LUMC_LIGHT_PROBE_PLAIN) {
+    if (!plain_scene(sc)) { ctx->error = "lumc_light_sample_probe_host: the plain form does not shade this scene"; return 1; }
+    for (uint32_t v = 0; v < num_vertices; v++)
+      if (vertices[(size_t) v * kLightSampleProbeVertexWords + 15] & 1u) { ctx->error = "lumc_light_sample_probe_host: a translucent vertex in the plain form"; return 1; }
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  DeviceBuffer<uint32_t> d_v, d_out;
+  HIP_TRY(ctx, d_v.assign(vertices, (size_t) num_vertices * kLightSampleProbeVertexWords));
+  HIP_TRY(ctx, d_out.resize(n * kLightSampleProbeWords));
+  HIP_TRY(ctx, hipMemset(d_out.get(), 0, sizeof(uint32_t) * n * kLightSampleProbeWords));
+  (ctx->wf == wavefront_kernels_exact() ? wavefront_probes_exact() : wavefront_probes_fast())->light_sample_probe(nullptr, sc, num_vertices, samples, first_sample, (uint32_t) form, d_v.get(), d_out.get());
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipDeviceSynchronize());
+  HIP_TRY(ctx, hipMemcpy(out, d_out.get(), sizeof(uint32_t) * n * kLightSampleProbeWords, hipMemcpyDeviceToHost));
+  return 0;
+}
+
 int lumc_pixel_query(LumContext* ctx, uint32_t x, uint32_t y, uint32_t sample_id, uint32_t out[6]) {
   if (!ctx || !ctx->has_scene || !out) { if (ctx) ctx->error = "lumc_pixel_query: no scene"; return 1; }
   if (x >= ctx->scene.width || y >= ctx->scene.height) { ctx->error = "lumc_pixel_query: pixel outside the frame"; return 1; }

@@ -1165,6 +1165,15 @@ void oracle_sobol(uint32_t offset, uint32_t dimension, uint32_t out[2]) { const 
 void oracle_random_2d(const uint32_t* bn, uint32_t target, uint32_t px, uint32_t py, uint32_t sample, uint32_t depth, uint32_t out[2]) {
   const uint2_t r = rng_2d_u32(bn, target, px, py, sample, depth); out[0] = r.x; out[1] = r.y;
 }
+/* oracle_random_2d as the paths read it (rnd2: two numbers in [0, 1)) for `samples` sample ids and a list of targets: out[sample][target][2] */
+void oracle_random_2d_table(const uint32_t* bn, uint32_t px, uint32_t py, uint32_t first, uint32_t samples, uint32_t depth, uint32_t num_targets, const uint32_t* targets,
+                            float* out) {
+  for (uint32_t i = 0; i < samples; i++)
+    for (uint32_t t = 0; t < num_targets; t++) {
+      const uint2_t q = rng_2d_u32(bn, targets[t], px, py, first + i, depth);
+      out[2 * ((size_t) i * num_targets + t)] = u32_to_unit(q.x); out[2 * ((size_t) i * num_targets + t) + 1] = u32_to_unit(q.y);
+    }
+}
 void oracle_record_roundtrip(const float in[3], uint32_t packed[2], float out[3]) {
   const uint2_t p = record_pack(c3(in[0], in[1], in[2])); packed[0] = p.x; packed[1] = p.y;
   const RGBF r = record_unpack(p); out[0] = r.r; out[1] = r.g; out[2] = r.b;
@@ -1403,6 +1412,69 @@ void oracle_probe_light_sample(const OracleScene* s, const OracleProbeMaterial* 
     colors[3 * i] = ls.light_color.r; colors[3 * i + 1] = ls.light_color.g; colors[3 * i + 2] = ls.light_color.b;
     dists[i] = ls.dist;
   }
+}
+/* light_sample with its stages, for vertices that name themselves: the words of the device's probe (include/lum_core.h lumc_light_sample_probe_host), in its layout.
+ * A vertex is 20 words {position, normal, V, albedo, opacity, roughness, ior ratio, flags, self instance, self triangle, pixel x, pixel y}; per (vertex, sample id)
+ * 154 words come back: light_sample's own result, the root pass, and for each lane what the loop of light_sample (o_light.h) computed on the way, restated here
+ * statement for statement. Words of stages a lane did not reach stay 0. */
+static uint32_t f_bits(float f) { uint32_t u; memcpy(&u, &f, 4); return u; }
+void oracle_probe_light_sample_stages(const OracleScene* s, uint32_t num_vertices, const uint32_t* vertices, uint32_t first, uint32_t samples, uint32_t* out) {
+  const OLuts luts = scene_luts(s);
+  memset(out, 0, sizeof(uint32_t) * (size_t) ORACLE_LIGHT_PROBE_WORDS * num_vertices * samples);
+  for (uint32_t v = 0; v < num_vertices; v++) {
+    const uint32_t* vw = vertices + (size_t) ORACLE_LIGHT_PROBE_VERTEX_WORDS * v;
+    float f[15]; memcpy(f, vw, sizeof(f));
+    const OracleProbeMaterial m = {{f[9], f[10], f[11]}, f[12], f[13], f[14], vw[15]};
+    GeoCtx gc = probe_context(&m, f, f + 3, f + 6);
+    gc.instance_id = vw[16]; gc.tri_id = vw[17];
+    const GeoCtx* g = &gc;
+    for (uint32_t i = 0; i < samples; i++) {
+      uint32_t* o = out + (size_t) ORACLE_LIGHT_PROBE_WORDS * ((size_t) v * samples + i);
+      const Sampler sampler = {s->bluenoise_2d, vw[18], vw[19], first + i, 0};
+      const Sampler* smp = &sampler;
+      const LightSample ls = light_sample(s, g, smp);
+      o[0] = ls.light_id; o[1] = f_bits(ls.ray.x); o[2] = f_bits(ls.ray.y); o[3] = f_bits(ls.ray.z);
+      o[4] = f_bits(ls.light_color.r); o[5] = f_bits(ls.light_color.g); o[6] = f_bits(ls.light_color.b); o[7] = f_bits(ls.dist); o[8] = f_bits(ls.root_sum);
+      const LTQuery query = lt_query_geometry(g);
+      const LTWork work = light_tree_prepass(s, &query, smp);
+      for (uint32_t l = 0; l < LIGHT_TREE_NUM_OUTPUTS; l++) o[9 + l] = work.data[l].is_light | (work.data[l].child_index << 1) | (work.data[l].probability << 9);
+      o[17] = f_bits(work.root_sum);
+      for (uint32_t lane = 0; lane < LIGHT_TREE_NUM_OUTPUTS; lane++) {
+        uint32_t* w = o + 18 + 17 * lane;
+        const LTResult r = light_tree_postpass(s, &query, smp, lane, &work);
+        w[0] = r.light_id; w[1] = f_bits(r.weight); w[2] = 0;
+        if (r.light_id == LIGHT_ID_INVALID) continue;
+        const uint32_t inst = s->light_tri_handles[2 * r.light_id], tri = s->light_tri_handles[2 * r.light_id + 1];
+        w[2] = 1;
+        if (inst == g->instance_id && tri == g->tri_id) continue;
+        uint32_t uvp[3];
+        TriLight tl = light_triangle_init(s, inst, tri, uvp);
+        const float2_t rr = rnd2(smp, RT_LIGHT_GEO_RAY + lane);
+        vec3 ray = v3(0.0f, 0.0f, 0.0f); float dist, sa = 0.0f;
+        w[2] = 2;
+        if (!light_triangle_sample_solid_angle(g->position, tl.vertex, tl.edge1, tl.edge2, rr, tl.bidirectional, &ray, &sa)) continue;
+        w[3] = f_bits(ray.x); w[4] = f_bits(ray.y); w[5] = f_bits(ray.z); w[6] = f_bits(sa);
+        w[2] = 3;
+        if (!light_triangle_finalize_dist(&tl, uvp, g->position, ray, &dist)) continue;
+        w[7] = f_bits(dist);
+        RGBF lc = light_get_color(s, &tl);
+        w[8] = f_bits(lc.r); w[9] = f_bits(lc.g); w[10] = f_bits(lc.b);
+        bool is_refr;
+        const RGBF bw = bsdf_evaluate(&luts, g, ray, HINT_GENERAL, &is_refr, 1.0f);
+        const float dir_prob = light_bsdf_get_probability(g, ray);
+        const float mis = mis_weight_dl(g, ray, &tl, lc, dist, sa, work.root_sum);
+        lc = c_scale(c_mul(lc, bw), mis);
+        w[2] = 4;
+        w[11] = f_bits(bw.r); w[12] = f_bits(bw.g); w[13] = f_bits(bw.b); w[14] = f_bits(dir_prob); w[15] = f_bits(mis); w[16] = f_bits(c_importance(lc));
+      }
+    }
+  }
+}
+/* light_bsdf_get_probability on its own: the probability with which the BSDF-driven light direction of the vertex would have been L */
+void oracle_probe_light_direction_probability(const OracleProbeMaterial* m, const float normal[3], const float V[3], uint32_t count, const float* L, float* out) {
+  const float origin[3] = {0.0f, 0.0f, 0.0f};
+  const GeoCtx g = probe_context(m, origin, normal, V);
+  for (uint32_t i = 0; i < count; i++) out[i] = light_bsdf_get_probability(&g, v3(L[3 * i], L[3 * i + 1], L[3 * i + 2]));
 }
 
 /* the light-only BVH query of a BSDF-sampled direction (optix_anyhit.cuh:145-205 restated order-independently, o_trace.h trace_light_bvh): for every

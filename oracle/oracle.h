@@ -154,6 +154,8 @@ int oracle_generate_lut(const uint32_t* bluenoise_2d, int table, uint32_t first,
 uint32_t oracle_squares32(uint32_t key, uint32_t counter);
 void oracle_sobol(uint32_t offset, uint32_t dimension, uint32_t out[2]);
 void oracle_random_2d(const uint32_t* bn, uint32_t target, uint32_t px, uint32_t py, uint32_t sample, uint32_t depth, uint32_t out[2]);
+void oracle_random_2d_table(const uint32_t* bn, uint32_t px, uint32_t py, uint32_t first, uint32_t samples, uint32_t depth, uint32_t num_targets, const uint32_t* targets,
+                            float* out);
 void oracle_record_roundtrip(const float in[3], uint32_t packed[2], float out[3]);
 void oracle_ray_roundtrip(const float in[3], uint32_t packed[2], float out[3]);
 uint32_t oracle_normal_pack(const float in[3]);
@@ -227,6 +229,12 @@ void oracle_probe_light_tree(const OracleScene* s, const OracleProbeMaterial* m,
                              uint32_t first, uint32_t count, uint32_t* light_ids, float* weights, float* root_sums);
 void oracle_probe_light_sample(const OracleScene* s, const OracleProbeMaterial* m, const float position[3], const float normal[3], const float V[3], uint32_t px, uint32_t py,
                                uint32_t first, uint32_t count, uint32_t* light_ids, float* rays, float* colors, float* dists);
+/* light_sample and its stages on vertices that name themselves, in the words of the device's probe (tests/test_light_sample_truth.py): 20 words per vertex, 154 per
+ * (vertex, sample id) */
+#define ORACLE_LIGHT_PROBE_VERTEX_WORDS 20 /* = LUMC_LIGHT_PROBE_VERTEX_WORDS, include/lum_core.h (tests/test_light_sample_truth.py compares the headers) */
+#define ORACLE_LIGHT_PROBE_WORDS 154       /* = LUMC_LIGHT_PROBE_WORDS: 18 + 8 lanes x 17 */
+void oracle_probe_light_sample_stages(const OracleScene* s, uint32_t num_vertices, const uint32_t* vertices, uint32_t first, uint32_t samples, uint32_t* out);
+void oracle_probe_light_direction_probability(const OracleProbeMaterial* m, const float normal[3], const float V[3], uint32_t count, const float* L, float* out);
 
 /* fog (o_volume.h) */
 void oracle_probe_volume_path(const float cam_pos[3], float dist, float height, uint32_t count, const float* origins, const float* dirs, const float* limits, float* out);

@@ -83,3 +83,11 @@ def test_the_launcher_table_assigns_every_member_by_name():
     assert all(assigned[p] == p for p in pointers), {p: assigned[p] for p in pointers if assigned[p] != p}
     for p in pointers:  # each name is a launcher defined in the same header
         assert re.search(r"^static (?:int|void) %s\(" % p, impl, re.M), p
+    # the tests' probes have a table of their own, filled the same way
+    probes = decl[decl.index("struct WavefrontProbes {"):decl.index("};", decl.index("struct WavefrontProbes {"))]
+    probe_pointers = re.findall(r"\(\*(\w+)\)\(", "\n".join(line.split("//")[0] for line in probes.splitlines()))
+    body = impl[impl.index("make_probes() {"):impl.index("return p;")]
+    assigned = dict(re.findall(r"\bp\.(\w+) = ([^;]+);", body))
+    assert probe_pointers == ["light_sample_probe"] and assigned == {p: p for p in probe_pointers}
+    for p in probe_pointers:
+        assert re.search(r"^static (?:int|void) %s\(" % p, impl, re.M), p

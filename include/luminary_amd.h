@@ -485,6 +485,39 @@ typedef struct LuminaryMeshMorphStats {
   uint64_t host_materialisations;       /* the counter of LuminaryMeshSkinStats: times the host posed or blended a mesh on the CPU because something read it */
 } LuminaryMeshMorphStats;
 LUMINARY_API LuminaryResult luminary_ext_get_mesh_morph_stats(LuminaryHost* host, LuminaryMeshMorphStats* out);
+/* Shutter: motion blur from two keys of the scene (csrc/host/mesh_shutter.h). The shutter interval is cut into slices; the scene is brought
+ * to each slice's time on the devices and a share of the sample ids is rendered into the same accumulators.
+ *   luminary_ext_shutter_open    the scene as it stands is the open key: every enabled device is brought up to date, as a render does before its first pass, the
+ *                                camera's pos and rotation and every instance's position, rotation and scale are remembered, and from now on the host records
+ *                                which meshes move. (Without a usable device the call still succeeds; luminary_ext_render_shutter then reports the device.)
+ *   edits that define the close key, each behaving exactly as without a shutter: luminary_ext_set_mesh_positions, luminary_ext_set_mesh_pose,
+ *                                luminary_ext_set_mesh_weights, luminary_ext_set_instance_transforms, a camera change of pos or rotation. A moved emitter needs
+ *                                luminary_ext_set_light_refit(host, 1, ...) before the shutter opens.
+ *   luminary_ext_render_shutter  slices 1 ... 1024, samples_per_slice >= 1. The moved meshes' open keys are taken on the devices, the ordinary update brings the
+ *                                devices to the close key, the close keys are taken; then for slice k of S, t_k = (float) (2k + 1) / (float) (2S): the meshes
+ *                                are written at t_k by a HIP kernel (a + t * (b - a) per coordinate in binary32), the camera's pos and rotation and the moved
+ *                                instances' position, rotation and scale are set to a + t_k * (b - a) per component in binary32 - Euler angles, blended as they
+ *                                are - and encoded into the device scene as the host's own encoders do, one lumc_scene_update applies them, and sample ids
+ *                                [first + k n, first + (k + 1) n) are rendered without clearing, first the samples accumulated so far. Then time 1 and the
+ *                                close key are applied once more: host and devices agree on the close key, bit for bit what an ordinary update leaves.
+ *                                accumulated samples += S n; the outputs are produced as luminary_ext_render_samples produces them. Calling it again without an
+ *                                edit in between keeps the keys and accumulates further; any edit afterwards drops the keys and restarts the integration.
+ *   luminary_ext_shutter_cancel  forgets the open key (and the devices' keys); nothing else changes.
+ * LUMINARY_ERROR_INVALID_API_ARGUMENT, with the reason in the log: luminary_ext_render_shutter without an open key, slices outside 1 ... 1024,
+ * samples_per_slice == 0, settings.enable_adaptive_sampling - the host stays as it was -; any pending change other than the edits above (materials, textures, the
+ * mesh or instance list, settings, sky, ocean, cloud, fog, particles, another camera field, the lens, the enabled devices, a pending rebuild of the light tree) -
+ * the shutter is cancelled and nothing is rendered. Any other render call between open and luminary_ext_render_shutter cancels the shutter. A slice whose light
+ * refit asks for a rebuild fails the call with LUMINARY_ERROR_API_EXCEPTION; the next render rebuilds the tree at the close key and the accumulation restarts.
+ * Limits: the undersampling preview does not run inside a shutter render, and the denoiser's guides are those of the close key. */
+typedef struct LuminaryShutterStats {
+  uint64_t renders, slices;             /* shutter renders / slices rendered since the host was created */
+  uint32_t last_moved_meshes, last_moved_instances, last_camera_moved, last_slices; /* of the last shutter render */
+  double seconds_update, seconds_render; /* ... host wall clock spent in scene updates (keys included) / in rendering the slices */
+} LuminaryShutterStats;
+LUMINARY_API LuminaryResult luminary_ext_shutter_open(LuminaryHost* host);
+LUMINARY_API LuminaryResult luminary_ext_shutter_cancel(LuminaryHost* host);
+LUMINARY_API LuminaryResult luminary_ext_render_shutter(LuminaryHost* host, uint32_t slices, uint32_t samples_per_slice, uint32_t samples_per_pass);
+LUMINARY_API LuminaryResult luminary_ext_get_shutter_stats(LuminaryHost* host, LuminaryShutterStats* out);
 /* Converts the current scene to the device format (device_structs.c conversions + light tree build). The view and everything it points
  * to stay valid until the next call or host destruction. Needs no GPU. */
 /* Whether replacing `old` by `input` restarts the integration (camera.c:80-147, settings.c:45-72) or only changes the outputs.

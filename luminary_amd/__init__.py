@@ -202,6 +202,12 @@ class MeshMorphStats(C.Structure):
                 ("seconds", C.c_double), ("seconds_upload", C.c_double), ("seconds_morph", C.c_double), ("host_materialisations", C.c_uint64)]
 
 
+class ShutterStats(C.Structure):
+    """LuminaryShutterStats"""
+    _fields_ = [("renders", C.c_uint64), ("slices", C.c_uint64), ("last_moved_meshes", C.c_uint32), ("last_moved_instances", C.c_uint32), ("last_camera_moved", C.c_uint32),
+                ("last_slices", C.c_uint32), ("seconds_update", C.c_double), ("seconds_render", C.c_double)]
+
+
 class Instance(C.Structure):
     _fields_ = [("id", C.c_uint32), ("mesh_id", C.c_uint32), ("position", Vec3), ("rotation", Vec3), ("scale", Vec3)]
 
@@ -694,6 +700,25 @@ class Host:
             px = np.ascontiguousarray(pixels, dtype=np.uint32)
             _call("luminary_ext_render_samples", self._h, px.ctypes.data_as(C.c_void_p), C.c_uint32(px.size), C.c_uint32(first_sample),
                   C.c_uint32(num_samples), C.c_uint32(samples_per_pass))
+
+    def shutter_open(self):
+        """luminary_ext_shutter_open: the scene as it stands is the open key of a motion-blurred render; moved vertices, poses, weights, instance transforms and
+        camera pos / rotation set from now on define the close key."""
+        _call("luminary_ext_shutter_open", self._h)
+
+    def shutter_cancel(self):
+        """luminary_ext_shutter_cancel"""
+        _call("luminary_ext_shutter_cancel", self._h)
+
+    def render_shutter(self, slices, samples_per_slice, samples_per_pass=1):
+        """luminary_ext_render_shutter: `slices` temporal samples between the keys, `samples_per_slice` sample ids each, into the same accumulators."""
+        _call("luminary_ext_render_shutter", self._h, C.c_uint32(slices), C.c_uint32(samples_per_slice), C.c_uint32(samples_per_pass))
+
+    def shutter_stats(self):
+        """luminary_ext_get_shutter_stats, as a dict."""
+        s = ShutterStats()
+        _call("luminary_ext_get_shutter_stats", self._h, C.byref(s))
+        return {name: getattr(s, name) for name, _ in s._fields_}
 
     def render(self, num_samples):
         """The reference's render loop for `num_samples` more sample allocations (adaptive sampling per the renderer settings)."""

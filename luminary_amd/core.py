@@ -10,6 +10,7 @@ DIRTY_MESH_POSITIONS = 128  # moved vertices: refit (not part of DIRTY_ALL, whic
 DIRTY_INSTANCE_TRANSFORMS = 256  # moved instances: the top level is rebuilt on the device, the mesh trees stay (not part of DIRTY_ALL)
 DIRTY_MESH_SKIN = 512  # bound meshes posed (Core.mesh_skin_pose): their vertices are written on the device, then they are refitted (not part of DIRTY_ALL)
 DIRTY_LIGHT_POSITIONS = 1024  # emissive triangles moved: the bound light tree is refitted on the device (Core.light_refit_bind; not part of DIRTY_ALL)
+DIRTY_MESH_SHUTTER = 2048  # meshes that hold both shutter keys got a time (Core.shutter_time): a HIP kernel writes them between their keys (not part of DIRTY_ALL)
 BVH_BUILDERS = {"sah": 0, "lbvh": 1, "ploc": 2, "sah_gpu": 3}
 CNT_TRACE, CNT_SHADOW, CNT_LIGHT_BVH, CNT_VERTICES, CNT_NODES, CNT_TRIS, CNT_NODES_SHADOW, CNT_TRIS_SHADOW, CNT_NODES_LIGHT, CNT_TRIS_LIGHT, CNT_NODES_LDS, CNT_NODES_LDS_SHADOW, CNT_AMBIENT_DEFERRED, CNT_AMBIENT_FALLBACK = range(14)
 CNT_COUNT = 16  # LUMC_CNT_COUNT
@@ -143,6 +144,28 @@ def skin_host(rest_positions, rest_normals, bone_ids, weights, bones):
     if fn(p.ctypes.data, n.ctypes.data, i.ctypes.data, w.ctypes.data, len(p), b.ctypes.data, len(b), op.ctypes.data, on.ctypes.data, pk.ctypes.data) != 0:
         raise CoreError("lumc_skin_host refused its arguments (bone count 1 ... 1024, ids below it)")
     return op, on, pk
+
+
+class ShutterStats(C.Structure):
+    """LumShutterStats"""
+    _fields_ = [("slices", C.c_uint64), ("last_meshes", C.c_uint32), ("last_launches", C.c_uint32), ("last_bytes_uploaded", C.c_uint64), ("seconds", C.c_double)]
+
+
+def shutter_host(open_records, close_records, t):
+    """lumc_shutter_host, no device needed: the host twin of the shutter kernel over 16-byte vertex records [n, 4] (float32, or their uint32 words). Returns (records
+    [n, 4] uint32, flags); raises ValueError where the twin refuses (a t outside [0, 1] or not finite)."""
+    fn = _lib().lumc_shutter_host
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p]
+    a = np.ascontiguousarray(open_records).view(np.uint32).reshape(-1, 4)
+    b = np.ascontiguousarray(close_records).view(np.uint32).reshape(-1, 4)
+    if a.shape != b.shape:
+        raise ValueError("shutter_host: the keys differ in size")
+    out = np.zeros_like(a)
+    flags = C.c_uint32(0)
+    if fn(a.ctypes.data, b.ctypes.data, len(a), float(t), out.ctypes.data, C.addressof(flags)) != 0:
+        raise ValueError("lumc_shutter_host refused its arguments")
+    return out, flags.value
 
 
 class MeshMorphStats(C.Structure):
@@ -794,6 +817,22 @@ class Core:
     def mesh_morph_stats(self):
         out = MeshMorphStats()
         self._call("lumc_mesh_morph_stats", C.byref(out))
+        return out
+
+    def mesh_shutter_key(self, mesh, which):
+        """lumc_mesh_shutter_key: the mesh's vertices as the device holds them become its open (0) or close (1) key."""
+        self._call("lumc_mesh_shutter_key", C.c_uint32(mesh), C.c_uint32(which))
+
+    def mesh_shutter_drop(self, mesh):
+        self._call("lumc_mesh_shutter_drop", C.c_uint32(mesh))
+
+    def shutter_time(self, t):
+        """lumc_shutter_time: t in [0, 1] for every mesh that holds both keys; pending until the next update with DIRTY_MESH_SHUTTER."""
+        self._call("lumc_shutter_time", C.c_float(t))
+
+    def shutter_stats(self):
+        out = ShutterStats()
+        self._call("lumc_shutter_stats", C.byref(out))
         return out
 
     def set_light_refit(self, max_cost_growth=0.0):

@@ -64,8 +64,29 @@ struct HostSkin {
   bool weighted() const { return has_morph() && morph_weights_serial != 0; }
 };
 
+// The shutter (luminary_ext_shutter_open ... luminary_ext_render_shutter): what the host remembers of the open key, what was edited since,
+// and - once a shutter render has run - what the slices blend between, for as long as nothing is edited.
+struct HostShutter {
+  struct Pose { LuminaryVec3 position, rotation, scale; };
+  bool open = false;            // an open key is held and edits are recorded
+  bool synced = false;          // ... and every enabled device held the open scene when it was taken
+  bool keyed = false;           // the contexts hold both keys of `meshes`: a shutter render ran and nothing was edited since
+  uint32_t edits = 0;           // LUMC_DIRTY_* bits of the edits since the shutter opened (a move's own LUMC_DIRTY_LIGHTS left out: emitter_needs_refit stands for it)
+  bool in_move = false;         // the next invalidate belongs to a move of vertices or instances
+  bool emitter_needs_refit = false;  // an emitter moved while luminary_ext_set_light_refit is off: the light tree would have to be built per slice
+  std::string other;            // the first change since then that the shutter cannot blend (empty: none)
+  LuminaryVec3 camera_pos{}, camera_rotation{};  // the open key's
+  std::vector<Pose> instances;  // the open key's, by instance
+  std::vector<uint32_t> meshes;           // meshes that moved between the keys
+  std::vector<uint32_t> moved_instances;  // instances whose position, rotation or scale differs between the keys
+  bool camera_moved = false;
+  uint32_t slice_dirty = 0;     // what a slice's lumc_scene_update takes
+  LuminaryShutterStats stats{};
+};
+
 struct LuminaryHost {
   lum::HostScene scene;
+  HostShutter shutter;
   std::map<uint32_t, HostSkin> skins;  // by mesh
   uint64_t skin_serial = 0;            // counts binds and poses
   uint64_t core_skin_seen = 0;         // the counter when the main context last took bindings and poses over
@@ -145,7 +166,44 @@ std::vector<uint32_t> embedded_bluenoise() {
 // the devices.
 uint32_t moved_emitter_bit(const LuminaryHost* h) { return h->light_refit ? LUMC_DIRTY_LIGHT_POSITIONS : LUMC_DIRTY_LIGHTS; }
 
+// The contexts' keys go: any edit after a shutter render restarts the integration as it always did.
+void shutter_drop_keys(LuminaryHost* h) {
+  if (!h->shutter.keyed) return;
+  for (uint32_t m : h->shutter.meshes) {
+    if (h->core) (void) lumc_mesh_shutter_drop(h->core, m);
+    for (uint32_t i = 0; i < h->devices.size(); i++)
+      if (i != h->main_slot && h->devices[i].core) (void) lumc_mesh_shutter_drop(h->devices[i].core, m);
+  }
+  h->shutter.keyed = false;
+}
+void shutter_cancel(LuminaryHost* h) {
+  shutter_drop_keys(h);
+  h->shutter.open = false; h->shutter.synced = false; h->shutter.edits = 0; h->shutter.other.clear(); h->shutter.in_move = false; h->shutter.emitter_needs_refit = false;
+  h->shutter.meshes.clear(); h->shutter.moved_instances.clear(); h->shutter.camera_moved = false; h->shutter.slice_dirty = 0;
+}
+void shutter_note_other(LuminaryHost* h, const char* what) {
+  if (h->shutter.open && h->shutter.other.empty()) h->shutter.other = what;
+}
+void shutter_note_mesh(LuminaryHost* h, uint32_t mesh) {
+  std::vector<uint32_t>& m = h->shutter.meshes;
+  if (h->shutter.open && std::find(m.begin(), m.end(), mesh) == m.end()) m.push_back(mesh);
+}
+
+// A move of vertices or instances is about to invalidate: it marks the lights' part whether or not an emitter moved (moved_emitter_bit). Without the light refit a
+// moved emitter cannot be blended; a move of something that does not emit leaves the lights as they are in every slice.
+void shutter_note_move(LuminaryHost* h, bool emits) {
+  if (!h->shutter.open) return;
+  h->shutter.in_move = true;
+  if (emits && !h->light_refit) h->shutter.emitter_needs_refit = true;
+}
+
 void invalidate(LuminaryHost* h, uint32_t dirty = LUMC_DIRTY_ALL) {
+  shutter_drop_keys(h);
+  if (h->shutter.open) {
+    h->shutter.edits |= h->shutter.in_move ? dirty & ~(uint32_t) LUMC_DIRTY_LIGHTS : dirty;
+    h->shutter.in_move = false;
+    if (dirty == 0) shutter_note_other(h, "the device partition");
+  }
   h->scene_dirty |= dirty; h->core_dirty |= dirty;
   // An adaptive accumulation ends with the edit. The context leaves adaptive mode in lumc_set_pixels only, and an unchanged frame size would keep the
   // pixel set (ensure_core): without this, a uniform render after `enable_adaptive_sampling = false` ran on a context whose result image still
@@ -206,6 +264,13 @@ bool settings_change_restarts(const LuminaryRendererSettings& in, const Luminary
 template <typename T> bool change_restarts(const T&, const T&) { return true; }  // sky, ocean, cloud, fog, particles: every field feeds the integration
 inline bool change_restarts(const LuminaryCamera& in, const LuminaryCamera& old) { return camera_change_restarts(in, old); }
 inline bool change_restarts(const LuminaryRendererSettings& in, const LuminaryRendererSettings& old) { return settings_change_restarts(in, old); }
+// An entity changed while the shutter is open: only the camera's pos and rotation are blended between the keys.
+template <typename T> void shutter_note_entity(LuminaryHost* h, const char* name, const T&, const T&) { shutter_note_other(h, name); }
+inline void shutter_note_entity(LuminaryHost* h, const char*, const LuminaryCamera& in, const LuminaryCamera& old) {
+  LuminaryCamera c = in;
+  c.pos = old.pos; c.rotation = old.rotation;
+  if (camera_change_restarts(c, old)) shutter_note_other(h, "a camera field other than pos and rotation");
+}
 
 // ---- skinned and morphed meshes: the lazy host mesh ----
 // HostMesh::positions / normals of a posed or morphed mesh from the host twin of the devices' kernel (in place: the pointers luminary_ext_get_mesh handed out
@@ -837,6 +902,7 @@ LuminaryResult luminary_host_request_sky_hdri_build(LuminaryHost* host) {
   CHECK_NULL(host);
   ApiLock lock(host);
   host->hdri_origin_pending = true;
+  shutter_note_other(host, "the sky panorama");
   invalidate(host, LUMC_DIRTY_CONSTANTS);
   return LUMINARY_SUCCESS;
 }
@@ -854,6 +920,7 @@ LuminaryResult luminary_host_request_sky_hdri_build(LuminaryHost* host) {
     ApiLock lock(host);                                                      \
     if (std::memcmp(&host->scene.FIELD, in, sizeof(TYPE)) != 0) {                                       \
       const bool restarts = change_restarts(*in, host->scene.FIELD);                                    \
+      if (restarts) shutter_note_entity(host, "the " #NAME, *in, host->scene.FIELD);                     \
       host->scene.FIELD = *in;                                                                          \
       if (std::is_same<TYPE, LuminarySky>::value) host->hdri_origin_pending = true; /* sky.c:45: every sky change dirties the panorama */ \
       /* these entities reach the kernels as constants (and tables derived from them): no mesh, instance or material array is touched */ \
@@ -958,6 +1025,7 @@ static void face_normals(const float* positions, uint32_t triangle_count, float*
   }
 }
 static void mark_moved(LuminaryHost* host, uint32_t mesh_id) {
+  shutter_note_mesh(host, mesh_id);
   if (std::find(host->moved_meshes.begin(), host->moved_meshes.end(), mesh_id) == host->moved_meshes.end()) host->moved_meshes.push_back(mesh_id);
 }
 LuminaryResult luminary_ext_set_mesh_positions(LuminaryHost* host, uint32_t mesh_id, const float* positions, const float* normals, uint32_t triangle_count) {
@@ -972,17 +1040,20 @@ LuminaryResult luminary_ext_set_mesh_positions(LuminaryHost* host, uint32_t mesh
   std::memmove(m.positions.data(), positions, sizeof(float) * 9 * (size_t) triangle_count);
   if (!normals) face_normals(m.positions.data(), triangle_count, m.normals.data());
   mark_moved(host, mesh_id);
+  shutter_note_move(host, mesh_emits(host, mesh_id));
   invalidate(host, LUMC_DIRTY_MESH_POSITIONS | moved_emitter_bit(host));  // the vertices and the mesh's tree; the light tree follows moved emitters
   return LUMINARY_SUCCESS;
 }
 // A bound mesh got a new pose or new weights: the devices write its vertices, the host mesh follows when something reads it.
 static void deformed(LuminaryHost* host, uint32_t mesh_id, HostSkin& k) {
+  shutter_note_mesh(host, mesh_id);
   k.host_current = false; k.view_current = false;
   uint32_t dirty = LUMC_DIRTY_MESH_SKIN;
   if (mesh_emits(host, mesh_id)) {
     if (host->light_refit) dirty |= LUMC_DIRTY_LIGHT_POSITIONS;  // the devices refit the light tree from the vertices they write: the host mesh stays lazy
     else { materialise(host, mesh_id); dirty |= LUMC_DIRTY_LIGHTS; }  // the light tree is built from the host mesh
   }
+  shutter_note_move(host, (dirty & (LUMC_DIRTY_LIGHTS | LUMC_DIRTY_LIGHT_POSITIONS)) != 0);
   invalidate(host, dirty);
 }
 // One of a mesh's two bindings went, or was replaced, while the other stays, and the one that went had shaped the mesh: the mesh is what the other one makes of the
@@ -1191,10 +1262,13 @@ LuminaryResult luminary_ext_set_instance_transforms(LuminaryHost* host, const Lu
     for (float x : f) if (!std::isfinite(x)) return LUMINARY_ERROR_INVALID_API_ARGUMENT;
   }
   if (count == 0) return LUMINARY_SUCCESS;
+  bool emitter = false;
   for (uint32_t k = 0; k < count; k++) {
     lum::HostInstance& i = host->scene.instances[instances[k].id];
     i.translation = instances[k].position; i.rotation = instances[k].rotation; i.scale = instances[k].scale;
+    emitter = emitter || (host->shutter.open && mesh_emits(host, i.mesh_id));
   }
+  shutter_note_move(host, emitter);
   invalidate(host, LUMC_DIRTY_INSTANCE_TRANSFORMS | moved_emitter_bit(host));  // the transforms and the top-level tree; the light tree follows moved emitters
   return LUMINARY_SUCCESS;
 }
@@ -1556,7 +1630,211 @@ LuminaryResult luminary_ext_render_samples(LuminaryHost* host, const uint32_t* p
                                            uint32_t samples_per_pass) {
   CHECK_NULL(host);
   ApiLock lock(host);
+  shutter_cancel(host);  // any other render call ends the shutter
   return render_samples_locked(host, pixels, num_pixels, first_sample, num_samples, samples_per_pass);
+}
+
+// ---- shutter (include/luminary_amd.h luminary_ext_shutter_open) ----
+namespace {
+float shutter_blend(float a, float b, float t) {  // one rounding per operation (this unit is compiled without contraction)
+  const float d = b - a;
+  const float s = t * d;
+  return a + s;
+}
+LuminaryVec3 shutter_blend3(const LuminaryVec3& a, const LuminaryVec3& b, float t) {
+  LuminaryVec3 r = b;
+  r.x = shutter_blend(a.x, b.x, t); r.y = shutter_blend(a.y, b.y, t); r.z = shutter_blend(a.z, b.z, t);
+  return r;
+}
+bool same_vec(const LuminaryVec3& a, const LuminaryVec3& b) { return std::memcmp(&a.x, &b.x, 4) == 0 && std::memcmp(&a.y, &b.y, 4) == 0 && std::memcmp(&a.z, &b.z, 4) == 0; }
+
+LuminaryResult shutter_refuse(LuminaryHost* h, const std::string& why, bool cancel) {
+  h->log.push_back("luminary_ext_render_shutter: " + why);
+  std::fprintf(stderr, "[luminary_amd] luminary_ext_render_shutter: %s\n", why.c_str());
+  if (cancel) shutter_cancel(h);
+  return LUMINARY_ERROR_INVALID_API_ARGUMENT;
+}
+
+// The scene at time t between the keys on every context: the host's camera and moved instances blended (`close`: the close key's own values, verbatim) and
+// encoded into the device scene, the moved meshes written by the devices. *rebuild: a device's light refit asked for a rebuild.
+int shutter_apply_time(LuminaryHost* h, const std::vector<LumContext*>& cores, float t, bool close, const LuminaryCamera& close_camera,
+                       const std::vector<HostShutter::Pose>& close_instances, bool* rebuild) {
+  HostShutter& sh = h->shutter;
+  if (sh.camera_moved) {
+    h->scene.camera.pos = close ? close_camera.pos : shutter_blend3(sh.camera_pos, close_camera.pos, t);
+    h->scene.camera.rotation = close ? close_camera.rotation : shutter_blend3(sh.camera_rotation, close_camera.rotation, t);
+  }
+  for (uint32_t i : sh.moved_instances) {
+    lum::HostInstance& inst = h->scene.instances[i];
+    const HostShutter::Pose &a = sh.instances[i], &b = close_instances[i];
+    inst.translation = close ? b.position : shutter_blend3(a.position, b.position, t);
+    inst.rotation = close ? b.rotation : shutter_blend3(a.rotation, b.rotation, t);
+    inst.scale = close ? b.scale : shutter_blend3(a.scale, b.scale, t);
+  }
+  const uint32_t encode = sh.slice_dirty & (LUMC_DIRTY_CONSTANTS | LUMC_DIRTY_INSTANCE_TRANSFORMS);
+  if (encode) {
+    const std::string err = lum::update_device_scene(h->scene, h->device_scene.bluenoise, encode, &h->device_scene);
+    if (!err.empty()) { h->log.push_back(err); std::fprintf(stderr, "[luminary_amd] %s\n", err.c_str()); return 1; }
+  }
+  if (sh.slice_dirty == LUMC_DIRTY_MESH_SHUTTER && sh.meshes.empty()) return 0;  // nothing moved: the devices hold this scene
+  const bool refits_lights = h->light_refit && (sh.slice_dirty & LUMC_DIRTY_LIGHT_POSITIONS);
+  if (refits_lights && !sh.moved_instances.empty()) lum::refresh_light_refit_transforms(h->scene, &h->device_scene.light_refit_plan);
+  for (LumContext* core : cores) {
+    const auto& lt = h->device_scene.light_refit_plan.transforms;
+    if (refits_lights && !sh.moved_instances.empty() && !lt.empty() && lumc_light_refit_transforms(core, lt.data(), (uint32_t) lt.size())) return 1;
+    if (lumc_shutter_time(core, t) || lumc_scene_update(core, &h->device_scene.view, sh.slice_dirty)) { std::fprintf(stderr, "[luminary_amd] %s\n", lumc_last_error(core)); return 1; }
+    if (set_camera(h, core)) return 1;
+    if (refits_lights && lumc_light_refit_needs_rebuild(core)) { *rebuild = true; return 1; }
+  }
+  return 0;
+}
+
+LuminaryResult render_shutter_locked(LuminaryHost* h, uint32_t slices, uint32_t samples_per_slice, uint32_t samples_per_pass) {
+  HostShutter& sh = h->shutter;
+  if (slices == 0 || slices > 1024) return shutter_refuse(h, "slices is 1 ... 1024", false);
+  if (samples_per_slice == 0) return shutter_refuse(h, "samples_per_slice is at least 1", false);
+  if (h->scene.settings.enable_adaptive_sampling) return shutter_refuse(h, "adaptive sampling does not run under a shutter (settings.enable_adaptive_sampling)", false);
+  if (!sh.open && !sh.keyed) return shutter_refuse(h, "no open key (luminary_ext_shutter_open)", false);
+  const auto clock = [] { return std::chrono::steady_clock::now(); };
+  const auto since = [&](std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double>(clock() - t0).count(); };
+  double seconds_update = 0.0, seconds_render = 0.0;
+  std::vector<LumContext*> cores;
+  const auto t_keys = clock();
+  if (sh.open) {
+    if (!sh.other.empty()) return shutter_refuse(h, sh.other + " changed since the shutter opened: only moved vertices, poses, weights, instance transforms and the camera's pos and rotation are blended", true);
+    const uint32_t blended = LUMC_DIRTY_CONSTANTS | LUMC_DIRTY_MESH_POSITIONS | LUMC_DIRTY_MESH_SKIN | LUMC_DIRTY_INSTANCE_TRANSFORMS | LUMC_DIRTY_LIGHT_POSITIONS;
+    const uint32_t bad = sh.edits & ~(blended | LUMC_DIRTY_LIGHTS);
+    if (bad) {
+      std::string what;
+      const std::pair<uint32_t, const char*> names[] = {{LUMC_DIRTY_MATERIALS, "materials"}, {LUMC_DIRTY_INSTANCES, "the instance list"}, {LUMC_DIRTY_MESHES, "the mesh list"},
+                                                        {LUMC_DIRTY_TEXTURES, "textures"}, {LUMC_DIRTY_PARTICLES, "particles"}};
+      for (const auto& n : names) if (bad & n.first) what += (what.empty() ? "" : ", ") + std::string(n.second);
+      return shutter_refuse(h, what + " changed since the shutter opened: only moved vertices, poses, weights, instance transforms and the camera's pos and rotation are blended", true);
+    }
+    if (sh.emitter_needs_refit)
+      return shutter_refuse(h, "an emitter moved and the light tree would have to be built again per slice (LUMC_DIRTY_LIGHTS): luminary_ext_set_light_refit(host, 1, ...) before the shutter opens lets the devices refit it", true);
+    if (sh.edits & LUMC_DIRTY_LIGHTS)
+      return shutter_refuse(h, "a rebuild of the light tree is pending (LUMC_DIRTY_LIGHTS; luminary_ext_set_light_refit was switched, or a binding changed) since the shutter opened", true);
+    if (!sh.synced || h->scene.instances.size() != sh.instances.size()) {
+      shutter_cancel(h);
+      std::fprintf(stderr, "[luminary_amd] luminary_ext_render_shutter: the devices did not take the open key\n");
+      return LUMINARY_ERROR_CUDA;
+    }
+    sh.camera_moved = !same_vec(h->scene.camera.pos, sh.camera_pos) || !same_vec(h->scene.camera.rotation, sh.camera_rotation);
+    sh.moved_instances.clear();
+    for (uint32_t i = 0; i < h->scene.instances.size(); i++) {
+      const lum::HostInstance& inst = h->scene.instances[i];
+      if (!same_vec(inst.translation, sh.instances[i].position) || !same_vec(inst.rotation, sh.instances[i].rotation) || !same_vec(inst.scale, sh.instances[i].scale)) sh.moved_instances.push_back(i);
+    }
+    sh.slice_dirty = LUMC_DIRTY_MESH_SHUTTER | (sh.camera_moved ? LUMC_DIRTY_CONSTANTS : 0u) | (sh.moved_instances.empty() ? 0u : LUMC_DIRTY_INSTANCE_TRANSFORMS) |
+                     (sh.edits & LUMC_DIRTY_LIGHT_POSITIONS);
+    std::sort(sh.meshes.begin(), sh.meshes.end());
+    auto fail = [&](LumContext* c) { std::fprintf(stderr, "[luminary_amd] %s\n", lumc_last_error(c)); shutter_cancel(h); return LUMINARY_ERROR_CUDA; };
+    // 1. the open keys, from the vertices the devices hold
+    for (LuminaryHost::DeviceSlot* slot : enabled_slots(h)) { LumContext* c = slot == &h->devices[h->main_slot] ? h->core : slot->core; if (c) cores.push_back(c); }
+    if (cores.empty() && h->core) cores.push_back(h->core);
+    for (LumContext* c : cores)
+      for (uint32_t m : sh.meshes) if (lumc_mesh_shutter_key(c, m, 0)) return fail(c);
+    // 2. the ordinary update: the devices hold the close key (the accumulation starts over exactly when something was edited)
+    LuminaryResult r = render_samples_locked(h, nullptr, 0, h->accumulated_samples, 0, 1);
+    if (!r) r = ensure_partition_cores(h, &cores);
+    if (r) { shutter_cancel(h); return r; }
+    // 3. the close keys
+    for (LumContext* c : cores)
+      for (uint32_t m : sh.meshes) if (lumc_mesh_shutter_key(c, m, 1)) return fail(c);
+    sh.open = false; sh.keyed = true; sh.edits = 0;
+  }
+  else {
+    LuminaryResult r = render_samples_locked(h, nullptr, 0, h->accumulated_samples, 0, 1);
+    if (!r) r = ensure_partition_cores(h, &cores);
+    if (r) return r;
+  }
+  seconds_update += since(t_keys);
+  // 4. the slices
+  const LuminaryCamera close_camera = h->scene.camera;
+  std::vector<HostShutter::Pose> close_instances(h->scene.instances.size());
+  for (size_t i = 0; i < close_instances.size(); i++) close_instances[i] = {h->scene.instances[i].translation, h->scene.instances[i].rotation, h->scene.instances[i].scale};
+  const uint32_t first = h->accumulated_samples;
+  h->handoff_preview = false;
+  bool rebuild = false, failed = false;
+  LumContext* failed_core = nullptr;
+  for (uint32_t k = 0; k < slices && !failed; k++) {
+    const float t = (float) (2 * k + 1) / (float) (2 * slices);
+    const auto t_update = clock();
+    failed = shutter_apply_time(h, cores, t, false, close_camera, close_instances, &rebuild) != 0;
+    seconds_update += since(t_update);
+    if (failed) break;
+    const auto t_render = clock();
+    // every device gets its kernels enqueued before the first one is waited for: the GPUs run side by side
+    for (LumContext* c : cores)
+      if (!failed && lumc_render(c, first + k * samples_per_slice, samples_per_slice, samples_per_pass, nullptr, nullptr, nullptr)) { failed = true; failed_core = c; }
+    for (LumContext* c : cores)
+      if (!failed && lumc_synchronize(c)) { failed = true; failed_core = c; }
+    const double dt = since(t_render);
+    seconds_render += dt; h->render_seconds += dt; h->last_sample_ms = 1e3 * dt / samples_per_slice;
+  }
+  // 5. time 1 and the close view once more: host and devices agree on the close key
+  const auto t_close = clock();
+  bool rebuild_close = false;
+  if (!failed) failed = shutter_apply_time(h, cores, 1.0f, true, close_camera, close_instances, &rebuild_close) != 0;
+  seconds_update += since(t_close);
+  if (failed) {  // the host's scene is the close key again; every device takes it whole, and the accumulation starts over
+    if (failed_core) std::fprintf(stderr, "[luminary_amd] %s\n", lumc_last_error(failed_core));
+    h->scene.camera.pos = close_camera.pos; h->scene.camera.rotation = close_camera.rotation;
+    for (uint32_t i : sh.moved_instances) { h->scene.instances[i].translation = close_instances[i].position; h->scene.instances[i].rotation = close_instances[i].rotation; h->scene.instances[i].scale = close_instances[i].scale; }
+    shutter_cancel(h);
+    invalidate(h);
+    if (rebuild || rebuild_close) {
+      h->log.push_back("luminary_ext_render_shutter: a slice's light refit asked for a rebuild of the light tree (lumc_light_refit_needs_rebuild); the next render rebuilds it at the close key and the accumulation restarts");
+      std::fprintf(stderr, "[luminary_amd] %s\n", h->log.back().c_str());
+      return LUMINARY_ERROR_API_EXCEPTION;
+    }
+    return LUMINARY_ERROR_CUDA;
+  }
+  h->accumulated_samples += slices * samples_per_slice;
+  h->guides_valid = false;
+  LuminaryShutterStats& st = sh.stats;
+  st.renders++; st.slices += slices;
+  st.last_moved_meshes = (uint32_t) sh.meshes.size(); st.last_moved_instances = (uint32_t) sh.moved_instances.size(); st.last_camera_moved = sh.camera_moved ? 1u : 0u; st.last_slices = slices;
+  st.seconds_update = seconds_update; st.seconds_render = seconds_render;
+  return produce_outputs(h);
+}
+}  // namespace
+
+LuminaryResult luminary_ext_shutter_open(LuminaryHost* host) {
+  CHECK_NULL(host);
+  ApiLock lock(host);
+  shutter_cancel(host);
+  if (const LuminaryResult r = ensure_device_scene(host)) return r;
+  host->handoff_preview = false;
+  // what a render does before its first pass: every enabled slot takes the scene, the pixels are dealt
+  std::vector<LumContext*> cores;
+  const LuminaryResult r = host->scene.settings.enable_adaptive_sampling ? ensure_partition_cores(host, &cores)  // (luminary_ext_render_shutter refuses adaptive sampling)
+                                                                         : render_samples_locked(host, nullptr, 0, host->accumulated_samples, 0, 1);
+  if (r && host->core) return r;  // (no usable device at all: luminary_ext_render_shutter reports it)
+  HostShutter& sh = host->shutter;
+  sh.open = true; sh.synced = r == LUMINARY_SUCCESS;
+  sh.camera_pos = host->scene.camera.pos; sh.camera_rotation = host->scene.camera.rotation;
+  sh.instances.resize(host->scene.instances.size());
+  for (size_t i = 0; i < sh.instances.size(); i++) sh.instances[i] = {host->scene.instances[i].translation, host->scene.instances[i].rotation, host->scene.instances[i].scale};
+  return LUMINARY_SUCCESS;
+}
+LuminaryResult luminary_ext_shutter_cancel(LuminaryHost* host) {
+  CHECK_NULL(host);
+  ApiLock lock(host);
+  shutter_cancel(host);
+  return LUMINARY_SUCCESS;
+}
+LuminaryResult luminary_ext_render_shutter(LuminaryHost* host, uint32_t slices, uint32_t samples_per_slice, uint32_t samples_per_pass) {
+  CHECK_NULL(host);
+  ApiLock lock(host);
+  return render_shutter_locked(host, slices, samples_per_slice, samples_per_pass);
+}
+LuminaryResult luminary_ext_get_shutter_stats(LuminaryHost* host, LuminaryShutterStats* out) {
+  CHECK_NULL(host); CHECK_NULL(out);
+  ApiLock lock(host);
+  *out = host->shutter.stats;
+  return LUMINARY_SUCCESS;
 }
 // The frame's first sample as the undersampling preview: every iteration renders one pixel per block, then the outputs are produced
 // from the coarse image; the last iteration completes sample 0 of every pixel. Returns through *ran whether the preview applied.
@@ -1583,6 +1861,7 @@ namespace {
 // luminary_ext_render with the host's mutex held by the caller (the render worker and the API call share it): the first sample id of the
 // allocation is read under the same lock the passes run under.
 LuminaryResult render_locked(LuminaryHost* host, uint32_t num_samples, uint32_t samples_per_pass) {
+  shutter_cancel(host);  // any other render call ends the shutter
   const LuminaryRendererSettings settings = host->scene.settings;
   if (!settings.enable_adaptive_sampling) {
     uint32_t first = host->pixels_all && !host->adaptive_active ? host->accumulated_samples : 0;
@@ -1833,7 +2112,7 @@ LuminaryResult luminary_ext_set_camera_lens(LuminaryHost* host, const LuminaryCa
   ApiLock lock(host);
   const bool restarts = host->scene.camera.use_physical_camera && lens_change_restarts(*lens, host->scene.lens);
   host->scene.lens = *lens;
-  if (restarts) invalidate(host, LUMC_DIRTY_CONSTANTS);
+  if (restarts) { shutter_note_other(host, "the lens"); invalidate(host, LUMC_DIRTY_CONSTANTS); }
   return LUMINARY_SUCCESS;
 }
 LuminaryResult luminary_ext_get_camera_lens(LuminaryHost* host, LuminaryCameraLens* lens) {

@@ -22,6 +22,7 @@
 #include "instance_update.h"
 #include "light_refit.h"
 #include "mesh_deform.h"
+#include "mesh_shutter.h"
 #include "scene_arrays.h"
 #include "work_layout.h"
 
@@ -79,6 +80,10 @@ struct LumContext {
   DeviceBuffer<uint32_t> d_skin_flags;       // one word of kSkinFlag* / kMorphFlag* bits per launch of an update
   LumMeshSkinStats skin_stats{};
   LumMeshMorphStats morph_stats{};
+  // shutter keys (lumc_mesh_shutter_*, lumc_shutter_time; mesh_shutter.hip, scene_device.hip shutter_meshes)
+  std::map<uint32_t, MeshShutter> mesh_shutter;  // by mesh, a record while it holds a key; dropped with the meshes
+  DeviceBuffer<uint32_t> d_shutter_flags;    // one word of kShutterFlag* bits per launch of an update
+  LumShutterStats shutter_stats{};
   // the light tree's refit (lumc_light_refit_*; light_refit.hip, scene_device.hip refit_lights)
   LightRefit light_refit;                    // the bound plan; dropped by every update that takes new lights or new meshes
   Bvh4 light_bvh;                            // the light BVH as the last LUMC_DIRTY_LIGHTS update built it: what a bind makes the refit's topology from

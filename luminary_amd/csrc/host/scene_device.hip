@@ -132,6 +132,7 @@ void free_scene(LumContext* ctx) {
   ctx->tri_material.clear(); ctx->material_words.clear(); ctx->light_handles.clear(); ctx->light_tree_flat = true;
   ctx->resident_refit.drop_layout(); ctx->stale_meshes = 0;
   ctx->mesh_deform.clear(); ctx->d_skin_flags.reset();
+  ctx->mesh_shutter.clear(); ctx->d_shutter_flags.reset();
   ctx->light_refit.reset(); ctx->light_bvh = Bvh4{}; ctx->light_refit_needs_rebuild = false;
   ctx->has_scene = false;
 }
@@ -417,7 +418,9 @@ static int build_mesh_trees(LumContext* ctx, const LumDeviceSceneView* v, std::v
 // A kernel wrote the scene's vertices of mesh m: the view's vertices of it are never trusted.
 static bool written_on_device(const LumContext* ctx, uint32_t m) {
   const auto it = ctx->mesh_deform.find(m);
-  return it != ctx->mesh_deform.end() && it->second.written_on_device();
+  if (it != ctx->mesh_deform.end() && it->second.written_on_device()) return true;
+  const auto sh = ctx->mesh_shutter.find(m);
+  return sh != ctx->mesh_shutter.end() && sh->second.both();  // (a mesh that holds both keys is k_shutter_vertices')
 }
 
 // The skinning step of an update that touches vertices (find_moved_meshes runs it, once), after the vertex arrays are in place and before anything reads them: every
@@ -490,6 +493,46 @@ static int skin_meshes(LumContext* ctx, bool view_uploaded, std::vector<uint32_t
   return 0;
 }
 
+// ---- shutter keys (lum_core.h lumc_mesh_shutter_key, lumc_shutter_time; mesh_shutter.hip) ----
+// The shutter step of an update that touches vertices (find_moved_meshes runs it, once), after skin_meshes' launches and before anything reads the vertices: every
+// mesh with a pending time is written by k_shutter_vertices at that time between its keys (those meshes are moved: appended to *posed); after an upload of the
+// vertex arrays from the view (view_uploaded) every other mesh that holds both keys is written again at its last time - the same bits as before the upload, so its
+// tree still fits. One launch per mesh, nothing goes up. Then the launches' flag words come back: a coordinate that is not finite fails the update.
+static int shutter_meshes(LumContext* ctx, bool view_uploaded, bool counts_as_slice, std::vector<uint32_t>* posed) {
+  std::vector<std::pair<uint32_t, MeshShutter*>> jobs;  // ascending
+  for (auto& kv : ctx->mesh_shutter)
+    if (kv.second.both() && (kv.second.pending || view_uploaded)) jobs.emplace_back(kv.first, &kv.second);
+  if (jobs.empty()) return 0;
+  LumShutterStats& st = ctx->shutter_stats;
+  st.last_meshes = st.last_launches = 0; st.last_bytes_uploaded = 0; st.seconds = 0.0;
+  DeviceBuffer<float4>& vertices = ctx->arrays.mesh.vertices;
+  for (const auto& [m, s] : jobs) {  // every range a kernel will write, against the array that is there
+    if ((size_t) m + 1 >= ctx->mesh_tri_offset.size() || 3 * (size_t) ctx->mesh_tri_offset[m + 1] > vertices.count() ||
+        ctx->mesh_tri_offset[m + 1] - ctx->mesh_tri_offset[m] != s->triangles) {
+      ctx->error = "lumc_scene_update: mesh " + std::to_string(m) + " holds shutter keys of another triangle count than the scene on the device";
+      return 1;
+    }
+  }
+  const Stopwatch t_all;
+  if (ctx->d_shutter_flags.count() < jobs.size()) HIP_TRY(ctx, ctx->d_shutter_flags.resize(jobs.size()));
+  HIP_TRY(ctx, hipMemset(ctx->d_shutter_flags.get(), 0, sizeof(uint32_t) * jobs.size()));
+  for (size_t j = 0; j < jobs.size(); j++) {
+    const size_t first = 3 * (size_t) ctx->mesh_tri_offset[jobs[j].first];
+    HIP_TRY(ctx, mesh_shutter_launch(*jobs[j].second, vertices.get() + first, vertices.count() - first, ctx->d_shutter_flags.get() + j));
+    st.last_launches++;
+  }
+  std::vector<uint32_t> flags(jobs.size());
+  HIP_TRY(ctx, hipMemcpy(flags.data(), ctx->d_shutter_flags.get(), sizeof(uint32_t) * jobs.size(), hipMemcpyDeviceToHost));  // (waits for the launches)
+  st.seconds = t_all.seconds();
+  for (size_t j = 0; j < jobs.size(); j++)
+    if (flags[j] & kShutterFlagNotFinite) { ctx->error = "lumc_scene_update: mesh " + std::to_string(jobs[j].first) + ": the shutter keys give a position that is not finite"; return 1; }
+  bool any_pending = false;
+  for (const auto& [m, s] : jobs)
+    if (s->pending) { posed->push_back(m); s->pending = false; st.last_meshes++; any_pending = true; }
+  if (any_pending && counts_as_slice) st.slices++;
+  return 0;
+}
+
 // A posed mesh's vertices for a builder: its 3 * nt records as the device holds them, the layout of the view's `vertices`. Counted.
 static int download_posed_vertices(LumContext* ctx, uint32_t m, uint32_t t0, uint32_t nt, std::vector<float>& out) {
   out.resize(12 * (size_t) nt);
@@ -514,7 +557,7 @@ struct MovedMeshes {
 // The front end of both paths: the vertex arrays of the same meshes again - the traversal triangles stay on the device (update_mesh_arrays) -, the skinning step,
 // then the meshes whose vertices differ from those their held tree was fitted to: by a pose, or - among the others, where the view's vertices were taken over -
 // by their hashes. upload_view: the view's vertex arrays are taken over (false: poses alone - only posed meshes move, the view's vertices are not read).
-static int find_moved_meshes(LumContext* ctx, const LumDeviceSceneView* v, bool upload_view, MovedMeshes* out) {
+static int find_moved_meshes(LumContext* ctx, const LumDeviceSceneView* v, bool upload_view, bool shutter_slice, MovedMeshes* out) {
   LumMeshRefitStats& st = ctx->refit_stats;
   reset_update(st);
   if (ctx->mesh_bvh.size() != v->num_meshes || ctx->mesh_refit.size() != v->num_meshes || ctx->mesh_tri_offset.size() != (size_t) v->num_meshes + 1 ||
@@ -529,6 +572,9 @@ static int find_moved_meshes(LumContext* ctx, const LumDeviceSceneView* v, bool 
   st.seconds_upload = t_all.seconds();
   std::vector<uint32_t> posed;
   if (skin_meshes(ctx, upload_view, &posed)) return 1;
+  if (shutter_meshes(ctx, upload_view, shutter_slice, &posed)) return 1;
+  std::sort(posed.begin(), posed.end());
+  posed.erase(std::unique(posed.begin(), posed.end()), posed.end());
   for (uint32_t m = 0; m < v->num_meshes; m++) {
     const uint32_t t0 = v->mesh_tri_offset[m], nt = v->mesh_tri_offset[m + 1] - t0;
     if (nt == 0) continue;
@@ -1218,19 +1264,21 @@ static int scene_update(LumContext* ctx, const LumDeviceSceneView* v, unsigned d
   if (v->max_ray_depth > 63) { ctx->error = "max_ray_depth exceeds 63 (6-bit field, device_structs.h:9)"; return 1; }
   bool pose_pending = false;
   for (const auto& kv : ctx->mesh_deform) pose_pending = pose_pending || kv.second.pending();  // pending weights are a pending pose
-  UpdatePlan plan = plan_update(dirty, ctx->refit_in_place != 0, ctx->refit_mode, ctx->instance_update_mode, pose_pending, ctx->light_refit.bound);
+  bool shutter_pending = false;
+  for (const auto& kv : ctx->mesh_shutter) shutter_pending = shutter_pending || (kv.second.both() && kv.second.pending);
+  UpdatePlan plan = plan_update(dirty, ctx->refit_in_place != 0, ctx->refit_mode, ctx->instance_update_mode, pose_pending, ctx->light_refit.bound, shutter_pending);
   if (plan.moved_by_host) reset_update(ctx->instance_stats);
   auto host_path_since = [&](const Stopwatch& t) { if (plan.moved_by_host) ctx->instance_stats.seconds += t.seconds(); };
   auto lights_since = [&](const Stopwatch& t) { if (plan.time_lights) ctx->refit_stats.seconds_lights += t.seconds(); };
   ctx->has_scene = false;
   ctx->lights_refitted = false;
   if (plan.lights || plan.meshes) { ctx->light_refit.reset(); ctx->light_refit_needs_rebuild = false; }  // new lights: the plan's topology is not theirs, the caller binds again
-  if (plan.meshes) { ctx->arrays.mesh = {}; ctx->mesh_deform.clear(); }  // the traversal triangles too; new meshes: the bindings go, the caller binds again
+  if (plan.meshes) { ctx->arrays.mesh = {}; ctx->mesh_deform.clear(); ctx->mesh_shutter.clear(); }  // the traversal triangles too; new meshes: the bindings go, the caller binds again
   if (plan.meshes && update_mesh_arrays(ctx, v)) return 1;
   bool triangles_rewritten = false;
   if (plan.positions) {
     MovedMeshes moved;
-    if (find_moved_meshes(ctx, v, plan.upload_view, &moved)) return 1;
+    if (find_moved_meshes(ctx, v, plan.upload_view, (dirty & LUMC_DIRTY_MESH_SHUTTER) != 0, &moved)) return 1;
     if (plan.in_place) {
       bool fell_back = false;
       if (refit_in_place(ctx, v, moved, &fell_back)) return 1;
@@ -1299,7 +1347,7 @@ int lumc_scene_update(LumContext* ctx, const LumDeviceSceneView* v, unsigned int
   if (!ctx->has_scene || (dirty & LUMC_DIRTY_ALL) == LUMC_DIRTY_ALL) return lumc_scene_upload(ctx, v);
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   HIP_TRY(ctx, hipDeviceSynchronize());  // nothing renders from the arrays that are about to be freed
-  if (scene_update(ctx, v, dirty & (LUMC_DIRTY_ALL | LUMC_DIRTY_MESH_POSITIONS | LUMC_DIRTY_INSTANCE_TRANSFORMS | LUMC_DIRTY_MESH_SKIN | LUMC_DIRTY_LIGHT_POSITIONS))) { free_scene(ctx); return 1; }  // a failed partial update leaves no half-updated scene behind
+  if (scene_update(ctx, v, dirty & (LUMC_DIRTY_ALL | LUMC_DIRTY_MESH_POSITIONS | LUMC_DIRTY_INSTANCE_TRANSFORMS | LUMC_DIRTY_MESH_SKIN | LUMC_DIRTY_LIGHT_POSITIONS | LUMC_DIRTY_MESH_SHUTTER))) { free_scene(ctx); return 1; }  // a failed partial update leaves no half-updated scene behind
   return 0;
 }
 
@@ -1429,6 +1477,57 @@ int lumc_mesh_morph_weights(LumContext* ctx, uint32_t mesh, const float* weights
 int lumc_mesh_morph_stats(const LumContext* ctx, LumMeshMorphStats* out) {
   if (!ctx || !out) return 1;
   *out = ctx->morph_stats;
+  return 0;
+}
+
+int lumc_mesh_shutter_key(LumContext* ctx, uint32_t mesh, uint32_t which) {
+  if (!ctx) return 1;
+  if (which > 1) { ctx->error = "lumc_mesh_shutter_key: which is 0 (open) or 1 (close)"; return 1; }
+  if (!ctx->has_scene || (size_t) mesh + 1 >= ctx->mesh_tri_offset.size()) { ctx->error = "lumc_mesh_shutter_key: mesh " + std::to_string(mesh) + " is not in the scene on the device"; return 1; }
+  const uint32_t t0 = ctx->mesh_tri_offset[mesh], nt = ctx->mesh_tri_offset[mesh + 1] - t0;
+  const size_t corners = 3 * (size_t) nt;
+  if (3 * ((size_t) t0 + nt) > ctx->arrays.mesh.vertices.count()) { ctx->error = "lumc_mesh_shutter_key: the mesh lies outside the vertex array"; return 1; }
+  const auto held = ctx->mesh_shutter.find(mesh);
+  if (which == 1 && (held == ctx->mesh_shutter.end() || !held->second.has_open || held->second.triangles != nt)) {
+    ctx->error = "lumc_mesh_shutter_key: mesh " + std::to_string(mesh) + " has no open key";
+    return 1;
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipDeviceSynchronize());
+  MeshShutter fresh;
+  MeshShutter& s = which == 1 ? held->second : fresh;
+  DeviceBuffer<float4>& plane = which == 1 ? s.close : s.open;
+  if (plane.count() != corners) HIP_TRY(ctx, plane.resize(corners));
+  if (corners) HIP_TRY(ctx, hipMemcpy(plane.get(), ctx->arrays.mesh.vertices.get() + 3 * (size_t) t0, sizeof(float4) * corners, hipMemcpyDeviceToDevice));
+  HIP_TRY(ctx, hipDeviceSynchronize());
+  if (which == 0) {  // a new open key: the close key, if any, belonged to the old one
+    fresh.triangles = nt; fresh.has_open = true;
+    ctx->mesh_shutter[mesh] = std::move(fresh);
+  }
+  else { s.has_close = true; s.t = 1.0f; s.pending = false; }  // the scene's vertices ARE the close key: written at t = 1
+  return 0;
+}
+
+int lumc_mesh_shutter_drop(LumContext* ctx, uint32_t mesh) {
+  if (!ctx) return 1;
+  const auto it = ctx->mesh_shutter.find(mesh);
+  if (it == ctx->mesh_shutter.end()) { ctx->error = "lumc_mesh_shutter_drop: mesh " + std::to_string(mesh) + " holds no key"; return 1; }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  ctx->mesh_shutter.erase(it);
+  return 0;
+}
+
+int lumc_shutter_time(LumContext* ctx, float t) {
+  if (!ctx) return 1;
+  if (!std::isfinite(t) || !(t >= 0.0f) || !(t <= 1.0f)) { ctx->error = "lumc_shutter_time: t is a finite number in [0, 1]"; return 1; }
+  for (auto& kv : ctx->mesh_shutter)
+    if (kv.second.both()) { kv.second.t = t; kv.second.pending = true; }
+  return 0;
+}
+
+int lumc_shutter_stats(const LumContext* ctx, LumShutterStats* out) {
+  if (!ctx || !out) return 1;
+  *out = ctx->shutter_stats;
   return 0;
 }
 

@@ -8,7 +8,7 @@
 
 struct UpdatePlan {
   bool meshes = false;                // new meshes: vertex arrays, trees and traversal triangles are built as by an upload; every skin binding goes
-  bool positions = false;             // the moved-vertices path runs: the view's vertices moved, or a pose is pending (never with `meshes`, which covers both)
+  bool positions = false;             // the moved-vertices path runs: the view's vertices moved, or a pose or a shutter time is pending (never with `meshes`, which covers both)
   bool upload_view = false;           // ... and it takes the view's vertex arrays over (false: poses alone - the view's vertices are not read)
   bool in_place = false;              // ... and refits in the resident node array; the top level follows on the device
   bool instances = false;             // the host assembles the node array and the leaf records (update_instance_arrays, update_scene_tree)
@@ -32,12 +32,14 @@ struct UpdatePlan {
 
 // pose_pending: a bound mesh holds a pose that no update has applied yet (LUMC_DIRTY_MESH_SKIN moves something). light_refit_bound: the context holds a light
 // refit plan (lumc_light_refit_bind); without one LUMC_DIRTY_LIGHT_POSITIONS plans nothing (scene_update reports that the lights need a rebuild).
-inline UpdatePlan plan_update(unsigned dirty, bool refit_in_place, uint32_t refit_mode, uint32_t instance_update_mode, bool pose_pending, bool light_refit_bound = false) {
+// shutter_pending: a mesh that holds both shutter keys has a time no update has applied yet (lumc_shutter_time): LUMC_DIRTY_MESH_SHUTTER moves it as a pose does.
+inline UpdatePlan plan_update(unsigned dirty, bool refit_in_place, uint32_t refit_mode, uint32_t instance_update_mode, bool pose_pending, bool light_refit_bound = false,
+                              bool shutter_pending = false) {
   auto has = [dirty](unsigned bits) { return (dirty & bits) != 0; };
   UpdatePlan p;
   p.meshes = has(LUMC_DIRTY_MESHES);  // a full rebuild of the meshes covers moved vertices and poses
   p.upload_view = !p.meshes && has(LUMC_DIRTY_MESH_POSITIONS);
-  p.positions = p.upload_view || (!p.meshes && has(LUMC_DIRTY_MESH_SKIN) && pose_pending);
+  p.positions = p.upload_view || (!p.meshes && has(LUMC_DIRTY_MESH_SKIN) && pose_pending) || (!p.meshes && has(LUMC_DIRTY_MESH_SHUTTER) && shutter_pending);
   // lumc_set_mesh_refit_in_place: moved vertices alone or with moved instances, both modes 0
   p.in_place = refit_in_place && p.positions && !has(LUMC_DIRTY_INSTANCES) && refit_mode == 0 && instance_update_mode == 0;
   p.instances_moved = has(LUMC_DIRTY_INSTANCE_TRANSFORMS);

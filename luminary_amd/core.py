@@ -478,6 +478,24 @@ class Core:
         fn.restype = C.c_int
         return int(fn(self._ctx))
 
+    def set_overlap_light_query(self, mode):
+        """-1 auto, 0 never, 1 when allowed: a depth's light queries run on the context's side stream beside the next depth's closest-hit pass
+        (lumc_set_overlap_light_query; bit-identical)"""
+        self._call("lumc_set_overlap_light_query", C.c_int(mode))
+
+    def get_overlap_light_query(self):
+        """1 when the next pass takes the overlapped order for the uploaded scene (lumc_get_overlap_light_query: by mode, scheme, scene and registers), else 0"""
+        fn = self._lib.lumc_get_overlap_light_query
+        fn.restype = C.c_int
+        return int(fn(self._ctx))
+
+    @staticmethod
+    def overlap_registers_fit(ray_kernel_regs, light_query_regs):
+        """lumc_overlap_registers_fit: does one wave of the light queries fit beside the ray kernel's four on a SIMD (no device needed)?"""
+        fn = _lib().lumc_overlap_registers_fit
+        fn.restype = C.c_int
+        return bool(fn(C.c_uint32(ray_kernel_regs), C.c_uint32(light_query_regs)))
+
     def set_physical_camera(self, camera):
         """lumc_set_physical_camera: a PhysicalCamera, or None for the scene's thin lens"""
         self._call("lumc_set_physical_camera", C.byref(camera) if camera is not None else C.c_void_p(0))
@@ -626,7 +644,9 @@ class Core:
         self._call("lumc_set_profiling", C.c_int(1 if on else 0))
 
     def kernel_times(self):
-        ms = (C.c_double * len(KERNELS))()
+        """{kernel: (ms, launches)} since set_profiling(True). Under the overlapped schedule (set_overlap_light_query) the light queries run beside the closest-hit
+        pass, so the times no longer add up to the step's."""
+        ms =(C.c_double * len(KERNELS))()
         n = (C.c_uint32 * len(KERNELS))()
         self._call("lumc_kernel_times", ms, n)
         return {k: (float(ms[i]), int(n[i])) for i, k in enumerate(KERNELS)}

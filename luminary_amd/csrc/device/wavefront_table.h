@@ -111,5 +111,9 @@ const WavefrontKernels* wavefront_kernels_exact();  // csrc/device/wavefront_exa
 const WavefrontKernels* wavefront_kernels_fast();   // csrc/device/wavefront_fast.hip
 const WavefrontProbes* wavefront_probes_exact();
 const WavefrontProbes* wavefront_probes_fast();
+// The vector registers per lane (hipFuncGetAttributes numRegs) of a flavour's closest-hit kernel in the given form and of its k_light_query, on the current device:
+// what the host asks before it lets the two run side by side (csrc/host/context.h overlap_registers_fit). They return a hipError_t.
+int ray_kernel_registers_exact(bool single_level, uint32_t* trace_regs, uint32_t* light_query_regs);
+int ray_kernel_registers_fast(bool single_level, uint32_t* trace_regs, uint32_t* light_query_regs);
 
 }  // namespace lum

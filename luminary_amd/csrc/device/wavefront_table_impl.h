@@ -26,6 +26,15 @@ static int set_ray_kernel_lds(size_t bytes) {
   if (e == hipSuccess) e = hipFuncSetAttribute((const void*) k_trace_particles, hipFuncAttributeMaxDynamicSharedMemorySize, (int) bytes);
   return (int) e;
 }
+static int ray_kernel_registers(bool single_level, uint32_t* trace_regs, uint32_t* light_query_regs) {
+  hipFuncAttributes a{};
+  hipError_t e = hipFuncGetAttributes(&a, (const void*) trace_kernel(single_level));
+  if (e != hipSuccess) return (int) e;
+  *trace_regs = (uint32_t) a.numRegs;
+  e = hipFuncGetAttributes(&a, (const void*) k_light_query);
+  if (e == hipSuccess) *light_query_regs = (uint32_t) a.numRegs;
+  return (int) e;
+}
 static int init_sampler_seeds() { return upload_sampler_seeds(); }
 static void sobol_table(hipStream_t s, uint2* table, uint32_t first_sample, uint32_t count, uint32_t stride, uint32_t dims) {
   hipLaunchKernelGGL(k_sobol_table, dim3((dims * stride + 255u) / 256u), dim3(256), 0, s, table, first_sample, count, stride, dims);
@@ -231,7 +240,9 @@ namespace lum {
 #if LUM_FAST
 const WavefrontKernels* wavefront_kernels_fast() { return &fast::table::kTable; }
 const WavefrontProbes* wavefront_probes_fast() { return &fast::table::kProbes; }
+int ray_kernel_registers_fast(bool single_level, uint32_t* trace_regs, uint32_t* light_query_regs) { return fast::table::ray_kernel_registers(single_level, trace_regs, light_query_regs); }
 #else
+int ray_kernel_registers_exact(bool single_level, uint32_t* trace_regs, uint32_t* light_query_regs) { return exact::table::ray_kernel_registers(single_level, trace_regs, light_query_regs); }
 const WavefrontKernels* wavefront_kernels_exact() { return &exact::table::kTable; }
 const WavefrontProbes* wavefront_probes_exact() { return &exact::table::kProbes; }
 #endif

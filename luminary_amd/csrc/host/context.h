@@ -102,6 +102,11 @@ struct LumContext {
   int single_level = -1;          // the ray kernels' single-level form on a scene of one hittable instance: -1 auto (on), 0 never, 1 when eligible (lumc_set_single_level; LUM_SINGLE_LEVEL)
   int plain_form = -1;            // k_shade's plain form on a scene that has nothing it leaves out (plain_scene, wavefront_table.h): -1 auto (on), 0 never, 1 when eligible (lumc_set_plain_form; LUM_PLAIN_FORM)
   bool first_leaf_identity = false;  // leaf record 0 of the top level maps a ray onto itself (update_scene_tree): see single_level_allowed
+  // The overlapped schedule (core.hip wavefront_depths, overlap_allowed): a depth's light queries run on `side_stream` beside the next depth's closest-hit pass.
+  int overlap_lq = -1;            // -1 auto (kOverlapAuto), 0 never, 1 when allowed (lumc_set_overlap_light_query; LUM_OVERLAP_LQ)
+  hipStream_t side_stream = nullptr;       // non-blocking, lowest priority; made with the context (null: it could not be made, the serial order is kept)
+  std::vector<hipEvent_t> overlap_events;  // two per depth: the depth is shaded (recorded on the caller's stream), its light queries are done (on side_stream)
+  bool overlap_fits[2][2] = {{false, false}, {false, false}};  // [exact, fast][two-level, single-level]: the register guard's verdict (overlap_registers_fit), read once per context
   uint32_t shade_grid_rounds = 2;  // k_shade's grid as a multiple of its resident set (0: the common 2048-workgroup cap); LUM_SHADE_GRID
   int fused_resolve = 1;          // with the fast flavour's ambient reuse: k_shade resolves the previous depth's vertices itself (lumc_set_fused_resolve; LUM_FUSED_RESOLVE)
   struct Fused : FusedBuffers {   // what that needs beyond the usual work buffers (work_layout.h lay_out_fused)
@@ -222,6 +227,14 @@ inline uint32_t grid_for(uint32_t n) {
 // The exact flavour compiles without contraction and takes every transform.
 inline bool single_level_allowed(const LumContext* ctx) {
   return ctx->single_level != 0 && (ctx->wf != wavefront_kernels_fast() || ctx->first_leaf_identity);
+}
+
+// The register guard of the overlapped schedule. A SIMD has 512 vector registers per lane, handed out in blocks of 8; the persistent closest-hit kernel keeps four
+// waves on it, and one wave of k_light_query must fit beside them or the two kernels only take turns. (The visibility kernel never runs beside the light queries:
+// it waits for them, so its count plays no part.)
+inline bool overlap_registers_fit(uint32_t ray_kernel_regs, uint32_t light_query_regs) {
+  const uint32_t ray = (ray_kernel_regs + 7u) & ~7u, lq = (light_query_regs + 7u) & ~7u;
+  return ray_kernel_regs > 0 && light_query_regs > 0 && 4u * ray + lq <= 512u;
 }
 
 // Persistent ray kernels: one workgroup per CU (kTraceBlock threads, its own LDS copy of the tree top); waves pull work from a cursor.

@@ -115,6 +115,31 @@ int resolve_stamps(LumContext* ctx) {
   return 0;
 }
 
+// The overlapped schedule's side stream and the register guard's verdicts (context.h; overlap_allowed below). A failure here is no error: the passes keep the serial order.
+void prepare_overlap(LumContext* ctx) {
+  int least = 0, greatest = 0;
+  if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess) least = 0;
+  // the lowest priority: the ray kernel's workgroups, one per CU, get their CUs before the light queries spread over them
+  if (hipStreamCreateWithPriority(&ctx->side_stream, hipStreamNonBlocking, least) != hipSuccess) ctx->side_stream = nullptr;
+  for (int fast = 0; fast < 2; fast++)
+    for (int single = 0; single < 2; single++) {
+      uint32_t trace_regs = 0, light_query_regs = 0;
+      const int e = fast ? ray_kernel_registers_fast(single != 0, &trace_regs, &light_query_regs) : ray_kernel_registers_exact(single != 0, &trace_regs, &light_query_regs);
+      ctx->overlap_fits[fast][single] = e == 0 && overlap_registers_fit(trace_regs, light_query_regs);
+    }
+  (void) hipGetLastError();
+}
+
+// The events of the overlapped schedule, two per depth, made once and used again by every pass.
+int ensure_overlap_events(LumContext* ctx, uint32_t depths) {
+  while (ctx->overlap_events.size() < 2u * (size_t) depths) {
+    hipEvent_t e;
+    HIP_TRY(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    ctx->overlap_events.push_back(e);
+  }
+  return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -131,6 +156,7 @@ int lumc_context_create(int device_ordinal, LumContext** out) {
   if (const char* e = getenv("LUM_AMBIENT_REUSE")) ctx->ambient_reuse = atoi(e) != 0 ? 1 : 0;
   if (const char* e = getenv("LUM_SINGLE_LEVEL")) ctx->single_level = atoi(e) != 0 ? 1 : 0;
   if (const char* e = getenv("LUM_PLAIN_FORM")) ctx->plain_form = atoi(e) != 0 ? 1 : 0;
+  if (const char* e = getenv("LUM_OVERLAP_LQ")) ctx->overlap_lq = atoi(e) != 0 ? 1 : 0;
   if (const char* e = getenv("LUM_FUSED_RESOLVE")) ctx->fused_resolve = atoi(e) != 0 ? 1 : 0;
   if (const char* e = getenv("LUM_SHADE_GRID")) ctx->shade_grid_rounds = (uint32_t) atoi(e);
   if (const char* e = getenv("LUM_SOBOL_TABLE_RT")) ctx->sobol_table = atoi(e) != 0 ? 1 : 0;
@@ -150,6 +176,7 @@ int lumc_context_create(int device_ordinal, LumContext** out) {
   HIP_TRY(ctx, hipMemset(ctx->d_ctrl.get(), 0, sizeof(uint32_t) * kCtlStride * kCtrlRows));
   HIP_TRY(ctx, ctx->d_counters.resize(LUMC_CNT_COUNT));
   HIP_TRY(ctx, hipMemset(ctx->d_counters.get(), 0, sizeof(uint64_t) * LUMC_CNT_COUNT));
+  prepare_overlap(ctx);
   return 0;
 }
 
@@ -158,6 +185,8 @@ void lumc_context_destroy(LumContext* ctx) {
   (void) hipSetDevice(ctx->device);
   (void) hipDeviceSynchronize();
   resolve_stamps(ctx);
+  for (hipEvent_t e : ctx->overlap_events) (void) hipEventDestroy(e);
+  if (ctx->side_stream) (void) hipStreamDestroy(ctx->side_stream);
   free_exchange(ctx);
   delete ctx;
 }
@@ -271,6 +300,31 @@ static void debug_pass(LumContext* ctx, hipStream_t stream, const DeviceScene& s
 //     is intact while depth d + 1 is shaded. The exact flavour's (provable) reuse keeps its own kernel: its sums must land in the reference's order.
 enum ResolveScheme { kResolvePlain, kResolveReuse, kResolveFused };
 
+// The scheme the next pass asks for (kResolveFused still needs its buffers: wavefront_depths).
+static ResolveScheme wanted_scheme(const LumContext* ctx) {
+  if (!ambient_reuse_active(ctx)) return kResolvePlain;
+  return (ctx->wf->fused_resolve && ctx->fused_resolve != 0 && ctx->wf == wavefront_kernels_fast() && ctx->scene.max_ray_depth > 0) ? kResolveFused : kResolveReuse;
+}
+
+// The overlapped schedule (wavefront_depths): k_light_query of depth d runs on the context's side stream while the caller's stream traces depth d + 1.
+//   The dependency is not there: the closest-hit pass of depth d + 1 reads and writes the next queue's planes and the control words of depth d + 1, which k_shade
+//   of depth d has finished; the light queries read depth d's queue and NEE records, write nee.bsdf_weight_sum and append to depth d's visibility items. The
+//   depth's visibility pass needs the light queries and nothing of the next depth's hits: it runs after both. Both kernels add to the counters atomically.
+//   kResolveReuse keeps the serial order (its closest_hits also resolves depth d, which needs depth d's visibility pass first), and so does everything that
+//   puts a pass between the closest hits and the shading (media_passes), the ray sort (its keys and the reorder pass are ordered on one stream) and a debug mode.
+//   The registers must be there (context.h overlap_registers_fit): today they are for the single-level ray kernels (4 x 96 + 112 = 496 of 512) and not for
+//   the two-level ones (4 x 120 + 112), which keep the serial order launch for launch.
+// kOverlapAuto: what mode -1 means - decided by measurement (profiles/overlap_lq_ab.txt, docs/HISTORY.md): hall +1.5 % samples/s against a spread of 0.2 %, k_light_query
+// 2.1 -> 7.7 ms per launch but off the critical path, k_trace 13.4 -> 14.7 ms beside it.
+constexpr bool kOverlapAuto = true;
+static bool overlap_allowed(const LumContext* ctx, ResolveScheme scheme) {
+  const DeviceScene& sc = ctx->scene;
+  const bool wanted = ctx->overlap_lq < 0 ? kOverlapAuto : ctx->overlap_lq != 0;
+  if (!wanted || !ctx->has_scene || !ctx->side_stream || scheme == kResolveReuse || ctx->sort.mode != 0 || sc.shading_mode != 0u || sc.max_ray_depth == 0u) return false;
+  if (sc.fog_active || sc.ocean_active || sc.particles_active || sc.cloud_active || sc.sky_aerial_perspective) return false;
+  return ctx->overlap_fits[ctx->wf == wavefront_kernels_fast() ? 1 : 0][(single_level_allowed(ctx) && single_level_scene(sc)) ? 1 : 0];
+}
+
 // What one depth reads and writes. Only depth_buffers knows how the queues and record sets rotate.
 struct DepthBuffers {
   PathQueue& cur;        // the depth's paths
@@ -298,16 +352,19 @@ static DepthBuffers depth_buffers(LumContext* ctx, ResolveScheme scheme, uint32_
                       depth == max_depth};
 }
 
+// The closest-hit launch of a depth, alone: the overlapped schedule issues it a depth early.
+static void trace_depth(LumContext* ctx, hipStream_t stream, const DeviceScene& sc, const DepthBuffers& d, const uint32_t* order, uint32_t N) {
+  Launch l(ctx, stream, LUMC_KERNEL_TRACE);
+  ctx->wf->trace(grid_persistent(ctx, N), ray_kernel_lds(ctx), stream, sc, d.cur, order, d.ctrl, ctx->d_counters.get(), ctx->lds_nodes, single_level_allowed(ctx));
+}
+
 // The closest hits of a depth; with kResolveReuse they also answer the ambient samples of the depth before, which is resolved here.
 static int closest_hits(LumContext* ctx, hipStream_t stream, const DeviceScene& sc, ResolveScheme scheme, const DepthBuffers& d, uint32_t N) {
   const WavefrontKernels& wf = *ctx->wf;
   // camera rays leave k_generate in pixel order, which is as coherent as rays get; later depths are sorted on request
   const uint32_t* order = nullptr;
   if (ctx->sort.mode >= 1 && d.depth >= 1 && sort_closest_rays(ctx, stream, d.cur, d.ctrl, N, &order)) return 1;
-  {
-    Launch l(ctx, stream, LUMC_KERNEL_TRACE);
-    wf.trace(grid_persistent(ctx, N), ray_kernel_lds(ctx), stream, sc, d.cur, order, d.ctrl, ctx->d_counters.get(), ctx->lds_nodes, single_level_allowed(ctx));
-  }
+  trace_depth(ctx, stream, sc, d, order, N);
   if (scheme == kResolveReuse && d.depth > 0) {  // the previous depth's resolve: ambient samples answered by the pass above; what it cannot answer is traced (the control words of the fog's visibility pass: no fog here) and resolved after
     uint32_t* prev = d.ctrl - kCtlStride;
     {
@@ -394,15 +451,20 @@ static void feature_shading(LumContext* ctx, hipStream_t stream, const DeviceSce
   }
 }
 
-// Light query, visibility rays, and the depth's resolve where the scheme does it at this point.
+// The depth's light queries. `beside_trace`: on the side stream, next to the persistent closest-hit kernel of the next depth (the overlapped schedule).
+static void light_queries(LumContext* ctx, hipStream_t stream, const DeviceScene& sc, const DepthBuffers& d, uint32_t N, bool beside_trace) {
+  Launch l(ctx, stream, LUMC_KERNEL_LIGHT_QUERY);
+  // (one resident round of its workgroups - four per CU: the kernel's workgroups are dear to start (a 1 KB stack per lane in scratch); 2 rounds, the common cap:
+  //  Example-class 4.6 -> 4.0 ms per 3 steps, scan 3.9 -> 3.6, hall equal; 4 / 8 / 16 rounds on the hall: 30.2 / 32.8 / 44.5 ms against 29.9)
+  // Beside the ray kernel: one workgroup per CU, one wave per SIMD - what the registers leave room for; four per CU could take a CU before the ray kernel's
+  // workgroup arrives and put the two in sequence again. The kernel loops over its rounds. (Two per CU measure the same: profiles/overlap_lq_ab.txt.)
+  const uint32_t per_cu = beside_trace ? 1u : 4u;
+  ctx->wf->light_query(std::min<uint32_t>(grid_for(N), ctx->trace_blocks * per_cu), stream, sc, d.cur, d.nee, ctx->work.shadow, d.ctrl, d.depth_const, ctx->d_counters.get());
+}
+
+// Visibility rays, and the depth's resolve where the scheme does it at this point.
 static int visibility_and_resolve(LumContext* ctx, hipStream_t stream, const DeviceScene& sc, ResolveScheme scheme, const DepthBuffers& d, uint32_t N) {
   const WavefrontKernels& wf = *ctx->wf;
-  {
-    Launch l(ctx, stream, LUMC_KERNEL_LIGHT_QUERY);
-    // (one resident round of its workgroups - four per CU: the kernel's workgroups are dear to start (a 1 KB stack per lane in scratch); 2 rounds, the common cap:
-    //  Example-class 4.6 -> 4.0 ms per 3 steps, scan 3.9 -> 3.6, hall equal; 4 / 8 / 16 rounds on the hall: 30.2 / 32.8 / 44.5 ms against 29.9)
-    wf.light_query(std::min<uint32_t>(grid_for(N), ctx->trace_blocks * 4u), stream, sc, d.cur, d.nee, ctx->work.shadow, d.ctrl, d.depth_const, ctx->d_counters.get());
-  }
   const uint32_t* shadow_order = nullptr;
   if (ctx->sort.mode == 2) {
     shadow_order = sort_rays(ctx, stream, ctx->work.shadow.origin_dist, ctx->work.shadow.dir_out, d.ctrl + kCtlShadowItems,
@@ -441,20 +503,39 @@ static int wavefront_depths(LumContext* ctx, hipStream_t stream, uint32_t N, uin
   const uint32_t max_depth = sc.max_ray_depth;
   prepare_sobol_table(ctx, stream, sc, first_sample, sample_count);
   if (sc.shading_mode != 0u) { debug_pass(ctx, stream, sc, N); return 0; }
-  ResolveScheme scheme = ambient_reuse_active(ctx) ? kResolveReuse : kResolvePlain;
-  if (scheme == kResolveReuse && ctx->wf->fused_resolve && ctx->fused_resolve != 0 && ctx->wf == wavefront_kernels_fast() && max_depth > 0) {
-    if (ensure_fused(ctx, stream) == 0) scheme = kResolveFused;
-    else {  // no room for its buffers (a third of the work buffers again): the separate resolve kernel does the same sums
-      (void) hipGetLastError();
-      ctx->error.clear();
-    }
+  ResolveScheme scheme = wanted_scheme(ctx);
+  if (scheme == kResolveFused && ensure_fused(ctx, stream) != 0) {  // no room for its buffers (a third of the work buffers again): the separate resolve kernel does the same sums
+    (void) hipGetLastError();
+    ctx->error.clear();
+    scheme = kResolveReuse;
   }
+  // The overlapped order (overlap_allowed), chosen per pass: after a depth is shaded its light queries go to the side stream and the caller's stream traces the
+  // next depth meanwhile, then waits for them before the depth's visibility pass. Depth 0's closest hits and the last depth's light queries stay on the caller's
+  // stream. Every launch on the side stream is followed by a wait on the caller's, so the pass ends - for the accumulate kernel, for lumc_synchronize, for whatever
+  // the caller puts on its stream next - where the serial order ends.
+  const bool overlap = overlap_allowed(ctx, scheme) && ensure_overlap_events(ctx, max_depth) == 0;
+  hipStream_t side = ctx->side_stream;
+  bool traced = false;  // this depth's closest-hit launch was issued with the depth before
   for (uint32_t depth = 0; depth <= max_depth; depth++) {
     const DepthBuffers d = depth_buffers(ctx, scheme, depth, max_depth);
-    if (closest_hits(ctx, stream, sc, scheme, d, N)) return 1;
+    if (!traced && closest_hits(ctx, stream, sc, scheme, d, N)) return 1;  // (overlapped: kResolvePlain or kResolveFused, no sort - closest_hits is that one launch)
+    traced = false;
     media_passes(ctx, stream, sc, d, N);
     shade_depth(ctx, stream, sc, scheme, d, N);
     feature_shading(ctx, stream, sc, d, N);
+    if (overlap && !d.last) {
+      hipEvent_t shaded = ctx->overlap_events[2u * depth], queried = ctx->overlap_events[2u * depth + 1u];
+      HIP_TRY(ctx, hipEventRecord(shaded, stream));
+      HIP_TRY(ctx, hipStreamWaitEvent(side, shaded, 0));
+      light_queries(ctx, side, sc, d, N, true);
+      const hipError_t recorded = hipEventRecord(queried, side);
+      if (recorded != hipSuccess) (void) hipStreamSynchronize(side);  // no event to wait for: the host joins the side stream before it reports the error
+      HIP_TRY(ctx, recorded);
+      trace_depth(ctx, stream, sc, depth_buffers(ctx, scheme, depth + 1u, max_depth), nullptr, N);
+      traced = true;
+      HIP_TRY(ctx, hipStreamWaitEvent(stream, queried, 0));
+    }
+    else light_queries(ctx, stream, sc, d, N, false);
     if (visibility_and_resolve(ctx, stream, sc, scheme, d, N)) return 1;
     volume_bounce(ctx, stream, sc, d, N);
   }
@@ -1387,6 +1468,15 @@ int lumc_set_plain_form(LumContext* ctx, int mode) {
 }
 
 int lumc_get_plain_form(const LumContext* ctx) { return (ctx && ctx->has_scene && ctx->plain_form != 0 && plain_scene(ctx->scene)) ? 1 : 0; }
+
+int lumc_set_overlap_light_query(LumContext* ctx, int mode) {
+  if (!ctx || mode < -1 || mode > 1) { if (ctx) ctx->error = "lumc_set_overlap_light_query: -1 (auto), 0 (never) or 1 (when the pass allows it)"; return 1; }
+  ctx->overlap_lq = mode;
+  return 0;
+}
+// what the next pass will do for the uploaded scene (a fused resolve that finds no room for its buffers falls back to the reuse scheme and the serial order)
+int lumc_get_overlap_light_query(const LumContext* ctx) { return (ctx && ctx->has_scene && overlap_allowed(ctx, wanted_scheme(ctx))) ? 1 : 0; }
+int lumc_overlap_registers_fit(uint32_t ray_kernel_regs, uint32_t light_query_regs) { return overlap_registers_fit(ray_kernel_regs, light_query_regs) ? 1 : 0; }
 int lumc_get_flavour(const LumContext* ctx) { return (ctx && ctx->wf == wavefront_kernels_exact()) ? LUMC_FLAVOUR_EXACT : LUMC_FLAVOUR_FAST; }
 
 unsigned int lumc_lds_stack_bytes(void) { return LUM_LDS_STACK_BYTES; }

@@ -489,6 +489,27 @@ class Core:
         fn.restype = C.c_int
         return int(fn(self._ctx))
 
+    def set_pixel_major(self, mode):
+        """-1 auto, 0 sample-major, 1 pixel-major: the order of render()'s path slots (lumc_set_pixel_major; bit-identical)"""
+        self._call("lumc_set_pixel_major", C.c_int(mode))
+
+    def get_pixel_major(self):
+        """1 when the next render() numbers its path slots pixel-major (lumc_get_pixel_major), else 0"""
+        fn = self._lib.lumc_get_pixel_major
+        fn.restype = C.c_int
+        return int(fn(self._ctx))
+
+    def set_coherent_first_hits(self, mode):
+        """-1 auto, 0 never, 1 when eligible (then for trace_closest too): the depth-0 closest-hit launch visits a node once per wave where its lanes agree
+        (lumc_set_coherent_first_hits; bit-identical)"""
+        self._call("lumc_set_coherent_first_hits", C.c_int(mode))
+
+    def get_coherent_first_hits(self):
+        """1 when the next render()'s depth-0 launch takes the coherent form at a batch of 64 (lumc_get_coherent_first_hits: by mode, slots and scene), else 0"""
+        fn = self._lib.lumc_get_coherent_first_hits
+        fn.restype = C.c_int
+        return int(fn(self._ctx))
+
     @staticmethod
     def overlap_registers_fit(ray_kernel_regs, light_query_regs):
         """lumc_overlap_registers_fit: does one wave of the light queries fit beside the ray kernel's four on a SIMD (no device needed)?"""

@@ -233,6 +233,7 @@ struct VolumeQueue {
 struct PassParams {
   const uint32_t* pixels;  // pixel index (x + y*width) per local pixel, or nullptr for identity
   uint32_t num_pixels, batch, first_sample;
+  uint32_t pixel_major;  // path slot = pixel * batch + sample_in_batch instead of sample_in_batch * num_pixels + pixel (kernels.h; lumc_set_pixel_major)
 };
 
 // Adaptive sampling bookkeeping shared by host and kernels (dev_adaptive.h).

@@ -35,6 +35,10 @@
 //     LDS-hit counters with them). Every output keeps its bits (tests/test_single_level.py); the fast flavour takes the form only for an identity transform
 //     (csrc/host/context.h single_level_allowed: under -ffp-contract=fast two instantiations of the map round differently). The two-level kernels' code is the
 //     parent's to the instruction (profiles/single_level_isa_identity.txt): what a scene of several instances runs did not change;
+//   * a third form for ONE launch: trace_items<Q, true, kCoherent>, the single-level walk of the depth-0 launch of a pass, whose waves hold the camera rays of one pixel
+//     (pixel-major path slots, kernels.h). Those rays differ by sub-pixel jitter: they stand on the same node at nearly every step. Where all live lanes do - two readlanes
+//     and two ballots per turn of the phase loop say so - the node's seven words come once per wave through the scalar unit (visit_node_uniform) instead of 64 times through
+//     the vector-memory address unit, the limiter named above; where they do not, the turn is the plain one. See the comment at trace_items; measured: profiles/first_depth_ab.txt;
 //   * persistent waves fetch rays from a global cursor and refill idle lanes when too few are still traversing;
 //   * the first nodes of the array (breadth-first across both levels; 448 of them beside 96 KB of stack bottoms since round 6, 704 beside 64 KB before) are staged in LDS by
 //     every workgroup, the oldest 12 (visibility rays: 24) stack entries of every lane live there too: LDS hit rate of the node visits 0.62 / 0.72 with the 704.
@@ -205,27 +209,11 @@ template <typename E> struct TraversalStack {
   LUM_DEV void store(int i, E e) { if (i < lds_entries) lds[(uint32_t) i * (uint32_t) kTraceBlock] = StackWord<E>::pack(e); else scratch[i] = StackWord<E>::pack(e); }
   LUM_DEV E load(int i) const { if (i < lds_entries) return StackWord<E>::unpack(lds[(uint32_t) i * (uint32_t) kTraceBlock]); return StackWord<E>::unpack(scratch[i]); }
 };
-template <bool kOrdered, bool kCull, int kFarFirst = 0, typename S>
-LUM_DEV uint32_t visit_node(const NodeSource& src, uint32_t cur, const TRay& r, float tmax, S& stk, int& sp,
-                            typename StackEntry<kCull>::E& top, RayStats& st) {
-  static_assert(!(kFarFirst && kCull), "the negated keys are not distances: only for queries that do not cull by them");
+// The second half of a node visit, from the node's words on (visit_node, visit_node_uniform): the four entry distances, the sort, the pushes.
+template <bool kOrdered, bool kCull, int kFarFirst, typename S>
+LUM_DEV uint32_t enter_children(float4 nx, float4 ny, float4 nz, float4 fx, float4 fy, float4 fz, uint4 ch, const TRay& r, float tmax, S& stk, int& sp,
+                                typename StackEntry<kCull>::E& top) {
   using SE = StackEntry<kCull>;
-  const uint32_t b = cur << 7;
-  float4 nx, ny, nz, fx, fy, fz;
-  uint4 ch;
-  if (cur < src.lds_count) {
-    const char* p = src.lds + b;
-    nx = *reinterpret_cast<const float4*>(p + r.nx); ny = *reinterpret_cast<const float4*>(p + r.ny); nz = *reinterpret_cast<const float4*>(p + r.nz);
-    fx = *reinterpret_cast<const float4*>(p + r.fx); fy = *reinterpret_cast<const float4*>(p + r.fy); fz = *reinterpret_cast<const float4*>(p + r.fz);
-    ch = *reinterpret_cast<const uint4*>(p + 96u);
-    st.lds_nodes++;
-  }
-  else {
-    const Bvh4Node* __restrict__ nodes = src.global;
-    nx = node_f4(nodes, b + r.nx); ny = node_f4(nodes, b + r.ny); nz = node_f4(nodes, b + r.nz);
-    fx = node_f4(nodes, b + r.fx); fy = node_f4(nodes, b + r.fy); fz = node_f4(nodes, b + r.fz);
-    ch = node_u4(nodes, b + 96u);
-  }
   float k0 = child_entry<kFarFirst>(nx.x, ny.x, nz.x, fx.x, fy.x, fz.x, r, tmax);
   float k1 = child_entry<kFarFirst>(nx.y, ny.y, nz.y, fx.y, fy.y, fz.y, r, tmax);
   float k2 = child_entry<kFarFirst>(nx.z, ny.z, nz.z, fx.z, fy.z, fz.z, r, tmax);
@@ -247,6 +235,66 @@ LUM_DEV uint32_t visit_node(const NodeSource& src, uint32_t cur, const TRay& r, 
     stk.store(sp, top); sp++; top = SE::make(c1, k1);
   }
   return (k0 < inf) ? c0 : kBvhEmpty;
+}
+
+template <bool kOrdered, bool kCull, int kFarFirst = 0, typename S>
+LUM_DEV uint32_t visit_node(const NodeSource& src, uint32_t cur, const TRay& r, float tmax, S& stk, int& sp,
+                            typename StackEntry<kCull>::E& top, RayStats& st) {
+  static_assert(!(kFarFirst && kCull), "the negated keys are not distances: only for queries that do not cull by them");
+  const uint32_t b = cur << 7;
+  float4 nx, ny, nz, fx, fy, fz;
+  uint4 ch;
+  if (cur < src.lds_count) {
+    const char* p = src.lds + b;
+    nx = *reinterpret_cast<const float4*>(p + r.nx); ny = *reinterpret_cast<const float4*>(p + r.ny); nz = *reinterpret_cast<const float4*>(p + r.nz);
+    fx = *reinterpret_cast<const float4*>(p + r.fx); fy = *reinterpret_cast<const float4*>(p + r.fy); fz = *reinterpret_cast<const float4*>(p + r.fz);
+    ch = *reinterpret_cast<const uint4*>(p + 96u);
+    st.lds_nodes++;
+  }
+  else {
+    const Bvh4Node* __restrict__ nodes = src.global;
+    nx = node_f4(nodes, b + r.nx); ny = node_f4(nodes, b + r.ny); nz = node_f4(nodes, b + r.nz);
+    fx = node_f4(nodes, b + r.fx); fy = node_f4(nodes, b + r.fy); fz = node_f4(nodes, b + r.fz);
+    ch = node_u4(nodes, b + 96u);
+  }
+  return enter_children<kOrdered, kCull, kFarFirst>(nx, ny, nz, fx, fy, fz, ch, r, tmax, stk, sp, top);
+}
+
+// The visit of a node that EVERY live lane of the wave stands on, with the same three direction signs (trace_items<Q, true, kCoherent>: the camera rays of one
+// pixel): the seven words of the node are the same for all lanes, so they are fetched once per wave - outside the staged top through the constant address space,
+// i.e. with scalar loads into SGPRs, which leaves the vector-memory address unit (a cycle per lane and load, the ray kernels' measured limiter) out of the visit;
+// inside it with one LDS read at a wave-uniform address. The box tests then take the planes as scalar operands. `octant`: the lanes' common near-plane offsets
+// (TRay::nx | ny << 8 | nz << 16). Everything per lane - entry distances, sort, pushes - is visit_node's, expression for expression: the same children in the same order.
+typedef float NodePlanes __attribute__((ext_vector_type(4)));  // (the HIP vector classes cannot be read through an address-space-qualified pointer)
+typedef uint32_t NodeChildren __attribute__((ext_vector_type(4)));
+template <bool kOrdered, bool kCull, int kFarFirst = 0, typename S>
+LUM_DEV uint32_t visit_node_uniform(const NodeSource& src, uint32_t cur, uint32_t octant, const TRay& r, float tmax, S& stk, int& sp, typename StackEntry<kCull>::E& top,
+                                    RayStats& st) {
+  const uint32_t b = cur << 7;
+  const uint32_t onx = octant & 0xFFu, ony = (octant >> 8) & 0xFFu, onz = octant >> 16;
+  const uint32_t ofx = 48u - onx, ofy = 80u - ony, ofz = 112u - onz;  // TRay::set
+  float4 nx, ny, nz, fx, fy, fz;
+  uint4 ch;
+  if (cur < src.lds_count) {
+    const char* p = src.lds + b;
+    nx = *reinterpret_cast<const float4*>(p + onx); ny = *reinterpret_cast<const float4*>(p + ony); nz = *reinterpret_cast<const float4*>(p + onz);
+    fx = *reinterpret_cast<const float4*>(p + ofx); fy = *reinterpret_cast<const float4*>(p + ofy); fz = *reinterpret_cast<const float4*>(p + ofz);
+    ch = *reinterpret_cast<const uint4*>(p + 96u);
+    st.lds_nodes++;
+  }
+  else {
+    typedef const char __attribute__((address_space(4)))* ConstBytes;
+    typedef const NodePlanes __attribute__((address_space(4)))* ConstPlanes;
+    typedef const NodeChildren __attribute__((address_space(4)))* ConstChildren;
+    const ConstBytes p = (ConstBytes) src.global + b;
+    const NodePlanes anx = *(ConstPlanes) (p + onx), any = *(ConstPlanes) (p + ony), anz = *(ConstPlanes) (p + onz);
+    const NodePlanes afx = *(ConstPlanes) (p + ofx), afy = *(ConstPlanes) (p + ofy), afz = *(ConstPlanes) (p + ofz);
+    const NodeChildren ach = *(ConstChildren) (p + 96u);
+    nx = make_float4(anx.x, anx.y, anx.z, anx.w); ny = make_float4(any.x, any.y, any.z, any.w); nz = make_float4(anz.x, anz.y, anz.z, anz.w);
+    fx = make_float4(afx.x, afx.y, afx.z, afx.w); fy = make_float4(afy.x, afy.y, afy.z, afy.w); fz = make_float4(afz.x, afz.y, afz.z, afz.w);
+    ch = make_uint4(ach.x, ach.y, ach.z, ach.w);
+  }
+  return enter_children<kOrdered, kCull, kFarFirst>(nx, ny, nz, fx, fy, fz, ch, r, tmax, stk, sp, top);
 }
 
 // Pops the newest entry into (node, tnear) and refills the register top from scratch. The bottom of the stack is a sentinel
@@ -304,8 +352,24 @@ LUM_DEV uint32_t instance_of(const OneInstance<true>& one, uint32_t) { return on
 // (the expressions of the instance-entry phase below, in their order) and starts at the mesh root: no visit of top-level node 0, no entry phase, no marker on
 // the stack, no restore of the world-space ray, two phases to vote on. Same triangles tested in the same order per lane: every output keeps its bits
 // (tests/test_single_level.py); CNT_NODES and the LDS-hit count drop by one per ray.
-template <class Q, bool kSingleLevel = false>
+// kCoherent (single level only; the launcher picks it for the depth-0 launch of a pass, whose waves hold the camera rays of one pixel under pixel-major path
+// slots - kernels.h, lumc_set_coherent_first_hits): at the top of every turn of the phase loop the wave asks whether all its live lanes stand on the same inner node
+// with the same direction signs - two readlanes (a live lane's node and sign word) and two ballots (who is live, who differs), which a turn that fails the test pays on
+// top of the vote's own ballots. If so the vote is decided (nobody holds a leaf) and the node is visited by visit_node_uniform: fetched
+// once per wave by the scalar unit (or one uniform LDS read), the box tests on scalar operands; sort, pushes and `top` stay per lane, since lanes may differ in
+// the children they enter. Otherwise the turn is the plain one. Per lane the same nodes and triangles in the same order: every output and counter keeps its bits.
+// Refill (LUM_COHERENT_REFILL): a wave of this form takes new items only when ALL its lanes are idle, 64 consecutive ones at a time. The plain rule - refill the idle
+// lanes once fewer than LUM_REFILL are live - gives a wave whose pixel ended on 60 lanes the first 60 rays of the next pixel beside the 4 stragglers; from then on
+// its fills straddle two pixels for the rest of the launch and the test above fails wherever the two part ways.
+#ifndef LUM_COHERENT_REFILL
+#define LUM_COHERENT_REFILL 1
+#endif
+template <bool kCoherent> struct WaveOctant {};  // (an empty type in the plain instantiations: nothing of it reaches their code - OneInstance, above)
+template <> struct WaveOctant<true> { uint32_t word; };  // TRay::nx | ny << 8 | nz << 16 of the lane's ray: equal words, equal plane offsets
+
+template <class Q, bool kSingleLevel = false, bool kCoherent = false>
 LUM_DEV void trace_items(const DeviceScene& sc, uint32_t n, uint32_t* __restrict__ cursor, Q& q, RayStats& st, uint32_t& rays, uint32_t lds_count) {
+  static_assert(kSingleLevel || !kCoherent, "the coherent form is a single-level form");
   if (n == 0u) return;  // wave-uniform (a kernel argument read from the control words): an empty launch - the ambient reuse's fallback list on an opaque scene - stages nothing
   using SE = StackEntry<Q::kCull>;
   using E = typename SE::E;
@@ -336,6 +400,9 @@ LUM_DEV void trace_items(const DeviceScene& sc, uint32_t n, uint32_t* __restrict
     __syncthreads();
   }
   [[maybe_unused]] OneInstance<kSingleLevel> one;
+  [[maybe_unused]] WaveOctant<kCoherent> oct;
+  if constexpr (kCoherent) oct.word = 0u;
+  constexpr bool kWholeWaveRefill = kCoherent && LUM_COHERENT_REFILL != 0;
   if constexpr (kSingleLevel) {  // wave-uniform: the address is a kernel argument
     const float4* __restrict__ leaf = sc.tlas_leaves;
     const float4 meta = leaf[3];
@@ -396,9 +463,9 @@ LUM_DEV void trace_items(const DeviceScene& sc, uint32_t n, uint32_t* __restrict
     const unsigned long long idle = __ballot(cur == kTraversalDone);
 #ifdef LUM_PHASE_STATS
     const unsigned long long t_refill_ = __builtin_readcyclecounter();
-    const bool refilling_ = idle != 0ull && more;
+    const bool refilling_ = (kWholeWaveRefill ? idle == ~0ull : idle != 0ull) && more;
 #endif
-    if (idle != 0ull && more) {  // wave-uniform
+    if ((kWholeWaveRefill ? idle == ~0ull : idle != 0ull) && more) {  // wave-uniform
       if (chunk_next >= chunk_end) {
         uint32_t base = 0;
         if (lane == 0) base = atomicAdd(cursor, chunk);
@@ -427,6 +494,7 @@ LUM_DEV void trace_items(const DeviceScene& sc, uint32_t n, uint32_t* __restrict
                 const V3 od = v3(mat_row_apply(r0.x, r0.y, r0.z, wd.x, wd.y, wd.z), mat_row_apply(r1.x, r1.y, r1.z, wd.x, wd.y, wd.z),
                                  mat_row_apply(r2.x, r2.y, r2.z, wd.x, wd.y, wd.z));
                 r.set(oo, od); cur = one.root; sp = 0; top = SE::make(kTraversalDone, 0.0f);
+                if constexpr (kCoherent) oct.word = r.nx | (r.ny << 8) | (r.nz << 16);
               }
               else q.finish(sc, idx);
             }
@@ -442,7 +510,12 @@ LUM_DEV void trace_items(const DeviceScene& sc, uint32_t n, uint32_t* __restrict
 #ifdef LUM_PHASE_STATS
     if (refilling_) { ptime_[8] += __builtin_readcyclecounter() - t_refill_; ptime_[9]++; }
 #endif
-    if (__ballot(cur != kTraversalDone) == 0ull) break;
+    if (__ballot(cur != kTraversalDone) == 0ull) {
+      // Whole-wave refill: every refill meets a wave with nothing live, so one whose items all ended where they were loaded (non-finite rays) must go on to the
+      // rest of its chunk - leaving here would drop it. (The plain rule leaves in the same case, which it meets only where a wave happens to be all idle.)
+      if constexpr (kWholeWaveRefill) { if (more) continue; }
+      break;
+    }
     LUM_PHASE(5);
 
     // Phase vote: every iteration the wave runs ONE phase (node visit, instance entry or triangle tests), the one most of its lanes
@@ -451,6 +524,30 @@ LUM_DEV void trace_items(const DeviceScene& sc, uint32_t n, uint32_t* __restrict
     // was 0.33-0.41 with the plain while-while loop.
     while (true) {
       const bool live = cur != kTraversalDone;
+      if constexpr (kCoherent) {  // one node, one set of direction signs for every live lane: the visit the wave makes as one (above)
+        const unsigned long long live_lanes = __ballot(live);
+        if (live_lanes == 0ull) break;
+        const int first = __builtin_ctzll(live_lanes);
+        const uint32_t cur0 = (uint32_t) __builtin_amdgcn_readlane((int) cur, first), oct0 = (uint32_t) __builtin_amdgcn_readlane((int) oct.word, first);
+        if (!(cur0 & kBvhLeafBit) && __ballot(live && (cur != cur0 || oct.word != oct0)) == 0ull) {
+          LUM_TIME_BEGIN();
+          if (live) {
+            LUM_PHASE(0);
+            st.nodes++;
+            cur = visit_node_uniform<Q::kOrdered, Q::kCull, Q::kFarFirst>(nodes, cur0, oct0, r, tmax, stk, sp, top, st);
+            if (cur == kBvhEmpty) {
+              pop();
+              if (cur == kTraversalDone) q.finish(sc, idx);
+            }
+          }
+#ifdef LUM_PHASE_STATS
+          asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");  // as at the end of the plain turn: the same slots, a node phase from memory (0) or from LDS (2)
+          LUM_TIME_END(cur0 >= lds_count ? 0 : 2);
+#endif
+          if constexpr (!kWholeWaveRefill) { if (more && (uint32_t) __popcll(live_lanes) < LUM_REFILL) break; }
+          continue;
+        }
+      }
       const bool at_leaf = live && (cur & kBvhLeafBit);
       // (single level: a leaf is a triangle leaf, nobody enters anything - two phases, two ballots)
       const bool want_tris = at_leaf && (kSingleLevel || inst != kNoInstance), want_enter = !kSingleLevel && at_leaf && inst == kNoInstance;
@@ -511,7 +608,7 @@ LUM_DEV void trace_items(const DeviceScene& sc, uint32_t n, uint32_t* __restrict
         LUM_TIME_END(kind);
       }
 #endif
-      if (more && n_live < LUM_REFILL) break;
+      if constexpr (!kWholeWaveRefill) { if (more && n_live < LUM_REFILL) break; }
     }
   }
 #ifdef LUM_PHASE_STATS

@@ -1,6 +1,8 @@
 // Wavefront path-tracing kernels for gfx950.
 //
-// One pass renders `batch` consecutive sample ids of `num_pixels` pixels: path slot = sample_in_batch * num_pixels + pixel.
+// One pass renders `batch` consecutive sample ids of `num_pixels` pixels. Path slot = pixel * batch + sample_in_batch (pixel-major, PassParams::pixel_major: the
+// sample ids of one pixel are neighbours, so a wave of the depth-0 closest-hit launch holds the rays of ONE pixel at a batch of 64 - lumc_set_pixel_major), or
+// sample_in_batch * num_pixels + pixel (sample-major: a wave holds one sample id of 64 pixels). Only k_generate and k_accumulate know the mapping (pass_slot_split).
 // Live paths are kept compacted in a PathQueue (SoA of 16-byte words); every depth runs
 //     trace (closest hit, persistent waves)
 //     -> shade (context, NEE sampling, bounce, emission, roulette; appends survivors to the other queue and the visibility
@@ -91,6 +93,12 @@ LUM_DEV void generate_path(const DeviceScene& sc, const DeviceLens& lens, const 
   }
 }
 
+// Slot -> (pixel of the pass, sample of the batch), in either slot order (the comment at the top of this file).
+LUM_DEV void pass_slot_split(const PassParams& pp, uint32_t i, uint32_t& p, uint32_t& b) {
+  if (pp.pixel_major) { p = i / pp.batch; b = i - p * pp.batch; }
+  else { b = i / pp.num_pixels; p = i - b * pp.num_pixels; }
+}
+
 // Camera paths of one pass. The thin lens fills slot i of the queue with the ray of slot i; the physical camera appends only the rays that left the
 // lens (generate_path), so the pass's path count is counted on the device from zero (the caller clears it).
 template <int kCam>
@@ -98,7 +106,8 @@ __global__ __launch_bounds__(kBlock) void k_generate(DeviceScene sc, PassParams 
   const uint32_t total = pp.num_pixels * pp.batch;
   if constexpr (kCam == kCamThinLens) {
     for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < total; i += gridDim.x * kBlock) {
-      const uint32_t b = i / pp.num_pixels, p = i - b * pp.num_pixels;
+      uint32_t b, p;
+      pass_slot_split(pp, i, p, b);
       const uint32_t index = pp.pixels ? pp.pixels[p] : p;
       const uint32_t y = index / sc.width, x = index - y * sc.width;
       const Sampler smp{sc.bluenoise_2d, x, y, pp.first_sample + b, 0};
@@ -122,8 +131,8 @@ __global__ __launch_bounds__(kBlock) void k_generate(DeviceScene sc, PassParams 
       const bool active = i < total;
       uint32_t x = 0, y = 0, b = 0;
       if (active) {
-        b = i / pp.num_pixels;
-        const uint32_t p = i - b * pp.num_pixels;
+        uint32_t p;
+        pass_slot_split(pp, i, p, b);
         const uint32_t index = pp.pixels ? pp.pixels[p] : p;
         y = index / sc.width; x = index - y * sc.width;
         results[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
@@ -264,6 +273,20 @@ __global__ LUM_TRACE_BOUNDS void k_trace(DeviceScene sc, PathQueue q, const uint
   tq.order = order;
   tq.item = 0;
   trace_items<TraceQuery, true>(sc, ctrl[kCtlPaths], ctrl + kCtlTraceCursor, tq, st, rays, lds_nodes);
+  flush_stats(counters, st, rays, kCntTrace, kCntNodes, kCntTris, kCntNodesLds);
+}
+// The single-level pass over waves of coherent rays (trace_items<Q, true, true>, dev_trace.h): the depth-0 launch of a pass, alone on the caller's stream - it may
+// take up to 128 registers (four waves per SIMD), the overlapped schedule's register guard reads the plain single-level kernel.
+template <bool kSingleLevel, bool kCoherent>
+__global__ LUM_TRACE_BOUNDS void k_trace(DeviceScene sc, PathQueue q, const uint32_t* order, uint32_t* ctrl, uint64_t* counters, uint32_t lds_nodes) {
+  static_assert(kSingleLevel && kCoherent, "the other forms are the kernels of this name with fewer parameters");
+  RayStats st{0, 0, 0};
+  uint32_t rays = 0;
+  TraceQuery tq;
+  tq.q = q;
+  tq.order = order;
+  tq.item = 0;
+  trace_items<TraceQuery, true, true>(sc, ctrl[kCtlPaths], ctrl + kCtlTraceCursor, tq, st, rays, lds_nodes);
   flush_stats(counters, st, rays, kCntTrace, kCntNodes, kCntTris, kCntNodesLds);
 }
 
@@ -1582,6 +1605,18 @@ __global__ LUM_TRACE_BOUNDS void k_trace_rays(DeviceScene sc, uint32_t n, const 
   RaysQuery q;
   q.origins = origins; q.dirs = dirs; q.ignore = ignore; q.out = out;
   trace_items<RaysQuery, true>(sc, n, cursor, q, st, rays, lds_nodes);
+  flush_stats(counters, st, rays, kCntTrace, kCntNodes, kCntTris, kCntNodesLds);
+}
+// ... and the coherent form of that (k_trace<true, true>), taken where the caller asks for it (lumc_set_coherent_first_hits(1)): the tests build its waves by hand
+template <bool kSingleLevel, bool kCoherent>
+__global__ LUM_TRACE_BOUNDS void k_trace_rays(DeviceScene sc, uint32_t n, const float* origins, const float* dirs, const uint32_t* ignore,
+                                                           uint32_t* out, uint32_t* cursor, uint64_t* counters, uint32_t lds_nodes) {
+  static_assert(kSingleLevel && kCoherent, "the other forms are the kernels of this name with fewer parameters");
+  RayStats st{0, 0, 0};
+  uint32_t rays = 0;
+  RaysQuery q;
+  q.origins = origins; q.dirs = dirs; q.ignore = ignore; q.out = out;
+  trace_items<RaysQuery, true, true>(sc, n, cursor, q, st, rays, lds_nodes);
   flush_stats(counters, st, rays, kCntTrace, kCntNodes, kCntTris, kCntNodesLds);
 }
 

@@ -307,7 +307,55 @@ __global__ __launch_bounds__(256) void k_generate_result(AdaptiveView a, ResultP
 }
 
 // ---- accumulation (cuda/accumulation.cuh:63-84): samples of a pixel are added in sample order ----
-__global__ __launch_bounds__(kBlock) void k_accumulate(const float4* results, uint32_t num_pixels, uint32_t batch, float* first_moment, float* second_moment) {
+// Pixel-major result slots (results[p * batch + k], kernels.h): a pixel's samples are neighbours in memory and the pixels of a wave lie `batch` x 16 bytes apart, so
+// a lane reading its own pixel's row would touch a cache line per lane and load. Instead a wave brings a tile of 64 pixels x kAccTile samples through LDS - rows of
+// kAccTile x 16 = 128 contiguous bytes, the tile's float4s dealt to the lanes in memory order - and every lane then adds its pixel's row from there in sample order,
+// one float add after the other: the expressions and their order are the sample-major loop's, so are the bits.
+// LDS layout (dynamic: kAccTileBytes per workgroup, none for sample-major slots): float4 `at` of tile row `row` sits at row * kAccTile + (at ^ (row & 7)): the rows
+// are 128 bytes apart, and without the swizzle the 64 lanes of a read (same `at`, 64 rows) would meet in the same four banks.
+constexpr uint32_t kAccTile = 8;
+constexpr uint32_t kAccTileBytes = kBlock * kAccTile * (uint32_t) sizeof(float4);
+LUM_DEV void accumulate_pixel_major(const float4* __restrict__ results, uint32_t num_pixels, uint32_t batch, float* first_moment, float* second_moment, float4* tiles) {
+  static_assert(kAccTile == 8u, "the swizzle and the shifts below are written for rows of eight");
+  const uint32_t lane = threadIdx.x & 63u;
+  float4* tile = tiles + (threadIdx.x >> 6) * (64u * kAccTile);
+  const uint32_t rounds = (num_pixels + gridDim.x * kBlock - 1u) / (gridDim.x * kBlock);  // whole workgroups go round together: the barriers below
+  for (uint32_t round = 0; round < rounds; round++) {
+    const uint32_t p = (round * gridDim.x + blockIdx.x) * kBlock + threadIdx.x;
+    const uint32_t p0 = p - lane;  // the wave's first pixel
+    const bool active = p < num_pixels;
+    float r = 0.0f, g = 0.0f, b = 0.0f, s = 0.0f;
+    if (active) {
+      r = first_moment[p]; g = first_moment[num_pixels + p]; b = first_moment[2 * num_pixels + p];
+      s = second_moment ? second_moment[p] : 0.0f;
+    }
+    for (uint32_t k0 = 0; k0 < batch; k0 += kAccTile) {
+      const uint32_t kc = min(kAccTile, batch - k0);
+#pragma unroll
+      for (uint32_t j = 0; j < kAccTile; j++) {
+        const uint32_t e = j * 64u + lane, row = e >> 3, at = e & 7u;
+        if (p0 + row < num_pixels && at < kc) tile[row * kAccTile + (at ^ (row & 7u))] = results[(size_t) (p0 + row) * batch + k0 + at];
+      }
+      __syncthreads();
+      if (active) {
+        for (uint32_t k = 0; k < kc; k++) {
+          const float4 v = tile[lane * kAccTile + (k ^ (lane & 7u))];
+          r += v.x; g += v.y; b += v.z;
+          s += luminance(col(v.x * v.x, v.y * v.y, v.z * v.z));
+        }
+      }
+      __syncthreads();
+    }
+    if (active) {
+      first_moment[p] = r; first_moment[num_pixels + p] = g; first_moment[2 * num_pixels + p] = b;
+      if (second_moment) second_moment[p] = s;
+    }
+  }
+}
+// pixel_major: the order of the result slots (PassParams::pixel_major); with it the launch brings kAccTileBytes of dynamic LDS
+__global__ __launch_bounds__(kBlock) void k_accumulate(const float4* results, uint32_t num_pixels, uint32_t batch, float* first_moment, float* second_moment, uint32_t pixel_major) {
+  extern __shared__ float4 accumulate_tiles[];
+  if (pixel_major) { accumulate_pixel_major(results, num_pixels, batch, first_moment, second_moment, accumulate_tiles); return; }
   for (uint32_t p = blockIdx.x * kBlock + threadIdx.x; p < num_pixels; p += gridDim.x * kBlock) {
     float r = first_moment[p], g = first_moment[num_pixels + p], b = first_moment[2 * num_pixels + p];
     float s = second_moment ? second_moment[p] : 0.0f;

@@ -40,7 +40,7 @@ struct WavefrontKernels {
   void (*generate_adaptive)(uint32_t grid, hipStream_t s, const DeviceScene& sc, const AdaptiveView& a, const AdaptivePass& pass, const PathQueue& q, float4* results,
                             uint32_t* count, const DeviceLens& lens, int cam);
   void (*trace)(uint32_t grid, size_t lds, hipStream_t s, const DeviceScene& sc, const PathQueue& q, const uint32_t* order, uint32_t* ctrl, uint64_t* counters,
-                uint32_t lds_nodes, bool single_level);
+                uint32_t lds_nodes, bool single_level, bool coherent);  // coherent: the waves hold rays that walk as one (trace_items<Q, true, true>; single-level scenes only)
   void (*sky_inscattering)(uint32_t grid, hipStream_t s, const DeviceScene& sc, const PathQueue& in, float4* results, const uint32_t* ctrl, uint32_t depth_const);
   void (*shade)(uint32_t grid, hipStream_t s, const DeviceScene& sc, const PathQueue& in, const PathQueue& out, const NeeQueue& nee, const ShadowQueue& sq, float4* results,
                 uint32_t* ctrl, uint32_t depth_const, uint64_t* counters, uint32_t ambient_reuse, const FusedResolve* fused_dev, uint32_t fused_flags,
@@ -81,7 +81,7 @@ struct WavefrontKernels {
   void (*clouds_march)(uint32_t grid, hipStream_t s, const DeviceScene& sc, const PathQueue& in, const CloudQueue& cq, uint32_t* ctrl, uint32_t depth_const);
   void (*clouds)(uint32_t grid, hipStream_t s, const DeviceScene& sc, const PathQueue& in, const CloudQueue& cq, float4* results, const uint32_t* ctrl, uint32_t depth_const);
   void (*trace_rays)(uint32_t grid, size_t lds, hipStream_t s, const DeviceScene& sc, uint32_t n, const float* origins, const float* dirs, const uint32_t* ignore, uint32_t* out,
-                     uint32_t* cursor, uint64_t* counters, uint32_t lds_nodes, bool single_level);
+                     uint32_t* cursor, uint64_t* counters, uint32_t lds_nodes, bool single_level, bool coherent);
   // every camera ray of `samples` sample ids of n pixels (device buffers; origin / dir float3, weight float), the invalid ones included (k_camera_rays)
   void (*camera_rays)(uint32_t grid, hipStream_t s, const DeviceScene& sc, const DeviceLens& lens, int cam, const uint32_t* pixels, uint32_t n, uint32_t first_sample,
                       uint32_t samples, float* origin, float* dir, float* weight);

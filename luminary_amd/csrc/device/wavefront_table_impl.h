@@ -12,9 +12,12 @@ namespace table {
 typedef void (*TraceKernel)(DeviceScene, PathQueue, const uint32_t*, uint32_t*, uint64_t*, uint32_t);
 typedef void (*ShadowKernel)(DeviceScene, ShadowQueue, const uint32_t*, uint32_t*, uint64_t*, uint32_t);
 typedef void (*TraceRaysKernel)(DeviceScene, uint32_t, const float*, const float*, const uint32_t*, uint32_t*, uint32_t*, uint64_t*, uint32_t);
-static TraceKernel trace_kernel(bool single) { return single ? k_trace<true> : static_cast<TraceKernel>(k_trace); }
+// (coherent: the single-level form for waves of rays that walk as one, the template's instance <true, true> - a single-level form, so it follows `single`)
+static TraceKernel trace_kernel(bool single, bool coherent = false) { return single ? (coherent ? k_trace<true, true> : k_trace<true>) : static_cast<TraceKernel>(k_trace); }
 static ShadowKernel shadow_kernel(bool single) { return single ? k_shadow_rays<true> : static_cast<ShadowKernel>(k_shadow_rays); }
-static TraceRaysKernel trace_rays_kernel(bool single) { return single ? k_trace_rays<true> : static_cast<TraceRaysKernel>(k_trace_rays); }
+static TraceRaysKernel trace_rays_kernel(bool single, bool coherent = false) {
+  return single ? (coherent ? k_trace_rays<true, true> : k_trace_rays<true>) : static_cast<TraceRaysKernel>(k_trace_rays);
+}
 
 static int set_ray_kernel_lds(size_t bytes) {
   hipError_t e = hipSuccess;
@@ -23,6 +26,8 @@ static int set_ray_kernel_lds(size_t bytes) {
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*) shadow_kernel(single != 0), hipFuncAttributeMaxDynamicSharedMemorySize, (int) bytes);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void*) trace_rays_kernel(single != 0), hipFuncAttributeMaxDynamicSharedMemorySize, (int) bytes);
   }
+  if (e == hipSuccess) e = hipFuncSetAttribute((const void*) trace_kernel(true, true), hipFuncAttributeMaxDynamicSharedMemorySize, (int) bytes);
+  if (e == hipSuccess) e = hipFuncSetAttribute((const void*) trace_rays_kernel(true, true), hipFuncAttributeMaxDynamicSharedMemorySize, (int) bytes);
   if (e == hipSuccess) e = hipFuncSetAttribute((const void*) k_trace_particles, hipFuncAttributeMaxDynamicSharedMemorySize, (int) bytes);
   return (int) e;
 }
@@ -56,8 +61,8 @@ static void camera_rays(uint32_t grid, hipStream_t s, const DeviceScene& sc, con
   hipLaunchKernelGGL(k, dim3(grid), dim3(kBlock), 0, s, sc, lens, pixels, n, first_sample, samples, origin, dir, weight);
 }
 static void trace(uint32_t grid, size_t lds, hipStream_t s, const DeviceScene& sc, const PathQueue& q, const uint32_t* order, uint32_t* ctrl, uint64_t* counters,
-                  uint32_t lds_nodes, bool single_level) {
-  hipLaunchKernelGGL(trace_kernel(single_level && single_level_scene(sc)), dim3(grid), dim3(kTraceBlock), lds, s, sc, q, order, ctrl, counters, lds_nodes);
+                  uint32_t lds_nodes, bool single_level, bool coherent) {
+  hipLaunchKernelGGL(trace_kernel(single_level && single_level_scene(sc), coherent), dim3(grid), dim3(kTraceBlock), lds, s, sc, q, order, ctrl, counters, lds_nodes);
 }
 static void sky_inscattering(uint32_t grid, hipStream_t s, const DeviceScene& sc, const PathQueue& in, float4* results, const uint32_t* ctrl, uint32_t depth_const) {
   hipLaunchKernelGGL(k_sky_inscattering, dim3(grid), dim3(kBlock), 0, s, sc, in, results, ctrl, depth_const);
@@ -144,8 +149,8 @@ static void clouds(uint32_t grid, hipStream_t s, const DeviceScene& sc, const Pa
   hipLaunchKernelGGL(k_clouds, dim3(grid), dim3(kBlock), 0, s, sc, in, cq, results, ctrl, depth_const);
 }
 static void trace_rays(uint32_t grid, size_t lds, hipStream_t s, const DeviceScene& sc, uint32_t n, const float* origins, const float* dirs, const uint32_t* ignore, uint32_t* out,
-                       uint32_t* cursor, uint64_t* counters, uint32_t lds_nodes, bool single_level) {
-  hipLaunchKernelGGL(trace_rays_kernel(single_level && single_level_scene(sc)), dim3(grid), dim3(kTraceBlock), lds, s, sc, n, origins, dirs, ignore, out, cursor, counters,
+                       uint32_t* cursor, uint64_t* counters, uint32_t lds_nodes, bool single_level, bool coherent) {
+  hipLaunchKernelGGL(trace_rays_kernel(single_level && single_level_scene(sc), coherent), dim3(grid), dim3(kTraceBlock), lds, s, sc, n, origins, dirs, ignore, out, cursor, counters,
                      lds_nodes);
 }
 static void guide(uint32_t grid, hipStream_t s, const DeviceScene& sc, const PathQueue& in, const uint32_t* ctrl, float* planes, uint32_t n) {

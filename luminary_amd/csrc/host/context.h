@@ -101,6 +101,8 @@ struct LumContext {
   int ambient_reuse = -1;         // -1 by flavour (fast: on), 0 off, 1 on (lumc_set_ambient_reuse; LUM_AMBIENT_REUSE)
   int single_level = -1;          // the ray kernels' single-level form on a scene of one hittable instance: -1 auto (on), 0 never, 1 when eligible (lumc_set_single_level; LUM_SINGLE_LEVEL)
   int plain_form = -1;            // k_shade's plain form on a scene that has nothing it leaves out (plain_scene, wavefront_table.h): -1 auto (on), 0 never, 1 when eligible (lumc_set_plain_form; LUM_PLAIN_FORM)
+  int pixel_major = -1;           // lumc_render's path slots: -1 auto (kPixelMajorAuto, core.hip), 0 sample-major, 1 pixel-major (lumc_set_pixel_major; LUM_PIXEL_MAJOR)
+  int coherent_first_hits = -1;   // the coherent form of the single-level closest-hit kernel for a pass's depth-0 launch: -1 auto (with pixel-major slots), 0 never, 1 when eligible - and then for lumc_trace_closest too (lumc_set_coherent_first_hits; LUM_COHERENT_FIRST_HITS)
   bool first_leaf_identity = false;  // leaf record 0 of the top level maps a ray onto itself (update_scene_tree): see single_level_allowed
   // The overlapped schedule (core.hip wavefront_depths, overlap_allowed): a depth's light queries run on `side_stream` beside the next depth's closest-hit pass.
   int overlap_lq = -1;            // -1 auto (kOverlapAuto), 0 never, 1 when allowed (lumc_set_overlap_light_query; LUM_OVERLAP_LQ)

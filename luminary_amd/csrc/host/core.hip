@@ -157,6 +157,8 @@ int lumc_context_create(int device_ordinal, LumContext** out) {
   if (const char* e = getenv("LUM_SINGLE_LEVEL")) ctx->single_level = atoi(e) != 0 ? 1 : 0;
   if (const char* e = getenv("LUM_PLAIN_FORM")) ctx->plain_form = atoi(e) != 0 ? 1 : 0;
   if (const char* e = getenv("LUM_OVERLAP_LQ")) ctx->overlap_lq = atoi(e) != 0 ? 1 : 0;
+  if (const char* e = getenv("LUM_PIXEL_MAJOR")) ctx->pixel_major = atoi(e) != 0 ? 1 : 0;
+  if (const char* e = getenv("LUM_COHERENT_FIRST_HITS")) ctx->coherent_first_hits = atoi(e) != 0 ? 1 : 0;
   if (const char* e = getenv("LUM_FUSED_RESOLVE")) ctx->fused_resolve = atoi(e) != 0 ? 1 : 0;
   if (const char* e = getenv("LUM_SHADE_GRID")) ctx->shade_grid_rounds = (uint32_t) atoi(e);
   if (const char* e = getenv("LUM_SOBOL_TABLE_RT")) ctx->sobol_table = atoi(e) != 0 ? 1 : 0;
@@ -265,7 +267,7 @@ static void first_hits(LumContext* ctx, hipStream_t stream, const DeviceScene& s
   const WavefrontKernels& wf = *ctx->wf;
   {
     Launch l(ctx, stream, LUMC_KERNEL_TRACE);
-    wf.trace(grid_persistent(ctx, N), ray_kernel_lds(ctx), stream, sc, ctx->work.queue[0], nullptr, ctx->d_ctrl.get(), ctx->d_counters.get(), ctx->lds_nodes, single_level_allowed(ctx));
+    wf.trace(grid_persistent(ctx, N), ray_kernel_lds(ctx), stream, sc, ctx->work.queue[0], nullptr, ctx->d_ctrl.get(), ctx->d_counters.get(), ctx->lds_nodes, single_level_allowed(ctx), false);
   }
   if (sc.particles_active) trace_particles(ctx, stream, ctx->work.queue[0], ctx->d_ctrl.get(), N);
   if (sc.ocean_active) {
@@ -353,18 +355,35 @@ static DepthBuffers depth_buffers(LumContext* ctx, ResolveScheme scheme, uint32_
 }
 
 // The closest-hit launch of a depth, alone: the overlapped schedule issues it a depth early.
-static void trace_depth(LumContext* ctx, hipStream_t stream, const DeviceScene& sc, const DepthBuffers& d, const uint32_t* order, uint32_t N) {
+static void trace_depth(LumContext* ctx, hipStream_t stream, const DeviceScene& sc, const DepthBuffers& d, const uint32_t* order, uint32_t N, bool coherent = false) {
   Launch l(ctx, stream, LUMC_KERNEL_TRACE);
-  ctx->wf->trace(grid_persistent(ctx, N), ray_kernel_lds(ctx), stream, sc, d.cur, order, d.ctrl, ctx->d_counters.get(), ctx->lds_nodes, single_level_allowed(ctx));
+  ctx->wf->trace(grid_persistent(ctx, N), ray_kernel_lds(ctx), stream, sc, d.cur, order, d.ctrl, ctx->d_counters.get(), ctx->lds_nodes, single_level_allowed(ctx), coherent);
+}
+
+// The pass's slot order (lumc_render says what it is; the adaptive and the undersampling passes have their own) and, from it, the form of the depth-0 closest-hit
+// launch. Pixel-major slots (kernels.h, top) put the sample ids of a pixel side by side, so that a wave of that launch holds the camera rays of one pixel (at 64 ids
+// per pass) instead of one ray of 64 pixels; the coherent form of the single-level kernel (dev_trace.h trace_items<Q, true, true>) lets such a wave visit a node as
+// one. A path's arithmetic does not depend on its slot, every result slot has one writer, the coherent form visits what the plain one visits: the frame moments and
+// the counters keep their bits. kPixelMajorAuto, kCoherentAuto: what mode -1 means - decided by measurement (profiles/first_depth_ab.txt).
+constexpr bool kPixelMajorAuto = true, kCoherentAuto = true;
+static bool pixel_major_wanted(const LumContext* ctx) { return ctx->pixel_major < 0 ? kPixelMajorAuto : ctx->pixel_major != 0; }
+// `forced`: asked for by name (mode 1), whatever the slot order - what lumc_trace_closest goes by, whose rays are the caller's
+static bool coherent_eligible(const LumContext* ctx) { return ctx->has_scene && single_level_allowed(ctx) && single_level_scene(ctx->scene); }
+static bool coherent_forced(const LumContext* ctx) { return ctx->coherent_first_hits == 1 && coherent_eligible(ctx); }
+// Auto takes the form only where a wave's 64 slots ARE one pixel's rays: pixel-major slots, the thin lens (the physical camera appends only the rays that left the
+// lens, so its queue is compacted and its waves straddle pixels - there a wave that waits for all its lanes before it refills has little to gain and stragglers to
+// wait for). The default rests on one scene, the hall; nothing else of one instance was measured.
+static bool coherent_first_hits(const LumContext* ctx, bool pixel_major) {
+  return coherent_forced(ctx) || (ctx->coherent_first_hits < 0 && kCoherentAuto && pixel_major && ctx->camera == kCamThinLens && coherent_eligible(ctx));
 }
 
 // The closest hits of a depth; with kResolveReuse they also answer the ambient samples of the depth before, which is resolved here.
-static int closest_hits(LumContext* ctx, hipStream_t stream, const DeviceScene& sc, ResolveScheme scheme, const DepthBuffers& d, uint32_t N) {
+static int closest_hits(LumContext* ctx, hipStream_t stream, const DeviceScene& sc, ResolveScheme scheme, const DepthBuffers& d, uint32_t N, bool coherent_depth0 = false) {
   const WavefrontKernels& wf = *ctx->wf;
   // camera rays leave k_generate in pixel order, which is as coherent as rays get; later depths are sorted on request
   const uint32_t* order = nullptr;
   if (ctx->sort.mode >= 1 && d.depth >= 1 && sort_closest_rays(ctx, stream, d.cur, d.ctrl, N, &order)) return 1;
-  trace_depth(ctx, stream, sc, d, order, N);
+  trace_depth(ctx, stream, sc, d, order, N, coherent_depth0 && d.depth == 0u && order == nullptr);
   if (scheme == kResolveReuse && d.depth > 0) {  // the previous depth's resolve: ambient samples answered by the pass above; what it cannot answer is traced (the control words of the fog's visibility pass: no fog here) and resolved after
     uint32_t* prev = d.ctrl - kCtlStride;
     {
@@ -498,7 +517,8 @@ static void volume_bounce(LumContext* ctx, hipStream_t stream, const DeviceScene
 
 // The depth loop of one wavefront pass over the paths k_generate* left in queue[0] (at most N of them, counted on the device).
 // `first_sample`, `sample_count`: the pass's sample ids when they are one contiguous range for every pixel (lumc_render), 0 otherwise.
-static int wavefront_depths(LumContext* ctx, hipStream_t stream, uint32_t N, uint32_t first_sample = 0, uint32_t sample_count = 0) {
+// `coherent`: the depth-0 closest-hit launch takes the coherent form (coherent_first_hits).
+static int wavefront_depths(LumContext* ctx, hipStream_t stream, uint32_t N, uint32_t first_sample = 0, uint32_t sample_count = 0, bool coherent = false) {
   DeviceScene sc = ctx->scene;
   const uint32_t max_depth = sc.max_ray_depth;
   prepare_sobol_table(ctx, stream, sc, first_sample, sample_count);
@@ -518,7 +538,7 @@ static int wavefront_depths(LumContext* ctx, hipStream_t stream, uint32_t N, uin
   bool traced = false;  // this depth's closest-hit launch was issued with the depth before
   for (uint32_t depth = 0; depth <= max_depth; depth++) {
     const DepthBuffers d = depth_buffers(ctx, scheme, depth, max_depth);
-    if (!traced && closest_hits(ctx, stream, sc, scheme, d, N)) return 1;  // (overlapped: kResolvePlain or kResolveFused, no sort - closest_hits is that one launch)
+    if (!traced && closest_hits(ctx, stream, sc, scheme, d, N, coherent)) return 1;  // (overlapped: kResolvePlain or kResolveFused, no sort - closest_hits is that one launch)
     traced = false;
     media_passes(ctx, stream, sc, d, N);
     shade_depth(ctx, stream, sc, scheme, d, N);
@@ -562,16 +582,18 @@ int lumc_render(LumContext* ctx, uint32_t first_sample, uint32_t num_samples, ui
   for (uint32_t done = 0; done < num_samples; done += samples_per_pass) {
     const uint32_t batch = std::min(samples_per_pass, num_samples - done);
     const uint32_t N = P * batch;
-    PassParams pp{ctx->d_pixels.get(), P, batch, first_sample + done};
+    const bool pixel_major = pixel_major_wanted(ctx);
+    PassParams pp{ctx->d_pixels.get(), P, batch, first_sample + done, pixel_major ? 1u : 0u};
     HIP_TRY(ctx, hipMemsetAsync(ctx->d_ctrl.get(), 0, sizeof(uint32_t) * kCtlStride * (max_depth + 2), stream));
     {
       Launch l(ctx, stream, LUMC_KERNEL_GENERATE);
       ctx->wf->generate(grid_for(N), stream, sc, pp, ctx->work.queue[0], ctx->work.results, ctx->d_ctrl.get() + kCtlPaths, ctx->lens, ctx->camera);
     }
-    if (wavefront_depths(ctx, stream, N, first_sample + done, batch)) return 1;
+    // (a wave of the depth-0 launch takes 64 consecutive slots: one pixel's where the batch is a multiple of 64)
+    if (wavefront_depths(ctx, stream, N, first_sample + done, batch, coherent_first_hits(ctx, pixel_major && batch % 64u == 0u))) return 1;
     {
       Launch l(ctx, stream, LUMC_KERNEL_ACCUMULATE);
-      hipLaunchKernelGGL(k_accumulate, dim3(grid_for(P)), dim3(kBlock), 0, stream, (const float4*) ctx->work.results, P, batch, d_fm, d_sm);
+      hipLaunchKernelGGL(k_accumulate, dim3(grid_for(P)), dim3(kBlock), pixel_major ? kAccTileBytes : 0u, stream, (const float4*) ctx->work.results, P, batch, d_fm, d_sm, pixel_major ? 1u : 0u);
     }
     HIP_TRY(ctx, hipGetLastError());
   }
@@ -1219,7 +1241,7 @@ int lumc_trace_closest(LumContext* ctx, uint32_t n, const float* d_origins, cons
   HIP_TRY(ctx, hipMemsetAsync(cursor, 0, sizeof(uint32_t), stream));  // the work cursor of trace_items (dev_trace.h)
   Launch l(ctx, stream, LUMC_KERNEL_TRACE);
   ctx->wf->trace_rays(grid_persistent(ctx, n), ray_kernel_lds(ctx), stream, ctx->scene, n, d_origins, d_dirs, d_ignore, d_out, cursor, ctx->d_counters.get(),
-                      ctx->lds_nodes, single_level_allowed(ctx));
+                      ctx->lds_nodes, single_level_allowed(ctx), coherent_forced(ctx));
   HIP_TRY(ctx, hipGetLastError());
   return 0;
 }
@@ -1476,6 +1498,19 @@ int lumc_set_overlap_light_query(LumContext* ctx, int mode) {
 }
 // what the next pass will do for the uploaded scene (a fused resolve that finds no room for its buffers falls back to the reuse scheme and the serial order)
 int lumc_get_overlap_light_query(const LumContext* ctx) { return (ctx && ctx->has_scene && overlap_allowed(ctx, wanted_scheme(ctx))) ? 1 : 0; }
+int lumc_set_pixel_major(LumContext* ctx, int mode) {
+  if (!ctx || mode < -1 || mode > 1) { if (ctx) ctx->error = "lumc_set_pixel_major: -1 (auto), 0 (sample-major slots) or 1 (pixel-major slots)"; return 1; }
+  ctx->pixel_major = mode;
+  return 0;
+}
+int lumc_get_pixel_major(const LumContext* ctx) { return (ctx && pixel_major_wanted(ctx)) ? 1 : 0; }
+int lumc_set_coherent_first_hits(LumContext* ctx, int mode) {
+  if (!ctx || mode < -1 || mode > 1) { if (ctx) ctx->error = "lumc_set_coherent_first_hits: -1 (auto), 0 (never) or 1 (when the scene is eligible)"; return 1; }
+  ctx->coherent_first_hits = mode;
+  return 0;
+}
+// what the depth-0 launch of the next lumc_render will be for the uploaded scene, at a batch that is a multiple of 64
+int lumc_get_coherent_first_hits(const LumContext* ctx) { return (ctx && coherent_first_hits(ctx, pixel_major_wanted(ctx))) ? 1 : 0; }
 int lumc_overlap_registers_fit(uint32_t ray_kernel_regs, uint32_t light_query_regs) { return overlap_registers_fit(ray_kernel_regs, light_query_regs) ? 1 : 0; }
 int lumc_get_flavour(const LumContext* ctx) { return (ctx && ctx->wf == wavefront_kernels_exact()) ? LUMC_FLAVOUR_EXACT : LUMC_FLAVOUR_FAST; }
 

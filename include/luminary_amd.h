@@ -601,6 +601,31 @@ LUMINARY_API LuminaryResult luminary_ext_get_denoiser(LuminaryHost* host, Lumina
 /* The denoised mean radiance of the full frame (rgb interleaved, width*height*3 floats), whether or not the denoiser is enabled for the outputs;
  * luminary_ext_get_radiance keeps returning the undenoised mean. */
 LUMINARY_API LuminaryResult luminary_ext_get_denoised(LuminaryHost* host, float* rgb, uint32_t width, uint32_t height);
+/* Firefly rejection (include/lum_core.h lumc_set_firefly_buckets / lumc_firefly_resolve; csrc/host/firefly.h): every sample id is also added to
+ * one of `buckets` per-pixel sums (id mod buckets; 12 bytes per pixel and bucket on the device), and the result image takes, for a pixel whose bucket means disagree,
+ * the mean of the buckets that are left after the Gini coefficient of their luminances has trimmed the darkest and the brightest; a bucket with a NaN or Inf is
+ * left out. When enabled the resolve runs before the denoiser, on beauty images of the whole frame in the default shading mode (where the denoiser and bloom
+ * run); never on the undersampling preview. An accumulation driven by adaptive sampling is not resolved (frames_skipped counts those images). Off by default.
+ * A change of `enabled` or of `buckets` restarts the integration - unlike the denoiser: the buckets must see every id. The call is refused with
+ * LUMINARY_ERROR_INVALID_API_ARGUMENT, with the reason in the log, for buckets outside 4 ... 16 and when the host renders on more than one device slot.
+ * luminary_ext_get_radiance and luminary_ext_get_accumulators keep returning the plain sums; luminary_ext_get_denoised follows the outputs: with the switch on
+ * it denoises the resolved image. The reference's `CAMERA FIREFLYC` key of .lum v4 files stays unread, as in the reference. */
+typedef struct LuminaryFireflySettings {
+  bool enabled;     /* false */
+  uint32_t buckets; /* 8: 4 ... 16 */
+} LuminaryFireflySettings;
+typedef struct LuminaryFireflyStats {
+  uint64_t frames_resolved, frames_skipped;                   /* result images resolved / left alone under adaptive sampling, since the host was created */
+  uint32_t last_rewritten, last_trimmed, last_nonfinite;      /* of the last resolve: pixels written, buckets left out of a mean, pixels with a non-finite bucket */
+  uint32_t buckets;                                           /* buckets the main device holds (0: none) */
+  uint64_t bytes;                                             /* ... and their bytes */
+} LuminaryFireflyStats;
+LUMINARY_API LuminaryResult luminary_ext_set_firefly_rejection(LuminaryHost* host, const LuminaryFireflySettings* settings);
+LUMINARY_API LuminaryResult luminary_ext_get_firefly_rejection(LuminaryHost* host, LuminaryFireflySettings* settings);
+/* The mean radiance of the full frame after the resolve (rgb interleaved, width*height*3 floats), whatever the outputs do: no local error minimisation, no
+ * denoiser. Needs the switch on and at least one sample. */
+LUMINARY_API LuminaryResult luminary_ext_get_robust_radiance(LuminaryHost* host, float* rgb, uint32_t width, uint32_t height);
+LUMINARY_API LuminaryResult luminary_ext_get_firefly_stats(LuminaryHost* host, LuminaryFireflyStats* out);
 /* out[0] closest-hit rays, [1] shadow rays, [2] light-BVH queries, [3] shaded vertices, [4] BVH nodes visited, [5] triangles tested. */
 LUMINARY_API LuminaryResult luminary_ext_get_ray_counters(LuminaryHost* host, uint64_t out[8]);
 /* The lumc context of this host (include/lum_core.h), for callers that drive passes themselves. */

@@ -202,6 +202,17 @@ class MeshMorphStats(C.Structure):
                 ("seconds", C.c_double), ("seconds_upload", C.c_double), ("seconds_morph", C.c_double), ("host_materialisations", C.c_uint64)]
 
 
+class FireflySettings(C.Structure):
+    """include/luminary_amd.h LuminaryFireflySettings (defaults: off, 8 buckets)."""
+    _fields_ = [("enabled", C.c_bool), ("buckets", C.c_uint32)]
+
+
+class FireflyStats(C.Structure):
+    """LuminaryFireflyStats"""
+    _fields_ = [("frames_resolved", C.c_uint64), ("frames_skipped", C.c_uint64), ("last_rewritten", C.c_uint32), ("last_trimmed", C.c_uint32),
+                ("last_nonfinite", C.c_uint32), ("buckets", C.c_uint32), ("bytes", C.c_uint64)]
+
+
 class ShutterStats(C.Structure):
     """LuminaryShutterStats"""
     _fields_ = [("renders", C.c_uint64), ("slices", C.c_uint64), ("last_moved_meshes", C.c_uint32), ("last_moved_instances", C.c_uint32), ("last_camera_moved", C.c_uint32),
@@ -752,6 +763,33 @@ class Host:
         out = np.zeros((height, width, 3), dtype=np.float32)
         _call("luminary_ext_get_denoised", self._h, out.ctypes.data_as(C.c_void_p), C.c_uint32(width), C.c_uint32(height))
         return out
+
+    def get_firefly_rejection(self):
+        """luminary_ext_get_firefly_rejection"""
+        f = FireflySettings()
+        _call("luminary_ext_get_firefly_rejection", self._h, C.byref(f))
+        return f
+
+    def set_firefly_rejection(self, settings=None, **fields):
+        """luminary_ext_set_firefly_rejection: the given settings, or the current ones with `fields` changed (set_firefly_rejection(enabled=True)). A change restarts
+        the integration."""
+        f = settings if settings is not None else self.get_firefly_rejection()
+        for k, v in fields.items():
+            setattr(f, k, v)
+        _call("luminary_ext_set_firefly_rejection", self._h, C.byref(f))
+
+    def robust_radiance(self, width, height):
+        """luminary_ext_get_robust_radiance: the mean radiance [H, W, 3] of the accumulated frame after the firefly resolve."""
+        import numpy as np
+        out = np.zeros((height, width, 3), dtype=np.float32)
+        _call("luminary_ext_get_robust_radiance", self._h, out.ctypes.data_as(C.c_void_p), C.c_uint32(width), C.c_uint32(height))
+        return out
+
+    def firefly_stats(self):
+        """luminary_ext_get_firefly_stats, as a dict."""
+        s = FireflyStats()
+        _call("luminary_ext_get_firefly_stats", self._h, C.byref(s))
+        return {name: getattr(s, name) for name, _ in s._fields_}
 
     def ray_counters(self):
         out = (C.c_uint64 * 8)()

@@ -146,6 +146,32 @@ def skin_host(rest_positions, rest_normals, bone_ids, weights, bones):
     return op, on, pk
 
 
+class FireflyStats(C.Structure):
+    """LumFireflyStats"""
+    _fields_ = [("buckets", C.c_uint32), ("reserved", C.c_uint32), ("bytes", C.c_uint64), ("resolves", C.c_uint64), ("last_rewritten", C.c_uint32),
+                ("last_trimmed", C.c_uint32), ("last_nonfinite", C.c_uint32), ("samples", C.c_uint32)]
+
+
+def firefly_resolve_host(sums, counts, image):
+    """lumc_firefly_resolve_host, no device needed: the host twin of the firefly resolve. sums [K, 3, P] float32 bucket sums, counts [K] ids per bucket, image
+    [3, P] (or [3, H, W]) the planar result image. Returns (image after the resolve - a copy, same shape -, (pixels rewritten, buckets trimmed, pixels with a
+    non-finite bucket)); raises ValueError where the twin refuses (K outside 4 ... 16, counts all zero)."""
+    fn = _lib().lumc_firefly_resolve_host
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]
+    s = np.ascontiguousarray(sums, dtype=np.float32)
+    n = np.ascontiguousarray(counts, dtype=np.uint32).reshape(-1)
+    out = np.ascontiguousarray(image, dtype=np.float32).copy()
+    K = len(n)
+    pixels = out.size // 3
+    if s.ndim < 2 or s.shape[0] != K or s.size != K * 3 * pixels:
+        raise ValueError("firefly_resolve_host: sums [K, 3, P], counts [K] and image [3, P] do not fit")
+    stats = (C.c_uint32 * 3)()
+    if fn(s.ctypes.data, n.ctypes.data, K, pixels, out.ctypes.data, C.addressof(stats)) != 0:
+        raise ValueError("lumc_firefly_resolve_host refused its arguments")
+    return out, tuple(int(x) for x in stats)
+
+
 class ShutterStats(C.Structure):
     """LumShutterStats"""
     _fields_ = [("slices", C.c_uint64), ("last_meshes", C.c_uint32), ("last_launches", C.c_uint32), ("last_bytes_uploaded", C.c_uint64), ("seconds", C.c_double)]
@@ -858,6 +884,41 @@ class Core:
     def mesh_morph_stats(self):
         out = MeshMorphStats()
         self._call("lumc_mesh_morph_stats", C.byref(out))
+        return out
+
+    # ---- firefly rejection (lumc_set_firefly_buckets, lumc_firefly_resolve) ----
+    def set_firefly_buckets(self, buckets):
+        """lumc_set_firefly_buckets: 0 off (default), 4 ... 16 median-of-means buckets beside the accumulators (12 bytes per pixel each); clears the accumulators."""
+        self._call("lumc_set_firefly_buckets", C.c_uint32(buckets))
+        self._firefly_buckets = int(buckets)
+
+    def buckets(self):
+        """lumc_download_buckets: (sums [K, 3, num_pixels] float32, counts [K] uint32)."""
+        K = getattr(self, "_firefly_buckets", 0)
+        sums = np.zeros((max(K, 1), 3, self.num_pixels), dtype=np.float32)
+        counts = np.zeros(max(K, 1), dtype=np.uint32)
+        self._call("lumc_download_buckets", sums.ctypes.data_as(C.c_void_p), counts.ctypes.data_as(C.c_void_p))
+        return sums, counts
+
+    def upload_buckets(self, sums=None, counts=None):
+        """lumc_upload_buckets: the inverse of buckets(); either part may be None."""
+        K = getattr(self, "_firefly_buckets", 0)
+        s = None if sums is None else np.ascontiguousarray(sums, dtype=np.float32)
+        n = None if counts is None else np.ascontiguousarray(counts, dtype=np.uint32)
+        if (s is not None and s.size != K * 3 * self.num_pixels) or (n is not None and n.size != K):
+            raise ValueError("upload_buckets: sums [K, 3, num_pixels], counts [K]")
+        self._call("lumc_upload_buckets", C.c_void_p(0 if s is None else s.ctypes.data), C.c_void_p(0 if n is None else n.ctypes.data))
+
+    def firefly_resolve(self):
+        """lumc_firefly_resolve in place on the context's result image (generate_result wrote it); returns it, [3, H, W]."""
+        self._call("lumc_firefly_resolve", C.c_void_p(0), C.c_void_p(0))
+        out = np.zeros((3, self.height, self.width), dtype=np.float32)
+        self._call("lumc_download_result_image", out.ctypes.data_as(C.c_void_p))
+        return out
+
+    def firefly_stats(self):
+        out = FireflyStats()
+        self._call("lumc_firefly_stats", C.byref(out))
         return out
 
     def mesh_shutter_key(self, mesh, which):

@@ -125,6 +125,9 @@ struct LuminaryHost {
   bool adaptive_active = false;      // the accumulation is driven by lumc_adaptive_* (luminary_ext_render with adaptive sampling enabled)
   LuminaryDenoiserSettings denoiser = {false, 4u, 5u, 4.0f, 128.0f, 1.0f};  // luminary_ext_set_denoiser
   bool guides_valid = false;         // the main context holds the denoiser's guides of the current accumulation
+  LuminaryFireflySettings firefly = {false, 8u};  // luminary_ext_set_firefly_rejection
+  uint32_t core_firefly = 0;         // buckets the main context holds (sync_firefly): 0 while the switch is off or the frame is tiled over several devices
+  uint64_t firefly_resolved = 0, firefly_skipped = 0;  // result images resolved / left alone because adaptive sampling drives the accumulation
   bool hdri_origin_pending = true;   // the next scene build re-bakes the sky panorama from the camera's position (SCENE_DIRTY_FLAG_HDRI)
   lum::OutputStore outputs;
   double render_seconds = 0.0;
@@ -424,6 +427,18 @@ LuminaryResult set_camera(LuminaryHost* h, LumContext* core) {
   return LUMINARY_SUCCESS;
 }
 
+// The main context holds the buckets of luminary_ext_set_firefly_rejection while it renders the whole accumulation alone. (The setter refuses a host with several
+// enabled devices; one enabled later switches the buckets off here, and post_process then has nothing to resolve.)
+int sync_firefly(LuminaryHost* h) {
+  uint32_t others = 0;  // (enabled_slots, below: the main slot and every other enabled one)
+  for (uint32_t i = 0; i < h->devices.size(); i++) others += (i != h->main_slot && h->devices[i].enabled) ? 1u : 0u;
+  const uint32_t want = (h->firefly.enabled && others == 0) ? h->firefly.buckets : 0u;
+  if (want == h->core_firefly) return 0;
+  if (lumc_set_firefly_buckets(h->core, want)) { std::fprintf(stderr, "[luminary_amd] %s\n", lumc_last_error(h->core)); return 1; }
+  h->core_firefly = want;
+  return 0;
+}
+
 LuminaryResult ensure_core(LuminaryHost* h) {
   if (!h->core) {
     if (lumc_context_create(h->device_ordinal, &h->core)) {
@@ -441,6 +456,7 @@ LuminaryResult ensure_core(LuminaryHost* h) {
     lumc_set_instance_update(h->core, h->instance_update_mode);
     lumc_set_mesh_refit_in_place(h->core, h->refit_in_place);
     lumc_set_light_refit(h->core, h->light_refit_max_cost_growth);
+    if (sync_firefly(h)) return LUMINARY_ERROR_CUDA;
     if (update_context_scene(h, h->core, h->core_dirty, &h->core_skin_seen)) { std::fprintf(stderr, "[luminary_amd] %s\n", lumc_last_error(h->core)); h->core_dirty = LUMC_DIRTY_ALL; return LUMINARY_ERROR_CUDA; }
     h->core_dirty = 0;
     h->core_scene_valid = true;
@@ -1464,11 +1480,21 @@ int denoise_result(LuminaryHost* h) {
   return lumc_denoise(h->core, &dp, nullptr, nullptr);
 }
 
+// The firefly resolve on the main context's result image (lumc_firefly_resolve), where the main context holds buckets (sync_firefly).
+int firefly_result(LuminaryHost* h) {
+  if (!h->core_firefly || h->partition_n > 1) return 0;
+  if (h->adaptive_active) { h->firefly_skipped++; return 0; }  // the adaptive sampler's passes fill no buckets: skipped and counted
+  if (lumc_firefly_resolve(h->core, nullptr, nullptr)) return 1;
+  h->firefly_resolved++;
+  return 0;
+}
+
 int post_process(LuminaryHost* h, PreviewState preview) {
   const LuminaryRendererSettings& st = h->scene.settings;
   if (st.shading_mode != LUMINARY_SHADING_MODE_DEFAULT || st.adaptive_sampling_output_mode != LUMINARY_ADAPTIVE_SAMPLING_OUTPUT_MODE_BEAUTY) return 0;
   if (!(st.region_width >= 1.0f && st.region_height >= 1.0f)) return 0;
-  if (h->denoiser.enabled && preview.stage == 0 && denoise_result(h)) return 1;  // result image -> denoise -> bloom; never the coarse preview images
+  if (preview.stage == 0 && firefly_result(h)) return 1;  // result image -> firefly resolve -> denoise -> bloom; never the coarse preview images
+  if (h->denoiser.enabled && preview.stage == 0 && denoise_result(h)) return 1;
   const float blend = h->scene.camera.bloom_blend;
   if (!(blend > 0.0f)) return 0;  // device_post_update, device_post.c:186-202
   const LumDeviceSceneView& v = h->device_scene.view;
@@ -2055,7 +2081,7 @@ LuminaryResult luminary_ext_get_denoised(LuminaryHost* host, float* rgb, uint32_
   const LumDeviceSceneView& v = host->device_scene.view;
   if (width != v.width || height != v.height) return LUMINARY_ERROR_INVALID_API_ARGUMENT;
   if (host->partition_n > 1) { const LuminaryResult ra = assemble_partition(host); if (ra) return ra; }
-  if (lumc_generate_result(host->core, 0, 0, host->adaptive_active ? 0u : host->accumulated_samples, 1.0f, nullptr, nullptr, nullptr) || denoise_result(host)) {
+  if (lumc_generate_result(host->core, 0, 0, host->adaptive_active ? 0u : host->accumulated_samples, 1.0f, nullptr, nullptr, nullptr) || firefly_result(host) || denoise_result(host)) {  // (the outputs' chain up to bloom)
     std::fprintf(stderr, "[luminary_amd] %s\n", lumc_last_error(host->core));
     return LUMINARY_ERROR_CUDA;
   }
@@ -2063,6 +2089,60 @@ LuminaryResult luminary_ext_get_denoised(LuminaryHost* host, float* rgb, uint32_
   if (lumc_download_result_image(host->core, planes.data())) return LUMINARY_ERROR_CUDA;
   for (size_t p = 0; p < host->num_pixels; p++)
     for (int c = 0; c < 3; c++) rgb[3 * p + c] = planes[(size_t) c * host->num_pixels + p];
+  return LUMINARY_SUCCESS;
+}
+// ---- firefly rejection (include/luminary_amd.h LuminaryFireflySettings) ----
+LuminaryResult luminary_ext_set_firefly_rejection(LuminaryHost* host, const LuminaryFireflySettings* settings) {
+  CHECK_NULL(host); CHECK_NULL(settings);
+  ApiLock lock(host);
+  auto refuse = [&](const std::string& why) {
+    host->log.push_back("luminary_ext_set_firefly_rejection: " + why);
+    std::fprintf(stderr, "[luminary_amd] %s\n", host->log.back().c_str());
+    return LUMINARY_ERROR_INVALID_API_ARGUMENT;
+  };
+  if (settings->buckets < 4 || settings->buckets > 16) return refuse(std::to_string(settings->buckets) + " buckets (4 ... 16)");
+  if (settings->enabled && enabled_slots(host).size() > 1) return refuse("the host renders on more than one device slot, and the gather of a tiled frame carries no bucket planes");
+  const bool changed = settings->enabled != host->firefly.enabled || (settings->enabled && settings->buckets != host->firefly.buckets);
+  host->firefly = *settings;
+  if (changed) {  // the buckets must see every id: the integration restarts, and the render loop sets the pixel set up again
+    invalidate(host, 0);
+    host->num_pixels = 0;
+  }
+  return LUMINARY_SUCCESS;
+}
+LuminaryResult luminary_ext_get_firefly_rejection(LuminaryHost* host, LuminaryFireflySettings* settings) {
+  CHECK_NULL(host); CHECK_NULL(settings);
+  ApiLock lock(host);
+  *settings = host->firefly;
+  return LUMINARY_SUCCESS;
+}
+LuminaryResult luminary_ext_get_robust_radiance(LuminaryHost* host, float* rgb, uint32_t width, uint32_t height) {
+  CHECK_NULL(host); CHECK_NULL(rgb);
+  ApiLock lock(host);
+  if (!host->core || !host->pixels_all || host->num_pixels == 0 || host->accumulated_samples == 0 || !host->core_firefly || host->partition_n > 1) return LUMINARY_ERROR_API_EXCEPTION;
+  const LumDeviceSceneView& v = host->device_scene.view;
+  if (width != v.width || height != v.height) return LUMINARY_ERROR_INVALID_API_ARGUMENT;
+  if (lumc_generate_result(host->core, 0, 0, host->adaptive_active ? 0u : host->accumulated_samples, 1.0f, nullptr, nullptr, nullptr) || firefly_result(host)) {
+    std::fprintf(stderr, "[luminary_amd] %s\n", lumc_last_error(host->core));
+    return LUMINARY_ERROR_CUDA;
+  }
+  std::vector<float> planes(3 * (size_t) host->num_pixels);
+  if (lumc_download_result_image(host->core, planes.data())) return LUMINARY_ERROR_CUDA;
+  for (size_t p = 0; p < host->num_pixels; p++)
+    for (int c = 0; c < 3; c++) rgb[3 * p + c] = planes[(size_t) c * host->num_pixels + p];
+  return LUMINARY_SUCCESS;
+}
+LuminaryResult luminary_ext_get_firefly_stats(LuminaryHost* host, LuminaryFireflyStats* out) {
+  CHECK_NULL(host); CHECK_NULL(out);
+  ApiLock lock(host);
+  std::memset(out, 0, sizeof(*out));
+  out->frames_resolved = host->firefly_resolved; out->frames_skipped = host->firefly_skipped;
+  if (host->core && host->core_firefly) {
+    LumFireflyStats st;
+    if (lumc_firefly_stats(host->core, &st)) return LUMINARY_ERROR_CUDA;
+    out->last_rewritten = st.last_rewritten; out->last_trimmed = st.last_trimmed; out->last_nonfinite = st.last_nonfinite;
+    out->buckets = st.buckets; out->bytes = st.bytes;
+  }
   return LUMINARY_SUCCESS;
 }
 LuminaryResult luminary_ext_get_ray_counters(LuminaryHost* host, uint64_t out[8]) {

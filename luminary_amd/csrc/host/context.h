@@ -1,5 +1,5 @@
 // The host layer's context and the helpers its translation units share. Private to csrc/host: core.hip (the context, the work buffers, the render schedule, the
-// adaptive sampler, the output chain and the ray queries, with the flavour-neutral kernels of kernels_shared.h), scene_device.hip (the scene on the device, with the
+// adaptive sampler, the output chain, the firefly buckets' entry points and the ray queries, with the flavour-neutral kernels of kernels_shared.h), scene_device.hip (the scene on the device, with the
 // kernels of kernels_scene.h), ray_sort.hip, multi_gpu.hip. The context owns its device memory through DeviceBuffer members (device_buffer.h): deleting it frees them.
 // Its other pointers - DeviceScene, the work buffers' arrays (work_layout.h) - are views into those buffers. kernels.h is not included, so a unit that includes
 // this header gets none of the flavoured kernels (their device symbols - the sampler's seed table, the phase counters - exist per translation unit).
@@ -19,6 +19,7 @@
 #include "bvh_build.h"
 #include "bvh_refit.h"
 #include "device_buffer.h"
+#include "firefly.h"
 #include "instance_update.h"
 #include "light_refit.h"
 #include "mesh_deform.h"
@@ -132,6 +133,7 @@ struct LumContext {
   uint32_t num_pixels = 0;
   uint64_t pixels_hash = 0;       // of the pixel list in its order (lumc_set_pixels): the tile gather checks that the set IS the share of the deal it assumes
   DeviceBuffer<float> d_first_moment, d_second_moment;
+  FireflyBuckets firefly;  // median-of-means buckets beside the accumulators (lumc_set_firefly_buckets; firefly.hip)
   struct Work : WorkBuffers { DeviceBuffer<char> block; } work;  // the work buffers, laid out for work.capacity paths (work_layout.h lay_out_work)
   uint32_t particle_lds_nodes = 0;
   DeviceBuffer<float> d_frame_output;  // display-referred planes of the output chain [3 * W * H]

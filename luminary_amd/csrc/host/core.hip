@@ -209,12 +209,17 @@ int lumc_set_pixels(LumContext* ctx, const uint32_t* pixels, uint32_t num_pixels
   if (!pixels) num_pixels = ctx->scene.width * ctx->scene.height;
   ctx->adaptive = LumContext::Adaptive();
   ctx->d_pixels.reset(); ctx->d_first_moment.reset(); ctx->d_second_moment.reset();
+  ctx->firefly.planes.reset(); ctx->firefly.pixels = 0; ctx->firefly.counts = FireflyCounts{};
   ctx->num_pixels = num_pixels;
   ctx->pixels_hash = pixel_list_hash(pixels, num_pixels);  // what lumc_frame_gather checks the set against (a null list = the frame in row-major order)
   if (num_pixels == 0) return 0;
   HIP_TRY(ctx, ctx->d_pixels.assign(pixels, num_pixels));  // (no list: the frame in row-major order, and no buffer)
   HIP_TRY(ctx, ctx->d_first_moment.resize(3 * (size_t) num_pixels));
   HIP_TRY(ctx, ctx->d_second_moment.resize(num_pixels));
+  if (ctx->firefly.K) {  // the buckets follow the pixel set
+    ctx->firefly.pixels = num_pixels;
+    HIP_TRY(ctx, ctx->firefly.planes.resize((size_t) ctx->firefly.K * 3 * num_pixels));
+  }
   return lumc_clear_accumulators(ctx);
 }
 
@@ -222,6 +227,8 @@ int lumc_clear_accumulators(LumContext* ctx) {
   if (!ctx || !ctx->d_first_moment) return 1;
   HIP_TRY(ctx, hipMemset(ctx->d_first_moment.get(), 0, sizeof(float) * 3 * (size_t) ctx->num_pixels));
   HIP_TRY(ctx, hipMemset(ctx->d_second_moment.get(), 0, sizeof(float) * (size_t) ctx->num_pixels));
+  if (ctx->firefly.planes) HIP_TRY(ctx, hipMemset(ctx->firefly.planes.get(), 0, sizeof(float) * ctx->firefly.planes.count()));
+  ctx->firefly.counts = FireflyCounts{};
   return 0;
 }
 
@@ -567,6 +574,7 @@ int lumc_render(LumContext* ctx, uint32_t first_sample, uint32_t num_samples, ui
   if (ctx->num_pixels == 0) return 0;
   hipStream_t stream = (hipStream_t) stream_;
   HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const bool buckets = !d_fm && !ctx->adaptive.active && ctx->firefly.K && ctx->firefly.planes && ctx->firefly.pixels == ctx->num_pixels;  // the context's own accumulators: its buckets too
   if (!d_fm) { d_fm = ctx->d_first_moment.get(); d_sm = ctx->d_second_moment.get(); }
   if (samples_per_pass == 0) samples_per_pass = 1;
   // sample ids beyond 2^20 would duplicate earlier ones (cuda/kernels.cuh:103-105)
@@ -594,6 +602,10 @@ int lumc_render(LumContext* ctx, uint32_t first_sample, uint32_t num_samples, ui
     {
       Launch l(ctx, stream, LUMC_KERNEL_ACCUMULATE);
       hipLaunchKernelGGL(k_accumulate, dim3(grid_for(P)), dim3(kBlock), pixel_major ? kAccTileBytes : 0u, stream, (const float4*) ctx->work.results, P, batch, d_fm, d_sm, pixel_major ? 1u : 0u);
+      if (buckets) {
+        HIP_TRY(ctx, firefly_accumulate_launch((const float4*) ctx->work.results, P, batch, first_sample + done, ctx->firefly.K, ctx->firefly.planes.get(), pixel_major, stream));
+        ctx->firefly.take(first_sample + done, batch);
+      }
     }
     HIP_TRY(ctx, hipGetLastError());
   }
@@ -627,6 +639,10 @@ int lumc_render_undersampled(LumContext* ctx, uint32_t stage, uint32_t iteration
     Launch l(ctx, stream, LUMC_KERNEL_ACCUMULATE);
     hipLaunchKernelGGL(k_accumulate_scatter, dim3(grid_for(n)), dim3(kBlock), 0, stream, (const float4*) ctx->work.results, (const uint32_t*) ctx->d_undersampling_pixels.get(), n,
                        ctx->num_pixels, ctx->d_first_moment.get(), ctx->d_second_moment.get());
+    if (ctx->firefly.K && ctx->firefly.planes && ctx->firefly.pixels == ctx->num_pixels) {
+      HIP_TRY(ctx, firefly_scatter_launch((const float4*) ctx->work.results, (const uint32_t*) ctx->d_undersampling_pixels.get(), n, ctx->num_pixels, ctx->firefly.planes.get(), stream));
+      if (stage == 1 && iteration == 0) ctx->firefly.counts.n[0]++;  // the schedule's last step: every pixel has its id 0 now
+    }
   }
   HIP_TRY(ctx, hipGetLastError());
   return 0;
@@ -1146,6 +1162,97 @@ int lumc_download_accumulators(LumContext* ctx, float* first_moment, float* seco
   HIP_TRY(ctx, hipDeviceSynchronize());
   if (first_moment) HIP_TRY(ctx, hipMemcpy(first_moment, ctx->d_first_moment.get(), sizeof(float) * 3 * (size_t) ctx->num_pixels, hipMemcpyDeviceToHost));
   if (second_moment) HIP_TRY(ctx, hipMemcpy(second_moment, ctx->d_second_moment.get(), sizeof(float) * (size_t) ctx->num_pixels, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// ---- firefly rejection (firefly.h, firefly.hip) ----
+int lumc_set_firefly_buckets(LumContext* ctx, uint32_t K) {
+  if (!ctx) return 1;
+  if (K != 0 && (K < kFireflyMinBuckets || K > kFireflyMaxBuckets)) {
+    ctx->error = "lumc_set_firefly_buckets: " + std::to_string(K) + " buckets (0: off, or 4 ... 16)";
+    return 1;
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  DeviceBuffer<float> planes;
+  DeviceBuffer<uint32_t> stats;
+  const size_t floats = (size_t) K * 3 * ctx->num_pixels;
+  if (K) {
+    hipError_t e = planes.resize(ctx->d_first_moment ? floats : 0);
+    if (e == hipSuccess) e = stats.resize(3);
+    if (e != hipSuccess) {  // (the context's planes are still what they were)
+      (void) hipGetLastError();
+      ctx->error = "lumc_set_firefly_buckets: no room for " + std::to_string(floats * sizeof(float)) + " bytes of bucket planes: " + hipGetErrorString(e);
+      return 1;
+    }
+  }
+  ctx->firefly.planes = std::move(planes);
+  ctx->firefly.d_stats = std::move(stats);
+  ctx->firefly.K = K;
+  ctx->firefly.pixels = ctx->firefly.planes ? ctx->num_pixels : 0u;
+  ctx->firefly.counts = FireflyCounts{};
+  return ctx->d_first_moment ? lumc_clear_accumulators(ctx) : 0;
+}
+
+int lumc_firefly_resolve(LumContext* ctx, float* d_image, void* stream_) {
+  if (!ctx) return 1;
+  FireflyBuckets& f = ctx->firefly;
+  if (!f.K || !f.planes) { ctx->error = "lumc_firefly_resolve: no buckets (lumc_set_firefly_buckets)"; return 1; }
+  if (ctx->adaptive.active) { ctx->error = "lumc_firefly_resolve: adaptive accumulation is active, its passes fill no buckets"; return 1; }
+  const uint32_t n = ctx->has_scene ? ctx->scene.width * ctx->scene.height : 0u;
+  if (!n || ctx->d_pixels || ctx->num_pixels != n || f.pixels != n) { ctx->error = "lumc_firefly_resolve: the image is not of the context's pixel set: the buckets need the full frame (lumc_set_pixels(ctx, NULL, 0))"; return 1; }
+  if (!f.any()) { ctx->error = "lumc_firefly_resolve: no bucket has samples"; return 1; }
+  if (!d_image) {
+    if (ctx->d_frame_result.count() != 3 * (size_t) n) { ctx->error = "lumc_firefly_resolve: no result image (lumc_generate_result)"; return 1; }
+    d_image = ctx->d_frame_result.get();
+  }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t stream = (hipStream_t) stream_;
+  HIP_TRY(ctx, hipMemsetAsync(f.d_stats.get(), 0, sizeof(uint32_t) * 3, stream));
+  {
+    Launch l(ctx, stream, LUMC_KERNEL_OUTPUT);
+    HIP_TRY(ctx, firefly_resolve_launch(f.planes.get(), f.counts, f.K, n, d_image, f.d_stats.get(), stream));
+  }
+  f.resolves++;
+  return 0;
+}
+
+int lumc_download_buckets(LumContext* ctx, float* sums, uint32_t* counts) {
+  if (!ctx) return 1;
+  const FireflyBuckets& f = ctx->firefly;
+  if (!f.K || !f.planes) { ctx->error = "lumc_download_buckets: no buckets (lumc_set_firefly_buckets)"; return 1; }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipDeviceSynchronize());
+  if (sums) HIP_TRY(ctx, hipMemcpy(sums, f.planes.get(), sizeof(float) * f.planes.count(), hipMemcpyDeviceToHost));
+  if (counts) std::memcpy(counts, f.counts.n, sizeof(uint32_t) * f.K);
+  return 0;
+}
+
+int lumc_upload_buckets(LumContext* ctx, const float* sums, const uint32_t* counts) {
+  if (!ctx) return 1;
+  FireflyBuckets& f = ctx->firefly;
+  if (!f.K || !f.planes) { ctx->error = "lumc_upload_buckets: no buckets (lumc_set_firefly_buckets)"; return 1; }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipDeviceSynchronize());
+  if (sums) HIP_TRY(ctx, hipMemcpy(f.planes.get(), sums, sizeof(float) * f.planes.count(), hipMemcpyHostToDevice));
+  if (counts) std::memcpy(f.counts.n, counts, sizeof(uint32_t) * f.K);
+  return 0;
+}
+
+int lumc_firefly_stats(LumContext* ctx, LumFireflyStats* out) {
+  if (!ctx || !out) return 1;
+  const FireflyBuckets& f = ctx->firefly;
+  std::memset(out, 0, sizeof(*out));
+  out->buckets = f.K;
+  out->bytes = sizeof(float) * (uint64_t) f.planes.count();
+  out->resolves = f.resolves;
+  for (uint32_t b = 0; b < f.K; b++) out->samples += f.counts.n[b];
+  if (f.d_stats && f.resolves) {
+    uint32_t st[3];
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipDeviceSynchronize());
+    HIP_TRY(ctx, hipMemcpy(st, f.d_stats.get(), sizeof(st), hipMemcpyDeviceToHost));
+    out->last_rewritten = st[0]; out->last_trimmed = st[1]; out->last_nonfinite = st[2];
+  }
   return 0;
 }
 

@@ -1070,6 +1070,19 @@ class Core:
                    C.c_int(self.LIGHT_PROBE_FORMS[form]), out.ctypes.data_as(C.c_void_p))
         return out
 
+    BOUNCE_PROBE_WORDS, BOUNCE_PROBE_HEAD_WORDS, BOUNCE_PROBE_TECH_WORDS, BOUNCE_PROBE_LIGHT_DIR_WORDS = 143, 44, 24, 27
+
+    def bounce_probe_host(self, vertices, first_sample, samples):
+        """sample_bounce and sample_light_direction on caller-made vertices (lumc_bounce_probe_host): vertices [V, 20] uint32 words, out [V, samples, 143] uint32
+        words - the two samples, the shading frame and the stages of every technique as include/lum_core.h lays them out."""
+        vertices = np.ascontiguousarray(vertices, dtype=np.uint32)
+        nv = vertices.shape[0]
+        assert vertices.shape == (nv, self.LIGHT_PROBE_VERTEX_WORDS)
+        out = np.zeros((nv, samples, self.BOUNCE_PROBE_WORDS), dtype=np.uint32)
+        self._call("lumc_bounce_probe_host", C.c_uint32(nv), vertices.ctypes.data_as(C.c_void_p), C.c_uint32(first_sample), C.c_uint32(samples),
+                   out.ctypes.data_as(C.c_void_p))
+        return out
+
     def trace_closest_device(self, n, origins_ptr, dirs_ptr, ignore_ptr, out_ptr, stream=0):
         self._call("lumc_trace_closest", C.c_uint32(n), C.c_void_p(origins_ptr), C.c_void_p(dirs_ptr), C.c_void_p(ignore_ptr), C.c_void_p(out_ptr),
                    C.c_void_p(stream))

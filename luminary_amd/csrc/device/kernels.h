@@ -1735,6 +1735,202 @@ __global__ __launch_bounds__(kBlock) void k_light_sample_probe(DeviceScene sc, u
   }
 }
 
+// ---- standalone bounce and BSDF-driven light direction for tests/test_bounce_truth.py: one thread per (vertex, sample id), sample_bounce and sample_light_direction
+// exactly as k_shade calls them (dev_bsdf.h, dev_light.h) ----
+// The vertex is the light probe's (20 words; self instance and triangle are not read here); state 0, the unseeded sampler at depth 0, set 0. Per thread kBounceProbeWords:
+//   [0..3)    transparent_pass, microfacet_based, is_pass_through of the one real call of sample_bounce
+//   [3..9)    its ray and weight
+//   [9..22)   local_frame: the quaternion, V, the face normal, the energy terms (conductor, glossy, dielectric)
+//   [22..29)  the second walk: the opacity draw and its outcome (0 not drawn, 1 stays, 2 passes), the initial pick, weight_sum after each technique, the chosen technique
+//             (kBounceProbeNoTechnique on a transparent pass)
+//   [29..37)  the second walk's weight, world ray, transparent_pass and microfacet_based
+//   [37..44)  the one real call of sample_light_direction: ray, weight, probability
+//   [44 + 24 t ..) per technique t (reflection, diffuse, refraction): status, m[3], local ray[3], the terms {fresnel_dielectric, NdotH, NdotL, NdotV, HdotL, HdotV,
+//             is_refraction}, eval[3], the own pdf, the two other pdfs (reflection: diffuse, refraction; diffuse: reflection, refraction; refraction: reflection,
+//             diffuse), mis, w, prob, pick after the decision
+//   [116..143) sample_light_direction's second walk: status, rr, the sampling roughness, m[3], local ray[3], the terms, pdf, the weight before and after 1 / rr,
+//             probability, world ray[3]
+// The second walks call the functions sample_bounce and sample_light_direction call on the arguments they pass them: shipped code is untouched. Words of a stage that is
+// not reached (a technique the material does not take, the pdfs of a refraction without total reflection, everything after a refused roulette) keep the caller's zero.
+constexpr uint32_t kBounceProbeHeadWords = 44, kBounceProbeTechWords = 24, kBounceProbeLightDirWords = 27;
+constexpr uint32_t kBounceProbeWordsPerThread = kBounceProbeHeadWords + 3 * kBounceProbeTechWords + kBounceProbeLightDirWords;
+enum BounceProbeStatus : uint32_t { kBounceProbeNotTaken = 0, kBounceProbeTaken = 1, kBounceProbeTotalReflection = 2 };
+enum BounceProbeLightDir : uint32_t { kBounceProbeRefused = 0, kBounceProbeReflection = 1, kBounceProbeRefraction = 2, kBounceProbeRefractionTotal = 3 };
+constexpr uint32_t kBounceProbeNoTechnique = 3;
+LUM_DEV void probe_put(uint32_t* w, V3 v) { w[0] = fbits(v.x); w[1] = fbits(v.y); w[2] = fbits(v.z); }
+LUM_DEV void probe_put(uint32_t* w, Col c) { w[0] = fbits(c.r); w[1] = fbits(c.g); w[2] = fbits(c.b); }
+LUM_DEV void probe_put(uint32_t* w, const RayTerms& c) {
+  w[0] = fbits(c.fresnel_dielectric); w[1] = fbits(c.NdotH); w[2] = fbits(c.NdotL); w[3] = fbits(c.NdotV); w[4] = fbits(c.HdotL); w[5] = fbits(c.HdotV);
+  w[6] = c.is_refraction ? 1u : 0u;
+}
+__global__ __launch_bounds__(kBlock) void k_bounce_probe(DeviceScene sc, uint32_t n, uint32_t samples, uint32_t first_sample, const uint32_t* vertices, uint32_t* out) {
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t* vw = vertices + (size_t) (i / samples) * kLightProbeVertexWords;
+  uint32_t* o = out + (size_t) i * kBounceProbeWordsPerThread;
+  GeoContext g;
+  g.instance_id = vw[16]; g.tri_id = vw[17];
+  g.position = v3(bitsf(vw[0]), bitsf(vw[1]), bitsf(vw[2]));
+  g.normal = normalize(v3(bitsf(vw[3]), bitsf(vw[4]), bitsf(vw[5])));
+  g.V = normalize(v3(bitsf(vw[6]), bitsf(vw[7]), bitsf(vw[8])));
+  g.face_normal_packed = normal_pack(g.normal);
+  g.state = 0;
+  g.params.flags = vw[15];
+  g.params.set(col(bitsf(vw[9]), bitsf(vw[10]), bitsf(vw[11])), bitsf(vw[12]), bitsf(vw[13]), splat(0.0f), bitsf(vw[14]));
+  const SamplerT<false> smp{sc.bluenoise_2d, vw[18], vw[19], first_sample + i % samples, 0u};
+  // the real calls
+  const LocalFrame lf = local_frame(sc, g);
+  const BounceSample bounce = sample_bounce(lf, g, smp, 0);
+  const LightDirSample lb = sample_light_direction(lf, g, smp);
+  o[0] = bounce.transparent_pass ? 1u : 0u; o[1] = bounce.microfacet_based ? 1u : 0u; o[2] = is_pass_through(g, bounce) ? 1u : 0u;
+  probe_put(o + 3, bounce.ray); probe_put(o + 6, bounce.weight);
+  o[9] = fbits(lf.to_z.x); o[10] = fbits(lf.to_z.y); o[11] = fbits(lf.to_z.z); o[12] = fbits(lf.to_z.w);
+  probe_put(o + 13, lf.V); probe_put(o + 16, lf.face_normal);
+  o[19] = fbits(lf.energy.conductor); o[20] = fbits(lf.energy.glossy); o[21] = fbits(lf.energy.dielectric);
+  probe_put(o + 37, lb.ray); probe_put(o + 40, lb.weight); o[43] = fbits(lb.probability);
+  const MatParams& p = g.params;
+  const V3 Vl = lf.V, fnl = lf.face_normal;
+  const V3 up = v3(0.0f, 0.0f, 1.0f);
+  const float ior = p.ior(), roughness = p.roughness();
+  const bool with_refraction = (p.flags & kMatSubstrateMask) == kMatTranslucent;
+  // the second walk over sample_bounce
+  {
+    bool passes = false;
+    const float opacity = p.opacity();
+    if (opacity < 1.0f) {
+      const float draw = smp.next1(kRndBsdfOpacity);
+      passes = draw > opacity;
+      o[22] = fbits(draw); o[23] = passes ? 2u : 1u;
+    }
+    if (passes) {
+      o[28] = kBounceProbeNoTechnique;
+      probe_put(o + 29, (p.flags & kMatColoredTransparency) ? p.albedo() : col(1.0f, 1.0f, 1.0f));
+      probe_put(o + 32, g.V * -1.0f);
+      o[35] = 1u; o[36] = 0u;
+    }
+    else {
+      const bool with_diffuse = ((p.flags & kMatSubstrateMask) == 0) && ((p.flags & kMatMetallic) == 0);
+      float pick = smp.next1(kRndBsdfResampling);
+      o[24] = fbits(pick);
+      V3 chosen_ray;
+      Col chosen_eval;
+      float weight_sum;
+      uint32_t chosen = 0;
+      bool transparent_pass = false, microfacet_based = true;
+      {
+        uint32_t* w = o + kBounceProbeHeadWords;
+        const V3 m = sample_vndf_bounded(Vl, roughness, smp.next2(kRndBsdfReflection));
+        const V3 ray = reflect(Vl, m);
+        const RayTerms c = sampled_direction_terms(p, up, Vl, m, ray, false);
+        const Col eval = eval_with_face_normal(lf.energy, p, c, kHintMicrofacet, ray, fnl, 1.0f);
+        const float pdf = pdf_vndf_bounded(Vl, roughness, c.NdotH, c.NdotV);
+        const float dp = with_diffuse ? pdf_diffuse(c.NdotL) : 0.0f;
+        const float rp = with_refraction ? pdf_refraction(roughness, c.NdotH, c.NdotV, c.HdotV, c.HdotL, ior) : 0.0f;
+        const float sum = pdf + dp + rp;
+        const float mis = (sum > 0.0f) ? pdf / sum : 0.0f;
+        chosen_ray = ray; chosen_eval = eval; weight_sum = importance(eval) * mis;
+        w[0] = kBounceProbeTaken; probe_put(w + 1, m); probe_put(w + 4, ray); probe_put(w + 7, c); probe_put(w + 14, eval);
+        w[17] = fbits(pdf); w[18] = fbits(dp); w[19] = fbits(rp); w[20] = fbits(mis); w[21] = fbits(weight_sum); w[23] = fbits(pick);
+      }
+      o[25] = fbits(weight_sum);
+      if (with_diffuse) {
+        uint32_t* w = o + kBounceProbeHeadWords + kBounceProbeTechWords;
+        const F2 r2 = smp.next2(kRndBsdfDiffuse);
+        const V3 ray = sample_ray_sphere(r2.x, r2.y);
+        const V3 m = normalize(Vl + ray);
+        const RayTerms c = sampled_direction_terms(p, up, Vl, m, ray, false);
+        const Col eval = eval_with_face_normal(lf.energy, p, c, kHintDiffuse, ray, fnl, 1.0f);
+        const float pdf = pdf_diffuse(c.NdotL);
+        const float mp = pdf_vndf_bounded(Vl, roughness, c.NdotH, c.NdotV);
+        const float rp = with_refraction ? pdf_refraction(roughness, c.NdotH, c.NdotV, c.HdotV, c.HdotL, ior) : 0.0f;
+        const float sum = pdf + mp + rp;
+        const float mis = (sum > 0.0f) ? pdf / sum : 0.0f;
+        const float wt = importance(eval) * mis;
+        weight_sum += wt;
+        const float prob = wt / weight_sum;
+        if (pick < prob) {
+          chosen_ray = ray; chosen_eval = eval; transparent_pass = false; microfacet_based = false; chosen = 1;
+          pick = clamp_random(pick / prob);
+        }
+        else pick = clamp_random((pick - prob) / (1.0f - prob));
+        w[0] = kBounceProbeTaken; probe_put(w + 1, m); probe_put(w + 4, ray); probe_put(w + 7, c); probe_put(w + 14, eval);
+        w[17] = fbits(pdf); w[18] = fbits(mp); w[19] = fbits(rp); w[20] = fbits(mis); w[21] = fbits(wt); w[22] = fbits(prob); w[23] = fbits(pick);
+      }
+      o[26] = fbits(weight_sum);
+      if (with_refraction) {
+        uint32_t* w = o + kBounceProbeHeadWords + 2 * kBounceProbeTechWords;
+        bool total_reflection;
+        const V3 m = sample_vndf_caps(Vl, roughness, smp.next2(kRndBsdfRefraction));
+        const V3 ray = refract(Vl, m, ior, total_reflection);
+        const RayTerms c = sampled_direction_terms(p, up, Vl, m, ray, !total_reflection);
+        const Col eval = eval_with_face_normal(lf.energy, p, c, kHintRefraction, ray, fnl, 1.0f);
+        float mis = 1.0f;
+        if (total_reflection) {
+          const float pdf = pdf_refraction(roughness, c.NdotH, c.NdotV, c.HdotV, c.HdotL, ior);
+          const float refl = pdf_vndf_bounded(Vl, roughness, c.NdotH, c.NdotV);
+          const float dp = with_diffuse ? pdf_diffuse(c.NdotL) : 0.0f;
+          const float sum = pdf + refl + dp;
+          mis = (sum > 0.0f) ? pdf / sum : 0.0f;
+          w[17] = fbits(pdf); w[18] = fbits(refl); w[19] = fbits(dp);
+        }
+        const float wt = importance(eval) * mis;
+        weight_sum += wt;
+        const float prob = wt / weight_sum;
+        if (pick < prob) {
+          chosen_ray = ray; chosen_eval = eval; transparent_pass = !total_reflection; microfacet_based = true; chosen = 2;
+          pick = clamp_random(pick / prob);
+        }
+        else pick = clamp_random((pick - prob) / (1.0f - prob));
+        w[0] = total_reflection ? kBounceProbeTotalReflection : kBounceProbeTaken;
+        probe_put(w + 1, m); probe_put(w + 4, ray); probe_put(w + 7, c); probe_put(w + 14, eval);
+        w[20] = fbits(mis); w[21] = fbits(wt); w[22] = fbits(prob); w[23] = fbits(pick);
+      }
+      o[27] = fbits(weight_sum);
+      o[28] = chosen;
+      probe_put(o + 29, (weight_sum > 0.0f) ? chosen_eval * (weight_sum / importance(chosen_eval)) : col(0.0f, 0.0f, 0.0f));
+      probe_put(o + 32, normalize(qapply(qinv(lf.to_z), chosen_ray)));
+      o[35] = transparent_pass ? 1u : 0u; o[36] = microfacet_based ? 1u : 0u;
+    }
+  }
+  // the second walk over sample_light_direction
+  {
+    uint32_t* w = o + kBounceProbeHeadWords + 3 * kBounceProbeTechWords;
+    const uint32_t num_tech = with_refraction ? 2 : 1;
+    const float refr_prob = with_refraction ? 1.0f / num_tech : 0.0f;
+    const uint32_t tech = (uint32_t) (smp.next1(kRndLightBsdfChoice) * num_tech);
+    const bool refraction = (tech == 1) && with_refraction;
+    const float rr = light_dir_rr(roughness);
+    w[0] = kBounceProbeRefused; w[1] = fbits(rr);
+    if (smp.next1(kRndLightBsdfRR) >= rr) return;
+    const float sr = light_dir_roughness(roughness);
+    w[2] = fbits(sr);
+    V3 m, ray;
+    RayTerms c;
+    float pdf, probability;
+    bool total_reflection = false;
+    if (!refraction) {
+      m = sample_vndf_bounded(Vl, sr, smp.next2(kRndLightBsdfDirection));
+      ray = reflect(Vl, m);
+      c = sampled_direction_terms(p, up, Vl, m, ray, false);
+      pdf = pdf_vndf_bounded(Vl, sr, c.NdotH, c.NdotV);
+      probability = (1.0f - refr_prob) * pdf;
+    }
+    else {
+      m = sample_vndf_caps(Vl, sr, smp.next2(kRndLightBsdfDirection));
+      ray = refract(Vl, m, ior, total_reflection);
+      c = sampled_direction_terms(p, up, Vl, m, ray, !total_reflection);
+      pdf = pdf_refraction(sr, c.NdotH, c.NdotV, c.HdotV, c.HdotL, ior);
+      probability = refr_prob * pdf;
+    }
+    const Col weight = eval_with_face_normal(lf.energy, p, c, kHintGeneral, ray, fnl, 1.0f / pdf);
+    w[0] = !refraction ? kBounceProbeReflection : total_reflection ? kBounceProbeRefractionTotal : kBounceProbeRefraction;
+    probe_put(w + 3, m); probe_put(w + 6, ray); probe_put(w + 9, c);
+    w[16] = fbits(pdf); probe_put(w + 17, weight); probe_put(w + 20, weight * (1.0f / rr));
+    w[23] = fbits(probability * rr);
+    probe_put(w + 24, normalize(qapply(qinv(lf.to_z), ray)));
+  }
+}
+
 // The Sobol / Owen pairs of one pass (dev_sampler.h LUM_SOBOL_TABLE): one thread per (dimension, sample id).
 __global__ __launch_bounds__(256) void k_sobol_table(uint2* __restrict__ table, uint32_t first_sample, uint32_t count, uint32_t stride, uint32_t dims) {
   const uint32_t t = blockIdx.x * 256u + threadIdx.x;

@@ -104,8 +104,11 @@ struct WavefrontProbes {
   // form: 0 the general form, 1 the plain form (the caller has asked plain_scene), 2 the general form with no light staged in LDS
   void (*light_sample_probe)(hipStream_t s, const DeviceScene& sc, uint32_t n_vertices, uint32_t samples, uint32_t first_sample, uint32_t form, const uint32_t* vertices,
                              uint32_t* out);
+  // sample_bounce and sample_light_direction on the same vertices, one (vertex, sample id) per thread (k_bounce_probe, kernels.h: 20 words in per vertex, 143 out per thread)
+  void (*bounce_probe)(hipStream_t s, const DeviceScene& sc, uint32_t n_vertices, uint32_t samples, uint32_t first_sample, const uint32_t* vertices, uint32_t* out);
 };
 constexpr uint32_t kLightSampleProbeVertexWords = 20, kLightSampleProbeWords = 154;  // that probe's words per vertex (in) and per thread (out)
+constexpr uint32_t kBounceProbeWords = 143;                                          // the bounce probe's words per thread (its vertex is the light probe's)
 
 const WavefrontKernels* wavefront_kernels_exact();  // csrc/device/wavefront_exact.hip
 const WavefrontKernels* wavefront_kernels_fast();   // csrc/device/wavefront_fast.hip

@@ -182,6 +182,11 @@ static void light_sample_probe(hipStream_t s, const DeviceScene& sc, uint32_t n_
   if (form == 1u) hipLaunchKernelGGL(k_light_sample_probe<true>, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, sc, n, samples, first_sample, 1u, vertices, out);
   else hipLaunchKernelGGL(k_light_sample_probe<false>, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, sc, n, samples, first_sample, form == 2u ? 0u : 1u, vertices, out);
 }
+static void bounce_probe(hipStream_t s, const DeviceScene& sc, uint32_t n_vertices, uint32_t samples, uint32_t first_sample, const uint32_t* vertices, uint32_t* out) {
+  static_assert(kBounceProbeWordsPerThread == kBounceProbeWords, "the host layer sizes the probe's buffers by this");
+  const uint32_t n = n_vertices * samples;
+  hipLaunchKernelGGL(k_bounce_probe, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, sc, n, samples, first_sample, vertices, out);
+}
 
 // Filled by member name: neighbouring members share a function-pointer type (resolve / resolve_listed, particle_shade / ocean_shade, sky_inscattering / clouds),
 // so a positional list with two of them swapped would compile. tests/test_build_units.py checks that no member stays null.
@@ -201,7 +206,7 @@ static constexpr WavefrontKernels make_table() {
 static constexpr WavefrontKernels kTable = make_table();
 static constexpr WavefrontProbes make_probes() {
   WavefrontProbes p{};
-  p.light_sample_probe = light_sample_probe;
+  p.light_sample_probe = light_sample_probe; p.bounce_probe = bounce_probe;
   return p;
 }
 static constexpr WavefrontProbes kProbes = make_probes();

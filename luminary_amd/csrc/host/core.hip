@@ -1478,6 +1478,30 @@ int lumc_light_sample_probe_host(LumContext* ctx, uint32_t num_vertices, const u
   return 0;
 }
 
+// sample_bounce (dev_bsdf.h) and sample_light_direction (dev_light.h) on the light probe's caller-made vertices in the active flavour, with their stages: out holds
+// LUMC_BOUNCE_PROBE_WORDS words per (vertex, sample id), zero where a stage was not reached (k_bounce_probe, kernels.h).
+int lumc_bounce_probe_host(LumContext* ctx, uint32_t num_vertices, const uint32_t* vertices, uint32_t first_sample, uint32_t samples, uint32_t* out) {
+  static_assert(LUMC_BOUNCE_PROBE_WORDS == kBounceProbeWords, "lum_core.h and wavefront_table.h");
+  static_assert(LUMC_BOUNCE_PROBE_WORDS == LUMC_BOUNCE_PROBE_HEAD_WORDS + 3 * LUMC_BOUNCE_PROBE_TECH_WORDS + LUMC_BOUNCE_PROBE_LIGHT_DIR_WORDS, "lum_core.h");
+  if (!ctx || !ctx->has_scene) { if (ctx) ctx->error = "lumc_bounce_probe_host: no scene"; return 1; }
+  if (num_vertices == 0 || samples == 0) return 0;
+  if (!vertices || !out) { ctx->error = "lumc_bounce_probe_host: null argument"; return 1; }
+  const DeviceScene& sc = ctx->scene;
+  if (!sc.bluenoise_2d || !sc.lut_conductor || !sc.lut_glossy || !sc.lut_dielectric || !sc.lut_dielectric_inv) { ctx->error = "lumc_bounce_probe_host: the scene has no energy tables"; return 1; }
+  const size_t n = (size_t) num_vertices * samples;
+  if (n > (1u << 24)) { ctx->error = "lumc_bounce_probe_host: more than 2^24 threads"; return 1; }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  DeviceBuffer<uint32_t> d_v, d_out;
+  HIP_TRY(ctx, d_v.assign(vertices, (size_t) num_vertices * kLightSampleProbeVertexWords));
+  HIP_TRY(ctx, d_out.resize(n * kBounceProbeWords));
+  HIP_TRY(ctx, hipMemset(d_out.get(), 0, sizeof(uint32_t) * n * kBounceProbeWords));
+  (ctx->wf == wavefront_kernels_exact() ? wavefront_probes_exact() : wavefront_probes_fast())->bounce_probe(nullptr, sc, num_vertices, samples, first_sample, d_v.get(), d_out.get());
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipDeviceSynchronize());
+  HIP_TRY(ctx, hipMemcpy(out, d_out.get(), sizeof(uint32_t) * n * kBounceProbeWords, hipMemcpyDeviceToHost));
+  return 0;
+}
+
 int lumc_pixel_query(LumContext* ctx, uint32_t x, uint32_t y, uint32_t sample_id, uint32_t out[6]) {
   if (!ctx || !ctx->has_scene || !out) { if (ctx) ctx->error = "lumc_pixel_query: no scene"; return 1; }
   if (x >= ctx->scene.width || y >= ctx->scene.height) { ctx->error = "lumc_pixel_query: pixel outside the frame"; return 1; }

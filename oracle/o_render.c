@@ -1470,6 +1470,181 @@ void oracle_probe_light_sample_stages(const OracleScene* s, uint32_t num_vertice
     }
   }
 }
+/* bsdf_sample and light_bsdf_get_sample with their stages on the same vertices: the words of the device's probe (include/lum_core.h lumc_bounce_probe_host), in its
+ * layout. The head holds the results of the two functions themselves; the stages are what they computed on the way, restated here statement for statement from the
+ * functions they call. The terms' fresnel word is the one the lobes read: the dielectric lobe alone reads it, so it is 1 unless the substrate is translucent. */
+static void put3(uint32_t* w, vec3 v) { w[0] = f_bits(v.x); w[1] = f_bits(v.y); w[2] = f_bits(v.z); }
+static void put_rgb(uint32_t* w, RGBF c) { w[0] = f_bits(c.r); w[1] = f_bits(c.g); w[2] = f_bits(c.b); }
+static void put_terms(uint32_t* w, const BSDFRayCtx* c, bool translucent) {
+  w[0] = f_bits(translucent ? c->fresnel_dielectric : 1.0f); w[1] = f_bits(c->NdotH); w[2] = f_bits(c->NdotL); w[3] = f_bits(c->NdotV); w[4] = f_bits(c->HdotL);
+  w[5] = f_bits(c->HdotV); w[6] = c->is_refraction ? 1u : 0u;
+}
+void oracle_probe_bounce_stages(const OracleScene* s, uint32_t num_vertices, const uint32_t* vertices, uint32_t first, uint32_t samples, uint32_t* out) {
+  const OLuts luts = scene_luts(s);
+  const OLuts* l = &luts;
+  memset(out, 0, sizeof(uint32_t) * (size_t) ORACLE_BOUNCE_PROBE_WORDS * num_vertices * samples);
+  for (uint32_t v = 0; v < num_vertices; v++) {
+    const uint32_t* vw = vertices + (size_t) ORACLE_LIGHT_PROBE_VERTEX_WORDS * v;
+    float f[15]; memcpy(f, vw, sizeof(f));
+    const OracleProbeMaterial m0 = {{f[9], f[10], f[11]}, f[12], f[13], f[14], vw[15]};
+    GeoCtx gc = probe_context(&m0, f, f + 3, f + 6);
+    gc.instance_id = vw[16]; gc.tri_id = vw[17];
+    const GeoCtx* g = &gc;
+    const MatParams* p = &g->params;
+    const Quat rot = q_rotation_to_z(g->normal);
+    const vec3 Vl = q_apply(rot, g->V);
+    const vec3 fnl = q_apply(rot, normal_unpack(g->face_normal));
+    const vec3 up = v3(0.0f, 0.0f, 1.0f);
+    const uint32_t substrate = p->flags & MAT_SUBSTRATE_MASK;
+    const bool include_diffuse = (substrate == 0) && ((p->flags & MAT_METALLIC) == 0);
+    const bool include_refraction = (substrate == MAT_TRANSLUCENT);
+    const float ior = mp_ior(p), roughness = mp_roughness(p), opacity = mp_opacity(p);
+    const float NdotV = o_saturate(v_dot(up, Vl));
+    for (uint32_t i = 0; i < samples; i++) {
+      uint32_t* o = out + (size_t) ORACLE_BOUNCE_PROBE_WORDS * ((size_t) v * samples + i);
+      const Sampler sampler = {s->bluenoise_2d, vw[18], vw[19], first + i, 0};
+      const Sampler* smp = &sampler;
+      const BSDFSample b = bsdf_sample(l, g, smp, 0);
+      const LightBSDFSample lb = light_bsdf_get_sample(l, g, smp);
+      o[0] = b.is_transparent_pass ? 1u : 0u; o[1] = b.is_microfacet_based ? 1u : 0u; o[2] = bsdf_is_pass_through_ray(g, &b) ? 1u : 0u;
+      put3(o + 3, b.ray); put_rgb(o + 6, b.weight);
+      o[9] = f_bits(rot.x); o[10] = f_bits(rot.y); o[11] = f_bits(rot.z); o[12] = f_bits(rot.w);
+      put3(o + 13, Vl); put3(o + 16, fnl);
+      /* the energy terms as the lobes fetch them (bsdf_conductor, bsdf_glossy, bsdf_dielectric): 1, 0, 1 where the material's lobes do not read them */
+      o[19] = f_bits(substrate == 0 ? lut2d(l->conductor, NdotV, roughness) : 1.0f);
+      o[20] = f_bits(include_diffuse ? lut2d(l->glossy, NdotV, roughness) : 0.0f);
+      o[21] = f_bits(substrate != 0 ? bsdf_dielectric_da(l, NdotV, roughness, roughness) : 1.0f);
+      put3(o + 37, lb.ray); put_rgb(o + 40, lb.weight); o[43] = f_bits(lb.sampling_probability);
+      /* bsdf_sample's stages */
+      bool passes = false;
+      if (opacity < 1.0f) {
+        const float tr = rnd1(smp, RT_BSDF_OPACITY);
+        passes = tr > opacity;
+        o[22] = f_bits(tr); o[23] = passes ? 2u : 1u;
+      }
+      if (passes) {
+        o[28] = 3;
+        put_rgb(o + 29, (p->flags & MAT_COLORED_TRANSPARENCY) ? mp_albedo(p) : c3(1.0f, 1.0f, 1.0f));
+        put3(o + 32, v_scale(g->V, -1.0f));
+        o[35] = 1; o[36] = 0;
+      }
+      else {
+        float rr = rnd1(smp, RT_BSDF_RESAMPLING);
+        o[24] = f_bits(rr);
+        vec3 ray_local;
+        RGBF selected;
+        float sum_weights;
+        uint32_t chosen = 0;
+        bool transparent = false, microfacet = true;
+        {
+          uint32_t* w = o + ORACLE_BOUNCE_PROBE_HEAD_WORDS;
+          const vec3 m = microfacet_sample_normal(Vl, roughness, rnd2(smp, RT_BSDF_REFLECTION));
+          const vec3 ray = v_reflect(Vl, m);
+          const BSDFRayCtx c = bsdf_sample_context(p, up, Vl, m, ray, false);
+          const RGBF eval = bsdf_evaluate_core(l, p, &c, HINT_MICROFACET, ray, fnl, 1.0f);
+          const float pdf = microfacet_pdf(Vl, roughness, c.NdotH, c.NdotV);
+          const float dpdf = include_diffuse ? diffuse_pdf(c.NdotL) : 0.0f;
+          const float rpdf = include_refraction ? microfacet_refraction_pdf(roughness, c.NdotH, c.NdotV, c.HdotV, c.HdotL, ior) : 0.0f;
+          const float sum = pdf + dpdf + rpdf;
+          const float mis = (sum > 0.0f) ? pdf / sum : 0.0f;
+          const float wt = c_importance(eval) * mis;
+          ray_local = ray; sum_weights = wt; selected = eval;
+          w[0] = 1; put3(w + 1, m); put3(w + 4, ray); put_terms(w + 7, &c, include_refraction); put_rgb(w + 14, eval);
+          w[17] = f_bits(pdf); w[18] = f_bits(dpdf); w[19] = f_bits(rpdf); w[20] = f_bits(mis); w[21] = f_bits(wt); w[23] = f_bits(rr);
+        }
+        o[25] = f_bits(sum_weights);
+        if (include_diffuse) {
+          uint32_t* w = o + ORACLE_BOUNCE_PROBE_HEAD_WORDS + ORACLE_BOUNCE_PROBE_TECH_WORDS;
+          const float2_t r2 = rnd2(smp, RT_BSDF_DIFFUSE);
+          const vec3 ray = sample_ray_sphere(r2.x, r2.y);
+          const vec3 m = v_norm(v_add(Vl, ray));
+          const BSDFRayCtx c = bsdf_sample_context(p, up, Vl, m, ray, false);
+          const RGBF eval = bsdf_evaluate_core(l, p, &c, HINT_DIFFUSE, ray, fnl, 1.0f);
+          const float pdf = diffuse_pdf(c.NdotL);
+          const float mpdf = microfacet_pdf(Vl, roughness, c.NdotH, c.NdotV);
+          const float rpdf = include_refraction ? microfacet_refraction_pdf(roughness, c.NdotH, c.NdotV, c.HdotV, c.HdotL, ior) : 0.0f;
+          const float sum = pdf + mpdf + rpdf;
+          const float mis = (sum > 0.0f) ? pdf / sum : 0.0f;
+          const float wt = c_importance(eval) * mis;
+          sum_weights += wt;
+          const float prob = wt / sum_weights;
+          if (rr < prob) { ray_local = ray; selected = eval; transparent = false; microfacet = false; chosen = 1; rr = rng_saturate(rr / prob); }
+          else rr = rng_saturate((rr - prob) / (1.0f - prob));
+          w[0] = 1; put3(w + 1, m); put3(w + 4, ray); put_terms(w + 7, &c, include_refraction); put_rgb(w + 14, eval);
+          w[17] = f_bits(pdf); w[18] = f_bits(mpdf); w[19] = f_bits(rpdf); w[20] = f_bits(mis); w[21] = f_bits(wt); w[22] = f_bits(prob); w[23] = f_bits(rr);
+        }
+        o[26] = f_bits(sum_weights);
+        if (include_refraction) {
+          uint32_t* w = o + ORACLE_BOUNCE_PROBE_HEAD_WORDS + 2 * ORACLE_BOUNCE_PROBE_TECH_WORDS;
+          bool total_reflection;
+          const vec3 m = microfacet_refraction_sample_normal(Vl, roughness, rnd2(smp, RT_BSDF_REFRACTION));
+          const vec3 ray = refract_vector(Vl, m, ior, &total_reflection);
+          const BSDFRayCtx c = bsdf_sample_context(p, up, Vl, m, ray, !total_reflection);
+          const RGBF eval = bsdf_evaluate_core(l, p, &c, HINT_MICROFACET_REFRACTION, ray, fnl, 1.0f);
+          float mis = 1.0f;
+          if (total_reflection) {
+            const float pdf = microfacet_refraction_pdf(roughness, c.NdotH, c.NdotV, c.HdotV, c.HdotL, ior);
+            const float refl = microfacet_pdf(Vl, roughness, c.NdotH, c.NdotV);
+            const float dpdf = include_diffuse ? diffuse_pdf(c.NdotL) : 0.0f;
+            const float sum = pdf + refl + dpdf;
+            mis = (sum > 0.0f) ? pdf / sum : 0.0f;
+            w[17] = f_bits(pdf); w[18] = f_bits(refl); w[19] = f_bits(dpdf);
+          }
+          const float wt = c_importance(eval) * mis;
+          sum_weights += wt;
+          const float prob = wt / sum_weights;
+          if (rr < prob) { ray_local = ray; selected = eval; transparent = !total_reflection; microfacet = true; chosen = 2; rr = rng_saturate(rr / prob); }
+          else rr = rng_saturate((rr - prob) / (1.0f - prob));
+          w[0] = total_reflection ? 2u : 1u;
+          put3(w + 1, m); put3(w + 4, ray); put_terms(w + 7, &c, true); put_rgb(w + 14, eval);
+          w[20] = f_bits(mis); w[21] = f_bits(wt); w[22] = f_bits(prob); w[23] = f_bits(rr);
+        }
+        o[27] = f_bits(sum_weights);
+        o[28] = chosen;
+        put_rgb(o + 29, (sum_weights > 0.0f) ? c_scale(selected, sum_weights / c_importance(selected)) : c3(0.0f, 0.0f, 0.0f));
+        put3(o + 32, v_norm(q_apply(q_inverse(rot), ray_local)));
+        o[35] = transparent ? 1u : 0u; o[36] = microfacet ? 1u : 0u;
+      }
+      /* light_bsdf_get_sample's stages */
+      {
+        uint32_t* w = o + ORACLE_BOUNCE_PROBE_HEAD_WORDS + 3 * ORACLE_BOUNCE_PROBE_TECH_WORDS;
+        const uint32_t num_tech = 1 + (include_refraction ? 1 : 0);
+        const float refr_prob = include_refraction ? 1.0f / num_tech : 0.0f;
+        const uint32_t tech_id = (uint32_t) (rnd1(smp, RT_LIGHT_BSDF_CHOICE) * num_tech);
+        const bool refraction = (tech_id == 1 && include_refraction);
+        const float rrp = light_bsdf_rr_prob(roughness);
+        w[0] = 0; w[1] = f_bits(rrp);
+        if (rnd1(smp, RT_LIGHT_BSDF_RR) >= rrp) continue;
+        const float sr = light_bsdf_sampling_roughness(roughness);
+        w[2] = f_bits(sr);
+        vec3 m, ray;
+        BSDFRayCtx c;
+        float pdf, probability;
+        bool tot = false;
+        if (!refraction) {
+          m = microfacet_sample_normal(Vl, sr, rnd2(smp, RT_LIGHT_BSDF_DIRECTION));
+          ray = v_reflect(Vl, m);
+          c = bsdf_sample_context(p, up, Vl, m, ray, false);
+          pdf = microfacet_pdf(Vl, sr, c.NdotH, c.NdotV);
+          probability = (1.0f - refr_prob) * pdf;
+        }
+        else {
+          m = microfacet_refraction_sample_normal(Vl, sr, rnd2(smp, RT_LIGHT_BSDF_DIRECTION));
+          ray = refract_vector(Vl, m, ior, &tot);
+          c = bsdf_sample_context(p, up, Vl, m, ray, !tot);
+          pdf = microfacet_refraction_pdf(sr, c.NdotH, c.NdotV, c.HdotV, c.HdotL, ior);
+          probability = refr_prob * pdf;
+        }
+        const RGBF weight = bsdf_evaluate_core(l, p, &c, HINT_GENERAL, ray, fnl, 1.0f / pdf);
+        w[0] = !refraction ? 1u : tot ? 3u : 2u;
+        put3(w + 3, m); put3(w + 6, ray); put_terms(w + 9, &c, include_refraction);
+        w[16] = f_bits(pdf); put_rgb(w + 17, weight); put_rgb(w + 20, c_scale(weight, 1.0f / rrp));
+        w[23] = f_bits(probability * rrp);
+        put3(w + 24, v_norm(q_apply(q_inverse(rot), ray)));
+      }
+    }
+  }
+}
 /* light_bsdf_get_probability on its own: the probability with which the BSDF-driven light direction of the vertex would have been L */
 void oracle_probe_light_direction_probability(const OracleProbeMaterial* m, const float normal[3], const float V[3], uint32_t count, const float* L, float* out) {
   const float origin[3] = {0.0f, 0.0f, 0.0f};

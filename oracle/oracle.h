@@ -234,6 +234,12 @@ void oracle_probe_light_sample(const OracleScene* s, const OracleProbeMaterial* 
 #define ORACLE_LIGHT_PROBE_VERTEX_WORDS 20 /* = LUMC_LIGHT_PROBE_VERTEX_WORDS, include/lum_core.h (tests/test_light_sample_truth.py compares the headers) */
 #define ORACLE_LIGHT_PROBE_WORDS 154       /* = LUMC_LIGHT_PROBE_WORDS: 18 + 8 lanes x 17 */
 void oracle_probe_light_sample_stages(const OracleScene* s, uint32_t num_vertices, const uint32_t* vertices, uint32_t first, uint32_t samples, uint32_t* out);
+/* bsdf_sample and light_bsdf_get_sample and their stages on the same vertices, in the words of the device's bounce probe (tests/test_bounce_truth.py) */
+#define ORACLE_BOUNCE_PROBE_WORDS 143          /* = LUMC_BOUNCE_PROBE_WORDS, include/lum_core.h: 44 + 3 techniques x 24 + 27 (the test compares the headers) */
+#define ORACLE_BOUNCE_PROBE_HEAD_WORDS 44
+#define ORACLE_BOUNCE_PROBE_TECH_WORDS 24
+#define ORACLE_BOUNCE_PROBE_LIGHT_DIR_WORDS 27
+void oracle_probe_bounce_stages(const OracleScene* s, uint32_t num_vertices, const uint32_t* vertices, uint32_t first, uint32_t samples, uint32_t* out);
 void oracle_probe_light_direction_probability(const OracleProbeMaterial* m, const float normal[3], const float V[3], uint32_t count, const float* L, float* out);
 
 /* fog (o_volume.h) */

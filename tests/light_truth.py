@@ -350,7 +350,7 @@ class Truth:
         return float(self.decisive.mean())
 
     # ---- the acceptor ----
-    def check(self, out, yardstick=None, factor=1.0, bsdf_reference=None, bsdf_tolerance=None):
+    def check(self, out, yardstick=None, factor=1.0, bsdf_reference=None, bsdf_tolerance=None, luts=None):
         """out [V, S, 154] uint32: the probe's words. Returns (failures: dict name -> bool [N] or [N, 8], figures: dict name -> the largest distance from the truth per
         quantity). yardstick: the figures of the reference run; the distances may be `factor` times them (floor: 4 ulp of the quantity's scale)."""
         sc = self.scene
@@ -490,6 +490,19 @@ class Truth:
             fig["BSDF weight relative to the oracle"] = float(np.max(np.where(ev & np.isfinite(rel), rel, 0.0)))
             if bsdf_tolerance is not None:
                 fail["BSDF weight beyond its tolerance"] = ev & ~(rel <= bsdf_tolerance)
+        if luts is not None:
+            # ... and to the float64 evaluation (bsdf_truth.py: eval_bsdf under the general hint) on the lane's own direction, away from the horizon
+            import bsdf_truth
+            lanes_of = np.repeat(self.vi, LANES)
+            want_bw, clear_of_horizon = bsdf_truth.evaluate_direction(luts, bsdf_truth.Material(self.vertices, lanes_of), self.nrm[lanes_of], self.view[lanes_of],
+                                                                      d_ray.reshape(-1, 3))
+            want_bw, clear_of_horizon = want_bw.reshape(N, LANES, 3), clear_of_horizon.reshape(N, LANES) & np.isfinite(want_bw).all(axis=-1).reshape(N, LANES)
+            with np.errstate(all="ignore"):
+                rel64 = np.max(np.abs(bw - want_bw) / np.maximum(np.abs(want_bw), 1e-6), axis=-1)
+            held = ev & clear_of_horizon
+            fig["BSDF weight relative to the float64 evaluation"] = float(np.max(np.where(held & np.isfinite(rel64), rel64, 0.0)))
+            if bsdf_tolerance is not None:
+                fail["BSDF weight beyond its tolerance of the float64 evaluation"] = held & ~(rel64 <= bsdf_tolerance)
         # the outer reservoir and the sample
         with np.errstate(all="ignore"):
             wgt = np.where(ev, target * weight * fl[:, :, 6], 0.0)

@@ -88,6 +88,6 @@ def test_the_launcher_table_assigns_every_member_by_name():
     probe_pointers = re.findall(r"\(\*(\w+)\)\(", "\n".join(line.split("//")[0] for line in probes.splitlines()))
     body = impl[impl.index("make_probes() {"):impl.index("return p;")]
     assigned = dict(re.findall(r"\bp\.(\w+) = ([^;]+);", body))
-    assert probe_pointers == ["light_sample_probe"] and assigned == {p: p for p in probe_pointers}
+    assert probe_pointers == ["light_sample_probe", "bounce_probe"] and assigned == {p: p for p in probe_pointers}
     for p in probe_pointers:
         assert re.search(r"^static (?:int|void) %s\(" % p, impl, re.M), p

@@ -3,7 +3,8 @@ tests/light_truth.py, in both flavours and both forms of the shading kernel.
 
 What is held, per (vertex, sample id): the root pass's eight continuation words (picked child, 20-bit probability) and root_sum; per lane the tree's light and weight
 (descent included), the candidate's status, ray, solid angle, distance, emitted colour, direction probability, MIS weight and reservoir target; the outer reservoir's
-choice and the sample's colour. The BSDF weight has no float64 restatement: it is held to oracle_probe_bsdf_eval on the device's own directions.
+choice and the sample's colour. The BSDF weight is held to oracle_probe_bsdf_eval on the device's own directions and, with the same tolerance, to the float64
+evaluation of tests/bsdf_truth.py (eval_bsdf under the general hint) on them, away from the horizon where the packed face normal decides.
 
 Families: one mesh of flat emissive triangles over a small floor, identity instance, 1 .. 300 lights (7 / 8 / 9: the root's padding; 127 / 128: the key's last index;
 129 .. 300: nodes below the root; 257 / 300: lights past the LDS stage), powers over four decades (up to 64 lights) and some a million times below the strongest, one-sided and bidirectional emitters;
@@ -152,7 +153,7 @@ def family(n):
 @functools.lru_cache(maxsize=None)
 def yardstick(n):
     fam = family(n)
-    fail, fig = fam.truth.check(fam.oracle)
+    fail, fig = fam.truth.check(fam.oracle, luts=oracle_lib.golden_luts(), bsdf_tolerance=4.0 * FAST_MEASURED)
     return fail, fig
 
 
@@ -495,7 +496,7 @@ def test_gpu_light_samples_against_the_truth(n):
             if got is None:
                 continue
             fail, fig = fam.truth.check(got, yardstick=stick, factor=4.0, bsdf_reference=_bsdf_reference(fam, got),
-                                        bsdf_tolerance=(4.0 * FAST_MEASURED) if FAST_MEASURED is not None else None)
+                                        bsdf_tolerance=(4.0 * FAST_MEASURED) if FAST_MEASURED is not None else None, luts=oracle_lib.golden_luts())
             print("%d lights, %s flavour, %s form: %s" % (n, flavour, name, ", ".join("%s %.3g" % kv for kv in sorted(fig.items()))))
             if flavour == "fast":
                 _record("fast", "%d %s" % (n, name), fig)

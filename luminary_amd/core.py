@@ -1083,6 +1083,36 @@ class Core:
                    out.ctypes.data_as(C.c_void_p))
         return out
 
+    SKY_PROBE_RAY_WORDS, SKY_PROBE_WORDS, SKY_PROBE_HEAD_WORDS, SKY_PROBE_STEP_WORDS, SKY_PROBE_MAX_STEPS = 12, 628, 40, 49, 12
+
+    def sky_probe(self, rays):
+        """sky_get_color / sky_trace_inscattering on caller-made rays (lumc_sky_probe_host): rays [N, 12] uint32 words, out [N, 628] uint32 words - the path, the
+        march's stages, the celestial bodies' hits and the colour as include/lum_core.h lays them out."""
+        rays = np.ascontiguousarray(rays, dtype=np.uint32)
+        n = rays.shape[0]
+        assert rays.shape == (n, self.SKY_PROBE_RAY_WORDS)
+        out = np.zeros((n, self.SKY_PROBE_WORDS), dtype=np.uint32)
+        self._call("lumc_sky_probe_host", C.c_uint32(n), rays.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p))
+        return out
+
+    SUN_PROBE_WORDS = 64
+
+    def sun_probe(self, vertices, first_sample, samples):
+        """sample_sun on caller-made vertices (lumc_sun_probe_host): vertices [V, 20] uint32 words, out [V, samples, 64] uint32 words as include/lum_core.h lays them out"""
+        vertices = np.ascontiguousarray(vertices, dtype=np.uint32)
+        nv = vertices.shape[0]
+        assert vertices.shape == (nv, self.LIGHT_PROBE_VERTEX_WORDS)
+        out = np.zeros((nv, samples, self.SUN_PROBE_WORDS), dtype=np.uint32)
+        self._call("lumc_sun_probe_host", C.c_uint32(nv), vertices.ctypes.data_as(C.c_void_p), C.c_uint32(first_sample), C.c_uint32(samples), out.ctypes.data_as(C.c_void_p))
+        return out
+
+    def sky_math_probe(self, op, x):
+        """v_exp_f32 ("exp2"), v_sin_f32 ("sin") or v_cos_f32 ("cos") of float32 arguments (lumc_sky_math_probe_host); sin and cos take revolutions"""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        y = np.zeros_like(x)
+        self._call("lumc_sky_math_probe_host", C.c_uint32({"exp2": 0, "sin": 1, "cos": 2}[op]), C.c_uint32(x.size), x.ctypes.data_as(C.c_void_p), y.ctypes.data_as(C.c_void_p))
+        return y
+
     def trace_closest_device(self, n, origins_ptr, dirs_ptr, ignore_ptr, out_ptr, stream=0):
         self._call("lumc_trace_closest", C.c_uint32(n), C.c_void_p(origins_ptr), C.c_void_p(dirs_ptr), C.c_void_p(ignore_ptr), C.c_void_p(out_ptr),
                    C.c_void_p(stream))

@@ -4,7 +4,8 @@
 // (multiscattering LUT, [Hil20]), :338-446 (ray-marched single scattering + multiscattering), :508-515, :567-577 (sky_color_main),
 // cuda/sky_utils.cuh (spectrum of 8 wavelengths, LUT parametrisation, spectrum -> RGB), cuda/math.cuh:620-779 (sphere tests),
 // :1162-1239 (Henyey-Greenstein / Draine / Jendersie-Eon phase functions), :1429-1439 (solid angle of the sun).
-// Kept out: cloud shadows, aerial perspective (off by default), HDRI mode.
+// Also here: the cloud layers' shadow on the sun's single scattering (dev_cloud.h), aerial perspective (sky_trace_inscattering, off by default), HDRI mode
+// (the baked panorama as the sky, sky_hdri_color) and the sun's next-event estimation (sample_sun). The bake kernel marches the clouds and is in kernels_shared.h.
 // Numerics contract as everywhere: IEEE + - x / sqrt only; expf := exp2_det(x * log2 e); asinf(x) := atan2_det(x, sqrt(1 - x^2));
 // the LUTs are float4 pairs filtered in software (clamp addressing, exact lerps) instead of by the texture unit.
 #pragma once
@@ -351,7 +352,7 @@ LUM_DEV Spectrum sky_compute_atmosphere(const DeviceScene& sc, const SkyView& s,
     const bool has_moon = s.moon_albedo_tex != 0xFFFFFFFFu;
     const float moon_hit = has_moon ? sphere_int(ray, origin, s.moon_pos, kSkyMoonRadius) : kFltMax;
     if (earth_hit > sun_hit && moon_hit > sun_hit) result = sp_add(result, sp_mul(transmittance, sp_scale(sky_sun_radiance(), s.sun_strength)));
-    else if (earth_hit > moon_hit) {
+    else if (earth_hit > moon_hit) {  // (k_sky_probe's second walk, kernels.h, and the oracle's twin restate this branch statement for statement: change them together)
       const V3 moon_point = origin + ray * moon_hit;
       const V3 bounce_ray = normalize(s.sun_pos - moon_point);
       if (!sphere_hit(bounce_ray, moon_point, v3(0.0f, 0.0f, 0.0f), kSkyEarthRadius)) {

@@ -1931,6 +1931,284 @@ __global__ __launch_bounds__(kBlock) void k_bounce_probe(DeviceScene sc, uint32_
   }
 }
 
+// ---- standalone procedural sky for tests/test_sky_truth.py: one thread per caller-made ray, sky_get_color or sky_trace_inscattering exactly as k_sky and
+// k_sky_inscattering call them (dev_sky.h), with no sampler: every random number is an input ----
+// Per ray kSkyProbeRayWords: origin[3] (sky space, km), direction[3], limit, flags (1 celestials, 2 primary ray, 4 aerial perspective instead of sky_get_color, 8 the panorama: sky_hdri_color, see there),
+// steps (aerial perspective: the sky.steps to derive the step count from), random_offset, step_random, 0. Per thread kSkyProbeWordsPerThread:
+//   [0..5)    the second walk's path start and distance (sky_compute_path), the distance marched (min with limit - start), the step count, light_angle
+//   [5..11)   the one real call: its colour, and the record (0.75, 0.5, 0.25) as sky_trace_inscattering leaves it (untouched by sky_get_color)
+//   [11..25)  the second walk: final spectrum, its colour, the record
+//   [25..31)  celestials: sun, earth and moon hit distances, the moon point (0 not reached, 1 lit, 2 in the earth's shadow), the star cell (kSkyProbeNoCell: not
+//             reached), the sum of the hit stars' intensities
+//   [31..39)  the marched segment's transmittance; [39] 0
+//   [40 + 49 k ..) per step k < kSkyProbeMaxSteps: reach, height, cos_angle, zenith_cos, u, v, shadow, the Rayleigh and Mie phases, extinction_sun[8], ms_tex[8],
+//             step_t[8], result and transmittance after the step [8 + 8]
+// The second walk calls the functions sky_compute_atmosphere calls on the arguments it passes them: shipped code is untouched. It marches without cloud shadows, so
+// the two walks agree in a scene without active clouds only. Words of steps that were not reached keep the caller's zero.
+constexpr uint32_t kSkyProbeRayWords = 12, kSkyProbeHeadWords = 40, kSkyProbeStepWords = 49, kSkyProbeMaxSteps = 12;
+constexpr uint32_t kSkyProbeWordsPerThread = kSkyProbeHeadWords + kSkyProbeMaxSteps * kSkyProbeStepWords;
+constexpr uint32_t kSkyProbeNoCell = 0xFFFFFFFFu;
+LUM_DEV void probe_put(uint32_t* w, const Spectrum& s) {
+#pragma unroll
+  for (int i = 0; i < 8; i++) w[i] = fbits(s.v[i]);
+}
+__global__ __launch_bounds__(kBlock) void k_sky_probe(DeviceScene sc, uint32_t n, const uint32_t* rays, uint32_t* out) {
+  const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
+  if (t >= n) return;
+  const uint32_t* rw = rays + (size_t) t * kSkyProbeRayWords;
+  uint32_t* o = out + (size_t) t * kSkyProbeWordsPerThread;
+  SkyView s = sky_view(sc);
+  const V3 origin = v3(bitsf(rw[0]), bitsf(rw[1]), bitsf(rw[2])), ray = v3(bitsf(rw[3]), bitsf(rw[4]), bitsf(rw[5]));
+  const float limit = bitsf(rw[6]), random_offset = bitsf(rw[9]), step_random = bitsf(rw[10]);
+  const bool celestials = (rw[7] & 1u) != 0, primary_ray = (rw[7] & 2u) != 0, aerial = (rw[7] & 4u) != 0;
+  const Col record_in = col(0.75f, 0.5f, 0.25f);
+  if (rw[7] & 8u) {
+    // the panorama: sky_hdri_color on a WORLD-space origin with the path state in word 8, then a second walk over sky_hdri_sample and sky_sun_color:
+    //   [0..3) the origin in sky space; [11..15) theta, phi, u, v; [15], [16] the texel; [25] the sun's disk, [26] the earth (0 not asked, 1 hit, 2 missed);
+    //   [31..34) the texel's colour; [34..37) the sun's colour, [37], [38] its table coordinates
+    const uint32_t state = rw[8];
+    probe_put(o + 5, sky_hdri_color(sc, origin, ray, state)); probe_put(o + 8, record_in); probe_put(o + 22, record_in);
+    Col c = splat(0.0f);
+    if (sc.sky_hdri != nullptr) {
+      const float theta = atan2_det(ray.z, ray.x), phi = asin_det(ray.y);
+      const float u = (theta + kRefPi) / (2.0f * kRefPi);
+      const float v = 1.0f - ((phi + 0.5f * kRefPi) / kRefPi);
+      const float dim = (float) sc.sky_hdri_dim;
+      const uint32_t x = (uint32_t) ((u - floorf(u)) * dim) % sc.sky_hdri_dim, y = (uint32_t) ((v - floorf(v)) * dim) % sc.sky_hdri_dim;
+      const float4 t = sc.sky_hdri[x + (size_t) y * sc.sky_hdri_dim];
+      c = col(t.x, t.y, t.z);
+      o[11] = fbits(theta); o[12] = fbits(phi); o[13] = fbits(u); o[14] = fbits(v); o[15] = x; o[16] = y;
+      probe_put(o + 31, c);
+    }
+    if (state & (kStCameraDirection | kStAllowEmission)) {
+      const V3 sky_origin = world_to_sky(s, origin);
+      probe_put(o, sky_origin);
+      const bool disk = sphere_hit(ray, sky_origin, s.sun_pos, kSkySunRadius), earth = sph_hit_p0(ray, sky_origin, kSkyEarthRadius);
+      o[25] = disk ? 1u : 2u; o[26] = earth ? 1u : 2u;
+      if (disk && !earth) {
+        const float height = sky_height(sky_origin);
+        const float zenith_cos = dot(normalize(sky_origin), ray);
+        const F2 uv = sky_transmittance_uv(height, zenith_cos);
+        const Spectrum extinction_sun = sp_mul(sp_ident(), sky_lut_fetch(s.tm, kSkyTmWidth, kSkyTmHeight, uv.x, uv.y));
+        const Col sun_color = sky_color_from_spectrum(sp_mul(extinction_sun, sp_scale(sky_sun_radiance(), s.sun_strength)));
+        o[37] = fbits(uv.x); o[38] = fbits(uv.y);
+        probe_put(o + 34, sun_color);
+        c = c + sun_color;
+      }
+    }
+    probe_put(o + 19, c);
+    return;
+  }
+  // the real call
+  int steps = (int) rw[8];
+  Col record = record_in, real;
+  if (aerial) {
+    s.steps = rw[8];
+    real = sky_trace_inscattering(sc, s, origin, ray, limit, record, primary_ray, step_random, random_offset);
+    steps = (int) (fminf(fmaxf(0.5f, limit / (primary_ray ? 40.0f : 80.0f)), 2.0f) * (float) (s.steps / 6u) + step_random - 0.5f);
+  }
+  else real = sky_get_color(sc, s, origin, ray, limit, celestials, steps, random_offset);
+  probe_put(o + 5, real); probe_put(o + 8, record);
+  // the second walk over sky_compute_atmosphere
+  Spectrum result = sp_set1(0.0f);
+  const F2 path = sky_compute_path(origin, ray, kSkyEarthRadius, kSkyAtmoRadius);
+  const float start = path.x, distance = fminf(path.y, limit - start);
+  Spectrum transmittance = aerial ? sp_set1(1.0f) : sp_ident();  // (sky_compute_atmosphere starts at sp_ident and multiplies the caller's 1 by it)
+  Spectrum marched = sp_ident();
+  o[0] = fbits(start); o[1] = fbits(path.y); o[2] = fbits(distance); o[3] = (uint32_t) steps;
+  if (distance > 0.0f) {
+    float reach = start;
+    const float light_angle = sphere_solid_angle(s.sun_pos, kSkySunRadius, origin);
+    o[4] = fbits(light_angle);
+    for (int i = 0; i < steps; i++) {
+      const float new_reach = start + distance * (i + random_offset) / steps;
+      const float step_size = new_reach - reach;
+      reach = new_reach;
+      const V3 pos = origin + ray * reach;
+      const float height = sky_height(pos);
+      const V3 ray_scatter = normalize(s.sun_pos - pos);
+      const float cos_angle = dot(ray, ray_scatter);
+      const float zenith_cos = dot(normalize(pos), ray_scatter);
+      const float phase_r = sky_rayleigh_phase(cos_angle), phase_m = sky_mie_phase(s, cos_angle);
+      const float shadow = sph_hit_p0(ray_scatter, pos, kSkyEarthRadius) ? 0.0f : 1.0f;
+      const F2 uv = sky_transmittance_uv(height, zenith_cos);
+      const Spectrum extinction_sun = sky_lut_fetch(s.tm, kSkyTmWidth, kSkyTmHeight, uv.x, uv.y);
+      const SkyMedium m = sky_medium(s, height);
+      const Spectrum phase_times_scattering = sp_add(sp_scale(m.scattering_rayleigh, phase_r), sp_set1(m.scattering_mie * phase_m));
+      const Spectrum ss_radiance = sp_scale(sp_mul(extinction_sun, phase_times_scattering), shadow * light_angle);
+      const Spectrum ms_tex = sky_lut_fetch(s.ms, kSkyMsSize, kSkyMsSize, zenith_cos * 0.5f + 0.5f, height / kSkyAtmoHeight);
+      const Spectrum S = sp_add(ss_radiance, sp_mul(ms_tex, m.scattering));
+      const Spectrum step_t = sp_exp(sp_scale(m.extinction, -step_size));
+      const Spectrum s_int = sp_mul(sp_sub(S, sp_mul(S, step_t)), sp_inv(m.extinction));
+      result = sp_add(result, sp_mul(s_int, marched));
+      marched = sp_mul(marched, step_t);
+      if (i < (int) kSkyProbeMaxSteps) {
+        uint32_t* w = o + kSkyProbeHeadWords + (uint32_t) i * kSkyProbeStepWords;
+        w[0] = fbits(reach); w[1] = fbits(height); w[2] = fbits(cos_angle); w[3] = fbits(zenith_cos); w[4] = fbits(uv.x); w[5] = fbits(uv.y); w[6] = fbits(shadow);
+        w[7] = fbits(phase_r); w[8] = fbits(phase_m);
+        probe_put(w + 9, extinction_sun); probe_put(w + 17, ms_tex); probe_put(w + 25, step_t); probe_put(w + 33, result); probe_put(w + 41, marched);
+      }
+    }
+    result = sp_mul(result, sp_scale(sky_sun_radiance(), s.sun_strength));
+  }
+  probe_put(o + 31, marched);
+  o[29] = kSkyProbeNoCell;
+  if (celestials && !aerial) {
+    const float sun_hit = sphere_int(ray, origin, s.sun_pos, kSkySunRadius);
+    const float earth_hit = sph_int_p0(ray, origin, kSkyEarthRadius);
+    const bool has_moon = s.moon_albedo_tex != 0xFFFFFFFFu;
+    const float moon_hit = has_moon ? sphere_int(ray, origin, s.moon_pos, kSkyMoonRadius) : kFltMax;
+    o[25] = fbits(sun_hit); o[26] = fbits(earth_hit); o[27] = fbits(moon_hit);
+    if (earth_hit > sun_hit && moon_hit > sun_hit) result = sp_add(result, sp_mul(marched, sp_scale(sky_sun_radiance(), s.sun_strength)));
+    else if (earth_hit > moon_hit) {
+      const V3 moon_point = origin + ray * moon_hit;
+      const V3 bounce_ray = normalize(s.sun_pos - moon_point);
+      const bool lit = !sphere_hit(bounce_ray, moon_point, v3(0.0f, 0.0f, 0.0f), kSkyEarthRadius);
+      o[28] = lit ? 1u : 2u;
+      if (lit) {  // the shaded colour, as sky_compute_atmosphere has it (create_basis + transform_vec3, two texture fetches); the truth leaves it out
+        V3 normal = normalize(moon_point - s.moon_pos);
+        const float tex_u = 0.5f + s.moon_tex_offset + atan2_det(normal.z, normal.x) * (1.0f / (2.0f * kRefPi));
+        const float tex_v = 0.5f + asin_det(normal.y) * (1.0f / kRefPi);
+        const F2 uv = F2{tex_u, tex_v};
+        const float sign = copysignf(1.0f, normal.z);
+        const float a = -1.0f / (sign + normal.z);
+        const float b = normal.x * normal.y * a;
+        const V3 u1 = v3(1.0f + sign * normal.x * normal.x * a, sign * b, -sign * normal.x);
+        const V3 u2 = v3(b, sign + normal.y * normal.y * a, -normal.y);
+        const float4 nv = texture_load(sc, s.moon_normal_tex, uv, true, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+        const V3 mn = v3(nv.x * 2.0f - 1.0f, nv.y * 2.0f - 1.0f, nv.z * 2.0f - 1.0f);
+        normal = normalize(v3(u1.x * mn.x + u2.x * mn.y + normal.x * mn.z, u1.y * mn.x + u2.y * mn.y + normal.y * mn.z, u1.z * mn.x + u2.z * mn.y + normal.z * mn.z));
+        const float NdotL = dot(normal, bounce_ray);
+        if (NdotL > 0.0f) {
+          const float albedo = texture_load(sc, s.moon_albedo_tex, uv, true, make_float4(0.0f, 0.0f, 0.0f, 0.0f)).x;
+          const float light_angle = sphere_solid_angle(s.sun_pos, kSkySunRadius, moon_point);
+          const float weight = albedo * s.sun_strength * NdotL * light_angle / (2.0f * kRefPi);
+          result = sp_add(result, sp_mul(marched, sp_mul(sky_moon_solar_flux(), sp_scale(sky_sun_radiance(), weight))));
+        }
+      }
+    }
+    if (s.stars != nullptr && sun_hit == kFltMax && earth_hit == kFltMax && moon_hit == kFltMax) {
+      const float ray_altitude = asin_det(ray.y);
+      const float ray_azimuth = atan2_det(-ray.z, -ray.x) + kRefPi;
+      const uint32_t x = f2u_sat(ray_azimuth * 10.0f), y = f2u_sat((ray_altitude + kRefPi * 0.5f) * 10.0f);
+      const uint32_t grid = min(x, 63u) + min(y, 31u) * 64u;
+      const uint32_t first = s.stars_offsets[grid], last = s.stars_offsets[grid + 1u];
+      float star_sum = 0.0f;
+      for (uint32_t i = first; i < last; i++) {
+        const float4 star = s.stars[i];
+        const V3 star_pos = angles_to_direction(star.x, star.y);
+        if (sphere_hit(ray, v3(0.0f, 0.0f, 0.0f), star_pos, star.z)) {
+          result = sp_add(result, sp_scale(marched, star.w * s.stars_intensity));
+          star_sum += star.w * s.stars_intensity;
+        }
+      }
+      o[29] = grid; o[30] = fbits(star_sum);
+    }
+  }
+  transmittance = sp_mul(transmittance, marched);
+  probe_put(o + 11, result);
+  const Col walk = sky_color_from_spectrum(result);
+  probe_put(o + 19, aerial ? walk * record_in : walk);
+  probe_put(o + 22, aerial ? record_in * sky_color_from_spectrum(transmittance) : record_in);
+}
+// ---- the sun's next-event estimation for the same test: one thread per (vertex, sample id) on the light probe's caller-made vertices, sample_sun exactly as k_shade
+// calls it (dev_sky.h), then a second walk over the functions it calls. Per thread kSunProbeWordsPerThread:
+//   [0..7)   the real call: returned, light[3], direction[3]
+//   [7..14)  sky_pos, the below-horizon and inside-earth flags (0 / 1), the reflection and refraction probabilities
+//   [14..21) the shading frame: quaternion, local V
+//   [21..27) the sampler's numbers: method, the BSDF pair, the sun pair, resampling
+//   [27..35) the BSDF candidate: local ray, technique (0 reflection, 1 refraction, 2 refraction that reflects totally), world direction, the disk (1 hit, 2 missed)
+//   [35..41) its sun colour and eval_bsdf (0 where the disk is missed)
+//   [41..51) the solid-angle candidate: direction, solid angle, sun colour, eval_bsdf
+//   [51..58) sun_bsdf_pdf of the two, the two MIS terms, the two weights, their sum
+//   [58..63) the choice (0 none, 1 BSDF, 2 solid angle), the light, returned; [63] 1 where the vertex sees the sun at all
+constexpr uint32_t kSunProbeWordsPerThread = 64;
+__global__ __launch_bounds__(kBlock) void k_sun_probe(DeviceScene sc, uint32_t n, uint32_t samples, uint32_t first_sample, const uint32_t* vertices, uint32_t* out) {
+  const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  const uint32_t* vw = vertices + (size_t) (i / samples) * kLightProbeVertexWords;
+  uint32_t* o = out + (size_t) i * kSunProbeWordsPerThread;
+  GeoContext g;
+  g.instance_id = vw[16]; g.tri_id = vw[17];
+  g.position = v3(bitsf(vw[0]), bitsf(vw[1]), bitsf(vw[2]));
+  g.normal = normalize(v3(bitsf(vw[3]), bitsf(vw[4]), bitsf(vw[5])));
+  g.V = normalize(v3(bitsf(vw[6]), bitsf(vw[7]), bitsf(vw[8])));
+  g.face_normal_packed = normal_pack(g.normal);
+  g.state = 0;
+  g.params.flags = vw[15];
+  g.params.set(col(bitsf(vw[9]), bitsf(vw[10]), bitsf(vw[11])), bitsf(vw[12]), bitsf(vw[13]), splat(0.0f), bitsf(vw[14]));
+  const SamplerT<false> smp{sc.bluenoise_2d, vw[18], vw[19], first_sample + i % samples, 0u};
+  const SkyView sky = sky_view(sc);
+  const LocalFrame lf = local_frame(sc, g);
+  // the real call
+  Col real_light = splat(0.0f);
+  V3 real_dir = v3(0.0f, 0.0f, 0.0f);
+  const bool real = sample_sun(sc, sky, lf, g, smp, real_light, real_dir);
+  o[0] = real ? 1u : 0u;
+  if (real) { probe_put(o + 1, real_light); probe_put(o + 4, real_dir); }
+  // the second walk
+  const Energy energy = energy_terms(sc, g.params, world_ndotv(g));
+  const V3 sky_pos = world_to_sky(sky, g.position);
+  const bool sun_below_horizon = sph_hit_p0(normalize(sky.sun_pos - sky_pos), sky_pos, kSkyEarthRadius);
+  const bool inside_earth = length(sky_pos) < kSkyEarthRadius;
+  probe_put(o + 7, sky_pos); o[10] = sun_below_horizon ? 1u : 0u; o[11] = inside_earth ? 1u : 0u;
+  const MatParams& p = g.params;
+  const bool translucent = (p.flags & kMatSubstrateMask) == kMatTranslucent;
+  const float w_refl = 1.0f, w_refr = translucent ? 1.0f : 0.0f;
+  const float reflection_prob = w_refl / (w_refl + w_refr), refraction_prob = w_refr / (w_refl + w_refr);
+  o[12] = fbits(reflection_prob); o[13] = fbits(refraction_prob);
+  o[14] = fbits(lf.to_z.x); o[15] = fbits(lf.to_z.y); o[16] = fbits(lf.to_z.z); o[17] = fbits(lf.to_z.w);
+  probe_put(o + 18, lf.V);
+  if (sun_below_horizon || inside_earth) return;
+  o[63] = 1u;
+  const float roughness = p.roughness();
+  const float method = smp.next1(kRndSunBsdfMethod), resampling = smp.next1(kRndSunResampling);
+  const F2 r_bsdf = smp.next2(kRndSunBsdf), r_sun = smp.next2(kRndSunRay);
+  o[21] = fbits(method); o[22] = fbits(r_bsdf.x); o[23] = fbits(r_bsdf.y); o[24] = fbits(r_sun.x); o[25] = fbits(r_sun.y); o[26] = fbits(resampling);
+  V3 ray_local;
+  uint32_t technique = 0;
+  if (method < reflection_prob) ray_local = reflect(lf.V, sample_vndf_bounded(lf.V, roughness, r_bsdf));
+  else { bool total_reflection; ray_local = refract(lf.V, sample_vndf_caps(lf.V, roughness, r_bsdf), p.ior(), total_reflection); technique = total_reflection ? 2u : 1u; }
+  const V3 dir_bsdf = normalize(qapply(qinv(lf.to_z), ray_local));
+  probe_put(o + 27, ray_local); o[30] = technique; probe_put(o + 31, dir_bsdf);
+  Col light_bsdf = splat(0.0f);
+  bool is_refraction;
+  const bool disk = sphere_hit(dir_bsdf, sky_pos, sky.sun_pos, kSkySunRadius);
+  o[34] = disk ? 1u : 2u;
+  if (disk) {
+    const Col sun = sky_sun_color(sky, sky_pos, dir_bsdf), ev = eval_bsdf(energy, g, dir_bsdf, kHintGeneral, is_refraction, 1.0f);
+    probe_put(o + 35, sun); probe_put(o + 38, ev);
+    light_bsdf = sun * ev;
+  }
+  float solid_angle;
+  const V3 dir_sa = sample_sphere(sky.sun_pos, kSkySunRadius, sky_pos, r_sun, solid_angle);
+  const Col sun_sa = sky_sun_color(sky, sky_pos, dir_sa), ev_sa = eval_bsdf(energy, g, dir_sa, kHintGeneral, is_refraction, 1.0f);
+  const Col light_sa = sun_sa * ev_sa;
+  probe_put(o + 41, dir_sa); o[44] = fbits(solid_angle); probe_put(o + 45, sun_sa); probe_put(o + 48, ev_sa);
+  const float target_bsdf = importance(light_bsdf), target_sa = importance(light_sa);
+  const float pdf_bsdf = sun_bsdf_pdf(g, dir_bsdf, reflection_prob, refraction_prob), pdf_sa = sun_bsdf_pdf(g, dir_sa, reflection_prob, refraction_prob);
+  const float mis_bsdf = solid_angle / (pdf_bsdf * solid_angle + 1.0f);
+  const float mis_sa = solid_angle / (pdf_sa * solid_angle + 1.0f);
+  const float weight_bsdf = target_bsdf * mis_bsdf, weight_sa = target_sa * mis_sa;
+  const float sum_weights = weight_bsdf + weight_sa;
+  o[51] = fbits(pdf_bsdf); o[52] = fbits(pdf_sa); o[53] = fbits(mis_bsdf); o[54] = fbits(mis_sa); o[55] = fbits(weight_bsdf); o[56] = fbits(weight_sa); o[57] = fbits(sum_weights);
+  if (sum_weights == 0.0f) return;
+  float target;
+  Col light;
+  if (resampling * sum_weights < weight_bsdf) { o[58] = 1u; target = target_bsdf; light = light_bsdf; }
+  else { o[58] = 2u; target = target_sa; light = light_sa; }
+  light = light * (sum_weights / target);
+  probe_put(o + 59, light);
+  o[62] = (target == 0.0f || importance(light) == 0.0f) ? 0u : 1u;
+}
+// The hardware's transcendental instructions alone, for the same test: y = v_exp_f32 (op 0), v_sin_f32 (1) or v_cos_f32 (2) of x, whatever the unit's flavour.
+__global__ __launch_bounds__(kBlock) void k_sky_math_probe(uint32_t n, uint32_t op, const float* __restrict__ x, float* __restrict__ y) {
+  const uint32_t t = blockIdx.x * kBlock + threadIdx.x;
+  if (t >= n) return;
+  const float v = x[t];
+  y[t] = (op == 0u) ? __builtin_amdgcn_exp2f(v) : (op == 1u) ? __builtin_amdgcn_sinf(v) : __builtin_amdgcn_cosf(v);
+}
+
 // The Sobol / Owen pairs of one pass (dev_sampler.h LUM_SOBOL_TABLE): one thread per (dimension, sample id).
 __global__ __launch_bounds__(256) void k_sobol_table(uint2* __restrict__ table, uint32_t first_sample, uint32_t count, uint32_t stride, uint32_t dims) {
   const uint32_t t = blockIdx.x * 256u + threadIdx.x;

@@ -107,13 +107,25 @@ struct WavefrontProbes {
   // sample_bounce and sample_light_direction on the same vertices, one (vertex, sample id) per thread (k_bounce_probe, kernels.h: 20 words in per vertex, 143 out per thread)
   void (*bounce_probe)(hipStream_t s, const DeviceScene& sc, uint32_t n_vertices, uint32_t samples, uint32_t first_sample, const uint32_t* vertices, uint32_t* out);
 };
+// The sky's probes (tests/test_sky_truth.py), a table of their own for the same reason
+struct WavefrontSkyProbes {
+  // sky_get_color or sky_trace_inscattering on n caller-made rays, one per thread (k_sky_probe, kernels.h: 12 words in per ray, 628 out per thread)
+  void (*sky_probe)(hipStream_t s, const DeviceScene& sc, uint32_t n, const uint32_t* rays, uint32_t* out);
+  // sample_sun on the light probe's caller-made vertices, one (vertex, sample id) per thread (k_sun_probe, kernels.h: 20 words in per vertex, 64 out per thread)
+  void (*sun_probe)(hipStream_t s, const DeviceScene& sc, uint32_t n_vertices, uint32_t samples, uint32_t first_sample, const uint32_t* vertices, uint32_t* out);
+  // v_exp_f32 (op 0), v_sin_f32 (1), v_cos_f32 (2) of n arguments (k_sky_math_probe)
+  void (*sky_math_probe)(hipStream_t s, uint32_t n, uint32_t op, const float* x, float* y);
+};
 constexpr uint32_t kLightSampleProbeVertexWords = 20, kLightSampleProbeWords = 154;  // that probe's words per vertex (in) and per thread (out)
 constexpr uint32_t kBounceProbeWords = 143;                                          // the bounce probe's words per thread (its vertex is the light probe's)
+constexpr uint32_t kSkyProbeInWords = 12, kSkyProbeWords = 628, kSunProbeWords = 64;                      // the sky probe's words per ray (in) and per thread (out)
 
 const WavefrontKernels* wavefront_kernels_exact();  // csrc/device/wavefront_exact.hip
 const WavefrontKernels* wavefront_kernels_fast();   // csrc/device/wavefront_fast.hip
 const WavefrontProbes* wavefront_probes_exact();
 const WavefrontProbes* wavefront_probes_fast();
+const WavefrontSkyProbes* wavefront_sky_probes_exact();
+const WavefrontSkyProbes* wavefront_sky_probes_fast();
 // The vector registers per lane (hipFuncGetAttributes numRegs) of a flavour's closest-hit kernel in the given form and of its k_light_query, on the current device:
 // what the host asks before it lets the two run side by side (csrc/host/context.h overlap_registers_fit). They return a hipError_t.
 int ray_kernel_registers_exact(bool single_level, uint32_t* trace_regs, uint32_t* light_query_regs);

@@ -187,6 +187,18 @@ static void bounce_probe(hipStream_t s, const DeviceScene& sc, uint32_t n_vertic
   const uint32_t n = n_vertices * samples;
   hipLaunchKernelGGL(k_bounce_probe, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, sc, n, samples, first_sample, vertices, out);
 }
+static void sky_probe(hipStream_t s, const DeviceScene& sc, uint32_t n, const uint32_t* rays, uint32_t* out) {
+  static_assert(kSkyProbeWordsPerThread == kSkyProbeWords && kSkyProbeRayWords == kSkyProbeInWords, "the host layer sizes the probe's buffers by these");
+  hipLaunchKernelGGL(k_sky_probe, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, sc, n, rays, out);
+}
+static void sun_probe(hipStream_t s, const DeviceScene& sc, uint32_t n_vertices, uint32_t samples, uint32_t first_sample, const uint32_t* vertices, uint32_t* out) {
+  static_assert(kSunProbeWordsPerThread == kSunProbeWords, "the host layer sizes the probe's buffers by this");
+  const uint32_t n = n_vertices * samples;
+  hipLaunchKernelGGL(k_sun_probe, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, sc, n, samples, first_sample, vertices, out);
+}
+static void sky_math_probe(hipStream_t s, uint32_t n, uint32_t op, const float* x, float* y) {
+  hipLaunchKernelGGL(k_sky_math_probe, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, n, op, x, y);
+}
 
 // Filled by member name: neighbouring members share a function-pointer type (resolve / resolve_listed, particle_shade / ocean_shade, sky_inscattering / clouds),
 // so a positional list with two of them swapped would compile. tests/test_build_units.py checks that no member stays null.
@@ -210,6 +222,12 @@ static constexpr WavefrontProbes make_probes() {
   return p;
 }
 static constexpr WavefrontProbes kProbes = make_probes();
+static constexpr WavefrontSkyProbes make_sky_probes() {
+  WavefrontSkyProbes q{};
+  q.sky_probe = sky_probe; q.sun_probe = sun_probe; q.sky_math_probe = sky_math_probe;
+  return q;
+}
+static constexpr WavefrontSkyProbes kSkyProbes = make_sky_probes();
 
 }  // namespace table
 LUM_NS_END
@@ -250,10 +268,12 @@ namespace lum {
 #if LUM_FAST
 const WavefrontKernels* wavefront_kernels_fast() { return &fast::table::kTable; }
 const WavefrontProbes* wavefront_probes_fast() { return &fast::table::kProbes; }
+const WavefrontSkyProbes* wavefront_sky_probes_fast() { return &fast::table::kSkyProbes; }
 int ray_kernel_registers_fast(bool single_level, uint32_t* trace_regs, uint32_t* light_query_regs) { return fast::table::ray_kernel_registers(single_level, trace_regs, light_query_regs); }
 #else
 int ray_kernel_registers_exact(bool single_level, uint32_t* trace_regs, uint32_t* light_query_regs) { return exact::table::ray_kernel_registers(single_level, trace_regs, light_query_regs); }
 const WavefrontKernels* wavefront_kernels_exact() { return &exact::table::kTable; }
 const WavefrontProbes* wavefront_probes_exact() { return &exact::table::kProbes; }
+const WavefrontSkyProbes* wavefront_sky_probes_exact() { return &exact::table::kSkyProbes; }
 #endif
 }  // namespace lum

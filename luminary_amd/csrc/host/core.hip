@@ -1502,6 +1502,69 @@ int lumc_bounce_probe_host(LumContext* ctx, uint32_t num_vertices, const uint32_
   return 0;
 }
 
+// sky_get_color or sky_trace_inscattering (dev_sky.h) on caller-made rays in the active flavour, with the march's stages: out holds LUMC_SKY_PROBE_WORDS words per
+// ray, zero where a stage was not reached (k_sky_probe, kernels.h). The scene is in sky mode DEFAULT or HDRI with the two tables on the device, and has no active clouds.
+int lumc_sky_probe_host(LumContext* ctx, uint32_t num_rays, const uint32_t* rays, uint32_t* out) {
+  static_assert(LUMC_SKY_PROBE_WORDS == kSkyProbeWords && LUMC_SKY_PROBE_RAY_WORDS == kSkyProbeInWords, "lum_core.h and wavefront_table.h");
+  static_assert(LUMC_SKY_PROBE_WORDS == LUMC_SKY_PROBE_HEAD_WORDS + LUMC_SKY_PROBE_MAX_STEPS * LUMC_SKY_PROBE_STEP_WORDS, "lum_core.h");
+  if (!ctx || !ctx->has_scene) { if (ctx) ctx->error = "lumc_sky_probe_host: no scene"; return 1; }
+  if (num_rays == 0) return 0;
+  if (!rays || !out) { ctx->error = "lumc_sky_probe_host: null argument"; return 1; }
+  const DeviceScene& sc = ctx->scene;
+  if (!sc.sky_lut_transmittance || !sc.sky_lut_multiscattering) { ctx->error = "lumc_sky_probe_host: the scene has no sky tables"; return 1; }
+  if (sc.cloud_active) { ctx->error = "lumc_sky_probe_host: the probe marches without cloud shadows"; return 1; }
+  if (num_rays > (1u << 20)) { ctx->error = "lumc_sky_probe_host: more than 2^20 rays"; return 1; }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  DeviceBuffer<uint32_t> d_r, d_out;
+  HIP_TRY(ctx, d_r.assign(rays, (size_t) num_rays * kSkyProbeInWords));
+  HIP_TRY(ctx, d_out.resize((size_t) num_rays * kSkyProbeWords));
+  HIP_TRY(ctx, hipMemset(d_out.get(), 0, sizeof(uint32_t) * num_rays * kSkyProbeWords));
+  (ctx->wf == wavefront_kernels_exact() ? wavefront_sky_probes_exact() : wavefront_sky_probes_fast())->sky_probe(nullptr, sc, num_rays, d_r.get(), d_out.get());
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipDeviceSynchronize());
+  HIP_TRY(ctx, hipMemcpy(out, d_out.get(), sizeof(uint32_t) * num_rays * kSkyProbeWords, hipMemcpyDeviceToHost));
+  return 0;
+}
+// sample_sun (dev_sky.h) on the light probe's caller-made vertices in the active flavour, with its stages: LUMC_SUN_PROBE_WORDS words per (vertex, sample id), zero where
+// a stage was not reached (k_sun_probe, kernels.h). The scene has the sky and the energy tables and no active clouds.
+int lumc_sun_probe_host(LumContext* ctx, uint32_t num_vertices, const uint32_t* vertices, uint32_t first_sample, uint32_t samples, uint32_t* out) {
+  static_assert(LUMC_SUN_PROBE_WORDS == kSunProbeWords, "lum_core.h and wavefront_table.h");
+  if (!ctx || !ctx->has_scene) { if (ctx) ctx->error = "lumc_sun_probe_host: no scene"; return 1; }
+  if (num_vertices == 0 || samples == 0) return 0;
+  if (!vertices || !out) { ctx->error = "lumc_sun_probe_host: null argument"; return 1; }
+  const DeviceScene& sc = ctx->scene;
+  if (!sc.bluenoise_2d || !sc.lut_conductor || !sc.lut_glossy || !sc.lut_dielectric || !sc.lut_dielectric_inv) { ctx->error = "lumc_sun_probe_host: the scene has no energy tables"; return 1; }
+  if (!sc.sky_lut_transmittance) { ctx->error = "lumc_sun_probe_host: the scene has no sky tables"; return 1; }
+  if (sc.cloud_active) { ctx->error = "lumc_sun_probe_host: the probe's scene has no clouds"; return 1; }
+  const size_t n = (size_t) num_vertices * samples;
+  if (n > (1u << 22)) { ctx->error = "lumc_sun_probe_host: more than 2^22 threads"; return 1; }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  DeviceBuffer<uint32_t> d_v, d_out;
+  HIP_TRY(ctx, d_v.assign(vertices, (size_t) num_vertices * kLightSampleProbeVertexWords));
+  HIP_TRY(ctx, d_out.resize(n * kSunProbeWords));
+  HIP_TRY(ctx, hipMemset(d_out.get(), 0, sizeof(uint32_t) * n * kSunProbeWords));
+  (ctx->wf == wavefront_kernels_exact() ? wavefront_sky_probes_exact() : wavefront_sky_probes_fast())->sun_probe(nullptr, sc, num_vertices, samples, first_sample, d_v.get(), d_out.get());
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipDeviceSynchronize());
+  HIP_TRY(ctx, hipMemcpy(out, d_out.get(), sizeof(uint32_t) * n * kSunProbeWords, hipMemcpyDeviceToHost));
+  return 0;
+}
+// The hardware's v_exp_f32 (op 0), v_sin_f32 (1) and v_cos_f32 (2) on caller-made arguments (k_sky_math_probe): what the fast flavour's exp2_det and sincos_det issue.
+int lumc_sky_math_probe_host(LumContext* ctx, uint32_t op, uint32_t count, const float* x, float* y) {
+  if (!ctx) return 1;
+  if (count == 0) return 0;
+  if (!x || !y || op > 2u) { ctx->error = "lumc_sky_math_probe_host: bad argument"; return 1; }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  DeviceBuffer<float> d_x, d_y;
+  HIP_TRY(ctx, d_x.assign(x, count));
+  HIP_TRY(ctx, d_y.resize(count));
+  wavefront_sky_probes_fast()->sky_math_probe(nullptr, count, op, d_x.get(), d_y.get());
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipDeviceSynchronize());
+  HIP_TRY(ctx, hipMemcpy(y, d_y.get(), sizeof(float) * count, hipMemcpyDeviceToHost));
+  return 0;
+}
+
 int lumc_pixel_query(LumContext* ctx, uint32_t x, uint32_t y, uint32_t sample_id, uint32_t out[6]) {
   if (!ctx || !ctx->has_scene || !out) { if (ctx) ctx->error = "lumc_pixel_query: no scene"; return 1; }
   if (x >= ctx->scene.width || y >= ctx->scene.height) { ctx->error = "lumc_pixel_query: pixel outside the frame"; return 1; }

@@ -1645,6 +1645,250 @@ void oracle_probe_bounce_stages(const OracleScene* s, uint32_t num_vertices, con
     }
   }
 }
+/* sky_get_color / sky_trace_inscattering with the march's stages on caller-made rays: the words of the device's probe (include/lum_core.h lumc_sky_probe_host), in
+ * its layout. The head holds the result of the function itself; the stages are what sky_compute_atmosphere computed on the way, restated here statement for statement
+ * from the functions it calls, without cloud shadows (the scene has no active clouds). */
+static void put_spectrum(uint32_t* w, Spectrum s) { for (int i = 0; i < 8; i++) w[i] = f_bits(s.v[i]); }
+void oracle_probe_sky_stages(const OracleScene* scene, uint32_t num_rays, const uint32_t* rays, uint32_t* out) {
+  memset(out, 0, sizeof(uint32_t) * (size_t) ORACLE_SKY_PROBE_WORDS * num_rays);
+  for (uint32_t t = 0; t < num_rays; t++) {
+    const uint32_t* rw = rays + (size_t) ORACLE_SKY_PROBE_RAY_WORDS * t;
+    uint32_t* o = out + (size_t) ORACLE_SKY_PROBE_WORDS * t;
+    float f[12]; memcpy(f, rw, sizeof(f));
+    OSky sky = osky_view(scene);
+    OSky* s = &sky;
+    const vec3 origin = v3(f[0], f[1], f[2]), ray = v3(f[3], f[4], f[5]);
+    const float limit = f[6], random_offset = f[9], step_random = f[10];
+    const bool celestials = (rw[7] & 1u) != 0, primary_ray = (rw[7] & 2u) != 0, aerial = (rw[7] & 4u) != 0;
+    const RGBF record_in = c3(0.75f, 0.5f, 0.25f);
+    if (rw[7] & 8u) { /* the panorama: sky_hdri_color on a world-space origin with the path state in word 8, and its stages */
+      const uint32_t state = rw[8];
+      put_rgb(o + 5, sky_hdri_color(scene, origin, ray, state)); put_rgb(o + 8, record_in); put_rgb(o + 22, record_in);
+      RGBF c = c_splat(0.0f);
+      if (scene->sky_hdri && scene->sky_hdri_dim) {
+        const float theta = o_atan2(ray.z, ray.x), phi = o_asin(ray.y);
+        const float u = (theta + REF_PI) / (2.0f * REF_PI);
+        const float v = 1.0f - ((phi + 0.5f * REF_PI) / REF_PI);
+        const float dim = (float) scene->sky_hdri_dim;
+        const uint32_t x = (uint32_t) ((u - floorf(u)) * dim) % scene->sky_hdri_dim, y = (uint32_t) ((v - floorf(v)) * dim) % scene->sky_hdri_dim;
+        const float* tx = scene->sky_hdri + 4 * ((size_t) x + (size_t) y * scene->sky_hdri_dim);
+        c = c3(tx[0], tx[1], tx[2]);
+        o[11] = f_bits(theta); o[12] = f_bits(phi); o[13] = f_bits(u); o[14] = f_bits(v); o[15] = x; o[16] = y;
+        put_rgb(o + 31, c);
+      }
+      if (state & (ST_CAMERA_DIRECTION | ST_ALLOW_EMISSION)) {
+        const vec3 sky_origin = world_to_sky(s, origin);
+        put3(o, sky_origin);
+        const bool disk = sphere_hit(ray, sky_origin, s->sun_pos, SKY_SUN_RADIUS), earth = sph_hit_p0(ray, sky_origin, SKY_EARTH_RADIUS);
+        o[25] = disk ? 1u : 2u; o[26] = earth ? 1u : 2u;
+        if (disk && !earth) {
+          const float height = sky_height(sky_origin);
+          const float zenith_cos = v_dot(v_norm(sky_origin), ray);
+          const float2_t uv = sky_transmittance_uv(height, zenith_cos);
+          const Spectrum extinction_sun = sp_mul(SP_IDENT, sky_lut_fetch(s->tm, SKY_TM_W, SKY_TM_H, uv.x, uv.y));
+          const RGBF sun_color = sky_color_from_spectrum(sp_mul(extinction_sun, sp_scale(SKY_SUN_RADIANCE, s->sun_strength)));
+          o[37] = f_bits(uv.x); o[38] = f_bits(uv.y);
+          put_rgb(o + 34, sun_color);
+          c = c_add(c, sun_color);
+        }
+      }
+      put_rgb(o + 19, c);
+      continue;
+    }
+    int steps = (int) rw[8];
+    RGBF record = record_in, real;
+    if (aerial) {
+      s->steps = rw[8];
+      real = sky_trace_inscattering(s, origin, ray, limit, &record, primary_ray, step_random, random_offset);
+      steps = (int) (fminf(fmaxf(0.5f, limit / (primary_ray ? 40.0f : 80.0f)), 2.0f) * (float) (s->steps / 6u) + step_random - 0.5f);
+    }
+    else real = sky_get_color(s, origin, ray, limit, celestials, steps, random_offset);
+    put_rgb(o + 5, real); put_rgb(o + 8, record);
+    Spectrum result = sp_set1(0.0f);
+    const float2_t path = sky_compute_path(origin, ray, SKY_EARTH_RADIUS, SKY_ATMO_RADIUS);
+    const float start = path.x, distance = fminf(path.y, limit - start);
+    Spectrum marched = SP_IDENT;
+    o[0] = f_bits(start); o[1] = f_bits(path.y); o[2] = f_bits(distance); o[3] = (uint32_t) steps;
+    if (distance > 0.0f) {
+      float reach = start;
+      const float light_angle = sphere_solid_angle(s->sun_pos, SKY_SUN_RADIUS, origin);
+      o[4] = f_bits(light_angle);
+      for (int i = 0; i < steps; i++) {
+        const float new_reach = start + distance * (i + random_offset) / steps;
+        const float step_size = new_reach - reach;
+        reach = new_reach;
+        const vec3 pos = v_add(origin, v_scale(ray, reach));
+        const float height = sky_height(pos);
+        const vec3 ray_scatter = v_norm(v_sub(s->sun_pos, pos));
+        const float cos_angle = v_dot(ray, ray_scatter);
+        const float zenith_cos = v_dot(v_norm(pos), ray_scatter);
+        const float phase_r = sky_rayleigh_phase(cos_angle), phase_m = sky_mie_phase(s, cos_angle);
+        const float shadow = sph_hit_p0(ray_scatter, pos, SKY_EARTH_RADIUS) ? 0.0f : 1.0f;
+        const float2_t uv = sky_transmittance_uv(height, zenith_cos);
+        const Spectrum extinction_sun = sky_lut_fetch(s->tm, SKY_TM_W, SKY_TM_H, uv.x, uv.y);
+        const SkyMedium m = sky_medium(s, height);
+        const Spectrum phase_times_scattering = sp_add(sp_scale(m.scattering_rayleigh, phase_r), sp_set1(m.scattering_mie * phase_m));
+        const Spectrum ss_radiance = sp_scale(sp_mul(extinction_sun, phase_times_scattering), shadow * light_angle);
+        const Spectrum ms_tex = sky_lut_fetch(s->ms, SKY_MS_SIZE, SKY_MS_SIZE, zenith_cos * 0.5f + 0.5f, height / SKY_ATMO_HEIGHT);
+        const Spectrum S = sp_add(ss_radiance, sp_mul(ms_tex, m.scattering));
+        const Spectrum step_t = sp_exp(sp_scale(m.extinction, -step_size));
+        const Spectrum s_int = sp_mul(sp_sub(S, sp_mul(S, step_t)), sp_inv(m.extinction));
+        result = sp_add(result, sp_mul(s_int, marched));
+        marched = sp_mul(marched, step_t);
+        if (i < ORACLE_SKY_PROBE_MAX_STEPS) {
+          uint32_t* w = o + ORACLE_SKY_PROBE_HEAD_WORDS + i * ORACLE_SKY_PROBE_STEP_WORDS;
+          w[0] = f_bits(reach); w[1] = f_bits(height); w[2] = f_bits(cos_angle); w[3] = f_bits(zenith_cos); w[4] = f_bits(uv.x); w[5] = f_bits(uv.y); w[6] = f_bits(shadow);
+          w[7] = f_bits(phase_r); w[8] = f_bits(phase_m);
+          put_spectrum(w + 9, extinction_sun); put_spectrum(w + 17, ms_tex); put_spectrum(w + 25, step_t); put_spectrum(w + 33, result); put_spectrum(w + 41, marched);
+        }
+      }
+      result = sp_mul(result, sp_scale(SKY_SUN_RADIANCE, s->sun_strength));
+    }
+    put_spectrum(o + 31, marched);
+    o[29] = 0xFFFFFFFFu;
+    if (celestials && !aerial) {
+      const float sun_hit = sphere_int(ray, origin, s->sun_pos, SKY_SUN_RADIUS);
+      const float earth_hit = sph_int_p0(ray, origin, SKY_EARTH_RADIUS);
+      const bool has_moon = s->moon_albedo_tex != 0xFFFFFFFFu;
+      const float moon_hit = has_moon ? sphere_int(ray, origin, s->moon_pos, SKY_MOON_RADIUS) : FLT_MAX;
+      o[25] = f_bits(sun_hit); o[26] = f_bits(earth_hit); o[27] = f_bits(moon_hit);
+      if (earth_hit > sun_hit && moon_hit > sun_hit) result = sp_add(result, sp_mul(marched, sp_scale(SKY_SUN_RADIANCE, s->sun_strength)));
+      else if (earth_hit > moon_hit) {
+        const vec3 moon_point = v_add(origin, v_scale(ray, moon_hit));
+        const vec3 bounce_ray = v_norm(v_sub(s->sun_pos, moon_point));
+        const bool lit = !sphere_hit(bounce_ray, moon_point, v3(0.0f, 0.0f, 0.0f), SKY_EARTH_RADIUS);
+        o[28] = lit ? 1u : 2u;
+        if (lit) {
+          vec3 normal = v_norm(v_sub(moon_point, s->moon_pos));
+          UV uv;
+          uv.u = 0.5f + s->moon_tex_offset + o_atan2(normal.z, normal.x) * (1.0f / (2.0f * REF_PI));
+          uv.v = 0.5f + o_asin(normal.y) * (1.0f / REF_PI);
+          const float sign = copysignf(1.0f, normal.z);
+          const float a = -1.0f / (sign + normal.z);
+          const float b = normal.x * normal.y * a;
+          const vec3 u1 = v3(1.0f + sign * normal.x * normal.x * a, sign * b, -sign * normal.x);
+          const vec3 u2 = v3(b, sign + normal.y * normal.y * a, -normal.y);
+          const float4_t nv = texture_load(s->scene, s->moon_normal_tex, uv, true, f4(0.0f, 0.0f, 0.0f, 0.0f));
+          const vec3 mn = v3(nv.x * 2.0f - 1.0f, nv.y * 2.0f - 1.0f, nv.z * 2.0f - 1.0f);
+          normal = v_norm(v3(u1.x * mn.x + u2.x * mn.y + normal.x * mn.z, u1.y * mn.x + u2.y * mn.y + normal.y * mn.z, u1.z * mn.x + u2.z * mn.y + normal.z * mn.z));
+          const float NdotL = v_dot(normal, bounce_ray);
+          if (NdotL > 0.0f) {
+            const float albedo = texture_load(s->scene, s->moon_albedo_tex, uv, true, f4(0.0f, 0.0f, 0.0f, 0.0f)).x;
+            const float light_angle = sphere_solid_angle(s->sun_pos, SKY_SUN_RADIUS, moon_point);
+            const float weight = albedo * s->sun_strength * NdotL * light_angle / (2.0f * REF_PI);
+            result = sp_add(result, sp_mul(marched, sp_mul(SKY_MOON_SOLAR_FLUX, sp_scale(SKY_SUN_RADIANCE, weight))));
+          }
+        }
+      }
+      if (s->stars != NULL && sun_hit == FLT_MAX && earth_hit == FLT_MAX && moon_hit == FLT_MAX) {
+        const float ray_altitude = o_asin(ray.y);
+        const float ray_azimuth = o_atan2(-ray.z, -ray.x) + REF_PI;
+        uint32_t x = f2u_sat(ray_azimuth * 10.0f), y = f2u_sat((ray_altitude + REF_PI * 0.5f) * 10.0f);
+        if (x > 63u) x = 63u;
+        if (y > 31u) y = 31u;
+        const uint32_t grid = x + y * 64u;
+        const uint32_t first = s->stars_offsets[grid], last = s->stars_offsets[grid + 1u];
+        float star_sum = 0.0f;
+        for (uint32_t i = first; i < last; i++) {
+          const float* star = s->stars + 4 * (size_t) i;
+          const vec3 star_pos = angles_to_direction(star[0], star[1]);
+          if (sphere_hit(ray, v3(0.0f, 0.0f, 0.0f), star_pos, star[2])) {
+            result = sp_add(result, sp_scale(marched, star[3] * s->stars_intensity));
+            star_sum += star[3] * s->stars_intensity;
+          }
+        }
+        o[29] = grid; o[30] = f_bits(star_sum);
+      }
+    }
+    put_spectrum(o + 11, result);
+    const RGBF walk = sky_color_from_spectrum(result);
+    put_rgb(o + 19, aerial ? c_mul(walk, record_in) : walk);
+    put_rgb(o + 22, aerial ? c_mul(record_in, sky_color_from_spectrum(sp_mul(sp_set1(1.0f), marched))) : record_in);
+  }
+}
+/* direct_lighting_sun_create_task / direct_lighting_sun_direct with their stages on the light probe's vertices: the words of the device's sun probe
+ * (include/lum_core.h lumc_sun_probe_host), in its layout. The head is sun_sample's own result; the stages are restated statement for statement from the functions
+ * it calls. */
+void oracle_probe_sun_stages(const OracleScene* s, uint32_t num_vertices, const uint32_t* vertices, uint32_t first, uint32_t samples, uint32_t* out) {
+  const OLuts luts = scene_luts(s);
+  const OLuts* l = &luts;
+  const OSky sky_v = osky_view(s);
+  const OSky* sky = &sky_v;
+  memset(out, 0, sizeof(uint32_t) * (size_t) ORACLE_SUN_PROBE_WORDS * num_vertices * samples);
+  for (uint32_t v = 0; v < num_vertices; v++) {
+    const uint32_t* vw = vertices + (size_t) ORACLE_LIGHT_PROBE_VERTEX_WORDS * v;
+    float f[15]; memcpy(f, vw, sizeof(f));
+    const OracleProbeMaterial m0 = {{f[9], f[10], f[11]}, f[12], f[13], f[14], vw[15]};
+    GeoCtx gc = probe_context(&m0, f, f + 3, f + 6);
+    gc.instance_id = vw[16]; gc.tri_id = vw[17];
+    const GeoCtx* g = &gc;
+    const MatParams* p = &g->params;
+    for (uint32_t i = 0; i < samples; i++) {
+      uint32_t* o = out + (size_t) ORACLE_SUN_PROBE_WORDS * ((size_t) v * samples + i);
+      const Sampler sampler = {s->bluenoise_2d, vw[18], vw[19], first + i, 0};
+      const Sampler* smp = &sampler;
+      RGBF real_light = c_splat(0.0f);
+      vec3 real_dir = v3(0.0f, 0.0f, 0.0f);
+      const bool real = sun_sample(sky, l, g, smp, &real_light, &real_dir);
+      o[0] = real ? 1u : 0u;
+      if (real) { put_rgb(o + 1, real_light); put3(o + 4, real_dir); }
+      const vec3 sky_pos = world_to_sky(sky, g->position);
+      const bool sun_below_horizon = sph_hit_p0(v_norm(v_sub(sky->sun_pos, sky_pos)), sky_pos, SKY_EARTH_RADIUS);
+      const bool inside_earth = v_len(sky_pos) < SKY_EARTH_RADIUS;
+      put3(o + 7, sky_pos); o[10] = sun_below_horizon ? 1u : 0u; o[11] = inside_earth ? 1u : 0u;
+      const bool translucent = (p->flags & MAT_SUBSTRATE_MASK) == MAT_TRANSLUCENT;
+      const float w_refl = 1.0f, w_refr = translucent ? 1.0f : 0.0f;
+      const float reflection_prob = w_refl / (w_refl + w_refr), refraction_prob = w_refr / (w_refl + w_refr);
+      o[12] = f_bits(reflection_prob); o[13] = f_bits(refraction_prob);
+      const Quat rot = q_rotation_to_z(g->normal);
+      const vec3 Vl = q_apply(rot, g->V);
+      o[14] = f_bits(rot.x); o[15] = f_bits(rot.y); o[16] = f_bits(rot.z); o[17] = f_bits(rot.w);
+      put3(o + 18, Vl);
+      if (sun_below_horizon || inside_earth) continue;
+      o[63] = 1u;
+      const float roughness = mp_roughness(p);
+      const float method = rnd1(smp, RT_SUN_BSDF_METHOD), resampling = rnd1(smp, RT_SUN_RESAMPLING);
+      const float2_t r_bsdf = rnd2(smp, RT_SUN_BSDF), r_sun = rnd2(smp, RT_SUN_RAY);
+      o[21] = f_bits(method); o[22] = f_bits(r_bsdf.x); o[23] = f_bits(r_bsdf.y); o[24] = f_bits(r_sun.x); o[25] = f_bits(r_sun.y); o[26] = f_bits(resampling);
+      vec3 ray_local;
+      uint32_t technique = 0;
+      if (method < reflection_prob) ray_local = v_reflect(Vl, microfacet_sample_normal(Vl, roughness, r_bsdf));
+      else { bool tot; ray_local = refract_vector(Vl, microfacet_refraction_sample_normal(Vl, roughness, r_bsdf), mp_ior(p), &tot); technique = tot ? 2u : 1u; }
+      const vec3 dir_bsdf = v_norm(q_apply(q_inverse(rot), ray_local));
+      put3(o + 27, ray_local); o[30] = technique; put3(o + 31, dir_bsdf);
+      RGBF light_bsdf = c_splat(0.0f);
+      bool is_refraction;
+      const bool disk = sphere_hit(dir_bsdf, sky_pos, sky->sun_pos, SKY_SUN_RADIUS);
+      o[34] = disk ? 1u : 2u;
+      if (disk) {
+        const RGBF sun = sky_sun_color(sky, sky_pos, dir_bsdf), ev = bsdf_evaluate(l, g, dir_bsdf, HINT_GENERAL, &is_refraction, 1.0f);
+        put_rgb(o + 35, sun); put_rgb(o + 38, ev);
+        light_bsdf = c_mul(sun, ev);
+      }
+      float solid_angle;
+      const vec3 dir_sa = sample_sphere(sky->sun_pos, SKY_SUN_RADIUS, sky_pos, r_sun, &solid_angle);
+      const RGBF sun_sa = sky_sun_color(sky, sky_pos, dir_sa), ev_sa = bsdf_evaluate(l, g, dir_sa, HINT_GENERAL, &is_refraction, 1.0f);
+      const RGBF light_sa = c_mul(sun_sa, ev_sa);
+      put3(o + 41, dir_sa); o[44] = f_bits(solid_angle); put_rgb(o + 45, sun_sa); put_rgb(o + 48, ev_sa);
+      const float target_bsdf = c_importance(light_bsdf), target_sa = c_importance(light_sa);
+      const float pdf_bsdf = sun_bsdf_pdf(g, dir_bsdf, reflection_prob, refraction_prob), pdf_sa = sun_bsdf_pdf(g, dir_sa, reflection_prob, refraction_prob);
+      const float mis_bsdf = solid_angle / (pdf_bsdf * solid_angle + 1.0f);
+      const float mis_sa = solid_angle / (pdf_sa * solid_angle + 1.0f);
+      const float weight_bsdf = target_bsdf * mis_bsdf, weight_sa = target_sa * mis_sa;
+      const float sum_weights = weight_bsdf + weight_sa;
+      o[51] = f_bits(pdf_bsdf); o[52] = f_bits(pdf_sa); o[53] = f_bits(mis_bsdf); o[54] = f_bits(mis_sa); o[55] = f_bits(weight_bsdf); o[56] = f_bits(weight_sa);
+      o[57] = f_bits(sum_weights);
+      if (sum_weights == 0.0f) continue;
+      float target;
+      RGBF light;
+      if (resampling * sum_weights < weight_bsdf) { o[58] = 1u; target = target_bsdf; light = light_bsdf; }
+      else { o[58] = 2u; target = target_sa; light = light_sa; }
+      light = c_scale(light, sum_weights / target);
+      put_rgb(o + 59, light);
+      o[62] = (target == 0.0f || c_importance(light) == 0.0f) ? 0u : 1u;
+    }
+  }
+}
 /* light_bsdf_get_probability on its own: the probability with which the BSDF-driven light direction of the vertex would have been L */
 void oracle_probe_light_direction_probability(const OracleProbeMaterial* m, const float normal[3], const float V[3], uint32_t count, const float* L, float* out) {
   const float origin[3] = {0.0f, 0.0f, 0.0f};

@@ -240,6 +240,15 @@ void oracle_probe_light_sample_stages(const OracleScene* s, uint32_t num_vertice
 #define ORACLE_BOUNCE_PROBE_TECH_WORDS 24
 #define ORACLE_BOUNCE_PROBE_LIGHT_DIR_WORDS 27
 void oracle_probe_bounce_stages(const OracleScene* s, uint32_t num_vertices, const uint32_t* vertices, uint32_t first, uint32_t samples, uint32_t* out);
+/* sky_get_color / sky_trace_inscattering and the march's stages on caller-made rays, in the words of the device's sky probe (tests/test_sky_truth.py) */
+#define ORACLE_SKY_PROBE_RAY_WORDS 12 /* = LUMC_SKY_PROBE_*, include/lum_core.h: 40 + 12 steps x 49 (the test compares the headers) */
+#define ORACLE_SKY_PROBE_WORDS 628
+#define ORACLE_SKY_PROBE_HEAD_WORDS 40
+#define ORACLE_SKY_PROBE_STEP_WORDS 49
+#define ORACLE_SKY_PROBE_MAX_STEPS 12
+void oracle_probe_sky_stages(const OracleScene* scene, uint32_t num_rays, const uint32_t* rays, uint32_t* out);
+#define ORACLE_SUN_PROBE_WORDS 64 /* = LUMC_SUN_PROBE_WORDS */
+void oracle_probe_sun_stages(const OracleScene* s, uint32_t num_vertices, const uint32_t* vertices, uint32_t first, uint32_t samples, uint32_t* out);
 void oracle_probe_light_direction_probability(const OracleProbeMaterial* m, const float normal[3], const float V[3], uint32_t count, const float* L, float* out);
 
 /* fog (o_volume.h) */

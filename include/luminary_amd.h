@@ -626,6 +626,40 @@ LUMINARY_API LuminaryResult luminary_ext_get_firefly_rejection(LuminaryHost* hos
  * denoiser. Needs the switch on and at least one sample. */
 LUMINARY_API LuminaryResult luminary_ext_get_robust_radiance(LuminaryHost* host, float* rgb, uint32_t width, uint32_t height);
 LUMINARY_API LuminaryResult luminary_ext_get_firefly_stats(LuminaryHost* host, LuminaryFireflyStats* out);
+/* ID mattes (include/lum_core.h lumc_render_first_hits; csrc/host/matte.h): which instances and which materials a pixel's first hits saw, ranked
+ * by the share of its samples - what a selection outline, a matte per object with anti-aliased edges (depth of field and the shutter included) or a grade per
+ * object needs, and what luminary_host_get_pixel_info, one ray of one pixel, cannot tell. Rendered on demand on the main device over the whole frame, with one
+ * closest-hit pass per sample id and no shading; the accumulation is not touched. Where the denoiser is on and its guides are due, the same rays make them.
+ *   luminary_ext_render_mattes  samples 1 ... 1024 (0 = 4), layers LUMINARY_MATTE_LAYER_INSTANCE | LUMINARY_MATTE_LAYER_MATERIAL. 68 bytes per pixel and layer.
+ *   luminary_ext_get_matte      one layer, ranks 1 ... 8: ids and coverage planar [ranks][width * height] (either may be NULL), rank 0 the id with most samples,
+ *                               ties by ascending id, coverage = samples of the id / samples; ranks a pixel does not fill hold LUMINARY_MATTE_ID_EMPTY and 0.
+ *                               LUMINARY_MATTE_ID_MISS / _OCEAN / _PARTICLE stand for first hits that are no triangle, in both layers. A pixel that saw more than
+ *                               eight ids keeps the first eight it saw (LuminaryMatteStats::dropped_pixels counts such pixels).
+ *   luminary_ext_get_matte_mask mask [width * height] = the share of a pixel's samples whose id is among ids[0 .. count), count <= 16.
+ *   luminary_ext_get_first_hit_guides  the denoiser's first-hit guides of the frame, planar: albedo [3][width * height], normal [3][...], depth [width * height]
+ *                               (-1: nothing hit); each may be NULL. Rendered with the denoiser's guide_samples where the host holds none.
+ * A wrong layer, rank count, id count or frame size is LUMINARY_ERROR_INVALID_API_ARGUMENT; the getters before any luminary_ext_render_mattes, or after an edit of
+ * the scene since, are LUMINARY_ERROR_API_EXCEPTION with a line in the log. */
+#define LUMINARY_MATTE_LAYER_INSTANCE 1u
+#define LUMINARY_MATTE_LAYER_MATERIAL 2u
+#define LUMINARY_MATTE_ID_EMPTY 0xFFFFFFFFu
+#define LUMINARY_MATTE_ID_MISS 0xFFFFFFFEu
+#define LUMINARY_MATTE_ID_OCEAN 0xFFFFFFFDu
+#define LUMINARY_MATTE_ID_PARTICLE 0xFFFFFFFCu
+typedef struct LuminaryMatteStats {
+  uint64_t renders;            /* luminary_ext_render_mattes calls that ran, since the host was created */
+  uint64_t bytes;              /* held by the main device's matte planes */
+  uint32_t valid;              /* 1: the getters would answer */
+  uint32_t samples, layers;    /* of the last render */
+  uint32_t dropped_pixels[2];  /* pixels that saw more than eight ids: instance layer, material layer */
+  uint32_t reserved;
+  double seconds;              /* the last render, first-hit rays included */
+} LuminaryMatteStats;
+LUMINARY_API LuminaryResult luminary_ext_render_mattes(LuminaryHost* host, uint32_t samples, uint32_t layers);
+LUMINARY_API LuminaryResult luminary_ext_get_matte(LuminaryHost* host, uint32_t layer, uint32_t ranks, uint32_t* ids, float* coverage, uint32_t width, uint32_t height);
+LUMINARY_API LuminaryResult luminary_ext_get_matte_mask(LuminaryHost* host, uint32_t layer, const uint32_t* ids, uint32_t count, float* mask, uint32_t width, uint32_t height);
+LUMINARY_API LuminaryResult luminary_ext_get_matte_stats(LuminaryHost* host, LuminaryMatteStats* out);
+LUMINARY_API LuminaryResult luminary_ext_get_first_hit_guides(LuminaryHost* host, float* albedo, float* normal, float* depth, uint32_t width, uint32_t height);
 /* out[0] closest-hit rays, [1] shadow rays, [2] light-BVH queries, [3] shaded vertices, [4] BVH nodes visited, [5] triangles tested. */
 LUMINARY_API LuminaryResult luminary_ext_get_ray_counters(LuminaryHost* host, uint64_t out[8]);
 /* The lumc context of this host (include/lum_core.h), for callers that drive passes themselves. */

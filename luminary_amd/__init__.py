@@ -213,6 +213,16 @@ class FireflyStats(C.Structure):
                 ("last_nonfinite", C.c_uint32), ("buckets", C.c_uint32), ("bytes", C.c_uint64)]
 
 
+class MatteStats(C.Structure):
+    """LuminaryMatteStats"""
+    _fields_ = [("renders", C.c_uint64), ("bytes", C.c_uint64), ("valid", C.c_uint32), ("samples", C.c_uint32), ("layers", C.c_uint32),
+                ("dropped_pixels", C.c_uint32 * 2), ("reserved", C.c_uint32), ("seconds", C.c_double)]
+
+
+MATTE_LAYER_INSTANCE, MATTE_LAYER_MATERIAL = 1, 2  # LUMINARY_MATTE_LAYER_*
+MATTE_ID_EMPTY, MATTE_ID_MISS, MATTE_ID_OCEAN, MATTE_ID_PARTICLE = 0xFFFFFFFF, 0xFFFFFFFE, 0xFFFFFFFD, 0xFFFFFFFC  # LUMINARY_MATTE_ID_*
+
+
 class ShutterStats(C.Structure):
     """LuminaryShutterStats"""
     _fields_ = [("renders", C.c_uint64), ("slices", C.c_uint64), ("last_moved_meshes", C.c_uint32), ("last_moved_instances", C.c_uint32), ("last_camera_moved", C.c_uint32),
@@ -790,6 +800,42 @@ class Host:
         s = FireflyStats()
         _call("luminary_ext_get_firefly_stats", self._h, C.byref(s))
         return {name: getattr(s, name) for name, _ in s._fields_}
+
+    def render_mattes(self, samples=4, layers=MATTE_LAYER_INSTANCE | MATTE_LAYER_MATERIAL):
+        """luminary_ext_render_mattes: ID mattes of the whole frame from `samples` first-hit passes on the main device; the accumulation is not touched."""
+        _call("luminary_ext_render_mattes", self._h, C.c_uint32(samples), C.c_uint32(layers))
+
+    def matte(self, layer, ranks, width, height):
+        """luminary_ext_get_matte: (ids [ranks, H, W] uint32, coverage [ranks, H, W] float32) of one layer, rank 0 the id with most samples."""
+        import numpy as np
+        r = max(min(int(ranks), 8), 1)
+        ids, cov = np.zeros((r, height, width), dtype=np.uint32), np.zeros((r, height, width), dtype=np.float32)
+        _call("luminary_ext_get_matte", self._h, C.c_uint32(layer), C.c_uint32(ranks), ids.ctypes.data_as(C.c_void_p), cov.ctypes.data_as(C.c_void_p), C.c_uint32(width),
+              C.c_uint32(height))
+        return ids, cov
+
+    def matte_mask(self, layer, ids, width, height):
+        """luminary_ext_get_matte_mask: [H, W] float32, the share of every pixel's samples whose id is among `ids` (at most 16)."""
+        import numpy as np
+        want = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+        mask = np.zeros((height, width), dtype=np.float32)
+        _call("luminary_ext_get_matte_mask", self._h, C.c_uint32(layer), C.c_void_p(want.ctypes.data if want.size else None), C.c_uint32(want.size),
+              mask.ctypes.data_as(C.c_void_p), C.c_uint32(width), C.c_uint32(height))
+        return mask
+
+    def matte_stats(self):
+        """luminary_ext_get_matte_stats, as a dict."""
+        s = MatteStats()
+        _call("luminary_ext_get_matte_stats", self._h, C.byref(s))
+        return {name: (list(getattr(s, name)) if name == "dropped_pixels" else getattr(s, name)) for name, _ in s._fields_}
+
+    def first_hit_guides(self, width, height):
+        """luminary_ext_get_first_hit_guides: (albedo [3, H, W], normal [3, H, W], depth [H, W]) float32, the denoiser's guides of the frame."""
+        import numpy as np
+        a, n, d = np.zeros((3, height, width), np.float32), np.zeros((3, height, width), np.float32), np.zeros((height, width), np.float32)
+        _call("luminary_ext_get_first_hit_guides", self._h, a.ctypes.data_as(C.c_void_p), n.ctypes.data_as(C.c_void_p), d.ctypes.data_as(C.c_void_p), C.c_uint32(width),
+              C.c_uint32(height))
+        return a, n, d
 
     def ray_counters(self):
         out = (C.c_uint64 * 8)()

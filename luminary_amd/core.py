@@ -14,7 +14,11 @@ DIRTY_MESH_SHUTTER = 2048  # meshes that hold both shutter keys got a time (Core
 BVH_BUILDERS = {"sah": 0, "lbvh": 1, "ploc": 2, "sah_gpu": 3}
 CNT_TRACE, CNT_SHADOW, CNT_LIGHT_BVH, CNT_VERTICES, CNT_NODES, CNT_TRIS, CNT_NODES_SHADOW, CNT_TRIS_SHADOW, CNT_NODES_LIGHT, CNT_TRIS_LIGHT, CNT_NODES_LDS, CNT_NODES_LDS_SHADOW, CNT_AMBIENT_DEFERRED, CNT_AMBIENT_FALLBACK = range(14)
 CNT_COUNT = 16  # LUMC_CNT_COUNT
-KERNELS = ("generate", "trace", "shade", "shadow", "accumulate", "light_query", "resolve", "output", "sky", "sort", "volume")
+KERNELS = ("generate", "trace", "shade", "shadow", "accumulate", "light_query", "resolve", "output", "sky", "sort", "volume", "matte")
+FIRST_HIT_GUIDES, FIRST_HIT_MATTES = 1, 2  # LUMC_FIRST_HIT_*
+MATTE_INSTANCE, MATTE_MATERIAL = 1, 2  # LUMC_MATTE_*: layers
+MATTE_ID_EMPTY, MATTE_ID_MISS, MATTE_ID_OCEAN, MATTE_ID_PARTICLE = 0xFFFFFFFF, 0xFFFFFFFE, 0xFFFFFFFD, 0xFFFFFFFC
+MATTE_SLOTS, MATTE_MAX_MASK_IDS = 8, 16
 
 
 class CoreError(RuntimeError):
@@ -170,6 +174,47 @@ def firefly_resolve_host(sums, counts, image):
     if fn(s.ctypes.data, n.ctypes.data, K, pixels, out.ctypes.data, C.addressof(stats)) != 0:
         raise ValueError("lumc_firefly_resolve_host refused its arguments")
     return out, tuple(int(x) for x in stats)
+
+
+class MatteStats(C.Structure):
+    """LumMatteStats"""
+    _fields_ = [("samples", C.c_uint32), ("layers", C.c_uint32), ("bytes", C.c_uint64), ("dropped_pixels", C.c_uint32 * 2), ("valid", C.c_uint32),
+                ("reserved", C.c_uint32), ("seconds", C.c_double)]
+
+
+def matte_host(ids, ranks=MATTE_SLOTS):
+    """lumc_matte_host, no device needed: the host twin of the matte kernels. ids [samples, pixels] uint32 in ascending sample id, MATTE_ID_EMPTY = the sample has
+    no path. Returns a dict: slots_id, slots_count [8, P], ids [ranks, P] uint32, coverage [ranks, P] float32, dropped, rays [P]; raises ValueError where the twin
+    refuses (samples outside 1 ... 1024, ranks outside 1 ... 8)."""
+    fn = _lib().lumc_matte_host
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32] + [C.c_void_p] * 6
+    a = np.ascontiguousarray(ids, dtype=np.uint32)
+    if a.ndim != 2:
+        raise ValueError("matte_host: ids [samples, pixels]")
+    S, P = a.shape
+    R = max(min(int(ranks), MATTE_SLOTS), 1)
+    out = {"slots_id": np.zeros((MATTE_SLOTS, P), np.uint32), "slots_count": np.zeros((MATTE_SLOTS, P), np.uint32), "ids": np.zeros((R, P), np.uint32),
+           "coverage": np.zeros((R, P), np.float32), "dropped": np.zeros(P, np.uint32), "rays": np.zeros(P, np.uint32)}
+    if fn(a.ctypes.data, S, P, int(ranks), *[out[k].ctypes.data for k in ("slots_id", "slots_count", "ids", "coverage", "dropped", "rays")]) != 0:
+        raise ValueError("lumc_matte_host refused its arguments")
+    return out
+
+
+def matte_mask_host_twin(slots_id, slots_count, samples, ids):
+    """lumc_matte_mask_host_twin, no device needed: the mask [P] float32 of up to 16 ids over raw slots [8, P]; raises ValueError where the twin refuses."""
+    fn = _lib().lumc_matte_mask_host_twin
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]
+    si = np.ascontiguousarray(slots_id, dtype=np.uint32)
+    sc = np.ascontiguousarray(slots_count, dtype=np.uint32)
+    if si.shape != sc.shape or si.ndim != 2 or si.shape[0] != MATTE_SLOTS:
+        raise ValueError("matte_mask_host_twin: slots [8, pixels]")
+    want = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+    mask = np.zeros(si.shape[1], np.float32)
+    if fn(si.ctypes.data, sc.ctypes.data, si.shape[1], int(samples), want.ctypes.data if want.size else None, want.size, mask.ctypes.data) != 0:
+        raise ValueError("lumc_matte_mask_host_twin refused its arguments")
+    return mask
 
 
 class ShutterStats(C.Structure):
@@ -919,6 +964,53 @@ class Core:
     def firefly_stats(self):
         out = FireflyStats()
         self._call("lumc_firefly_stats", C.byref(out))
+        return out
+
+    # ---- ID mattes (lumc_render_first_hits, lumc_download_mattes, lumc_matte_mask) ----
+    def render_first_hits(self, num_samples=4, what=FIRST_HIT_GUIDES | FIRST_HIT_MATTES, layers=MATTE_INSTANCE | MATTE_MATERIAL, stream=0):
+        """lumc_render_first_hits: one closest-hit pass per sample id of the whole frame into the denoiser's guides, the ID mattes, or both from the same rays."""
+        self._call("lumc_render_first_hits", C.c_uint32(num_samples), C.c_uint32(what), C.c_uint32(layers), C.c_void_p(stream))
+
+    def render_mattes(self, num_samples=4, layers=MATTE_INSTANCE | MATTE_MATERIAL):
+        self.render_first_hits(num_samples, FIRST_HIT_MATTES, layers)
+
+    def mattes(self, layer, ranks=MATTE_SLOTS):
+        """lumc_download_mattes of one layer (MATTE_INSTANCE or MATTE_MATERIAL): (ids [ranks, P] uint32, coverage [ranks, P] float32, dropped [P], rays [P])."""
+        P, R = self.width * self.height, max(min(int(ranks), MATTE_SLOTS), 1)
+        ids, cov, dropped, rays = np.zeros((R, P), np.uint32), np.zeros((R, P), np.float32), np.zeros(P, np.uint32), np.zeros(P, np.uint32)
+        self._call("lumc_download_mattes", C.c_uint32(layer), C.c_uint32(ranks), *[C.c_void_p(a.ctypes.data) for a in (ids, cov, dropped, rays)])
+        return ids, cov, dropped, rays
+
+    def matte_tables(self, layer):
+        """lumc_download_matte_tables: the raw slots (slots_id [8, P], slots_count [8, P], dropped [P])."""
+        P = self.width * self.height
+        si, sc, dropped = np.zeros((MATTE_SLOTS, P), np.uint32), np.zeros((MATTE_SLOTS, P), np.uint32), np.zeros(P, np.uint32)
+        self._call("lumc_download_matte_tables", C.c_uint32(layer), *[C.c_void_p(a.ctypes.data) for a in (si, sc, dropped)])
+        return si, sc, dropped
+
+    def matte_mask(self, layer, ids):
+        """lumc_matte_mask_host: the coverage [P] float32 of up to 16 ids per pixel."""
+        want = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+        mask = np.zeros(self.width * self.height, np.float32)
+        self._call("lumc_matte_mask_host", C.c_uint32(layer), C.c_void_p(want.ctypes.data if want.size else None), C.c_uint32(want.size), C.c_void_p(mask.ctypes.data))
+        return mask
+
+    def has_mattes(self):
+        fn = self._lib.lumc_has_mattes
+        fn.restype = C.c_int
+        return bool(fn(self._ctx))
+
+    def has_guides(self):
+        fn = self._lib.lumc_has_guides
+        fn.restype = C.c_int
+        return bool(fn(self._ctx))
+
+    def matte_release(self):
+        self._call("lumc_matte_release")
+
+    def matte_stats(self):
+        out = MatteStats()
+        self._call("lumc_matte_stats", C.byref(out))
         return out
 
     def mesh_shutter_key(self, mesh, which):

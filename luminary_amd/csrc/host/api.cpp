@@ -125,6 +125,8 @@ struct LuminaryHost {
   bool adaptive_active = false;      // the accumulation is driven by lumc_adaptive_* (luminary_ext_render with adaptive sampling enabled)
   LuminaryDenoiserSettings denoiser = {false, 4u, 5u, 4.0f, 128.0f, 1.0f};  // luminary_ext_set_denoiser
   bool guides_valid = false;         // the main context holds the denoiser's guides of the current accumulation
+  bool mattes_valid = false;         // the main context holds ID mattes of the scene as it is (luminary_ext_render_mattes): any edit drops them
+  uint64_t matte_renders = 0;
   LuminaryFireflySettings firefly = {false, 8u};  // luminary_ext_set_firefly_rejection
   uint32_t core_firefly = 0;         // buckets the main context holds (sync_firefly): 0 while the switch is off or the frame is tiled over several devices
   uint64_t firefly_resolved = 0, firefly_skipped = 0;  // result images resolved / left alone because adaptive sampling drives the accumulation
@@ -213,7 +215,7 @@ void invalidate(LuminaryHost* h, uint32_t dirty = LUMC_DIRTY_ALL) {
   // normalised by the stale per-block sample counts.
   if (h->adaptive_active) h->num_pixels = 0;
   h->device_scene_valid = false; h->core_scene_valid = false; h->accumulated_samples = 0; h->adaptive_active = false;
-  h->guides_valid = false;
+  h->guides_valid = false; h->mattes_valid = false;
   for (auto& slot : h->devices) { slot.scene_valid = false; slot.dirty |= dirty; }
   { std::lock_guard<std::mutex> l(h->worker_mutex); h->async_failed = false; }  // the edit may have repaired what failed
   h->worker_cv.notify_all();
@@ -2143,6 +2145,90 @@ LuminaryResult luminary_ext_get_firefly_stats(LuminaryHost* host, LuminaryFirefl
     out->last_rewritten = st.last_rewritten; out->last_trimmed = st.last_trimmed; out->last_nonfinite = st.last_nonfinite;
     out->buckets = st.buckets; out->bytes = st.bytes;
   }
+  return LUMINARY_SUCCESS;
+}
+// ---- ID mattes (include/luminary_amd.h luminary_ext_render_mattes; include/lum_core.h lumc_render_first_hits) ----
+namespace {
+LuminaryResult matte_refuse(LuminaryHost* host, const char* fn, const std::string& why, LuminaryResult code) {
+  host->log.push_back(std::string(fn) + ": " + why);
+  std::fprintf(stderr, "[luminary_amd] %s\n", host->log.back().c_str());
+  return code;
+}
+bool one_matte_layer(uint32_t layer) { return layer == LUMINARY_MATTE_LAYER_INSTANCE || layer == LUMINARY_MATTE_LAYER_MATERIAL; }
+// the main context holds mattes of the scene as the host has it now
+bool mattes_current(const LuminaryHost* host) { return host->core && host->mattes_valid && host->core_scene_valid && lumc_has_mattes(host->core); }
+}  // namespace
+
+LuminaryResult luminary_ext_render_mattes(LuminaryHost* host, uint32_t samples, uint32_t layers) {
+  CHECK_NULL(host);
+  if (samples > 1024 || layers == 0 || (layers & ~(uint32_t) (LUMINARY_MATTE_LAYER_INSTANCE | LUMINARY_MATTE_LAYER_MATERIAL))) return LUMINARY_ERROR_INVALID_API_ARGUMENT;
+  ApiLock lock(host);
+  host->mattes_valid = false;
+  if (const LuminaryResult r = ensure_core(host)) return r;
+  // The denoiser's guides come from the same first hits: where they are due and want the same sample ids, one set of rays makes both. With another count of
+  // guide samples they are rendered on their own, so that the guides are what luminary_ext_set_denoiser asked for.
+  const bool guides_due = host->denoiser.enabled && (!host->guides_valid || !lumc_has_guides(host->core));
+  const bool shared = guides_due && (samples ? samples : 4u) == host->denoiser.guide_samples;
+  if (lumc_render_first_hits(host->core, samples, LUMC_FIRST_HIT_MATTES | (shared ? LUMC_FIRST_HIT_GUIDES : 0), layers, nullptr) ||
+      (guides_due && !shared && lumc_render_guides(host->core, host->denoiser.guide_samples, nullptr))) {
+    std::fprintf(stderr, "[luminary_amd] %s\n", lumc_last_error(host->core));
+    return LUMINARY_ERROR_CUDA;
+  }
+  if (guides_due) host->guides_valid = true;
+  host->mattes_valid = true;
+  host->matte_renders++;
+  return LUMINARY_SUCCESS;
+}
+LuminaryResult luminary_ext_get_matte(LuminaryHost* host, uint32_t layer, uint32_t ranks, uint32_t* ids, float* coverage, uint32_t width, uint32_t height) {
+  CHECK_NULL(host);
+  if (!ids && !coverage) return LUMINARY_ERROR_ARGUMENT_NULL;
+  if (!one_matte_layer(layer) || ranks == 0 || ranks > 8) return LUMINARY_ERROR_INVALID_API_ARGUMENT;
+  ApiLock lock(host);
+  if (!mattes_current(host)) return matte_refuse(host, "luminary_ext_get_matte", "no mattes of the scene as it is (luminary_ext_render_mattes)", LUMINARY_ERROR_API_EXCEPTION);
+  const LumDeviceSceneView& v = host->device_scene.view;
+  if (width != v.width || height != v.height) return LUMINARY_ERROR_INVALID_API_ARGUMENT;
+  if (lumc_download_mattes(host->core, layer, ranks, ids, coverage, nullptr, nullptr)) return matte_refuse(host, "luminary_ext_get_matte", lumc_last_error(host->core), LUMINARY_ERROR_API_EXCEPTION);
+  return LUMINARY_SUCCESS;
+}
+LuminaryResult luminary_ext_get_matte_mask(LuminaryHost* host, uint32_t layer, const uint32_t* ids, uint32_t count, float* mask, uint32_t width, uint32_t height) {
+  CHECK_NULL(host); CHECK_NULL(mask);
+  if (count && !ids) return LUMINARY_ERROR_ARGUMENT_NULL;
+  if (!one_matte_layer(layer) || count > 16) return LUMINARY_ERROR_INVALID_API_ARGUMENT;
+  ApiLock lock(host);
+  if (!mattes_current(host)) return matte_refuse(host, "luminary_ext_get_matte_mask", "no mattes of the scene as it is (luminary_ext_render_mattes)", LUMINARY_ERROR_API_EXCEPTION);
+  const LumDeviceSceneView& v = host->device_scene.view;
+  if (width != v.width || height != v.height) return LUMINARY_ERROR_INVALID_API_ARGUMENT;
+  if (lumc_matte_mask_host(host->core, layer, ids, count, mask)) return matte_refuse(host, "luminary_ext_get_matte_mask", lumc_last_error(host->core), LUMINARY_ERROR_API_EXCEPTION);
+  return LUMINARY_SUCCESS;
+}
+LuminaryResult luminary_ext_get_matte_stats(LuminaryHost* host, LuminaryMatteStats* out) {
+  CHECK_NULL(host); CHECK_NULL(out);
+  ApiLock lock(host);
+  std::memset(out, 0, sizeof(*out));
+  out->renders = host->matte_renders;
+  if (host->core) {
+    LumMatteStats st;
+    if (lumc_matte_stats(host->core, &st)) return LUMINARY_ERROR_CUDA;
+    out->bytes = st.bytes; out->layers = st.layers;
+    if (mattes_current(host)) {
+      out->valid = 1; out->samples = st.samples; out->seconds = st.seconds;
+      out->dropped_pixels[0] = st.dropped_pixels[0]; out->dropped_pixels[1] = st.dropped_pixels[1];
+    }
+  }
+  return LUMINARY_SUCCESS;
+}
+LuminaryResult luminary_ext_get_first_hit_guides(LuminaryHost* host, float* albedo, float* normal, float* depth, uint32_t width, uint32_t height) {
+  CHECK_NULL(host);
+  if (!albedo && !normal && !depth) return LUMINARY_ERROR_ARGUMENT_NULL;
+  ApiLock lock(host);
+  if (const LuminaryResult r = ensure_core(host)) return r;
+  const LumDeviceSceneView& v = host->device_scene.view;
+  if (width != v.width || height != v.height) return LUMINARY_ERROR_INVALID_API_ARGUMENT;
+  if (!host->guides_valid || !lumc_has_guides(host->core)) {  // as the denoiser makes them (denoise_result)
+    if (lumc_render_guides(host->core, host->denoiser.guide_samples, nullptr)) { std::fprintf(stderr, "[luminary_amd] %s\n", lumc_last_error(host->core)); return LUMINARY_ERROR_CUDA; }
+    host->guides_valid = true;
+  }
+  if (lumc_download_guides(host->core, albedo, normal, depth)) return LUMINARY_ERROR_CUDA;
   return LUMINARY_SUCCESS;
 }
 LuminaryResult luminary_ext_get_ray_counters(LuminaryHost* host, uint64_t out[8]) {

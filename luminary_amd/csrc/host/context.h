@@ -22,6 +22,7 @@
 #include "firefly.h"
 #include "instance_update.h"
 #include "light_refit.h"
+#include "matte.h"
 #include "mesh_deform.h"
 #include "mesh_shutter.h"
 #include "scene_arrays.h"
@@ -170,6 +171,9 @@ struct LumContext {
   // denoiser (dev_denoise.h): the guide planes (9 while they are summed, then albedo[3] normal[3] depth), the filter's records (A twice: ping-pong, B once)
   DeviceBuffer<float> d_guides;
   bool guides_valid = false;
+  Mattes mattes;  // ID mattes of the same first-hit passes (lumc_render_first_hits; matte.hip): nothing is allocated until they are asked for
+  // the scene, the lens or the camera changed: both were rendered from what was. `why` is what a refused matte download names.
+  void drop_first_hit_products(const char* why) { guides_valid = false; if (mattes.valid) { mattes.valid = false; mattes.stale = why; } }
   DeviceBuffer<float4> d_denoise_rec[3];  // one 16-byte record per pixel each
   int denoise_lds = 1;              // a-trous steps 1 and 2 stage their tile in LDS (lumc_set_denoise_form; LUM_DENOISE_LDS=0|1)
   // ray ordering (N1): keys + permutation, double-buffered for hipcub's radix sort; sized for the visibility items (4 per path)

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -1045,20 +1046,62 @@ int lumc_post_bloom_host(LumContext* ctx, float* image, uint32_t full_width, uin
 // ---- denoiser (dev_denoise.h) ----
 static size_t guide_pixels(const LumContext* ctx) { return ctx->d_guides.count() / kGuideSumPlanes; }  // the frame the guide planes were allocated for
 
-int lumc_render_guides(LumContext* ctx, uint32_t num_samples, void* stream_) {
-  if (!ctx || !ctx->has_scene) { if (ctx) ctx->error = "lumc_render_guides: no scene"; return 1; }
+static double now_seconds() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+// The matte planes for a frame of n pixels and the layers asked for, every table empty: slot ids kMatteIdEmpty, counts and dropped 0.
+static int begin_mattes(LumContext* ctx, const char* fn, uint32_t n, uint32_t layers, hipStream_t stream) {
+  Mattes& m = ctx->mattes;
+  m.valid = false; m.stale = nullptr;
+  if (m.pixels != n || m.layers != layers || !m.planes) {
+    m.planes.reset(); m.pixels = 0; m.layers = 0;
+    const uint32_t held = (layers & 1u) + ((layers >> 1) & 1u);
+    const size_t words = (size_t) held * kMatteWordsPerLayer * n;
+    hipError_t e = m.planes.resize(words);
+    if (e == hipSuccess && !m.d_dropped) e = m.d_dropped.resize(kMatteLayers);
+    if (e != hipSuccess) {
+      (void) hipGetLastError();
+      m.planes.reset();
+      ctx->error = std::string(fn) + ": no room for " + std::to_string(words * sizeof(uint32_t)) + " bytes of matte planes: " + hipGetErrorString(e);
+      return 1;
+    }
+    m.pixels = n; m.layers = layers;
+  }
+  for (uint32_t layer = 0; layer < kMatteLayers; layer++) {
+    uint32_t* planes = m.layer_planes(layer);
+    if (!planes) continue;
+    HIP_TRY(ctx, hipMemsetAsync(planes, 0xFF, sizeof(uint32_t) * kMatteSlots * (size_t) n, stream));
+    HIP_TRY(ctx, hipMemsetAsync(planes + kMatteSlots * (size_t) n, 0, sizeof(uint32_t) * (kMatteSlots + 1u) * (size_t) n, stream));
+  }
+  return 0;
+}
+
+// One closest-hit pass per sample id over every pixel of the frame, and what is made of its first hits: the denoiser's guides (k_guide), the ID mattes
+// (k_matte_accumulate), or both from the same rays. With guides alone this is lumc_render_guides as it always was: the same launches in the same order.
+static int render_first_hits(LumContext* ctx, const char* fn, uint32_t num_samples, uint32_t what, uint32_t layers, hipStream_t stream) {
+  const std::string name(fn);
+  if (!ctx->has_scene) { ctx->error = name + ": no scene"; return 1; }
   if (num_samples == 0) num_samples = 4;
-  if (num_samples > 1024u) { ctx->error = "lumc_render_guides: at most 1024 guide samples"; return 1; }
-  hipStream_t stream = (hipStream_t) stream_;
+  if (num_samples > 1024u) { ctx->error = name + ": at most 1024 guide samples"; return 1; }
+  const bool guides = (what & LUMC_FIRST_HIT_GUIDES) != 0, mattes = (what & LUMC_FIRST_HIT_MATTES) != 0;
+  if (!what || (what & ~(uint32_t) (LUMC_FIRST_HIT_GUIDES | LUMC_FIRST_HIT_MATTES))) { ctx->error = name + ": what is LUMC_FIRST_HIT_GUIDES | LUMC_FIRST_HIT_MATTES"; return 1; }
+  if (mattes && (!layers || (layers & ~(uint32_t) (LUMC_MATTE_INSTANCE | LUMC_MATTE_MATERIAL)))) { ctx->error = name + ": layers is LUMC_MATTE_INSTANCE | LUMC_MATTE_MATERIAL"; return 1; }
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   DeviceScene sc = ctx->scene;
   sc.sobol_table = nullptr;
   const uint32_t n = sc.width * sc.height;
-  if (n == 0 || sc.width > 0xFFFFu || sc.height > 0xFFFFu) { ctx->error = "lumc_render_guides: frame size"; return 1; }
-  ctx->guides_valid = false;
-  if (guide_pixels(ctx) != n) HIP_TRY(ctx, ctx->d_guides.resize(kGuideSumPlanes * (size_t) n));
+  if (n == 0 || sc.width > 0xFFFFu || sc.height > 0xFFFFu) { ctx->error = name + ": frame size"; return 1; }
+  if (guides) {
+    ctx->guides_valid = false;
+    if (guide_pixels(ctx) != n) HIP_TRY(ctx, ctx->d_guides.resize(kGuideSumPlanes * (size_t) n));
+  }
   if (ensure_work(ctx, n)) return 1;
-  HIP_TRY(ctx, hipMemsetAsync(ctx->d_guides.get(), 0, sizeof(float) * kGuideSumPlanes * (size_t) n, stream));
+  if (guides) HIP_TRY(ctx, hipMemsetAsync(ctx->d_guides.get(), 0, sizeof(float) * kGuideSumPlanes * (size_t) n, stream));
+  double t0 = 0.0;
+  if (mattes) {
+    if (begin_mattes(ctx, fn, n, layers, stream)) return 1;
+    HIP_TRY(ctx, hipStreamSynchronize(stream));  // (the clock of lumc_matte_stats; a render of guides alone synchronises nothing)
+    t0 = now_seconds();
+  }
   const WavefrontKernels& wf = *ctx->wf;
   // one sample id of every pixel per pass: the closest-hit pass of the debug shading modes (wavefront_depths), then k_guide adds into the planes
   for (uint32_t s = 0; s < num_samples; s++) {
@@ -1069,15 +1112,152 @@ int lumc_render_guides(LumContext* ctx, uint32_t num_samples, void* stream_) {
       wf.generate(grid_for(n), stream, sc, pp, ctx->work.queue[0], ctx->work.results, ctx->d_ctrl.get() + kCtlPaths, ctx->lens, ctx->camera);
     }
     first_hits(ctx, stream, sc, n);
-    Launch l(ctx, stream, LUMC_KERNEL_OUTPUT);
-    wf.guide(grid_for(n), stream, sc, ctx->work.queue[0], (const uint32_t*) ctx->d_ctrl.get(), ctx->d_guides.get(), n);
+    if (guides) {
+      Launch l(ctx, stream, LUMC_KERNEL_OUTPUT);
+      wf.guide(grid_for(n), stream, sc, ctx->work.queue[0], (const uint32_t*) ctx->d_ctrl.get(), ctx->d_guides.get(), n);
+    }
+    if (mattes) {
+      Launch l(ctx, stream, LUMC_KERNEL_MATTE);
+      const PathQueue& q = ctx->work.queue[0];
+      HIP_TRY(ctx, matte_accumulate_launch(q.hit_id, q.hit_scene_tri, ctx->d_ctrl.get() + kCtlPaths, sc.tri_tex, sc.width, n, ctx->mattes.layer_planes(0), ctx->mattes.layer_planes(1), stream));
+    }
   }
-  {
+  if (guides) {
     Launch l(ctx, stream, LUMC_KERNEL_OUTPUT);
     wf.guide_normalise(grid_for(n), stream, ctx->d_guides.get(), n, num_samples);
   }
   HIP_TRY(ctx, hipGetLastError());
-  ctx->guides_valid = true;
+  if (mattes) {
+    HIP_TRY(ctx, hipStreamSynchronize(stream));
+    ctx->mattes.seconds = now_seconds() - t0;
+    ctx->mattes.samples = num_samples;
+    ctx->mattes.valid = true;
+  }
+  if (guides) ctx->guides_valid = true;
+  return 0;
+}
+
+int lumc_render_guides(LumContext* ctx, uint32_t num_samples, void* stream) {
+  if (!ctx) return 1;
+  return render_first_hits(ctx, "lumc_render_guides", num_samples, LUMC_FIRST_HIT_GUIDES, 0u, (hipStream_t) stream);
+}
+
+int lumc_render_first_hits(LumContext* ctx, uint32_t num_samples, uint32_t what, uint32_t layers, void* stream) {
+  if (!ctx) return 1;
+  return render_first_hits(ctx, "lumc_render_first_hits", num_samples, what, layers, (hipStream_t) stream);
+}
+
+// ---- ID mattes (matte.h - the definition -, matte.hip) ----
+// The layer's planes of a valid set, or null with the error set. `layer` is one LUMC_MATTE_* bit.
+static const uint32_t* matte_layer(LumContext* ctx, const char* fn, uint32_t layer) {
+  const Mattes& m = ctx->mattes;
+  const std::string name(fn);
+  if (layer != LUMC_MATTE_INSTANCE && layer != LUMC_MATTE_MATERIAL) { ctx->error = name + ": layer is LUMC_MATTE_INSTANCE or LUMC_MATTE_MATERIAL"; return nullptr; }
+  if (!m.valid) {
+    ctx->error = m.stale ? name + ": the mattes are stale: " + m.stale + " (lumc_render_first_hits)" : name + ": no mattes (lumc_render_first_hits)";
+    return nullptr;
+  }
+  const uint32_t* planes = m.layer_planes(layer == LUMC_MATTE_MATERIAL ? 1u : 0u);
+  if (!planes) ctx->error = name + ": the last matte render did not ask for this layer";
+  return planes;
+}
+
+int lumc_download_mattes(LumContext* ctx, uint32_t layer, uint32_t ranks, uint32_t* ids, float* coverage, uint32_t* dropped, uint32_t* rays) {
+  if (!ctx) return 1;
+  const uint32_t* planes = matte_layer(ctx, "lumc_download_mattes", layer);
+  if (!planes) return 1;
+  if (ranks == 0 || ranks > kMatteSlots) { ctx->error = "lumc_download_mattes: " + std::to_string(ranks) + " ranks (1 ... 8)"; return 1; }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const size_t n = ctx->mattes.pixels;
+  DeviceBuffer<uint32_t> d_ids, d_dropped, d_rays;
+  DeviceBuffer<float> d_coverage;
+  if (ids) HIP_TRY(ctx, d_ids.resize(ranks * n));
+  if (coverage) HIP_TRY(ctx, d_coverage.resize(ranks * n));
+  if (dropped) HIP_TRY(ctx, d_dropped.resize(n));
+  if (rays) HIP_TRY(ctx, d_rays.resize(n));
+  HIP_TRY(ctx, hipDeviceSynchronize());
+  {
+    Launch l(ctx, nullptr, LUMC_KERNEL_MATTE);
+    HIP_TRY(ctx, matte_resolve_launch(planes, (uint32_t) n, ctx->mattes.samples, ranks, d_ids.get(), d_coverage.get(), d_dropped.get(), d_rays.get(), nullptr, nullptr));
+  }
+  HIP_TRY(ctx, hipDeviceSynchronize());
+  if (ids) HIP_TRY(ctx, hipMemcpy(ids, d_ids.get(), sizeof(uint32_t) * ranks * n, hipMemcpyDeviceToHost));
+  if (coverage) HIP_TRY(ctx, hipMemcpy(coverage, d_coverage.get(), sizeof(float) * ranks * n, hipMemcpyDeviceToHost));
+  if (dropped) HIP_TRY(ctx, hipMemcpy(dropped, d_dropped.get(), sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
+  if (rays) HIP_TRY(ctx, hipMemcpy(rays, d_rays.get(), sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int lumc_download_matte_tables(LumContext* ctx, uint32_t layer, uint32_t* slots_id, uint32_t* slots_count, uint32_t* dropped) {
+  if (!ctx) return 1;
+  const uint32_t* planes = matte_layer(ctx, "lumc_download_matte_tables", layer);
+  if (!planes) return 1;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipDeviceSynchronize());
+  const size_t n = ctx->mattes.pixels;
+  if (slots_id) HIP_TRY(ctx, hipMemcpy(slots_id, planes, sizeof(uint32_t) * kMatteSlots * n, hipMemcpyDeviceToHost));
+  if (slots_count) HIP_TRY(ctx, hipMemcpy(slots_count, planes + kMatteSlots * n, sizeof(uint32_t) * kMatteSlots * n, hipMemcpyDeviceToHost));
+  if (dropped) HIP_TRY(ctx, hipMemcpy(dropped, planes + 2u * kMatteSlots * n, sizeof(uint32_t) * n, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int lumc_matte_mask(LumContext* ctx, uint32_t layer, const uint32_t* ids, uint32_t count, float* d_mask, void* stream_) {
+  if (!ctx) return 1;
+  const uint32_t* planes = matte_layer(ctx, "lumc_matte_mask", layer);
+  if (!planes) return 1;
+  if (!d_mask || (count && !ids)) { ctx->error = "lumc_matte_mask: null argument"; return 1; }
+  if (count > kMatteMaxMaskIds) { ctx->error = "lumc_matte_mask: " + std::to_string(count) + " ids (at most 16)"; return 1; }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t stream = (hipStream_t) stream_;
+  MatteIdList list{};
+  list.count = count;
+  for (uint32_t i = 0; i < count; i++) list.id[i] = ids[i];
+  Launch l(ctx, stream, LUMC_KERNEL_MATTE);
+  HIP_TRY(ctx, matte_mask_launch(planes, ctx->mattes.pixels, ctx->mattes.samples, list, d_mask, stream));
+  return 0;
+}
+
+int lumc_matte_mask_host(LumContext* ctx, uint32_t layer, const uint32_t* ids, uint32_t count, float* mask) {
+  if (!ctx || !mask) { if (ctx) ctx->error = "lumc_matte_mask_host: null argument"; return 1; }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  DeviceBuffer<float> d;
+  HIP_TRY(ctx, d.resize(std::max<size_t>(ctx->mattes.pixels, 1)));
+  if (lumc_matte_mask(ctx, layer, ids, count, d.get(), nullptr)) return 1;
+  HIP_TRY(ctx, hipDeviceSynchronize());
+  HIP_TRY(ctx, hipMemcpy(mask, d.get(), sizeof(float) * ctx->mattes.pixels, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int lumc_has_mattes(const LumContext* ctx) { return (ctx && ctx->mattes.valid) ? 1 : 0; }
+
+int lumc_matte_release(LumContext* ctx) {
+  if (!ctx) return 1;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipDeviceSynchronize());
+  ctx->mattes = Mattes{};
+  return 0;
+}
+
+int lumc_matte_stats(LumContext* ctx, LumMatteStats* out) {
+  if (!ctx || !out) return 1;
+  const Mattes& m = ctx->mattes;
+  std::memset(out, 0, sizeof(*out));
+  out->bytes = sizeof(uint32_t) * (uint64_t) m.planes.count();
+  out->layers = m.layers;
+  out->valid = m.valid ? 1u : 0u;
+  if (!m.valid) return 0;
+  out->samples = m.samples;
+  out->seconds = m.seconds;
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipDeviceSynchronize());
+  HIP_TRY(ctx, hipMemset(m.d_dropped.get(), 0, sizeof(uint32_t) * kMatteLayers));
+  for (uint32_t layer = 0; layer < kMatteLayers; layer++)
+    if (const uint32_t* planes = m.layer_planes(layer)) {
+      Launch l(ctx, nullptr, LUMC_KERNEL_MATTE);
+      HIP_TRY(ctx, matte_resolve_launch(planes, m.pixels, m.samples, 1u, nullptr, nullptr, nullptr, nullptr, m.d_dropped.get() + layer, nullptr));
+    }
+  HIP_TRY(ctx, hipDeviceSynchronize());
+  HIP_TRY(ctx, hipMemcpy(out->dropped_pixels, m.d_dropped.get(), sizeof(uint32_t) * kMatteLayers, hipMemcpyDeviceToHost));
   return 0;
 }
 
@@ -1585,8 +1765,18 @@ int lumc_pixel_query(LumContext* ctx, uint32_t x, uint32_t y, uint32_t sample_id
 
 int lumc_set_physical_camera(LumContext* ctx, const LumPhysicalCamera* c) {
   if (!ctx) return 1;
-  ctx->guides_valid = false;
-  if (!c) { ctx->camera = kCamThinLens; return 0; }
+  // What was rendered from the first hits - the denoiser's guides, the ID mattes - is dropped when the camera changes. A host sets the camera on every use
+  // (api.cpp set_camera): the camera it already had is no change. (A refused camera drops them too.)
+  const char* changed = "the camera's lens was set since (lumc_set_physical_camera)";
+  if (!c) {
+    if (ctx->camera != kCamThinLens) ctx->drop_first_hit_products(changed);
+    ctx->camera = kCamThinLens;
+    return 0;
+  }
+  struct DropUnlessSame {
+    LumContext* ctx; const char* why; bool same = false;
+    ~DropUnlessSame() { if (!same) ctx->drop_first_hit_products(why); }
+  } drop{ctx, changed};
   if (c->num_interfaces == 0 || c->num_interfaces > LUMC_LENS_MAX_INTERFACES) { ctx->error = "lumc_set_physical_camera: 1 ... 24 interfaces"; return 1; }
   const uint32_t n = c->num_interfaces;
   bool finite = std::isfinite(c->aperture_point) && std::isfinite(c->aperture_radius) && std::isfinite(c->exit_pupil_point) && std::isfinite(c->exit_pupil_radius) &&
@@ -1610,8 +1800,10 @@ int lumc_set_physical_camera(LumContext* ctx, const LumPhysicalCamera* c) {
   l.image_plane_distance = c->image_plane_distance; l.sensor_width = c->sensor_width; l.num_interfaces = n;
   std::memcpy(l.iface, c->interfaces, sizeof(LensInterface) * n);
   std::memcpy(l.medium, c->media, sizeof(LensMedium) * (n + 1));
-  ctx->lens = l;
-  ctx->camera = c->allow_reflections ? kCamPhysicalReflections : kCamPhysical;
+  const int kind = c->allow_reflections ? kCamPhysicalReflections : kCamPhysical;
+  drop.same = ctx->camera == kind && std::memcmp(&ctx->lens, &l, sizeof(l)) == 0;
+  if (!drop.same) ctx->lens = l;
+  ctx->camera = kind;
   return 0;
 }
 

@@ -1258,7 +1258,7 @@ static int update_bridge_table(LumContext* ctx, const LumDeviceSceneView* v) {
 // The scene on the device: the plan of this update (update_plan.h), then its parts in the order their kernels and uploads depend on. Until the update has gone
 // through the context has no scene.
 static int scene_update(LumContext* ctx, const LumDeviceSceneView* v, unsigned dirty) {
-  ctx->guides_valid = false;  // the denoiser's guides were rendered from the scene as it was
+  ctx->drop_first_hit_products("the scene was uploaded or updated since");  // the denoiser's guides and the mattes were rendered from the scene as it was
   DeviceScene& sc = ctx->scene;
   if (!v->bluenoise_2d) { ctx->error = "scene has no blue-noise mask"; return 1; }
   if (v->max_ray_depth > 63) { ctx->error = "max_ray_depth exceeds 63 (6-bit field, device_structs.h:9)"; return 1; }

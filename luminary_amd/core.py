@@ -1135,6 +1135,30 @@ class Core:
                    ids.ctypes.data_as(C.c_void_p), op, out.ctypes.data_as(C.c_void_p))
         return out
 
+    def last_pass_path_counts(self, depths=64):
+        """The number of paths every depth of the last pass held (lumc_last_pass_path_counts): a list, depth 0 first, 0 beyond the scene's depth limit"""
+        out = (C.c_uint32 * depths)()
+        self._call("lumc_last_pass_path_counts", C.c_uint32(depths), out)
+        return [int(x) for x in out]
+
+    PARTICLE_PROBE_UNTOUCHED = 0xFFFFFFFF
+
+    def trace_particles_probe(self, origins, dirs, tmax, states, pixel_samples):
+        """Caller-made queue entries through the active flavour's k_trace_particles (lumc_trace_particles_probe_host): world origins and directions [n, 3],
+        tmax [n], state words [n] (bit 0: a delta path - the others are not traced), pixel x, pixel y and sample id [n, 3]. Returns (t [n] float32: tmax where
+        nothing nearer was hit; hit [n] uint32: PARTICLE_PROBE_UNTOUCHED, or 0x80000000 + the particle's index)."""
+        origins = np.ascontiguousarray(origins, dtype=np.float32)
+        dirs = np.ascontiguousarray(dirs, dtype=np.float32)
+        tmax = np.ascontiguousarray(tmax, dtype=np.float32)
+        states = np.ascontiguousarray(states, dtype=np.uint32)
+        pixel_samples = np.ascontiguousarray(pixel_samples, dtype=np.uint32)
+        n = origins.shape[0]
+        assert origins.shape == dirs.shape == pixel_samples.shape == (n, 3) and tmax.shape == states.shape == (n,)
+        t, hit = np.zeros(n, dtype=np.float32), np.zeros(n, dtype=np.uint32)
+        self._call("lumc_trace_particles_probe_host", C.c_uint32(n), origins.ctypes.data_as(C.c_void_p), dirs.ctypes.data_as(C.c_void_p), tmax.ctypes.data_as(C.c_void_p),
+                   states.ctypes.data_as(C.c_void_p), pixel_samples.ctypes.data_as(C.c_void_p), t.ctypes.data_as(C.c_void_p), hit.ctypes.data_as(C.c_void_p))
+        return t, hit
+
     def light_query_host(self, origins, dirs, self_handles, randoms):
         """The light-BVH query of BSDF-sampled directions on plain rays: (light ids [n] uint32, 0xFFFFFFFF = none; num_hits [n] uint32)."""
         origins = np.ascontiguousarray(origins, dtype=np.float32)

@@ -511,10 +511,16 @@ LUM_DEV void trace_items(const DeviceScene& sc, uint32_t n, uint32_t* __restrict
     if (refilling_) { ptime_[8] += __builtin_readcyclecounter() - t_refill_; ptime_[9]++; }
 #endif
     if (__ballot(cur != kTraversalDone) == 0ull) {
-      // Whole-wave refill: every refill meets a wave with nothing live, so one whose items all ended where they were loaded (non-finite rays) must go on to the
-      // rest of its chunk - leaving here would drop it. (The plain rule leaves in the same case, which it meets only where a wave happens to be all idle.)
-      if constexpr (kWholeWaveRefill) { if (more) continue; }
-      break;
+      // Nothing live after a refill. While `more` holds that is no end: the items just handed out all ended where they were loaded - non-finite rays, or a
+      // query whose load declines them (ParticleQuery: every non-delta path, which at depth >= 1 come in runs of thousands) - and the wave must go on to the
+      // rest of its chunk and to further chunks. Leaving here dropped the rest of the chunk and took the wave out of the launch: beyond waves x chunk items the
+      // tail of the queue was traced only by the waves that happened to survive (profiles/multi_round_pass_reproducibility.txt; tests/test_dead_items.py).
+      // The wave leaves when the cursor has passed n (`more` false) and its lanes are done.
+      // How: the whole-wave refill goes back to the refill by name. The plain forms only refrain from leaving: the phase loop below finds nothing live and
+      // leaves at once, which is the same way back and costs the hot kernels no register - with `continue` here the two-level k_trace, k_trace_rays and
+      // k_shadow_rays went from 107-116 to 128 registers and spilled, k_trace_particles from 96 to 122 (profiles/dead_items_isa.txt).
+      if constexpr (kWholeWaveRefill) { if (more) continue; break; }
+      else { if (!more) break; }
     }
     LUM_PHASE(5);
 

@@ -1600,6 +1600,57 @@ int lumc_trace_visibility_host(LumContext* ctx, uint32_t n, const float* origins
   return 0;
 }
 
+// The number of paths every depth of the LAST pass held (the control words' kCtlPaths, zeroed when a pass begins): out[d] for d < min(count, max_ray_depth + 2).
+// Read-only; waits for the device.
+int lumc_last_pass_path_counts(LumContext* ctx, uint32_t count, uint32_t* out) {
+  if (!ctx || !ctx->has_scene || !out) { if (ctx) ctx->error = "lumc_last_pass_path_counts: no scene or null argument"; return 1; }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HIP_TRY(ctx, hipDeviceSynchronize());
+  const uint32_t rows = std::min(std::min(count, ctx->scene.max_ray_depth + 2u), kCtrlRows - 2u);
+  for (uint32_t d = 0; d < count; d++) out[d] = 0u;
+  for (uint32_t d = 0; d < rows; d++) HIP_TRY(ctx, hipMemcpy(out + d, ctx->d_ctrl.get() + kCtlStride * d + kCtlPaths, sizeof(uint32_t), hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// The particle pass on caller-made queue entries through the render's own kernel: a temporary PathQueue filled on the host (no kernel of the probe's own), the
+// item count and the work cursor in the spare control row, the active flavour's k_trace_particles launched by trace_particles as a pass launches it. The hit words
+// start as LUMC_PARTICLE_PROBE_UNTOUCHED, so an item that nobody answered - or that the kernel does not trace - shows.
+int lumc_trace_particles_probe_host(LumContext* ctx, uint32_t n, const float* origins, const float* dirs, const float* tmax, const uint32_t* states, const uint32_t* pixel_samples,
+                                    float* out_t, uint32_t* out_hit) {
+  if (!ctx || !ctx->has_scene) { if (ctx) ctx->error = "lumc_trace_particles_probe_host: no scene"; return 1; }
+  if (n == 0) return 0;
+  if (!origins || !dirs || !tmax || !states || !pixel_samples || !out_t || !out_hit) { ctx->error = "lumc_trace_particles_probe_host: null argument"; return 1; }
+  if (!ctx->scene.particles_active || !ctx->scene.particle_bvh_nodes) { ctx->error = "lumc_trace_particles_probe_host: the scene has no particles"; return 1; }
+  HIP_TRY(ctx, hipSetDevice(ctx->device));
+  std::vector<float4> h_origin_t(n), h_dir_slot(n);
+  std::vector<uint4> h_aux(n), h_hit_id(n);
+  for (uint32_t i = 0; i < n; i++) {
+    h_origin_t[i] = make_float4(origins[3 * (size_t) i], origins[3 * (size_t) i + 1], origins[3 * (size_t) i + 2], tmax[i]);
+    h_dir_slot[i] = make_float4(dirs[3 * (size_t) i], dirs[3 * (size_t) i + 1], dirs[3 * (size_t) i + 2], 0.0f);
+    h_aux[i] = make_uint4(0u, 0u, 0u, states[i]);
+    const uint32_t* ps = pixel_samples + 3 * (size_t) i;
+    h_hit_id[i] = make_uint4(LUMC_PARTICLE_PROBE_UNTOUCHED, 0u, (ps[0] & 0xFFFFu) | (ps[1] << 16), ps[2]);
+  }
+  DeviceBuffer<float4> d_origin_t, d_dir_slot;
+  DeviceBuffer<uint4> d_aux, d_hit_id;
+  HIP_TRY(ctx, d_origin_t.assign(h_origin_t.data(), n));
+  HIP_TRY(ctx, d_dir_slot.assign(h_dir_slot.data(), n));
+  HIP_TRY(ctx, d_aux.assign(h_aux.data(), n));
+  HIP_TRY(ctx, d_hit_id.assign(h_hit_id.data(), n));
+  PathQueue q{};
+  q.origin_t = d_origin_t.get(); q.dir_slot = d_dir_slot.get(); q.aux = d_aux.get(); q.hit_id = d_hit_id.get();
+  uint32_t* ctrl = ctx->d_ctrl.get() + kCtlStride * (kCtrlRows - 2);
+  HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t) (ctrl + kCtlPaths), (int) n, 1, nullptr));
+  HIP_TRY(ctx, hipMemsetAsync(ctrl + kCtlParticleCursor, 0, sizeof(uint32_t), nullptr));
+  trace_particles(ctx, nullptr, q, ctrl, n);
+  HIP_TRY(ctx, hipGetLastError());
+  HIP_TRY(ctx, hipDeviceSynchronize());
+  HIP_TRY(ctx, hipMemcpy(h_origin_t.data(), d_origin_t.get(), sizeof(float4) * (size_t) n, hipMemcpyDeviceToHost));
+  HIP_TRY(ctx, hipMemcpy(h_hit_id.data(), d_hit_id.get(), sizeof(uint4) * (size_t) n, hipMemcpyDeviceToHost));
+  for (uint32_t i = 0; i < n; i++) { out_t[i] = h_origin_t[i].w; out_hit[i] = h_hit_id[i].x; }
+  return 0;
+}
+
 // The light-BVH query of BSDF-sampled directions (light_query, dev_trace.h) on plain rays, in the active flavour: out_ids = the picked light or 0xFFFFFFFF, out_num_hits = the
 // number of candidates. A scene without lights answers (0xFFFFFFFF, 0) without a launch.
 int lumc_light_query_host(LumContext* ctx, uint32_t n, const float* origins, const float* dirs, const uint32_t* self, const float* randoms, uint32_t* out_ids, uint32_t* out_num_hits) {

@@ -373,8 +373,9 @@ def test_a_pass_of_more_than_one_round_with_ocean_fog_and_clouds(flavour):
     the next. A pass of a few thousand paths has one round; this one holds a little more than the capped grid has threads, so that some workgroups have
     a second, partial round and others none. Ocean, fog and clouds under the procedural sky with aerial perspective put k_ocean_shade, k_clouds,
     k_volume_inscatter and k_shade<.., water> into the schedule. The same sample ids in passes of one round each give the same moments bit for bit (each
-    flavour against itself). Particles are NOT in the scene: with them a pass of more than one round is not reproducible from one run to the next
-    (profiles/multi_round_pass_reproducibility.txt), so k_particle_shade's carry stays unchecked until that is found."""
+    flavour against itself). Particles are in the scene too, for k_particle_shade's carry: such a pass used not to reproduce itself from one run to the next,
+    because waves of k_trace_particles that were handed 64 non-delta paths left the launch (profiles/multi_round_pass_reproducibility.txt;
+    tests/test_dead_items.py, tests/test_particles.py::test_a_large_pass_with_particles_is_the_same_image_however_it_is_split)."""
     from luminary_amd.core import Core
     W, H = 192, 128
     cap = _grid_cap_threads()
@@ -384,6 +385,7 @@ def test_a_pass_of_more_than_one_round_with_ocean_fog_and_clouds(flavour):
     f = host.get_fog(); f.active, f.density = True, 40.0; host.set_fog(f)
     c = host.get_cloud(); c.active = True; host.set_cloud(c)
     k = host.get_sky(); k.aerial_perspective = True; host.set_sky(k)
+    _with_particles(host, count=1500, size=20.0, scale=5.0)
     view = oracle_lib.with_cloud_noise(_view(host))
     core = Core(0)
     try:

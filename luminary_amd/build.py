@@ -39,9 +39,11 @@ if os.environ.get("LUM_FAST_FLAGS") is not None:  # diagnosis only (tools/flavou
 # (csrc/device/kernel_shadow.h, profiles/r05_ab_experiments.txt); LUM_FAST_SHADOW_SCHED= (empty) in the environment builds it with the default scheduler
 SHADOW_SCHED = os.environ.get("LUM_FAST_SHADOW_SCHED", "max-ilp")
 SHADOW_FLAGS = (["-mllvm", "-amdgpu-sched-strategy=" + SHADOW_SCHED] if SHADOW_SCHED else [])
-HIP_SOURCES = [("host/core.hip", EXACT), ("host/scene_device.hip", EXACT), ("host/ray_sort.hip", EXACT), ("host/multi_gpu.hip", EXACT), ("host/lbvh.hip", EXACT), ("host/bvh_refit.hip", EXACT), ("host/instance_update.hip", EXACT), ("host/mesh_deform.hip", EXACT), ("host/light_refit.hip", EXACT), ("host/mesh_shutter.hip", EXACT), ("host/firefly.hip", EXACT), ("host/matte.hip", EXACT),
+HIP_SOURCES = [("host/core.hip", EXACT), ("host/scene_device.hip", EXACT), ("host/ray_sort.hip", EXACT), ("host/multi_gpu.hip", EXACT), ("host/lbvh.hip", EXACT), ("host/bvh_refit.hip", EXACT), ("host/instance_update.hip", EXACT), ("host/mesh_deform.hip", EXACT), ("host/light_refit.hip", EXACT), ("host/mesh_shutter.hip", EXACT), ("host/firefly.hip", EXACT), ("host/matte.hip", EXACT), ("host/probes.hip", EXACT),
                ("device/wavefront_exact.hip", EXACT + ["-DLUM_SHADOW_KERNEL_EXTERN=1"]), ("device/wavefront_fast.hip", FAST + ["-DLUM_SHADOW_KERNEL_EXTERN=1"]),
-               ("device/wavefront_fast_shadow.hip", FAST + SHADOW_FLAGS), ("device/wavefront_exact_shadow.hip", EXACT + SHADOW_FLAGS)]
+               ("device/wavefront_fast_shadow.hip", FAST + SHADOW_FLAGS), ("device/wavefront_exact_shadow.hip", EXACT + SHADOW_FLAGS),
+               # the tests' probe kernels, each flavour's in a unit of its own (device/kernels_probe.h); host/probes.hip launches them
+               ("device/wavefront_exact_probes.hip", EXACT), ("device/wavefront_fast_probes.hip", FAST)]
 STAMP = os.path.join(LIB_DIR, "build_flags.txt")
 
 
@@ -110,7 +112,7 @@ def build(force=False, verbose=False, variant=None):
         out = _run([HIPCC, "--offload-arch=gfx950", *COMMON, *HIP_OPT, *flags, "-fno-slp-vectorize", *EXTRA, "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(CSRC, src), "-o", o])
         return o, out
 
-    with ThreadPoolExecutor(max_workers=len(HIP_SOURCES)) as pool:
+    with ThreadPoolExecutor(max_workers=min(16, len(HIP_SOURCES))) as pool:
         results = list(pool.map(compile_hip, HIP_SOURCES))
     with open(os.path.join(OBJ_DIR, "kernel_resource_usage.txt"), "w") as f:
         for (src, _), (o, out) in zip(HIP_SOURCES, results):

@@ -46,7 +46,8 @@ LUM_DEV uint32_t sobol_second_dim(uint32_t v) {
 // the same in every lane of every wave, so its seed is one scalar load from this table instead of six 32-bit multiplies (quarter-rate instructions) and
 // a dozen other vector instructions per random number and lane - the hash was a twelfth of the shading kernel. The table exists once per translation unit
 // that includes this header; upload_sampler_seeds() fills the including unit's copy on the current device with the same integer function. Every unit whose
-// kernels draw random numbers calls it per device: each flavour's table (init_sampler_seeds, wavefront_table_impl.h) and core.hip (lumc_context_create).
+// kernels draw random numbers calls it per device: each flavour's table (init_sampler_seeds, wavefront_table_impl.h), each flavour's
+// probe table (kernels_probe.h) and core.hip (lumc_context_create).
 constexpr uint32_t kSeedTableSize = 64u * kRndTargetCount;
 __constant__ uint32_t g_sampler_seeds[kSeedTableSize];
 static int upload_sampler_seeds() {  // returns a hipError_t

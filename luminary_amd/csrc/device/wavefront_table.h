@@ -2,6 +2,7 @@
 // table per context (lumc_set_flavour) and launches through it; everything in the signatures is a plain layout from dev_scene.h.
 // Kernels that produce data both flavours must agree on (BSDF / sky tables, panorama bake), bookkeeping (accumulation, adaptive rates) and
 // the display chain exist once, in the exact flavour's namespace: kernels_shared.h, compiled in and launched directly by core.hip.
+// The tests' probe kernels are no part of that table: WavefrontProbes below, filled by each flavour's probe unit and launched by csrc/host/probes.hip.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -93,39 +94,33 @@ struct WavefrontKernels {
                           float4* rec_a, uint4* rec_b);
   void (*denoise_atrous)(hipStream_t s, const DenoiseArgs& p, const float4* a_in, const uint4* rec_b, float4* a_out, bool lds);
   void (*denoise_finish)(uint32_t grid, hipStream_t s, const DenoiseArgs& p, const float4* rec_a, const float* guides, float* image);
+};
+// The truth probes: kernels that only the tests launch and whose signatures follow a test's needs (kernels_probe.h; the records' word counts: probe_layout.h). They
+// live in units of their own with a table of their own, one per flavour like the kernels': the render's launcher table above keeps its shape when a probe comes or goes.
+struct WavefrontProbes {
+  // fills the probe unit's own table of sampler seeds on the current device (dev_sampler.h); returns a hipError_t
+  int (*init_sampler_seeds)();
   // the light-BVH query of n plain rays, one per thread (k_light_query_probe; device buffers: float3 origins / dirs, uint2 self handles, float randoms)
   void (*light_query_probe)(hipStream_t s, const DeviceScene& sc, uint32_t n, const float* origins, const float* dirs, const uint32_t* self, const float* randoms, uint32_t* out_ids,
                             uint32_t* out_num_hits);
-};
-// Probes that only the tests launch and whose signatures follow a test's needs live in a table of their own, one per flavour like the kernels': the render's launcher
-// table above keeps its shape when a probe comes or goes.
-struct WavefrontProbes {
-  // sample_light on n_vertices caller-made vertices x `samples` sample ids, one per thread (k_light_sample_probe, kernels.h: 20 words in per vertex, 154 out per thread);
+  // sample_light on n_vertices caller-made vertices x `samples` sample ids, one per thread (k_light_sample_probe: kLightProbeVertexWords in per vertex, kLightProbeWords out per thread);
   // form: 0 the general form, 1 the plain form (the caller has asked plain_scene), 2 the general form with no light staged in LDS
   void (*light_sample_probe)(hipStream_t s, const DeviceScene& sc, uint32_t n_vertices, uint32_t samples, uint32_t first_sample, uint32_t form, const uint32_t* vertices,
                              uint32_t* out);
-  // sample_bounce and sample_light_direction on the same vertices, one (vertex, sample id) per thread (k_bounce_probe, kernels.h: 20 words in per vertex, 143 out per thread)
+  // sample_bounce and sample_light_direction on the same vertices, one (vertex, sample id) per thread (k_bounce_probe: kBounceProbeWordsPerThread out per thread)
   void (*bounce_probe)(hipStream_t s, const DeviceScene& sc, uint32_t n_vertices, uint32_t samples, uint32_t first_sample, const uint32_t* vertices, uint32_t* out);
-};
-// The sky's probes (tests/test_sky_truth.py), a table of their own for the same reason
-struct WavefrontSkyProbes {
-  // sky_get_color or sky_trace_inscattering on n caller-made rays, one per thread (k_sky_probe, kernels.h: 12 words in per ray, 628 out per thread)
+  // sky_get_color or sky_trace_inscattering on n caller-made rays, one per thread (k_sky_probe: kSkyProbeRayWords in per ray, kSkyProbeWordsPerThread out per thread)
   void (*sky_probe)(hipStream_t s, const DeviceScene& sc, uint32_t n, const uint32_t* rays, uint32_t* out);
-  // sample_sun on the light probe's caller-made vertices, one (vertex, sample id) per thread (k_sun_probe, kernels.h: 20 words in per vertex, 64 out per thread)
+  // sample_sun on the light probe's caller-made vertices, one (vertex, sample id) per thread (k_sun_probe: kSunProbeWordsPerThread out per thread)
   void (*sun_probe)(hipStream_t s, const DeviceScene& sc, uint32_t n_vertices, uint32_t samples, uint32_t first_sample, const uint32_t* vertices, uint32_t* out);
   // v_exp_f32 (op 0), v_sin_f32 (1), v_cos_f32 (2) of n arguments (k_sky_math_probe)
   void (*sky_math_probe)(hipStream_t s, uint32_t n, uint32_t op, const float* x, float* y);
 };
-constexpr uint32_t kLightSampleProbeVertexWords = 20, kLightSampleProbeWords = 154;  // that probe's words per vertex (in) and per thread (out)
-constexpr uint32_t kBounceProbeWords = 143;                                          // the bounce probe's words per thread (its vertex is the light probe's)
-constexpr uint32_t kSkyProbeInWords = 12, kSkyProbeWords = 628, kSunProbeWords = 64;                      // the sky probe's words per ray (in) and per thread (out)
 
 const WavefrontKernels* wavefront_kernels_exact();  // csrc/device/wavefront_exact.hip
 const WavefrontKernels* wavefront_kernels_fast();   // csrc/device/wavefront_fast.hip
-const WavefrontProbes* wavefront_probes_exact();
-const WavefrontProbes* wavefront_probes_fast();
-const WavefrontSkyProbes* wavefront_sky_probes_exact();
-const WavefrontSkyProbes* wavefront_sky_probes_fast();
+const WavefrontProbes* wavefront_probes_exact();    // csrc/device/wavefront_exact_probes.hip
+const WavefrontProbes* wavefront_probes_fast();     // csrc/device/wavefront_fast_probes.hip
 // The vector registers per lane (hipFuncGetAttributes numRegs) of a flavour's closest-hit kernel in the given form and of its k_light_query, on the current device:
 // what the host asks before it lets the two run side by side (csrc/host/context.h overlap_registers_fit). They return a hipError_t.
 int ray_kernel_registers_exact(bool single_level, uint32_t* trace_regs, uint32_t* light_query_regs);

@@ -171,34 +171,6 @@ static void denoise_atrous(hipStream_t s, const DenoiseArgs& p, const float4* a_
 static void denoise_finish(uint32_t grid, hipStream_t s, const DenoiseArgs& p, const float4* rec_a, const float* guides, float* image) {
   hipLaunchKernelGGL(k_denoise_finish, dim3(grid), dim3(256), 0, s, p, rec_a, guides, image);
 }
-static void light_query_probe(hipStream_t s, const DeviceScene& sc, uint32_t n, const float* origins, const float* dirs, const uint32_t* self, const float* randoms, uint32_t* out_ids,
-                              uint32_t* out_num_hits) {
-  hipLaunchKernelGGL(k_light_query_probe, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, sc, n, origins, dirs, self, randoms, out_ids, out_num_hits);
-}
-static void light_sample_probe(hipStream_t s, const DeviceScene& sc, uint32_t n_vertices, uint32_t samples, uint32_t first_sample, uint32_t form, const uint32_t* vertices,
-                               uint32_t* out) {
-  static_assert(kLightProbeVertexWords == kLightSampleProbeVertexWords && kLightProbeWords == kLightSampleProbeWords, "the host layer sizes the probe's buffers by these");
-  const uint32_t n = n_vertices * samples;
-  if (form == 1u) hipLaunchKernelGGL(k_light_sample_probe<true>, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, sc, n, samples, first_sample, 1u, vertices, out);
-  else hipLaunchKernelGGL(k_light_sample_probe<false>, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, sc, n, samples, first_sample, form == 2u ? 0u : 1u, vertices, out);
-}
-static void bounce_probe(hipStream_t s, const DeviceScene& sc, uint32_t n_vertices, uint32_t samples, uint32_t first_sample, const uint32_t* vertices, uint32_t* out) {
-  static_assert(kBounceProbeWordsPerThread == kBounceProbeWords, "the host layer sizes the probe's buffers by this");
-  const uint32_t n = n_vertices * samples;
-  hipLaunchKernelGGL(k_bounce_probe, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, sc, n, samples, first_sample, vertices, out);
-}
-static void sky_probe(hipStream_t s, const DeviceScene& sc, uint32_t n, const uint32_t* rays, uint32_t* out) {
-  static_assert(kSkyProbeWordsPerThread == kSkyProbeWords && kSkyProbeRayWords == kSkyProbeInWords, "the host layer sizes the probe's buffers by these");
-  hipLaunchKernelGGL(k_sky_probe, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, sc, n, rays, out);
-}
-static void sun_probe(hipStream_t s, const DeviceScene& sc, uint32_t n_vertices, uint32_t samples, uint32_t first_sample, const uint32_t* vertices, uint32_t* out) {
-  static_assert(kSunProbeWordsPerThread == kSunProbeWords, "the host layer sizes the probe's buffers by this");
-  const uint32_t n = n_vertices * samples;
-  hipLaunchKernelGGL(k_sun_probe, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, sc, n, samples, first_sample, vertices, out);
-}
-static void sky_math_probe(hipStream_t s, uint32_t n, uint32_t op, const float* x, float* y) {
-  hipLaunchKernelGGL(k_sky_math_probe, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, s, n, op, x, y);
-}
 
 // Filled by member name: neighbouring members share a function-pointer type (resolve / resolve_listed, particle_shade / ocean_shade, sky_inscattering / clouds),
 // so a positional list with two of them swapped would compile. tests/test_build_units.py checks that no member stays null.
@@ -212,22 +184,10 @@ static constexpr WavefrontKernels make_table() {
   t.trace_particles = trace_particles; t.particle_shade = particle_shade; t.trace_ocean = trace_ocean; t.ocean_shade = ocean_shade;
   t.clouds_list = clouds_list; t.clouds_march = clouds_march; t.clouds = clouds; t.trace_rays = trace_rays;
   t.camera_rays = camera_rays; t.guide = guide;
-  t.guide_normalise = guide_normalise; t.denoise_prepare = denoise_prepare; t.denoise_atrous = denoise_atrous; t.denoise_finish = denoise_finish; t.light_query_probe = light_query_probe;
+  t.guide_normalise = guide_normalise; t.denoise_prepare = denoise_prepare; t.denoise_atrous = denoise_atrous; t.denoise_finish = denoise_finish;
   return t;
 }
 static constexpr WavefrontKernels kTable = make_table();
-static constexpr WavefrontProbes make_probes() {
-  WavefrontProbes p{};
-  p.light_sample_probe = light_sample_probe; p.bounce_probe = bounce_probe;
-  return p;
-}
-static constexpr WavefrontProbes kProbes = make_probes();
-static constexpr WavefrontSkyProbes make_sky_probes() {
-  WavefrontSkyProbes q{};
-  q.sky_probe = sky_probe; q.sun_probe = sun_probe; q.sky_math_probe = sky_math_probe;
-  return q;
-}
-static constexpr WavefrontSkyProbes kSkyProbes = make_sky_probes();
 
 }  // namespace table
 LUM_NS_END
@@ -267,13 +227,9 @@ extern "C" int lumc_debug_phase_stats(uint64_t out[16], int reset) {
 namespace lum {
 #if LUM_FAST
 const WavefrontKernels* wavefront_kernels_fast() { return &fast::table::kTable; }
-const WavefrontProbes* wavefront_probes_fast() { return &fast::table::kProbes; }
-const WavefrontSkyProbes* wavefront_sky_probes_fast() { return &fast::table::kSkyProbes; }
 int ray_kernel_registers_fast(bool single_level, uint32_t* trace_regs, uint32_t* light_query_regs) { return fast::table::ray_kernel_registers(single_level, trace_regs, light_query_regs); }
 #else
 int ray_kernel_registers_exact(bool single_level, uint32_t* trace_regs, uint32_t* light_query_regs) { return exact::table::ray_kernel_registers(single_level, trace_regs, light_query_regs); }
 const WavefrontKernels* wavefront_kernels_exact() { return &exact::table::kTable; }
-const WavefrontProbes* wavefront_probes_exact() { return &exact::table::kProbes; }
-const WavefrontSkyProbes* wavefront_sky_probes_exact() { return &exact::table::kSkyProbes; }
 #endif
 }  // namespace lum

@@ -1,6 +1,6 @@
 // The host layer's context and the helpers its translation units share. Private to csrc/host: core.hip (the context, the work buffers, the render schedule, the
 // adaptive sampler, the output chain, the firefly buckets' entry points and the ray queries, with the flavour-neutral kernels of kernels_shared.h), scene_device.hip (the scene on the device, with the
-// kernels of kernels_scene.h), ray_sort.hip, multi_gpu.hip. The context owns its device memory through DeviceBuffer members (device_buffer.h): deleting it frees them.
+// kernels of kernels_scene.h), probes.hip (the truth probes' entry points), ray_sort.hip, multi_gpu.hip. The context owns its device memory through DeviceBuffer members (device_buffer.h): deleting it frees them.
 // Its other pointers - DeviceScene, the work buffers' arrays (work_layout.h) - are views into those buffers. kernels.h is not included, so a unit that includes
 // this header gets none of the flavoured kernels (their device symbols - the sampler's seed table, the phase counters - exist per translation unit).
 #pragma once
@@ -236,6 +236,9 @@ inline uint32_t grid_for(uint32_t n) {
 inline bool single_level_allowed(const LumContext* ctx) {
   return ctx->single_level != 0 && (ctx->wf != wavefront_kernels_fast() || ctx->first_leaf_identity);
 }
+
+// The truth probes' table (wavefront_table.h WavefrontProbes) of the context's flavour: the one place that tells it from ctx->wf.
+inline const WavefrontProbes* probes_of(const LumContext* ctx) { return ctx->wf == wavefront_kernels_exact() ? wavefront_probes_exact() : wavefront_probes_fast(); }
 
 // The register guard of the overlapped schedule. A SIMD has 512 vector registers per lane, handed out in blocks of 8; the persistent closest-hit kernel keeps four
 // waves on it, and one wave of k_light_query must fit beside them or the two kernels only take turns. (The visibility kernel never runs beside the light queries:

@@ -173,6 +173,8 @@ int lumc_context_create(int device_ordinal, LumContext** out) {
   HIP_TRY(ctx, hipSetDevice(device_ordinal));
   HIP_TRY(ctx, (hipError_t) wavefront_kernels_exact()->init_sampler_seeds());  // per device: module globals live on each GPU
   HIP_TRY(ctx, (hipError_t) wavefront_kernels_fast()->init_sampler_seeds());
+  HIP_TRY(ctx, (hipError_t) wavefront_probes_exact()->init_sampler_seeds());  // the probe units' own tables (kernels_probe.h)
+  HIP_TRY(ctx, (hipError_t) wavefront_probes_fast()->init_sampler_seeds());
   HIP_TRY(ctx, (hipError_t) exact::upload_sampler_seeds());  // this unit's own table: k_pixel_ray draws random numbers
   HIP_TRY(ctx, (hipError_t) scene_device_init());
   HIP_TRY(ctx, ctx->d_ctrl.resize(kCtlStride * kCtrlRows));
@@ -1648,151 +1650,6 @@ int lumc_trace_particles_probe_host(LumContext* ctx, uint32_t n, const float* or
   HIP_TRY(ctx, hipMemcpy(h_origin_t.data(), d_origin_t.get(), sizeof(float4) * (size_t) n, hipMemcpyDeviceToHost));
   HIP_TRY(ctx, hipMemcpy(h_hit_id.data(), d_hit_id.get(), sizeof(uint4) * (size_t) n, hipMemcpyDeviceToHost));
   for (uint32_t i = 0; i < n; i++) { out_t[i] = h_origin_t[i].w; out_hit[i] = h_hit_id[i].x; }
-  return 0;
-}
-
-// The light-BVH query of BSDF-sampled directions (light_query, dev_trace.h) on plain rays, in the active flavour: out_ids = the picked light or 0xFFFFFFFF, out_num_hits = the
-// number of candidates. A scene without lights answers (0xFFFFFFFF, 0) without a launch.
-int lumc_light_query_host(LumContext* ctx, uint32_t n, const float* origins, const float* dirs, const uint32_t* self, const float* randoms, uint32_t* out_ids, uint32_t* out_num_hits) {
-  if (!ctx || !ctx->has_scene) { if (ctx) ctx->error = "lumc_light_query_host: no scene"; return 1; }
-  if (n == 0) return 0;
-  if (!origins || !dirs || !self || !randoms || !out_ids || !out_num_hits) { ctx->error = "lumc_light_query_host: null argument"; return 1; }
-  const DeviceScene& sc = ctx->scene;
-  if (!sc.num_lights || !sc.light_nodes || !sc.light_tris || !sc.light_tri_handles) {
-    for (uint32_t i = 0; i < n; i++) { out_ids[i] = 0xFFFFFFFFu; out_num_hits[i] = 0u; }
-    return 0;
-  }
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  DeviceBuffer<float> d_o, d_d, d_r;
-  DeviceBuffer<uint32_t> d_s, d_out;
-  HIP_TRY(ctx, d_o.assign(origins, 3 * (size_t) n));
-  HIP_TRY(ctx, d_d.assign(dirs, 3 * (size_t) n));
-  HIP_TRY(ctx, d_s.assign(self, 2 * (size_t) n));
-  HIP_TRY(ctx, d_r.assign(randoms, n));
-  HIP_TRY(ctx, d_out.resize(2 * (size_t) n));
-  HIP_TRY(ctx, hipMemset(d_out.get(), 0xFF, sizeof(uint32_t) * 2 * (size_t) n));
-  ctx->wf->light_query_probe(nullptr, sc, n, d_o.get(), d_d.get(), d_s.get(), d_r.get(), d_out.get(), d_out.get() + n);
-  HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipDeviceSynchronize());
-  HIP_TRY(ctx, hipMemcpy(out_ids, d_out.get(), sizeof(uint32_t) * (size_t) n, hipMemcpyDeviceToHost));
-  HIP_TRY(ctx, hipMemcpy(out_num_hits, d_out.get() + n, sizeof(uint32_t) * (size_t) n, hipMemcpyDeviceToHost));
-  return 0;
-}
-
-// sample_light (dev_light.h) on caller-made vertices in the active flavour: num_vertices records of LUMC_LIGHT_PROBE_VERTEX_WORDS words, each sampled with the sample ids
-// first_sample .. first_sample + samples - 1; out: LUMC_LIGHT_PROBE_WORDS words per (vertex, sample id), zero where a lane did not get that far (k_light_sample_probe,
-// kernels.h). form: LUMC_LIGHT_PROBE_GENERAL, _PLAIN (refused unless the scene is one k_shade's plain form shades and no vertex is translucent), _UNSTAGED.
-int lumc_light_sample_probe_host(LumContext* ctx, uint32_t num_vertices, const uint32_t* vertices, uint32_t first_sample, uint32_t samples, int form, uint32_t* out) {
-  static_assert(LUMC_LIGHT_PROBE_VERTEX_WORDS == kLightSampleProbeVertexWords && LUMC_LIGHT_PROBE_WORDS == kLightSampleProbeWords, "lum_core.h and wavefront_table.h");
-  if (!ctx || !ctx->has_scene) { if (ctx) ctx->error = "lumc_light_sample_probe_host: no scene"; return 1; }
-  if (num_vertices == 0 || samples == 0) return 0;
-  if (!vertices || !out) { ctx->error = "lumc_light_sample_probe_host: null argument"; return 1; }
-  if (form < LUMC_LIGHT_PROBE_GENERAL || form > LUMC_LIGHT_PROBE_UNSTAGED) { ctx->error = "lumc_light_sample_probe_host: unknown form"; return 1; }
-  const DeviceScene& sc = ctx->scene;
-  if (!sc.num_lights || !sc.light_tree_root || !sc.light_root_children || !sc.light_tri_table || !sc.light_tri_handles) { ctx->error = "lumc_light_sample_probe_host: the scene has no lights"; return 1; }
-  const size_t n = (size_t) num_vertices * samples;
-  if (n > (1u << 24)) { ctx->error = "lumc_light_sample_probe_host: more than 2^24 threads"; return 1; }
-  if (form == LUMC_LIGHT_PROBE_PLAIN) {
-    if (!plain_scene(sc)) { ctx->error = "lumc_light_sample_probe_host: the plain form does not shade this scene"; return 1; }
-    for (uint32_t v = 0; v < num_vertices; v++)
-      if (vertices[(size_t) v * kLightSampleProbeVertexWords + 15] & 1u) { ctx->error = "lumc_light_sample_probe_host: a translucent vertex in the plain form"; return 1; }
-  }
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  DeviceBuffer<uint32_t> d_v, d_out;
-  HIP_TRY(ctx, d_v.assign(vertices, (size_t) num_vertices * kLightSampleProbeVertexWords));
-  HIP_TRY(ctx, d_out.resize(n * kLightSampleProbeWords));
-  HIP_TRY(ctx, hipMemset(d_out.get(), 0, sizeof(uint32_t) * n * kLightSampleProbeWords));
-  (ctx->wf == wavefront_kernels_exact() ? wavefront_probes_exact() : wavefront_probes_fast())->light_sample_probe(nullptr, sc, num_vertices, samples, first_sample, (uint32_t) form, d_v.get(), d_out.get());
-  HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipDeviceSynchronize());
-  HIP_TRY(ctx, hipMemcpy(out, d_out.get(), sizeof(uint32_t) * n * kLightSampleProbeWords, hipMemcpyDeviceToHost));
-  return 0;
-}
-
-// sample_bounce (dev_bsdf.h) and sample_light_direction (dev_light.h) on the light probe's caller-made vertices in the active flavour, with their stages: out holds
-// LUMC_BOUNCE_PROBE_WORDS words per (vertex, sample id), zero where a stage was not reached (k_bounce_probe, kernels.h).
-int lumc_bounce_probe_host(LumContext* ctx, uint32_t num_vertices, const uint32_t* vertices, uint32_t first_sample, uint32_t samples, uint32_t* out) {
-  static_assert(LUMC_BOUNCE_PROBE_WORDS == kBounceProbeWords, "lum_core.h and wavefront_table.h");
-  static_assert(LUMC_BOUNCE_PROBE_WORDS == LUMC_BOUNCE_PROBE_HEAD_WORDS + 3 * LUMC_BOUNCE_PROBE_TECH_WORDS + LUMC_BOUNCE_PROBE_LIGHT_DIR_WORDS, "lum_core.h");
-  if (!ctx || !ctx->has_scene) { if (ctx) ctx->error = "lumc_bounce_probe_host: no scene"; return 1; }
-  if (num_vertices == 0 || samples == 0) return 0;
-  if (!vertices || !out) { ctx->error = "lumc_bounce_probe_host: null argument"; return 1; }
-  const DeviceScene& sc = ctx->scene;
-  if (!sc.bluenoise_2d || !sc.lut_conductor || !sc.lut_glossy || !sc.lut_dielectric || !sc.lut_dielectric_inv) { ctx->error = "lumc_bounce_probe_host: the scene has no energy tables"; return 1; }
-  const size_t n = (size_t) num_vertices * samples;
-  if (n > (1u << 24)) { ctx->error = "lumc_bounce_probe_host: more than 2^24 threads"; return 1; }
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  DeviceBuffer<uint32_t> d_v, d_out;
-  HIP_TRY(ctx, d_v.assign(vertices, (size_t) num_vertices * kLightSampleProbeVertexWords));
-  HIP_TRY(ctx, d_out.resize(n * kBounceProbeWords));
-  HIP_TRY(ctx, hipMemset(d_out.get(), 0, sizeof(uint32_t) * n * kBounceProbeWords));
-  (ctx->wf == wavefront_kernels_exact() ? wavefront_probes_exact() : wavefront_probes_fast())->bounce_probe(nullptr, sc, num_vertices, samples, first_sample, d_v.get(), d_out.get());
-  HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipDeviceSynchronize());
-  HIP_TRY(ctx, hipMemcpy(out, d_out.get(), sizeof(uint32_t) * n * kBounceProbeWords, hipMemcpyDeviceToHost));
-  return 0;
-}
-
-// sky_get_color or sky_trace_inscattering (dev_sky.h) on caller-made rays in the active flavour, with the march's stages: out holds LUMC_SKY_PROBE_WORDS words per
-// ray, zero where a stage was not reached (k_sky_probe, kernels.h). The scene is in sky mode DEFAULT or HDRI with the two tables on the device, and has no active clouds.
-int lumc_sky_probe_host(LumContext* ctx, uint32_t num_rays, const uint32_t* rays, uint32_t* out) {
-  static_assert(LUMC_SKY_PROBE_WORDS == kSkyProbeWords && LUMC_SKY_PROBE_RAY_WORDS == kSkyProbeInWords, "lum_core.h and wavefront_table.h");
-  static_assert(LUMC_SKY_PROBE_WORDS == LUMC_SKY_PROBE_HEAD_WORDS + LUMC_SKY_PROBE_MAX_STEPS * LUMC_SKY_PROBE_STEP_WORDS, "lum_core.h");
-  if (!ctx || !ctx->has_scene) { if (ctx) ctx->error = "lumc_sky_probe_host: no scene"; return 1; }
-  if (num_rays == 0) return 0;
-  if (!rays || !out) { ctx->error = "lumc_sky_probe_host: null argument"; return 1; }
-  const DeviceScene& sc = ctx->scene;
-  if (!sc.sky_lut_transmittance || !sc.sky_lut_multiscattering) { ctx->error = "lumc_sky_probe_host: the scene has no sky tables"; return 1; }
-  if (sc.cloud_active) { ctx->error = "lumc_sky_probe_host: the probe marches without cloud shadows"; return 1; }
-  if (num_rays > (1u << 20)) { ctx->error = "lumc_sky_probe_host: more than 2^20 rays"; return 1; }
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  DeviceBuffer<uint32_t> d_r, d_out;
-  HIP_TRY(ctx, d_r.assign(rays, (size_t) num_rays * kSkyProbeInWords));
-  HIP_TRY(ctx, d_out.resize((size_t) num_rays * kSkyProbeWords));
-  HIP_TRY(ctx, hipMemset(d_out.get(), 0, sizeof(uint32_t) * num_rays * kSkyProbeWords));
-  (ctx->wf == wavefront_kernels_exact() ? wavefront_sky_probes_exact() : wavefront_sky_probes_fast())->sky_probe(nullptr, sc, num_rays, d_r.get(), d_out.get());
-  HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipDeviceSynchronize());
-  HIP_TRY(ctx, hipMemcpy(out, d_out.get(), sizeof(uint32_t) * num_rays * kSkyProbeWords, hipMemcpyDeviceToHost));
-  return 0;
-}
-// sample_sun (dev_sky.h) on the light probe's caller-made vertices in the active flavour, with its stages: LUMC_SUN_PROBE_WORDS words per (vertex, sample id), zero where
-// a stage was not reached (k_sun_probe, kernels.h). The scene has the sky and the energy tables and no active clouds.
-int lumc_sun_probe_host(LumContext* ctx, uint32_t num_vertices, const uint32_t* vertices, uint32_t first_sample, uint32_t samples, uint32_t* out) {
-  static_assert(LUMC_SUN_PROBE_WORDS == kSunProbeWords, "lum_core.h and wavefront_table.h");
-  if (!ctx || !ctx->has_scene) { if (ctx) ctx->error = "lumc_sun_probe_host: no scene"; return 1; }
-  if (num_vertices == 0 || samples == 0) return 0;
-  if (!vertices || !out) { ctx->error = "lumc_sun_probe_host: null argument"; return 1; }
-  const DeviceScene& sc = ctx->scene;
-  if (!sc.bluenoise_2d || !sc.lut_conductor || !sc.lut_glossy || !sc.lut_dielectric || !sc.lut_dielectric_inv) { ctx->error = "lumc_sun_probe_host: the scene has no energy tables"; return 1; }
-  if (!sc.sky_lut_transmittance) { ctx->error = "lumc_sun_probe_host: the scene has no sky tables"; return 1; }
-  if (sc.cloud_active) { ctx->error = "lumc_sun_probe_host: the probe's scene has no clouds"; return 1; }
-  const size_t n = (size_t) num_vertices * samples;
-  if (n > (1u << 22)) { ctx->error = "lumc_sun_probe_host: more than 2^22 threads"; return 1; }
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  DeviceBuffer<uint32_t> d_v, d_out;
-  HIP_TRY(ctx, d_v.assign(vertices, (size_t) num_vertices * kLightSampleProbeVertexWords));
-  HIP_TRY(ctx, d_out.resize(n * kSunProbeWords));
-  HIP_TRY(ctx, hipMemset(d_out.get(), 0, sizeof(uint32_t) * n * kSunProbeWords));
-  (ctx->wf == wavefront_kernels_exact() ? wavefront_sky_probes_exact() : wavefront_sky_probes_fast())->sun_probe(nullptr, sc, num_vertices, samples, first_sample, d_v.get(), d_out.get());
-  HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipDeviceSynchronize());
-  HIP_TRY(ctx, hipMemcpy(out, d_out.get(), sizeof(uint32_t) * n * kSunProbeWords, hipMemcpyDeviceToHost));
-  return 0;
-}
-// The hardware's v_exp_f32 (op 0), v_sin_f32 (1) and v_cos_f32 (2) on caller-made arguments (k_sky_math_probe): what the fast flavour's exp2_det and sincos_det issue.
-int lumc_sky_math_probe_host(LumContext* ctx, uint32_t op, uint32_t count, const float* x, float* y) {
-  if (!ctx) return 1;
-  if (count == 0) return 0;
-  if (!x || !y || op > 2u) { ctx->error = "lumc_sky_math_probe_host: bad argument"; return 1; }
-  HIP_TRY(ctx, hipSetDevice(ctx->device));
-  DeviceBuffer<float> d_x, d_y;
-  HIP_TRY(ctx, d_x.assign(x, count));
-  HIP_TRY(ctx, d_y.resize(count));
-  wavefront_sky_probes_fast()->sky_math_probe(nullptr, count, op, d_x.get(), d_y.get());
-  HIP_TRY(ctx, hipGetLastError());
-  HIP_TRY(ctx, hipDeviceSynchronize());
-  HIP_TRY(ctx, hipMemcpy(y, d_y.get(), sizeof(float) * count, hipMemcpyDeviceToHost));
   return 0;
 }
 

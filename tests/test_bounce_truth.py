@@ -173,7 +173,7 @@ def _record(section, name, figures):
 
 
 def test_the_bounce_probes_layout_is_one_layout():
-    """The words per thread and per part, as include/lum_core.h, oracle/oracle.h, wavefront_table.h, kernels.h, luminary_amd/core.py, tests/oracle_lib.py and the
+    """The words per thread and per part, as include/lum_core.h, oracle/oracle.h, probe_layout.h, luminary_amd/core.py, tests/oracle_lib.py and the
     truth state them."""
     from luminary_amd.core import Core
 
@@ -186,9 +186,13 @@ def test_the_bounce_probes_layout_is_one_layout():
     assert (oracle_lib.BOUNCE_PROBE_WORDS, oracle_lib.BOUNCE_PROBE_HEAD_WORDS, oracle_lib.BOUNCE_PROBE_TECH_WORDS, oracle_lib.BOUNCE_PROBE_LIGHT_DIR_WORDS) == tuple(want.values())
     assert bt.WORDS == bt.HEAD + 3 * bt.TECH_WORDS + bt.LD_WORDS and bt.LD0 == bt.HEAD + 3 * bt.TECH_WORDS
     device = os.path.join(oracle_lib.ROOT, "luminary_amd", "csrc", "device")
-    assert re.search(r"kBounceProbeWords = %d;" % bt.WORDS, open(os.path.join(device, "wavefront_table.h")).read())
-    assert re.search(r"kBounceProbeHeadWords = %d, kBounceProbeTechWords = %d, kBounceProbeLightDirWords = %d;" % (bt.HEAD, bt.TECH_WORDS, bt.LD_WORDS),
-                     open(os.path.join(device, "kernels.h")).read())
+    layout = open(os.path.join(device, "probe_layout.h")).read()  # the one definition: the kernels (kernels_probe.h) and the host layer (probes.hip) include it
+    assert re.search(r"kBounceProbeHeadWords = %d, kBounceProbeTechWords = %d, kBounceProbeLightDirWords = %d;" % (bt.HEAD, bt.TECH_WORDS, bt.LD_WORDS), layout)
+    assert re.search(r"kBounceProbeWordsPerThread = kBounceProbeHeadWords \+ 3 \* kBounceProbeTechWords \+ kBounceProbeLightDirWords;", layout)
+    host = open(os.path.join(oracle_lib.ROOT, "luminary_amd", "csrc", "host", "probes.hip")).read()
+    assert "static_assert(LUMC_BOUNCE_PROBE_WORDS == kBounceProbeWordsPerThread" in host  # lum_core.h's WORDS is bt.WORDS (above)
+    for f in ("wavefront_table.h", "kernels_probe.h"):
+        assert not re.search(r"constexpr[^;\n]*kBounceProbe\w*Words\w* =", open(os.path.join(device, f)).read()), f
     core_h = open(os.path.join(oracle_lib.ROOT, "include", "lum_core.h")).read()
     enum = re.search(r"enum \{ LUMC_BOUNCE_PROBE_NOT_TAKEN = (\d), LUMC_BOUNCE_PROBE_TAKEN = (\d), LUMC_BOUNCE_PROBE_TOTAL_REFLECTION = (\d) \}", core_h)
     assert [int(x) for x in enum.groups()] == [bt.NOT_TAKEN, bt.TAKEN, bt.TOTAL_REFLECTION]
@@ -680,3 +684,36 @@ def test_gpu_fast_flavour_estimators_are_unbiased():
                 k, what, a.mean(axis=0), b.mean(axis=0), diff, se, paired))
             assert (np.abs(diff) <= 3.0 * se).all(), (k, what, diff, se)
             assert (b.mean(axis=0) > 0).all(), "the estimator is not empty"
+
+
+@pytest.mark.gpu
+def test_gpu_a_switched_context_runs_the_probe_of_a_fresh_context_in_that_flavour(monkeypatch):
+    """Each flavour's probes are a unit of their own with a sampler seed table of their own (kernels_probe.h), chosen per launch from the context's flavour
+    (context.h probes_of). One context switched exact -> fast -> exact answers, bit for bit, what a context created in that flavour answers; the exact words are the
+    oracle's, so a seed table that was never filled does not pass as two equal wrong answers."""
+    from luminary_amd.core import Core
+    mats = [MATERIALS["opaque smooth"], MATERIALS["glass above"], MATERIALS["metallic"], MATERIALS["half coloured"]]
+    v = lt.Vertices(np.zeros((4, 3)), [GENERIC] * 4, [_view(GENERIC, c) for c in (0.5, 0.85, 0.3, 0.6)], [m[0] for m in mats], [m[1] for m in mats], [m[2] for m in mats],
+                    [m[3] for m in mats], [m[4] for m in mats], [(NONE, NONE)] * 4, [(4, 9), (7, 2), (11, 13), (1, 5)]).words()
+    fresh = {}
+    for flavour in ("exact", "fast"):
+        monkeypatch.setenv("LUM_FLAVOUR", flavour)  # read by lumc_context_create: no lumc_set_flavour on this context
+        core = Core(0)
+        try:
+            assert core.flavour == flavour
+            core.upload(_view_with_luts())
+            fresh[flavour] = core.bounce_probe_host(v, 0, 2)
+        finally:
+            core.close()
+    assert fresh["exact"].shape == (4, 2, bt.WORDS) and (fresh["exact"] == oracle_lib.bounce_stages(_view_with_luts(), v, 0, 2)).all()
+    assert (fresh["fast"] != fresh["exact"]).any() and (fresh["fast"][..., 28] == fresh["exact"][..., 28]).all()  # another arithmetic, the same random numbers
+    core = Core(0)
+    try:
+        core.upload(_view_with_luts())
+        for flavour in ("exact", "fast", "exact"):
+            core.set_flavour(flavour)
+            got = core.bounce_probe_host(v, 0, 2)
+            diff = got != fresh[flavour]
+            assert not diff.any(), "after the switch to %s: %d words differ from a fresh context's, first at (vertex, sample, word) %s" % (flavour, int(diff.sum()), np.argwhere(diff)[:8].tolist())
+    finally:
+        core.close()

@@ -75,7 +75,7 @@ def test_the_launcher_table_assigns_every_member_by_name():
     code = "\n".join(line.split("//")[0] for line in struct.splitlines())
     pointers = re.findall(r"\(\*(\w+)\)\(", code)
     plain = re.findall(r"^\s*(?:const char\*|uint32_t|bool)\s+(\w+);", code, re.M)
-    assert len(pointers) == 35 and plain == ["flavour", "trace_block", "fused_resolve"], (len(pointers), plain)
+    assert len(pointers) == 34 and plain == ["flavour", "trace_block", "fused_resolve"], (len(pointers), plain)
     impl = open(os.path.join(DEVICE, "wavefront_table_impl.h")).read()
     body = impl[impl.index("make_table() {"):impl.index("return t;")]
     assigned = dict(re.findall(r"\bt\.(\w+) = ([^;]+);", body))
@@ -83,11 +83,51 @@ def test_the_launcher_table_assigns_every_member_by_name():
     assert all(assigned[p] == p for p in pointers), {p: assigned[p] for p in pointers if assigned[p] != p}
     for p in pointers:  # each name is a launcher defined in the same header
         assert re.search(r"^static (?:int|void) %s\(" % p, impl, re.M), p
-    # the tests' probes have a table of their own, filled the same way
+    # the tests' probes have one table of their own, filled the same way by each flavour's probe unit
+    impl = open(os.path.join(DEVICE, "kernels_probe.h")).read()
+    assert decl.count("struct Wavefront") == 2 and not re.search(r"WavefrontSkyProbes|wavefront_sky_probes", decl + impl)
     probes = decl[decl.index("struct WavefrontProbes {"):decl.index("};", decl.index("struct WavefrontProbes {"))]
     probe_pointers = re.findall(r"\(\*(\w+)\)\(", "\n".join(line.split("//")[0] for line in probes.splitlines()))
     body = impl[impl.index("make_probes() {"):impl.index("return p;")]
     assigned = dict(re.findall(r"\bp\.(\w+) = ([^;]+);", body))
-    assert probe_pointers == ["light_sample_probe", "bounce_probe"] and assigned == {p: p for p in probe_pointers}
+    assert probe_pointers == ["init_sampler_seeds", "light_query_probe", "light_sample_probe", "bounce_probe", "sky_probe", "sun_probe", "sky_math_probe"]
+    assert assigned == {p: p for p in probe_pointers}
     for p in probe_pointers:
         assert re.search(r"^static (?:int|void) %s\(" % p, impl, re.M), p
+    assert sorted(re.findall(r"^const WavefrontProbes\* (\w+)\(\);", decl, re.M)) == ["wavefront_probes_exact", "wavefront_probes_fast"]
+
+
+PROBE_UNITS = {"lum::exact::": "device/wavefront_exact_probes.hip", "lum::fast::": "device/wavefront_fast_probes.hip"}
+
+
+def test_the_probe_kernels_belong_to_the_probe_units_alone():
+    """Every k_*_probe stub is defined by exactly one of the two probe units, its flavour's; neither main unit nor any object built from csrc/host/ defines one."""
+    defined, source_of = _stubs()
+    probes = {k: objs for k, objs in defined.items() if re.search(r"::k_\w+_probe[<(]", k)}
+    names = {re.search(r"::(k_\w+_probe)[<(]", k).group(1) for k in probes}
+    assert names == {"k_light_query_probe", "k_light_sample_probe", "k_bounce_probe", "k_sky_probe", "k_sun_probe", "k_sky_math_probe"}, sorted(names)
+    for flavour, unit in PROBE_UNITS.items():  # both flavours hold all six (k_light_sample_probe in its two forms)
+        mine = [k for k in probes if k.replace("void ", "").startswith(flavour)]
+        assert {re.search(r"::(k_\w+_probe)[<(]", k).group(1) for k in mine} == names and len(mine) == 7, (flavour, mine)
+        for k in mine:
+            assert [source_of[o] for o in probes[k]] == [unit], (k, probes[k])
+    assert len(probes) == 14
+    # ... and the probe units hold nothing else
+    others = sorted(k for k, objs in defined.items() if k not in probes and any(source_of[o] in PROBE_UNITS.values() for o in objs))
+    assert not others, others
+
+
+def test_kernels_h_names_no_probe_and_probes_hip_defines_no_kernel():
+    assert not re.search(r"k_\w+_probe", open(os.path.join(DEVICE, "kernels.h")).read())
+    for header in ("wavefront_table_impl.h", "kernel_shadow.h"):
+        assert not re.search(r"k_\w+_probe|kernels_probe\.h", open(os.path.join(DEVICE, header)).read()), header
+    probe = open(os.path.join(DEVICE, "kernels_probe.h")).read()
+    assert not re.search(r'#include\s+"(kernels|kernel_shadow)\.h"', probe)
+    defined, source_of = _stubs()
+    assert "host/probes.hip" in source_of.values()
+    in_probes_hip = sorted(k for k, objs in defined.items() if "probes.hip.o" in objs)
+    assert not in_probes_hip, in_probes_hip
+    out = subprocess.run(["nm", "-C", "--defined-only", os.path.join(lum_build.OBJ_DIR, "probes.hip.o")], stdout=subprocess.PIPE, text=True, check=True).stdout
+    assert "__device_stub__" not in out and "lumc_bounce_probe_host" in out
+    host = open(os.path.join(ROOT, "luminary_amd", "csrc", "host", "probes.hip")).read()
+    assert "__global__" not in host and not re.search(r'#include\s+"[^"]*\b(kernels\w*|wavefront_table_impl)\.h"', host)

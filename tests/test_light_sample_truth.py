@@ -210,8 +210,13 @@ def test_the_probes_layout_is_one_layout():
     assert core_h == oracle_h == {"VERTEX_WORDS": 20, "WORDS": lt.WORDS} == {"VERTEX_WORDS": Core.LIGHT_PROBE_VERTEX_WORDS, "WORDS": Core.LIGHT_PROBE_WORDS}
     assert (oracle_lib.LIGHT_PROBE_VERTEX_WORDS, oracle_lib.LIGHT_PROBE_WORDS) == (20, lt.WORDS) and lt.WORDS == lt.HEAD + lt.LANES * lt.LANE_WORDS
     assert lt.Vertices([[0, 0, 0]], [[0, 1, 0]], [[0, 1, 0]], [[1, 1, 1]], [1], [1], [1], [0], [(0, 0)], [(0, 0)]).words().shape == (1, 20)
-    table = open(os.path.join(oracle_lib.ROOT, "luminary_amd", "csrc", "device", "wavefront_table.h")).read()
-    assert re.search(r"kLightSampleProbeVertexWords = 20, kLightSampleProbeWords = %d;" % lt.WORDS, table)
+    csrc = os.path.join(oracle_lib.ROOT, "luminary_amd", "csrc")
+    layout = open(os.path.join(csrc, "device", "probe_layout.h")).read()  # the one definition: the kernels (kernels_probe.h) and the host layer (probes.hip) include it
+    assert re.search(r"kLightProbeVertexWords = 20, kLightProbeLaneWords = %d, kLightProbeHeadWords = %d, kLightProbeLanes = %d;" % (lt.LANE_WORDS, lt.HEAD, lt.LANES), layout)
+    assert re.search(r"kLightProbeWords = kLightProbeHeadWords \+ kLightProbeLanes \* kLightProbeLaneWords;", layout)
+    assert "static_assert(kLightProbeLanes == kLightTreeOutputs" in open(os.path.join(csrc, "device", "kernels_probe.h")).read()
+    assert "LUMC_LIGHT_PROBE_VERTEX_WORDS == kLightProbeVertexWords && LUMC_LIGHT_PROBE_WORDS == kLightProbeWords" in open(os.path.join(csrc, "host", "probes.hip")).read()
+    assert "ProbeWords =" not in open(os.path.join(csrc, "device", "wavefront_table.h")).read()
     enum = re.search(r"enum \{ LUMC_LIGHT_PROBE_NO_PICK = (\d), LUMC_LIGHT_PROBE_SELF = (\d), LUMC_LIGHT_PROBE_REFUSED = (\d), LUMC_LIGHT_PROBE_MISSED = (\d), LUMC_LIGHT_PROBE_EVALUATED = (\d) \}",
                      open(os.path.join(oracle_lib.ROOT, "include", "lum_core.h")).read())
     assert [int(x) for x in enum.groups()] == [lt.NO_PICK, lt.SELF, lt.REFUSED, lt.MISSED, lt.EVALUATED]

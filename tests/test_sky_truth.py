@@ -384,16 +384,24 @@ def test_the_sky_probes_layout_is_one_layout():
     assert (oracle_lib.SKY_PROBE_RAY_WORDS, oracle_lib.SKY_PROBE_WORDS, oracle_lib.SKY_PROBE_HEAD_WORDS, oracle_lib.SKY_PROBE_STEP_WORDS, oracle_lib.SKY_PROBE_MAX_STEPS) == tuple(want.values())
     assert st.WORDS == st.HEAD + st.MAX_STEPS * st.STEP_WORDS
     device = os.path.join(oracle_lib.ROOT, "luminary_amd", "csrc", "device")
-    # the sky's probes have a launcher table of their own, filled by member name like the other two
+    # the sky's probes are members of the one probe table, filled by member name in the probe units' header
     decl = open(os.path.join(device, "wavefront_table.h")).read()
-    probes = decl[decl.index("struct WavefrontSkyProbes {"):decl.index("};", decl.index("struct WavefrontSkyProbes {"))]
+    probes = decl[decl.index("struct WavefrontProbes {"):decl.index("};", decl.index("struct WavefrontProbes {"))]
     pointers = re.findall(r"\(\*(\w+)\)\(", "\n".join(line.split("//")[0] for line in probes.splitlines()))
-    impl = open(os.path.join(device, "wavefront_table_impl.h")).read()
-    body = impl[impl.index("make_sky_probes() {"):impl.index("return q;")]
-    assert pointers == ["sky_probe", "sun_probe", "sky_math_probe"] and dict(re.findall(r"\bq\.(\w+) = ([^;]+);", body)) == {p: p for p in pointers}
-    assert re.search(r"kSkyProbeInWords = %d, kSkyProbeWords = %d, kSunProbeWords = %d;" % (st.RAY_WORDS, st.WORDS, st.SUN_WORDS), open(os.path.join(device, "wavefront_table.h")).read())
-    assert re.search(r"kSkyProbeRayWords = %d, kSkyProbeHeadWords = %d, kSkyProbeStepWords = %d, kSkyProbeMaxSteps = %d;" % (st.RAY_WORDS, st.HEAD, st.STEP_WORDS, st.MAX_STEPS),
-                     open(os.path.join(device, "kernels.h")).read())
+    impl = open(os.path.join(device, "kernels_probe.h")).read()
+    body = impl[impl.index("make_probes() {"):impl.index("return p;")]
+    assigned = dict(re.findall(r"\bp\.(\w+) = ([^;]+);", body))
+    assert pointers[-3:] == ["sky_probe", "sun_probe", "sky_math_probe"] and sorted(assigned) == sorted(pointers) and all(assigned[p] == p for p in pointers)
+    # one definition per word count: probe_layout.h, which the kernels and the host layer include; neither states a number of its own
+    layout = open(os.path.join(device, "probe_layout.h")).read()
+    assert re.search(r"kSkyProbeRayWords = %d, kSkyProbeHeadWords = %d, kSkyProbeStepWords = %d, kSkyProbeMaxSteps = %d;" % (st.RAY_WORDS, st.HEAD, st.STEP_WORDS, st.MAX_STEPS), layout)
+    assert re.search(r"kSkyProbeWordsPerThread = kSkyProbeHeadWords \+ kSkyProbeMaxSteps \* kSkyProbeStepWords;", layout) and st.WORDS == st.HEAD + st.MAX_STEPS * st.STEP_WORDS
+    assert re.search(r"kSunProbeWordsPerThread = %d;" % st.SUN_WORDS, layout)
+    host = open(os.path.join(oracle_lib.ROOT, "luminary_amd", "csrc", "host", "probes.hip")).read()
+    for text in (decl, impl, host):
+        assert not re.search(r"constexpr[^;\n]*k(Sky|Sun)Probe\w*Words\w* =", text)
+    assert '#include "probe_layout.h"' in impl and '#include "../device/probe_layout.h"' in host
+    assert "LUMC_SKY_PROBE_WORDS == kSkyProbeWordsPerThread && LUMC_SKY_PROBE_RAY_WORDS == kSkyProbeRayWords" in host
     core_h = open(os.path.join(oracle_lib.ROOT, "include", "lum_core.h")).read()
     enum = re.search(r"LUMC_SKY_PROBE_CELESTIALS = (\d), LUMC_SKY_PROBE_PRIMARY_RAY = (\d), LUMC_SKY_PROBE_AERIAL = (\d)", core_h)
     assert [int(x) for x in enum.groups()] == [st.CELESTIALS, st.PRIMARY, st.AERIAL]
@@ -743,8 +751,9 @@ def test_the_sun_probes_layout_is_one_layout():
     text = lambda path: open(os.path.join(oracle_lib.ROOT, path)).read()
     assert re.search(r"#define LUMC_SUN_PROBE_WORDS %d\b" % st.SUN_WORDS, text("include/lum_core.h")) and re.search(r"#define ORACLE_SUN_PROBE_WORDS %d\b" % st.SUN_WORDS, text("oracle/oracle.h"))
     assert Core.SUN_PROBE_WORDS == oracle_lib.SUN_PROBE_WORDS == st.SUN_WORDS
-    assert re.search(r"kSunProbeWords = %d;" % st.SUN_WORDS, text("luminary_amd/csrc/device/wavefront_table.h"))
-    assert re.search(r"kSunProbeWordsPerThread = %d;" % st.SUN_WORDS, text("luminary_amd/csrc/device/kernels.h"))
+    assert re.search(r"kSunProbeWordsPerThread = %d;" % st.SUN_WORDS, text("luminary_amd/csrc/device/probe_layout.h"))
+    assert "static_assert(LUMC_SUN_PROBE_WORDS == kSunProbeWordsPerThread" in text("luminary_amd/csrc/host/probes.hip")
+    assert "kSunProbeWordsPerThread" in text("luminary_amd/csrc/device/kernels_probe.h") and "kSunProbeWordsPerThread =" not in text("luminary_amd/csrc/device/kernels_probe.h")
     dev = text("luminary_amd/csrc/device/dev_sky.h")
     assert re.search(r"kRndSunBsdf = %d, kRndSunBsdfMethod = %d, kRndSunRay = %d, kRndSunResampling = %d;" % (st.RT_SUN_BSDF, st.RT_SUN_BSDF_METHOD, st.RT_SUN_RAY, st.RT_SUN_RESAMPLING), dev)
 

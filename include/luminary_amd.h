@@ -660,6 +660,41 @@ LUMINARY_API LuminaryResult luminary_ext_get_matte(LuminaryHost* host, uint32_t 
 LUMINARY_API LuminaryResult luminary_ext_get_matte_mask(LuminaryHost* host, uint32_t layer, const uint32_t* ids, uint32_t count, float* mask, uint32_t width, uint32_t height);
 LUMINARY_API LuminaryResult luminary_ext_get_matte_stats(LuminaryHost* host, LuminaryMatteStats* out);
 LUMINARY_API LuminaryResult luminary_ext_get_first_hit_guides(LuminaryHost* host, float* albedo, float* normal, float* depth, uint32_t width, uint32_t height);
+/* Image history (include/lum_core.h lumc_set_history / lumc_history_carry / lumc_history_blend; csrc/host/history.h): while it is on, a restart
+ * of the integration whose only cause is a move of the thin-lens camera (luminary_host_set_camera with nothing changed but pos, rotation, thin_lens.fov,
+ * thin_lens.aperture_size and object_distance - luminary_ext_camera_change_carries_history) keeps the image as it was last shown: the next output reprojects it
+ * into the new camera through the first-hit guides and blends it with the new accumulation, shown = (W C + N cur) / (W + N). The stage runs in the output chain after
+ * the denoiser and before bloom, for beauty images of the whole frame in the default shading mode, never for the undersampling preview's coarse images; the guides
+ * are then rendered for every accumulation (the denoiser's guide_samples), with the denoiser on or off. Every other restart - any other entity, a material, a mesh, an
+ * instance, the device partition, a frame-size change, a physical camera, a lens change, a shutter render, luminary_host_start_new_render - drops the history, with a
+ * line in the log. Several moves without an output in between carry from the older frame. An accumulation driven by adaptive sampling is skipped and counted.
+ * Off by default; setting it does not restart the integration; with it off no output changes a byte. luminary_ext_get_radiance, _get_accumulators, _get_denoised and the
+ * mattes are never affected.
+ *   luminary_ext_set_history        LUMINARY_ERROR_INVALID_API_ARGUMENT with a line in the log: max_history not > 0, depth_tolerance not >= 0, normal_threshold outside
+ *                                   [-1, 1], clamp_sigma not >= 0, or a value that is not finite.
+ *   luminary_ext_get_history_image  the image as last shown before bloom, interleaved rgb [height][width][3], and its weight plane (samples it stands for); each may
+ *                                   be NULL. LUMINARY_ERROR_API_EXCEPTION while there is none (off, before the first output, after a drop). */
+typedef struct LuminaryHistorySettings {
+  bool enabled;            /* false */
+  float max_history;       /* cap of the carried weight, in samples: 32 */
+  float depth_tolerance;   /* a tap is refused when its depth differs from the reprojected distance by more than this fraction: 0.02 */
+  float normal_threshold;  /* ... or when the dot product of the two normals is below this: 0.9 */
+  float clamp_sigma;       /* > 0: the carried colour is clamped to mean +- clamp_sigma sigma of the new image's 3 x 3 neighbourhood; 0: off */
+} LuminaryHistorySettings;
+typedef struct LuminaryHistoryStats {
+  uint64_t frames_carried, frames_dropped, frames_skipped;  /* accumulations that started from a reprojected frame / drops of a held frame / outputs skipped under adaptive sampling */
+  uint32_t last_carried, last_rejected, last_off;            /* pixels of the last reprojection: carried; refused by the depth / normal / weight tests; behind or off the old frame */
+  uint32_t valid;                                            /* 1: luminary_ext_get_history_image would answer */
+  uint64_t bytes;                                            /* held by the main device's state and carried planes */
+  double seconds;                                            /* device time of the history kernels while the core profiles (lumc_set_profiling), else 0 */
+  char last_drop[96];                                        /* the last drop's cause, empty if none */
+} LuminaryHistoryStats;
+LUMINARY_API LuminaryResult luminary_ext_set_history(LuminaryHost* host, const LuminaryHistorySettings* settings);
+LUMINARY_API LuminaryResult luminary_ext_get_history(LuminaryHost* host, LuminaryHistorySettings* settings);
+LUMINARY_API LuminaryResult luminary_ext_get_history_image(LuminaryHost* host, float* rgb, float* weight, uint32_t width, uint32_t height);
+LUMINARY_API LuminaryResult luminary_ext_get_history_stats(LuminaryHost* host, LuminaryHistoryStats* out);
+/* Whether replacing camera `old` by `input` restarts the integration AND keeps the history (see above); false for a change that does not restart at all. */
+LUMINARY_API LuminaryResult luminary_ext_camera_change_carries_history(const LuminaryCamera* input, const LuminaryCamera* old, bool* carries);
 /* out[0] closest-hit rays, [1] shadow rays, [2] light-BVH queries, [3] shaded vertices, [4] BVH nodes visited, [5] triangles tested. */
 LUMINARY_API LuminaryResult luminary_ext_get_ray_counters(LuminaryHost* host, uint64_t out[8]);
 /* The lumc context of this host (include/lum_core.h), for callers that drive passes themselves. */

@@ -219,6 +219,17 @@ class MatteStats(C.Structure):
                 ("dropped_pixels", C.c_uint32 * 2), ("reserved", C.c_uint32), ("seconds", C.c_double)]
 
 
+class HistorySettings(C.Structure):
+    """include/luminary_amd.h LuminaryHistorySettings (defaults: off, 32, 0.02, 0.9, no clamp)."""
+    _fields_ = [("enabled", C.c_bool), ("max_history", C.c_float), ("depth_tolerance", C.c_float), ("normal_threshold", C.c_float), ("clamp_sigma", C.c_float)]
+
+
+class HistoryStats(C.Structure):
+    """LuminaryHistoryStats"""
+    _fields_ = [("frames_carried", C.c_uint64), ("frames_dropped", C.c_uint64), ("frames_skipped", C.c_uint64), ("last_carried", C.c_uint32), ("last_rejected", C.c_uint32),
+                ("last_off", C.c_uint32), ("valid", C.c_uint32), ("bytes", C.c_uint64), ("seconds", C.c_double), ("last_drop", C.c_char * 96)]
+
+
 MATTE_LAYER_INSTANCE, MATTE_LAYER_MATERIAL = 1, 2  # LUMINARY_MATTE_LAYER_*
 MATTE_ID_EMPTY, MATTE_ID_MISS, MATTE_ID_OCEAN, MATTE_ID_PARTICLE = 0xFFFFFFFF, 0xFFFFFFFE, 0xFFFFFFFD, 0xFFFFFFFC  # LUMINARY_MATTE_ID_*
 
@@ -800,6 +811,32 @@ class Host:
         s = FireflyStats()
         _call("luminary_ext_get_firefly_stats", self._h, C.byref(s))
         return {name: getattr(s, name) for name, _ in s._fields_}
+
+    def get_history(self):
+        """luminary_ext_get_history"""
+        f = HistorySettings()
+        _call("luminary_ext_get_history", self._h, C.byref(f))
+        return f
+
+    def set_history(self, settings=None, **fields):
+        """luminary_ext_set_history: the given settings, or the current ones with `fields` changed (set_history(enabled=True)). Does not restart the integration."""
+        f = settings if settings is not None else self.get_history()
+        for k, v in fields.items():
+            setattr(f, k, v)
+        _call("luminary_ext_set_history", self._h, C.byref(f))
+
+    def history_image(self, width, height):
+        """luminary_ext_get_history_image: (the image as last shown before bloom [H, W, 3], its weight plane [H, W]) float32."""
+        import numpy as np
+        rgb, weight = np.zeros((height, width, 3), dtype=np.float32), np.zeros((height, width), dtype=np.float32)
+        _call("luminary_ext_get_history_image", self._h, rgb.ctypes.data_as(C.c_void_p), weight.ctypes.data_as(C.c_void_p), C.c_uint32(width), C.c_uint32(height))
+        return rgb, weight
+
+    def history_stats(self):
+        """luminary_ext_get_history_stats, as a dict."""
+        s = HistoryStats()
+        _call("luminary_ext_get_history_stats", self._h, C.byref(s))
+        return {name: (getattr(s, name).decode() if name == "last_drop" else getattr(s, name)) for name, _ in s._fields_}
 
     def render_mattes(self, samples=4, layers=MATTE_LAYER_INSTANCE | MATTE_LAYER_MATERIAL):
         """luminary_ext_render_mattes: ID mattes of the whole frame from `samples` first-hit passes on the main device; the accumulation is not touched."""

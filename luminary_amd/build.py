@@ -16,7 +16,7 @@ OBJ_DIR = os.path.join(ROOT, "lib", "obj")
 ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 HIPCC = os.path.join(ROCM, "bin", "hipcc")
 
-HOST_SOURCES = ["host/scene.cpp", "host/bvh_build.cpp", "host/loaders.cpp", "host/api.cpp", "host/utils_api.cpp", "host/output.cpp", "host/tiles.cpp", "host/mesh_deform.cpp", "host/light_refit.cpp", "host/mesh_shutter.cpp", "host/firefly.cpp", "host/matte.cpp"]
+HOST_SOURCES = ["host/scene.cpp", "host/bvh_build.cpp", "host/loaders.cpp", "host/api.cpp", "host/utils_api.cpp", "host/output.cpp", "host/tiles.cpp", "host/mesh_deform.cpp", "host/light_refit.cpp", "host/mesh_shutter.cpp", "host/firefly.cpp", "host/matte.cpp", "host/history.cpp"]
 EXTRA = os.environ.get("LUM_CXXFLAGS", "").split()
 COMMON = ["-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 # The HIP sources are compiled with -Os. Measured (profiles/r05_ab_experiments.txt, three interleaved repeats): 1.3 % off k_trace, 0.7 % off k_shade, 1.5 % off
@@ -39,7 +39,7 @@ if os.environ.get("LUM_FAST_FLAGS") is not None:  # diagnosis only (tools/flavou
 # (csrc/device/kernel_shadow.h, profiles/r05_ab_experiments.txt); LUM_FAST_SHADOW_SCHED= (empty) in the environment builds it with the default scheduler
 SHADOW_SCHED = os.environ.get("LUM_FAST_SHADOW_SCHED", "max-ilp")
 SHADOW_FLAGS = (["-mllvm", "-amdgpu-sched-strategy=" + SHADOW_SCHED] if SHADOW_SCHED else [])
-HIP_SOURCES = [("host/core.hip", EXACT), ("host/scene_device.hip", EXACT), ("host/ray_sort.hip", EXACT), ("host/multi_gpu.hip", EXACT), ("host/lbvh.hip", EXACT), ("host/bvh_refit.hip", EXACT), ("host/instance_update.hip", EXACT), ("host/mesh_deform.hip", EXACT), ("host/light_refit.hip", EXACT), ("host/mesh_shutter.hip", EXACT), ("host/firefly.hip", EXACT), ("host/matte.hip", EXACT), ("host/probes.hip", EXACT),
+HIP_SOURCES = [("host/core.hip", EXACT), ("host/scene_device.hip", EXACT), ("host/ray_sort.hip", EXACT), ("host/multi_gpu.hip", EXACT), ("host/lbvh.hip", EXACT), ("host/bvh_refit.hip", EXACT), ("host/instance_update.hip", EXACT), ("host/mesh_deform.hip", EXACT), ("host/light_refit.hip", EXACT), ("host/mesh_shutter.hip", EXACT), ("host/firefly.hip", EXACT), ("host/matte.hip", EXACT), ("host/history.hip", EXACT), ("host/probes.hip", EXACT),
                ("device/wavefront_exact.hip", EXACT + ["-DLUM_SHADOW_KERNEL_EXTERN=1"]), ("device/wavefront_fast.hip", FAST + ["-DLUM_SHADOW_KERNEL_EXTERN=1"]),
                ("device/wavefront_fast_shadow.hip", FAST + SHADOW_FLAGS), ("device/wavefront_exact_shadow.hip", EXACT + SHADOW_FLAGS),
                # the tests' probe kernels, each flavour's in a unit of its own (device/kernels_probe.h); host/probes.hip launches them

@@ -217,6 +217,95 @@ def matte_mask_host_twin(slots_id, slots_count, samples, ids):
     return mask
 
 
+class HistoryParams(C.Structure):
+    """LumHistoryParams"""
+    _fields_ = [("enabled", C.c_uint32), ("max_history", C.c_float), ("depth_tolerance", C.c_float), ("normal_threshold", C.c_float), ("clamp_sigma", C.c_float)]
+
+
+class HistoryKey(C.Structure):
+    """LumHistoryKey: the thin-lens camera a frame was shown from, as the scene view holds it"""
+    _fields_ = [("pos", C.c_float * 3), ("rotation", C.c_float * 4), ("fov", C.c_float), ("width", C.c_uint32), ("height", C.c_uint32)]
+
+
+class HistoryStats(C.Structure):
+    """LumHistoryStats"""
+    _fields_ = [("carries", C.c_uint64), ("blends", C.c_uint64), ("drops", C.c_uint64), ("bytes", C.c_uint64), ("last_carried", C.c_uint32), ("last_rejected", C.c_uint32),
+                ("last_off", C.c_uint32), ("has_state", C.c_uint32), ("has_carried", C.c_uint32), ("reserved", C.c_uint32), ("carry_ms", C.c_double), ("blend_ms", C.c_double),
+                ("carry_launches", C.c_uint32), ("blend_launches", C.c_uint32), ("dropped_why", C.c_char_p)]
+
+
+def history_params(enabled=True, max_history=32.0, depth_tolerance=0.02, normal_threshold=0.9, clamp_sigma=0.0):
+    return HistoryParams(1 if enabled else 0, max_history, depth_tolerance, normal_threshold, clamp_sigma)
+
+
+def history_key(pos, rotation, fov, width, height):
+    """rotation: the quaternion (x, y, z, w)"""
+    return HistoryKey((C.c_float * 3)(*[float(v) for v in pos]), (C.c_float * 4)(*[float(v) for v in rotation]), float(fov), int(width), int(height))
+
+
+def _f32(a, shape, what):
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    if a.size != int(np.prod(shape)):
+        raise ValueError("%s: %d floats expected" % (what, int(np.prod(shape))))
+    return a.reshape(shape)
+
+
+def history_reproject_host(now_key, old_key, params, normal, depth, old_shown, old_weight, old_normal, old_depth):
+    """lumc_history_reproject_host, no device needed: the host twin of k_history_reproject. normal [3, P], depth [P] of now_key's frame; old_* of old_key's.
+    Returns (carried [3, P], carried_weight [P], (carried, rejected, off)); raises ValueError where the twin refuses."""
+    fn = _lib().lumc_history_reproject_host
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p] * 12
+    P, Q = now_key.width * now_key.height, old_key.width * old_key.height
+    ins = [_f32(normal, (3, P), "normal"), _f32(depth, (P,), "depth"), _f32(old_shown, (3, Q), "old_shown"), _f32(old_weight, (Q,), "old_weight"),
+           _f32(old_normal, (3, Q), "old_normal"), _f32(old_depth, (Q,), "old_depth")]
+    carried, weight = np.zeros((3, P), np.float32), np.zeros(P, np.float32)
+    stats = (C.c_uint32 * 3)()
+    if fn(C.addressof(now_key), C.addressof(old_key), C.addressof(params), *[a.ctypes.data for a in ins], carried.ctypes.data, weight.ctypes.data, C.addressof(stats)) != 0:
+        raise ValueError("lumc_history_reproject_host refused its arguments")
+    return carried, weight, tuple(int(x) for x in stats)
+
+
+def history_blend_host(params, width, height, uniform_samples, image, carried=None, carried_weight=None):
+    """lumc_history_blend_host, no device needed: the host twin of k_history_blend. image [3, P] planar (a copy is blended); carried [3, P], carried_weight [P] or
+    both None. Returns (image after the blend, shown [3, P], weight [P])."""
+    fn = _lib().lumc_history_blend_host
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32] + [C.c_void_p] * 5
+    P = int(width) * int(height)
+    out = _f32(image, (3, P), "image").copy()
+    c = None if carried is None else _f32(carried, (3, P), "carried")
+    w = None if carried_weight is None else _f32(carried_weight, (P,), "carried_weight")
+    shown, weight = np.zeros((3, P), np.float32), np.zeros(P, np.float32)
+    if fn(C.addressof(params), int(width), int(height), int(uniform_samples), out.ctypes.data, None if c is None else c.ctypes.data, None if w is None else w.ctypes.data,
+          shown.ctypes.data, weight.ctypes.data) != 0:
+        raise ValueError("lumc_history_blend_host refused its arguments")
+    return out, shown, weight
+
+
+def history_centre_ray_host(key, px, py):
+    fn = _lib().lumc_history_centre_ray_host
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+    d = np.zeros(3, np.float32)
+    if fn(C.addressof(key), int(px), int(py), d.ctypes.data) != 0:
+        raise ValueError("lumc_history_centre_ray_host refused its arguments")
+    return d
+
+
+def history_project_host(key, v):
+    """lumc_history_project_host: (fx, fy) of a vector relative to the key's camera, or None where it lies behind it."""
+    fn = _lib().lumc_history_project_host
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p] * 4
+    vv = np.ascontiguousarray(v, dtype=np.float32).reshape(3)
+    fx, fy = C.c_float(), C.c_float()
+    rc = fn(C.addressof(key), vv.ctypes.data, C.addressof(fx), C.addressof(fy))
+    if rc == 1:
+        raise ValueError("lumc_history_project_host refused its arguments")
+    return None if rc == 2 else (np.float32(fx.value), np.float32(fy.value))
+
+
 class ShutterStats(C.Structure):
     """LumShutterStats"""
     _fields_ = [("slices", C.c_uint64), ("last_meshes", C.c_uint32), ("last_launches", C.c_uint32), ("last_bytes_uploaded", C.c_uint64), ("seconds", C.c_double)]
@@ -1011,6 +1100,57 @@ class Core:
     def matte_stats(self):
         out = MatteStats()
         self._call("lumc_matte_stats", C.byref(out))
+        return out
+
+    # ---- image history (lumc_set_history, lumc_history_carry, lumc_history_blend) ----
+    def set_history(self, params):
+        self._call("lumc_set_history", C.byref(params))
+
+    def history_carry(self, stream=0):
+        self._call("lumc_history_carry", C.c_void_p(stream))
+
+    def history_blend(self, uniform_samples, d_image=None, stream=0):
+        self._call("lumc_history_blend", C.c_uint32(uniform_samples), C.c_void_p(d_image), C.c_void_p(stream))
+
+    def history_drop(self, why=b"dropped by the caller"):
+        self._history_why = why if isinstance(why, bytes) else str(why).encode()  # (kept by pointer)
+        self._call("lumc_history_drop", C.c_char_p(self._history_why))
+
+    def history_release(self):
+        self._call("lumc_history_release")
+
+    def history_stats(self):
+        out = HistoryStats()
+        self._call("lumc_history_stats", C.byref(out))
+        return out
+
+    def history_keys(self):
+        """(the state's key, the context's camera as a key)"""
+        a, b = HistoryKey(), HistoryKey()
+        self._call("lumc_history_key", C.byref(a), C.byref(b))
+        return a, b
+
+    def download_history(self):
+        """lumc_download_history: (shown [3, P], weight [P], carried [3, P], carried_weight [P])"""
+        P = self.width * self.height
+        shown, weight, carried, cw = np.zeros((3, P), np.float32), np.zeros(P, np.float32), np.zeros((3, P), np.float32), np.zeros(P, np.float32)
+        self._call("lumc_download_history", *[C.c_void_p(a.ctypes.data) for a in (shown, weight, carried, cw)])
+        return shown, weight, carried, cw
+
+    def history_kernels(self, now_key, old_key, params, uniform_samples, image, normal, depth, old_shown, old_weight, old_normal, old_depth):
+        """lumc_history_kernels_host: k_history_reproject and k_history_blend on host planes (as the twins take them). Returns a dict: image, carried, carried_weight,
+        stats, shown, weight, state_normal, state_depth."""
+        P, Q = now_key.width * now_key.height, old_key.width * old_key.height
+        ins = [_f32(normal, (3, P), "normal"), _f32(depth, (P,), "depth"), _f32(old_shown, (3, Q), "old_shown"), _f32(old_weight, (Q,), "old_weight"),
+               _f32(old_normal, (3, Q), "old_normal"), _f32(old_depth, (Q,), "old_depth")]
+        out = {"image": _f32(image, (3, P), "image").copy(), "carried": np.zeros((3, P), np.float32), "carried_weight": np.zeros(P, np.float32), "shown": np.zeros((3, P), np.float32),
+               "weight": np.zeros(P, np.float32), "state_normal": np.zeros((3, P), np.float32), "state_depth": np.zeros(P, np.float32)}
+        stats = (C.c_uint32 * 3)()
+        self._call("lumc_history_kernels_host", C.byref(now_key), C.byref(old_key), C.byref(params), C.c_uint32(uniform_samples),
+                   *[C.c_void_p(a.ctypes.data) for a in ins], C.c_void_p(out["image"].ctypes.data), C.c_void_p(out["carried"].ctypes.data),
+                   C.c_void_p(out["carried_weight"].ctypes.data), stats, C.c_void_p(out["shown"].ctypes.data), C.c_void_p(out["weight"].ctypes.data),
+                   C.c_void_p(out["state_normal"].ctypes.data), C.c_void_p(out["state_depth"].ctypes.data))
+        out["stats"] = tuple(int(x) for x in stats)
         return out
 
     def mesh_shutter_key(self, mesh, which):

@@ -130,6 +130,12 @@ struct LuminaryHost {
   LuminaryFireflySettings firefly = {false, 8u};  // luminary_ext_set_firefly_rejection
   uint32_t core_firefly = 0;         // buckets the main context holds (sync_firefly): 0 while the switch is off or the frame is tiled over several devices
   uint64_t firefly_resolved = 0, firefly_skipped = 0;  // result images resolved / left alone because adaptive sampling drives the accumulation
+  LuminaryHistorySettings history = {false, 32.0f, 0.02f, 0.9f, 0.0f};  // luminary_ext_set_history
+  bool history_carry_due = false;      // the integration restarted by camera moves alone since the main context's state was shown: the next output reprojects it
+  bool history_camera_move = false;    // luminary_host_set_camera is about to invalidate for a move that carries (camera_change_carries)
+  const char* history_cause = nullptr; // what the caller of the next invalidate names as the cause of a drop
+  uint64_t history_carried = 0, history_dropped = 0, history_skipped = 0;
+  std::string history_last_drop;
   bool hdri_origin_pending = true;   // the next scene build re-bakes the sky panorama from the camera's position (SCENE_DIRTY_FLAG_HDRI)
   lum::OutputStore outputs;
   double render_seconds = 0.0;
@@ -202,8 +208,38 @@ void shutter_note_move(LuminaryHost* h, bool emits) {
   if (emits && !h->light_refit) h->shutter.emitter_needs_refit = true;
 }
 
+// ---- image history (include/luminary_amd.h LuminaryHistorySettings) ----
+bool history_held(const LuminaryHost* h) { return h->core && lumc_has_history(h->core); }
+// The main context's state and carried plane go, with the reason logged and counted (`why` is a literal: the core keeps the pointer).
+void history_drop(LuminaryHost* h, const char* why) {
+  h->history_carry_due = false;
+  if (!history_held(h)) return;
+  (void) lumc_history_drop(h->core, why);
+  h->history_dropped++;
+  h->history_last_drop = why;
+  h->log.push_back(std::string("image history dropped: ") + why);
+}
+// A restart of the integration: it carries when its caller said that its sole cause is a camera move that does, and drops otherwise.
+void history_restart(LuminaryHost* h, uint32_t dirty) {
+  const char* cause = h->history_cause;
+  const bool move = h->history_camera_move;
+  h->history_cause = nullptr; h->history_camera_move = false;
+  if (!history_held(h)) return;
+  if (move && h->history.enabled) { h->history_carry_due = true; return; }
+  if (!cause) {
+    if (dirty == 0) cause = "the device partition or a setting of the accumulation changed";
+    else if (dirty == LUMC_DIRTY_ALL) cause = "the scene changed";
+    else if (dirty & (LUMC_DIRTY_MESHES | LUMC_DIRTY_MESH_POSITIONS)) cause = "a mesh changed";
+    else if (dirty & (LUMC_DIRTY_INSTANCES | LUMC_DIRTY_INSTANCE_TRANSFORMS)) cause = "an instance changed";
+    else if (dirty & LUMC_DIRTY_MATERIALS) cause = "a material changed";
+    else cause = "the scene changed";
+  }
+  history_drop(h, cause);
+}
+
 void invalidate(LuminaryHost* h, uint32_t dirty = LUMC_DIRTY_ALL) {
   shutter_drop_keys(h);
+  history_restart(h, dirty);
   if (h->shutter.open) {
     h->shutter.edits |= h->shutter.in_move ? dirty & ~(uint32_t) LUMC_DIRTY_LIGHTS : dirty;
     h->shutter.in_move = false;
@@ -275,6 +311,24 @@ inline void shutter_note_entity(LuminaryHost* h, const char*, const LuminaryCame
   LuminaryCamera c = in;
   c.pos = old.pos; c.rotation = old.rotation;
   if (camera_change_restarts(c, old)) shutter_note_other(h, "a camera field other than pos and rotation");
+}
+
+// Does this change of the camera restart the integration and keep the image history? Only a move of the thin-lens camera does: nothing differs but pos, rotation,
+// thin_lens.fov, thin_lens.aperture_size and object_distance.
+bool camera_change_carries(const LuminaryCamera& in, const LuminaryCamera& old) {
+  if (!camera_change_restarts(in, old) || in.use_physical_camera || old.use_physical_camera) return false;
+  LuminaryCamera c = in;
+  c.pos = old.pos; c.rotation = old.rotation; c.thin_lens.fov = old.thin_lens.fov; c.thin_lens.aperture_size = old.thin_lens.aperture_size; c.object_distance = old.object_distance;
+  return !camera_change_restarts(c, old);
+}
+// An entity is about to restart the integration: what the history makes of it (history_restart).
+template <typename T> void history_note_entity(LuminaryHost* h, const char* name, const T&, const T&) { h->history_cause = name; }
+inline void history_note_entity(LuminaryHost* h, const char*, const LuminaryCamera& in, const LuminaryCamera& old) {
+  if (camera_change_carries(in, old)) h->history_camera_move = true;
+  else h->history_cause = (in.use_physical_camera || old.use_physical_camera) ? "the physical camera is not reprojected" : "a camera field other than pos, rotation, fov, aperture size and object distance changed";
+}
+inline void history_note_entity(LuminaryHost* h, const char* name, const LuminaryRendererSettings& in, const LuminaryRendererSettings& old) {
+  h->history_cause = (in.width != old.width || in.height != old.height || in.supersampling != old.supersampling) ? "the frame size changed" : name;
 }
 
 // ---- skinned and morphed meshes: the lazy host mesh ----
@@ -675,6 +729,7 @@ LuminaryResult luminary_host_start_new_render(LuminaryHost* host) {
   CHECK_NULL(host);
   {
     ApiLock lock(host);
+    history_drop(host, "luminary_host_start_new_render");
     host->accumulated_samples = 0;
     host->guides_valid = false;
     host->render_seconds = 0.0;
@@ -939,6 +994,7 @@ LuminaryResult luminary_host_request_sky_hdri_build(LuminaryHost* host) {
     if (std::memcmp(&host->scene.FIELD, in, sizeof(TYPE)) != 0) {                                       \
       const bool restarts = change_restarts(*in, host->scene.FIELD);                                    \
       if (restarts) shutter_note_entity(host, "the " #NAME, *in, host->scene.FIELD);                     \
+      if (restarts) history_note_entity(host, "the " #NAME " changed", *in, host->scene.FIELD);          \
       host->scene.FIELD = *in;                                                                          \
       if (std::is_same<TYPE, LuminarySky>::value) host->hdri_origin_pending = true; /* sky.c:45: every sky change dirties the panorama */ \
       /* these entities reach the kernels as constants (and tables derived from them): no mesh, instance or material array is touched */ \
@@ -1491,12 +1547,35 @@ int firefly_result(LuminaryHost* h) {
   return 0;
 }
 
+// The image history on the main context's result image (lumc_history_carry, lumc_history_blend), after the denoiser: the first output of an accumulation that
+// camera moves alone restarted reprojects the held frame, every output blends. The guides are the denoiser's, rendered here where it is off.
+int history_result(LuminaryHost* h) {
+  if (h->adaptive_active) { h->history_skipped++; return 0; }  // every pixel has its own sample count: skipped and counted, as the firefly resolve is
+  LumHistoryParams hp;
+  hp.enabled = 1u; hp.max_history = h->history.max_history; hp.depth_tolerance = h->history.depth_tolerance; hp.normal_threshold = h->history.normal_threshold;
+  hp.clamp_sigma = h->history.clamp_sigma;
+  if (lumc_set_history(h->core, &hp)) return 1;
+  if (!h->guides_valid || !lumc_has_guides(h->core)) {
+    if (lumc_render_guides(h->core, h->denoiser.guide_samples, nullptr)) return 1;
+    h->guides_valid = true;
+  }
+  if (h->history_carry_due) {
+    h->history_carry_due = false;
+    if (history_held(h)) {
+      if (lumc_history_carry(h->core, nullptr)) return 1;
+      h->history_carried++;
+    }
+  }
+  return lumc_history_blend(h->core, h->accumulated_samples, nullptr, nullptr);
+}
+
 int post_process(LuminaryHost* h, PreviewState preview) {
   const LuminaryRendererSettings& st = h->scene.settings;
   if (st.shading_mode != LUMINARY_SHADING_MODE_DEFAULT || st.adaptive_sampling_output_mode != LUMINARY_ADAPTIVE_SAMPLING_OUTPUT_MODE_BEAUTY) return 0;
   if (!(st.region_width >= 1.0f && st.region_height >= 1.0f)) return 0;
   if (preview.stage == 0 && firefly_result(h)) return 1;  // result image -> firefly resolve -> denoise -> bloom; never the coarse preview images
   if (h->denoiser.enabled && preview.stage == 0 && denoise_result(h)) return 1;
+  if (h->history.enabled && preview.stage == 0 && history_result(h)) return 1;
   const float blend = h->scene.camera.bloom_blend;
   if (!(blend > 0.0f)) return 0;  // device_post_update, device_post.c:186-202
   const LumDeviceSceneView& v = h->device_scene.view;
@@ -1599,6 +1678,7 @@ LuminaryResult render_samples_locked(LuminaryHost* host, const uint32_t* pixels,
     // the first sample of this frame was rendered on the main device as the preview: its sums go to whoever owns the pixels from now on
     const bool handoff = host->handoff_preview && all && first_sample == 1 && host->accumulated_samples == 1 && host->pixels_all && host->num_pixels == v.width * v.height;
     host->handoff_preview = false;
+    if (!handoff) history_drop(host, "the pixel set or the device partition changed");
     if (handoff && lumc_frame_assemble(host->core, v.width * v.height, 0, nullptr, nullptr)) { std::fprintf(stderr, "[luminary_amd] %s\n", lumc_last_error(host->core)); return LUMINARY_ERROR_CUDA; }
     if (want_n > 1) {
       std::vector<uint32_t> tiles;
@@ -1723,6 +1803,7 @@ LuminaryResult render_shutter_locked(LuminaryHost* h, uint32_t slices, uint32_t 
   if (samples_per_slice == 0) return shutter_refuse(h, "samples_per_slice is at least 1", false);
   if (h->scene.settings.enable_adaptive_sampling) return shutter_refuse(h, "adaptive sampling does not run under a shutter (settings.enable_adaptive_sampling)", false);
   if (!sh.open && !sh.keyed) return shutter_refuse(h, "no open key (luminary_ext_shutter_open)", false);
+  history_drop(h, "a shutter render");
   const auto clock = [] { return std::chrono::steady_clock::now(); };
   const auto since = [&](std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double>(clock() - t0).count(); };
   double seconds_update = 0.0, seconds_render = 0.0;
@@ -1926,6 +2007,7 @@ LuminaryResult render_locked(LuminaryHost* host, uint32_t num_samples, uint32_t 
   auto fail = [&](LumContext* c) { std::fprintf(stderr, "[luminary_amd] %s\n", lumc_last_error(c)); return LUMINARY_ERROR_CUDA; };
   if (!host->adaptive_active || host->partition_n != n) {
     const LumDeviceSceneView& v = host->device_scene.view;
+    history_drop(host, "adaptive sampling drives the accumulation");
     lumc_use_assembled_frame(host->core, 0);
     LumAdaptiveParams ap;
     std::memset(&ap, 0, sizeof(ap));
@@ -2147,6 +2229,68 @@ LuminaryResult luminary_ext_get_firefly_stats(LuminaryHost* host, LuminaryFirefl
   }
   return LUMINARY_SUCCESS;
 }
+// ---- image history (include/luminary_amd.h LuminaryHistorySettings; include/lum_core.h lumc_set_history) ----
+LuminaryResult luminary_ext_set_history(LuminaryHost* host, const LuminaryHistorySettings* settings) {
+  CHECK_NULL(host); CHECK_NULL(settings);
+  ApiLock lock(host);
+  auto refuse = [&](const std::string& why) {
+    host->log.push_back("luminary_ext_set_history: " + why);
+    std::fprintf(stderr, "[luminary_amd] %s\n", host->log.back().c_str());
+    return LUMINARY_ERROR_INVALID_API_ARGUMENT;
+  };
+  if (!(settings->max_history > 0.0f) || !std::isfinite(settings->max_history)) return refuse("max_history must be positive and finite");
+  if (!(settings->depth_tolerance >= 0.0f) || !std::isfinite(settings->depth_tolerance)) return refuse("depth_tolerance must be >= 0 and finite");
+  if (!(settings->normal_threshold >= -1.0f && settings->normal_threshold <= 1.0f)) return refuse("normal_threshold must lie in [-1, 1]");
+  if (!(settings->clamp_sigma >= 0.0f) || !std::isfinite(settings->clamp_sigma)) return refuse("clamp_sigma must be >= 0 and finite");
+  if (host->history.enabled && !settings->enabled) history_drop(host, "history was switched off");
+  host->history = *settings;  // changes how the accumulated frame is shown, like the denoiser's settings: the integration goes on
+  return LUMINARY_SUCCESS;
+}
+LuminaryResult luminary_ext_get_history(LuminaryHost* host, LuminaryHistorySettings* settings) {
+  CHECK_NULL(host); CHECK_NULL(settings);
+  ApiLock lock(host);
+  *settings = host->history;
+  return LUMINARY_SUCCESS;
+}
+LuminaryResult luminary_ext_get_history_image(LuminaryHost* host, float* rgb, float* weight, uint32_t width, uint32_t height) {
+  CHECK_NULL(host);
+  ApiLock lock(host);
+  if (!host->history.enabled || !history_held(host)) {
+    host->log.push_back(std::string("luminary_ext_get_history_image: no shown frame is held") + (host->history_last_drop.empty() ? "" : ": " + host->history_last_drop));
+    return LUMINARY_ERROR_API_EXCEPTION;
+  }
+  LumHistoryKey key;
+  if (lumc_history_key(host->core, &key, nullptr)) return LUMINARY_ERROR_API_EXCEPTION;
+  if (width != key.width || height != key.height) return LUMINARY_ERROR_INVALID_API_ARGUMENT;
+  const size_t n = (size_t) width * height;
+  std::vector<float> planes(3 * n);
+  if (lumc_download_history(host->core, rgb ? planes.data() : nullptr, weight, nullptr, nullptr)) return LUMINARY_ERROR_CUDA;
+  if (rgb)
+    for (size_t p = 0; p < n; p++)
+      for (int c = 0; c < 3; c++) rgb[3 * p + c] = planes[(size_t) c * n + p];
+  return LUMINARY_SUCCESS;
+}
+LuminaryResult luminary_ext_get_history_stats(LuminaryHost* host, LuminaryHistoryStats* out) {
+  CHECK_NULL(host); CHECK_NULL(out);
+  ApiLock lock(host);
+  std::memset(out, 0, sizeof(*out));
+  out->frames_carried = host->history_carried; out->frames_dropped = host->history_dropped; out->frames_skipped = host->history_skipped;
+  std::snprintf(out->last_drop, sizeof(out->last_drop), "%s", host->history_last_drop.c_str());
+  if (host->core) {
+    LumHistoryStats st;
+    if (lumc_history_stats(host->core, &st)) return LUMINARY_ERROR_CUDA;
+    out->last_carried = st.last_carried; out->last_rejected = st.last_rejected; out->last_off = st.last_off;
+    out->valid = (host->history.enabled && st.has_state) ? 1u : 0u;
+    out->bytes = st.bytes;
+    out->seconds = 1e-3 * (st.carry_ms + st.blend_ms);
+  }
+  return LUMINARY_SUCCESS;
+}
+LuminaryResult luminary_ext_camera_change_carries_history(const LuminaryCamera* input, const LuminaryCamera* old, bool* carries) {
+  CHECK_NULL(input); CHECK_NULL(old); CHECK_NULL(carries);
+  *carries = camera_change_carries(*input, *old);
+  return LUMINARY_SUCCESS;
+}
 // ---- ID mattes (include/luminary_amd.h luminary_ext_render_mattes; include/lum_core.h lumc_render_first_hits) ----
 namespace {
 LuminaryResult matte_refuse(LuminaryHost* host, const char* fn, const std::string& why, LuminaryResult code) {
@@ -2278,7 +2422,7 @@ LuminaryResult luminary_ext_set_camera_lens(LuminaryHost* host, const LuminaryCa
   ApiLock lock(host);
   const bool restarts = host->scene.camera.use_physical_camera && lens_change_restarts(*lens, host->scene.lens);
   host->scene.lens = *lens;
-  if (restarts) { shutter_note_other(host, "the lens"); invalidate(host, LUMC_DIRTY_CONSTANTS); }
+  if (restarts) { shutter_note_other(host, "the lens"); host->history_cause = "the lens changed"; invalidate(host, LUMC_DIRTY_CONSTANTS); }
   return LUMINARY_SUCCESS;
 }
 LuminaryResult luminary_ext_get_camera_lens(LuminaryHost* host, LuminaryCameraLens* lens) {

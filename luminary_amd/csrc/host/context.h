@@ -20,6 +20,7 @@
 #include "bvh_refit.h"
 #include "device_buffer.h"
 #include "firefly.h"
+#include "history.h"
 #include "instance_update.h"
 #include "light_refit.h"
 #include "matte.h"
@@ -175,6 +176,7 @@ struct LumContext {
   // the scene, the lens or the camera changed: both were rendered from what was. `why` is what a refused matte download names.
   void drop_first_hit_products(const char* why) { guides_valid = false; if (mattes.valid) { mattes.valid = false; mattes.stale = why; } }
   DeviceBuffer<float4> d_denoise_rec[3];  // one 16-byte record per pixel each
+  History history;  // the shown frame carried across camera moves (lumc_set_history; history.hip): nothing is allocated until it is switched on and blends
   int denoise_lds = 1;              // a-trous steps 1 and 2 stage their tile in LDS (lumc_set_denoise_form; LUM_DENOISE_LDS=0|1)
   // ray ordering (N1): keys + permutation, double-buffered for hipcub's radix sort; sized for the visibility items (4 per path)
   struct RaySort {  // ray_sort.hip

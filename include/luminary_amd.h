@@ -695,6 +695,40 @@ LUMINARY_API LuminaryResult luminary_ext_get_history_image(LuminaryHost* host, f
 LUMINARY_API LuminaryResult luminary_ext_get_history_stats(LuminaryHost* host, LuminaryHistoryStats* out);
 /* Whether replacing camera `old` by `input` restarts the integration AND keeps the history (see above); false for a change that does not restart at all. */
 LUMINARY_API LuminaryResult luminary_ext_camera_change_carries_history(const LuminaryCamera* input, const LuminaryCamera* old, bool* carries);
+/* Image history, motion (include/lum_core.h lumc_set_history_motion; csrc/host/history.h "Motion"): an extension of the history, off by default.
+ * While history and motion are on, a restart whose only cause is luminary_ext_set_instance_transforms keeps the shown image too - alone or together with camera moves
+ * that carry -: every pixel is reprojected through the old and new transform of the instance its first hit saw (its owner), a pixel takes nothing from a tap another
+ * moved instance or the background owned, and the weight carried on a moved instance is capped by motion_max_history, since its lighting has changed even where its
+ * surface has not. A move of an instance with an emissive material drops the history ("a moved instance emits"), as every other cause does with the string it had.
+ * Moved lights and shadows are not detected, only damped by the cap and the clamp; deforming meshes still drop. The guide render of an accumulation then makes the
+ * owner plane as well (4 + 4 bytes per pixel, 32 + 128 bytes per instance). With the motion off nothing of this is allocated or launched and every output keeps its
+ * bytes. Setting it does not restart the integration; switching it off drops the shown frame only while a carry granted for an instance move is still due
+ * ("the history's motion was switched off"). Under the physical camera an instance move drops as it always did.
+ *   luminary_ext_set_history_motion               LUMINARY_ERROR_INVALID_API_ARGUMENT with a line in the log: motion_max_history not > 0 or not finite.
+ *   luminary_ext_instance_change_carries_history  whether luminary_ext_set_instance_transforms with these arguments would keep the history as the host stands
+ *                                                 (false with history or motion off, for no instances, or where an instance that changes emits).
+ *   luminary_ext_get_history_owner                the owner planes [height][width] of the shown frame and of the current guides (LUMINARY_MATTE_ID_* for first hits that
+ *                                                 are no triangle); each may be NULL. LUMINARY_ERROR_API_EXCEPTION where the plane asked for is not held.
+ *   luminary_ext_get_history_transforms           8 words per instance as the device holds them: the transforms the shown frame was shown with and the current ones;
+ *                                                 each may be NULL; *shown_instances: how many the shown frame holds. */
+typedef struct LuminaryHistoryMotionSettings {
+  bool enabled;              /* false */
+  float motion_max_history;  /* cap of the carried weight of pixels on a moved instance, in samples: 8 */
+} LuminaryHistoryMotionSettings;
+typedef struct LuminaryHistoryMotionStats {
+  uint64_t frames_carried;   /* reprojections that went through the instance records */
+  uint64_t bytes;            /* owner planes, transform snapshot, records on the main device */
+  uint32_t instances_moved, instances_same, instances_void;  /* of the last such reprojection */
+  uint32_t last_moved_pixels, last_moved_carried;            /* pixels whose owner moved; those of them that carried */
+  uint32_t valid;            /* 1: the shown frame holds its owner plane and transforms: an instance move would carry */
+  double owner_seconds, motion_seconds, reproject_seconds;   /* device time of the three launches while the core profiles, else 0 */
+} LuminaryHistoryMotionStats;
+LUMINARY_API LuminaryResult luminary_ext_set_history_motion(LuminaryHost* host, const LuminaryHistoryMotionSettings* settings);
+LUMINARY_API LuminaryResult luminary_ext_get_history_motion(LuminaryHost* host, LuminaryHistoryMotionSettings* settings);
+LUMINARY_API LuminaryResult luminary_ext_get_history_motion_stats(LuminaryHost* host, LuminaryHistoryMotionStats* out);
+LUMINARY_API LuminaryResult luminary_ext_instance_change_carries_history(LuminaryHost* host, const LuminaryInstance* instances, uint32_t count, bool* carries);
+LUMINARY_API LuminaryResult luminary_ext_get_history_owner(LuminaryHost* host, uint32_t* shown_owner, uint32_t* current_owner, uint32_t width, uint32_t height);
+LUMINARY_API LuminaryResult luminary_ext_get_history_transforms(LuminaryHost* host, float* shown_transforms, float* current_transforms, uint32_t instances, uint32_t* shown_instances);
 /* out[0] closest-hit rays, [1] shadow rays, [2] light-BVH queries, [3] shaded vertices, [4] BVH nodes visited, [5] triangles tested. */
 LUMINARY_API LuminaryResult luminary_ext_get_ray_counters(LuminaryHost* host, uint64_t out[8]);
 /* The lumc context of this host (include/lum_core.h), for callers that drive passes themselves. */

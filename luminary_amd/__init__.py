@@ -230,6 +230,18 @@ class HistoryStats(C.Structure):
                 ("last_off", C.c_uint32), ("valid", C.c_uint32), ("bytes", C.c_uint64), ("seconds", C.c_double), ("last_drop", C.c_char * 96)]
 
 
+class HistoryMotionSettings(C.Structure):
+    """include/luminary_amd.h LuminaryHistoryMotionSettings (defaults: off, 8)."""
+    _fields_ = [("enabled", C.c_bool), ("motion_max_history", C.c_float)]
+
+
+class HistoryMotionStats(C.Structure):
+    """LuminaryHistoryMotionStats"""
+    _fields_ = [("frames_carried", C.c_uint64), ("bytes", C.c_uint64), ("instances_moved", C.c_uint32), ("instances_same", C.c_uint32), ("instances_void", C.c_uint32),
+                ("last_moved_pixels", C.c_uint32), ("last_moved_carried", C.c_uint32), ("valid", C.c_uint32), ("owner_seconds", C.c_double), ("motion_seconds", C.c_double),
+                ("reproject_seconds", C.c_double)]
+
+
 MATTE_LAYER_INSTANCE, MATTE_LAYER_MATERIAL = 1, 2  # LUMINARY_MATTE_LAYER_*
 MATTE_ID_EMPTY, MATTE_ID_MISS, MATTE_ID_OCEAN, MATTE_ID_PARTICLE = 0xFFFFFFFF, 0xFFFFFFFE, 0xFFFFFFFD, 0xFFFFFFFC  # LUMINARY_MATTE_ID_*
 
@@ -837,6 +849,51 @@ class Host:
         s = HistoryStats()
         _call("luminary_ext_get_history_stats", self._h, C.byref(s))
         return {name: (getattr(s, name).decode() if name == "last_drop" else getattr(s, name)) for name, _ in s._fields_}
+
+    def get_history_motion(self):
+        """luminary_ext_get_history_motion"""
+        f = HistoryMotionSettings()
+        _call("luminary_ext_get_history_motion", self._h, C.byref(f))
+        return f
+
+    def set_history_motion(self, settings=None, **fields):
+        """luminary_ext_set_history_motion: the given settings, or the current ones with `fields` changed (set_history_motion(enabled=True)). Restarts and drops nothing."""
+        f = settings if settings is not None else self.get_history_motion()
+        for k, v in fields.items():
+            setattr(f, k, v)
+        _call("luminary_ext_set_history_motion", self._h, C.byref(f))
+
+    def history_motion_stats(self):
+        """luminary_ext_get_history_motion_stats, as a dict."""
+        s = HistoryMotionStats()
+        _call("luminary_ext_get_history_motion_stats", self._h, C.byref(s))
+        return {name: getattr(s, name) for name, _ in s._fields_}
+
+    def instance_change_carries_history(self, instances):
+        """luminary_ext_instance_change_carries_history: would set_instance_transforms(instances) keep the image history as the host stands?"""
+        instances = list(instances)
+        arr = (Instance * max(len(instances), 1))()
+        for k, inst in enumerate(instances):
+            arr[k] = inst
+        out = C.c_bool()
+        _call("luminary_ext_instance_change_carries_history", self._h, arr, C.c_uint32(len(instances)), C.byref(out))
+        return out.value
+
+    def history_owner(self, width, height, shown=True, current=True):
+        """luminary_ext_get_history_owner: (the shown frame's owner plane [H, W] uint32 or None, the current guides' or None)."""
+        import numpy as np
+        a, b = (np.zeros((height, width), np.uint32) if shown else None), (np.zeros((height, width), np.uint32) if current else None)
+        _call("luminary_ext_get_history_owner", self._h, C.c_void_p(a.ctypes.data if shown else None), C.c_void_p(b.ctypes.data if current else None), C.c_uint32(width), C.c_uint32(height))
+        return a, b
+
+    def history_transforms(self, instances):
+        """luminary_ext_get_history_transforms: (the transforms the shown frame was shown with [instances, 8] float32, the current ones, how many the shown frame
+        holds), 8 words each as the device holds them. Raises (invalid argument) where `instances` is not the count of both."""
+        import numpy as np
+        a, b = np.zeros((instances, 8), np.float32), np.zeros((instances, 8), np.float32)
+        held = C.c_uint32()
+        _call("luminary_ext_get_history_transforms", self._h, C.c_void_p(a.ctypes.data), C.c_void_p(b.ctypes.data), C.c_uint32(instances), C.byref(held))
+        return a, b, held.value
 
     def render_mattes(self, samples=4, layers=MATTE_LAYER_INSTANCE | MATTE_LAYER_MATERIAL):
         """luminary_ext_render_mattes: ID mattes of the whole frame from `samples` first-hit passes on the main device; the accumulation is not touched."""

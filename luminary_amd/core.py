@@ -16,6 +16,8 @@ CNT_TRACE, CNT_SHADOW, CNT_LIGHT_BVH, CNT_VERTICES, CNT_NODES, CNT_TRIS, CNT_NOD
 CNT_COUNT = 16  # LUMC_CNT_COUNT
 KERNELS = ("generate", "trace", "shade", "shadow", "accumulate", "light_query", "resolve", "output", "sky", "sort", "volume", "matte")
 FIRST_HIT_GUIDES, FIRST_HIT_MATTES = 1, 2  # LUMC_FIRST_HIT_*
+FIRST_HIT_OWNER = 4  # the image history's owner plane, with FIRST_HIT_GUIDES (lumc_set_history_motion)
+HISTORY_MOTION_SAME, HISTORY_MOTION_MOVED, HISTORY_MOTION_VOID = 0, 1, 2  # LUMC_HISTORY_MOTION_*
 MATTE_INSTANCE, MATTE_MATERIAL = 1, 2  # LUMC_MATTE_*: layers
 MATTE_ID_EMPTY, MATTE_ID_MISS, MATTE_ID_OCEAN, MATTE_ID_PARTICLE = 0xFFFFFFFF, 0xFFFFFFFE, 0xFFFFFFFD, 0xFFFFFFFC
 MATTE_SLOTS, MATTE_MAX_MASK_IDS = 8, 16
@@ -304,6 +306,65 @@ def history_project_host(key, v):
     if rc == 1:
         raise ValueError("lumc_history_project_host refused its arguments")
     return None if rc == 2 else (np.float32(fx.value), np.float32(fy.value))
+
+
+class HistoryMotionParams(C.Structure):
+    """LumHistoryMotionParams"""
+    _fields_ = [("enabled", C.c_uint32), ("motion_max_history", C.c_float)]
+
+
+class HistoryMotionStats(C.Structure):
+    """LumHistoryMotionStats"""
+    _fields_ = [("motion_carries", C.c_uint64), ("bytes", C.c_uint64), ("instances_moved", C.c_uint32), ("instances_same", C.c_uint32), ("instances_void", C.c_uint32),
+                ("last_moved_pixels", C.c_uint32), ("last_moved_carried", C.c_uint32), ("has_snapshot", C.c_uint32), ("has_owner", C.c_uint32), ("snapshot_instances", C.c_uint32),
+                ("owner_ms", C.c_double), ("motion_ms", C.c_double), ("reproject_ms", C.c_double), ("owner_launches", C.c_uint32), ("motion_launches", C.c_uint32),
+                ("reproject_launches", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+# LumHistoryMotionRecord (history.h HistoryMotion), 128 bytes per instance
+HISTORY_MOTION_RECORD = np.dtype([("cls", np.uint32), ("t_new", np.float32, 3), ("t_old", np.float32, 3), ("L", np.float32, 9), ("NL", np.float32, 9), ("pad", np.uint32, 7)])
+
+
+def _u32(a, shape, what):
+    a = np.ascontiguousarray(a, dtype=np.uint32)
+    if a.size != int(np.prod(shape)):
+        raise ValueError("%s: %d words expected" % (what, int(np.prod(shape))))
+    return a.reshape(shape)
+
+
+def history_motion_records_host(old8, new8):
+    """lumc_history_motion_records_host, no device needed: the twin of k_history_motion. old8, new8 [count, 8] float32 (the 8 words of each instance's transform as
+    the scene view holds them). Returns (records [count] of HISTORY_MOTION_RECORD, (moved, same, void))."""
+    fn = _lib().lumc_history_motion_records_host
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+    o, n = np.ascontiguousarray(old8, np.float32).reshape(-1, 8), np.ascontiguousarray(new8, np.float32).reshape(-1, 8)
+    if o.shape != n.shape:
+        raise ValueError("old8 and new8 differ in shape")
+    rec = np.zeros(o.shape[0], HISTORY_MOTION_RECORD)
+    stats = (C.c_uint32 * 3)()
+    if fn(o.ctypes.data, n.ctypes.data, o.shape[0], rec.ctypes.data, C.addressof(stats)) != 0:
+        raise ValueError("lumc_history_motion_records_host refused its arguments")
+    return rec, tuple(int(x) for x in stats)
+
+
+def history_reproject_motion_host(now_key, old_key, params, motion_max_history, normal, depth, old_shown, old_weight, old_normal, old_depth, owner, old_owner, records):
+    """lumc_history_reproject_motion_host, no device needed: the twin of k_history_reproject_motion. history_reproject_host's arguments, the cap of moved owners,
+    owner [P] and old_owner [Q] (uint32), records [count] of HISTORY_MOTION_RECORD. Returns (carried [3, P], carried_weight [P], (carried, rejected, off, owner
+    moved, owner moved and carried))."""
+    fn = _lib().lumc_history_reproject_motion_host
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p] * 3 + [C.c_float] + [C.c_void_p] * 9 + [C.c_uint32] + [C.c_void_p] * 3
+    P, Q = now_key.width * now_key.height, old_key.width * old_key.height
+    ins = [_f32(normal, (3, P), "normal"), _f32(depth, (P,), "depth"), _f32(old_shown, (3, Q), "old_shown"), _f32(old_weight, (Q,), "old_weight"),
+           _f32(old_normal, (3, Q), "old_normal"), _f32(old_depth, (Q,), "old_depth"), _u32(owner, (P,), "owner"), _u32(old_owner, (Q,), "old_owner")]
+    rec = np.ascontiguousarray(records, HISTORY_MOTION_RECORD).reshape(-1)
+    carried, weight = np.zeros((3, P), np.float32), np.zeros(P, np.float32)
+    stats = (C.c_uint32 * 5)()
+    if fn(C.addressof(now_key), C.addressof(old_key), C.addressof(params), float(motion_max_history), *[a.ctypes.data for a in ins], rec.ctypes.data if rec.size else None, rec.size,
+          carried.ctypes.data, weight.ctypes.data, C.addressof(stats)) != 0:
+        raise ValueError("lumc_history_reproject_motion_host refused its arguments")
+    return carried, weight, tuple(int(x) for x in stats)
 
 
 class ShutterStats(C.Structure):
@@ -1151,6 +1212,58 @@ class Core:
                    C.c_void_p(out["carried_weight"].ctypes.data), stats, C.c_void_p(out["shown"].ctypes.data), C.c_void_p(out["weight"].ctypes.data),
                    C.c_void_p(out["state_normal"].ctypes.data), C.c_void_p(out["state_depth"].ctypes.data))
         out["stats"] = tuple(int(x) for x in stats)
+        return out
+
+    # ---- image history, motion (lumc_set_history_motion) ----
+    def set_history_motion(self, enabled=True, motion_max_history=8.0):
+        p = HistoryMotionParams(1 if enabled else 0, motion_max_history)
+        self._call("lumc_set_history_motion", C.byref(p))
+
+    def has_history_snapshot(self):
+        fn = self._lib.lumc_has_history_snapshot
+        fn.restype = C.c_int
+        return bool(fn(self._ctx))
+
+    def history_motion_stats(self):
+        out = HistoryMotionStats()
+        self._call("lumc_history_motion_stats", C.byref(out))
+        return out
+
+    def download_history_owner(self, state=True, current=True):
+        """lumc_download_history_owner: (the state's owner plane or None, the current one or None), uint32 [P]"""
+        P = self.width * self.height
+        a, b = (np.zeros(P, np.uint32) if state else None), (np.zeros(P, np.uint32) if current else None)
+        self._call("lumc_download_history_owner", C.c_void_p(a.ctypes.data if state else None), C.c_void_p(b.ctypes.data if current else None))
+        return a, b
+
+    def download_history_transforms(self, instances):
+        """lumc_download_history_transforms: (the state's snapshot [count, 8] or None where none is held, the scene's current transforms [instances, 8])"""
+        count = C.c_uint32()
+        self._call("lumc_download_history_transforms", C.c_void_p(None), C.c_void_p(None), C.byref(count))
+        snap, cur = np.zeros((count.value, 8), np.float32), np.zeros((int(instances), 8), np.float32)
+        self._call("lumc_download_history_transforms", C.c_void_p(snap.ctypes.data if count.value else None), C.c_void_p(cur.ctypes.data if instances else None), C.byref(count))
+        return (snap if count.value else None), cur
+
+    def history_motion_kernels(self, now_key, old_key, params, motion_max_history, normal, depth, old_shown, old_weight, old_normal, old_depth, owner, old_owner, old8, new8, hit_ids=None):
+        """lumc_history_motion_kernels_host: k_history_owner (where hit_ids [paths, 4] uint32 is given; `owner` is ignored then), k_history_motion and
+        k_history_reproject_motion on host planes. Returns a dict: owner, records, motion_stats, carried, carried_weight, stats."""
+        P, Q = now_key.width * now_key.height, old_key.width * old_key.height
+        ins = [_f32(normal, (3, P), "normal"), _f32(depth, (P,), "depth"), _f32(old_shown, (3, Q), "old_shown"), _f32(old_weight, (Q,), "old_weight"),
+               _f32(old_normal, (3, Q), "old_normal"), _f32(old_depth, (Q,), "old_depth")]
+        hits = None if hit_ids is None else np.ascontiguousarray(hit_ids, np.uint32).reshape(-1, 4)
+        own = None if owner is None else _u32(owner, (P,), "owner")
+        oown = _u32(old_owner, (Q,), "old_owner")
+        o8, n8 = np.ascontiguousarray(old8, np.float32).reshape(-1, 8), np.ascontiguousarray(new8, np.float32).reshape(-1, 8)
+        if o8.shape != n8.shape:
+            raise ValueError("old8 and new8 differ in shape")
+        count = o8.shape[0]
+        out = {"owner": np.zeros(P, np.uint32), "records": np.zeros(count, HISTORY_MOTION_RECORD), "carried": np.zeros((3, P), np.float32), "carried_weight": np.zeros(P, np.float32)}
+        ms, st = (C.c_uint32 * 3)(), (C.c_uint32 * 5)()
+        ptr = lambda a: C.c_void_p(None if a is None or a.size == 0 else a.ctypes.data)
+        self._call("lumc_history_motion_kernels_host", C.byref(now_key), C.byref(old_key), C.byref(params), C.c_float(motion_max_history), *[ptr(a) for a in ins],
+                   ptr(hits), C.c_uint32(0 if hits is None else hits.shape[0]), ptr(own), ptr(oown), ptr(o8), ptr(n8), C.c_uint32(count), ptr(out["owner"]), ptr(out["records"]), ms,
+                   ptr(out["carried"]), ptr(out["carried_weight"]), st)
+        out["motion_stats"], out["stats"] = tuple(int(x) for x in ms), tuple(int(x) for x in st)
         return out
 
     def mesh_shutter_key(self, mesh, which):

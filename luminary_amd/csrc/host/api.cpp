@@ -133,6 +133,9 @@ struct LuminaryHost {
   LuminaryHistorySettings history = {false, 32.0f, 0.02f, 0.9f, 0.0f};  // luminary_ext_set_history
   bool history_carry_due = false;      // the integration restarted by camera moves alone since the main context's state was shown: the next output reprojects it
   bool history_camera_move = false;    // luminary_host_set_camera is about to invalidate for a move that carries (camera_change_carries)
+  LuminaryHistoryMotionSettings history_motion = {false, 8.0f};  // luminary_ext_set_history_motion
+  bool history_carry_instances = false;  // the carry that is due was granted, at least once, for a move of instances: it needs the motion form
+  bool history_instance_move = false;  // luminary_ext_set_instance_transforms is about to invalidate for a move that carries (no moved instance emits, motion is on)
   const char* history_cause = nullptr; // what the caller of the next invalidate names as the cause of a drop
   uint64_t history_carried = 0, history_dropped = 0, history_skipped = 0;
   std::string history_last_drop;
@@ -212,20 +215,37 @@ void shutter_note_move(LuminaryHost* h, bool emits) {
 bool history_held(const LuminaryHost* h) { return h->core && lumc_has_history(h->core); }
 // The main context's state and carried plane go, with the reason logged and counted (`why` is a literal: the core keeps the pointer).
 void history_drop(LuminaryHost* h, const char* why) {
-  h->history_carry_due = false;
+  h->history_carry_due = false; h->history_carry_instances = false;
   if (!history_held(h)) return;
   (void) lumc_history_drop(h->core, why);
   h->history_dropped++;
   h->history_last_drop = why;
   h->log.push_back(std::string("image history dropped: ") + why);
 }
-// A restart of the integration: it carries when its caller said that its sole cause is a camera move that does, and drops otherwise.
+// The guides of the current accumulation, as the denoiser makes them; while the history's motion is on, the owner plane from the same first hits too.
+bool history_motion_on(const LuminaryHost* h) { return h->history.enabled && h->history_motion.enabled; }
+int render_guides(LuminaryHost* h) {
+  LumHistoryMotionParams mp;
+  mp.enabled = history_motion_on(h) ? 1u : 0u; mp.motion_max_history = h->history_motion.motion_max_history;
+  if (lumc_set_history_motion(h->core, &mp)) return 1;
+  if (!mp.enabled) return lumc_render_guides(h->core, h->denoiser.guide_samples, nullptr);
+  return lumc_render_first_hits(h->core, h->denoiser.guide_samples, LUMC_FIRST_HIT_GUIDES | LUMC_FIRST_HIT_OWNER, 0u, nullptr);
+}
+// A restart of the integration: it carries when its caller said that its sole cause is a camera move that does, or - with the motion on - a move of instances
+// that does (nothing beside the instance transforms is dirty but the lights' part every move marks, and the shown frame holds the transforms it was shown with),
+// and drops otherwise.
 void history_restart(LuminaryHost* h, uint32_t dirty) {
   const char* cause = h->history_cause;
-  const bool move = h->history_camera_move;
-  h->history_cause = nullptr; h->history_camera_move = false;
+  const bool move = h->history_camera_move, instances = h->history_instance_move;
+  h->history_cause = nullptr; h->history_camera_move = false; h->history_instance_move = false;
   if (!history_held(h)) return;
   if (move && h->history.enabled) { h->history_carry_due = true; return; }
+  // (the physical camera is not reprojected: under it an instance move drops as it always did)
+  if (instances && history_motion_on(h) && !h->scene.camera.use_physical_camera &&
+      dirty == (LUMC_DIRTY_INSTANCE_TRANSFORMS | (dirty & (LUMC_DIRTY_LIGHTS | LUMC_DIRTY_LIGHT_POSITIONS))) && lumc_has_history_snapshot(h->core)) {
+    h->history_carry_due = true; h->history_carry_instances = true;
+    return;
+  }
   if (!cause) {
     if (dirty == 0) cause = "the device partition or a setting of the accumulation changed";
     else if (dirty == LUMC_DIRTY_ALL) cause = "the scene changed";
@@ -1322,6 +1342,33 @@ LuminaryResult luminary_ext_get_mesh_refit_stats(LuminaryHost* host, LuminaryMes
   std::memcpy(out, &s, sizeof(s));
   return LUMINARY_SUCCESS;
 }
+// Does this set of new transforms keep the image history (with the motion on)? It does unless an instance whose transform changes has an emissive material:
+// the reprojection follows surfaces, not the light they cast. The arguments are valid (luminary_ext_set_instance_transforms checked them).
+bool instance_change_carries(const LuminaryHost* host, const LuminaryInstance* instances, uint32_t count) {
+  for (uint32_t k = 0; k < count; k++) {
+    const lum::HostInstance& i = host->scene.instances[instances[k].id];
+    const LuminaryInstance& in = instances[k];
+    const bool changed = std::memcmp(&i.translation, &in.position, sizeof(in.position)) != 0 || std::memcmp(&i.rotation, &in.rotation, sizeof(in.rotation)) != 0 ||
+                         std::memcmp(&i.scale, &in.scale, sizeof(in.scale)) != 0;
+    if (changed && mesh_emits(host, i.mesh_id)) return false;
+  }
+  return true;
+}
+LuminaryResult luminary_ext_instance_change_carries_history(LuminaryHost* host, const LuminaryInstance* instances, uint32_t count, bool* carries) {
+  CHECK_NULL(host); CHECK_NULL(carries);
+  ApiLock lock(host);
+  *carries = false;
+  if (!instances && count) return LUMINARY_ERROR_INVALID_API_ARGUMENT;
+  const lum::HostScene& sc = host->scene;
+  for (uint32_t k = 0; k < count; k++) {
+    const LuminaryInstance& in = instances[k];
+    if (in.id >= sc.instances.size()) return LUMINARY_ERROR_INVALID_API_ARGUMENT;
+    const lum::HostInstance& i = sc.instances[in.id];
+    if (!i.active || i.mesh_id >= sc.meshes.size() || in.mesh_id != i.mesh_id) return LUMINARY_ERROR_INVALID_API_ARGUMENT;
+  }
+  *carries = count > 0 && history_motion_on(host) && !host->scene.camera.use_physical_camera && instance_change_carries(host, instances, count);
+  return LUMINARY_SUCCESS;
+}
 LuminaryResult luminary_ext_set_instance_transforms(LuminaryHost* host, const LuminaryInstance* instances, uint32_t count) {
   CHECK_NULL(host);
   ApiLock lock(host);
@@ -1337,12 +1384,17 @@ LuminaryResult luminary_ext_set_instance_transforms(LuminaryHost* host, const Lu
   }
   if (count == 0) return LUMINARY_SUCCESS;
   bool emitter = false;
+  const bool carries = instance_change_carries(host, instances, count);
   for (uint32_t k = 0; k < count; k++) {
     lum::HostInstance& i = host->scene.instances[instances[k].id];
     i.translation = instances[k].position; i.rotation = instances[k].rotation; i.scale = instances[k].scale;
     emitter = emitter || (host->shutter.open && mesh_emits(host, i.mesh_id));
   }
   shutter_note_move(host, emitter);
+  if (history_motion_on(host) && !host->scene.camera.use_physical_camera) {
+    if (carries) host->history_instance_move = true;
+    else host->history_cause = "a moved instance emits";
+  }
   invalidate(host, LUMC_DIRTY_INSTANCE_TRANSFORMS | moved_emitter_bit(host));  // the transforms and the top-level tree; the light tree follows moved emitters
   return LUMINARY_SUCCESS;
 }
@@ -1529,7 +1581,7 @@ std::vector<PreviewState> preview_schedule(LuminaryHost* h) {
 // drops them (invalidate and the other places that zero accumulated_samples).
 int denoise_result(LuminaryHost* h) {
   if (!h->guides_valid || !lumc_has_guides(h->core)) {
-    if (lumc_render_guides(h->core, h->denoiser.guide_samples, nullptr)) return 1;
+    if (render_guides(h)) return 1;
     h->guides_valid = true;
   }
   LumDenoiseParams dp;
@@ -1555,12 +1607,16 @@ int history_result(LuminaryHost* h) {
   hp.enabled = 1u; hp.max_history = h->history.max_history; hp.depth_tolerance = h->history.depth_tolerance; hp.normal_threshold = h->history.normal_threshold;
   hp.clamp_sigma = h->history.clamp_sigma;
   if (lumc_set_history(h->core, &hp)) return 1;
+  LumHistoryMotionParams mp;
+  mp.enabled = history_motion_on(h) ? 1u : 0u; mp.motion_max_history = h->history_motion.motion_max_history;
+  if (lumc_set_history_motion(h->core, &mp)) return 1;
+  if (history_motion_on(h) && !lumc_has_history_owner(h->core)) h->guides_valid = false;  // (the guides were made before the motion was switched on: again, with their owner plane)
   if (!h->guides_valid || !lumc_has_guides(h->core)) {
-    if (lumc_render_guides(h->core, h->denoiser.guide_samples, nullptr)) return 1;
+    if (render_guides(h)) return 1;
     h->guides_valid = true;
   }
   if (h->history_carry_due) {
-    h->history_carry_due = false;
+    h->history_carry_due = false; h->history_carry_instances = false;
     if (history_held(h)) {
       if (lumc_history_carry(h->core, nullptr)) return 1;
       h->history_carried++;
@@ -2282,7 +2338,67 @@ LuminaryResult luminary_ext_get_history_stats(LuminaryHost* host, LuminaryHistor
     out->last_carried = st.last_carried; out->last_rejected = st.last_rejected; out->last_off = st.last_off;
     out->valid = (host->history.enabled && st.has_state) ? 1u : 0u;
     out->bytes = st.bytes;
-    out->seconds = 1e-3 * (st.carry_ms + st.blend_ms);
+    out->seconds = 1e-3 * (st.carry_ms + st.blend_ms);  // (the motion form's launches: luminary_ext_get_history_motion_stats)
+  }
+  return LUMINARY_SUCCESS;
+}
+LuminaryResult luminary_ext_set_history_motion(LuminaryHost* host, const LuminaryHistoryMotionSettings* settings) {
+  CHECK_NULL(host); CHECK_NULL(settings);
+  ApiLock lock(host);
+  if (!(settings->motion_max_history > 0.0f) || !std::isfinite(settings->motion_max_history)) {
+    host->log.push_back("luminary_ext_set_history_motion: motion_max_history must be positive and finite");
+    std::fprintf(stderr, "[luminary_amd] %s\n", host->log.back().c_str());
+    return LUMINARY_ERROR_INVALID_API_ARGUMENT;
+  }
+  // A carry granted for a move of instances needs the motion form: without it the camera form would leave the mover's old image where it was.
+  if (host->history_motion.enabled && !settings->enabled && host->history_carry_due && host->history_carry_instances) history_drop(host, "the history's motion was switched off");
+  host->history_motion = *settings;  // (how the next restart is taken and the next frame shown: the integration goes on, nothing is dropped)
+  return LUMINARY_SUCCESS;
+}
+LuminaryResult luminary_ext_get_history_motion(LuminaryHost* host, LuminaryHistoryMotionSettings* settings) {
+  CHECK_NULL(host); CHECK_NULL(settings);
+  ApiLock lock(host);
+  *settings = host->history_motion;
+  return LUMINARY_SUCCESS;
+}
+LuminaryResult luminary_ext_get_history_motion_stats(LuminaryHost* host, LuminaryHistoryMotionStats* out) {
+  CHECK_NULL(host); CHECK_NULL(out);
+  ApiLock lock(host);
+  std::memset(out, 0, sizeof(*out));
+  if (!host->core) return LUMINARY_SUCCESS;
+  LumHistoryMotionStats st;
+  if (lumc_history_motion_stats(host->core, &st)) return LUMINARY_ERROR_CUDA;
+  out->frames_carried = st.motion_carries; out->bytes = st.bytes;
+  out->instances_moved = st.instances_moved; out->instances_same = st.instances_same; out->instances_void = st.instances_void;
+  out->last_moved_pixels = st.last_moved_pixels; out->last_moved_carried = st.last_moved_carried;
+  out->valid = (history_motion_on(host) && st.has_snapshot) ? 1u : 0u;
+  out->owner_seconds = 1e-3 * st.owner_ms; out->motion_seconds = 1e-3 * st.motion_ms; out->reproject_seconds = 1e-3 * st.reproject_ms;
+  return LUMINARY_SUCCESS;
+}
+LuminaryResult luminary_ext_get_history_owner(LuminaryHost* host, uint32_t* shown_owner, uint32_t* current_owner, uint32_t width, uint32_t height) {
+  CHECK_NULL(host);
+  ApiLock lock(host);
+  if (!history_motion_on(host) || !host->core) return LUMINARY_ERROR_API_EXCEPTION;
+  LumHistoryKey key;
+  if (lumc_history_key(host->core, nullptr, &key)) return LUMINARY_ERROR_API_EXCEPTION;
+  if (width != key.width || height != key.height) return LUMINARY_ERROR_INVALID_API_ARGUMENT;
+  if (lumc_download_history_owner(host->core, shown_owner, current_owner)) {
+    host->log.push_back(std::string("luminary_ext_get_history_owner: ") + lumc_last_error(host->core));
+    return LUMINARY_ERROR_API_EXCEPTION;
+  }
+  return LUMINARY_SUCCESS;
+}
+LuminaryResult luminary_ext_get_history_transforms(LuminaryHost* host, float* shown_transforms, float* current_transforms, uint32_t instances, uint32_t* shown_instances) {
+  CHECK_NULL(host);
+  ApiLock lock(host);
+  if (!history_motion_on(host) || !host->core) return LUMINARY_ERROR_API_EXCEPTION;
+  uint32_t held = 0;
+  if (lumc_download_history_transforms(host->core, nullptr, nullptr, &held)) return LUMINARY_ERROR_API_EXCEPTION;
+  if (shown_instances) *shown_instances = held;
+  if ((shown_transforms && held != instances) || (current_transforms && host->device_scene.view.num_instances != instances)) return LUMINARY_ERROR_INVALID_API_ARGUMENT;
+  if (lumc_download_history_transforms(host->core, shown_transforms, current_transforms, nullptr)) {
+    host->log.push_back(std::string("luminary_ext_get_history_transforms: ") + lumc_last_error(host->core));
+    return LUMINARY_ERROR_API_EXCEPTION;
   }
   return LUMINARY_SUCCESS;
 }
@@ -2313,8 +2429,11 @@ LuminaryResult luminary_ext_render_mattes(LuminaryHost* host, uint32_t samples, 
   // guide samples they are rendered on their own, so that the guides are what luminary_ext_set_denoiser asked for.
   const bool guides_due = host->denoiser.enabled && (!host->guides_valid || !lumc_has_guides(host->core));
   const bool shared = guides_due && (samples ? samples : 4u) == host->denoiser.guide_samples;
-  if (lumc_render_first_hits(host->core, samples, LUMC_FIRST_HIT_MATTES | (shared ? LUMC_FIRST_HIT_GUIDES : 0), layers, nullptr) ||
-      (guides_due && !shared && lumc_render_guides(host->core, host->denoiser.guide_samples, nullptr))) {
+  LumHistoryMotionParams mp;  // (the guides of an accumulation come with the owner plane while the history's motion is on: render_guides)
+  mp.enabled = history_motion_on(host) ? 1u : 0u; mp.motion_max_history = host->history_motion.motion_max_history;
+  const uint32_t with_guides = shared ? (uint32_t) LUMC_FIRST_HIT_GUIDES | (mp.enabled ? (uint32_t) LUMC_FIRST_HIT_OWNER : 0u) : 0u;
+  if ((shared && lumc_set_history_motion(host->core, &mp)) || lumc_render_first_hits(host->core, samples, LUMC_FIRST_HIT_MATTES | with_guides, layers, nullptr) ||
+      (guides_due && !shared && render_guides(host))) {
     std::fprintf(stderr, "[luminary_amd] %s\n", lumc_last_error(host->core));
     return LUMINARY_ERROR_CUDA;
   }
@@ -2369,7 +2488,7 @@ LuminaryResult luminary_ext_get_first_hit_guides(LuminaryHost* host, float* albe
   const LumDeviceSceneView& v = host->device_scene.view;
   if (width != v.width || height != v.height) return LUMINARY_ERROR_INVALID_API_ARGUMENT;
   if (!host->guides_valid || !lumc_has_guides(host->core)) {  // as the denoiser makes them (denoise_result)
-    if (lumc_render_guides(host->core, host->denoiser.guide_samples, nullptr)) { std::fprintf(stderr, "[luminary_amd] %s\n", lumc_last_error(host->core)); return LUMINARY_ERROR_CUDA; }
+    if (render_guides(host)) { std::fprintf(stderr, "[luminary_amd] %s\n", lumc_last_error(host->core)); return LUMINARY_ERROR_CUDA; }
     host->guides_valid = true;
   }
   if (lumc_download_guides(host->core, albedo, normal, depth)) return LUMINARY_ERROR_CUDA;

@@ -174,7 +174,7 @@ struct LumContext {
   bool guides_valid = false;
   Mattes mattes;  // ID mattes of the same first-hit passes (lumc_render_first_hits; matte.hip): nothing is allocated until they are asked for
   // the scene, the lens or the camera changed: both were rendered from what was. `why` is what a refused matte download names.
-  void drop_first_hit_products(const char* why) { guides_valid = false; if (mattes.valid) { mattes.valid = false; mattes.stale = why; } }
+  void drop_first_hit_products(const char* why) { guides_valid = false; history.motion.owner_cur_valid = false; history.motion.state_current = false; if (mattes.valid) { mattes.valid = false; mattes.stale = why; } }
   DeviceBuffer<float4> d_denoise_rec[3];  // one 16-byte record per pixel each
   History history;  // the shown frame carried across camera moves (lumc_set_history; history.hip): nothing is allocated until it is switched on and blends
   int denoise_lds = 1;              // a-trous steps 1 and 2 stage their tile in LDS (lumc_set_denoise_form; LUM_DENOISE_LDS=0|1)
@@ -286,6 +286,8 @@ int sort_closest_rays(LumContext* ctx, hipStream_t stream, PathQueue& queue, uin
 void free_sort(LumContext* ctx);  // the buffers of every mode; the settings and the scene's bounds stay
 void free_exchange(LumContext* ctx);  // multi_gpu.hip
 int scene_device_init();  // scene_device.hip: that unit's copy of the sampler's seed table, per device (a hipError_t; lumc_context_create)
+int history_owner_begin(LumContext* ctx, const char* fn, uint32_t n, hipStream_t stream);  // history.hip: the current owner plane, preset to "no path", for a guide render with LUMC_FIRST_HIT_OWNER
+int history_owner_pass(LumContext* ctx, const uint4* d_hit_id, const uint32_t* d_paths, uint32_t width, uint32_t n, hipStream_t stream);  // k_history_owner on a pass's first hits
 extern "C" uint64_t pixel_list_hash(const uint32_t* pixels, uint32_t n);  // core.hip, among the entry points that use it
 
 #pragma GCC visibility pop

@@ -1084,8 +1084,9 @@ static int render_first_hits(LumContext* ctx, const char* fn, uint32_t num_sampl
   if (!ctx->has_scene) { ctx->error = name + ": no scene"; return 1; }
   if (num_samples == 0) num_samples = 4;
   if (num_samples > 1024u) { ctx->error = name + ": at most 1024 guide samples"; return 1; }
-  const bool guides = (what & LUMC_FIRST_HIT_GUIDES) != 0, mattes = (what & LUMC_FIRST_HIT_MATTES) != 0;
-  if (!what || (what & ~(uint32_t) (LUMC_FIRST_HIT_GUIDES | LUMC_FIRST_HIT_MATTES))) { ctx->error = name + ": what is LUMC_FIRST_HIT_GUIDES | LUMC_FIRST_HIT_MATTES"; return 1; }
+  const bool guides = (what & LUMC_FIRST_HIT_GUIDES) != 0, mattes = (what & LUMC_FIRST_HIT_MATTES) != 0, owner = (what & LUMC_FIRST_HIT_OWNER) != 0;
+  if (!what || (what & ~(uint32_t) (LUMC_FIRST_HIT_GUIDES | LUMC_FIRST_HIT_MATTES | LUMC_FIRST_HIT_OWNER))) { ctx->error = name + ": what is LUMC_FIRST_HIT_GUIDES | LUMC_FIRST_HIT_MATTES | LUMC_FIRST_HIT_OWNER"; return 1; }
+  if (owner && !guides) { ctx->error = name + ": LUMC_FIRST_HIT_OWNER is the owner plane of a guide render: it goes with LUMC_FIRST_HIT_GUIDES"; return 1; }
   if (mattes && (!layers || (layers & ~(uint32_t) (LUMC_MATTE_INSTANCE | LUMC_MATTE_MATERIAL)))) { ctx->error = name + ": layers is LUMC_MATTE_INSTANCE | LUMC_MATTE_MATERIAL"; return 1; }
   HIP_TRY(ctx, hipSetDevice(ctx->device));
   DeviceScene sc = ctx->scene;
@@ -1094,10 +1095,12 @@ static int render_first_hits(LumContext* ctx, const char* fn, uint32_t num_sampl
   if (n == 0 || sc.width > 0xFFFFu || sc.height > 0xFFFFu) { ctx->error = name + ": frame size"; return 1; }
   if (guides) {
     ctx->guides_valid = false;
+    ctx->history.motion.owner_cur_valid = false;  // (the plane of an earlier guide render is not this one's)
     if (guide_pixels(ctx) != n) HIP_TRY(ctx, ctx->d_guides.resize(kGuideSumPlanes * (size_t) n));
   }
   if (ensure_work(ctx, n)) return 1;
   if (guides) HIP_TRY(ctx, hipMemsetAsync(ctx->d_guides.get(), 0, sizeof(float) * kGuideSumPlanes * (size_t) n, stream));
+  if (owner && history_owner_begin(ctx, fn, n, stream)) return 1;
   double t0 = 0.0;
   if (mattes) {
     if (begin_mattes(ctx, fn, n, layers, stream)) return 1;
@@ -1118,6 +1121,7 @@ static int render_first_hits(LumContext* ctx, const char* fn, uint32_t num_sampl
       Launch l(ctx, stream, LUMC_KERNEL_OUTPUT);
       wf.guide(grid_for(n), stream, sc, ctx->work.queue[0], (const uint32_t*) ctx->d_ctrl.get(), ctx->d_guides.get(), n);
     }
+    if (owner && s == 0 && history_owner_pass(ctx, ctx->work.queue[0].hit_id, ctx->d_ctrl.get() + kCtlPaths, sc.width, n, stream)) return 1;
     if (mattes) {
       Launch l(ctx, stream, LUMC_KERNEL_MATTE);
       const PathQueue& q = ctx->work.queue[0];
@@ -1136,6 +1140,7 @@ static int render_first_hits(LumContext* ctx, const char* fn, uint32_t num_sampl
     ctx->mattes.valid = true;
   }
   if (guides) ctx->guides_valid = true;
+  if (owner) ctx->history.motion.owner_cur_valid = true;
   return 0;
 }
 

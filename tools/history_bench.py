@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
 """Image history (lumc_history_carry / lumc_history_blend): what it costs and what it buys, measured on the GPU.
 
-  python tools/history_bench.py [--width 1920 --height 1080] [--repeats 20] [--skip-effect] [--out FILE.json]
+  python tools/history_bench.py [--width 1920 --height 1080] [--repeats 20] [--skip-effect] [--skip-motion] [--out FILE.json]
 
 The bench's hall in the library's default flavour.
   cost     with the core's profiling on, k_history_reproject (for a moved camera) and k_history_blend (without and with the clamp) by the history's own launch stamps, each against the bytes by shape: carry 28 B of guides + 32 B of state gathered + 16 B written per pixel, blend
            44 B read + 44 B written (the clamp adds a 24 B device copy of the image, stamped with the kernel). Beside them, in the same session: the denoiser's five
            iterations (the `output` stamps around lumc_denoise) and one sample id of the hall (host clock around lumc_render of one id, synchronised).
+  motion   the moving-instance case (lumc_set_history_motion): the scene's first instance moved by 0.3 along x between two shown frames; k_history_owner,
+           k_history_motion and k_history_reproject_motion by the history's launch stamps, with the records' classes and the pixels whose owner moved.
   effect   for three fixed camera moves and a table of settings: 64 ids, the move, then the shown image at 1, 4 and 16 ids with history against the plain mean of the
            same ids, both as relative L2 distance to 256 ids of the moved camera."""
 import argparse
@@ -99,6 +101,47 @@ def cost(host, base, a):
     return out
 
 
+def motion_cost(host, a):
+    from luminary_amd.core import FIRST_HIT_GUIDES, FIRST_HIT_OWNER, Core, history_params
+    core = Core(0)
+    out = {"instances": host.get_num_instances()}
+    inst = host.get_instance(0)
+    home = type(inst).from_buffer_copy(inst)
+    try:
+        def frame(ids):
+            core.upload(host.device_scene())
+            core.set_pixels(None)
+            core.render(0, ids, samples_per_pass=ids)
+            core.generate_result(uniform_samples=ids)
+            core.render_first_hits(4, FIRST_HIT_GUIDES | FIRST_HIT_OWNER, 0)
+        core.set_history(history_params())
+        core.set_history_motion(True, 8.0)
+        frame(8)
+        core.history_blend(8)
+        inst.position.x += 0.3
+        host.set_instance_transforms([inst])
+        frame(1)
+        core.set_profiling(True)
+        before = core.history_motion_stats()
+        for _ in range(a.repeats):
+            core.render_first_hits(4, FIRST_HIT_GUIDES | FIRST_HIT_OWNER, 0)
+            core.history_carry()
+        after = core.history_motion_stats()
+        for name in ("owner", "motion", "reproject"):
+            launches = getattr(after, name + "_launches") - getattr(before, name + "_launches")
+            out["k_history_" + name + ("_motion" if name == "reproject" else "")] = {"ms": (getattr(after, name + "_ms") - getattr(before, name + "_ms")) / max(launches, 1)}
+        st = core.history_stats()
+        out["records"] = {"moved": after.instances_moved, "same": after.instances_same, "void": after.instances_void}
+        out["pixels"] = {"carried": st.last_carried, "rejected": st.last_rejected, "off": st.last_off, "owner_moved": after.last_moved_pixels, "owner_moved_carried": after.last_moved_carried}
+        out["bytes"] = after.bytes
+    finally:
+        core.close()
+        host.set_instance_transforms([home])
+    for k, v in out.items():
+        print("motion", k, v)
+    return out
+
+
 def effect(host, base, a):
     w, h = a.width, a.height
 
@@ -145,6 +188,7 @@ def main():
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--repeats", type=int, default=20)
     ap.add_argument("--skip-effect", action="store_true")
+    ap.add_argument("--skip-motion", action="store_true")
     ap.add_argument("--out")
     a = ap.parse_args()
     import bench
@@ -153,6 +197,8 @@ def main():
     try:
         base = host.get_camera()
         result["cost"] = cost(host, base, a)
+        if not a.skip_motion:
+            result["motion"] = motion_cost(host, a)
         if not a.skip_effect:
             result["effect"] = effect(host, base, a)
     finally:
